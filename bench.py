@@ -35,6 +35,7 @@ HBM_PEAK_GBPS = 8000.0                    # MI355X_MICROARCH.md: HBM3E 8 TB/s
 N_SIMDS = 1024                            # 256 CUs x 4 SIMDs
 SHADER_CLOCK_HZ = 2.4e9                   # MI355X_MICROARCH.md: peak engine clock
 WALK_VALU_PER_TRIP = 14                   # k_count_band32, one annulus, two objects per lane: vector instructions per trip
+DUMP_LIMIT_BYTES = 64 * 10**6             # --dump-outputs: all files together
 
 
 def parse_args():
@@ -62,7 +63,36 @@ def parse_args():
                          "data objects and this many randoms, both binned in redshift, submitted as yaw.autocorrelate submits them "
                          "(one batch); --n-unk is ignored; one GPU")
     ap.add_argument("--no-probe", action="store_true", help="with --gpus > 1: skip the scaling probe (BASELINE config #5) beside the headline")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "in float64 (e.g. DIR = bench_outputs/<build>, which git ignores): per count (DD; DD, DR, RR with --auto-randoms) and scale s the pair counts "
+                         "<count>_s<s>_counts [z-bins, patches, patches] and the sums of weights <count>_sum_weights1/2 "
+                         f"[z-bins, patches]; at most {DUMP_LIMIT_BYTES // 10**6} MB in all (beyond that, every array keeps a "
+                         "fixed, seeded sample of its flattened elements)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, results):
+    """Write the result of the last timed step -- ``results`` = {count name: [NormalisedCounts per scale]} -- as float64
+    .npy files; inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    arrays = {}
+    for name, per_scale in results.items():
+        for s, nc in enumerate(per_scale):
+            arrays[f"{name}_s{s}_counts"] = np.asarray(nc.counts.counts, dtype=np.float64)
+        arrays[f"{name}_sum_weights1"] = np.asarray(per_scale[0].sum_weights.sum_weights1, dtype=np.float64)
+        arrays[f"{name}_sum_weights2"] = np.asarray(per_scale[0].sum_weights.sum_weights2, dtype=np.float64)
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # room for the .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for key, arr in arrays.items():
+        if total > budget:
+            keep = int(arr.size * (budget / total))
+            pick = np.sort(np.random.default_rng(0).choice(arr.size, keep, replace=False))
+            arr = arr.reshape(-1)[pick]
+        np.save(os.path.join(directory, f"{key}.npy"), arr)
 
 
 def traffic_key(args, kernel_name, band_variant=None):
@@ -372,12 +402,16 @@ def main_autocorrelation(args):
     per = {k: dict(count_ms=0.0, kernel_ms=0.0) for k in ("DD", "DR", "RR")}
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        links.count_pairs_batch(requests)
+        results = links.count_pairs_batch(requests)
+        if not args.dump_outputs:
+            del results  # a step's result is freed before the next step runs, unless it is to be written
         for k, st in links.last_batch_stats.items():
             per[k]["count_ms"] += st.count_ms
             per[k]["kernel_ms"] += st.kernel_ms
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {info: res for (_, info), res in zip(requests, results)})
     steps = max(args.steps, 1)
     stats = links.last_batch_stats
     cand = float(sum(st.candidate_pairs for st in stats.values()))
@@ -503,8 +537,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_result = []  # what the last step's count_pairs returned (--dump-outputs)
+
     def step():
-        links.count_pairs(ref, unk)
+        result = links.count_pairs(ref, unk)
+        if args.dump_outputs:
+            last_result[:] = result
         return links.last_stats
 
     # inputs must be resident in HBM before the timed region: upload (PCIe + device-side ordering) now
@@ -547,6 +585,8 @@ def main():
             copy_ms += links.last_rank_info["copy_back_ms"]
     barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"DD": last_result})
     multi = multi_gpu_record(dist, world, rank, device, links, first_info, count_ms_sum, reduce_ms, copy_ms, args.steps) if world > 1 else None
 
     # whole-job numbers: max time over ranks, sum of per-rank work

@@ -4,6 +4,8 @@ import json
 import os
 import types
 
+import numpy as np
+
 import bench
 from conftest import ROOT
 
@@ -53,3 +55,43 @@ def test_reference_timing_finds_the_committed_runs():
     assert bench.reference_timing(_args(weights=True))["seconds"] > 5       # round 3 returned nothing for --weights
     assert bench.reference_timing(_args(kpc=True)) is None                  # not what the reference was timed on
     assert bench.reference_timing(_args(n_ref=3e6)) is None
+
+
+def _normalised_counts(rng, num_scales, num_bins, num_patches):
+    from yet_another_wizz_amd.binning import Binning
+    from yet_another_wizz_amd.paircounts import NormalisedCounts, PatchedCounts, PatchedSumWeights
+
+    binning = Binning(np.linspace(0.1, 1.0, num_bins + 1))
+    sw = PatchedSumWeights(binning, rng.uniform(1, 2, (num_bins, num_patches)), rng.uniform(1, 2, (num_bins, num_patches)),
+                           auto=False)
+    return [NormalisedCounts(PatchedCounts(binning, rng.integers(0, 99, (num_bins, num_patches, num_patches)).astype(float),
+                                           auto=False), sw) for _ in range(num_scales)]
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: every array a caller of count_pairs receives, float64, one file each."""
+    rng = np.random.default_rng(5)
+    dd, dr = _normalised_counts(rng, 2, 3, 4), _normalised_counts(rng, 2, 3, 4)
+    bench.dump_outputs(str(tmp_path), {"DD": dd, "DR": dr})
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == sorted(f"{c}_{k}.npy" for c in ("DD", "DR") for k in ("s0_counts", "s1_counts", "sum_weights1", "sum_weights2"))
+    for c, res in (("DD", dd), ("DR", dr)):
+        for s in range(2):
+            got = np.load(tmp_path / f"{c}_s{s}_counts.npy")
+            assert got.dtype == np.float64 and np.array_equal(got, res[s].counts.counts)
+        assert np.array_equal(np.load(tmp_path / f"{c}_sum_weights1.npy"), res[0].sum_weights.sum_weights1)
+        assert np.array_equal(np.load(tmp_path / f"{c}_sum_weights2.npy"), res[0].sum_weights.sum_weights2)
+
+
+def test_dump_outputs_samples_large_results_within_the_limit(tmp_path, monkeypatch):
+    """Beyond the size limit every array keeps the same seeded sample of its elements, so runs stay comparable."""
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200_000)
+    res = _normalised_counts(np.random.default_rng(6), 3, 30, 40)  # 3 x 288 kB of counts
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), {"DD": res})
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 200_000
+    full = res[0].counts.counts.reshape(-1)
+    got = np.load(tmp_path / "a" / "DD_s0_counts.npy")
+    assert got.dtype == np.float64 and 0 < got.size < full.size and np.isin(got, full).all()
+    for p in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name)), p.name

@@ -86,23 +86,52 @@ def test_reference_cache_measurements_match_the_reference(monkeypatch):
     helpers.run_refcache_case()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference sources only exist in the build container")
-def test_reference_reads_our_cache(tmp_path):
-    """Other direction, build container only: the reference restores a cache written here."""
-    import subprocess
-    import sys
+def _read_cache_as_the_reference_does(directory):
+    """The reference's reader of a cache, restated from its format (catalog.py:325-331, patch.py:149-178,
+    datachunk.py:74-117) without this package: patch_ids.bin = int16 ids; patch_<id>/meta.yml = exactly the keys
+    Metadata.from_dict takes; patch_<id>/data.bin = one byte of column flags, then float64 records."""
+    import yaml
 
+    flag_bits = dict(ra=0, dec=1, weights=2, redshifts=3, patch_ids=4, kappa=5)
+    ids = np.fromfile(os.path.join(directory, "patch_ids.bin"), dtype=np.int16).tolist()
+    metas, records, columns = [], [], []
+    for pid in ids:
+        with open(os.path.join(directory, f"patch_{pid}", "meta.yml")) as f:
+            meta = yaml.safe_load(f)
+        assert set(meta) == {"num_records", "sum_weights", "center", "radius"}, meta
+        assert isinstance(meta["num_records"], int) and len(meta["center"]) == 2
+        metas.append(meta)
+        with open(os.path.join(directory, f"patch_{pid}", "data.bin"), "rb") as f:
+            state = f.read(1)[0]
+            raw = np.fromfile(f, dtype=np.byte)
+        names = [name for name, bit in flag_bits.items() if state & (1 << bit)]
+        assert state < (1 << len(flag_bits)) and names[:2] == ["ra", "dec"], state
+        assert raw.size % (8 * len(names)) == 0
+        records.append(raw.view([(name, "f8") for name in names]))
+        columns.append(names)
+    return ids, metas, records, columns
+
+
+def test_reference_reads_our_cache(tmp_path):
+    """Other direction: the reference restores a cache written here. tests/golden/ourcache_reference_readback.npz holds
+    what the reference read from a cache this package wrote from the same frame (tools/make_golden.py
+    --ourcache-readback); a fresh cache, parsed as the reference parses it, must give the same."""
     exp = load_golden("refcache_expect.npz")
+    got = load_golden("ourcache_reference_readback.npz")
     frame = dict(ra=exp["input.ra"], dec=exp["input.dec"], z=exp["input.z"], w=exp["input.w"])
     out = tmp_path / "mine"
     cat = yaw.Catalog.from_dataframe(out, frame, ra_name="ra", dec_name="dec", weight_name="w", redshift_name="z",
                                      patch_centers=yaw.AngularCoordinates(exp["patch_centers"]))
-    from conftest import ROOT
-
-    code = (
-        f"import sys; sys.path.insert(0, '{ROOT}/tools'); from ref_loader import load_reference; yaw = load_reference();"
-        f"c = yaw.Catalog('{out}'); print(c.get_num_records(), c.has_weights, c.has_redshifts, c.get_radii().data.tolist())"
-    )
-    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
-    assert str(cat.get_num_records()) in res.stdout and "True True" in res.stdout
+    ids, metas, records, columns = _read_cache_as_the_reference_does(out)
+    assert ids == list(range(4)) and bool(got["has_weights"]) and bool(got["has_redshifts"])
+    assert all(names == ["ra", "dec", "weights", "redshifts"] for names in columns)
+    assert [m["num_records"] for m in metas] == got["meta.num_records"].tolist() == list(cat.get_num_records())
+    assert [len(r) for r in records] == got["meta.num_records"].tolist()
+    np.testing.assert_allclose([m["center"] for m in metas], got["meta.centers"], rtol=0, atol=1e-14)
+    np.testing.assert_allclose([m["radius"] for m in metas], got["meta.radii"], rtol=1e-12)
+    np.testing.assert_allclose([m["sum_weights"] for m in metas], got["meta.sum_weights"], rtol=1e-13)
+    for pid, rec in enumerate(records):
+        # the records the reference returned, bit for bit (order inside a patch is not part of the format)
+        mine = np.column_stack([rec[name] for name in columns[pid]])
+        theirs = got[f"patch_{pid}.records"]
+        assert np.array_equal(mine[np.lexsort(mine.T)], theirs[np.lexsort(theirs.T)]), pid

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -49,3 +50,19 @@ def test_config4_mode_line():
     assert d["candidate_pairs_per_step"] == sum(c["candidate_pairs"] for c in counts.values())
     assert d["ms_per_step"] >= d["roofline"]["count_kernels_ms"]
     assert d["cpu_baseline"]["parity_with_gpu"] is True
+
+
+def test_dump_outputs_repeat_exactly(tmp_path):
+    """--dump-outputs writes the last timed step's result; the inputs are seeded, so a second run writes the same values."""
+    args = ("--n-ref", "3e5", "--n-unk", "3e5", "--patches", "16", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0")
+    runs = []
+    for name in ("a", "b"):
+        d = _bench(*args, "--dump-outputs", str(tmp_path / name))
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        runs.append(tmp_path / name)
+    names = sorted(p.name for p in runs[0].iterdir())
+    assert names == ["DD_s0_counts.npy", "DD_sum_weights1.npy", "DD_sum_weights2.npy"]
+    counts = np.load(runs[0] / "DD_s0_counts.npy")
+    assert counts.dtype == np.float64 and counts.shape == (30, 16, 16) and counts.sum() > 0
+    for n in names:
+        assert np.array_equal(np.load(runs[0] / n), np.load(runs[1] / n)), n

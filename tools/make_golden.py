@@ -13,6 +13,8 @@ Vector groups:
   G6  full_cross.npz / full_auto.npz   8-patch ``yaw.crosscorrelate`` (DD, DR, RD, RR) and
                         ``yaw.autocorrelate`` (DD, DR, RR) tensors + ``CorrFunc.sample()``
   G7  twodflens.npz     bundled 2dFLenS example catalogue (11 patches, weights) in arcmin units
+  G8  ourcache_reference_readback.npz   what the reference reads from a cache written by this package
+                        (--ourcache-readback regenerates only this group)
 
 Usage:  python tools/make_golden.py
 """
@@ -353,11 +355,36 @@ def make_refcache_counts(tmp):
     save("refcache_counts.npz", **out)
 
 
+def make_ourcache_readback(tmp):
+    """The other direction of the cache contract: a cache written by THIS package from the refcache_expect.npz frame,
+    restored by the reference, and what the reference read from it (per-patch metadata, column flags and records in the
+    order the reference returns them). tests/test_cache_format.py::test_reference_reads_our_cache holds a fresh cache
+    written here to these values without needing the reference."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import yet_another_wizz_amd as ours
+
+    exp = np.load(os.path.join(OUT, "refcache_expect.npz"))
+    frame = {c: exp[f"input.{c}"] for c in ("ra", "dec", "z", "w")}
+    path = os.path.join(tmp, "ourcache")
+    ours.Catalog.from_dataframe(path, frame, ra_name="ra", dec_name="dec", weight_name="w", redshift_name="z",
+                                patch_centers=ours.AngularCoordinates(exp["patch_centers"]))
+    cat = yaw.Catalog(path)
+    out = dict(has_weights=np.array(cat.has_weights), has_redshifts=np.array(cat.has_redshifts))
+    catalog_meta("meta", cat, out)
+    for i in range(cat.num_patches):
+        patch = cat[i]
+        out[f"patch_{i}.records"] = np.column_stack([patch.coords.ra, patch.coords.dec, patch.weights, patch.redshifts])
+    save("ourcache_reference_readback.npz", **out)
+
+
 def main():
     tmp = tempfile.mkdtemp(prefix="yawgolden_", dir="/dev/shm")
     try:
         if "--refcache-counts" in sys.argv:  # only this group (the others are already committed)
             make_refcache_counts(tmp)
+            return
+        if "--ourcache-readback" in sys.argv:
+            make_ourcache_readback(tmp)
             return
         make_refcache(tmp)
         make_greatcircle()
@@ -365,6 +392,7 @@ def main():
         make_full(tmp)
         make_2dflens(tmp)
         make_refcache_counts(tmp)
+        make_ourcache_readback(tmp)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
