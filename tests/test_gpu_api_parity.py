@@ -214,6 +214,11 @@ def test_remembered_plans_follow_their_inputs():
     assert st.band_variant == 64 and np.array_equal(c, truth["t1"])
     d, st = engine.count_fine(l1, l2, jobs, t1)
     assert st.band_variant == 32 and np.array_equal(d, truth["t1"])
+    # a refused option changes nothing: the option set and the plans stay as they were
+    with pytest.raises(_lib.YawhipError):
+        ctx.set_option("tile_r", 3)
+    d, st = engine.count_fine(l1, l2, jobs, t1)
+    assert st.band_variant == 32 and np.array_equal(d, truth["t1"])
     # a catalogue that is freed and uploaded again (possibly at the same address) gets new plans
     for _ in range(3):
         for lay in (l1, l2):

@@ -51,6 +51,7 @@
 #include <new>
 #include <string>
 #include <system_error>
+#include <type_traits>
 #include <utility>
 #include <functional>
 #include <vector>
@@ -1140,23 +1141,24 @@ __device__ __forceinline__ void count_merged_body(const DevTab *__restrict__ tab
 // The kernel proper. With one or two objects per lane the body fits 64 VGPRs without spilling, so the compiler is
 // told to keep 8 waves per SIMD (80 VGPRs / 6 waves otherwise: -9 % time at the headline); with four objects per
 // lane that limit would spill, the default allocation stays.
-#define YAW_COUNT_MERGED_ARGS                                                                                         \
-    const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,                                      \
-        int n_edges, const double *__restrict__ t, const float *__restrict__ dthr, const double *__restrict__ rwin_k, \
-        int64_t item_base, unsigned long long *__restrict__ out_counts, double *__restrict__ partials,                \
-        const unsigned long long *__restrict__ counters
-#define YAW_COUNT_MERGED_PASS tabs, items, n_bins, n_edges, t, dthr, rwin_k, item_base, out_counts, partials, counters
 template <int R, bool WEIGHTED, bool NF1, bool MERGED>
-__global__ __launch_bounds__(MWG) void k_count_merged(YAW_COUNT_MERGED_ARGS) {
-    count_merged_body<R, WEIGHTED, NF1, MERGED>(YAW_COUNT_MERGED_PASS);
+__global__ __launch_bounds__(MWG) void k_count_merged(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
+                                                      int n_edges, const double *__restrict__ t, const float *__restrict__ dthr,
+                                                      const double *__restrict__ rwin_k, int64_t item_base,
+                                                      unsigned long long *__restrict__ out_counts, double *__restrict__ partials,
+                                                      const unsigned long long *__restrict__ counters) {
+    count_merged_body<R, WEIGHTED, NF1, MERGED>(tabs, items, n_bins, n_edges, t, dthr, rwin_k, item_base, out_counts, partials, counters);
 }
 template <int R, bool WEIGHTED, bool NF1, bool MERGED>
-__global__ __launch_bounds__(MWG) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_count_merged_occ8(YAW_COUNT_MERGED_ARGS) {
-    count_merged_body<R, WEIGHTED, NF1, MERGED>(YAW_COUNT_MERGED_PASS);
+__global__ __launch_bounds__(MWG) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_count_merged_occ8(
+    const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins, int n_edges, const double *__restrict__ t,
+    const float *__restrict__ dthr, const double *__restrict__ rwin_k, int64_t item_base, unsigned long long *__restrict__ out_counts,
+    double *__restrict__ partials, const unsigned long long *__restrict__ counters) {
+    count_merged_body<R, WEIGHTED, NF1, MERGED>(tabs, items, n_bins, n_edges, t, dthr, rwin_k, item_base, out_counts, partials, counters);
 }
 
 template <int R, bool WEIGHTED, bool NF1, bool MERGED>
-auto pick_count_merged() -> void (*)(YAW_COUNT_MERGED_ARGS) {
+auto pick_count_merged() -> decltype(&k_count_merged<R, WEIGHTED, NF1, MERGED>) {
     if constexpr (R <= 2) return k_count_merged_occ8<R, WEIGHTED, NF1, MERGED>;
     else return k_count_merged<R, WEIGHTED, NF1, MERGED>;
 }
@@ -2273,7 +2275,44 @@ constexpr size_t MAX_PLANS = 16;  // plans kept per context (least recently used
 
 namespace {
 struct HostPlan;  // what a call derives from its inputs on the host, kept for the next call with the same inputs (below)
-}
+
+// Everything a plan depends on: the catalogue pair (by upload id), the option set, sizes, kernel, the outputs asked for, job
+// list and thresholds (compared exactly) -- and, for the job partition of a multi-device call, the device count. A key made
+// from a call's arguments borrows their job list and thresholds; keep() gives it copies of its own before it is stored.
+struct CallKey {
+    uint64_t c1_uid = 0, c2_uid = 0, opt_gen = 0, hash = 0;
+    int32_t n_jobs = 0, n_bins = 0, n_edges = 0, kernel = 0, n_dev = 0;
+    bool want_counts = false, want_sums = false, for_work = false;
+    const int32_t *jobs = nullptr;
+    const double *t = nullptr;
+    std::vector<int32_t> own_jobs;
+    std::vector<double> own_t;
+
+    CallKey() = default;
+    CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
+            int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
+            int32_t n_dev = 0);  // (below yawhip_catalog)
+    // (moves keep jobs / t valid: a vector's elements stay where they are; copies would not)
+    CallKey(CallKey &&) = default;
+    CallKey &operator=(CallKey &&) = default;
+    CallKey(const CallKey &) = delete;
+    CallKey &operator=(const CallKey &) = delete;
+
+    void keep() {
+        own_jobs.assign(jobs, jobs + 2 * (size_t)n_jobs);
+        own_t.assign(t, t + (size_t)n_bins * n_edges);
+        jobs = own_jobs.data();
+        t = own_t.data();
+    }
+    bool operator==(const CallKey &o) const {
+        return hash == o.hash && c1_uid == o.c1_uid && c2_uid == o.c2_uid && opt_gen == o.opt_gen && n_jobs == o.n_jobs &&
+               n_bins == o.n_bins && n_edges == o.n_edges && kernel == o.kernel && n_dev == o.n_dev && want_counts == o.want_counts &&
+               want_sums == o.want_sums && for_work == o.for_work &&
+               memcmp(jobs, o.jobs, sizeof(int32_t) * 2 * (size_t)n_jobs) == 0 &&
+               memcmp(t, o.t, sizeof(double) * (size_t)n_bins * n_edges) == 0;
+    }
+};
+}  // namespace
 
 struct yawhip_ctx : CallBufs {
     int device = 0;
@@ -2307,13 +2346,13 @@ struct yawhip_ctx : CallBufs {
     // replicated on all of them and yawhip_count_pairs splits its job list over them.
     std::vector<yawhip_ctx *> peers;
     struct Plan {  // job partition of the last multi-device call (a function of its inputs only)
-        uint64_t key = 0;
+        CallKey key;
         std::vector<std::vector<int32_t>> parts;  // job indices per device
     } plan;
     yawsort::Workspace sort_ws;  // upload-side sorts
     CallBufs parked[MAX_BATCH];  // the slots that are not active (the active one's entry is empty)
     int slot = 0;
-    uint64_t opt_gen = 1;        // bumped by every yawhip_ctx_set_option: plans are keyed on it
+    uint64_t opt_gen = 1;        // bumped by every accepted yawhip_ctx_set_option: plans and the partition are keyed on it
     uint64_t plan_clock = 0;     // least-recently-used stamp of the plans
     std::vector<HostPlan *> plans;
 };
@@ -2403,46 +2442,37 @@ CatView view_of(const yawhip_catalog *c) {
     return CatView{c->x, c->y, c->z, c->w, c->off, c->nb, key_of(c->x, c->y, c->z, c->axis), c->axis};
 }
 
-template <int R, bool W, bool P, bool F>
-hipError_t launch_count(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int n_slots, int n_bins,
-                        int n_edges, int64_t n_items, size_t lds_bytes) {
-    auto kern = k_count<R, W, P, F>;
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+// One launch of a count kernel: its dynamic-LDS limit raised first where it needs more than 64 KiB.
+template <typename... Params, typename... Args>
+hipError_t launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    const int64_t max_grid = (1ll << 31) / WG;  // a launch addresses at most 2^32 - 1 work-items per dimension
-    for (int64_t base = 0; base < n_items; base += max_grid) {
-        const int64_t g = std::min(max_grid, n_items - base);
-        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(WG), lds_bytes, ctx->stream, view_of(c1), view_of(c2),
-                           ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, base, ctx->d_counts.ptr,
-                           ctx->d_partials.ptr, ctx->d_ctr.ptr);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
 }
 
-template <bool W, bool P, bool F>
-hipError_t launch_count_r(int r, yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int n_slots,
-                          int n_bins, int n_edges, int64_t n_items, size_t lds) {
-    switch (r) {
-        case 1: return launch_count<1, W, P, F>(ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds);
-        case 2: return launch_count<2, W, P, F>(ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds);
-        default: return launch_count<4, W, P, F>(ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds);
-    }
+// Kernel variant dispatch: f(T{}) for the T among Ts whose ::value equals v. The variants named at the call sites are the
+// ones compiled, and make_plan plans only those: a value that names none is an error, not a fall-back.
+template <typename... Ts, typename V, typename F>
+hipError_t pick(const V &v, F &&f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)(((v == Ts::value) && (e = f(Ts{}), true)) || ...);
+    return e;
 }
-
-template <bool W>
-hipError_t launch_count_any(bool priv, bool filter, int r, yawhip_ctx *ctx, const yawhip_catalog *c1,
-                            const yawhip_catalog *c2, int n_slots, int n_bins, int n_edges, int64_t n_items, size_t lds) {
-    if (priv)
-        return filter ? launch_count_r<W, true, true>(r, ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds)
-                      : launch_count_r<W, true, false>(r, ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds);
-    return filter ? launch_count_r<W, false, true>(r, ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds)
-                  : launch_count_r<W, false, false>(r, ctx, c1, c2, n_slots, n_bins, n_edges, n_items, lds);
-}
+template <bool B> using Bool = std::integral_constant<bool, B>;
+template <int I> using Int = std::integral_constant<int, I>;
+// (objects per lane, entries per LDS stage) of a band kernel
+template <int R_, int CAP_> struct Stage {
+    static constexpr int R = R_, CAP = CAP_;
+    static constexpr std::pair<int, int> value{R_, CAP_};
+};
+// (MERGED, UNI) of a band kernel: one item for all bins; one threshold row for all of an item's bins
+template <bool MERGED_, bool UNI_> struct Rows {
+    static constexpr bool MERGED = MERGED_, UNI = UNI_;
+    static constexpr std::pair<bool, bool> value{MERGED_, UNI_};
+};
 
 // Nearest patch centre of every object (replaces scipy.cluster.vq.vq in assign_patch_centers, catalog.py:229-249):
 // squared distance accumulated x, y, z in that order with separately rounded products and sums, first minimum
@@ -2918,102 +2948,73 @@ int yawhip_ctx_destroy(yawhip_ctx *ctx) {
 
 int yawhip_ctx_set_option(yawhip_ctx *ctx, const char *key, int64_t value) {
     if (!ctx || !key) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_set_option: NULL argument");
-    for (yawhip_ctx *peer : ctx->peers) {  // every device of a multi-device context follows
-        const int rc = yawhip_ctx_set_option(peer, key, value);
-        if (rc != YAWHIP_OK) return rc;
-    }
-    ctx->plan.key = 0;  // options change the work per job
-    ++ctx->opt_gen;     // ... and every decision of a plan
-    drop_plans(ctx, nullptr);
+    // The option is checked before anything changes: a refused key or value leaves plans, option set and devices as they were.
+    std::function<void(yawhip_ctx &)> set;
+    auto flag = [&](int yawhip_ctx::*field) { set = [=](yawhip_ctx &c) { c.*field = value != 0; }; };
+    auto number = [&](int yawhip_ctx::*field) { set = [=](yawhip_ctx &c) { c.*field = (int)value; }; };
     if (!strcmp(key, "half_bands")) {
-        ctx->half_bands = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "tile_r")) {
+        flag(&yawhip_ctx::half_bands);
+    } else if (!strcmp(key, "tile_r")) {
         if (value != 0 && value != 1 && value != 2 && value != 4)
             return fail(YAWHIP_ERR_INVALID, "tile_r must be 0 (auto), 1, 2 or 4");
-        ctx->tile_r = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "band_batch_log2")) {
+        number(&yawhip_ctx::tile_r);
+    } else if (!strcmp(key, "band_batch_log2")) {
         if (value < -1 || value > 6) return fail(YAWHIP_ERR_INVALID, "band_batch_log2 must be -1 (auto) or 0..6");
-        ctx->band_batch_log2 = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "hist_copies_log2")) {
+        number(&yawhip_ctx::band_batch_log2);
+    } else if (!strcmp(key, "hist_copies_log2")) {
         if (value < -1 || value > 6) return fail(YAWHIP_ERR_INVALID, "hist_copies_log2 must be -1 (auto) or 0..6");
-        ctx->hist_copies_log2 = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "triple_runs")) {  // 0: never, 1: where the merged window fits the stage, 2: wherever the partner strips are c - 1, c, c + 1
+        number(&yawhip_ctx::hist_copies_log2);
+    } else if (!strcmp(key, "triple_runs")) {  // 0: never, 1: where the merged window fits the stage, 2: wherever the partner strips are c - 1, c, c + 1
         if (value < 0 || value > 2) return fail(YAWHIP_ERR_INVALID, "triple_runs must be 0, 1 or 2");
-        ctx->triple_runs = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "item_segments")) {
-        ctx->item_segments = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "spin_wait")) {
-        ctx->spin_wait = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "band_cap")) {
+        number(&yawhip_ctx::triple_runs);
+    } else if (!strcmp(key, "item_segments")) {
+        flag(&yawhip_ctx::item_segments);
+    } else if (!strcmp(key, "spin_wait")) {
+        flag(&yawhip_ctx::spin_wait);
+    } else if (!strcmp(key, "band_cap")) {
         if (value != 0 && value != BCAP && value != BCAP_MID && value != B32_CAP && value != B32_CAP_BIG)
             return fail(YAWHIP_ERR_INVALID, "band_cap must be 0 (auto), 192 or 288 (float64 / fine-grid band kernels), %d or %d (float32 band kernel)",
                         B32_CAP, B32_CAP_BIG);
-        ctx->band_cap = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "strip_width_micro")) {  // strip grid spacing in units of 1e-6 (0 = off)
+        number(&yawhip_ctx::band_cap);
+    } else if (!strcmp(key, "strip_width_micro")) {  // strip grid spacing in units of 1e-6 (0 = off)
         if (value != 0 && (value < 1000 || value > 2000000))
             return fail(YAWHIP_ERR_INVALID, "strip_width_micro must be 0 (off) or in [1e3, 2e6]");
-        ctx->strip_width = (double)value * 1e-6;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "seg_strips_min_run")) {
+        set = [=](yawhip_ctx &c) { c.strip_width = (double)value * 1e-6; };
+    } else if (!strcmp(key, "seg_strips_min_run")) {
         if (value < 1) return fail(YAWHIP_ERR_INVALID, "seg_strips_min_run must be >= 1");
-        ctx->seg_min_run = (int)std::min<int64_t>(value, INT32_MAX);
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "seg_strips")) {
-        ctx->seg_strips = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "debug_no_hits")) {
-        ctx->debug_no_hits = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "auto_orient")) {
-        ctx->auto_orient = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "slab_budget_bytes")) {
+        set = [=](yawhip_ctx &c) { c.seg_min_run = (int)std::min<int64_t>(value, INT32_MAX); };
+    } else if (!strcmp(key, "seg_strips")) {
+        flag(&yawhip_ctx::seg_strips);
+    } else if (!strcmp(key, "debug_no_hits")) {
+        flag(&yawhip_ctx::debug_no_hits);
+    } else if (!strcmp(key, "auto_orient")) {
+        flag(&yawhip_ctx::auto_orient);
+    } else if (!strcmp(key, "slab_budget_bytes")) {
         if (value < 4096) return fail(YAWHIP_ERR_INVALID, "slab_budget_bytes must be >= 4096");
-        ctx->slab_budget = value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "band_grid_div")) {
+        set = [=](yawhip_ctx &c) { c.slab_budget = value; };
+    } else if (!strcmp(key, "band_grid_div")) {
         if (value < 0 || value > 64) return fail(YAWHIP_ERR_INVALID, "band_grid_div must be 0 (auto) or in [1, 64]");
-        ctx->band_grid_div = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "flush_stages_log2")) {
+        number(&yawhip_ctx::band_grid_div);
+    } else if (!strcmp(key, "flush_stages_log2")) {
         if (value < 0 || value > 17) return fail(YAWHIP_ERR_INVALID, "flush_stages_log2 must be in [0, 17]");
-        ctx->flush_log2 = (int)value;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "band_fp32")) {
-        ctx->band_fp32 = value != 0;
-        return YAWHIP_OK;
-    }
-    if (!strcmp(key, "kernel")) {
+        number(&yawhip_ctx::flush_log2);
+    } else if (!strcmp(key, "band_fp32")) {
+        flag(&yawhip_ctx::band_fp32);
+    } else if (!strcmp(key, "kernel")) {
         if (value < YAWHIP_KERNEL_AUTO || value > YAWHIP_KERNEL_BAND)
             return fail(YAWHIP_ERR_INVALID, "unknown kernel id %lld", (long long)value);
-        ctx->default_kernel = (int)value;
-        return YAWHIP_OK;
+        number(&yawhip_ctx::default_kernel);
+    } else {
+        return fail(YAWHIP_ERR_INVALID, "unknown option '%s'", key);
     }
-    return fail(YAWHIP_ERR_INVALID, "unknown option '%s'", key);
+    std::vector<yawhip_ctx *> devices(ctx->peers);  // every device of a multi-device context follows
+    devices.push_back(ctx);
+    for (yawhip_ctx *c : devices) {
+        ++c->opt_gen;  // options change every decision of a plan and the work per job
+        drop_plans(c, nullptr);
+        set(*c);
+    }
+    return YAWHIP_OK;
 }
 
 int yawhip_catalog_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
@@ -3151,7 +3152,6 @@ int yawhip_catalog_free(yawhip_catalog *c) {
     if (!c) return YAWHIP_OK;
     for (yawhip_catalog *rep : c->replicas) (void)yawhip_catalog_free(rep);
     c->replicas.clear();
-    if (c->ctx) c->ctx->plan.key = 0;  // a later catalogue may reuse the address the plan was keyed on
     if (c->ctx) (void)hipSetDevice(c->ctx->device);
     if (c->ctx) {  // its plans hold pointers into its layouts (nothing of them is in flight: calls are blocking)
         if (c->ctx->stream) (void)hipStreamSynchronize(c->ctx->stream);
@@ -3268,27 +3268,45 @@ std::vector<float> build_fine32(const double *t, int n_bins, int n_edges) {
     return out;
 }
 
+CallKey::CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs_, const int32_t *jobs_,
+                 int32_t n_bins_, int32_t n_edges_, const double *t_, int32_t kernel_, bool want_counts_, bool want_sums_,
+                 bool for_work_, int32_t n_dev_)
+    : c1_uid(c1->uid), c2_uid(c2->uid), opt_gen(ctx->opt_gen), n_jobs(n_jobs_), n_bins(n_bins_), n_edges(n_edges_),
+      kernel(kernel_), n_dev(n_dev_), want_counts(want_counts_), want_sums(want_sums_), for_work(for_work_), jobs(jobs_), t(t_) {
+    // word by word: a job is one 64-bit word, a threshold another
+    auto mix = [this](uint64_t w) { hash = (hash ^ w) * 0x100000001b3ull; hash ^= hash >> 29; };
+    for (uint64_t w : {c1_uid, c2_uid, opt_gen, (uint64_t)(uint32_t)n_jobs << 32 | (uint32_t)n_bins,
+                       (uint64_t)(uint32_t)n_edges << 32 | (uint32_t)kernel,
+                       (uint64_t)(uint32_t)n_dev << 32 | (uint64_t)(want_counts | want_sums << 1 | for_work << 2)})
+        mix(w);
+    for (size_t j = 0; j < (size_t)n_jobs; ++j) {
+        uint64_t w;
+        memcpy(&w, jobs + 2 * j, sizeof w);
+        mix(w);
+    }
+    for (size_t i = 0; i < (size_t)n_bins * n_edges; ++i) {
+        uint64_t w;
+        memcpy(&w, t + i, sizeof w);
+        mix(w);
+    }
+}
+
 // What a count call derives from its inputs on the HOST before anything is launched -- kernel choice, layouts, tile and stage
 // sizes, the job records / prefix / threshold tables of the item builder and the count kernel (uploaded once, into the plan's
-// own device buffer) -- kept for the next call with the same inputs: the same catalogue pair (by upload id), job list,
-// thresholds (both compared byte for byte), kernel, outputs asked for and option set. A repeated call (the next step of a
-// bench, the same count of the next measurement, DR after DD with the same job list is ANOTHER plan) then marshals no
-// tables at all; the item builder and the count kernels run every call. Plans die with their catalogues and options.
+// own device buffer) -- kept for the next call with the same inputs (CallKey). A repeated call (the next step of a bench, the
+// same count of the next measurement, DR after DD with the same job list is ANOTHER plan) then marshals no tables at all; the
+// item builder and the count kernels run every call. Plans die with their catalogues and options.
 struct HostPlan {
-    // identity
-    uint64_t hash = 0, stamp = 0, c1_uid = 0, c2_uid = 0, opt_gen = 0;
-    int32_t n_jobs_in = 0, n_bins_in = 0, n_edges_in = 0, kernel_in = 0;
-    bool want_counts = false, want_sums = false, for_work = false;
-    std::vector<int32_t> jobs_in;
-    std::vector<double> t_in;
+    CallKey key;
+    uint64_t stamp = 0;
     // decisions
     bool empty = false;   // nothing to count (no output values)
     bool split = false;   // the job list has to be counted in pieces (SPLIT_JOBS)
     int grid_div = 8;  // band kernels: workgroups = potential items / this
     int R = 0, band_ne = 0, cap = 0, hp_shift = 0, lean_bins = 0, mode = 0, reach = 0, kernel = 0, nf = 0, n_orient = 0;
     bool band = false, band32 = false, band_fine = false, filter = false, lean = false, merged = false, run_unweighted = false,
-         run_weighted = false, strip_items = false, swap = false, sweep = false, triple = false, uniform_t = false, weighted = false,
-         weighted_any = false;
+         run_weighted = false, strip_items = false, swap = false, sweep = false, triple = false, uni = false, uniform_t = false,
+         weighted = false, weighted_any = false;
     int64_t abytes = 0, cand = 0, n_items = 0, n_out = 0, n_pslots = 0, n_sjobs = 0, n_slots = 0, slab = 0, tile = 0;
     double rwin_max = 0.0;
     size_t lds_band = 0, lds_merged = 0;
@@ -3303,7 +3321,7 @@ struct HostPlan {
 // Forget the plans that involve catalogue `c` (nullptr: all of them).
 void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c) {
     for (size_t i = 0; i < ctx->plans.size();) {
-        if (!c || ctx->plans[i]->c1_uid == c->uid || ctx->plans[i]->c2_uid == c->uid) {
+        if (!c || ctx->plans[i]->key.c1_uid == c->uid || ctx->plans[i]->key.c2_uid == c->uid) {
             delete ctx->plans[i];
             ctx->plans[i] = ctx->plans.back();
             ctx->plans.pop_back();
@@ -3311,17 +3329,24 @@ void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c) {
     }
 }
 
-// The host half of a count call: validation, every decision, the tables -- into a plan (see HostPlan).
-int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-              int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
-              HostPlan &P) {
-    const void *job_work = for_work ? static_cast<const void *>(&P) : nullptr;  // (only its truth value matters below)
-    if (c1->ctx != ctx || c2->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (c1->n_patches != c2->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", c1->n_patches, c2->n_patches);
+// The handle and size checks of a count call, made by every entry point before any device work.
+int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
+               int32_t n_bins, int32_t n_edges, const double *t) {
+    if (!ctx || !c1 || !c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: NULL handle");
     if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && !jobs))
         return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: bad sizes (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
                     n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (c1->ctx != ctx || c2->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (c1->n_patches != c2->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", c1->n_patches, c2->n_patches);
+    return YAWHIP_OK;
+}
+
+// The host half of a count call (its arguments passed check_call): every decision, the tables -- into a plan (see HostPlan).
+// for_work: the plan of a cost estimate (count_enqueue's job_work).
+int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
+              int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
+              HostPlan &P) {
     if ((c1->nb != 1 && c1->nb != n_bins) || (c2->nb != 1 && c2->nb != n_bins))
         return fail(YAWHIP_ERR_MISMATCH, "catalogue bin counts (%d, %d) do not fit n_bins=%d", c1->nb, c2->nb, n_bins);
     for (int k = 0; k < n_bins; ++k)
@@ -3544,7 +3569,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // stage capacity of the band kernel: the smallest compiled one that holds a whole window (see BCAP_MID)
     int cap = ctx->band_cap == BCAP || ctx->band_cap == BCAP_MID ? ctx->band_cap : 0;
     if (band && cap == 0) cap = R >= 4 || est_window > 0.95 * BCAP ? BCAP_MID : BCAP;
-    if (band) {  // combinations that are compiled
+    if (band) {  // (R, stage) pairs that are compiled (the Stage lists of count_enqueue): the plan names one of them
         if (R == 1) cap = BCAP;
         if (R == 4 && cap == BCAP) cap = BCAP_MID;
     }
@@ -3552,7 +3577,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
                                                                          : (est_window > 0.75 * (B32_CAP - 4) ? B32_CAP_BIG : B32_CAP);
     // (0.75: window lengths scatter around the estimate, and a window cut in two costs more than a larger stage -- 50M x 50M
     // with windows of ~265 entries: 21.0 ms in the 320-entry stage, 18.3 ms in a 448-entry one)
-    if (R == 1) cap32 = B32_CAP;      // combinations that are compiled
+    if (R == 1) cap32 = B32_CAP;  // (compiled pairs, as above)
     if (R >= 4) cap32 = B32_CAP_BIG;
     if (band32) cap = cap32;  // (the fine-grid kernel still stages window by window, with the capacities of k_count_band)
     const int64_t tile = (int64_t)(lean ? MWG : WG) * R;
@@ -3607,7 +3632,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // in its window, b as lane object with a in its. On merged triple runs with one object per lane the lane walks only the
     // entries BEHIND its own place in the triple of its strip (one total order of objects in all triples, k_merge_triples): every
     // pair is met once and counts twice (an exact doubling, also of weighted sums). Half the walk of DD / RR of an autocorrelation.
-    const bool half_ok = band32 && triple && R == 1 && c1 == c2 && !swap && ctx->half_bands != 0 && !job_work;
+    const bool half_ok = band32 && triple && R == 1 && c1 == c2 && !swap && ctx->half_bands != 0 && !for_work;
     if (strip_items) {
         const double width = c1->strip_width;
         // |dv| <= rwin_max  ->  grid indices differ by at most floor(rwin_max / width) + 1
@@ -3695,7 +3720,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // A weighted call keeps one slab of partial sums per potential item; long job lists of big catalogues would need
     // tens of GB (50M x 50M, three scales: 40 GB). Above the budget -- and when the items no longer fit 31 bits -- the
     // caller cuts the job list in two and counts the halves one after the other (rows of the result are independent).
-    if (n_jobs > 1 && !job_work &&
+    if (n_jobs > 1 && !for_work &&
         ((run_weighted && n_items * slab * (int64_t)sizeof(double) > ctx->slab_budget) || n_items >= (1ll << 31)))
         { P.split = true; return YAWHIP_OK; }
     // layout table of the call: [o] = c1, [3 + o] = c2 for orientation o (plain layouts: entries 0 and 3)
@@ -3816,6 +3841,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     P.tile = tile;
     P.triple = triple;
     P.uniform_t = uniform_t;
+    P.uni = merged || band_fine ? uniform_t : true;  // UNI of the band kernels (per-bin items of the others: one threshold row)
     P.weighted = weighted;
     P.weighted_any = weighted_any;
     P.kernel = kernel;
@@ -3835,30 +3861,11 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     g_trace.mark("enqueue");
     cs.want_counts = want_counts;
     cs.want_sums = want_sums;
-    if (!ctx || !c1 || !c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: NULL handle");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && !jobs))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: bad sizes (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
-                    n_jobs, n_bins, n_edges, MAX_EDGES);
     HIP_TRY(hipSetDevice(ctx->device));
-    // the plan of these inputs: FNV-1a over everything it depends on, then an exact comparison of job list and thresholds
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *ptr, size_t n) {
-        const unsigned char *bytes = static_cast<const unsigned char *>(ptr);
-        for (size_t i = 0; i < n; ++i) { h ^= bytes[i]; h *= 1099511628211ull; }
-    };
-    const int32_t head_key[6] = {n_jobs, n_bins, n_edges, kernel, (want_counts ? 1 : 0) | (want_sums ? 2 : 0), job_work ? 1 : 0};
-    mix(head_key, sizeof head_key);
-    mix(&c1->uid, sizeof c1->uid); mix(&c2->uid, sizeof c2->uid); mix(&ctx->opt_gen, sizeof ctx->opt_gen);
-    mix(jobs, sizeof(int32_t) * 2 * (size_t)n_jobs);
-    mix(t, sizeof(double) * (size_t)n_bins * n_edges);
+    CallKey key(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, want_counts, want_sums, job_work != nullptr);
     HostPlan *plan = nullptr;
     for (HostPlan *cand_plan : ctx->plans)
-        if (cand_plan->hash == h && cand_plan->c1_uid == c1->uid && cand_plan->c2_uid == c2->uid && cand_plan->opt_gen == ctx->opt_gen &&
-            cand_plan->n_jobs_in == n_jobs && cand_plan->n_bins_in == n_bins && cand_plan->n_edges_in == n_edges &&
-            cand_plan->kernel_in == kernel && cand_plan->want_counts == want_counts && cand_plan->want_sums == want_sums &&
-            cand_plan->for_work == (job_work != nullptr) &&
-            memcmp(cand_plan->jobs_in.data(), jobs, sizeof(int32_t) * 2 * (size_t)n_jobs) == 0 &&
-            memcmp(cand_plan->t_in.data(), t, sizeof(double) * (size_t)n_bins * n_edges) == 0) {
+        if (cand_plan->key == key) {
             plan = cand_plan;
             break;
         }
@@ -3867,11 +3874,8 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         if (!fresh) return fail(YAWHIP_ERR_OOM, "host allocation failed");
         const int rc = make_plan(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, want_counts, want_sums, job_work != nullptr, *fresh);
         if (rc != YAWHIP_OK) return rc;
-        fresh->hash = h; fresh->c1_uid = c1->uid; fresh->c2_uid = c2->uid; fresh->opt_gen = ctx->opt_gen;
-        fresh->n_jobs_in = n_jobs; fresh->n_bins_in = n_bins; fresh->n_edges_in = n_edges; fresh->kernel_in = kernel;
-        fresh->want_counts = want_counts; fresh->want_sums = want_sums; fresh->for_work = job_work != nullptr;
-        fresh->jobs_in.assign(jobs, jobs + 2 * (size_t)n_jobs);
-        fresh->t_in.assign(t, t + (size_t)n_bins * n_edges);
+        key.keep();
+        fresh->key = std::move(key);
         if (ctx->plans.size() >= MAX_PLANS) {  // evict the least recently used one (nothing of it is in flight: calls are blocking,
             size_t old = 0;                    // and a batch is never longer than the plans kept)
             for (size_t i = 1; i < ctx->plans.size(); ++i)
@@ -3910,9 +3914,6 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     ctx->d_sums.ptr = reinterpret_cast<double *>(ctx->out.d + o_sums);
     HIP_TRY(hipMemsetAsync(ctx->out.d, 0, P.n_items > 0 ? o_sums : out_bytes, ctx->stream));
 
-    // LDS: two stages + thresholds + histogram(s)
-    const size_t lds_fixed = 2 * STAGE * (sizeof(Obj) + sizeof(ObjF)) + (size_t)((n_edges + 1) & ~1) * sizeof(double);
-    auto lds_for = [&](bool w, bool priv) { return lds_fixed + (size_t)P.nf * (priv ? WG : 1) * (w ? 8 : 4); };
     int launches = 0;
     const int64_t n_pot = P.n_items;
     int64_t n_items = P.n_items;  // the count grid: all potential items, or what the builder kept (SWEEP)
@@ -3993,226 +3994,133 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         return hipGetLastError();
     };
     HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
-    bool band_ran = false;
-    if (n_items > 0 && P.lean && P.band) {
-        // Grid from the number of POTENTIAL items (known on the host); the kernel reads the number the builder kept
-        // from the device counter, workgroups beyond it exit, workgroups loop if more were kept than the grid holds.
-        // The strip builder keeps about one potential item in five, ordinary items are all kept.
-        const int grid_div = P.grid_div;
-        int64_t grid = P.strip_items && n_pot > 65536 ? n_pot / grid_div : n_pot;
-        // items per workgroup visit (unweighted): batches of 4 / 8 when the histogram has hundreds of cells to flush
-        const int n_cells = P.lean_bins * P.nf;
-        // Batches of consecutive items (one flush of the histogram per batch) are a tunable, off by default: consecutive
-        // items are tiles of the same run, so on clustered data a batch strings the heaviest items together on one
-        // workgroup (measured: DD of the clustered survey with 31 fine bins 7.2 -> 20.6 ms with batches of four), and on
-        // uniform data the flush they save is not what the time goes to (2.27 ms either way at the headline, 51 fine bins).
-        (void)n_cells;
-        const int batch_log2 = ctx->band_batch_log2 >= 0 ? ctx->band_batch_log2 : 0;
-        if (!P.run_weighted) grid = std::max<int64_t>(grid >> batch_log2, 8);
-        grid = std::min<int64_t>((grid + 7) & ~7ll, 1ll << 22);
-        // 32-bit LDS counters: one stage adds at most 64 R x CAP to a cell, so flush at the latest every
-        // 2^32 / (64 R CAP) stages (2^17 for two objects per lane and 192-entry stages, 2^15 for four and 288)
-        int flush_log2 = ctx->flush_log2;
-        while (flush_log2 > 0 && ((uint64_t)64 * P.R * 2 * P.cap << flush_log2) >= (1ull << 32)) --flush_log2;  // (x 2: half bands count double)
-        const unsigned flush_mask = (1u << flush_log2) - 1u;
-        const size_t lds_band32 = band32_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.merged && !P.uniform_t ? n_bins : 0, n_edges);
+    // The count kernels. Their variants are picked from the plan (pick; each list runs from the last variant to the first:
+    // the compiler lays the kernels out in the reverse order, which keeps the code object as it was).
+    // Band kernels: grid from the number of POTENTIAL items (known on the host); the kernel reads the number the builder kept
+    // from the device counter, workgroups beyond it exit, workgroups loop if more were kept than the grid holds.
+    // The strip builder keeps about one potential item in five, ordinary items are all kept.
+    int64_t grid = P.strip_items && n_pot > 65536 ? n_pot / P.grid_div : n_pot;
+    // Batches of consecutive items (one flush of the histogram per batch) are a tunable, off by default: consecutive
+    // items are tiles of the same run, so on clustered data a batch strings the heaviest items together on one
+    // workgroup (measured: DD of the clustered survey with 31 fine bins 7.2 -> 20.6 ms with batches of four), and on
+    // uniform data the flush they save is not what the time goes to (2.27 ms either way at the headline, 51 fine bins).
+    const int batch_log2 = ctx->band_batch_log2 >= 0 ? ctx->band_batch_log2 : 0;
+    if (!P.run_weighted) grid = std::max<int64_t>(grid >> batch_log2, 8);
+    grid = std::min<int64_t>((grid + 7) & ~7ll, 1ll << 22);
+    const dim3 band_grid((unsigned)grid), wave(64);
+    // 32-bit LDS counters: one stage adds at most 64 R x CAP to a cell, so flush at the latest every
+    // 2^32 / (64 R CAP) stages (2^17 for two objects per lane and 192-entry stages, 2^15 for four and 288)
+    int flush_log2 = ctx->flush_log2;
+    while (flush_log2 > 0 && ((uint64_t)64 * P.R * 2 * P.cap << flush_log2) >= (1ull << 32)) --flush_log2;  // (x 2: half bands count double)
+    const unsigned flush_mask = (1u << flush_log2) - 1u;
+    const std::pair<int, int> stage{P.R, P.cap};
+    const std::pair<bool, bool> rows{P.merged, P.uni};
+    auto launch_band32 = [&](bool wgt) -> hipError_t {
+        const size_t lds = band32_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.merged && !P.uniform_t ? n_bins : 0, n_edges);
         const bool one_chunk = P.triple || !P.strip_items;  // every item has one window
-        auto launch_band32 = [&](bool wgt) -> hipError_t {
-#define YAW_LAUNCH_B32_CH(RR, CC, WW, NN, MM, UU, KNAME)                                                              \
-    do {                                                                                                              \
-        auto kern = KNAME<RR, CC, WW, NN, MM, UU>;                                                                    \
-        if (lds_band32 > 64 * 1024) {                                                                                 \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_band32);         \
-            if (ea != hipSuccess) return ea;                                                                          \
-        }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds_band32, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, \
-                           n_bins, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, \
-                           ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);                                             \
-    } while (0)
-#define YAW_LAUNCH_B32(RR, CC, WW, NN, MM, UU)                                                                        \
-    do {                                                                                                              \
-        if (one_chunk) YAW_LAUNCH_B32_CH(RR, CC, WW, NN, MM, UU, k_count_band32_one);                                 \
-        else YAW_LAUNCH_B32_CH(RR, CC, WW, NN, MM, UU, k_count_band32);                                               \
-    } while (0)
-#define YAW_LAUNCH_B32_R(WW, NN, MM, UU)                                                                              \
-    do {                                                                                                              \
-        if (P.R == 1) YAW_LAUNCH_B32(1, B32_CAP, WW, NN, MM, UU);                                                       \
-        else if (P.R == 2 && P.cap == B32_CAP) YAW_LAUNCH_B32(2, B32_CAP, WW, NN, MM, UU);                                \
-        else if (P.R == 2) YAW_LAUNCH_B32(2, B32_CAP_BIG, WW, NN, MM, UU);                                              \
-        else YAW_LAUNCH_B32(4, B32_CAP_BIG, WW, NN, MM, UU);                                                          \
-    } while (0)
-#define YAW_LAUNCH_B32_M(WW, NN)                                                                                      \
-    do {                                                                                                              \
-        if (!P.merged) YAW_LAUNCH_B32_R(WW, NN, false, true);                                                           \
-        else if (P.uniform_t) YAW_LAUNCH_B32_R(WW, NN, true, true);                                                     \
-        else YAW_LAUNCH_B32_R(WW, NN, true, false);                                                                   \
-    } while (0)
-#define YAW_LAUNCH_B32_N(WW)                                                                                          \
-    do {                                                                                                              \
-        if (n_edges == 2) YAW_LAUNCH_B32_M(WW, 2); else if (n_edges == 3) YAW_LAUNCH_B32_M(WW, 3);                    \
-        else YAW_LAUNCH_B32_M(WW, 4);                                                                                 \
-    } while (0)
-            if (wgt) YAW_LAUNCH_B32_N(true); else YAW_LAUNCH_B32_N(false);
-#undef YAW_LAUNCH_B32_N
-#undef YAW_LAUNCH_B32_M
-#undef YAW_LAUNCH_B32_R
-#undef YAW_LAUNCH_B32
-#undef YAW_LAUNCH_B32_CH
-            return hipGetLastError();
-        };
-        auto launch_band64 = [&](bool wgt) -> hipError_t {
-#define YAW_LAUNCH_BAND(RR, CC, WW, NN, MM, UU)                                                                       \
-    do {                                                                                                              \
-        auto kern = k_count_band<RR, CC, WW, NN, MM, UU>;                                                             \
-        if (P.lds_band > 64 * 1024) {                                                                                   \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_band);           \
-            if (ea != hipSuccess) return ea;                                                                          \
-        }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), P.lds_band, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, \
-                           n_bins, n_edges, ctx->d_t.ptr, ctx->d_rwin.ptr, flush_mask, P.hp_shift, WW ? 0 : batch_log2, ctx->d_counts.ptr, \
-                           ctx->d_partials.ptr, ctx->d_ctr.ptr);                                                      \
-    } while (0)
-#define YAW_LAUNCH_BAND_R(WW, NN, MM, UU)                                                                             \
-    do {                                                                                                              \
-        if (P.R == 1) YAW_LAUNCH_BAND(1, BCAP, WW, NN, MM, UU);                                                         \
-        else if (P.R == 2 && P.cap == BCAP) YAW_LAUNCH_BAND(2, BCAP, WW, NN, MM, UU);                                     \
-        else if (P.R == 2) YAW_LAUNCH_BAND(2, BCAP_MID, WW, NN, MM, UU);                                                \
-        else YAW_LAUNCH_BAND(4, BCAP_MID, WW, NN, MM, UU);                                                            \
-    } while (0)
-#define YAW_LAUNCH_BAND_M(WW, NN)                                                                                     \
-    do {                                                                                                              \
-        if (!P.merged) YAW_LAUNCH_BAND_R(WW, NN, false, true);                                                          \
-        else if (P.uniform_t) YAW_LAUNCH_BAND_R(WW, NN, true, true);                                                    \
-        else YAW_LAUNCH_BAND_R(WW, NN, true, false);                                                                  \
-    } while (0)
-#define YAW_LAUNCH_BAND_N(WW)                                                                                         \
-    do {                                                                                                              \
-        if (P.band_ne == 2) YAW_LAUNCH_BAND_M(WW, 2); else if (P.band_ne == 3) YAW_LAUNCH_BAND_M(WW, 3);                  \
-        else if (P.band_ne == 4) YAW_LAUNCH_BAND_M(WW, 4); else YAW_LAUNCH_BAND_M(WW, 0);                               \
-    } while (0)
-            if (wgt) YAW_LAUNCH_BAND_N(true); else YAW_LAUNCH_BAND_N(false);
-#undef YAW_LAUNCH_BAND_N
-#undef YAW_LAUNCH_BAND_M
-#undef YAW_LAUNCH_BAND_R
-#undef YAW_LAUNCH_BAND
-            return hipGetLastError();
-        };
-        const size_t lds_fine = band32_fine_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.uniform_t ? 1 : n_bins, n_edges);
-        auto launch_fine = [&](bool wgt) -> hipError_t {
-#define YAW_LAUNCH_FINE(RR, CC, WW, MM, UU)                                                                           \
-    do {                                                                                                              \
-        auto kern = k_count_band32_fine<RR, CC, WW, MM, UU>;                                                          \
-        if (lds_fine > 64 * 1024) {                                                                                   \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fine);           \
-            if (ea != hipSuccess) return ea;                                                                          \
-        }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds_fine, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, \
-                           n_bins, n_edges, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, \
-                           ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);                                             \
-    } while (0)
-#define YAW_LAUNCH_FINE_R(WW, MM, UU)                                                                                 \
-    do {                                                                                                              \
-        if (P.R == 1) YAW_LAUNCH_FINE(1, BCAP, WW, MM, UU);                                                             \
-        else if (P.R == 2 && P.cap == BCAP) YAW_LAUNCH_FINE(2, BCAP, WW, MM, UU);                                         \
-        else if (P.R == 2) YAW_LAUNCH_FINE(2, BCAP_MID, WW, MM, UU);                                                    \
-        else YAW_LAUNCH_FINE(4, BCAP_MID, WW, MM, UU);                                                                \
-    } while (0)
-#define YAW_LAUNCH_FINE_M(WW)                                                                                         \
-    do {                                                                                                              \
-        if (!P.merged && P.uniform_t) YAW_LAUNCH_FINE_R(WW, false, true);                                                 \
-        else if (!P.merged) YAW_LAUNCH_FINE_R(WW, false, false);                                                        \
-        else if (P.uniform_t) YAW_LAUNCH_FINE_R(WW, true, true);                                                        \
-        else YAW_LAUNCH_FINE_R(WW, true, false);                                                                      \
-    } while (0)
-            if (wgt) YAW_LAUNCH_FINE_M(true); else YAW_LAUNCH_FINE_M(false);
-#undef YAW_LAUNCH_FINE_M
-#undef YAW_LAUNCH_FINE_R
-#undef YAW_LAUNCH_FINE
-            return hipGetLastError();
-        };
-        auto launch_band = [&](bool wgt) -> hipError_t {
-            return P.band32 ? launch_band32(wgt) : (P.band_fine ? launch_fine(wgt) : launch_band64(wgt));
-        };
-        if (P.run_unweighted) {
-            HIP_TRY(launch_band(false));
-            ++launches;
+        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+            return pick<Int<4>, Int<3>, Int<2>>(n_edges, [&](auto ne) {
+                return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
+                    return pick<Stage<4, B32_CAP_BIG>, Stage<2, B32_CAP_BIG>, Stage<2, B32_CAP>, Stage<1, B32_CAP>>(stage, [&](auto s) {
+                        using S = decltype(s);
+                        using M = decltype(r);
+                        auto kern = one_chunk ? k_count_band32_one<S::R, S::CAP, w, ne, M::MERGED, M::UNI>
+                                              : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
+                        return launch(kern, band_grid, wave, lds, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, ctx->d_t.ptr,
+                                      ctx->d_thr32.ptr, ctx->d_rwin.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr,
+                                      ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
+                    });
+                });
+            });
+        });
+    };
+    auto launch_band64 = [&](bool wgt) -> hipError_t {
+        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+            return pick<Int<0>, Int<4>, Int<3>, Int<2>>(P.band_ne, [&](auto ne) {
+                return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
+                    return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
+                        using S = decltype(s);
+                        using M = decltype(r);
+                        return launch(k_count_band<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, P.lds_band, ctx->stream,
+                                      ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_rwin.ptr, flush_mask,
+                                      P.hp_shift, w ? 0 : batch_log2, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                    });
+                });
+            });
+        });
+    };
+    auto launch_fine = [&](bool wgt) -> hipError_t {
+        const size_t lds = band32_fine_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.uniform_t ? 1 : n_bins, n_edges);
+        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+            return pick<Rows<true, false>, Rows<true, true>, Rows<false, false>, Rows<false, true>>(rows, [&](auto r) {
+                return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
+                    using S = decltype(s);
+                    using M = decltype(r);
+                    return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, lds, ctx->stream,
+                                  ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr,
+                                  flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
+                });
+            });
+        });
+    };
+    // The lean kernel (k_count_merged / _occ8) and k_count, one workgroup per item: grids in pieces of at most 2^32 - 1
+    // work-items per launch dimension.
+    auto in_pieces = [&](int wg, auto &&launch_at) -> hipError_t {
+        const int64_t max_grid = (1ll << 31) / wg;
+        for (int64_t base = 0; base < n_items; base += max_grid) {
+            const hipError_t e = launch_at(dim3((unsigned)std::min(max_grid, n_items - base)), base);
+            if (e != hipSuccess) return e;
         }
-        if (P.run_weighted) {
-            HIP_TRY(launch_band(true));
-            ++launches;
-            HIP_TRY(reduce_partials(P.merged ? (int64_t)n_jobs : P.n_slots, P.slab));  // slabs are reduced per output slot
-            launches += 2;
-        }
-        band_ran = true;
-    } else if (n_items > 0 && P.lean) {
-        auto launch_lean = [&](bool wgt) -> hipError_t {
-            const int64_t max_grid = (1ll << 31) / MWG;  // at most 2^32 - 1 work-items per launch dimension
-            for (int64_t base = 0; base < n_items; base += max_grid) {
-                const unsigned g = (unsigned)std::min(max_grid, n_items - base);
-#define YAW_LAUNCH_LEAN(RR, WW, NN, MM)                                                                               \
-    do {                                                                                                              \
-        auto kern = pick_count_merged<RR, WW, NN, MM>();                                                              \
-        if (P.lds_merged > 64 * 1024) {                                                                                 \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merged);         \
-            if (ea != hipSuccess) return ea;                                                                          \
-        }                                                                                                             \
-        hipLaunchKernelGGL(kern, dim3(g), dim3(MWG), P.lds_merged, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr,      \
-                           n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, ctx->d_rwin.ptr, base, ctx->d_counts.ptr,  \
-                           ctx->d_partials.ptr, ctx->d_ctr.ptr);                                                      \
-    } while (0)
-#define YAW_LAUNCH_LEAN_R(WW, NN, MM)                                                                                 \
-    do {                                                                                                              \
-        if (P.R == 1) YAW_LAUNCH_LEAN(1, WW, NN, MM); else if (P.R == 2) YAW_LAUNCH_LEAN(2, WW, NN, MM); else YAW_LAUNCH_LEAN(4, WW, NN, MM); \
-    } while (0)
-#define YAW_LAUNCH_LEAN_M(WW, NN)                                                                                     \
-    do {                                                                                                              \
-        if (P.merged) YAW_LAUNCH_LEAN_R(WW, NN, true); else YAW_LAUNCH_LEAN_R(WW, NN, false);                           \
-    } while (0)
-                const bool nf1 = P.nf == 1;
-                if (wgt) {
-                    if (nf1) YAW_LAUNCH_LEAN_M(true, true); else YAW_LAUNCH_LEAN_M(true, false);
-                } else {
-                    if (nf1) YAW_LAUNCH_LEAN_M(false, true); else YAW_LAUNCH_LEAN_M(false, false);
-                }
-#undef YAW_LAUNCH_LEAN_M
-#undef YAW_LAUNCH_LEAN_R
-#undef YAW_LAUNCH_LEAN
-                hipError_t el = hipGetLastError();
-                if (el != hipSuccess) return el;
-            }
-            return hipSuccess;
-        };
-        if (P.run_unweighted) {
-            HIP_TRY(launch_lean(false));
-            ++launches;
-        }
-        if (P.run_weighted) {
-            HIP_TRY(launch_lean(true));
-            ++launches;
-            HIP_TRY(reduce_partials(P.merged ? (int64_t)n_jobs : P.n_slots, P.slab));  // slabs are reduced per output slot
-            launches += 2;
-        }
-    } else if (n_items > 0) {
-        if (P.run_unweighted) {
-            const bool priv = lds_for(false, true) <= (size_t)ctx->lds_limit;
-            hipError_t e = launch_count_any<false>(priv, P.filter, P.R, ctx, c1, c2, (int)P.n_slots, n_bins, n_edges, P.n_items,
-                                                   lds_for(false, priv));
-            HIP_TRY(e);
-            ++launches;
-        }
-        if (P.run_weighted) {
-            const bool priv = lds_for(true, true) <= (size_t)ctx->lds_limit;
-            hipError_t e = launch_count_any<true>(priv, P.filter, P.R, ctx, c1, c2, (int)P.n_slots, n_bins, n_edges, P.n_items,
-                                                  lds_for(true, priv));
-            HIP_TRY(e);
-            ++launches;
-            HIP_TRY(reduce_partials(P.n_slots, P.nf));
-            launches += 2;
-        }
+        return hipSuccess;
+    };
+    auto launch_lean = [&](bool wgt) -> hipError_t {
+        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+            return pick<Bool<false>, Bool<true>>(P.nf == 1, [&](auto nf1) {
+                return pick<Bool<false>, Bool<true>>(P.merged, [&](auto m) {
+                    return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
+                        return in_pieces(MWG, [&](dim3 g, int64_t base) {
+                            return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), P.lds_merged, ctx->stream, ctx->d_tabs.ptr,
+                                          ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, ctx->d_rwin.ptr, base,
+                                          ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                        });
+                    });
+                });
+            });
+        });
+    };
+    // LDS of k_count: two stages + thresholds + histogram(s)
+    const size_t lds_fixed = 2 * STAGE * (sizeof(Obj) + sizeof(ObjF)) + (size_t)((n_edges + 1) & ~1) * sizeof(double);
+    auto lds_for = [&](bool w, bool priv) { return lds_fixed + (size_t)P.nf * (priv ? WG : 1) * (w ? 8 : 4); };
+    auto launch_plain = [&](bool wgt) -> hipError_t {
+        const bool priv = lds_for(wgt, true) <= (size_t)ctx->lds_limit;
+        return pick<Bool<true>, Bool<false>>(wgt, [&](auto w) {
+            return pick<Bool<false>, Bool<true>>(priv, [&](auto pv) {
+                return pick<Bool<false>, Bool<true>>(P.filter, [&](auto f) {
+                    return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
+                        return in_pieces(WG, [&](dim3 g, int64_t base) {
+                            return launch(k_count<r, w, pv, f>, g, dim3(WG), lds_for(w, pv), ctx->stream, view_of(c1), view_of(c2),
+                                          ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, base, ctx->d_counts.ptr,
+                                          ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                        });
+                    });
+                });
+            });
+        });
+    };
+    const bool band_ran = n_items > 0 && P.lean && P.band;
+    auto launch_count = [&](bool wgt) {
+        if (band_ran) return P.band32 ? launch_band32(wgt) : (P.band_fine ? launch_fine(wgt) : launch_band64(wgt));
+        return P.lean ? launch_lean(wgt) : launch_plain(wgt);
+    };
+    if (n_items > 0 && P.run_unweighted) {
+        HIP_TRY(launch_count(false));
+        ++launches;
+    }
+    if (n_items > 0 && P.run_weighted) {
+        HIP_TRY(launch_count(true));
+        ++launches;
+        HIP_TRY(reduce_partials(P.merged ? (int64_t)n_jobs : P.n_slots, P.slab));  // slabs are reduced per output slot
+        launches += 2;
     }
     HIP_TRY(hipEventRecord(ctx->evc1, ctx->stream));
     if (!P.weighted && want_sums) {
@@ -4372,21 +4280,6 @@ int run_single(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *
     return YAWHIP_OK;
 }
 
-// FNV-1a over the inputs that determine the job partition of a multi-device call
-uint64_t plan_key(const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
-                  int32_t n_edges, const double *t, int32_t kernel, size_t n_dev) {
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *p, size_t n) {
-        const unsigned char *b = static_cast<const unsigned char *>(p);
-        for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
-    };
-    mix(&c1, sizeof c1); mix(&c2, sizeof c2); mix(&c1->n, sizeof c1->n); mix(&c2->n, sizeof c2->n);
-    mix(&n_jobs, sizeof n_jobs); mix(jobs, sizeof(int32_t) * 2 * (size_t)n_jobs);
-    mix(&n_bins, sizeof n_bins); mix(&n_edges, sizeof n_edges); mix(t, sizeof(double) * (size_t)n_bins * n_edges);
-    mix(&kernel, sizeof kernel); mix(&n_dev, sizeof n_dev);
-    return h;
-}
-
 }  // namespace
 
 namespace {
@@ -4450,22 +4343,22 @@ int yawhip_count_pairs(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_c
                        const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
                        int64_t *fine_counts, double *fine_sums, yawhip_stats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    if (!ctx || !c1 || !c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: NULL handle");
+    const int rc_args = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
+    if (rc_args != YAWHIP_OK) return rc_args;
     if (ctx->peers.empty() || n_jobs < 2)
         return run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_counts, fine_sums, stats);
     // ---- several devices: the independent jobs are split over them (replaces the reference's process pool,
     // src/yaw/utils/parallel.py:251-346). Every device holds both catalogues; a job's rows of the result come from
     // exactly one device, so nothing has to be reduced: the rows are copied into place.
-    if (c1->ctx != ctx || c2->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
     const size_t n_dev = ctx->peers.size() + 1;
     if (c1->replicas.size() != n_dev - 1 || c2->replicas.size() != n_dev - 1)
         return fail(YAWHIP_ERR_MISMATCH, "catalogue was not uploaded to every device of the context");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || !t || !jobs) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: bad sizes");
     const auto wall0 = std::chrono::steady_clock::now();
     // the plan: evaluated pairs per job from the item builder (device 0), longest-processing-time-first over the devices;
     // it depends on the inputs only and is kept for the next call with the same inputs
-    const uint64_t key = plan_key(c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, n_dev);
-    if (ctx->plan.key != key || ctx->plan.parts.size() != n_dev) {
+    // (the inputs of the cost estimate below, and the device count)
+    CallKey key(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, true, (int32_t)n_dev);
+    if (!(ctx->plan.key == key)) {
         std::vector<int64_t> work((size_t)n_jobs, 0);
         CallState cs;
         int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, work.data(), cs);
@@ -4482,7 +4375,8 @@ int yawhip_count_pairs(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_c
             load[d] += (double)work[(size_t)j] + fixed;
         }
         for (auto &part : ctx->plan.parts) std::sort(part.begin(), part.end());
-        ctx->plan.key = key;
+        key.keep();
+        ctx->plan.key = std::move(key);
     }
     const int64_t row = (int64_t)n_bins * (n_edges - 1);
     std::vector<CallState> states(n_dev);
@@ -4541,7 +4435,9 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
     if (!ctx || !c1 || !c2 || !device_rows) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: NULL argument");
     *device_rows = nullptr;
     if (!ctx->peers.empty()) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: single-device contexts only");
-    if (n_jobs < 0 || n_rows_total < n_jobs || n_bins <= 0 || n_edges < 2 || (n_jobs > 0 && (!jobs || !row_index)))
+    const int rc_args = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
+    if (rc_args != YAWHIP_OK) return rc_args;
+    if (n_rows_total < n_jobs || (n_jobs > 0 && !row_index))
         return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: bad sizes or NULL arrays");
     const int64_t row = (int64_t)n_bins * (n_edges - 1);
     for (int j = 0; j < n_jobs; ++j)
@@ -4632,10 +4528,11 @@ struct DenseState {
     size_t h_comb_off = 0;
 };
 
-int dense_check(const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, int32_t n_scales, const int32_t *slices) {
-    if (!r.c1 || !r.c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: NULL handle");
-    if (r.n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_scales <= 0 || !slices || !r.dense || (r.n_jobs > 0 && !r.jobs))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: bad sizes or NULL arrays");
+int dense_check(const yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t,
+                int32_t n_scales, const int32_t *slices) {
+    const int rc = check_call(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t);
+    if (rc != YAWHIP_OK) return rc;
+    if (n_scales <= 0 || !slices || !r.dense) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: bad sizes or NULL arrays");
     const int64_t P = r.c1->n_patches;
     for (int64_t j = 0; j < r.n_jobs; ++j)
         if (r.jobs[2 * j] < 0 || r.jobs[2 * j] >= P || r.jobs[2 * j + 1] < 0 || r.jobs[2 * j + 1] >= P)
@@ -4837,7 +4734,7 @@ int yawhip_count_pairs_dense_batch(yawhip_ctx *ctx, int32_t n_requests, const ya
         return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense_batch: NULL argument");
     for (int i = 0; i < n_requests; ++i) {
         if (requests[i].stats) memset(requests[i].stats, 0, sizeof(yawhip_stats));
-        const int rc = dense_check(requests[i], n_bins, n_edges, n_scales, slices);
+        const int rc = dense_check(ctx, requests[i], n_bins, n_edges, t, n_scales, slices);
         if (rc != YAWHIP_OK) return rc;
     }
     const int nf = n_edges - 1;
@@ -4994,6 +4891,8 @@ int yawhip_job_work(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_cata
                     int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, int64_t *work) {
     if (!ctx || !work) return fail(YAWHIP_ERR_INVALID, "yawhip_job_work: NULL argument");
     for (int j = 0; j < n_jobs; ++j) work[j] = 0;
+    const int rc = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
+    if (rc != YAWHIP_OK) return rc;
     CallState cs;
     return count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, work, cs);
 }
