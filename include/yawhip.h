@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define YAWHIP_ABI_VERSION 5
+#define YAWHIP_ABI_VERSION 6
 
 typedef enum yawhip_status {
     YAWHIP_OK = 0,
@@ -80,7 +80,19 @@ typedef struct yawhip_stats {
     int32_t band_variant;      /* which band kernel ran (ABI >= 4): 0 none, 64 every entry in float64, 32 float32 classes +
                                   exact guard bands, 33 the same for fine log-spaced radial grids             */
     int32_t merged_triples;       /* 1: the float32 band kernel streamed merged triple runs (one window per item), else 0 */
+    int32_t count_variant;        /* compiled count kernel of the call's unweighted launch, weighted launch (ABI >= 6): 0 none,
+                                     YAWHIP_VARIANT_MIXED where pieces of the call (slab budget, devices) launched different
+                                     variants, else the code below                                                    */
+    int32_t count_variant_weighted;
 } yawhip_stats;
+
+/* Count-kernel variant codes (yawhip_stats.count_variant*): the kernel family and every template argument it was launched with.
+ *   bits 0-3   family: 1 k_count<R, WEIGHTED, PRIV, FILTER>, 2 k_count_merged<R, WEIGHTED, NF1, MERGED>, 3 k_count_merged_occ8 (same),
+ *              4 k_count_band<R, CAP, WEIGHTED, NE, MERGED, UNI>, 5 k_count_band32 (same), 6 k_count_band32_one (same),
+ *              7 k_count_band32_fine<R, CAP, WEIGHTED, MERGED, UNI>
+ *   bits 4-6   R            bits 8-17  CAP (LDS stage entries)      bit 18  WEIGHTED     bits 19-21  NE (edges)
+ *   bit 22     MERGED       bit 23     UNI      bit 24  PRIV        bit 25  FILTER       bit 26      NF1 */
+#define YAWHIP_VARIANT_MIXED (-1)
 
 const char *yawhip_last_error(void);
 int yawhip_abi_version(void);

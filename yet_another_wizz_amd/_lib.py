@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -66,6 +67,8 @@ class _Stats(ctypes.Structure):
         ("exact_reevaluations", ctypes.c_int64),
         ("band_variant", ctypes.c_int32),
         ("merged_triples", ctypes.c_int32),
+        ("count_variant", ctypes.c_int32),
+        ("count_variant_weighted", ctypes.c_int32),
     ]
 
 
@@ -98,6 +101,57 @@ class CountStats:
     exact_reevaluations: int = 0
     band_variant: int = 0
     merged_triples: int = 0
+    count_variant: int = 0           # variant code of the unweighted count launch (variant_name), 0 none, VARIANT_MIXED
+    count_variant_weighted: int = 0  # ... of the weighted one
+
+    @property
+    def variants(self) -> set:
+        """Names of the count kernels the call launched (``variant_name`` of both codes; none: empty)."""
+        return {variant_name(c) for c in (self.count_variant, self.count_variant_weighted) if c != 0}
+
+
+# yawhip_stats.count_variant* (include/yawhip.h): family in bits 0-3, then the template arguments
+VARIANT_MIXED = -1
+VARIANT_FAMILIES = {1: "k_count", 2: "k_count_merged", 3: "k_count_merged_occ8", 4: "k_count_band", 5: "k_count_band32",
+                    6: "k_count_band32_one", 7: "k_count_band32_fine"}
+# template parameters of each family, in order
+VARIANT_PARAMS = {"k_count": ("R", "WEIGHTED", "PRIV", "FILTER"), "k_count_merged": ("R", "WEIGHTED", "NF1", "MERGED"),
+                  "k_count_merged_occ8": ("R", "WEIGHTED", "NF1", "MERGED"),
+                  "k_count_band": ("R", "CAP", "WEIGHTED", "NE", "MERGED", "UNI"),
+                  "k_count_band32": ("R", "CAP", "WEIGHTED", "NE", "MERGED", "UNI"),
+                  "k_count_band32_one": ("R", "CAP", "WEIGHTED", "NE", "MERGED", "UNI"),
+                  "k_count_band32_fine": ("R", "CAP", "WEIGHTED", "MERGED", "UNI")}
+_VARIANT_FIELDS = {"R": (4, 3), "CAP": (8, 10), "WEIGHTED": (18, 1), "NE": (19, 3), "MERGED": (22, 1), "UNI": (23, 1),
+                   "PRIV": (24, 1), "FILTER": (25, 1), "NF1": (26, 1)}  # (first bit, bits)
+
+
+def variant_name(code: int) -> str:
+    """A count-kernel variant code rendered as ``nm -C`` prints the kernel, e.g. ``k_count_band32_one<2, 512, false, 2, true,
+    true>``; ``"mixed"`` for VARIANT_MIXED. Raises ValueError for 0 or a code that names no family."""
+    if code == VARIANT_MIXED:
+        return "mixed"
+    family = VARIANT_FAMILIES.get(code & 0xF)
+    if family is None:
+        raise ValueError(f"not a count-kernel variant code: {code}")
+    args = []
+    for p in VARIANT_PARAMS[family]:
+        lo, bits = _VARIANT_FIELDS[p]
+        v = (code >> lo) & ((1 << bits) - 1)
+        args.append(str(v) if bits > 1 else ("true" if v else "false"))
+    return f"{family}<{', '.join(args)}>"
+
+
+def variant_code(name: str) -> int:
+    """Inverse of ``variant_name``: the code of a kernel named as ``nm -C`` prints it."""
+    family, args = name.rstrip(">").split("<")
+    code = {v: k for k, v in VARIANT_FAMILIES.items()}[family]
+    for p, a in zip(VARIANT_PARAMS[family], (a.strip() for a in args.split(",")), strict=True):
+        lo, bits = _VARIANT_FIELDS[p]
+        v = {"true": 1, "false": 0}[a] if bits == 1 else int(a)
+        if not 0 <= v < (1 << bits):
+            raise ValueError(f"{p} = {a} does not fit the code")
+        code |= v << lo
+    return code
 
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -218,6 +272,7 @@ class Context:
             self.devices = (int(device),)
         self.device = self.devices[0]
         self.strip_micro = DEFAULT_STRIP_MICRO
+        self._catalogs = weakref.WeakSet()  # live catalogues: freed before the context (a catalogue's free reads its context)
 
     def set_option(self, key: str, value: int) -> None:
         _check(load_library().yawhip_ctx_set_option(self._h, key.encode(), int(value)), "yawhip_ctx_set_option")
@@ -226,6 +281,8 @@ class Context:
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
+            for cat in list(self._catalogs):
+                cat.free()
             load_library().yawhip_ctx_destroy(self._h)
             self._h = _vp()
 
@@ -266,6 +323,7 @@ class DeviceCatalog:
             "yawhip_catalog_upload_axis",
         )
         self.sort_axis = int(sort_axis)
+        ctx._catalogs.add(self)
 
     @property
     def device_bytes(self) -> int:

@@ -3190,7 +3190,18 @@ struct CallState {
     bool segmented = false;        // the item list was kept in segments: the kept items are the sum of the segment counters
     int64_t cand = 0, abytes = 0, n_pot = 0;
     int launches = 0, kernel = 0, mode = 0, n_orient = 0, band_variant = 0, merged_triples = 0;
+    int32_t variant[2] = {0, 0};   // count kernel of the unweighted, weighted launch (variant_code)
 };
+
+// yawhip_stats.count_variant*: the family and template arguments of a count kernel (code layout: include/yawhip.h)
+enum VariantFamily : int32_t { VF_COUNT = 1, VF_MERGED, VF_MERGED_OCC8, VF_BAND, VF_BAND32, VF_BAND32_ONE, VF_BAND32_FINE };
+constexpr int32_t variant_code(int32_t family, int R, int cap, bool weighted, int ne = 0, bool merged = false, bool uni = false,
+                               bool priv = false, bool filter = false, bool nf1 = false) {
+    return family | R << 4 | cap << 8 | (int32_t)weighted << 18 | ne << 19 | (int32_t)merged << 22 | (int32_t)uni << 23 |
+           (int32_t)priv << 24 | (int32_t)filter << 25 | (int32_t)nf1 << 26;
+}
+// the variant of a call from those of its pieces: pieces that launched none do not count, different ones make it mixed
+int32_t merge_variant(int32_t a, int32_t b) { return a == 0 || a == b ? b : (b == 0 ? a : YAWHIP_VARIANT_MIXED); }
 
 // Float32 bounds of every edge for k_count_band32 (see there): for unit vectors rounded to float32,
 //   |s32 - s| <= g(t) = 2.1e-7 sqrt(t) + 5e-7 t + 1e-12 near s = t,
@@ -3996,6 +4007,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
     // The count kernels. Their variants are picked from the plan (pick; each list runs from the last variant to the first:
     // the compiler lays the kernels out in the reverse order, which keeps the code object as it was).
+    // Every launch records its variant in cs.variant[weighted] (yawhip_stats.count_variant*).
     // Band kernels: grid from the number of POTENTIAL items (known on the host); the kernel reads the number the builder kept
     // from the device counter, workgroups beyond it exit, workgroups loop if more were kept than the grid holds.
     // The strip builder keeps about one potential item in five, ordinary items are all kept.
@@ -4026,6 +4038,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                         using M = decltype(r);
                         auto kern = one_chunk ? k_count_band32_one<S::R, S::CAP, w, ne, M::MERGED, M::UNI>
                                               : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
+                        cs.variant[w] = variant_code(one_chunk ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
                         return launch(kern, band_grid, wave, lds, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, ctx->d_t.ptr,
                                       ctx->d_thr32.ptr, ctx->d_rwin.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr,
                                       ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
@@ -4041,6 +4054,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                     return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
                         using S = decltype(s);
                         using M = decltype(r);
+                        cs.variant[w] = variant_code(VF_BAND, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
                         return launch(k_count_band<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, P.lds_band, ctx->stream,
                                       ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_rwin.ptr, flush_mask,
                                       P.hp_shift, w ? 0 : batch_log2, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr);
@@ -4056,6 +4070,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                 return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
                     using S = decltype(s);
                     using M = decltype(r);
+                    cs.variant[w] = variant_code(VF_BAND32_FINE, S::R, S::CAP, w, 0, M::MERGED, M::UNI);
                     return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, lds, ctx->stream,
                                   ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr,
                                   flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
@@ -4078,6 +4093,8 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
             return pick<Bool<false>, Bool<true>>(P.nf == 1, [&](auto nf1) {
                 return pick<Bool<false>, Bool<true>>(P.merged, [&](auto m) {
                     return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
+                        cs.variant[w] = variant_code(r <= 2 ? VF_MERGED_OCC8 : VF_MERGED,  // (the choice of pick_count_merged)
+                                                      r, 0, w, 0, m, false, false, false, nf1);
                         return in_pieces(MWG, [&](dim3 g, int64_t base) {
                             return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), P.lds_merged, ctx->stream, ctx->d_tabs.ptr,
                                           ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, ctx->d_rwin.ptr, base,
@@ -4097,6 +4114,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
             return pick<Bool<false>, Bool<true>>(priv, [&](auto pv) {
                 return pick<Bool<false>, Bool<true>>(P.filter, [&](auto f) {
                     return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
+                        cs.variant[w] = variant_code(VF_COUNT, r, 0, w, 0, false, false, pv, f);
                         return in_pieces(WG, [&](dim3 g, int64_t base) {
                             return launch(k_count<r, w, pv, f>, g, dim3(WG), lds_for(w, pv), ctx->stream, view_of(c1), view_of(c2),
                                           ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, base, ctx->d_counts.ptr,
@@ -4222,6 +4240,8 @@ int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, dou
         stats->n_orientations = cs.n_orient;
         stats->band_variant = cs.band_variant;
         stats->merged_triples = cs.merged_triples;
+        stats->count_variant = cs.variant[0];
+        stats->count_variant_weighted = cs.variant[1];
         if (cs.band_ran)
             for (int i = 0; i < EVAL_SLOTS; ++i) stats->exact_reevaluations += (int64_t)ctr[9 + 8 * (size_t)i];
         stats->kernel_ms = ms;
@@ -4242,6 +4262,8 @@ void add_stats(yawhip_stats &total, const yawhip_stats &part, bool side_by_side)
     total.n_orientations = std::max(total.n_orientations, part.n_orientations);
     total.band_variant = part.band_variant;
     total.merged_triples = part.merged_triples;
+    total.count_variant = merge_variant(total.count_variant, part.count_variant);
+    total.count_variant_weighted = merge_variant(total.count_variant_weighted, part.count_variant_weighted);
     total.exact_reevaluations += part.exact_reevaluations;
     if (side_by_side) {  // devices of one call run at the same time: the slowest counts
         total.kernel_ms = std::max(total.kernel_ms, part.kernel_ms);
