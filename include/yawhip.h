@@ -280,6 +280,26 @@ int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const dou
                           int32_t n_centers, const double *centers_xyz, int32_t *patch_out);
 
 /*
+ * Uniform random points in an ra / dec box with optional attached values -- BoxRandoms.__call__ of the reference
+ * (src/yaw/randoms.py:152-178, 256-259) called for n values in chunks of chunksize, as Catalog.from_random does
+ * (catalog/readers.py:137-192) -- drawn on the device from numpy's PCG64 stream: every value and the end state are
+ * numpy's, bit for bit. Per chunk of k values: k x ~ U(x_min, x_min + x_range), k y the same way, then, with attached
+ * data, k indices Generator.integers(0, n_data) and the values at them.
+ *   state        numpy's bit_generator.state before the first chunk: state hi, state lo, inc hi, inc lo (64-bit halves)
+ *   has_uint32, uinteger   its pending 32-bit half (read before any other half by the first index draw)
+ *   n_data       -1: nothing attached (no index draws); else 1 .. 2^32 (more: YAWHIP_ERR_INVALID, numpy's 64-bit path)
+ *   data_w, data_z         float64[n_data] values to draw from (host, may be NULL), w_out / z_out float64[n] given with them
+ *   x_out, y_out float64[n] (host): x = ra in radian, y = sin(dec)
+ *   idx_out      int64[n] drawn indices (host, may be NULL)
+ *   state_out, has_uint32_out, uinteger_out   numpy's state after the last chunk (inc does not change)
+ */
+int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32,
+                      uint32_t uinteger, double x_min, double x_range, double y_min, double y_range, int64_t n_data,
+                      const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
+                      double *z_out, int64_t *idx_out, uint64_t state_out[2], int32_t *has_uint32_out,
+                      uint32_t *uinteger_out);
+
+/*
  * Host-only helper of the ingest path (no device, no context): stable grouping of float64 columns by an integer key --
  * what the reference does per chunk with groupby(patch_ids, chunk) (catalog/catalog.py:293, utils/misc.py:40-51) and
  * groupby(bin_idx, chunk) (catalog/trees.py:413), i.e. np.argsort(kind="stable") + a gather per column, here as one

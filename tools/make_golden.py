@@ -15,11 +15,16 @@ Vector groups:
   G7  twodflens.npz     bundled 2dFLenS example catalogue (11 patches, weights) in arcmin units
   G8  ourcache_reference_readback.npz   what the reference reads from a cache written by this package
                         (--ourcache-readback regenerates only this group)
+  G9  random_box.npz    the reference's first BoxRandoms call, its Catalog.from_random catalogue (odd chunk size, attached
+                        weights and redshifts) as a per-patch digest of every record plus a sample of records, the
+                        generator's end state and autocorrelate totals against those randoms (--random-box regenerates
+                        only this group)
 
 Usage:  python tools/make_golden.py
 """
 from __future__ import annotations
 
+import hashlib
 import math
 import os
 import shutil
@@ -377,6 +382,69 @@ def make_ourcache_readback(tmp):
     save("ourcache_reference_readback.npz", **out)
 
 
+def state_words(state):
+    """numpy's PCG64 bit_generator.state as uint64[6]: state hi, lo, inc hi, lo, has_uint32, uinteger."""
+    mask = (1 << 64) - 1
+    s, inc = state["state"]["state"], state["state"]["inc"]
+    return np.array([s >> 64, s & mask, inc >> 64, inc & mask, state["has_uint32"], state["uinteger"]], dtype=np.uint64)
+
+
+RANDOM_BOX_SAMPLE = 64  # every 64th record of a patch in ra order is stored in full
+
+
+def records_sha256(ra, weights, redshifts):
+    """SHA-256 of the float64 rows (ra, weights, redshifts) in ascending ra; tests/test_randoms.py computes the same."""
+    order = np.argsort(ra, kind="stable")
+    rows = np.ascontiguousarray(np.column_stack([ra[order], weights[order], redshifts[order]]), dtype="<f8")
+    return hashlib.sha256(rows.tobytes()).hexdigest()
+
+
+def make_random_box(tmp):
+    """``yaw.randoms.BoxRandoms`` and ``yaw.Catalog.from_random`` in a 60 x 30 degree box with 1001 attached weights and
+    redshifts, 50 000 randoms in chunks of 7919 (odd: the pending 32-bit half crosses chunks) over 3 fixed patch centres;
+    then ``yaw.autocorrelate`` of a small data catalogue against these randoms."""
+    from yaw.randoms import BoxRandoms
+
+    rng = np.random.default_rng(4242)
+    box = np.array([10.0, 70.0, -20.0, 10.0])  # ra_min, ra_max, dec_min, dec_max (degrees)
+    n_attached, num, chunksize, seed, first_call = 1001, 50_000, 7919, 31415, 500
+    data_w = rng.uniform(0.5, 1.5, n_attached)
+    data_z = rng.uniform(0.05, 1.05, n_attached)
+    centers = np.deg2rad(np.array([[25.0, -5.0], [45.0, -12.0], [58.0, 3.0]]))
+    gen = BoxRandoms(*box, weights=data_w, redshifts=data_z, seed=seed)
+    out = dict(box=box, data_w=data_w, data_z=data_z, patch_centers=centers, seed=np.array(seed), num=np.array(num),
+               chunksize=np.array(chunksize))
+    chunk = gen(first_call)
+    for name in ("ra", "dec", "weights", "redshifts"):
+        out[f"first.{name}"] = np.asarray(chunk[name], dtype=np.float64)
+    rand = yaw.Catalog.from_random(os.path.join(tmp, "random_box"), gen, num, patch_centers=AngularCoordinates(centers),
+                                   chunksize=chunksize, overwrite=True, max_workers=1)  # sequential: chunks in order
+    out["end_state"] = state_words(gen.rng.bit_generator.state)
+    for i in range(rand.num_patches):  # a digest of every record and a sample of them: the catalogue itself is 1.6 MB
+        patch = rand[i]
+        ra, dec = patch.coords.ra, patch.coords.dec
+        order = np.argsort(ra, kind="stable")  # the reference orders a patch by an unstable argsort: compare in ra order
+        out[f"patch_{i}.sha256"] = np.array(records_sha256(ra, patch.weights, patch.redshifts))
+        sample = order[::RANDOM_BOX_SAMPLE]
+        out[f"patch_{i}.sample.ra"], out[f"patch_{i}.sample.dec"] = ra[sample], dec[sample]
+    catalog_meta("random.meta", rand, out)
+
+    frame = box_catalog_frame(rng, 1000, box[0], box[1], box[2], box[3], redshifts=True, weights=True)
+    data = yaw.Catalog.from_dataframe(os.path.join(tmp, "random_box_data"), frame, ra_name="ra", dec_name="dec",
+                                      weight_name="w", redshift_name="z", patch_centers=AngularCoordinates(centers),
+                                      overwrite=True)
+    frame_arrays("data", frame, out)
+    config = yaw.Configuration.create(rmin=[5.0, 20.0], rmax=[30.0, 90.0], unit="arcmin", zmin=0.1, zmax=1.0, num_bins=4)
+    out["config.rmin"], out["config.rmax"] = np.array([5.0, 20.0]), np.array([30.0, 90.0])
+    for s, cf in enumerate(yaw.autocorrelate(config, data, rand, count_rr=True)):
+        for kind in ("dd", "dr", "rr"):
+            nc = getattr(cf, kind)
+            out[f"auto.s{s}.{kind}.counts"] = nc.counts.counts.sum(axis=(1, 2))  # per redshift bin
+            out[f"auto.s{s}.{kind}.sum_weights1"] = nc.sum_weights.sum_weights1
+            out[f"auto.s{s}.{kind}.sum_weights2"] = nc.sum_weights.sum_weights2
+    save("random_box.npz", **out)
+
+
 def main():
     tmp = tempfile.mkdtemp(prefix="yawgolden_", dir="/dev/shm")
     try:
@@ -386,6 +454,9 @@ def main():
         if "--ourcache-readback" in sys.argv:
             make_ourcache_readback(tmp)
             return
+        if "--random-box" in sys.argv:
+            make_random_box(tmp)
+            return
         make_refcache(tmp)
         make_greatcircle()
         make_single_job()
@@ -393,6 +464,7 @@ def main():
         make_2dflens(tmp)
         make_refcache_counts(tmp)
         make_ourcache_readback(tmp)
+        make_random_box(tmp)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

@@ -22,6 +22,7 @@ from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc
 from .measurements import PatchLinkage, autocorrelate, crosscorrelate
+from . import randoms
 from .paircounts import NormalisedCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import RedshiftData
 
@@ -45,4 +46,5 @@ __all__ = [
     "SampledData",
     "autocorrelate",
     "crosscorrelate",
+    "randoms",
 ]

@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "yawhip_count_pairs_rows_device",
     "yawhip_job_work",
     "yawhip_assign_patches",
+    "yawhip_random_box",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
 )
@@ -211,6 +212,11 @@ def load_library() -> ctypes.CDLL:
         ctypes.c_int64, _i32p, ctypes.POINTER(_vp), ctypes.POINTER(_Stats),
     ]
     lib.yawhip_assign_patches.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, ctypes.c_int32, _dp, _i32p]
+    lib.yawhip_random_box.argtypes = [
+        _vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_uint32, ctypes.c_double,
+        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p,
+        ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
+    ]
     lib.yawhip_job_work.argtypes = [
         _vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _i64p,
     ]
@@ -469,6 +475,40 @@ def job_work(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, jobs, threshold
         "yawhip_job_work",
     )
     return work
+
+
+RANDOM_MAX_DATA = 1 << 32  # yawhip_random_box: most attached values (numpy's 32-bit bounded-integer path)
+
+
+def random_box(ctx: Context, n: int, chunksize: int, state: dict, x_min: float, x_range: float, y_min: float, y_range: float,
+               n_data: int = -1, data_w=None, data_z=None, *, want_idx: bool = False):
+    """Run ``yawhip_random_box``: ``n`` values of BoxRandoms drawn in chunks of ``chunksize`` from numpy's PCG64 stream.
+    ``state`` is ``Generator.bit_generator.state`` before the first chunk. Returns ``(x, y, w, z, idx, end_state)``: float64[n]
+    columns (``w`` / ``z`` None without ``data_w`` / ``data_z``), int64[n] indices (None unless ``want_idx``) and the
+    bit-generator state numpy is left in after the same draws."""
+    if state.get("bit_generator") != "PCG64":
+        raise ValueError("yawhip_random_box follows numpy's PCG64 stream only")
+    data_w, data_z = _f64(data_w), _f64(data_z)
+    n = int(n)
+    x, y = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+    w = None if data_w is None else np.empty(n, dtype=np.float64)
+    z = None if data_z is None else np.empty(n, dtype=np.float64)
+    idx = np.empty(n, dtype=np.int64) if want_idx else None
+    mask = (1 << 64) - 1
+    s, inc = int(state["state"]["state"]), int(state["state"]["inc"])
+    words = (ctypes.c_uint64 * 4)(s >> 64, s & mask, inc >> 64, inc & mask)
+    out = (ctypes.c_uint64 * 2)()
+    has_out, uint_out = ctypes.c_int32(0), ctypes.c_uint32(0)
+    _check(
+        load_library().yawhip_random_box(
+            ctx._h, n, int(chunksize), words, int(state["has_uint32"]), int(state["uinteger"]), float(x_min), float(x_range),
+            float(y_min), float(y_range), int(n_data), _ptr(data_w, _dp), _ptr(data_z, _dp), _ptr(x, _dp), _ptr(y, _dp),
+            _ptr(w, _dp), _ptr(z, _dp), _ptr(idx, _i64p), out, ctypes.byref(has_out), ctypes.byref(uint_out)),
+        "yawhip_random_box",
+    )
+    end = {"bit_generator": "PCG64", "state": {"state": (int(out[0]) << 64) | int(out[1]), "inc": inc},
+           "has_uint32": int(has_out.value), "uinteger": int(uint_out.value)}
+    return x, y, w, z, idx, end
 
 
 def group_columns(keys, num_groups: int, columns, n_threads: int = 0):

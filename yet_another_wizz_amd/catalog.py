@@ -47,6 +47,7 @@ def _stable_argsort_small(keys, num_values: int):
 
 DEVICE_ASSIGN_MIN = 200_000  # below this the host is as fast as a round trip to the device
 HOST_GROUP_MIN = 200_000     # below this numpy's argsort + gathers are as fast as the library's threaded counting sort
+RANDOM_CHUNKSIZE = 16_777_216  # values per generator call of from_random (the reference's CHUNKSIZE, readers.py:49)
 
 
 def nearest_center(xyz, centers_xyz, chunk: int = 1 << 18):
@@ -476,6 +477,51 @@ class Catalog(Mapping):
         return cls.from_dataframe(cache_directory, frame, ra_name=ra_name, dec_name=dec_name, weight_name=weight_name,
                                   redshift_name=redshift_name, patch_centers=patch_centers, patch_name=patch_name,
                                   patch_num=patch_num, kappa_name=kappa_name, degrees=degrees, **kwargs)
+
+    @classmethod
+    def from_random(cls, cache_directory, generator, num_randoms: int, *, patch_centers=None, patch_num: int | None = None,
+                    overwrite: bool = False, progress: bool = False, max_workers: int | None = None,
+                    chunksize: int | None = None, probe_size: int = -1):
+        """Same signature as ``yaw.Catalog.from_random`` (catalog.py:1245-1340): ``num_randoms`` points of ``generator``
+        (a :class:`~yet_another_wizz_amd.randoms.BoxRandoms`), drawn from its reseeded stream in calls of ``chunksize``
+        (default 16 777 216, readers.py:49) -- the reference's catalogue for the same seed, and the generator is left in
+        the reference's end state. A ``BoxRandoms`` is drawn on the GPU when there is one (``engine.draw_box_randoms``,
+        the same values), otherwise chunk by chunk on the host; ``dec = arcsin(y)`` is taken on the host either way.
+        The columns then go through ``from_arrays``. ``patch_num`` runs this package's k-means (as ``from_dataframe``
+        does), whose centres differ from the treecorr centres of the reference; pass ``patch_centers`` for the
+        reference's patches. ``progress`` and ``max_workers`` are accepted for compatibility and have no effect."""
+        from .randoms import BoxRandoms
+
+        num = int(num_randoms)
+        if num < 1:
+            raise ValueError("catalogue is empty")
+        if patch_centers is None and patch_num is None:
+            raise ValueError("no patch method specified")
+        chunksize = int(chunksize or RANDOM_CHUNKSIZE)
+        generator.reseed()
+        drawn = None
+        if type(generator) is BoxRandoms:
+            from . import engine
+
+            drawn = engine.draw_box_randoms(generator, num, chunksize)
+        if drawn is not None:
+            (ra, y, weights, redshifts), _ = drawn
+            dec = np.empty_like(y)
+            for lo in range(0, num, chunksize):  # numpy's arcsin on the same slices as the reference's chunks
+                np.arcsin(y[lo : lo + chunksize], out=dec[lo : lo + chunksize])
+            route = "device"
+        else:
+            chunks = [generator(min(chunksize, num - lo)) for lo in range(0, num, chunksize)]
+
+            def joined(name):
+                return np.concatenate([c[name] for c in chunks]) if name in chunks[0] else None
+
+            ra, dec, weights, redshifts = joined("ra"), joined("dec"), joined("weights"), joined("redshifts")
+            route = "host"
+        new = cls.from_arrays(ra, dec, weights=weights, redshifts=redshifts, patch_centers=patch_centers, patch_num=patch_num,
+                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size)
+        new._random_route = route
+        return new
 
     # ------------------------------------------------------------------ mapping interface
     def __len__(self) -> int:

@@ -57,6 +57,7 @@
 #include <vector>
 
 #include "yawhip.h"
+#include "yawhip_random.h"
 #include "yawhip_sort.h"
 
 namespace {
@@ -4870,6 +4871,43 @@ int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const dou
     cleanup();
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_assign_patches failed: %s", hipGetErrorString(e));
+    return YAWHIP_OK;
+}
+
+int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
+                      double x_min, double x_range, double y_min, double y_range, int64_t n_data, const double *data_w,
+                      const double *data_z, double *x_out, double *y_out, double *w_out, double *z_out, int64_t *idx_out,
+                      uint64_t state_out[2], int32_t *has_uint32_out, uint32_t *uinteger_out) {
+    if (!ctx || !state || !state_out || !has_uint32_out || !uinteger_out)
+        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: NULL argument");
+    if (n < 0 || chunksize < 1) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n < 0 or chunksize < 1");
+    if (n_data > (int64_t)1 << 32)
+        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n_data = %lld > 2^32: numpy draws these indices from its 64-bit bounded "
+                    "path, which the device does not implement", (long long)n_data);
+    if (n_data == 0 || n_data < -1) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n_data must be -1 or 1 .. 2^32");
+    if (n_data == -1 && (data_w || data_z || idx_out))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: data arrays or indices without attached data (n_data = -1)");
+    if (!data_w != !w_out || !data_z != !z_out)
+        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: w_out / z_out must be given exactly with data_w / data_z");
+    if (n > 0 && (!x_out || !y_out)) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: x_out / y_out is NULL");
+    if ((state[3] & 1) == 0) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: the increment of a PCG64 state is odd");
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawrand::BoxDraw d;
+    d.n = n;
+    d.chunksize = chunksize;
+    d.state_hi = state[0], d.state_lo = state[1], d.inc_hi = state[2], d.inc_lo = state[3];
+    d.has_uint32 = has_uint32, d.uinteger = uinteger;
+    d.x_min = x_min, d.x_range = x_range, d.y_min = y_min, d.y_range = y_range;
+    d.n_data = n_data, d.data_w = data_w, d.data_z = data_z;
+    d.x_out = x_out, d.y_out = y_out, d.w_out = w_out, d.z_out = z_out, d.idx_out = idx_out;
+    yawrand::DrawEnd end;
+    const hipError_t e = yawrand::draw_box(ctx->stream, d, end);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_random_box failed: %s", hipGetErrorString(e));
+    state_out[0] = end.state_hi;
+    state_out[1] = end.state_lo;
+    *has_uint32_out = end.has_uint32;
+    *uinteger_out = end.uinteger;
     return YAWHIP_OK;
 }
 

@@ -14,7 +14,8 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "release", "default_kernel"]
+__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms",
+           "release", "default_kernel"]
 
 _contexts: dict = {}
 default_kernel = "auto"
@@ -188,3 +189,25 @@ def assign_patches(xyz, centers_xyz):
         x, y, z = (np.ascontiguousarray(xyz[:, a]) for a in range(3))
     ids = _lib.assign_patches(ctx, x, y, z, centers_xyz)
     return ids.astype(np.int64)
+
+
+def draw_box_randoms(generator, num: int, chunksize: int):
+    """``num`` points of a ``BoxRandoms`` drawn on the device (``yawhip_random_box``) in calls of ``chunksize`` from the
+    generator's current state, as ``Catalog.from_random`` calls it on the host. Returns ``((x, y, w, z), end_state)`` --
+    float64 host columns, ``w`` / ``z`` None without attached values, and the bit-generator state the calls end in, which
+    the generator is left in too -- or ``None`` when there is no library or device, or more than 2^32 attached values
+    (numpy's 64-bit bounded-integer path). Drawing randoms is catalogue preparation: like ``assign_patches`` it may fall
+    back to the host, the pair counts may not."""
+    if generator.data_size > _lib.RANDOM_MAX_DATA:
+        return None
+    try:
+        if _lib.device_count() < 1:
+            return None
+        ctx = get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+    x, y, w, z, _, end = _lib.random_box(
+        ctx, num, chunksize, generator.rng.bit_generator.state, generator.x_min, generator.x_max - generator.x_min,
+        generator.y_min, generator.y_max - generator.y_min, generator.data_size, generator.weights, generator.redshifts)
+    generator.rng.bit_generator.state = end
+    return (x, y, w, z), end
