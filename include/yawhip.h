@@ -122,9 +122,15 @@ int yawhip_ctx_device_count(const yawhip_ctx *ctx, int *n);
  *   "band_cap"          entries per LDS stage of the band kernel (0 = auto; 192 / 288: float64 and fine-grid kernels;
  *                       320 / 512: float32 kernel -- the larger one when a lane tile's window is expected to need it)
  *   "kernel"            default yawhip_kernel of yawhip_count_pairs(kernel = AUTO)
- *   "strip_width_micro" spacing, in 1e-6 chord units, of the strip grid of catalogues uploaded afterwards
- *                       (0 = no strips, default 5000). Catalogues counted against each other should share it;
- *                       otherwise the cross-correlation path falls back to ordinary (job, bin) items.
+ *   "strip_width_micro" spacing, in 1e-6 rad of latitude (1e-6 chord units with strip_grid = 0), of the strip grid of
+ *                       catalogues uploaded afterwards (0 = no strips, default 5000). Catalogues counted against each other
+ *                       should share it; otherwise the cross-correlation path falls back to ordinary (job, bin) items.
+ *   "strip_grid"        strip grid of catalogues uploaded afterwards: 1 (default) uniform in the latitude of the object's
+ *                       direction about the strip axis, 0 linear in that coordinate (same results; catalogues counted
+ *                       against each other must share it for the strip path)
+ *   "band_trim"         1 (default): the strip item builder and the float32 band kernels cut every u-window and band to the
+ *                       u-range the lane objects' largest separation angle can reach on the sphere; 0: +/- sqrt(t_max)
+ *                       around the keys (same results)
  *   "seg_strips"        binned x binned counts use the per-(patch, bin) strip layouts of dense catalogues (default 1)
  *   "seg_strips_min_run" mean objects per (patch, bin, strip) run of the lane-side catalogue from which they are used (default 16)
  *   "debug_no_hits"     diagnostics: the pre-filter rejects everything (times the filter alone; wrong counts)

@@ -16,7 +16,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # YAW_AMD_LIB points experiments at a variant build (tools/build_variant.py); the product loads the in-tree library
 LIB_PATH = os.environ.get("YAW_AMD_LIB") or os.path.join(_PKG_DIR, "libyawhip.so")
 
-DEFAULT_STRIP_MICRO = 5000  # the library's default strip grid spacing, in 1e-6 chord units
+DEFAULT_STRIP_MICRO = 5000  # the library's default strip grid spacing, in 1e-6 rad of latitude (strip_grid = 1)
 KERNEL_AUTO, KERNEL_EXACT, KERNEL_FILTER, KERNEL_SWEEP, KERNEL_BAND = 0, 1, 2, 3, 4
 KERNEL_IDS = {"auto": KERNEL_AUTO, "exact": KERNEL_EXACT, "filter": KERNEL_FILTER, "sweep": KERNEL_SWEEP,
               "band": KERNEL_BAND}
@@ -278,12 +278,15 @@ class Context:
             self.devices = (int(device),)
         self.device = self.devices[0]
         self.strip_micro = DEFAULT_STRIP_MICRO
+        self.strip_grid = 1  # the library's default: strip grid uniform in latitude
         self._catalogs = weakref.WeakSet()  # live catalogues: freed before the context (a catalogue's free reads its context)
 
     def set_option(self, key: str, value: int) -> None:
         _check(load_library().yawhip_ctx_set_option(self._h, key.encode(), int(value)), "yawhip_ctx_set_option")
         if key == "strip_width_micro":
             self.strip_micro = int(value)
+        elif key == "strip_grid":
+            self.strip_grid = int(value)
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
@@ -304,8 +307,9 @@ class DeviceCatalog:
 
     def __init__(self, ctx: Context, x, y, z, w, n_patches: int, n_bins_or_1: int, offsets, sort_axis: int = 2,
                  strip_micro: int | None = None):
-        """``strip_micro``: spacing of the strip grid of the cross-correlation layout in 1e-6 chord
-        units (0 = no strips, None = whatever the context is set to)."""
+        """``strip_micro``: spacing of the strip grid of the cross-correlation layout in 1e-6 rad of
+        latitude -- 1e-6 chord units where the context's ``strip_grid`` option is 0 (linear in v) --
+        (0 = no strips, None = whatever the context is set to)."""
         x, y, z, w = _f64(x), _f64(y), _f64(z), _f64(w)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(x)
@@ -321,6 +325,7 @@ class DeviceCatalog:
             ctx.set_option("strip_width_micro", int(strip_micro))
             ctx.strip_micro = int(strip_micro)
         self.strip_micro = ctx.strip_micro
+        self.strip_grid = ctx.strip_grid
         _check(
             load_library().yawhip_catalog_upload_axis(
                 ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), self.n_patches, self.n_bins,

@@ -147,6 +147,47 @@ struct alignas(16) ObjF {  // its float32 image for the pre-filter: one 16-byte 
 constexpr double FILTER_GUARD = 8.0 * 5.9604644775390625e-8;
 constexpr double UNIT_NORM_TOL = 1e-9;
 
+// ------------------------------------------------------------------------------------------------
+// Spherical caps (strip grid in latitude, trimmed u-bands; DESIGN.md sections 3 and 4).
+// A pair passes s <= t_max only if its chord |a - b| <= rwin = sqrt(t_max) (1 + 1e-12) + 1e-15 (the float64 rounding of s,
+// see k_build_items). The DIRECTIONS of a and b are then at most the angle sep_angle(rwin) apart: |a|^2 is within
+// UNIT_NORM_TOL of 1, so ||a| - 1| <= 5e-10 and |a^ - b^| <= |a - b| + 1e-9 (2e-9 is added). Two consequences:
+//   * latitudes about any axis (atan2(v, hypot(u, w)), the direction's own) differ by at most that angle: the strip grid of
+//     k_strip_index in latitude pairs runs whose grid indices differ by at most floor(theta / width) + 1;
+//   * with alpha = acos(u^) the polar angle of a about the sort axis, every partner has polar angle alpha -/+ theta, i.e.
+//     u^_b in [cos(min(pi, alpha + theta)), cos(max(0, alpha - theta))] = [u c - sqrt(1 - u^2) s, u c + sqrt(1 - u^2) s]
+//     (c = cos theta, s = sin theta), -1 below where alpha + theta > pi (u < -c), +1 above where alpha < theta (u > c).
+//     Both bounds are monotone in u, so the band of objects with keys in [u0, u1] runs from lo(u0) to hi(u1).
+// The bounds are culling bounds only: classification and the exact float64 path do not see them.
+inline double sep_angle(double rwin) { return 2.0 * std::asin(std::min(1.0, 0.5 * (rwin + 2e-9))); }
+
+// float64 (item builder): the key u is a float64 coordinate, |u - u^| <= 5e-10 (unit norm); shifting u by 1e-9 outward keeps
+// the exact bound below / above the one of u^, the clip decisions are widened by 1e-12 (rounding of cos theta), and the
+// result by 2e-9 (|u_b - u^_b| <= 5e-10 for the partner's key, plus the double-rounding of the formula, ~1e-15).
+__device__ __forceinline__ double cap_lo64(double u, double c, double s) {
+    const double ul = fmax(u - 1e-9, -1.0);
+    return ul <= -c + 1e-12 ? -1.0 - 2e-9 : fma(ul, c, -sqrt(fmax(fma(-ul, ul, 1.0), 0.0)) * s) - 2e-9;
+}
+__device__ __forceinline__ double cap_hi64(double u, double c, double s) {
+    const double uh = fmin(u + 1e-9, 1.0);
+    return uh >= c - 1e-12 ? 1.0 + 2e-9 : fma(uh, c, sqrt(fmax(fma(-uh, uh, 1.0), 0.0)) * s) + 2e-9;
+}
+// float32 (band kernels): the lane key u is the float32 image, |u - u^| <= 2^-25 + 5e-10 < 3.1e-8. Input shift 1e-7: the
+// rounding of u - 1e-7 (<= 6e-8) still leaves ul <= u^. Clip decisions widened by 1.2e-7 (c rounded to float32: 3e-8, and
+// the rounding of -c + 1.2e-7: 6e-8). The formula in float32: c and s rounded (6e-8 u, 6e-8 s), fma(-u, u, 1) one rounding
+// relative to 1 - u^2 and sqrtf within 2 ulp (together 2e-7 relative, times s), the product and the final fma (6e-8 each),
+// the margin's own subtraction (6e-8): at most 1.8e-7 + 3.2e-7 s; the partner's float32 image adds 3.1e-8. The margin
+// CAP32_MARGIN = 8e-7 covers s <= 1 (3e-4 of the band half width r at the headline's r = 2.9e-3).
+constexpr float CAP32_SHIFT = 1e-7f, CAP32_CLIP = 1.2e-7f, CAP32_MARGIN = 8e-7f;
+__device__ __forceinline__ float cap_lo32(float u, float c, float s) {
+    const float ul = fmaxf(u - CAP32_SHIFT, -1.0f);
+    return ul <= -c + CAP32_CLIP ? -1.0f - CAP32_MARGIN : fmaf(ul, c, -sqrtf(fmaxf(fmaf(-ul, ul, 1.0f), 0.0f)) * s) - CAP32_MARGIN;
+}
+__device__ __forceinline__ float cap_hi32(float u, float c, float s) {
+    const float uh = fminf(u + CAP32_SHIFT, 1.0f);
+    return uh >= c - CAP32_CLIP ? 1.0f + CAP32_MARGIN : fmaf(uh, c, sqrtf(fmaxf(fmaf(-uh, uh, 1.0f), 0.0f)) * s) + CAP32_MARGIN;
+}
+
 constexpr int MAX_WIN = 3;  // windows (partner runs of c1) one work item can carry
 struct alignas(16) Item {  // one unit of work for a workgroup: a lane tile of c2 and up to MAX_WIN windows of c1
     int64_t a0;    // first lane object (c2 side)
@@ -472,7 +513,8 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items(CatView c1, CatView c2
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *__restrict__ tabs, const JobRec *__restrict__ jobs,
                                                             const int64_t *__restrict__ prefix, int n_jobs, int reach,
-                                                            int tile, double rwin, int swap, int triple, int64_t n_pot,
+                                                            int tile, double rwin, double cap_c, double cap_s, int swap,
+                                                            int triple, int64_t n_pot,
                                                             Item *__restrict__ items, unsigned long long *__restrict__ counters,
                                                             unsigned char *__restrict__ kept, unsigned long long seg_cap) {
     // triple: the streamed side consists of merged triple runs (k_merge_triples) -- the host passes reach = 0 (one partner
@@ -534,7 +576,12 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
         const int64_t r2 = tr.run, a0 = tr.a0, a1 = a0 + tr.na;
         const double kpad = triple ? 1.2e-7 : 0.0;  // float32 rounding of a streamed key (|u| <= 1: 2^-24)
         // (half bands: no lane of the tile looks at an entry in front of the tile's first object -- the window starts there)
-        const double wlo = key2[a0] - (it.pad_ ? 0.0 : rwin) - kpad, whi = key2[a1 - 1] + rwin + kpad;
+        // cap_s > 0 (band_trim): the window is trimmed to the caps the tile's first and last objects can reach (sep_angle)
+        double wlo = key2[a0] - (it.pad_ ? 0.0 : rwin) - kpad, whi = key2[a1 - 1] + rwin + kpad;
+        if (cap_s > 0.0) {
+            if (!it.pad_) wlo = cap_lo64(key2[a0], cap_c, cap_s) - kpad;
+            whi = cap_hi64(key2[a1 - 1], cap_c, cap_s) + kpad;
+        }
         it.a0 = a0; it.na = tr.na; it.nwin = 0;
         it.slot = (int32_t)((unsigned)job | ((unsigned)o << 30)); it.pot = (int32_t)pot;
         // The windows of the (up to) three partner runs are searched in lockstep: three independent chains of loads per
@@ -1777,7 +1824,8 @@ __host__ __device__ inline size_t band32_fine_lds(bool weighted, int cap, int ns
 template <int R, int CAP, bool WEIGHTED, bool MERGED, bool UNI>
 __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
                                                           int n_edges, const double *__restrict__ t, const float *__restrict__ fine32,
-                                                          const double *__restrict__ rwin_k, unsigned flush_mask, int swap,
+                                                          const double *__restrict__ rwin_k, const float *__restrict__ ucap,
+                                                          unsigned flush_mask, int swap,
                                                           unsigned long long *__restrict__ out_counts,
                                                           double *__restrict__ partials,
                                                           unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
@@ -1864,6 +1912,11 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
                 if (r == last_r) u_last = cl.axis == 0 ? ax[r] : (cl.axis == 1 ? ay[r] : az[r]);
             klo = u_first - rwin;
             khi = u_last + rwin;
+            const float cap_c = ucap[2 * kfix], cap_s = ucap[2 * kfix + 1];  // band_trim, as in k_count_band32
+            if (cap_s > 0.0f) {
+                klo = cap_lo32(u_first, cap_c, cap_s);
+                khi = cap_hi32(u_last, cap_c, cap_s);
+            }
         }
         unsigned int nev = 0;
         auto flush_counts = [&]() {  // LDS histogram -> global result (unweighted)
@@ -2245,6 +2298,7 @@ struct CallBufs {
     View<float> d_dthr;
     View<float> d_thr32;
     View<double> d_rwin;
+    View<float> d_ucap;
     DevBuf<Item> d_items;
     View<unsigned long long> d_ctr;
     View<unsigned long long> d_counts;
@@ -2336,7 +2390,9 @@ struct yawhip_ctx : CallBufs {
     int triple_runs = 1;     // float32 band kernels stream merged triple runs (k_merge_triples) when the partner strips are c - 1, c, c + 1
     int band_fp32 = 1;       // band kernel on strip layouts of unit vectors: float32 classification + exact float64 for the
                              // guard bands (k_count_band32); 0: every entry in float64 (k_count_band)
-    double strip_width = 0.005;  // strip grid of newly uploaded catalogues (chord units, ~17 arcmin); 0 = no strips
+    double strip_width = 0.005;  // strip grid of newly uploaded catalogues (strip_grid units, ~17 arcmin); 0 = no strips
+    int strip_grid = 1;          // strip grid of newly uploaded catalogues: 1 = uniform in latitude (radians), 0 = linear in v (chord units)
+    int band_trim = 1;           // strip builder and float32 band kernels trim u-windows and bands to the reachable caps (sep_angle)
     int default_kernel = YAWHIP_KERNEL_AUTO;
     int lds_limit = 160 * 1024;
     int n_cu = 256;
@@ -2430,7 +2486,8 @@ struct yawhip_catalog {
     StripLayout strips[3], seg[3];
     std::vector<yawhip_catalog *> replicas;  // copies on ctx->peers (multi-device contexts), same order
     bool has_strips = false;          // strip layouts can be built (unit vectors, n > 0)
-    double strip_width = 0.0;         // grid spacing (chord units); 0 = one run per patch
+    double strip_width = 0.0;         // grid spacing (strip_grid units); 0 = one run per patch
+    int strip_grid = 0;               // 1: grid index floor((latitude + pi/2) / spacing), 0: floor((v + 1) / spacing) (k_strip_index)
     std::vector<double> h_box;        // [P][6] bounding box of every patch: min x, y, z, max x, y, z (empty patch: +4 / -4)
 };
 
@@ -2554,15 +2611,19 @@ __global__ void k_same_bin_neighbours(int64_t n, const int32_t *__restrict__ bin
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__popcll(m));
 }
 
-// grid index floor((v + 1) / width) of every object (0 without strips) and the occupied range per patch
-__global__ void k_strip_index(int64_t n, const double *__restrict__ v, double width, const int64_t *__restrict__ poff,
-                              int n_patches, int32_t *__restrict__ gidx, int32_t *__restrict__ lohi) {
+// grid index of every object (0 without strips) and the occupied range per patch: floor((v + 1) / width) (lat = 0), or
+// floor((latitude + pi/2) / width) with the latitude atan2(v, hypot(u, w)) of the object's direction (lat = 1, sep_angle)
+__global__ void k_strip_index(int64_t n, const double *__restrict__ v, const double *__restrict__ u, const double *__restrict__ w,
+                              double width, int lat, const int64_t *__restrict__ poff, int n_patches, int32_t *__restrict__ gidx,
+                              int32_t *__restrict__ lohi) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool ok = i < n;
     int32_t g = 0;
     int p = -1;
     if (ok) {
-        g = width > 0.0 ? (int32_t)floor((v[i] + 1.0) / width) : 0;
+        const double vi = v[i];
+        if (width > 0.0)
+            g = lat ? (int32_t)floor((atan2(vi, hypot(u[i], w[i])) + 1.5707963267948966) / width) : (int32_t)floor((vi + 1.0) / width);
         gidx[i] = g;
         p = segment_of(poff, n_patches, i);
     }
@@ -2711,7 +2772,8 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     if (e != hipSuccess) return bail(e, "strip tables");
     const unsigned ngrid = (unsigned)((n1 + 255) / 256);
     // grid index of every object, first / last occupied strip of every group
-    hipLaunchKernelGGL(k_strip_index, dim3(ngrid), dim3(256), 0, ctx->stream, n, key_of(c->x, c->y, c->z, saxis), width, poff,
+    hipLaunchKernelGGL(k_strip_index, dim3(ngrid), dim3(256), 0, ctx->stream, n, key_of(c->x, c->y, c->z, saxis),
+                       key_of(c->x, c->y, c->z, (saxis + 1) % 3), key_of(c->x, c->y, c->z, (saxis + 2) % 3), width, c->strip_grid && !seg ? 1 : 0, poff,
                        n_groups, gidx, lohi);
     e = hipMemcpyAsync(h_lohi.data(), lohi, (size_t)2 * n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -2977,7 +3039,13 @@ int yawhip_ctx_set_option(yawhip_ctx *ctx, const char *key, int64_t value) {
             return fail(YAWHIP_ERR_INVALID, "band_cap must be 0 (auto), 192 or 288 (float64 / fine-grid band kernels), %d or %d (float32 band kernel)",
                         B32_CAP, B32_CAP_BIG);
         number(&yawhip_ctx::band_cap);
-    } else if (!strcmp(key, "strip_width_micro")) {  // strip grid spacing in units of 1e-6 (0 = off)
+    } else if (!strcmp(key, "strip_grid")) {  // 1: latitude, 0: linear in v (catalogues uploaded afterwards)
+        if (value != 0 && value != 1) return fail(YAWHIP_ERR_INVALID, "strip_grid must be 0 (linear in v) or 1 (latitude)");
+        number(&yawhip_ctx::strip_grid);
+    } else if (!strcmp(key, "band_trim")) {
+        if (value != 0 && value != 1) return fail(YAWHIP_ERR_INVALID, "band_trim must be 0 or 1");
+        number(&yawhip_ctx::band_trim);
+    } else if (!strcmp(key, "strip_width_micro")) {  // strip grid spacing in units of 1e-6 rad (latitude grid) or chord (0 = off)
         if (value != 0 && (value < 1000 || value > 2000000))
             return fail(YAWHIP_ERR_INVALID, "strip_width_micro must be 0 (off) or in [1e3, 2e6]");
         set = [=](yawhip_ctx &c) { c.strip_width = (double)value * 1e-6; };
@@ -3127,6 +3195,7 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
     for (size_t i = 0; i < c->h_box.size(); ++i) c->h_box[i] = double_of(h_box[i]);
     c->device_bytes = (int64_t)col * (w ? 4 : 3) + (nseg + 1) * (int64_t)sizeof(int64_t);
     c->strip_width = ctx->strip_width;
+    c->strip_grid = ctx->strip_grid;
     c->has_strips = c->unit_norm && n > 0;
     if (c->has_strips) {
         const int rc = build_strip_layout(ctx, c, sort_axis, false);
@@ -3321,11 +3390,12 @@ struct HostPlan {
          weighted = false, weighted_any = false;
     int64_t abytes = 0, cand = 0, n_items = 0, n_out = 0, n_pslots = 0, n_sjobs = 0, n_slots = 0, slab = 0, tile = 0;
     double rwin_max = 0.0;
+    double cap_c = 1.0, cap_s = 0.0;  // cos / sin of sep_angle(rwin_max): the strip builder's trimmed windows (cap_s = 0: untrimmed)
     size_t lds_band = 0, lds_merged = 0;
     // device tables (one allocation): jobs / job records, prefix, thresholds, pre-filter thresholds, window widths, float32
     // classes, layout table, and -- weighted calls -- the chunk prefix of the slab reduction
     unsigned char *d_in = nullptr;
-    size_t o_jobs = 0, o_prefix = 0, o_t = 0, o_dthr = 0, o_rwin = 0, o_thr32 = 0, o_tabs = 0, o_cprefix = 0;
+    size_t o_jobs = 0, o_prefix = 0, o_t = 0, o_dthr = 0, o_rwin = 0, o_ucap = 0, o_thr32 = 0, o_tabs = 0, o_cprefix = 0;
     int64_t n_chunks = 0, n_oslots = 0;
     ~HostPlan() { if (d_in) (void)hipFree(d_in); }
 };
@@ -3408,8 +3478,11 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
         rwin_max = std::max(rwin_max, std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15);
     // strip pairing pays while a run has few partner runs; for separations far beyond the grid spacing the
     // ordinary (patch, bin) layout is used instead
+    // (grid_sep: the largest separation in the grid's own unit -- chord for a grid linear in v, angle for one in latitude)
+    const double grid_sep = c1->strip_grid ? sep_angle(rwin_max) : rwin_max;
     const bool strips = lean && c1->has_strips && c2->has_strips && c1->strip_width == c2->strip_width &&
-                        (c1->strip_width <= 0.0 || rwin_max / c1->strip_width <= (double)MAX_STRIP_REACH);
+                        c1->strip_grid == c2->strip_grid &&
+                        (c1->strip_width <= 0.0 || grid_sep / c1->strip_width <= (double)MAX_STRIP_REACH);
     // mode 3: binned x binned on the per-segment strip layouts: ordinary (job, bin) items whose lane tiles and windows
     // come from (patch, bin, strip) runs -- it pays when the lane side is dense: runs of at least a few lane tiles per
     // (patch, bin, strip); estimated from the patch-level layout the upload built (B times as many runs)
@@ -3429,6 +3502,9 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
                               (size_t)n_bins * sizeof(float) + BandLds<BCAP_MID>::FIXED + (BCAP_MID + 2) * 8 + 2 * MSTAGE * sizeof(ObjF) + 1024;
     const bool merged_fits = merged_lds <= (size_t)ctx->lds_limit;
     const int mode = !strips ? 0 : (c1->nb > 1 && c2->nb == 1) ? (merged_fits ? 1 : 0) : (seg_ok ? 3 : 0);
+    // per-segment strip layouts keep the grid linear in v (build_strip_layout): their short runs make items of fixed cost, and
+    // the latitude grid's narrower strips away from v = 0 only add items there
+    const double layout_sep = mode == 3 ? rwin_max : grid_sep;
     const bool merged = mode == 1;                // one item covers all bins, output slot = job
     const bool strip_items = mode != 0;           // items come from strip runs (k_build_items_strips)
     // Orientation of every job: the (u, v) projection that compresses the sphere least around its two patches, i.e.
@@ -3565,7 +3641,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // searches one window per item instead of three (0.045 against 0.063 ms).
     bool triple = false;
     if ((band32 || band_fine) && strip_items && ctx->triple_runs && c_strm->n < (1ll << 31) && c1->strip_width > 0.0 &&
-        (int)std::floor(rwin_max / c1->strip_width + 1e-6) + 1 == 1) {
+        (int)std::floor(layout_sep / c1->strip_width + 1e-6) + 1 == 1) {
         const double est3 = 3.0 * est_window;
         triple = ctx->triple_runs == 2 ||
                  (band32 ? est3 <= 0.88 * (B32_CAP_BIG - 4) : est3 <= 0.9 * BCAP_MID);
@@ -3647,8 +3723,8 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     const bool half_ok = band32 && triple && R == 1 && c1 == c2 && !swap && ctx->half_bands != 0 && !for_work;
     if (strip_items) {
         const double width = c1->strip_width;
-        // |dv| <= rwin_max  ->  grid indices differ by at most floor(rwin_max / width) + 1
-        reach = width > 0.0 ? (int)std::floor(rwin_max / width + 1e-6) + 1 : 0;
+        // |dv| <= rwin_max (|d latitude| <= sep_angle(rwin_max))  ->  grid indices differ by at most floor(layout_sep / width) + 1
+        reach = width > 0.0 ? (int)std::floor(layout_sep / width + 1e-6) + 1 : 0;
         sjobs.resize((size_t)2 * n_sjobs);
         for (int j = 0; j < n_jobs; ++j)
             for (int k = 0; k < (mode == 3 ? n_bins : 1); ++k) {
@@ -3729,6 +3805,15 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     std::vector<double> rwin((size_t)n_bins);
     for (int k = 0; k < n_bins; ++k) rwin[(size_t)k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
     if (merged) rwin[0] = rwin_max;  // one window for all bins of the merged run
+    // band_trim: {cos, sin} of the largest separation angle per row of rwin, float32 for the band kernels ({1, 0}: untrimmed).
+    // The caps assume |a|^2 within UNIT_NORM_TOL of 1 (sep_angle).
+    const bool trim = ctx->band_trim && c1->unit_norm && c2->unit_norm;
+    std::vector<float> ucap((size_t)2 * n_bins);
+    for (int k = 0; k < n_bins; ++k) {
+        const double th = sep_angle(rwin[(size_t)k]);
+        ucap[(size_t)2 * k] = trim ? (float)std::cos(th) : 1.0f;
+        ucap[(size_t)2 * k + 1] = trim ? (float)std::sin(th) : 0.0f;
+    }
     // A weighted call keeps one slab of partial sums per potential item; long job lists of big catalogues would need
     // tens of GB (50M x 50M, three scales: 40 GB). Above the budget -- and when the items no longer fit 31 bits -- the
     // caller cuts the job list in two and counts the halves one after the other (rows of the result are independent).
@@ -3770,6 +3855,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     const size_t o_t = take((size_t)n_bins * n_edges * sizeof(double));
     const size_t o_dthr = take((size_t)3 * n_bins * sizeof(float));
     const size_t o_rwin = take((size_t)n_bins * sizeof(double));
+    const size_t o_ucap = take((size_t)2 * n_bins * sizeof(float));
     const std::vector<float> thr32 = band32 ? build_thr32(t, n_bins, n_edges) : (band_fine ? fine32 : std::vector<float>());
     const size_t o_thr32 = take(thr32.size() * sizeof(float));
     const size_t o_tabs = take(sizeof h_tabs);
@@ -3792,12 +3878,13 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     memcpy(image.data() + o_t, t, sizeof(double) * n_bins * n_edges);
     memcpy(image.data() + o_dthr, dthr.data(), sizeof(float) * 3 * n_bins);
     memcpy(image.data() + o_rwin, rwin.data(), sizeof(double) * n_bins);
+    memcpy(image.data() + o_ucap, ucap.data(), sizeof(float) * 2 * n_bins);
     if (!thr32.empty()) memcpy(image.data() + o_thr32, thr32.data(), sizeof(float) * thr32.size());
     memcpy(image.data() + o_tabs, h_tabs, sizeof h_tabs);
     if (!cprefix.empty()) memcpy(image.data() + o_cprefix, cprefix.data(), sizeof(int64_t) * cprefix.size());
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&P.d_in), std::max<size_t>(off_in, 16)));
     HIP_TRY(hipMemcpy(P.d_in, image.data(), off_in, hipMemcpyHostToDevice));  // once per plan
-    P.o_jobs = o_jobs; P.o_prefix = o_prefix; P.o_t = o_t; P.o_dthr = o_dthr; P.o_rwin = o_rwin; P.o_thr32 = o_thr32;
+    P.o_jobs = o_jobs; P.o_prefix = o_prefix; P.o_t = o_t; P.o_dthr = o_dthr; P.o_rwin = o_rwin; P.o_ucap = o_ucap; P.o_thr32 = o_thr32;
     P.o_tabs = o_tabs; P.o_cprefix = o_cprefix;
     P.n_chunks = cprefix.empty() ? 0 : cprefix.back();
     P.n_oslots = n_oslots;
@@ -3846,6 +3933,10 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     P.run_unweighted = run_unweighted;
     P.run_weighted = run_weighted;
     P.rwin_max = rwin_max;
+    if (trim) {
+        P.cap_c = std::cos(sep_angle(rwin_max));
+        P.cap_s = std::sin(sep_angle(rwin_max));
+    }
     P.slab = slab;
     P.strip_items = strip_items;
     P.swap = swap;
@@ -3911,6 +4002,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     ctx->d_t.ptr = reinterpret_cast<double *>(P.d_in + P.o_t);
     ctx->d_dthr.ptr = reinterpret_cast<float *>(P.d_in + P.o_dthr);
     ctx->d_rwin.ptr = reinterpret_cast<double *>(P.d_in + P.o_rwin);
+    ctx->d_ucap.ptr = reinterpret_cast<float *>(P.d_in + P.o_ucap);
     ctx->d_thr32.ptr = reinterpret_cast<float *>(P.d_in + P.o_thr32);
     ctx->d_tabs.ptr = reinterpret_cast<DevTab *>(P.d_in + P.o_tabs);
     ctx->d_cprefix.ptr = reinterpret_cast<int64_t *>(P.d_in + P.o_cprefix);
@@ -3950,7 +4042,8 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         if (P.strip_items)
             hipLaunchKernelGGL(k_build_items_strips, dim3(bgrid), dim3(bwg), 0, ctx->stream, ctx->d_tabs.ptr,
                                reinterpret_cast<const JobRec *>(ctx->d_jobs.ptr), ctx->d_prefix.ptr, (int)P.n_sjobs,
-                               P.triple ? 0 : P.reach, (int)P.tile, P.rwin_max, P.swap ? 1 : 0, P.triple ? 1 : 0, n_pot, ctx->d_items.ptr,
+                               P.triple ? 0 : P.reach, (int)P.tile, P.rwin_max, P.cap_c, P.cap_s, P.swap ? 1 : 0, P.triple ? 1 : 0,
+                               n_pot, ctx->d_items.ptr,
                                ctx->d_ctr.ptr, kept_flags, seg_cap);
         else if (P.sweep)
             hipLaunchKernelGGL(k_build_items<true>, dim3(bgrid), dim3(bwg), 0, ctx->stream, view_of(c1), view_of(c2),
@@ -4041,7 +4134,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                                               : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
                         cs.variant[w] = variant_code(one_chunk ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
                         return launch(kern, band_grid, wave, lds, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, ctx->d_t.ptr,
-                                      ctx->d_thr32.ptr, ctx->d_rwin.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr,
+                                      ctx->d_thr32.ptr, ctx->d_rwin.ptr, ctx->d_ucap.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr,
                                       ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
                     });
                 });
@@ -4074,7 +4167,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                     cs.variant[w] = variant_code(VF_BAND32_FINE, S::R, S::CAP, w, 0, M::MERGED, M::UNI);
                     return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, lds, ctx->stream,
                                   ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr,
-                                  flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
+                                  ctx->d_ucap.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
                 });
             });
         });

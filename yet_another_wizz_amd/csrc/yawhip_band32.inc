@@ -6,7 +6,8 @@
 template <int R, int CAP, bool WEIGHTED, int NE, bool MERGED, bool UNI>
 __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 && UNI ? (WEIGHTED ? (R == 1 ? YAW_B32_WAVES_W1 : YAW_B32_WAVES_W) : (CAP >= YAW_B32_CAP_BIG ? YAW_B32_WAVES_BIG : 7)) : (NE == 2 && !WEIGHTED ? YAW_B32_WAVES_LT : 1)))) void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
                                                      const double *__restrict__ t, const float *__restrict__ thr32,
-                                                     const double *__restrict__ rwin_k, unsigned flush_mask, int swap,
+                                                     const double *__restrict__ rwin_k, const float *__restrict__ ucap,
+                                                     unsigned flush_mask, int swap,
                                                      unsigned long long *__restrict__ out_counts,
                                                      double *__restrict__ partials,
                                                      unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
@@ -184,6 +185,12 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                 if (r == last_r) u_last = cl.axis == 0 ? ax[r] : (cl.axis == 1 ? ay[r] : az[r]);
             klo = u_first - rwin;
             khi = u_last + rwin;
+            // band_trim: the caps the lane's first and last objects can reach (sep_angle; lanes without an object walk nothing)
+            const float cap_c = ucap[2 * kfix], cap_s = ucap[2 * kfix + 1];
+            if (cap_s > 0.0f) {
+                klo = cap_lo32(u_first, cap_c, cap_s);
+                khi = cap_hi32(u_last, cap_c, cap_s);
+            }
         }
         if constexpr (R >= 2) {
 #pragma unroll

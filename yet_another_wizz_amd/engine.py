@@ -64,16 +64,16 @@ _strip_micro_cache: dict = {}
 
 
 def strip_micro_for(thresholds) -> int:
-    """Spacing of the strip grid (1e-6 chord units) that suits the widest separation of a threshold
-    table: just above the largest chord, so that a run has partners in three strips only and those are
-    as narrow as possible. Measured on the 10M x 10M headline (chord 2909): 2950 -> 2.09 ms per step,
+    """Spacing of the strip grid (1e-6 rad of latitude) that suits the widest separation of a threshold
+    table: just above the largest separation angle, so that a run has partners in three strips only and
+    those are as narrow as possible. Measured on the 10M x 10M headline (chord 2909): 2950 -> 2.09 ms per step,
     3600 -> 2.16, 4400 -> 2.21, 5200 -> 2.28; below the chord five strips take part (2000: 30 % slower)."""
     key = (id(thresholds), thresholds.shape)
     hit = _strip_micro_cache.get(key)
     if hit is not None and hit[0] is thresholds:  # threshold tables are built once per configuration and never modified
         return hit[1]
-    r = float(np.sqrt(np.max(thresholds)))
-    micro = int(min(max(np.ceil(1.02e6 * r / 50.0) * 50.0, 1000), 100000))
+    theta = 2.0 * float(np.arcsin(min(1.0, 0.5 * float(np.sqrt(np.max(thresholds))))))  # chord -> angle
+    micro = int(min(max(np.ceil(1.02e6 * theta / 50.0) * 50.0, 1000), 100000))
     if len(_strip_micro_cache) > 16:
         _strip_micro_cache.clear()
     _strip_micro_cache[key] = (thresholds, micro)
@@ -89,7 +89,7 @@ def device_catalog(layout, ctx=None, sort_axis: int = 2, strip_micro: int | None
     ctx = ctx or get_context()
     dev = layout.device.get(id(ctx))
     if dev is not None:
-        stale = dev.sort_axis != sort_axis
+        stale = dev.sort_axis != sort_axis or dev.strip_grid != ctx.strip_grid
         if strip_micro is not None and not stale:
             have = dev.strip_micro
             stale = have != strip_micro if (exact or have == 0 or strip_micro == 0) else \
