@@ -133,13 +133,17 @@ def test_random_measurements_device_vs_oracle(seed, monkeypatch):
     assert total > 1000
 
 
-@pytest.mark.parametrize("tag,cfg", [("w", "s2"), ("u", "rw"), ("w", "rw")])
-def test_batch_submission_equals_single_calls_bit_for_bit(tag, cfg):
+@pytest.mark.parametrize("tag,cfg,slab_budget", [("w", "s2", None), ("u", "rw", None), ("w", "rw", None), ("w", "rw", 4096)],
+                         ids=["w-s2", "u-rw", "w-rw", "w-rw-split"])
+def test_batch_submission_equals_single_calls_bit_for_bit(tag, cfg, slab_budget):
     """``yawhip_count_pairs_dense_batch`` (ABI 5; DD, DR, RD, RR of a cross-correlation and DD, DR, RR of an autocorrelation
     as ONE submission, src/yaw/correlation/measurements.py:617-628,517-523) returns what as many single
     ``yawhip_count_pairs_dense`` calls return -- every tensor bit for bit, weighted sums included -- with one fine bin per
-    scale (values scattered from the slot's result block) and with separation weights (recombined on the device)."""
+    scale (values scattered from the slot's result block) and with separation weights (recombined on the device).
+    With a ``slab_budget_bytes`` far below one job's slabs, the batch's weighted requests are counted in pieces (the blocking
+    route: fine values on the host, recombined there): still bit for bit what the unsplit single calls return."""
     import yet_another_wizz_amd as yaw
+    from yet_another_wizz_amd import engine
 
     inp, cats = helpers.full_catalogs(tag)
     config = helpers.full_config(inp, cfg, "right")
@@ -152,8 +156,17 @@ def test_batch_submission_equals_single_calls_bit_for_bit(tag, cfg):
     requests = [((ref, unk), "DD"), ((ref, ur), "DR"), ((rr, unk), "RD"), ((rr, ur), "RR"), ((ref,), "DD"), ((rr,), "RR"),
                 ((None, unk), "RD")]
     singles = [links.count_pairs(*cats_) if None not in cats_ else None for cats_, _ in requests]
+    ctx = engine.get_context()
+    if slab_budget is not None:
+        links.count_pairs_batch(requests)
+        unsplit = dict(links.last_batch_stats)
     for _ in range(2):  # the second round runs on remembered plans
-        batch = links.count_pairs_batch(requests)
+        if slab_budget is not None:
+            ctx.set_option("slab_budget_bytes", slab_budget)
+        try:
+            batch = links.count_pairs_batch(requests)
+        finally:
+            ctx.set_option("slab_budget_bytes", 1 << 30)
         assert len(batch) == len(requests)
         for one, many in zip(singles, batch):
             if one is None:
@@ -163,6 +176,9 @@ def test_batch_submission_equals_single_calls_bit_for_bit(tag, cfg):
                 assert np.array_equal(a.counts.counts, b.counts.counts)
                 assert a.counts.counts.sum() > 0 and a.counts.auto == b.counts.auto
                 assert np.array_equal(a.sum_weights.sum_weights1, b.sum_weights.sum_weights1)
+        if slab_budget is not None:  # the weighted counts went through the pieces (DD: the autocorrelation's, halved diagonal)
+            for name in ("DD", "DR", "RD"):
+                assert links.last_batch_stats[name].n_launches > unsplit[name].n_launches, name
     # more requests than slots in flight (four): the fifth waits for the first one's slot
     many = links.count_pairs_batch([((ref, unk), "DD")] * 6)
     for res in many:

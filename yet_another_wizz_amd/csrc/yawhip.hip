@@ -2281,35 +2281,20 @@ inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
 
-template <typename T>
-struct View {  // typed window into one of the context's arenas, set by every yawhip_count_pairs call
-    T *ptr = nullptr;
-};
-
-// Everything ONE count call in flight owns: the tables it sent, its work items, partial sums, result block and timing
-// events. A context keeps MAX_BATCH of these; the active one is the base-class part of the context (all the code below
-// says ctx->d_items ...), the others are parked -- yawhip_count_pairs_dense_batch activates one per request so that
-// several counts of a measurement are on the stream at once (use_slot).
+// Everything ONE count call in flight owns: its work items, partial sums, result block and timing events (the tables it
+// reads are its plan's, HostPlan). A context keeps MAX_BATCH of these; the active one is the base-class part of the context
+// (all the code below says ctx->d_items ...), the others are parked -- yawhip_count_pairs_dense_batch activates one per
+// request so that several counts of a measurement are on the stream at once (use_slot).
 struct CallBufs {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evc0 = nullptr, evc1 = nullptr, ev_done = nullptr;
-    View<int32_t> d_jobs;
-    View<int64_t> d_prefix;
-    View<double> d_t;
-    View<float> d_dthr;
-    View<float> d_thr32;
-    View<double> d_rwin;
-    View<float> d_ucap;
     DevBuf<Item> d_items;
-    View<unsigned long long> d_ctr;
-    View<unsigned long long> d_counts;
-    View<double> d_sums;
+    unsigned long long *d_ctr = nullptr, *d_counts = nullptr;  // counters and results: windows into `out`, set by every count call
+    double *d_sums = nullptr;
     DevBuf<double> d_partials;
     DevBuf<double> d_chunk_sums;
-    View<int64_t> d_cprefix;        // weighted calls: first chunk of every output slot (in the plan's device tables)
     DevBuf<unsigned char> d_kept;   // weighted runs: 1 for potential items the builder kept
     Arena out;   // results (device -> host)
     Arena comb;  // yawhip_count_pairs_dense: recombination tables in, per-scale values out
-    View<DevTab> d_tabs;
     hipError_t make_events() {
         hipError_t e = hipSuccess;
         for (hipEvent_t *ev : {&ev0, &ev1, &evc0, &evc1, &ev_done})
@@ -3387,16 +3372,21 @@ struct HostPlan {
     int R = 0, band_ne = 0, cap = 0, hp_shift = 0, lean_bins = 0, mode = 0, reach = 0, kernel = 0, nf = 0, n_orient = 0;
     bool band = false, band32 = false, band_fine = false, filter = false, lean = false, merged = false, run_unweighted = false,
          run_weighted = false, strip_items = false, swap = false, sweep = false, triple = false, uni = false, uniform_t = false,
-         weighted = false, weighted_any = false;
+         weighted = false;
     int64_t abytes = 0, cand = 0, n_items = 0, n_out = 0, n_pslots = 0, n_sjobs = 0, n_slots = 0, slab = 0, tile = 0;
     double rwin_max = 0.0;
     double cap_c = 1.0, cap_s = 0.0;  // cos / sin of sep_angle(rwin_max): the strip builder's trimmed windows (cap_s = 0: untrimmed)
     size_t lds_band = 0, lds_merged = 0;
-    // device tables (one allocation): jobs / job records, prefix, thresholds, pre-filter thresholds, window widths, float32
-    // classes, layout table, and -- weighted calls -- the chunk prefix of the slab reduction
+    // device tables, in one allocation (d_in) made when the plan's table image is uploaded (Planner::tables): jobs / job records,
+    // prefix, thresholds, pre-filter thresholds, window widths, float32 classes, layout table, and -- weighted calls -- the chunk
+    // prefix of the slab reduction
     unsigned char *d_in = nullptr;
-    size_t o_jobs = 0, o_prefix = 0, o_t = 0, o_dthr = 0, o_rwin = 0, o_ucap = 0, o_thr32 = 0, o_tabs = 0, o_cprefix = 0;
-    int64_t n_chunks = 0, n_oslots = 0;
+    int32_t *d_jobs = nullptr;
+    int64_t *d_prefix = nullptr, *d_cprefix = nullptr;
+    double *d_t = nullptr, *d_rwin = nullptr;
+    float *d_dthr = nullptr, *d_ucap = nullptr, *d_thr32 = nullptr;
+    DevTab *d_tabs = nullptr;
+    int64_t n_chunks = 0;
     ~HostPlan() { if (d_in) (void)hipFree(d_in); }
 };
 
@@ -3411,7 +3401,8 @@ void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c) {
     }
 }
 
-// The handle and size checks of a count call, made by every entry point before any device work.
+// The argument checks of a count call, made by every entry point before any device work: handles, sizes, bin counts of the
+// catalogues, thresholds and the patch ids of the jobs.
 int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
                int32_t n_bins, int32_t n_edges, const double *t) {
     if (!ctx || !c1 || !c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: NULL handle");
@@ -3421,14 +3412,6 @@ int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_cat
     if (c1->ctx != ctx || c2->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
     if (c1->n_patches != c2->n_patches)
         return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", c1->n_patches, c2->n_patches);
-    return YAWHIP_OK;
-}
-
-// The host half of a count call (its arguments passed check_call): every decision, the tables -- into a plan (see HostPlan).
-// for_work: the plan of a cost estimate (count_enqueue's job_work).
-int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-              int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
-              HostPlan &P) {
     if ((c1->nb != 1 && c1->nb != n_bins) || (c2->nb != 1 && c2->nb != n_bins))
         return fail(YAWHIP_ERR_MISMATCH, "catalogue bin counts (%d, %d) do not fit n_bins=%d", c1->nb, c2->nb, n_bins);
     for (int k = 0; k < n_bins; ++k)
@@ -3440,30 +3423,71 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     for (int j = 0; j < n_jobs; ++j)
         if (jobs[2 * j] < 0 || jobs[2 * j] >= c1->n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= c1->n_patches)
             return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, c1->n_patches);
+    return YAWHIP_OK;
+}
+
+// make_plan in steps, run in this order: each one fills its own fields of the plan; what a later step needs and the plan does
+// not keep stays in the planner.
+struct Planner {
+    yawhip_ctx *ctx;
+    const yawhip_catalog *c1, *c2;
+    int32_t n_jobs;
+    const int32_t *jobs;
+    int32_t n_bins, n_edges;
+    const double *t;
+    bool for_work;
+    HostPlan &P;
+    bool unit = false, auto_pick = false, half_ok = false;
+    int tile_idx = 0;  // tile table of the layouts (R = 1, 2, 4)
+    double layout_sep = 0.0;
+    std::vector<double> rwin;     // window half width per bin
+    std::vector<int32_t> orient;  // sort axis of the strip layouts of every job
+    const StripLayout *L1[3] = {nullptr, nullptr, nullptr}, *L2[3] = {nullptr, nullptr, nullptr};
+    const yawhip_catalog *c_lane = nullptr, *c_strm = nullptr;
+    const StripLayout *const *LL = nullptr, *const *LS = nullptr;  // lane side, streamed side
+    std::vector<float> fine32;
+    std::vector<int64_t> prefix;
+    std::vector<JobRec> job_recs;  // strip path, per job: what the builder needs of the two groups (JobRec)
+    void sides(bool swap) {
+        c_lane = swap ? c1 : c2; c_strm = swap ? c2 : c1;
+        LL = swap ? L1 : L2; LS = swap ? L2 : L1;
+    }
+    int kernel_and_sizes(int32_t kernel, bool want_counts, bool want_sums);
+    int layouts();
+    int tile_and_stage();
+    int histogram();
+    int items();
+    int tables();
+};
+
+// Step 1: the kernel, and the sizes of the output.
+int Planner::kernel_and_sizes(int32_t kernel, bool want_counts, bool want_sums) {
     if (kernel == YAWHIP_KERNEL_AUTO) kernel = ctx->default_kernel;
-    const bool auto_pick = kernel == YAWHIP_KERNEL_AUTO;  // BAND or SWEEP, whichever suits the layouts (decided below)
+    auto_pick = kernel == YAWHIP_KERNEL_AUTO;  // BAND or SWEEP, whichever suits the layouts (decided below)
     if (kernel == YAWHIP_KERNEL_AUTO) kernel = YAWHIP_KERNEL_BAND;
     if (kernel < YAWHIP_KERNEL_EXACT || kernel > YAWHIP_KERNEL_BAND)
         return fail(YAWHIP_ERR_INVALID, "unknown kernel id %d", kernel);
     // the FP32 pre-filter assumes unit vectors; anything else is evaluated pair by pair in FP64
-    const bool unit = c1->unit_norm && c2->unit_norm;
+    unit = c1->unit_norm && c2->unit_norm;
     if (kernel == YAWHIP_KERNEL_FILTER && !unit) kernel = YAWHIP_KERNEL_EXACT;
     // the window search compares the sorted coordinate of both sides: the axes must agree
     if ((kernel == YAWHIP_KERNEL_SWEEP || kernel == YAWHIP_KERNEL_BAND) && c1->axis != c2->axis)
         kernel = unit ? YAWHIP_KERNEL_FILTER : YAWHIP_KERNEL_EXACT;
     // the band kernels park finished lanes on a sentinel at coordinate 4.0 and bound their searches by it: unit vectors only
     if (kernel == YAWHIP_KERNEL_BAND && !unit) kernel = YAWHIP_KERNEL_EXACT;
-    bool band = kernel == YAWHIP_KERNEL_BAND;
-    const bool sweep = kernel == YAWHIP_KERNEL_SWEEP || band;
-    const bool filter = unit && kernel != YAWHIP_KERNEL_EXACT;
+    P.kernel = kernel;
+    P.band = kernel == YAWHIP_KERNEL_BAND;
+    P.sweep = kernel == YAWHIP_KERNEL_SWEEP || P.band;
+    P.filter = unit && kernel != YAWHIP_KERNEL_EXACT;
 
-    const int nf = n_edges - 1;
-    const int64_t n_slots = (int64_t)n_jobs * n_bins;
-    const int64_t n_out = n_slots * nf;
-    const bool weighted = (c1->w != nullptr) || (c2->w != nullptr);
-    P.n_out = n_out;
-    if (n_out == 0) { P.empty = true; return YAWHIP_OK; }
-    if (n_slots > (1ll << 30)) return fail(YAWHIP_ERR_INVALID, "too many (job,bin) slots");
+    P.nf = n_edges - 1;
+    P.n_slots = (int64_t)n_jobs * n_bins;
+    P.n_out = P.n_slots * P.nf;
+    P.weighted = (c1->w != nullptr) || (c2->w != nullptr);
+    P.run_weighted = P.weighted && want_sums;
+    P.run_unweighted = want_counts || (!P.weighted && want_sums);
+    if (P.n_out == 0) { P.empty = true; return YAWHIP_OK; }
+    if (P.n_slots > (1ll << 30)) return fail(YAWHIP_ERR_INVALID, "too many (job,bin) slots");
     HIP_TRY(hipSetDevice(ctx->device));
 
     // tile size: objects per lane. Larger tiles amortise the streamed-object read; small segments
@@ -3471,16 +3495,25 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // Lean path (k_count_merged): z-window culling + FP32 pre-filter + queued exact evaluation. Its merged
     // form (one item for all bins, strip layouts on both sides) serves c1 binned x c2 unbinned, i.e. every
     // count of a cross-correlation.
-    const bool weighted_any = (c1->w != nullptr) || (c2->w != nullptr);
-    const bool lean = sweep && (filter || band);  // single-wave workgroups on windowed items (k_count_merged / k_count_band)
+    P.lean = P.sweep && (P.filter || P.band);  // single-wave workgroups on windowed items (k_count_merged / k_count_band)
+    return YAWHIP_OK;
+}
+
+// Step 2: layout mode, orientations and strip layouts, the float32 band kernels, the sides, BAND or SWEEP.
+int Planner::layouts() {
+    const int nf = P.nf;
+    rwin.resize((size_t)n_bins);
     double rwin_max = 0.0;  // widest window half width over the bins
-    for (int k = 0; k < n_bins; ++k)
-        rwin_max = std::max(rwin_max, std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15);
+    for (int k = 0; k < n_bins; ++k) {
+        rwin[(size_t)k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
+        rwin_max = std::max(rwin_max, rwin[(size_t)k]);
+    }
+    P.rwin_max = rwin_max;
     // strip pairing pays while a run has few partner runs; for separations far beyond the grid spacing the
     // ordinary (patch, bin) layout is used instead
     // (grid_sep: the largest separation in the grid's own unit -- chord for a grid linear in v, angle for one in latitude)
     const double grid_sep = c1->strip_grid ? sep_angle(rwin_max) : rwin_max;
-    const bool strips = lean && c1->has_strips && c2->has_strips && c1->strip_width == c2->strip_width &&
+    const bool strips = P.lean && c1->has_strips && c2->has_strips && c1->strip_width == c2->strip_width &&
                         c1->strip_grid == c2->strip_grid &&
                         (c1->strip_width <= 0.0 || grid_sep / c1->strip_width <= (double)MAX_STRIP_REACH);
     // mode 3: binned x binned on the per-segment strip layouts: ordinary (job, bin) items whose lane tiles and windows
@@ -3495,24 +3528,24 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     bool uniform_t = true;  // every bin has the same threshold row (angular scales)
     for (int k = 1; k < n_bins && uniform_t; ++k)
         uniform_t = memcmp(t, t + (size_t)k * n_edges, sizeof(double) * n_edges) == 0;
+    P.uniform_t = uniform_t;
     // One item for all bins needs a histogram of B x (E - 1) cells (and B edge rows when they differ) in LDS. Where that
     // does not fit (hundreds of bins times dozens of separation-weight bins), the count falls back to ordinary
     // (job, bin) items, whose histogram has E - 1 cells.
-    const size_t merged_lds = (size_t)n_bins * nf * (weighted_any ? 8 : 4) + (size_t)(uniform_t ? 1 : n_bins) * n_edges * sizeof(double) +
+    const size_t merged_lds = (size_t)n_bins * nf * (P.weighted ? 8 : 4) + (size_t)(uniform_t ? 1 : n_bins) * n_edges * sizeof(double) +
                               (size_t)n_bins * sizeof(float) + BandLds<BCAP_MID>::FIXED + (BCAP_MID + 2) * 8 + 2 * MSTAGE * sizeof(ObjF) + 1024;
     const bool merged_fits = merged_lds <= (size_t)ctx->lds_limit;
-    const int mode = !strips ? 0 : (c1->nb > 1 && c2->nb == 1) ? (merged_fits ? 1 : 0) : (seg_ok ? 3 : 0);
+    const int mode = P.mode = !strips ? 0 : (c1->nb > 1 && c2->nb == 1) ? (merged_fits ? 1 : 0) : (seg_ok ? 3 : 0);
     // per-segment strip layouts keep the grid linear in v (build_strip_layout): their short runs make items of fixed cost, and
     // the latitude grid's narrower strips away from v = 0 only add items there
-    const double layout_sep = mode == 3 ? rwin_max : grid_sep;
-    const bool merged = mode == 1;                // one item covers all bins, output slot = job
-    const bool strip_items = mode != 0;           // items come from strip runs (k_build_items_strips)
+    layout_sep = mode == 3 ? rwin_max : grid_sep;
+    const bool merged = P.merged = mode == 1;                // one item covers all bins, output slot = job
+    const bool strip_items = P.strip_items = mode != 0;      // items come from strip runs (k_build_items_strips)
     // Orientation of every job: the (u, v) projection that compresses the sphere least around its two patches, i.e.
     // the one that drops the coordinate w in which the patches lie farthest from the origin. (Projected along an
     // axis the patches are nearly perpendicular to, objects pile up in (u, v) -- density grows like 1 / |w| -- and
     // the opposite hemisphere folds onto the same cells: every u-window then holds several times the partners.)
-    std::vector<int32_t> orient((size_t)n_jobs, (int32_t)c1->axis);
-    const StripLayout *L1[3] = {nullptr, nullptr, nullptr}, *L2[3] = {nullptr, nullptr, nullptr};
+    orient.assign((size_t)n_jobs, (int32_t)c1->axis);
     if (strip_items) {
         bool need[3] = {false, false, false};
         for (int j = 0; j < n_jobs; ++j) {
@@ -3541,22 +3574,20 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // Float32 classification (k_count_band32) on strip layouts of unit vectors with up to four edges per bin. Where one
     // side is binned (merged items) the roles are swapped against k_count_band: lane tiles come from the binned catalogue
     // c1, the windows from the unbinned c2 (see the kernel).
-    const bool want32 = band && strip_items && unit && n_edges <= 4 && ctx->band_fp32 != 0 &&
-                        band32_lds(weighted_any, BCAP_MID, (merged ? n_bins : 1) * nf, merged && !uniform_t ? n_bins : 0, n_edges) <=
+    const bool want32 = P.band && strip_items && unit && n_edges <= 4 && ctx->band_fp32 != 0 &&
+                        band32_lds(P.weighted, BCAP_MID, (merged ? n_bins : 1) * nf, merged && !uniform_t ? n_bins : 0, n_edges) <=
                             (size_t)ctx->lds_limit;
     // ... and the fine radial grids of separation weights (k_count_band32_fine), when their edges follow the log-spaced model
-    std::vector<float> fine32;
-    if (band && strip_items && unit && n_edges > 4 && ctx->band_fp32 != 0 &&
-        band32_fine_lds(weighted_any, BCAP_MID, (merged ? n_bins : 1) * nf, uniform_t ? 1 : n_bins, n_edges) <= (size_t)ctx->lds_limit)
+    if (P.band && strip_items && unit && n_edges > 4 && ctx->band_fp32 != 0 &&
+        band32_fine_lds(P.weighted, BCAP_MID, (merged ? n_bins : 1) * nf, uniform_t ? 1 : n_bins, n_edges) <= (size_t)ctx->lds_limit)
         fine32 = build_fine32(t, n_bins, n_edges);
     const bool want_fine = !fine32.empty();
     // (Binned x binned counts of two different catalogues keep c2 on the lanes whichever is sparser: with the 10M data on the
     // lanes and the 100M randoms streamed, DR of config #4 has 570 k items instead of 1.28 M but walks 2.3 x the entries --
     // neighbouring lane objects of a sparse run lie far apart, their common band is long -- 4.1 against 2.2 ms.)
-    bool swap = (want32 || want_fine) && merged;
-    const yawhip_catalog *c_lane = swap ? c1 : c2, *c_strm = swap ? c2 : c1;
-    const StripLayout *const *LL = swap ? L1 : L2, *const *LS = swap ? L2 : L1;  // lane side, streamed side
-    if (auto_pick && band && unit) {
+    P.swap = (want32 || want_fine) && merged;
+    sides(P.swap);
+    if (auto_pick && P.band && unit) {
         // The band kernel decides every entry of a per-object band: unbeatable while a band is a handful of entries of which
         // half are pairs (strip layouts). Without strips a band is the whole u-window of a segment, nearly all of it far away
         // along v -- the FP32 pre-filter of the sweep kernel is made for that. Sparse streamed runs (a few dozen objects: an
@@ -3573,15 +3604,24 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
             use_sweep = obj_run < (double)BAND_MIN_STREAM_RUN;
         }
         if (use_sweep) {
-            kernel = YAWHIP_KERNEL_SWEEP;
-            band = false;
+            P.kernel = YAWHIP_KERNEL_SWEEP;
+            P.band = false;
         }
     }
-    const bool band32 = want32 && band, band_fine = want_fine && band;
-    if (!band32 && !band_fine && swap) {  // the sweep kernel streams c1 past lane tiles of c2
-        swap = false;
-        c_lane = c2; c_strm = c1; LL = L2; LS = L1;
+    P.band32 = want32 && P.band;
+    P.band_fine = want_fine && P.band;
+    if (!P.band32 && !P.band_fine && P.swap) {  // the sweep kernel streams c1 past lane tiles of c2
+        P.swap = false;
+        sides(false);
     }
+    P.uni = merged || P.band_fine ? uniform_t : true;  // UNI of the band kernels (per-bin items of the others: one threshold row)
+    return YAWHIP_OK;
+}
+
+// Step 3: objects per lane, the expected window, merged triple runs, the stage capacity.
+int Planner::tile_and_stage() {
+    const bool band = P.band, strip_items = P.strip_items;
+    const int mode = P.mode;
     int R = ctx->tile_r;
     double est_window = 0.0;  // band kernel: expected entries of one window
     if (R == 0) {
@@ -3597,7 +3637,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
             for (int j = 0; j < n_jobs; ++j)
                 for (int k = 0; k < (c2->nb == 1 ? 1 : n_bins); ++k) max_seg = std::max(max_seg, seg_len(c2, jobs[2 * j + 1], k));
         }
-        const int wg = lean ? MWG : WG;
+        const int wg = P.lean ? MWG : WG;
         R = max_seg >= 8 * wg * 4 ? 4 : (max_seg >= 4 * wg * 2 ? 2 : 1);
         if (strip_items && R > 2) R = 2;  // on strip runs two objects per lane beat four at every size measured (10M: 2.25 / 2.5 ms, 50M: 68 / 72 ms)
         if (band && strip_items) {
@@ -3627,7 +3667,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
             // two (DD of config #4: 2.7e7 instead of 5.6e7 entries, 0.63 -> 0.41 ms; RR 3.74 -> 3.57), unless the streamed side
             // is much the sparser one and items are all fixed cost (DR: 2.05e6 items instead of 1.28e6, 1.86 -> 2.25 ms)
             if (mode == 3 && d1 >= 0.5 * d2) R = 1;
-            est_window = 64.0 * R * d1 / std::max(d2, 1e-12) + 2.0 * rwin_max * d1;
+            est_window = 64.0 * R * d1 / std::max(d2, 1e-12) + 2.0 * P.rwin_max * d1;
         }
     }
     if (band && R == 0) R = 2;
@@ -3640,11 +3680,11 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // with one chunk per round exists: the count kernel takes the same 0.48 ms at the headline in the big stage, the builder
     // searches one window per item instead of three (0.045 against 0.063 ms).
     bool triple = false;
-    if ((band32 || band_fine) && strip_items && ctx->triple_runs && c_strm->n < (1ll << 31) && c1->strip_width > 0.0 &&
+    if ((P.band32 || P.band_fine) && strip_items && ctx->triple_runs && c_strm->n < (1ll << 31) && c1->strip_width > 0.0 &&
         (int)std::floor(layout_sep / c1->strip_width + 1e-6) + 1 == 1) {
         const double est3 = 3.0 * est_window;
         triple = ctx->triple_runs == 2 ||
-                 (band32 ? est3 <= 0.88 * (B32_CAP_BIG - 4) : est3 <= 0.9 * BCAP_MID);
+                 (P.band32 ? est3 <= 0.88 * (B32_CAP_BIG - 4) : est3 <= 0.9 * BCAP_MID);
         for (int o = 0; o < 3 && triple; ++o) {
             if (!LS[o]) continue;
             const int rc = build_triples(ctx, const_cast<yawhip_catalog *>(c_strm), o, mode == 3);
@@ -3653,6 +3693,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
         }
         if (triple) est_window = est3;
     }
+    P.triple = triple;
     if (g_trace.on) fprintf(stderr, "[yawhip trace] est_window %.1f (triple %d) R %d mode %d\n", est_window, (int)triple, R, mode);
     // stage capacity of the band kernel: the smallest compiled one that holds a whole window (see BCAP_MID)
     int cap = ctx->band_cap == BCAP || ctx->band_cap == BCAP_MID ? ctx->band_cap : 0;
@@ -3667,12 +3708,22 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // with windows of ~265 entries: 21.0 ms in the 320-entry stage, 18.3 ms in a 448-entry one)
     if (R == 1) cap32 = B32_CAP;  // (compiled pairs, as above)
     if (R >= 4) cap32 = B32_CAP_BIG;
-    if (band32) cap = cap32;  // (the fine-grid kernel still stages window by window, with the capacities of k_count_band)
-    const int64_t tile = (int64_t)(lean ? MWG : WG) * R;
-    const int lean_bins = merged ? n_bins : 1;
-    const size_t lds_merged = 2 * MSTAGE * sizeof(ObjF) + (size_t)lean_bins * n_edges * sizeof(double) +
-                              (size_t)lean_bins * nf * (weighted_any ? 8 * (MWG / 64) : 4) + (size_t)lean_bins * sizeof(float) +
-                              (size_t)MWG * sizeof(unsigned int) + 16;
+    if (P.band32) cap = cap32;  // (the fine-grid kernel still stages window by window, with the capacities of k_count_band)
+    P.R = R;
+    tile_idx = R == 1 ? 0 : (R == 2 ? 1 : 2);
+    P.cap = cap;
+    P.tile = (int64_t)(P.lean ? MWG : WG) * R;
+    P.lean_bins = P.merged ? n_bins : 1;
+    P.lds_merged = 2 * MSTAGE * sizeof(ObjF) + (size_t)P.lean_bins * n_edges * sizeof(double) +
+                   (size_t)P.lean_bins * P.nf * (P.weighted ? 8 * (MWG / 64) : 4) + (size_t)P.lean_bins * sizeof(float) +
+                   (size_t)MWG * sizeof(unsigned int) + 16;
+    return YAWHIP_OK;
+}
+
+// Step 4: copies of the band kernel's LDS histogram, its compile-time edge count, its LDS.
+int Planner::histogram() {
+    const int lean_bins = P.lean_bins, nf = P.nf;
+    const bool merged = P.merged, uniform_t = P.uniform_t;
     // Copies of the LDS histogram, lanes spread over them by lane id: same-address atomics of one instruction are
     // serialised. Four copies when there are few slots and the bins of neighbouring entries are unrelated (headline:
     // 0.535 ms with four, 0.565 with eight -- the flush grows with the copies). When the histogram has only the fine bins
@@ -3680,62 +3731,64 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // (same_bin: neighbours of the layout's order sharing their bin; clustered survey: 108 -> 62 ms weighted cross count,
     // 31 -> 18 ms autocorrelation count), more copies pay: up to 16 within 2 KB.
     int hp_shift = lean_bins * nf <= 32 ? 2 : 0;
-    if (band) {
+    if (P.band) {
         double coherence = merged ? 0.0 : 1.0;
         if (merged)
             for (int o = 0; o < 3; ++o)
                 if (L1[o]) coherence = std::max(coherence, L1[o]->same_bin);
         if (coherence > 0.25) {
-            const int cell = weighted_any ? 8 : 4;
+            const int cell = P.weighted ? 8 : 4;
             while (hp_shift < (merged ? 3 : 4) && ((size_t)lean_bins * nf * cell << (hp_shift + 1)) <= 2048) ++hp_shift;
         }
     }
     if (ctx->hist_copies_log2 >= 0) hp_shift = ctx->hist_copies_log2;
-    const int band_ne = (!merged || uniform_t) && n_edges <= 4 ? n_edges : (nf == 1 ? 2 : 0);  // compile-time edge count of k_count_band
-    const bool band_thr = !(band_ne >= 2 && (!merged || uniform_t));
-    const size_t LDS_FIXED = (size_t)band_lds_fixed(cap);
+    P.band_ne = (!merged || uniform_t) && n_edges <= 4 ? n_edges : (nf == 1 ? 2 : 0);  // compile-time edge count of k_count_band
+    const bool band_thr = !(P.band_ne >= 2 && (!merged || uniform_t));
+    const size_t LDS_FIXED = (size_t)band_lds_fixed(P.cap);
     auto band_lds_for = [&](int shift) {
-        return band_lds_dynamic(weighted_any, band_thr, lean_bins, n_edges, 1 << shift, cap, merged && !uniform_t ? lean_bins : 1);
+        return band_lds_dynamic(P.weighted, band_thr, lean_bins, n_edges, 1 << shift, P.cap, merged && !uniform_t ? lean_bins : 1);
     };
-    while (band && hp_shift > 0 && band_lds_for(hp_shift) + LDS_FIXED > (size_t)ctx->lds_limit) --hp_shift;  // copies are a tunable, not a need
-    const size_t lds_band = band_lds_for(hp_shift);
-    if (lean && (band ? lds_band + LDS_FIXED : lds_merged) > (size_t)ctx->lds_limit)
-        return fail(YAWHIP_ERR_INVALID, "too many bins x edges for the LDS histogram (%zu bytes)", band ? lds_band + LDS_FIXED : lds_merged);
+    while (P.band && hp_shift > 0 && band_lds_for(hp_shift) + LDS_FIXED > (size_t)ctx->lds_limit) --hp_shift;  // copies are a tunable, not a need
+    P.hp_shift = hp_shift;
+    P.lds_band = band_lds_for(hp_shift);
+    if (P.lean && (P.band ? P.lds_band + LDS_FIXED : P.lds_merged) > (size_t)ctx->lds_limit)
+        return fail(YAWHIP_ERR_INVALID, "too many bins x edges for the LDS histogram (%zu bytes)", P.band ? P.lds_band + LDS_FIXED : P.lds_merged);
+    return YAWHIP_OK;
+}
 
+// Step 5: the item table -- job records, prefix, candidates and bytes, half bands -- and whether the job list has to be split.
+int Planner::items() {
+    const bool strip_items = P.strip_items;
+    const int mode = P.mode;
     // item table: prefix[slot] = first item of the slot; items of a slot are its lane tiles.
     // standard path: slot = (job, bin); merged path: slot = job (one item covers all bins).
     // strip path: slot = job; its potential items = (lane tiles of patch q) x (groups of up to MAX_WIN of the 2*reach+1
     // neighbouring strips), enumerated by the builder kernel from the catalogues' run tables.
-    std::vector<int64_t> prefix;
-    std::vector<JobRec> job_recs;  // strip path, per job: what the builder needs of the two groups (JobRec)
     int64_t n_items = 0, cand = 0, abytes = 0;
     const int obj_bytes1 = c1->w ? 32 : 24, obj_bytes2 = c2->w ? 32 : 24;
-    int reach = 0;
-    const int tile_idx = R == 1 ? 0 : (R == 2 ? 1 : 2);
     // strip paths: the builder's job table. Modes 1/2: the jobs themselves (groups = patches); mode 3: one pseudo job
     // per (job, bin) between the segments (p, k) and (q, k) (groups = segments), numbered like the output slots.
-    std::vector<int32_t> sjobs;
-    const int64_t n_sjobs = mode == 3 ? n_slots : (int64_t)n_jobs;
+    P.n_sjobs = mode == 3 ? P.n_slots : (int64_t)n_jobs;
     // Half bands: a catalogue counted against ITSELF meets every unordered pair of a diagonal job twice -- a as lane object with b
     // in its window, b as lane object with a in its. On merged triple runs with one object per lane the lane walks only the
     // entries BEHIND its own place in the triple of its strip (one total order of objects in all triples, k_merge_triples): every
     // pair is met once and counts twice (an exact doubling, also of weighted sums). Half the walk of DD / RR of an autocorrelation.
-    const bool half_ok = band32 && triple && R == 1 && c1 == c2 && !swap && ctx->half_bands != 0 && !for_work;
+    half_ok = P.band32 && P.triple && P.R == 1 && c1 == c2 && !P.swap && ctx->half_bands != 0 && !for_work;
     if (strip_items) {
         const double width = c1->strip_width;
         // |dv| <= rwin_max (|d latitude| <= sep_angle(rwin_max))  ->  grid indices differ by at most floor(layout_sep / width) + 1
-        reach = width > 0.0 ? (int)std::floor(layout_sep / width + 1e-6) + 1 : 0;
-        sjobs.resize((size_t)2 * n_sjobs);
+        const int reach = P.reach = width > 0.0 ? (int)std::floor(layout_sep / width + 1e-6) + 1 : 0;
+        std::vector<int32_t> sjobs((size_t)2 * P.n_sjobs);
         for (int j = 0; j < n_jobs; ++j)
             for (int k = 0; k < (mode == 3 ? n_bins : 1); ++k) {
                 const int64_t sj = mode == 3 ? (int64_t)j * n_bins + k : j;
                 sjobs[(size_t)2 * sj] = mode == 3 ? jobs[2 * j] * n_bins + k : jobs[2 * j];
                 sjobs[(size_t)2 * sj + 1] = mode == 3 ? jobs[2 * j + 1] * n_bins + k : jobs[2 * j + 1];
             }
-        prefix.resize((size_t)n_sjobs + 1);
-        job_recs.assign((size_t)n_sjobs, JobRec{0, 0, 0, 0, 0});
-        for (int64_t j = 0; j < n_sjobs; ++j) {
-            const int p = sjobs[(size_t)2 * j + (swap ? 1 : 0)], q = sjobs[(size_t)2 * j + (swap ? 0 : 1)];  // streamed, lane side
+        prefix.resize((size_t)P.n_sjobs + 1);
+        job_recs.assign((size_t)P.n_sjobs, JobRec{0, 0, 0, 0, 0});
+        for (int64_t j = 0; j < P.n_sjobs; ++j) {
+            const int p = sjobs[(size_t)2 * j + (P.swap ? 1 : 0)], q = sjobs[(size_t)2 * j + (P.swap ? 0 : 1)];  // streamed, lane side
             const int o = orient[(size_t)(mode == 3 ? j / n_bins : j)];
             const StripLayout &sl1 = *LS[o], &sl2 = *LL[o];
             const std::vector<int64_t> &tiles = sl2.h_tiles[tile_idx];
@@ -3752,7 +3805,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
                 jr.k_off = lo2 - sl2.h_vbase[(size_t)q] - lo1;  // strip index of lane run r2 on the common grid, relative to group p
                 jr.vbase1 = sl1.h_vbase[(size_t)p];
                 jr.n_strips1 = (int32_t)cnt1;
-                if (triple) {  // triple runs of group p: strips [lo1 - 1, lo1 + cnt1], the first one at vbase + 2 p
+                if (P.triple) {  // triple runs of group p: strips [lo1 - 1, lo1 + cnt1], the first one at vbase + 2 p
                     jr.k_off += 1;
                     jr.vbase1 += 2 * (int64_t)p;
                     jr.n_strips1 += 2;
@@ -3760,11 +3813,11 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
                 n_items += (tiles[(size_t)(r0 + s_hi - s_lo + 1)] - tiles[(size_t)r0]) * ((2 * reach + 1 + MAX_WIN - 1) / MAX_WIN);
             }
         }
-        prefix[(size_t)n_sjobs] = n_items;
+        prefix[(size_t)P.n_sjobs] = n_items;
     } else {
-        prefix.resize((size_t)n_slots + 1);
+        prefix.resize((size_t)P.n_slots + 1);
     }
-    const int64_t n_pslots = merged ? (int64_t)n_jobs : n_slots;
+    P.n_pslots = P.merged ? (int64_t)n_jobs : P.n_slots;
     auto patch_total = [](const yawhip_catalog *c, int patch) {  // objects of a patch over all its bins
         return c->h_off[(size_t)(patch + 1) * c->nb] - c->h_off[(size_t)patch * c->nb];
     };
@@ -3779,7 +3832,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
                 const int64_t n1 = seg_len(c1, p, k), n2 = seg_len(c2, q, k);
                 if (!strip_items) prefix[(size_t)j * n_bins + k] = n_items;
                 if (n1 > 0 && n2 > 0) {
-                    if (!strip_items) n_items += (n2 + tile - 1) / tile;
+                    if (!strip_items) n_items += (n2 + P.tile - 1) / P.tile;
                     cand += n1 * n2;
                 }
             }
@@ -3787,12 +3840,21 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
         // algorithmic bytes of a job = every object of the two patches once (Bobj * (N1 + N2))
         abytes += patch_total(c1, p) * obj_bytes1 + patch_total(c2, q) * obj_bytes2;
     }
-    if (!strip_items) prefix[(size_t)n_pslots] = n_items;
-    const int64_t slab = merged ? (int64_t)n_bins * nf : nf;  // float64 values per item of the weighted slab
+    if (!strip_items) prefix[(size_t)P.n_pslots] = n_items;
+    P.n_items = n_items;
+    P.cand = cand;
+    P.abytes = abytes;
+    P.slab = P.merged ? (int64_t)n_bins * P.nf : P.nf;  // float64 values per item of the weighted slab
+    // A weighted call keeps one slab of partial sums per potential item; long job lists of big catalogues would need
+    // tens of GB (50M x 50M, three scales: 40 GB). Above the budget -- and when the items no longer fit 31 bits -- the
+    // caller cuts the job list in two and counts the halves one after the other (rows of the result are independent).
+    P.split = n_jobs > 1 && !for_work &&
+              ((P.run_weighted && n_items * P.slab * (int64_t)sizeof(double) > ctx->slab_budget) || n_items >= (1ll << 31));
+    return YAWHIP_OK;
+}
 
-    const bool run_weighted = weighted && want_sums;
-    const bool run_unweighted = want_counts || (!weighted && want_sums);
-
+// Step 6: the per-bin tables and the layout table; all tables packed into one image, uploaded once; the grid divisor.
+int Planner::tables() {
     std::vector<float> dthr((size_t)3 * n_bins);  // per bin: pre-filter threshold, certain-band lower / upper bound
     auto round_down = [](double v) { float f = (float)v; if ((double)f > v) f = nextafterf(f, -4.0f); return f; };
     for (int k = 0; k < n_bins; ++k) {
@@ -3802,9 +3864,7 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
         dthr[(size_t)3 * k + 1] = 0.f;  // reserved
         dthr[(size_t)3 * k + 2] = 0.f;
     }
-    std::vector<double> rwin((size_t)n_bins);
-    for (int k = 0; k < n_bins; ++k) rwin[(size_t)k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-    if (merged) rwin[0] = rwin_max;  // one window for all bins of the merged run
+    if (P.merged) rwin[0] = P.rwin_max;  // one window for all bins of the merged run
     // band_trim: {cos, sin} of the largest separation angle per row of rwin, float32 for the band kernels ({1, 0}: untrimmed).
     // The caps assume |a|^2 within UNIT_NORM_TOL of 1 (sep_angle).
     const bool trim = ctx->band_trim && c1->unit_norm && c2->unit_norm;
@@ -3814,28 +3874,26 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
         ucap[(size_t)2 * k] = trim ? (float)std::cos(th) : 1.0f;
         ucap[(size_t)2 * k + 1] = trim ? (float)std::sin(th) : 0.0f;
     }
-    // A weighted call keeps one slab of partial sums per potential item; long job lists of big catalogues would need
-    // tens of GB (50M x 50M, three scales: 40 GB). Above the budget -- and when the items no longer fit 31 bits -- the
-    // caller cuts the job list in two and counts the halves one after the other (rows of the result are independent).
-    if (n_jobs > 1 && !for_work &&
-        ((run_weighted && n_items * slab * (int64_t)sizeof(double) > ctx->slab_budget) || n_items >= (1ll << 31)))
-        { P.split = true; return YAWHIP_OK; }
+    if (trim) {
+        P.cap_c = std::cos(sep_angle(P.rwin_max));
+        P.cap_s = std::sin(sep_angle(P.rwin_max));
+    }
     // layout table of the call: [o] = c1, [3 + o] = c2 for orientation o (plain layouts: entries 0 and 3)
     DevTab h_tabs[6];
     memset(h_tabs, 0, sizeof h_tabs);
-    if (strip_items) {
+    if (P.strip_items) {
         for (int o = 0; o < 3; ++o) {
             if (!L1[o]) continue;
             const StripLayout &a = *L1[o], &b = *L2[o];
-            h_tabs[o] = make_tab(a.x, a.y, a.z, a.w, merged ? a.k : nullptr, a.off, a.d_vbase, a.d_slo, a.d_tiles[tile_idx],
+            h_tabs[o] = make_tab(a.x, a.y, a.z, a.w, P.merged ? a.k : nullptr, a.off, a.d_vbase, a.d_slo, a.d_tiles[tile_idx],
                                  a.d_tile_rec[tile_idx], a.d_grid, o, a.q, a.q_stride);
             h_tabs[3 + o] = make_tab(b.x, b.y, b.z, b.w, nullptr, b.off, b.d_vbase, b.d_slo, b.d_tiles[tile_idx],
                                      b.d_tile_rec[tile_idx], b.d_grid, o, b.q, b.q_stride);
-            if (triple) {
+            if (P.triple) {
                 // the streamed side as merged triple runs: images, weights, offsets and grid index of the triples; the float64
                 // columns stay the layout's own (reached through idx by the exact re-evaluation)
-                const StripLayout &st = swap ? b : a;
-                DevTab &tb = h_tabs[swap ? 3 + o : o];
+                const StripLayout &st = P.swap ? b : a;
+                DevTab &tb = h_tabs[P.swap ? 3 + o : o];
                 tb = make_tab(st.x, st.y, st.z, st.w3, nullptr, st.off3, st.d_vbase, st.d_slo, st.d_tiles[tile_idx],
                               st.d_tile_rec[tile_idx], st.d_grid3, o, st.q3, st.q3_stride, st.idx3);
                 if (half_ok) h_tabs[3 + o].pos3 = (gi32p)b.pos3;  // (c1 == c2: the lane side's layout is the streamed one)
@@ -3847,47 +3905,37 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     }
     // the tables of the call, packed into the pinned staging buffer and sent with one copy
     static_assert(sizeof(JobRec) == 8 * sizeof(int32_t), "JobRec is 32 bytes");
-    const size_t n_jobtab = strip_items ? (size_t)8 * n_sjobs : (size_t)2 * n_jobs;  // JobRec per job, or (p, q) pairs
-    size_t off_in = 0;
-    auto take = [&](size_t bytes) { const size_t o = off_in; off_in = align16(off_in + bytes); return o; };
-    const size_t o_jobs = take(n_jobtab * sizeof(int32_t));
-    const size_t o_prefix = take(((size_t)n_pslots + 1) * sizeof(int64_t));
-    const size_t o_t = take((size_t)n_bins * n_edges * sizeof(double));
-    const size_t o_dthr = take((size_t)3 * n_bins * sizeof(float));
-    const size_t o_rwin = take((size_t)n_bins * sizeof(double));
-    const size_t o_ucap = take((size_t)2 * n_bins * sizeof(float));
-    const std::vector<float> thr32 = band32 ? build_thr32(t, n_bins, n_edges) : (band_fine ? fine32 : std::vector<float>());
-    const size_t o_thr32 = take(thr32.size() * sizeof(float));
-    const size_t o_tabs = take(sizeof h_tabs);
+    const std::vector<float> thr32 = P.band32 ? build_thr32(t, n_bins, n_edges) : (P.band_fine ? fine32 : std::vector<float>());
     // weighted calls: the two-level ordered reduction of the slabs needs the first chunk of every output slot
-    const int64_t n_oslots = !lean ? n_slots : (merged ? (int64_t)n_jobs : n_slots);
     std::vector<int64_t> cprefix;
-    if (run_weighted) {
-        cprefix.assign((size_t)n_oslots + 1, 0);
-        for (int64_t sl = 0; sl < n_oslots; ++sl)
+    if (P.run_weighted) {
+        cprefix.assign((size_t)P.n_pslots + 1, 0);
+        for (int64_t sl = 0; sl < P.n_pslots; ++sl)
             cprefix[(size_t)sl + 1] = cprefix[(size_t)sl] + (prefix[(size_t)sl + 1] - prefix[(size_t)sl] + REDUCE_CHUNK - 1) / REDUCE_CHUNK;
     }
-    const size_t o_cprefix = take(cprefix.size() * sizeof(int64_t));
+    P.n_chunks = cprefix.empty() ? 0 : cprefix.back();
+    const void *src[9] = {P.strip_items ? (const void *)job_recs.data() : (const void *)jobs, prefix.data(), t, dthr.data(),
+                          rwin.data(), ucap.data(), thr32.data(), h_tabs, cprefix.data()};
+    const size_t bytes[9] = {P.strip_items ? sizeof(JobRec) * (size_t)P.n_sjobs : sizeof(int32_t) * 2 * (size_t)n_jobs,
+                             sizeof(int64_t) * ((size_t)P.n_pslots + 1), sizeof(double) * n_bins * n_edges, sizeof(float) * 3 * n_bins,
+                             sizeof(double) * n_bins, sizeof(float) * 2 * n_bins, sizeof(float) * thr32.size(), sizeof h_tabs,
+                             sizeof(int64_t) * cprefix.size()};
+    size_t off[9], off_in = 0;
+    for (int i = 0; i < 9; ++i) { off[i] = off_in; off_in = align16(off_in + bytes[i]); }
     std::vector<unsigned char> image(off_in, 0);
-    if (strip_items) {
-        memcpy(image.data() + o_jobs, job_recs.data(), sizeof(JobRec) * n_sjobs);
-    } else {
-        memcpy(image.data() + o_jobs, jobs, sizeof(int32_t) * 2 * n_jobs);
-    }
-    memcpy(image.data() + o_prefix, prefix.data(), sizeof(int64_t) * ((size_t)n_pslots + 1));
-    memcpy(image.data() + o_t, t, sizeof(double) * n_bins * n_edges);
-    memcpy(image.data() + o_dthr, dthr.data(), sizeof(float) * 3 * n_bins);
-    memcpy(image.data() + o_rwin, rwin.data(), sizeof(double) * n_bins);
-    memcpy(image.data() + o_ucap, ucap.data(), sizeof(float) * 2 * n_bins);
-    if (!thr32.empty()) memcpy(image.data() + o_thr32, thr32.data(), sizeof(float) * thr32.size());
-    memcpy(image.data() + o_tabs, h_tabs, sizeof h_tabs);
-    if (!cprefix.empty()) memcpy(image.data() + o_cprefix, cprefix.data(), sizeof(int64_t) * cprefix.size());
+    for (int i = 0; i < 9; ++i)
+        if (bytes[i]) memcpy(image.data() + off[i], src[i], bytes[i]);
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&P.d_in), std::max<size_t>(off_in, 16)));
     HIP_TRY(hipMemcpy(P.d_in, image.data(), off_in, hipMemcpyHostToDevice));  // once per plan
-    P.o_jobs = o_jobs; P.o_prefix = o_prefix; P.o_t = o_t; P.o_dthr = o_dthr; P.o_rwin = o_rwin; P.o_ucap = o_ucap; P.o_thr32 = o_thr32;
-    P.o_tabs = o_tabs; P.o_cprefix = o_cprefix;
-    P.n_chunks = cprefix.empty() ? 0 : cprefix.back();
-    P.n_oslots = n_oslots;
+    P.d_jobs = reinterpret_cast<int32_t *>(P.d_in + off[0]);
+    P.d_prefix = reinterpret_cast<int64_t *>(P.d_in + off[1]);
+    P.d_t = reinterpret_cast<double *>(P.d_in + off[2]);
+    P.d_dthr = reinterpret_cast<float *>(P.d_in + off[3]);
+    P.d_rwin = reinterpret_cast<double *>(P.d_in + off[4]);
+    P.d_ucap = reinterpret_cast<float *>(P.d_in + off[5]);
+    P.d_thr32 = reinterpret_cast<float *>(P.d_in + off[6]);
+    P.d_tabs = reinterpret_cast<DevTab *>(P.d_in + off[7]);
+    P.d_cprefix = reinterpret_cast<int64_t *>(P.d_in + off[8]);
     P.n_orient = (L1[0] ? 1 : 0) + (L1[1] ? 1 : 0) + (L1[2] ? 1 : 0);
     // Workgroups of the band kernels = potential items / grid_div (the kernel loops over the rest). Uniform catalogues, whose
     // items are alike, run best with few, longer-lived workgroups: / 8, / 16 for the per-bin items of binned x binned counts, of
@@ -3895,61 +3943,33 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     // 3.04 / 3.02). On CLUSTERED catalogues items differ a hundredfold and the hardware's dispatch of many short workgroups is the
     // load balancer: / 4 (clustered survey, 3M x 4M: cross count 40.1 against 43.3 ms with / 8, autocorrelation count 7.1
     // against 8.2 with / 16). Clustered = the run the typical OBJECT sits in (sum len^2 / sum len) is more than twice the mean run.
-    {
-        double skew = 1.0;
-        for (const StripLayout *const *LX : {L1, L2})
-            for (int o = 0; o < 3; ++o)
-                if (LX[o] && LX[o]->built) {
-                    const yawhip_catalog *cx = LX == L1 ? c1 : c2;
-                    const double runs = (double)std::max<int64_t>(LX[o]->h_vbase[(size_t)LX[o]->n_groups], 1);
-                    skew = std::max(skew, LX[o]->obj_run / std::max((double)cx->n / runs, 1.0));
-                }
-        P.grid_div = ctx->band_grid_div > 0 ? ctx->band_grid_div : (skew > 2.0 ? 4 : (mode == 3 ? 16 : 8));
-        if (g_trace.on) fprintf(stderr, "[yawhip trace] run skew %.2f -> grid / %d\n", skew, P.grid_div);
-    }
-    P.R = R;
-    P.abytes = abytes;
-    P.band = band;
-    P.band32 = band32;
-    P.band_fine = band_fine;
-    P.band_ne = band_ne;
-    P.cand = cand;
-    P.cap = cap;
-    P.filter = filter;
-    P.hp_shift = hp_shift;
-    P.lds_band = lds_band;
-    P.lds_merged = lds_merged;
-    P.lean = lean;
-    P.lean_bins = lean_bins;
-    P.merged = merged;
-    P.mode = mode;
-    P.n_items = n_items;
-    P.n_out = n_out;
-    P.n_pslots = n_pslots;
-    P.n_sjobs = n_sjobs;
-    P.n_slots = n_slots;
-    P.nf = nf;
-    P.reach = reach;
-    P.run_unweighted = run_unweighted;
-    P.run_weighted = run_weighted;
-    P.rwin_max = rwin_max;
-    if (trim) {
-        P.cap_c = std::cos(sep_angle(rwin_max));
-        P.cap_s = std::sin(sep_angle(rwin_max));
-    }
-    P.slab = slab;
-    P.strip_items = strip_items;
-    P.swap = swap;
-    P.sweep = sweep;
-    P.tile = tile;
-    P.triple = triple;
-    P.uniform_t = uniform_t;
-    P.uni = merged || band_fine ? uniform_t : true;  // UNI of the band kernels (per-bin items of the others: one threshold row)
-    P.weighted = weighted;
-    P.weighted_any = weighted_any;
-    P.kernel = kernel;
-    g_trace.mark("planned");
+    double skew = 1.0;
+    for (const StripLayout *const *LX : {L1, L2})
+        for (int o = 0; o < 3; ++o)
+            if (LX[o] && LX[o]->built) {
+                const yawhip_catalog *cx = LX == L1 ? c1 : c2;
+                const double runs = (double)std::max<int64_t>(LX[o]->h_vbase[(size_t)LX[o]->n_groups], 1);
+                skew = std::max(skew, LX[o]->obj_run / std::max((double)cx->n / runs, 1.0));
+            }
+    P.grid_div = ctx->band_grid_div > 0 ? ctx->band_grid_div : (skew > 2.0 ? 4 : (P.mode == 3 ? 16 : 8));
+    if (g_trace.on) fprintf(stderr, "[yawhip trace] run skew %.2f -> grid / %d\n", skew, P.grid_div);
     return YAWHIP_OK;
+}
+
+// The host half of a count call (its arguments passed check_call): every decision, the tables -- into a plan (see HostPlan).
+// for_work: the plan of a cost estimate (count_enqueue's job_work).
+int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
+              int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
+              HostPlan &P) {
+    Planner pl{ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, for_work, P};
+    int rc = pl.kernel_and_sizes(kernel, want_counts, want_sums);
+    if (rc == YAWHIP_OK && !P.empty) rc = pl.layouts();
+    if (rc == YAWHIP_OK && !P.empty) rc = pl.tile_and_stage();
+    if (rc == YAWHIP_OK && !P.empty) rc = pl.histogram();
+    if (rc == YAWHIP_OK && !P.empty) rc = pl.items();
+    if (rc == YAWHIP_OK && !P.empty && !P.split) rc = pl.tables();
+    if (rc == YAWHIP_OK) g_trace.mark("planned");
+    return rc;
 }
 
 // First half of yawhip_count_pairs on ONE device: everything up to and including the copy of the results into the
@@ -3997,15 +4017,6 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     if (P.empty) return YAWHIP_OK;
     if (P.split) return SPLIT_JOBS;
     if (P.run_weighted) HIP_TRY(ctx->d_partials.reserve((size_t)std::max<int64_t>(P.n_items, 1) * P.slab));
-    ctx->d_jobs.ptr = reinterpret_cast<int32_t *>(P.d_in + P.o_jobs);
-    ctx->d_prefix.ptr = reinterpret_cast<int64_t *>(P.d_in + P.o_prefix);
-    ctx->d_t.ptr = reinterpret_cast<double *>(P.d_in + P.o_t);
-    ctx->d_dthr.ptr = reinterpret_cast<float *>(P.d_in + P.o_dthr);
-    ctx->d_rwin.ptr = reinterpret_cast<double *>(P.d_in + P.o_rwin);
-    ctx->d_ucap.ptr = reinterpret_cast<float *>(P.d_in + P.o_ucap);
-    ctx->d_thr32.ptr = reinterpret_cast<float *>(P.d_in + P.o_thr32);
-    ctx->d_tabs.ptr = reinterpret_cast<DevTab *>(P.d_in + P.o_tabs);
-    ctx->d_cprefix.ptr = reinterpret_cast<int64_t *>(P.d_in + P.o_cprefix);
     g_trace.mark("plan");
     // results: [counters][counts][sums] in one device buffer, zeroed by one memset (sums are always fully written) and
     // fetched by one copy
@@ -4013,9 +4024,9 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                  o_sums = o_counts + align16((size_t)P.n_out * sizeof(unsigned long long));
     const size_t out_bytes = o_sums + align16((size_t)P.n_out * sizeof(double));
     HIP_TRY(ctx->out.reserve(out_bytes));
-    ctx->d_ctr.ptr = reinterpret_cast<unsigned long long *>(ctx->out.d + o_ctr);
-    ctx->d_counts.ptr = reinterpret_cast<unsigned long long *>(ctx->out.d + o_counts);
-    ctx->d_sums.ptr = reinterpret_cast<double *>(ctx->out.d + o_sums);
+    ctx->d_ctr = reinterpret_cast<unsigned long long *>(ctx->out.d + o_ctr);
+    ctx->d_counts = reinterpret_cast<unsigned long long *>(ctx->out.d + o_counts);
+    ctx->d_sums = reinterpret_cast<double *>(ctx->out.d + o_sums);
     HIP_TRY(hipMemsetAsync(ctx->out.d, 0, P.n_items > 0 ? o_sums : out_bytes, ctx->stream));
 
     int launches = 0;
@@ -4040,19 +4051,19 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
             kept_flags = ctx->d_kept.ptr;
         }
         if (P.strip_items)
-            hipLaunchKernelGGL(k_build_items_strips, dim3(bgrid), dim3(bwg), 0, ctx->stream, ctx->d_tabs.ptr,
-                               reinterpret_cast<const JobRec *>(ctx->d_jobs.ptr), ctx->d_prefix.ptr, (int)P.n_sjobs,
+            hipLaunchKernelGGL(k_build_items_strips, dim3(bgrid), dim3(bwg), 0, ctx->stream, P.d_tabs,
+                               reinterpret_cast<const JobRec *>(P.d_jobs), P.d_prefix, (int)P.n_sjobs,
                                P.triple ? 0 : P.reach, (int)P.tile, P.rwin_max, P.cap_c, P.cap_s, P.swap ? 1 : 0, P.triple ? 1 : 0,
                                n_pot, ctx->d_items.ptr,
-                               ctx->d_ctr.ptr, kept_flags, seg_cap);
+                               ctx->d_ctr, kept_flags, seg_cap);
         else if (P.sweep)
             hipLaunchKernelGGL(k_build_items<true>, dim3(bgrid), dim3(bwg), 0, ctx->stream, view_of(c1), view_of(c2),
-                               ctx->d_jobs.ptr, ctx->d_prefix.ptr, (int)P.n_pslots, n_bins, (int)P.tile,
-                               ctx->d_rwin.ptr, n_pot, ctx->d_items.ptr, ctx->d_ctr.ptr, kept_flags);
+                               P.d_jobs, P.d_prefix, (int)P.n_pslots, n_bins, (int)P.tile,
+                               P.d_rwin, n_pot, ctx->d_items.ptr, ctx->d_ctr, kept_flags);
         else
             hipLaunchKernelGGL(k_build_items<false>, dim3(bgrid), dim3(bwg), 0, ctx->stream, view_of(c1), view_of(c2),
-                               ctx->d_jobs.ptr, ctx->d_prefix.ptr, (int)P.n_pslots, n_bins, (int)P.tile, ctx->d_rwin.ptr, n_pot,
-                               ctx->d_items.ptr, ctx->d_ctr.ptr, nullptr);
+                               P.d_jobs, P.d_prefix, (int)P.n_pslots, n_bins, (int)P.tile, P.d_rwin, n_pot,
+                               ctx->d_items.ptr, ctx->d_ctr, nullptr);
         HIP_TRY(hipGetLastError());
         ++launches;
         // The count kernels are launched over all potential items and return at once for indices beyond the
@@ -4063,7 +4074,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
             // dispatching workgroups that exit at once (measured at 1.6e6 potential items, 10M x 10M), more than
             // this round trip (~0.05 ms) costs. Small calls (one GPU's share of a sharded job list) skip it.
             // (The band kernel sizes its grid from the potential items and loops: no round trip.)
-            HIP_TRY(hipMemcpyAsync(ctx->out.h, ctx->d_ctr.ptr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(ctx->out.h, ctx->d_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
             n_items = (int64_t)reinterpret_cast<unsigned long long *>(ctx->out.h)[0];
         }
@@ -4073,7 +4084,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         HIP_TRY(hipMemsetAsync(ctx->d_jobwork.ptr, 0, sizeof(unsigned long long) * (size_t)n_jobs, ctx->stream));
         if (n_pot > 0) {
             hipLaunchKernelGGL(k_item_work, dim3((unsigned)((n_pot + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_items.ptr,
-                               ctx->d_ctr.ptr, P.merged ? 1 : n_bins, ctx->d_jobwork.ptr);
+                               ctx->d_ctr, P.merged ? 1 : n_bins, ctx->d_jobwork.ptr);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(job_work, ctx->d_jobwork.ptr, sizeof(int64_t) * (size_t)n_jobs, hipMemcpyDeviceToHost,
@@ -4081,21 +4092,20 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return YAWHIP_OK;
     }
-    // two-level ordered reduction of the weighted slabs (k_reduce_chunks / k_reduce_slots); prefix = first potential
-    // item of every output slot
-    auto reduce_partials = [&](int64_t n_oslots, int64_t values) -> hipError_t {
-        const int64_t n_chunks = P.n_chunks;  // (chunk prefix: in the plan's device tables, ctx->d_cprefix)
-        if (n_oslots != P.n_oslots) return hipErrorInvalidValue;
+    // two-level ordered reduction of the weighted slabs (k_reduce_chunks / k_reduce_slots), per output slot; prefix = first
+    // potential item of every output slot, chunk prefix = first chunk of every output slot
+    auto reduce_partials = [&]() -> hipError_t {
+        const int64_t n_oslots = P.n_pslots, values = P.slab, n_chunks = P.n_chunks;
         hipError_t er = ctx->d_chunk_sums.reserve((size_t)std::max<int64_t>(n_chunks, 1) * values);
         if (er != hipSuccess) return er;
         const int thr = 256;
         const bool all_kept = !(P.run_weighted && P.sweep);
         if (n_chunks > 0)
             hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((n_chunks * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                               ctx->d_partials.ptr, all_kept ? nullptr : ctx->d_kept.ptr, ctx->d_prefix.ptr, ctx->d_cprefix.ptr,
+                               ctx->d_partials.ptr, all_kept ? nullptr : ctx->d_kept.ptr, P.d_prefix, P.d_cprefix,
                                (int)n_oslots, (int)values, ctx->d_chunk_sums.ptr);
         hipLaunchKernelGGL(k_reduce_slots, dim3((unsigned)((n_oslots * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_chunk_sums.ptr, ctx->d_cprefix.ptr, (int)n_oslots, (int)values, ctx->d_sums.ptr);
+                           ctx->d_chunk_sums.ptr, P.d_cprefix, (int)n_oslots, (int)values, ctx->d_sums);
         return hipGetLastError();
     };
     HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
@@ -4122,7 +4132,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     const std::pair<int, int> stage{P.R, P.cap};
     const std::pair<bool, bool> rows{P.merged, P.uni};
     auto launch_band32 = [&](bool wgt) -> hipError_t {
-        const size_t lds = band32_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.merged && !P.uniform_t ? n_bins : 0, n_edges);
+        const size_t lds = band32_lds(P.weighted, P.cap, P.lean_bins * P.nf, P.merged && !P.uniform_t ? n_bins : 0, n_edges);
         const bool one_chunk = P.triple || !P.strip_items;  // every item has one window
         return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
             return pick<Int<4>, Int<3>, Int<2>>(n_edges, [&](auto ne) {
@@ -4133,9 +4143,9 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                         auto kern = one_chunk ? k_count_band32_one<S::R, S::CAP, w, ne, M::MERGED, M::UNI>
                                               : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
                         cs.variant[w] = variant_code(one_chunk ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
-                        return launch(kern, band_grid, wave, lds, ctx->stream, ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, ctx->d_t.ptr,
-                                      ctx->d_thr32.ptr, ctx->d_rwin.ptr, ctx->d_ucap.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr,
-                                      ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
+                        return launch(kern, band_grid, wave, lds, ctx->stream, P.d_tabs, ctx->d_items.ptr, n_bins, P.d_t,
+                                      P.d_thr32, P.d_rwin, P.d_ucap, flush_mask, P.swap ? 1 : 0, ctx->d_counts,
+                                      ctx->d_partials.ptr, ctx->d_ctr, seg_cap);
                     });
                 });
             });
@@ -4150,15 +4160,15 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                         using M = decltype(r);
                         cs.variant[w] = variant_code(VF_BAND, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
                         return launch(k_count_band<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, P.lds_band, ctx->stream,
-                                      ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_rwin.ptr, flush_mask,
-                                      P.hp_shift, w ? 0 : batch_log2, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                                      P.d_tabs, ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_rwin, flush_mask,
+                                      P.hp_shift, w ? 0 : batch_log2, ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr);
                     });
                 });
             });
         });
     };
     auto launch_fine = [&](bool wgt) -> hipError_t {
-        const size_t lds = band32_fine_lds(P.weighted_any, P.cap, P.lean_bins * P.nf, P.uniform_t ? 1 : n_bins, n_edges);
+        const size_t lds = band32_fine_lds(P.weighted, P.cap, P.lean_bins * P.nf, P.uniform_t ? 1 : n_bins, n_edges);
         return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
             return pick<Rows<true, false>, Rows<true, true>, Rows<false, false>, Rows<false, true>>(rows, [&](auto r) {
                 return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
@@ -4166,8 +4176,8 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                     using M = decltype(r);
                     cs.variant[w] = variant_code(VF_BAND32_FINE, S::R, S::CAP, w, 0, M::MERGED, M::UNI);
                     return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, lds, ctx->stream,
-                                  ctx->d_tabs.ptr, ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_thr32.ptr, ctx->d_rwin.ptr,
-                                  ctx->d_ucap.ptr, flush_mask, P.swap ? 1 : 0, ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr, seg_cap);
+                                  P.d_tabs, ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_thr32, P.d_rwin,
+                                  P.d_ucap, flush_mask, P.swap ? 1 : 0, ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr, seg_cap);
                 });
             });
         });
@@ -4190,9 +4200,9 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                         cs.variant[w] = variant_code(r <= 2 ? VF_MERGED_OCC8 : VF_MERGED,  // (the choice of pick_count_merged)
                                                       r, 0, w, 0, m, false, false, false, nf1);
                         return in_pieces(MWG, [&](dim3 g, int64_t base) {
-                            return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), P.lds_merged, ctx->stream, ctx->d_tabs.ptr,
-                                          ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, ctx->d_rwin.ptr, base,
-                                          ctx->d_counts.ptr, ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                            return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), P.lds_merged, ctx->stream, P.d_tabs,
+                                          ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_dthr, P.d_rwin, base,
+                                          ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr);
                         });
                     });
                 });
@@ -4211,8 +4221,8 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
                         cs.variant[w] = variant_code(VF_COUNT, r, 0, w, 0, false, false, pv, f);
                         return in_pieces(WG, [&](dim3 g, int64_t base) {
                             return launch(k_count<r, w, pv, f>, g, dim3(WG), lds_for(w, pv), ctx->stream, view_of(c1), view_of(c2),
-                                          ctx->d_items.ptr, n_bins, n_edges, ctx->d_t.ptr, ctx->d_dthr.ptr, base, ctx->d_counts.ptr,
-                                          ctx->d_partials.ptr, ctx->d_ctr.ptr);
+                                          ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_dthr, base, ctx->d_counts,
+                                          ctx->d_partials.ptr, ctx->d_ctr);
                         });
                     });
                 });
@@ -4231,14 +4241,14 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     if (n_items > 0 && P.run_weighted) {
         HIP_TRY(launch_count(true));
         ++launches;
-        HIP_TRY(reduce_partials(P.merged ? (int64_t)n_jobs : P.n_slots, P.slab));  // slabs are reduced per output slot
+        HIP_TRY(reduce_partials());
         launches += 2;
     }
     HIP_TRY(hipEventRecord(ctx->evc1, ctx->stream));
     if (!P.weighted && want_sums) {
         const int thr = 256;
         hipLaunchKernelGGL(k_counts_to_double, dim3((unsigned)((P.n_out + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_counts.ptr, ctx->d_sums.ptr, P.n_out);
+                           ctx->d_counts, ctx->d_sums, P.n_out);
         HIP_TRY(hipGetLastError());
         ++launches;
     }
@@ -4259,6 +4269,22 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     return YAWHIP_OK;
 }
 
+// Row r of a call's result `in` (nullptr: zeros) into row at[r] of `out` (at == nullptr: row r), rows of `row` values;
+// out == nullptr: not asked for.
+template <typename T>
+void place_rows(T *out, const T *in, int64_t n_rows, int64_t row, const int32_t *at = nullptr) {
+    if (!out) return;
+    if (!at) {  // contiguous: one piece
+        row *= n_rows;
+        n_rows = 1;
+    }
+    for (int64_t r = 0; r < n_rows; ++r) {
+        T *dst = out + (size_t)(at ? at[r] : 0) * (size_t)row;
+        if (in) memcpy(dst, in + (size_t)r * row, sizeof(T) * (size_t)row);
+        else memset(dst, 0, sizeof(T) * (size_t)row);
+    }
+}
+
 // Second half: wait for the context's stream, hand the results (contiguous rows of the jobs given to count_enqueue) and
 // the statistics over.
 // row_index != nullptr: row r of this call's result goes to row row_index[r] of the caller's arrays (rows of row_len values):
@@ -4268,17 +4294,10 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
 int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, double *fine_sums, yawhip_stats *stats,
                  const int32_t *row_index = nullptr, int64_t row_len = 0, bool wait_done = false) {
     if (stats) memset(stats, 0, sizeof *stats);
-    const int64_t n_rows = row_index && row_len > 0 ? cs.n_out / row_len : 0;
+    const int64_t n_rows = !row_index ? 1 : (row_len > 0 ? cs.n_out / row_len : 0), row = row_index ? row_len : cs.n_out;
     if (!cs.pending) {
-        if (!row_index) {
-            if (fine_counts) memset(fine_counts, 0, sizeof(int64_t) * (size_t)cs.n_out);
-            if (fine_sums) memset(fine_sums, 0, sizeof(double) * (size_t)cs.n_out);
-        } else {
-            for (int64_t r = 0; r < n_rows; ++r) {
-                if (fine_counts) memset(fine_counts + (size_t)row_index[r] * row_len, 0, sizeof(int64_t) * (size_t)row_len);
-                if (fine_sums) memset(fine_sums + (size_t)row_index[r] * row_len, 0, sizeof(double) * (size_t)row_len);
-            }
-        }
+        place_rows<int64_t>(fine_counts, nullptr, n_rows, row, row_index);
+        place_rows<double>(fine_sums, nullptr, n_rows, row, row_index);
         return YAWHIP_OK;
     }
     g_trace.mark("meanwhile");
@@ -4296,17 +4315,8 @@ int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, dou
         HIP_TRY(wait_done ? hipEventSynchronize(ctx->ev_done) : hipStreamSynchronize(ctx->stream));
     }
     g_trace.mark("waited");
-    if (!row_index) {
-        if (fine_counts) memcpy(fine_counts, ctx->out.h + cs.o_counts, sizeof(int64_t) * (size_t)cs.n_out);
-        if (fine_sums) memcpy(fine_sums, ctx->out.h + cs.o_sums, sizeof(double) * (size_t)cs.n_out);
-    } else {
-        const int64_t *hc = reinterpret_cast<const int64_t *>(ctx->out.h + cs.o_counts);
-        const double *hs = reinterpret_cast<const double *>(ctx->out.h + cs.o_sums);
-        for (int64_t r = 0; r < n_rows; ++r) {
-            if (fine_counts) memcpy(fine_counts + (size_t)row_index[r] * row_len, hc + (size_t)r * row_len, sizeof(int64_t) * (size_t)row_len);
-            if (fine_sums) memcpy(fine_sums + (size_t)row_index[r] * row_len, hs + (size_t)r * row_len, sizeof(double) * (size_t)row_len);
-        }
-    }
+    place_rows(fine_counts, reinterpret_cast<const int64_t *>(ctx->out.h + cs.o_counts), n_rows, row, row_index);
+    place_rows(fine_sums, reinterpret_cast<const double *>(ctx->out.h + cs.o_sums), n_rows, row, row_index);
     const unsigned long long *ctr = reinterpret_cast<const unsigned long long *>(ctx->out.h + cs.o_ctr);
     g_trace.mark("copied");
     if (stats) {
@@ -4525,12 +4535,10 @@ int yawhip_count_pairs(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_c
             if (fine_sums) rows_s.resize(nj * (size_t)row);
             rc = run_single(dc, a, b, (int32_t)nj, sub[d].data(), n_bins, n_edges, t, kernel, fine_counts ? rows_c.data() : nullptr,
                             fine_sums ? rows_s.data() : nullptr, &part);
-            if (rc == YAWHIP_OK)
-                for (size_t r = 0; r < nj; ++r) {
-                    const size_t j = (size_t)ctx->plan.parts[d][r];
-                    if (fine_counts) memcpy(fine_counts + j * (size_t)row, rows_c.data() + r * (size_t)row, sizeof(int64_t) * (size_t)row);
-                    if (fine_sums) memcpy(fine_sums + j * (size_t)row, rows_s.data() + r * (size_t)row, sizeof(double) * (size_t)row);
-                }
+            if (rc == YAWHIP_OK) {
+                place_rows(fine_counts, (const int64_t *)rows_c.data(), (int64_t)nj, row, ctx->plan.parts[d].data());
+                place_rows(fine_sums, (const double *)rows_s.data(), (int64_t)nj, row, ctx->plan.parts[d].data());
+            }
         } else {         // rows go from the device's pinned buffer straight into the caller's arrays
             rc = count_finish(dc, states[d], fine_counts, fine_sums, &part, ctx->plan.parts[d].data(), row);
         }
@@ -4571,8 +4579,7 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
         std::vector<double> rows((size_t)n_jobs * (size_t)row), full(n_full, 0.0);
         rc = run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, nullptr, rows.data(), stats);
         if (rc != YAWHIP_OK) return rc;
-        for (int j = 0; j < n_jobs; ++j)
-            memcpy(full.data() + (size_t)row_index[j] * row, rows.data() + (size_t)j * row, sizeof(double) * (size_t)row);
+        place_rows(full.data(), (const double *)rows.data(), n_jobs, row, row_index);
         HIP_TRY(hipMemcpy(ctx->d_full.ptr, full.data(), sizeof(double) * n_full, hipMemcpyHostToDevice));
         *device_rows = ctx->d_full.ptr;
         return YAWHIP_OK;
@@ -4582,7 +4589,7 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
     if (cs.pending && n_jobs > 0) {
         HIP_TRY(hipMemcpyAsync(ctx->d_rowidx.ptr, row_index, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
         const int64_t n = (int64_t)n_jobs * row;
-        hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_sums.ptr,
+        hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_sums,
                            ctx->d_rowidx.ptr, row, n, ctx->d_full.ptr);
         HIP_TRY(hipGetLastError());
     }
@@ -4649,10 +4656,6 @@ int dense_check(const yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_
     const int rc = check_call(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t);
     if (rc != YAWHIP_OK) return rc;
     if (n_scales <= 0 || !slices || !r.dense) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: bad sizes or NULL arrays");
-    const int64_t P = r.c1->n_patches;
-    for (int64_t j = 0; j < r.n_jobs; ++j)
-        if (r.jobs[2 * j] < 0 || r.jobs[2 * j] >= P || r.jobs[2 * j + 1] < 0 || r.jobs[2 * j + 1] >= P)
-            return fail(YAWHIP_ERR_INVALID, "job %lld has a patch id outside [0,%lld)", (long long)j, (long long)P);
     return YAWHIP_OK;
 }
 
@@ -4681,7 +4684,7 @@ int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins
         double *d_comb = reinterpret_cast<double *>(ctx->comb.d + ds.h_comb_off);
         if (ds.cs.pending && ds.n_comb > 0) {
             hipLaunchKernelGGL(k_combine_scales, dim3((unsigned)((ds.n_comb + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->d_counts.ptr, ctx->d_sums.ptr, ds.weighted ? 1 : 0, (int64_t)r.n_jobs, n_bins, nf, n_scales,
+                               ctx->d_counts, ctx->d_sums, ds.weighted ? 1 : 0, (int64_t)r.n_jobs, n_bins, nf, n_scales,
                                reinterpret_cast<const int32_t *>(ctx->comb.d),
                                fine_factors ? reinterpret_cast<const double *>(ctx->comb.d + b_slices) : nullptr, d_comb);
             HIP_TRY(hipGetLastError());
@@ -4693,39 +4696,25 @@ int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins
     return YAWHIP_OK;
 }
 
-int dense_blocking(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                   int32_t n_scales, const int32_t *slices, const double *fine_factors);
+// A request's result tensor cleared: unlinked slots and empty scales stay 0 (done while the device counts wherever the route
+// allows: 1 MB, 0.04 ms at the headline).
+void dense_clear(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scales) {
+    const size_t P = (size_t)r.c1->n_patches;
+    memset(r.dense, 0, sizeof(double) * (size_t)n_scales * (size_t)n_bins * P * P);
+}
 
-// Wait for a request's slot and write its result tensor: the host epilogue, O(jobs x B x S), of PatchLinkage.count_pairs
-// (reference src/yaw/correlation/measurements.py:354-364): halving of the doubly counted diagonal of an autocorrelation and
-// the scatter into [scale][bin][patch i][patch j]; unlinked slots are 0. Values come straight from the slot's pinned buffer.
-int dense_finish(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                 int32_t n_scales, const int32_t *slices, const double *fine_factors, DenseState &ds) {
-    if (!ds.enqueued) return dense_blocking(ctx, r, n_bins, n_edges, t, kernel, n_scales, slices, fine_factors);
+// The host epilogue, O(jobs x B x S), of PatchLinkage.count_pairs (reference src/yaw/correlation/measurements.py:354-364), into
+// the cleared tensor: halving of the doubly counted diagonal of an autocorrelation and the scatter into
+// [scale][bin][patch i][patch j]. The values of every route:
+//   comb != nullptr: [job][bin][scale], the per-scale sums of the fine bins (k_combine_scales, or the host's numpy_sum);
+//   else one fine bin per (job, bin): numpy's sum of one element is the element, times its separation weight -- hs
+//   (weighted), or hc: unweighted catalogues are counted in int64 and converted here (exact below 2^53, the reference's
+//   .astype(float64), trees.py:353).
+void dense_scatter(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scales, const int32_t *slices, const double *fine_factors,
+                   const double *comb, bool weighted, const int64_t *hc, const double *hs) {
     const int64_t P = r.c1->n_patches;
     const int32_t n_jobs = r.n_jobs;
     const int32_t *jobs = r.jobs;
-    double *dense = r.dense;
-    // (the result tensor is cleared while the device counts: 1 MB, 0.04 ms at the headline)
-    memset(dense, 0, sizeof(double) * (size_t)n_scales * (size_t)n_bins * (size_t)(P * P));
-    const int rc = count_finish(ctx, ds.cs, nullptr, nullptr, r.stats, nullptr, 0, /*wait_done=*/true);
-    if (rc != YAWHIP_OK) return rc;
-    if (!ds.cs.pending) return YAWHIP_OK;
-    if (ds.device_combine) {
-        const double *h_comb = reinterpret_cast<const double *>(ctx->comb.h + ds.h_comb_off);
-        for (int k = 0; k < n_bins; ++k)
-            for (int64_t j = 0; j < n_jobs; ++j) {
-                const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
-                const double f = (r.halve_diagonal && p == q) ? 0.5 : 1.0;
-                for (int s_ = 0; s_ < n_scales; ++s_)
-                    dense[(((size_t)s_ * n_bins + k) * P + p) * P + q] = h_comb[((size_t)j * n_bins + k) * n_scales + s_] * f;
-            }
-        return YAWHIP_OK;
-    }
-    // one fine bin per (job, bin): numpy's sum of one element is the element; unweighted catalogues are counted in int64 and
-    // converted here (exact below 2^53, the reference's .astype(float64), trees.py:353)
-    const int64_t *hc = reinterpret_cast<const int64_t *>(ctx->out.h + ds.cs.o_counts);
-    const double *hs = reinterpret_cast<const double *>(ctx->out.h + ds.cs.o_sums);
     // position and factor of every job, once; then job by job: a job's B values are read in one piece, each goes to its own
     // [P, P] slice (13 200 scattered stores at the headline)
     thread_local std::vector<int64_t> cell;
@@ -4738,22 +4727,26 @@ int dense_finish(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins,
     }
     const size_t PP = (size_t)(P * P);
     for (int s_ = 0; s_ < n_scales; ++s_) {
-        double *base = dense + (size_t)s_ * n_bins * PP;
+        double *base = r.dense + (size_t)s_ * n_bins * PP;
         for (int64_t j = 0; j < n_jobs; ++j) {
             double *dst = base + cell[(size_t)j];
             const double f = half[(size_t)j];
-            const int64_t *cj = hc + (size_t)j * n_bins;
-            const double *sj = hs + (size_t)j * n_bins;
             for (int k = 0; k < n_bins; ++k) {
-                if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared above)
-                const double v = ds.weighted ? sj[k] : (double)cj[k];
-                dst[(size_t)k * PP] = (fine_factors ? v * fine_factors[(size_t)k] : v) * f;
+                if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared)
+                const size_t at = (size_t)j * n_bins + k;
+                double v;
+                if (comb) {
+                    v = comb[at * n_scales + s_];
+                } else {
+                    v = weighted ? hs[at] : (double)hc[at];
+                    if (fine_factors) v = v * fine_factors[(size_t)k];
+                }
+                dst[(size_t)k * PP] = v * f;
             }
         }
     }
     g_trace.mark("scattered");
     g_trace.flush();
-    return YAWHIP_OK;
 }
 
 // The blocking route of one request: several devices in the context (the library splits the job list), or a job list that
@@ -4763,79 +4756,61 @@ int dense_blocking(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bin
     const yawhip_catalog *c1 = r.c1, *c2 = r.c2;
     const int32_t n_jobs = r.n_jobs;
     const int32_t *jobs = r.jobs;
-    const int32_t halve_diagonal = r.halve_diagonal;
-    double *dense = r.dense;
-    yawhip_stats *stats = r.stats;
     const int nf = n_edges - 1;
-    const int64_t P = c1->n_patches, row = (int64_t)n_bins * nf;
+    const int64_t row = (int64_t)n_bins * nf;
     const bool weighted = c1->w != nullptr || c2->w != nullptr;
-    // unweighted catalogues are counted in int64 and converted here (exact below 2^53, the reference's .astype(float64),
-    // trees.py:353): one kernel and half the device-to-host bytes less than asking the device for both
+    // unweighted catalogues are counted in int64 and converted on the host: one kernel and half the device-to-host bytes less
+    // than asking the device for both
     const size_t n_fine = (size_t)std::max<int64_t>((int64_t)n_jobs * row, 1);
     std::unique_ptr<double[]> fine_s(weighted ? new (std::nothrow) double[n_fine] : nullptr);
     std::unique_ptr<int64_t[]> fine_c(weighted ? nullptr : new (std::nothrow) int64_t[n_fine]);
     if (!fine_s && !fine_c) return fail(YAWHIP_ERR_OOM, "yawhip_count_pairs_dense: out of host memory");
-    // Host epilogue, O(jobs x B x E), of PatchLinkage.count_pairs (reference src/yaw/correlation/measurements.py:354-364 with
-    // src/yaw/catalog/trees.py:358-362,134-160 applied per job): separation weights, per-scale sums of the fine bins, halving
-    // of the doubly counted diagonal of an autocorrelation, scatter into [scale][bin][patch i][patch j]; unlinked slots are 0.
-    // The tensor is cleared while the device counts (1 MB, 0.04 ms at the headline) when the call runs on one device.
-    bool cleared = false;
+    bool cleared = false;  // (on one device the tensor is cleared while the device counts)
     const std::function<void()> clear = [&]() {
-        memset(dense, 0, sizeof(double) * (size_t)n_scales * (size_t)n_bins * (size_t)(P * P));
+        dense_clear(r, n_bins, n_scales);
         cleared = true;
     };
-    const int rc = ctx->peers.empty() ? run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), stats, &clear)
-                                      : yawhip_count_pairs(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), stats);
+    const int rc = ctx->peers.empty() ? run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats, &clear)
+                                      : yawhip_count_pairs(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats);
     if (rc != YAWHIP_OK) return rc;
     g_trace.mark("finished");
     if (!cleared) clear();
-    std::vector<double> scaled((size_t)nf);
-    std::vector<int64_t> cell((size_t)n_jobs);  // p * P + q and the factor of every job, once
-    std::vector<double> half((size_t)n_jobs);
-    for (int64_t j = 0; j < n_jobs; ++j) {
-        cell[(size_t)j] = (int64_t)jobs[2 * j] * P + jobs[2 * j + 1];
-        half[(size_t)j] = (halve_diagonal && jobs[2 * j] == jobs[2 * j + 1]) ? 0.5 : 1.0;
+    // Several fine bins: separation weights and the per-scale sums of the fine bins per job (reference
+    // src/yaw/catalog/trees.py:358-362,134-160), into the [job][bin][scale] layout of k_combine_scales, with its products
+    // (counts *= weights) and its order of additions
+    std::vector<double> comb;
+    if (nf > 1) {
+        comb.resize((size_t)n_jobs * n_bins * n_scales);
+        std::vector<double> scaled((size_t)nf);
+        for (int64_t j = 0; j < n_jobs; ++j)
+            for (int k = 0; k < n_bins; ++k) {
+                const size_t at = ((size_t)j * n_bins + k) * nf;
+                const double *wk = fine_factors ? fine_factors + (size_t)k * nf : nullptr;
+                for (int e = 0; e < nf; ++e) {
+                    const double v = weighted ? fine_s[at + e] : (double)fine_c[at + e];
+                    scaled[(size_t)e] = wk ? v * wk[e] : v;
+                }
+                for (int s_ = 0; s_ < n_scales; ++s_) {
+                    const int lo = slices[2 * ((int64_t)k * n_scales + s_)], hi = slices[2 * ((int64_t)k * n_scales + s_) + 1];
+                    comb[((size_t)j * n_bins + k) * n_scales + s_] = hi > lo ? numpy_sum(scaled.data() + lo, hi - lo) : 0.0;
+                }
+            }
     }
-    for (int k = 0; k < n_bins; ++k) {  // bin by bin: the scattered writes of one pass stay inside S slices of [P, P]
-        const double *wk = fine_factors ? fine_factors + (size_t)k * nf : nullptr;
-        if (nf == 1) {  // one value per (job, bin), the usual call: numpy's sum of one element is the element
-            for (int s_ = 0; s_ < n_scales; ++s_) {
-                const bool take = slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)];
-                if (!take) continue;  // (cleared above)
-                double *slice = dense + ((size_t)s_ * n_bins + k) * (size_t)(P * P);
-                const double w0 = wk ? wk[0] : 1.0;
-                if (weighted)
-                    for (int64_t j = 0; j < n_jobs; ++j) {
-                        const double v = fine_s[(size_t)j * row + (size_t)k];
-                        slice[cell[(size_t)j]] = (wk ? v * w0 : v) * half[(size_t)j];
-                    }
-                else
-                    for (int64_t j = 0; j < n_jobs; ++j) {
-                        const double v = (double)fine_c[(size_t)j * row + (size_t)k];
-                        slice[cell[(size_t)j]] = (wk ? v * w0 : v) * half[(size_t)j];
-                    }
-            }
-            continue;
-        }
-        for (int64_t j = 0; j < n_jobs; ++j) {
-            const double f = half[(size_t)j];
-            const size_t at = (size_t)j * row + (size_t)k * nf;
-            const double *fk = weighted ? fine_s.get() + at : scaled.data();
-            if (!weighted)
-                for (int e = 0; e < nf; ++e) scaled[(size_t)e] = (double)fine_c[at + (size_t)e];
-            if (wk) {  // counts *= weights (trees.py:358-360), then the sums
-                for (int e = 0; e < nf; ++e) scaled[(size_t)e] = fk[e] * wk[e];
-                fk = scaled.data();
-            }
-            for (int s_ = 0; s_ < n_scales; ++s_) {
-                const int lo = slices[2 * ((int64_t)k * n_scales + s_)], hi = slices[2 * ((int64_t)k * n_scales + s_) + 1];
-                const double acc = hi > lo ? numpy_sum(fk + lo, hi - lo) : 0.0;
-                dense[((size_t)s_ * n_bins + k) * (size_t)(P * P) + (size_t)cell[(size_t)j]] = acc * f;
-            }
-        }
-    }
-    g_trace.mark("scattered");
-    g_trace.flush();
+    dense_scatter(r, n_bins, n_scales, slices, fine_factors, nf > 1 ? comb.data() : nullptr, weighted, fine_c.get(), fine_s.get());
+    return YAWHIP_OK;
+}
+
+// Wait for a request's slot and write its result tensor (dense_scatter) from the slot's pinned buffers.
+int dense_finish(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
+                 int32_t n_scales, const int32_t *slices, const double *fine_factors, DenseState &ds) {
+    if (!ds.enqueued) return dense_blocking(ctx, r, n_bins, n_edges, t, kernel, n_scales, slices, fine_factors);
+    dense_clear(r, n_bins, n_scales);
+    const int rc = count_finish(ctx, ds.cs, nullptr, nullptr, r.stats, nullptr, 0, /*wait_done=*/true);
+    if (rc != YAWHIP_OK) return rc;
+    if (!ds.cs.pending) return YAWHIP_OK;
+    dense_scatter(r, n_bins, n_scales, slices, fine_factors,
+                  ds.device_combine ? reinterpret_cast<const double *>(ctx->comb.h + ds.h_comb_off) : nullptr, ds.weighted,
+                  reinterpret_cast<const int64_t *>(ctx->out.h + ds.cs.o_counts), reinterpret_cast<const double *>(ctx->out.h + ds.cs.o_sums));
     return YAWHIP_OK;
 }
 
