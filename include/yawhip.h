@@ -155,7 +155,9 @@ int yawhip_ctx_device_count(const yawhip_ctx *ctx, int *n);
  *   "spin_wait"         1 (default): the host waits for a call's results by polling the stream for the first 2 ms, then blocks;
  *                       0: it blocks at once
  *   "flush_stages_log2" band kernel: the 32-bit LDS counters of an item are flushed to the 64-bit result every
- *                       2^value stages (default 17: 128 lane objects x 192 entries x 2^17 < 2^32; tests lower it) */
+ *                       2^value stages (default 17: 128 lane objects x 192 entries x 2^17 < 2^32; tests lower it)
+ *   "hist_chunk_log2"   yawhip_redshift_histogram uploads its columns in chunks of 2^value objects (8..30, default 23);
+ *                       peak device memory does not grow with n (same results) */
 int yawhip_ctx_set_option(yawhip_ctx *ctx, const char *key, int64_t value);
 
 /*
@@ -304,6 +306,22 @@ int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint6
                       const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
                       double *z_out, int64_t *idx_out, uint64_t state_out[2], int32_t *has_uint32_out,
                       uint32_t *uinteger_out);
+
+/*
+ * Per-patch redshift histogram (HistData.from_catalog / _redshift_histogram, src/yaw/redshifts.py:44-57, 101-151).
+ *   z, w          float64[n] host columns, grouped by patch (the catalogue's own order); w may be NULL
+ *   offsets       int64[n_patches + 1], offsets[0] == 0, offsets[n_patches] == n, non-decreasing (empty patches allowed)
+ *   edges         float64[n_edges], strictly increasing, n_edges >= 2
+ *   closed_right  1: "right", 0: "left"
+ *   out           float64[n_patches][n_edges - 1] (host): object count (w == NULL) or sum of weights per patch and bin
+ * The reference's rule: first its mask (z > edges[0] when closed right, z < edges[B] when closed left), then numpy's
+ * histogram rule: bin i if edges[i] <= z < edges[i + 1], the last bin also takes z == edges[B]; values outside
+ * [edges[0], edges[B]] and NaN are dropped. Bins are decided by float64 comparisons against the given edges. Counts are
+ * exact; weighted sums are float64 per tile of at most 4096 objects of one patch, tiles summed in object order (ABI >= 6).
+ */
+int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const double *w, int32_t n_patches,
+                              const int64_t *offsets, int32_t n_edges, const double *edges, int32_t closed_right,
+                              double *out);
 
 /*
  * Host-only helper of the ingest path (no device, no context): stable grouping of float64 columns by an integer key --

@@ -24,7 +24,7 @@ from .corrfunc import CorrFunc
 from .measurements import PatchLinkage, autocorrelate, crosscorrelate
 from . import randoms
 from .paircounts import NormalisedCounts, PatchedCounts, PatchedSumWeights
-from .redshifts import RedshiftData
+from .redshifts import HistData, RedshiftData
 
 __version__ = "0.1.0"
 
@@ -36,6 +36,7 @@ __all__ = [
     "Configuration",
     "CorrData",
     "CorrFunc",
+    "HistData",
     "InconsistentPatchesError",
     "NormalisedCounts",
     "Patch",

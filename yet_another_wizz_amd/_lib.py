@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "yawhip_job_work",
     "yawhip_assign_patches",
     "yawhip_random_box",
+    "yawhip_redshift_histogram",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
 )
@@ -216,6 +217,9 @@ def load_library() -> ctypes.CDLL:
         _vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_uint32, ctypes.c_double,
         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p,
         ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
+    ]
+    lib.yawhip_redshift_histogram.argtypes = [
+        _vp, ctypes.c_int64, _dp, _dp, ctypes.c_int32, _i64p, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
     ]
     lib.yawhip_job_work.argtypes = [
         _vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _i64p,
@@ -571,5 +575,22 @@ def assign_patches(ctx: Context, x, y, z, centers_xyz) -> np.ndarray:
         load_library().yawhip_assign_patches(ctx._h, len(x), _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), len(centers),
                                              _ptr(centers, _dp), _ptr(out, _i32p)),
         "yawhip_assign_patches",
+    )
+    return out
+
+
+def redshift_histogram(ctx: Context, z, w, offsets, edges, closed_right: bool) -> np.ndarray:
+    """Run ``yawhip_redshift_histogram``: per-patch histogram (float64[P, B]) of the redshifts ``z`` grouped by patch
+    (``offsets`` int64[P + 1]); object counts without ``w``, sums of weights with it."""
+    z, w, edges = _f64(z), _f64(w), _f64(edges)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if w is not None and len(w) != len(z):
+        raise ValueError("redshifts and weights differ in length")
+    n_patches, n_edges = len(offsets) - 1, len(edges)
+    out = np.empty((max(n_patches, 0), max(n_edges - 1, 0)), dtype=np.float64)
+    _check(
+        load_library().yawhip_redshift_histogram(ctx._h, len(z), _ptr(z, _dp), _ptr(w, _dp), n_patches, _ptr(offsets, _i64p), n_edges,
+                                                 _ptr(edges, _dp), int(bool(closed_right)), _ptr(out, _dp)),
+        "yawhip_redshift_histogram",
     )
     return out

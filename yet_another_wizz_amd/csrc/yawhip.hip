@@ -58,6 +58,7 @@
 
 #include "yawhip.h"
 #include "yawhip_random.h"
+#include "yawhip_hist.h"
 #include "yawhip_sort.h"
 
 namespace {
@@ -2379,6 +2380,7 @@ struct yawhip_ctx : CallBufs {
     int strip_grid = 1;          // strip grid of newly uploaded catalogues: 1 = uniform in latitude (radians), 0 = linear in v (chord units)
     int band_trim = 1;           // strip builder and float32 band kernels trim u-windows and bands to the reachable caps (sep_angle)
     int default_kernel = YAWHIP_KERNEL_AUTO;
+    int hist_chunk_log2 = 23;    // yawhip_redshift_histogram: objects per upload = 2^hist_chunk_log2
     int lds_limit = 160 * 1024;
     int n_cu = 256;
     DevBuf<unsigned long long> d_jobwork;
@@ -3054,6 +3056,9 @@ int yawhip_ctx_set_option(yawhip_ctx *ctx, const char *key, int64_t value) {
         number(&yawhip_ctx::flush_log2);
     } else if (!strcmp(key, "band_fp32")) {
         flag(&yawhip_ctx::band_fp32);
+    } else if (!strcmp(key, "hist_chunk_log2")) {
+        if (value < 8 || value > 30) return fail(YAWHIP_ERR_INVALID, "hist_chunk_log2 must be in [8, 30]");
+        number(&yawhip_ctx::hist_chunk_log2);
     } else if (!strcmp(key, "kernel")) {
         if (value < YAWHIP_KERNEL_AUTO || value > YAWHIP_KERNEL_BAND)
             return fail(YAWHIP_ERR_INVALID, "unknown kernel id %lld", (long long)value);
@@ -4939,6 +4944,31 @@ int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const dou
     cleanup();
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_assign_patches failed: %s", hipGetErrorString(e));
+    return YAWHIP_OK;
+}
+
+int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const double *w, int32_t n_patches,
+                              const int64_t *offsets, int32_t n_edges, const double *edges, int32_t closed_right, double *out) {
+    if (!ctx || !offsets || !edges || !out) return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: NULL argument");
+    if (n < 0 || n_patches < 1 || n_edges < 2 || (n > 0 && !z))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: bad sizes (n=%lld n_patches=%d n_edges=%d) or NULL z",
+                    (long long)n, n_patches, n_edges);
+    if (closed_right != 0 && closed_right != 1) return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: closed_right must be 0 or 1");
+    if (offsets[0] != 0 || offsets[n_patches] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
+    for (int32_t p = 0; p < n_patches; ++p)
+        if (offsets[p + 1] < offsets[p]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
+    for (int32_t i = 0; i + 1 < n_edges; ++i)
+        if (!(edges[i + 1] > edges[i])) return fail(YAWHIP_ERR_INVALID, "bin edges must increase strictly (edge %d)", i + 1);
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawhist::HistCall c;
+    c.n = n, c.z = z, c.w = w;
+    c.n_patches = n_patches, c.offsets = offsets;
+    c.n_edges = n_edges, c.edges = edges, c.closed_right = closed_right;
+    c.chunk_log2 = ctx->hist_chunk_log2;
+    c.out = out;
+    const hipError_t e = yawhist::redshift_histogram(ctx->stream, c);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_redshift_histogram failed: %s", hipGetErrorString(e));
     return YAWHIP_OK;
 }
 

@@ -15,7 +15,7 @@ from . import _lib
 from .parallel import local_device_index, world
 
 __all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms",
-           "release", "default_kernel"]
+           "redshift_histogram", "release", "default_kernel"]
 
 _contexts: dict = {}
 default_kernel = "auto"
@@ -211,3 +211,11 @@ def draw_box_randoms(generator, num: int, chunksize: int):
         generator.y_min, generator.y_max - generator.y_min, generator.data_size, generator.weights, generator.redshifts)
     generator.rng.bit_generator.state = end
     return (x, y, w, z), end
+
+
+def redshift_histogram(z, w, offsets, edges, closed_right: bool) -> np.ndarray:
+    """Per-patch redshift histogram on the device (``yawhip_redshift_histogram``): float64[P, B] object counts, or sums of
+    weights with ``w``. One device does it, as for ``assign_patches``; unlike that there is no host fallback -- a
+    missing library or GPU raises ``YawhipError``."""
+    ctx = get_context(default_devices()[0])
+    return _lib.redshift_histogram(ctx, z, w, offsets, edges, closed_right)
