@@ -4720,8 +4720,7 @@ void dense_scatter(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scal
     const int64_t P = r.c1->n_patches;
     const int32_t n_jobs = r.n_jobs;
     const int32_t *jobs = r.jobs;
-    // position and factor of every job, once; then job by job: a job's B values are read in one piece, each goes to its own
-    // [P, P] slice (13 200 scattered stores at the headline)
+    // position and factor of every job, once per call (two short loops over the job list: well under a microsecond)
     thread_local std::vector<int64_t> cell;
     thread_local std::vector<double> half;
     cell.resize((size_t)n_jobs);
@@ -4730,26 +4729,39 @@ void dense_scatter(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scal
         cell[(size_t)j] = (int64_t)jobs[2 * j] * P + jobs[2 * j + 1];
         half[(size_t)j] = (r.halve_diagonal && jobs[2 * j] == jobs[2 * j + 1]) ? 0.5 : 1.0;
     }
+    // Slice by slice: the stores of a (scale, bin) land in one [P, P] slice (32 KB at the headline) while the reads walk the
+    // result block with a stride of one job's values -- 110 KB that stay in the cache over the bins. (Job by job, every store
+    // of a job went to another slice, P * P * 8 bytes apart: one cache set for all of them, 46 us at the headline against 19.)
     const size_t PP = (size_t)(P * P);
-    for (int s_ = 0; s_ < n_scales; ++s_) {
-        double *base = r.dense + (size_t)s_ * n_bins * PP;
-        for (int64_t j = 0; j < n_jobs; ++j) {
-            double *dst = base + cell[(size_t)j];
-            const double f = half[(size_t)j];
-            for (int k = 0; k < n_bins; ++k) {
-                if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared)
-                const size_t at = (size_t)j * n_bins + k;
-                double v;
-                if (comb) {
-                    v = comb[at * n_scales + s_];
+    auto slice = [&](double *dst, auto value) {
+        for (int64_t j = 0; j < n_jobs; ++j) dst[cell[(size_t)j]] = value(j) * half[(size_t)j];
+    };
+    for (int s_ = 0; s_ < n_scales; ++s_)
+        for (int k = 0; k < n_bins; ++k) {
+            if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared)
+            double *dst = r.dense + ((size_t)s_ * n_bins + (size_t)k) * PP;
+            if (comb) {
+                const double *src = comb + (size_t)k * n_scales + s_;
+                const size_t stride = (size_t)n_bins * n_scales;
+                slice(dst, [=](int64_t j) { return src[(size_t)j * stride]; });
+            } else if (weighted) {
+                const double *src = hs + k;
+                if (fine_factors) {
+                    const double fk = fine_factors[(size_t)k];
+                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins] * fk; });
                 } else {
-                    v = weighted ? hs[at] : (double)hc[at];
-                    if (fine_factors) v = v * fine_factors[(size_t)k];
+                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins]; });
                 }
-                dst[(size_t)k * PP] = v * f;
+            } else {
+                const int64_t *src = hc + k;
+                if (fine_factors) {
+                    const double fk = fine_factors[(size_t)k];
+                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins] * fk; });
+                } else {
+                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins]; });
+                }
             }
         }
-    }
     g_trace.mark("scattered");
     g_trace.flush();
 }
