@@ -143,8 +143,8 @@ def test_ragged_jobs_vs_oracle(ctx, kernel, nb2, weights):
 @pytest.mark.parametrize("n1", [300, 1200, 2600])
 def test_sparse_items_share_their_bands(ctx, n1, weights):
     """Lane tiles with a handful of objects facing ONE window that fits the stage: k_count_band32 shares the bands of the few
-    lanes that have one out over the wave (8, 4 or 2 lanes per lane's objects, every 8th / 4th / 2nd entry each; yawhip.hip,
-    YAW_B32_SHARE). Runs of ~15, ~60 and ~130 objects per (patch, strip); one annulus with common and with per-bin edges
+    lanes that have one out over the wave (8, 4 or 2 lanes per lane's objects, every 8th / 4th / 2nd entry each;
+    "Sparse items" in csrc/yawhip_band32.inc). Runs of ~15, ~60 and ~130 objects per (patch, strip); one annulus with common and with per-bin edges
     (thresholds per lane object), two scales sharing no edge (four edges, cumulative counters), 1, 2 and 4 objects per lane,
     with and without the strip grid, binned x unbinned and the binned catalogue against itself."""
     from yet_another_wizz_amd import _lib

@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
-"""Build a VARIANT of libyawhip.so for same-box A/B runs (build container; the result travels with gpurun):
+"""Build a VARIANT of libyawhip.so for same-box A/B runs:
 
-    python tools/build_variant.py diag1 -DYAW_BAND_DIAG=1      ->  yet_another_wizz_amd/build/variants/libyawhip_diag1.so
+    python tools/build_variant.py waves8 -DSOME_FLAG=8
+    python tools/build_variant.py diag1 --patch tools/experiments/band_diagnostics.patch -D<a mode of its header>=1
+        ->  yet_another_wizz_amd/build/variants/libyawhip_diag1.so
     YAW_AMD_LIB=yet_another_wizz_amd/build/variants/libyawhip_diag1.so python bench.py ...
 
-Only the kernel translation unit is recompiled; the in-tree product library is not touched."""
+Only the kernel translation unit is recompiled and linked with the product's other objects. With --patch FILE the unit is
+compiled from a patched COPY of csrc/ and include/yawhip.h under variants/src_<tag>/: neither the working tree nor the
+in-tree product library is touched."""
+import argparse
 import os
+import shutil
 import subprocess
 import sys
 
@@ -13,14 +19,29 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from yet_another_wizz_amd import build  # noqa: E402
 
-tag, flags = sys.argv[1], sys.argv[2:]
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("tag")
+ap.add_argument("--patch", metavar="FILE", help="unified diff against the repository root, applied to a copy of the sources")
+args, flags = ap.parse_known_args()  # everything else goes to hipcc
+
 out_dir = os.path.join(build.OBJ_DIR, "variants")
 os.makedirs(out_dir, exist_ok=True)
-build.build_library()  # the sort object comes from the regular build
-obj = os.path.join(out_dir, f"yawhip_{tag}.o")
-lib = os.path.join(out_dir, f"libyawhip_{tag}.so")
+build.build_library()  # the objects of the other translation units come from the regular build
+csrc, include = build.CSRC, build.INCLUDE
+if args.patch:
+    src_dir = os.path.join(out_dir, f"src_{args.tag}")
+    shutil.rmtree(src_dir, ignore_errors=True)
+    csrc = os.path.join(src_dir, os.path.relpath(build.CSRC, ROOT))
+    include = os.path.join(src_dir, os.path.relpath(build.INCLUDE, ROOT))
+    shutil.copytree(build.CSRC, csrc)
+    os.makedirs(include)
+    shutil.copy(os.path.join(build.INCLUDE, "yawhip.h"), include)
+    subprocess.check_call(["patch", "-p1", "--no-backup-if-mismatch", "-d", src_dir, "-i", os.path.abspath(args.patch)])
+obj = os.path.join(out_dir, f"yawhip_{args.tag}.o")
+lib = os.path.join(out_dir, f"libyawhip_{args.tag}.so")
 hipcc = build.hipcc_path()
-subprocess.check_call([hipcc, *build.HIPCC_FLAGS, *flags, f"-I{build.INCLUDE}", f"-I{build.CSRC}", "-c", build.SOURCES[0], "-o", obj])
-subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj,
-                       os.path.join(build.OBJ_DIR, os.path.basename(build.SOURCES[1]) + ".o")])
+subprocess.check_call([hipcc, *build.HIPCC_FLAGS, *flags, f"-I{include}", f"-I{csrc}", "-c",
+                       os.path.join(csrc, os.path.basename(build.SOURCES[0])), "-o", obj])
+others = [os.path.join(build.OBJ_DIR, os.path.basename(src) + ".o") for src in build.SOURCES[1:]]
+subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj, *others])
 print(lib)

@@ -70,8 +70,8 @@ def _built_with() -> str | None:
 
 
 def is_stale(extra_flags=()) -> bool:
-    """The library is missing, older than a source, or was built with another flag set (an experiment build such as
-    -DYAW_BAND_DIAG must never be mistaken for the product)."""
+    """The library is missing, older than a source, or was built with another flag set (a build with experiment
+    flags must never be mistaken for the product)."""
     if not os.path.exists(LIB):
         return True
     newest = max(os.path.getmtime(p) for p in (*SOURCES, *HEADERS))

@@ -87,15 +87,9 @@ thread_local Trace g_trace;
 
 constexpr int WG = 256;      // threads per workgroup = 4 waves of 64
 constexpr int STAGE = 256;   // streamed objects per LDS stage (one per thread)
-#ifndef YAW_MSTAGE
-#define YAW_MSTAGE 64
-#endif
-#ifndef YAW_MWG
-#define YAW_MWG 64
-#endif
-constexpr int MWG = YAW_MWG;        // threads per workgroup of the lean kernel (k_count_merged)
+constexpr int MWG = 64;      // threads per workgroup of the lean kernel (k_count_merged)
 static_assert(MWG == 64, "the band kernels are single-wave workgroups: their lane tile is 64 * R objects");
-constexpr int MSTAGE = YAW_MSTAGE;  // stage of the merged path: smaller -> less LDS -> more workgroups per CU
+constexpr int MSTAGE = 64;   // stage of the merged path: smaller -> less LDS -> more workgroups per CU
 constexpr int MAX_EDGES = 512;
 constexpr int SEG_STRIPS_MIN_RUN = 16;  // mean objects per (patch, bin, strip) run of the lane side from which mode 3 is used
 constexpr int BAND_MIN_STREAM_RUN = 64;  // AUTO: objects per run of the streamed side (as the typical object sees it) from which the band kernel is used
@@ -215,42 +209,6 @@ __host__ __device__ inline int item_orient(const Item &it) { return (int)((unsig
 typedef const __attribute__((address_space(1))) double *gf64p;
 typedef const __attribute__((address_space(1))) int32_t *gi32p;
 typedef const __attribute__((address_space(1))) int64_t *gi64p;
-#ifndef YAW_B32_PREFETCH
-#define YAW_B32_PREFETCH 0  // next trip's LDS reads issued before this trip's arithmetic: 0.404 against 0.379 ms (registers -> 5 waves)
-#endif
-#ifndef YAW_B32_UNROLL
-#define YAW_B32_UNROLL 1  // entries per trip of the walk loop: 1, 2 and 4 measure the same (0.362 / 0.366 / 0.374 ms at the headline)
-#endif
-#ifndef YAW_B32_PAIRS
-#define YAW_B32_PAIRS 1  // k_count_band32_one with one object per lane evaluates two entries per trip (packed float32)
-#endif
-#ifndef YAW_B32_SHARE
-#define YAW_B32_SHARE 1  // bands of sparse single-window items are shared out over the wave (k_count_band32)
-#endif
-#define YAW_STR_(x) #x
-#define YAW_STR(x) YAW_STR_(x)
-#ifndef YAW_B32_ITEM_PREFETCH
-#define YAW_B32_ITEM_PREFETCH 0  // the record of a workgroup's next item is fetched while it counts the present one
-#endif
-#ifndef YAW_B32_AW_EARLY
-#define YAW_B32_AW_EARLY 1  // weighted: a lane object's own weight is loaded with its coordinates instead of at the flush, the end of the
-                            // item's chain of dependent memory latencies (config #4: DD 0.370 -> 0.349, DR 1.67 -> 1.56, RR 3.20 -> 3.13 ms)
-#endif
-#ifndef YAW_B32_WAVES_W
-#define YAW_B32_WAVES_W 5  // waves per SIMD the weighted one-annulus variants are compiled for (96 VGPRs; the compiler took 97 by itself: 4 waves, 0.57 against 0.51 ms)
-#endif
-#ifndef YAW_B32_WAVES_W1
-#define YAW_B32_WAVES_W1 5  // ... with one object per lane (DD / RR of an autocorrelation: 82 VGPRs)
-#endif
-#ifndef YAW_B32_WAVES_BIG
-#define YAW_B32_WAVES_BIG 6  // ... the plain count with the big stage: its 6.3 KB of LDS admit 25 workgroups per CU anyway, and at 80 registers
-#endif                       // nothing is spilled (headline 0.305 -> 0.286 ms; 8: 0.343)
-#ifndef YAW_B32_WAVES_LT
-#define YAW_B32_WAVES_LT 1   // ... the plain count with per-bin thresholds (physical scales): the compiler's choice (87 registers, 5 waves)
-#endif
-#ifndef YAW_B32_WAVES
-#define YAW_B32_WAVES 1  // > 1: waves per SIMD every variant is compiled for (experiments). Default: 7 for the plain count (72 VGPRs
-#endif                   // instead of 79: 0.359 against 0.371 ms at the headline; 8 spills: 0.405), the compiler's choice elsewhere
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) float *gf32p;
@@ -290,13 +248,8 @@ struct JobRec {    // per job of a call
 // table is built and when it is queried, so for any w the first entry with key >= w and the first with key > w both lie in
 // [g[cell(w)], g[cell(w) + 1]] -- exactly, whatever the rounding of the product: the bisection over a run of 900 entries
 // (ten dependent loads) becomes one table look-up and four steps.
-#ifndef YAW_RUN_GRID
-#define YAW_RUN_GRID 64
-#endif
-#ifndef YAW_BUILD_BISECT
-#define YAW_BUILD_BISECT 32  // bisection steps of the strip builder inside a grid cell (fewer: the window is a superset, a few entries longer)
-#endif
-constexpr int RUN_GRID = YAW_RUN_GRID;
+constexpr int RUN_GRID = 64;
+constexpr int BUILD_BISECT = 32;  // most bisection steps of the strip builder inside a grid cell: as many as a 32-bit range can take
 struct RunGrid {
     double inv;                  // RUN_GRID / (last - first), 0 for a run with one distinct key
     uint32_t g[RUN_GRID + 2];    // + 1 pad: 8-byte multiple
@@ -402,10 +355,8 @@ constexpr int BUILD_WG = 1024;       // most threads per workgroup of the item b
 // Builder workgroups: one atomic per workgroup appends its items, so few large workgroups suit long lists (16 k atomics on
 // the one counter cost 0.15 ms at 4 M potential items), but 1024 threads make 300 workgroups for 256 CUs at the headline
 // and half the chip waits for the CUs that got two (+0.07 ms): 256 threads while that keeps the atomics below 4096.
-#ifndef YAW_BUILD_WG_SMALL
-#define YAW_BUILD_WG_SMALL 256
-#endif
-inline int build_wg_for(int64_t n_pot) { return n_pot / 256 <= 4096 ? YAW_BUILD_WG_SMALL : BUILD_WG; }
+constexpr int BUILD_WG_SMALL = 256;
+inline int build_wg_for(int64_t n_pot) { return n_pot / 256 <= 4096 ? BUILD_WG_SMALL : BUILD_WG; }
 constexpr int BUILD_PREFIX_LDS = 1024;  // job tables up to this many entries are searched in LDS by the strip builder (8 KB: no occupancy cost)
 
 // Append the kept items of a builder workgroup to the item list and add its evaluated-pair total: ONE atomic
@@ -557,11 +508,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
         const int o = jr.o & 3;  // orientation of the job: which pair of layouts it runs on
         it.pad_ = (jr.o >> 2) & 1;  // 1: diagonal job of a self count: lanes walk only the entries behind their own place (see k_merge_triples)
         // swap: the lane tiles come from the first catalogue of the job (the binned one), the windows from the second
-#if defined(YAW_BUILD_TABS_GLOBAL)  // (A/B: the records read from the table in global memory, as before)
-        const DevTab &c1 = tabs[swap ? 3 + o : o], &c2 = tabs[swap ? o : 3 + o];
-#else
         const DevTab &c1 = s_tabs[swap ? 3 + o : o], &c2 = s_tabs[swap ? o : 3 + o];
-#endif
         const gf64p key1d = tab_key(c1), key2 = tab_key(c2);
         const gf32p key1f = c1.axis == 0 ? c1.qx : (c1.axis == 1 ? c1.qy : c1.qz);
         auto key1 = [&](int64_t i) { return triple ? (double)key1f[i] : key1d[i]; };
@@ -619,7 +566,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
             sl[j] = l0; sh[j] = l1; ul[j] = u0; uh[j] = u1;  // all 0 for a dead window
         }
         // lower bounds (first index with key >= wlo) and upper bounds (first index with key > whi), all at once
-        for (int step = 0; step < YAW_BUILD_BISECT &&
+        for (int step = 0; step < BUILD_BISECT &&
                            ((sl[0] < sh[0]) | (sl[1] < sh[1]) | (sl[2] < sh[2]) | (ul[0] < uh[0]) | (ul[1] < uh[1]) | (ul[2] < uh[2])); ++step) {
             double kl[MAX_WIN], ku[MAX_WIN];
             uint32_t ml[MAX_WIN], mu[MAX_WIN];
@@ -638,9 +585,9 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
             }
         }
 #pragma unroll
-        for (int j = 0; j < MAX_WIN; ++j) {  // (a search cut short leaves sl <= first entry of the window, uh >= its end)
+        for (int j = 0; j < MAX_WIN; ++j) {
             wb[j] += sl[j];
-            wn[j] = (int32_t)((YAW_BUILD_BISECT < 32 ? uh[j] : ul[j]) - sl[j]);  // 0 for a dead window
+            wn[j] = (int32_t)(ul[j] - sl[j]);  // 0 for a dead window
         }
 #pragma unroll
         for (int j = 0; j < MAX_WIN; ++j) {  // non-empty windows to the front
@@ -925,11 +872,7 @@ __device__ __forceinline__ void count_merged_body(const DevTab *__restrict__ tab
     // Everything the item needs from global memory is requested here, back to back, before the first use:
     // lane objects, the key range of the wave, the first stage of the stream, thresholds (one memory latency).
     int64_t nb_total = b1 - b0;
-#ifdef YAW_DIAG_SKIP_STREAM
-    int nstages = 0;  // diagnostics: per-item fixed cost only (wrong counts)
-#else
     int nstages = (int)((nb_total + MSTAGE - 1) / MSTAGE);
-#endif
     constexpr int NPF = (MSTAGE + MWG - 1) / MWG;  // stage slots a thread fills
     struct Raw { double x, y, z; int k; bool in; };
     auto fetch_raw = [&](int64_t i) {  // streamed object i (clamped into the window: unconditional loads)
@@ -1022,9 +965,7 @@ __device__ __forceinline__ void count_merged_body(const DevTab *__restrict__ tab
         b0 = win == 1 ? it.b0[1] : it.b0[2];
         b1 = b0 + (win == 1 ? it.nb[1] : it.nb[2]);
         nb_total = b1 - b0;
-#ifndef YAW_DIAG_SKIP_STREAM
         nstages = (int)((nb_total + MSTAGE - 1) / MSTAGE);
-#endif
 #pragma unroll
         for (int f = 0; f < NPF; ++f) first[f] = fetch_raw(b0 + f * MWG + tid);
         __syncthreads();  // every lane is done with the previous window's last stage
@@ -1233,10 +1174,7 @@ auto pick_count_merged() -> decltype(&k_count_merged<R, WEIGHTED, NF1, MERGED>) 
 // XCD's L2 instead of being fetched by all eight.
 //   UNI: all redshift bins share one threshold row (angular scales): edges live in registers.
 // ------------------------------------------------------------------------------------------------
-#ifndef YAW_BCAP
-#define YAW_BCAP 192
-#endif
-constexpr int BCAP = YAW_BCAP;  // window objects per LDS stage. 192: the window of a 128-object lane tile at equal densities (128 +- 11
+constexpr int BCAP = 192;       // window objects per LDS stage. 192: the window of a 128-object lane tile at equal densities (128 +- 11
                                 // entries + one band) fits in one stage; 6.2 KB -> 26 single-wave workgroups per CU. Measured
                                 // 160 / 176 / 192 / 208 / 224: count kernel 0.545 / 0.529 / 0.523 / 0.535 / 0.531 ms at the headline
 constexpr int N_CTR = 8 + 8 * EVAL_SLOTS;  // counters: [0] kept items, [8 + 8 i] band entries, [9 + 8 i] exact re-evaluations, [10 + 8 i] lane-tile x window pairs
@@ -1505,11 +1443,7 @@ __global__ __launch_bounds__(64) void k_count_band(const DevTab *__restrict__ ta
             const unsigned a_key = a_sx + (c2.axis == 0 ? 0u : (c2.axis == 1 ? (unsigned)(LDS_Y - LDS_X) : (unsigned)(LDS_Z - LDS_X)));
             const unsigned a_sent = a_key + ((unsigned)n << 3);
             unsigned ql = a_key - 8u, qh = ql;
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG >= 2
-            for (unsigned step8 = 0; step8 >= 8u; step8 >>= 1) {  // diagnostics: no search either
-#else
             for (unsigned step8 = 8u << (31 - __builtin_clz(n)); step8 >= 8u; step8 >>= 1) {  // largest power of two <= n
-#endif
                 const unsigned pl = ql + step8, ph = qh + step8;
                 const double kl = lds_f64(pl < a_sent ? pl : a_sent), kh = lds_f64(ph < a_sent ? ph : a_sent);
                 ql = kl < klo ? pl : ql;    // entries [0, lo) have key <  klo
@@ -1519,11 +1453,7 @@ __global__ __launch_bounds__(64) void k_count_band(const DevTab *__restrict__ ta
             if (n_own == 0) lo = hi = n;  // lanes without an object walk the sentinel
             int len = hi - lo;
             nev += (unsigned int)(len * n_own);
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG >= 1
-            const int steps = 0;  // diagnostics: everything but the walk (wrong counts)
-#else
             const int steps = wave_max_nonneg(len);  // the longest band of the wave: uniform trip count
-#endif
 
             // Walk the band, one entry per trip, evaluated against the lane's R objects. A lane whose band has ended moves
             // on through the window (entries beyond a band have |du| > r_win, hence s > every upper edge: they fail the
@@ -1771,18 +1701,27 @@ __device__ __attribute__((noinline)) ExactEval<NT> band32_exact(gf64p lx, gf64p 
     return r;
 }
 
-#ifndef YAW_B32_CAP
-#define YAW_B32_CAP 320
-#endif
-#ifndef YAW_B32_CAP_BIG
-#define YAW_B32_CAP_BIG 512
-#endif
 // Stage of k_count_band32 (entries, 12 bytes each + 8 with weights). 320 holds two windows of a typical lane tile (128 objects
 // at equal densities: ~142 entries each) -- measured 192 / 288 / 320 / 448 at the headline: 0.367 / 0.355 / 0.350 / 0.360 ms,
 // weighted 0.521 / 0.519 / 0.511 / 0.556, RR of config #4 4.65 / 4.44 / 4.41 / 4.89 (the larger the stage, the fewer workgroups
 // a CU holds). The big one is for lane tiles whose single window would not fit (denser streamed side, four objects per lane).
-constexpr int B32_CAP = YAW_B32_CAP;
-constexpr int B32_CAP_BIG = YAW_B32_CAP_BIG;
+constexpr int B32_CAP = 320;
+constexpr int B32_CAP_BIG = 512;
+// Waves per SIMD the variants of k_count_band32 are compiled for (the second argument of their __launch_bounds__):
+constexpr int B32_WAVES_PLAIN = 7; // the plain count, one annulus, one threshold row: 72 VGPRs instead of 79, 0.359 against 0.371 ms at the
+                                   // headline (8 spills: 0.405)
+constexpr int B32_WAVES_BIG = 6;   // ... with the big stage: its 6.3 KB of LDS admit 25 workgroups per CU anyway, and at 80 registers
+                                   // nothing is spilled (headline 0.305 -> 0.286 ms; 8: 0.343)
+constexpr int B32_WAVES_W = 5;     // the weighted one-annulus variants (96 VGPRs; the compiler took 97 by itself: 4 waves, 0.57 against 0.51 ms)
+constexpr int B32_WAVES_W1 = 5;    // ... with one object per lane (DD / RR of an autocorrelation: 82 VGPRs)
+constexpr int B32_WAVES_LT = 1;    // the plain count with per-bin thresholds (physical scales): the compiler's choice (87 registers, 5 waves)
+constexpr int band32_min_waves(int R, int CAP, bool WEIGHTED, int NE, bool UNI) {
+    if (NE == 2 && UNI) {
+        if (WEIGHTED) return R == 1 ? B32_WAVES_W1 : B32_WAVES_W;
+        return CAP >= B32_CAP_BIG ? B32_WAVES_BIG : B32_WAVES_PLAIN;
+    }
+    return NE == 2 && !WEIGHTED ? B32_WAVES_LT : 1;  // everything else: the compiler's choice
+}
 // The kernel itself: csrc/yawhip_band32.inc, compiled twice -- k_count_band32 stages up to three windows (or pieces of one)
 // in a round, k_count_band32_one a single one, for calls whose items all have one window (merged triple runs, items of
 // k_build_items): the bookkeeping of two more chunks costs scalar registers (spilled) and instructions per item, 0.283 against
@@ -1921,9 +1860,6 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
         }
         unsigned int nev = 0;
         auto flush_counts = [&]() {  // LDS histogram -> global result (unweighted)
-#if defined(YAW_FINE_DIAG) && YAW_FINE_DIAG == 5
-            return;  // diagnostics: no flush (wrong counts)
-#endif
             __syncthreads();
             for (int idx = lane; idx < nslots; idx += 64) {
                 const unsigned int c = (unsigned int)hist[idx];
@@ -1986,11 +1922,7 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
             if (n_own == 0) lo = hi = n;
             const int len = hi - lo;
             nev += (unsigned int)(len * n_own);
-#if defined(YAW_FINE_DIAG) && YAW_FINE_DIAG == 1
-            const int steps = 0;  // diagnostics: everything but the walk (wrong counts)
-#else
             const int steps = wave_max_nonneg(len);
-#endif
 
             unsigned cur = a_stage + ((unsigned)lo << 2);
             const unsigned last = a_stage + ((unsigned)n << 2);
@@ -2072,9 +2004,6 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
                         pend[r] = hit ? cell : a_dummy;  // a miss adds to the lane's dummy cell
                     }
                 }
-#if defined(YAW_FINE_DIAG) && YAW_FINE_DIAG == 6
-                any_unc_mask = 0ull;  // diagnostics: no exact re-evaluation (wrong counts)
-#endif
                 if (any_unc_mask != 0ull) {
                     // the exact float64 predicate on the float64 columns decides, against the host's float64 thresholds (rare)
                     const unsigned eidx = (a16 - a_stage) >> 2;

@@ -4,18 +4,19 @@
 // macro of two inclusions rather than a template parameter because hipcc 7.2 emits no host stubs for this kernel as soon as a
 // template parameter sizes its chunk arrays. Not a translation unit of its own: everything it uses is defined in yawhip.hip.
 template <int R, int CAP, bool WEIGHTED, int NE, bool MERGED, bool UNI>
-__global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 && UNI ? (WEIGHTED ? (R == 1 ? YAW_B32_WAVES_W1 : YAW_B32_WAVES_W) : (CAP >= YAW_B32_CAP_BIG ? YAW_B32_WAVES_BIG : 7)) : (NE == 2 && !WEIGHTED ? YAW_B32_WAVES_LT : 1)))) void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
-                                                     const double *__restrict__ t, const float *__restrict__ thr32,
-                                                     const double *__restrict__ rwin_k, const float *__restrict__ ucap,
-                                                     unsigned flush_mask, int swap,
-                                                     unsigned long long *__restrict__ out_counts,
-                                                     double *__restrict__ partials,
-                                                     unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
+__global__ __launch_bounds__(64, band32_min_waves(R, CAP, WEIGHTED, NE, UNI))
+void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
+                  const double *__restrict__ t, const float *__restrict__ thr32,
+                  const double *__restrict__ rwin_k, const float *__restrict__ ucap,
+                  unsigned flush_mask, int swap,
+                  unsigned long long *__restrict__ out_counts,
+                  double *__restrict__ partials,
+                  unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
     static_assert(NE >= 2 && NE <= 4, "edges per bin");
     constexpr int CH = YAW_B32_CH;  // chunks per round (see yawhip.hip)
     // One object per lane (sparse per-bin runs) in the one-chunk kernel: two ENTRIES per trip of the walk, see eval_entry.
     // (A chunk is then followed by two sentinel entries; with several chunks in a stage the second would be the next chunk's first.)
-    constexpr bool PAIRS = YAW_B32_PAIRS && R == 1 && CH == 1;
+    constexpr bool PAIRS = R == 1 && CH == 1;
     constexpr int NS = PAIRS ? 2 : R;  // evaluations per trip
     static_assert(CH == 1 || CH == 3, "chunks per round");
     static_assert(CAP % 4 == 0, "stage capacity");
@@ -45,39 +46,11 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
     if (LANE_THR)
         for (int e = lane; e < n_bins * TW; e += 64) sthr[e] = thr32[e];
     unsigned round_no = 0;
-#if YAW_B32_ITEM_PREFETCH
-    // The record of the NEXT item is fetched while this one is counted: the list was written by the builder just before and
-    // comes from memory -- a round trip at the head of every item's chain of dependent latencies (record -> lane objects and
-    // LDS-DMA -> search -> walk -> flush), which is what the per-bin items of binned x binned counts consist of. Lane j < 16
-    // holds word j of the record in ONE vector register (sixteen scalar registers would be spilled); the wait for the stage
-    // covers the load.
-    auto ticket_at = [&](unsigned long long vv) { return (vv >> 3) >= tmap.per_xcd ? ~0ull : tmap.ticket(vv); };
-    unsigned long long ticket_next = ticket_at(blockIdx.x);
-    unsigned int it_word = 0u;
-    auto fetch_item = [&]() {
-        if (ticket_next < n_kept && lane < 16) it_word = reinterpret_cast<const unsigned int *>(items + ticket_next)[lane];
-    };
-    fetch_item();
-#endif
     for (unsigned long long v = blockIdx.x;; v += gridDim.x) {
         if ((v >> 3) >= tmap.per_xcd) break;
-#if YAW_B32_ITEM_PREFETCH
-        const unsigned long long ticket = ticket_next;
-        Item it;
-        {
-            unsigned int wd[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) wd[j] = __builtin_amdgcn_readlane(it_word, j);
-            __builtin_memcpy(&it, wd, sizeof(Item));
-        }
-        ticket_next = ticket_at(v + gridDim.x);
-        fetch_item();
-        if (ticket >= n_kept) continue;  // beyond the last block's end
-#else
         const unsigned long long ticket = tmap.ticket(v);
         if (ticket >= n_kept) continue;  // beyond the last block's end
         const Item it = items[ticket];
-#endif
         const int o = item_orient(it), islot = item_slot(it);
         const DevTab cl = tabs[swap ? o : 3 + o], cs = tabs[swap ? 3 + o : o];  // lane side, streamed side
         const int kfix = MERGED ? 0 : islot % n_bins;
@@ -149,7 +122,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
         f32x2 ax2[R / 2 > 0 ? R / 2 : 1], ay2[R / 2 > 0 ? R / 2 : 1], az2[R / 2 > 0 ? R / 2 : 1];  // packed pairs (R even)
         float ax[R], ay[R], az[R];
         int kb[R];
-        double aw_own[R];  // (YAW_B32_AW_EARLY)
+        double aw_own[R];  // weighted: the lane objects' own weights
         int lane_obj = lane;  // whose objects this lane counts for: its own, until the bands of a sparse item are shared out
         int n_own = (int)it.na - lane * R;
         n_own = n_own < 0 ? 0 : (n_own > R ? R : n_own);
@@ -161,11 +134,10 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
             ay[r] = have ? (cl.qy + it.a0)[ic] : PAD_COORD32;
             az[r] = have ? (cl.qz + it.a0)[ic] : PAD_COORD32;
             kb[r] = MERGED ? (have ? (cl.k + it.a0)[ic] : 0) : 0;
-#if YAW_B32_AW_EARLY
             // weighted: the object's own weight travels with its coordinates (one memory latency for both) instead of being
-            // fetched at the flush, at the end of the item's chain of dependent latencies
+            // fetched at the flush, at the end of the item's chain of dependent latencies (config #4: DD 0.370 -> 0.349,
+            // DR 1.67 -> 1.56, RR 3.20 -> 3.13 ms)
             if constexpr (WEIGHTED) aw_own[r] = (cl.w && have) ? (cl.w + it.a0)[ic] : 1.0;
-#endif
         }
         // thresholds: per lane object (its bin's row from the LDS table) or one row for the wave
         float th[R][TW];
@@ -222,12 +194,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                         const double vsum = NE == 2 ? acc[r][0] : acc[r][f + 1] - acc[r][f];
                         // float64 adds of ONE instruction that hit the same cell are serialised by the LDS in a fixed lane
                         // order; the histogram belongs to this wave alone -> reproducible sums
-                        // (the object's own weight is fetched here, once per item, instead of living in registers through the walk)
-#if YAW_B32_AW_EARLY
                         const double aw = aw_own[r];
-#else
-                        const double aw = (cl.w && r < n_own) ? (cl.w + it.a0)[lane_obj * R + r] : 1.0;
-#endif
                         if (vsum != 0.0)
                             (void)__hip_atomic_fetch_add((__attribute__((address_space(3))) double *)(size_t)cell, HALF ? aw * vsum * pair_mult : aw * vsum,
                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -252,7 +219,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
             }
         };
 
-        const bool single_window = it.nwin == 1 && it.nb[0] + 1 <= CAP;  // the item is this one chunk (see YAW_B32_SHARE)
+        const bool single_window = it.nwin == 1 && it.nb[0] + 1 <= CAP;  // the item is this one chunk (its bands may be shared out, below)
         for (;; ++round_no) {
             // The round has landed: nothing but the issuing wave's own vmcnt orders an LDS read behind a pending LDS-DMA. The
             // wait is spelled out -- in a single-wave workgroup __syncthreads() is no barrier instruction, and on this loop's
@@ -288,11 +255,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                 ql[c] = qh[c] = a_key[c] - 4u;
                 n_max = cn[c] > n_max ? cn[c] : n_max;
             }
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == 2
-            for (unsigned step = 0; step >= 4u; step >>= 1) {  // diagnostics: no search either
-#else
             for (unsigned step = 4u << (31 - __builtin_clz(n_max)); step >= 4u; step >>= 1) {  // largest power of two <= n_max
-#endif
 #pragma unroll
                 for (int c = 0; c < CH; ++c) {
                     if (c < nch) {
@@ -321,10 +284,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
             }
             int len = hi - lo;
             unsigned stride = PAIRS ? 8u : 4u;  // bytes between the entries (pairs of entries) a lane evaluates (wave-uniform)
-#if !defined(YAW_BAND_DIAG) || YAW_BAND_DIAG != 3
             nev += (unsigned int)(len * n_own);
-#endif
-#if YAW_B32_SHARE
             // Sparse items -- a lane tile at the border of its patch whose partner run reaches only a few of its objects, the
             // short last tile of a run: the walk takes as many trips as the longest band however few lanes have one (a seventh
             // of all trips at the headline belonged to windows with bands in at most 32 lanes). When the lanes with a band
@@ -351,9 +311,7 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                     for (int r = 0; r < R; ++r) {
                         if constexpr (R < 2) { ax[r] = __shfl(ax[r], src, 64); ay[r] = __shfl(ay[r], src, 64); az[r] = __shfl(az[r], src, 64); }
                         if constexpr (MERGED) kb[r] = __shfl(kb[r], src, 64);
-#if YAW_B32_AW_EARLY
                         if constexpr (WEIGHTED) aw_own[r] = __shfl(aw_own[r], src, 64);
-#endif
                         if constexpr (LANE_THR) {
 #pragma unroll
                             for (int q = 0; q < TW; ++q) th[r][q] = sthr[kb[r] * TW + q];
@@ -381,43 +339,19 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                     }
                 }
             }
-#endif
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG >= 1 && YAW_BAND_DIAG < 3
-            const int steps = 0;  // diagnostics: everything but the walk (wrong counts)
-#else
             const int steps = wave_max_nonneg(PAIRS ? (len + 1) >> 1 : len);  // the longest band of the wave: uniform trip count
-#endif
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == 3
-#ifdef YAW_DIAG_ACT   // ... of the (item, window)s with at most YAW_DIAG_ACT lanes that have a band at all
-            int act = __popcll(__builtin_amdgcn_ballot_w64(len > 0));
-            asm volatile("" : "+s"(act));  // the ballot stays in front of the lane-0 branch
-            nev += lane == 0 && act <= YAW_DIAG_ACT ? (unsigned int)steps : 0u;
-#else
-            nev += lane == 0 ? (unsigned int)steps : 0u;  // diagnostics: "evaluated" reports the trips of the walk
-#endif
-#endif
 
             const unsigned a_chunk = a_stage + ((unsigned)co[c] << 2);
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == 4
-            unsigned cur = a_chunk + ((unsigned)lane << 2);  // diagnostics: the walk without LDS bank conflicts (wrong counts)
-#else
             unsigned cur = a_chunk + ((unsigned)lo << 2);
-#endif
             const unsigned last = a_chunk + ((unsigned)n << 2);
             // One entry per evaluation step: three 4-byte reads from columns a fixed distance apart (lanes read nearly
-            // consecutive words of a column). YAW_B32_UNROLL entries per trip of the loop: their LDS reads go out together and the
-            // loop's own instructions are shared (a trip past the end of the longest band meets entries beyond every band,
-            // or the sentinel: they fail the predicate by themselves).
+            // consecutive words of a column). A trip past the end of the longest band meets entries beyond every band, or
+            // the sentinel: they fail the predicate by themselves.
             auto eval_entry = [&](const unsigned a16) {
                 // PAIRS (one object per lane, one chunk per round): the trip evaluates TWO neighbouring entries for the lane's
                 // object -- the packed float32 instructions that serve two objects per entry elsewhere serve two entries per
                 // object here (evaluation i = entry a16 + 4 i of object 0); otherwise evaluation i = object i of the entry.
                 struct { float x, y, z; } en, en1;
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == -1
-                en.x = klo; en.y = khi; en.z = klo;  // diagnostics: the walk's arithmetic without its LDS reads (wrong counts)
-                asm volatile("" : "+v"(en.x), "+v"(en.y), "+v"(en.z));
-                en1 = en;
-#else
                 en.x = *(const __attribute__((address_space(3))) float *)(size_t)a16;
                 en.y = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + COLB);
                 en.z = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 2 * COLB);
@@ -426,7 +360,6 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                     en1.y = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 4u + COLB);
                     en1.z = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 4u + 2 * COLB);
                 }
-#endif
                 double ewi[NS];
                 const unsigned a_w = ((a16 - a_stage) << 1) + a_sw;  // the entry's weight (one address for both entries of a pair)
                 ewi[0] = WEIGHTED ? lds_f64(a_w) : 1.0;
@@ -435,10 +368,6 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
 #pragma unroll
                     for (int i = 1; i < NS; ++i) ewi[i] = ewi[0];
                 }
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == -2
-                cnt[0][0] += __float_as_uint(en.x) ^ __float_as_uint(en.y) ^ __float_as_uint(en.z);  // diagnostics: the LDS reads alone
-                return;
-#endif
                 // One annulus: the centre c of the annulus is the addend of the first product, q = s32 - c comes out of the three
                 // fused multiply-adds (no subtraction per evaluation; the host widens both classes by the rounding of the
                 // intermediate sums, build_thr32). More edges: s32 itself.
@@ -493,10 +422,6 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                     }
                     any_mask |= unc_mask[i];
                 }
-#if defined(YAW_BAND_DIAG) && YAW_BAND_DIAG == 5
-                any_mask = 0ull;  // diagnostics: no guard bands at all -- neither the "possibly" compares nor the exact re-evaluation
-                                  // (NOT a reachable state: it also drops a seventh of the walk's vector instructions; counts off by ~1e-4)
-#endif
                 if (any_mask != 0ull) {
                     // inside a guard band: the exact float64 predicate on the float64 columns decides (rare)
 #pragma unroll
@@ -527,20 +452,17 @@ __global__ __launch_bounds__(64, (YAW_B32_WAVES > 1 ? YAW_B32_WAVES : (NE == 2 &
                     }
                 }
             };
-#if defined(YAW_WALK_ALIGN)
-            asm volatile(".p2align " YAW_STR(YAW_WALK_ALIGN));  // experiment: where the walk loop starts relative to the instruction cache lines
-#endif
-#if defined(YAW_WALK_PAD)
+            // UNROLL entries per trip of the loop: their LDS reads go out together and the loop's own instructions are shared.
+            // 1, 2 and 4 measure the same (0.362 / 0.366 / 0.374 ms at the headline). The loop keeps its two levels at depth 1:
+            // written as one plain loop, hipcc 7.2 schedules every variant differently (and, in sum, to more instructions).
+            constexpr int UNROLL = 1;
+            for (int s = 0; s < steps; s += UNROLL) {
 #pragma unroll
-            for (int pp = 0; pp < YAW_WALK_PAD; ++pp) asm volatile("s_nop 0");  // experiment: shift the walk loop by 4-byte steps
-#endif
-            for (int s = 0; s < steps; s += YAW_B32_UNROLL) {
-#pragma unroll
-                for (int uu = 0; uu < YAW_B32_UNROLL; ++uu) {
+                for (int uu = 0; uu < UNROLL; ++uu) {
                     const unsigned at = cur + stride * (unsigned)uu;
                     eval_entry(at < last ? at : last);
                 }
-                cur += stride * YAW_B32_UNROLL;
+                cur += stride * UNROLL;
             }
             }
             }
