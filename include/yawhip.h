@@ -183,6 +183,29 @@ int yawhip_catalog_upload(yawhip_ctx *ctx, int64_t n, const double *x, const dou
 int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
                                const double *w, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
                                int32_t sort_axis, yawhip_catalog **out);
+/*
+ * One catalogue with a scalar field ("kappa") as the TWO catalogues a scalar count runs on (ABI 6, additive; replaces the
+ * per-count weight product of AngularTree.get_pair_weights, trees.py:270-301): the coordinates are copied to the device once
+ * and every (patch, bin) segment is sorted once, then one gather writes
+ *   cat_n   the catalogue yawhip_catalog_upload_axis(x, y, z, w) makes (unweighted when w is NULL): the "n" side
+ *   cat_k   the same objects in the same order with the weight column kappa * w (kappa when w is NULL): the "k" side
+ *   kappa   float64[n], any sign
+ * The product is one float64 multiply on the device, rounded on its own: cat_k is, bit for bit, the catalogue
+ * yawhip_catalog_upload_axis makes from a host column kappa * w. Both are ordinary catalogues -- each has its own identity
+ * for the plans, builds its strip layouts as any other, is replicated on every device of a multi-device context and is
+ * released by its own yawhip_catalog_free. On failure neither is returned: both are NULL, whichever check failed.
+ */
+int yawhip_catalog_upload_scalar(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
+                                 const double *w, const double *kappa, int32_t n_patches, int32_t n_bins_or_1,
+                                 const int64_t *offsets, int32_t sort_axis, yawhip_catalog **cat_n, yawhip_catalog **cat_k);
+/*
+ * Sum of the weight column over every (patch, bin) segment of a resident catalogue (ABI 6, additive; AngularTree.sum_weights
+ * and .sum_kappa, trees.py:225-244, for all trees at once: cat_n gives sum w, cat_k sum kappa * w).
+ *   sums   float64[P * n_bins_or_1] (host), segment order of the offsets; an unweighted catalogue reports its object counts
+ * Summed on the device in a fixed order per segment (256 strided partial sums, folded in halves): the same catalogue gives the
+ * same bits every time; numpy's pairwise sum of the same values agrees to rounding. No atomics.
+ */
+int yawhip_catalog_segment_sums(const yawhip_catalog *cat, double *sums);
 int yawhip_catalog_sort_axis(const yawhip_catalog *cat, int32_t *axis);
 int yawhip_catalog_free(yawhip_catalog *cat);
 /* Device bytes held by a catalogue (for memory accounting). */

@@ -20,10 +20,11 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import CorrFunc
-from .measurements import PatchLinkage, autocorrelate, crosscorrelate
+from .corrfunc import CorrFunc, ScalarCorrFunc
+from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
+                           crosscorrelate_scalar)
 from . import randoms
-from .paircounts import NormalisedCounts, PatchedCounts, PatchedSumWeights
+from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
 
 __version__ = "0.1.0"
@@ -39,13 +40,18 @@ __all__ = [
     "HistData",
     "InconsistentPatchesError",
     "NormalisedCounts",
+    "NormalisedScalarCounts",
     "Patch",
     "PatchLinkage",
     "PatchedCounts",
     "PatchedSumWeights",
     "RedshiftData",
     "SampledData",
+    "ScalarCorrFunc",
     "autocorrelate",
+    "autocorrelate_scalar",
+    "compute_scalar_normalisation",
     "crosscorrelate",
+    "crosscorrelate_scalar",
     "randoms",
 ]

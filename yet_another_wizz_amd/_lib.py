@@ -33,6 +33,8 @@ ABI_SYMBOLS = (
     "yawhip_ctx_set_option",
     "yawhip_catalog_upload",
     "yawhip_catalog_upload_axis",
+    "yawhip_catalog_upload_scalar",
+    "yawhip_catalog_segment_sums",
     "yawhip_catalog_sort_axis",
     "yawhip_catalog_free",
     "yawhip_catalog_device_bytes",
@@ -193,6 +195,11 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_catalog_upload_axis.argtypes = [
         _vp, ctypes.c_int64, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _i64p, ctypes.c_int32, ctypes.POINTER(_vp),
     ]
+    lib.yawhip_catalog_upload_scalar.argtypes = [
+        _vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _i64p, ctypes.c_int32, ctypes.POINTER(_vp),
+        ctypes.POINTER(_vp),
+    ]
+    lib.yawhip_catalog_segment_sums.argtypes = [_vp, _dp]
     lib.yawhip_catalog_sort_axis.argtypes = [_vp, ctypes.POINTER(ctypes.c_int32)]
     lib.yawhip_catalog_free.argtypes = [_vp]
     lib.yawhip_catalog_device_bytes.argtypes = [_vp, _i64p]
@@ -314,6 +321,19 @@ class DeviceCatalog:
         """``strip_micro``: spacing of the strip grid of the cross-correlation layout in 1e-6 rad of
         latitude -- 1e-6 chord units where the context's ``strip_grid`` option is 0 (linear in v) --
         (0 = no strips, None = whatever the context is set to)."""
+        x, y, z, w, offsets = self._prepare(ctx, x, y, z, w, n_patches, n_bins_or_1, offsets, sort_axis, strip_micro)
+        _check(
+            load_library().yawhip_catalog_upload_axis(
+                ctx._h, self.n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), self.n_patches, self.n_bins,
+                _ptr(offsets, _i64p), int(sort_axis), ctypes.byref(self._h),
+            ),
+            "yawhip_catalog_upload_axis",
+        )
+        ctx._catalogs.add(self)
+
+    def _prepare(self, ctx, x, y, z, w, n_patches, n_bins_or_1, offsets, sort_axis, strip_micro, weighted=None):
+        """Checks and attributes shared by the two ways a catalogue reaches the device; returns the arrays as the library
+        takes them."""
         x, y, z, w = _f64(x), _f64(y), _f64(z), _f64(w)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(x)
@@ -323,22 +343,44 @@ class DeviceCatalog:
             raise ValueError("offsets must have n_patches * n_bins_or_1 + 1 entries")
         self.ctx = ctx  # keep the context alive
         self.n, self.n_patches, self.n_bins = n, int(n_patches), int(n_bins_or_1)
-        self.weighted = w is not None
+        self.weighted = (w is not None) if weighted is None else bool(weighted)
         self._h = _vp()
         if strip_micro is not None:
             ctx.set_option("strip_width_micro", int(strip_micro))
             ctx.strip_micro = int(strip_micro)
         self.strip_micro = ctx.strip_micro
         self.strip_grid = ctx.strip_grid
-        _check(
-            load_library().yawhip_catalog_upload_axis(
-                ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), self.n_patches, self.n_bins,
-                _ptr(offsets, _i64p), int(sort_axis), ctypes.byref(self._h),
-            ),
-            "yawhip_catalog_upload_axis",
-        )
         self.sort_axis = int(sort_axis)
-        ctx._catalogs.add(self)
+        return x, y, z, w, offsets
+
+    @classmethod
+    def upload_scalar(cls, ctx: Context, x, y, z, w, kappa, n_patches: int, n_bins_or_1: int, offsets, sort_axis: int = 2,
+                      strip_micro: int | None = None):
+        """``yawhip_catalog_upload_scalar``: the plain catalogue and its twin weighted by ``kappa * w`` (``kappa`` without
+        ``w``) from one copy of the coordinates and one segment sort -> ``(cat_n, cat_k)``."""
+        cat_n, cat_k = cls.__new__(cls), cls.__new__(cls)
+        kappa = _f64(kappa)
+        x, y, z, w, offsets = cat_n._prepare(ctx, x, y, z, w, n_patches, n_bins_or_1, offsets, sort_axis, strip_micro)
+        cat_k._prepare(ctx, x, y, z, w, n_patches, n_bins_or_1, offsets, sort_axis, None, weighted=True)
+        if len(kappa) != cat_n.n:
+            raise ValueError("catalogue columns differ in length")
+        _check(
+            load_library().yawhip_catalog_upload_scalar(
+                ctx._h, cat_n.n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(kappa, _dp), cat_n.n_patches,
+                cat_n.n_bins, _ptr(offsets, _i64p), int(sort_axis), ctypes.byref(cat_n._h), ctypes.byref(cat_k._h),
+            ),
+            "yawhip_catalog_upload_scalar",
+        )
+        ctx._catalogs.add(cat_n)
+        ctx._catalogs.add(cat_k)
+        return cat_n, cat_k
+
+    def segment_sums(self) -> np.ndarray:
+        """``yawhip_catalog_segment_sums``: float64[P, B_or_1] sum of the weight column per (patch, bin) segment, summed on
+        the device in a fixed order (object counts for an unweighted catalogue)."""
+        out = np.empty((self.n_patches, self.n_bins), dtype=np.float64)
+        _check(load_library().yawhip_catalog_segment_sums(self._h, _ptr(out, _dp)), "yawhip_catalog_segment_sums")
+        return out
 
     @property
     def device_bytes(self) -> int:

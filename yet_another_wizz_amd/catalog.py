@@ -22,7 +22,7 @@ from .options import Closed
 
 radec_to_xyz = _threads.radec_to_xyz  # numpy's cos / sin on slices of the columns, side by side (same values)
 
-__all__ = ["Catalog", "Patch", "Metadata", "InconsistentPatchesError", "PatchLayout"]
+__all__ = ["Catalog", "Patch", "Metadata", "InconsistentPatchesError", "PatchLayout", "ScalarTwin"]
 
 PATCH_ID_MAX = np.iinfo(np.int16).max  # the reference stores patch ids as 16-bit integers (datachunk.py:40-42)
 
@@ -133,9 +133,10 @@ def read_patch_file(path):
     return {name: table[:, i].copy() for i, name in enumerate(fields)}
 
 
-def write_patch_file(path, ra, dec, weights=None, redshifts=None) -> None:
-    cols = [ra, dec] + [c for c in (weights, redshifts) if c is not None]
-    flags = 0b11 | (int(weights is not None) << 2) | (int(redshifts is not None) << 3)
+def write_patch_file(path, ra, dec, weights=None, redshifts=None, kappa=None) -> None:
+    """Columns in the reference's ATTR_ORDER (ra, dec, weights, redshifts, [patch ids: never stored], kappa; datachunk.py:47)."""
+    cols = [ra, dec] + [c for c in (weights, redshifts, kappa) if c is not None]
+    flags = 0b11 | (int(weights is not None) << 2) | (int(redshifts is not None) << 3) | (int(kappa is not None) << 5)
     with open(path, "wb") as f:
         f.write(flags.to_bytes(1, byteorder="big"))
         np.column_stack(cols).astype(np.float64).tofile(f)
@@ -211,6 +212,10 @@ class Patch:
         return self._cat._z is not None
 
     @property
+    def has_kappa(self) -> bool:
+        return self._cat._k is not None
+
+    @property
     def coords(self) -> AngularCoordinates:
         sl = slice(self._lo, self._hi)
         return AngularCoordinates(np.column_stack([self._cat._ra[sl], self._cat._dec[sl]]))
@@ -223,6 +228,11 @@ class Patch:
     def redshifts(self):
         return None if self._cat._z is None else self._cat._z[self._lo : self._hi]
 
+    @property
+    def kappa(self):
+        """Scalar-field values of the patch's objects, or ``None`` (patch.py:431-436)."""
+        return None if self._cat._k is None else self._cat._k[self._lo : self._hi]
+
 
 class PatchLayout:
     """Device-ready layout of one catalogue for one redshift binning: float64 SoA columns sorted
@@ -231,10 +241,12 @@ class PatchLayout:
     This is the counterpart of ``build_trees`` (src/yaw/catalog/trees.py:365-429): objects outside
     the binning are dropped (:414), an unbinned catalogue has one segment per patch (:400-404)."""
 
-    __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent")
+    __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent", "kappa", "twin")
 
-    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int) -> None:
+    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None) -> None:
         self.x, self.y, self.z, self.w = x, y, z, w
+        self.kappa = kappa  # scalar-field column in the layout's order, or None
+        self.twin = None if kappa is None else ScalarTwin(self)  # the "k" side of a scalar count
         self.offsets = offsets
         self.num_patches, self.num_bins = num_patches, num_bins
         if w is None:
@@ -265,6 +277,40 @@ class PatchLayout:
         if self.num_bins == 1 and num_bins != 1:
             return np.repeat(self.sum_weights, num_bins, axis=0)
         return self.sum_weights
+
+
+class ScalarTwin:
+    """The "k" side of a layout that carries a scalar field: the same objects, segments and order with the per-object weight
+    ``kappa * w`` (``kappa`` without weights) -- what ``AngularTree.get_pair_weights`` hands to the count for a tree on the
+    "k" side of a mode (trees.py:270-301). On the device it is the second catalogue of ``yawhip_catalog_upload_scalar``, made
+    together with the plain one (``engine.device_catalog``); the host never needs the product, ``w`` forms it on first use
+    for code that reads layouts on the host (the CPU oracle of the tests, the cost model)."""
+
+    __slots__ = ("base", "device", "_w")
+
+    def __init__(self, base: PatchLayout) -> None:
+        self.base = base
+        self.device = {}  # Context id -> DeviceCatalog (the twin)
+        self._w = None
+
+    x = property(lambda self: self.base.x)
+    y = property(lambda self: self.base.y)
+    z = property(lambda self: self.base.z)
+    offsets = property(lambda self: self.base.offsets)
+    num_patches = property(lambda self: self.base.num_patches)
+    num_bins = property(lambda self: self.base.num_bins)
+    z_extent = property(lambda self: self.base.z_extent)
+    num_records = property(lambda self: self.base.num_records)
+    weighted = True
+
+    @property
+    def w(self):
+        if self._w is None:
+            self._w = self.base.kappa.copy() if self.base.w is None else self.base.kappa * self.base.w
+        return self._w
+
+    def segment_sizes(self):
+        return self.base.segment_sizes()
 
 
 class Catalog(Mapping):
@@ -301,7 +347,7 @@ class Catalog(Mapping):
 
         self._setup(joined("ra"), joined("dec"), patch_ids=np.repeat(np.arange(len(ids)), [len(c["ra"]) for c in columns]),
                     num_patches=len(ids), weights=joined("weights"), redshifts=joined("redshifts"),
-                    cache_directory=directory, stored_meta=metas)
+                    kappa=joined("kappa"), cache_directory=directory, stored_meta=metas)
 
     @classmethod
     def _from_columns(cls, ra, dec, **kwargs):
@@ -309,7 +355,7 @@ class Catalog(Mapping):
         new._setup(ra, dec, **kwargs)
         return new
 
-    def _setup(self, ra, dec, *, patch_ids, num_patches: int | None = None, weights=None, redshifts=None,
+    def _setup(self, ra, dec, *, patch_ids, num_patches: int | None = None, weights=None, redshifts=None, kappa=None,
                patch_centers: AngularCoordinates | None = None, cache_directory=None, stored_meta=None,
                xyz=None) -> None:
         """Common initialiser; coordinates in radian. ``xyz`` = ``radec_to_xyz(ra, dec)`` if already known."""
@@ -333,10 +379,13 @@ class Catalog(Mapping):
             raise ValueError(f"empty patches are not supported (patch ids {empty})")
         weights = None if weights is None else np.asarray_chkfinite(weights, dtype=np.float64)
         redshifts = None if redshifts is None else np.asarray_chkfinite(redshifts, dtype=np.float64)
+        kappa = None if kappa is None else np.asarray_chkfinite(kappa, dtype=np.float64)
+        if any(c is not None and len(c) != len(ra) for c in (weights, redshifts, kappa)):
+            raise ValueError("input columns differ in length")
         # unit vectors: computed once per catalogue (assignment, patch metadata and the device layouts all use
         # these values -- the exact host numbers the pair predicate runs on)
         xyz = radec_to_xyz(ra, dec) if xyz is None else tuple(np.asarray(c, dtype=np.float64) for c in xyz)
-        columns = [ra, dec, *xyz] + [c for c in (weights, redshifts) if c is not None]
+        columns = [ra, dec, *xyz] + [c for c in (weights, redshifts, kappa) if c is not None]
         grouped = False
         if np.all(patch_ids[1:] >= patch_ids[:-1]):
             # already grouped by patch (a restored cache): the stable order is the identity. The catalogue keeps its own copy
@@ -358,6 +407,7 @@ class Catalog(Mapping):
         rest = iter(columns[5:])
         self._w = None if weights is None else next(rest)
         self._z = None if redshifts is None else next(rest)
+        self._k = None if kappa is None else next(rest)  # scalar field ("kappa"), carried like any other column
         self._patch_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         self._layouts: dict = {}
         self._active_layout = None
@@ -387,7 +437,7 @@ class Catalog(Mapping):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_arrays(cls, ra, dec, *, weights=None, redshifts=None, patch_centers=None, patch_ids=None,
+    def from_arrays(cls, ra, dec, *, weights=None, redshifts=None, kappa=None, patch_centers=None, patch_ids=None,
                     patch_num: int | None = None, degrees: bool = True, cache_directory=None, overwrite: bool = False,
                     probe_size: int = -1):
         """Build from plain arrays. One of ``patch_centers`` (nearest-centre assignment),
@@ -425,7 +475,7 @@ class Catalog(Mapping):
             patch_ids = nearest_center(xyz, centers.to_3d())
             num = len(centers)
         new = cls._from_columns(ra, dec, patch_ids=patch_ids, num_patches=num, weights=weights, redshifts=redshifts,
-                                patch_centers=centers, cache_directory=None, xyz=xyz)
+                                kappa=kappa, patch_centers=centers, cache_directory=None, xyz=xyz)
         if cache_directory is not None:
             new.to_cache(cache_directory, overwrite=overwrite)
         return new
@@ -440,9 +490,8 @@ class Catalog(Mapping):
         be a pandas DataFrame or any mapping from column name to array. ``cache_directory`` may be
         ``None`` (nothing is written: the catalogue lives in memory and in HBM); a path gets a cache in
         the reference's on-disk format, readable by both packages (``overwrite`` as in the reference).
-        ``kappa_name`` (scalar-field correlations) is outside the nn pair-count path."""
-        if kappa_name is not None:
-            raise NotImplementedError("scalar field ('kappa') correlations are not part of the nn pair-count path")
+        ``kappa_name`` names a column of scalar-field values (convergence, a shear amplitude, ...) for
+        ``autocorrelate_scalar`` / ``crosscorrelate_scalar``."""
         if patch_name is not None and not isinstance(patch_name, str):
             raise TypeError("'patch_name' must be a string")
 
@@ -452,7 +501,7 @@ class Catalog(Mapping):
         use_ids = patch_centers is None and patch_name is not None
         return cls.from_arrays(
             column(ra_name), column(dec_name), weights=column(weight_name), redshifts=column(redshift_name),
-            patch_centers=patch_centers, patch_ids=column(patch_name) if use_ids else None, patch_num=patch_num,
+            kappa=column(kappa_name), patch_centers=patch_centers, patch_ids=column(patch_name) if use_ids else None, patch_num=patch_num,
             degrees=degrees, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size,
         )
 
@@ -463,7 +512,7 @@ class Catalog(Mapping):
         """Parquet (``.pqt/.parquet``) or ``.npz`` input (reference: catalog.py:1111-1243; FITS and
         HDF5 readers need libraries that are outside this build's scope)."""
         path = Path(path)
-        names = [n for n in (ra_name, dec_name, weight_name, redshift_name, patch_name) if n is not None]
+        names = [n for n in (ra_name, dec_name, weight_name, redshift_name, patch_name, kappa_name) if n is not None]
         if path.suffix.lower() in (".pqt", ".parquet"):
             import pyarrow.parquet as pq
 
@@ -549,6 +598,10 @@ class Catalog(Mapping):
     def has_redshifts(self) -> bool:
         return self._z is not None
 
+    @property
+    def has_kappa(self) -> bool:
+        return self._k is not None
+
     def get_num_records(self) -> tuple:
         return tuple(p.meta.num_records for p in self.values())
 
@@ -583,7 +636,8 @@ class Catalog(Mapping):
             patch_dir.mkdir()
             lo, hi = patch._lo, patch._hi
             write_patch_file(patch_dir / PATCH_DATA_FILE, self._ra[lo:hi], self._dec[lo:hi],
-                             None if self._w is None else self._w[lo:hi], None if self._z is None else self._z[lo:hi])
+                             None if self._w is None else self._w[lo:hi], None if self._z is None else self._z[lo:hi],
+                             None if self._k is None else self._k[lo:hi])
             with (patch_dir / PATCH_META_FILE).open("w") as f:
                 yaml.safe_dump(patch.meta.to_dict(), f, indent=4)
         self.cache_directory = directory
@@ -609,13 +663,13 @@ class Catalog(Mapping):
         x, y, z = self._unit_vectors()
         num_patches = self.num_patches
         if bins is None:
-            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1)
+            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1, kappa=self._k)
         else:
             num_bins = len(bins)
             bin_idx = bins.assign(self._z)
             patch_of = np.repeat(np.arange(num_patches), np.diff(self._patch_off))
             offsets = np.zeros(num_patches * num_bins + 1, dtype=np.int64)
-            columns = [x, y, z] + ([] if self._w is None else [self._w])
+            columns = [x, y, z] + [c for c in (self._w, self._k) if c is not None]  # kappa is binned (and dropped) as the rest
             grouped = False
             if len(x) >= HOST_GROUP_MIN:  # (patch, bin) grouping in one threaded pass; objects outside the binning dropped
                 from . import _lib
@@ -633,8 +687,9 @@ class Catalog(Mapping):
                 order = keep[_stable_argsort_small(seg_key, num_patches * num_bins)]
                 np.cumsum(np.bincount(seg_key, minlength=num_patches * num_bins), out=offsets[1:])
                 columns = [c[order] for c in columns]
-            layout = PatchLayout(columns[0], columns[1], columns[2], None if self._w is None else columns[3], offsets,
-                                 num_patches, num_bins)
+            rest = iter(columns[3:])
+            layout = PatchLayout(columns[0], columns[1], columns[2], None if self._w is None else next(rest), offsets,
+                                 num_patches, num_bins, kappa=None if self._k is None else next(rest))
         self._layouts[key] = layout
         self._active_layout = layout  # what the next count_pairs() uses, like the cached trees.pkl
         return layout
@@ -642,8 +697,11 @@ class Catalog(Mapping):
     def drop_layouts(self) -> None:
         """Release cached layouts (and with them the device copies)."""
         for layout in self._layouts.values():
-            for dev in layout.device.values():
-                dev.free()
-            layout.device.clear()
+            for held in (layout, layout.twin):  # the plain device catalogue and, with kappa, its twin
+                if held is None:
+                    continue
+                for dev in held.device.values():
+                    dev.free()
+                held.device.clear()
         self._layouts.clear()
         self._active_layout = None

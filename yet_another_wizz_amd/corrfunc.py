@@ -3,9 +3,9 @@
 from __future__ import annotations
 
 from .corrdata import CorrData
-from .paircounts import NormalisedCounts
+from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "EstimatorError", "davis_peebles", "landy_szalay"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -33,17 +33,31 @@ def landy_szalay(*, dd, dr, rd=None, rr):
 landy_szalay.name = "LS"
 
 
+def scalar_correlation(*, dd, dr=None):
+    """DD, or DD - DR when DR is given (corrfunc.py:91-97)."""
+    return dd if dr is None else dd - dr
+
+
+scalar_correlation.name = "SC"
+
+
 class CorrFunc:
     """Normalised pair counts of one correlation scale; ``sample()`` turns them into w(z)."""
 
     __slots__ = ("_counts_dict",)
     _kinds = ("dd", "dr", "rd", "rr")
+    _counts_type = NormalisedCounts
 
     def __init__(self, dd, dr=None, rd=None, rr=None) -> None:
-        if type(dd) is not NormalisedCounts:
-            raise TypeError(f"pair counts must be of type {NormalisedCounts}")
+        self._init(dd, dr=dr, rd=rd, rr=rr)
+        if len(self._counts_dict) == 1:
+            raise EstimatorError("missing at least one additional pair count")
+
+    def _init(self, dd, **counts) -> None:
+        if type(dd) is not self._counts_type:
+            raise TypeError(f"pair counts must be of type {self._counts_type}")
         self._counts_dict = dict(dd=dd)
-        for kind, count in (("dr", dr), ("rd", rd), ("rr", rr)):
+        for kind, count in counts.items():
             if count is None:
                 continue
             try:
@@ -51,8 +65,6 @@ class CorrFunc:
             except ValueError as err:
                 raise ValueError(f"pair counts '{kind}' and 'dd' are not compatible") from err
             self._counts_dict[kind] = count
-        if len(self._counts_dict) == 1:
-            raise EstimatorError("missing at least one additional pair count")
 
     def __repr__(self) -> str:
         kinds = "|".join(self._counts_dict)
@@ -118,3 +130,19 @@ class CorrFunc:
 
     def patches_subset(self, item):
         return type(self).from_dict({k: c.patches_subset(item) for k, c in self._counts_dict.items()})
+
+
+class ScalarCorrFunc(CorrFunc):
+    """Scalar-field pair counts of one correlation scale (corrfunc.py:355-399): ``dd`` and optionally ``dr``, both
+    ``NormalisedScalarCounts``; the estimator is DD, or DD - DR. Everything else -- ``sample()``, ``to_dict`` /
+    ``from_dict``, ``==``, ``is_compatible``, the bin and patch subsets -- is ``CorrFunc``'s."""
+
+    __slots__ = ()
+    _kinds = ("dd", "dr")
+    _counts_type = NormalisedScalarCounts
+
+    def __init__(self, dd, dr=None) -> None:
+        self._init(dd, dr=dr)
+
+    def get_estimator(self):
+        return scalar_correlation

@@ -2491,6 +2491,51 @@ __global__ void k_gather_columns(int64_t n, const uint32_t *__restrict__ perm, c
     if (sw) dw[i] = sw[src];
 }
 
+// The gather of yawhip_catalog_upload_scalar: ONE permutation fills two catalogues -- the plain one (d*: weights sw, none
+// without) and its twin (k*: the same coordinates, weights kappa * w, kappa without sw). The product is one float64 multiply
+// rounded on its own (no sum follows it, and the build contracts nothing): the value numpy's kappa * w has on the host.
+__global__ void k_gather_columns_scalar(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
+                                        const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
+                                        const double *__restrict__ sk, double *__restrict__ dx, double *__restrict__ dy,
+                                        double *__restrict__ dz, double *__restrict__ dw, double *__restrict__ kx,
+                                        double *__restrict__ ky, double *__restrict__ kz, double *__restrict__ kw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t src = perm[i];
+    const double vx = sx[src], vy = sy[src], vz = sz[src], kappa = sk[src];
+    dx[i] = vx;
+    dy[i] = vy;
+    dz[i] = vz;
+    kx[i] = vx;
+    ky[i] = vy;
+    kz[i] = vz;
+    if (sw) {
+        const double wv = sw[src];
+        dw[i] = wv;
+        kw[i] = kappa * wv;
+    } else {
+        kw[i] = kappa;
+    }
+}
+
+// Sum of the weight column over every (patch, bin) segment of a resident catalogue, one workgroup per segment: thread t adds
+// the objects lo + t, lo + t + 256, ... in that order, then the 256 partial sums are folded in halves through the LDS. The
+// order is a function of the segment alone: the same catalogue gives the same bits every time; no atomics.
+__global__ __launch_bounds__(256) void k_segment_weight_sums(const double *__restrict__ w, const int64_t *__restrict__ off,
+                                                            double *__restrict__ out) {
+    __shared__ double part[256];
+    const int64_t lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
+    double acc = 0.0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) acc += w[i];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = part[0];
+}
+
 // largest s in [0, n_seg) with off[s] <= i (off[0] = 0 <= i < off[n_seg])
 __device__ __forceinline__ int segment_of(const int64_t *__restrict__ off, int n_seg, int64_t i) {
     int lo = 0, hi = n_seg;
@@ -3017,12 +3062,16 @@ int yawhip_catalog_sort_axis(const yawhip_catalog *cat, int32_t *axis) {
     return YAWHIP_OK;
 }
 
-int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                               const double *w, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
-                               int32_t sort_axis, yawhip_catalog **out) {
+// The upload behind yawhip_catalog_upload_axis (kappa == NULL: one catalogue, *out) and yawhip_catalog_upload_scalar (kappa
+// given: the plain catalogue *out and its twin *out_k with weights kappa * w, both from ONE copy of the coordinates and ONE
+// segment sort; the twin is a catalogue like any other from there on -- own uid, own layouts, own replicas).
+static int upload_catalogs(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                           const double *kappa, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
+                           int32_t sort_axis, yawhip_catalog **out, yawhip_catalog **out_k) {
     if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: out is NULL");
     if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
     *out = nullptr;
+    if (out_k) *out_k = nullptr;
     if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: ctx is NULL");
     if (n < 0 || n_patches <= 0 || n_bins_or_1 <= 0 || !offsets || (n > 0 && (!x || !y || !z)))
         return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: bad sizes or NULL columns");
@@ -3036,27 +3085,40 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
     static std::atomic<uint64_t> next_uid{1};
     if (c) c->uid = next_uid.fetch_add(1);
     if (!c) return fail(YAWHIP_ERR_OOM, "host allocation failed");
-    c->ctx = ctx;
-    c->n = n;
-    c->n_patches = n_patches;
-    c->nb = n_bins_or_1;
-    c->axis = sort_axis;
-    c->h_off.assign(offsets, offsets + nseg + 1);
+    yawhip_catalog *ck = nullptr;  // the twin (kappa given)
+    if (kappa) {
+        ck = new (std::nothrow) yawhip_catalog();
+        if (!ck) {
+            delete c;
+            return fail(YAWHIP_ERR_OOM, "host allocation failed");
+        }
+        ck->uid = next_uid.fetch_add(1);
+    }
+    for (yawhip_catalog *t : {c, ck}) {
+        if (!t) continue;
+        t->ctx = ctx;
+        t->n = n;
+        t->n_patches = n_patches;
+        t->nb = n_bins_or_1;
+        t->axis = sort_axis;
+        t->h_off.assign(offsets, offsets + nseg + 1);
+    }
     // Library-private order: the columns go to the device as they are and are ordered there (rocPRIM radix sorts,
     // yawhip_sort.hip): ascending along the sort axis inside every (patch, bin) segment. The strip layouts are derived
     // from this resident copy (build_strip_layout), the one of the catalogue's own sort axis right away.
     const size_t col = (size_t)std::max<int64_t>(n, 1) * sizeof(double) + 16;  // + 16: see build_strip_layout
-    double *rx = nullptr, *ry = nullptr, *rz = nullptr, *rw = nullptr;  // raw columns (temporary)
+    double *rx = nullptr, *ry = nullptr, *rz = nullptr, *rw = nullptr, *rk = nullptr;  // raw columns (temporary)
     uint32_t *perm = nullptr;
     int64_t *poff = nullptr;
     unsigned long long *box = nullptr;  // [P][6] sortable images of min / max per axis, [6 P]: violations of the unit norm
     auto free_tmp = [&]() {
-        for (void *q : {(void *)rx, (void *)ry, (void *)rz, (void *)rw, (void *)perm, (void *)poff, (void *)box})
+        for (void *q : {(void *)rx, (void *)ry, (void *)rz, (void *)rw, (void *)rk, (void *)perm, (void *)poff, (void *)box})
             if (q) (void)hipFree(q);
     };
     auto bail = [&](hipError_t err, const char *what) {
         free_tmp();
         yawhip_catalog_free(c);
+        yawhip_catalog_free(ck);
         return fail(err == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "catalog upload (%s) failed: %s", what,
                     hipGetErrorString(err));
     };
@@ -3074,6 +3136,11 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->z), col);
     if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&c->w), col);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->off), (size_t)(nseg + 1) * sizeof(int64_t));
+    if (ck) {  // the twin's columns: coordinates, the product (always weighted), its own copy of the offsets
+        for (double **q : {&ck->x, &ck->y, &ck->z, &ck->w, &rk})
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(q), col);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ck->off), (size_t)(nseg + 1) * sizeof(int64_t));
+    }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rx), col);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ry), col);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rz), col);
@@ -3086,7 +3153,10 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
         if (e == hipSuccess) e = hipMemcpyAsync(ry, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(rz, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess && w) e = hipMemcpyAsync(rw, w, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && ck) e = hipMemcpyAsync(rk, kappa, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     }
+    if (e == hipSuccess && ck)
+        e = hipMemcpyAsync(ck->off, offsets, (size_t)(nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(c->off, offsets, (size_t)(nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
@@ -3101,7 +3171,11 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
         hipLaunchKernelGGL(k_patch_boxes, dim3(ngrid), dim3(256), 0, ctx->stream, n, rx, ry, rz, poff, n_patches, box);
         e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(rx, ry, rz, sort_axis), c->off, nseg, perm);
         if (e != hipSuccess) return bail(e, "segment sort");
-        hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, rx, ry, rz, rw, c->x, c->y, c->z, c->w);
+        if (ck)
+            hipLaunchKernelGGL(k_gather_columns_scalar, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, rx, ry, rz, rw, rk, c->x,
+                               c->y, c->z, c->w, ck->x, ck->y, ck->z, ck->w);
+        else
+            hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, rx, ry, rz, rw, c->x, c->y, c->z, c->w);
         if ((e = hipGetLastError()) != hipSuccess) return bail(e, "gather");
         e = hipMemcpyAsync(h_box.data(), box, h_box.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) return bail(e, "patch boxes");
@@ -3109,31 +3183,77 @@ int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, cons
     e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return bail(e, "finish");
     free_tmp();
-    c->unit_norm = h_box[(size_t)6 * n_patches] == 0ull;
-    c->h_box.resize((size_t)6 * n_patches);
-    for (size_t i = 0; i < c->h_box.size(); ++i) c->h_box[i] = double_of(h_box[i]);
-    c->device_bytes = (int64_t)col * (w ? 4 : 3) + (nseg + 1) * (int64_t)sizeof(int64_t);
-    c->strip_width = ctx->strip_width;
-    c->strip_grid = ctx->strip_grid;
-    c->has_strips = c->unit_norm && n > 0;
-    if (c->has_strips) {
-        const int rc = build_strip_layout(ctx, c, sort_axis, false);
+    for (yawhip_catalog *t : {c, ck}) {
+        if (!t) continue;
+        t->unit_norm = h_box[(size_t)6 * n_patches] == 0ull;
+        t->h_box.resize((size_t)6 * n_patches);
+        for (size_t i = 0; i < t->h_box.size(); ++i) t->h_box[i] = double_of(h_box[i]);
+        t->device_bytes = (int64_t)col * (t->w ? 4 : 3) + (nseg + 1) * (int64_t)sizeof(int64_t);
+        t->strip_width = ctx->strip_width;
+        t->strip_grid = ctx->strip_grid;
+        t->has_strips = t->unit_norm && n > 0;
+    }
+    for (yawhip_catalog *t : {c, ck}) {  // layouts are built per catalogue (the twin's carry its own weight column)
+        if (!t || !t->has_strips) continue;
+        const int rc = build_strip_layout(ctx, t, sort_axis, false);
         if (rc != YAWHIP_OK) {
             yawhip_catalog_free(c);
+            yawhip_catalog_free(ck);
             return rc;
         }
     }
     if (ctx->sort_ws.cap > ((size_t)1 << 25)) ctx->sort_ws.release();  // ~30 bytes per object: keep only small workspaces
-    for (yawhip_ctx *peer : ctx->peers) {  // multi-device context: the same catalogue on every further device
-        yawhip_catalog *rep = nullptr;
-        const int rc = yawhip_catalog_upload_axis(peer, n, x, y, z, w, n_patches, n_bins_or_1, offsets, sort_axis, &rep);
+    for (yawhip_ctx *peer : ctx->peers) {  // multi-device context: the same catalogue(s) on every further device
+        yawhip_catalog *rep = nullptr, *rep_k = nullptr;
+        const int rc = upload_catalogs(peer, n, x, y, z, w, kappa, n_patches, n_bins_or_1, offsets, sort_axis, &rep,
+                                       ck ? &rep_k : nullptr);
         if (rc != YAWHIP_OK) {
             yawhip_catalog_free(c);
+            yawhip_catalog_free(ck);
             return rc;
         }
         c->replicas.push_back(rep);
+        if (ck) ck->replicas.push_back(rep_k);
     }
+    if (ck) *out_k = ck;
     *out = c;
+    return YAWHIP_OK;
+}
+
+int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
+                               const double *w, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
+                               int32_t sort_axis, yawhip_catalog **out) {
+    return upload_catalogs(ctx, n, x, y, z, w, nullptr, n_patches, n_bins_or_1, offsets, sort_axis, out, nullptr);
+}
+
+int yawhip_catalog_upload_scalar(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
+                                 const double *w, const double *kappa, int32_t n_patches, int32_t n_bins_or_1,
+                                 const int64_t *offsets, int32_t sort_axis, yawhip_catalog **out_n, yawhip_catalog **out_k) {
+    if (!out_n || !out_k) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload_scalar: out_n / out_k is NULL");
+    *out_n = *out_k = nullptr;  // before every check: on any failure neither is returned
+    if (n > 0 && !kappa) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload_scalar: kappa is NULL");
+    static const double none = 0.0;  // (n == 0: nothing is read through it)
+    return upload_catalogs(ctx, n, x, y, z, w, kappa ? kappa : &none, n_patches, n_bins_or_1, offsets, sort_axis, out_n, out_k);
+}
+
+int yawhip_catalog_segment_sums(const yawhip_catalog *cat, double *sums) {
+    if (!cat || !sums) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_segment_sums: NULL argument");
+    const int64_t nseg = (int64_t)cat->n_patches * cat->nb;
+    if (!cat->w) {  // unweighted: the number of objects (exact)
+        for (int64_t s = 0; s < nseg; ++s) sums[s] = (double)(cat->h_off[(size_t)s + 1] - cat->h_off[(size_t)s]);
+        return YAWHIP_OK;
+    }
+    yawhip_ctx *ctx = cat->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    double *d_out = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_out), (size_t)nseg * sizeof(double));
+    if (e != hipSuccess) return fail(YAWHIP_ERR_OOM, "segment sums: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_segment_weight_sums, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, cat->w, cat->off, d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(sums, d_out, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(YAWHIP_ERR_HIP, "segment sums failed: %s", hipGetErrorString(e));
     return YAWHIP_OK;
 }
 

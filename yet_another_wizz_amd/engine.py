@@ -15,7 +15,7 @@ from . import _lib
 from .parallel import local_device_index, world
 
 __all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms",
-           "redshift_histogram", "release", "default_kernel"]
+           "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
 default_kernel = "auto"
@@ -85,7 +85,9 @@ def device_catalog(layout, ctx=None, sort_axis: int = 2, strip_micro: int | None
     """Upload (once per context) and return the device copy of a layout. ``sort_axis`` is the
     coordinate the library sorts segments by for its window culling; ``strip_micro`` the wanted
     spacing of the strip grid. A copy made for another axis, or for a grid more than 1.6 x off the
-    wanted spacing (``exact``: any other spacing), is replaced."""
+    wanted spacing (``exact``: any other spacing), is replaced. A layout with a scalar field and its ``ScalarTwin`` reach the
+    device together (``yawhip_catalog_upload_scalar``: one copy of the coordinates, one segment sort, two catalogues), and
+    are replaced together."""
     ctx = ctx or get_context()
     dev = layout.device.get(id(ctx))
     if dev is not None:
@@ -98,9 +100,20 @@ def device_catalog(layout, ctx=None, sort_axis: int = 2, strip_micro: int | None
             dev.free()
             dev = None
     if dev is None:
-        dev = _lib.DeviceCatalog(ctx, layout.x, layout.y, layout.z, layout.w, layout.num_patches, layout.num_bins,
-                                 layout.offsets, sort_axis=sort_axis, strip_micro=strip_micro)
-        layout.device[id(ctx)] = dev
+        base = getattr(layout, "base", layout)  # (of a ScalarTwin: the layout it weights)
+        if base.kappa is None:
+            dev = _lib.DeviceCatalog(ctx, layout.x, layout.y, layout.z, layout.w, layout.num_patches, layout.num_bins,
+                                     layout.offsets, sort_axis=sort_axis, strip_micro=strip_micro)
+            layout.device[id(ctx)] = dev
+        else:
+            for held in (base, base.twin):
+                old = held.device.pop(id(ctx), None)
+                if old is not None:
+                    old.free()
+            base.device[id(ctx)], base.twin.device[id(ctx)] = _lib.DeviceCatalog.upload_scalar(
+                ctx, base.x, base.y, base.z, base.w, base.kappa, base.num_patches, base.num_bins, base.offsets,
+                sort_axis=sort_axis, strip_micro=strip_micro)
+            dev = layout.device[id(ctx)]
     return dev
 
 
@@ -162,6 +175,20 @@ def _device_pair(layout1, layout2, thresholds, sort_axis, max_workers=None):
     d1 = device_catalog(layout1, ctx, sort_axis, micro, exact=forced_strip_micro is not None)
     d2 = d1 if layout2 is layout1 else device_catalog(layout2, ctx, sort_axis, d1.strip_micro, exact=True)
     return ctx, d1, d2
+
+
+def scalar_segment_sums(layout, *, sort_axis: int | None = None):
+    """``(sum kappa * w, sum w)`` per (patch, bin) segment of a layout with a scalar field, float64[P, B_or_1] each, summed
+    on the device from its two resident catalogues (``yawhip_catalog_segment_sums``; uploaded first if they are not). There
+    is no host fallback."""
+    if layout.kappa is None:
+        raise ValueError("catalog has no 'kappa' attached")
+    ctx = get_context()
+    have = layout.device.get(id(ctx))
+    axis = sort_axis if sort_axis is not None else (have.sort_axis if have is not None else 2)
+    dev_n = device_catalog(layout, ctx, axis)
+    dev_k = device_catalog(layout.twin, ctx, axis)
+    return dev_k.segment_sums(), dev_n.segment_sums()
 
 
 def job_work(layout1, layout2, jobs, thresholds, *, kernel: str | None = None, sort_axis: int = 2) -> np.ndarray:

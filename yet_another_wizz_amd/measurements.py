@@ -20,10 +20,12 @@ from . import _lib, engine, parallel
 from .angular_bins import plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
-from .corrfunc import CorrFunc
-from .paircounts import NormalisedCounts, PatchedCounts, PatchedSumWeights
+from .corrfunc import CorrFunc, ScalarCorrFunc
+from .options import CountMode
+from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
-__all__ = ["autocorrelate", "crosscorrelate", "PatchLinkage", "get_max_angle", "check_patch_conistency"]
+__all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "compute_scalar_normalisation",
+           "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
 
@@ -270,9 +272,10 @@ class PatchLinkage:
     def count_pairs(self, main_catalog: Catalog, *optional_catalog: Catalog, progress: bool = False,
                     max_workers: int | None = None, mode: str = "nn", count_type_info: str | None = None):
         """Pair counts between the patches of one (auto) or two catalogues -> one
-        ``NormalisedCounts`` per scale (measurements.py:307-367)."""
-        if str(mode) != "nn":
-            raise NotImplementedError("only the 'nn' counting mode is part of this build")
+        ``NormalisedCounts`` per scale (measurements.py:307-367). ``mode`` ("nn", "nk", "kn", "kk") picks per side the
+        catalogue's weights ("n") or its weights times its scalar field ("k": the κ-weighted twin on the device); the
+        normalisation is the plain sum of weights in every mode, as in the reference."""
+        mode = CountMode.parse(mode)
         if len(optional_catalog) > 1:
             raise TypeError("count_pairs() takes at most two catalogues")
         if count_type_info is not None:
@@ -282,6 +285,7 @@ class PatchLinkage:
         binning = self.config.binning.binning
         num_bins, num_patches = len(binning), len(main_catalog)
         layout1, layout2 = _active_layout(main_catalog, num_bins), _active_layout(cat2, num_bins)
+        side1, side2 = _count_sides(layout1, layout2, mode)  # what the device counts on: the layouts or their κ-weighted twins
 
         jobs = self.get_patch_pairs(main_catalog, None if auto else cat2)
         plans, thresholds = self._angular_setup()
@@ -299,7 +303,7 @@ class PatchLinkage:
             if self._dense_spec is None:
                 self._dense_spec = self._combine.dense_spec(num_fine)
             slices, factors = self._dense_spec
-            counts, stats = engine.count_dense(layout1, layout2, jobs, thresholds, slices, factors, auto,
+            counts, stats = engine.count_dense(side1, side2, jobs, thresholds, slices, factors, auto,
                                                sort_axis=self.sort_axis, max_workers=max_workers)
             self.last_stats = stats
             self._report(count_type_info, len(jobs), stats, progress)
@@ -320,13 +324,13 @@ class PatchLinkage:
         digest = hashlib.blake2b(digest_size=16)
         for part in (layout1.offsets, layout2.offsets, thresholds, jobs):
             digest.update(np.ascontiguousarray(part).tobytes())
-        key = (digest.hexdigest(), layout1.w is not None, layout2.w is not None, auto, size)
+        key = (digest.hexdigest(), side1.weighted, side2.weighted, auto, size)
         if key not in self._partitions:
             t_part = _time.perf_counter()
             parts = None
             if rank == 0:
                 try:
-                    work = engine.job_work(layout1, layout2, jobs, thresholds, sort_axis=self.sort_axis)
+                    work = engine.job_work(side1, side2, jobs, thresholds, sort_axis=self.sort_axis)
                     parts = parallel.partition_jobs(work.astype(np.float64) + JOB_FIXED_COST, size)
                 except Exception as err:  # noqa: BLE001 -- the other ranks wait in the broadcast: tell them
                     parts = f"{type(err).__name__}: {err}"  # (as text: an exception object may not pickle)
@@ -345,10 +349,10 @@ class PatchLinkage:
         on_device = (parallel.device_collectives() or FORCE_DEVICE_REDUCE) and len(devices) == 1
         try:
             if on_device:  # this rank's rows stay in HBM, in their place of the full tensor (zero elsewhere)
-                rows, stats = engine.count_rows_device(layout1, layout2, jobs[mine], thresholds, len(jobs), mine,
+                rows, stats = engine.count_rows_device(side1, side2, jobs[mine], thresholds, len(jobs), mine,
                                                        sort_axis=self.sort_axis)
             else:
-                fine, stats = engine.count_fine(layout1, layout2, jobs[mine], thresholds, sort_axis=self.sort_axis,
+                fine, stats = engine.count_fine(side1, side2, jobs[mine], thresholds, sort_axis=self.sort_axis,
                                                 max_workers=max_workers)
             self.last_stats = stats
         except Exception as err:  # noqa: BLE001 -- with several ranks the others must not wait for this one forever
@@ -400,7 +404,8 @@ class PatchLinkage:
         return [NormalisedCounts(counts, sum_weights) for counts in scale_counts]
 
     def count_pairs_batch(self, requests, *, progress: bool = False, max_workers: int | None = None) -> list:
-        """The pair counts of ONE measurement -- ``requests`` = ``[(catalogs, info), ...]`` with ``catalogs`` a tuple of one
+        """The pair counts of ONE measurement -- ``requests`` = ``[(catalogs, info), ...]`` or ``[(catalogs, info, mode), ...]``
+        (``mode`` as in ``count_pairs``, "nn" if left out) with ``catalogs`` a tuple of one
         (auto count) or two catalogues, e.g. DD, DR, RD, RR of ``crosscorrelate``
         (src/yaw/correlation/measurements.py:617-628) -- as one submission: every count is put on the GPU's stream at once
         (``yawhip_count_pairs_dense_batch``), the host prepares count k + 1 and writes the tensor of count k while the
@@ -411,16 +416,17 @@ class PatchLinkage:
         rank, size = parallel.world()
         results: list = [[None] * num_scales for _ in requests]
         todo = []
-        for i, (catalogs, info) in enumerate(requests):
+        for i, (catalogs, info, *mode) in enumerate(requests):
+            mode = CountMode.parse(mode[0] if mode else "nn")
             if len(catalogs) not in (1, 2):
                 raise TypeError("a count takes one or two catalogues")
             if any(cat is None for cat in catalogs):
                 continue  # (count_pairs_optional: a missing random sample)
-            todo.append((i, catalogs[0], catalogs[1] if len(catalogs) == 2 else None, info))
+            todo.append((i, catalogs[0], catalogs[1] if len(catalogs) == 2 else None, info, mode))
         if size > 1 or FORCE_DEVICE_REDUCE or len(todo) <= 1:
-            for i, main, other, info in todo:
+            for i, main, other, info, mode in todo:
                 args = (main,) if other is None else (main, other)
-                results[i] = self.count_pairs(*args, progress=progress, max_workers=max_workers, count_type_info=info)
+                results[i] = self.count_pairs(*args, progress=progress, max_workers=max_workers, mode=mode, count_type_info=info)
             return results
         binning = self.config.binning.binning
         num_bins = len(binning)
@@ -429,14 +435,15 @@ class PatchLinkage:
             self._dense_spec = self._combine.dense_spec(thresholds.shape[1] - 1)
         slices, factors = self._dense_spec
         pairs, meta = [], []
-        for i, main, other, info in todo:
+        for i, main, other, info, mode in todo:
             auto = other is None
             cat2 = main if auto else other
             layout1, layout2 = _active_layout(main, num_bins), _active_layout(cat2, num_bins)
+            side1, side2 = _count_sides(layout1, layout2, mode)
             jobs = self.get_patch_pairs(main, None if auto else cat2)
             if info is not None:
                 _log_info("counting %s from patch pairs", info)
-            pairs.append((layout1, layout2, jobs, auto))
+            pairs.append((side1, side2, jobs, auto))
             meta.append((i, layout1, layout2, auto, info, len(jobs)))
         outs = engine.count_dense_batch(pairs, thresholds, slices, factors, sort_axis=self.sort_axis, max_workers=max_workers)
         self.last_batch_stats = {}
@@ -448,6 +455,27 @@ class PatchLinkage:
             sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
             results[i] = [NormalisedCounts(c, sum_weights) for c in scale_counts]
         return results
+
+    def count_scalar_pairs(self, main_catalog: Catalog, *optional_catalog: Catalog, progress: bool = False,
+                           max_workers: int | None = None, mode: str = "nn", count_type_info: str | None = None) -> list:
+        """Pair counts of a scalar-field correlation -> one ``NormalisedScalarCounts`` per scale
+        (measurements.py:394-429): the count in ``mode`` (typically "kn" or "kk") and the plain "nn" count that normalises
+        it, over the same patch pairs. Both go out as ONE batch submission (``last_batch_stats`` holds the two, named
+        "<info> (<mode>)" and "<info> (nn)"); several ranks count them one after the other."""
+        return self._count_scalar_batch([((main_catalog, *optional_catalog), count_type_info)], mode, progress=progress,
+                                        max_workers=max_workers)[0]
+
+    def _count_scalar_batch(self, counts, mode, *, progress: bool = False, max_workers: int | None = None) -> list:
+        """``count_scalar_pairs`` for several catalogue pairs of one measurement (DD and DR of ``crosscorrelate_scalar``):
+        ``counts`` = ``[(catalogs, info), ...]``; two requests each, all in one ``count_pairs_batch`` submission."""
+        mode = CountMode.parse(mode)
+        requests = []
+        for k, (catalogs, info) in enumerate(counts):
+            name = info if info is not None else f"count {k}"
+            requests += [(catalogs, f"{name} ({mode})", mode), (catalogs, f"{name} (nn)", CountMode.nn)]
+        results = self.count_pairs_batch(requests, progress=progress, max_workers=max_workers)
+        return [[NormalisedScalarCounts(kk.counts, nn.counts) for kk, nn in zip(results[2 * k], results[2 * k + 1])]
+                for k in range(len(counts))]
 
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
@@ -480,6 +508,20 @@ def _active_layout(catalog: Catalog, num_bins: int):
     if layout.num_bins not in (1, num_bins):
         raise ValueError(f"catalog was binned into {layout.num_bins} redshift bins, configuration has {num_bins}")
     return layout
+
+
+def _count_sides(layout1, layout2, mode):
+    """The layouts a count in ``mode`` runs on: per side the layout itself ("n") or its κ-weighted twin ("k"). A "k" side
+    without a scalar field raises as ``AngularTree.get_pair_weights`` does (trees.py:284-301)."""
+    k1, k2 = mode[0] == "k", mode[1] == "k"
+    if k1 and k2:
+        if layout1.kappa is None or layout2.kappa is None:
+            raise ValueError("missing required 'kappa' for both tree.")
+    elif k1 and layout1.kappa is None:
+        raise ValueError("missing required 'kappa' for first tree.")
+    elif k2 and layout2.kappa is None:
+        raise ValueError("missing required 'kappa' for second tree.")
+    return (layout1.twin if k1 else layout1), (layout2.twin if k2 else layout2)
 
 
 def _require_distinct(*catalogs) -> None:
@@ -538,3 +580,63 @@ def crosscorrelate(config, reference: Catalog, unknown: Catalog, *, ref_rand: Ca
         [((reference, unknown), "DD"), ((reference, unk_rand), "DR"), ((ref_rand, unknown), "RD"), ((ref_rand, unk_rand), "RR")],
         progress=progress, max_workers=max_workers)
     return [CorrFunc(dd, dr, rd, rr) for dd, dr, rd, rr in zip(DD, DR, RD, RR)]
+
+
+# ---------------------------------------------------------------------------------------------
+# scalar-field (nk / kk) correlations (measurements.py:631-794)
+def compute_scalar_normalisation(catalog: Catalog, binning) -> NormalisedScalarCounts:
+    """The mean scalar field per patch and redshift bin as a pair-count container: ``[B, P, P]`` tensors whose diagonals
+    hold the sum of ``kappa * w`` and the sum of ``w`` of every (patch, bin) tree, zero elsewhere
+    (measurements.py:634-648). The sums are taken on the device from the two resident catalogues of the layout
+    ``build_trees`` made (``yawhip_catalog_segment_sums``)."""
+    num_bins, num_patches = len(binning), catalog.num_patches
+    layout = _active_layout(catalog, num_bins)
+    if layout.kappa is None:
+        raise ValueError("catalog has no 'kappa' attached")
+    sums_k, sums_w = engine.scalar_segment_sums(layout)  # [P, B_or_1]
+    if layout.num_bins == 1 and num_bins != 1:  # an unbinned catalogue repeats its single tree (trees.py:600-601)
+        sums_k, sums_w = np.repeat(sums_k, num_bins, axis=1), np.repeat(sums_w, num_bins, axis=1)
+    sum_kappa = np.zeros((num_bins, num_patches, num_patches))
+    sum_weights = np.zeros_like(sum_kappa)
+    idx = np.arange(num_patches)
+    sum_kappa[:, idx, idx] = sums_k.T
+    sum_weights[:, idx, idx] = sums_w.T
+    return NormalisedScalarCounts(PatchedCounts(binning, sum_kappa, auto=False), PatchedCounts(binning, sum_weights, auto=False))
+
+
+def autocorrelate_scalar(config, data: Catalog, *, progress: bool = False, max_workers: int | None = None) -> list:
+    """Angular autocorrelation amplitude of a scalar field in redshift slices: the "kk" count of ``data`` with itself over
+    its "nn" count -> ``[ScalarCorrFunc]``, one per scale (measurements.py:651-705). ``data`` carries kappa and redshifts."""
+    edges, closed = config.binning.edges, config.binning.closed
+    _log_info("building data trees")
+    data.build_trees(edges, closed=closed)
+    _log_info("computing auto-correlation with DD")
+    links = PatchLinkage.from_catalogs(config, data)
+    DD = links.count_scalar_pairs(data, mode="kk", progress=progress, max_workers=max_workers, count_type_info="DD")
+    return [ScalarCorrFunc(dd) for dd in DD]
+
+
+def crosscorrelate_scalar(config, reference: Catalog, unknown: Catalog, *, unk_rand: Catalog | None = None,
+                          progress: bool = False, max_workers: int | None = None) -> list:
+    """Angular cross-correlation amplitude between the scalar field carried by ``reference`` (with redshifts) and the
+    ``unknown`` sample: "kn" DD, minus the same count against ``unk_rand`` when it is given, else minus the mean field per
+    patch (``compute_scalar_normalisation``) -> ``[ScalarCorrFunc]``, one per scale (measurements.py:708-794)."""
+    _require_distinct(reference, unknown, unk_rand)
+    count_dr = unk_rand is not None
+    edges, closed = config.binning.edges, config.binning.closed
+    randoms = []
+    _log_info("building reference data trees")
+    reference.build_trees(edges, closed=closed)
+    unknown.build_trees(None)
+    if count_dr:
+        unk_rand.build_trees(None)
+        randoms.append(unk_rand)
+    _log_info("computing cross-correlation with DD" + (", DR" if count_dr else ""))
+    links = PatchLinkage.from_catalogs(config, reference, unknown, *randoms)
+    kwargs = dict(progress=progress, max_workers=max_workers)
+    if count_dr:  # the reference counts DD (kn), DD (nn), DR (kn), DR (nn) one after the other; here they are ONE submission
+        DD, DR = links._count_scalar_batch([((reference, unknown), "DD"), ((reference, unk_rand), "DR")], "kn", **kwargs)
+    else:
+        DD = links.count_scalar_pairs(reference, unknown, mode="kn", count_type_info="DD", **kwargs)
+        DR = [compute_scalar_normalisation(reference, config.binning.binning)] * len(DD)
+    return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]

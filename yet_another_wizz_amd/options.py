@@ -30,6 +30,16 @@ class Closed(_StrOption):
     right = "right"
 
 
+class CountMode(_StrOption):
+    """What a pair count sums on each side (options.py:57-70): "n" the objects' weights, "k" their weights times the
+    scalar field ("kappa")."""
+
+    nn = "nn"
+    nk = "nk"
+    kn = "kn"
+    kk = "kk"
+
+
 class Unit(_StrOption):
     """Units of the correlation scales (options.py:168-208)."""
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from .corrdata import SampledData
 
-__all__ = ["PatchedSumWeights", "PatchedCounts", "NormalisedCounts"]
+__all__ = ["PatchedSumWeights", "PatchedCounts", "NormalisedCounts", "NormalisedScalarCounts"]
 
 
 def _as_index(item):
@@ -219,3 +219,25 @@ class NormalisedCounts(_BinPatchArray):
 
     def patches_subset(self, item):
         return type(self)(self._counts.patches_subset(item), self._weights.patches_subset(item))
+
+
+class NormalisedScalarCounts(NormalisedCounts):
+    """Pair counts weighted by a scalar field together with the plain (number) pair counts that normalise them
+    (paircounts.py:619-666): both are ``PatchedCounts`` over the same patch pairs. ``get_array`` is counts / patch-summed
+    number counts, ``sample_patch_sum`` the ratio of the two patch sums for the data and every jackknife sample -- the
+    arithmetic of ``NormalisedCounts`` with a second count tensor in the place of the product of weight sums."""
+
+    __slots__ = ()
+
+    def __init__(self, kappa_counts: PatchedCounts, number_counts: PatchedCounts) -> None:
+        if not isinstance(kappa_counts, PatchedCounts) or not isinstance(number_counts, PatchedCounts):
+            raise TypeError("'kappa_counts' and 'number_counts' must be of type PatchedCounts")
+        super().__init__(kappa_counts, number_counts)
+
+    @property
+    def kappa_counts(self) -> PatchedCounts:
+        return self._counts
+
+    @property
+    def number_counts(self) -> PatchedCounts:
+        return self._weights
