@@ -67,10 +67,13 @@ typedef struct yawhip_stats {
     int64_t n_workgroups;      /* workgroups of the dominant (count) kernel                              */
     int32_t n_launches;        /* kernel launches in this call                                           */
     int32_t kernel_used;       /* yawhip_kernel actually run                                             */
-    double kernel_ms;          /* HIP-event time of all launches of the call (item builder, count kernel,
-                                  reduction) on the context's stream                                     */
+    double kernel_ms;          /* device time from the first to the last kernel of the call (item builder, count
+                                  kernel, reduction): start of the builder to start of the call's tail kernel, from
+                                  stamps of the device's constant 100 MHz clock (HIP events when no builder ran) */
     double total_ms;           /* host wall time of the whole call (job upload, kernels, result download)*/
-    double count_ms;           /* HIP-event time of the count kernel(s) alone (ABI >= 2)                 */
+    double count_ms;           /* device time of the count kernel(s) alone (ABI >= 2): from the last builder workgroup's
+                                  exit to the start of the next kernel behind them, from the same clock stamps --
+                                  so it includes the two dispatch gaps next to the count kernel(s)            */
     int32_t layout_mode;       /* which device layouts the items came from (ABI >= 3): 0 = (patch, bin, u) segments,
                                   1 = (patch, strip) runs with all bins merged (binned x unbinned), 3 = (patch, bin,
                                   strip) runs (binned x binned, dense catalogues)                       */

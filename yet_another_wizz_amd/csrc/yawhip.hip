@@ -369,6 +369,23 @@ constexpr int BUILD_PREFIX_LDS = 1024;  // job tables up to this many entries ar
 // segment x.
 constexpr int ITEM_SEGS = 8;
 __host__ __device__ constexpr int ITEM_SEG_CTR(int seg) { return 12 + 8 * seg; }  // counters[]: one 64-byte line each
+// Clock stamps of a call (wall_clock64: the constant 100 MHz counter) and the words of its tail, in free words of the counter
+// block; they travel to the host with the counters (k_call_tail) and give yawhip_stats.kernel_ms / count_ms without an
+// event between the kernels.
+//   CTR_T_BUILD     the builder's first workgroup starts
+//   SEG_EXIT_CTR(s) latest exit of a builder workgroup, one word per item segment: spread like the append counters (one
+//                   shared word would take every workgroup's atomic in turn)
+//   CTR_T_COUNTED   the first kernel behind the count kernel(s) starts (reductions, k_counts_to_double); the tail writes its
+//                   own start here when there is none
+//   CTR_T_TAIL      the tail's first workgroup starts
+//   CTR_TICKET      the tail's workgroups draw tickets here (the last one to finish signs the call off); wraps to 0
+//   CTR_DONE        host image only: the sequence number of the call whose results the pinned block holds
+constexpr int CTR_T_BUILD = 1, CTR_T_COUNTED = 2, CTR_T_TAIL = 3, CTR_TICKET = 4, CTR_DONE = 6;
+__host__ __device__ constexpr int SEG_EXIT_CTR(int seg) { return ITEM_SEG_CTR(seg) + 1; }
+constexpr double CLOCK_MS = 1.0e-5;  // milliseconds per tick of wall_clock64
+__device__ __forceinline__ void stamp_start(unsigned long long *__restrict__ counters, int word) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counters[word] = wall_clock64();
+}
 __device__ __forceinline__ void append_items(bool keep, const Item &it, unsigned long long work, Item *__restrict__ items,
                                              unsigned long long *__restrict__ counters, unsigned char *__restrict__ kept,
                                              unsigned long long seg_cap = 0) {
@@ -402,6 +419,7 @@ __device__ __forceinline__ void append_items(bool keep, const Item &it, unsigned
     }
     __syncthreads();
     if (keep) items[s_base + s_cnt[wave] + __popcll(mask & ((1ull << lane) - 1ull))] = it;
+    if (threadIdx.x == 0) atomicMax(&counters[SEG_EXIT_CTR((int)(blockIdx.x % ITEM_SEGS))], (unsigned long long)wall_clock64());
 }
 
 template <bool SWEEP>
@@ -410,6 +428,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items(CatView c1, CatView c2
                                                      int tile, const double *__restrict__ rwin, int64_t n_pot,
                                                      Item *__restrict__ items, unsigned long long *__restrict__ counters,
                                                      unsigned char *__restrict__ kept) {
+    stamp_start(counters, CTR_T_BUILD);
     const int64_t pot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool keep = false;
     Item it{};
@@ -473,6 +492,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
     // run per lane tile: the triple centred on its strip) and the triples' offsets and grid index in the streamed table; their
     // sort key exists as float32 image only, so the window is widened by the rounding of a key (the count kernel searches
     // its bands in float32 with a margin of its own).
+    stamp_start(counters, CTR_T_BUILD);
     const int64_t pot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool keep = false;
     Item it{};
@@ -2071,7 +2091,8 @@ __global__ void k_item_work(const Item *__restrict__ items, const unsigned long 
 constexpr int REDUCE_CHUNK = 32;
 __global__ void k_reduce_chunks(const double *__restrict__ partials, const unsigned char *__restrict__ kept,
                                 const int64_t *__restrict__ prefix, const int64_t *__restrict__ cprefix, int n_slots,
-                                int slab, double *__restrict__ chunk_sums) {
+                                int slab, double *__restrict__ chunk_sums, unsigned long long *__restrict__ counters) {
+    stamp_start(counters, CTR_T_COUNTED);  // the first kernel behind the count kernels
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t g = idx / slab;
     if (g >= cprefix[n_slots]) return;
@@ -2090,7 +2111,8 @@ __global__ void k_reduce_chunks(const double *__restrict__ partials, const unsig
 }
 
 __global__ void k_reduce_slots(const double *__restrict__ chunk_sums, const int64_t *__restrict__ cprefix, int n_slots,
-                               int slab, double *__restrict__ out) {
+                               int slab, double *__restrict__ out, unsigned long long *__restrict__ stamp) {
+    if (stamp) stamp_start(stamp, CTR_T_COUNTED);  // (no chunks: this is the first kernel behind the count kernels)
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)n_slots * slab) return;
     const int slot = (int)(idx / slab), e = (int)(idx - (int64_t)slot * slab);
@@ -2151,9 +2173,47 @@ __global__ void k_scatter_rows(const double *__restrict__ in, const int32_t *__r
     out[(int64_t)row_index[r] * row + (i - r * row)] = in[i];
 }
 
-__global__ void k_counts_to_double(const unsigned long long *__restrict__ in, double *__restrict__ out, int64_t n) {
+__global__ void k_counts_to_double(const unsigned long long *__restrict__ in, double *__restrict__ out, int64_t n,
+                                   unsigned long long *__restrict__ counters) {
+    stamp_start(counters, CTR_T_COUNTED);  // the first kernel behind the count kernel
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (double)in[i];
+}
+
+// The last kernel of a count call: the first n_copy 16-byte units of the slot's result block [counters][counts][sums] go to
+// its pinned image, and the first n_clean of them are zeroed behind the read, so that the next call of the slot finds
+// counters and counts at zero without a fill (sums are always fully written and are not cleaned). Plain loads: the kernel
+// boundary has made the count kernel's atomics visible. The words of the call's own bookkeeping are not copied: the ticket
+// (device only), the completion word (host only) and the two stamps this kernel supplies.
+// Completion: every thread fences its stores to the host, every workgroup then draws a ticket, and the one that draws the
+// last writes the call's sequence number into the pinned block with a system-scope release -- the host polls that word
+// (count_finish). The ticket word wraps to zero with the last draw. No workgroup waits for another.
+constexpr int TAIL_WG = 256;
+constexpr unsigned TAIL_MAX_GRID = 64;
+__global__ __launch_bounds__(TAIL_WG) void k_call_tail(uint4 *__restrict__ dev, uint4 *__restrict__ host, unsigned n_copy,
+                                                      unsigned n_clean, unsigned long long seq) {
+    const unsigned long long t0 = wall_clock64();
+    static_assert(CTR_T_COUNTED == 2 && CTR_T_TAIL == 3 && CTR_TICKET == 4 && CTR_DONE == 6, "units 1, 2 and 3 of the block");
+    for (unsigned u = blockIdx.x * TAIL_WG + threadIdx.x; u < n_copy; u += gridDim.x * TAIL_WG) {
+        if (u == CTR_TICKET / 2 || u == CTR_DONE / 2) continue;
+        uint4 v = dev[u];
+        if (u == CTR_T_COUNTED / 2) {  // (a thread of the first workgroup)
+            if ((v.x | v.y) == 0u) { v.x = (unsigned)t0; v.y = (unsigned)(t0 >> 32); }  // no kernel behind the count kernel
+            v.z = (unsigned)t0; v.w = (unsigned)(t0 >> 32);
+        }
+        host[u] = v;
+        if (u < n_clean) dev[u] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned *ticket = reinterpret_cast<unsigned *>(dev) + 2 * CTR_TICKET;
+        if (atomicInc(ticket, gridDim.x - 1) == gridDim.x - 1) {
+            __threadfence_system();
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(host) + CTR_DONE, seq, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
 }
 
 inline DevTab make_tab(const double *x, const double *y, const double *z, const double *w, const int32_t *k, const int64_t *off,
@@ -2195,7 +2255,8 @@ struct Arena {
         if (n <= cap) return hipSuccess;
         release();
         const size_t want = n + n / 4 + 4096;
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&h), want, hipHostMallocPortable);
+        // (coherent: k_call_tail writes a result block and its completion word while the host polls for it)
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&h), want, hipHostMallocPortable | hipHostMallocCoherent);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), want);
         if (e == hipSuccess) cap = want; else release();
         return e;
@@ -2224,6 +2285,15 @@ struct CallBufs {
     DevBuf<double> d_chunk_sums;
     DevBuf<unsigned char> d_kept;   // weighted runs: 1 for potential items the builder kept
     Arena out;   // results (device -> host)
+    // The [counters][counts] part of out.d is zero whenever no call of the slot is in flight: k_call_tail zeroes it behind its
+    // reads. `dirty` is set while that may not hold -- from the moment a call starts to enqueue until count_finish has seen it
+    // complete, so also after a call that failed or was abandoned on the way, after a builder-only call (job_work) and after a
+    // call whose tail left the counts in place (fetch_results = false) -- and the next call then fills the block itself.
+    // zero_upto: the bytes from the start of out.d known to be zero while !dirty (a call with a larger result block than the
+    // last one's has its counts where that one's sums were).
+    bool dirty = true;
+    size_t zero_upto = 0;
+    uint64_t seq = 0;  // sequence number of the slot's calls: what k_call_tail writes into the pinned block when it is done
     Arena comb;  // yawhip_count_pairs_dense: recombination tables in, per-scale values out
     hipError_t make_events() {
         hipError_t e = hipSuccess;
@@ -3300,6 +3370,11 @@ struct CallState {
     int64_t cand = 0, abytes = 0, n_pot = 0;
     int launches = 0, kernel = 0, mode = 0, n_orient = 0, band_variant = 0, merged_triples = 0;
     int32_t variant[2] = {0, 0};   // count kernel of the unweighted, weighted launch (variant_code)
+    uint64_t seq = 0;              // what k_call_tail writes into the slot's pinned block when the call is done
+    bool word_wait = true;         // the completion word ends the wait (false: the caller put more behind the tail -- stream or event)
+    bool stamps = false;           // kernel_ms / count_ms from the device clock stamps (false: no builder ran -- events)
+    bool cleaned = false;          // the tail zeroes all of [counters][counts]: the slot is clean once the call is done
+    size_t zero_after = 0;         // ... and this many bytes from the start of the block are zero then
 };
 
 // yawhip_stats.count_variant*: the family and template arguments of a count kernel (code layout: include/yawhip.h)
@@ -4072,23 +4147,37 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     if (P.split) return SPLIT_JOBS;
     if (P.run_weighted) HIP_TRY(ctx->d_partials.reserve((size_t)std::max<int64_t>(P.n_items, 1) * P.slab));
     g_trace.mark("plan");
-    // results: [counters][counts][sums] in one device buffer, zeroed by one memset (sums are always fully written) and
-    // fetched by one copy
+    // results: [counters][counts][sums] in one device buffer; counters and counts are zero when no call of the slot is in
+    // flight (CallBufs::dirty; sums are always fully written), and k_call_tail brings back what was asked for
     const size_t o_ctr = 0, o_counts = align16(N_CTR * sizeof(unsigned long long)),
                  o_sums = o_counts + align16((size_t)P.n_out * sizeof(unsigned long long));
     const size_t out_bytes = o_sums + align16((size_t)P.n_out * sizeof(double));
+    const unsigned char *const block_was = ctx->out.d;
     HIP_TRY(ctx->out.reserve(out_bytes));
+    if (ctx->out.d != block_was) {  // a new block: nothing is known of it, and no call has signed it off
+        ctx->dirty = true;
+        reinterpret_cast<unsigned long long *>(ctx->out.h)[CTR_DONE] = 0;
+    }
     ctx->d_ctr = reinterpret_cast<unsigned long long *>(ctx->out.d + o_ctr);
     ctx->d_counts = reinterpret_cast<unsigned long long *>(ctx->out.d + o_counts);
     ctx->d_sums = reinterpret_cast<double *>(ctx->out.d + o_sums);
-    HIP_TRY(hipMemsetAsync(ctx->out.d, 0, P.n_items > 0 ? o_sums : out_bytes, ctx->stream));
+    // (no items: no kernel writes the sums either)
+    const size_t zero_needed = P.n_items > 0 ? o_sums : out_bytes;
+    if (ctx->dirty) ctx->zero_upto = 0;
+    if (ctx->zero_upto < zero_needed) {
+        HIP_TRY(hipMemsetAsync(ctx->out.d + ctx->zero_upto, 0, zero_needed - ctx->zero_upto, ctx->stream));
+        ctx->zero_upto = zero_needed;
+    }
+    ctx->dirty = true;  // until count_finish has seen this call's tail complete
+    cs.seq = ++ctx->seq;
+    cs.stamps = P.n_items > 0;  // a builder runs
 
     int launches = 0;
     const int64_t n_pot = P.n_items;
     int64_t n_items = P.n_items;  // the count grid: all potential items, or what the builder kept (SWEEP)
     unsigned long long seg_cap = 0;  // > 0: the item list is kept in ITEM_SEGS segments of this many records
     g_trace.mark("memset");
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     if (n_pot > 0) {
         if (n_pot >= (1ll << 31))
             return fail(YAWHIP_ERR_INVALID, "too many work items (%lld) in one job", (long long)n_pot);
@@ -4157,12 +4246,13 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         if (n_chunks > 0)
             hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((n_chunks * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
                                ctx->d_partials.ptr, all_kept ? nullptr : ctx->d_kept.ptr, P.d_prefix, P.d_cprefix,
-                               (int)n_oslots, (int)values, ctx->d_chunk_sums.ptr);
+                               (int)n_oslots, (int)values, ctx->d_chunk_sums.ptr, ctx->d_ctr);
         hipLaunchKernelGGL(k_reduce_slots, dim3((unsigned)((n_oslots * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_chunk_sums.ptr, P.d_cprefix, (int)n_oslots, (int)values, ctx->d_sums);
+                           ctx->d_chunk_sums.ptr, P.d_cprefix, (int)n_oslots, (int)values, ctx->d_sums,
+                           n_chunks > 0 ? nullptr : ctx->d_ctr);
         return hipGetLastError();
     };
-    HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
+    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
     // The count kernels. Their variants are picked from the plan (pick; each list runs from the last variant to the first:
     // the compiler lays the kernels out in the reverse order, which keeps the code object as it was).
     // Every launch records its variant in cs.variant[weighted] (yawhip_stats.count_variant*).
@@ -4298,19 +4388,32 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         HIP_TRY(reduce_partials());
         launches += 2;
     }
-    HIP_TRY(hipEventRecord(ctx->evc1, ctx->stream));
+    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->evc1, ctx->stream));
     if (!P.weighted && want_sums) {
         const int thr = 256;
         hipLaunchKernelGGL(k_counts_to_double, dim3((unsigned)((P.n_out + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_counts, ctx->d_sums, P.n_out);
+                           ctx->d_counts, ctx->d_sums, P.n_out, ctx->d_ctr);
         HIP_TRY(hipGetLastError());
         ++launches;
     }
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    // one copy brings back the counters and whatever was asked for, into pinned memory
-    // (fetch_results = false: the caller reduces the results on the device first and fetches what is left; counters only here)
+    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    // the tail brings back the counters and whatever was asked for, into pinned memory, and cleans behind itself
+    // (fetch_results = false: the caller reduces the results on the device first and fetches what is left; counters only here,
+    // and the counts stay where they are: the slot stays dirty)
     const size_t fetch = !fetch_results ? o_counts : (want_sums ? out_bytes : (want_counts ? o_sums : o_counts));
-    HIP_TRY(hipMemcpyAsync(ctx->out.h, ctx->out.d, fetch, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t clean = std::min(fetch, o_sums);
+    const bool sums_written = P.n_items > 0 && (P.run_weighted || want_sums);
+    cs.cleaned = clean == o_sums;
+    cs.zero_after = sums_written ? o_sums : ctx->zero_upto;
+    const unsigned n_copy = (unsigned)(fetch / 16), n_clean = (unsigned)(clean / 16);
+    static_assert(N_CTR * sizeof(unsigned long long) % 16 == 0 && (CTR_DONE + 2) * sizeof(unsigned long long) <= N_CTR * sizeof(unsigned long long),
+                  "the tail's words lie inside the counter block");
+    if (fetch / 16 > 0xffffffffull) return fail(YAWHIP_ERR_INVALID, "result block too large (%zu bytes)", fetch);
+    hipLaunchKernelGGL(k_call_tail, dim3(std::min((n_copy + TAIL_WG - 1) / TAIL_WG, TAIL_MAX_GRID)), dim3(TAIL_WG), 0, ctx->stream,
+                       reinterpret_cast<uint4 *>(ctx->out.d), reinterpret_cast<uint4 *>(ctx->out.h), n_copy, n_clean,
+                       (unsigned long long)cs.seq);
+    HIP_TRY(hipGetLastError());
+    ++launches;
     cs.pending = true;
     cs.o_ctr = o_ctr; cs.o_counts = o_counts; cs.o_sums = o_sums;
     cs.band_ran = band_ran; cs.run_unweighted = P.run_unweighted; cs.run_weighted = P.run_weighted;
@@ -4357,27 +4460,53 @@ int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, dou
     g_trace.mark("meanwhile");
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->spin_wait) {
-        // poll for up to 2 ms (a headline call takes 0.5 ms; the wake-up of a blocked thread costs ~0.01 ms), then block
-        hipError_t qe;
+        // poll for up to 2 ms (a headline call takes 0.5 ms; the wake-up of a blocked thread costs ~0.01 ms), then block.
+        // What is polled is the completion word k_call_tail writes into the slot's pinned block behind the results -- no
+        // runtime call per look -- unless the caller put more behind the tail: then the stream or the slot's ev_done, as before.
+        const unsigned long long *done_word = reinterpret_cast<const unsigned long long *>(ctx->out.h) + CTR_DONE;
+        auto query = [&]() { return wait_done ? hipEventQuery(ctx->ev_done) : hipStreamQuery(ctx->stream); };
+        hipError_t qe = hipErrorNotReady;
         const auto spin0 = std::chrono::steady_clock::now();
-        while ((qe = wait_done ? hipEventQuery(ctx->ev_done) : hipStreamQuery(ctx->stream)) == hipErrorNotReady &&
-               std::chrono::steady_clock::now() - spin0 < std::chrono::milliseconds(2))
+        do {
+            if (cs.word_wait) {
+                if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == cs.seq) qe = hipSuccess;
+            } else {
+                qe = query();
+            }
+            if (qe != hipErrorNotReady) break;
             __builtin_ia32_pause();
+        } while (std::chrono::steady_clock::now() - spin0 < std::chrono::milliseconds(2));
+        if (qe == hipSuccess && cs.word_wait) {  // one look at the runtime: an asynchronous error surfaces here, not a call later
+            const hipError_t late = query();
+            if (late != hipErrorNotReady) qe = late;  // (not ready: the packets behind the tail, or other slots' requests)
+        }
         if (qe == hipErrorNotReady) qe = wait_done ? hipEventSynchronize(ctx->ev_done) : hipStreamSynchronize(ctx->stream);
         HIP_TRY(qe);
     } else {
         HIP_TRY(wait_done ? hipEventSynchronize(ctx->ev_done) : hipStreamSynchronize(ctx->stream));
     }
     g_trace.mark("waited");
+    if (cs.cleaned) {  // the tail has left [counters][counts] of the slot's block at zero
+        ctx->dirty = false;
+        ctx->zero_upto = cs.zero_after;
+    }
     place_rows(fine_counts, reinterpret_cast<const int64_t *>(ctx->out.h + cs.o_counts), n_rows, row, row_index);
     place_rows(fine_sums, reinterpret_cast<const double *>(ctx->out.h + cs.o_sums), n_rows, row, row_index);
     const unsigned long long *ctr = reinterpret_cast<const unsigned long long *>(ctx->out.h + cs.o_ctr);
     g_trace.mark("copied");
     if (stats) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        float cms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&cms, ctx->evc0, ctx->evc1));
+        float ms = 0.f, cms = 0.f;
+        if (cs.stamps) {
+            // device clock stamps (see CTR_T_BUILD): the builder's start to the tail's start, and the latest builder exit to the
+            // start of the first kernel behind the count kernel(s) -- the count kernels with the dispatch gaps on either side
+            unsigned long long built = 0;
+            for (int sg = 0; sg < ITEM_SEGS; ++sg) built = std::max(built, ctr[SEG_EXIT_CTR(sg)]);
+            ms = (float)((double)(ctr[CTR_T_TAIL] - ctr[CTR_T_BUILD]) * CLOCK_MS);
+            cms = (float)((double)(ctr[CTR_T_COUNTED] - built) * CLOCK_MS);
+        } else {
+            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+            HIP_TRY(hipEventElapsedTime(&cms, ctx->evc0, ctx->evc1));
+        }
         stats->count_ms = cms;
         stats->candidate_pairs = cs.cand;
         unsigned long long tile_pairs = 0;
@@ -4639,6 +4768,7 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
         return YAWHIP_OK;
     }
     if (rc != YAWHIP_OK) return rc;
+    cs.word_wait = false;  // the rows are scattered behind the tail: the stream ends the wait
     HIP_TRY(hipMemsetAsync(ctx->d_full.ptr, 0, sizeof(double) * n_full, ctx->stream));
     if (cs.pending && n_jobs > 0) {
         HIP_TRY(hipMemcpyAsync(ctx->d_rowidx.ptr, row_index, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
@@ -4727,6 +4857,7 @@ int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins
     if (rc == SPLIT_JOBS) return YAWHIP_OK;  // counted in pieces by the blocking route when its turn comes (ds.enqueued stays false)
     if (rc != YAWHIP_OK) return rc;
     if (ds.device_combine) {
+        ds.cs.word_wait = false;  // the recombination and its copy follow the tail: ev_done, recorded behind them, ends the wait
         ds.n_comb = (int64_t)r.n_jobs * n_bins * n_scales;
         const size_t b_slices = align16(sizeof(int32_t) * 2 * (size_t)n_bins * n_scales);
         const size_t b_fact = fine_factors ? align16(sizeof(double) * (size_t)n_bins * nf) : 0;
