@@ -334,6 +334,28 @@ int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint6
                       uint32_t *uinteger_out);
 
 /*
+ * Random points inside a HEALPix mask or probability map with optional attached values -- HealPixRandoms.__call__ called
+ * for n values in chunks of chunksize, on the stream that generator defines (the reference picks its mask pixels from
+ * numpy's global RNG, so there is no reference stream): every value and the end state are the host route's, bit for bit.
+ * Per chunk of k values: k 64-bit outputs give u = (out >> 11) * 2^-53 and the pixel ipix_unmasked[j], j = number of
+ * cdf values <= u (numpy's searchsorted(cdf, u, "right")); k more give sub = out >> (64 - 2 (29 - order)) and the nested
+ * order-29 pixel ipix * 4^(29 - order) + sub, whose centre is the point; then the indices as for yawhip_random_box.
+ * Arguments as for yawhip_random_box, with the map instead of the box:
+ *   order          of the map, 0 .. 13
+ *   n_unmasked     1 .. 12 * 4^order
+ *   ipix_unmasked  int64[n_unmasked] nested pixel numbers at `order` (host)
+ *   cdf            float64[n_unmasked] cumulative probabilities, non-decreasing, cdf[n_unmasked - 1] == 1 (host)
+ *   x_out, y_out   float64[n] (host): x = ra = phi in radian, y = sin(dec) = z of the pixel centre
+ *   pix_out        int64[n] drawn order-29 pixels (host, may be NULL)
+ * The pixel list and the cdf are copied to the device once per call.
+ */
+int yawhip_random_healpix(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32,
+                          uint32_t uinteger, int32_t order, int64_t n_unmasked, const int64_t *ipix_unmasked,
+                          const double *cdf, int64_t n_data, const double *data_w, const double *data_z, double *x_out,
+                          double *y_out, double *w_out, double *z_out, int64_t *idx_out, int64_t *pix_out,
+                          uint64_t state_out[2], int32_t *has_uint32_out, uint32_t *uinteger_out);
+
+/*
  * Per-patch redshift histogram (HistData.from_catalog / _redshift_histogram, src/yaw/redshifts.py:44-57, 101-151).
  *   z, w          float64[n] host columns, grouped by patch (the catalogue's own order); w may be NULL
  *   offsets       int64[n_patches + 1], offsets[0] == 0, offsets[n_patches] == n, non-decreasing (empty patches allowed)

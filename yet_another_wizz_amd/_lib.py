@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "yawhip_job_work",
     "yawhip_assign_patches",
     "yawhip_random_box",
+    "yawhip_random_healpix",
     "yawhip_redshift_histogram",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
@@ -223,6 +224,11 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_random_box.argtypes = [
         _vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_uint32, ctypes.c_double,
         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p,
+        ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
+    ]
+    lib.yawhip_random_healpix.argtypes = [
+        _vp, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
+        ctypes.c_int64, _i64p, _dp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p,
         ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
     ]
     lib.yawhip_redshift_histogram.argtypes = [
@@ -528,7 +534,39 @@ def job_work(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, jobs, threshold
     return work
 
 
-RANDOM_MAX_DATA = 1 << 32  # yawhip_random_box: most attached values (numpy's 32-bit bounded-integer path)
+RANDOM_MAX_DATA = 1 << 32  # yawhip_random_box / _healpix: most attached values (numpy's 32-bit bounded-integer path)
+
+
+def _random_call(symbol: str, ctx: Context, n: int, chunksize: int, state: dict, shape_args, n_data: int, data_w, data_z,
+                 want_idx: bool, want_pix: bool):
+    """The call both generators make: ``shape_args`` are the arguments between the state and ``n_data`` (the box, or the
+    map). Returns ``(x, y, w, z, idx, pix, end_state)``."""
+    if state.get("bit_generator") != "PCG64":
+        raise ValueError(f"{symbol} follows numpy's PCG64 stream only")
+    data_w, data_z = _f64(data_w), _f64(data_z)
+    n = int(n)
+    x, y = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+    w = None if data_w is None else np.empty(n, dtype=np.float64)
+    z = None if data_z is None else np.empty(n, dtype=np.float64)
+    idx = np.empty(n, dtype=np.int64) if want_idx else None
+    pix = np.empty(n, dtype=np.int64) if want_pix else None
+    mask = (1 << 64) - 1
+    s, inc = int(state["state"]["state"]), int(state["state"]["inc"])
+    words = (ctypes.c_uint64 * 4)(s >> 64, s & mask, inc >> 64, inc & mask)
+    out = (ctypes.c_uint64 * 2)()
+    has_out, uint_out = ctypes.c_int32(0), ctypes.c_uint32(0)
+    outputs = [_ptr(x, _dp), _ptr(y, _dp), _ptr(w, _dp), _ptr(z, _dp), _ptr(idx, _i64p)]
+    if symbol == "yawhip_random_healpix":
+        outputs.append(_ptr(pix, _i64p))
+    _check(
+        getattr(load_library(), symbol)(
+            ctx._h, n, int(chunksize), words, int(state["has_uint32"]), int(state["uinteger"]), *shape_args, int(n_data),
+            _ptr(data_w, _dp), _ptr(data_z, _dp), *outputs, out, ctypes.byref(has_out), ctypes.byref(uint_out)),
+        symbol,
+    )
+    end = {"bit_generator": "PCG64", "state": {"state": (int(out[0]) << 64) | int(out[1]), "inc": inc},
+           "has_uint32": int(has_out.value), "uinteger": int(uint_out.value)}
+    return x, y, w, z, idx, pix, end
 
 
 def random_box(ctx: Context, n: int, chunksize: int, state: dict, x_min: float, x_range: float, y_min: float, y_range: float,
@@ -537,29 +575,22 @@ def random_box(ctx: Context, n: int, chunksize: int, state: dict, x_min: float, 
     ``state`` is ``Generator.bit_generator.state`` before the first chunk. Returns ``(x, y, w, z, idx, end_state)``: float64[n]
     columns (``w`` / ``z`` None without ``data_w`` / ``data_z``), int64[n] indices (None unless ``want_idx``) and the
     bit-generator state numpy is left in after the same draws."""
-    if state.get("bit_generator") != "PCG64":
-        raise ValueError("yawhip_random_box follows numpy's PCG64 stream only")
-    data_w, data_z = _f64(data_w), _f64(data_z)
-    n = int(n)
-    x, y = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
-    w = None if data_w is None else np.empty(n, dtype=np.float64)
-    z = None if data_z is None else np.empty(n, dtype=np.float64)
-    idx = np.empty(n, dtype=np.int64) if want_idx else None
-    mask = (1 << 64) - 1
-    s, inc = int(state["state"]["state"]), int(state["state"]["inc"])
-    words = (ctypes.c_uint64 * 4)(s >> 64, s & mask, inc >> 64, inc & mask)
-    out = (ctypes.c_uint64 * 2)()
-    has_out, uint_out = ctypes.c_int32(0), ctypes.c_uint32(0)
-    _check(
-        load_library().yawhip_random_box(
-            ctx._h, n, int(chunksize), words, int(state["has_uint32"]), int(state["uinteger"]), float(x_min), float(x_range),
-            float(y_min), float(y_range), int(n_data), _ptr(data_w, _dp), _ptr(data_z, _dp), _ptr(x, _dp), _ptr(y, _dp),
-            _ptr(w, _dp), _ptr(z, _dp), _ptr(idx, _i64p), out, ctypes.byref(has_out), ctypes.byref(uint_out)),
-        "yawhip_random_box",
-    )
-    end = {"bit_generator": "PCG64", "state": {"state": (int(out[0]) << 64) | int(out[1]), "inc": inc},
-           "has_uint32": int(has_out.value), "uinteger": int(uint_out.value)}
+    box = (float(x_min), float(x_range), float(y_min), float(y_range))
+    x, y, w, z, idx, _, end = _random_call("yawhip_random_box", ctx, n, chunksize, state, box, n_data, data_w, data_z,
+                                           want_idx, False)
     return x, y, w, z, idx, end
+
+
+def random_healpix(ctx: Context, n: int, chunksize: int, state: dict, order: int, ipix_unmasked, cdf, n_data: int = -1, data_w=None,
+                   data_z=None, *, want_idx: bool = False, want_pix: bool = False):
+    """Run ``yawhip_random_healpix``: ``n`` values of HealPixRandoms drawn in chunks of ``chunksize`` from numpy's PCG64 stream,
+    from the nested map of ``order`` whose unmasked pixels are ``ipix_unmasked`` with cumulative probabilities ``cdf``. Returns
+    ``(x, y, w, z, idx, pix, end_state)`` as :func:`random_box` does, with the drawn order-29 pixels (None unless ``want_pix``)."""
+    ipix, cdf = np.ascontiguousarray(ipix_unmasked, dtype=np.int64), _f64(cdf)
+    if len(cdf) != len(ipix):
+        raise ValueError("ipix_unmasked and cdf differ in length")
+    shape_args = (int(order), len(ipix), _ptr(ipix, _i64p), _ptr(cdf, _dp))
+    return _random_call("yawhip_random_healpix", ctx, n, chunksize, state, shape_args, n_data, data_w, data_z, want_idx, want_pix)
 
 
 def group_columns(keys, num_groups: int, columns, n_threads: int = 0):

@@ -532,14 +532,15 @@ class Catalog(Mapping):
                     overwrite: bool = False, progress: bool = False, max_workers: int | None = None,
                     chunksize: int | None = None, probe_size: int = -1):
         """Same signature as ``yaw.Catalog.from_random`` (catalog.py:1245-1340): ``num_randoms`` points of ``generator``
-        (a :class:`~yet_another_wizz_amd.randoms.BoxRandoms`), drawn from its reseeded stream in calls of ``chunksize``
-        (default 16 777 216, readers.py:49) -- the reference's catalogue for the same seed, and the generator is left in
-        the reference's end state. A ``BoxRandoms`` is drawn on the GPU when there is one (``engine.draw_box_randoms``,
-        the same values), otherwise chunk by chunk on the host; ``dec = arcsin(y)`` is taken on the host either way.
+        (a :class:`~yet_another_wizz_amd.randoms.BoxRandoms` or :class:`~yet_another_wizz_amd.randoms.HealPixRandoms`), drawn
+        from its reseeded stream in calls of ``chunksize`` (default 16 777 216, readers.py:49) -- for a ``BoxRandoms`` the
+        reference's catalogue for the same seed, and the generator is left in the reference's end state. Both generators
+        are drawn on the GPU when there is one (``engine.draw_box_randoms`` / ``engine.draw_healpix_randoms``, the same
+        values), otherwise chunk by chunk on the host; ``dec = arcsin(y)`` is taken on the host either way.
         The columns then go through ``from_arrays``. ``patch_num`` runs this package's k-means (as ``from_dataframe``
         does), whose centres differ from the treecorr centres of the reference; pass ``patch_centers`` for the
         reference's patches. ``progress`` and ``max_workers`` are accepted for compatibility and have no effect."""
-        from .randoms import BoxRandoms
+        from .randoms import BoxRandoms, HealPixRandoms
 
         num = int(num_randoms)
         if num < 1:
@@ -553,6 +554,10 @@ class Catalog(Mapping):
             from . import engine
 
             drawn = engine.draw_box_randoms(generator, num, chunksize)
+        elif type(generator) is HealPixRandoms:
+            from . import engine
+
+            drawn = engine.draw_healpix_randoms(generator, num, chunksize)
         if drawn is not None:
             (ra, y, weights, redshifts), _ = drawn
             dec = np.empty_like(y)

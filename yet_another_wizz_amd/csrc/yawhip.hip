@@ -5164,41 +5164,90 @@ int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const
     return YAWHIP_OK;
 }
 
-int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
-                      double x_min, double x_range, double y_min, double y_range, int64_t n_data, const double *data_w,
-                      const double *data_z, double *x_out, double *y_out, double *w_out, double *z_out, int64_t *idx_out,
-                      uint64_t state_out[2], int32_t *has_uint32_out, uint32_t *uinteger_out) {
-    if (!ctx || !state || !state_out || !has_uint32_out || !uinteger_out)
-        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: NULL argument");
-    if (n < 0 || chunksize < 1) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n < 0 or chunksize < 1");
+// What yawhip_random_box and yawhip_random_healpix check alike (`fn`: the name in the message); YAWHIP_OK or the failure.
+static int check_random_args(const char *fn, const yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int64_t n_data,
+                             const double *data_w, const double *data_z, const double *x_out, const double *y_out, const double *w_out,
+                             const double *z_out, const int64_t *idx_out, const uint64_t state_out[2], const int32_t *has_uint32_out,
+                             const uint32_t *uinteger_out) {
+    if (!ctx || !state || !state_out || !has_uint32_out || !uinteger_out) return fail(YAWHIP_ERR_INVALID, "%s: NULL argument", fn);
+    if (n < 0 || chunksize < 1) return fail(YAWHIP_ERR_INVALID, "%s: n < 0 or chunksize < 1", fn);
     if (n_data > (int64_t)1 << 32)
-        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n_data = %lld > 2^32: numpy draws these indices from its 64-bit bounded "
-                    "path, which the device does not implement", (long long)n_data);
-    if (n_data == 0 || n_data < -1) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: n_data must be -1 or 1 .. 2^32");
+        return fail(YAWHIP_ERR_INVALID, "%s: n_data = %lld > 2^32: numpy draws these indices from its 64-bit bounded "
+                    "path, which the device does not implement", fn, (long long)n_data);
+    if (n_data == 0 || n_data < -1) return fail(YAWHIP_ERR_INVALID, "%s: n_data must be -1 or 1 .. 2^32", fn);
     if (n_data == -1 && (data_w || data_z || idx_out))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: data arrays or indices without attached data (n_data = -1)");
+        return fail(YAWHIP_ERR_INVALID, "%s: data arrays or indices without attached data (n_data = -1)", fn);
     if (!data_w != !w_out || !data_z != !z_out)
-        return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: w_out / z_out must be given exactly with data_w / data_z");
-    if (n > 0 && (!x_out || !y_out)) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: x_out / y_out is NULL");
-    if ((state[3] & 1) == 0) return fail(YAWHIP_ERR_INVALID, "yawhip_random_box: the increment of a PCG64 state is odd");
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawrand::BoxDraw d;
+        return fail(YAWHIP_ERR_INVALID, "%s: w_out / z_out must be given exactly with data_w / data_z", fn);
+    if (n > 0 && (!x_out || !y_out)) return fail(YAWHIP_ERR_INVALID, "%s: x_out / y_out is NULL", fn);
+    if ((state[3] & 1) == 0) return fail(YAWHIP_ERR_INVALID, "%s: the increment of a PCG64 state is odd", fn);
+    return YAWHIP_OK;
+}
+
+static void fill_draw(yawrand::Draw &d, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
+                      int64_t n_data, const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
+                      double *z_out, int64_t *idx_out) {
     d.n = n;
     d.chunksize = chunksize;
     d.state_hi = state[0], d.state_lo = state[1], d.inc_hi = state[2], d.inc_lo = state[3];
     d.has_uint32 = has_uint32, d.uinteger = uinteger;
-    d.x_min = x_min, d.x_range = x_range, d.y_min = y_min, d.y_range = y_range;
     d.n_data = n_data, d.data_w = data_w, d.data_z = data_z;
     d.x_out = x_out, d.y_out = y_out, d.w_out = w_out, d.z_out = z_out, d.idx_out = idx_out;
-    yawrand::DrawEnd end;
-    const hipError_t e = yawrand::draw_box(ctx->stream, d, end);
+}
+
+static int finish_draw(const char *fn, hipError_t e, const yawrand::DrawEnd &end, uint64_t state_out[2], int32_t *has_uint32_out,
+                       uint32_t *uinteger_out) {
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_random_box failed: %s", hipGetErrorString(e));
+        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "%s failed: %s", fn, hipGetErrorString(e));
     state_out[0] = end.state_hi;
     state_out[1] = end.state_lo;
     *has_uint32_out = end.has_uint32;
     *uinteger_out = end.uinteger;
     return YAWHIP_OK;
+}
+
+int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
+                      double x_min, double x_range, double y_min, double y_range, int64_t n_data, const double *data_w,
+                      const double *data_z, double *x_out, double *y_out, double *w_out, double *z_out, int64_t *idx_out,
+                      uint64_t state_out[2], int32_t *has_uint32_out, uint32_t *uinteger_out) {
+    static const char fn[] = "yawhip_random_box";
+    if (const int rc = check_random_args(fn, ctx, n, chunksize, state, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out,
+                                         state_out, has_uint32_out, uinteger_out))
+        return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawrand::BoxDraw d;
+    fill_draw(d, n, chunksize, state, has_uint32, uinteger, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out);
+    d.x_min = x_min, d.x_range = x_range, d.y_min = y_min, d.y_range = y_range;
+    yawrand::DrawEnd end;
+    return finish_draw(fn, yawrand::draw_box(ctx->stream, d, end), end, state_out, has_uint32_out, uinteger_out);
+}
+
+int yawhip_random_healpix(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32,
+                          uint32_t uinteger, int32_t order, int64_t n_unmasked, const int64_t *ipix_unmasked, const double *cdf,
+                          int64_t n_data, const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
+                          double *z_out, int64_t *idx_out, int64_t *pix_out, uint64_t state_out[2], int32_t *has_uint32_out,
+                          uint32_t *uinteger_out) {
+    static const char fn[] = "yawhip_random_healpix";
+    if (const int rc = check_random_args(fn, ctx, n, chunksize, state, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out,
+                                         state_out, has_uint32_out, uinteger_out))
+        return rc;
+    if (order < 0 || order > 13) return fail(YAWHIP_ERR_INVALID, "%s: order %d outside 0 .. 13", fn, order);
+    const int64_t npix = (int64_t)12 << (2 * order);
+    if (n_unmasked < 1 || n_unmasked > npix || !ipix_unmasked || !cdf)
+        return fail(YAWHIP_ERR_INVALID, "%s: n_unmasked outside 1 .. 12 * 4^order, or ipix_unmasked / cdf is NULL", fn);
+    for (int64_t j = 0; j < n_unmasked; ++j) {
+        if (ipix_unmasked[j] < 0 || ipix_unmasked[j] >= npix)
+            return fail(YAWHIP_ERR_INVALID, "%s: ipix_unmasked[%lld] is no pixel of order %d", fn, (long long)j, order);
+        if (!(cdf[j] >= (j ? cdf[j - 1] : 0.0)))
+            return fail(YAWHIP_ERR_INVALID, "%s: cdf[%lld] is negative, NaN or below its predecessor", fn, (long long)j);
+    }
+    if (cdf[n_unmasked - 1] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the cdf must end in 1", fn);
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawrand::HealpixDraw d;
+    fill_draw(d, n, chunksize, state, has_uint32, uinteger, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out);
+    d.order = order, d.n_unmasked = n_unmasked, d.ipix_unmasked = ipix_unmasked, d.cdf = cdf, d.pix_out = pix_out;
+    yawrand::DrawEnd end;
+    return finish_draw(fn, yawrand::draw_healpix(ctx->stream, d, end), end, state_out, has_uint32_out, uinteger_out);
 }
 
 int yawhip_host_group_columns(int64_t n, const void *keys, int32_t key_bytes, int64_t num_groups, int32_t n_cols,

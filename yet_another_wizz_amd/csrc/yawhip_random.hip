@@ -18,6 +18,14 @@
 //     gathers weights[idx] / redshifts[idx] from device copies of the data. A window too short for the chunk is
 //     followed by the next one, from the output after its end.
 // The host follows the state from chunk to chunk with the same affine maps (unsigned __int128).
+//
+// HealPixRandoms (yawhip_random_healpix) reads the stream in the same shape -- 2k 64-bit outputs, then the k indices -- and
+// differs in what it makes of the outputs: output i picks a pixel of the mask, u = (out >> 11) * 2^-53 searched in the
+// cumulative probabilities of the unmasked pixels (numpy's searchsorted(cdf, u, "right")), output k + i picks one of the
+// 4^(29 - order) order-29 pixels inside it, sub = out >> (64 - 2 (29 - order)). k_random_healpix does both and writes the
+// centre of that order-29 nested pixel as x = phi, y = z = sin(dec): integer ring arithmetic of HEALPix' pix2loc, then
+// the few float64 operations of the host route (randoms.py: pix2loc_nest) in its order, every one rounded on its own.
+// The index pass and the state bookkeeping are the ones above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -91,6 +99,88 @@ __global__ __launch_bounds__(WG) void k_random_uniform(U128 s0, const Affine *__
         else
             y[i - n] = y_min + y_range * u;
         s = apply(stride, s);
+    }
+}
+
+// ---- HealPixRandoms ----
+constexpr int HP_ORDER = 29;                                // every point is the centre of a nested pixel of this order
+constexpr int64_t HP_NSIDE = (int64_t)1 << HP_ORDER;
+constexpr double HP_FACT2 = 4.0 / 3458764513820540928.0;    // 4 / npix, npix = 12 * 4^29
+constexpr double HP_FACT1 = 1073741824.0 * HP_FACT2;        // 2 nside * fact2
+constexpr double HP_HALFPI = 0x1.921fb54442d18p+0;          // numpy's pi / 2
+
+struct HealpixMap {
+    int shift;           // 2 (29 - order): bits of the sub-pixel number
+    int64_t n_unmasked;
+    const int64_t *__restrict__ ipix;  // unmasked pixels of the map, nested, ascending
+    const double *__restrict__ cdf;    // their cumulative probabilities, cdf[n_unmasked - 1] == 1
+};
+
+// every second bit of v (bits 0, 2, 4, ...), packed
+__device__ __forceinline__ int64_t even_bits(uint64_t v) {
+    v &= 0x5555555555555555ull;
+    v = (v | (v >> 1)) & 0x3333333333333333ull;
+    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
+    v = (v | (v >> 16)) & 0x00000000ffffffffull;
+    return (int64_t)v;
+}
+
+// Centre of the nested order-29 pixel p: phi and z = cos(theta). Float64 steps as in randoms.py (pix2loc_nest).
+__device__ __forceinline__ void healpix_centre(uint64_t p, double &phi, double &z) {
+    const int face = (int)(p >> (2 * HP_ORDER));
+    const uint64_t low = p & (((uint64_t)1 << (2 * HP_ORDER)) - 1);
+    const int64_t ix = even_bits(low), iy = even_bits(low >> 1);
+    const int64_t jrll = 2 + (face >> 2);                               // 2 2 2 2 3 3 3 3 4 4 4 4
+    const int64_t jpll = (int64_t)((0x753164207531ull >> (4 * (face & 15))) & 7);  // 1 3 5 7 0 2 4 6 1 3 5 7
+    const int64_t jr = (jrll << HP_ORDER) - ix - iy - 1;                // ring, 1 .. 4 nside - 1 from the north
+    int64_t nr, kshift;
+    if (jr < HP_NSIDE) {  // north cap
+        nr = jr, kshift = 0;
+        const double f = (double)nr;
+        z = 1.0 - f * f * HP_FACT2;
+    } else if (jr > 3 * HP_NSIDE) {  // south cap
+        nr = 4 * HP_NSIDE - jr, kshift = 0;
+        const double f = (double)nr;
+        z = f * f * HP_FACT2 - 1.0;
+    } else {
+        nr = HP_NSIDE, kshift = (jr - HP_NSIDE) & 1;
+        z = (double)(2 * HP_NSIDE - jr) * HP_FACT1;
+    }
+    int64_t jp = (jpll * nr + ix - iy + 1 + kshift) / 2;  // the sum is even
+    if (jp > 4 * HP_NSIDE) jp -= 4 * HP_NSIDE;
+    if (jp < 1) jp += 4 * HP_NSIDE;
+    phi = ((double)jp - (double)(kshift + 1) * 0.5) * (HP_HALFPI / (double)nr);
+}
+
+// Points 0 .. n-1 of a chunk after the state s0: output i picks the mask pixel, output n + i the sub-pixel.
+__global__ __launch_bounds__(WG) void k_random_healpix(U128 s0, const Affine *__restrict__ pow2, int64_t n, HealpixMap map,
+                                                       double *__restrict__ x, double *__restrict__ y, int64_t *__restrict__ pix) {
+    const int64_t first = (int64_t)blockIdx.x * TILE + threadIdx.x;
+    if (first >= n) return;
+    const Affine stride = pow2[WG_LOG2];
+    U128 sa = jump(pow2, s0, (uint64_t)first + 1);
+    U128 sb = jump(pow2, s0, (uint64_t)(n + first) + 1);
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int64_t i = first + (int64_t)r * WG;
+        if (i >= n) break;
+        const double u = (double)(output(sa) >> 11) * 0x1.0p-53;
+        const uint64_t sub = output(sb) >> (64 - map.shift);
+        int64_t lo = 0, hi = map.n_unmasked;  // the slot is the number of cdf values <= u
+        while (lo < hi) {
+            const int64_t m = (lo + hi) >> 1;
+            if (map.cdf[m] <= u) lo = m + 1; else hi = m;
+        }
+        lo = lo < map.n_unmasked ? lo : map.n_unmasked - 1;  // u < 1 == cdf[n_unmasked - 1]: never taken, keeps the load inside
+        const uint64_t p = ((uint64_t)map.ipix[lo] << map.shift) | sub;
+        double phi, z;
+        healpix_centre(p, phi, z);
+        x[i] = phi;
+        y[i] = z;
+        if (pix) pix[i] = (int64_t)p;
+        sa = apply(stride, sa);
+        sb = apply(stride, sb);
     }
 }
 
@@ -259,7 +349,7 @@ uint64_t host_output(u128 s) {
 U128 dev(u128 s) { return {(uint64_t)(s >> 64), (uint64_t)s}; }
 
 struct Buffers {
-    void *p[12] = {};
+    void *p[16] = {};
     int n = 0;
     template <class T>
     hipError_t get(T **out, size_t count) {
@@ -280,9 +370,11 @@ struct Buffers {
         if (e_ != hipSuccess) return e_;   \
     } while (0)
 
-}  // namespace
-
-hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
+// The chunks of one draw. `coords` is what tells the generators apart: coords.launch(stream, s0, pow2, k, x, y) writes the
+// k coordinate pairs of a chunk from the 2k outputs after the state s0, coords.fetch(stream, off, k) copies what it
+// made besides x and y to the host; `buf` already holds what coords needs on the device.
+template <class Coords>
+hipError_t draw_chunks(hipStream_t stream, const Draw &d, DrawEnd &end, Buffers &buf, const Coords &coords) {
     const u128 inc = ((u128)d.inc_hi << 64) | d.inc_lo;
     u128 state = ((u128)d.state_hi << 64) | d.state_lo;
     bool pending = d.has_uint32 != 0;
@@ -293,7 +385,6 @@ hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
     const uint32_t threshold = bounded ? (uint32_t)((((uint64_t)1 << 32) - (uint64_t)d.n_data) % (uint64_t)d.n_data) : 0;
     const double accept_rate = 1.0 - threshold / 4294967296.0;
 
-    Buffers buf;
     Affine *pow2 = nullptr;
     double *x = nullptr, *y = nullptr, *w = nullptr, *z = nullptr, *dw = nullptr, *dz = nullptr;
     int64_t *idx = nullptr, *offs = nullptr, *scalars = nullptr;
@@ -323,9 +414,7 @@ hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
 
     for (int64_t off = 0; off < d.n; off += chunk_max) {
         const int64_t k = std::min(chunk_max, d.n - off);
-        hipLaunchKernelGGL(k_random_uniform, dim3((unsigned)((2 * k + TILE - 1) / TILE)), dim3(WG), 0, stream, dev(state), pow2, k,
-                           d.x_min, d.x_range, d.y_min, d.y_range, x, y);
-        TRY(hipGetLastError());
+        TRY(coords.launch(stream, dev(state), pow2, k, x, y));
         state = steps(inc, 2 * (uint64_t)k)(state);
         if (bounded) {
             Sink sink = sink_proto;
@@ -381,6 +470,7 @@ hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
         }
         TRY(hipMemcpyAsync(d.x_out + off, x, k * sizeof(double), hipMemcpyDeviceToHost, stream));
         TRY(hipMemcpyAsync(d.y_out + off, y, k * sizeof(double), hipMemcpyDeviceToHost, stream));
+        TRY(coords.fetch(stream, off, k));
         if (bounded) {
             if (d.w_out) TRY(hipMemcpyAsync(d.w_out + off, w, k * sizeof(double), hipMemcpyDeviceToHost, stream));
             if (d.z_out) TRY(hipMemcpyAsync(d.z_out + off, z, k * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -398,6 +488,51 @@ hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
     end.has_uint32 = pending ? 1 : 0;
     end.uinteger = half;
     return hipSuccess;
+}
+
+struct BoxCoords {
+    const BoxDraw &d;
+    hipError_t launch(hipStream_t stream, U128 s0, const Affine *pow2, int64_t k, double *x, double *y) const {
+        hipLaunchKernelGGL(k_random_uniform, dim3((unsigned)((2 * k + TILE - 1) / TILE)), dim3(WG), 0, stream, s0, pow2, k, d.x_min,
+                           d.x_range, d.y_min, d.y_range, x, y);
+        return hipGetLastError();
+    }
+    hipError_t fetch(hipStream_t, int64_t, int64_t) const { return hipSuccess; }
+};
+
+struct HealpixCoords {
+    HealpixMap map;
+    int64_t *pix, *pix_out;  // device chunk and host output of the drawn order-29 pixels, both null if not asked for
+    hipError_t launch(hipStream_t stream, U128 s0, const Affine *pow2, int64_t k, double *x, double *y) const {
+        hipLaunchKernelGGL(k_random_healpix, dim3((unsigned)((k + TILE - 1) / TILE)), dim3(WG), 0, stream, s0, pow2, k, map, x, y, pix);
+        return hipGetLastError();
+    }
+    hipError_t fetch(hipStream_t stream, int64_t off, int64_t k) const {
+        return pix_out ? hipMemcpyAsync(pix_out + off, pix, k * sizeof(int64_t), hipMemcpyDeviceToHost, stream) : hipSuccess;
+    }
+};
+
+}  // namespace
+
+hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
+    Buffers buf;
+    return draw_chunks(stream, d, end, buf, BoxCoords{d});
+}
+
+hipError_t draw_healpix(hipStream_t stream, const HealpixDraw &d, DrawEnd &end) {
+    Buffers buf;  // the map goes up once, before the chunks
+    HealpixCoords c{{2 * (HP_ORDER - d.order), d.n_unmasked, nullptr, nullptr}, nullptr, d.pix_out};
+    int64_t *ipix = nullptr;
+    double *cdf = nullptr;
+    TRY(buf.get(&ipix, d.n_unmasked));
+    TRY(buf.get(&cdf, d.n_unmasked));
+    TRY(hipMemcpyAsync(ipix, d.ipix_unmasked, d.n_unmasked * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    TRY(hipMemcpyAsync(cdf, d.cdf, d.n_unmasked * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (d.pix_out) TRY(buf.get(&c.pix, std::min(d.n, d.chunksize)));
+    c.map.ipix = ipix, c.map.cdf = cdf;
+    const hipError_t e = draw_chunks(stream, d, end, buf, c);
+    if (e != hipSuccess) (void)hipStreamSynchronize(stream);  // the uploads read this call's host memory
+    return e;
 }
 
 }  // namespace yawrand

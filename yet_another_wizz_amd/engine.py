@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms", "draw_healpix_randoms",
            "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -218,6 +218,19 @@ def assign_patches(xyz, centers_xyz):
     return ids.astype(np.int64)
 
 
+def _random_context(generator):
+    """The context random catalogues are drawn on, or ``None`` when there is no library or device, or the generator has
+    more than 2^32 attached values (numpy's 64-bit bounded-integer path)."""
+    if generator.data_size > _lib.RANDOM_MAX_DATA:
+        return None
+    try:
+        if _lib.device_count() < 1:
+            return None
+        return get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+
+
 def draw_box_randoms(generator, num: int, chunksize: int):
     """``num`` points of a ``BoxRandoms`` drawn on the device (``yawhip_random_box``) in calls of ``chunksize`` from the
     generator's current state, as ``Catalog.from_random`` calls it on the host. Returns ``((x, y, w, z), end_state)`` --
@@ -225,17 +238,25 @@ def draw_box_randoms(generator, num: int, chunksize: int):
     the generator is left in too -- or ``None`` when there is no library or device, or more than 2^32 attached values
     (numpy's 64-bit bounded-integer path). Drawing randoms is catalogue preparation: like ``assign_patches`` it may fall
     back to the host, the pair counts may not."""
-    if generator.data_size > _lib.RANDOM_MAX_DATA:
-        return None
-    try:
-        if _lib.device_count() < 1:
-            return None
-        ctx = get_context(default_devices()[0])
-    except _lib.YawhipError:
+    ctx = _random_context(generator)
+    if ctx is None:
         return None
     x, y, w, z, _, end = _lib.random_box(
         ctx, num, chunksize, generator.rng.bit_generator.state, generator.x_min, generator.x_max - generator.x_min,
         generator.y_min, generator.y_max - generator.y_min, generator.data_size, generator.weights, generator.redshifts)
+    generator.rng.bit_generator.state = end
+    return (x, y, w, z), end
+
+
+def draw_healpix_randoms(generator, num: int, chunksize: int):
+    """``num`` points of a ``HealPixRandoms`` drawn on the device (``yawhip_random_healpix``): the contract of
+    :func:`draw_box_randoms`, with ``x = ra`` and ``y = sin(dec)`` of order-29 pixel centres inside the generator's map."""
+    ctx = _random_context(generator)
+    if ctx is None:
+        return None
+    x, y, w, z, _, _, end = _lib.random_healpix(
+        ctx, num, chunksize, generator.rng.bit_generator.state, generator.order, generator._ipix_unmasked, generator._cdf,
+        generator.data_size, generator.weights, generator.redshifts)
     generator.rng.bit_generator.state = end
     return (x, y, w, z), end
 
