@@ -372,6 +372,27 @@ int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const
                               double *out);
 
 /*
+ * HEALPix pixels of n points and their map (healpix.ang2pix / healpix.healpix_map, Catalog.healpix_map; what the reference
+ * leaves to healpy's ang2pix and np.bincount). The pixel is HEALPix' loc2pix in the float64 steps healpix.py documents,
+ * one IEEE operation each: every pixel is the host route's, bit for bit. A ring-scheme number is the nested pixel put
+ * through the ring arithmetic of yawhip_random_healpix' pixel centres (ABI >= 6).
+ *   chunksize   objects per pass (0: 2^24; values above 2^28 are cut to 2^28); the results do not depend on it
+ *   phi, z      float64[n] host columns: ra in radian (any finite value) and sin(dec)
+ *   w           float64[n] weights (host), may be NULL; read only for map_out
+ *   order       of the map, 0 .. 13 (nside = 2^order)
+ *   nested      1: NESTED numbers, 0: RING numbers
+ *   pix_out     int64[n] pixel of every point (host, may be NULL); -1 for a point with a non-finite phi or z or |z| > 1
+ *   map_out     float64[12 * 4^order] (host, may be NULL): objects per pixel (w == NULL; 64-bit integer counters on the
+ *               device, exact) or the sum of weights per pixel; points with pixel -1 are left out
+ * pix_out and map_out may not both be NULL. The weighted map equals numpy's sequential np.bincount(pix, w) bit for bit
+ * and is the same from run to run: per pass a stable radix sort by pixel, then one thread per pixel adds its weights to
+ * the map's value in object order (no floating-point atomics). That thread is alone with its pixel, so a weighted map of
+ * few pixels and many objects is slow (order 0: twelve threads).
+ */
+int yawhip_healpix_map(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const double *phi, const double *z,
+                       const double *w, int32_t order, int32_t nested, int64_t *pix_out, double *map_out);
+
+/*
  * Host-only helper of the ingest path (no device, no context): stable grouping of float64 columns by an integer key --
  * what the reference does per chunk with groupby(patch_ids, chunk) (catalog/catalog.py:293, utils/misc.py:40-51) and
  * groupby(bin_idx, chunk) (catalog/trees.py:413), i.e. np.argsort(kind="stable") + a gather per column, here as one

@@ -23,7 +23,7 @@ from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
                            crosscorrelate_scalar)
-from . import randoms
+from . import healpix, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
 
@@ -53,5 +53,6 @@ __all__ = [
     "compute_scalar_normalisation",
     "crosscorrelate",
     "crosscorrelate_scalar",
+    "healpix",
     "randoms",
 ]

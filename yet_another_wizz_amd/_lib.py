@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "yawhip_assign_patches",
     "yawhip_random_box",
     "yawhip_random_healpix",
+    "yawhip_healpix_map",
     "yawhip_redshift_histogram",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
@@ -231,6 +232,7 @@ def load_library() -> ctypes.CDLL:
         ctypes.c_int64, _i64p, _dp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p,
         ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
     ]
+    lib.yawhip_healpix_map.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _i64p, _dp]
     lib.yawhip_redshift_histogram.argtypes = [
         _vp, ctypes.c_int64, _dp, _dp, ctypes.c_int32, _i64p, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
     ]
@@ -650,6 +652,24 @@ def assign_patches(ctx: Context, x, y, z, centers_xyz) -> np.ndarray:
         "yawhip_assign_patches",
     )
     return out
+
+
+def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,
+                chunksize: int = 0):
+    """Run ``yawhip_healpix_map``: ``(pix, map)`` of the points ``(phi, z)`` at ``order`` -- int64[n] pixels (-1 for a point
+    with a non-finite coordinate or ``|z| > 1``) and the float64[12 * 4^order] map of object counts, or of summed ``w`` --
+    each ``None`` unless wanted. The arrays go to the library as they are: it checks sizes, not values."""
+    phi, z, w = _f64(phi), _f64(z), _f64(w)
+    if len(z) != len(phi) or (w is not None and len(w) != len(phi)):
+        raise ValueError("phi, z and weights differ in length")
+    pix = np.empty(len(phi), dtype=np.int64) if want_pixels else None
+    out = np.empty(12 << (2 * order), dtype=np.float64) if want_map and 0 <= order <= 13 else None
+    _check(
+        load_library().yawhip_healpix_map(ctx._h, len(phi), int(chunksize), _ptr(phi, _dp), _ptr(z, _dp), _ptr(w, _dp), int(order),
+                                          int(bool(nested)), _ptr(pix, _i64p), _ptr(out, _dp)),
+        "yawhip_healpix_map",
+    )
+    return pix, out
 
 
 def redshift_histogram(ctx: Context, z, w, offsets, edges, closed_right: bool) -> np.ndarray:

@@ -15,9 +15,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = [os.path.join(CSRC, "yawhip.hip"), os.path.join(CSRC, "yawhip_sort.hip"), os.path.join(CSRC, "yawhip_random.hip"),
-           os.path.join(CSRC, "yawhip_hist.hip")]
+           os.path.join(CSRC, "yawhip_hist.hip"), os.path.join(CSRC, "yawhip_healpix.hip")]
 HEADERS = [os.path.join(ROOT, "include", "yawhip.h"), os.path.join(CSRC, "yawhip_sort.h"), os.path.join(CSRC, "yawhip_random.h"),
-           os.path.join(CSRC, "yawhip_hist.h"),
+           os.path.join(CSRC, "yawhip_hist.h"), os.path.join(CSRC, "yawhip_healpix.h"),
            os.path.join(CSRC, "yawhip_band32.inc")]
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT, "include")

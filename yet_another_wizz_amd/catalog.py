@@ -577,6 +577,17 @@ class Catalog(Mapping):
         new._random_route = route
         return new
 
+    def healpix_map(self, nside: int, *, nested: bool = True, weighted: bool = True):
+        """HEALPix map (float64[12 nside^2]) of the catalogue: the sum of weights per pixel if it has weights and
+        ``weighted``, else the objects per pixel; NESTED numbers unless ``nested=False`` (RING). ``nside`` is a power of two
+        up to 8192 (ValueError otherwise). The pixels are those of ``healpix.ang2pix`` for ``(ra, sin dec)``; large
+        catalogues are mapped on the GPU when there is one (``healpix.healpix_map``, the same values)."""
+        from . import healpix
+
+        order = healpix.nside2order(nside)
+        weights = self._w if weighted else None
+        return healpix.healpix_map(order, self._ra, self._unit_vectors()[2], weights, nested=nested)
+
     # ------------------------------------------------------------------ mapping interface
     def __len__(self) -> int:
         return len(self._patches)

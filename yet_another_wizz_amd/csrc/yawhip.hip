@@ -58,6 +58,7 @@
 
 #include "yawhip.h"
 #include "yawhip_random.h"
+#include "yawhip_healpix.h"
 #include "yawhip_hist.h"
 #include "yawhip_sort.h"
 
@@ -2393,6 +2394,7 @@ struct yawhip_ctx : CallBufs {
         std::vector<std::vector<int32_t>> parts;  // job indices per device
     } plan;
     yawsort::Workspace sort_ws;  // upload-side sorts
+    yawpix::Workspace pix_ws;    // yawhip_healpix_map
     CallBufs parked[MAX_BATCH];  // the slots that are not active (the active one's entry is empty)
     int slot = 0;
     uint64_t opt_gen = 1;        // bumped by every accepted yawhip_ctx_set_option: plans and the partition are keyed on it
@@ -3035,6 +3037,7 @@ int yawhip_ctx_destroy(yawhip_ctx *ctx) {
     ctx->d_full.release();
     ctx->d_rowidx.release();
     ctx->sort_ws.release();
+    ctx->pix_ws.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return YAWHIP_OK;
@@ -5161,6 +5164,32 @@ int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const
     const hipError_t e = yawhist::redshift_histogram(ctx->stream, c);
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_redshift_histogram failed: %s", hipGetErrorString(e));
+    return YAWHIP_OK;
+}
+
+int yawhip_healpix_map(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const double *phi, const double *z, const double *w, int32_t order,
+                       int32_t nested, int64_t *pix_out, double *map_out) {
+    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: ctx is NULL");
+    if (!pix_out && !map_out) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: pix_out and map_out are both NULL");
+    if (n < 0 || chunksize < 0 || (n > 0 && (!phi || !z)))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: n < 0, chunksize < 0 or NULL phi / z");
+    if (order < 0 || order > yawpix::MAX_ORDER)
+        return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: order %d outside 0 .. %d", order, yawpix::MAX_ORDER);
+    if (nested != 0 && nested != 1) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: nested must be 0 or 1");
+    if (n == 0) {
+        if (map_out) std::fill(map_out, map_out + ((size_t)12 << (2 * order)), 0.0);
+        return YAWHIP_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawpix::MapCall c;
+    c.n = n, c.chunksize = std::min(chunksize > 0 ? chunksize : yawpix::DEFAULT_CHUNK, yawpix::MAX_CHUNK);
+    c.phi = phi, c.z = z, c.w = w;
+    c.order = order, c.nested = nested;
+    c.pix_out = pix_out, c.map_out = map_out;
+    const hipError_t e = yawpix::healpix_map(ctx->pix_ws, ctx->stream, c);
+    if (ctx->pix_ws.bytes() > ((size_t)1 << 28)) ctx->pix_ws.release();  // keep only small workspaces, as the sort workspace
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_healpix_map failed: %s", hipGetErrorString(e));
     return YAWHIP_OK;
 }
 

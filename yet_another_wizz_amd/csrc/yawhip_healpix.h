@@ -1,0 +1,44 @@
+// Internal interface between yawhip.hip and yawhip_healpix.hip (HEALPix pixels and maps of a catalogue,
+// yawhip_healpix_map). Not part of the C ABI: yawhip.hip checks the arguments and owns the error reporting.
+#ifndef YAWHIP_HEALPIX_H
+#define YAWHIP_HEALPIX_H
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+namespace yawpix {
+
+constexpr int MAX_ORDER = 13;                         // a float64 map of order 14 is 25 GB
+constexpr int64_t DEFAULT_CHUNK = (int64_t)1 << 24;   // objects per pass when the caller gives 0
+constexpr int64_t MAX_CHUNK = (int64_t)1 << 28;       // larger chunk sizes are cut to this
+
+// Device buffers of the call (grow-only, owned by the caller's context).
+struct Workspace {
+    double *cols = nullptr;      // [3][chunk_cap]: phi, z, w of one pass
+    int64_t *pix = nullptr;      // [chunk_cap] pixels of one pass
+    uint32_t *keys = nullptr;    // [2][chunk_cap] sort keys, in and out (weighted maps)
+    double *w_sorted = nullptr;  // [chunk_cap]
+    size_t chunk_cap = 0;
+    bool sort_bufs = false;      // keys and w_sorted are allocated for chunk_cap
+    void *tmp = nullptr;         // rocPRIM's temporary storage
+    size_t tmp_bytes = 0;
+    double *map = nullptr;       // [map_cap] the map: uint64 counters while objects are counted, float64 at the end
+    size_t map_cap = 0;
+    size_t bytes() const;
+    void release();
+};
+
+// One call (see yawhip_healpix_map in include/yawhip.h for the meaning of every field).
+struct MapCall {
+    int64_t n = 0, chunksize = 0;                           // chunksize in 1 .. MAX_CHUNK
+    const double *phi = nullptr, *z = nullptr, *w = nullptr;  // host, n values each, w may be null
+    int32_t order = 0, nested = 1;
+    int64_t *pix_out = nullptr;  // host, n values, may be null
+    double *map_out = nullptr;   // host, 12 * 4^order values, may be null
+};
+
+// Runs the call on the current device's `stream` and waits for it. Arguments are already checked.
+hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c);
+
+}  // namespace yawpix
+#endif

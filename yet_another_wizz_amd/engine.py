@@ -15,7 +15,7 @@ from . import _lib
 from .parallel import local_device_index, world
 
 __all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms", "draw_healpix_randoms",
-           "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
+           "healpix_map", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
 default_kernel = "auto"
@@ -259,6 +259,19 @@ def draw_healpix_randoms(generator, num: int, chunksize: int):
         generator.data_size, generator.weights, generator.redshifts)
     generator.rng.bit_generator.state = end
     return (x, y, w, z), end
+
+
+def healpix_map(phi, z, weights, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True, chunksize: int = 0):
+    """HEALPix pixels and map of the points ``(phi, z)`` on the device (``yawhip_healpix_map``): ``(pix, map)``, each ``None``
+    unless wanted (see ``_lib.healpix_map``), or ``None`` when no GPU / library is available -- like patch assignment this is
+    catalogue preparation, and ``healpix.ang2pix`` / ``healpix.healpix_map`` then compute the same values with numpy."""
+    try:
+        if _lib.device_count() < 1:
+            return None
+        ctx = get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+    return _lib.healpix_map(ctx, phi, z, weights, order, nested, want_pixels=want_pixels, want_map=want_map, chunksize=chunksize)
 
 
 def redshift_histogram(z, w, offsets, edges, closed_right: bool) -> np.ndarray:

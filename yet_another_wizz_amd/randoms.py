@@ -219,6 +219,15 @@ class HealPixRandoms(RandomsBase):
         cdf /= cdf[-1]
         self._cdf = cdf
 
+    @classmethod
+    def from_catalog(cls, catalog, nside: int, *, is_mask: bool = True, weights=None, redshifts=None, seed: int = 12345):
+        """Generator over the footprint of ``catalog``: its nested map at ``nside`` (``Catalog.healpix_map``: summed weights,
+        or counts for a catalogue without weights) as ``pix_values``. With ``is_mask`` (the default) every occupied pixel is
+        drawn alike, otherwise in proportion to its value. ``weights`` / ``redshifts`` are the values to attach, as in the
+        constructor."""
+        return cls(catalog.healpix_map(nside, nested=True), nested=True, is_mask=is_mask, weights=weights, redshifts=redshifts,
+                   seed=seed)
+
     def _ring2nest(self, values):
         nested = np.empty_like(values)
         step = 1 << 22  # pixels reordered at a time: bounds the index temporaries of a large map
