@@ -393,6 +393,33 @@ int yawhip_healpix_map(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const doub
                        const double *w, int32_t order, int32_t nested, int64_t *pix_out, double *map_out);
 
 /*
+ * The unmasked pixels of a full-sky HEALPix scalar map as the columns of a catalogue (healpix.map_pixels,
+ * Catalog.from_healpix_map): what a user of the reference does with healpy's pix2ang and a mask. A pixel is selected when
+ * its value is finite and not healpy's UNSEEN (-1.6375e30) and, with a weight map, its weight is finite and > 0. The
+ * outputs list the selected pixels in ascending NESTED number, whatever the scheme of the maps (ABI >= 6).
+ *   n_pix       12 * 4^order
+ *   chunksize   nested pixels per pass (0: 2^24; values above 2^28 are cut to 2^28); the results do not depend on it
+ *   values      float64[n_pix] the map (host)
+ *   weights     float64[n_pix] weight / coverage map in the same scheme (host), may be NULL
+ *   order       of the maps, 0 .. 13 (nside = 2^order)
+ *   nested      1: the maps are in NESTED order, 0: in RING order
+ *   capacity    entries of every output: the number of selected pixels, counted by the caller with the same rule
+ *   ipix_out    int64[capacity] pixel number in the maps' own scheme: values[ipix] is kappa (host)
+ *   phi_out, z_out   float64[capacity] pixel centre: ra in radian and sin(dec), the float64 steps of randoms.pix2loc_nest,
+ *               one IEEE operation each, bit for bit the host route's
+ *   kappa_out   float64[capacity] the value
+ *   w_out       float64[capacity] the weight; not written (may be NULL) without weights
+ *   n_selected  pixels selected and written (out)
+ * Outputs may be NULL when capacity is 0. Nothing is written at or beyond `capacity`: a pass that would go beyond it ends
+ * the call with YAWHIP_ERR_MISMATCH before it is copied, and so does a total other than `capacity`. Per pass a count kernel
+ * (wave ballot, one count per workgroup), an exclusive scan and a write kernel that places every selected pixel by its
+ * rank: order preserving, without atomics or floating-point sums; all pixel and element indices are 64-bit.
+ */
+int yawhip_healpix_pixels(yawhip_ctx *ctx, int64_t n_pix, int64_t chunksize, const double *values, const double *weights,
+                          int32_t order, int32_t nested, int64_t capacity, int64_t *ipix_out, double *phi_out,
+                          double *z_out, double *kappa_out, double *w_out, int64_t *n_selected);
+
+/*
  * Host-only helper of the ingest path (no device, no context): stable grouping of float64 columns by an integer key --
  * what the reference does per chunk with groupby(patch_ids, chunk) (catalog/catalog.py:293, utils/misc.py:40-51) and
  * groupby(bin_idx, chunk) (catalog/trees.py:413), i.e. np.argsort(kind="stable") + a gather per column, here as one

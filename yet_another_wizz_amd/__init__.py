@@ -22,7 +22,7 @@ from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
-                           crosscorrelate_scalar)
+                           crosscorrelate_scalar, crosscorrelate_scalar_map)
 from . import healpix, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -53,6 +53,7 @@ __all__ = [
     "compute_scalar_normalisation",
     "crosscorrelate",
     "crosscorrelate_scalar",
+    "crosscorrelate_scalar_map",
     "healpix",
     "randoms",
 ]

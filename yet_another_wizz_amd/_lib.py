@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "yawhip_random_box",
     "yawhip_random_healpix",
     "yawhip_healpix_map",
+    "yawhip_healpix_pixels",
     "yawhip_redshift_histogram",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
@@ -233,6 +234,8 @@ def load_library() -> ctypes.CDLL:
         ctypes.POINTER(ctypes.c_uint64), _i32p, ctypes.POINTER(ctypes.c_uint32),
     ]
     lib.yawhip_healpix_map.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _i64p, _dp]
+    lib.yawhip_healpix_pixels.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, _dp, _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                          _i64p, _dp, _dp, _dp, _dp, _i64p]
     lib.yawhip_redshift_histogram.argtypes = [
         _vp, ctypes.c_int64, _dp, _dp, ctypes.c_int32, _i64p, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
     ]
@@ -670,6 +673,31 @@ def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixel
         "yawhip_healpix_map",
     )
     return pix, out
+
+
+def healpix_pixels(ctx: Context, values, weights, order: int, nested: bool, capacity: int, *, chunksize: int = 0, outputs=None):
+    """Run ``yawhip_healpix_pixels``: the selected pixels of the map ``values`` (with the weight map ``weights``, or None) at
+    ``order`` -> ``(n_selected, ipix, phi, z, kappa, w)``, columns of ``capacity`` entries (``w`` None without ``weights``).
+    ``capacity`` is the number of selected pixels, counted by the caller; the library raises when it selects another number
+    and writes nothing beyond it. ``outputs``: the five arrays (int64, then four float64; the last may be None without
+    weights) to write to instead of new ones, each of at least ``capacity`` entries. The maps go to the library as they are."""
+    values, weights = _f64(values), _f64(weights)
+    capacity = int(capacity)
+    if outputs is None:
+        outputs = (np.empty(capacity, dtype=np.int64), *(np.empty(capacity, dtype=np.float64) for _ in range(3)),
+                   None if weights is None else np.empty(capacity, dtype=np.float64))
+    ipix, phi, z, kappa, w = outputs
+    for out, dtype in ((ipix, np.int64), (phi, np.float64), (z, np.float64), (kappa, np.float64), (w, np.float64)):
+        if out is not None and (out.dtype != dtype or not out.flags.c_contiguous or len(out) < capacity):
+            raise ValueError("healpix_pixels: an output is not a contiguous array of its type with 'capacity' entries")
+    n_selected = ctypes.c_int64(0)
+    _check(
+        load_library().yawhip_healpix_pixels(ctx._h, len(values), int(chunksize), _ptr(values, _dp), _ptr(weights, _dp), int(order),
+                                             int(bool(nested)), capacity, _ptr(ipix, _i64p), _ptr(phi, _dp), _ptr(z, _dp),
+                                             _ptr(kappa, _dp), _ptr(w, _dp), ctypes.byref(n_selected)),
+        "yawhip_healpix_pixels",
+    )
+    return int(n_selected.value), ipix, phi, z, kappa, w
 
 
 def redshift_histogram(ctx: Context, z, w, offsets, edges, closed_right: bool) -> np.ndarray:

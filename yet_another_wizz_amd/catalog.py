@@ -577,6 +577,27 @@ class Catalog(Mapping):
         new._random_route = route
         return new
 
+    @classmethod
+    def from_healpix_map(cls, cache_directory, values, *, weights=None, nested: bool = False, patch_centers=None,
+                         patch_num: int | None = None, overwrite: bool = False, probe_size: int = -1, chunksize: int | None = None):
+        """A full-sky HEALPix scalar map (a convergence map, a y-map) as a catalogue: one object per unmasked pixel, at the
+        pixel's centre, with the map's value as ``kappa`` and, with a weight / coverage map ``weights``, its weight. The
+        maps hold ``12 nside^2`` values, ``nside`` a power of two up to 8192, in RING order unless ``nested``; which pixels are
+        masked and the order of the objects are those of :func:`healpix.map_pixels <yet_another_wizz_amd.healpix.map_pixels>`.
+        Large maps are compacted on the GPU when there is one (the same values, in passes of ``chunksize`` nested pixels);
+        ``dec = arcsin(z)`` is taken on the host either way. The columns then go through ``from_arrays``: one of
+        ``patch_centers`` / ``patch_num`` is required, as for ``from_random``. The catalogue has no redshifts: it is the
+        scalar side of ``crosscorrelate_scalar_map``."""
+        from . import healpix
+
+        if patch_centers is None and patch_num is None:
+            raise ValueError("no patch method specified")
+        (_, ra, z, kappa, w), route = healpix._map_pixels(values, weights, nested, int(chunksize or 0))
+        new = cls.from_arrays(ra, np.arcsin(z), weights=w, kappa=kappa, patch_centers=patch_centers, patch_num=patch_num,
+                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size)
+        new._random_route = route
+        return new
+
     def healpix_map(self, nside: int, *, nested: bool = True, weighted: bool = True):
         """HEALPix map (float64[12 nside^2]) of the catalogue: the sum of weights per pixel if it has weights and
         ``weighted``, else the objects per pixel; NESTED numbers unless ``nested=False`` (RING). ``nside`` is a power of two

@@ -2394,7 +2394,7 @@ struct yawhip_ctx : CallBufs {
         std::vector<std::vector<int32_t>> parts;  // job indices per device
     } plan;
     yawsort::Workspace sort_ws;  // upload-side sorts
-    yawpix::Workspace pix_ws;    // yawhip_healpix_map
+    yawpix::Workspace pix_ws;    // yawhip_healpix_map, yawhip_healpix_pixels
     CallBufs parked[MAX_BATCH];  // the slots that are not active (the active one's entry is empty)
     int slot = 0;
     uint64_t opt_gen = 1;        // bumped by every accepted yawhip_ctx_set_option: plans and the partition are keyed on it
@@ -5190,6 +5190,41 @@ int yawhip_healpix_map(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const doub
     if (ctx->pix_ws.bytes() > ((size_t)1 << 28)) ctx->pix_ws.release();  // keep only small workspaces, as the sort workspace
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_healpix_map failed: %s", hipGetErrorString(e));
+    return YAWHIP_OK;
+}
+
+int yawhip_healpix_pixels(yawhip_ctx *ctx, int64_t n_pix, int64_t chunksize, const double *values, const double *weights, int32_t order,
+                          int32_t nested, int64_t capacity, int64_t *ipix_out, double *phi_out, double *z_out, double *kappa_out,
+                          double *w_out, int64_t *n_selected) {
+    static const char fn[] = "yawhip_healpix_pixels";
+    if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!values || !n_selected) return fail(YAWHIP_ERR_INVALID, "%s: NULL values or n_selected", fn);
+    *n_selected = 0;
+    if (order < 0 || order > yawpix::MAX_ORDER) return fail(YAWHIP_ERR_INVALID, "%s: order %d outside 0 .. %d", fn, order, yawpix::MAX_ORDER);
+    if (n_pix != (int64_t)12 << (2 * order))
+        return fail(YAWHIP_ERR_INVALID, "%s: n_pix %lld is not 12 * 4^order (order %d)", fn, (long long)n_pix, order);
+    if (nested != 0 && nested != 1) return fail(YAWHIP_ERR_INVALID, "%s: nested must be 0 or 1", fn);
+    if (chunksize < 0 || capacity < 0) return fail(YAWHIP_ERR_INVALID, "%s: chunksize < 0 or capacity < 0", fn);
+    if (capacity > 0 && (!ipix_out || !phi_out || !z_out || !kappa_out || (weights && !w_out)))
+        return fail(YAWHIP_ERR_INVALID, "%s: NULL output with capacity %lld", fn, (long long)capacity);
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawpix::PixelsCall c;
+    c.chunksize = std::min(chunksize > 0 ? chunksize : yawpix::DEFAULT_CHUNK, yawpix::MAX_CHUNK);
+    c.values = values, c.weights = weights;
+    c.order = order, c.nested = nested;
+    c.capacity = capacity;
+    c.ipix_out = ipix_out, c.phi_out = phi_out, c.z_out = z_out, c.kappa_out = kappa_out, c.w_out = w_out;
+    int64_t selected = 0;
+    bool overflow = false;
+    const hipError_t e = yawpix::healpix_pixels(ctx->pix_ws, ctx->stream, c, selected, overflow);
+    if (ctx->pix_ws.bytes() > ((size_t)1 << 28)) ctx->pix_ws.release();  // keep only small workspaces, as yawhip_healpix_map
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "%s failed: %s", fn, hipGetErrorString(e));
+    *n_selected = selected;
+    if (overflow)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the map selects more pixels than the capacity %lld of the outputs", fn, (long long)capacity);
+    if (selected != capacity)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the map selects %lld pixels, the outputs were sized for %lld", fn, (long long)selected,
+                    (long long)capacity);
     return YAWHIP_OK;
 }
 

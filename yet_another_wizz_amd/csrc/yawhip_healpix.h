@@ -1,5 +1,6 @@
 // Internal interface between yawhip.hip and yawhip_healpix.hip (HEALPix pixels and maps of a catalogue,
-// yawhip_healpix_map). Not part of the C ABI: yawhip.hip checks the arguments and owns the error reporting.
+// yawhip_healpix_map; the unmasked pixels of a scalar map as a catalogue's columns, yawhip_healpix_pixels). Not part of
+// the C ABI: yawhip.hip checks the arguments and owns the error reporting.
 #ifndef YAWHIP_HEALPIX_H
 #define YAWHIP_HEALPIX_H
 #include <hip/hip_runtime.h>
@@ -24,6 +25,13 @@ struct Workspace {
     size_t tmp_bytes = 0;
     double *map = nullptr;       // [map_cap] the map: uint64 counters while objects are counted, float64 at the end
     size_t map_cap = 0;
+    // yawhip_healpix_pixels
+    double *src = nullptr;       // [src_cap] the uploaded scalar map, then (with a weight map) the weight map behind it
+    size_t src_cap = 0;
+    double *sel = nullptr;       // [4][sel_cap]: phi, z, kappa, w of the selected pixels of one pass
+    int64_t *sel_pix = nullptr;  // [sel_cap] their pixel numbers
+    int64_t *wg_counts = nullptr;  // [2][sel_cap / 256 + 2]: selected pixels per workgroup of a pass, and their exclusive scan
+    size_t sel_cap = 0;
     size_t bytes() const;
     void release();
 };
@@ -39,6 +47,21 @@ struct MapCall {
 
 // Runs the call on the current device's `stream` and waits for it. Arguments are already checked.
 hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c);
+
+// One call of yawhip_healpix_pixels (see include/yawhip.h for the meaning of every field).
+struct PixelsCall {
+    int64_t chunksize = 0;                                  // nested pixels per pass, 1 .. MAX_CHUNK
+    const double *values = nullptr, *weights = nullptr;     // host, 12 * 4^order values each, weights may be null
+    int32_t order = 0, nested = 0;
+    int64_t capacity = 0;                                   // entries of every host output
+    int64_t *ipix_out = nullptr;                            // host outputs; w_out is null without weights
+    double *phi_out = nullptr, *z_out = nullptr, *kappa_out = nullptr, *w_out = nullptr;
+};
+
+// Runs the call on the current device's `stream` and waits for it. Arguments are already checked. `selected` is the
+// number of pixels copied to the outputs; `overflow` is set, and the call stops before it copies, when a pass would go
+// beyond `capacity`.
+hipError_t healpix_pixels(Workspace &ws, hipStream_t stream, const PixelsCall &c, int64_t &selected, bool &overflow);
 
 }  // namespace yawpix
 #endif

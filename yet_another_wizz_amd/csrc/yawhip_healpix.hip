@@ -16,6 +16,19 @@
 //     np.bincount(pix, w) bit for bit, run to run. A run is summed by one thread: a low-order weighted map of a huge
 //     catalogue is slow (order 0: twelve threads), and still exact.
 // The counters become float64 in place at the end (k_counts_to_f64) and the map goes to the host in one copy.
+//
+// yawhip_healpix_pixels goes the other way (healpix.map_pixels, Catalog.from_healpix_map): a full-sky scalar map, with an
+// optional weight map, becomes the columns of a catalogue. The maps are uploaded once; nested pixel numbers are walked in
+// passes of `chunksize`. Per pass:
+//   * k_select_count: one nested pixel q per thread -> its index in the map (q, or the ring arithmetic above), the
+//     selection rule of healpix.py (finite, not UNSEEN; weight finite and > 0), wave ballot + popcount, one count per
+//     workgroup.
+//   * rocPRIM's exclusive scan of the workgroup counts (one more entry holds the pass's total, read by the host).
+//   * k_select_write: the same predicate again; a selected pixel's place is the workgroup's base + the counts of the waves
+//     before its own + the ballot bits below its lane, so the output keeps ascending q. It stores the map's own pixel
+//     number, the centre (phi, z) in the float64 steps of randoms.pix2loc_nest, the value and the weight.
+// No atomics and no floating-point sums; every pixel and element index is 64-bit (an order-13 map is 6.4 GB). The selected
+// part of the pass is then copied to the host outputs at the running offset -- after the host has checked that it fits.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -46,21 +59,33 @@ __device__ __forceinline__ int64_t spread_bits(int64_t v) {
     return (int64_t)x;
 }
 
-// Ring-scheme number of the pixel (face, ix, iy) of `order`: the integer steps of randoms._ring_position / nest2ring.
-__device__ __forceinline__ int64_t ring_number(int order, int64_t face, int64_t ix, int64_t iy) {
+// Where the pixel (face, ix, iy) of `order` lies in the ring scheme: the integer steps of randoms._ring_position.
+struct RingPos {
+    int64_t jr, nr, kshift, jp;  // ring (1 .. 4 nside - 1 from the north), its pixels per quadrant, 1 on belt rings that start at
+    bool north, south;           // phi = 0, position in the ring (1 .. 4 nr); the caps
+};
+
+__device__ __forceinline__ RingPos ring_position(int order, int64_t face, int64_t ix, int64_t iy) {
     const int64_t nside = (int64_t)1 << order;
     const int64_t jrll = 2 + (face >> 2);                                          // 2 2 2 2 3 3 3 3 4 4 4 4
     const int64_t jpll = (int64_t)((0x753164207531ull >> (4 * (face & 15))) & 7);  // 1 3 5 7 0 2 4 6 1 3 5 7
-    const int64_t jr = (jrll << order) - ix - iy - 1;                              // ring, 1 .. 4 nside - 1 from the north
-    const bool north = jr < nside, south = jr > 3 * nside;
-    const int64_t nr = north ? jr : (south ? 4 * nside - jr : nside);
-    const int64_t kshift = (north || south) ? 0 : ((jr - nside) & 1);
-    int64_t jp = (jpll * nr + ix - iy + 1 + kshift) / 2;  // the sum is even
-    if (jp > 4 * nside) jp -= 4 * nside;
-    if (jp < 1) jp += 4 * nside;
-    if (north) return 2 * jr * (jr - 1) + jp - 1;
-    if (south) return 12 * nside * nside - 2 * nr * (nr + 1) + jp - 1;
-    return 2 * nside * (nside - 1) + (jr - nside) * (4 * nside) + jp - 1;
+    RingPos r;
+    r.jr = (jrll << order) - ix - iy - 1;
+    r.north = r.jr < nside, r.south = r.jr > 3 * nside;
+    r.nr = r.north ? r.jr : (r.south ? 4 * nside - r.jr : nside);
+    r.kshift = (r.north || r.south) ? 0 : ((r.jr - nside) & 1);
+    r.jp = (jpll * r.nr + ix - iy + 1 + r.kshift) / 2;  // the sum is even
+    if (r.jp > 4 * nside) r.jp -= 4 * nside;
+    if (r.jp < 1) r.jp += 4 * nside;
+    return r;
+}
+
+// Ring-scheme number of a pixel of `order` at `r`: the integer steps of randoms.nest2ring.
+__device__ __forceinline__ int64_t ring_number(int order, const RingPos &r) {
+    const int64_t nside = (int64_t)1 << order;
+    if (r.north) return 2 * r.jr * (r.jr - 1) + r.jp - 1;
+    if (r.south) return 12 * nside * nside - 2 * r.nr * (r.nr + 1) + r.jp - 1;
+    return 2 * nside * (nside - 1) + (r.jr - nside) * (4 * nside) + r.jp - 1;
 }
 
 // Pixel of `order` that holds (phi, z); -1 for a non-finite phi or z, or |z| > 1. The float64 steps of healpix.py.
@@ -96,7 +121,7 @@ __device__ __forceinline__ int64_t loc2pix(int order, int nested, double phi, do
             face = ntt + 8, ix = jp, iy = jm;
         }
     }
-    if (!nested) return ring_number(order, face, ix, iy);
+    if (!nested) return ring_number(order, ring_position(order, face, ix, iy));
     return face * nside * nside + spread_bits(ix) + 2 * spread_bits(iy);
 }
 
@@ -130,6 +155,97 @@ __global__ __launch_bounds__(WG) void k_counts_to_f64(int64_t npix, double *map)
     if (i >= npix) return;
     const unsigned long long c = reinterpret_cast<const unsigned long long *>(map)[i];
     map[i] = (double)c;
+}
+
+// ---- yawhip_healpix_pixels ----
+constexpr double UNSEEN = -1.6375e30;  // healpy's sentinel of a pixel without data
+constexpr int WAVES = WG / 64;
+
+// every second bit of v (bits 0, 2, 4, ...), packed
+__device__ __forceinline__ int64_t even_bits(uint64_t v) {
+    v &= 0x5555555555555555ull;
+    v = (v | (v >> 1)) & 0x3333333333333333ull;
+    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
+    v = (v | (v >> 16)) & 0x00000000ffffffffull;
+    return (int64_t)v;
+}
+
+// The maps on the device and the nested pixels [q0, q_end) of one pass.
+struct PixelPass {
+    const double *__restrict__ values;
+    const double *__restrict__ weights;  // may be null
+    int order, nested;
+    int64_t q0, q_end;
+};
+
+__device__ __forceinline__ RingPos ring_position_nest(int order, int64_t q) {
+    const uint64_t low = (uint64_t)q & (((uint64_t)1 << (2 * order)) - 1);
+    return ring_position(order, q >> (2 * order), even_bits(low), even_bits(low >> 1));
+}
+
+// The selection rule on entry `src` of the maps; v and wt are the values read (wt only with a weight map).
+__device__ __forceinline__ bool pixel_selected(const PixelPass &m, int64_t src, double &v, double &wt) {
+    v = m.values[src];
+    if (!(fabs(v) < __builtin_huge_val()) || v == UNSEEN) return false;  // a NaN fails the comparison
+    if (!m.weights) return true;
+    wt = m.weights[src];
+    return wt > 0.0 && wt < __builtin_huge_val();
+}
+
+// counts[workgroup] = selected pixels among the workgroup's WG nested pixels.
+__global__ __launch_bounds__(WG) void k_select_count(PixelPass m, int64_t *__restrict__ counts) {
+    __shared__ int s_cnt[WAVES];
+    const int64_t q = m.q0 + (int64_t)blockIdx.x * WG + threadIdx.x;
+    bool keep = false;
+    if (q < m.q_end) {
+        const int64_t src = m.nested ? q : ring_number(m.order, ring_position_nest(m.order, q));
+        double v, wt;
+        keep = pixel_selected(m, src, v, wt);
+    }
+    const unsigned long long mask = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < WAVES; ++w) total += s_cnt[w];
+        counts[blockIdx.x] = total;
+    }
+}
+
+// base[workgroup] = selected pixels of the pass before the workgroup's. Nothing is stored at or beyond `cap`.
+__global__ __launch_bounds__(WG) void k_select_write(PixelPass m, double fact1, double fact2, const int64_t *__restrict__ base, int64_t cap,
+                                                     int64_t *__restrict__ ipix, double *__restrict__ phi, double *__restrict__ z,
+                                                     double *__restrict__ kappa, double *__restrict__ w) {
+    __shared__ int s_cnt[WAVES];
+    const int64_t q = m.q0 + (int64_t)blockIdx.x * WG + threadIdx.x;
+    const int64_t nside = (int64_t)1 << m.order;
+    bool keep = false;
+    int64_t src = 0;
+    double v = 0.0, wt = 0.0;
+    RingPos r{};
+    if (q < m.q_end) {
+        r = ring_position_nest(m.order, q);
+        src = m.nested ? q : ring_number(m.order, r);
+        keep = pixel_selected(m, src, v, wt);
+    }
+    const unsigned long long mask = __ballot(keep);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    if (!keep) return;
+    int64_t at = base[blockIdx.x] + __popcll(mask & (((unsigned long long)1 << lane) - 1));
+    for (int k = 0; k < wave; ++k) at += s_cnt[k];
+    if (at >= cap) return;  // (cannot happen: the counts come from the same predicate on the same maps)
+    // the float64 steps of randoms.pix2loc_nest, each rounded on its own
+    const double nrf = (double)r.nr;
+    const double tmp = nrf * nrf * fact2;
+    ipix[at] = src;
+    z[at] = r.north ? 1.0 - tmp : (r.south ? tmp - 1.0 : (double)(2 * nside - r.jr) * fact1);
+    phi[at] = ((double)r.jp - (double)(r.kshift + 1) * 0.5) * (HALFPI / nrf);
+    kappa[at] = v;
+    if (w) w[at] = wt;
 }
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + WG - 1) / WG); }
@@ -172,11 +288,32 @@ hipError_t reserve_tmp(Workspace &ws, size_t bytes) {
     return e;
 }
 
+// Buffers of yawhip_healpix_pixels: the uploaded maps (`src_count` values) and the outputs of a pass of `chunk` pixels.
+hipError_t reserve_pixels(Workspace &ws, size_t src_count, size_t chunk) {
+    hipError_t e = hipSuccess;
+    if (src_count > ws.src_cap) {
+        ws.src_cap = 0;
+        e = regrow(ws.src, src_count);
+        if (e != hipSuccess) return e;
+        ws.src_cap = src_count;
+    }
+    if (chunk > ws.sel_cap) {
+        ws.sel_cap = 0;
+        e = regrow(ws.sel, 4 * chunk);
+        if (e == hipSuccess) e = regrow(ws.sel_pix, chunk);
+        if (e == hipSuccess) e = regrow(ws.wg_counts, 2 * (chunk / WG + 2));
+        if (e != hipSuccess) return e;
+        ws.sel_cap = chunk;
+    }
+    return e;
+}
+
 }  // namespace
 
 size_t Workspace::bytes() const {
     return chunk_cap * (3 * sizeof(double) + sizeof(int64_t) + (sort_bufs ? 2 * sizeof(uint32_t) + sizeof(double) : 0)) + tmp_bytes +
-           map_cap * sizeof(double);
+           map_cap * sizeof(double) + src_cap * sizeof(double) +
+           (sel_cap ? sel_cap * (4 * sizeof(double) + sizeof(int64_t)) + 2 * (sel_cap / WG + 2) * sizeof(int64_t) : 0);
 }
 
 void Workspace::release() {
@@ -186,6 +323,10 @@ void Workspace::release() {
     if (w_sorted) (void)hipFree(w_sorted);
     if (tmp) (void)hipFree(tmp);
     if (map) (void)hipFree(map);
+    if (src) (void)hipFree(src);
+    if (sel) (void)hipFree(sel);
+    if (sel_pix) (void)hipFree(sel_pix);
+    if (wg_counts) (void)hipFree(wg_counts);
     *this = Workspace{};
 }
 
@@ -230,6 +371,57 @@ hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c) {
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(c.map_out, ws.map, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // nothing of this call is left in flight
+    else (void)hipStreamSynchronize(stream);
+    return e;
+}
+
+hipError_t healpix_pixels(Workspace &ws, hipStream_t stream, const PixelsCall &c, int64_t &selected, bool &overflow) {
+    selected = 0, overflow = false;
+    const int64_t npix = (int64_t)12 << (2 * c.order);
+    const int64_t chunk = std::min(c.chunksize, npix);
+    hipError_t e = reserve_pixels(ws, (size_t)npix * (c.weights ? 2 : 1), (size_t)chunk);
+    if (e != hipSuccess) return e;
+    double *d_values = ws.src, *d_weights = c.weights ? ws.src + npix : nullptr;
+    double *d_phi = ws.sel, *d_z = ws.sel + ws.sel_cap, *d_kappa = ws.sel + 2 * ws.sel_cap, *d_w = c.weights ? ws.sel + 3 * ws.sel_cap : nullptr;
+    int64_t *counts = ws.wg_counts, *base = ws.wg_counts + (ws.sel_cap / WG + 2);
+    const double fact2 = 4.0 / (double)npix;                              // as randoms.pix2loc_nest
+    const double fact1 = (double)((int64_t)2 << c.order) * fact2;
+    e = hipMemcpyAsync(d_values, c.values, (size_t)npix * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && c.weights) e = hipMemcpyAsync(d_weights, c.weights, (size_t)npix * sizeof(double), hipMemcpyHostToDevice, stream);
+    for (int64_t q0 = 0; q0 < npix && e == hipSuccess; q0 += chunk) {
+        const int64_t k = std::min(chunk, npix - q0);
+        const unsigned nb = grid_for(k);
+        const PixelPass pass{d_values, d_weights, (int)c.order, (int)c.nested, q0, q0 + k};
+        e = hipMemsetAsync(counts + nb, 0, sizeof(int64_t), stream);  // the entry whose scan is the pass's total
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(k_select_count, dim3(nb), dim3(WG), 0, stream, pass, counts);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        size_t bytes = 0;
+        e = rocprim::exclusive_scan(nullptr, bytes, counts, base, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), stream);
+        if (e == hipSuccess) e = reserve_tmp(ws, bytes);
+        if (e != hipSuccess) break;
+        bytes = ws.tmp_bytes;
+        e = rocprim::exclusive_scan(ws.tmp, bytes, counts, base, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), stream);
+        int64_t total = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, base + nb, sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess || total == 0) continue;
+        if (total < 0 || total > k || total > c.capacity - selected) {  // nothing of this pass is written
+            overflow = true;
+            break;
+        }
+        hipLaunchKernelGGL(k_select_write, dim3(nb), dim3(WG), 0, stream, pass, fact1, fact2, base, k, ws.sel_pix, d_phi, d_z, d_kappa, d_w);
+        e = hipGetLastError();
+        const size_t n8 = (size_t)total * sizeof(double);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.ipix_out + selected, ws.sel_pix, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.phi_out + selected, d_phi, n8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.z_out + selected, d_z, n8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.kappa_out + selected, d_kappa, n8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && d_w) e = hipMemcpyAsync(c.w_out + selected, d_w, n8, hipMemcpyDeviceToHost, stream);
+        selected += total;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);  // nothing of this call is left in flight
     else (void)hipStreamSynchronize(stream);

@@ -15,7 +15,7 @@ from . import _lib
 from .parallel import local_device_index, world
 
 __all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms", "draw_healpix_randoms",
-           "healpix_map", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
+           "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
 default_kernel = "auto"
@@ -272,6 +272,26 @@ def healpix_map(phi, z, weights, order: int, nested: bool, *, want_pixels: bool 
     except _lib.YawhipError:
         return None
     return _lib.healpix_map(ctx, phi, z, weights, order, nested, want_pixels=want_pixels, want_map=want_map, chunksize=chunksize)
+
+
+def healpix_pixels(values, weights, order: int, nested: bool, *, chunksize: int = 0):
+    """The unmasked pixels of the scalar map ``values`` (and its weight map, or None) compacted on the device
+    (``yawhip_healpix_pixels``): ``(ipix, phi, z, kappa, w)`` as ``healpix.map_pixels`` returns them, or ``None`` when no GPU /
+    library is available -- catalogue preparation, as :func:`healpix_map`, and ``healpix.map_pixels`` then computes the same
+    values with numpy. The number of selected pixels is counted here, on the host, and the outputs are sized by it; the
+    library raises if it selects another number. ValueError when every pixel is masked."""
+    from . import healpix
+
+    try:
+        if _lib.device_count() < 1:
+            return None
+        ctx = get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+    capacity = healpix.count_selected(values, weights)
+    if capacity == 0:
+        raise ValueError("every pixel is masked")
+    return _lib.healpix_pixels(ctx, values, weights, order, nested, capacity, chunksize=chunksize)[1:]
 
 
 def redshift_histogram(z, w, offsets, edges, closed_right: bool) -> np.ndarray:

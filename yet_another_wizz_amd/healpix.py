@@ -24,16 +24,27 @@ resolution is that of ``1 - |z|``, as for the generators.
 
 The plain-numpy route here is the oracle of the device route (``yawhip_healpix_map``, ``csrc/yawhip_healpix.hip``), which
 repeats it bit for bit and is taken from :data:`DEVICE_MAP_MIN` points on when there is a GPU.
+
+:func:`map_pixels` goes the other way, from a full-sky scalar map (a convergence map, a y-map) to the columns of a
+catalogue: the unmasked pixels in ascending nested number, their centres (``randoms.pix2loc_nest``), values and weights
+(DESIGN.md section 13); its device route is ``yawhip_healpix_pixels``, from :data:`DEVICE_PIXELS_MIN` pixels on.
+:func:`map_values` samples a map at positions.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
-from .randoms import MAX_MAP_ORDER, nest2ring
+from .randoms import MAX_MAP_ORDER, nest2ring, pix2loc_nest
 
-__all__ = ["ang2pix", "healpix_map", "nside2order"]
+__all__ = ["ang2pix", "healpix_map", "map_pixels", "map_values", "nside2order", "UNSEEN"]
 
 DEVICE_MAP_MIN = 200_000  # points from which the device route is taken: catalog.DEVICE_ASSIGN_MIN until measured (DESIGN.md 12)
+# pixels of a map from which map_pixels takes the device route: nside 64, the smallest map measured, where the device route
+# already took a fifth of the numpy route's time; the break-even lies below and has not been located (DESIGN.md 13)
+DEVICE_PIXELS_MIN = 49_152
+UNSEEN = -1.6375e30  # healpy's sentinel of a pixel without data
 _TWOPI = 2.0 * np.pi
 _HALFPI = np.pi / 2
 _TWOTHIRD = 2.0 / 3.0
@@ -146,3 +157,98 @@ def healpix_map(order: int, phi, z, weights=None, *, nested: bool = True):
         return done[1]
     npix = 12 << (2 * order)
     return np.bincount(_host_pixels(order, phi, z, nested), weights, minlength=npix).astype(np.float64, copy=False)
+
+
+# ---- from a map to a catalogue's columns ----
+def _checked_map(values, weights):
+    """``(order, values, weights)`` of a full-sky map and its optional weight map as contiguous float64; the checks of
+    ``HealPixRandoms`` without its sign rule."""
+    values = np.asarray(values)
+    if values.ndim != 1:
+        raise ValueError("pixel values must be a one-dimensional map")
+    nside = math.isqrt(len(values) // 12)
+    if 12 * nside * nside != len(values) or nside < 1 or nside & (nside - 1):
+        raise ValueError(f"{len(values)} pixel values are no HEALPix map: not 12 nside^2 with nside a power of two")
+    order = nside.bit_length() - 1
+    if order > MAX_MAP_ORDER:
+        raise ValueError(f"maps above order {MAX_MAP_ORDER} (nside {1 << MAX_MAP_ORDER}) are not supported: the map alone "
+                         "is more than 6 GB")
+    values = np.ascontiguousarray(values, dtype=np.float64)  # (after the checks: no copy of what is no map)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != values.shape:
+            raise ValueError(f"a map of {len(values)} pixels but a weight map of shape {weights.shape}")
+    return order, values, weights
+
+
+def _selected(v, wt):
+    """The selection rule on map values ``v`` and their weights ``wt`` (or None) -> bool mask."""
+    keep = np.isfinite(v) & (v != UNSEEN)
+    if wt is not None:
+        keep &= np.isfinite(wt) & (wt > 0.0)
+    return keep
+
+
+def count_selected(values, weights=None) -> int:
+    """Number of pixels :func:`map_pixels` selects (the rule does not depend on the scheme), counted in blocks."""
+    total = 0
+    for lo in range(0, len(values), _HOST_STEP):
+        total += int(np.count_nonzero(_selected(values[lo : lo + _HOST_STEP], None if weights is None else weights[lo : lo + _HOST_STEP])))
+    return total
+
+
+def _host_map_pixels(order: int, values, weights, nested: bool):
+    parts = []
+    for lo in range(0, len(values), _HOST_STEP):  # blocks of nested pixels: no index temporary of the map's size
+        q = np.arange(lo, min(lo + _HOST_STEP, len(values)), dtype=np.int64)
+        src = q if nested else nest2ring(order, q)
+        v = values[src]
+        wt = None if weights is None else weights[src]
+        keep = _selected(v, wt)
+        if not keep.any():
+            continue
+        phi, z = pix2loc_nest(order, q[keep])
+        parts.append((src[keep], phi, z, v[keep], None if wt is None else wt[keep]))
+    if not parts:
+        raise ValueError("every pixel is masked")
+    columns = [np.concatenate(c) for c in list(zip(*parts))[:4]]
+    return (*columns, None if weights is None else np.concatenate([p[4] for p in parts]))
+
+
+def _map_pixels(values, weights, nested: bool, chunksize: int = 0):
+    """:func:`map_pixels` and the route it took, "device" or "host"."""
+    order, values, weights = _checked_map(values, weights)
+    if len(values) >= DEVICE_PIXELS_MIN:
+        from . import engine
+
+        done = engine.healpix_pixels(values, weights, order, nested, chunksize=chunksize)
+        if done is not None:
+            return done, "device"
+    return _host_map_pixels(order, values, weights, bool(nested)), "host"
+
+
+def map_pixels(values, weights=None, *, nested: bool = False, chunksize: int = 0):
+    """The unmasked pixels of a full-sky scalar map as columns: ``(ipix, phi, z, kappa, w)``.
+
+    ``values`` is a float64 map of ``12 nside^2`` entries, ``nside`` a power of two up to 8192, in RING order unless
+    ``nested``; ``weights`` is None or a weight / coverage map of the same length and scheme. A pixel is selected when its
+    value is finite and not :data:`UNSEEN` (healpy's -1.6375e30) and, with ``weights``, its weight is finite and > 0:
+    ``-0.0``, denormals and negative values are data; NaN, +-inf, ``UNSEEN`` and a weight that is 0, negative, NaN or inf
+    mask a pixel. The selected pixels come in ascending NESTED number for either scheme: ``ipix`` (int64) is the pixel
+    number in the map's own scheme (``values[ipix]`` is ``kappa``), ``(phi, z)`` = (ra in radian, sin dec) the pixel centre
+    (``randoms.pix2loc_nest``), ``kappa`` the value and ``w`` the weight (None without ``weights``). ValueError for an input
+    that is no such map, a weight map of another length, or when every pixel is masked.
+
+    Maps of at least :data:`DEVICE_PIXELS_MIN` pixels are compacted on the GPU when there is one (``yawhip_healpix_pixels``
+    in passes of ``chunksize`` nested pixels, 0: the library's default), the same values bit for bit."""
+    return _map_pixels(values, weights, nested, chunksize)[0]
+
+
+def map_values(order: int, phi, z, values, *, nested: bool = True):
+    """The map ``values`` (``12 * 4^order`` entries, NESTED unless ``nested=False``) sampled at the points ``(phi, z)``:
+    ``values[ang2pix(order, phi, z, nested=nested)]`` -- a kappa column for a galaxy sample, weights from a completeness
+    map. Arguments and errors as for :func:`ang2pix`; ValueError for a map of another length."""
+    values = np.asarray(values)
+    if values.ndim != 1 or not 0 <= int(order) <= MAX_MAP_ORDER or len(values) != 12 << (2 * int(order)):
+        raise ValueError(f"a map of order {order} has 12 * 4^order entries (order 0 .. {MAX_MAP_ORDER}), got shape {values.shape}")
+    return values[ang2pix(order, phi, z, nested=nested)]

@@ -24,7 +24,8 @@ from .corrfunc import CorrFunc, ScalarCorrFunc
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
-__all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "compute_scalar_normalisation",
+__all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
+           "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -639,4 +640,37 @@ def crosscorrelate_scalar(config, reference: Catalog, unknown: Catalog, *, unk_r
     else:
         DD = links.count_scalar_pairs(reference, unknown, mode="kn", count_type_info="DD", **kwargs)
         DR = [compute_scalar_normalisation(reference, config.binning.binning)] * len(DD)
+    return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]
+
+
+def crosscorrelate_scalar_map(config, reference: Catalog, scalar_map: Catalog, *, ref_rand: Catalog | None = None,
+                              progress: bool = False, max_workers: int | None = None) -> list:
+    """Angular cross-correlation amplitude between redshift slices of ``reference`` and a scalar field WITHOUT redshifts,
+    typically a map (``Catalog.from_healpix_map``): the "nk" DD count of ``reference`` against ``scalar_map``, minus the same
+    count of ``ref_rand`` against the map when it is given, else minus the map's mean field per patch
+    (``compute_scalar_normalisation``) -> ``[ScalarCorrFunc]``, one per scale.
+
+    This driver has no counterpart in the reference. The reference's ``crosscorrelate_scalar`` takes the scalar field from
+    the catalogue that carries the redshifts ("kn": the field is binned with its own objects); a map has no redshifts, so
+    it can only be the unbinned side of the count, and the count that fits, "nk", is one the reference's drivers never
+    issue. The pieces are the reference's all the same: the "nk" mode of its pair counts, ``NormalisedScalarCounts`` and
+    ``ScalarCorrFunc``."""
+    _require_distinct(reference, scalar_map, ref_rand)
+    count_dr = ref_rand is not None
+    edges, closed = config.binning.edges, config.binning.closed
+    randoms = []
+    _log_info("building reference data trees")
+    reference.build_trees(edges, closed=closed)
+    scalar_map.build_trees(None)
+    if count_dr:
+        ref_rand.build_trees(edges, closed=closed)
+        randoms.append(ref_rand)
+    _log_info("computing cross-correlation with DD" + (", DR" if count_dr else ""))
+    links = PatchLinkage.from_catalogs(config, reference, scalar_map, *randoms)
+    kwargs = dict(progress=progress, max_workers=max_workers)
+    if count_dr:  # DD (nk), DD (nn), DR (nk), DR (nn) in ONE submission
+        DD, DR = links._count_scalar_batch([((reference, scalar_map), "DD"), ((ref_rand, scalar_map), "DR")], "nk", **kwargs)
+    else:
+        DD = links.count_scalar_pairs(reference, scalar_map, mode="nk", count_type_info="DD", **kwargs)
+        DR = [compute_scalar_normalisation(scalar_map, config.binning.binning)] * len(DD)
     return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]
