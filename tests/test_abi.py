@@ -76,3 +76,29 @@ def test_dense_request_struct_matches_header():
             names += [n.strip(" *") for n in re.sub(r"^(const\s+)?\w+\s", "", decl).split(",")]
     assert names == [n for n, _ in _lib._DenseRequest._fields_]
     assert ctypes.sizeof(_lib._DenseRequest) == 48  # two pointers, two int32, three pointers
+
+
+def test_build_lists_cover_every_source_and_header(tmp_path, monkeypatch):
+    """Every csrc/*.hip is compiled (the kernel unit first), every header is watched for staleness, and source_sha16() sees
+    a change of one byte of the private header (hashed from a copy: the tree is not edited)."""
+    import glob
+    import shutil
+
+    from yet_another_wizz_amd import build
+
+    csrc = os.path.join(ROOT, "yet_another_wizz_amd", "csrc")
+    assert build.SOURCES[0] == build.KERNEL_UNIT == os.path.join(csrc, "yawhip.hip")
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    assert set(build.SOURCES) == set(glob.glob(os.path.join(csrc, "*.hip")))
+    headers = {os.path.join(ROOT, "include", "yawhip.h"), *glob.glob(os.path.join(csrc, "*.h")), *glob.glob(os.path.join(csrc, "*.inc"))}
+    assert headers <= set(build.HEADERS)
+    internal = os.path.join(csrc, "yawhip_internal.h")
+    assert internal in build.HEADERS
+    copy = str(tmp_path / "yawhip_internal.h")  # same base name: the hash covers names and contents
+    shutil.copy(internal, copy)
+    monkeypatch.setattr(build, "HEADERS", [copy if h == internal else h for h in build.HEADERS])
+    unchanged = build.source_sha16()
+    data = bytearray(open(copy, "rb").read())
+    data[len(data) // 2] ^= 1
+    open(copy, "wb").write(bytes(data))
+    assert build.source_sha16() != unchanged

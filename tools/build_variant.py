@@ -6,7 +6,9 @@
         ->  yet_another_wizz_amd/build/variants/libyawhip_diag1.so
     YAW_AMD_LIB=yet_another_wizz_amd/build/variants/libyawhip_diag1.so python bench.py ...
 
-Only the kernel translation unit is recompiled and linked with the product's other objects. With --patch FILE the unit is
+Only the kernel translation unit (build.KERNEL_UNIT, csrc/yawhip.hip) is recompiled and linked with the product's other
+objects -- unless the patch changes a file other than that unit and its yawhip_band32.inc (the private header, another
+unit): then every unit is compiled from the patched copy, so that all of them agree on the shared records. With --patch FILE the unit is
 compiled from a patched COPY of csrc/ and include/yawhip.h under variants/src_<tag>/: neither the working tree nor the
 in-tree product library is touched."""
 import argparse
@@ -37,11 +39,24 @@ if args.patch:
     os.makedirs(include)
     shutil.copy(os.path.join(build.INCLUDE, "yawhip.h"), include)
     subprocess.check_call(["patch", "-p1", "--no-backup-if-mismatch", "-d", src_dir, "-i", os.path.abspath(args.patch)])
-obj = os.path.join(out_dir, f"yawhip_{args.tag}.o")
+kernel_only = {os.path.basename(build.KERNEL_UNIT), "yawhip_band32.inc"}  # what only the kernel unit is compiled from
+everything = False
+if args.patch:
+    with open(args.patch) as f:
+        touched = {line.split()[1].split("/")[-1] for line in f if line.startswith("+++ ")}
+    everything = not touched <= kernel_only
 lib = os.path.join(out_dir, f"libyawhip_{args.tag}.so")
 hipcc = build.hipcc_path()
-subprocess.check_call([hipcc, *build.HIPCC_FLAGS, *flags, f"-I{include}", f"-I{csrc}", "-c",
-                       os.path.join(csrc, os.path.basename(build.SOURCES[0])), "-o", obj])
-others = [os.path.join(build.OBJ_DIR, os.path.basename(src) + ".o") for src in build.SOURCES[1:]]
-subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj, *others])
+objects = []
+for src in build.SOURCES:
+    name = os.path.basename(src)
+    is_kernels = src == build.KERNEL_UNIT
+    if not (is_kernels or everything):
+        objects.append(os.path.join(build.OBJ_DIR, name + ".o"))  # as the regular build made it
+        continue
+    obj = os.path.join(out_dir, f"{os.path.splitext(name)[0]}_{args.tag}.o")
+    subprocess.check_call([hipcc, *build.HIPCC_FLAGS, *(flags if is_kernels else []), f"-I{include}", f"-I{csrc}", "-c",
+                           os.path.join(csrc, name), "-o", obj])
+    objects.append(obj)
+subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objects])
 print(lib)

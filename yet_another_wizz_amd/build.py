@@ -6,6 +6,7 @@ The shared object is git-ignored but travels to the GPU box with the working-tre
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -14,12 +15,12 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-SOURCES = [os.path.join(CSRC, "yawhip.hip"), os.path.join(CSRC, "yawhip_sort.hip"), os.path.join(CSRC, "yawhip_random.hip"),
-           os.path.join(CSRC, "yawhip_hist.hip"), os.path.join(CSRC, "yawhip_healpix.hip")]
-HEADERS = [os.path.join(ROOT, "include", "yawhip.h"), os.path.join(CSRC, "yawhip_sort.h"), os.path.join(CSRC, "yawhip_random.h"),
-           os.path.join(CSRC, "yawhip_hist.h"), os.path.join(CSRC, "yawhip_healpix.h"),
-           os.path.join(CSRC, "yawhip_band32.inc")]
-SRC = SOURCES[0]
+KERNEL_UNIT = os.path.join(CSRC, "yawhip.hip")  # the count kernels: what experiment flags and variant builds recompile
+# every csrc/*.hip is a translation unit and every header can change one: a new file is never missing from the staleness
+# check or from source_sha16()
+SOURCES = [KERNEL_UNIT, *sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) if p != KERNEL_UNIT)]
+HEADERS = [os.path.join(ROOT, "include", "yawhip.h"),
+           *sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")))]
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG_DIR, "libyawhip.so")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
@@ -93,7 +94,7 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=()) ->
     for src in SOURCES:
         obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
         objects.append(obj)
-        is_kernels = src == SOURCES[0]
+        is_kernels = src == KERNEL_UNIT
         flags = list(extra_flags) if is_kernels else []  # experiment flags only concern the kernels
         fresh = os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_header)
         if fresh and not (is_kernels and (force or flags_changed)) and not (force == "all"):

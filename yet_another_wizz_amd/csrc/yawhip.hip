@@ -1,4 +1,10 @@
-// yawhip.hip -- MI355X (gfx950 / CDNA4) angular pair counting behind the C ABI of include/yawhip.h.
+// yawhip.hip -- MI355X (gfx950 / CDNA4) angular pair counting: the count kernels, the item builders and the count call
+// that plans and launches them (count_enqueue / count_finish / run_single, yawhip_count_pairs, yawhip_job_work), behind the C
+// ABI of include/yawhip.h. The rest of the library lives in units of its own, joined by csrc/yawhip_internal.h:
+//   yawhip_ingest.hip   catalogue upload, strip layouts and merged triple runs, yawhip_assign_patches (with their kernels);
+//   yawhip_dense.hip    the dense epilogue on top of the count call: yawhip_count_pairs_dense(_batch), ..._rows_device;
+//   yawhip_api.hip      contexts and options, error reporting, host-side grouping, and the wrappers of yawhip_hist.hip,
+//                       yawhip_healpix.hip and yawhip_random.hip.
 //
 // Replaces the per-job loop of PatchLinkage.count_pairs (reference src/yaw/correlation/measurements.py:344-364):
 // for each linked patch pair (p,q) and redshift bin k it counts, per fine angular bin e, the object
@@ -9,7 +15,7 @@
 // Design (wave64, no MFMA -- K=3 distances are not a contraction and bit parity forbids replacing the
 // predicate by a dot-product form; DESIGN.md section 4 has the details and the measurements):
 //   * catalogues live in HBM as SoA float64 columns x,y,z,(w) in two library-private orders, both made on the
-//     device at upload (yawhip_sort.hip): (patch, z-bin, u) with a CSR offset table, u = the sort axis; and the
+//     device at upload (yawhip_ingest.hip, yawhip_sort.hip): (patch, z-bin, u) with a CSR offset table, u = the sort axis; and the
 //     strip layout (patch, strip, u) -- strips of a global grid along a second axis, all bins together, bin id
 //     per object -- whose runs can be paired across catalogues by grid index alone;
 //   * k_build_items / k_build_items_strips turn the job table into work items (lane tile of c2) x (window of a
@@ -27,7 +33,7 @@
 //     images of the columns, every lane walks only the band |du| <= r of its objects, classifies every entry in
 //     float32 against guard bands around the edges and decides the few inside a guard band with the exact FP64
 //     predicate on the float64 columns (results identical to an all-float64 evaluation). The streamed side is read
-//     from merged runs of three neighbouring strips (k_merge_triples) where such a window fits the stage;
+//     from merged runs of three neighbouring strips (k_merge_triples, yawhip_ingest.hip) where such a window fits the stage;
 //     k_count_band32_fine: the same for fine radial grids (separation weights); k_count_band: every entry in FP64.
 // Unweighted counts: uint32 LDS histograms -> 64-bit integer atomics. Weighted sums: per-item slabs (LDS float64
 // atomics private to one wave) reduced in a fixed two-level order -> bit-reproducible run to run. No floating
@@ -37,97 +43,36 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <numeric>
-#include <thread>
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
 #include <string>
-#include <system_error>
 #include <type_traits>
 #include <utility>
 #include <functional>
 #include <vector>
 
-#include "yawhip.h"
-#include "yawhip_random.h"
-#include "yawhip_healpix.h"
-#include "yawhip_hist.h"
-#include "yawhip_sort.h"
+#include "yawhip_internal.h"
+
+using namespace yawhip_detail;
 
 namespace {
-// YAWHIP_TRACE=1: wall-clock marks of a call's host side, printed to stderr when the call returns (diagnostics; two
-// clock reads per mark when off)
-struct Trace {
-    bool on = getenv("YAWHIP_TRACE") != nullptr;
-    int n = 0;
-    const char *name[32];
-    std::chrono::steady_clock::time_point at[32];
-    void mark(const char *what) {
-        if (on && n < 32) { name[n] = what; at[n++] = std::chrono::steady_clock::now(); }
-    }
-    void flush() {
-        if (on && n > 1) {
-            fprintf(stderr, "[yawhip trace]");
-            for (int i = 1; i < n; ++i)
-                fprintf(stderr, " %s +%.1f", name[i], std::chrono::duration<double, std::micro>(at[i] - at[i - 1]).count());
-            fprintf(stderr, " | total %.1f us\n", std::chrono::duration<double, std::micro>(at[n - 1] - at[0]).count());
-        }
-        n = 0;
-    }
-};
-thread_local Trace g_trace;
-
-
 constexpr int WG = 256;      // threads per workgroup = 4 waves of 64
 constexpr int STAGE = 256;   // streamed objects per LDS stage (one per thread)
-constexpr int MWG = 64;      // threads per workgroup of the lean kernel (k_count_merged)
-static_assert(MWG == 64, "the band kernels are single-wave workgroups: their lane tile is 64 * R objects");
 constexpr int MSTAGE = 64;   // stage of the merged path: smaller -> less LDS -> more workgroups per CU
 constexpr int MAX_EDGES = 512;
-constexpr int SEG_STRIPS_MIN_RUN = 16;  // mean objects per (patch, bin, strip) run of the lane side from which mode 3 is used
 constexpr int BAND_MIN_STREAM_RUN = 64;  // AUTO: objects per run of the streamed side (as the typical object sees it) from which the band kernel is used
 constexpr int64_t SYNC_GRID_MIN_ITEMS = 400000;  // potential items from which the count grid is sized exactly (one host sync)
 constexpr int MAX_STRIP_REACH = 12;  // strip pairing is used while sqrt(t_max) <= 12 grid spacings
 constexpr int COUNT_FLUSH_MASK = (1 << 13) - 1;  // k_count: stages between flushes of the 32-bit LDS counters (see there)
 constexpr int MERGED_FLUSH_MASK = (1 << 16) - 1; // k_count_merged: 256 lane objects x 64 streamed objects per stage
-constexpr int SPLIT_JOBS = 1;  // internal status of count_enqueue: nothing was enqueued, the caller must split the job list
 constexpr double PAD_COORD = 4.0;  // padded lanes sit >= 3 away from any unit vector: s >= 9 > max t = 4
-
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                        #expr, hipGetErrorString(e_), __FILE__, __LINE__);                         \
-    } while (0)
-
-struct CatView {
-    const double *x, *y, *z, *w;  // w may be null
-    const int64_t *off;           // [P*nb+1]
-    int nb;
-    const double *key;            // the column the segments are sorted by (x, y or z)
-    int axis;                     // 0, 1, 2
-};
 
 struct alignas(16) Obj {  // one streamed object in LDS: two 16-byte broadcast reads
     double x, y, z, w;
@@ -141,7 +86,6 @@ struct alignas(16) ObjF {  // its float32 image for the pre-filter: one 16-byte 
 // a mul + 2 fma evaluation (u = 2^-24); 8 u leaves room for |a|^2 deviating from 1 by < 1e-9 and for
 // the rounding of the threshold itself.
 constexpr double FILTER_GUARD = 8.0 * 5.9604644775390625e-8;
-constexpr double UNIT_NORM_TOL = 1e-9;
 
 // ------------------------------------------------------------------------------------------------
 // Spherical caps (strip grid in latitude, trimmed u-bands; DESIGN.md sections 3 and 4).
@@ -184,162 +128,13 @@ __device__ __forceinline__ float cap_hi32(float u, float c, float s) {
     return uh >= c - CAP32_CLIP ? 1.0f + CAP32_MARGIN : fmaf(uh, c, sqrtf(fmaxf(fmaf(-uh, uh, 1.0f), 0.0f)) * s) + CAP32_MARGIN;
 }
 
-constexpr int MAX_WIN = 3;  // windows (partner runs of c1) one work item can carry
-struct alignas(16) Item {  // one unit of work for a workgroup: a lane tile of c2 and up to MAX_WIN windows of c1
-    int64_t a0;    // first lane object (c2 side)
-    int32_t na;    // lane objects (<= 256*R, <= 64*R on the SWEEP / BAND paths)
-    int32_t slot;  // output slot: job * n_bins + bin, or the job itself on the strip path (bits 0..29);
-                   // bits 30..31: orientation = which of the catalogues' three strip layouts a0 / b0 index
-    int32_t pot;   // index among all potential items (slab index of weighted partial sums)
-    int32_t nwin;  // windows in use (>= 1 for a kept item)
-    int64_t b0[MAX_WIN];  // first streamed object of every window (c1 side)
-    int32_t nb[MAX_WIN];  // streamed objects of every window
-    int32_t pad_;
-};
-static_assert(sizeof(Item) == 64, "Item layout");
 constexpr int SLOT_MASK = 0x3fffffff;
 __host__ __device__ inline int item_slot(const Item &it) { return it.slot & SLOT_MASK; }
 __host__ __device__ inline int item_orient(const Item &it) { return (int)((unsigned)it.slot >> 30); }
 
-// One layout of one catalogue as the kernels see it. The count kernels and the strip builder receive a table of six:
-// [o] = layout of c1 for orientation o, [3 + o] = layout of c2 (plain layouts: entry 0 / 3 only).
-// Orientation o = the sort axis u of the layout (0 = x, 1 = y, 2 = z); strips are cut along v = (o + 2) % 3 and the
-// third axis w = (o + 1) % 3 is the one the projection drops: a job uses the orientation whose w points towards its
-// two patches, where the (u, v) projection of the sphere is least compressed.
-// (pointers carry the global address space: loaded from a table the compiler could not tell, and would use flat loads)
-typedef const __attribute__((address_space(1))) double *gf64p;
-typedef const __attribute__((address_space(1))) int32_t *gi32p;
-typedef const __attribute__((address_space(1))) int64_t *gi64p;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) float *gf32p;
-struct DevTab {
-    gf64p x, y, z, w;          // columns; w may be null
-    gi32p k;                   // bin id per object (merged cross-correlation layouts), else null
-    gi64p off;                 // run offsets [V+1] (strip layouts) or segment offsets
-    gi64p vbase, slo, tiles;   // strip layouts: first run of a group, its grid index, lane-tile prefix over runs
-    const struct TileRec *tile_rec;  // strip layouts: first object, length and run of every lane tile
-    const struct RunGrid *grid;      // strip layouts: per-run index along the sort axis (item builder)
-    gf32p qx, qy, qz;          // strip layouts: float32 images of the columns (k_count_band32)
-    gi32p idx;                 // merged triple runs (streamed side): index of an entry in the layout's own order, else null
-    gi32p pos3;                // lane side of a self count on merged triple runs: place of an object in its own strip's triple, else null
-    int32_t axis;              // sort axis inside a run / segment
-    int32_t pad_;
-};
-__device__ __forceinline__ gf64p tab_key(const DevTab &t) { return t.axis == 0 ? t.x : (t.axis == 1 ? t.y : t.z); }
-
-// Tables of the strip item builder. Every thread of the builder walks a chain of dependent loads and the chain's length
-// is the kernel's run time (0.06 of the 0.55 ms of a headline call), so what the host or the layout build can precompute
-// travels as one record per job, per lane tile and per run instead of being looked up table by table.
-struct TileRec {   // per lane tile of a layout (one table per tile size)
-    int64_t a0;    // first object
-    int32_t na;    // objects (<= tile)
-    int32_t run;   // run the tile belongs to
-};
-struct JobRec {    // per job of a call
-    int64_t t_lo;      // first lane tile of the job (absolute index into the lane side's tile table)
-    int64_t k_off;     // strip of the streamed group facing lane run r2 under neighbour offset d: r2 + k_off + d
-    int64_t vbase1;    // first run of the streamed group
-    int32_t n_strips1; // runs of the streamed group
-    int32_t o;         // orientation: which pair of layouts the job runs on
-};
-// Per-run index along the sort axis: the key range [first, last] of a run is cut into RUN_GRID cells by
-// cell(key) = clamp(floor((key - first) * inv), 0, RUN_GRID - 1), and g[c] = number of entries whose cell is < c
-// (g[0] = 0, g[RUN_GRID] = run length). cell() is monotone in the key and evaluated by the same instructions when the
-// table is built and when it is queried, so for any w the first entry with key >= w and the first with key > w both lie in
-// [g[cell(w)], g[cell(w) + 1]] -- exactly, whatever the rounding of the product: the bisection over a run of 900 entries
-// (ten dependent loads) becomes one table look-up and four steps.
-constexpr int RUN_GRID = 64;
 constexpr int BUILD_BISECT = 32;  // most bisection steps of the strip builder inside a grid cell: as many as a 32-bit range can take
-struct RunGrid {
-    double inv;                  // RUN_GRID / (last - first), 0 for a run with one distinct key
-    uint32_t g[RUN_GRID + 2];    // + 1 pad: 8-byte multiple
-};
-__device__ __forceinline__ int run_cell(double key, double first, double inv) {
-    const double f = (key - first) * inv;
-    return f >= (double)RUN_GRID ? RUN_GRID - 1 : (f >= 1.0 ? (int)f : 0);
-}
-// one thread per (run, cell boundary): g[c] by bisection with the predicate cell(key) < c
-template <typename KeyT>
-__global__ __launch_bounds__(256) void k_run_grid(int64_t n_runs, const int64_t *__restrict__ off, const KeyT *__restrict__ key,
-                                                  RunGrid *__restrict__ grid) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = i / (RUN_GRID + 1);
-    const int c = (int)(i - r * (RUN_GRID + 1));
-    if (r >= n_runs) return;
-    const int64_t b0 = off[r], b1 = off[r + 1];
-    double inv = 0.0, first = 0.0;
-    if (b1 > b0) {
-        first = (double)key[b0];
-        const double span = (double)key[b1 - 1] - first;
-        inv = span > 0.0 ? (double)RUN_GRID / span : 0.0;
-        if (!(inv < 1e300)) inv = 0.0;  // a denormal span: one cell
-    }
-    int64_t l = b0, h = b1;
-    while (l < h) {
-        const int64_t m = (l + h) >> 1;
-        if (run_cell((double)key[m], first, inv) < c) l = m + 1; else h = m;
-    }
-    grid[r].g[c] = (uint32_t)(l - b0);
-    if (c == 0) { grid[r].inv = inv; grid[r].g[RUN_GRID + 1] = 0; }
-}
-
-// Merged triple runs of a strip layout (streamed side of the float32 band kernels). With a grid as wide as the largest
-// separation the partners of a lane tile in strip c are the strips c - 1, c, c + 1 of the other patch: three windows, three
-// band searches and three walks per item, each walk as long as the longest of 64 short bands. The triple run T(group, c)
-// holds the objects of those three strips MERGED along u (float32 images, weights, and the index of every entry in the
-// layout's own order for the exact re-evaluation): one window, one search, one walk whose trip count is the longest of 64
-// bands three times as long -- relatively more even. Every object is a member of three triples: 36 bytes of float32 images
-// per object more (+ 4 for the index, + 24 with weights). c runs over [first strip - 1, last strip + 1] of the group.
-// One thread per entry: its place in each of its three triples is its rank among the members (ties: lower run first) -- the
-// order (key, run, position in the run) is the SAME total order of objects in every triple two objects share, which is what
-// lets a self count take every unordered pair once: a lane object walks only the entries BEHIND its own place in the triple
-// of its strip (pos3), and the pair (a, b) is then met from exactly one side (k_count_band32_one, half bands).
-__global__ __launch_bounds__(256) void k_merge_triples(int64_t n, int64_t n_runs, const int64_t *__restrict__ off,
-                                                       const int32_t *__restrict__ run_group, const int64_t *__restrict__ vbase,
-                                                       const int64_t *__restrict__ off3, const double *__restrict__ key,
-                                                       const float *__restrict__ q, int64_t q_stride, const double *__restrict__ w,
-                                                       float *__restrict__ q3, int64_t q3_stride, double *__restrict__ w3,
-                                                       int32_t *__restrict__ idx3, int32_t *__restrict__ pos3) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int64_t lo = 0, hi = n_runs;  // run of the entry: the largest r with off[r] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    const int64_t r = lo;
-    const int64_t g = run_group[r], g_lo = vbase[g], g_hi = vbase[g + 1];
-    const double ki = key[i];
-    const float fx = q[i], fy = q[q_stride + i], fz = q[2 * q_stride + i];
-    const double wi = w ? w[i] : 0.0;
-    // entries of the group's runs r - 2 .. r + 2 in front of this one
-    int64_t before[5];
-#pragma unroll
-    for (int d = -2; d <= 2; ++d) {
-        const int64_t m = r + d;
-        int64_t cnt = 0;
-        if (d == 0) {
-            cnt = i - off[r];
-        } else if (m >= g_lo && m < g_hi) {
-            int64_t l = off[m], h = off[m + 1];
-            const int64_t base = l;
-            if (d < 0) { while (l < h) { const int64_t mid = (l + h) >> 1; if (key[mid] <= ki) l = mid + 1; else h = mid; } }
-            else       { while (l < h) { const int64_t mid = (l + h) >> 1; if (key[mid] < ki) l = mid + 1; else h = mid; } }
-            cnt = l - base;
-        }
-        before[d + 2] = cnt;
-    }
-#pragma unroll
-    for (int d = -1; d <= 1; ++d) {  // triple centred on run r + d: members r + d - 1, r + d, r + d + 1
-        const int64_t t = r + d + 1 + 2 * g;
-        const int64_t dst = off3[t] + before[d + 1] + before[d + 2] + before[d + 3];
-        q3[dst] = fx; q3[q3_stride + dst] = fy; q3[2 * q3_stride + dst] = fz;
-        idx3[dst] = (int32_t)i;
-        if (w3) w3[dst] = wi;
-        if (d == 0) pos3[i] = (int32_t)dst;  // where the object stands in the triple of its OWN strip (half bands of self counts)
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Item builder: one thread per potential item (slot, lane tile).
@@ -2122,58 +1917,6 @@ __global__ void k_reduce_slots(const double *__restrict__ chunk_sums, const int6
     out[idx] = acc;
 }
 
-// ndarray.sum() of values v(0) .. v(n - 1), in numpy's order (see numpy_sum on the host side of yawhip_count_pairs_dense)
-template <typename F>
-__device__ double numpy_sum_dev(F v, int lo, int n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += v(lo + i);
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = v(lo + j);
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += v(lo + i + j);
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += v(lo + i);
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return numpy_sum_dev(v, lo, n2) + numpy_sum_dev(v, lo + n2, n - n2);
-}
-
-// Per-scale recombination of the fine bins on the device (yawhip_count_pairs_dense): out[job][bin][scale] = sum over the
-// scale's fine bins of count (or weighted sum) x separation weight -- the same products and the same order of additions as
-// the host epilogue; what crosses PCIe afterwards is S values per (job, bin) instead of E - 1.
-__global__ void k_combine_scales(const unsigned long long *__restrict__ counts, const double *__restrict__ sums, int weighted,
-                                 int64_t n_jobs, int n_bins, int nf, int n_scales, const int32_t *__restrict__ slices,
-                                 const double *__restrict__ factors, double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_jobs * n_bins * n_scales) return;
-    const int sc = (int)(i % n_scales), k = (int)((i / n_scales) % n_bins);
-    const int64_t j = i / ((int64_t)n_scales * n_bins);
-    const int lo = slices[2 * (k * n_scales + sc)], hi = slices[2 * (k * n_scales + sc) + 1];
-    const int64_t base = (j * n_bins + k) * (int64_t)nf;
-    const double *wk = factors ? factors + (int64_t)k * nf : nullptr;
-    auto value = [&](int e) {
-        const double v = weighted ? sums[base + e] : (double)counts[base + e];
-        return wk ? v * wk[e] : v;
-    };
-    out[i] = hi > lo ? numpy_sum_dev(value, lo, hi - lo) : 0.0;
-}
-
-// rows of a call's result into their place in the full [rows][row] tensor (device-resident all-reduce of the process route)
-__global__ void k_scatter_rows(const double *__restrict__ in, const int32_t *__restrict__ row_index, int64_t row, int64_t n,
-                               double *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = i / row;
-    out[(int64_t)row_index[r] * row + (i - r * row)] = in[i];
-}
-
 __global__ void k_counts_to_double(const unsigned long long *__restrict__ in, double *__restrict__ out, int64_t n,
                                    unsigned long long *__restrict__ counters) {
     stamp_start(counters, CTR_T_COUNTED);  // the first kernel behind the count kernel
@@ -2225,269 +1968,6 @@ inline DevTab make_tab(const double *x, const double *y, const double *z, const 
                   (gi32p)nullptr, axis, 0};
 }
 
-template <typename T>
-struct DevBuf {  // grow-only device workspace
-    T *ptr = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        size_t want = n + n / 4 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&ptr), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-};
-
-// Small per-call tables travel in ONE host-to-device copy from a pinned staging buffer, and the results (counters, counts,
-// sums) come back in ONE copy into pinned memory: a dozen pageable copies of a few hundred bytes each cost more host
-// time than the kernels of a small call take.
-struct Arena {
-    unsigned char *h = nullptr, *d = nullptr;  // pinned host image and device buffer of the same size
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        release();
-        const size_t want = n + n / 4 + 4096;
-        // (coherent: k_call_tail writes a result block and its completion word while the host polls for it)
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&h), want, hipHostMallocPortable | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), want);
-        if (e == hipSuccess) cap = want; else release();
-        return e;
-    }
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr;
-        cap = 0;
-    }
-};
-inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-}  // namespace
-
-// Everything ONE count call in flight owns: its work items, partial sums, result block and timing events (the tables it
-// reads are its plan's, HostPlan). A context keeps MAX_BATCH of these; the active one is the base-class part of the context
-// (all the code below says ctx->d_items ...), the others are parked -- yawhip_count_pairs_dense_batch activates one per
-// request so that several counts of a measurement are on the stream at once (use_slot).
-struct CallBufs {
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evc0 = nullptr, evc1 = nullptr, ev_done = nullptr;
-    DevBuf<Item> d_items;
-    unsigned long long *d_ctr = nullptr, *d_counts = nullptr;  // counters and results: windows into `out`, set by every count call
-    double *d_sums = nullptr;
-    DevBuf<double> d_partials;
-    DevBuf<double> d_chunk_sums;
-    DevBuf<unsigned char> d_kept;   // weighted runs: 1 for potential items the builder kept
-    Arena out;   // results (device -> host)
-    // The [counters][counts] part of out.d is zero whenever no call of the slot is in flight: k_call_tail zeroes it behind its
-    // reads. `dirty` is set while that may not hold -- from the moment a call starts to enqueue until count_finish has seen it
-    // complete, so also after a call that failed or was abandoned on the way, after a builder-only call (job_work) and after a
-    // call whose tail left the counts in place (fetch_results = false) -- and the next call then fills the block itself.
-    // zero_upto: the bytes from the start of out.d known to be zero while !dirty (a call with a larger result block than the
-    // last one's has its counts where that one's sums were).
-    bool dirty = true;
-    size_t zero_upto = 0;
-    uint64_t seq = 0;  // sequence number of the slot's calls: what k_call_tail writes into the pinned block when it is done
-    Arena comb;  // yawhip_count_pairs_dense: recombination tables in, per-scale values out
-    hipError_t make_events() {
-        hipError_t e = hipSuccess;
-        for (hipEvent_t *ev : {&ev0, &ev1, &evc0, &evc1, &ev_done})
-            if (e == hipSuccess && !*ev) e = hipEventCreate(ev);
-        return e;
-    }
-    void release_all() {
-        d_items.release(); d_partials.release(); d_chunk_sums.release(); d_kept.release();
-        out.release(); comb.release();
-        for (hipEvent_t *ev : {&ev0, &ev1, &evc0, &evc1, &ev_done}) {
-            if (*ev) (void)hipEventDestroy(*ev);
-            *ev = nullptr;
-        }
-    }
-};
-constexpr int MAX_BATCH = 4;
-constexpr size_t MAX_PLANS = 16;  // plans kept per context (least recently used one goes)  // counts of one measurement on the stream at once (DD, DR, RD, RR)
-
-namespace {
-struct HostPlan;  // what a call derives from its inputs on the host, kept for the next call with the same inputs (below)
-
-// Everything a plan depends on: the catalogue pair (by upload id), the option set, sizes, kernel, the outputs asked for, job
-// list and thresholds (compared exactly) -- and, for the job partition of a multi-device call, the device count. A key made
-// from a call's arguments borrows their job list and thresholds; keep() gives it copies of its own before it is stored.
-struct CallKey {
-    uint64_t c1_uid = 0, c2_uid = 0, opt_gen = 0, hash = 0;
-    int32_t n_jobs = 0, n_bins = 0, n_edges = 0, kernel = 0, n_dev = 0;
-    bool want_counts = false, want_sums = false, for_work = false;
-    const int32_t *jobs = nullptr;
-    const double *t = nullptr;
-    std::vector<int32_t> own_jobs;
-    std::vector<double> own_t;
-
-    CallKey() = default;
-    CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-            int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
-            int32_t n_dev = 0);  // (below yawhip_catalog)
-    // (moves keep jobs / t valid: a vector's elements stay where they are; copies would not)
-    CallKey(CallKey &&) = default;
-    CallKey &operator=(CallKey &&) = default;
-    CallKey(const CallKey &) = delete;
-    CallKey &operator=(const CallKey &) = delete;
-
-    void keep() {
-        own_jobs.assign(jobs, jobs + 2 * (size_t)n_jobs);
-        own_t.assign(t, t + (size_t)n_bins * n_edges);
-        jobs = own_jobs.data();
-        t = own_t.data();
-    }
-    bool operator==(const CallKey &o) const {
-        return hash == o.hash && c1_uid == o.c1_uid && c2_uid == o.c2_uid && opt_gen == o.opt_gen && n_jobs == o.n_jobs &&
-               n_bins == o.n_bins && n_edges == o.n_edges && kernel == o.kernel && n_dev == o.n_dev && want_counts == o.want_counts &&
-               want_sums == o.want_sums && for_work == o.for_work &&
-               memcmp(jobs, o.jobs, sizeof(int32_t) * 2 * (size_t)n_jobs) == 0 &&
-               memcmp(t, o.t, sizeof(double) * (size_t)n_bins * n_edges) == 0;
-    }
-};
-}  // namespace
-
-struct yawhip_ctx : CallBufs {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int tile_r = 0;          // 0 = auto
-    int hist_copies_log2 = -1;  // band kernel: log2 of the copies of the LDS histogram (-1 = auto)
-    int band_batch_log2 = -1;   // band kernel: log2 of the consecutive items a workgroup takes per visit (-1 = auto)
-    int band_cap = 0;        // entries per LDS stage of the band kernel: 0 = auto, BCAP (192), BCAP_MID (288)
-    int seg_strips = 1;      // binned x binned counts of dense catalogues use the per-segment strip layouts
-    int seg_min_run = SEG_STRIPS_MIN_RUN;  // mean run length of the lane side from which binned x binned counts use it
-    int debug_no_hits = 0;   // diagnostics only: pre-filter threshold above 1 -> no pair survives (timing of the fast path)
-    int auto_orient = 1;     // every job runs on the strip layouts of the orientation that suits its patches (0: the catalogues' sort axis)
-    int64_t slab_budget = 1ll << 30;  // bytes of per-item partial sums (weighted calls) above which a job list is cut in two
-    int band_grid_div = 0;   // band kernel on strip items: workgroups = potential items / this (the kernel loops over the rest);
-                             // 0 = auto (make_plan: 8, 16 for per-bin items, 4 on clustered catalogues)
-    int flush_log2 = 17;     // band kernel: stages between flushes of the 32-bit LDS counters = 2^flush_log2
-    int spin_wait = 1;       // wait for a call's results by polling the stream for the first 2 ms, then block (0: block at once)
-    int item_segments = 1;   // strip builder -> float32 band kernels: the item list in eight segments, one per XCD (append_items)
-    int half_bands = 1;      // self counts on merged triple runs, one object per lane: diagonal jobs take every unordered pair once (x 2)
-    int triple_runs = 1;     // float32 band kernels stream merged triple runs (k_merge_triples) when the partner strips are c - 1, c, c + 1
-    int band_fp32 = 1;       // band kernel on strip layouts of unit vectors: float32 classification + exact float64 for the
-                             // guard bands (k_count_band32); 0: every entry in float64 (k_count_band)
-    double strip_width = 0.005;  // strip grid of newly uploaded catalogues (strip_grid units, ~17 arcmin); 0 = no strips
-    int strip_grid = 1;          // strip grid of newly uploaded catalogues: 1 = uniform in latitude (radians), 0 = linear in v (chord units)
-    int band_trim = 1;           // strip builder and float32 band kernels trim u-windows and bands to the reachable caps (sep_angle)
-    int default_kernel = YAWHIP_KERNEL_AUTO;
-    int hist_chunk_log2 = 23;    // yawhip_redshift_histogram: objects per upload = 2^hist_chunk_log2
-    int lds_limit = 160 * 1024;
-    int n_cu = 256;
-    DevBuf<unsigned long long> d_jobwork;
-    DevBuf<double> d_full;          // yawhip_count_pairs_rows_device: the full result tensor of a sharded count
-    DevBuf<int32_t> d_rowidx;
-    // A context made by yawhip_ctx_create_multi owns one further context per additional device: catalogues are
-    // replicated on all of them and yawhip_count_pairs splits its job list over them.
-    std::vector<yawhip_ctx *> peers;
-    struct Plan {  // job partition of the last multi-device call (a function of its inputs only)
-        CallKey key;
-        std::vector<std::vector<int32_t>> parts;  // job indices per device
-    } plan;
-    yawsort::Workspace sort_ws;  // upload-side sorts
-    yawpix::Workspace pix_ws;    // yawhip_healpix_map, yawhip_healpix_pixels
-    CallBufs parked[MAX_BATCH];  // the slots that are not active (the active one's entry is empty)
-    int slot = 0;
-    uint64_t opt_gen = 1;        // bumped by every accepted yawhip_ctx_set_option: plans and the partition are keyed on it
-    uint64_t plan_clock = 0;     // least-recently-used stamp of the plans
-    std::vector<HostPlan *> plans;
-};
-// Make slot i the active set of per-call buffers (its events are created on first use).
-inline hipError_t use_slot(yawhip_ctx *ctx, int i) {
-    if (i != ctx->slot) {
-        std::swap(static_cast<CallBufs &>(*ctx), ctx->parked[ctx->slot]);  // park the active one
-        std::swap(static_cast<CallBufs &>(*ctx), ctx->parked[i]);          // activate slot i
-        ctx->slot = i;
-    }
-    return ctx->make_events();
-}
-
-
-struct StripLayout {
-    bool built = false;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *w = nullptr;
-    int32_t *k = nullptr;             // bin id per object (patch-level layout of a binned catalogue)
-    float *q = nullptr;               // [3][q_stride] float32 images of x, y, z (k_count_band32)
-    int64_t q_stride = 0;
-    int64_t *off = nullptr;           // [V+1] offsets of the runs
-    std::vector<int64_t> h_off;       // same on the host
-    std::vector<int64_t> h_vbase;     // [G+1] first run of every group
-    std::vector<int64_t> h_slo;       // [G]   global strip index of a group's first run
-    std::vector<int64_t> h_tiles[3];  // [V+1] prefix of lane tiles over the runs, for tiles of MWG * {1, 2, 4} objects
-    int64_t *d_vbase = nullptr, *d_slo = nullptr, *d_tiles[3] = {nullptr, nullptr, nullptr};
-    TileRec *d_tile_rec[3] = {nullptr, nullptr, nullptr};  // [tiles] first object, length and run of every lane tile
-    RunGrid *d_grid = nullptr;        // [V+1] per-run index along the sort axis (item builder)
-    // merged triple runs (k_merge_triples), built when a float32 band kernel first streams this layout
-    bool triples = false;
-    float *q3 = nullptr;              // [3][q3_stride] float32 images in merged order (3 n entries)
-    int64_t q3_stride = 0;
-    double *w3 = nullptr;             // weights in merged order
-    int32_t *idx3 = nullptr;          // [3 n] entry -> index in the layout's own order
-    int32_t *pos3 = nullptr;          // [n] object -> its place in the triple run centred on its own strip
-    int64_t *off3 = nullptr;          // [V + 2 G + 1] offsets of the triple runs: group g has its strips + 2, first one = vbase[g] + 2 g
-    RunGrid *d_grid3 = nullptr;       // [V + 2 G + 1]
-    int64_t n_groups = 0;
-    int64_t device_bytes = 0;
-    double obj_run = 0.0;             // run length seen by the typical object (sum len^2 / sum len)
-    double same_bin = 0.0;            // fraction of neighbours in the layout's order that share their bin (binned patch-level layouts)
-    void release() {
-        for (void *ptr : {(void *)x, (void *)y, (void *)z, (void *)w, (void *)k, (void *)q, (void *)off, (void *)d_vbase, (void *)d_slo,
-                          (void *)d_tiles[0], (void *)d_tiles[1], (void *)d_tiles[2], (void *)d_tile_rec[0], (void *)d_tile_rec[1],
-                          (void *)d_tile_rec[2], (void *)d_grid, (void *)q3, (void *)w3, (void *)idx3, (void *)pos3, (void *)off3, (void *)d_grid3})
-            if (ptr) (void)hipFree(ptr);
-        q3 = nullptr; w3 = nullptr; idx3 = nullptr; pos3 = nullptr; off3 = nullptr; d_grid3 = nullptr; triples = false;
-        x = y = z = w = nullptr; k = nullptr; q = nullptr; off = d_vbase = d_slo = nullptr;
-        d_tiles[0] = d_tiles[1] = d_tiles[2] = nullptr;
-        d_tile_rec[0] = d_tile_rec[1] = d_tile_rec[2] = nullptr;
-        d_grid = nullptr;
-        built = false;
-    }
-};
-
-struct yawhip_catalog {
-    yawhip_ctx *ctx = nullptr;
-    uint64_t uid = 0;  // upload id, never reused (plans are keyed on it, not on the address)
-    int64_t n = 0;
-    int32_t n_patches = 0, nb = 1;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *w = nullptr;
-    int64_t *off = nullptr;
-    std::vector<int64_t> h_off;
-    int64_t device_bytes = 0;
-    bool unit_norm = true;  // every |a|^2 within UNIT_NORM_TOL of 1 (precondition of the FP32 pre-filter)
-    int axis = 2;           // coordinate the segments are sorted by (0 = x, 1 = y, 2 = z)
-    // strip layouts: the objects of every *group* cut into strips of a global grid along a second axis; inside a
-    // (group, strip) run sorted along the sort axis. Partner runs of two catalogues are those whose grid indices
-    // differ by at most sqrt(t_max) / spacing + 1.
-    //   strips: group = patch, all redshift bins together, bin id per object (cross-correlation counts);
-    //   seg:    group = (patch, bin) segment (binned x binned counts of dense catalogues; binned catalogues only).
-    // One layout per orientation o = sort axis u (strips along (o + 2) % 3), built when a job first needs it (the one of
-    // the catalogue's own sort axis at upload): see DevTab.
-    StripLayout strips[3], seg[3];
-    std::vector<yawhip_catalog *> replicas;  // copies on ctx->peers (multi-device contexts), same order
-    bool has_strips = false;          // strip layouts can be built (unit vectors, n > 0)
-    double strip_width = 0.0;         // grid spacing (strip_grid units); 0 = one run per patch
-    int strip_grid = 0;               // 1: grid index floor((latitude + pi/2) / spacing), 0: floor((v + 1) / spacing) (k_strip_index)
-    std::vector<double> h_box;        // [P][6] bounding box of every patch: min x, y, z, max x, y, z (empty patch: +4 / -4)
-};
-
-namespace {
-
-void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c);  // (defined with HostPlan)
-
-const double *key_of(const double *x, const double *y, const double *z, int axis) { return axis == 0 ? x : (axis == 1 ? y : z); }
-CatView view_of(const yawhip_catalog *c) {
-    return CatView{c->x, c->y, c->z, c->w, c->off, c->nb, key_of(c->x, c->y, c->z, c->axis), c->axis};
-}
-
 // One launch of a count kernel: its dynamic-LDS limit raised first where it needs more than 64 KiB.
 template <typename... Params, typename... Args>
 hipError_t launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
@@ -2520,865 +2000,11 @@ template <bool MERGED_, bool UNI_> struct Rows {
     static constexpr std::pair<bool, bool> value{MERGED_, UNI_};
 };
 
-// Nearest patch centre of every object (replaces scipy.cluster.vq.vq in assign_patch_centers, catalog.py:229-249):
-// squared distance accumulated x, y, z in that order with separately rounded products and sums, first minimum
-// wins -- the arithmetic of scipy's small-dimension vq loop, so ids are identical including exact ties.
-__global__ __launch_bounds__(256) void k_assign_patches(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
-                                                       const double *__restrict__ z, int n_centers,
-                                                       const double *__restrict__ centers, int32_t *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    double *c = reinterpret_cast<double *>(lds_raw);  // [n_centers][3]
-    for (int e = threadIdx.x; e < 3 * n_centers; e += blockDim.x) c[e] = centers[e];
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double px = x[i], py = y[i], pz = z[i];
-    double best = INFINITY;
-    int best_j = -1;
-    for (int j = 0; j < n_centers; ++j) {
-        const double dx = px - c[3 * j], dy = py - c[3 * j + 1], dz = pz - c[3 * j + 2];
-        const double xx = dx * dx;
-        const double yy = dy * dy;
-        const double zz = dz * dz;
-        const double sxy = xx + yy;
-        const double d = sxy + zz;
-        if (d < best) {
-            best = d;
-            best_j = j;
-        }
-    }
-    out[i] = best_j;
-}
-
-// ---- upload-side kernels: ordering of a catalogue on the device (the sorts themselves: yawhip_sort.hip) ----
-__global__ void k_gather_columns(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
-                                 const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
-                                 double *__restrict__ dx, double *__restrict__ dy, double *__restrict__ dz, double *__restrict__ dw) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = perm[i];
-    dx[i] = sx[src];
-    dy[i] = sy[src];
-    dz[i] = sz[src];
-    if (sw) dw[i] = sw[src];
-}
-
-// The gather of yawhip_catalog_upload_scalar: ONE permutation fills two catalogues -- the plain one (d*: weights sw, none
-// without) and its twin (k*: the same coordinates, weights kappa * w, kappa without sw). The product is one float64 multiply
-// rounded on its own (no sum follows it, and the build contracts nothing): the value numpy's kappa * w has on the host.
-__global__ void k_gather_columns_scalar(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
-                                        const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
-                                        const double *__restrict__ sk, double *__restrict__ dx, double *__restrict__ dy,
-                                        double *__restrict__ dz, double *__restrict__ dw, double *__restrict__ kx,
-                                        double *__restrict__ ky, double *__restrict__ kz, double *__restrict__ kw) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = perm[i];
-    const double vx = sx[src], vy = sy[src], vz = sz[src], kappa = sk[src];
-    dx[i] = vx;
-    dy[i] = vy;
-    dz[i] = vz;
-    kx[i] = vx;
-    ky[i] = vy;
-    kz[i] = vz;
-    if (sw) {
-        const double wv = sw[src];
-        dw[i] = wv;
-        kw[i] = kappa * wv;
-    } else {
-        kw[i] = kappa;
-    }
-}
-
-// Sum of the weight column over every (patch, bin) segment of a resident catalogue, one workgroup per segment: thread t adds
-// the objects lo + t, lo + t + 256, ... in that order, then the 256 partial sums are folded in halves through the LDS. The
-// order is a function of the segment alone: the same catalogue gives the same bits every time; no atomics.
-__global__ __launch_bounds__(256) void k_segment_weight_sums(const double *__restrict__ w, const int64_t *__restrict__ off,
-                                                            double *__restrict__ out) {
-    __shared__ double part[256];
-    const int64_t lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
-    double acc = 0.0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) acc += w[i];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = part[0];
-}
-
-// largest s in [0, n_seg) with off[s] <= i (off[0] = 0 <= i < off[n_seg])
-__device__ __forceinline__ int segment_of(const int64_t *__restrict__ off, int n_seg, int64_t i) {
-    int lo = 0, hi = n_seg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// bin id of every object of the strip layout = its (patch, bin) segment in the input order, modulo B
-__global__ void k_gather_bins(int64_t n, const uint32_t *__restrict__ perm, const int64_t *__restrict__ off, int64_t n_seg,
-                              int n_bins, int32_t *__restrict__ bins) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bins[i] = segment_of(off, (int)n_seg, (int64_t)perm[i]) % n_bins;
-}
-
-// float32 images of a strip layout's columns, rounded to nearest: [3][stride]
-__global__ void k_make_q(int64_t n, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-                         int64_t stride, float *__restrict__ q) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    q[i] = (float)x[i];
-    q[stride + i] = (float)y[i];
-    q[2 * stride + i] = (float)z[i];
-}
-
-// How often two neighbours of the (strip, u)-sorted order share their redshift bin: ~1/B when redshift and position are
-// unrelated, towards 1 when they are not -- then the lanes of a wave keep hitting the same histogram cells.
-__global__ void k_same_bin_neighbours(int64_t n, const int32_t *__restrict__ bins, unsigned long long *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool same = i + 1 < n && bins[i] == bins[i + 1];
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(same);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__popcll(m));
-}
-
-// grid index of every object (0 without strips) and the occupied range per patch: floor((v + 1) / width) (lat = 0), or
-// floor((latitude + pi/2) / width) with the latitude atan2(v, hypot(u, w)) of the object's direction (lat = 1, sep_angle)
-__global__ void k_strip_index(int64_t n, const double *__restrict__ v, const double *__restrict__ u, const double *__restrict__ w,
-                              double width, int lat, const int64_t *__restrict__ poff, int n_patches, int32_t *__restrict__ gidx,
-                              int32_t *__restrict__ lohi) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ok = i < n;
-    int32_t g = 0;
-    int p = -1;
-    if (ok) {
-        const double vi = v[i];
-        if (width > 0.0)
-            g = lat ? (int32_t)floor((atan2(vi, hypot(u[i], w[i])) + 1.5707963267948966) / width) : (int32_t)floor((vi + 1.0) / width);
-        gidx[i] = g;
-        p = segment_of(poff, n_patches, i);
-    }
-    // Objects of a patch are contiguous, so nearly every wave sits inside one patch: reduce there and issue one
-    // atomic pair per wave (one pair per object on 2P addresses cost 97 ms for 10 M objects).
-    const int p0 = __builtin_amdgcn_readfirstlane(p);
-    if (__builtin_amdgcn_ballot_w64(p != p0) == 0ull) {
-        if (p0 < 0) return;  // whole wave past the end
-        int32_t lo = g, hi = g;
-        for (int off = 32; off > 0; off >>= 1) {
-            lo = min(lo, __shfl_xor(lo, off, 64));
-            hi = max(hi, __shfl_xor(hi, off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            atomicMin(&lohi[2 * p0], lo);
-            atomicMax(&lohi[2 * p0 + 1], hi);
-        }
-    } else if (ok) {  // a wave across a patch boundary (or the ragged end)
-        atomicMin(&lohi[2 * p], g);
-        atomicMax(&lohi[2 * p + 1], g);
-    }
-}
-
-// run id of the object that is i-th in `order` (objects of a patch are contiguous in the input)
-__global__ void k_run_of(int64_t n, const uint32_t *__restrict__ order, const int32_t *__restrict__ gidx,
-                         const int64_t *__restrict__ poff, int n_patches, const int64_t *__restrict__ vbase,
-                         const int64_t *__restrict__ slo, uint32_t *__restrict__ run) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t src = order[i];
-    const int p = segment_of(poff, n_patches, (int64_t)src);
-    run[i] = (uint32_t)(vbase[p] + (int64_t)gidx[src] - slo[p]);
-}
-
-// moff[r] = first position of the (sorted) run column that holds a run >= r; moff[n_runs] = n
-__global__ void k_run_offsets(const uint32_t *__restrict__ run_sorted, int64_t n, int64_t n_runs, int64_t *__restrict__ moff) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n_runs) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)run_sorted[mid] < r) lo = mid + 1; else hi = mid;
-    }
-    moff[r] = lo;
-}
-
-// monotone map double -> uint64 (atomicMin / atomicMax on the images order like the doubles)
-__host__ __device__ inline unsigned long long sortable_of(double d) {
-    unsigned long long b;
-    memcpy(&b, &d, sizeof b);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-inline double double_of(unsigned long long s) {
-    const unsigned long long b = (s >> 63) ? (s & 0x7fffffffffffffffull) : ~s;
-    double d;
-    memcpy(&d, &b, sizeof d);
-    return d;
-}
-
-// Bounding box of every patch ([P][6]: min x, y, z, max x, y, z as sortable images) and, in box[6 P], the number of
-// waves that saw an object off the unit sphere. One atomic set per wave inside a patch (see k_strip_index).
-__global__ void k_patch_boxes(int64_t n, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-                              const int64_t *__restrict__ poff, int n_patches, unsigned long long *__restrict__ box) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ok = i < n;
-    double v[3] = {0.0, 0.0, 0.0};
-    int p = -1;
-    bool off_sphere = false;
-    if (ok) {
-        v[0] = x[i]; v[1] = y[i]; v[2] = z[i];
-        p = segment_of(poff, n_patches, i);
-        const double n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-        off_sphere = !(n2 > 1.0 - UNIT_NORM_TOL && n2 < 1.0 + UNIT_NORM_TOL);
-    }
-    if (__builtin_amdgcn_ballot_w64(off_sphere) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&box[(size_t)6 * n_patches], 1ull);
-    const int p0 = __builtin_amdgcn_readfirstlane(p);
-    if (__builtin_amdgcn_ballot_w64(p != p0) == 0ull) {
-        if (p0 < 0) return;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            unsigned long long lo = sortable_of(v[a]), hi = lo;
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long l2 = __shfl_xor(lo, off, 64), h2 = __shfl_xor(hi, off, 64);
-                lo = l2 < lo ? l2 : lo;
-                hi = h2 > hi ? h2 : hi;
-            }
-            if ((threadIdx.x & 63) == 0) {
-                atomicMin(&box[(size_t)6 * p0 + a], lo);
-                atomicMax(&box[(size_t)6 * p0 + 3 + a], hi);
-            }
-        }
-    } else if (ok) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            atomicMin(&box[(size_t)6 * p + a], sortable_of(v[a]));
-            atomicMax(&box[(size_t)6 * p + 3 + a], sortable_of(v[a]));
-        }
-    }
-}
-
 inline int64_t seg_len(const yawhip_catalog *c, int patch, int k) {
     const int kk = c->nb == 1 ? 0 : k;
     const int64_t i = (int64_t)patch * c->nb + kk;
     return c->h_off[i + 1] - c->h_off[i];
 }
-
-// Build one strip layout of a catalogue from its resident (patch, bin, u) copy: orientation o = sort axis inside a run,
-// strips of the global grid along (o + 2) % 3; seg = groups are the (patch, bin) segments instead of the patches.
-int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
-    StripLayout &L = seg ? c->seg[o] : c->strips[o];
-    if (L.built) return YAWHIP_OK;
-    const int64_t n = c->n, nseg = (int64_t)c->n_patches * c->nb;
-    const int n_groups = seg ? (int)nseg : c->n_patches;
-    const bool want_bins = !seg && c->nb > 1;
-    const double width = c->strip_width;
-    const int saxis = (o + 2) % 3;  // z -> y, y -> x, x -> z
-    std::vector<int64_t> h_poff((size_t)n_groups + 1);
-    for (int g = 0; g <= n_groups; ++g) h_poff[(size_t)g] = seg ? c->h_off[(size_t)g] : c->h_off[(size_t)g * c->nb];
-    const size_t col = (size_t)std::max<int64_t>(n, 1) * sizeof(double) + 16;  // + 16: the band kernel's 16-byte loads may touch the bytes behind the last element
-    uint32_t *perm = nullptr, *perm2 = nullptr, *run = nullptr, *run_sorted = nullptr;
-    int32_t *gidx = nullptr, *lohi = nullptr;
-    int64_t *poff = nullptr;
-    auto bail = [&](hipError_t err, const char *what) {
-        for (void *q : {(void *)perm, (void *)perm2, (void *)run, (void *)run_sorted, (void *)gidx, (void *)lohi, (void *)poff})
-            if (q) (void)hipFree(q);
-        if (err == hipSuccess) return (int)YAWHIP_OK;
-        L.release();
-        return fail(err == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "strip layout (%s) failed: %s", what,
-                    hipGetErrorString(err));
-    };
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<int32_t> h_lohi((size_t)2 * n_groups);
-    for (int g = 0; g < n_groups; ++g) { h_lohi[(size_t)2 * g] = INT32_MAX; h_lohi[(size_t)2 * g + 1] = INT32_MIN; }
-    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&poff), (size_t)(n_groups + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&lohi), (size_t)2 * n_groups * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&gidx), n1 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm2), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&run), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&run_sorted), n1 * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(poff, h_poff.data(), (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(lohi, h_lohi.data(), (size_t)2 * n_groups * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return bail(e, "strip tables");
-    const unsigned ngrid = (unsigned)((n1 + 255) / 256);
-    // grid index of every object, first / last occupied strip of every group
-    hipLaunchKernelGGL(k_strip_index, dim3(ngrid), dim3(256), 0, ctx->stream, n, key_of(c->x, c->y, c->z, saxis),
-                       key_of(c->x, c->y, c->z, (saxis + 1) % 3), key_of(c->x, c->y, c->z, (saxis + 2) % 3), width, c->strip_grid && !seg ? 1 : 0, poff,
-                       n_groups, gidx, lohi);
-    e = hipMemcpyAsync(h_lohi.data(), lohi, (size_t)2 * n_groups * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(e, "strip index");
-    std::vector<int64_t> vbase((size_t)n_groups + 1, 0), slo((size_t)n_groups, 0);
-    for (int g = 0; g < n_groups; ++g) {
-        const bool any = h_poff[(size_t)g + 1] > h_poff[(size_t)g];
-        slo[(size_t)g] = any ? h_lohi[(size_t)2 * g] : 0;
-        vbase[(size_t)g + 1] = vbase[(size_t)g] + (any ? (int64_t)h_lohi[(size_t)2 * g + 1] - h_lohi[(size_t)2 * g] + 1 : 0);
-    }
-    const int64_t n_runs = vbase[(size_t)n_groups];
-    if (n_runs >= (1ll << 31)) return bail(hipErrorInvalidValue, "too many strip runs");
-    int run_bits = 1;
-    while ((1ll << run_bits) < n_runs) ++run_bits;
-    e = hipMalloc(reinterpret_cast<void **>(&L.d_vbase), (size_t)(n_groups + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_slo), (size_t)std::max(n_groups, 1) * sizeof(int64_t));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(L.d_vbase, vbase.data(), (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(L.d_slo, slo.data(), (size_t)n_groups * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    // order along the sort axis inside every group, then group by run (unique keys (run, rank): no reliance on
-    // the stability of the sort)
-    if (e == hipSuccess) e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(c->x, c->y, c->z, o), poff, n_groups, perm);
-    if (e != hipSuccess) return bail(e, "group sort");
-    hipLaunchKernelGGL(k_run_of, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, gidx, poff, n_groups, L.d_vbase, L.d_slo, run);
-    e = yawsort::sort_runs(ctx->sort_ws, ctx->stream, n, run, perm, run_bits, perm2, run_sorted);
-    if (e != hipSuccess) return bail(e, "run sort");
-    e = hipMalloc(reinterpret_cast<void **>(&L.x), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.y), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.z), col);
-    if (e == hipSuccess && c->w) e = hipMalloc(reinterpret_cast<void **>(&L.w), col);
-    if (e == hipSuccess && want_bins) e = hipMalloc(reinterpret_cast<void **>(&L.k), n1 * sizeof(int32_t) + 16);
-    L.q_stride = (int64_t)((n1 + 3) & ~(size_t)3) + 8;  // a 16-byte load of the band kernel may run up to 12 bytes past a column
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.q), (size_t)3 * L.q_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.off), (size_t)(n_runs + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_grid), (size_t)(n_runs + 1) * sizeof(RunGrid));
-    if (e == hipSuccess) e = hipMemsetAsync(L.d_grid, 0, (size_t)(n_runs + 1) * sizeof(RunGrid), ctx->stream);  // [V]: read for groups without runs
-    if (e != hipSuccess) return bail(e, "strip layout");
-    hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm2, c->x, c->y, c->z, c->w, L.x, L.y, L.z, L.w);
-    if (want_bins)
-        hipLaunchKernelGGL(k_gather_bins, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm2, c->off, nseg, c->nb, L.k);
-    hipLaunchKernelGGL(k_make_q, dim3(ngrid), dim3(256), 0, ctx->stream, n, L.x, L.y, L.z, L.q_stride, L.q);
-    hipLaunchKernelGGL(k_run_offsets, dim3((unsigned)((n_runs + 1 + 255) / 256)), dim3(256), 0, ctx->stream, run_sorted, n, n_runs,
-                       L.off);
-    if (n_runs > 0)
-        hipLaunchKernelGGL(k_run_grid<double>, dim3((unsigned)((n_runs * (RUN_GRID + 1) + 255) / 256)), dim3(256), 0, ctx->stream, n_runs,
-                           L.off, o == 0 ? L.x : (o == 1 ? L.y : L.z), L.d_grid);
-    std::vector<int64_t> voff((size_t)n_runs + 1);
-    e = hipMemcpyAsync(voff.data(), L.off, (size_t)(n_runs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-    unsigned long long h_same = 0;
-    if (want_bins && n > 1) {  // `run` (sorted away by now) serves as the 8-byte result cell
-        unsigned long long *d_same = reinterpret_cast<unsigned long long *>(run);
-        if (e == hipSuccess) e = hipMemsetAsync(d_same, 0, sizeof(unsigned long long), ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_same_bin_neighbours, dim3(ngrid), dim3(256), 0, ctx->stream, n, L.k, d_same);
-            e = hipMemcpyAsync(&h_same, d_same, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(e, "run offsets");
-    L.same_bin = n > 1 ? (double)h_same / (double)(n - 1) : 0.0;
-    for (int64_t r = 0; r < n_runs; ++r)
-        if (voff[(size_t)r + 1] - voff[(size_t)r] >= (1ll << 32)) return bail(hipErrorInvalidValue, "a strip run of 2^32 objects or more");
-    // small per-run tables the item builder walks on the device
-    for (int ri = 0; ri < 3; ++ri) {
-        const int64_t tile = (int64_t)MWG << ri;
-        L.h_tiles[ri].assign((size_t)n_runs + 1, 0);
-        for (int64_t r = 0; r < n_runs; ++r)
-            L.h_tiles[ri][(size_t)r + 1] = L.h_tiles[ri][(size_t)r] + (voff[(size_t)r + 1] - voff[(size_t)r] + tile - 1) / tile;
-        {  // record of every tile: the item builder decodes a potential item with one load instead of a search over the
-           // prefix and a look-up of the run's offsets
-            const int64_t n_tiles = L.h_tiles[ri][(size_t)n_runs];
-            std::vector<TileRec> tile_rec((size_t)std::max<int64_t>(n_tiles, 1), TileRec{0, 0, 0});
-            for (int64_t r = 0; r < n_runs; ++r)
-                for (int64_t tl = L.h_tiles[ri][(size_t)r]; tl < L.h_tiles[ri][(size_t)r + 1]; ++tl) {
-                    const int64_t a0 = voff[(size_t)r] + (tl - L.h_tiles[ri][(size_t)r]) * tile;
-                    tile_rec[(size_t)tl] = TileRec{a0, (int32_t)std::min<int64_t>(tile, voff[(size_t)r + 1] - a0), (int32_t)r};
-                }
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_tile_rec[ri]), tile_rec.size() * sizeof(TileRec));
-            if (e == hipSuccess)
-                e = hipMemcpy(L.d_tile_rec[ri], tile_rec.data(), tile_rec.size() * sizeof(TileRec), hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_tiles[ri]), (size_t)(n_runs + 1) * sizeof(int64_t));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(L.d_tiles[ri], L.h_tiles[ri].data(), (size_t)(n_runs + 1) * sizeof(int64_t),
-                               hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(e, "tile tables");
-    {  // run length as the typical OBJECT sees it (sum of squares / sum): equals the mean for uniform data, far above it
-       // for clustered data, where most objects live in a few dense runs
-        double sq = 0.0;
-        for (int64_t r = 0; r < n_runs; ++r) {
-            const double len = (double)(voff[(size_t)r + 1] - voff[(size_t)r]);
-            sq += len * len;
-        }
-        L.obj_run = n > 0 ? sq / (double)n : 0.0;
-    }
-    L.h_off = std::move(voff);
-    L.h_vbase = std::move(vbase);
-    L.h_slo = std::move(slo);
-    L.n_groups = n_groups;
-    L.device_bytes = (int64_t)col * (c->w ? 4 : 3) + (want_bins ? n * (int64_t)sizeof(int32_t) : 0) + 3 * L.q_stride * (int64_t)sizeof(float) +
-                     (4 * (n_runs + 1) + 2 * (int64_t)n_groups + 1) * (int64_t)sizeof(int64_t) + (n_runs + 1) * (int64_t)sizeof(RunGrid) +
-                     (L.h_tiles[0][(size_t)n_runs] + L.h_tiles[1][(size_t)n_runs] + L.h_tiles[2][(size_t)n_runs]) * (int64_t)sizeof(TileRec);
-    c->device_bytes += L.device_bytes;
-    L.built = true;
-    return bail(hipSuccess, "");
-}
-
-// Merged triple runs of a built strip layout (see k_merge_triples); built once, on first use as the streamed side of a
-// float32 band kernel with partner strips c - 1, c, c + 1.
-int build_triples(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
-    StripLayout &L = seg ? c->seg[o] : c->strips[o];
-    if (!L.built) return fail(YAWHIP_ERR_INVALID, "build_triples: layout not built");
-    if (L.triples) return YAWHIP_OK;
-    const int64_t n = c->n, G = L.n_groups, V = L.h_vbase[(size_t)G], V3 = V + 2 * G;
-    if (3 * n >= (1ll << 31)) return fail(YAWHIP_ERR_INVALID, "build_triples: catalogue too large for 32-bit entry indices");
-    std::vector<int64_t> off3((size_t)V3 + 1, 0);
-    std::vector<int32_t> run_group((size_t)std::max<int64_t>(V, 1), 0);
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t lo = L.h_vbase[(size_t)g], hi = L.h_vbase[(size_t)g + 1];
-        for (int64_t r = lo; r < hi; ++r) run_group[(size_t)r] = (int32_t)g;
-        for (int64_t c_rel = 0; c_rel < hi - lo + 2; ++c_rel) {
-            const int64_t t = lo + 2 * g + c_rel, rc = lo + c_rel - 1;
-            int64_t len = 0;
-            for (int64_t m = rc - 1; m <= rc + 1; ++m)
-                if (m >= lo && m < hi) len += L.h_off[(size_t)m + 1] - L.h_off[(size_t)m];
-            off3[(size_t)t + 1] = len;
-        }
-    }
-    for (int64_t t = 0; t < V3; ++t) off3[(size_t)t + 1] += off3[(size_t)t];
-    if (off3[(size_t)V3] != 3 * n) return fail(YAWHIP_ERR_HIP, "build_triples: %lld entries for %lld objects", (long long)off3[(size_t)V3], (long long)n);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n3 = (size_t)std::max<int64_t>(3 * n, 1);
-    L.q3_stride = (int64_t)((n3 + 3) & ~(size_t)3) + 8;  // as q_stride: a 16-byte load may run up to 12 bytes past a column
-    int32_t *d_run_group = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&L.q3), (size_t)3 * L.q3_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.idx3), n3 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.pos3), (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t));
-    if (e == hipSuccess && c->w) e = hipMalloc(reinterpret_cast<void **>(&L.w3), n3 * sizeof(double) + 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.off3), (size_t)(V3 + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_grid3), (size_t)(V3 + 1) * sizeof(RunGrid));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_run_group), run_group.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(L.q3, 0, (size_t)3 * L.q3_stride * sizeof(float), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(L.d_grid3, 0, (size_t)(V3 + 1) * sizeof(RunGrid), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(L.off3, off3.data(), (size_t)(V3 + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_run_group, run_group.data(), run_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n > 0) {
-        hipLaunchKernelGGL(k_merge_triples, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, V, L.off, d_run_group,
-                           L.d_vbase, L.off3, o == 0 ? L.x : (o == 1 ? L.y : L.z), L.q, L.q_stride, L.w, L.q3, L.q3_stride, L.w3, L.idx3, L.pos3);
-        hipLaunchKernelGGL(k_run_grid<float>, dim3((unsigned)((V3 * (RUN_GRID + 1) + 255) / 256)), dim3(256), 0, ctx->stream, V3, L.off3,
-                           L.q3 + (size_t)o * L.q3_stride, L.d_grid3);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_run_group) (void)hipFree(d_run_group);
-    if (e != hipSuccess) {
-        for (void *ptr : {(void *)L.q3, (void *)L.w3, (void *)L.idx3, (void *)L.pos3, (void *)L.off3, (void *)L.d_grid3})
-            if (ptr) (void)hipFree(ptr);
-        L.q3 = nullptr; L.w3 = nullptr; L.idx3 = nullptr; L.pos3 = nullptr; L.off3 = nullptr; L.d_grid3 = nullptr;
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "merged triple runs failed: %s", hipGetErrorString(e));
-    }
-    const int64_t bytes = 3 * L.q3_stride * (int64_t)sizeof(float) + (int64_t)n3 * (4 + (c->w ? 8 : 0)) + n * 4 + (V3 + 1) * (int64_t)(sizeof(int64_t) + sizeof(RunGrid));
-    L.device_bytes += bytes;
-    c->device_bytes += bytes;
-    L.triples = true;
-    return YAWHIP_OK;
-}
-
-}  // namespace
-
-// ================================================================================================
-extern "C" {
-
-const char *yawhip_last_error(void) { return g_last_error.c_str(); }
-int yawhip_abi_version(void) { return YAWHIP_ABI_VERSION; }
-
-int yawhip_device_count(int *n) {
-    if (!n) return fail(YAWHIP_ERR_INVALID, "yawhip_device_count: n is NULL");
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) {
-        *n = 0;
-        return fail(YAWHIP_ERR_NO_DEVICE, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
-    }
-    *n = c;
-    return YAWHIP_OK;
-}
-
-int yawhip_ctx_create(int device_id, yawhip_ctx **out) {
-    if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_create: out is NULL");
-    *out = nullptr;
-    int c = 0;
-    if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
-        return fail(YAWHIP_ERR_NO_DEVICE, "no HIP device visible (the HIP path is mandatory; there is no CPU fallback)");
-    if (device_id < 0 || device_id >= c)
-        return fail(YAWHIP_ERR_NO_DEVICE, "device id %d out of range [0,%d)", device_id, c);
-    HIP_TRY(hipSetDevice(device_id));
-    yawhip_ctx *ctx = new (std::nothrow) yawhip_ctx();
-    if (!ctx) return fail(YAWHIP_ERR_OOM, "host allocation failed");
-    ctx->device = device_id;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = ctx->make_events();
-    if (e != hipSuccess) {
-        delete ctx;
-        return fail(YAWHIP_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) {
-        if (prop.sharedMemPerBlock > 0) ctx->lds_limit = (int)std::min<size_t>(prop.sharedMemPerBlock, 160 * 1024);
-        if (prop.multiProcessorCount > 0) ctx->n_cu = prop.multiProcessorCount;
-    }
-    *out = ctx;
-    return YAWHIP_OK;
-}
-
-int yawhip_ctx_destroy(yawhip_ctx *ctx) {
-    if (!ctx) return YAWHIP_OK;
-    for (yawhip_ctx *peer : ctx->peers) (void)yawhip_ctx_destroy(peer);
-    ctx->peers.clear();
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    drop_plans(ctx, nullptr);
-    ctx->release_all();
-    for (CallBufs &pb : ctx->parked) pb.release_all();
-    ctx->d_jobwork.release();
-    ctx->d_full.release();
-    ctx->d_rowidx.release();
-    ctx->sort_ws.release();
-    ctx->pix_ws.release();
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-    return YAWHIP_OK;
-}
-
-int yawhip_ctx_set_option(yawhip_ctx *ctx, const char *key, int64_t value) {
-    if (!ctx || !key) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_set_option: NULL argument");
-    // The option is checked before anything changes: a refused key or value leaves plans, option set and devices as they were.
-    std::function<void(yawhip_ctx &)> set;
-    auto flag = [&](int yawhip_ctx::*field) { set = [=](yawhip_ctx &c) { c.*field = value != 0; }; };
-    auto number = [&](int yawhip_ctx::*field) { set = [=](yawhip_ctx &c) { c.*field = (int)value; }; };
-    if (!strcmp(key, "half_bands")) {
-        flag(&yawhip_ctx::half_bands);
-    } else if (!strcmp(key, "tile_r")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4)
-            return fail(YAWHIP_ERR_INVALID, "tile_r must be 0 (auto), 1, 2 or 4");
-        number(&yawhip_ctx::tile_r);
-    } else if (!strcmp(key, "band_batch_log2")) {
-        if (value < -1 || value > 6) return fail(YAWHIP_ERR_INVALID, "band_batch_log2 must be -1 (auto) or 0..6");
-        number(&yawhip_ctx::band_batch_log2);
-    } else if (!strcmp(key, "hist_copies_log2")) {
-        if (value < -1 || value > 6) return fail(YAWHIP_ERR_INVALID, "hist_copies_log2 must be -1 (auto) or 0..6");
-        number(&yawhip_ctx::hist_copies_log2);
-    } else if (!strcmp(key, "triple_runs")) {  // 0: never, 1: where the merged window fits the stage, 2: wherever the partner strips are c - 1, c, c + 1
-        if (value < 0 || value > 2) return fail(YAWHIP_ERR_INVALID, "triple_runs must be 0, 1 or 2");
-        number(&yawhip_ctx::triple_runs);
-    } else if (!strcmp(key, "item_segments")) {
-        flag(&yawhip_ctx::item_segments);
-    } else if (!strcmp(key, "spin_wait")) {
-        flag(&yawhip_ctx::spin_wait);
-    } else if (!strcmp(key, "band_cap")) {
-        if (value != 0 && value != BCAP && value != BCAP_MID && value != B32_CAP && value != B32_CAP_BIG)
-            return fail(YAWHIP_ERR_INVALID, "band_cap must be 0 (auto), 192 or 288 (float64 / fine-grid band kernels), %d or %d (float32 band kernel)",
-                        B32_CAP, B32_CAP_BIG);
-        number(&yawhip_ctx::band_cap);
-    } else if (!strcmp(key, "strip_grid")) {  // 1: latitude, 0: linear in v (catalogues uploaded afterwards)
-        if (value != 0 && value != 1) return fail(YAWHIP_ERR_INVALID, "strip_grid must be 0 (linear in v) or 1 (latitude)");
-        number(&yawhip_ctx::strip_grid);
-    } else if (!strcmp(key, "band_trim")) {
-        if (value != 0 && value != 1) return fail(YAWHIP_ERR_INVALID, "band_trim must be 0 or 1");
-        number(&yawhip_ctx::band_trim);
-    } else if (!strcmp(key, "strip_width_micro")) {  // strip grid spacing in units of 1e-6 rad (latitude grid) or chord (0 = off)
-        if (value != 0 && (value < 1000 || value > 2000000))
-            return fail(YAWHIP_ERR_INVALID, "strip_width_micro must be 0 (off) or in [1e3, 2e6]");
-        set = [=](yawhip_ctx &c) { c.strip_width = (double)value * 1e-6; };
-    } else if (!strcmp(key, "seg_strips_min_run")) {
-        if (value < 1) return fail(YAWHIP_ERR_INVALID, "seg_strips_min_run must be >= 1");
-        set = [=](yawhip_ctx &c) { c.seg_min_run = (int)std::min<int64_t>(value, INT32_MAX); };
-    } else if (!strcmp(key, "seg_strips")) {
-        flag(&yawhip_ctx::seg_strips);
-    } else if (!strcmp(key, "debug_no_hits")) {
-        flag(&yawhip_ctx::debug_no_hits);
-    } else if (!strcmp(key, "auto_orient")) {
-        flag(&yawhip_ctx::auto_orient);
-    } else if (!strcmp(key, "slab_budget_bytes")) {
-        if (value < 4096) return fail(YAWHIP_ERR_INVALID, "slab_budget_bytes must be >= 4096");
-        set = [=](yawhip_ctx &c) { c.slab_budget = value; };
-    } else if (!strcmp(key, "band_grid_div")) {
-        if (value < 0 || value > 64) return fail(YAWHIP_ERR_INVALID, "band_grid_div must be 0 (auto) or in [1, 64]");
-        number(&yawhip_ctx::band_grid_div);
-    } else if (!strcmp(key, "flush_stages_log2")) {
-        if (value < 0 || value > 17) return fail(YAWHIP_ERR_INVALID, "flush_stages_log2 must be in [0, 17]");
-        number(&yawhip_ctx::flush_log2);
-    } else if (!strcmp(key, "band_fp32")) {
-        flag(&yawhip_ctx::band_fp32);
-    } else if (!strcmp(key, "hist_chunk_log2")) {
-        if (value < 8 || value > 30) return fail(YAWHIP_ERR_INVALID, "hist_chunk_log2 must be in [8, 30]");
-        number(&yawhip_ctx::hist_chunk_log2);
-    } else if (!strcmp(key, "kernel")) {
-        if (value < YAWHIP_KERNEL_AUTO || value > YAWHIP_KERNEL_BAND)
-            return fail(YAWHIP_ERR_INVALID, "unknown kernel id %lld", (long long)value);
-        number(&yawhip_ctx::default_kernel);
-    } else {
-        return fail(YAWHIP_ERR_INVALID, "unknown option '%s'", key);
-    }
-    std::vector<yawhip_ctx *> devices(ctx->peers);  // every device of a multi-device context follows
-    devices.push_back(ctx);
-    for (yawhip_ctx *c : devices) {
-        ++c->opt_gen;  // options change every decision of a plan and the work per job
-        drop_plans(c, nullptr);
-        set(*c);
-    }
-    return YAWHIP_OK;
-}
-
-int yawhip_catalog_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                          const double *w, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
-                          yawhip_catalog **out) {
-    return yawhip_catalog_upload_axis(ctx, n, x, y, z, w, n_patches, n_bins_or_1, offsets, 2, out);
-}
-
-int yawhip_catalog_sort_axis(const yawhip_catalog *cat, int32_t *axis) {
-    if (!cat || !axis) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_sort_axis: NULL argument");
-    *axis = cat->axis;
-    return YAWHIP_OK;
-}
-
-// The upload behind yawhip_catalog_upload_axis (kappa == NULL: one catalogue, *out) and yawhip_catalog_upload_scalar (kappa
-// given: the plain catalogue *out and its twin *out_k with weights kappa * w, both from ONE copy of the coordinates and ONE
-// segment sort; the twin is a catalogue like any other from there on -- own uid, own layouts, own replicas).
-static int upload_catalogs(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                           const double *kappa, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
-                           int32_t sort_axis, yawhip_catalog **out, yawhip_catalog **out_k) {
-    if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: out is NULL");
-    if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
-    *out = nullptr;
-    if (out_k) *out_k = nullptr;
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: ctx is NULL");
-    if (n < 0 || n_patches <= 0 || n_bins_or_1 <= 0 || !offsets || (n > 0 && (!x || !y || !z)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload: bad sizes or NULL columns");
-    const int64_t nseg = (int64_t)n_patches * n_bins_or_1;
-    if (n >= (1ll << 32)) return fail(YAWHIP_ERR_INVALID, "at most 2^32 - 1 objects per catalogue");
-    if (offsets[0] != 0 || offsets[nseg] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
-    for (int64_t i = 0; i < nseg; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawhip_catalog *c = new (std::nothrow) yawhip_catalog();
-    static std::atomic<uint64_t> next_uid{1};
-    if (c) c->uid = next_uid.fetch_add(1);
-    if (!c) return fail(YAWHIP_ERR_OOM, "host allocation failed");
-    yawhip_catalog *ck = nullptr;  // the twin (kappa given)
-    if (kappa) {
-        ck = new (std::nothrow) yawhip_catalog();
-        if (!ck) {
-            delete c;
-            return fail(YAWHIP_ERR_OOM, "host allocation failed");
-        }
-        ck->uid = next_uid.fetch_add(1);
-    }
-    for (yawhip_catalog *t : {c, ck}) {
-        if (!t) continue;
-        t->ctx = ctx;
-        t->n = n;
-        t->n_patches = n_patches;
-        t->nb = n_bins_or_1;
-        t->axis = sort_axis;
-        t->h_off.assign(offsets, offsets + nseg + 1);
-    }
-    // Library-private order: the columns go to the device as they are and are ordered there (rocPRIM radix sorts,
-    // yawhip_sort.hip): ascending along the sort axis inside every (patch, bin) segment. The strip layouts are derived
-    // from this resident copy (build_strip_layout), the one of the catalogue's own sort axis right away.
-    const size_t col = (size_t)std::max<int64_t>(n, 1) * sizeof(double) + 16;  // + 16: see build_strip_layout
-    double *rx = nullptr, *ry = nullptr, *rz = nullptr, *rw = nullptr, *rk = nullptr;  // raw columns (temporary)
-    uint32_t *perm = nullptr;
-    int64_t *poff = nullptr;
-    unsigned long long *box = nullptr;  // [P][6] sortable images of min / max per axis, [6 P]: violations of the unit norm
-    auto free_tmp = [&]() {
-        for (void *q : {(void *)rx, (void *)ry, (void *)rz, (void *)rw, (void *)rk, (void *)perm, (void *)poff, (void *)box})
-            if (q) (void)hipFree(q);
-    };
-    auto bail = [&](hipError_t err, const char *what) {
-        free_tmp();
-        yawhip_catalog_free(c);
-        yawhip_catalog_free(ck);
-        return fail(err == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "catalog upload (%s) failed: %s", what,
-                    hipGetErrorString(err));
-    };
-    std::vector<int64_t> h_poff((size_t)n_patches + 1);
-    for (int p = 0; p <= n_patches; ++p) h_poff[(size_t)p] = offsets[(int64_t)p * n_bins_or_1];
-    std::vector<unsigned long long> h_box((size_t)6 * n_patches + 1);
-    for (int p = 0; p < n_patches; ++p)
-        for (int a = 0; a < 3; ++a) {
-            h_box[(size_t)6 * p + a] = sortable_of(4.0);       // running minimum
-            h_box[(size_t)6 * p + 3 + a] = sortable_of(-4.0);  // running maximum
-        }
-    h_box[(size_t)6 * n_patches] = 0ull;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->x), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->y), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->z), col);
-    if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&c->w), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->off), (size_t)(nseg + 1) * sizeof(int64_t));
-    if (ck) {  // the twin's columns: coordinates, the product (always weighted), its own copy of the offsets
-        for (double **q : {&ck->x, &ck->y, &ck->z, &ck->w, &rk})
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(q), col);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ck->off), (size_t)(nseg + 1) * sizeof(int64_t));
-    }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rx), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ry), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rz), col);
-    if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&rw), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm), (size_t)std::max<int64_t>(n, 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&poff), (size_t)(n_patches + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&box), h_box.size() * sizeof(unsigned long long));
-    if (e == hipSuccess && n > 0) {
-        e = hipMemcpyAsync(rx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ry, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(rz, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && w) e = hipMemcpyAsync(rw, w, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && ck) e = hipMemcpyAsync(rk, kappa, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess && ck)
-        e = hipMemcpyAsync(ck->off, offsets, (size_t)(nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(c->off, offsets, (size_t)(nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(poff, h_poff.data(), (size_t)(n_patches + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(box, h_box.data(), h_box.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return bail(e, "columns");
-    const unsigned ngrid = (unsigned)((std::max<int64_t>(n, 1) + 255) / 256);
-    if (n > 0) {
-        // bounding box of every patch (the orientation of a job follows from the boxes of its two patches) and the
-        // unit-norm check of the pre-filter, both on the device
-        hipLaunchKernelGGL(k_patch_boxes, dim3(ngrid), dim3(256), 0, ctx->stream, n, rx, ry, rz, poff, n_patches, box);
-        e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(rx, ry, rz, sort_axis), c->off, nseg, perm);
-        if (e != hipSuccess) return bail(e, "segment sort");
-        if (ck)
-            hipLaunchKernelGGL(k_gather_columns_scalar, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, rx, ry, rz, rw, rk, c->x,
-                               c->y, c->z, c->w, ck->x, ck->y, ck->z, ck->w);
-        else
-            hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, rx, ry, rz, rw, c->x, c->y, c->z, c->w);
-        if ((e = hipGetLastError()) != hipSuccess) return bail(e, "gather");
-        e = hipMemcpyAsync(h_box.data(), box, h_box.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) return bail(e, "patch boxes");
-    }
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(e, "finish");
-    free_tmp();
-    for (yawhip_catalog *t : {c, ck}) {
-        if (!t) continue;
-        t->unit_norm = h_box[(size_t)6 * n_patches] == 0ull;
-        t->h_box.resize((size_t)6 * n_patches);
-        for (size_t i = 0; i < t->h_box.size(); ++i) t->h_box[i] = double_of(h_box[i]);
-        t->device_bytes = (int64_t)col * (t->w ? 4 : 3) + (nseg + 1) * (int64_t)sizeof(int64_t);
-        t->strip_width = ctx->strip_width;
-        t->strip_grid = ctx->strip_grid;
-        t->has_strips = t->unit_norm && n > 0;
-    }
-    for (yawhip_catalog *t : {c, ck}) {  // layouts are built per catalogue (the twin's carry its own weight column)
-        if (!t || !t->has_strips) continue;
-        const int rc = build_strip_layout(ctx, t, sort_axis, false);
-        if (rc != YAWHIP_OK) {
-            yawhip_catalog_free(c);
-            yawhip_catalog_free(ck);
-            return rc;
-        }
-    }
-    if (ctx->sort_ws.cap > ((size_t)1 << 25)) ctx->sort_ws.release();  // ~30 bytes per object: keep only small workspaces
-    for (yawhip_ctx *peer : ctx->peers) {  // multi-device context: the same catalogue(s) on every further device
-        yawhip_catalog *rep = nullptr, *rep_k = nullptr;
-        const int rc = upload_catalogs(peer, n, x, y, z, w, kappa, n_patches, n_bins_or_1, offsets, sort_axis, &rep,
-                                       ck ? &rep_k : nullptr);
-        if (rc != YAWHIP_OK) {
-            yawhip_catalog_free(c);
-            yawhip_catalog_free(ck);
-            return rc;
-        }
-        c->replicas.push_back(rep);
-        if (ck) ck->replicas.push_back(rep_k);
-    }
-    if (ck) *out_k = ck;
-    *out = c;
-    return YAWHIP_OK;
-}
-
-int yawhip_catalog_upload_axis(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                               const double *w, int32_t n_patches, int32_t n_bins_or_1, const int64_t *offsets,
-                               int32_t sort_axis, yawhip_catalog **out) {
-    return upload_catalogs(ctx, n, x, y, z, w, nullptr, n_patches, n_bins_or_1, offsets, sort_axis, out, nullptr);
-}
-
-int yawhip_catalog_upload_scalar(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                                 const double *w, const double *kappa, int32_t n_patches, int32_t n_bins_or_1,
-                                 const int64_t *offsets, int32_t sort_axis, yawhip_catalog **out_n, yawhip_catalog **out_k) {
-    if (!out_n || !out_k) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload_scalar: out_n / out_k is NULL");
-    *out_n = *out_k = nullptr;  // before every check: on any failure neither is returned
-    if (n > 0 && !kappa) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_upload_scalar: kappa is NULL");
-    static const double none = 0.0;  // (n == 0: nothing is read through it)
-    return upload_catalogs(ctx, n, x, y, z, w, kappa ? kappa : &none, n_patches, n_bins_or_1, offsets, sort_axis, out_n, out_k);
-}
-
-int yawhip_catalog_segment_sums(const yawhip_catalog *cat, double *sums) {
-    if (!cat || !sums) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_segment_sums: NULL argument");
-    const int64_t nseg = (int64_t)cat->n_patches * cat->nb;
-    if (!cat->w) {  // unweighted: the number of objects (exact)
-        for (int64_t s = 0; s < nseg; ++s) sums[s] = (double)(cat->h_off[(size_t)s + 1] - cat->h_off[(size_t)s]);
-        return YAWHIP_OK;
-    }
-    yawhip_ctx *ctx = cat->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    double *d_out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_out), (size_t)nseg * sizeof(double));
-    if (e != hipSuccess) return fail(YAWHIP_ERR_OOM, "segment sums: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_segment_weight_sums, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, cat->w, cat->off, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(sums, d_out, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(YAWHIP_ERR_HIP, "segment sums failed: %s", hipGetErrorString(e));
-    return YAWHIP_OK;
-}
-
-int yawhip_catalog_free(yawhip_catalog *c) {
-    if (!c) return YAWHIP_OK;
-    for (yawhip_catalog *rep : c->replicas) (void)yawhip_catalog_free(rep);
-    c->replicas.clear();
-    if (c->ctx) (void)hipSetDevice(c->ctx->device);
-    if (c->ctx) {  // its plans hold pointers into its layouts (nothing of them is in flight: calls are blocking)
-        if (c->ctx->stream) (void)hipStreamSynchronize(c->ctx->stream);
-        drop_plans(c->ctx, c);
-    }
-    if (c->x) (void)hipFree(c->x);
-    if (c->y) (void)hipFree(c->y);
-    if (c->z) (void)hipFree(c->z);
-    if (c->w) (void)hipFree(c->w);
-    if (c->off) (void)hipFree(c->off);
-    for (int o = 0; o < 3; ++o) {
-        c->strips[o].release();
-        c->seg[o].release();
-    }
-    delete c;
-    return YAWHIP_OK;
-}
-
-int yawhip_catalog_device_bytes(const yawhip_catalog *cat, int64_t *bytes) {
-    if (!cat || !bytes) return fail(YAWHIP_ERR_INVALID, "yawhip_catalog_device_bytes: NULL argument");
-    *bytes = cat->device_bytes;
-    return YAWHIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// What count_finish needs to know about a call count_enqueue has put on a context's stream.
-struct CallState {
-    std::chrono::steady_clock::time_point wall0;
-    bool pending = false;          // something was enqueued (false: nothing to count, outputs are zero)
-    int64_t n_out = 0;
-    size_t o_ctr = 0, o_counts = 0, o_sums = 0;
-    bool want_counts = false, want_sums = false, band_ran = false, run_unweighted = false, run_weighted = false;
-    bool segmented = false;        // the item list was kept in segments: the kept items are the sum of the segment counters
-    int64_t cand = 0, abytes = 0, n_pot = 0;
-    int launches = 0, kernel = 0, mode = 0, n_orient = 0, band_variant = 0, merged_triples = 0;
-    int32_t variant[2] = {0, 0};   // count kernel of the unweighted, weighted launch (variant_code)
-    uint64_t seq = 0;              // what k_call_tail writes into the slot's pinned block when the call is done
-    bool word_wait = true;         // the completion word ends the wait (false: the caller put more behind the tail -- stream or event)
-    bool stamps = false;           // kernel_ms / count_ms from the device clock stamps (false: no builder ran -- events)
-    bool cleaned = false;          // the tail zeroes all of [counters][counts]: the slot is clean once the call is done
-    size_t zero_after = 0;         // ... and this many bytes from the start of the block are zero then
-};
 
 // yawhip_stats.count_variant*: the family and template arguments of a count kernel (code layout: include/yawhip.h)
 enum VariantFamily : int32_t { VF_COUNT = 1, VF_MERGED, VF_MERGED_OCC8, VF_BAND, VF_BAND32, VF_BAND32_ONE, VF_BAND32_FINE };
@@ -3465,6 +2091,10 @@ std::vector<float> build_fine32(const double *t, int n_bins, int n_edges) {
     }
     return out;
 }
+
+}  // namespace
+
+namespace yawhip_detail {  // what the other units call (declared in yawhip_internal.h)
 
 CallKey::CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs_, const int32_t *jobs_,
                  int32_t n_bins_, int32_t n_edges_, const double *t_, int32_t kernel_, bool want_counts_, bool want_sums_,
@@ -3557,6 +2187,18 @@ int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_cat
             return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, c1->n_patches);
     return YAWHIP_OK;
 }
+
+// The band_cap option (yawhip_ctx_set_option): 0, or a stage capacity the band kernels are compiled for.
+int check_band_cap(int64_t value) {
+    if (value != 0 && value != BCAP && value != BCAP_MID && value != B32_CAP && value != B32_CAP_BIG)
+        return fail(YAWHIP_ERR_INVALID, "band_cap must be 0 (auto), 192 or 288 (float64 / fine-grid band kernels), %d or %d (float32 band kernel)",
+                    B32_CAP, B32_CAP_BIG);
+    return YAWHIP_OK;
+}
+
+}  // namespace yawhip_detail
+
+namespace {
 
 // make_plan in steps, run in this order: each one fills its own fields of the plan; what a later step needs and the plan does
 // not keep stays in the planner.
@@ -4104,13 +2746,17 @@ int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c
     return rc;
 }
 
+}  // namespace
+
+namespace yawhip_detail {
+
 // First half of yawhip_count_pairs on ONE device: everything up to and including the copy of the results into the
 // context's pinned buffer is put on the context's stream; nothing waits for the device (SWEEP's grid sizing aside).
 // The host side of it (make_plan) is done once per distinct set of inputs and looked up afterwards.
 // job_work != nullptr: cost estimate only -- the item builder runs, evaluated pairs per job are returned, no counting.
 int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
                   const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                  bool want_counts, bool want_sums, int64_t *job_work, CallState &cs, bool fetch_results = true) {
+                  bool want_counts, bool want_sums, int64_t *job_work, CallState &cs, bool fetch_results) {
     cs = CallState{};
     cs.wall0 = std::chrono::steady_clock::now();
     g_trace.mark("enqueue");
@@ -4429,22 +3075,6 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     return YAWHIP_OK;
 }
 
-// Row r of a call's result `in` (nullptr: zeros) into row at[r] of `out` (at == nullptr: row r), rows of `row` values;
-// out == nullptr: not asked for.
-template <typename T>
-void place_rows(T *out, const T *in, int64_t n_rows, int64_t row, const int32_t *at = nullptr) {
-    if (!out) return;
-    if (!at) {  // contiguous: one piece
-        row *= n_rows;
-        n_rows = 1;
-    }
-    for (int64_t r = 0; r < n_rows; ++r) {
-        T *dst = out + (size_t)(at ? at[r] : 0) * (size_t)row;
-        if (in) memcpy(dst, in + (size_t)r * row, sizeof(T) * (size_t)row);
-        else memset(dst, 0, sizeof(T) * (size_t)row);
-    }
-}
-
 // Second half: wait for the context's stream, hand the results (contiguous rows of the jobs given to count_enqueue) and
 // the statistics over.
 // row_index != nullptr: row r of this call's result goes to row row_index[r] of the caller's arrays (rows of row_len values):
@@ -4452,7 +3082,7 @@ void place_rows(T *out, const T *in, int64_t n_rows, int64_t row, const int32_t 
 // wait_done: wait for the active slot's ev_done (recorded by the caller behind everything this call put on the stream)
 // instead of the whole stream -- the requests of a batch behind it keep running.
 int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, double *fine_sums, yawhip_stats *stats,
-                 const int32_t *row_index = nullptr, int64_t row_len = 0, bool wait_done = false) {
+                 const int32_t *row_index, int64_t row_len, bool wait_done) {
     if (stats) memset(stats, 0, sizeof *stats);
     const int64_t n_rows = !row_index ? 1 : (row_len > 0 ? cs.n_out / row_len : 0), row = row_index ? row_len : cs.n_out;
     if (!cs.pending) {
@@ -4567,7 +3197,7 @@ void add_stats(yawhip_stats &total, const yawhip_stats &part, bool side_by_side)
 // One job list on one device, cut in halves as often as count_enqueue asks for (SPLIT_JOBS).
 int run_single(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
                int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, int64_t *fine_counts, double *fine_sums,
-               yawhip_stats *stats, const std::function<void()> *meanwhile = nullptr) {
+               yawhip_stats *stats, const std::function<void()> *meanwhile) {
     // meanwhile: host work of the caller that does not need the result, done while the device counts (once)
     CallState cs;
     int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_counts != nullptr, fine_sums != nullptr,
@@ -4592,62 +3222,7 @@ int run_single(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *
     return YAWHIP_OK;
 }
 
-}  // namespace
-
-namespace {
-// Host-side grouping of catalogue columns (no device involved): a stable counting sort by key, run by a few threads.
-// Chunk c of the input counts its keys; group g then holds the entries of chunk 0, chunk 1, ... in input order, so every
-// chunk knows where its entries of every group go and scatters all columns in one pass over its slice.
-template <typename K>
-static int group_columns(int64_t n, const K *keys, int64_t num_groups, int32_t n_cols, const double *const *in, double *const *out,
-                         int64_t *sizes, int n_threads) {
-    const int64_t min_chunk = 1 << 16;
-    int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, (n + min_chunk - 1) / min_chunk));
-    std::vector<std::vector<int64_t>> hist((size_t)T, std::vector<int64_t>((size_t)num_groups, 0));
-    std::atomic<int> bad{0};
-    auto bounds = [&](int c) { return std::make_pair(n * c / T, n * (c + 1) / T); };
-    auto run = [&](auto &&fn) {
-        if (T == 1) { fn(0); return; }
-        std::vector<std::thread> th;
-        for (int c = 0; c < T; ++c) th.emplace_back(fn, c);
-        for (auto &t : th) t.join();
-    };
-    run([&](int c) {
-        auto [lo, hi] = bounds(c);
-        int64_t *h = hist[(size_t)c].data();
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t k = (int64_t)keys[i];
-            if (k >= num_groups) { bad.store(1); return; }
-            if (k >= 0) ++h[k];
-        }
-    });
-    if (bad.load()) return fail(YAWHIP_ERR_INVALID, "yawhip_host_group_columns: key >= num_groups");
-    int64_t at = 0;
-    for (int64_t g = 0; g < num_groups; ++g) {
-        int64_t size = 0;
-        for (int c = 0; c < T; ++c) {
-            const int64_t cnt = hist[(size_t)c][(size_t)g];
-            hist[(size_t)c][(size_t)g] = at + size;  // first slot of chunk c in group g
-            size += cnt;
-        }
-        sizes[g] = size;
-        at += size;
-    }
-    if (n_cols > 0)
-        run([&](int c) {
-            auto [lo, hi] = bounds(c);
-            int64_t *h = hist[(size_t)c].data();
-            for (int64_t i = lo; i < hi; ++i) {
-                const int64_t k = (int64_t)keys[i];
-                if (k < 0) continue;
-                const int64_t dst = h[k]++;
-                for (int32_t col = 0; col < n_cols; ++col) out[col][dst] = in[col][i];
-            }
-        });
-    return YAWHIP_OK;
-}
-
-}  // namespace
+}  // namespace yawhip_detail
 
 extern "C" {
 
@@ -4735,618 +3310,6 @@ int yawhip_count_pairs(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_c
     if (rc_all != YAWHIP_OK) return rc_all;
     total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     if (stats) *stats = total;
-    return YAWHIP_OK;
-}
-
-int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
-                                   const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                                   int64_t n_rows_total, const int32_t *row_index, double **device_rows, yawhip_stats *stats) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (!ctx || !c1 || !c2 || !device_rows) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: NULL argument");
-    *device_rows = nullptr;
-    if (!ctx->peers.empty()) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: single-device contexts only");
-    const int rc_args = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
-    if (rc_args != YAWHIP_OK) return rc_args;
-    if (n_rows_total < n_jobs || (n_jobs > 0 && !row_index))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: bad sizes or NULL arrays");
-    const int64_t row = (int64_t)n_bins * (n_edges - 1);
-    for (int j = 0; j < n_jobs; ++j)
-        if (row_index[j] < 0 || row_index[j] >= n_rows_total)
-            return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: row index %d outside [0, %lld)", row_index[j], (long long)n_rows_total);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n_full = (size_t)n_rows_total * (size_t)row + 1;  // + 1: the caller's status element
-    HIP_TRY(ctx->d_full.reserve(n_full));
-    HIP_TRY(ctx->d_rowidx.reserve((size_t)std::max(n_jobs, 1)));
-    CallState cs;
-    // (the rows stay on the device: only the statistics counters are fetched)
-    int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, true, nullptr, cs, /*fetch_results=*/false);
-    if (rc == SPLIT_JOBS) {
-        // a job list that is counted in pieces: through the host (rare: weighted slabs beyond the budget)
-        std::vector<double> rows((size_t)n_jobs * (size_t)row), full(n_full, 0.0);
-        rc = run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, nullptr, rows.data(), stats);
-        if (rc != YAWHIP_OK) return rc;
-        place_rows(full.data(), (const double *)rows.data(), n_jobs, row, row_index);
-        HIP_TRY(hipMemcpy(ctx->d_full.ptr, full.data(), sizeof(double) * n_full, hipMemcpyHostToDevice));
-        *device_rows = ctx->d_full.ptr;
-        return YAWHIP_OK;
-    }
-    if (rc != YAWHIP_OK) return rc;
-    cs.word_wait = false;  // the rows are scattered behind the tail: the stream ends the wait
-    HIP_TRY(hipMemsetAsync(ctx->d_full.ptr, 0, sizeof(double) * n_full, ctx->stream));
-    if (cs.pending && n_jobs > 0) {
-        HIP_TRY(hipMemcpyAsync(ctx->d_rowidx.ptr, row_index, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
-        const int64_t n = (int64_t)n_jobs * row;
-        hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_sums,
-                           ctx->d_rowidx.ptr, row, n, ctx->d_full.ptr);
-        HIP_TRY(hipGetLastError());
-    }
-    rc = count_finish(ctx, cs, nullptr, nullptr, stats);  // waits for the stream: the rows are in place when this returns
-    if (rc != YAWHIP_OK) return rc;
-    *device_rows = ctx->d_full.ptr;
-    return YAWHIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// ndarray.sum() of a contiguous float64 vector, in numpy's order (pairwise summation: plain loop below 8 values, eight
-// running sums up to 128, halves above): the reference sums the fine bins of a scale this way (trees.py:134-160), so
-// separation-weighted counts of unweighted catalogues come out bit for bit as the reference's.
-double numpy_sum(const double *a, int64_t n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = a[j];
-        int64_t i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return numpy_sum(a, n2) + numpy_sum(a + n2, n - n2);
-}
-}  // namespace
-
-extern "C" {
-
-int yawhip_count_pairs_dense(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
-                             const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                             int32_t n_scales, const int32_t *slices, const double *fine_factors, int32_t halve_diagonal,
-                             double *dense, yawhip_stats *stats) {
-    yawhip_dense_request req{c1, c2, n_jobs, halve_diagonal, jobs, dense, stats};
-    return yawhip_count_pairs_dense_batch(ctx, 1, &req, n_bins, n_edges, t, kernel, n_scales, slices, fine_factors);
-}
-
-}  // extern "C"
-
-namespace {
-
-struct DenseState {
-    CallState cs;
-    bool enqueued = false;        // on the stream (false: counted by the blocking route at finish time)
-    bool device_combine = false;  // the per-scale values were recombined on the device (k_combine_scales)
-    bool weighted = false;
-    int slot = 0;
-    int64_t n_comb = 0;
-    size_t h_comb_off = 0;
-};
-
-int dense_check(const yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t,
-                int32_t n_scales, const int32_t *slices) {
-    const int rc = check_call(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t);
-    if (rc != YAWHIP_OK) return rc;
-    if (n_scales <= 0 || !slices || !r.dense) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: bad sizes or NULL arrays");
-    return YAWHIP_OK;
-}
-
-// Put one request on the context's stream, in the ACTIVE slot: the count, the recombination of several fine bins on the
-// device (one device, E - 1 > 1: S values per (job, bin) come back instead of E - 1 -- separation weights: 51 -> 1), the copies
-// into the slot's pinned buffers, and the slot's ev_done behind all of it. Nothing waits.
-int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                  int32_t n_scales, const int32_t *slices, const double *fine_factors, DenseState &ds) {
-    const int nf = n_edges - 1;
-    ds.weighted = r.c1->w != nullptr || r.c2->w != nullptr;
-    ds.slot = ctx->slot;
-    ds.device_combine = nf > 1;
-    int rc = count_enqueue(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t, kernel, !ds.weighted, ds.weighted, nullptr, ds.cs,
-                           /*fetch_results=*/!ds.device_combine);
-    if (rc == SPLIT_JOBS) return YAWHIP_OK;  // counted in pieces by the blocking route when its turn comes (ds.enqueued stays false)
-    if (rc != YAWHIP_OK) return rc;
-    if (ds.device_combine) {
-        ds.cs.word_wait = false;  // the recombination and its copy follow the tail: ev_done, recorded behind them, ends the wait
-        ds.n_comb = (int64_t)r.n_jobs * n_bins * n_scales;
-        const size_t b_slices = align16(sizeof(int32_t) * 2 * (size_t)n_bins * n_scales);
-        const size_t b_fact = fine_factors ? align16(sizeof(double) * (size_t)n_bins * nf) : 0;
-        HIP_TRY(ctx->comb.reserve(b_slices + b_fact + sizeof(double) * (size_t)std::max<int64_t>(ds.n_comb, 1)));
-        memcpy(ctx->comb.h, slices, sizeof(int32_t) * 2 * (size_t)n_bins * n_scales);
-        if (fine_factors) memcpy(ctx->comb.h + b_slices, fine_factors, sizeof(double) * (size_t)n_bins * nf);
-        HIP_TRY(hipMemcpyAsync(ctx->comb.d, ctx->comb.h, b_slices + b_fact, hipMemcpyHostToDevice, ctx->stream));
-        ds.h_comb_off = b_slices + b_fact;
-        double *d_comb = reinterpret_cast<double *>(ctx->comb.d + ds.h_comb_off);
-        if (ds.cs.pending && ds.n_comb > 0) {
-            hipLaunchKernelGGL(k_combine_scales, dim3((unsigned)((ds.n_comb + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->d_counts, ctx->d_sums, ds.weighted ? 1 : 0, (int64_t)r.n_jobs, n_bins, nf, n_scales,
-                               reinterpret_cast<const int32_t *>(ctx->comb.d),
-                               fine_factors ? reinterpret_cast<const double *>(ctx->comb.d + b_slices) : nullptr, d_comb);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(ctx->comb.h + ds.h_comb_off, d_comb, sizeof(double) * (size_t)ds.n_comb, hipMemcpyDeviceToHost, ctx->stream));
-        }
-    }
-    HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
-    ds.enqueued = true;
-    return YAWHIP_OK;
-}
-
-// A request's result tensor cleared: unlinked slots and empty scales stay 0 (done while the device counts wherever the route
-// allows: 1 MB, 0.04 ms at the headline).
-void dense_clear(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scales) {
-    const size_t P = (size_t)r.c1->n_patches;
-    memset(r.dense, 0, sizeof(double) * (size_t)n_scales * (size_t)n_bins * P * P);
-}
-
-// The host epilogue, O(jobs x B x S), of PatchLinkage.count_pairs (reference src/yaw/correlation/measurements.py:354-364), into
-// the cleared tensor: halving of the doubly counted diagonal of an autocorrelation and the scatter into
-// [scale][bin][patch i][patch j]. The values of every route:
-//   comb != nullptr: [job][bin][scale], the per-scale sums of the fine bins (k_combine_scales, or the host's numpy_sum);
-//   else one fine bin per (job, bin): numpy's sum of one element is the element, times its separation weight -- hs
-//   (weighted), or hc: unweighted catalogues are counted in int64 and converted here (exact below 2^53, the reference's
-//   .astype(float64), trees.py:353).
-void dense_scatter(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scales, const int32_t *slices, const double *fine_factors,
-                   const double *comb, bool weighted, const int64_t *hc, const double *hs) {
-    const int64_t P = r.c1->n_patches;
-    const int32_t n_jobs = r.n_jobs;
-    const int32_t *jobs = r.jobs;
-    // position and factor of every job, once per call (two short loops over the job list: well under a microsecond)
-    thread_local std::vector<int64_t> cell;
-    thread_local std::vector<double> half;
-    cell.resize((size_t)n_jobs);
-    half.resize((size_t)n_jobs);
-    for (int64_t j = 0; j < n_jobs; ++j) {
-        cell[(size_t)j] = (int64_t)jobs[2 * j] * P + jobs[2 * j + 1];
-        half[(size_t)j] = (r.halve_diagonal && jobs[2 * j] == jobs[2 * j + 1]) ? 0.5 : 1.0;
-    }
-    // Slice by slice: the stores of a (scale, bin) land in one [P, P] slice (32 KB at the headline) while the reads walk the
-    // result block with a stride of one job's values -- 110 KB that stay in the cache over the bins. (Job by job, every store
-    // of a job went to another slice, P * P * 8 bytes apart: one cache set for all of them, 46 us at the headline against 19.)
-    const size_t PP = (size_t)(P * P);
-    auto slice = [&](double *dst, auto value) {
-        for (int64_t j = 0; j < n_jobs; ++j) dst[cell[(size_t)j]] = value(j) * half[(size_t)j];
-    };
-    for (int s_ = 0; s_ < n_scales; ++s_)
-        for (int k = 0; k < n_bins; ++k) {
-            if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared)
-            double *dst = r.dense + ((size_t)s_ * n_bins + (size_t)k) * PP;
-            if (comb) {
-                const double *src = comb + (size_t)k * n_scales + s_;
-                const size_t stride = (size_t)n_bins * n_scales;
-                slice(dst, [=](int64_t j) { return src[(size_t)j * stride]; });
-            } else if (weighted) {
-                const double *src = hs + k;
-                if (fine_factors) {
-                    const double fk = fine_factors[(size_t)k];
-                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins] * fk; });
-                } else {
-                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins]; });
-                }
-            } else {
-                const int64_t *src = hc + k;
-                if (fine_factors) {
-                    const double fk = fine_factors[(size_t)k];
-                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins] * fk; });
-                } else {
-                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins]; });
-                }
-            }
-        }
-    g_trace.mark("scattered");
-    g_trace.flush();
-}
-
-// The blocking route of one request: several devices in the context (the library splits the job list), or a job list that
-// has to be counted in pieces (weighted slabs beyond the budget). Per-job fine values on the host, then the epilogue.
-int dense_blocking(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                   int32_t n_scales, const int32_t *slices, const double *fine_factors) {
-    const yawhip_catalog *c1 = r.c1, *c2 = r.c2;
-    const int32_t n_jobs = r.n_jobs;
-    const int32_t *jobs = r.jobs;
-    const int nf = n_edges - 1;
-    const int64_t row = (int64_t)n_bins * nf;
-    const bool weighted = c1->w != nullptr || c2->w != nullptr;
-    // unweighted catalogues are counted in int64 and converted on the host: one kernel and half the device-to-host bytes less
-    // than asking the device for both
-    const size_t n_fine = (size_t)std::max<int64_t>((int64_t)n_jobs * row, 1);
-    std::unique_ptr<double[]> fine_s(weighted ? new (std::nothrow) double[n_fine] : nullptr);
-    std::unique_ptr<int64_t[]> fine_c(weighted ? nullptr : new (std::nothrow) int64_t[n_fine]);
-    if (!fine_s && !fine_c) return fail(YAWHIP_ERR_OOM, "yawhip_count_pairs_dense: out of host memory");
-    bool cleared = false;  // (on one device the tensor is cleared while the device counts)
-    const std::function<void()> clear = [&]() {
-        dense_clear(r, n_bins, n_scales);
-        cleared = true;
-    };
-    const int rc = ctx->peers.empty() ? run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats, &clear)
-                                      : yawhip_count_pairs(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats);
-    if (rc != YAWHIP_OK) return rc;
-    g_trace.mark("finished");
-    if (!cleared) clear();
-    // Several fine bins: separation weights and the per-scale sums of the fine bins per job (reference
-    // src/yaw/catalog/trees.py:358-362,134-160), into the [job][bin][scale] layout of k_combine_scales, with its products
-    // (counts *= weights) and its order of additions
-    std::vector<double> comb;
-    if (nf > 1) {
-        comb.resize((size_t)n_jobs * n_bins * n_scales);
-        std::vector<double> scaled((size_t)nf);
-        for (int64_t j = 0; j < n_jobs; ++j)
-            for (int k = 0; k < n_bins; ++k) {
-                const size_t at = ((size_t)j * n_bins + k) * nf;
-                const double *wk = fine_factors ? fine_factors + (size_t)k * nf : nullptr;
-                for (int e = 0; e < nf; ++e) {
-                    const double v = weighted ? fine_s[at + e] : (double)fine_c[at + e];
-                    scaled[(size_t)e] = wk ? v * wk[e] : v;
-                }
-                for (int s_ = 0; s_ < n_scales; ++s_) {
-                    const int lo = slices[2 * ((int64_t)k * n_scales + s_)], hi = slices[2 * ((int64_t)k * n_scales + s_) + 1];
-                    comb[((size_t)j * n_bins + k) * n_scales + s_] = hi > lo ? numpy_sum(scaled.data() + lo, hi - lo) : 0.0;
-                }
-            }
-    }
-    dense_scatter(r, n_bins, n_scales, slices, fine_factors, nf > 1 ? comb.data() : nullptr, weighted, fine_c.get(), fine_s.get());
-    return YAWHIP_OK;
-}
-
-// Wait for a request's slot and write its result tensor (dense_scatter) from the slot's pinned buffers.
-int dense_finish(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                 int32_t n_scales, const int32_t *slices, const double *fine_factors, DenseState &ds) {
-    if (!ds.enqueued) return dense_blocking(ctx, r, n_bins, n_edges, t, kernel, n_scales, slices, fine_factors);
-    dense_clear(r, n_bins, n_scales);
-    const int rc = count_finish(ctx, ds.cs, nullptr, nullptr, r.stats, nullptr, 0, /*wait_done=*/true);
-    if (rc != YAWHIP_OK) return rc;
-    if (!ds.cs.pending) return YAWHIP_OK;
-    dense_scatter(r, n_bins, n_scales, slices, fine_factors,
-                  ds.device_combine ? reinterpret_cast<const double *>(ctx->comb.h + ds.h_comb_off) : nullptr, ds.weighted,
-                  reinterpret_cast<const int64_t *>(ctx->out.h + ds.cs.o_counts), reinterpret_cast<const double *>(ctx->out.h + ds.cs.o_sums));
-    return YAWHIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int yawhip_count_pairs_dense_batch(yawhip_ctx *ctx, int32_t n_requests, const yawhip_dense_request *requests, int32_t n_bins,
-                                   int32_t n_edges, const double *t, int32_t kernel, int32_t n_scales, const int32_t *slices,
-                                   const double *fine_factors) {
-    if (!ctx || n_requests < 0 || (n_requests > 0 && !requests))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense_batch: NULL argument");
-    for (int i = 0; i < n_requests; ++i) {
-        if (requests[i].stats) memset(requests[i].stats, 0, sizeof(yawhip_stats));
-        const int rc = dense_check(ctx, requests[i], n_bins, n_edges, t, n_scales, slices);
-        if (rc != YAWHIP_OK) return rc;
-    }
-    const int nf = n_edges - 1;
-    if (n_bins > 0 && n_scales > 0 && slices)
-        for (int64_t i = 0; i < (int64_t)n_bins * n_scales; ++i)
-            if (slices[2 * i] < 0 || slices[2 * i + 1] > nf)
-                return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: slice %lld outside [0, %d]", (long long)i, nf);
-    if (n_requests == 0) return YAWHIP_OK;
-    if (!ctx->peers.empty()) {  // several devices: every request is split over them by yawhip_count_pairs, one after the other
-        for (int i = 0; i < n_requests; ++i) {
-            const int rc = dense_blocking(ctx, requests[i], n_bins, n_edges, t, kernel, n_scales, slices, fine_factors);
-            if (rc != YAWHIP_OK) return rc;
-        }
-        return YAWHIP_OK;
-    }
-    // One device: up to MAX_BATCH requests are on the stream at once, each in a slot of its own (tables, work items, partial
-    // sums, result block, events). The host enqueues request k + 1 while the device counts request k, and writes the tensor of
-    // request k (its epilogue) while the device counts the ones behind it; the device never waits for the host in between.
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<DenseState> st((size_t)n_requests);
-    int rc_all = YAWHIP_OK, done = 0;
-    auto finish_next = [&]() {
-        hipError_t e = use_slot(ctx, done % MAX_BATCH);
-        int rc = e == hipSuccess ? dense_finish(ctx, requests[done], n_bins, n_edges, t, kernel, n_scales, slices, fine_factors, st[(size_t)done])
-                                 : fail(YAWHIP_ERR_HIP, "event creation failed: %s", hipGetErrorString(e));
-        if (rc != YAWHIP_OK && rc_all == YAWHIP_OK) rc_all = rc;
-        ++done;
-    };
-    int issued = 0;
-    for (; issued < n_requests && rc_all == YAWHIP_OK; ++issued) {
-        if (issued - done >= MAX_BATCH) finish_next();  // its slot is needed again
-        if (rc_all != YAWHIP_OK) break;
-        hipError_t e = use_slot(ctx, issued % MAX_BATCH);
-        if (e != hipSuccess) { rc_all = fail(YAWHIP_ERR_HIP, "event creation failed: %s", hipGetErrorString(e)); break; }
-        const int rc = dense_enqueue(ctx, requests[issued], n_bins, n_edges, t, kernel, n_scales, slices, fine_factors, st[(size_t)issued]);
-        if (rc != YAWHIP_OK) { rc_all = rc; break; }
-    }
-    if (rc_all != YAWHIP_OK) {  // leave nothing in flight behind an error
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)use_slot(ctx, 0);
-        return rc_all;
-    }
-    while (done < issued) finish_next();
-    (void)use_slot(ctx, 0);
-    if (rc_all != YAWHIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    return rc_all;
-}
-
-int yawhip_ctx_create_multi(const int *device_ids, int n_devices, yawhip_ctx **out) {
-    if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_create_multi: out is NULL");
-    *out = nullptr;
-    if (!device_ids || n_devices < 1 || n_devices > 64) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_create_multi: 1 to 64 device ids");
-    yawhip_ctx *ctx = nullptr;
-    int rc = yawhip_ctx_create(device_ids[0], &ctx);
-    if (rc != YAWHIP_OK) return rc;
-    for (int i = 1; i < n_devices; ++i) {
-        yawhip_ctx *peer = nullptr;
-        rc = yawhip_ctx_create(device_ids[i], &peer);
-        if (rc != YAWHIP_OK) {
-            yawhip_ctx_destroy(ctx);
-            return rc;
-        }
-        ctx->peers.push_back(peer);
-    }
-    *out = ctx;
-    return YAWHIP_OK;
-}
-
-int yawhip_ctx_device_count(const yawhip_ctx *ctx, int *n) {
-    if (!ctx || !n) return fail(YAWHIP_ERR_INVALID, "yawhip_ctx_device_count: NULL argument");
-    *n = (int)ctx->peers.size() + 1;
-    return YAWHIP_OK;
-}
-
-int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, int32_t n_centers,
-                          const double *centers_xyz, int32_t *patch_out) {
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_assign_patches: ctx is NULL");
-    if (n < 0 || n_centers <= 0 || !centers_xyz || (n > 0 && (!x || !y || !z || !patch_out)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_assign_patches: bad sizes or NULL arrays");
-    if ((size_t)n_centers * 3 * sizeof(double) > (size_t)ctx->lds_limit)
-        return fail(YAWHIP_ERR_INVALID, "too many centres (%d) for the LDS table", n_centers);
-    if (n == 0) return YAWHIP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    double *dx = nullptr, *dc = nullptr;
-    int32_t *dout = nullptr;
-    auto cleanup = [&]() {
-        if (dx) (void)hipFree(dx);
-        if (dc) (void)hipFree(dc);
-        if (dout) (void)hipFree(dout);
-    };
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dx), (size_t)3 * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dc), (size_t)3 * n_centers * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dout), (size_t)n * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dx + n, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dx + 2 * n, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dc, centers_xyz, (size_t)3 * n_centers * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        const size_t lds = (size_t)3 * n_centers * sizeof(double);
-        if (lds > 64 * 1024)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_assign_patches), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_assign_patches, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, ctx->stream, n, dx, dx + n, dx + 2 * n,
-                               n_centers, dc, dout);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(patch_out, dout, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_assign_patches failed: %s", hipGetErrorString(e));
-    return YAWHIP_OK;
-}
-
-int yawhip_redshift_histogram(yawhip_ctx *ctx, int64_t n, const double *z, const double *w, int32_t n_patches,
-                              const int64_t *offsets, int32_t n_edges, const double *edges, int32_t closed_right, double *out) {
-    if (!ctx || !offsets || !edges || !out) return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: NULL argument");
-    if (n < 0 || n_patches < 1 || n_edges < 2 || (n > 0 && !z))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: bad sizes (n=%lld n_patches=%d n_edges=%d) or NULL z",
-                    (long long)n, n_patches, n_edges);
-    if (closed_right != 0 && closed_right != 1) return fail(YAWHIP_ERR_INVALID, "yawhip_redshift_histogram: closed_right must be 0 or 1");
-    if (offsets[0] != 0 || offsets[n_patches] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
-    for (int32_t p = 0; p < n_patches; ++p)
-        if (offsets[p + 1] < offsets[p]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
-    for (int32_t i = 0; i + 1 < n_edges; ++i)
-        if (!(edges[i + 1] > edges[i])) return fail(YAWHIP_ERR_INVALID, "bin edges must increase strictly (edge %d)", i + 1);
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawhist::HistCall c;
-    c.n = n, c.z = z, c.w = w;
-    c.n_patches = n_patches, c.offsets = offsets;
-    c.n_edges = n_edges, c.edges = edges, c.closed_right = closed_right;
-    c.chunk_log2 = ctx->hist_chunk_log2;
-    c.out = out;
-    const hipError_t e = yawhist::redshift_histogram(ctx->stream, c);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_redshift_histogram failed: %s", hipGetErrorString(e));
-    return YAWHIP_OK;
-}
-
-int yawhip_healpix_map(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const double *phi, const double *z, const double *w, int32_t order,
-                       int32_t nested, int64_t *pix_out, double *map_out) {
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: ctx is NULL");
-    if (!pix_out && !map_out) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: pix_out and map_out are both NULL");
-    if (n < 0 || chunksize < 0 || (n > 0 && (!phi || !z)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: n < 0, chunksize < 0 or NULL phi / z");
-    if (order < 0 || order > yawpix::MAX_ORDER)
-        return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: order %d outside 0 .. %d", order, yawpix::MAX_ORDER);
-    if (nested != 0 && nested != 1) return fail(YAWHIP_ERR_INVALID, "yawhip_healpix_map: nested must be 0 or 1");
-    if (n == 0) {
-        if (map_out) std::fill(map_out, map_out + ((size_t)12 << (2 * order)), 0.0);
-        return YAWHIP_OK;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawpix::MapCall c;
-    c.n = n, c.chunksize = std::min(chunksize > 0 ? chunksize : yawpix::DEFAULT_CHUNK, yawpix::MAX_CHUNK);
-    c.phi = phi, c.z = z, c.w = w;
-    c.order = order, c.nested = nested;
-    c.pix_out = pix_out, c.map_out = map_out;
-    const hipError_t e = yawpix::healpix_map(ctx->pix_ws, ctx->stream, c);
-    if (ctx->pix_ws.bytes() > ((size_t)1 << 28)) ctx->pix_ws.release();  // keep only small workspaces, as the sort workspace
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "yawhip_healpix_map failed: %s", hipGetErrorString(e));
-    return YAWHIP_OK;
-}
-
-int yawhip_healpix_pixels(yawhip_ctx *ctx, int64_t n_pix, int64_t chunksize, const double *values, const double *weights, int32_t order,
-                          int32_t nested, int64_t capacity, int64_t *ipix_out, double *phi_out, double *z_out, double *kappa_out,
-                          double *w_out, int64_t *n_selected) {
-    static const char fn[] = "yawhip_healpix_pixels";
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!values || !n_selected) return fail(YAWHIP_ERR_INVALID, "%s: NULL values or n_selected", fn);
-    *n_selected = 0;
-    if (order < 0 || order > yawpix::MAX_ORDER) return fail(YAWHIP_ERR_INVALID, "%s: order %d outside 0 .. %d", fn, order, yawpix::MAX_ORDER);
-    if (n_pix != (int64_t)12 << (2 * order))
-        return fail(YAWHIP_ERR_INVALID, "%s: n_pix %lld is not 12 * 4^order (order %d)", fn, (long long)n_pix, order);
-    if (nested != 0 && nested != 1) return fail(YAWHIP_ERR_INVALID, "%s: nested must be 0 or 1", fn);
-    if (chunksize < 0 || capacity < 0) return fail(YAWHIP_ERR_INVALID, "%s: chunksize < 0 or capacity < 0", fn);
-    if (capacity > 0 && (!ipix_out || !phi_out || !z_out || !kappa_out || (weights && !w_out)))
-        return fail(YAWHIP_ERR_INVALID, "%s: NULL output with capacity %lld", fn, (long long)capacity);
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawpix::PixelsCall c;
-    c.chunksize = std::min(chunksize > 0 ? chunksize : yawpix::DEFAULT_CHUNK, yawpix::MAX_CHUNK);
-    c.values = values, c.weights = weights;
-    c.order = order, c.nested = nested;
-    c.capacity = capacity;
-    c.ipix_out = ipix_out, c.phi_out = phi_out, c.z_out = z_out, c.kappa_out = kappa_out, c.w_out = w_out;
-    int64_t selected = 0;
-    bool overflow = false;
-    const hipError_t e = yawpix::healpix_pixels(ctx->pix_ws, ctx->stream, c, selected, overflow);
-    if (ctx->pix_ws.bytes() > ((size_t)1 << 28)) ctx->pix_ws.release();  // keep only small workspaces, as yawhip_healpix_map
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "%s failed: %s", fn, hipGetErrorString(e));
-    *n_selected = selected;
-    if (overflow)
-        return fail(YAWHIP_ERR_MISMATCH, "%s: the map selects more pixels than the capacity %lld of the outputs", fn, (long long)capacity);
-    if (selected != capacity)
-        return fail(YAWHIP_ERR_MISMATCH, "%s: the map selects %lld pixels, the outputs were sized for %lld", fn, (long long)selected,
-                    (long long)capacity);
-    return YAWHIP_OK;
-}
-
-// What yawhip_random_box and yawhip_random_healpix check alike (`fn`: the name in the message); YAWHIP_OK or the failure.
-static int check_random_args(const char *fn, const yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int64_t n_data,
-                             const double *data_w, const double *data_z, const double *x_out, const double *y_out, const double *w_out,
-                             const double *z_out, const int64_t *idx_out, const uint64_t state_out[2], const int32_t *has_uint32_out,
-                             const uint32_t *uinteger_out) {
-    if (!ctx || !state || !state_out || !has_uint32_out || !uinteger_out) return fail(YAWHIP_ERR_INVALID, "%s: NULL argument", fn);
-    if (n < 0 || chunksize < 1) return fail(YAWHIP_ERR_INVALID, "%s: n < 0 or chunksize < 1", fn);
-    if (n_data > (int64_t)1 << 32)
-        return fail(YAWHIP_ERR_INVALID, "%s: n_data = %lld > 2^32: numpy draws these indices from its 64-bit bounded "
-                    "path, which the device does not implement", fn, (long long)n_data);
-    if (n_data == 0 || n_data < -1) return fail(YAWHIP_ERR_INVALID, "%s: n_data must be -1 or 1 .. 2^32", fn);
-    if (n_data == -1 && (data_w || data_z || idx_out))
-        return fail(YAWHIP_ERR_INVALID, "%s: data arrays or indices without attached data (n_data = -1)", fn);
-    if (!data_w != !w_out || !data_z != !z_out)
-        return fail(YAWHIP_ERR_INVALID, "%s: w_out / z_out must be given exactly with data_w / data_z", fn);
-    if (n > 0 && (!x_out || !y_out)) return fail(YAWHIP_ERR_INVALID, "%s: x_out / y_out is NULL", fn);
-    if ((state[3] & 1) == 0) return fail(YAWHIP_ERR_INVALID, "%s: the increment of a PCG64 state is odd", fn);
-    return YAWHIP_OK;
-}
-
-static void fill_draw(yawrand::Draw &d, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
-                      int64_t n_data, const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
-                      double *z_out, int64_t *idx_out) {
-    d.n = n;
-    d.chunksize = chunksize;
-    d.state_hi = state[0], d.state_lo = state[1], d.inc_hi = state[2], d.inc_lo = state[3];
-    d.has_uint32 = has_uint32, d.uinteger = uinteger;
-    d.n_data = n_data, d.data_w = data_w, d.data_z = data_z;
-    d.x_out = x_out, d.y_out = y_out, d.w_out = w_out, d.z_out = z_out, d.idx_out = idx_out;
-}
-
-static int finish_draw(const char *fn, hipError_t e, const yawrand::DrawEnd &end, uint64_t state_out[2], int32_t *has_uint32_out,
-                       uint32_t *uinteger_out) {
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "%s failed: %s", fn, hipGetErrorString(e));
-    state_out[0] = end.state_hi;
-    state_out[1] = end.state_lo;
-    *has_uint32_out = end.has_uint32;
-    *uinteger_out = end.uinteger;
-    return YAWHIP_OK;
-}
-
-int yawhip_random_box(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32, uint32_t uinteger,
-                      double x_min, double x_range, double y_min, double y_range, int64_t n_data, const double *data_w,
-                      const double *data_z, double *x_out, double *y_out, double *w_out, double *z_out, int64_t *idx_out,
-                      uint64_t state_out[2], int32_t *has_uint32_out, uint32_t *uinteger_out) {
-    static const char fn[] = "yawhip_random_box";
-    if (const int rc = check_random_args(fn, ctx, n, chunksize, state, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out,
-                                         state_out, has_uint32_out, uinteger_out))
-        return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawrand::BoxDraw d;
-    fill_draw(d, n, chunksize, state, has_uint32, uinteger, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out);
-    d.x_min = x_min, d.x_range = x_range, d.y_min = y_min, d.y_range = y_range;
-    yawrand::DrawEnd end;
-    return finish_draw(fn, yawrand::draw_box(ctx->stream, d, end), end, state_out, has_uint32_out, uinteger_out);
-}
-
-int yawhip_random_healpix(yawhip_ctx *ctx, int64_t n, int64_t chunksize, const uint64_t state[4], int32_t has_uint32,
-                          uint32_t uinteger, int32_t order, int64_t n_unmasked, const int64_t *ipix_unmasked, const double *cdf,
-                          int64_t n_data, const double *data_w, const double *data_z, double *x_out, double *y_out, double *w_out,
-                          double *z_out, int64_t *idx_out, int64_t *pix_out, uint64_t state_out[2], int32_t *has_uint32_out,
-                          uint32_t *uinteger_out) {
-    static const char fn[] = "yawhip_random_healpix";
-    if (const int rc = check_random_args(fn, ctx, n, chunksize, state, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out,
-                                         state_out, has_uint32_out, uinteger_out))
-        return rc;
-    if (order < 0 || order > 13) return fail(YAWHIP_ERR_INVALID, "%s: order %d outside 0 .. 13", fn, order);
-    const int64_t npix = (int64_t)12 << (2 * order);
-    if (n_unmasked < 1 || n_unmasked > npix || !ipix_unmasked || !cdf)
-        return fail(YAWHIP_ERR_INVALID, "%s: n_unmasked outside 1 .. 12 * 4^order, or ipix_unmasked / cdf is NULL", fn);
-    for (int64_t j = 0; j < n_unmasked; ++j) {
-        if (ipix_unmasked[j] < 0 || ipix_unmasked[j] >= npix)
-            return fail(YAWHIP_ERR_INVALID, "%s: ipix_unmasked[%lld] is no pixel of order %d", fn, (long long)j, order);
-        if (!(cdf[j] >= (j ? cdf[j - 1] : 0.0)))
-            return fail(YAWHIP_ERR_INVALID, "%s: cdf[%lld] is negative, NaN or below its predecessor", fn, (long long)j);
-    }
-    if (cdf[n_unmasked - 1] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the cdf must end in 1", fn);
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawrand::HealpixDraw d;
-    fill_draw(d, n, chunksize, state, has_uint32, uinteger, n_data, data_w, data_z, x_out, y_out, w_out, z_out, idx_out);
-    d.order = order, d.n_unmasked = n_unmasked, d.ipix_unmasked = ipix_unmasked, d.cdf = cdf, d.pix_out = pix_out;
-    yawrand::DrawEnd end;
-    return finish_draw(fn, yawrand::draw_healpix(ctx->stream, d, end), end, state_out, has_uint32_out, uinteger_out);
-}
-
-int yawhip_host_group_columns(int64_t n, const void *keys, int32_t key_bytes, int64_t num_groups, int32_t n_cols,
-                              const double *const *in, double *const *out, int64_t *sizes, int32_t n_threads) {
-    if (n < 0 || num_groups <= 0 || n_cols < 0 || !sizes || (n > 0 && !keys) || (key_bytes != 4 && key_bytes != 8))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_host_group_columns: bad sizes or NULL arrays");
-    for (int32_t c = 0; c < n_cols; ++c)
-        if (n > 0 && (!in || !out || !in[c] || !out[c] || in[c] == out[c]))
-            return fail(YAWHIP_ERR_INVALID, "yawhip_host_group_columns: column %d is NULL or aliases its output", c);
-    if (n_threads <= 0) n_threads = (int32_t)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);
-    try {
-        return key_bytes == 4 ? group_columns(n, (const int32_t *)keys, num_groups, n_cols, in, out, sizes, n_threads)
-                              : group_columns(n, (const int64_t *)keys, num_groups, n_cols, in, out, sizes, n_threads);
-    } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "yawhip_host_group_columns: out of host memory");
-    } catch (const std::system_error &err) {
-        return fail(YAWHIP_ERR_INVALID, "yawhip_host_group_columns: %s", err.what());
-    }
-}
-
-int yawhip_host_scatter_rows(int64_t n_rows, int64_t row_len, double *out, int64_t n_cols, const int64_t *cols,
-                             const double *vals, int64_t val_row_stride, int64_t val_col_stride, const double *col_factor) {
-    if (n_rows < 0 || row_len < 0 || n_cols < 0 || (n_rows * row_len > 0 && !out) || (n_cols > 0 && (!cols || (n_rows > 0 && !vals))))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_host_scatter_rows: bad sizes or NULL arrays");
-    for (int64_t j = 0; j < n_cols; ++j)
-        if (cols[j] < 0 || cols[j] >= row_len) return fail(YAWHIP_ERR_INVALID, "yawhip_host_scatter_rows: column %lld out of range", (long long)cols[j]);
-    memset(out, 0, sizeof(double) * (size_t)(n_rows * row_len));
-    for (int64_t r = 0; r < n_rows; ++r) {
-        double *dst = out + r * row_len;
-        const double *src = vals + r * val_row_stride;
-        if (col_factor)
-            for (int64_t j = 0; j < n_cols; ++j) dst[cols[j]] = src[j * val_col_stride] * col_factor[j];
-        else
-            for (int64_t j = 0; j < n_cols; ++j) dst[cols[j]] = src[j * val_col_stride];
-    }
     return YAWHIP_OK;
 }
 

@@ -1,6 +1,7 @@
-// Internal interface between yawhip.hip and yawhip_healpix.hip (HEALPix pixels and maps of a catalogue,
+// Internal interface between yawhip_api.hip and yawhip_healpix.hip (HEALPix pixels and maps of a catalogue,
 // yawhip_healpix_map; the unmasked pixels of a scalar map as a catalogue's columns, yawhip_healpix_pixels). Not part of
-// the C ABI: yawhip.hip checks the arguments and owns the error reporting.
+// the C ABI: yawhip_api.hip checks the arguments and owns the error reporting. The Workspace is a member of every context
+// (yawhip_internal.h).
 #ifndef YAWHIP_HEALPIX_H
 #define YAWHIP_HEALPIX_H
 #include <hip/hip_runtime.h>

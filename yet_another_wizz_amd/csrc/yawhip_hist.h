@@ -1,5 +1,5 @@
-// Internal interface between yawhip.hip and yawhip_hist.hip (per-patch redshift histograms, yawhip_redshift_histogram).
-// Not part of the C ABI: yawhip.hip checks the arguments and owns the error reporting.
+// Internal interface between yawhip_api.hip and yawhip_hist.hip (per-patch redshift histograms, yawhip_redshift_histogram).
+// Not part of the C ABI: yawhip_api.hip checks the arguments and owns the error reporting.
 #ifndef YAWHIP_HIST_H
 #define YAWHIP_HIST_H
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
-// Internal interface between yawhip.hip and yawhip_random.hip (random catalogues drawn from numpy's PCG64 stream,
-// yawhip_random_box and yawhip_random_healpix). Not part of the C ABI: yawhip.hip checks the arguments and owns the
+// Internal interface between yawhip_api.hip and yawhip_random.hip (random catalogues drawn from numpy's PCG64 stream,
+// yawhip_random_box and yawhip_random_healpix). Not part of the C ABI: yawhip_api.hip checks the arguments and owns the
 // error reporting.
 #ifndef YAWHIP_RANDOM_H
 #define YAWHIP_RANDOM_H

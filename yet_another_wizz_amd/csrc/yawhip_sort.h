@@ -1,5 +1,5 @@
-// Internal interface between yawhip.hip and yawhip_sort.hip (device-side ordering of a catalogue at upload).
-// Not part of the C ABI.
+// Internal interface between yawhip_ingest.hip and yawhip_sort.hip (device-side ordering of a catalogue at upload).
+// Not part of the C ABI. The Workspace is a member of every context (yawhip_internal.h), which yawhip_api.hip releases.
 #ifndef YAWHIP_SORT_H
 #define YAWHIP_SORT_H
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // Device-side ordering of a catalogue at upload: rocPRIM radix sorts (ROCm's own header library) wrapped for
-// yawhip.hip. Replaces the per-job tree build of the reference (BinnedTrees.build, catalog/trees.py:483-545) and
+// yawhip_ingest.hip. Replaces the per-job tree build of the reference (BinnedTrees.build, catalog/trees.py:483-545) and
 // the host-thread sorts the first version of this library used (0.45 s per 10 M objects).
 #include <cstdlib>
 #include <cstring>
