@@ -455,6 +455,41 @@ int yawhip_job_work(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_cata
                     const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
                     int64_t *work);
 
+/*
+ * Deterministic k-means over ALL objects of a catalogue, columns resident on the device (patches.create_patch_centers,
+ * Catalog.from_*(patch_num=..., patch_method="full"); stands in for treecorr's k-means behind create_patch_centers,
+ * catalog/catalog.py:183-226). Everything summed over objects is an integer, so the results do not depend on the order of
+ * the additions (atomics, grid shape) and equal the numpy route of patches.py bit for bit. Additive to ABI 6.
+ * The squared distance of object i and centre c is ((x_i - c_x)^2 + (y_i - c_y)^2) + (z_i - c_z)^2, every product and sum
+ * rounded on its own (the arithmetic of yawhip_assign_patches); among equal distances the lowest centre index wins.
+ *
+ * yawhip_kmeans_open   uploads the columns ONCE (first device of a multi-device context); the other calls move centre
+ *                      tables, k-sized results and scalars only (and ids, where asked for).
+ *   n        1 .. 2^31 objects;  x, y, z  float64[n] unit vectors (host);  w  float64[n] finite weights (host) or NULL
+ *   wscale   with w: the power of two 2^(30 - e), e the binary exponent of max |w| (frexp), so that |w x wscale| <= 2^30
+ * yawhip_kmeans_seed   one k-means++ step: m_i = d(i, centre) (first = 1) or min(m_i, d(i, centre)) (first = 0), then
+ *                      q_i = floor(m_i * 2^29) as an integer; *total = sum of all q_i (exact).
+ * yawhip_kmeans_pick   after a seed: *index = the smallest i whose inclusive prefix sum of q exceeds r; r < total.
+ * yawhip_kmeans_step   one Lloyd round against centres[k][3]: id_i = nearest centre; per cluster counts[c] = objects,
+ *                      sums[c][axis] = sum of a_i, a_i = rint(x_i * 2^30), with weights rint((w_i * x_i) * wscale)
+ *                      (round half to even), all int64; *inertia = sum of floor(d(i, id_i) * 2^29); ids int32[n] (host)
+ *                      or NULL. 3 k doubles must fit the LDS (as for yawhip_assign_patches), else YAWHIP_ERR_INVALID.
+ *                      Where the per-workgroup partial sums [k][4] fit the LDS beside the centres they are kept there and
+ *                      flushed once per workgroup, otherwise every object adds to global memory (integer atomics both).
+ * yawhip_kmeans_query  what = 0: objects per segment of the seed sums, 1: path of the last step (0 none, 1 LDS partials,
+ *                      2 global atomics), 2: largest k of the LDS-partials path, 3: largest k of yawhip_kmeans_step.
+ * yawhip_kmeans_close  frees the handle (NULL: nothing happens). Close it before its context is destroyed.
+ */
+typedef struct yawhip_kmeans yawhip_kmeans;
+int yawhip_kmeans_open(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                       double wscale, yawhip_kmeans **out);
+int yawhip_kmeans_seed(yawhip_kmeans *km, const double centre[3], int32_t first, uint64_t *total);
+int yawhip_kmeans_pick(yawhip_kmeans *km, uint64_t r, int64_t *index);
+int yawhip_kmeans_step(yawhip_kmeans *km, int32_t k, const double *centres, int64_t *sums, int64_t *counts,
+                       uint64_t *inertia, int32_t *ids);
+int yawhip_kmeans_query(const yawhip_kmeans *km, int32_t what, int64_t *value);
+void yawhip_kmeans_close(yawhip_kmeans *km);
+
 #ifdef __cplusplus
 }
 #endif

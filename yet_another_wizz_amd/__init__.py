@@ -23,7 +23,7 @@ from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
                            crosscorrelate_scalar, crosscorrelate_scalar_map)
-from . import healpix, randoms
+from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
 
@@ -55,5 +55,6 @@ __all__ = [
     "crosscorrelate_scalar",
     "crosscorrelate_scalar_map",
     "healpix",
+    "patches",
     "randoms",
 ]

@@ -51,6 +51,12 @@ ABI_SYMBOLS = (
     "yawhip_redshift_histogram",
     "yawhip_host_group_columns",
     "yawhip_host_scatter_rows",
+    "yawhip_kmeans_open",
+    "yawhip_kmeans_seed",
+    "yawhip_kmeans_pick",
+    "yawhip_kmeans_step",
+    "yawhip_kmeans_query",
+    "yawhip_kmeans_close",
 )
 
 
@@ -248,9 +254,16 @@ def load_library() -> ctypes.CDLL:
     ]
     lib.yawhip_host_scatter_rows.argtypes = [ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64,
                                              ctypes.c_int64, _vp]
+    lib.yawhip_kmeans_open.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, ctypes.c_double, ctypes.POINTER(_vp)]
+    lib.yawhip_kmeans_seed.argtypes = [_vp, _dp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.yawhip_kmeans_pick.argtypes = [_vp, ctypes.c_uint64, _i64p]
+    lib.yawhip_kmeans_step.argtypes = [_vp, ctypes.c_int32, _dp, _i64p, _i64p, ctypes.POINTER(ctypes.c_uint64), _i32p]
+    lib.yawhip_kmeans_query.argtypes = [_vp, ctypes.c_int32, _i64p]
+    lib.yawhip_kmeans_close.argtypes = [_vp]
+    lib.yawhip_kmeans_close.restype = None
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
-        if name != "yawhip_last_error":
+        if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
             fn.restype = ctypes.c_int
     _lib = lib
     return lib
@@ -302,6 +315,7 @@ class Context:
         self.strip_micro = DEFAULT_STRIP_MICRO
         self.strip_grid = 1  # the library's default: strip grid uniform in latitude
         self._catalogs = weakref.WeakSet()  # live catalogues: freed before the context (a catalogue's free reads its context)
+        self._kmeans = weakref.WeakSet()    # live k-means handles: they use the context's stream
 
     def set_option(self, key: str, value: int) -> None:
         _check(load_library().yawhip_ctx_set_option(self._h, key.encode(), int(value)), "yawhip_ctx_set_option")
@@ -314,6 +328,8 @@ class Context:
         if getattr(self, "_h", None) is not None and self._h:
             for cat in list(self._catalogs):
                 cat.free()
+            for km in list(self._kmeans):
+                km.close()
             load_library().yawhip_ctx_destroy(self._h)
             self._h = _vp()
 
@@ -655,6 +671,78 @@ def assign_patches(ctx: Context, x, y, z, centers_xyz) -> np.ndarray:
         "yawhip_assign_patches",
     )
     return out
+
+
+class KMeans:
+    """``yawhip_kmeans``: the columns of a catalogue resident on the device for the full-catalogue k-means of ``patches.py``
+    (the arithmetic is written out there). ``x, y, z``: float64 unit vectors; ``w``: finite float64 weights or None, with
+    ``wscale`` the power of two that brings ``max |w|`` below 2^30. Closes on ``__exit__`` / ``__del__``; closing twice is
+    harmless."""
+
+    PATH_NAMES = {0: None, 1: "lds", 2: "global"}
+
+    def __init__(self, ctx: Context, x, y, z, w=None, wscale: float = 0.0):
+        self._h = _vp()
+        x, y, z, w = _f64(x), _f64(y), _f64(z), _f64(w)
+        n = len(x)
+        if not (len(y) == n and len(z) == n and (w is None or len(w) == n)):
+            raise ValueError("k-means columns differ in length")
+        self.ctx, self.n, self.weighted = ctx, n, w is not None  # (keeps the context alive)
+        _check(load_library().yawhip_kmeans_open(ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), float(wscale),
+                                                 ctypes.byref(self._h)), "yawhip_kmeans_open")
+        ctx._kmeans.add(self)
+
+    def seed(self, centre, first: bool) -> int:
+        """One k-means++ step against ``centre`` (three float64): the exact total of ``q = floor(m 2^29)``."""
+        c = np.ascontiguousarray(centre, dtype=np.float64).reshape(3)
+        total = ctypes.c_uint64(0)
+        _check(load_library().yawhip_kmeans_seed(self._h, _ptr(c, _dp), 1 if first else 0, ctypes.byref(total)), "yawhip_kmeans_seed")
+        return int(total.value)
+
+    def pick(self, r: int) -> int:
+        """The smallest index whose inclusive prefix sum of the last seed's ``q`` exceeds ``r``."""
+        index = ctypes.c_int64(-1)
+        _check(load_library().yawhip_kmeans_pick(self._h, int(r), ctypes.byref(index)), "yawhip_kmeans_pick")
+        return int(index.value)
+
+    def step(self, centres, *, want_ids: bool = False):
+        """One Lloyd round against ``centres`` float64[k, 3] -> ``(sums int64[k, 3], counts int64[k], inertia int, ids int32[n]
+        or None)``."""
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+        k = len(centres)
+        sums, counts = np.empty((k, 3), dtype=np.int64), np.empty(k, dtype=np.int64)
+        ids = np.empty(self.n, dtype=np.int32) if want_ids else None
+        inertia = ctypes.c_uint64(0)
+        _check(load_library().yawhip_kmeans_step(self._h, k, _ptr(centres, _dp), _ptr(sums, _i64p), _ptr(counts, _i64p),
+                                                 ctypes.byref(inertia), _ptr(ids, _i32p)), "yawhip_kmeans_step")
+        return sums, counts, int(inertia.value), ids
+
+    def _query(self, what: int) -> int:
+        value = ctypes.c_int64(0)
+        _check(load_library().yawhip_kmeans_query(self._h, what, ctypes.byref(value)), "yawhip_kmeans_query")
+        return int(value.value)
+
+    segment = property(lambda self: self._query(0), doc="objects per segment of the seed sums")
+    last_path = property(lambda self: self.PATH_NAMES[self._query(1)], doc='"lds" / "global": where the last step kept its partials')
+    max_centres_lds = property(lambda self: self._query(2), doc="largest k whose partials fit the LDS beside the centres")
+    max_centres = property(lambda self: self._query(3), doc="largest k of step()")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            load_library().yawhip_kmeans_close(self._h)
+            self._h = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,

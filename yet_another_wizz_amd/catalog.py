@@ -48,6 +48,7 @@ def _stable_argsort_small(keys, num_values: int):
 DEVICE_ASSIGN_MIN = 200_000  # below this the host is as fast as a round trip to the device
 HOST_GROUP_MIN = 200_000     # below this numpy's argsort + gathers are as fast as the library's threaded counting sort
 RANDOM_CHUNKSIZE = 16_777_216  # values per generator call of from_random (the reference's CHUNKSIZE, readers.py:49)
+PATCH_METHODS = ("probe", "full")  # what patch_num= runs: kmeans_centers on a probe sample, or patches.py on all objects
 
 
 def nearest_center(xyz, centers_xyz, chunk: int = 1 << 18):
@@ -439,15 +440,21 @@ class Catalog(Mapping):
     @classmethod
     def from_arrays(cls, ra, dec, *, weights=None, redshifts=None, kappa=None, patch_centers=None, patch_ids=None,
                     patch_num: int | None = None, degrees: bool = True, cache_directory=None, overwrite: bool = False,
-                    probe_size: int = -1):
+                    probe_size: int = -1, patch_method: str = "probe"):
         """Build from plain arrays. One of ``patch_centers`` (nearest-centre assignment),
         ``patch_ids`` (pre-assigned, contiguous from 0) or ``patch_num`` (k-means) is required, with
-        that precedence (``PatchMode.determine``, catalog.py:95-167)."""
+        that precedence (``PatchMode.determine``, catalog.py:95-167). ``patch_method`` says which k-means ``patch_num``
+        runs: ``"probe"``, :func:`kmeans_centers` on a probe sample, or ``"full"``, the deterministic k-means of
+        :mod:`~yet_another_wizz_amd.patches` over all objects with the catalogue's weights (on the GPU when there is one);
+        it is ignored where centres or ids take precedence."""
+        if patch_method not in PATCH_METHODS:
+            raise ValueError(f"'patch_method' must be one of {PATCH_METHODS}, got {patch_method!r}")
         ra = np.asarray_chkfinite(ra, dtype=np.float64)
         dec = np.asarray_chkfinite(dec, dtype=np.float64)
         if degrees:  # datachunk.py:265-267
             ra, dec = np.deg2rad(ra), np.deg2rad(dec)
         centers = None
+        xyz = None
         if patch_centers is not None:
             if isinstance(patch_centers, Catalog):
                 centers = patch_centers.get_centers()
@@ -462,16 +469,22 @@ class Catalog(Mapping):
             if not isinstance(patch_num, (int, np.integer)):
                 raise TypeError("'patch_num' must be an integer")
             _check_patch_count(int(patch_num))
-            if probe_size < 10 * patch_num:
-                probe_size = int(100_000 * np.sqrt(patch_num))
-            step = max(1, len(ra) // probe_size)
-            x, y, z = radec_to_xyz(ra[::step], dec[::step])
-            centers = kmeans_centers(np.column_stack([x, y, z]), None if weights is None else np.asarray(weights)[::step],
-                                     int(patch_num))
+            if patch_method == "full":
+                from . import patches
+
+                xyz = radec_to_xyz(ra, dec)
+                centers = patches.centers_from_xyz(xyz, weights, int(patch_num))
+            else:
+                if probe_size < 10 * patch_num:
+                    probe_size = int(100_000 * np.sqrt(patch_num))
+                step = max(1, len(ra) // probe_size)
+                x, y, z = radec_to_xyz(ra[::step], dec[::step])
+                centers = kmeans_centers(np.column_stack([x, y, z]), None if weights is None else np.asarray(weights)[::step],
+                                         int(patch_num))
         num = None
-        xyz = None
         if centers is not None:
-            xyz = radec_to_xyz(ra, dec)
+            if xyz is None:
+                xyz = radec_to_xyz(ra, dec)
             patch_ids = nearest_center(xyz, centers.to_3d())
             num = len(centers)
         new = cls._from_columns(ra, dec, patch_ids=patch_ids, num_patches=num, weights=weights, redshifts=redshifts,
@@ -485,13 +498,13 @@ class Catalog(Mapping):
                        redshift_name: str | None = None, patch_centers=None, patch_name: str | None = None,
                        patch_num: int | None = None, kappa_name: str | None = None, degrees: bool = True,
                        overwrite: bool = False, progress: bool = False, max_workers: int | None = None,
-                       chunksize: int | None = None, probe_size: int = -1, **reader_kwargs):
+                       chunksize: int | None = None, probe_size: int = -1, patch_method: str = "probe", **reader_kwargs):
         """Same signature as ``yaw.Catalog.from_dataframe`` (catalog.py:980-1108). ``dataframe`` may
         be a pandas DataFrame or any mapping from column name to array. ``cache_directory`` may be
         ``None`` (nothing is written: the catalogue lives in memory and in HBM); a path gets a cache in
         the reference's on-disk format, readable by both packages (``overwrite`` as in the reference).
         ``kappa_name`` names a column of scalar-field values (convergence, a shear amplitude, ...) for
-        ``autocorrelate_scalar`` / ``crosscorrelate_scalar``."""
+        ``autocorrelate_scalar`` / ``crosscorrelate_scalar``. ``patch_method``: see :meth:`from_arrays`."""
         if patch_name is not None and not isinstance(patch_name, str):
             raise TypeError("'patch_name' must be a string")
 
@@ -503,6 +516,7 @@ class Catalog(Mapping):
             column(ra_name), column(dec_name), weights=column(weight_name), redshifts=column(redshift_name),
             kappa=column(kappa_name), patch_centers=patch_centers, patch_ids=column(patch_name) if use_ids else None, patch_num=patch_num,
             degrees=degrees, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size,
+            patch_method=patch_method,
         )
 
     @classmethod
@@ -530,7 +544,7 @@ class Catalog(Mapping):
     @classmethod
     def from_random(cls, cache_directory, generator, num_randoms: int, *, patch_centers=None, patch_num: int | None = None,
                     overwrite: bool = False, progress: bool = False, max_workers: int | None = None,
-                    chunksize: int | None = None, probe_size: int = -1):
+                    chunksize: int | None = None, probe_size: int = -1, patch_method: str = "probe"):
         """Same signature as ``yaw.Catalog.from_random`` (catalog.py:1245-1340): ``num_randoms`` points of ``generator``
         (a :class:`~yet_another_wizz_amd.randoms.BoxRandoms` or :class:`~yet_another_wizz_amd.randoms.HealPixRandoms`), drawn
         from its reseeded stream in calls of ``chunksize`` (default 16 777 216, readers.py:49) -- for a ``BoxRandoms`` the
@@ -539,7 +553,8 @@ class Catalog(Mapping):
         values), otherwise chunk by chunk on the host; ``dec = arcsin(y)`` is taken on the host either way.
         The columns then go through ``from_arrays``. ``patch_num`` runs this package's k-means (as ``from_dataframe``
         does), whose centres differ from the treecorr centres of the reference; pass ``patch_centers`` for the
-        reference's patches. ``progress`` and ``max_workers`` are accepted for compatibility and have no effect."""
+        reference's patches; ``patch_method``: see :meth:`from_arrays`. ``progress`` and ``max_workers`` are accepted for
+        compatibility and have no effect."""
         from .randoms import BoxRandoms, HealPixRandoms
 
         num = int(num_randoms)
@@ -573,20 +588,23 @@ class Catalog(Mapping):
             ra, dec, weights, redshifts = joined("ra"), joined("dec"), joined("weights"), joined("redshifts")
             route = "host"
         new = cls.from_arrays(ra, dec, weights=weights, redshifts=redshifts, patch_centers=patch_centers, patch_num=patch_num,
-                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size)
+                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size,
+                              patch_method=patch_method)
         new._random_route = route
         return new
 
     @classmethod
     def from_healpix_map(cls, cache_directory, values, *, weights=None, nested: bool = False, patch_centers=None,
-                         patch_num: int | None = None, overwrite: bool = False, probe_size: int = -1, chunksize: int | None = None):
+                         patch_num: int | None = None, overwrite: bool = False, probe_size: int = -1, chunksize: int | None = None,
+                         patch_method: str = "probe"):
         """A full-sky HEALPix scalar map (a convergence map, a y-map) as a catalogue: one object per unmasked pixel, at the
         pixel's centre, with the map's value as ``kappa`` and, with a weight / coverage map ``weights``, its weight. The
         maps hold ``12 nside^2`` values, ``nside`` a power of two up to 8192, in RING order unless ``nested``; which pixels are
         masked and the order of the objects are those of :func:`healpix.map_pixels <yet_another_wizz_amd.healpix.map_pixels>`.
         Large maps are compacted on the GPU when there is one (the same values, in passes of ``chunksize`` nested pixels);
         ``dec = arcsin(z)`` is taken on the host either way. The columns then go through ``from_arrays``: one of
-        ``patch_centers`` / ``patch_num`` is required, as for ``from_random``. The catalogue has no redshifts: it is the
+        ``patch_centers`` / ``patch_num`` is required, as for ``from_random`` (``patch_method``: see :meth:`from_arrays`; with
+        ``"full"`` the centres are jackknife regions of the map's footprint). The catalogue has no redshifts: it is the
         scalar side of ``crosscorrelate_scalar_map``."""
         from . import healpix
 
@@ -594,7 +612,8 @@ class Catalog(Mapping):
             raise ValueError("no patch method specified")
         (_, ra, z, kappa, w), route = healpix._map_pixels(values, weights, nested, int(chunksize or 0))
         new = cls.from_arrays(ra, np.arcsin(z), weights=w, kappa=kappa, patch_centers=patch_centers, patch_num=patch_num,
-                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size)
+                              degrees=False, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size,
+                              patch_method=patch_method)
         new._random_route = route
         return new
 

@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -216,6 +216,20 @@ def assign_patches(xyz, centers_xyz):
         x, y, z = (np.ascontiguousarray(xyz[:, a]) for a in range(3))
     ids = _lib.assign_patches(ctx, x, y, z, centers_xyz)
     return ids.astype(np.int64)
+
+
+def kmeans_open(x, y, z, weights=None, wscale: float = 0.0):
+    """The unit vectors (and weights) of a catalogue uploaded once for the full-catalogue k-means of ``patches.py``
+    (``yawhip_kmeans_open``) -> ``_lib.KMeans``, or ``None`` when no GPU / library is available: patch creation is
+    catalogue preparation, as ``assign_patches``, and ``patches.py`` then runs the same arithmetic with numpy. One device
+    does it."""
+    try:
+        if _lib.device_count() < 1:
+            return None
+        ctx = get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+    return _lib.KMeans(ctx, x, y, z, weights, wscale)
 
 
 def _random_context(generator):
