@@ -86,3 +86,65 @@ def test_upload_orders_segments_and_runs():
     exp, _ = oracle.count_jobs(cat, unk, jobs, t)
     assert np.array_equal(a, exp) and np.array_equal(b, exp) and exp.sum() > 1000
     ctx.close()
+
+
+# device_bytes of the catalogues below, in the order (upload_axis, scalar pair's plain one, its twin), right after the upload
+# and after one self count each. Measured at commit 2592561 ("Add full-catalogue k-means patch centres on the GPU"), the last
+# one whose units allocated and accounted by hand: whoever owns the memory, the accounting of an upload, of its strip layout
+# and of its merged triple runs stays what it was.
+STRIP_MICRO = 25000
+DEVICE_BYTES_AFTER_UPLOAD = (173280, 173280, 173280)
+DEVICE_BYTES_AFTER_COUNT = (481712, 481712, 481712)
+
+
+def _pinned_catalogue():
+    """2,000 unit vectors on a 0.2 rad cap around the x axis, 4 patches (quadrants), 3 redshift bins, weights and a scalar:
+    columns in (patch, bin) order and the segment offsets. Integer hashes instead of a generator: no stream that could
+    change, and unlike a lattice it has close pairs."""
+    n, P, B = 2000, 4, 3
+
+    def hashed(salt):  # uniform in [0, 1): a 32-bit integer mix of the object number
+        v = (np.arange(n, dtype=np.uint64) + np.uint64(salt)) & np.uint64(0xFFFFFFFF)
+        for _ in range(2):
+            v = ((v ^ (v >> np.uint64(16))) * np.uint64(0x45D9F3B)) & np.uint64(0xFFFFFFFF)
+        v ^= v >> np.uint64(16)
+        return v.astype(np.float64) / 2.0**32
+
+    r, a = 0.2 * np.sqrt(hashed(1000)), 2 * np.pi * hashed(5000)
+    ra, dec = r * np.cos(a), r * np.sin(a)
+    xyz = np.column_stack([np.cos(ra) * np.cos(dec), np.sin(ra) * np.cos(dec), np.sin(dec)])
+    seg = (2 * (ra >= 0) + (dec >= 0)).astype(np.int64) * B + (hashed(9000) * B).astype(np.int64)
+    order = np.argsort(seg, kind="stable")
+    x, y, z = (np.ascontiguousarray(xyz[order, k]) for k in range(3))
+    w = 0.5 + hashed(13000)[order]
+    kappa = 2.0 * hashed(17000)[order] - 1.0
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(seg, minlength=P * B))]).astype(np.int64)
+    assert np.all(np.diff(offsets) > 0) and offsets[-1] == n
+    return x, y, z, w, kappa, P, B, offsets
+
+
+def test_device_bytes_accounting_is_pinned():
+    from yet_another_wizz_amd import _lib
+
+    x, y, z, w, kappa, P, B, offsets = _pinned_catalogue()
+    ctx = _lib.Context(0)
+    # strips of 0.025: some 18 objects per (patch, bin, strip) run, so that the binned self count below goes through the
+    # per-segment strip layouts (SEG_STRIPS_MIN_RUN) and their merged triple runs -- both kinds of layout are built
+    plain = _lib.DeviceCatalog(ctx, x, y, z, w, P, B, offsets, strip_micro=STRIP_MICRO)
+    cat_n, cat_k = _lib.DeviceCatalog.upload_scalar(ctx, x, y, z, w, kappa, P, B, offsets, strip_micro=STRIP_MICRO)
+    cats = (plain, cat_n, cat_k)
+    after_upload = tuple(c.device_bytes for c in cats)
+    jobs = np.array([(p, q) for p in range(P) for q in range(P)], dtype=np.int32)
+    t = np.tile((2.0 * np.sin(0.5 * np.deg2rad(np.array([1.0, 9.0]) / 60.0))) ** 2, (B, 1))  # squared chords of 1' and 9'
+    merged, pairs = [], []
+    for c in cats:
+        _, sums, stats = _lib.count_pairs(ctx, c, c, jobs, t, kernel="band")
+        merged.append(stats.merged_triples)
+        pairs.append(int(np.count_nonzero(sums)))
+    after_count = tuple(c.device_bytes for c in cats)
+    ctx.close()
+    print("device_bytes after upload", after_upload, "after count", after_count, "merged_triples", merged, "slots hit", pairs)
+    assert min(pairs) > 0
+    assert merged == [1, 1, 1]  # the count streamed merged triple runs: they exist, and are part of the figures
+    assert after_upload == DEVICE_BYTES_AFTER_UPLOAD
+    assert after_count == DEVICE_BYTES_AFTER_COUNT

@@ -1970,7 +1970,7 @@ inline DevTab make_tab(const double *x, const double *y, const double *z, const 
 
 // One launch of a count kernel: its dynamic-LDS limit raised first where it needs more than 64 KiB.
 template <typename... Params, typename... Args>
-hipError_t launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+hipError_t launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args &...args) {
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -2142,14 +2142,13 @@ struct HostPlan {
     // device tables, in one allocation (d_in) made when the plan's table image is uploaded (Planner::tables): jobs / job records,
     // prefix, thresholds, pre-filter thresholds, window widths, float32 classes, layout table, and -- weighted calls -- the chunk
     // prefix of the slab reduction
-    unsigned char *d_in = nullptr;
+    DevPtr<unsigned char> d_in;
     int32_t *d_jobs = nullptr;
     int64_t *d_prefix = nullptr, *d_cprefix = nullptr;
     double *d_t = nullptr, *d_rwin = nullptr;
     float *d_dthr = nullptr, *d_ucap = nullptr, *d_thr32 = nullptr;
     DevTab *d_tabs = nullptr;
     int64_t n_chunks = 0;
-    ~HostPlan() { if (d_in) (void)hipFree(d_in); }
 };
 
 // Forget the plans that involve catalogue `c` (nullptr: all of them).
@@ -2670,7 +2669,7 @@ int Planner::tables() {
                 DevTab &tb = h_tabs[P.swap ? 3 + o : o];
                 tb = make_tab(st.x, st.y, st.z, st.w3, nullptr, st.off3, st.d_vbase, st.d_slo, st.d_tiles[tile_idx],
                               st.d_tile_rec[tile_idx], st.d_grid3, o, st.q3, st.q3_stride, st.idx3);
-                if (half_ok) h_tabs[3 + o].pos3 = (gi32p)b.pos3;  // (c1 == c2: the lane side's layout is the streamed one)
+                if (half_ok) h_tabs[3 + o].pos3 = (gi32p)(const int32_t *)b.pos3;  // (c1 == c2: the lane side's layout is the streamed one)
             }
         }
     } else {
@@ -2699,7 +2698,7 @@ int Planner::tables() {
     std::vector<unsigned char> image(off_in, 0);
     for (int i = 0; i < 9; ++i)
         if (bytes[i]) memcpy(image.data() + off[i], src[i], bytes[i]);
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&P.d_in), std::max<size_t>(off_in, 16)));
+    HIP_TRY(P.d_in.alloc(std::max<size_t>(off_in, 16)));
     HIP_TRY(hipMemcpy(P.d_in, image.data(), off_in, hipMemcpyHostToDevice));  // once per plan
     P.d_jobs = reinterpret_cast<int32_t *>(P.d_in + off[0]);
     P.d_prefix = reinterpret_cast<int64_t *>(P.d_in + off[1]);
@@ -2794,7 +2793,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     cs.n_out = P.n_out;
     if (P.empty) return YAWHIP_OK;
     if (P.split) return SPLIT_JOBS;
-    if (P.run_weighted) HIP_TRY(ctx->d_partials.reserve((size_t)std::max<int64_t>(P.n_items, 1) * P.slab));
+    if (P.run_weighted) HIP_TRY(reserve_call(ctx->d_partials, (size_t)std::max<int64_t>(P.n_items, 1) * P.slab));
     g_trace.mark("plan");
     // results: [counters][counts][sums] in one device buffer; counters and counts are zero when no call of the slot is in
     // flight (CallBufs::dirty; sums are always fully written), and k_call_tail brings back what was asked for
@@ -2835,10 +2834,10 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         // item list in segments (append_items): where the float32 band kernels consume what the strip builder keeps
         if (P.strip_items && (P.band32 || P.band_fine) && !job_work && ctx->item_segments)
             seg_cap = (unsigned long long)((bgrid + ITEM_SEGS - 1) / ITEM_SEGS) * (unsigned long long)bwg;
-        HIP_TRY(ctx->d_items.reserve(seg_cap ? (size_t)(seg_cap * ITEM_SEGS) : (size_t)n_pot));
+        HIP_TRY(reserve_call(ctx->d_items, seg_cap ? (size_t)(seg_cap * ITEM_SEGS) : (size_t)n_pot));
         unsigned char *kept_flags = nullptr;  // weighted runs of the culling builders: which potential items write a slab
         if (P.run_weighted && P.sweep) {
-            HIP_TRY(ctx->d_kept.reserve((size_t)n_pot));
+            HIP_TRY(reserve_call(ctx->d_kept, (size_t)n_pot));
             HIP_TRY(hipMemsetAsync(ctx->d_kept.ptr, 0, (size_t)n_pot, ctx->stream));
             kept_flags = ctx->d_kept.ptr;
         }
@@ -2872,7 +2871,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
         }
     }
     if (job_work) {  // cost estimate only: evaluated pairs per job from the item list, no counting
-        HIP_TRY(ctx->d_jobwork.reserve((size_t)n_jobs));
+        HIP_TRY(reserve_call(ctx->d_jobwork, (size_t)n_jobs));
         HIP_TRY(hipMemsetAsync(ctx->d_jobwork.ptr, 0, sizeof(unsigned long long) * (size_t)n_jobs, ctx->stream));
         if (n_pot > 0) {
             hipLaunchKernelGGL(k_item_work, dim3((unsigned)((n_pot + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_items.ptr,
@@ -2888,7 +2887,7 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     // potential item of every output slot, chunk prefix = first chunk of every output slot
     auto reduce_partials = [&]() -> hipError_t {
         const int64_t n_oslots = P.n_pslots, values = P.slab, n_chunks = P.n_chunks;
-        hipError_t er = ctx->d_chunk_sums.reserve((size_t)std::max<int64_t>(n_chunks, 1) * values);
+        hipError_t er = reserve_call(ctx->d_chunk_sums, (size_t)std::max<int64_t>(n_chunks, 1) * values);
         if (er != hipSuccess) return er;
         const int thr = 256;
         const bool all_kept = !(P.run_weighted && P.sweep);
@@ -3058,8 +3057,9 @@ int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalo
     static_assert(N_CTR * sizeof(unsigned long long) % 16 == 0 && (CTR_DONE + 2) * sizeof(unsigned long long) <= N_CTR * sizeof(unsigned long long),
                   "the tail's words lie inside the counter block");
     if (fetch / 16 > 0xffffffffull) return fail(YAWHIP_ERR_INVALID, "result block too large (%zu bytes)", fetch);
+    unsigned char *const out_d = ctx->out.d;
     hipLaunchKernelGGL(k_call_tail, dim3(std::min((n_copy + TAIL_WG - 1) / TAIL_WG, TAIL_MAX_GRID)), dim3(TAIL_WG), 0, ctx->stream,
-                       reinterpret_cast<uint4 *>(ctx->out.d), reinterpret_cast<uint4 *>(ctx->out.h), n_copy, n_clean,
+                       reinterpret_cast<uint4 *>(out_d), reinterpret_cast<uint4 *>(ctx->out.h), n_copy, n_clean,
                        (unsigned long long)cs.seq);
     HIP_TRY(hipGetLastError());
     ++launches;

@@ -136,12 +136,13 @@ int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins
         if (fine_factors) memcpy(ctx->comb.h + b_slices, fine_factors, sizeof(double) * (size_t)n_bins * nf);
         HIP_TRY(hipMemcpyAsync(ctx->comb.d, ctx->comb.h, b_slices + b_fact, hipMemcpyHostToDevice, ctx->stream));
         ds.h_comb_off = b_slices + b_fact;
-        double *d_comb = reinterpret_cast<double *>(ctx->comb.d + ds.h_comb_off);
+        unsigned char *const comb_d = ctx->comb.d;
+        double *d_comb = reinterpret_cast<double *>(comb_d + ds.h_comb_off);
         if (ds.cs.pending && ds.n_comb > 0) {
             hipLaunchKernelGGL(k_combine_scales, dim3((unsigned)((ds.n_comb + 255) / 256)), dim3(256), 0, ctx->stream,
                                ctx->d_counts, ctx->d_sums, ds.weighted ? 1 : 0, (int64_t)r.n_jobs, n_bins, nf, n_scales,
-                               reinterpret_cast<const int32_t *>(ctx->comb.d),
-                               fine_factors ? reinterpret_cast<const double *>(ctx->comb.d + b_slices) : nullptr, d_comb);
+                               reinterpret_cast<const int32_t *>(comb_d),
+                               fine_factors ? reinterpret_cast<const double *>(comb_d + b_slices) : nullptr, d_comb);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(ctx->comb.h + ds.h_comb_off, d_comb, sizeof(double) * (size_t)ds.n_comb, hipMemcpyDeviceToHost, ctx->stream));
         }
@@ -302,8 +303,8 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
             return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: row index %d outside [0, %lld)", row_index[j], (long long)n_rows_total);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n_full = (size_t)n_rows_total * (size_t)row + 1;  // + 1: the caller's status element
-    HIP_TRY(ctx->d_full.reserve(n_full));
-    HIP_TRY(ctx->d_rowidx.reserve((size_t)std::max(n_jobs, 1)));
+    HIP_TRY(reserve_call(ctx->d_full, n_full));
+    HIP_TRY(reserve_call(ctx->d_rowidx, (size_t)std::max(n_jobs, 1)));
     CallState cs;
     // (the rows stay on the device: only the statistics counters are fetched)
     int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, true, nullptr, cs, /*fetch_results=*/false);

@@ -8,7 +8,12 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "yawhip_devmem.h"
+
 namespace yawpix {
+
+using yawhip_detail::DevBuf;
+using yawhip_detail::DevPtr;
 
 constexpr int MAX_ORDER = 13;                         // a float64 map of order 14 is 25 GB
 constexpr int64_t DEFAULT_CHUNK = (int64_t)1 << 24;   // objects per pass when the caller gives 0
@@ -16,25 +21,22 @@ constexpr int64_t MAX_CHUNK = (int64_t)1 << 28;       // larger chunk sizes are 
 
 // Device buffers of the call (grow-only, owned by the caller's context).
 struct Workspace {
-    double *cols = nullptr;      // [3][chunk_cap]: phi, z, w of one pass
-    int64_t *pix = nullptr;      // [chunk_cap] pixels of one pass
-    uint32_t *keys = nullptr;    // [2][chunk_cap] sort keys, in and out (weighted maps)
-    double *w_sorted = nullptr;  // [chunk_cap]
+    DevPtr<double> cols;         // [3][chunk_cap]: phi, z, w of one pass
+    DevPtr<int64_t> pix;         // [chunk_cap] pixels of one pass
+    DevPtr<uint32_t> keys;       // [2][chunk_cap] sort keys, in and out (weighted maps)
+    DevPtr<double> w_sorted;     // [chunk_cap]
     size_t chunk_cap = 0;
     bool sort_bufs = false;      // keys and w_sorted are allocated for chunk_cap
-    void *tmp = nullptr;         // rocPRIM's temporary storage
-    size_t tmp_bytes = 0;
-    double *map = nullptr;       // [map_cap] the map: uint64 counters while objects are counted, float64 at the end
-    size_t map_cap = 0;
+    DevBuf<unsigned char> tmp;   // rocPRIM's temporary storage
+    DevBuf<double> map;          // the map: uint64 counters while objects are counted, float64 at the end
     // yawhip_healpix_pixels
-    double *src = nullptr;       // [src_cap] the uploaded scalar map, then (with a weight map) the weight map behind it
-    size_t src_cap = 0;
-    double *sel = nullptr;       // [4][sel_cap]: phi, z, kappa, w of the selected pixels of one pass
-    int64_t *sel_pix = nullptr;  // [sel_cap] their pixel numbers
-    int64_t *wg_counts = nullptr;  // [2][sel_cap / 256 + 2]: selected pixels per workgroup of a pass, and their exclusive scan
+    DevBuf<double> src;          // the uploaded scalar map, then (with a weight map) the weight map behind it
+    DevPtr<double> sel;          // [4][sel_cap]: phi, z, kappa, w of the selected pixels of one pass
+    DevPtr<int64_t> sel_pix;     // [sel_cap] their pixel numbers
+    DevPtr<int64_t> wg_counts;   // [2][sel_cap / 256 + 2]: selected pixels per workgroup of a pass, and their exclusive scan
     size_t sel_cap = 0;
     size_t bytes() const;
-    void release();
+    void release() { *this = Workspace{}; }
 };
 
 // One call (see yawhip_healpix_map in include/yawhip.h for the meaning of every field).

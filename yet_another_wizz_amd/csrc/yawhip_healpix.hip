@@ -37,56 +37,18 @@
 #include <rocprim/rocprim.hpp>
 
 #include "yawhip_healpix.h"
+#include "yawhip_healpix_math.h"
 
 namespace yawpix {
+
+using yawhip_detail::grid_for;
 
 namespace {
 
 constexpr int WG = 256;
-constexpr double TWOPI = 0x1.921fb54442d18p+2;   // numpy's 2 pi
-constexpr double HALFPI = 0x1.921fb54442d18p+0;  // numpy's pi / 2
 constexpr double TWOTHIRD = 2.0 / 3.0;
 
 __device__ __forceinline__ int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
-
-// bits 0 .. 13 of v moved to the even positions 0, 2, .. 26
-__device__ __forceinline__ int64_t spread_bits(int64_t v) {
-    uint64_t x = (uint64_t)v;
-    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-    x = (x | (x << 2)) & 0x3333333333333333ull;
-    x = (x | (x << 1)) & 0x5555555555555555ull;
-    return (int64_t)x;
-}
-
-// Where the pixel (face, ix, iy) of `order` lies in the ring scheme: the integer steps of randoms._ring_position.
-struct RingPos {
-    int64_t jr, nr, kshift, jp;  // ring (1 .. 4 nside - 1 from the north), its pixels per quadrant, 1 on belt rings that start at
-    bool north, south;           // phi = 0, position in the ring (1 .. 4 nr); the caps
-};
-
-__device__ __forceinline__ RingPos ring_position(int order, int64_t face, int64_t ix, int64_t iy) {
-    const int64_t nside = (int64_t)1 << order;
-    const int64_t jrll = 2 + (face >> 2);                                          // 2 2 2 2 3 3 3 3 4 4 4 4
-    const int64_t jpll = (int64_t)((0x753164207531ull >> (4 * (face & 15))) & 7);  // 1 3 5 7 0 2 4 6 1 3 5 7
-    RingPos r;
-    r.jr = (jrll << order) - ix - iy - 1;
-    r.north = r.jr < nside, r.south = r.jr > 3 * nside;
-    r.nr = r.north ? r.jr : (r.south ? 4 * nside - r.jr : nside);
-    r.kshift = (r.north || r.south) ? 0 : ((r.jr - nside) & 1);
-    r.jp = (jpll * r.nr + ix - iy + 1 + r.kshift) / 2;  // the sum is even
-    if (r.jp > 4 * nside) r.jp -= 4 * nside;
-    if (r.jp < 1) r.jp += 4 * nside;
-    return r;
-}
-
-// Ring-scheme number of a pixel of `order` at `r`: the integer steps of randoms.nest2ring.
-__device__ __forceinline__ int64_t ring_number(int order, const RingPos &r) {
-    const int64_t nside = (int64_t)1 << order;
-    if (r.north) return 2 * r.jr * (r.jr - 1) + r.jp - 1;
-    if (r.south) return 12 * nside * nside - 2 * r.nr * (r.nr + 1) + r.jp - 1;
-    return 2 * nside * (nside - 1) + (r.jr - nside) * (4 * nside) + r.jp - 1;
-}
 
 // Pixel of `order` that holds (phi, z); -1 for a non-finite phi or z, or |z| > 1. The float64 steps of healpix.py.
 __device__ __forceinline__ int64_t loc2pix(int order, int nested, double phi, double z) {
@@ -161,17 +123,6 @@ __global__ __launch_bounds__(WG) void k_counts_to_f64(int64_t npix, double *map)
 constexpr double UNSEEN = -1.6375e30;  // healpy's sentinel of a pixel without data
 constexpr int WAVES = WG / 64;
 
-// every second bit of v (bits 0, 2, 4, ...), packed
-__device__ __forceinline__ int64_t even_bits(uint64_t v) {
-    v &= 0x5555555555555555ull;
-    v = (v | (v >> 1)) & 0x3333333333333333ull;
-    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
-    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
-    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
-    v = (v | (v >> 16)) & 0x00000000ffffffffull;
-    return (int64_t)v;
-}
-
 // The maps on the device and the nested pixels [q0, q_end) of one pass.
 struct PixelPass {
     const double *__restrict__ values;
@@ -179,11 +130,6 @@ struct PixelPass {
     int order, nested;
     int64_t q0, q_end;
 };
-
-__device__ __forceinline__ RingPos ring_position_nest(int order, int64_t q) {
-    const uint64_t low = (uint64_t)q & (((uint64_t)1 << (2 * order)) - 1);
-    return ring_position(order, q >> (2 * order), even_bits(low), even_bits(low >> 1));
-}
 
 // The selection rule on entry `src` of the maps; v and wt are the values read (wt only with a weight map).
 __device__ __forceinline__ bool pixel_selected(const PixelPass &m, int64_t src, double &v, double &wt) {
@@ -220,7 +166,6 @@ __global__ __launch_bounds__(WG) void k_select_write(PixelPass m, double fact1, 
                                                      double *__restrict__ kappa, double *__restrict__ w) {
     __shared__ int s_cnt[WAVES];
     const int64_t q = m.q0 + (int64_t)blockIdx.x * WG + threadIdx.x;
-    const int64_t nside = (int64_t)1 << m.order;
     bool keep = false;
     int64_t src = 0;
     double v = 0.0, wt = 0.0;
@@ -238,23 +183,10 @@ __global__ __launch_bounds__(WG) void k_select_write(PixelPass m, double fact1, 
     int64_t at = base[blockIdx.x] + __popcll(mask & (((unsigned long long)1 << lane) - 1));
     for (int k = 0; k < wave; ++k) at += s_cnt[k];
     if (at >= cap) return;  // (cannot happen: the counts come from the same predicate on the same maps)
-    // the float64 steps of randoms.pix2loc_nest, each rounded on its own
-    const double nrf = (double)r.nr;
-    const double tmp = nrf * nrf * fact2;
     ipix[at] = src;
-    z[at] = r.north ? 1.0 - tmp : (r.south ? tmp - 1.0 : (double)(2 * nside - r.jr) * fact1);
-    phi[at] = ((double)r.jp - (double)(r.kshift + 1) * 0.5) * (HALFPI / nrf);
+    pixel_centre(m.order, r, fact1, fact2, phi[at], z[at]);
     kappa[at] = v;
     if (w) w[at] = wt;
-}
-
-inline unsigned grid_for(int64_t n) { return (unsigned)((n + WG - 1) / WG); }
-
-template <typename T>
-hipError_t regrow(T *&p, size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T));
 }
 
 hipError_t reserve(Workspace &ws, size_t chunk, bool sort_bufs, size_t npix) {
@@ -262,46 +194,28 @@ hipError_t reserve(Workspace &ws, size_t chunk, bool sort_bufs, size_t npix) {
     if (chunk > ws.chunk_cap || (sort_bufs && !ws.sort_bufs)) {
         const size_t want = std::max(chunk, ws.chunk_cap);
         ws.chunk_cap = 0, ws.sort_bufs = false;
-        e = regrow(ws.cols, 3 * want);
-        if (e == hipSuccess) e = regrow(ws.pix, want);
-        if (e == hipSuccess && sort_bufs) e = regrow(ws.keys, 2 * want);
-        if (e == hipSuccess && sort_bufs) e = regrow(ws.w_sorted, want);
+        const size_t want1 = std::max<size_t>(want, 1);  // (an empty pass still has its buffers)
+        e = ws.cols.alloc(3 * want1);
+        if (e == hipSuccess) e = ws.pix.alloc(want1);
+        if (e == hipSuccess && sort_bufs) e = ws.keys.alloc(2 * want1);
+        if (e == hipSuccess && sort_bufs) e = ws.w_sorted.alloc(want1);
         if (e != hipSuccess) return e;
         ws.chunk_cap = want, ws.sort_bufs = sort_bufs;
     }
-    if (npix > ws.map_cap) {
-        ws.map_cap = 0;
-        e = regrow(ws.map, npix);
-        if (e == hipSuccess) ws.map_cap = npix;
-    }
-    return e;
+    return ws.map.reserve(npix);
 }
 
-hipError_t reserve_tmp(Workspace &ws, size_t bytes) {
-    if (bytes <= ws.tmp_bytes) return hipSuccess;
-    if (ws.tmp) (void)hipFree(ws.tmp);
-    ws.tmp = nullptr;
-    ws.tmp_bytes = 0;
-    const size_t want = bytes + bytes / 8 + 4096;
-    const hipError_t e = hipMalloc(&ws.tmp, want);
-    if (e == hipSuccess) ws.tmp_bytes = want;
-    return e;
-}
+hipError_t reserve_tmp(Workspace &ws, size_t bytes) { return ws.tmp.reserve(bytes, bytes / 8 + 4096); }
 
 // Buffers of yawhip_healpix_pixels: the uploaded maps (`src_count` values) and the outputs of a pass of `chunk` pixels.
 hipError_t reserve_pixels(Workspace &ws, size_t src_count, size_t chunk) {
-    hipError_t e = hipSuccess;
-    if (src_count > ws.src_cap) {
-        ws.src_cap = 0;
-        e = regrow(ws.src, src_count);
-        if (e != hipSuccess) return e;
-        ws.src_cap = src_count;
-    }
+    hipError_t e = ws.src.reserve(src_count);
+    if (e != hipSuccess) return e;
     if (chunk > ws.sel_cap) {
         ws.sel_cap = 0;
-        e = regrow(ws.sel, 4 * chunk);
-        if (e == hipSuccess) e = regrow(ws.sel_pix, chunk);
-        if (e == hipSuccess) e = regrow(ws.wg_counts, 2 * (chunk / WG + 2));
+        e = ws.sel.alloc(4 * chunk);
+        if (e == hipSuccess) e = ws.sel_pix.alloc(chunk);
+        if (e == hipSuccess) e = ws.wg_counts.alloc(2 * (chunk / WG + 2));
         if (e != hipSuccess) return e;
         ws.sel_cap = chunk;
     }
@@ -311,23 +225,9 @@ hipError_t reserve_pixels(Workspace &ws, size_t src_count, size_t chunk) {
 }  // namespace
 
 size_t Workspace::bytes() const {
-    return chunk_cap * (3 * sizeof(double) + sizeof(int64_t) + (sort_bufs ? 2 * sizeof(uint32_t) + sizeof(double) : 0)) + tmp_bytes +
-           map_cap * sizeof(double) + src_cap * sizeof(double) +
+    return chunk_cap * (3 * sizeof(double) + sizeof(int64_t) + (sort_bufs ? 2 * sizeof(uint32_t) + sizeof(double) : 0)) + tmp.cap +
+           map.cap * sizeof(double) + src.cap * sizeof(double) +
            (sel_cap ? sel_cap * (4 * sizeof(double) + sizeof(int64_t)) + 2 * (sel_cap / WG + 2) * sizeof(int64_t) : 0);
-}
-
-void Workspace::release() {
-    if (cols) (void)hipFree(cols);
-    if (pix) (void)hipFree(pix);
-    if (keys) (void)hipFree(keys);
-    if (w_sorted) (void)hipFree(w_sorted);
-    if (tmp) (void)hipFree(tmp);
-    if (map) (void)hipFree(map);
-    if (src) (void)hipFree(src);
-    if (sel) (void)hipFree(sel);
-    if (sel_pix) (void)hipFree(sel_pix);
-    if (wg_counts) (void)hipFree(wg_counts);
-    *this = Workspace{};
 }
 
 hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c) {
@@ -338,8 +238,9 @@ hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c) {
     if (e != hipSuccess) return e;
     double *d_phi = ws.cols, *d_z = ws.cols + ws.chunk_cap, *d_w = ws.cols + 2 * ws.chunk_cap;
     uint32_t *keys_in = ws.keys, *keys_out = ws.keys + ws.chunk_cap;
+    double *map = ws.map.ptr, *w_sorted = ws.w_sorted;  // (plain pointers: rocPRIM deduces its iterator types from the arguments)
     const unsigned end_bit = (unsigned)(2 * c.order + 4);
-    if (c.map_out) e = hipMemsetAsync(ws.map, 0, (size_t)npix * sizeof(double), stream);
+    if (c.map_out) e = hipMemsetAsync(map, 0, (size_t)npix * sizeof(double), stream);
     for (int64_t c0 = 0; c0 < c.n && e == hipSuccess; c0 += chunk) {
         const int64_t k = std::min(chunk, c.n - c0);
         e = hipMemcpyAsync(d_phi, c.phi + c0, (size_t)k * sizeof(double), hipMemcpyHostToDevice, stream);
@@ -348,18 +249,18 @@ hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c) {
         if (e != hipSuccess) break;
         hipLaunchKernelGGL(k_pixels, dim3(grid_for(k)), dim3(WG), 0, stream, k, d_phi, d_z, (int)c.order, (int)c.nested, npix,
                            c.pix_out ? ws.pix : nullptr,
-                           c.map_out && !weighted ? reinterpret_cast<unsigned long long *>(ws.map) : nullptr,
+                           c.map_out && !weighted ? reinterpret_cast<unsigned long long *>(map) : nullptr,
                            weighted ? keys_in : nullptr);
         e = hipGetLastError();
         if (e == hipSuccess && weighted) {
             size_t bytes = 0;
-            e = rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, d_w, ws.w_sorted, (size_t)k, 0, end_bit, stream);
+            e = rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, d_w, w_sorted, (size_t)k, 0, end_bit, stream);
             if (e == hipSuccess) e = reserve_tmp(ws, bytes);
             if (e != hipSuccess) break;
-            bytes = ws.tmp_bytes;
-            e = rocprim::radix_sort_pairs(ws.tmp, bytes, keys_in, keys_out, d_w, ws.w_sorted, (size_t)k, 0, end_bit, stream);
+            bytes = ws.tmp.cap;
+            e = rocprim::radix_sort_pairs(ws.tmp.ptr, bytes, keys_in, keys_out, d_w, w_sorted, (size_t)k, 0, end_bit, stream);
             if (e != hipSuccess) break;
-            hipLaunchKernelGGL(k_sum_runs, dim3(grid_for(k)), dim3(WG), 0, stream, k, keys_out, ws.w_sorted, (uint32_t)npix, ws.map);
+            hipLaunchKernelGGL(k_sum_runs, dim3(grid_for(k)), dim3(WG), 0, stream, k, keys_out, w_sorted, (uint32_t)npix, map);
             e = hipGetLastError();
         }
         if (e == hipSuccess && c.pix_out)
@@ -367,10 +268,10 @@ hipError_t healpix_map(Workspace &ws, hipStream_t stream, const MapCall &c) {
     }
     if (e == hipSuccess && c.map_out) {
         if (!weighted) {
-            hipLaunchKernelGGL(k_counts_to_f64, dim3(grid_for(npix)), dim3(WG), 0, stream, npix, ws.map);
+            hipLaunchKernelGGL(k_counts_to_f64, dim3(grid_for(npix)), dim3(WG), 0, stream, npix, map);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(c.map_out, ws.map, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.map_out, map, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);  // nothing of this call is left in flight
     else (void)hipStreamSynchronize(stream);
@@ -383,7 +284,7 @@ hipError_t healpix_pixels(Workspace &ws, hipStream_t stream, const PixelsCall &c
     const int64_t chunk = std::min(c.chunksize, npix);
     hipError_t e = reserve_pixels(ws, (size_t)npix * (c.weights ? 2 : 1), (size_t)chunk);
     if (e != hipSuccess) return e;
-    double *d_values = ws.src, *d_weights = c.weights ? ws.src + npix : nullptr;
+    double *d_values = ws.src.ptr, *d_weights = c.weights ? ws.src.ptr + npix : nullptr;
     double *d_phi = ws.sel, *d_z = ws.sel + ws.sel_cap, *d_kappa = ws.sel + 2 * ws.sel_cap, *d_w = c.weights ? ws.sel + 3 * ws.sel_cap : nullptr;
     int64_t *counts = ws.wg_counts, *base = ws.wg_counts + (ws.sel_cap / WG + 2);
     const double fact2 = 4.0 / (double)npix;                              // as randoms.pix2loc_nest
@@ -403,8 +304,8 @@ hipError_t healpix_pixels(Workspace &ws, hipStream_t stream, const PixelsCall &c
         e = rocprim::exclusive_scan(nullptr, bytes, counts, base, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), stream);
         if (e == hipSuccess) e = reserve_tmp(ws, bytes);
         if (e != hipSuccess) break;
-        bytes = ws.tmp_bytes;
-        e = rocprim::exclusive_scan(ws.tmp, bytes, counts, base, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), stream);
+        bytes = ws.tmp.cap;
+        e = rocprim::exclusive_scan(ws.tmp.ptr, bytes, counts, base, (int64_t)0, (size_t)nb + 1, rocprim::plus<int64_t>(), stream);
         int64_t total = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&total, base + nb, sizeof(int64_t), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);

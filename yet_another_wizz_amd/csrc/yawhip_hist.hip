@@ -23,6 +23,7 @@
 #include <cstring>
 #include <vector>
 
+#include "yawhip_devmem.h"
 #include "yawhip_hist.h"
 
 namespace yawhist {
@@ -129,15 +130,6 @@ hipError_t launch_tiles(hipStream_t stream, unsigned n_tiles, const double *z, c
     return launch_tiles<WEIGHTED, false, false>(stream, n_tiles, z, w, tiles, edges, n_edges, closed_right, partial);
 }
 
-template <typename T>
-struct DevArray {
-    T *p = nullptr;
-    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)); }
-    ~DevArray() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 
 hipError_t redshift_histogram(hipStream_t stream, const HistCall &c) {
@@ -149,8 +141,9 @@ hipError_t redshift_histogram(hipStream_t stream, const HistCall &c) {
     const int64_t chunk = std::min<int64_t>((int64_t)1 << c.chunk_log2, c.n);
     const int64_t batch_max = std::max<int64_t>(1, std::min<int64_t>(BATCH_TILES_MAX, PARTIAL_BUDGET / ((int64_t)n_bins * 8)));
 
-    DevArray<double> d_z, d_w, d_edges, d_partial, d_run_out;
-    DevArray<int2> d_tiles, d_runs;
+    using yawhip_detail::DevPtr;  // (no count below is zero: n, n_edges, n_bins and batch_max are all >= 1 here)
+    DevPtr<double> d_z, d_w, d_edges, d_partial, d_run_out;
+    DevPtr<int2> d_tiles, d_runs;
     hipError_t e = d_z.alloc((size_t)chunk);
     if (e == hipSuccess && weighted) e = d_w.alloc((size_t)chunk);
     if (e == hipSuccess) e = d_edges.alloc((size_t)c.n_edges);
@@ -158,7 +151,7 @@ hipError_t redshift_histogram(hipStream_t stream, const HistCall &c) {
     if (e == hipSuccess) e = d_run_out.alloc((size_t)batch_max * n_bins);
     if (e == hipSuccess) e = d_tiles.alloc((size_t)batch_max);
     if (e == hipSuccess) e = d_runs.alloc((size_t)batch_max);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_edges.p, c.edges, (size_t)c.n_edges * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_edges, c.edges, (size_t)c.n_edges * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return e;
 
     std::vector<int2> tiles, runs;
@@ -167,9 +160,9 @@ hipError_t redshift_histogram(hipStream_t stream, const HistCall &c) {
     int32_t p_first = 0;  // first patch that ends after the current chunk's start
     for (int64_t c0 = 0; c0 < c.n && e == hipSuccess; c0 += chunk) {
         const int64_t c1 = std::min(c.n, c0 + chunk);
-        e = hipMemcpyAsync(d_z.p, c.z + c0, (size_t)(c1 - c0) * sizeof(double), hipMemcpyHostToDevice, stream);
+        e = hipMemcpyAsync(d_z, c.z + c0, (size_t)(c1 - c0) * sizeof(double), hipMemcpyHostToDevice, stream);
         if (e == hipSuccess && weighted)
-            e = hipMemcpyAsync(d_w.p, c.w + c0, (size_t)(c1 - c0) * sizeof(double), hipMemcpyHostToDevice, stream);
+            e = hipMemcpyAsync(d_w, c.w + c0, (size_t)(c1 - c0) * sizeof(double), hipMemcpyHostToDevice, stream);
         // tiles of this chunk: the pieces of every patch it overlaps, cut into TILE objects
         tiles.clear();
         tile_patch.clear();
@@ -193,21 +186,21 @@ hipError_t redshift_histogram(hipStream_t stream, const HistCall &c) {
                 runs.back().y = (int)(t - t0 + 1);
             }
             const unsigned n_tiles = (unsigned)(t1 - t0), n_runs = (unsigned)runs.size();
-            e = hipMemcpyAsync(d_tiles.p, tiles.data() + t0, n_tiles * sizeof(int2), hipMemcpyHostToDevice, stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_runs.p, runs.data(), n_runs * sizeof(int2), hipMemcpyHostToDevice, stream);
+            e = hipMemcpyAsync(d_tiles, tiles.data() + t0, n_tiles * sizeof(int2), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_runs, runs.data(), n_runs * sizeof(int2), hipMemcpyHostToDevice, stream);
             if (e == hipSuccess && n_bins > HIST_LDS_BINS)  // rows the workgroups add into
-                e = hipMemsetAsync(d_partial.p, 0, (size_t)n_tiles * n_bins * sizeof(double), stream);
+                e = hipMemsetAsync(d_partial, 0, (size_t)n_tiles * n_bins * sizeof(double), stream);
             if (e == hipSuccess)
-                e = weighted ? launch_tiles<true>(stream, n_tiles, d_z.p, d_w.p, d_tiles.p, d_edges.p, c.n_edges, c.closed_right, d_partial.p)
-                             : launch_tiles<false>(stream, n_tiles, d_z.p, nullptr, d_tiles.p, d_edges.p, c.n_edges, c.closed_right, d_partial.p);
+                e = weighted ? launch_tiles<true>(stream, n_tiles, d_z, d_w, d_tiles, d_edges, c.n_edges, c.closed_right, d_partial)
+                             : launch_tiles<false>(stream, n_tiles, d_z, nullptr, d_tiles, d_edges, c.n_edges, c.closed_right, d_partial);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_hist_combine, dim3((unsigned)((n_bins + WG - 1) / WG), n_runs), dim3(WG), 0, stream, d_partial.p, d_runs.p,
-                                   n_bins, (int)(!weighted && n_bins > HIST_LDS_BINS), d_run_out.p);
+                hipLaunchKernelGGL(k_hist_combine, dim3((unsigned)((n_bins + WG - 1) / WG), n_runs), dim3(WG), 0, stream, d_partial, d_runs,
+                                   n_bins, (int)(!weighted && n_bins > HIST_LDS_BINS), d_run_out);
                 e = hipGetLastError();
             }
             run_out.resize((size_t)n_runs * n_bins);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(run_out.data(), d_run_out.p, run_out.size() * sizeof(double), hipMemcpyDeviceToHost, stream);
+                e = hipMemcpyAsync(run_out.data(), d_run_out, run_out.size() * sizeof(double), hipMemcpyDeviceToHost, stream);
             if (e == hipSuccess) e = hipStreamSynchronize(stream);
             if (e != hipSuccess) break;
             for (unsigned r = 0; r < n_runs; ++r) {  // runs in order: a patch's pieces are added in object order

@@ -356,13 +356,10 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     std::vector<int64_t> h_poff((size_t)n_groups + 1);
     for (int g = 0; g <= n_groups; ++g) h_poff[(size_t)g] = seg ? c->h_off[(size_t)g] : c->h_off[(size_t)g * c->nb];
     const size_t col = (size_t)std::max<int64_t>(n, 1) * sizeof(double) + 16;  // + 16: the band kernel's 16-byte loads may touch the bytes behind the last element
-    uint32_t *perm = nullptr, *perm2 = nullptr, *run = nullptr, *run_sorted = nullptr;
-    int32_t *gidx = nullptr, *lohi = nullptr;
-    int64_t *poff = nullptr;
+    DevPtr<uint32_t> perm, perm2, run, run_sorted;  // sort scratch: freed on the way out
+    DevPtr<int32_t> gidx, lohi;
+    DevPtr<int64_t> poff;
     auto bail = [&](hipError_t err, const char *what) {
-        for (void *q : {(void *)perm, (void *)perm2, (void *)run, (void *)run_sorted, (void *)gidx, (void *)lohi, (void *)poff})
-            if (q) (void)hipFree(q);
-        if (err == hipSuccess) return (int)YAWHIP_OK;
         L.release();
         return fail(err == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "strip layout (%s) failed: %s", what,
                     hipGetErrorString(err));
@@ -371,13 +368,13 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     std::vector<int32_t> h_lohi((size_t)2 * n_groups);
     for (int g = 0; g < n_groups; ++g) { h_lohi[(size_t)2 * g] = INT32_MAX; h_lohi[(size_t)2 * g + 1] = INT32_MIN; }
     const size_t n1 = (size_t)std::max<int64_t>(n, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&poff), (size_t)(n_groups + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&lohi), (size_t)2 * n_groups * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&gidx), n1 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm2), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&run), n1 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&run_sorted), n1 * sizeof(uint32_t));
+    hipError_t e = poff.alloc((size_t)(n_groups + 1));
+    if (e == hipSuccess) e = lohi.alloc((size_t)2 * n_groups);
+    if (e == hipSuccess) e = gidx.alloc(n1);
+    if (e == hipSuccess) e = perm.alloc(n1);
+    if (e == hipSuccess) e = perm2.alloc(n1);
+    if (e == hipSuccess) e = run.alloc(n1);
+    if (e == hipSuccess) e = run_sorted.alloc(n1);
     if (e == hipSuccess)
         e = hipMemcpyAsync(poff, h_poff.data(), (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
@@ -401,8 +398,8 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     if (n_runs >= (1ll << 31)) return bail(hipErrorInvalidValue, "too many strip runs");
     int run_bits = 1;
     while ((1ll << run_bits) < n_runs) ++run_bits;
-    e = hipMalloc(reinterpret_cast<void **>(&L.d_vbase), (size_t)(n_groups + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_slo), (size_t)std::max(n_groups, 1) * sizeof(int64_t));
+    e = L.d_vbase.alloc((size_t)(n_groups + 1));
+    if (e == hipSuccess) e = L.d_slo.alloc((size_t)std::max(n_groups, 1));
     if (e == hipSuccess)
         e = hipMemcpyAsync(L.d_vbase, vbase.data(), (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
@@ -414,15 +411,15 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     hipLaunchKernelGGL(k_run_of, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm, gidx, poff, n_groups, L.d_vbase, L.d_slo, run);
     e = yawsort::sort_runs(ctx->sort_ws, ctx->stream, n, run, perm, run_bits, perm2, run_sorted);
     if (e != hipSuccess) return bail(e, "run sort");
-    e = hipMalloc(reinterpret_cast<void **>(&L.x), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.y), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.z), col);
-    if (e == hipSuccess && c->w) e = hipMalloc(reinterpret_cast<void **>(&L.w), col);
-    if (e == hipSuccess && want_bins) e = hipMalloc(reinterpret_cast<void **>(&L.k), n1 * sizeof(int32_t) + 16);
+    e = L.x.alloc(n1, 16);
+    if (e == hipSuccess) e = L.y.alloc(n1, 16);
+    if (e == hipSuccess) e = L.z.alloc(n1, 16);
+    if (e == hipSuccess && c->w) e = L.w.alloc(n1, 16);
+    if (e == hipSuccess && want_bins) e = L.k.alloc(n1, 16);
     L.q_stride = (int64_t)((n1 + 3) & ~(size_t)3) + 8;  // a 16-byte load of the band kernel may run up to 12 bytes past a column
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.q), (size_t)3 * L.q_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.off), (size_t)(n_runs + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_grid), (size_t)(n_runs + 1) * sizeof(RunGrid));
+    if (e == hipSuccess) e = L.q.alloc((size_t)3 * L.q_stride);
+    if (e == hipSuccess) e = L.off.alloc((size_t)(n_runs + 1));
+    if (e == hipSuccess) e = L.d_grid.alloc((size_t)(n_runs + 1));
     if (e == hipSuccess) e = hipMemsetAsync(L.d_grid, 0, (size_t)(n_runs + 1) * sizeof(RunGrid), ctx->stream);  // [V]: read for groups without runs
     if (e != hipSuccess) return bail(e, "strip layout");
     hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm2, c->x, c->y, c->z, c->w, L.x, L.y, L.z, L.w);
@@ -438,7 +435,7 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     e = hipMemcpyAsync(voff.data(), L.off, (size_t)(n_runs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
     unsigned long long h_same = 0;
     if (want_bins && n > 1) {  // `run` (sorted away by now) serves as the 8-byte result cell
-        unsigned long long *d_same = reinterpret_cast<unsigned long long *>(run);
+        unsigned long long *d_same = reinterpret_cast<unsigned long long *>(static_cast<uint32_t *>(run));
         if (e == hipSuccess) e = hipMemsetAsync(d_same, 0, sizeof(unsigned long long), ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_same_bin_neighbours, dim3(ngrid), dim3(256), 0, ctx->stream, n, L.k, d_same);
@@ -465,11 +462,11 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
                     const int64_t a0 = voff[(size_t)r] + (tl - L.h_tiles[ri][(size_t)r]) * tile;
                     tile_rec[(size_t)tl] = TileRec{a0, (int32_t)std::min<int64_t>(tile, voff[(size_t)r + 1] - a0), (int32_t)r};
                 }
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_tile_rec[ri]), tile_rec.size() * sizeof(TileRec));
+            if (e == hipSuccess) e = L.d_tile_rec[ri].alloc(tile_rec.size());
             if (e == hipSuccess)
                 e = hipMemcpy(L.d_tile_rec[ri], tile_rec.data(), tile_rec.size() * sizeof(TileRec), hipMemcpyHostToDevice);
         }
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_tiles[ri]), (size_t)(n_runs + 1) * sizeof(int64_t));
+        if (e == hipSuccess) e = L.d_tiles[ri].alloc((size_t)(n_runs + 1));
         if (e == hipSuccess)
             e = hipMemcpyAsync(L.d_tiles[ri], L.h_tiles[ri].data(), (size_t)(n_runs + 1) * sizeof(int64_t),
                                hipMemcpyHostToDevice, ctx->stream);
@@ -494,7 +491,7 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
                      (L.h_tiles[0][(size_t)n_runs] + L.h_tiles[1][(size_t)n_runs] + L.h_tiles[2][(size_t)n_runs]) * (int64_t)sizeof(TileRec);
     c->device_bytes += L.device_bytes;
     L.built = true;
-    return bail(hipSuccess, "");
+    return YAWHIP_OK;
 }
 
 // Merged triple runs of a built strip layout (see k_merge_triples); built once, on first use as the streamed side of a
@@ -523,14 +520,14 @@ int build_triples(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n3 = (size_t)std::max<int64_t>(3 * n, 1);
     L.q3_stride = (int64_t)((n3 + 3) & ~(size_t)3) + 8;  // as q_stride: a 16-byte load may run up to 12 bytes past a column
-    int32_t *d_run_group = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&L.q3), (size_t)3 * L.q3_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.idx3), n3 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.pos3), (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t));
-    if (e == hipSuccess && c->w) e = hipMalloc(reinterpret_cast<void **>(&L.w3), n3 * sizeof(double) + 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.off3), (size_t)(V3 + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&L.d_grid3), (size_t)(V3 + 1) * sizeof(RunGrid));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_run_group), run_group.size() * sizeof(int32_t));
+    DevPtr<int32_t> d_run_group;
+    hipError_t e = L.q3.alloc((size_t)3 * L.q3_stride);
+    if (e == hipSuccess) e = L.idx3.alloc(n3);
+    if (e == hipSuccess) e = L.pos3.alloc((size_t)std::max<int64_t>(n, 1));
+    if (e == hipSuccess && c->w) e = L.w3.alloc(n3, 16);
+    if (e == hipSuccess) e = L.off3.alloc((size_t)(V3 + 1));
+    if (e == hipSuccess) e = L.d_grid3.alloc((size_t)(V3 + 1));
+    if (e == hipSuccess) e = d_run_group.alloc(run_group.size());
     if (e == hipSuccess) e = hipMemsetAsync(L.q3, 0, (size_t)3 * L.q3_stride * sizeof(float), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(L.d_grid3, 0, (size_t)(V3 + 1) * sizeof(RunGrid), ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(L.off3, off3.data(), (size_t)(V3 + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
@@ -543,11 +540,9 @@ int build_triples(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_run_group) (void)hipFree(d_run_group);
+    d_run_group.release();
     if (e != hipSuccess) {
-        for (void *ptr : {(void *)L.q3, (void *)L.w3, (void *)L.idx3, (void *)L.pos3, (void *)L.off3, (void *)L.d_grid3})
-            if (ptr) (void)hipFree(ptr);
-        L.q3 = nullptr; L.w3 = nullptr; L.idx3 = nullptr; L.pos3 = nullptr; L.off3 = nullptr; L.d_grid3 = nullptr;
+        L.release_triples();
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "merged triple runs failed: %s", hipGetErrorString(e));
     }
     const int64_t bytes = 3 * L.q3_stride * (int64_t)sizeof(float) + (int64_t)n3 * (4 + (c->w ? 8 : 0)) + n * 4 + (V3 + 1) * (int64_t)(sizeof(int64_t) + sizeof(RunGrid));
@@ -617,17 +612,13 @@ static int upload_catalogs(yawhip_ctx *ctx, int64_t n, const double *x, const do
     // Library-private order: the columns go to the device as they are and are ordered there (rocPRIM radix sorts,
     // yawhip_sort.hip): ascending along the sort axis inside every (patch, bin) segment. The strip layouts are derived
     // from this resident copy (build_strip_layout), the one of the catalogue's own sort axis right away.
-    const size_t col = (size_t)std::max<int64_t>(n, 1) * sizeof(double) + 16;  // + 16: see build_strip_layout
-    double *rx = nullptr, *ry = nullptr, *rz = nullptr, *rw = nullptr, *rk = nullptr;  // raw columns (temporary)
-    uint32_t *perm = nullptr;
-    int64_t *poff = nullptr;
-    unsigned long long *box = nullptr;  // [P][6] sortable images of min / max per axis, [6 P]: violations of the unit norm
-    auto free_tmp = [&]() {
-        for (void *q : {(void *)rx, (void *)ry, (void *)rz, (void *)rw, (void *)rk, (void *)perm, (void *)poff, (void *)box})
-            if (q) (void)hipFree(q);
-    };
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+    const size_t col = n1 * sizeof(double) + 16;  // + 16: see build_strip_layout
+    DevPtr<double> rx, ry, rz, rw, rk;  // raw columns (temporary)
+    DevPtr<uint32_t> perm;
+    DevPtr<int64_t> poff;
+    DevPtr<unsigned long long> box;  // [P][6] sortable images of min / max per axis, [6 P]: violations of the unit norm
     auto bail = [&](hipError_t err, const char *what) {
-        free_tmp();
         yawhip_catalog_free(c);
         yawhip_catalog_free(ck);
         return fail(err == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "catalog upload (%s) failed: %s", what,
@@ -642,23 +633,23 @@ static int upload_catalogs(yawhip_ctx *ctx, int64_t n, const double *x, const do
             h_box[(size_t)6 * p + 3 + a] = sortable_of(-4.0);  // running maximum
         }
     h_box[(size_t)6 * n_patches] = 0ull;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->x), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->y), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->z), col);
-    if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&c->w), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->off), (size_t)(nseg + 1) * sizeof(int64_t));
+    hipError_t e = c->x.alloc(n1, 16);
+    if (e == hipSuccess) e = c->y.alloc(n1, 16);
+    if (e == hipSuccess) e = c->z.alloc(n1, 16);
+    if (e == hipSuccess && w) e = c->w.alloc(n1, 16);
+    if (e == hipSuccess) e = c->off.alloc((size_t)(nseg + 1));
     if (ck) {  // the twin's columns: coordinates, the product (always weighted), its own copy of the offsets
-        for (double **q : {&ck->x, &ck->y, &ck->z, &ck->w, &rk})
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(q), col);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ck->off), (size_t)(nseg + 1) * sizeof(int64_t));
+        for (DevPtr<double> *q : {&ck->x, &ck->y, &ck->z, &ck->w, &rk})
+            if (e == hipSuccess) e = q->alloc(n1, 16);
+        if (e == hipSuccess) e = ck->off.alloc((size_t)(nseg + 1));
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rx), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ry), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&rz), col);
-    if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&rw), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&perm), (size_t)std::max<int64_t>(n, 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&poff), (size_t)(n_patches + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&box), h_box.size() * sizeof(unsigned long long));
+    if (e == hipSuccess) e = rx.alloc(n1, 16);
+    if (e == hipSuccess) e = ry.alloc(n1, 16);
+    if (e == hipSuccess) e = rz.alloc(n1, 16);
+    if (e == hipSuccess && w) e = rw.alloc(n1, 16);
+    if (e == hipSuccess) e = perm.alloc(n1);
+    if (e == hipSuccess) e = poff.alloc((size_t)(n_patches + 1));
+    if (e == hipSuccess) e = box.alloc(h_box.size());
     if (e == hipSuccess && n > 0) {
         e = hipMemcpyAsync(rx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ry, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
@@ -693,7 +684,8 @@ static int upload_catalogs(yawhip_ctx *ctx, int64_t n, const double *x, const do
     }
     e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return bail(e, "finish");
-    free_tmp();
+    // the temporaries go before the layouts are built, not at the end: they are half of an upload's peak memory
+    rx.release(); ry.release(); rz.release(); rw.release(); rk.release(); perm.release(); poff.release(); box.release();
     for (yawhip_catalog *t : {c, ck}) {
         if (!t) continue;
         t->unit_norm = h_box[(size_t)6 * n_patches] == 0ull;
@@ -756,14 +748,13 @@ int yawhip_catalog_segment_sums(const yawhip_catalog *cat, double *sums) {
     }
     yawhip_ctx *ctx = cat->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    double *d_out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_out), (size_t)nseg * sizeof(double));
+    DevPtr<double> d_out;
+    hipError_t e = d_out.alloc((size_t)nseg);
     if (e != hipSuccess) return fail(YAWHIP_ERR_OOM, "segment sums: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(k_segment_weight_sums, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, cat->w, cat->off, d_out);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(sums, d_out, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(YAWHIP_ERR_HIP, "segment sums failed: %s", hipGetErrorString(e));
     return YAWHIP_OK;
 }
@@ -777,16 +768,7 @@ int yawhip_catalog_free(yawhip_catalog *c) {
         if (c->ctx->stream) (void)hipStreamSynchronize(c->ctx->stream);
         drop_plans(c->ctx, c);
     }
-    if (c->x) (void)hipFree(c->x);
-    if (c->y) (void)hipFree(c->y);
-    if (c->z) (void)hipFree(c->z);
-    if (c->w) (void)hipFree(c->w);
-    if (c->off) (void)hipFree(c->off);
-    for (int o = 0; o < 3; ++o) {
-        c->strips[o].release();
-        c->seg[o].release();
-    }
-    delete c;
+    delete c;  // its columns and layouts go with it
     return YAWHIP_OK;
 }
 
@@ -805,16 +787,11 @@ int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const dou
         return fail(YAWHIP_ERR_INVALID, "too many centres (%d) for the LDS table", n_centers);
     if (n == 0) return YAWHIP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    double *dx = nullptr, *dc = nullptr;
-    int32_t *dout = nullptr;
-    auto cleanup = [&]() {
-        if (dx) (void)hipFree(dx);
-        if (dc) (void)hipFree(dc);
-        if (dout) (void)hipFree(dout);
-    };
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dx), (size_t)3 * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dc), (size_t)3 * n_centers * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dout), (size_t)n * sizeof(int32_t));
+    DevPtr<double> dx, dc;
+    DevPtr<int32_t> dout;
+    hipError_t e = dx.alloc((size_t)3 * n);
+    if (e == hipSuccess) e = dc.alloc((size_t)3 * n_centers);
+    if (e == hipSuccess) e = dout.alloc((size_t)n);
     if (e == hipSuccess) e = hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dx + n, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dx + 2 * n, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
@@ -832,7 +809,6 @@ int yawhip_assign_patches(yawhip_ctx *ctx, int64_t n, const double *x, const dou
     }
     if (e == hipSuccess) e = hipMemcpyAsync(patch_out, dout, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cleanup();
     if (e != hipSuccess) return hip_fail("yawhip_assign_patches", e);
     return YAWHIP_OK;
 }

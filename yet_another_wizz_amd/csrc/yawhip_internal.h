@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "yawhip.h"
+#include "yawhip_devmem.h"
 #include "yawhip_healpix.h"
 #include "yawhip_sort.h"
 
@@ -145,47 +146,37 @@ __device__ __forceinline__ int run_cell(double key, double first, double inv) {
     return f >= (double)RUN_GRID ? RUN_GRID - 1 : (f >= 1.0 ? (int)f : 0);
 }
 
+// the count call's buffers grow with a quarter to spare: calls of similar sizes keep them
 template <typename T>
-struct DevBuf {  // grow-only device workspace
-    T *ptr = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        size_t want = n + n / 4 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&ptr), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-};
+hipError_t reserve_call(DevBuf<T> &buf, size_t n) { return buf.reserve(n, n / 4 + 64); }
 
 // Small per-call tables travel in ONE host-to-device copy from a pinned staging buffer, and the results (counters, counts,
 // sums) come back in ONE copy into pinned memory: a dozen pageable copies of a few hundred bytes each cost more host
 // time than the kernels of a small call take.
 struct Arena {
-    unsigned char *h = nullptr, *d = nullptr;  // pinned host image and device buffer of the same size
+    unsigned char *h = nullptr;  // pinned host image ...
+    DevPtr<unsigned char> d;     // ... and device buffer of the same size
     size_t cap = 0;
+    Arena() = default;
+    Arena(Arena &&o) noexcept : h(std::exchange(o.h, nullptr)), d(std::move(o.d)), cap(std::exchange(o.cap, 0)) {}
+    Arena &operator=(Arena &&o) noexcept {  // (h has no owner type: the two trade places, nothing is freed here)
+        std::swap(h, o.h); std::swap(d, o.d); std::swap(cap, o.cap);
+        return *this;
+    }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         release();
         const size_t want = n + n / 4 + 4096;
         // (coherent: k_call_tail writes a result block and its completion word while the host polls for it)
         hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&h), want, hipHostMallocPortable | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), want);
+        if (e == hipSuccess) e = d.alloc(want);
         if (e == hipSuccess) cap = want; else release();
         return e;
     }
     void release() {
         if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr;
+        d.release();
+        h = nullptr;
         cap = 0;
     }
 };
@@ -273,43 +264,36 @@ struct CallKey {
 
 struct StripLayout {
     bool built = false;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *w = nullptr;
-    int32_t *k = nullptr;             // bin id per object (patch-level layout of a binned catalogue)
-    float *q = nullptr;               // [3][q_stride] float32 images of x, y, z (k_count_band32)
+    DevPtr<double> x, y, z, w;
+    DevPtr<int32_t> k;                // bin id per object (patch-level layout of a binned catalogue)
+    DevPtr<float> q;                  // [3][q_stride] float32 images of x, y, z (k_count_band32)
     int64_t q_stride = 0;
-    int64_t *off = nullptr;           // [V+1] offsets of the runs
+    DevPtr<int64_t> off;              // [V+1] offsets of the runs
     std::vector<int64_t> h_off;       // same on the host
     std::vector<int64_t> h_vbase;     // [G+1] first run of every group
     std::vector<int64_t> h_slo;       // [G]   global strip index of a group's first run
     std::vector<int64_t> h_tiles[3];  // [V+1] prefix of lane tiles over the runs, for tiles of MWG * {1, 2, 4} objects
-    int64_t *d_vbase = nullptr, *d_slo = nullptr, *d_tiles[3] = {nullptr, nullptr, nullptr};
-    TileRec *d_tile_rec[3] = {nullptr, nullptr, nullptr};  // [tiles] first object, length and run of every lane tile
-    RunGrid *d_grid = nullptr;        // [V+1] per-run index along the sort axis (item builder)
+    DevPtr<int64_t> d_vbase, d_slo, d_tiles[3];
+    DevPtr<TileRec> d_tile_rec[3];    // [tiles] first object, length and run of every lane tile
+    DevPtr<RunGrid> d_grid;           // [V+1] per-run index along the sort axis (item builder)
     // merged triple runs (k_merge_triples), built when a float32 band kernel first streams this layout
     bool triples = false;
-    float *q3 = nullptr;              // [3][q3_stride] float32 images in merged order (3 n entries)
+    DevPtr<float> q3;                 // [3][q3_stride] float32 images in merged order (3 n entries)
     int64_t q3_stride = 0;
-    double *w3 = nullptr;             // weights in merged order
-    int32_t *idx3 = nullptr;          // [3 n] entry -> index in the layout's own order
-    int32_t *pos3 = nullptr;          // [n] object -> its place in the triple run centred on its own strip
-    int64_t *off3 = nullptr;          // [V + 2 G + 1] offsets of the triple runs: group g has its strips + 2, first one = vbase[g] + 2 g
-    RunGrid *d_grid3 = nullptr;       // [V + 2 G + 1]
+    DevPtr<double> w3;                // weights in merged order
+    DevPtr<int32_t> idx3;             // [3 n] entry -> index in the layout's own order
+    DevPtr<int32_t> pos3;             // [n] object -> its place in the triple run centred on its own strip
+    DevPtr<int64_t> off3;             // [V + 2 G + 1] offsets of the triple runs: group g has its strips + 2, first one = vbase[g] + 2 g
+    DevPtr<RunGrid> d_grid3;          // [V + 2 G + 1]
     int64_t n_groups = 0;
     int64_t device_bytes = 0;
     double obj_run = 0.0;             // run length seen by the typical object (sum len^2 / sum len)
     double same_bin = 0.0;            // fraction of neighbours in the layout's order that share their bin (binned patch-level layouts)
-    void release() {
-        for (void *ptr : {(void *)x, (void *)y, (void *)z, (void *)w, (void *)k, (void *)q, (void *)off, (void *)d_vbase, (void *)d_slo,
-                          (void *)d_tiles[0], (void *)d_tiles[1], (void *)d_tiles[2], (void *)d_tile_rec[0], (void *)d_tile_rec[1],
-                          (void *)d_tile_rec[2], (void *)d_grid, (void *)q3, (void *)w3, (void *)idx3, (void *)pos3, (void *)off3, (void *)d_grid3})
-            if (ptr) (void)hipFree(ptr);
-        q3 = nullptr; w3 = nullptr; idx3 = nullptr; pos3 = nullptr; off3 = nullptr; d_grid3 = nullptr; triples = false;
-        x = y = z = w = nullptr; k = nullptr; q = nullptr; off = d_vbase = d_slo = nullptr;
-        d_tiles[0] = d_tiles[1] = d_tiles[2] = nullptr;
-        d_tile_rec[0] = d_tile_rec[1] = d_tile_rec[2] = nullptr;
-        d_grid = nullptr;
-        built = false;
+    void release_triples() {
+        q3.release(); w3.release(); idx3.release(); pos3.release(); off3.release(); d_grid3.release();
+        triples = false;
     }
+    void release() { *this = StripLayout{}; }  // (host tables and statistics go with the device memory: nothing reads them unbuilt)
 };
 
 }  // namespace yawhip_detail
@@ -366,8 +350,8 @@ struct yawhip_catalog {
     uint64_t uid = 0;  // upload id, never reused (plans are keyed on it, not on the address)
     int64_t n = 0;
     int32_t n_patches = 0, nb = 1;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *w = nullptr;
-    int64_t *off = nullptr;
+    yawhip_detail::DevPtr<double> x, y, z, w;  // w may be null
+    yawhip_detail::DevPtr<int64_t> off;
     std::vector<int64_t> h_off;
     int64_t device_bytes = 0;
     bool unit_norm = true;  // every |a|^2 within UNIT_NORM_TOL of 1 (precondition of the FP32 pre-filter)

@@ -193,40 +193,30 @@ __global__ __launch_bounds__(WG) void k_kmeans_step(int64_t n, const double *__r
     }
 }
 
-template <typename T>
-hipError_t grow(T *&ptr, size_t &cap, size_t count) {  // grow-only device table
-    if (count <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ptr), count * sizeof(T));
-    if (e == hipSuccess) cap = count;
-    return e;
-}
-
 }  // namespace
 
+#pragma GCC visibility push(hidden)  // (its destructor is not an export)
 struct yawhip_kmeans {
     int device = 0;
     hipStream_t stream = nullptr;  // the context's
     int lds_limit = 0, n_cu = 0;
     int64_t n = 0, n_seg = 0;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *w = nullptr;  // w may be null
+    DevPtr<double> x, y, z, w;  // w may be null
     double wscale = 0.0;
-    double *m = nullptr;        // [n] squared distance to the nearest chosen centre
-    uint32_t *q = nullptr;      // [n] floor(m 2^29)
-    u64 *segsum = nullptr;      // [n_seg]
-    int64_t *pick_out = nullptr;
+    DevPtr<double> m;           // [n] squared distance to the nearest chosen centre
+    DevPtr<uint32_t> q;         // [n] floor(m 2^29)
+    DevPtr<u64> segsum;         // [n_seg]
+    DevPtr<int64_t> pick_out;
     std::vector<u64> h_segsum;  // of the last seed
     u64 total = 0;
     bool seeded = false;
-    u64 *acc = nullptr;         // [4 k + 1]
-    double *centres = nullptr;  // [3 k]
-    size_t acc_cap = 0, centres_cap = 0;
-    int32_t *ids = nullptr;     // [n], allocated when ids are first asked for
+    DevBuf<u64> acc;            // [4 k + 1]
+    DevBuf<double> centres;     // [3 k]
+    DevPtr<int32_t> ids;        // [n], allocated when ids are first asked for
     std::vector<u64> h_acc;
     int last_path = PATH_NONE;
 };
+#pragma GCC visibility pop
 
 namespace {
 
@@ -241,7 +231,7 @@ hipError_t launch_step(const yawhip_kmeans *km, unsigned grid, size_t lds, int k
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL((k_kmeans_step<WEIGHTED, LDS_ACC>), dim3(grid), dim3(WG), lds, km->stream, km->n, km->x, km->y, km->z, km->w,
-                       km->wscale, k, km->centres, km->acc, ids);
+                       km->wscale, k, km->centres.ptr, km->acc.ptr, ids);
     return hipGetLastError();
 }
 
@@ -252,10 +242,7 @@ extern "C" {
 void yawhip_kmeans_close(yawhip_kmeans *km) {
     if (!km) return;
     (void)hipSetDevice(km->device);
-    for (void *p : {(void *)km->x, (void *)km->y, (void *)km->z, (void *)km->w, (void *)km->m, (void *)km->q, (void *)km->segsum,
-                    (void *)km->pick_out, (void *)km->acc, (void *)km->centres, (void *)km->ids})
-        if (p) (void)hipFree(p);
-    delete km;
+    delete km;  // its device memory goes with it
 }
 
 int yawhip_kmeans_open(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w, double wscale,
@@ -276,14 +263,14 @@ int yawhip_kmeans_open(yawhip_ctx *ctx, int64_t n, const double *x, const double
     km->n_seg = (n + SEG - 1) / SEG;
     km->wscale = w ? wscale : 0.0;
     const size_t col = (size_t)n * sizeof(double);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&km->x), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->y), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->z), col);
-    if (e == hipSuccess && w) e = hipMalloc(reinterpret_cast<void **>(&km->w), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->m), col);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->q), (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->segsum), (size_t)km->n_seg * sizeof(u64));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&km->pick_out), sizeof(int64_t));
+    hipError_t e = km->x.alloc((size_t)n);
+    if (e == hipSuccess) e = km->y.alloc((size_t)n);
+    if (e == hipSuccess) e = km->z.alloc((size_t)n);
+    if (e == hipSuccess && w) e = km->w.alloc((size_t)n);
+    if (e == hipSuccess) e = km->m.alloc((size_t)n);
+    if (e == hipSuccess) e = km->q.alloc((size_t)n);
+    if (e == hipSuccess) e = km->segsum.alloc((size_t)km->n_seg);
+    if (e == hipSuccess) e = km->pick_out.alloc(1);
     if (e == hipSuccess) e = hipMemcpyAsync(km->x, x, col, hipMemcpyHostToDevice, km->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(km->y, y, col, hipMemcpyHostToDevice, km->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(km->z, z, col, hipMemcpyHostToDevice, km->stream);
@@ -352,16 +339,16 @@ int yawhip_kmeans_step(yawhip_kmeans *km, int32_t k, const double *centres, int6
     if (k > max_k_step(km)) return fail(YAWHIP_ERR_INVALID, "too many centres (%d) for the LDS table (at most %d)", k, max_k_step(km));
     HIP_TRY(hipSetDevice(km->device));
     const size_t n_acc = 4 * (size_t)k + 1;
-    HIP_TRY(grow(km->acc, km->acc_cap, n_acc));
-    HIP_TRY(grow(km->centres, km->centres_cap, 3 * (size_t)k));
-    if (ids && !km->ids) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&km->ids), (size_t)km->n * sizeof(int32_t)));
+    HIP_TRY(km->acc.reserve(n_acc));
+    HIP_TRY(km->centres.reserve(3 * (size_t)k));
+    if (ids && !km->ids) HIP_TRY(km->ids.alloc((size_t)km->n));
     try {
         km->h_acc.resize(n_acc);
     } catch (const std::bad_alloc &) {
         return fail(YAWHIP_ERR_OOM, "yawhip_kmeans_step: out of host memory");
     }
-    HIP_TRY(hipMemsetAsync(km->acc, 0, n_acc * sizeof(u64), km->stream));
-    HIP_TRY(hipMemcpyAsync(km->centres, centres, 3 * (size_t)k * sizeof(double), hipMemcpyHostToDevice, km->stream));
+    HIP_TRY(hipMemsetAsync(km->acc.ptr, 0, n_acc * sizeof(u64), km->stream));
+    HIP_TRY(hipMemcpyAsync(km->centres.ptr, centres, 3 * (size_t)k * sizeof(double), hipMemcpyHostToDevice, km->stream));
     // the partials share the LDS with the centres where both fit; the limit follows the device's LDS size
     const bool lds_acc = k <= max_k_lds(km);
     const size_t lds = (size_t)k * (lds_acc ? 7 : 3) * sizeof(double);
@@ -373,7 +360,7 @@ int yawhip_kmeans_step(yawhip_kmeans *km, int32_t k, const double *centres, int6
     if (km->w) e = lds_acc ? launch_step<true, true>(km, grid, lds, k, d_ids) : launch_step<true, false>(km, grid, lds, k, d_ids);
     else e = lds_acc ? launch_step<false, true>(km, grid, lds, k, d_ids) : launch_step<false, false>(km, grid, lds, k, d_ids);
     if (e != hipSuccess) return hip_fail("yawhip_kmeans_step", e);
-    HIP_TRY(hipMemcpyAsync(km->h_acc.data(), km->acc, n_acc * sizeof(u64), hipMemcpyDeviceToHost, km->stream));
+    HIP_TRY(hipMemcpyAsync(km->h_acc.data(), km->acc.ptr, n_acc * sizeof(u64), hipMemcpyDeviceToHost, km->stream));
     if (ids) HIP_TRY(hipMemcpyAsync(ids, km->ids, (size_t)km->n * sizeof(int32_t), hipMemcpyDeviceToHost, km->stream));
     HIP_TRY(hipStreamSynchronize(km->stream));
     for (int32_t c = 0; c < k; ++c) {

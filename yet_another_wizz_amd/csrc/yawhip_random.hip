@@ -32,9 +32,13 @@
 #include <cmath>
 #include <cstring>
 
+#include "yawhip_devmem.h"
+#include "yawhip_healpix_math.h"
 #include "yawhip_random.h"
 
 namespace yawrand {
+
+using yawhip_detail::DevPtr;
 
 namespace {
 
@@ -104,10 +108,8 @@ __global__ __launch_bounds__(WG) void k_random_uniform(U128 s0, const Affine *__
 
 // ---- HealPixRandoms ----
 constexpr int HP_ORDER = 29;                                // every point is the centre of a nested pixel of this order
-constexpr int64_t HP_NSIDE = (int64_t)1 << HP_ORDER;
 constexpr double HP_FACT2 = 4.0 / 3458764513820540928.0;    // 4 / npix, npix = 12 * 4^29
 constexpr double HP_FACT1 = 1073741824.0 * HP_FACT2;        // 2 nside * fact2
-constexpr double HP_HALFPI = 0x1.921fb54442d18p+0;          // numpy's pi / 2
 
 struct HealpixMap {
     int shift;           // 2 (29 - order): bits of the sub-pixel number
@@ -115,44 +117,6 @@ struct HealpixMap {
     const int64_t *__restrict__ ipix;  // unmasked pixels of the map, nested, ascending
     const double *__restrict__ cdf;    // their cumulative probabilities, cdf[n_unmasked - 1] == 1
 };
-
-// every second bit of v (bits 0, 2, 4, ...), packed
-__device__ __forceinline__ int64_t even_bits(uint64_t v) {
-    v &= 0x5555555555555555ull;
-    v = (v | (v >> 1)) & 0x3333333333333333ull;
-    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
-    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
-    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
-    v = (v | (v >> 16)) & 0x00000000ffffffffull;
-    return (int64_t)v;
-}
-
-// Centre of the nested order-29 pixel p: phi and z = cos(theta). Float64 steps as in randoms.py (pix2loc_nest).
-__device__ __forceinline__ void healpix_centre(uint64_t p, double &phi, double &z) {
-    const int face = (int)(p >> (2 * HP_ORDER));
-    const uint64_t low = p & (((uint64_t)1 << (2 * HP_ORDER)) - 1);
-    const int64_t ix = even_bits(low), iy = even_bits(low >> 1);
-    const int64_t jrll = 2 + (face >> 2);                               // 2 2 2 2 3 3 3 3 4 4 4 4
-    const int64_t jpll = (int64_t)((0x753164207531ull >> (4 * (face & 15))) & 7);  // 1 3 5 7 0 2 4 6 1 3 5 7
-    const int64_t jr = (jrll << HP_ORDER) - ix - iy - 1;                // ring, 1 .. 4 nside - 1 from the north
-    int64_t nr, kshift;
-    if (jr < HP_NSIDE) {  // north cap
-        nr = jr, kshift = 0;
-        const double f = (double)nr;
-        z = 1.0 - f * f * HP_FACT2;
-    } else if (jr > 3 * HP_NSIDE) {  // south cap
-        nr = 4 * HP_NSIDE - jr, kshift = 0;
-        const double f = (double)nr;
-        z = f * f * HP_FACT2 - 1.0;
-    } else {
-        nr = HP_NSIDE, kshift = (jr - HP_NSIDE) & 1;
-        z = (double)(2 * HP_NSIDE - jr) * HP_FACT1;
-    }
-    int64_t jp = (jpll * nr + ix - iy + 1 + kshift) / 2;  // the sum is even
-    if (jp > 4 * HP_NSIDE) jp -= 4 * HP_NSIDE;
-    if (jp < 1) jp += 4 * HP_NSIDE;
-    phi = ((double)jp - (double)(kshift + 1) * 0.5) * (HP_HALFPI / (double)nr);
-}
 
 // Points 0 .. n-1 of a chunk after the state s0: output i picks the mask pixel, output n + i the sub-pixel.
 __global__ __launch_bounds__(WG) void k_random_healpix(U128 s0, const Affine *__restrict__ pow2, int64_t n, HealpixMap map,
@@ -175,7 +139,7 @@ __global__ __launch_bounds__(WG) void k_random_healpix(U128 s0, const Affine *__
         lo = lo < map.n_unmasked ? lo : map.n_unmasked - 1;  // u < 1 == cdf[n_unmasked - 1]: never taken, keeps the load inside
         const uint64_t p = ((uint64_t)map.ipix[lo] << map.shift) | sub;
         double phi, z;
-        healpix_centre(p, phi, z);
+        yawpix::pixel_centre(HP_ORDER, yawpix::ring_position_nest(HP_ORDER, (int64_t)p), HP_FACT1, HP_FACT2, phi, z);
         x[i] = phi;
         y[i] = z;
         if (pix) pix[i] = (int64_t)p;
@@ -348,22 +312,6 @@ uint64_t host_output(u128 s) {
 
 U128 dev(u128 s) { return {(uint64_t)(s >> 64), (uint64_t)s}; }
 
-struct Buffers {
-    void *p[16] = {};
-    int n = 0;
-    template <class T>
-    hipError_t get(T **out, size_t count) {
-        *out = nullptr;
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc(&p[n], count * sizeof(T));
-        if (e == hipSuccess) *out = static_cast<T *>(p[n++]);
-        return e;
-    }
-    ~Buffers() {
-        for (int i = 0; i < n; ++i) (void)hipFree(p[i]);
-    }
-};
-
 #define TRY(expr)                          \
     do {                                   \
         hipError_t e_ = (expr);            \
@@ -372,9 +320,9 @@ struct Buffers {
 
 // The chunks of one draw. `coords` is what tells the generators apart: coords.launch(stream, s0, pow2, k, x, y) writes the
 // k coordinate pairs of a chunk from the 2k outputs after the state s0, coords.fetch(stream, off, k) copies what it
-// made besides x and y to the host; `buf` already holds what coords needs on the device.
+// made besides x and y to the host; what coords needs on the device is already there.
 template <class Coords>
-hipError_t draw_chunks(hipStream_t stream, const Draw &d, DrawEnd &end, Buffers &buf, const Coords &coords) {
+hipError_t draw_chunks(hipStream_t stream, const Draw &d, DrawEnd &end, const Coords &coords) {
     const u128 inc = ((u128)d.inc_hi << 64) | d.inc_lo;
     u128 state = ((u128)d.state_hi << 64) | d.state_lo;
     bool pending = d.has_uint32 != 0;
@@ -385,22 +333,22 @@ hipError_t draw_chunks(hipStream_t stream, const Draw &d, DrawEnd &end, Buffers 
     const uint32_t threshold = bounded ? (uint32_t)((((uint64_t)1 << 32) - (uint64_t)d.n_data) % (uint64_t)d.n_data) : 0;
     const double accept_rate = 1.0 - threshold / 4294967296.0;
 
-    Affine *pow2 = nullptr;
-    double *x = nullptr, *y = nullptr, *w = nullptr, *z = nullptr, *dw = nullptr, *dz = nullptr;
-    int64_t *idx = nullptr, *offs = nullptr, *scalars = nullptr;
-    int32_t *counts = nullptr;
-    TRY(buf.get(&pow2, 64));
-    TRY(buf.get(&x, chunk_max));
-    TRY(buf.get(&y, chunk_max));
+    DevPtr<Affine> pow2;  // (a count of zero allocates nothing and leaves the pointer null)
+    DevPtr<double> x, y, w, z, dw, dz;
+    DevPtr<int64_t> idx, offs, scalars;
+    DevPtr<int32_t> counts;
+    TRY(pow2.alloc(64));
+    TRY(x.alloc(chunk_max));
+    TRY(y.alloc(chunk_max));
     if (bounded) {
-        if (d.data_w) TRY(buf.get(&w, chunk_max));
-        if (d.data_z) TRY(buf.get(&z, chunk_max));
-        if (d.idx_out) TRY(buf.get(&idx, chunk_max));
-        if (d.data_w) TRY(buf.get(&dw, d.n_data));
-        if (d.data_z) TRY(buf.get(&dz, d.n_data));
-        TRY(buf.get(&counts, WINDOW_TILES));
-        TRY(buf.get(&offs, WINDOW_TILES));
-        TRY(buf.get(&scalars, 2));
+        if (d.data_w) TRY(w.alloc(chunk_max));
+        if (d.data_z) TRY(z.alloc(chunk_max));
+        if (d.idx_out) TRY(idx.alloc(chunk_max));
+        if (d.data_w) TRY(dw.alloc(d.n_data));
+        if (d.data_z) TRY(dz.alloc(d.n_data));
+        TRY(counts.alloc(WINDOW_TILES));
+        TRY(offs.alloc(WINDOW_TILES));
+        TRY(scalars.alloc(2));
         if (d.data_w) TRY(hipMemcpyAsync(dw, d.data_w, d.n_data * sizeof(double), hipMemcpyHostToDevice, stream));
         if (d.data_z) TRY(hipMemcpyAsync(dz, d.data_z, d.n_data * sizeof(double), hipMemcpyHostToDevice, stream));
     }
@@ -515,22 +463,20 @@ struct HealpixCoords {
 }  // namespace
 
 hipError_t draw_box(hipStream_t stream, const BoxDraw &d, DrawEnd &end) {
-    Buffers buf;
-    return draw_chunks(stream, d, end, buf, BoxCoords{d});
+    return draw_chunks(stream, d, end, BoxCoords{d});
 }
 
 hipError_t draw_healpix(hipStream_t stream, const HealpixDraw &d, DrawEnd &end) {
-    Buffers buf;  // the map goes up once, before the chunks
     HealpixCoords c{{2 * (HP_ORDER - d.order), d.n_unmasked, nullptr, nullptr}, nullptr, d.pix_out};
-    int64_t *ipix = nullptr;
-    double *cdf = nullptr;
-    TRY(buf.get(&ipix, d.n_unmasked));
-    TRY(buf.get(&cdf, d.n_unmasked));
+    DevPtr<int64_t> ipix, pix;  // the map goes up once, before the chunks
+    DevPtr<double> cdf;
+    TRY(ipix.alloc(d.n_unmasked));
+    TRY(cdf.alloc(d.n_unmasked));
     TRY(hipMemcpyAsync(ipix, d.ipix_unmasked, d.n_unmasked * sizeof(int64_t), hipMemcpyHostToDevice, stream));
     TRY(hipMemcpyAsync(cdf, d.cdf, d.n_unmasked * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (d.pix_out) TRY(buf.get(&c.pix, std::min(d.n, d.chunksize)));
-    c.map.ipix = ipix, c.map.cdf = cdf;
-    const hipError_t e = draw_chunks(stream, d, end, buf, c);
+    if (d.pix_out) TRY(pix.alloc(std::min(d.n, d.chunksize)));
+    c.map.ipix = ipix, c.map.cdf = cdf, c.pix = pix;
+    const hipError_t e = draw_chunks(stream, d, end, c);
     if (e != hipSuccess) (void)hipStreamSynchronize(stream);  // the uploads read this call's host memory
     return e;
 }

@@ -6,19 +6,20 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "yawhip_devmem.h"
+
 namespace yawsort {
 
 // Workspace of the sorts (grow-only, owned by the caller's context).
 struct Workspace {
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-    double *keys_out = nullptr;     // [cap]
-    uint64_t *k64_in = nullptr;     // [cap]
-    uint64_t *k64_out = nullptr;    // [cap]
-    uint32_t *iota = nullptr;       // [cap]
+    yawhip_detail::DevBuf<unsigned char> tmp;  // rocPRIM's temporary storage
+    yawhip_detail::DevPtr<double> keys_out;    // [cap]
+    yawhip_detail::DevPtr<uint64_t> k64_in;    // [cap]
+    yawhip_detail::DevPtr<uint64_t> k64_out;   // [cap]
+    yawhip_detail::DevPtr<uint32_t> iota;      // [cap]
     size_t cap = 0;
     hipError_t reserve(size_t n);
-    void release();
+    void release() { *this = Workspace{}; }
 };
 
 // perm[i] = index (into the input order) of the object that comes i-th when every segment

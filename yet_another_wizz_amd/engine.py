@@ -199,15 +199,24 @@ def job_work(layout1, layout2, jobs, thresholds, *, kernel: str | None = None, s
     return _lib.job_work(ctx, d1, d2, jobs, thresholds, kernel=kernel or default_kernel)
 
 
+def _preparation_context():
+    """The context catalogue preparation runs on (patch assignment and creation, randoms, HEALPix maps), or ``None`` when
+    there is no library or device: the caller then takes its host route. One device does it: no reason to span (and
+    replicate on) every GPU."""
+    try:
+        if _lib.device_count() < 1:
+            return None
+        return get_context(default_devices()[0])
+    except _lib.YawhipError:
+        return None
+
+
 def assign_patches(xyz, centers_xyz):
     """Nearest patch centre per object on the device (``yawhip_assign_patches``), or ``None`` when no
     GPU / library is available -- patch assignment is catalogue preparation, which the reference does on
     the host too, so unlike the pair counts it may fall back to scipy there."""
-    try:
-        if _lib.device_count() < 1:
-            return None
-        ctx = get_context(default_devices()[0])  # one device does it: no reason to span (and replicate on) every GPU
-    except _lib.YawhipError:
+    ctx = _preparation_context()
+    if ctx is None:
         return None
     if isinstance(xyz, tuple):  # three columns
         x, y, z = (np.ascontiguousarray(c, dtype=np.float64) for c in xyz)
@@ -223,11 +232,8 @@ def kmeans_open(x, y, z, weights=None, wscale: float = 0.0):
     (``yawhip_kmeans_open``) -> ``_lib.KMeans``, or ``None`` when no GPU / library is available: patch creation is
     catalogue preparation, as ``assign_patches``, and ``patches.py`` then runs the same arithmetic with numpy. One device
     does it."""
-    try:
-        if _lib.device_count() < 1:
-            return None
-        ctx = get_context(default_devices()[0])
-    except _lib.YawhipError:
+    ctx = _preparation_context()
+    if ctx is None:
         return None
     return _lib.KMeans(ctx, x, y, z, weights, wscale)
 
@@ -237,12 +243,7 @@ def _random_context(generator):
     more than 2^32 attached values (numpy's 64-bit bounded-integer path)."""
     if generator.data_size > _lib.RANDOM_MAX_DATA:
         return None
-    try:
-        if _lib.device_count() < 1:
-            return None
-        return get_context(default_devices()[0])
-    except _lib.YawhipError:
-        return None
+    return _preparation_context()
 
 
 def draw_box_randoms(generator, num: int, chunksize: int):
@@ -279,11 +280,8 @@ def healpix_map(phi, z, weights, order: int, nested: bool, *, want_pixels: bool 
     """HEALPix pixels and map of the points ``(phi, z)`` on the device (``yawhip_healpix_map``): ``(pix, map)``, each ``None``
     unless wanted (see ``_lib.healpix_map``), or ``None`` when no GPU / library is available -- like patch assignment this is
     catalogue preparation, and ``healpix.ang2pix`` / ``healpix.healpix_map`` then compute the same values with numpy."""
-    try:
-        if _lib.device_count() < 1:
-            return None
-        ctx = get_context(default_devices()[0])
-    except _lib.YawhipError:
+    ctx = _preparation_context()
+    if ctx is None:
         return None
     return _lib.healpix_map(ctx, phi, z, weights, order, nested, want_pixels=want_pixels, want_map=want_map, chunksize=chunksize)
 
@@ -296,11 +294,8 @@ def healpix_pixels(values, weights, order: int, nested: bool, *, chunksize: int 
     library raises if it selects another number. ValueError when every pixel is masked."""
     from . import healpix
 
-    try:
-        if _lib.device_count() < 1:
-            return None
-        ctx = get_context(default_devices()[0])
-    except _lib.YawhipError:
+    ctx = _preparation_context()
+    if ctx is None:
         return None
     capacity = healpix.count_selected(values, weights)
     if capacity == 0:
