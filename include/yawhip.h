@@ -490,6 +490,47 @@ int yawhip_kmeans_step(yawhip_kmeans *km, int32_t k, const double *centres, int6
 int yawhip_kmeans_query(const yawhip_kmeans *km, int32_t what, int64_t *value);
 void yawhip_kmeans_close(yawhip_kmeans *km);
 
+/*
+ * Tangential and cross shear of a source catalogue around the lenses of a catalogue binned in redshift
+ * (measurements.crosscorrelate_shear; no counterpart in the reference). Additive to ABI 6.
+ *
+ * yawhip_shear_upload   a shear catalogue as an opaque handle on the context (first device of a multi-device context): the
+ *                       columns are copied up once, every patch segment is sorted along sort_axis on the device and the
+ *                       columns are gathered into that order; the handle keeps x, y, z, w, w * g1 and w * g2 (each product
+ *                       one float64 multiply, rounded on its own; g1, g2 when w is NULL).
+ *   x, y, z      float64[n] unit vectors (host);  w  float64[n] weights or NULL (every weight 1.0)
+ *   g1, g2       float64[n] shear components in the local frame whose first axis points east (+RA) and whose second axis
+ *                points north: g1 > 0 stretches along east-west, g2 > 0 along the diagonal between +east and +north
+ *   offsets      int64[n_patches + 1] CSR over the patches (sources are never binned); objects are grouped by patch
+ * yawhip_shear_free     frees the handle (NULL: nothing happens). Free it before its context is destroyed.
+ * yawhip_shear_count    for every job (lens patch p, source patch q) and redshift bin k, over the pairs (lens l of segment
+ *                       (p, k), source s of patch q) with t[k][e] < s2 <= t[k][e + 1] -- s2 and the thresholds exactly those of
+ *                       yawhip_count_pairs -- the sums, in float64 with every product and sum rounded on its own,
+ *       a = x ly - y lx,  rho2 = x x + y y,  b = rho2 lz - z (x lx + y ly),  den = a a + b b     (x, y, z: the source)
+ *       c2 = (a a - b b) / den,  s2p = (2 a b) / den      cos and sin of twice the position angle of the lens seen from the
+ *                                                         source, from east towards north
+ *       fine_t += w_l * -((w_s g1) c2 + (w_s g2) s2p)     tangential
+ *       fine_x += w_l *  ((w_s g1) s2p - (w_s g2) c2)     cross
+ *       fine_w += w_l * w_s
+ *     A pair with den == 0 (the source on a pole of the frame) adds to fine_w only.
+ *   lenses       a resident catalogue of the same context with n_bins_or_1 equal to 1 or n_bins
+ *   jobs         int32[n_jobs][2] = (lens patch, source patch);  t  float64[B][E] as for yawhip_count_pairs, E <= 256
+ *   fine_t, fine_x, fine_w   float64[n_jobs][B][E-1] each (host); every element is written
+ *   stats        may be NULL; candidate / evaluated pairs, workgroups, launches and the times are filled, the rest is 0
+ * One workgroup per (job, bin) cell adds into one float64 LDS histogram per wave and stores the cell with plain stores: no
+ * floating-point atomics on global memory; the reproducibility note of yawhip_count_pairs' BAND path applies (tested run
+ * to run). The count runs on the context's first device. Errors as for yawhip_count_pairs (handles of another context or
+ * unequal patch counts: YAWHIP_ERR_MISMATCH), checked before any device work.
+ */
+typedef struct yawhip_shear_sources yawhip_shear_sources;
+int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                        const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
+                        yawhip_shear_sources **out);
+int yawhip_shear_free(yawhip_shear_sources *sources);
+int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                       const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
+                       double *fine_w, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
-                           crosscorrelate_scalar, crosscorrelate_scalar_map)
+                           crosscorrelate_scalar, crosscorrelate_scalar_map, crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -54,6 +54,7 @@ __all__ = [
     "crosscorrelate",
     "crosscorrelate_scalar",
     "crosscorrelate_scalar_map",
+    "crosscorrelate_shear",
     "healpix",
     "patches",
     "randoms",

@@ -57,6 +57,9 @@ ABI_SYMBOLS = (
     "yawhip_kmeans_step",
     "yawhip_kmeans_query",
     "yawhip_kmeans_close",
+    "yawhip_shear_upload",
+    "yawhip_shear_free",
+    "yawhip_shear_count",
 )
 
 
@@ -261,6 +264,11 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_kmeans_query.argtypes = [_vp, ctypes.c_int32, _i64p]
     lib.yawhip_kmeans_close.argtypes = [_vp]
     lib.yawhip_kmeans_close.restype = None
+    lib.yawhip_shear_upload.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, _i64p, ctypes.c_int32,
+                                        ctypes.POINTER(_vp)]
+    lib.yawhip_shear_free.argtypes = [_vp]
+    lib.yawhip_shear_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                       ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -316,6 +324,7 @@ class Context:
         self.strip_grid = 1  # the library's default: strip grid uniform in latitude
         self._catalogs = weakref.WeakSet()  # live catalogues: freed before the context (a catalogue's free reads its context)
         self._kmeans = weakref.WeakSet()    # live k-means handles: they use the context's stream
+        self._shear = weakref.WeakSet()     # live shear-source handles: freed before the context, as the catalogues
 
     def set_option(self, key: str, value: int) -> None:
         _check(load_library().yawhip_ctx_set_option(self._h, key.encode(), int(value)), "yawhip_ctx_set_option")
@@ -330,6 +339,8 @@ class Context:
                 cat.free()
             for km in list(self._kmeans):
                 km.close()
+            for src in list(self._shear):
+                src.free()
             load_library().yawhip_ctx_destroy(self._h)
             self._h = _vp()
 
@@ -743,6 +754,61 @@ class KMeans:
             self.close()
         except Exception:
             pass
+
+
+class ShearSources:
+    """``yawhip_shear_sources``: a shear catalogue resident in HBM, every patch sorted along ``sort_axis`` -- unit vectors,
+    weights (or None) and the shear components ``g1, g2`` (east / north frame, include/yawhip.h); ``offsets`` int64[P + 1]
+    over the patches."""
+
+    def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2):
+        self._h = _vp()
+        x, y, z, w, g1, g2 = (_f64(c) for c in (x, y, z, w, g1, g2))
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(x)
+        if any(c is not None and len(c) != n for c in (y, z, w, g1, g2)):
+            raise ValueError("catalogue columns differ in length")
+        if len(offsets) != n_patches + 1:
+            raise ValueError("offsets must have n_patches + 1 entries")
+        self.ctx = ctx  # keep the context alive
+        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
+        _check(
+            load_library().yawhip_shear_upload(
+                ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(g1, _dp), _ptr(g2, _dp), self.n_patches,
+                _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
+            "yawhip_shear_upload",
+        )
+        ctx._shear.add(self)
+
+    def free(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            load_library().yawhip_shear_free(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs, thresholds):
+    """Run ``yawhip_shear_count``: jobs int[n_jobs, 2] = (lens patch, source patch); thresholds f64[B, E]. Returns
+    ``(T, X, W, CountStats)``: the tangential, cross and weight sums, f64[n_jobs, B, E-1] each."""
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError("thresholds must be [n_bins, n_edges]")
+    n_bins, n_edges = t.shape
+    shape = (len(jobs), n_bins, max(n_edges - 1, 0))
+    out = [np.empty(shape, dtype=np.float64) for _ in range(3)]  # the library writes every element
+    st = _Stats()
+    _check(
+        load_library().yawhip_shear_count(ctx._h, lenses._h, sources._h, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
+                                          *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
+        "yawhip_shear_count",
+    )
+    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
 
 
 def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,

@@ -234,6 +234,16 @@ class Patch:
         """Scalar-field values of the patch's objects, or ``None`` (patch.py:431-436)."""
         return None if self._cat._k is None else self._cat._k[self._lo : self._hi]
 
+    @property
+    def g1(self):
+        """First shear component of the patch's objects (east / north frame, see ``Catalog.from_arrays``), or ``None``."""
+        return None if self._cat._g1 is None else self._cat._g1[self._lo : self._hi]
+
+    @property
+    def g2(self):
+        """Second shear component of the patch's objects, or ``None``."""
+        return None if self._cat._g2 is None else self._cat._g2[self._lo : self._hi]
+
 
 class PatchLayout:
     """Device-ready layout of one catalogue for one redshift binning: float64 SoA columns sorted
@@ -242,10 +252,13 @@ class PatchLayout:
     This is the counterpart of ``build_trees`` (src/yaw/catalog/trees.py:365-429): objects outside
     the binning are dropped (:414), an unbinned catalogue has one segment per patch (:400-404)."""
 
-    __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent", "kappa", "twin")
+    __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent", "kappa", "twin", "g1", "g2",
+                 "shear_device")
 
-    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None) -> None:
+    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None, g1=None, g2=None) -> None:
         self.x, self.y, self.z, self.w = x, y, z, w
+        self.g1, self.g2 = g1, g2  # shear columns in the layout's order (unbinned layouts only), or None
+        self.shear_device = {}  # Context id -> ShearSources
         self.kappa = kappa  # scalar-field column in the layout's order, or None
         self.twin = None if kappa is None else ScalarTwin(self)  # the "k" side of a scalar count
         self.offsets = offsets
@@ -357,7 +370,7 @@ class Catalog(Mapping):
         return new
 
     def _setup(self, ra, dec, *, patch_ids, num_patches: int | None = None, weights=None, redshifts=None, kappa=None,
-               patch_centers: AngularCoordinates | None = None, cache_directory=None, stored_meta=None,
+               g1=None, g2=None, patch_centers: AngularCoordinates | None = None, cache_directory=None, stored_meta=None,
                xyz=None) -> None:
         """Common initialiser; coordinates in radian. ``xyz`` = ``radec_to_xyz(ra, dec)`` if already known."""
         ra = np.asarray_chkfinite(ra, dtype=np.float64)
@@ -381,12 +394,16 @@ class Catalog(Mapping):
         weights = None if weights is None else np.asarray_chkfinite(weights, dtype=np.float64)
         redshifts = None if redshifts is None else np.asarray_chkfinite(redshifts, dtype=np.float64)
         kappa = None if kappa is None else np.asarray_chkfinite(kappa, dtype=np.float64)
-        if any(c is not None and len(c) != len(ra) for c in (weights, redshifts, kappa)):
+        if (g1 is None) != (g2 is None):
+            raise ValueError("shear needs both components: give 'g1' and 'g2', or neither")
+        g1 = None if g1 is None else np.asarray_chkfinite(g1, dtype=np.float64)
+        g2 = None if g2 is None else np.asarray_chkfinite(g2, dtype=np.float64)
+        if any(c is not None and len(c) != len(ra) for c in (weights, redshifts, kappa, g1, g2)):
             raise ValueError("input columns differ in length")
         # unit vectors: computed once per catalogue (assignment, patch metadata and the device layouts all use
         # these values -- the exact host numbers the pair predicate runs on)
         xyz = radec_to_xyz(ra, dec) if xyz is None else tuple(np.asarray(c, dtype=np.float64) for c in xyz)
-        columns = [ra, dec, *xyz] + [c for c in (weights, redshifts, kappa) if c is not None]
+        columns = [ra, dec, *xyz] + [c for c in (weights, redshifts, kappa, g1, g2) if c is not None]
         grouped = False
         if np.all(patch_ids[1:] >= patch_ids[:-1]):
             # already grouped by patch (a restored cache): the stable order is the identity. The catalogue keeps its own copy
@@ -409,6 +426,8 @@ class Catalog(Mapping):
         self._w = None if weights is None else next(rest)
         self._z = None if redshifts is None else next(rest)
         self._k = None if kappa is None else next(rest)  # scalar field ("kappa"), carried like any other column
+        self._g1 = None if g1 is None else next(rest)    # shear components, carried the same way
+        self._g2 = None if g2 is None else next(rest)
         self._patch_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         self._layouts: dict = {}
         self._active_layout = None
@@ -438,17 +457,26 @@ class Catalog(Mapping):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_arrays(cls, ra, dec, *, weights=None, redshifts=None, kappa=None, patch_centers=None, patch_ids=None,
-                    patch_num: int | None = None, degrees: bool = True, cache_directory=None, overwrite: bool = False,
-                    probe_size: int = -1, patch_method: str = "probe"):
+    def from_arrays(cls, ra, dec, *, weights=None, redshifts=None, kappa=None, g1=None, g2=None, flip_g2: bool = False,
+                    patch_centers=None, patch_ids=None, patch_num: int | None = None, degrees: bool = True,
+                    cache_directory=None, overwrite: bool = False, probe_size: int = -1, patch_method: str = "probe"):
         """Build from plain arrays. One of ``patch_centers`` (nearest-centre assignment),
         ``patch_ids`` (pre-assigned, contiguous from 0) or ``patch_num`` (k-means) is required, with
         that precedence (``PatchMode.determine``, catalog.py:95-167). ``patch_method`` says which k-means ``patch_num``
         runs: ``"probe"``, :func:`kmeans_centers` on a probe sample, or ``"full"``, the deterministic k-means of
         :mod:`~yet_another_wizz_amd.patches` over all objects with the catalogue's weights (on the GPU when there is one);
-        it is ignored where centres or ids take precedence."""
+        it is ignored where centres or ids take precedence.
+
+        ``g1`` / ``g2`` (both or neither) attach a shear for ``crosscorrelate_shear``, given in the local frame whose first
+        axis points east (+RA) and whose second axis points north: ``g1 > 0`` is an elongation along east-west, ``g2 > 0``
+        one along the diagonal between +east and +north. Catalogues in the opposite handedness pass ``flip_g2=True``,
+        which stores ``-g2``."""
         if patch_method not in PATCH_METHODS:
             raise ValueError(f"'patch_method' must be one of {PATCH_METHODS}, got {patch_method!r}")
+        if (g1 is None) != (g2 is None):
+            raise ValueError("shear needs both components: give 'g1' and 'g2', or neither")
+        if g2 is not None and flip_g2:
+            g2 = -np.asarray(g2, dtype=np.float64)
         ra = np.asarray_chkfinite(ra, dtype=np.float64)
         dec = np.asarray_chkfinite(dec, dtype=np.float64)
         if degrees:  # datachunk.py:265-267
@@ -488,7 +516,7 @@ class Catalog(Mapping):
             patch_ids = nearest_center(xyz, centers.to_3d())
             num = len(centers)
         new = cls._from_columns(ra, dec, patch_ids=patch_ids, num_patches=num, weights=weights, redshifts=redshifts,
-                                kappa=kappa, patch_centers=centers, cache_directory=None, xyz=xyz)
+                                kappa=kappa, g1=g1, g2=g2, patch_centers=centers, cache_directory=None, xyz=xyz)
         if cache_directory is not None:
             new.to_cache(cache_directory, overwrite=overwrite)
         return new
@@ -498,13 +526,15 @@ class Catalog(Mapping):
                        redshift_name: str | None = None, patch_centers=None, patch_name: str | None = None,
                        patch_num: int | None = None, kappa_name: str | None = None, degrees: bool = True,
                        overwrite: bool = False, progress: bool = False, max_workers: int | None = None,
-                       chunksize: int | None = None, probe_size: int = -1, patch_method: str = "probe", **reader_kwargs):
+                       chunksize: int | None = None, probe_size: int = -1, patch_method: str = "probe",
+                       g1_name: str | None = None, g2_name: str | None = None, flip_g2: bool = False, **reader_kwargs):
         """Same signature as ``yaw.Catalog.from_dataframe`` (catalog.py:980-1108). ``dataframe`` may
         be a pandas DataFrame or any mapping from column name to array. ``cache_directory`` may be
         ``None`` (nothing is written: the catalogue lives in memory and in HBM); a path gets a cache in
         the reference's on-disk format, readable by both packages (``overwrite`` as in the reference).
         ``kappa_name`` names a column of scalar-field values (convergence, a shear amplitude, ...) for
-        ``autocorrelate_scalar`` / ``crosscorrelate_scalar``. ``patch_method``: see :meth:`from_arrays`."""
+        ``autocorrelate_scalar`` / ``crosscorrelate_scalar``; ``g1_name`` / ``g2_name`` name the two shear columns for
+        ``crosscorrelate_shear`` (frame and ``flip_g2``: see :meth:`from_arrays`). ``patch_method``: see :meth:`from_arrays`."""
         if patch_name is not None and not isinstance(patch_name, str):
             raise TypeError("'patch_name' must be a string")
 
@@ -514,7 +544,8 @@ class Catalog(Mapping):
         use_ids = patch_centers is None and patch_name is not None
         return cls.from_arrays(
             column(ra_name), column(dec_name), weights=column(weight_name), redshifts=column(redshift_name),
-            kappa=column(kappa_name), patch_centers=patch_centers, patch_ids=column(patch_name) if use_ids else None, patch_num=patch_num,
+            kappa=column(kappa_name), g1=column(g1_name), g2=column(g2_name), flip_g2=flip_g2, patch_centers=patch_centers,
+            patch_ids=column(patch_name) if use_ids else None, patch_num=patch_num,
             degrees=degrees, cache_directory=cache_directory, overwrite=overwrite, probe_size=probe_size,
             patch_method=patch_method,
         )
@@ -522,11 +553,12 @@ class Catalog(Mapping):
     @classmethod
     def from_file(cls, cache_directory, path, *, ra_name: str, dec_name: str, weight_name: str | None = None,
                   redshift_name: str | None = None, patch_centers=None, patch_name: str | None = None,
-                  patch_num: int | None = None, kappa_name: str | None = None, degrees: bool = True, **kwargs):
+                  patch_num: int | None = None, kappa_name: str | None = None, degrees: bool = True,
+                  g1_name: str | None = None, g2_name: str | None = None, **kwargs):
         """Parquet (``.pqt/.parquet``) or ``.npz`` input (reference: catalog.py:1111-1243; FITS and
         HDF5 readers need libraries that are outside this build's scope)."""
         path = Path(path)
-        names = [n for n in (ra_name, dec_name, weight_name, redshift_name, patch_name, kappa_name) if n is not None]
+        names = [n for n in (ra_name, dec_name, weight_name, redshift_name, patch_name, kappa_name, g1_name, g2_name) if n is not None]
         if path.suffix.lower() in (".pqt", ".parquet"):
             import pyarrow.parquet as pq
 
@@ -539,7 +571,8 @@ class Catalog(Mapping):
             raise ValueError(f"unsupported file type '{path.suffix}' (supported: .pqt, .parquet, .npz)")
         return cls.from_dataframe(cache_directory, frame, ra_name=ra_name, dec_name=dec_name, weight_name=weight_name,
                                   redshift_name=redshift_name, patch_centers=patch_centers, patch_name=patch_name,
-                                  patch_num=patch_num, kappa_name=kappa_name, degrees=degrees, **kwargs)
+                                  patch_num=patch_num, kappa_name=kappa_name, degrees=degrees, g1_name=g1_name, g2_name=g2_name,
+                                  **kwargs)
 
     @classmethod
     def from_random(cls, cache_directory, generator, num_randoms: int, *, patch_centers=None, patch_num: int | None = None,
@@ -658,6 +691,10 @@ class Catalog(Mapping):
     def has_kappa(self) -> bool:
         return self._k is not None
 
+    @property
+    def has_shear(self) -> bool:
+        return self._g1 is not None
+
     def get_num_records(self) -> tuple:
         return tuple(p.meta.num_records for p in self.values())
 
@@ -673,11 +710,14 @@ class Catalog(Mapping):
     # ------------------------------------------------------------------ cache on disk
     def to_cache(self, cache_directory, *, overwrite: bool = False) -> None:
         """Write the catalogue in the reference's cache format (``patch_ids.bin``, ``patch_<id>/data.bin``,
-        ``patch_<id>/meta.yml``); restore with ``Catalog(cache_directory)`` here or in the reference."""
+        ``patch_<id>/meta.yml``); restore with ``Catalog(cache_directory)`` here or in the reference. A catalogue with shear
+        columns raises ``ValueError``: the format has no place for them."""
         import shutil
 
         import yaml
 
+        if self.has_shear:  # data.bin has no place for the two columns
+            raise ValueError("a catalogue with shear columns cannot be written to a cache")
         directory = Path(cache_directory)
         if directory.exists():
             if not overwrite:
@@ -719,7 +759,7 @@ class Catalog(Mapping):
         x, y, z = self._unit_vectors()
         num_patches = self.num_patches
         if bins is None:
-            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1, kappa=self._k)
+            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1, kappa=self._k, g1=self._g1, g2=self._g2)
         else:
             num_bins = len(bins)
             bin_idx = bins.assign(self._z)
@@ -759,5 +799,8 @@ class Catalog(Mapping):
                 for dev in held.device.values():
                     dev.free()
                 held.device.clear()
+            for src in layout.shear_device.values():
+                src.free()
+            layout.shear_device.clear()
         self._layouts.clear()
         self._active_layout = None

@@ -1,0 +1,385 @@
+// yawhip_shear.hip -- tangential and cross shear of a source catalogue around the lenses of a catalogue binned in redshift
+// (yawhip_shear_*, include/yawhip.h; the host side: measurements.crosscorrelate_shear).
+//
+// A pair (lens l, source s) belongs to fine bin e of redshift bin k by the predicate of yawhip_count_pairs, bit for bit:
+//   s2 = ((sx - lx)^2 + (sy - ly)^2) + (sz - lz)^2,   t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
+// and then adds, with (x, y, z) the source and (lx, ly, lz) the lens,
+//   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
+//   c2 = (a a - b b) / den,   s2p = (2 a b) / den       cos / sin of twice the position angle of the lens seen from the
+//                                                       source, from east towards north (the 1 / rho of the local basis
+//                                                       cancels: no square root, no trigonometry)
+//   T += w_l * -(wg1 c2 + wg2 s2p)     X += w_l * (wg1 s2p - wg2 c2)     W += w_l * w_s        (wg = w_s g, made at upload)
+// den == 0 (the source sits on a pole of the frame): W only.
+//
+//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products.
+//   k_count_shear    one workgroup per (job, bin) cell. Lanes hold 256 sources of the job's source patch in registers, the
+//                    cell's lens segment streams through LDS 256 objects at a time (double-buffered); per lane tile only
+//                    the window of lenses whose sort key lies within the chord sqrt(t_max) of the tile's keys. The hot
+//                    loop is the 8-flop separation of k_count behind a wave-wide ballot; the division runs once per pair
+//                    inside the outer edge. Sums go to one float64 LDS histogram [3][E-1] per wave that only its own wave
+//                    adds to (the reproducibility assumption of the band kernels: adds of ONE instruction to one cell are
+//                    serialised by the LDS in a fixed lane order); the four are folded in a fixed order and stored with
+//                    plain stores. No floating-point atomic touches global memory.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "yawhip_shear.h"
+
+using namespace yawhip_detail;
+
+namespace {
+
+constexpr int WG = 256;      // threads per workgroup = 4 waves of 64 = sources per lane tile
+constexpr int WAVES = WG / 64;
+constexpr int STAGE = 256;   // streamed lenses per LDS stage (one per thread)
+constexpr int MAX_EDGES = 256;     // 4 histograms [3][E-1] + thresholds + two stages stay below 48 KiB of LDS
+constexpr double PAD_COORD = 4.0;  // padded lanes sit >= 3 away from any unit vector (as k_count parks them)
+
+struct alignas(16) Obj {  // one streamed lens in LDS: two 16-byte broadcast reads
+    double x, y, z, w;
+};
+
+size_t lds_bytes(int n_edges) {
+    return 2 * STAGE * sizeof(Obj) + (size_t)((n_edges + 1) & ~1) * sizeof(double) + (size_t)WAVES * 3 * (n_edges - 1) * sizeof(double);
+}
+
+__global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
+                               const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
+                               const double *__restrict__ sg1, const double *__restrict__ sg2, double *__restrict__ x,
+                               double *__restrict__ y, double *__restrict__ z, double *__restrict__ w, double *__restrict__ wg1,
+                               double *__restrict__ wg2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = perm[i];
+    x[i] = sx[j];
+    y[i] = sy[j];
+    z[i] = sz[j];
+    const double g1 = sg1[j], g2 = sg2[j];
+    if (sw) {
+        const double wj = sw[j];
+        w[i] = wj;
+        wg1[i] = wj * g1;
+        wg2[i] = wj * g2;
+    } else {
+        wg1[i] = g1;
+        wg2[i] = g2;
+    }
+}
+
+// out: [3][n_cells][E-1] (T, X, W), every element written; evaluated: [n_cells] separations the cell's workgroup evaluated
+__global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src, const int32_t *__restrict__ jobs, int n_bins,
+                                                    int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
+                                                    int64_t n_cells, double *__restrict__ out,
+                                                    unsigned long long *__restrict__ evaluated) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Obj *stage = reinterpret_cast<Obj *>(lds_raw);                                  // [2][STAGE]
+    double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(Obj));    // [n_edges]
+    double *hist = thr + ((n_edges + 1) & ~1);                                      // [WAVES][3][nf]
+
+    const int tid = threadIdx.x;
+    const int nf = n_edges - 1;
+    const int64_t cell = blockIdx.x;
+    const int64_t job = cell / n_bins;
+    const int k = (int)(cell - job * n_bins);
+    const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+    const int64_t lseg = p * lens.nb + (lens.nb == 1 ? 0 : k);
+    const int64_t seg0 = lens.off[lseg], seg1 = lens.off[lseg + 1];
+    const int64_t a_beg = src.off[q], a_end = src.off[q + 1];
+
+    for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
+    for (int j = tid; j < WAVES * 3 * nf; j += WG) hist[j] = 0.0;
+    const double tmax = t[(int64_t)k * n_edges + n_edges - 1];
+    const double rw = rwin[k];
+    const bool windowed = lens.axis == src.axis;  // else the keys say nothing about each other: the whole segment
+    double *wh = hist + (tid >> 6) * 3 * nf;      // this wave's histogram
+    unsigned long long work = 0;
+    __syncthreads();
+
+    for (int64_t ta = a_beg; ta < a_end && seg1 > seg0; ta += WG) {
+        const int64_t t_last = (ta + WG < a_end ? ta + WG : a_end) - 1;
+        // lenses that can hold partners of the tile: keys in [first key - rw, last key + rw]; rw = sqrt(t_max) widened for
+        // every rounding of s2 >= du^2 (1 - 2 eps) and of the two bounds themselves (yawhip_shear_count)
+        int64_t b0 = seg0, b1 = seg1;
+        if (windowed) {
+            const double wlo = src.key[ta] - rw, whi = src.key[t_last] + rw;
+            int64_t l = seg0, h = seg1;  // first index with key >= wlo
+            while (l < h) {
+                const int64_t m = (l + h) >> 1;
+                if (lens.key[m] < wlo) l = m + 1; else h = m;
+            }
+            b0 = l;
+            h = seg1;  // first index with key > whi
+            while (l < h) {
+                const int64_t m = (l + h) >> 1;
+                if (lens.key[m] <= whi) l = m + 1; else h = m;
+            }
+            b1 = l;
+        }
+        const int64_t nb_total = b1 - b0;
+        if (nb_total <= 0) continue;  // (the same for every thread)
+        work += (unsigned long long)(t_last - ta + 1) * (unsigned long long)nb_total;
+
+        // this lane's source -> registers; padded lanes are parked far away
+        const int64_t ia = ta + tid;
+        const bool ok = ia < a_end;
+        const double ax = ok ? src.x[ia] : PAD_COORD;
+        const double ay = ok ? src.y[ia] : PAD_COORD;
+        const double az = ok ? src.z[ia] : PAD_COORD;
+        const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
+        const double ag1 = ok ? src.wg1[ia] : 0.0;
+        const double ag2 = ok ? src.wg2[ia] : 0.0;
+        const double rho2 = ax * ax + ay * ay;
+
+        const int nstages = (int)((nb_total + STAGE - 1) / STAGE);
+        {  // stage 0 (the barrier that ended the previous tile's last stage has freed both buffers)
+            const int64_t i = b0 + tid;
+            const bool have = i < b1;
+            Obj o;
+            o.x = have ? lens.x[i] : 0.0; o.y = have ? lens.y[i] : 0.0; o.z = have ? lens.z[i] : 0.0;
+            o.w = (have && lens.w) ? lens.w[i] : 1.0;
+            stage[tid] = o;
+        }
+        __syncthreads();
+
+        for (int st = 0; st < nstages; ++st) {
+            const Obj *cur = stage + (st & 1) * STAGE;
+            Obj nxt;  // the next stage's global loads are issued early: they land in registers while this one is computed
+            const bool have_next = st + 1 < nstages;
+            if (have_next) {
+                const int64_t i = b0 + (int64_t)(st + 1) * STAGE + tid;
+                const bool have = i < b1;
+                nxt.x = have ? lens.x[i] : 0.0; nxt.y = have ? lens.y[i] : 0.0; nxt.z = have ? lens.z[i] : 0.0;
+                nxt.w = (have && lens.w) ? lens.w[i] : 1.0;
+            }
+            const int64_t left = nb_total - (int64_t)st * STAGE;
+            const int n = left < STAGE ? (int)left : STAGE;
+            for (int i = 0; i < n; ++i) {
+                const Obj b = cur[i];  // wave-wide broadcast read
+                const double dx = ax - b.x;
+                const double dy = ay - b.y;
+                const double dz = az - b.z;
+                const double xx = dx * dx;
+                const double yy = dy * dy;
+                const double zz = dz * dz;
+                const double sxy = xx + yy;
+                const double s = sxy + zz;
+                if (__builtin_amdgcn_ballot_w64(s <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
+                    if (ok && s <= tmax) {
+                        int cnt = 0, hi = n_edges;  // edges below s (they ascend): the first e with thr[e] >= s, by bisection
+                        while (cnt < hi) {
+                            const int mid = (cnt + hi) >> 1;
+                            if (thr[mid] < s) cnt = mid + 1; else hi = mid;
+                        }
+                        if (cnt > 0) {  // t[cnt-1] < s <= t[cnt]
+                            const double pa = ax * b.y - ay * b.x;
+                            const double dot = ax * b.x + ay * b.y;
+                            const double pb = rho2 * b.z - az * dot;
+                            const double a2 = pa * pa;
+                            const double b2 = pb * pb;
+                            const double den = a2 + b2;
+                            if (den != 0.0) {
+                                const double c2 = (a2 - b2) / den;
+                                const double s2 = ((2.0 * pa) * pb) / den;
+                                const double tv = -(ag1 * c2 + ag2 * s2);
+                                const double xv = ag1 * s2 - ag2 * c2;
+                                atomicAdd(&wh[cnt - 1], b.w * tv);
+                                atomicAdd(&wh[nf + cnt - 1], b.w * xv);
+                            }
+                            atomicAdd(&wh[2 * nf + cnt - 1], b.w * aw);
+                        }
+                    }
+                }
+            }
+            if (have_next) stage[((st + 1) & 1) * STAGE + tid] = nxt;
+            __syncthreads();
+        }
+    }
+
+    __syncthreads();
+    const int64_t plane = n_cells * nf;
+    for (int j = tid; j < 3 * nf; j += WG) {  // the four waves' histograms in a fixed order
+        const double v = ((hist[j] + hist[3 * nf + j]) + hist[2 * 3 * nf + j]) + hist[3 * 3 * nf + j];
+        const int c = j / nf;
+        out[(int64_t)c * plane + cell * nf + (j - c * nf)] = v;
+    }
+    if (tid == 0) evaluated[cell] = work;
+}
+
+}  // namespace
+
+extern "C" {
+
+int yawhip_shear_free(yawhip_shear_sources *src) {
+    if (!src) return YAWHIP_OK;
+    if (src->ctx) {
+        (void)hipSetDevice(src->ctx->device);
+        if (src->ctx->stream) (void)hipStreamSynchronize(src->ctx->stream);
+    }
+    delete src;  // its device memory goes with it
+    return YAWHIP_OK;
+}
+
+int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                        const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
+                        yawhip_shear_sources **out) {
+    if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: ctx is NULL");
+    if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
+    if (n < 0 || n_patches <= 0 || !offsets || (n > 0 && (!x || !y || !z || !g1 || !g2)))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: bad sizes or NULL columns");
+    if (n >= (1ll << 32)) return fail(YAWHIP_ERR_INVALID, "at most 2^32 - 1 objects per catalogue");
+    if (offsets[0] != 0 || offsets[n_patches] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
+    for (int32_t i = 0; i < n_patches; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
+    HIP_TRY(hipSetDevice(ctx->device));
+    yawhip_shear_sources *s = new (std::nothrow) yawhip_shear_sources;
+    if (!s) return fail(YAWHIP_ERR_OOM, "yawhip_shear_upload: out of host memory");
+    s->ctx = ctx;
+    s->n = n;
+    s->n_patches = n_patches;
+    s->axis = sort_axis;
+    try {
+        s->h_off.assign(offsets, offsets + n_patches + 1);
+    } catch (const std::bad_alloc &) {
+        delete s;
+        return fail(YAWHIP_ERR_OOM, "yawhip_shear_upload: out of host memory");
+    }
+    const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
+    DevPtr<double> raw[6];  // x, y, z, g1, g2, w as they came (temporary)
+    const double *host[6] = {x, y, z, g1, g2, w};
+    DevPtr<uint32_t> perm;
+    hipError_t e = hipSuccess;
+    for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
+        if (e == hipSuccess) e = c->alloc(n1);
+    if (e == hipSuccess && w) e = s->w.alloc(n1);
+    if (e == hipSuccess) e = s->off.alloc((size_t)n_patches + 1);
+    for (int c = 0; c < 6; ++c)
+        if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
+    if (e == hipSuccess) e = perm.alloc(n1);
+    for (int c = 0; c < 6; ++c)
+        if (e == hipSuccess && host[c] && n > 0) e = hipMemcpyAsync(raw[c], host[c], col, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(s->off, offsets, ((size_t)n_patches + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && n > 0) {
+        e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_patches, perm);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
+                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (ctx->sort_ws.cap > ((size_t)1 << 25)) ctx->sort_ws.release();  // as the catalogue upload: keep only small workspaces
+    if (e != hipSuccess) {
+        yawhip_shear_free(s);
+        return hip_fail("yawhip_shear_upload", e);
+    }
+    *out = s;
+    return YAWHIP_OK;
+}
+
+int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                       const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
+                       double *fine_w, yawhip_stats *stats) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    // the argument checks of a count call (check_call), before any device work
+    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
+    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && (!jobs || !fine_t || !fine_x || !fine_w)))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
+                    n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (lenses->n_patches != sources->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
+    if (lenses->nb != 1 && lenses->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+    for (int k = 0; k < n_bins; ++k)
+        for (int e = 0; e < n_edges; ++e) {
+            const double v = t[(size_t)k * n_edges + e];
+            if (!(v >= 0.0) || (e > 0 && !(v >= t[(size_t)k * n_edges + e - 1])))
+                return fail(YAWHIP_ERR_INVALID, "thresholds of bin %d are not ascending non-negative numbers", k);
+        }
+    for (int j = 0; j < n_jobs; ++j)
+        if (jobs[2 * j] < 0 || jobs[2 * j] >= lenses->n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= lenses->n_patches)
+            return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, lenses->n_patches);
+    const int64_t n_cells = (int64_t)n_jobs * n_bins, nf = n_edges - 1;
+    if (n_cells > INT32_MAX) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: more than 2^31 - 1 (job, bin) cells");
+    if (stats) *stats = yawhip_stats{};
+    if (n_jobs == 0) return YAWHIP_OK;
+
+    // one table in: thresholds [B][E], window half widths [B], jobs [n_jobs][2]
+    const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + 2 * (size_t)n_jobs * sizeof(int32_t);
+    std::vector<unsigned char> h_in;
+    int64_t candidates = 0;
+    try {
+        h_in.resize(in_bytes);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "yawhip_shear_count: out of host memory");
+    }
+    double *h_t = reinterpret_cast<double *>(h_in.data()), *h_rwin = h_t + n_t;
+    memcpy(h_t, t, n_t * sizeof(double));
+    // a pair passes s2 <= t_max only if |du| <= sqrt(t_max) (1 + 2 eps) along any axis u (s2 >= fl(du^2), du rounded once);
+    // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
+    for (int k = 0; k < n_bins; ++k) h_rwin[k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
+    memcpy(h_rwin + n_bins, jobs, 2 * (size_t)n_jobs * sizeof(int32_t));
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
+        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
+        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
+                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
+        candidates += n_src * n_lens;
+    }
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->make_events());
+    const size_t n_out = 3 * (size_t)n_cells * (size_t)nf;
+    HIP_TRY(sources->d_in.reserve(in_bytes, in_bytes / 4 + 64));
+    HIP_TRY(sources->d_out.reserve(n_out + (size_t)n_cells, n_out / 4 + 64));
+    HIP_TRY(hipMemcpyAsync(sources->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const double *d_t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr);
+    const double *d_rwin = d_t + n_t;
+    const int32_t *d_jobs = reinterpret_cast<const int32_t *>(d_rwin + n_bins);
+    double *d_out = sources->d_out.ptr;
+    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
+    const ShearView sv{sources->x, sources->y, sources->z, sources->w, sources->wg1, sources->wg2, sources->off,
+                       key_of(sources->x, sources->y, sources->z, sources->axis), sources->axis};
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges), ctx->stream, view_of(lenses), sv, d_jobs,
+                       n_bins, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    const size_t plane = (size_t)n_cells * (size_t)nf;
+    HIP_TRY(hipMemcpyAsync(fine_t, d_out, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fine_x, d_out + plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fine_w, d_out + 2 * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<unsigned long long> h_eval;
+    if (stats) {
+        try {
+            h_eval.resize((size_t)n_cells);
+        } catch (const std::bad_alloc &) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return fail(YAWHIP_ERR_OOM, "yawhip_shear_count: out of host memory");
+        }
+        HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, (size_t)n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        stats->candidate_pairs = candidates;
+        for (unsigned long long v : h_eval) stats->evaluated_pairs += (int64_t)v;
+        stats->n_workgroups = n_cells;
+        stats->n_launches = 1;
+        stats->kernel_ms = stats->count_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    }
+    return YAWHIP_OK;
+}
+
+}  // extern "C"

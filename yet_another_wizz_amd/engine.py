@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -167,6 +167,28 @@ def count_rows_device(layout1, layout2, jobs, thresholds, n_rows_total: int, row
     (``yawhip_count_pairs_rows_device``) -> (``_lib.DeviceRows``, CountStats)."""
     ctx, d1, d2 = _device_pair(layout1, layout2, thresholds, sort_axis)
     return _lib.count_pairs_rows_device(ctx, d1, d2, jobs, thresholds, n_rows_total, row_index, kernel=kernel or default_kernel)
+
+
+def count_shear_fine(lens_layout, source_layout, jobs, thresholds, *, sort_axis: int = 2):
+    """Fine-bin shear sums for ``jobs`` (int[n, 2] = (lens patch, source patch)) -> ``(T, X, W, CountStats)``, f64[n_jobs, B, E-1]
+    each: tangential and cross shear sums and the sum of ``w_l * w_s`` of the pairs (``yawhip_shear_count``). The lenses are the
+    resident catalogue of ``lens_layout``; the sources (an unbinned layout with ``g1`` / ``g2``) reach the device once per
+    context as a ``_lib.ShearSources`` kept on the layout, replaced when another sort axis is asked for. On a context of
+    several devices the count runs on its first one. No CPU fallback; the CPU tests replace this function."""
+    if source_layout.g1 is None or source_layout.g2 is None:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    ctx = get_context()
+    micro = forced_strip_micro if forced_strip_micro is not None else strip_micro_for(thresholds)
+    lenses = device_catalog(lens_layout, ctx, sort_axis, micro, exact=forced_strip_micro is not None)
+    sources = source_layout.shear_device.get(id(ctx))
+    if sources is not None and (sources.sort_axis != sort_axis or not sources._h):
+        sources.free()
+        sources = None
+    if sources is None:
+        sources = source_layout.shear_device[id(ctx)] = _lib.ShearSources(
+            ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1, source_layout.g2,
+            source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis)
+    return _lib.shear_count(ctx, lenses, sources, jobs, thresholds)
 
 
 def _device_pair(layout1, layout2, thresholds, sort_axis, max_workers=None):

@@ -25,7 +25,7 @@ from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
 __all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
-           "compute_scalar_normalisation",
+           "crosscorrelate_shear", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -478,6 +478,35 @@ class PatchLinkage:
         return [[NormalisedScalarCounts(kk.counts, nn.counts) for kk, nn in zip(results[2 * k], results[2 * k + 1])]
                 for k in range(len(counts))]
 
+    def count_shear_pairs(self, lenses: Catalog, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
+                          count_type_info: str | None = None) -> list:
+        """Shear of ``sources`` (unbinned, with ``g1`` / ``g2``) around ``lenses`` (binned in redshift) over the linked patch
+        pairs -> per scale ``(NormalisedScalarCounts(T, W), NormalisedScalarCounts(X, W))``: the sums of the tangential and of
+        the cross shear of the pairs, each over the sum of their weights ``w_l * w_s``. Thresholds, separation weights and
+        per-scale sums are those of ``count_pairs``; ONE library call counts all jobs (``engine.count_shear_fine``), on one
+        device of one process: several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("shear counts run in one process on one device")
+        if count_type_info is not None:
+            _log_info("counting %s from patch pairs", count_type_info)
+        binning = self.config.binning.binning
+        num_bins, num_patches = len(binning), len(lenses)
+        lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
+        if source_layout.g1 is None or source_layout.g2 is None:
+            raise ValueError("catalog has no 'g1'/'g2' attached")
+        jobs = self.get_patch_pairs(lenses, sources)
+        _, thresholds = self._angular_setup()
+        *fine, stats = engine.count_shear_fine(lens_layout, source_layout, jobs, thresholds, sort_axis=self.sort_axis)
+        self.last_stats = stats
+        self._report(count_type_info, len(jobs), stats, progress)
+        flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
+        shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
+        # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
+        T, X, W = (_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine)
+        return [(NormalisedScalarCounts(PatchedCounts(binning, T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
+                 NormalisedScalarCounts(PatchedCounts(binning, X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
+                for s in range(shape[0])]
+
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
         """The reference logs every pair count and shows a progress bar over its patch-pair tasks
@@ -674,3 +703,33 @@ def crosscorrelate_scalar_map(config, reference: Catalog, scalar_map: Catalog, *
         DD = links.count_scalar_pairs(reference, scalar_map, mode="nk", count_type_info="DD", **kwargs)
         DR = [compute_scalar_normalisation(scalar_map, config.binning.binning)] * len(DD)
     return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]
+
+
+def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_rand: Catalog | None = None,
+                         progress: bool = False, max_workers: int | None = None) -> list:
+    """Tangential shear of ``sources`` (a catalogue with ``g1`` / ``g2``, no redshifts needed) around ``reference`` in its
+    redshift slices, and the cross shear as its null test: per redshift bin and scale ``gamma_t = sum T / sum W`` over the
+    pairs in range, minus the same ratio around the lenses of ``ref_rand`` when it is given (``gamma_x`` alike) ->
+    ``[(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)), ...]``, one pair per scale, ``dr = None`` without randoms.
+    A pair adds ``T = w_l w_s * -(g1 cos 2phi + g2 sin 2phi)`` and ``X = w_l w_s * (g1 sin 2phi - g2 cos 2phi)``, ``phi`` the
+    position angle of the lens seen from the source, from east towards north (frame of ``g1, g2``: ``Catalog.from_arrays``).
+
+    This driver has no counterpart in the reference. Linkage, scales, patches and jackknife are ``crosscorrelate``'s; the
+    count runs on one device of one process."""
+    _require_distinct(reference, sources, ref_rand)
+    if not sources.has_shear:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    edges, closed = config.binning.edges, config.binning.closed
+    randoms = []
+    _log_info("building reference data trees")
+    reference.build_trees(edges, closed=closed)
+    if ref_rand is not None:
+        ref_rand.build_trees(edges, closed=closed)
+        randoms.append(ref_rand)
+    sources.build_trees(None)
+    _log_info("computing shear cross-correlation with DD" + (", DR" if randoms else ""))
+    links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
+    kwargs = dict(progress=progress, max_workers=max_workers)
+    DD = links.count_shear_pairs(reference, sources, count_type_info="DD", **kwargs)
+    DR = links.count_shear_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
+    return [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
