@@ -501,7 +501,7 @@ void yawhip_kmeans_close(yawhip_kmeans *km);
  *   x, y, z      float64[n] unit vectors (host);  w  float64[n] weights or NULL (every weight 1.0)
  *   g1, g2       float64[n] shear components in the local frame whose first axis points east (+RA) and whose second axis
  *                points north: g1 > 0 stretches along east-west, g2 > 0 along the diagonal between +east and +north
- *   offsets      int64[n_patches + 1] CSR over the patches (sources are never binned); objects are grouped by patch
+ *   offsets      int64[n_patches + 1] CSR over the patches (these sources are not binned); objects are grouped by patch
  * yawhip_shear_free     frees the handle (NULL: nothing happens). Free it before its context is destroyed.
  * yawhip_shear_count    for every job (lens patch p, source patch q) and redshift bin k, over the pairs (lens l of segment
  *                       (p, k), source s of patch q) with t[k][e] < s2 <= t[k][e + 1] -- s2 and the thresholds exactly those of
@@ -530,6 +530,49 @@ int yawhip_shear_free(yawhip_shear_sources *sources);
 int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
                        const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
                        double *fine_w, yawhip_stats *stats);
+
+/*
+ * Shear-shear sums of ONE shear catalogue inside its own redshift bins: the numerators of xi_plus, xi_minus and of the
+ * parity-odd xi_cross (measurements.autocorrelate_shear; no counterpart in the reference). Additive to ABI 6: new symbols
+ * only, the opaque handle is the one above.
+ *
+ * yawhip_shear_upload_binned   yawhip_shear_upload for a catalogue grouped by (patch, redshift bin): offsets is
+ *                       int64[n_patches * n_bins + 1], every (patch, bin) segment is sorted along sort_axis. The handle
+ *                       carries n_bins; yawhip_shear_upload is the n_bins = 1 case. yawhip_shear_count refuses a handle with
+ *                       n_bins != 1 (YAWHIP_ERR_MISMATCH).
+ * yawhip_shear_auto_count      objects a, b of the same redshift bin k, unit vectors (ax, ay, az), (bx, by, bz), weights w (1.0
+ *                       without a weight column) and wg1 = w g1, wg2 = w g2 as the upload made them. Pair membership is that
+ *                       of every count: s2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2, fine bin e iff
+ *                       t[k][e] < s2 <= t[k][e + 1] -- a pair at s2 == 0 never counts, an object with itself included. A pair
+ *                       in a fine bin adds, in float64 with every product and sum rounded on its own,
+ *       pa   = ax by - ay bx                       dot = ax bx + ay by
+ *       pbA  = (ax ax + ay ay) bz - az dot         b seen from a: (east, north) cos(dec_a) = (pa, pbA)
+ *       pbB  = (bx bx + by by) az - bz dot         a seen from b: (-pa, pbB)
+ *       denA = pa pa + pbA pbA                     denB = pa pa + pbB pbB
+ *       cA = (pa pa - pbA pbA) / denA   sA = ((2 pa) pbA) / denA        cos, sin of twice the position angle at a
+ *       cB = (pa pa - pbB pbB) / denB   sB = ((-2 pa) pbB) / denB       cos, sin of twice the position angle at b
+ *       tA = -(wg1a cA + wg2a sA)       xA = wg1a sA - wg2a cA          the shear of a along / across the great circle
+ *       tB = -(wg1b cB + wg2b sB)       xB = wg1b sB - wg2b cB
+ *       fine_p += tA tB + xA xB     fine_m += tA tB - xA xB     fine_c += tA xB + xA tB     fine_w += w_a w_b
+ *     denA == 0 or denB == 0 (one of the two on a pole of the frame): fine_w only. All four terms are bit-symmetric under
+ *     swapping a and b. Cell (job (p, q), bin k, fine bin e) holds the sum over the pairs a in (p, k), b in (q, k) for p < q,
+ *     and over every UNORDERED pair {a, b} of segment (p, k) once for p == q (what an autocorrelation count holds after its
+ *     x 0.5 of the diagonal).
+ *   jobs         int32[n_jobs][2] with p <= q;  n_bins must be the handle's;  t  float64[B][E] as for yawhip_count_pairs,
+ *                E <= 256 (58 KiB of LDS at the cap: two stages of 48-byte objects, thresholds, four histograms [4][E-1])
+ *   fine_p, fine_m, fine_c, fine_w   float64[n_jobs][B][E-1] each (host); every element is written, a cell with an empty
+ *                segment is exactly 0
+ *   stats        as for yawhip_shear_count; candidate pairs count a diagonal cell's unordered pairs
+ * Kernel, accumulation and reproducibility as yawhip_shear_count (one workgroup per (job, bin) cell, one float64 LDS
+ * histogram per wave, plain stores); a diagonal cell walks only partners with a larger index. Errors: the checks of
+ * yawhip_shear_count, a job with p > q: YAWHIP_ERR_INVALID, a handle with another bin count: YAWHIP_ERR_MISMATCH.
+ */
+int yawhip_shear_upload_binned(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                               const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                               int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
+                            int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c, double *fine_w,
+                            yawhip_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -21,8 +21,8 @@ from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
-from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, compute_scalar_normalisation, crosscorrelate,
-                           crosscorrelate_scalar, crosscorrelate_scalar_map, crosscorrelate_shear)
+from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
+                           crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map, crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -50,6 +50,7 @@ __all__ = [
     "ScalarCorrFunc",
     "autocorrelate",
     "autocorrelate_scalar",
+    "autocorrelate_shear",
     "compute_scalar_normalisation",
     "crosscorrelate",
     "crosscorrelate_scalar",

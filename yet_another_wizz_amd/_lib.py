@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     "yawhip_shear_upload",
     "yawhip_shear_free",
     "yawhip_shear_count",
+    "yawhip_shear_upload_binned",
+    "yawhip_shear_auto_count",
 )
 
 
@@ -269,6 +271,10 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_shear_free.argtypes = [_vp]
     lib.yawhip_shear_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
                                        ctypes.POINTER(_Stats)]
+    lib.yawhip_shear_upload_binned.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32,
+                                               _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
+    lib.yawhip_shear_auto_count.argtypes = [_vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp,
+                                            ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -757,27 +763,31 @@ class KMeans:
 
 
 class ShearSources:
-    """``yawhip_shear_sources``: a shear catalogue resident in HBM, every patch sorted along ``sort_axis`` -- unit vectors,
-    weights (or None) and the shear components ``g1, g2`` (east / north frame, include/yawhip.h); ``offsets`` int64[P + 1]
-    over the patches."""
+    """``yawhip_shear_sources``: a shear catalogue resident in HBM, every (patch, bin) segment sorted along ``sort_axis`` -- unit
+    vectors, weights (or None) and the shear components ``g1, g2`` (east / north frame, include/yawhip.h); ``offsets``
+    int64[P * n_bins + 1] over the segments. ``n_bins = 1`` is the unbinned catalogue ``shear_count`` takes
+    (``yawhip_shear_upload``), more the binned one of ``shear_auto_count`` (``yawhip_shear_upload_binned``)."""
 
-    def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2):
+    def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2, n_bins: int = 1):
         self._h = _vp()
         x, y, z, w, g1, g2 = (_f64(c) for c in (x, y, z, w, g1, g2))
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(x)
         if any(c is not None and len(c) != n for c in (y, z, w, g1, g2)):
             raise ValueError("catalogue columns differ in length")
-        if len(offsets) != n_patches + 1:
-            raise ValueError("offsets must have n_patches + 1 entries")
+        if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
+            raise ValueError("offsets must have n_patches * n_bins + 1 entries")
         self.ctx = ctx  # keep the context alive
         self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
-        _check(
-            load_library().yawhip_shear_upload(
-                ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(g1, _dp), _ptr(g2, _dp), self.n_patches,
-                _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
-            "yawhip_shear_upload",
-        )
+        self.n_bins = int(n_bins)
+        columns = (ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(g1, _dp), _ptr(g2, _dp), self.n_patches)
+        if self.n_bins == 1:
+            _check(load_library().yawhip_shear_upload(*columns, _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
+                   "yawhip_shear_upload")
+        else:
+            _check(load_library().yawhip_shear_upload_binned(*columns, self.n_bins, _ptr(offsets, _i64p), self.sort_axis,
+                                                             ctypes.byref(self._h)),
+                   "yawhip_shear_upload_binned")
         ctx._shear.add(self)
 
     def free(self) -> None:
@@ -807,6 +817,26 @@ def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs
         load_library().yawhip_shear_count(ctx._h, lenses._h, sources._h, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
                                           *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
         "yawhip_shear_count",
+    )
+    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
+
+
+def shear_auto_count(ctx: Context, sources: ShearSources, jobs, thresholds):
+    """Run ``yawhip_shear_auto_count`` on a binned handle: jobs int[n_jobs, 2] = patch pairs with ``p <= q``; thresholds
+    f64[B, E]. Returns ``(P, M, C, W, CountStats)``: the numerators of xi_plus, xi_minus and xi_cross and the weight sums,
+    f64[n_jobs, B, E-1] each; a diagonal job holds every unordered pair once."""
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError("thresholds must be [n_bins, n_edges]")
+    n_bins, n_edges = t.shape
+    shape = (len(jobs), n_bins, max(n_edges - 1, 0))
+    out = [np.empty(shape, dtype=np.float64) for _ in range(4)]  # the library writes every element
+    st = _Stats()
+    _check(
+        load_library().yawhip_shear_auto_count(ctx._h, sources._h, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
+                                               *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
+        "yawhip_shear_auto_count",
     )
     return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
 

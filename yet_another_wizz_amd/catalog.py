@@ -257,7 +257,7 @@ class PatchLayout:
 
     def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None, g1=None, g2=None) -> None:
         self.x, self.y, self.z, self.w = x, y, z, w
-        self.g1, self.g2 = g1, g2  # shear columns in the layout's order (unbinned layouts only), or None
+        self.g1, self.g2 = g1, g2  # shear columns in the layout's order (unbinned layouts, and build_trees(with_shear=True)), or None
         self.shear_device = {}  # Context id -> ShearSources
         self.kappa = kappa  # scalar-field column in the layout's order, or None
         self.twin = None if kappa is None else ScalarTwin(self)  # the "k" side of a scalar count
@@ -745,14 +745,18 @@ class Catalog(Mapping):
         return self._xyz
 
     def build_trees(self, binning=None, *, closed=Closed.right, leafsize: int = 16, force: bool = False,
-                    progress: bool = False, max_workers: int | None = None) -> PatchLayout:
+                    progress: bool = False, max_workers: int | None = None, with_shear: bool = False) -> PatchLayout:
         """Prepare (and cache) the (patch, bin)-sorted layout for ``binning`` (array of edges or
         ``None``).  Keeps the name and arguments of ``yaw.Catalog.build_trees`` (catalog.py:1406-1461);
-        no tree is built -- ``leafsize`` is accepted and ignored."""
+        no tree is built -- ``leafsize`` is accepted and ignored. ``with_shear`` (no counterpart in the reference) makes a
+        binned layout carry ``g1`` / ``g2``, grouped with the other columns, for ``autocorrelate_shear``: a layout of its own
+        in the cache, next to the plain one of the same binning; the unbinned layout always carries them."""
         bins = None if binning is None else (binning if isinstance(binning, Binning) else Binning(binning, closed=closed))
+        if with_shear and not self.has_shear:
+            raise ValueError("catalog has no 'g1'/'g2' attached")
         if bins is not None and not self.has_redshifts:
             raise ValueError("patch has no 'redshifts' attached")  # trees.py:396-397
-        key = None if bins is None else (bins.edges.tobytes(), str(bins.closed))
+        key = None if bins is None else (bins.edges.tobytes(), str(bins.closed), *(("shear",) if with_shear else ()))
         if not force and key in self._layouts:
             self._active_layout = self._layouts[key]
             return self._active_layout
@@ -765,7 +769,8 @@ class Catalog(Mapping):
             bin_idx = bins.assign(self._z)
             patch_of = np.repeat(np.arange(num_patches), np.diff(self._patch_off))
             offsets = np.zeros(num_patches * num_bins + 1, dtype=np.int64)
-            columns = [x, y, z] + [c for c in (self._w, self._k) if c is not None]  # kappa is binned (and dropped) as the rest
+            shear = (self._g1, self._g2) if with_shear else ()
+            columns = [x, y, z] + [c for c in (self._w, self._k, *shear) if c is not None]  # kappa is binned (and dropped) as the rest
             grouped = False
             if len(x) >= HOST_GROUP_MIN:  # (patch, bin) grouping in one threaded pass; objects outside the binning dropped
                 from . import _lib
@@ -785,7 +790,8 @@ class Catalog(Mapping):
                 columns = [c[order] for c in columns]
             rest = iter(columns[3:])
             layout = PatchLayout(columns[0], columns[1], columns[2], None if self._w is None else next(rest), offsets,
-                                 num_patches, num_bins, kappa=None if self._k is None else next(rest))
+                                 num_patches, num_bins, kappa=None if self._k is None else next(rest),
+                                 g1=next(rest) if with_shear else None, g2=next(rest) if with_shear else None)
         self._layouts[key] = layout
         self._active_layout = layout  # what the next count_pairs() uses, like the cached trees.pkl
         return layout

@@ -1,5 +1,5 @@
-// Private to yawhip_shear.hip (tangential shear counts, yawhip_shear_*, include/yawhip.h): the source
-// handle and what its kernels see of it. Never installed, not part of the C ABI.
+// Private to yawhip_shear.hip (tangential shear and shear-shear counts, yawhip_shear_*, include/yawhip.h; DESIGN.md sections
+// 15 and 16): the source handle and what its kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -9,19 +9,21 @@
 
 #pragma GCC visibility push(hidden)  // (its destructor is not an export)
 
-// A shear catalogue resident on its context's device: the objects of every patch sorted along `axis`, never binned.
+// A shear catalogue resident on its context's device: the objects of every (patch, bin) segment sorted along `axis`; nb == 1
+// (yawhip_shear_upload) is the unbinned catalogue of yawhip_shear_count, nb redshift bins that of yawhip_shear_auto_count.
 struct yawhip_shear_sources {
     yawhip_ctx *ctx = nullptr;
     int64_t n = 0;
     int32_t n_patches = 0;
+    int32_t nb = 1;
     int axis = 2;                               // coordinate the patch segments are sorted by (0 = x, 1 = y, 2 = z)
     yawhip_detail::DevPtr<double> x, y, z, w;   // w may be null (every weight 1.0)
     yawhip_detail::DevPtr<double> wg1, wg2;     // w * g1, w * g2, each product rounded on its own (g1, g2 without weights)
-    yawhip_detail::DevPtr<int64_t> off;         // [P + 1]
+    yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;
-    // per-call buffers of yawhip_shear_count (grow-only)
+    // per-call buffers of the two counts (grow-only)
     yawhip_detail::DevBuf<unsigned char> d_in;  // thresholds, window half widths, jobs
-    yawhip_detail::DevBuf<double> d_out;        // [3][cells][E-1] sums, then [cells] evaluated pairs (64-bit integers)
+    yawhip_detail::DevBuf<double> d_out;        // [3 or 4][cells][E-1] sums, then [cells] evaluated pairs (64-bit integers)
 };
 
 namespace yawhip_detail {
@@ -29,8 +31,8 @@ namespace yawhip_detail {
 struct ShearView {
     const double *x, *y, *z, *w;  // w may be null
     const double *wg1, *wg2;
-    const int64_t *off;           // [P + 1]
-    const double *key;            // the column the patch segments are sorted by
+    const int64_t *off;           // [P * nb + 1]
+    const double *key;            // the column the segments are sorted by
     int axis;
 };
 

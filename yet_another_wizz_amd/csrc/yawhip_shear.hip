@@ -1,5 +1,6 @@
 // yawhip_shear.hip -- tangential and cross shear of a source catalogue around the lenses of a catalogue binned in redshift
-// (yawhip_shear_*, include/yawhip.h; the host side: measurements.crosscorrelate_shear).
+// (yawhip_shear_count; measurements.crosscorrelate_shear), and the shear-shear sums of a source catalogue
+// inside its own redshift bins (yawhip_shear_auto_count; measurements.autocorrelate_shear).
 //
 // A pair (lens l, source s) belongs to fine bin e of redshift bin k by the predicate of yawhip_count_pairs, bit for bit:
 //   s2 = ((sx - lx)^2 + (sy - ly)^2) + (sz - lz)^2,   t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
@@ -20,6 +21,18 @@
 //                    adds to (the reproducibility assumption of the band kernels: adds of ONE instruction to one cell are
 //                    serialised by the LDS in a fixed lane order); the four are folded in a fixed order and stored with
 //                    plain stores. No floating-point atomic touches global memory.
+//
+// Shear-shear: objects a, b of the same redshift bin k of ONE handle, the same predicate, and (include/yawhip.h has the whole
+// contract) both shears rotated to the great circle that joins the two -- each end by its own position angle:
+//   pa = ax by - ay bx,  dot = ax bx + ay by,  pbA = (ax ax + ay ay) bz - az dot,  pbB = (bx bx + by by) az - bz dot
+//   cA, sA from (pa, pbA) and cB, sB from (-pa, pbB) as above;  tA, xA, tB, xB the rotated (weighted) shears
+//   P += tA tB + xA xB    M += tA tB - xA xB    C += tA xB + xA tB    W += w_a w_b        (a den == 0: W only)
+// Every term is bit-symmetric under swapping a and b, so it does not matter which of the two a lane holds.
+//
+//   k_count_shear_auto   the skeleton of k_count_shear with both sides from the handle: lanes hold 256 objects of segment (q, k),
+//                        segment (p, k) streams through LDS as 48-byte objects (x, y, z, w, wg1, wg2: three 16-byte reads); the
+//                        key window is always on. A diagonal cell (p == q) walks only partners with a LARGER index, so every
+//                        unordered pair is met once. Histograms [4][E-1] per wave, folded and stored as above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,9 +58,17 @@ struct alignas(16) Obj {  // one streamed lens in LDS: two 16-byte broadcast rea
     double x, y, z, w;
 };
 
-size_t lds_bytes(int n_edges) {
-    return 2 * STAGE * sizeof(Obj) + (size_t)((n_edges + 1) & ~1) * sizeof(double) + (size_t)WAVES * 3 * (n_edges - 1) * sizeof(double);
+struct alignas(16) Obj6 {  // one streamed object of the shear-shear count: three 16-byte broadcast reads
+    double x, y, z, w, g1, g2;  // (g1, g2: the weighted shear wg1, wg2 of the handle)
+};
+
+// two stages + thresholds + one histogram [planes][E-1] per wave
+size_t lds_bytes(int n_edges, size_t obj_bytes = sizeof(Obj), int planes = 3) {
+    return 2 * STAGE * obj_bytes + (size_t)((n_edges + 1) & ~1) * sizeof(double) + (size_t)WAVES * planes * (n_edges - 1) * sizeof(double);
 }
+// yawhip_shear_auto_count takes the edge cap of yawhip_shear_count: 24 KiB of stages + 2 KiB + 31.9 KiB of histograms
+static_assert(2 * STAGE * sizeof(Obj6) + MAX_EDGES * sizeof(double) + WAVES * 4 * (MAX_EDGES - 1) * sizeof(double) <= 64 * 1024,
+              "k_count_shear_auto: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
                                const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
@@ -211,6 +232,163 @@ __global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src,
     if (tid == 0) evaluated[cell] = work;
 }
 
+// out: [4][n_cells][E-1] (P, M, C, W), every element written; evaluated: [n_cells] separations the cell's workgroup evaluated
+// (on a diagonal cell that includes the few of a tile's first stage that the index test then drops)
+__global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, const int32_t *__restrict__ jobs, int n_edges,
+                                                         const double *__restrict__ t, const double *__restrict__ rwin,
+                                                         int64_t n_cells, double *__restrict__ out,
+                                                         unsigned long long *__restrict__ evaluated) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Obj6 *stage = reinterpret_cast<Obj6 *>(lds_raw);                                 // [2][STAGE]
+    double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(Obj6));    // [n_edges]
+    double *hist = thr + ((n_edges + 1) & ~1);                                       // [WAVES][4][nf]
+
+    const int tid = threadIdx.x;
+    const int nf = n_edges - 1;
+    const int64_t cell = blockIdx.x;
+    const int64_t job = cell / nb;
+    const int k = (int)(cell - job * nb);
+    const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+    const bool diag = p == q;
+    const int64_t seg0 = src.off[p * nb + k], seg1 = src.off[p * nb + k + 1];    // streamed
+    const int64_t a_beg = src.off[q * nb + k], a_end = src.off[q * nb + k + 1];  // in lanes
+
+    for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
+    for (int j = tid; j < WAVES * 4 * nf; j += WG) hist[j] = 0.0;
+    const double tmax = t[(int64_t)k * n_edges + n_edges - 1];
+    const double rw = rwin[k];
+    double *wh = hist + (tid >> 6) * 4 * nf;  // this wave's histogram
+    unsigned long long work = 0;
+    __syncthreads();
+
+    for (int64_t ta = a_beg; ta < a_end && seg1 > seg0; ta += WG) {
+        const int64_t t_last = (ta + WG < a_end ? ta + WG : a_end) - 1;
+        // streamed objects that can hold partners of the tile: keys in [first key - rw, last key + rw] (k_count_shear); both
+        // sides are segments of one handle, sorted along the same axis
+        const double wlo = src.key[ta] - rw, whi = src.key[t_last] + rw;
+        int64_t l = seg0, h = seg1;  // first index with key >= wlo
+        while (l < h) {
+            const int64_t m = (l + h) >> 1;
+            if (src.key[m] < wlo) l = m + 1; else h = m;
+        }
+        int64_t b0 = l;
+        h = seg1;  // first index with key > whi
+        while (l < h) {
+            const int64_t m = (l + h) >> 1;
+            if (src.key[m] <= whi) l = m + 1; else h = m;
+        }
+        const int64_t b1 = l;
+        if (diag && b0 <= ta) b0 = ta + 1;  // a partner with a larger index than some lane of the tile
+        const int64_t nb_total = b1 - b0;
+        if (nb_total <= 0) continue;  // (the same for every thread)
+        work += (unsigned long long)(t_last - ta + 1) * (unsigned long long)nb_total;
+
+        // this lane's object -> registers; padded lanes are parked far away
+        const int64_t ia = ta + tid;
+        const bool ok = ia < a_end;
+        const double ax = ok ? src.x[ia] : PAD_COORD;
+        const double ay = ok ? src.y[ia] : PAD_COORD;
+        const double az = ok ? src.z[ia] : PAD_COORD;
+        const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
+        const double ag1 = ok ? src.wg1[ia] : 0.0;
+        const double ag2 = ok ? src.wg2[ia] : 0.0;
+        const double rho2 = ax * ax + ay * ay;
+        // a diagonal cell counts the streamed object i of a stage only for lanes with ia < its index: i > ia - (first of stage)
+        const int64_t lane_rel = diag ? ia - b0 : (int64_t)-1 - (int64_t)STAGE;
+
+        const int nstages = (int)((nb_total + STAGE - 1) / STAGE);
+        {  // stage 0 (the barrier that ended the previous tile's last stage has freed both buffers)
+            const int64_t i = b0 + tid;
+            const bool have = i < b1;
+            Obj6 o;
+            o.x = have ? src.x[i] : 0.0; o.y = have ? src.y[i] : 0.0; o.z = have ? src.z[i] : 0.0;
+            o.w = (have && src.w) ? src.w[i] : 1.0;
+            o.g1 = have ? src.wg1[i] : 0.0; o.g2 = have ? src.wg2[i] : 0.0;
+            stage[tid] = o;
+        }
+        __syncthreads();
+
+        for (int st = 0; st < nstages; ++st) {
+            const Obj6 *cur = stage + (st & 1) * STAGE;
+            Obj6 nxt;  // the next stage's global loads are issued early: they land in registers while this one is computed
+            const bool have_next = st + 1 < nstages;
+            if (have_next) {
+                const int64_t i = b0 + (int64_t)(st + 1) * STAGE + tid;
+                const bool have = i < b1;
+                nxt.x = have ? src.x[i] : 0.0; nxt.y = have ? src.y[i] : 0.0; nxt.z = have ? src.z[i] : 0.0;
+                nxt.w = (have && src.w) ? src.w[i] : 1.0;
+                nxt.g1 = have ? src.wg1[i] : 0.0; nxt.g2 = have ? src.wg2[i] : 0.0;
+            }
+            const int64_t left = nb_total - (int64_t)st * STAGE;
+            const int n = left < STAGE ? (int)left : STAGE;
+            // streamed i of this stage counts for the lane iff i > rel (-1: all of them); tested behind the bisection, so that
+            // the hot loop stays that of k_count_shear
+            const int64_t rel64 = lane_rel - (int64_t)st * STAGE;
+            const int rel = rel64 < 0 ? -1 : (int)rel64;
+            for (int i = 0; i < n; ++i) {
+                const Obj6 &b = cur[i];  // wave-wide broadcast reads (g1, g2 only behind the ballot)
+                const double bx = b.x, by = b.y, bz = b.z;
+                const double dx = ax - bx;
+                const double dy = ay - by;
+                const double dz = az - bz;
+                const double xx = dx * dx;
+                const double yy = dy * dy;
+                const double zz = dz * dz;
+                const double sxy = xx + yy;
+                const double s = sxy + zz;
+                if (__builtin_amdgcn_ballot_w64(s <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
+                    if (ok && s <= tmax) {
+                        int cnt = 0, hi = n_edges;  // edges below s (they ascend): the first e with thr[e] >= s, by bisection
+                        while (cnt < hi) {
+                            const int mid = (cnt + hi) >> 1;
+                            if (thr[mid] < s) cnt = mid + 1; else hi = mid;
+                        }
+                        if (cnt > 0 && i > rel) {  // t[cnt-1] < s <= t[cnt], and not the lower half of a diagonal cell
+                            const double pa = ax * by - ay * bx;
+                            const double dot = ax * bx + ay * by;
+                            const double pbA = rho2 * bz - az * dot;
+                            const double pbB = (bx * bx + by * by) * az - bz * dot;
+                            const double a2 = pa * pa;
+                            const double bA2 = pbA * pbA;
+                            const double bB2 = pbB * pbB;
+                            const double denA = a2 + bA2;
+                            const double denB = a2 + bB2;
+                            if (denA != 0.0 && denB != 0.0) {
+                                const double cA = (a2 - bA2) / denA;
+                                const double sA = ((2.0 * pa) * pbA) / denA;
+                                const double cB = (a2 - bB2) / denB;
+                                const double sB = ((-2.0 * pa) * pbB) / denB;
+                                const double bg1 = b.g1, bg2 = b.g2;
+                                const double tA = -(ag1 * cA + ag2 * sA);
+                                const double xA = ag1 * sA - ag2 * cA;
+                                const double tB = -(bg1 * cB + bg2 * sB);
+                                const double xB = bg1 * sB - bg2 * cB;
+                                const double tt = tA * tB;
+                                const double xx2 = xA * xB;
+                                atomicAdd(&wh[cnt - 1], tt + xx2);
+                                atomicAdd(&wh[nf + cnt - 1], tt - xx2);
+                                atomicAdd(&wh[2 * nf + cnt - 1], tA * xB + xA * tB);
+                            }
+                            atomicAdd(&wh[3 * nf + cnt - 1], aw * b.w);
+                        }
+                    }
+                }
+            }
+            if (have_next) stage[((st + 1) & 1) * STAGE + tid] = nxt;
+            __syncthreads();
+        }
+    }
+
+    __syncthreads();
+    const int64_t plane = n_cells * nf;
+    for (int j = tid; j < 4 * nf; j += WG) {  // the four waves' histograms in a fixed order
+        const double v = ((hist[j] + hist[4 * nf + j]) + hist[2 * 4 * nf + j]) + hist[3 * 4 * nf + j];
+        const int c = j / nf;
+        out[(int64_t)c * plane + cell * nf + (j - c * nf)] = v;
+    }
+    if (tid == 0) evaluated[cell] = work;
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,31 +403,39 @@ int yawhip_shear_free(yawhip_shear_sources *src) {
     return YAWHIP_OK;
 }
 
-int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                        const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
-                        yawhip_shear_sources **out) {
-    if (!out) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: out is NULL");
+}  // extern "C"
+
+namespace {
+
+// the upload of both entry points: n_bins segments per patch (1: the unbinned catalogue of yawhip_shear_upload), each sorted
+// along sort_axis and gathered
+int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                    const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets, int32_t sort_axis,
+                    yawhip_shear_sources **out) {
+    if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
     *out = nullptr;
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: ctx is NULL");
+    if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
     if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
-    if (n < 0 || n_patches <= 0 || !offsets || (n > 0 && (!x || !y || !z || !g1 || !g2)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_upload: bad sizes or NULL columns");
+    if (n < 0 || n_patches <= 0 || n_bins <= 0 || !offsets || (n > 0 && (!x || !y || !z || !g1 || !g2)))
+        return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL columns", fn);
     if (n >= (1ll << 32)) return fail(YAWHIP_ERR_INVALID, "at most 2^32 - 1 objects per catalogue");
-    if (offsets[0] != 0 || offsets[n_patches] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
-    for (int32_t i = 0; i < n_patches; ++i)
+    const int64_t n_seg = (int64_t)n_patches * n_bins;
+    if (offsets[0] != 0 || offsets[n_seg] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
+    for (int64_t i = 0; i < n_seg; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
     HIP_TRY(hipSetDevice(ctx->device));
     yawhip_shear_sources *s = new (std::nothrow) yawhip_shear_sources;
-    if (!s) return fail(YAWHIP_ERR_OOM, "yawhip_shear_upload: out of host memory");
+    if (!s) return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     s->ctx = ctx;
     s->n = n;
     s->n_patches = n_patches;
+    s->nb = n_bins;
     s->axis = sort_axis;
     try {
-        s->h_off.assign(offsets, offsets + n_patches + 1);
+        s->h_off.assign(offsets, offsets + n_seg + 1);
     } catch (const std::bad_alloc &) {
         delete s;
-        return fail(YAWHIP_ERR_OOM, "yawhip_shear_upload: out of host memory");
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
     DevPtr<double> raw[6];  // x, y, z, g1, g2, w as they came (temporary)
@@ -259,16 +445,16 @@ int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const doubl
     for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
         if (e == hipSuccess) e = c->alloc(n1);
     if (e == hipSuccess && w) e = s->w.alloc(n1);
-    if (e == hipSuccess) e = s->off.alloc((size_t)n_patches + 1);
+    if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
     for (int c = 0; c < 6; ++c)
         if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
     if (e == hipSuccess) e = perm.alloc(n1);
     for (int c = 0; c < 6; ++c)
         if (e == hipSuccess && host[c] && n > 0) e = hipMemcpyAsync(raw[c], host[c], col, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(s->off, offsets, ((size_t)n_patches + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(s->off, offsets, ((size_t)n_seg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && n > 0) {
-        e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_patches, perm);
+        e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_seg, perm);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
                                raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2);
@@ -279,26 +465,14 @@ int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const doubl
     if (ctx->sort_ws.cap > ((size_t)1 << 25)) ctx->sort_ws.release();  // as the catalogue upload: keep only small workspaces
     if (e != hipSuccess) {
         yawhip_shear_free(s);
-        return hip_fail("yawhip_shear_upload", e);
+        return hip_fail(fn, e);
     }
     *out = s;
     return YAWHIP_OK;
 }
 
-int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
-                       const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
-                       double *fine_w, yawhip_stats *stats) {
-    const auto wall0 = std::chrono::steady_clock::now();
-    // the argument checks of a count call (check_call), before any device work
-    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && (!jobs || !fine_t || !fine_x || !fine_w)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
-                    n_jobs, n_bins, n_edges, MAX_EDGES);
-    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (lenses->n_patches != sources->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
-    if (lenses->nb != 1 && lenses->nb != n_bins)
-        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+// the argument checks the two counts share (check_call of a count call), before any device work
+int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_patches, int32_t n_bins, int32_t n_edges, const double *t) {
     for (int k = 0; k < n_bins; ++k)
         for (int e = 0; e < n_edges; ++e) {
             const double v = t[(size_t)k * n_edges + e];
@@ -306,21 +480,30 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
                 return fail(YAWHIP_ERR_INVALID, "thresholds of bin %d are not ascending non-negative numbers", k);
         }
     for (int j = 0; j < n_jobs; ++j)
-        if (jobs[2 * j] < 0 || jobs[2 * j] >= lenses->n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= lenses->n_patches)
-            return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, lenses->n_patches);
-    const int64_t n_cells = (int64_t)n_jobs * n_bins, nf = n_edges - 1;
-    if (n_cells > INT32_MAX) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: more than 2^31 - 1 (job, bin) cells");
-    if (stats) *stats = yawhip_stats{};
-    if (n_jobs == 0) return YAWHIP_OK;
+        if (jobs[2 * j] < 0 || jobs[2 * j] >= n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= n_patches)
+            return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, n_patches);
+    if ((int64_t)n_jobs * n_bins > INT32_MAX) return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (job, bin) cells", fn);
+    return YAWHIP_OK;
+}
 
-    // one table in: thresholds [B][E], window half widths [B], jobs [n_jobs][2]
+// What a count call keeps on the handle: one table in (thresholds [B][E], window half widths [B], jobs [n_jobs][2]) and the
+// result block (n_planes planes [cells][E-1], then the cells' evaluated separations).
+struct CallBlock {
+    const double *t, *rwin;
+    const int32_t *jobs;
+    double *out;
+    unsigned long long *evaluated;
+    size_t plane;  // elements of one plane
+};
+
+int stage_call(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
+               int32_t n_edges, const double *t, int n_planes, CallBlock *blk) {
     const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + 2 * (size_t)n_jobs * sizeof(int32_t);
     std::vector<unsigned char> h_in;
-    int64_t candidates = 0;
     try {
         h_in.resize(in_bytes);
     } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "yawhip_shear_count: out of host memory");
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
     double *h_t = reinterpret_cast<double *>(h_in.data()), *h_rwin = h_t + n_t;
     memcpy(h_t, t, n_t * sizeof(double));
@@ -328,45 +511,38 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
     for (int k = 0; k < n_bins; ++k) h_rwin[k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
     memcpy(h_rwin + n_bins, jobs, 2 * (size_t)n_jobs * sizeof(int32_t));
-    for (int j = 0; j < n_jobs; ++j) {
-        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
-        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
-        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
-                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
-        candidates += n_src * n_lens;
-    }
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
-    const size_t n_out = 3 * (size_t)n_cells * (size_t)nf;
+    const size_t n_cells = (size_t)n_jobs * (size_t)n_bins;
+    blk->plane = n_cells * (size_t)(n_edges - 1);
+    const size_t n_out = (size_t)n_planes * blk->plane;
     HIP_TRY(sources->d_in.reserve(in_bytes, in_bytes / 4 + 64));
-    HIP_TRY(sources->d_out.reserve(n_out + (size_t)n_cells, n_out / 4 + 64));
+    HIP_TRY(sources->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
+    // (pageable memory: the copy has left h_in when the call returns)
     HIP_TRY(hipMemcpyAsync(sources->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const double *d_t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr);
-    const double *d_rwin = d_t + n_t;
-    const int32_t *d_jobs = reinterpret_cast<const int32_t *>(d_rwin + n_bins);
-    double *d_out = sources->d_out.ptr;
-    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
-    const ShearView sv{sources->x, sources->y, sources->z, sources->w, sources->wg1, sources->wg2, sources->off,
-                       key_of(sources->x, sources->y, sources->z, sources->axis), sources->axis};
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges), ctx->stream, view_of(lenses), sv, d_jobs,
-                       n_bins, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    const size_t plane = (size_t)n_cells * (size_t)nf;
-    HIP_TRY(hipMemcpyAsync(fine_t, d_out, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fine_x, d_out + plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fine_w, d_out + 2 * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    blk->t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr);
+    blk->rwin = blk->t + n_t;
+    blk->jobs = reinterpret_cast<const int32_t *>(blk->rwin + n_bins);
+    blk->out = sources->d_out.ptr;
+    blk->evaluated = reinterpret_cast<unsigned long long *>(blk->out + n_out);
+    return YAWHIP_OK;
+}
+
+// after the kernel, between the context's two events: the planes and the counters back to the host, and the statistics
+int finish_call(const char *fn, yawhip_ctx *ctx, const CallBlock &blk, int n_planes, double *const *fine, int64_t n_cells,
+                int64_t candidates, std::chrono::steady_clock::time_point wall0, yawhip_stats *stats) {
+    for (int c = 0; c < n_planes; ++c)
+        HIP_TRY(hipMemcpyAsync(fine[c], blk.out + (size_t)c * blk.plane, blk.plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     std::vector<unsigned long long> h_eval;
     if (stats) {
         try {
             h_eval.resize((size_t)n_cells);
         } catch (const std::bad_alloc &) {
             (void)hipStreamSynchronize(ctx->stream);
-            return fail(YAWHIP_ERR_OOM, "yawhip_shear_count: out of host memory");
+            return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
         }
-        HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, (size_t)n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_eval.data(), blk.evaluated, (size_t)n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (stats) {
@@ -380,6 +556,105 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     }
     return YAWHIP_OK;
+}
+
+ShearView view_of(const yawhip_shear_sources *s) {
+    return ShearView{s->x, s->y, s->z, s->w, s->wg1, s->wg2, s->off, key_of(s->x, s->y, s->z, s->axis), s->axis};
+}
+
+}  // namespace
+
+extern "C" {
+
+int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                        const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
+                        yawhip_shear_sources **out) {
+    return upload_segments("yawhip_shear_upload", ctx, n, x, y, z, w, g1, g2, n_patches, 1, offsets, sort_axis, out);
+}
+
+int yawhip_shear_upload_binned(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                               const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                               int32_t sort_axis, yawhip_shear_sources **out) {
+    return upload_segments("yawhip_shear_upload_binned", ctx, n, x, y, z, w, g1, g2, n_patches, n_bins, offsets, sort_axis, out);
+}
+
+int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                       const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
+                       double *fine_w, yawhip_stats *stats) {
+    const char *fn = "yawhip_shear_count";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
+    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && (!jobs || !fine_t || !fine_x || !fine_w)))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
+                    n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (sources->nb != 1)
+        return fail(YAWHIP_ERR_MISMATCH, "yawhip_shear_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
+    if (lenses->n_patches != sources->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
+    if (lenses->nb != 1 && lenses->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
+    const int64_t n_cells = (int64_t)n_jobs * n_bins;
+    if (stats) *stats = yawhip_stats{};
+    if (n_jobs == 0) return YAWHIP_OK;
+
+    int64_t candidates = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
+        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
+        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
+                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
+        candidates += n_src * n_lens;
+    }
+    CallBlock blk;
+    if (const int rc = stage_call(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, 3, &blk)) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges), ctx->stream, view_of(lenses), view_of(sources),
+                       blk.jobs, n_bins, n_edges, blk.t, blk.rwin, n_cells, blk.out, blk.evaluated);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    double *const fine[3] = {fine_t, fine_x, fine_w};
+    return finish_call(fn, ctx, blk, 3, fine, n_cells, candidates, wall0, stats);
+}
+
+int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
+                            int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c, double *fine_w,
+                            yawhip_stats *stats) {
+    const char *fn = "yawhip_shear_auto_count";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (!ctx || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: NULL handle");
+    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t ||
+        (n_jobs > 0 && (!jobs || !fine_p || !fine_m || !fine_c || !fine_w)))
+        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
+                    n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (sources->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "source catalogue bin count (%d) does not fit n_bins=%d", sources->nb, n_bins);
+    if (const int rc = check_count(fn, n_jobs, jobs, sources->n_patches, n_bins, n_edges, t)) return rc;
+    for (int j = 0; j < n_jobs; ++j)
+        if (jobs[2 * j] > jobs[2 * j + 1])
+            return fail(YAWHIP_ERR_INVALID, "job %d = (%d, %d): an autocorrelation job has p <= q", j, jobs[2 * j], jobs[2 * j + 1]);
+    const int64_t n_cells = (int64_t)n_jobs * n_bins;
+    if (stats) *stats = yawhip_stats{};
+    if (n_jobs == 0) return YAWHIP_OK;
+
+    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
+    for (int j = 0; j < n_jobs; ++j)
+        for (int k = 0; k < n_bins; ++k) {
+            const size_t sp = (size_t)jobs[2 * j] * n_bins + k, sq = (size_t)jobs[2 * j + 1] * n_bins + k;
+            const int64_t n_p = sources->h_off[sp + 1] - sources->h_off[sp], n_q = sources->h_off[sq + 1] - sources->h_off[sq];
+            candidates += sp == sq ? n_p * (n_p - 1) / 2 : n_p * n_q;
+        }
+    CallBlock blk;
+    if (const int rc = stage_call(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, 4, &blk)) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_count_shear_auto, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges, sizeof(Obj6), 4), ctx->stream,
+                       view_of(sources), n_bins, blk.jobs, n_edges, blk.t, blk.rwin, n_cells, blk.out, blk.evaluated);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    double *const fine[4] = {fine_p, fine_m, fine_c, fine_w};
+    return finish_call(fn, ctx, blk, 4, fine, n_cells, candidates, wall0, stats);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -180,15 +180,33 @@ def count_shear_fine(lens_layout, source_layout, jobs, thresholds, *, sort_axis:
     ctx = get_context()
     micro = forced_strip_micro if forced_strip_micro is not None else strip_micro_for(thresholds)
     lenses = device_catalog(lens_layout, ctx, sort_axis, micro, exact=forced_strip_micro is not None)
-    sources = source_layout.shear_device.get(id(ctx))
+    return _lib.shear_count(ctx, lenses, _shear_sources(source_layout, ctx, sort_axis), jobs, thresholds)
+
+
+def count_shear_auto_fine(layout, jobs, thresholds, *, sort_axis: int = 2):
+    """Fine-bin shear-shear sums of ONE catalogue inside its redshift bins for ``jobs`` (int[n, 2] patch pairs with ``p <= q``)
+    -> ``(P, M, C, W, CountStats)``, f64[n_jobs, B, E-1] each: the numerators of xi_plus, xi_minus and xi_cross and the sum of
+    ``w_a * w_b`` of the pairs, a diagonal job holding every unordered pair once (``yawhip_shear_auto_count``). ``layout`` is a
+    binned layout with ``g1`` / ``g2`` (``build_trees(edges, with_shear=True)``); it reaches the device once per context as a
+    binned ``_lib.ShearSources`` kept on the layout, replaced when another sort axis is asked for. On a context of several
+    devices the count runs on its first one. No CPU fallback; the CPU tests replace this function."""
+    if layout.g1 is None or layout.g2 is None:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    ctx = get_context()
+    return _lib.shear_auto_count(ctx, _shear_sources(layout, ctx, sort_axis), jobs, thresholds)
+
+
+def _shear_sources(layout, ctx, sort_axis):
+    """The resident ``_lib.ShearSources`` of a layout with shear columns on ``ctx``, uploaded on first use."""
+    sources = layout.shear_device.get(id(ctx))
     if sources is not None and (sources.sort_axis != sort_axis or not sources._h):
         sources.free()
         sources = None
     if sources is None:
-        sources = source_layout.shear_device[id(ctx)] = _lib.ShearSources(
-            ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1, source_layout.g2,
-            source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis)
-    return _lib.shear_count(ctx, lenses, sources, jobs, thresholds)
+        sources = layout.shear_device[id(ctx)] = _lib.ShearSources(
+            ctx, layout.x, layout.y, layout.z, layout.w, layout.g1, layout.g2, layout.num_patches, layout.offsets,
+            sort_axis=sort_axis, n_bins=layout.num_bins)
+    return sources
 
 
 def _device_pair(layout1, layout2, thresholds, sort_axis, max_workers=None):

@@ -25,7 +25,7 @@ from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
 __all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
-           "crosscorrelate_shear", "compute_scalar_normalisation",
+           "crosscorrelate_shear", "autocorrelate_shear", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -507,6 +507,39 @@ class PatchLinkage:
                  NormalisedScalarCounts(PatchedCounts(binning, X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
                 for s in range(shape[0])]
 
+    def count_shear_auto_pairs(self, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
+                               count_type_info: str | None = None) -> list:
+        """Shear-shear sums of ``sources`` (binned in redshift with ``g1`` / ``g2``: ``build_trees(edges, with_shear=True)``)
+        inside every redshift bin over the linked patch pairs ``i <= j`` -> per scale ``(NormalisedScalarCounts(P, W),
+        NormalisedScalarCounts(M, W), NormalisedScalarCounts(C, W))``: the numerators of xi_plus, xi_minus and xi_cross, each
+        over the sum of the pair weights ``w_a * w_b``. A diagonal slot holds every unordered pair of its patch once, what an
+        autocorrelation count holds after its x 0.5. Thresholds, separation weights and per-scale sums are those of
+        ``count_pairs``; ONE library call counts all jobs (``engine.count_shear_auto_fine``), on one device of one process:
+        several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("shear counts run in one process on one device")
+        if count_type_info is not None:
+            _log_info("counting %s from patch pairs", count_type_info)
+        binning = self.config.binning.binning
+        num_bins, num_patches = len(binning), len(sources)
+        layout = _active_layout(sources, num_bins)
+        if layout.g1 is None or layout.g2 is None:
+            raise ValueError("catalog has no 'g1'/'g2' attached")
+        if layout.num_bins != num_bins:
+            raise ValueError("shear-shear counts need the sources binned in redshift")
+        jobs = self.get_patch_pairs(sources)
+        _, thresholds = self._angular_setup()
+        *fine, stats = engine.count_shear_auto_fine(layout, jobs, thresholds, sort_axis=self.sort_axis)
+        self.last_stats = stats
+        self._report(count_type_info, len(jobs), stats, progress)
+        flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
+        shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
+        # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
+        P, M, C, W = (_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine)
+        return [tuple(NormalisedScalarCounts(PatchedCounts(binning, num[s], auto=True), PatchedCounts(binning, W[s], auto=True))
+                      for num in (P, M, C))
+                for s in range(shape[0])]
+
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
         """The reference logs every pair count and shows a progress bar over its patch-pair tasks
@@ -733,3 +766,26 @@ def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_ra
     DD = links.count_shear_pairs(reference, sources, count_type_info="DD", **kwargs)
     DR = links.count_shear_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
     return [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
+
+
+def autocorrelate_shear(config, sources: Catalog, *, linkage: PatchLinkage | None = None, progress: bool = False,
+                        max_workers: int | None = None) -> list:
+    """Shear-shear correlations of ``sources`` (a catalogue with ``g1`` / ``g2`` and redshifts) inside the redshift bins of
+    the configuration: per bin and scale ``xi_plus = sum P / sum W``, ``xi_minus = sum M / sum W`` and the parity-odd
+    ``xi_cross = sum C / sum W`` (a null test) over the pairs in range ->
+    ``[(ScalarCorrFunc(dd_plus), ScalarCorrFunc(dd_minus), ScalarCorrFunc(dd_cross)), ...]``, one triple per scale. With
+    ``(t, x)`` the shear of an object along and across the great circle that joins the pair -- each end rotated by its own
+    position angle, since the east / north frames (``Catalog.from_arrays``) at the two ends are not parallel on the sphere --
+    a pair adds ``P = w_a w_b (t_a t_b + x_a x_b)``, ``M = w_a w_b (t_a t_b - x_a x_b)``, ``C = w_a w_b (t_a x_b + x_a t_b)``
+    and ``W = w_a w_b`` (include/yawhip.h has the arithmetic).
+
+    This driver has no counterpart in the reference. Patches, scales and jackknife are ``autocorrelate``'s; ``linkage`` may
+    pass a prepared ``PatchLinkage``; the count runs on one device of one process."""
+    if not sources.has_shear:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    _log_info("building source trees")
+    sources.build_trees(config.binning.edges, closed=config.binning.closed, with_shear=True)
+    _log_info("computing shear auto-correlation with DD")
+    links = linkage if linkage is not None else PatchLinkage.from_catalogs(config, sources)
+    DD = links.count_shear_auto_pairs(sources, count_type_info="DD", progress=progress, max_workers=max_workers)
+    return [tuple(ScalarCorrFunc(dd) for dd in triple) for triple in DD]
