@@ -291,7 +291,8 @@ def count_pairs(cat1, cat2, jobs, ang_min_per_bin, ang_max_per_bin, n_patches, *
     weighted = cat1["w"] is not None or cat2["w"] is not None
     fine = sums if weighted else icounts.astype(np.float64)
     out = np.zeros((n_scales, n_bins, n_patches, n_patches))
-    for j, (p, q) in enumerate(jobs):
+    for j in np.flatnonzero(fine.reshape(len(jobs), -1).any(axis=1)):  # (a job without pairs leaves its zeros in `out`)
+        p, q = jobs[j]
         for k in range(n_bins):
             vals = finalize(fine[j, k], bins[k], lims[k], rweight)
             if auto and p == q:
