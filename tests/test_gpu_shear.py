@@ -120,6 +120,25 @@ def test_fine_sums_match_the_oracle(weights, nf, sort_axis):
     check_against_oracle(f"{weights} nf={nf} axis={sort_axis}", (T, X, W), exp)
 
 
+def test_unbinned_lenses_under_two_redshift_bins():
+    """Lenses without redshift bins (``nb = 1``) under the thresholds of two bins: both cells of a job stream the one lens
+    segment of its patch, each with the edges of its own bin."""
+    lens, src = weighted_scene("both")
+    lens = dict(lens, nb=1, off=lens["off"][::N_BINS].copy())  # the scene's lenses with their bin boundaries dropped
+    t = thresholds(12, n_bins=2)
+    exp = shear_oracle.shear_jobs(lens, src, JOBS, t)
+    assert np.all(exp[3].sum(axis=2) > 0)  # both bins hold pairs in every job ...
+    assert not np.any(np.all(exp[2][:, 0] == exp[2][:, 1], axis=1))  # ... and no job has the same sums in the two
+    ctx = engine.get_context(0)
+    lenses, sources = upload(ctx, lens, src, 2)
+    try:
+        T, X, W, stats = _lib.shear_count(ctx, lenses, sources, JOBS, t)
+    finally:
+        lenses.free(), sources.free()
+    assert stats.n_workgroups == len(JOBS) * 2 and 0 < stats.evaluated_pairs <= stats.candidate_pairs
+    check_against_oracle("unbinned lenses, two bins", (T, X, W), exp)
+
+
 # --------------------------------------------------------------------------- 2. W against the shipped count
 @pytest.mark.parametrize("axes", [(2, 2), (1, 1), (2, 0)], ids=["z", "y", "lens z, sources x"])
 @pytest.mark.parametrize("weights", ["both", "none"])

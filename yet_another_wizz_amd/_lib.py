@@ -802,43 +802,36 @@ class ShearSources:
             pass
 
 
-def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs, thresholds):
-    """Run ``yawhip_shear_count``: jobs int[n_jobs, 2] = (lens patch, source patch); thresholds f64[B, E]. Returns
-    ``(T, X, W, CountStats)``: the tangential, cross and weight sums, f64[n_jobs, B, E-1] each."""
+def _shear_counts(symbol: str, n_planes: int, handles, jobs, thresholds):
+    """What ``shear_count`` and ``shear_auto_count`` share: ``symbol(*handles, n_jobs, jobs, B, E, thresholds, n_planes output
+    planes, stats)`` -> the planes f64[n_jobs, B, E-1] and the ``CountStats``."""
     jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
     t = np.ascontiguousarray(thresholds, dtype=np.float64)
     if t.ndim != 2:
         raise ValueError("thresholds must be [n_bins, n_edges]")
     n_bins, n_edges = t.shape
     shape = (len(jobs), n_bins, max(n_edges - 1, 0))
-    out = [np.empty(shape, dtype=np.float64) for _ in range(3)]  # the library writes every element
+    out = [np.empty(shape, dtype=np.float64) for _ in range(n_planes)]  # the library writes every element
     st = _Stats()
     _check(
-        load_library().yawhip_shear_count(ctx._h, lenses._h, sources._h, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
-                                          *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
-        "yawhip_shear_count",
+        getattr(load_library(), symbol)(*handles, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
+                                        *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
+        symbol,
     )
     return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
+
+
+def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs, thresholds):
+    """Run ``yawhip_shear_count``: jobs int[n_jobs, 2] = (lens patch, source patch); thresholds f64[B, E]. Returns
+    ``(T, X, W, CountStats)``: the tangential, cross and weight sums, f64[n_jobs, B, E-1] each."""
+    return _shear_counts("yawhip_shear_count", 3, (ctx._h, lenses._h, sources._h), jobs, thresholds)
 
 
 def shear_auto_count(ctx: Context, sources: ShearSources, jobs, thresholds):
     """Run ``yawhip_shear_auto_count`` on a binned handle: jobs int[n_jobs, 2] = patch pairs with ``p <= q``; thresholds
     f64[B, E]. Returns ``(P, M, C, W, CountStats)``: the numerators of xi_plus, xi_minus and xi_cross and the weight sums,
     f64[n_jobs, B, E-1] each; a diagonal job holds every unordered pair once."""
-    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
-    t = np.ascontiguousarray(thresholds, dtype=np.float64)
-    if t.ndim != 2:
-        raise ValueError("thresholds must be [n_bins, n_edges]")
-    n_bins, n_edges = t.shape
-    shape = (len(jobs), n_bins, max(n_edges - 1, 0))
-    out = [np.empty(shape, dtype=np.float64) for _ in range(4)]  # the library writes every element
-    st = _Stats()
-    _check(
-        load_library().yawhip_shear_auto_count(ctx._h, sources._h, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
-                                               *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
-        "yawhip_shear_auto_count",
-    )
-    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
+    return _shear_counts("yawhip_shear_auto_count", 4, (ctx._h, sources._h), jobs, thresholds)
 
 
 def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,

@@ -1,10 +1,28 @@
-// yawhip_shear.hip -- tangential and cross shear of a source catalogue around the lenses of a catalogue binned in redshift
-// (yawhip_shear_count; measurements.crosscorrelate_shear), and the shear-shear sums of a source catalogue
-// inside its own redshift bins (yawhip_shear_auto_count; measurements.autocorrelate_shear).
+// yawhip_shear.hip -- the two shear counts of a catalogue with (g1, g2): tangential and cross shear of a source catalogue around
+// the lenses of a catalogue binned in redshift (yawhip_shear_count; measurements.crosscorrelate_shear), and
+// the shear-shear sums of a source catalogue inside its own redshift bins (yawhip_shear_auto_count;
+// measurements.autocorrelate_shear). include/yawhip.h has both contracts, product by product.
 //
-// A pair (lens l, source s) belongs to fine bin e of redshift bin k by the predicate of yawhip_count_pairs, bit for bit:
-//   s2 = ((sx - lx)^2 + (sy - ly)^2) + (sz - lz)^2,   t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
-// and then adds, with (x, y, z) the source and (lx, ly, lz) the lens,
+// Both are ONE streaming walk, shear_walk<P>, under two thin entry kernels. One workgroup of 256 threads owns one (job, bin)
+// cell. Lanes hold 256 objects of the cell's lane segment in registers (parked far away where the tile is padded); the cell's
+// streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
+// sort key lies within the chord sqrt(t_max) of the tile's keys. The hot loop is the 8-flop separation of k_count,
+//   s2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2,   fine bin e iff t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
+// behind a wave-wide ballot; the fine-bin bisection and the pair term run only inside the outer edge. Sums go to one float64
+// LDS histogram [planes][E-1] per wave that only its own wave adds to (the reproducibility assumption of the band kernels: adds
+// of ONE instruction to one cell are serialised by the LDS in a fixed lane order); the four are folded in a fixed order and
+// stored with plain stores, every element written. No floating-point atomic touches global memory. All indices are 64-bit.
+//
+// What differs is a policy P, resolved at compile time -- no branch of it is in the streaming loop:
+//                      Tangential (k_count_shear)                           ShearShear (k_count_shear_auto)
+//   streamed segment   lens.off[p * nb + (nb == 1 ? 0 : k)] of a CatView    off[p * nb + k] of the one ShearView
+//   lane segment       off[q] of the unbinned sources                       off[q * nb + k] of the same handle
+//   streamed object    Obj  (x, y, z, w: 32 bytes)                          Obj6 (x, y, z, w, wg1, wg2: 48 bytes)
+//   key window         only if both sides are sorted along one axis         always
+//   diagonal cells     none                                                 p == q walks only partners with a LARGER index
+//   pair term, planes  one rotation: T, X, W                                two rotations: P, M, C, W
+//
+// Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
 //   c2 = (a a - b b) / den,   s2p = (2 a b) / den       cos / sin of twice the position angle of the lens seen from the
 //                                                       source, from east towards north (the 1 / rho of the local basis
@@ -12,27 +30,14 @@
 //   T += w_l * -(wg1 c2 + wg2 s2p)     X += w_l * (wg1 s2p - wg2 c2)     W += w_l * w_s        (wg = w_s g, made at upload)
 // den == 0 (the source sits on a pole of the frame): W only.
 //
-//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products.
-//   k_count_shear    one workgroup per (job, bin) cell. Lanes hold 256 sources of the job's source patch in registers, the
-//                    cell's lens segment streams through LDS 256 objects at a time (double-buffered); per lane tile only
-//                    the window of lenses whose sort key lies within the chord sqrt(t_max) of the tile's keys. The hot
-//                    loop is the 8-flop separation of k_count behind a wave-wide ballot; the division runs once per pair
-//                    inside the outer edge. Sums go to one float64 LDS histogram [3][E-1] per wave that only its own wave
-//                    adds to (the reproducibility assumption of the band kernels: adds of ONE instruction to one cell are
-//                    serialised by the LDS in a fixed lane order); the four are folded in a fixed order and stored with
-//                    plain stores. No floating-point atomic touches global memory.
-//
-// Shear-shear: objects a, b of the same redshift bin k of ONE handle, the same predicate, and (include/yawhip.h has the whole
-// contract) both shears rotated to the great circle that joins the two -- each end by its own position angle:
+// Shear-shear, objects a, b of the same redshift bin k of ONE handle, both shears rotated to the great circle that joins the
+// two -- each end by its own position angle:
 //   pa = ax by - ay bx,  dot = ax bx + ay by,  pbA = (ax ax + ay ay) bz - az dot,  pbB = (bx bx + by by) az - bz dot
 //   cA, sA from (pa, pbA) and cB, sB from (-pa, pbB) as above;  tA, xA, tB, xB the rotated (weighted) shears
 //   P += tA tB + xA xB    M += tA tB - xA xB    C += tA xB + xA tB    W += w_a w_b        (a den == 0: W only)
 // Every term is bit-symmetric under swapping a and b, so it does not matter which of the two a lane holds.
 //
-//   k_count_shear_auto   the skeleton of k_count_shear with both sides from the handle: lanes hold 256 objects of segment (q, k),
-//                        segment (p, k) streams through LDS as 48-byte objects (x, y, z, w, wg1, wg2: three 16-byte reads); the
-//                        key window is always on. A diagonal cell (p == q) walks only partners with a LARGER index, so every
-//                        unordered pair is met once. Histograms [4][E-1] per wave, folded and stored as above.
+//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,10 +53,10 @@ using namespace yawhip_detail;
 
 namespace {
 
-constexpr int WG = 256;      // threads per workgroup = 4 waves of 64 = sources per lane tile
+constexpr int WG = 256;      // threads per workgroup = 4 waves of 64 = objects per lane tile
 constexpr int WAVES = WG / 64;
-constexpr int STAGE = 256;   // streamed lenses per LDS stage (one per thread)
-constexpr int MAX_EDGES = 256;     // 4 histograms [3][E-1] + thresholds + two stages stay below 48 KiB of LDS
+constexpr int STAGE = 256;   // streamed objects per LDS stage (one per thread)
+constexpr int MAX_EDGES = 256;     // both counts: two stages + thresholds + 4 histograms [planes][E-1] fit the LDS (lds_bytes)
 constexpr double PAD_COORD = 4.0;  // padded lanes sit >= 3 away from any unit vector (as k_count parks them)
 
 struct alignas(16) Obj {  // one streamed lens in LDS: two 16-byte broadcast reads
@@ -62,13 +67,104 @@ struct alignas(16) Obj6 {  // one streamed object of the shear-shear count: thre
     double x, y, z, w, g1, g2;  // (g1, g2: the weighted shear wg1, wg2 of the handle)
 };
 
-// two stages + thresholds + one histogram [planes][E-1] per wave
-size_t lds_bytes(int n_edges, size_t obj_bytes = sizeof(Obj), int planes = 3) {
-    return 2 * STAGE * obj_bytes + (size_t)((n_edges + 1) & ~1) * sizeof(double) + (size_t)WAVES * planes * (n_edges - 1) * sizeof(double);
+struct Lane {  // what a lane keeps of its own object in registers (g1, g2: the weighted shear)
+    double x, y, z, w, g1, g2, rho2;
+};
+
+// x, y, z, w of streamed object i of a CatView or a ShearView; beyond the window (!have) an object nobody reads
+template <class O, class View>
+__device__ __forceinline__ O load_xyzw(const View &v, int64_t i, bool have) {
+    O o;
+    o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
+    o.w = (have && v.w) ? v.w[i] : 1.0;
+    return o;
 }
-// yawhip_shear_auto_count takes the edge cap of yawhip_shear_count: 24 KiB of stages + 2 KiB + 31.9 KiB of histograms
-static_assert(2 * STAGE * sizeof(Obj6) + MAX_EDGES * sizeof(double) + WAVES * 4 * (MAX_EDGES - 1) * sizeof(double) <= 64 * 1024,
-              "k_count_shear_auto: more than 64 KiB of dynamic LDS at MAX_EDGES");
+
+// The two policies of shear_walk (the table at the head of the file). add() is the pair term: `wh` the wave's histogram
+// [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of include/yawhip.h.
+struct Tangential {
+    using View = CatView;  // the streamed side: the lenses
+    using Streamed = Obj;
+    using Read = Obj;      // the hot loop reads the whole object: two ds_read_b128
+    static constexpr int PLANES = 3;  // T, X, W
+    static constexpr bool DIAGONAL = false;
+    static __device__ int64_t streamed_segment(const CatView &lens, int64_t p, int k, int) { return p * lens.nb + (lens.nb == 1 ? 0 : k); }
+    static __device__ int64_t lane_segment(int64_t q, int, int) { return q; }
+    // else the keys say nothing about each other: the whole segment
+    static __device__ bool windowed(const CatView &lens, const ShearView &src) { return lens.axis == src.axis; }
+    static __device__ Obj load(const CatView &lens, int64_t i, bool have) { return load_xyzw<Obj>(lens, i, have); }
+    static __device__ void add(const Lane &a, const Obj &b, double *wh, int e, int nf) {
+        const double pa = a.x * b.y - a.y * b.x;
+        const double dot = a.x * b.x + a.y * b.y;
+        const double pb = a.rho2 * b.z - a.z * dot;
+        const double a2 = pa * pa;
+        const double b2 = pb * pb;
+        const double den = a2 + b2;
+        if (den != 0.0) {
+            const double c2 = (a2 - b2) / den;
+            const double s2 = ((2.0 * pa) * pb) / den;
+            const double tv = -(a.g1 * c2 + a.g2 * s2);
+            const double xv = a.g1 * s2 - a.g2 * c2;
+            atomicAdd(&wh[e], b.w * tv);
+            atomicAdd(&wh[nf + e], b.w * xv);
+        }
+        atomicAdd(&wh[2 * nf + e], b.w * a.w);
+    }
+};
+
+struct ShearShear {
+    using View = ShearView;  // the streamed side: the handle itself
+    using Streamed = Obj6;
+    using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
+    static constexpr int PLANES = 4;  // P, M, C, W
+    static constexpr bool DIAGONAL = true;
+    static __device__ int64_t streamed_segment(const ShearView &, int64_t p, int k, int nb) { return p * nb + k; }
+    static __device__ int64_t lane_segment(int64_t q, int k, int nb) { return q * nb + k; }
+    static __device__ bool windowed(const ShearView &, const ShearView &) { return true; }  // segments of one handle: one sort axis
+    static __device__ Obj6 load(const ShearView &src, int64_t i, bool have) {
+        Obj6 o = load_xyzw<Obj6>(src, i, have);
+        o.g1 = have ? src.wg1[i] : 0.0; o.g2 = have ? src.wg2[i] : 0.0;
+        return o;
+    }
+    static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf) {
+        const double bx = b.x, by = b.y, bz = b.z;
+        const double pa = a.x * by - a.y * bx;
+        const double dot = a.x * bx + a.y * by;
+        const double pbA = a.rho2 * bz - a.z * dot;
+        const double pbB = (bx * bx + by * by) * a.z - bz * dot;
+        const double a2 = pa * pa;
+        const double bA2 = pbA * pbA;
+        const double bB2 = pbB * pbB;
+        const double denA = a2 + bA2;
+        const double denB = a2 + bB2;
+        if (denA != 0.0 && denB != 0.0) {
+            const double cA = (a2 - bA2) / denA;
+            const double sA = ((2.0 * pa) * pbA) / denA;
+            const double cB = (a2 - bB2) / denB;
+            const double sB = ((-2.0 * pa) * pbB) / denB;
+            const double bg1 = b.g1, bg2 = b.g2;
+            const double tA = -(a.g1 * cA + a.g2 * sA);
+            const double xA = a.g1 * sA - a.g2 * cA;
+            const double tB = -(bg1 * cB + bg2 * sB);
+            const double xB = bg1 * sB - bg2 * cB;
+            const double tt = tA * tB;
+            const double xx2 = xA * xB;
+            atomicAdd(&wh[e], tt + xx2);
+            atomicAdd(&wh[nf + e], tt - xx2);
+            atomicAdd(&wh[2 * nf + e], tA * xB + xA * tB);
+        }
+        atomicAdd(&wh[3 * nf + e], a.w * b.w);
+    }
+};
+
+// dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
+template <class P>
+constexpr size_t lds_bytes(int n_edges) {
+    return 2 * STAGE * sizeof(typename P::Streamed) + (size_t)((n_edges + 1) & ~1) * sizeof(double) +
+           (size_t)WAVES * P::PLANES * (n_edges - 1) * sizeof(double);
+}
+static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024,
+              "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
                                const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
@@ -93,15 +189,19 @@ __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, con
     }
 }
 
-// out: [3][n_cells][E-1] (T, X, W), every element written; evaluated: [n_cells] separations the cell's workgroup evaluated
-__global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src, const int32_t *__restrict__ jobs, int n_bins,
-                                                    int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
-                                                    int64_t n_cells, double *__restrict__ out,
-                                                    unsigned long long *__restrict__ evaluated) {
+// The walk of one (job, bin) cell = one workgroup. str: the streamed side, src: the side in the lanes.
+// out: [PLANES][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
+// diagonal cell that includes the few of a tile's first stage that the index test then drops)
+template <class P>
+__device__ __forceinline__ void shear_walk(const typename P::View &str, const ShearView &src, const int32_t *__restrict__ jobs,
+                                           int n_bins, int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
+                                           int64_t n_cells, double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
+    using O = typename P::Streamed;
+    constexpr int NP = P::PLANES;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    Obj *stage = reinterpret_cast<Obj *>(lds_raw);                                  // [2][STAGE]
-    double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(Obj));    // [n_edges]
-    double *hist = thr + ((n_edges + 1) & ~1);                                      // [WAVES][3][nf]
+    O *stage = reinterpret_cast<O *>(lds_raw);                                  // [2][STAGE]
+    double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(O));  // [n_edges]
+    double *hist = thr + ((n_edges + 1) & ~1);                                  // [WAVES][NP][nf]
 
     const int tid = threadIdx.x;
     const int nf = n_edges - 1;
@@ -109,175 +209,40 @@ __global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src,
     const int64_t job = cell / n_bins;
     const int k = (int)(cell - job * n_bins);
     const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
-    const int64_t lseg = p * lens.nb + (lens.nb == 1 ? 0 : k);
-    const int64_t seg0 = lens.off[lseg], seg1 = lens.off[lseg + 1];
-    const int64_t a_beg = src.off[q], a_end = src.off[q + 1];
+    const bool diag = P::DIAGONAL && p == q;
+    const int64_t sseg = P::streamed_segment(str, p, k, n_bins), lseg = P::lane_segment(q, k, n_bins);
+    const int64_t seg0 = str.off[sseg], seg1 = str.off[sseg + 1];  // streamed
+    const int64_t a_beg = src.off[lseg], a_end = src.off[lseg + 1];  // in lanes
 
     for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
-    for (int j = tid; j < WAVES * 3 * nf; j += WG) hist[j] = 0.0;
+    for (int j = tid; j < WAVES * NP * nf; j += WG) hist[j] = 0.0;
     const double tmax = t[(int64_t)k * n_edges + n_edges - 1];
     const double rw = rwin[k];
-    const bool windowed = lens.axis == src.axis;  // else the keys say nothing about each other: the whole segment
-    double *wh = hist + (tid >> 6) * 3 * nf;      // this wave's histogram
+    const bool windowed = P::windowed(str, src);
+    double *wh = hist + (tid >> 6) * NP * nf;  // this wave's histogram
     unsigned long long work = 0;
     __syncthreads();
 
     for (int64_t ta = a_beg; ta < a_end && seg1 > seg0; ta += WG) {
         const int64_t t_last = (ta + WG < a_end ? ta + WG : a_end) - 1;
-        // lenses that can hold partners of the tile: keys in [first key - rw, last key + rw]; rw = sqrt(t_max) widened for
-        // every rounding of s2 >= du^2 (1 - 2 eps) and of the two bounds themselves (yawhip_shear_count)
+        // streamed objects that can hold partners of the tile: keys in [first key - rw, last key + rw]; rw = sqrt(t_max) widened
+        // for every rounding of s2 >= du^2 (1 - 2 eps) and of the two bounds themselves (run_count)
         int64_t b0 = seg0, b1 = seg1;
         if (windowed) {
             const double wlo = src.key[ta] - rw, whi = src.key[t_last] + rw;
             int64_t l = seg0, h = seg1;  // first index with key >= wlo
             while (l < h) {
                 const int64_t m = (l + h) >> 1;
-                if (lens.key[m] < wlo) l = m + 1; else h = m;
+                if (str.key[m] < wlo) l = m + 1; else h = m;
             }
             b0 = l;
             h = seg1;  // first index with key > whi
             while (l < h) {
                 const int64_t m = (l + h) >> 1;
-                if (lens.key[m] <= whi) l = m + 1; else h = m;
+                if (str.key[m] <= whi) l = m + 1; else h = m;
             }
             b1 = l;
         }
-        const int64_t nb_total = b1 - b0;
-        if (nb_total <= 0) continue;  // (the same for every thread)
-        work += (unsigned long long)(t_last - ta + 1) * (unsigned long long)nb_total;
-
-        // this lane's source -> registers; padded lanes are parked far away
-        const int64_t ia = ta + tid;
-        const bool ok = ia < a_end;
-        const double ax = ok ? src.x[ia] : PAD_COORD;
-        const double ay = ok ? src.y[ia] : PAD_COORD;
-        const double az = ok ? src.z[ia] : PAD_COORD;
-        const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
-        const double ag1 = ok ? src.wg1[ia] : 0.0;
-        const double ag2 = ok ? src.wg2[ia] : 0.0;
-        const double rho2 = ax * ax + ay * ay;
-
-        const int nstages = (int)((nb_total + STAGE - 1) / STAGE);
-        {  // stage 0 (the barrier that ended the previous tile's last stage has freed both buffers)
-            const int64_t i = b0 + tid;
-            const bool have = i < b1;
-            Obj o;
-            o.x = have ? lens.x[i] : 0.0; o.y = have ? lens.y[i] : 0.0; o.z = have ? lens.z[i] : 0.0;
-            o.w = (have && lens.w) ? lens.w[i] : 1.0;
-            stage[tid] = o;
-        }
-        __syncthreads();
-
-        for (int st = 0; st < nstages; ++st) {
-            const Obj *cur = stage + (st & 1) * STAGE;
-            Obj nxt;  // the next stage's global loads are issued early: they land in registers while this one is computed
-            const bool have_next = st + 1 < nstages;
-            if (have_next) {
-                const int64_t i = b0 + (int64_t)(st + 1) * STAGE + tid;
-                const bool have = i < b1;
-                nxt.x = have ? lens.x[i] : 0.0; nxt.y = have ? lens.y[i] : 0.0; nxt.z = have ? lens.z[i] : 0.0;
-                nxt.w = (have && lens.w) ? lens.w[i] : 1.0;
-            }
-            const int64_t left = nb_total - (int64_t)st * STAGE;
-            const int n = left < STAGE ? (int)left : STAGE;
-            for (int i = 0; i < n; ++i) {
-                const Obj b = cur[i];  // wave-wide broadcast read
-                const double dx = ax - b.x;
-                const double dy = ay - b.y;
-                const double dz = az - b.z;
-                const double xx = dx * dx;
-                const double yy = dy * dy;
-                const double zz = dz * dz;
-                const double sxy = xx + yy;
-                const double s = sxy + zz;
-                if (__builtin_amdgcn_ballot_w64(s <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
-                    if (ok && s <= tmax) {
-                        int cnt = 0, hi = n_edges;  // edges below s (they ascend): the first e with thr[e] >= s, by bisection
-                        while (cnt < hi) {
-                            const int mid = (cnt + hi) >> 1;
-                            if (thr[mid] < s) cnt = mid + 1; else hi = mid;
-                        }
-                        if (cnt > 0) {  // t[cnt-1] < s <= t[cnt]
-                            const double pa = ax * b.y - ay * b.x;
-                            const double dot = ax * b.x + ay * b.y;
-                            const double pb = rho2 * b.z - az * dot;
-                            const double a2 = pa * pa;
-                            const double b2 = pb * pb;
-                            const double den = a2 + b2;
-                            if (den != 0.0) {
-                                const double c2 = (a2 - b2) / den;
-                                const double s2 = ((2.0 * pa) * pb) / den;
-                                const double tv = -(ag1 * c2 + ag2 * s2);
-                                const double xv = ag1 * s2 - ag2 * c2;
-                                atomicAdd(&wh[cnt - 1], b.w * tv);
-                                atomicAdd(&wh[nf + cnt - 1], b.w * xv);
-                            }
-                            atomicAdd(&wh[2 * nf + cnt - 1], b.w * aw);
-                        }
-                    }
-                }
-            }
-            if (have_next) stage[((st + 1) & 1) * STAGE + tid] = nxt;
-            __syncthreads();
-        }
-    }
-
-    __syncthreads();
-    const int64_t plane = n_cells * nf;
-    for (int j = tid; j < 3 * nf; j += WG) {  // the four waves' histograms in a fixed order
-        const double v = ((hist[j] + hist[3 * nf + j]) + hist[2 * 3 * nf + j]) + hist[3 * 3 * nf + j];
-        const int c = j / nf;
-        out[(int64_t)c * plane + cell * nf + (j - c * nf)] = v;
-    }
-    if (tid == 0) evaluated[cell] = work;
-}
-
-// out: [4][n_cells][E-1] (P, M, C, W), every element written; evaluated: [n_cells] separations the cell's workgroup evaluated
-// (on a diagonal cell that includes the few of a tile's first stage that the index test then drops)
-__global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, const int32_t *__restrict__ jobs, int n_edges,
-                                                         const double *__restrict__ t, const double *__restrict__ rwin,
-                                                         int64_t n_cells, double *__restrict__ out,
-                                                         unsigned long long *__restrict__ evaluated) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    Obj6 *stage = reinterpret_cast<Obj6 *>(lds_raw);                                 // [2][STAGE]
-    double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(Obj6));    // [n_edges]
-    double *hist = thr + ((n_edges + 1) & ~1);                                       // [WAVES][4][nf]
-
-    const int tid = threadIdx.x;
-    const int nf = n_edges - 1;
-    const int64_t cell = blockIdx.x;
-    const int64_t job = cell / nb;
-    const int k = (int)(cell - job * nb);
-    const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
-    const bool diag = p == q;
-    const int64_t seg0 = src.off[p * nb + k], seg1 = src.off[p * nb + k + 1];    // streamed
-    const int64_t a_beg = src.off[q * nb + k], a_end = src.off[q * nb + k + 1];  // in lanes
-
-    for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
-    for (int j = tid; j < WAVES * 4 * nf; j += WG) hist[j] = 0.0;
-    const double tmax = t[(int64_t)k * n_edges + n_edges - 1];
-    const double rw = rwin[k];
-    double *wh = hist + (tid >> 6) * 4 * nf;  // this wave's histogram
-    unsigned long long work = 0;
-    __syncthreads();
-
-    for (int64_t ta = a_beg; ta < a_end && seg1 > seg0; ta += WG) {
-        const int64_t t_last = (ta + WG < a_end ? ta + WG : a_end) - 1;
-        // streamed objects that can hold partners of the tile: keys in [first key - rw, last key + rw] (k_count_shear); both
-        // sides are segments of one handle, sorted along the same axis
-        const double wlo = src.key[ta] - rw, whi = src.key[t_last] + rw;
-        int64_t l = seg0, h = seg1;  // first index with key >= wlo
-        while (l < h) {
-            const int64_t m = (l + h) >> 1;
-            if (src.key[m] < wlo) l = m + 1; else h = m;
-        }
-        int64_t b0 = l;
-        h = seg1;  // first index with key > whi
-        while (l < h) {
-            const int64_t m = (l + h) >> 1;
-            if (src.key[m] <= whi) l = m + 1; else h = m;
-        }
-        const int64_t b1 = l;
         if (diag && b0 <= ta) b0 = ta + 1;  // a partner with a larger index than some lane of the tile
         const int64_t nb_total = b1 - b0;
         if (nb_total <= 0) continue;  // (the same for every thread)
@@ -292,45 +257,34 @@ __global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, 
         const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
         const double ag1 = ok ? src.wg1[ia] : 0.0;
         const double ag2 = ok ? src.wg2[ia] : 0.0;
-        const double rho2 = ax * ax + ay * ay;
+        const Lane a{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay};
         // a diagonal cell counts the streamed object i of a stage only for lanes with ia < its index: i > ia - (first of stage)
         const int64_t lane_rel = diag ? ia - b0 : (int64_t)-1 - (int64_t)STAGE;
 
         const int nstages = (int)((nb_total + STAGE - 1) / STAGE);
-        {  // stage 0 (the barrier that ended the previous tile's last stage has freed both buffers)
-            const int64_t i = b0 + tid;
-            const bool have = i < b1;
-            Obj6 o;
-            o.x = have ? src.x[i] : 0.0; o.y = have ? src.y[i] : 0.0; o.z = have ? src.z[i] : 0.0;
-            o.w = (have && src.w) ? src.w[i] : 1.0;
-            o.g1 = have ? src.wg1[i] : 0.0; o.g2 = have ? src.wg2[i] : 0.0;
-            stage[tid] = o;
-        }
+        // stage 0 (the barrier that ended the previous tile's last stage has freed both buffers)
+        stage[tid] = P::load(str, b0 + tid, b0 + tid < b1);
         __syncthreads();
 
         for (int st = 0; st < nstages; ++st) {
-            const Obj6 *cur = stage + (st & 1) * STAGE;
-            Obj6 nxt;  // the next stage's global loads are issued early: they land in registers while this one is computed
+            const O *cur = stage + (st & 1) * STAGE;
+            O nxt;  // the next stage's global loads are issued early: they land in registers while this one is computed
             const bool have_next = st + 1 < nstages;
             if (have_next) {
                 const int64_t i = b0 + (int64_t)(st + 1) * STAGE + tid;
-                const bool have = i < b1;
-                nxt.x = have ? src.x[i] : 0.0; nxt.y = have ? src.y[i] : 0.0; nxt.z = have ? src.z[i] : 0.0;
-                nxt.w = (have && src.w) ? src.w[i] : 1.0;
-                nxt.g1 = have ? src.wg1[i] : 0.0; nxt.g2 = have ? src.wg2[i] : 0.0;
+                nxt = P::load(str, i, i < b1);
             }
             const int64_t left = nb_total - (int64_t)st * STAGE;
             const int n = left < STAGE ? (int)left : STAGE;
-            // streamed i of this stage counts for the lane iff i > rel (-1: all of them); tested behind the bisection, so that
-            // the hot loop stays that of k_count_shear
+            // streamed i of this stage counts for the lane iff i > rel (-1: all of them); tested behind the bisection, as a
+            // 32-bit compare, so that the hot loop is the same with and without diagonal cells
             const int64_t rel64 = lane_rel - (int64_t)st * STAGE;
             const int rel = rel64 < 0 ? -1 : (int)rel64;
             for (int i = 0; i < n; ++i) {
-                const Obj6 &b = cur[i];  // wave-wide broadcast reads (g1, g2 only behind the ballot)
-                const double bx = b.x, by = b.y, bz = b.z;
-                const double dx = ax - bx;
-                const double dy = ay - by;
-                const double dz = az - bz;
+                typename P::Read b = cur[i];  // wave-wide broadcast read
+                const double dx = a.x - b.x;
+                const double dy = a.y - b.y;
+                const double dz = a.z - b.z;
                 const double xx = dx * dx;
                 const double yy = dy * dy;
                 const double zz = dz * dz;
@@ -343,34 +297,8 @@ __global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, 
                             const int mid = (cnt + hi) >> 1;
                             if (thr[mid] < s) cnt = mid + 1; else hi = mid;
                         }
-                        if (cnt > 0 && i > rel) {  // t[cnt-1] < s <= t[cnt], and not the lower half of a diagonal cell
-                            const double pa = ax * by - ay * bx;
-                            const double dot = ax * bx + ay * by;
-                            const double pbA = rho2 * bz - az * dot;
-                            const double pbB = (bx * bx + by * by) * az - bz * dot;
-                            const double a2 = pa * pa;
-                            const double bA2 = pbA * pbA;
-                            const double bB2 = pbB * pbB;
-                            const double denA = a2 + bA2;
-                            const double denB = a2 + bB2;
-                            if (denA != 0.0 && denB != 0.0) {
-                                const double cA = (a2 - bA2) / denA;
-                                const double sA = ((2.0 * pa) * pbA) / denA;
-                                const double cB = (a2 - bB2) / denB;
-                                const double sB = ((-2.0 * pa) * pbB) / denB;
-                                const double bg1 = b.g1, bg2 = b.g2;
-                                const double tA = -(ag1 * cA + ag2 * sA);
-                                const double xA = ag1 * sA - ag2 * cA;
-                                const double tB = -(bg1 * cB + bg2 * sB);
-                                const double xB = bg1 * sB - bg2 * cB;
-                                const double tt = tA * tB;
-                                const double xx2 = xA * xB;
-                                atomicAdd(&wh[cnt - 1], tt + xx2);
-                                atomicAdd(&wh[nf + cnt - 1], tt - xx2);
-                                atomicAdd(&wh[2 * nf + cnt - 1], tA * xB + xA * tB);
-                            }
-                            atomicAdd(&wh[3 * nf + cnt - 1], aw * b.w);
-                        }
+                        // t[cnt-1] < s <= t[cnt], and not the lower half of a diagonal cell
+                        if (cnt > 0 && (!P::DIAGONAL || i > rel)) P::add(a, b, wh, cnt - 1, nf);
                     }
                 }
             }
@@ -381,12 +309,28 @@ __global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, 
 
     __syncthreads();
     const int64_t plane = n_cells * nf;
-    for (int j = tid; j < 4 * nf; j += WG) {  // the four waves' histograms in a fixed order
-        const double v = ((hist[j] + hist[4 * nf + j]) + hist[2 * 4 * nf + j]) + hist[3 * 4 * nf + j];
+    for (int j = tid; j < NP * nf; j += WG) {  // the four waves' histograms in a fixed order
+        const double v = ((hist[j] + hist[NP * nf + j]) + hist[2 * NP * nf + j]) + hist[3 * NP * nf + j];
         const int c = j / nf;
         out[(int64_t)c * plane + cell * nf + (j - c * nf)] = v;
     }
     if (tid == 0) evaluated[cell] = work;
+}
+
+// out: [3][n_cells][E-1] (T, X, W)
+__global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src, const int32_t *__restrict__ jobs, int n_bins,
+                                                    int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
+                                                    int64_t n_cells, double *__restrict__ out,
+                                                    unsigned long long *__restrict__ evaluated) {
+    shear_walk<Tangential>(lens, src, jobs, n_bins, n_edges, t, rwin, n_cells, out, evaluated);
+}
+
+// out: [4][n_cells][E-1] (P, M, C, W); nb: the handle's redshift bins = the bins of the call
+__global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, const int32_t *__restrict__ jobs, int n_edges,
+                                                         const double *__restrict__ t, const double *__restrict__ rwin,
+                                                         int64_t n_cells, double *__restrict__ out,
+                                                         unsigned long long *__restrict__ evaluated) {
+    shear_walk<ShearShear>(src, src, jobs, nb, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -486,22 +430,24 @@ int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_p
     return YAWHIP_OK;
 }
 
-// What a count call keeps on the handle: one table in (thresholds [B][E], window half widths [B], jobs [n_jobs][2]) and the
-// result block (n_planes planes [cells][E-1], then the cells' evaluated separations).
-struct CallBlock {
-    const double *t, *rwin;
-    const int32_t *jobs;
-    double *out;
-    unsigned long long *evaluated;
-    size_t plane;  // elements of one plane
-};
 
-int stage_call(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
-               int32_t n_edges, const double *t, int n_planes, CallBlock *blk) {
+// What the two counts share once their arguments are checked. One table goes to the handle's d_in (thresholds [B][E], window
+// half widths [B], jobs [n_jobs][2]); launch(jobs, t, rwin, n_cells, out, evaluated) puts the kernel on the stream between the
+// context's two events, writing the result block in d_out (n_planes planes [cells][E-1], then the cells' evaluated
+// separations); the planes come back to fine[], the counters and the event time to the statistics.
+template <class Launch>
+int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
+              int32_t n_edges, const double *t, int n_planes, double *const *fine, int64_t candidates,
+              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Launch launch) {
+    if (stats) *stats = yawhip_stats{};
+    if (n_jobs == 0) return YAWHIP_OK;
     const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + 2 * (size_t)n_jobs * sizeof(int32_t);
+    const size_t n_cells = (size_t)n_jobs * (size_t)n_bins, plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)n_planes * plane;
     std::vector<unsigned char> h_in;
+    std::vector<unsigned long long> h_eval;
     try {
         h_in.resize(in_bytes);
+        if (stats) h_eval.resize(n_cells);
     } catch (const std::bad_alloc &) {
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
@@ -514,43 +460,27 @@ int stage_call(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, i
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
-    const size_t n_cells = (size_t)n_jobs * (size_t)n_bins;
-    blk->plane = n_cells * (size_t)(n_edges - 1);
-    const size_t n_out = (size_t)n_planes * blk->plane;
     HIP_TRY(sources->d_in.reserve(in_bytes, in_bytes / 4 + 64));
     HIP_TRY(sources->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
     // (pageable memory: the copy has left h_in when the call returns)
     HIP_TRY(hipMemcpyAsync(sources->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    blk->t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr);
-    blk->rwin = blk->t + n_t;
-    blk->jobs = reinterpret_cast<const int32_t *>(blk->rwin + n_bins);
-    blk->out = sources->d_out.ptr;
-    blk->evaluated = reinterpret_cast<unsigned long long *>(blk->out + n_out);
-    return YAWHIP_OK;
-}
-
-// after the kernel, between the context's two events: the planes and the counters back to the host, and the statistics
-int finish_call(const char *fn, yawhip_ctx *ctx, const CallBlock &blk, int n_planes, double *const *fine, int64_t n_cells,
-                int64_t candidates, std::chrono::steady_clock::time_point wall0, yawhip_stats *stats) {
+    const double *d_t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr), *d_rwin = d_t + n_t;
+    double *d_out = sources->d_out.ptr;
+    unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    launch(reinterpret_cast<const int32_t *>(d_rwin + n_bins), d_t, d_rwin, (int64_t)n_cells, d_out, d_eval);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     for (int c = 0; c < n_planes; ++c)
-        HIP_TRY(hipMemcpyAsync(fine[c], blk.out + (size_t)c * blk.plane, blk.plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<unsigned long long> h_eval;
-    if (stats) {
-        try {
-            h_eval.resize((size_t)n_cells);
-        } catch (const std::bad_alloc &) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-        }
-        HIP_TRY(hipMemcpyAsync(h_eval.data(), blk.evaluated, (size_t)n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    }
+        HIP_TRY(hipMemcpyAsync(fine[c], d_out + (size_t)c * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats) HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (stats) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
         stats->candidate_pairs = candidates;
         for (unsigned long long v : h_eval) stats->evaluated_pairs += (int64_t)v;
-        stats->n_workgroups = n_cells;
+        stats->n_workgroups = (int64_t)n_cells;
         stats->n_launches = 1;
         stats->kernel_ms = stats->count_ms = ms;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
@@ -595,9 +525,6 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
     if (lenses->nb != 1 && lenses->nb != n_bins)
         return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
     if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
-    const int64_t n_cells = (int64_t)n_jobs * n_bins;
-    if (stats) *stats = yawhip_stats{};
-    if (n_jobs == 0) return YAWHIP_OK;
 
     int64_t candidates = 0;
     for (int j = 0; j < n_jobs; ++j) {
@@ -607,15 +534,13 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
                                                : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
         candidates += n_src * n_lens;
     }
-    CallBlock blk;
-    if (const int rc = stage_call(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, 3, &blk)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges), ctx->stream, view_of(lenses), view_of(sources),
-                       blk.jobs, n_bins, n_edges, blk.t, blk.rwin, n_cells, blk.out, blk.evaluated);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    double *const fine[3] = {fine_t, fine_x, fine_w};
-    return finish_call(fn, ctx, blk, 3, fine, n_cells, candidates, wall0, stats);
+    double *const fine[] = {fine_t, fine_x, fine_w};
+    return run_count(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, Tangential::PLANES, fine, candidates, wall0, stats,
+                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes<Tangential>(n_edges), ctx->stream,
+                                            view_of(lenses), view_of(sources), d_jobs, n_bins, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
+                     });
 }
 
 int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
@@ -635,9 +560,6 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
     for (int j = 0; j < n_jobs; ++j)
         if (jobs[2 * j] > jobs[2 * j + 1])
             return fail(YAWHIP_ERR_INVALID, "job %d = (%d, %d): an autocorrelation job has p <= q", j, jobs[2 * j], jobs[2 * j + 1]);
-    const int64_t n_cells = (int64_t)n_jobs * n_bins;
-    if (stats) *stats = yawhip_stats{};
-    if (n_jobs == 0) return YAWHIP_OK;
 
     int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
     for (int j = 0; j < n_jobs; ++j)
@@ -646,15 +568,13 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
             const int64_t n_p = sources->h_off[sp + 1] - sources->h_off[sp], n_q = sources->h_off[sq + 1] - sources->h_off[sq];
             candidates += sp == sq ? n_p * (n_p - 1) / 2 : n_p * n_q;
         }
-    CallBlock blk;
-    if (const int rc = stage_call(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, 4, &blk)) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_count_shear_auto, dim3((unsigned)n_cells), dim3(WG), lds_bytes(n_edges, sizeof(Obj6), 4), ctx->stream,
-                       view_of(sources), n_bins, blk.jobs, n_edges, blk.t, blk.rwin, n_cells, blk.out, blk.evaluated);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    double *const fine[4] = {fine_p, fine_m, fine_c, fine_w};
-    return finish_call(fn, ctx, blk, 4, fine, n_cells, candidates, wall0, stats);
+    double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
+    return run_count(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, ShearShear::PLANES, fine, candidates, wall0, stats,
+                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_shear_auto, dim3((unsigned)n_cells), dim3(WG), lds_bytes<ShearShear>(n_edges), ctx->stream,
+                                            view_of(sources), n_bins, d_jobs, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
+                     });
 }
 
 }  // extern "C"

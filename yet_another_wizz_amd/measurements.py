@@ -485,27 +485,16 @@ class PatchLinkage:
         the cross shear of the pairs, each over the sum of their weights ``w_l * w_s``. Thresholds, separation weights and
         per-scale sums are those of ``count_pairs``; ONE library call counts all jobs (``engine.count_shear_fine``), on one
         device of one process: several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
-        if parallel.world()[1] > 1:
-            raise NotImplementedError("shear counts run in one process on one device")
-        if count_type_info is not None:
-            _log_info("counting %s from patch pairs", count_type_info)
-        binning = self.config.binning.binning
-        num_bins, num_patches = len(binning), len(lenses)
-        lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
-        if source_layout.g1 is None or source_layout.g2 is None:
-            raise ValueError("catalog has no 'g1'/'g2' attached")
-        jobs = self.get_patch_pairs(lenses, sources)
-        _, thresholds = self._angular_setup()
-        *fine, stats = engine.count_shear_fine(lens_layout, source_layout, jobs, thresholds, sort_axis=self.sort_axis)
-        self.last_stats = stats
-        self._report(count_type_info, len(jobs), stats, progress)
-        flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
-        shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
-        # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
-        T, X, W = (_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine)
+        def layouts(num_bins):
+            lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
+            if source_layout.g1 is None or source_layout.g2 is None:
+                raise ValueError("catalog has no 'g1'/'g2' attached")
+            return engine.count_shear_fine, (lens_layout, source_layout)
+
+        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress)
         return [(NormalisedScalarCounts(PatchedCounts(binning, T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
                  NormalisedScalarCounts(PatchedCounts(binning, X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
-                for s in range(shape[0])]
+                for s in range(len(W))]
 
     def count_shear_auto_pairs(self, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
                                count_type_info: str | None = None) -> list:
@@ -516,29 +505,40 @@ class PatchLinkage:
         autocorrelation count holds after its x 0.5. Thresholds, separation weights and per-scale sums are those of
         ``count_pairs``; ONE library call counts all jobs (``engine.count_shear_auto_fine``), on one device of one process:
         several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
+        def layouts(num_bins):
+            layout = _active_layout(sources, num_bins)
+            if layout.g1 is None or layout.g2 is None:
+                raise ValueError("catalog has no 'g1'/'g2' attached")
+            if layout.num_bins != num_bins:
+                raise ValueError("shear-shear counts need the sources binned in redshift")
+            return engine.count_shear_auto_fine, (layout,)
+
+        binning, (P, M, C, W) = self._count_shear_planes((sources,), layouts, count_type_info, progress)
+        return [tuple(NormalisedScalarCounts(PatchedCounts(binning, num[s], auto=True), PatchedCounts(binning, W[s], auto=True))
+                      for num in (P, M, C))
+                for s in range(len(W))]
+
+    def _count_shear_planes(self, catalogs, layouts, count_type_info, progress):
+        """What the two shear counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the engine's
+        count (``count_shear_fine`` / ``count_shear_auto_fine``, looked up at call time: the CPU tests replace them) with the
+        layouts it takes; its job list is ``get_patch_pairs(*catalogs)``. Returns the binning and one f64[S, B, P, P] per
+        plane of the count, zero outside the jobs."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("shear counts run in one process on one device")
         if count_type_info is not None:
             _log_info("counting %s from patch pairs", count_type_info)
         binning = self.config.binning.binning
-        num_bins, num_patches = len(binning), len(sources)
-        layout = _active_layout(sources, num_bins)
-        if layout.g1 is None or layout.g2 is None:
-            raise ValueError("catalog has no 'g1'/'g2' attached")
-        if layout.num_bins != num_bins:
-            raise ValueError("shear-shear counts need the sources binned in redshift")
-        jobs = self.get_patch_pairs(sources)
+        num_bins, num_patches = len(binning), len(catalogs[0])
+        count_fine, count_layouts = layouts(num_bins)
+        jobs = self.get_patch_pairs(*catalogs)
         _, thresholds = self._angular_setup()
-        *fine, stats = engine.count_shear_auto_fine(layout, jobs, thresholds, sort_axis=self.sort_axis)
+        *fine, stats = count_fine(*count_layouts, jobs, thresholds, sort_axis=self.sort_axis)
         self.last_stats = stats
         self._report(count_type_info, len(jobs), stats, progress)
         flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
         shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
         # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
-        P, M, C, W = (_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine)
-        return [tuple(NormalisedScalarCounts(PatchedCounts(binning, num[s], auto=True), PatchedCounts(binning, W[s], auto=True))
-                      for num in (P, M, C))
-                for s in range(shape[0])]
+        return binning, [_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine]
 
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
