@@ -30,8 +30,10 @@ def _guard(s):
 
 
 def test_constants_match_the_kernel_source():
-    src = open(os.path.join(ROOT, "yet_another_wizz_amd", "csrc", "yawhip.hip")).read()
-    assert re.search(r"BAND32_GUARD_SQRT = 2\.1e-7;", src)
+    csrc = os.path.join(ROOT, "yet_another_wizz_amd", "csrc")
+    header = open(os.path.join(csrc, "yawhip_count_kernels.h")).read()  # the constant the kernels and the host tables share
+    src = open(os.path.join(csrc, "yawhip_count.hip")).read()           # build_thr32 / build_fine32
+    assert re.search(r"BAND32_GUARD_SQRT = 2\.1e-7;", header)
     assert src.count("BAND32_GUARD_SQRT * std::sqrt(te) + 5e-7 * te + 1e-12") == 2
     assert "const double fold = 4e-7 * cd;" in src
 
@@ -70,7 +72,7 @@ def _q32(a, b, c):
 
 
 def _annulus_classes(t0, t1):
-    """build_thr32 for two edges (yawhip.hip), restated: centre, half width of "certainly inside", of "possibly inside"."""
+    """build_thr32 for two edges (yawhip_count.hip), restated: centre, half width of "certainly inside", of "possibly inside"."""
     g0, g1 = _guard(t0), _guard(t1)
     c = (0.5 * (t0 + t1)).astype(np.float32)
     cd = c.astype(np.float64)

@@ -18,7 +18,7 @@ from oracle import oracle
 pytestmark = pytest.mark.gpu
 RTOL_W = 1e-10
 ARCMIN = np.pi / 10800
-LDS_TABLE = 1024  # BUILD_PREFIX_LDS of csrc/yawhip.hip: job tables of n + 1 <= 1024 entries are searched in LDS
+LDS_TABLE = 1024  # BUILD_PREFIX_LDS of csrc/yawhip_count_kernels.h: job tables of n + 1 <= 1024 entries are searched in LDS
 
 
 @pytest.fixture(scope="module")

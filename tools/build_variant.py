@@ -6,9 +6,11 @@
         ->  yet_another_wizz_amd/build/variants/libyawhip_diag1.so
     YAW_AMD_LIB=yet_another_wizz_amd/build/variants/libyawhip_diag1.so python bench.py ...
 
-Only the kernel translation unit (build.KERNEL_UNIT, csrc/yawhip.hip) is recompiled and linked with the product's other
-objects -- unless the patch changes a file other than that unit and its yawhip_band32.inc (the private header, another
-unit): then every unit is compiled from the patched copy, so that all of them agree on the shared records. With --patch FILE the unit is
+Only the kernel translation unit (build.KERNEL_UNIT, csrc/yawhip.hip: the count kernels and the functions that launch them,
+nothing else -- the planner and the entry points are yawhip_count.hip's and never see a -D flag) is recompiled and linked
+with the product's other objects -- unless the patch changes a file other than that unit and its yawhip_band32.inc (a
+private header such as yawhip_count_kernels.h, another unit): then every unit is compiled from the patched copy, so that all
+of them agree on the shared records. With --patch FILE the unit is
 compiled from a patched COPY of csrc/ and include/yawhip.h under variants/src_<tag>/: neither the working tree nor the
 in-tree product library is touched."""
 import argparse

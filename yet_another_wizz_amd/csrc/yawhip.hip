@@ -1,6 +1,10 @@
-// yawhip.hip -- MI355X (gfx950 / CDNA4) angular pair counting: the count kernels, the item builders and the count call
-// that plans and launches them (count_enqueue / count_finish / run_single, yawhip_count_pairs, yawhip_job_work), behind the C
-// ABI of include/yawhip.h. The rest of the library lives in units of its own, joined by csrc/yawhip_internal.h:
+// yawhip.hip -- MI355X (gfx950 / CDNA4) angular pair counting: the DEVICE code of the count call -- the item builders, the
+// count kernels, the reductions and the tail -- and the launch layer that puts them on a stream. This unit decides nothing:
+// the count call of yawhip_count.hip plans a call (kernel, layouts, tile and stage sizes, tables) and hands every launch one
+// record, CountLaunch, whose selectors name the variant to run; csrc/yawhip_count_kernels.h declares that interface with the
+// geometry and the counter-block layout the two units share. No entry point of include/yawhip.h lives here, and experiment
+// flags and variant builds (build.KERNEL_UNIT, tools/build_variant.py) recompile this unit alone. The rest of the library:
+//   yawhip_count.hip    the count call: plans, count_enqueue / count_finish / run_single, yawhip_count_pairs, yawhip_job_work;
 //   yawhip_ingest.hip   catalogue upload, strip layouts and merged triple runs, yawhip_assign_patches (with their kernels);
 //   yawhip_dense.hip    the dense epilogue on top of the count call: yawhip_count_pairs_dense(_batch), ..._rows_device;
 //   yawhip_api.hip      contexts and options, error reporting, host-side grouping, and the wrappers of yawhip_hist.hip,
@@ -43,33 +47,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <numeric>
-#include <chrono>
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <new>
-#include <string>
+#include <cstdint>
 #include <type_traits>
 #include <utility>
-#include <functional>
-#include <vector>
 
-#include "yawhip_internal.h"
+#include "yawhip_count_kernels.h"
 
 using namespace yawhip_detail;
 
 namespace {
-constexpr int WG = 256;      // threads per workgroup = 4 waves of 64
-constexpr int STAGE = 256;   // streamed objects per LDS stage (one per thread)
-constexpr int MSTAGE = 64;   // stage of the merged path: smaller -> less LDS -> more workgroups per CU
-constexpr int MAX_EDGES = 512;
-constexpr int BAND_MIN_STREAM_RUN = 64;  // AUTO: objects per run of the streamed side (as the typical object sees it) from which the band kernel is used
-constexpr int64_t SYNC_GRID_MIN_ITEMS = 400000;  // potential items from which the count grid is sized exactly (one host sync)
-constexpr int MAX_STRIP_REACH = 12;  // strip pairing is used while sqrt(t_max) <= 12 grid spacings
 constexpr int COUNT_FLUSH_MASK = (1 << 13) - 1;  // k_count: stages between flushes of the 32-bit LDS counters (see there)
 constexpr int MERGED_FLUSH_MASK = (1 << 16) - 1; // k_count_merged: 256 lane objects x 64 streamed objects per stage
 constexpr double PAD_COORD = 4.0;  // padded lanes sit >= 3 away from any unit vector: s >= 9 > max t = 4
@@ -82,25 +68,10 @@ struct alignas(16) ObjF {  // its float32 image for the pre-filter: one 16-byte 
     float x, y, z, pad;
 };
 
-// Pre-filter guard (see k_count): |dot32 - a.b| <= 5.000001 u for unit vectors rounded to float32 and
-// a mul + 2 fma evaluation (u = 2^-24); 8 u leaves room for |a|^2 deviating from 1 by < 1e-9 and for
-// the rounding of the threshold itself.
-constexpr double FILTER_GUARD = 8.0 * 5.9604644775390625e-8;
-
 // ------------------------------------------------------------------------------------------------
-// Spherical caps (strip grid in latitude, trimmed u-bands; DESIGN.md sections 3 and 4).
-// A pair passes s <= t_max only if its chord |a - b| <= rwin = sqrt(t_max) (1 + 1e-12) + 1e-15 (the float64 rounding of s,
-// see k_build_items). The DIRECTIONS of a and b are then at most the angle sep_angle(rwin) apart: |a|^2 is within
-// UNIT_NORM_TOL of 1, so ||a| - 1| <= 5e-10 and |a^ - b^| <= |a - b| + 1e-9 (2e-9 is added). Two consequences:
-//   * latitudes about any axis (atan2(v, hypot(u, w)), the direction's own) differ by at most that angle: the strip grid of
-//     k_strip_index in latitude pairs runs whose grid indices differ by at most floor(theta / width) + 1;
-//   * with alpha = acos(u^) the polar angle of a about the sort axis, every partner has polar angle alpha -/+ theta, i.e.
-//     u^_b in [cos(min(pi, alpha + theta)), cos(max(0, alpha - theta))] = [u c - sqrt(1 - u^2) s, u c + sqrt(1 - u^2) s]
-//     (c = cos theta, s = sin theta), -1 below where alpha + theta > pi (u < -c), +1 above where alpha < theta (u > c).
-//     Both bounds are monotone in u, so the band of objects with keys in [u0, u1] runs from lo(u0) to hi(u1).
+// Spherical caps: the u-range the partners of an object with key u can have, [u c - sqrt(1 - u^2) s, u c + sqrt(1 - u^2) s]
+// with c, s = cos, sin of the largest separation angle (sep_angle, yawhip_count_kernels.h: the derivation is there).
 // The bounds are culling bounds only: classification and the exact float64 path do not see them.
-inline double sep_angle(double rwin) { return 2.0 * std::asin(std::min(1.0, 0.5 * (rwin + 2e-9))); }
-
 // float64 (item builder): the key u is a float64 coordinate, |u - u^| <= 5e-10 (unit norm); shifting u by 1e-9 outward keeps
 // the exact bound below / above the one of u^, the clip decisions are widened by 1e-12 (rounding of cos theta), and the
 // result by 2e-9 (|u_b - u^_b| <= 5e-10 for the partner's key, plus the double-rounding of the formula, ~1e-15).
@@ -146,15 +117,10 @@ constexpr int BUILD_BISECT = 32;  // most bisection steps of the strip builder i
 //                  s = fl(fl(dx^2 + dy^2) + dz^2) >= dz^2 (1 - 3 eps). Items with an empty window are
 //                  dropped; survivors are appended with one atomic per workgroup (order is irrelevant).
 // ------------------------------------------------------------------------------------------------
-constexpr int EVAL_SLOTS = 256;  // statistics counters, one 64-byte line each (a single hot address would serialise)
-constexpr int BUILD_WG = 1024;       // most threads per workgroup of the item builders
-// Builder workgroups: one atomic per workgroup appends its items, so few large workgroups suit long lists (16 k atomics on
-// the one counter cost 0.15 ms at 4 M potential items), but 1024 threads make 300 workgroups for 256 CUs at the headline
-// and half the chip waits for the CUs that got two (+0.07 ms): 256 threads while that keeps the atomics below 4096.
-constexpr int BUILD_WG_SMALL = 256;
-inline int build_wg_for(int64_t n_pot) { return n_pot / 256 <= 4096 ? BUILD_WG_SMALL : BUILD_WG; }
-constexpr int BUILD_PREFIX_LDS = 1024;  // job tables up to this many entries are searched in LDS by the strip builder (8 KB: no occupancy cost)
-
+// A clock stamp of the call (CTR_T_*, yawhip_count_kernels.h), by the first thread of a kernel
+__device__ __forceinline__ void stamp_start(unsigned long long *__restrict__ counters, int word) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counters[word] = wall_clock64();
+}
 // Append the kept items of a builder workgroup to the item list and add its evaluated-pair total: ONE atomic
 // per workgroup on each of the two counters. (They are single hot addresses -- with an atomic per wave the
 // builders spent three quarters of their time queueing on them.) Order of the list is irrelevant.
@@ -163,25 +129,6 @@ constexpr int BUILD_PREFIX_LDS = 1024;  // job tables up to this many entries ar
 // address the 1200 appends of the headline queue for 10 of the builder's 43 us), and a segment -- every eighth builder
 // workgroup's tiles -- is the same mix of dense and sparse items as the whole list: the float32 band kernels give XCD x
 // segment x.
-constexpr int ITEM_SEGS = 8;
-__host__ __device__ constexpr int ITEM_SEG_CTR(int seg) { return 12 + 8 * seg; }  // counters[]: one 64-byte line each
-// Clock stamps of a call (wall_clock64: the constant 100 MHz counter) and the words of its tail, in free words of the counter
-// block; they travel to the host with the counters (k_call_tail) and give yawhip_stats.kernel_ms / count_ms without an
-// event between the kernels.
-//   CTR_T_BUILD     the builder's first workgroup starts
-//   SEG_EXIT_CTR(s) latest exit of a builder workgroup, one word per item segment: spread like the append counters (one
-//                   shared word would take every workgroup's atomic in turn)
-//   CTR_T_COUNTED   the first kernel behind the count kernel(s) starts (reductions, k_counts_to_double); the tail writes its
-//                   own start here when there is none
-//   CTR_T_TAIL      the tail's first workgroup starts
-//   CTR_TICKET      the tail's workgroups draw tickets here (the last one to finish signs the call off); wraps to 0
-//   CTR_DONE        host image only: the sequence number of the call whose results the pinned block holds
-constexpr int CTR_T_BUILD = 1, CTR_T_COUNTED = 2, CTR_T_TAIL = 3, CTR_TICKET = 4, CTR_DONE = 6;
-__host__ __device__ constexpr int SEG_EXIT_CTR(int seg) { return ITEM_SEG_CTR(seg) + 1; }
-constexpr double CLOCK_MS = 1.0e-5;  // milliseconds per tick of wall_clock64
-__device__ __forceinline__ void stamp_start(unsigned long long *__restrict__ counters, int word) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) counters[word] = wall_clock64();
-}
 __device__ __forceinline__ void append_items(bool keep, const Item &it, unsigned long long work, Item *__restrict__ items,
                                              unsigned long long *__restrict__ counters, unsigned char *__restrict__ kept,
                                              unsigned long long seg_cap = 0) {
@@ -209,9 +156,9 @@ __device__ __forceinline__ void append_items(bool keep, const Item &it, unsigned
             const int seg = (int)(blockIdx.x % ITEM_SEGS);
             s_base = (unsigned long long)seg * seg_cap + (total ? atomicAdd(&counters[ITEM_SEG_CTR(seg)], (unsigned long long)total) : 0ull);
         } else {
-            s_base = total ? atomicAdd(&counters[0], (unsigned long long)total) : 0ull;
+            s_base = total ? atomicAdd(&counters[CTR_KEPT], (unsigned long long)total) : 0ull;
         }
-        if (wsum) atomicAdd(&counters[10 + 8 * (blockIdx.x & (EVAL_SLOTS - 1))], wsum);  // statistics, spread like the other totals
+        if (wsum) atomicAdd(&counters[TILE_PAIR_CTR(blockIdx.x & (EVAL_SLOTS - 1))], wsum);  // statistics, spread like the other totals
     }
     __syncthreads();
     if (keep) items[s_base + s_cnt[wave] + __popcll(mask & ((1ull << lane) - 1ull))] = it;
@@ -267,7 +214,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items(CatView c1, CatView c2
     } else {
         if (pot < n_pot) items[pot] = it;  // every potential item is kept
         append_items(false, it, work, items, counters, nullptr);
-        if (pot == 0) counters[0] = (unsigned long long)n_pot;
+        if (pot == 0) counters[CTR_KEPT] = (unsigned long long)n_pot;
     }
 }
 
@@ -668,7 +615,7 @@ __device__ __forceinline__ void count_merged_body(const DevTab *__restrict__ tab
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nf = n_edges - 1;
     const unsigned long long ticket = item_base + blockIdx.x;
-    if (ticket >= counters[0]) return;  // never taken when the host sized the grid from the builder's count
+    if (ticket >= counters[CTR_KEPT]) return;  // never taken when the host sized the grid from the builder's count
     const Item it = items[ticket];
     const int o = item_orient(it), islot = item_slot(it);
     const DevTab T1 = tabs[o], T2 = tabs[3 + o];
@@ -990,11 +937,6 @@ auto pick_count_merged() -> decltype(&k_count_merged<R, WEIGHTED, NF1, MERGED>) 
 // XCD's L2 instead of being fetched by all eight.
 //   UNI: all redshift bins share one threshold row (angular scales): edges live in registers.
 // ------------------------------------------------------------------------------------------------
-constexpr int BCAP = 192;       // window objects per LDS stage. 192: the window of a 128-object lane tile at equal densities (128 +- 11
-                                // entries + one band) fits in one stage; 6.2 KB -> 26 single-wave workgroups per CU. Measured
-                                // 160 / 176 / 192 / 208 / 224: count kernel 0.545 / 0.529 / 0.523 / 0.535 / 0.531 ms at the headline
-constexpr int N_CTR = 8 + 8 * EVAL_SLOTS;  // counters: [0] kept items, [8 + 8 i] band entries, [9 + 8 i] exact re-evaluations, [10 + 8 i] lane-tile x window pairs
-
 // LDS image of a band workgroup. The staged window lives in float64 SoA columns filled by LDS-DMA (global_load_lds_dwordx4:
 // 16 bytes per lane straight from HBM into LDS, no staging registers, no ds_write), one entry of slack per column for the
 // sentinel. The columns sit in a STATIC array at fixed offsets 2064 bytes apart, with the small tables in the gaps:
@@ -1021,20 +963,6 @@ struct BandLds {  // byte offsets inside the static LDS image of a band workgrou
 };
 static_assert(BandLds<160>::Y == 2064 && BandLds<160>::Z == 4128 && BandLds<160>::FIXED == 5424, "band LDS image");
 static_assert(BandLds<192>::FIXED == 6208, "band LDS image");
-// Stage capacities the band kernel is compiled for. A stage should hold the whole window of a lane tile (the tile's own
-// extent in streamed entries plus one band): a window cut into stages makes every stage wait for the longest clipped band
-// while the lanes whose bands lie in the other stage idle (50M x 50M, bands of 216 entries: 400 trips per 256 lane objects
-// with 288-entry stages against 219 in one stage).
-// (416-entry stages were measured too: never ahead of 288 -- 23.3 / 23.3 ms at 50M x 50M, 0.70 / 0.59 ms at the headline.)
-constexpr int BCAP_MID = 288;
-inline int band_lds_fixed(int cap) { return cap == BCAP_MID ? BandLds<BCAP_MID>::FIXED : BandLds<BCAP>::FIXED; }
-__host__ __device__ inline bool band_small_hist(bool weighted, int nslots, int hp) { return (size_t)nslots * hp * (weighted ? 8 : 4) <= 512; }
-// dynamic LDS bytes of a band workgroup (host and device agree through this one function)
-__host__ __device__ inline size_t band_lds_dynamic(bool weighted, bool need_thr, int nkb, int n_edges, int hp, int cap, int thr_rows) {
-    const int nslots = nkb * (n_edges - 1);
-    return (weighted ? (size_t)(cap + 2) * 8 : 0) + (need_thr ? (size_t)thr_rows * n_edges * sizeof(double) : 0) +
-           (band_small_hist(weighted, nslots, hp) ? 0 : (size_t)nslots * hp * (weighted ? 8 : 4)) + 16;
-}
 typedef __attribute__((address_space(3))) unsigned char lds_byte;
 __device__ __forceinline__ __attribute__((address_space(3))) void *lds_ptr(unsigned addr) { return (__attribute__((address_space(3))) void *)(size_t)addr; }
 __device__ __forceinline__ double lds_f64(unsigned addr) { return *(const __attribute__((address_space(3))) double *)(size_t)addr; }
@@ -1106,7 +1034,7 @@ __global__ __launch_bounds__(64) void k_count_band(const DevTab *__restrict__ ta
     const unsigned a_dummy = (unsigned)(size_t)(lds_byte *)reinterpret_cast<unsigned char *>(dummy + lane);
     const int ksh = hp_shift + HB;                  // slot number -> byte offset of its first histogram cell
 
-    const unsigned long long n_kept = counters[0];
+    const unsigned long long n_kept = counters[CTR_KEPT];
     const unsigned long long chunk = (n_kept + 7) >> 3;  // items per XCD
     // A workgroup takes 2^batch_log2 CONSECUTIVE items at a time (default: one) and carries its (unweighted) histogram from
     // one to the next while they add to the same output slot -- consecutive items are lane tiles of one job -- so that a
@@ -1406,7 +1334,7 @@ __global__ __launch_bounds__(64) void k_count_band(const DevTab *__restrict__ ta
         if (WEIGHTED) flush_slab();
         // evaluated band entries of the item -> one of EVAL_SLOTS counters (statistics)
         for (int off = 32; off > 0; off >>= 1) nev += __shfl_down(nev, off, 64);
-        if (lane == 0 && nev) atomicAdd(&counters[8 + 8 * (ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
+        if (lane == 0 && nev) atomicAdd(&counters[BAND_ENTRY_CTR(ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
       }
         if (!WEIGHTED && pend_slot >= 0) {  // end of the batch
             flush_counts(pend_slot);
@@ -1468,7 +1396,7 @@ __device__ __forceinline__ TicketMap ticket_map(const unsigned long long *__rest
         m.bs = 0;
         return m;
     }
-    const unsigned long long n_kept = counters[0];
+    const unsigned long long n_kept = counters[CTR_KEPT];
     m.n_kept = n_kept;
     m.seg_base = 0;
     const unsigned long long want = n_kept >> 7;  // ~16 blocks per XCD
@@ -1481,15 +1409,6 @@ __device__ __forceinline__ TicketMap ticket_map(const unsigned long long *__rest
 }
 
 constexpr float PAD_COORD32 = 4.0f;
-constexpr double BAND32_GUARD_SQRT = 2.1e-7;  // coefficient of sqrt(t) in the float32 guard g(t), see k_count_band32
-// float32 words per bin of the threshold table: NE == 2: {c, h_in, h_out, 0}; else per edge {t - g, t + g}
-__host__ __device__ constexpr int thr32_width(int ne) { return ne == 2 ? 4 : 2 * ne; }
-// dynamic LDS of a k_count_band32 workgroup (host and device agree through this one function)
-__host__ __device__ inline size_t band32_lds(bool weighted, int cap, int nslots, int thr_rows, int ne) {
-    return (size_t)3 * (cap + 4) * 4 + (weighted ? (size_t)(cap + 4) * 8 : 0) + (size_t)nslots * (weighted ? 8 : 4) +
-           (size_t)thr_rows * thr32_width(ne) * 4 + 32;
-}
-
 // The exact predicate of the parity contract on the float64 columns, for an evaluation the float32 classes left undecided
 // (rare: kept out of line so that its addresses and temporaries do not live in the walk loop's registers). The float64
 // thresholds the caller will compare with travel in the same round trip as the coordinates: an undecided evaluation stalls
@@ -1517,12 +1436,6 @@ __device__ __attribute__((noinline)) ExactEval<NT> band32_exact(gf64p lx, gf64p 
     return r;
 }
 
-// Stage of k_count_band32 (entries, 12 bytes each + 8 with weights). 320 holds two windows of a typical lane tile (128 objects
-// at equal densities: ~142 entries each) -- measured 192 / 288 / 320 / 448 at the headline: 0.367 / 0.355 / 0.350 / 0.360 ms,
-// weighted 0.521 / 0.519 / 0.511 / 0.556, RR of config #4 4.65 / 4.44 / 4.41 / 4.89 (the larger the stage, the fewer workgroups
-// a CU holds). The big one is for lane tiles whose single window would not fit (denser streamed side, four objects per lane).
-constexpr int B32_CAP = 320;
-constexpr int B32_CAP_BIG = 512;
 // Waves per SIMD the variants of k_count_band32 are compiled for (the second argument of their __launch_bounds__):
 constexpr int B32_WAVES_PLAIN = 7; // the plain count, one annulus, one threshold row: 72 VGPRs instead of 79, 0.359 against 0.371 ms at the
                                    // headline (8 spills: 0.405)
@@ -1571,12 +1484,6 @@ constexpr int band32_min_waves(int R, int CAP, bool WEIGHTED, int NE, bool UNI) 
 // from the grid, with a second look at the table otherwise: 32 instruction slots per evaluation against 18 now, and a
 // third of the walk's trips took the second look. 2.09 -> 1.25 ms then, -> see DESIGN.md for this one.)
 // ------------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int fine32_width(int n_edges) { return 4 + 2 * n_edges; }
-__host__ __device__ inline size_t band32_fine_lds(bool weighted, int cap, int nslots, int rows, int n_edges) {
-    return (size_t)3 * (cap + 4) * 4 + (weighted ? (size_t)(cap + 2) * 8 : 0) + (size_t)nslots * (weighted ? 8 : 4) + 64 * 8 +
-           (size_t)rows * fine32_width(n_edges) * 4 + 48;
-}
-
 template <int R, int CAP, bool WEIGHTED, bool MERGED, bool UNI>
 __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
                                                           int n_edges, const double *__restrict__ t, const float *__restrict__ fine32,
@@ -1831,7 +1738,7 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
                             const ExactEval<1> ev = band32_exact<1>(cl.x, cl.y, cl.z, it.a0 + lane * R + r, cs.x, cs.y, cs.z,
                                                                     cs.idx ? (int64_t)cs.idx[b0 + st0 + eidx] : b0 + st0 + (int64_t)eidx,
                                                                     t + (size_t)(MERGED ? kb[r] : kfix) * n_edges + j,
-                                                                    counters + 9 + 8 * (ticket & (EVAL_SLOTS - 1)));
+                                                                    counters + EXACT_EVAL_CTR(0) + CTR_SLOT_WORDS * (ticket & (EVAL_SLOTS - 1)));
                             const int bin = ev.s <= ev.th[0] ? j - 1 : j;  // t[bin] < s <= t[bin + 1]
                             if ((unsigned)bin < (unsigned)nf) {
                                 const unsigned cell = a_rowh[r] + ((unsigned)bin << HB);
@@ -1865,7 +1772,7 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
             flush_counts();
         }
         nev = wave_sum_lane63(nev);  // (DPP: the shuffle form is six trips through the LDS crossbar, per item, for a statistic)
-        if (lane == 63 && nev) atomicAdd(&counters[8 + 8 * (ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
+        if (lane == 63 && nev) atomicAdd(&counters[BAND_ENTRY_CTR(ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
     }
 }
 
@@ -1873,7 +1780,7 @@ __global__ __launch_bounds__(64) void k_count_band32_fine(const DevTab *__restri
 __global__ void k_item_work(const Item *__restrict__ items, const unsigned long long *__restrict__ counters,
                             int slots_per_job, unsigned long long *__restrict__ job_work) {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= counters[0]) return;
+    if (i >= counters[CTR_KEPT]) return;
     const Item it = items[i];
     unsigned long long streamed = 0;
     for (int w = 0; w < it.nwin; ++w) streamed += (unsigned long long)it.nb[w];
@@ -1884,7 +1791,6 @@ __global__ void k_item_work(const Item *__restrict__ items, const unsigned long 
 // slot in a fixed two-level order -- chunks of REDUCE_CHUNK consecutive potential items, then the chunks of a slot in
 // order -- so the result is bit-reproducible and the reduction is parallel over (chunk, value). Dropped potential
 // items (kept[pot] == 0, their slab is never written) are skipped; kept == nullptr means every item was kept.
-constexpr int REDUCE_CHUNK = 32;
 __global__ void k_reduce_chunks(const double *__restrict__ partials, const unsigned char *__restrict__ kept,
                                 const int64_t *__restrict__ prefix, const int64_t *__restrict__ cprefix, int n_slots,
                                 int slab, double *__restrict__ chunk_sums, unsigned long long *__restrict__ counters) {
@@ -1932,8 +1838,6 @@ __global__ void k_counts_to_double(const unsigned long long *__restrict__ in, do
 // Completion: every thread fences its stores to the host, every workgroup then draws a ticket, and the one that draws the
 // last writes the call's sequence number into the pinned block with a system-scope release -- the host polls that word
 // (count_finish). The ticket word wraps to zero with the last draw. No workgroup waits for another.
-constexpr int TAIL_WG = 256;
-constexpr unsigned TAIL_MAX_GRID = 64;
 __global__ __launch_bounds__(TAIL_WG) void k_call_tail(uint4 *__restrict__ dev, uint4 *__restrict__ host, unsigned n_copy,
                                                       unsigned n_clean, unsigned long long seq) {
     const unsigned long long t0 = wall_clock64();
@@ -1958,14 +1862,6 @@ __global__ __launch_bounds__(TAIL_WG) void k_call_tail(uint4 *__restrict__ dev, 
                                __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-}
-
-inline DevTab make_tab(const double *x, const double *y, const double *z, const double *w, const int32_t *k, const int64_t *off,
-                       const int64_t *vbase, const int64_t *slo, const int64_t *tiles, const TileRec *tile_rec, const RunGrid *grid,
-                       int axis, const float *q = nullptr, int64_t q_stride = 0, const int32_t *idx = nullptr) {
-    return DevTab{(gf64p)x, (gf64p)y, (gf64p)z, (gf64p)w, (gi32p)k, (gi64p)off, (gi64p)vbase, (gi64p)slo, (gi64p)tiles,
-                  tile_rec, grid, (gf32p)q, (gf32p)(q ? q + q_stride : nullptr), (gf32p)(q ? q + 2 * q_stride : nullptr), (gi32p)idx,
-                  (gi32p)nullptr, axis, 0};
 }
 
 // One launch of a count kernel: its dynamic-LDS limit raised first where it needs more than 64 KiB.
@@ -2000,12 +1896,6 @@ template <bool MERGED_, bool UNI_> struct Rows {
     static constexpr std::pair<bool, bool> value{MERGED_, UNI_};
 };
 
-inline int64_t seg_len(const yawhip_catalog *c, int patch, int k) {
-    const int kk = c->nb == 1 ? 0 : k;
-    const int64_t i = (int64_t)patch * c->nb + kk;
-    return c->h_off[i + 1] - c->h_off[i];
-}
-
 // yawhip_stats.count_variant*: the family and template arguments of a count kernel (code layout: include/yawhip.h)
 enum VariantFamily : int32_t { VF_COUNT = 1, VF_MERGED, VF_MERGED_OCC8, VF_BAND, VF_BAND32, VF_BAND32_ONE, VF_BAND32_FINE };
 constexpr int32_t variant_code(int32_t family, int R, int cap, bool weighted, int ne = 0, bool merged = false, bool uni = false,
@@ -2013,1314 +1903,200 @@ constexpr int32_t variant_code(int32_t family, int R, int cap, bool weighted, in
     return family | R << 4 | cap << 8 | (int32_t)weighted << 18 | ne << 19 | (int32_t)merged << 22 | (int32_t)uni << 23 |
            (int32_t)priv << 24 | (int32_t)filter << 25 | (int32_t)nf1 << 26;
 }
-// the variant of a call from those of its pieces: pieces that launched none do not count, different ones make it mixed
-int32_t merge_variant(int32_t a, int32_t b) { return a == 0 || a == b ? b : (b == 0 ? a : YAWHIP_VARIANT_MIXED); }
-
-// Float32 bounds of every edge for k_count_band32 (see there): for unit vectors rounded to float32,
-//   |s32 - s| <= g(t) = 2.1e-7 sqrt(t) + 5e-7 t + 1e-12 near s = t,
-// so s32 < t - g proves s <= t and s32 > t + g proves s > t; in between the kernel evaluates in float64.
-//   n_edges == 2: {c, h_in, h_out, 0}: |s32 - c| < h_in proves t0 < s <= t1, |s32 - c| >= h_out proves the opposite
-//                 (s32 - c is what the kernel's three fused multiply-adds deliver; both widths carry their rounding);
-//   else per edge {t - g rounded down, t + g rounded up}.
-std::vector<float> build_thr32(const double *t, int n_bins, int n_edges) {
-    auto down = [](double v) { float f = (float)v; if ((double)f > v) f = nextafterf(f, -INFINITY); return f; };
-    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = nextafterf(f, INFINITY); return f; };
-    auto guard = [](double te) { return BAND32_GUARD_SQRT * std::sqrt(te) + 5e-7 * te + 1e-12; };
-    const int tw = thr32_width(n_edges);
-    std::vector<float> out((size_t)n_bins * tw, 0.f);
-    for (int k = 0; k < n_bins; ++k) {
-        const double *tk = t + (size_t)k * n_edges;
-        float *row = &out[(size_t)k * tw];
-        if (n_edges == 2) {
-            const double g0 = guard(tk[0]), g1 = guard(tk[1]);
-            const float c = (float)(0.5 * (tk[0] + tk[1]));
-            const double cd = (double)c;
-            // q = fma(dz, dz, fma(dy, dy, fma(dx, dx, -c))): three roundings of intermediate sums that stay below 2 c wherever
-            // a class is claimed (|q| < h_in <= c, or s inside the annulus: s32 <= t1 + g1 <= 2 c) -> 6 x 2^-24 x c = 3.6e-7 c
-            const double fold = 4e-7 * cd;
-            const double h_in = (std::min(cd - (tk[0] + g0), (tk[1] - g1) - cd) - fold) * (1.0 - 1e-6);
-            const double h_out = (std::max(cd - (tk[0] - g0), (tk[1] + g1) - cd) + fold) * (1.0 + 1e-6);
-            row[0] = c;
-            row[1] = h_in > 0.0 ? down(h_in) : 0.f;   // |q| < 0 never holds: nothing is certain
-            row[2] = up(std::max(h_out, 0.0));
-            row[3] = 0.f;
-        } else {
-            for (int e = 0; e < n_edges; ++e) {
-                const double g = guard(tk[e]);
-                row[2 * e] = down(tk[e] - g);
-                row[2 * e + 1] = up(tk[e] + g);
-            }
-        }
-    }
-    return out;
-}
-
-// Float32 table of k_count_band32_fine (see there), one row per redshift bin: {m, a, e0, e1}, then {t_j - g, t_j + g} per edge.
-// Empty when the edges of some bin do not follow the log-spaced model closely enough for float32 (the caller then counts
-// with the float64 band kernel): deviation above 0.05 fine bins, a guard wider than a fifth of a fine bin, t_0 = 0.
-std::vector<float> build_fine32(const double *t, int n_bins, int n_edges) {
-    auto down = [](double v) { float f = (float)v; if ((double)f > v) f = nextafterf(f, -INFINITY); return f; };
-    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = nextafterf(f, INFINITY); return f; };
-    auto guard = [](double te) { return BAND32_GUARD_SQRT * std::sqrt(te) + 5e-7 * te + 1e-12; };
-    const int tw = fine32_width(n_edges), nf = n_edges - 1;
-    std::vector<float> out((size_t)n_bins * tw, 0.f);
-    for (int k = 0; k < n_bins; ++k) {
-        const double *tk = t + (size_t)k * n_edges;
-        if (!(tk[0] > 1e-12) || !(tk[nf] > tk[0])) return {};
-        const double l0 = std::log2(tk[0]), l1 = std::log2(tk[nf]);
-        const double m = (double)nf / (l1 - l0), a = l0 * m;
-        double dev = 0.0;
-        for (int j = 0; j <= nf; ++j) {
-            if (j > 0 && !(tk[j] > tk[j - 1])) return {};
-            dev = std::max(dev, std::fabs((std::log2(tk[j]) - l0) * m - (double)j));
-        }
-        // error of the device's f: hardware log2 (1 ulp of a result below 64), float32 images of m and a, the fma
-        const double dev_f = m * (1e-5 + 6e-8 * 64.0) + 2.0 * 6e-8 * std::fabs(a) + 4e-5 + 6e-8 * (nf + 2);
-        const double per_s = 1.05 * m / std::log(2.0);  // d f / (d s / s), with room for the second order
-        // Admission: an s32 between the guard bands of edges j and j + 1 must round to one of the two, i.e. f may be off by
-        // less than half a bin: the model's deviation at the edges, the device's arithmetic, and the guard (widest,
-        // relative to t, at the first edge).
-        if (dev + dev_f + per_s * guard(tk[0]) / tk[0] > 0.45) return {};
-        float *row = &out[(size_t)k * tw];
-        row[0] = (float)m; row[1] = (float)a; row[2] = 0.f; row[3] = 0.f;
-        for (int j = 0; j <= nf; ++j) {
-            const double g = guard(tk[j]);
-            row[4 + 2 * j] = down(tk[j] - g);
-            row[5 + 2 * j] = up(tk[j] + g);
-        }
-    }
-    return out;
-}
 
 }  // namespace
 
-namespace yawhip_detail {  // what the other units call (declared in yawhip_internal.h)
+namespace yawhip_detail {  // the launch interface (declared in yawhip_count_kernels.h)
 
-CallKey::CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs_, const int32_t *jobs_,
-                 int32_t n_bins_, int32_t n_edges_, const double *t_, int32_t kernel_, bool want_counts_, bool want_sums_,
-                 bool for_work_, int32_t n_dev_)
-    : c1_uid(c1->uid), c2_uid(c2->uid), opt_gen(ctx->opt_gen), n_jobs(n_jobs_), n_bins(n_bins_), n_edges(n_edges_),
-      kernel(kernel_), n_dev(n_dev_), want_counts(want_counts_), want_sums(want_sums_), for_work(for_work_), jobs(jobs_), t(t_) {
-    // word by word: a job is one 64-bit word, a threshold another
-    auto mix = [this](uint64_t w) { hash = (hash ^ w) * 0x100000001b3ull; hash ^= hash >> 29; };
-    for (uint64_t w : {c1_uid, c2_uid, opt_gen, (uint64_t)(uint32_t)n_jobs << 32 | (uint32_t)n_bins,
-                       (uint64_t)(uint32_t)n_edges << 32 | (uint32_t)kernel,
-                       (uint64_t)(uint32_t)n_dev << 32 | (uint64_t)(want_counts | want_sums << 1 | for_work << 2)})
-        mix(w);
-    for (size_t j = 0; j < (size_t)n_jobs; ++j) {
-        uint64_t w;
-        memcpy(&w, jobs + 2 * j, sizeof w);
-        mix(w);
-    }
-    for (size_t i = 0; i < (size_t)n_bins * n_edges; ++i) {
-        uint64_t w;
-        memcpy(&w, t + i, sizeof w);
-        mix(w);
-    }
+int band_lds_fixed(int cap) { return cap == BCAP_MID ? BandLds<BCAP_MID>::FIXED : BandLds<BCAP>::FIXED; }
+size_t count_lds(bool weighted, bool priv, int n_edges) {
+    return 2 * STAGE * (sizeof(Obj) + sizeof(ObjF)) + (size_t)((n_edges + 1) & ~1) * sizeof(double) +
+           (size_t)(n_edges - 1) * (priv ? WG : 1) * (weighted ? 8 : 4);
+}
+size_t merged_stage_lds() { return 2 * MSTAGE * sizeof(ObjF); }
+size_t merged_lds(bool weighted, int bins, int n_edges) {
+    return merged_stage_lds() + (size_t)bins * n_edges * sizeof(double) + (size_t)bins * (n_edges - 1) * (weighted ? 8 * (MWG / 64) : 4) +
+           (size_t)bins * sizeof(float) + (size_t)MWG * sizeof(unsigned int) + 16;
 }
 
-// What a count call derives from its inputs on the HOST before anything is launched -- kernel choice, layouts, tile and stage
-// sizes, the job records / prefix / threshold tables of the item builder and the count kernel (uploaded once, into the plan's
-// own device buffer) -- kept for the next call with the same inputs (CallKey). A repeated call (the next step of a bench, the
-// same count of the next measurement, DR after DD with the same job list is ANOTHER plan) then marshals no tables at all; the
-// item builder and the count kernels run every call. Plans die with their catalogues and options.
-struct HostPlan {
-    CallKey key;
-    uint64_t stamp = 0;
-    // decisions
-    bool empty = false;   // nothing to count (no output values)
-    bool split = false;   // the job list has to be counted in pieces (SPLIT_JOBS)
-    int grid_div = 8;  // band kernels: workgroups = potential items / this
-    int R = 0, band_ne = 0, cap = 0, hp_shift = 0, lean_bins = 0, mode = 0, reach = 0, kernel = 0, nf = 0, n_orient = 0;
-    bool band = false, band32 = false, band_fine = false, filter = false, lean = false, merged = false, run_unweighted = false,
-         run_weighted = false, strip_items = false, swap = false, sweep = false, triple = false, uni = false, uniform_t = false,
-         weighted = false;
-    int64_t abytes = 0, cand = 0, n_items = 0, n_out = 0, n_pslots = 0, n_sjobs = 0, n_slots = 0, slab = 0, tile = 0;
-    double rwin_max = 0.0;
-    double cap_c = 1.0, cap_s = 0.0;  // cos / sin of sep_angle(rwin_max): the strip builder's trimmed windows (cap_s = 0: untrimmed)
-    size_t lds_band = 0, lds_merged = 0;
-    // device tables, in one allocation (d_in) made when the plan's table image is uploaded (Planner::tables): jobs / job records,
-    // prefix, thresholds, pre-filter thresholds, window widths, float32 classes, layout table, and -- weighted calls -- the chunk
-    // prefix of the slab reduction
-    DevPtr<unsigned char> d_in;
-    int32_t *d_jobs = nullptr;
-    int64_t *d_prefix = nullptr, *d_cprefix = nullptr;
-    double *d_t = nullptr, *d_rwin = nullptr;
-    float *d_dthr = nullptr, *d_ucap = nullptr, *d_thr32 = nullptr;
-    DevTab *d_tabs = nullptr;
-    int64_t n_chunks = 0;
-};
-
-// Forget the plans that involve catalogue `c` (nullptr: all of them).
-void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c) {
-    for (size_t i = 0; i < ctx->plans.size();) {
-        if (!c || ctx->plans[i]->key.c1_uid == c->uid || ctx->plans[i]->key.c2_uid == c->uid) {
-            delete ctx->plans[i];
-            ctx->plans[i] = ctx->plans.back();
-            ctx->plans.pop_back();
-        } else ++i;
-    }
+hipError_t launch_build_strips(const CountLaunch &L) {
+    hipLaunchKernelGGL(k_build_items_strips, dim3(L.build_grid), dim3(L.build_wg), 0, L.stream, L.d_tabs,
+                       reinterpret_cast<const JobRec *>(L.d_jobs), L.d_prefix, (int)L.n_build_jobs,
+                       L.triple ? 0 : L.reach, (int)L.tile, L.rwin_max, L.cap_c, L.cap_s, L.swap ? 1 : 0, L.triple ? 1 : 0,
+                       L.n_pot, L.d_items, L.d_ctr, L.d_kept, L.seg_cap);
+    return hipGetLastError();
+}
+hipError_t launch_build_windows(const CountLaunch &L) {
+    hipLaunchKernelGGL(k_build_items<true>, dim3(L.build_grid), dim3(L.build_wg), 0, L.stream, L.c1, L.c2,
+                       L.d_jobs, L.d_prefix, (int)L.n_build_jobs, L.n_bins, (int)L.tile,
+                       L.d_rwin, L.n_pot, L.d_items, L.d_ctr, L.d_kept);
+    return hipGetLastError();
+}
+hipError_t launch_build_whole(const CountLaunch &L) {
+    hipLaunchKernelGGL(k_build_items<false>, dim3(L.build_grid), dim3(L.build_wg), 0, L.stream, L.c1, L.c2,
+                       L.d_jobs, L.d_prefix, (int)L.n_build_jobs, L.n_bins, (int)L.tile, L.d_rwin, L.n_pot,
+                       L.d_items, L.d_ctr, nullptr);
+    return hipGetLastError();
+}
+hipError_t launch_item_work(const CountLaunch &L, int slots_per_job, unsigned long long *job_work) {
+    hipLaunchKernelGGL(k_item_work, dim3((unsigned)((L.n_pot + 255) / 256)), dim3(256), 0, L.stream, L.d_items,
+                       L.d_ctr, slots_per_job, job_work);
+    return hipGetLastError();
 }
 
-// The argument checks of a count call, made by every entry point before any device work: handles, sizes, bin counts of the
-// catalogues, thresholds and the patch ids of the jobs.
-int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-               int32_t n_bins, int32_t n_edges, const double *t) {
-    if (!ctx || !c1 || !c2) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: NULL handle");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && !jobs))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs: bad sizes (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
-                    n_jobs, n_bins, n_edges, MAX_EDGES);
-    if (c1->ctx != ctx || c2->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (c1->n_patches != c2->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", c1->n_patches, c2->n_patches);
-    if ((c1->nb != 1 && c1->nb != n_bins) || (c2->nb != 1 && c2->nb != n_bins))
-        return fail(YAWHIP_ERR_MISMATCH, "catalogue bin counts (%d, %d) do not fit n_bins=%d", c1->nb, c2->nb, n_bins);
-    for (int k = 0; k < n_bins; ++k)
-        for (int e = 0; e < n_edges; ++e) {
-            const double v = t[(size_t)k * n_edges + e];
-            if (!(v >= 0.0) || (e > 0 && !(v >= t[(size_t)k * n_edges + e - 1])))
-                return fail(YAWHIP_ERR_INVALID, "thresholds of bin %d are not ascending non-negative numbers", k);
-        }
-    for (int j = 0; j < n_jobs; ++j)
-        if (jobs[2 * j] < 0 || jobs[2 * j] >= c1->n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= c1->n_patches)
-            return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, c1->n_patches);
-    return YAWHIP_OK;
+// two-level ordered reduction of the weighted slabs, per output slot; prefix = first potential item of every output slot,
+// chunk prefix = first chunk of every output slot
+hipError_t launch_reduce_chunks(const CountLaunch &L) {
+    const int thr = 256;
+    hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((L.n_chunks * L.slab + thr - 1) / thr)), dim3(thr), 0, L.stream,
+                       L.d_partials, L.d_kept, L.d_prefix, L.d_cprefix,
+                       (int)L.n_oslots, (int)L.slab, L.d_chunk_sums, L.d_ctr);
+    return hipGetLastError();
 }
-
-// The band_cap option (yawhip_ctx_set_option): 0, or a stage capacity the band kernels are compiled for.
-int check_band_cap(int64_t value) {
-    if (value != 0 && value != BCAP && value != BCAP_MID && value != B32_CAP && value != B32_CAP_BIG)
-        return fail(YAWHIP_ERR_INVALID, "band_cap must be 0 (auto), 192 or 288 (float64 / fine-grid band kernels), %d or %d (float32 band kernel)",
-                    B32_CAP, B32_CAP_BIG);
-    return YAWHIP_OK;
+hipError_t launch_reduce_slots(const CountLaunch &L) {
+    const int thr = 256;
+    hipLaunchKernelGGL(k_reduce_slots, dim3((unsigned)((L.n_oslots * L.slab + thr - 1) / thr)), dim3(thr), 0, L.stream,
+                       L.d_chunk_sums, L.d_cprefix, (int)L.n_oslots, (int)L.slab, L.d_sums,
+                       L.n_chunks > 0 ? nullptr : L.d_ctr);
+    return hipGetLastError();
 }
-
 }  // namespace yawhip_detail
 
 namespace {
 
-// make_plan in steps, run in this order: each one fills its own fields of the plan; what a later step needs and the plan does
-// not keep stays in the planner.
-struct Planner {
-    yawhip_ctx *ctx;
-    const yawhip_catalog *c1, *c2;
-    int32_t n_jobs;
-    const int32_t *jobs;
-    int32_t n_bins, n_edges;
-    const double *t;
-    bool for_work;
-    HostPlan &P;
-    bool unit = false, auto_pick = false, half_ok = false;
-    int tile_idx = 0;  // tile table of the layouts (R = 1, 2, 4)
-    double layout_sep = 0.0;
-    std::vector<double> rwin;     // window half width per bin
-    std::vector<int32_t> orient;  // sort axis of the strip layouts of every job
-    const StripLayout *L1[3] = {nullptr, nullptr, nullptr}, *L2[3] = {nullptr, nullptr, nullptr};
-    const yawhip_catalog *c_lane = nullptr, *c_strm = nullptr;
-    const StripLayout *const *LL = nullptr, *const *LS = nullptr;  // lane side, streamed side
-    std::vector<float> fine32;
-    std::vector<int64_t> prefix;
-    std::vector<JobRec> job_recs;  // strip path, per job: what the builder needs of the two groups (JobRec)
-    void sides(bool swap) {
-        c_lane = swap ? c1 : c2; c_strm = swap ? c2 : c1;
-        LL = swap ? L1 : L2; LS = swap ? L2 : L1;
-    }
-    int kernel_and_sizes(int32_t kernel, bool want_counts, bool want_sums);
-    int layouts();
-    int tile_and_stage();
-    int histogram();
-    int items();
-    int tables();
-};
-
-// Step 1: the kernel, and the sizes of the output.
-int Planner::kernel_and_sizes(int32_t kernel, bool want_counts, bool want_sums) {
-    if (kernel == YAWHIP_KERNEL_AUTO) kernel = ctx->default_kernel;
-    auto_pick = kernel == YAWHIP_KERNEL_AUTO;  // BAND or SWEEP, whichever suits the layouts (decided below)
-    if (kernel == YAWHIP_KERNEL_AUTO) kernel = YAWHIP_KERNEL_BAND;
-    if (kernel < YAWHIP_KERNEL_EXACT || kernel > YAWHIP_KERNEL_BAND)
-        return fail(YAWHIP_ERR_INVALID, "unknown kernel id %d", kernel);
-    // the FP32 pre-filter assumes unit vectors; anything else is evaluated pair by pair in FP64
-    unit = c1->unit_norm && c2->unit_norm;
-    if (kernel == YAWHIP_KERNEL_FILTER && !unit) kernel = YAWHIP_KERNEL_EXACT;
-    // the window search compares the sorted coordinate of both sides: the axes must agree
-    if ((kernel == YAWHIP_KERNEL_SWEEP || kernel == YAWHIP_KERNEL_BAND) && c1->axis != c2->axis)
-        kernel = unit ? YAWHIP_KERNEL_FILTER : YAWHIP_KERNEL_EXACT;
-    // the band kernels park finished lanes on a sentinel at coordinate 4.0 and bound their searches by it: unit vectors only
-    if (kernel == YAWHIP_KERNEL_BAND && !unit) kernel = YAWHIP_KERNEL_EXACT;
-    P.kernel = kernel;
-    P.band = kernel == YAWHIP_KERNEL_BAND;
-    P.sweep = kernel == YAWHIP_KERNEL_SWEEP || P.band;
-    P.filter = unit && kernel != YAWHIP_KERNEL_EXACT;
-
-    P.nf = n_edges - 1;
-    P.n_slots = (int64_t)n_jobs * n_bins;
-    P.n_out = P.n_slots * P.nf;
-    P.weighted = (c1->w != nullptr) || (c2->w != nullptr);
-    P.run_weighted = P.weighted && want_sums;
-    P.run_unweighted = want_counts || (!P.weighted && want_sums);
-    if (P.n_out == 0) { P.empty = true; return YAWHIP_OK; }
-    if (P.n_slots > (1ll << 30)) return fail(YAWHIP_ERR_INVALID, "too many (job,bin) slots");
-    HIP_TRY(hipSetDevice(ctx->device));
-
-    // tile size: objects per lane. Larger tiles amortise the streamed-object read; small segments
-    // prefer small tiles so that padded lanes do not dominate.
-    // Lean path (k_count_merged): z-window culling + FP32 pre-filter + queued exact evaluation. Its merged
-    // form (one item for all bins, strip layouts on both sides) serves c1 binned x c2 unbinned, i.e. every
-    // count of a cross-correlation.
-    P.lean = P.sweep && (P.filter || P.band);  // single-wave workgroups on windowed items (k_count_merged / k_count_band)
-    return YAWHIP_OK;
+// The count kernels. Their variants are picked from the selectors of the launch record (pick; each list runs from the last
+// variant to the first: the compiler lays the kernels out in the reverse order, which keeps the code object as it was).
+// The variants named in these lists are the ones compiled.
+// Band kernels: grid from the number of POTENTIAL items (known on the host); the kernel reads the number the builder kept
+// from the device counter, workgroups beyond it exit, workgroups loop if more were kept than the grid holds.
+hipError_t launch_band32(const CountLaunch &L, bool wgt, int32_t *variant) {
+    const std::pair<int, int> stage{L.R, L.cap};
+    const std::pair<bool, bool> rows{L.merged, L.uni};
+    const dim3 band_grid(L.band_grid), wave(64);
+    return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+        return pick<Int<4>, Int<3>, Int<2>>(L.n_edges, [&](auto ne) {
+            return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
+                return pick<Stage<4, B32_CAP_BIG>, Stage<2, B32_CAP_BIG>, Stage<2, B32_CAP>, Stage<1, B32_CAP>>(stage, [&](auto s) {
+                    using S = decltype(s);
+                    using M = decltype(r);
+                    auto kern = L.one_chunk ? k_count_band32_one<S::R, S::CAP, w, ne, M::MERGED, M::UNI>
+                                            : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
+                    *variant = variant_code(L.one_chunk ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
+                    return launch(kern, band_grid, wave, L.lds, L.stream, L.d_tabs, L.d_items, L.n_bins, L.d_t,
+                                  L.d_thr32, L.d_rwin, L.d_ucap, L.flush_mask, L.swap ? 1 : 0, L.d_counts,
+                                  L.d_partials, L.d_ctr, L.seg_cap);
+                });
+            });
+        });
+    });
 }
-
-// Step 2: layout mode, orientations and strip layouts, the float32 band kernels, the sides, BAND or SWEEP.
-int Planner::layouts() {
-    const int nf = P.nf;
-    rwin.resize((size_t)n_bins);
-    double rwin_max = 0.0;  // widest window half width over the bins
-    for (int k = 0; k < n_bins; ++k) {
-        rwin[(size_t)k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-        rwin_max = std::max(rwin_max, rwin[(size_t)k]);
-    }
-    P.rwin_max = rwin_max;
-    // strip pairing pays while a run has few partner runs; for separations far beyond the grid spacing the
-    // ordinary (patch, bin) layout is used instead
-    // (grid_sep: the largest separation in the grid's own unit -- chord for a grid linear in v, angle for one in latitude)
-    const double grid_sep = c1->strip_grid ? sep_angle(rwin_max) : rwin_max;
-    const bool strips = P.lean && c1->has_strips && c2->has_strips && c1->strip_width == c2->strip_width &&
-                        c1->strip_grid == c2->strip_grid &&
-                        (c1->strip_width <= 0.0 || grid_sep / c1->strip_width <= (double)MAX_STRIP_REACH);
-    // mode 3: binned x binned on the per-segment strip layouts: ordinary (job, bin) items whose lane tiles and windows
-    // come from (patch, bin, strip) runs -- it pays when the lane side is dense: runs of at least a few lane tiles per
-    // (patch, bin, strip); estimated from the patch-level layout the upload built (B times as many runs)
-    bool seg_ok = false;
-    if (strips && c1->nb == n_bins && c2->nb == n_bins && n_bins > 1 && ctx->seg_strips) {
-        const StripLayout &base2 = c2->strips[c2->axis];
-        const int64_t seg_runs = base2.h_vbase[(size_t)base2.n_groups] * (int64_t)c2->nb;
-        seg_ok = c2->n / std::max<int64_t>(seg_runs, 1) >= ctx->seg_min_run;
-    }
-    bool uniform_t = true;  // every bin has the same threshold row (angular scales)
-    for (int k = 1; k < n_bins && uniform_t; ++k)
-        uniform_t = memcmp(t, t + (size_t)k * n_edges, sizeof(double) * n_edges) == 0;
-    P.uniform_t = uniform_t;
-    // One item for all bins needs a histogram of B x (E - 1) cells (and B edge rows when they differ) in LDS. Where that
-    // does not fit (hundreds of bins times dozens of separation-weight bins), the count falls back to ordinary
-    // (job, bin) items, whose histogram has E - 1 cells.
-    const size_t merged_lds = (size_t)n_bins * nf * (P.weighted ? 8 : 4) + (size_t)(uniform_t ? 1 : n_bins) * n_edges * sizeof(double) +
-                              (size_t)n_bins * sizeof(float) + BandLds<BCAP_MID>::FIXED + (BCAP_MID + 2) * 8 + 2 * MSTAGE * sizeof(ObjF) + 1024;
-    const bool merged_fits = merged_lds <= (size_t)ctx->lds_limit;
-    const int mode = P.mode = !strips ? 0 : (c1->nb > 1 && c2->nb == 1) ? (merged_fits ? 1 : 0) : (seg_ok ? 3 : 0);
-    // per-segment strip layouts keep the grid linear in v (build_strip_layout): their short runs make items of fixed cost, and
-    // the latitude grid's narrower strips away from v = 0 only add items there
-    layout_sep = mode == 3 ? rwin_max : grid_sep;
-    const bool merged = P.merged = mode == 1;                // one item covers all bins, output slot = job
-    const bool strip_items = P.strip_items = mode != 0;      // items come from strip runs (k_build_items_strips)
-    // Orientation of every job: the (u, v) projection that compresses the sphere least around its two patches, i.e.
-    // the one that drops the coordinate w in which the patches lie farthest from the origin. (Projected along an
-    // axis the patches are nearly perpendicular to, objects pile up in (u, v) -- density grows like 1 / |w| -- and
-    // the opposite hemisphere folds onto the same cells: every u-window then holds several times the partners.)
-    orient.assign((size_t)n_jobs, (int32_t)c1->axis);
-    if (strip_items) {
-        bool need[3] = {false, false, false};
-        for (int j = 0; j < n_jobs; ++j) {
-            if (ctx->auto_orient) {
-                const double *b1 = &c1->h_box[(size_t)6 * jobs[2 * j]], *b2 = &c2->h_box[(size_t)6 * jobs[2 * j + 1]];
-                double best = -1.0;
-                int wax = (c1->axis + 1) % 3;
-                for (int a = 0; a < 3; ++a) {
-                    const double m = (b1[a] <= b1[3 + a] ? 0.5 * (b1[a] + b1[3 + a]) : 0.0) +
-                                     (b2[a] <= b2[3 + a] ? 0.5 * (b2[a] + b2[3 + a]) : 0.0);
-                    if (std::fabs(m) > best) { best = std::fabs(m); wax = a; }
-                }
-                orient[(size_t)j] = (wax + 2) % 3;  // sort axis u whose dropped axis (u + 1) % 3 is wax
-            }
-            need[orient[(size_t)j]] = true;
-        }
-        for (int o = 0; o < 3; ++o) {
-            if (!need[o]) continue;
-            int rc = build_strip_layout(ctx, const_cast<yawhip_catalog *>(c1), o, mode == 3);
-            if (rc == YAWHIP_OK && c2 != c1) rc = build_strip_layout(ctx, const_cast<yawhip_catalog *>(c2), o, mode == 3);
-            if (rc != YAWHIP_OK) return rc;
-            L1[o] = mode == 3 ? &c1->seg[o] : &c1->strips[o];
-            L2[o] = mode == 3 ? &c2->seg[o] : &c2->strips[o];
-        }
-    }
-    // Float32 classification (k_count_band32) on strip layouts of unit vectors with up to four edges per bin. Where one
-    // side is binned (merged items) the roles are swapped against k_count_band: lane tiles come from the binned catalogue
-    // c1, the windows from the unbinned c2 (see the kernel).
-    const bool want32 = P.band && strip_items && unit && n_edges <= 4 && ctx->band_fp32 != 0 &&
-                        band32_lds(P.weighted, BCAP_MID, (merged ? n_bins : 1) * nf, merged && !uniform_t ? n_bins : 0, n_edges) <=
-                            (size_t)ctx->lds_limit;
-    // ... and the fine radial grids of separation weights (k_count_band32_fine), when their edges follow the log-spaced model
-    if (P.band && strip_items && unit && n_edges > 4 && ctx->band_fp32 != 0 &&
-        band32_fine_lds(P.weighted, BCAP_MID, (merged ? n_bins : 1) * nf, uniform_t ? 1 : n_bins, n_edges) <= (size_t)ctx->lds_limit)
-        fine32 = build_fine32(t, n_bins, n_edges);
-    const bool want_fine = !fine32.empty();
-    // (Binned x binned counts of two different catalogues keep c2 on the lanes whichever is sparser: with the 10M data on the
-    // lanes and the 100M randoms streamed, DR of config #4 has 570 k items instead of 1.28 M but walks 2.3 x the entries --
-    // neighbouring lane objects of a sparse run lie far apart, their common band is long -- 4.1 against 2.2 ms.)
-    P.swap = (want32 || want_fine) && merged;
-    sides(P.swap);
-    if (auto_pick && P.band && unit) {
-        // The band kernel decides every entry of a per-object band: unbeatable while a band is a handful of entries of which
-        // half are pairs (strip layouts). Without strips a band is the whole u-window of a segment, nearly all of it far away
-        // along v -- the FP32 pre-filter of the sweep kernel is made for that. Sparse streamed runs (a few dozen objects: an
-        // item is all fixed cost) went to the sweep kernel while the band kernel evaluated in float64; the float32 band kernel
-        // has the smaller fixed cost (measured: DD of config #4 0.61 against 0.83 ms, 1M x 1M / 64 patches 0.047 against 0.102,
-        // 3M x 0.3M 0.09 against 0.28; sweep stays ahead only where the two sides differ tenfold in density and the items are
-        // tiny: DR of config #4 2.09 against 2.23 ms, 0.3M x 3M 0.092 against 0.119) -- so only the float64 band kernel
-        // (band_fp32 = 0, more than four edges off the log grid) keeps the density rule.
-        bool use_sweep = mode == 0;
-        if (!use_sweep && !want32 && !want_fine) {
-            double obj_run = 0.0;  // of the densest built orientation
-            for (int o = 0; o < 3; ++o)
-                if (LS[o]) obj_run = std::max(obj_run, LS[o]->obj_run);
-            use_sweep = obj_run < (double)BAND_MIN_STREAM_RUN;
-        }
-        if (use_sweep) {
-            P.kernel = YAWHIP_KERNEL_SWEEP;
-            P.band = false;
-        }
-    }
-    P.band32 = want32 && P.band;
-    P.band_fine = want_fine && P.band;
-    if (!P.band32 && !P.band_fine && P.swap) {  // the sweep kernel streams c1 past lane tiles of c2
-        P.swap = false;
-        sides(false);
-    }
-    P.uni = merged || P.band_fine ? uniform_t : true;  // UNI of the band kernels (per-bin items of the others: one threshold row)
-    return YAWHIP_OK;
+hipError_t launch_band64(const CountLaunch &L, bool wgt, int32_t *variant) {
+    const std::pair<int, int> stage{L.R, L.cap};
+    const std::pair<bool, bool> rows{L.merged, L.uni};
+    const dim3 band_grid(L.band_grid), wave(64);
+    return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+        return pick<Int<0>, Int<4>, Int<3>, Int<2>>(L.band_ne, [&](auto ne) {
+            return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
+                return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
+                    using S = decltype(s);
+                    using M = decltype(r);
+                    *variant = variant_code(VF_BAND, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
+                    return launch(k_count_band<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, L.lds, L.stream,
+                                  L.d_tabs, L.d_items, L.n_bins, L.n_edges, L.d_t, L.d_rwin, L.flush_mask,
+                                  L.hp_shift, w ? 0 : L.batch_log2, L.d_counts, L.d_partials, L.d_ctr);
+                });
+            });
+        });
+    });
 }
-
-// Step 3: objects per lane, the expected window, merged triple runs, the stage capacity.
-int Planner::tile_and_stage() {
-    const bool band = P.band, strip_items = P.strip_items;
-    const int mode = P.mode;
-    int R = ctx->tile_r;
-    double est_window = 0.0;  // band kernel: expected entries of one window
-    if (R == 0) {
-        int64_t max_seg = 0;
-        if (strip_items) {  // lanes hold runs of a strip layout: their typical (mean) length decides
-            int64_t n_runs = 1;
-            for (int o = 0; o < 3; ++o)
-                if (LL[o]) n_runs = std::max(n_runs, LL[o]->h_vbase[(size_t)LL[o]->n_groups]);
-            max_seg = c_lane->n / std::max<int64_t>(n_runs, 1);
-            if (mode == 3) max_seg = std::max<int64_t>(max_seg, 4 * MWG * 2);  // at least two objects per lane: per-bin runs are
-                                                                                // sparse, the per-item cost outweighs the wider window
-        } else {
-            for (int j = 0; j < n_jobs; ++j)
-                for (int k = 0; k < (c2->nb == 1 ? 1 : n_bins); ++k) max_seg = std::max(max_seg, seg_len(c2, jobs[2 * j + 1], k));
-        }
-        const int wg = P.lean ? MWG : WG;
-        R = max_seg >= 8 * wg * 4 ? 4 : (max_seg >= 4 * wg * 2 ? 2 : 1);
-        if (strip_items && R > 2) R = 2;  // on strip runs two objects per lane beat four at every size measured (10M: 2.25 / 2.5 ms, 50M: 68 / 72 ms)
-        if (band && strip_items) {
-            // band kernel: two neighbouring objects per lane at every density measured once a stage holds the whole
-            // window (four per lane: 0.66 / 0.59 ms at the headline, 33 / 24 ms at 50M x 50M, 7.0 / 5.7 ms for RR of
-            // config #4). Expected window = the tile's own extent in streamed entries + one band of
-            // 2 r_win x (streamed objects of a run per unit of u).
-            R = 2;
-            auto per_u = [](const auto *c, const StripLayout *const *Ls) {
-                int64_t runs = 1;
-                for (int o = 0; o < 3; ++o)
-                    if (Ls[o]) runs = std::max(runs, Ls[o]->h_vbase[(size_t)Ls[o]->n_groups]);
-                double extent = 0.0;
-                int n_ext = 0;
-                for (int p = 0; p < c->n_patches; ++p) {
-                    const double *b = &c->h_box[(size_t)6 * p];
-                    double widest = 0.0;
-                    for (int a = 0; a < 3; ++a) widest = std::max(widest, b[3 + a] - b[a]);
-                    if (widest > 0.0) { extent += widest; ++n_ext; }
-                }
-                extent = n_ext ? extent / n_ext : 1.0;
-                return ((double)c->n / (double)runs) / std::max(extent, 1e-6);
-            };
-            const double d1 = per_u(c_strm, LS), d2 = per_u(c_lane, LL);
-            // binned x binned counts on per-(patch, bin) strip runs: runs are short (35 objects at 10 M, 350 at 100 M objects in
-            // 30 bins), bands a handful of entries -- ONE object per lane then evaluates its own band instead of the union of
-            // two (DD of config #4: 2.7e7 instead of 5.6e7 entries, 0.63 -> 0.41 ms; RR 3.74 -> 3.57), unless the streamed side
-            // is much the sparser one and items are all fixed cost (DR: 2.05e6 items instead of 1.28e6, 1.86 -> 2.25 ms)
-            if (mode == 3 && d1 >= 0.5 * d2) R = 1;
-            est_window = 64.0 * R * d1 / std::max(d2, 1e-12) + 2.0 * P.rwin_max * d1;
-        }
-    }
-    if (band && R == 0) R = 2;
-    // Merged triple runs on the streamed side: one window per item instead of three (k_merge_triples), when the partner
-    // strips are exactly c - 1, c, c + 1 (grid at least as wide as the largest separation) AND the merged window still goes
-    // through the stage in one piece: cut in pieces it costs more than three whole windows (100M x 100M: 22.0 against 14.9 ms,
-    // 50M x 50M with three scales 25.8 against 17.9). The fine-grid kernel has less room (a larger stage costs it residency:
-    // 51 fine bins 1.25 against 1.06 ms in a 512-entry stage), so it merges only windows that fit the stage it uses anyway
-    // (sparse streamed sides: DR of config #4 2.07 against 2.43). Weighted counts merge like unweighted ones since the kernel
-    // with one chunk per round exists: the count kernel takes the same 0.48 ms at the headline in the big stage, the builder
-    // searches one window per item instead of three (0.045 against 0.063 ms).
-    bool triple = false;
-    if ((P.band32 || P.band_fine) && strip_items && ctx->triple_runs && c_strm->n < (1ll << 31) && c1->strip_width > 0.0 &&
-        (int)std::floor(layout_sep / c1->strip_width + 1e-6) + 1 == 1) {
-        const double est3 = 3.0 * est_window;
-        triple = ctx->triple_runs == 2 ||
-                 (P.band32 ? est3 <= 0.88 * (B32_CAP_BIG - 4) : est3 <= 0.9 * BCAP_MID);
-        for (int o = 0; o < 3 && triple; ++o) {
-            if (!LS[o]) continue;
-            const int rc = build_triples(ctx, const_cast<yawhip_catalog *>(c_strm), o, mode == 3);
-            if (rc == YAWHIP_ERR_OOM) triple = false;  // no room for the copies: three windows per item as before
-            else if (rc != YAWHIP_OK) return rc;
-        }
-        if (triple) est_window = est3;
-    }
-    P.triple = triple;
-    if (g_trace.on) fprintf(stderr, "[yawhip trace] est_window %.1f (triple %d) R %d mode %d\n", est_window, (int)triple, R, mode);
-    // stage capacity of the band kernel: the smallest compiled one that holds a whole window (see BCAP_MID)
-    int cap = ctx->band_cap == BCAP || ctx->band_cap == BCAP_MID ? ctx->band_cap : 0;
-    if (band && cap == 0) cap = R >= 4 || est_window > 0.95 * BCAP ? BCAP_MID : BCAP;
-    if (band) {  // (R, stage) pairs that are compiled (the Stage lists of count_enqueue): the plan names one of them
-        if (R == 1) cap = BCAP;
-        if (R == 4 && cap == BCAP) cap = BCAP_MID;
-    }
-    int cap32 = ctx->band_cap == B32_CAP || ctx->band_cap == B32_CAP_BIG ? ctx->band_cap
-                                                                         : (est_window > 0.75 * (B32_CAP - 4) ? B32_CAP_BIG : B32_CAP);
-    // (0.75: window lengths scatter around the estimate, and a window cut in two costs more than a larger stage -- 50M x 50M
-    // with windows of ~265 entries: 21.0 ms in the 320-entry stage, 18.3 ms in a 448-entry one)
-    if (R == 1) cap32 = B32_CAP;  // (compiled pairs, as above)
-    if (R >= 4) cap32 = B32_CAP_BIG;
-    if (P.band32) cap = cap32;  // (the fine-grid kernel still stages window by window, with the capacities of k_count_band)
-    P.R = R;
-    tile_idx = R == 1 ? 0 : (R == 2 ? 1 : 2);
-    P.cap = cap;
-    P.tile = (int64_t)(P.lean ? MWG : WG) * R;
-    P.lean_bins = P.merged ? n_bins : 1;
-    P.lds_merged = 2 * MSTAGE * sizeof(ObjF) + (size_t)P.lean_bins * n_edges * sizeof(double) +
-                   (size_t)P.lean_bins * P.nf * (P.weighted ? 8 * (MWG / 64) : 4) + (size_t)P.lean_bins * sizeof(float) +
-                   (size_t)MWG * sizeof(unsigned int) + 16;
-    return YAWHIP_OK;
+hipError_t launch_fine(const CountLaunch &L, bool wgt, int32_t *variant) {
+    const std::pair<int, int> stage{L.R, L.cap};
+    const std::pair<bool, bool> rows{L.merged, L.uni};
+    const dim3 band_grid(L.band_grid), wave(64);
+    return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+        return pick<Rows<true, false>, Rows<true, true>, Rows<false, false>, Rows<false, true>>(rows, [&](auto r) {
+            return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
+                using S = decltype(s);
+                using M = decltype(r);
+                *variant = variant_code(VF_BAND32_FINE, S::R, S::CAP, w, 0, M::MERGED, M::UNI);
+                return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, L.lds, L.stream,
+                              L.d_tabs, L.d_items, L.n_bins, L.n_edges, L.d_t, L.d_thr32, L.d_rwin,
+                              L.d_ucap, L.flush_mask, L.swap ? 1 : 0, L.d_counts, L.d_partials, L.d_ctr, L.seg_cap);
+            });
+        });
+    });
 }
-
-// Step 4: copies of the band kernel's LDS histogram, its compile-time edge count, its LDS.
-int Planner::histogram() {
-    const int lean_bins = P.lean_bins, nf = P.nf;
-    const bool merged = P.merged, uniform_t = P.uniform_t;
-    // Copies of the LDS histogram, lanes spread over them by lane id: same-address atomics of one instruction are
-    // serialised. Four copies when there are few slots and the bins of neighbouring entries are unrelated (headline:
-    // 0.535 ms with four, 0.565 with eight -- the flush grows with the copies). When the histogram has only the fine bins
-    // of ONE redshift bin (per-bin items: every hit of the wave lands in 1-3 cells), or when redshift follows position
-    // (same_bin: neighbours of the layout's order sharing their bin; clustered survey: 108 -> 62 ms weighted cross count,
-    // 31 -> 18 ms autocorrelation count), more copies pay: up to 16 within 2 KB.
-    int hp_shift = lean_bins * nf <= 32 ? 2 : 0;
-    if (P.band) {
-        double coherence = merged ? 0.0 : 1.0;
-        if (merged)
-            for (int o = 0; o < 3; ++o)
-                if (L1[o]) coherence = std::max(coherence, L1[o]->same_bin);
-        if (coherence > 0.25) {
-            const int cell = P.weighted ? 8 : 4;
-            while (hp_shift < (merged ? 3 : 4) && ((size_t)lean_bins * nf * cell << (hp_shift + 1)) <= 2048) ++hp_shift;
-        }
+// The lean kernel (k_count_merged / _occ8) and k_count, one workgroup per item: grids in pieces of at most 2^32 - 1
+// work-items per launch dimension.
+template <typename F>
+hipError_t in_pieces(int64_t n_items, int wg, F &&launch_at) {
+    const int64_t max_grid = (1ll << 31) / wg;
+    for (int64_t base = 0; base < n_items; base += max_grid) {
+        const hipError_t e = launch_at(dim3((unsigned)std::min(max_grid, n_items - base)), base);
+        if (e != hipSuccess) return e;
     }
-    if (ctx->hist_copies_log2 >= 0) hp_shift = ctx->hist_copies_log2;
-    P.band_ne = (!merged || uniform_t) && n_edges <= 4 ? n_edges : (nf == 1 ? 2 : 0);  // compile-time edge count of k_count_band
-    const bool band_thr = !(P.band_ne >= 2 && (!merged || uniform_t));
-    const size_t LDS_FIXED = (size_t)band_lds_fixed(P.cap);
-    auto band_lds_for = [&](int shift) {
-        return band_lds_dynamic(P.weighted, band_thr, lean_bins, n_edges, 1 << shift, P.cap, merged && !uniform_t ? lean_bins : 1);
-    };
-    while (P.band && hp_shift > 0 && band_lds_for(hp_shift) + LDS_FIXED > (size_t)ctx->lds_limit) --hp_shift;  // copies are a tunable, not a need
-    P.hp_shift = hp_shift;
-    P.lds_band = band_lds_for(hp_shift);
-    if (P.lean && (P.band ? P.lds_band + LDS_FIXED : P.lds_merged) > (size_t)ctx->lds_limit)
-        return fail(YAWHIP_ERR_INVALID, "too many bins x edges for the LDS histogram (%zu bytes)", P.band ? P.lds_band + LDS_FIXED : P.lds_merged);
-    return YAWHIP_OK;
+    return hipSuccess;
 }
-
-// Step 5: the item table -- job records, prefix, candidates and bytes, half bands -- and whether the job list has to be split.
-int Planner::items() {
-    const bool strip_items = P.strip_items;
-    const int mode = P.mode;
-    // item table: prefix[slot] = first item of the slot; items of a slot are its lane tiles.
-    // standard path: slot = (job, bin); merged path: slot = job (one item covers all bins).
-    // strip path: slot = job; its potential items = (lane tiles of patch q) x (groups of up to MAX_WIN of the 2*reach+1
-    // neighbouring strips), enumerated by the builder kernel from the catalogues' run tables.
-    int64_t n_items = 0, cand = 0, abytes = 0;
-    const int obj_bytes1 = c1->w ? 32 : 24, obj_bytes2 = c2->w ? 32 : 24;
-    // strip paths: the builder's job table. Modes 1/2: the jobs themselves (groups = patches); mode 3: one pseudo job
-    // per (job, bin) between the segments (p, k) and (q, k) (groups = segments), numbered like the output slots.
-    P.n_sjobs = mode == 3 ? P.n_slots : (int64_t)n_jobs;
-    // Half bands: a catalogue counted against ITSELF meets every unordered pair of a diagonal job twice -- a as lane object with b
-    // in its window, b as lane object with a in its. On merged triple runs with one object per lane the lane walks only the
-    // entries BEHIND its own place in the triple of its strip (one total order of objects in all triples, k_merge_triples): every
-    // pair is met once and counts twice (an exact doubling, also of weighted sums). Half the walk of DD / RR of an autocorrelation.
-    half_ok = P.band32 && P.triple && P.R == 1 && c1 == c2 && !P.swap && ctx->half_bands != 0 && !for_work;
-    if (strip_items) {
-        const double width = c1->strip_width;
-        // |dv| <= rwin_max (|d latitude| <= sep_angle(rwin_max))  ->  grid indices differ by at most floor(layout_sep / width) + 1
-        const int reach = P.reach = width > 0.0 ? (int)std::floor(layout_sep / width + 1e-6) + 1 : 0;
-        std::vector<int32_t> sjobs((size_t)2 * P.n_sjobs);
-        for (int j = 0; j < n_jobs; ++j)
-            for (int k = 0; k < (mode == 3 ? n_bins : 1); ++k) {
-                const int64_t sj = mode == 3 ? (int64_t)j * n_bins + k : j;
-                sjobs[(size_t)2 * sj] = mode == 3 ? jobs[2 * j] * n_bins + k : jobs[2 * j];
-                sjobs[(size_t)2 * sj + 1] = mode == 3 ? jobs[2 * j + 1] * n_bins + k : jobs[2 * j + 1];
-            }
-        prefix.resize((size_t)P.n_sjobs + 1);
-        job_recs.assign((size_t)P.n_sjobs, JobRec{0, 0, 0, 0, 0});
-        for (int64_t j = 0; j < P.n_sjobs; ++j) {
-            const int p = sjobs[(size_t)2 * j + (P.swap ? 1 : 0)], q = sjobs[(size_t)2 * j + (P.swap ? 0 : 1)];  // streamed, lane side
-            const int o = orient[(size_t)(mode == 3 ? j / n_bins : j)];
-            const StripLayout &sl1 = *LS[o], &sl2 = *LL[o];
-            const std::vector<int64_t> &tiles = sl2.h_tiles[tile_idx];
-            JobRec &jr = job_recs[(size_t)j];
-            jr.o = o | (half_ok && p == q ? 4 : 0);
-            prefix[(size_t)j] = n_items;
-            // strips of q whose grid index lies within `reach` of the strips group p occupies
-            const int64_t cnt1 = sl1.h_vbase[(size_t)p + 1] - sl1.h_vbase[(size_t)p], lo1 = sl1.h_slo[(size_t)p];
-            const int64_t cnt2 = sl2.h_vbase[(size_t)q + 1] - sl2.h_vbase[(size_t)q], lo2 = sl2.h_slo[(size_t)q];
-            const int64_t s_lo = std::max<int64_t>(lo1 - reach - lo2, 0), s_hi = std::min<int64_t>(lo1 + cnt1 - 1 + reach - lo2, cnt2 - 1);
-            if (cnt1 > 0 && s_hi >= s_lo) {
-                const int64_t r0 = sl2.h_vbase[(size_t)q] + s_lo;
-                jr.t_lo = tiles[(size_t)r0];
-                jr.k_off = lo2 - sl2.h_vbase[(size_t)q] - lo1;  // strip index of lane run r2 on the common grid, relative to group p
-                jr.vbase1 = sl1.h_vbase[(size_t)p];
-                jr.n_strips1 = (int32_t)cnt1;
-                if (P.triple) {  // triple runs of group p: strips [lo1 - 1, lo1 + cnt1], the first one at vbase + 2 p
-                    jr.k_off += 1;
-                    jr.vbase1 += 2 * (int64_t)p;
-                    jr.n_strips1 += 2;
-                }
-                n_items += (tiles[(size_t)(r0 + s_hi - s_lo + 1)] - tiles[(size_t)r0]) * ((2 * reach + 1 + MAX_WIN - 1) / MAX_WIN);
-            }
-        }
-        prefix[(size_t)P.n_sjobs] = n_items;
-    } else {
-        prefix.resize((size_t)P.n_slots + 1);
-    }
-    P.n_pslots = P.merged ? (int64_t)n_jobs : P.n_slots;
-    auto patch_total = [](const yawhip_catalog *c, int patch) {  // objects of a patch over all its bins
-        return c->h_off[(size_t)(patch + 1) * c->nb] - c->h_off[(size_t)patch * c->nb];
-    };
-    for (int j = 0; j < n_jobs; ++j) {
-        const int p = jobs[2 * j], q = jobs[2 * j + 1];
-        if (strip_items && (c1->nb == 1 || c2->nb == 1)) {
-            // an unbinned side is one segment used for every bin: sum_k N1(p,k) N2(q,k) factorises
-            cand += c1->nb == 1 ? patch_total(c1, p) * patch_total(c2, q) * (c2->nb == 1 ? n_bins : 1)
-                                : patch_total(c1, p) * patch_total(c2, q);
-        } else {
-            for (int k = 0; k < n_bins; ++k) {
-                const int64_t n1 = seg_len(c1, p, k), n2 = seg_len(c2, q, k);
-                if (!strip_items) prefix[(size_t)j * n_bins + k] = n_items;
-                if (n1 > 0 && n2 > 0) {
-                    if (!strip_items) n_items += (n2 + P.tile - 1) / P.tile;
-                    cand += n1 * n2;
-                }
-            }
-        }
-        // algorithmic bytes of a job = every object of the two patches once (Bobj * (N1 + N2))
-        abytes += patch_total(c1, p) * obj_bytes1 + patch_total(c2, q) * obj_bytes2;
-    }
-    if (!strip_items) prefix[(size_t)P.n_pslots] = n_items;
-    P.n_items = n_items;
-    P.cand = cand;
-    P.abytes = abytes;
-    P.slab = P.merged ? (int64_t)n_bins * P.nf : P.nf;  // float64 values per item of the weighted slab
-    // A weighted call keeps one slab of partial sums per potential item; long job lists of big catalogues would need
-    // tens of GB (50M x 50M, three scales: 40 GB). Above the budget -- and when the items no longer fit 31 bits -- the
-    // caller cuts the job list in two and counts the halves one after the other (rows of the result are independent).
-    P.split = n_jobs > 1 && !for_work &&
-              ((P.run_weighted && n_items * P.slab * (int64_t)sizeof(double) > ctx->slab_budget) || n_items >= (1ll << 31));
-    return YAWHIP_OK;
+hipError_t launch_lean(const CountLaunch &L, bool wgt, int32_t *variant) {
+    return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+        return pick<Bool<false>, Bool<true>>(L.nf1, [&](auto nf1) {
+            return pick<Bool<false>, Bool<true>>(L.merged, [&](auto m) {
+                return pick<Int<4>, Int<2>, Int<1>>(L.R, [&](auto r) {
+                    *variant = variant_code(r <= 2 ? VF_MERGED_OCC8 : VF_MERGED,  // (the choice of pick_count_merged)
+                                            r, 0, w, 0, m, false, false, false, nf1);
+                    return in_pieces(L.n_items, MWG, [&](dim3 g, int64_t base) {
+                        return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), L.lds, L.stream, L.d_tabs,
+                                      L.d_items, L.n_bins, L.n_edges, L.d_t, L.d_dthr, L.d_rwin, base,
+                                      L.d_counts, L.d_partials, L.d_ctr);
+                    });
+                });
+            });
+        });
+    });
 }
-
-// Step 6: the per-bin tables and the layout table; all tables packed into one image, uploaded once; the grid divisor.
-int Planner::tables() {
-    std::vector<float> dthr((size_t)3 * n_bins);  // per bin: pre-filter threshold, certain-band lower / upper bound
-    auto round_down = [](double v) { float f = (float)v; if ((double)f > v) f = nextafterf(f, -4.0f); return f; };
-    for (int k = 0; k < n_bins; ++k) {
-        const double thi = t[(size_t)k * n_edges + n_edges - 1];
-        float thr32 = ctx->debug_no_hits ? 2.0f : round_down(1.0 - 0.5 * thi - FILTER_GUARD);
-        dthr[(size_t)3 * k] = thr32;
-        dthr[(size_t)3 * k + 1] = 0.f;  // reserved
-        dthr[(size_t)3 * k + 2] = 0.f;
-    }
-    if (P.merged) rwin[0] = P.rwin_max;  // one window for all bins of the merged run
-    // band_trim: {cos, sin} of the largest separation angle per row of rwin, float32 for the band kernels ({1, 0}: untrimmed).
-    // The caps assume |a|^2 within UNIT_NORM_TOL of 1 (sep_angle).
-    const bool trim = ctx->band_trim && c1->unit_norm && c2->unit_norm;
-    std::vector<float> ucap((size_t)2 * n_bins);
-    for (int k = 0; k < n_bins; ++k) {
-        const double th = sep_angle(rwin[(size_t)k]);
-        ucap[(size_t)2 * k] = trim ? (float)std::cos(th) : 1.0f;
-        ucap[(size_t)2 * k + 1] = trim ? (float)std::sin(th) : 0.0f;
-    }
-    if (trim) {
-        P.cap_c = std::cos(sep_angle(P.rwin_max));
-        P.cap_s = std::sin(sep_angle(P.rwin_max));
-    }
-    // layout table of the call: [o] = c1, [3 + o] = c2 for orientation o (plain layouts: entries 0 and 3)
-    DevTab h_tabs[6];
-    memset(h_tabs, 0, sizeof h_tabs);
-    if (P.strip_items) {
-        for (int o = 0; o < 3; ++o) {
-            if (!L1[o]) continue;
-            const StripLayout &a = *L1[o], &b = *L2[o];
-            h_tabs[o] = make_tab(a.x, a.y, a.z, a.w, P.merged ? a.k : nullptr, a.off, a.d_vbase, a.d_slo, a.d_tiles[tile_idx],
-                                 a.d_tile_rec[tile_idx], a.d_grid, o, a.q, a.q_stride);
-            h_tabs[3 + o] = make_tab(b.x, b.y, b.z, b.w, nullptr, b.off, b.d_vbase, b.d_slo, b.d_tiles[tile_idx],
-                                     b.d_tile_rec[tile_idx], b.d_grid, o, b.q, b.q_stride);
-            if (P.triple) {
-                // the streamed side as merged triple runs: images, weights, offsets and grid index of the triples; the float64
-                // columns stay the layout's own (reached through idx by the exact re-evaluation)
-                const StripLayout &st = P.swap ? b : a;
-                DevTab &tb = h_tabs[P.swap ? 3 + o : o];
-                tb = make_tab(st.x, st.y, st.z, st.w3, nullptr, st.off3, st.d_vbase, st.d_slo, st.d_tiles[tile_idx],
-                              st.d_tile_rec[tile_idx], st.d_grid3, o, st.q3, st.q3_stride, st.idx3);
-                if (half_ok) h_tabs[3 + o].pos3 = (gi32p)(const int32_t *)b.pos3;  // (c1 == c2: the lane side's layout is the streamed one)
-            }
-        }
-    } else {
-        h_tabs[0] = make_tab(c1->x, c1->y, c1->z, c1->w, nullptr, c1->off, nullptr, nullptr, nullptr, nullptr, nullptr, c1->axis);
-        h_tabs[3] = make_tab(c2->x, c2->y, c2->z, c2->w, nullptr, c2->off, nullptr, nullptr, nullptr, nullptr, nullptr, c2->axis);
-    }
-    // the tables of the call, packed into the pinned staging buffer and sent with one copy
-    static_assert(sizeof(JobRec) == 8 * sizeof(int32_t), "JobRec is 32 bytes");
-    const std::vector<float> thr32 = P.band32 ? build_thr32(t, n_bins, n_edges) : (P.band_fine ? fine32 : std::vector<float>());
-    // weighted calls: the two-level ordered reduction of the slabs needs the first chunk of every output slot
-    std::vector<int64_t> cprefix;
-    if (P.run_weighted) {
-        cprefix.assign((size_t)P.n_pslots + 1, 0);
-        for (int64_t sl = 0; sl < P.n_pslots; ++sl)
-            cprefix[(size_t)sl + 1] = cprefix[(size_t)sl] + (prefix[(size_t)sl + 1] - prefix[(size_t)sl] + REDUCE_CHUNK - 1) / REDUCE_CHUNK;
-    }
-    P.n_chunks = cprefix.empty() ? 0 : cprefix.back();
-    const void *src[9] = {P.strip_items ? (const void *)job_recs.data() : (const void *)jobs, prefix.data(), t, dthr.data(),
-                          rwin.data(), ucap.data(), thr32.data(), h_tabs, cprefix.data()};
-    const size_t bytes[9] = {P.strip_items ? sizeof(JobRec) * (size_t)P.n_sjobs : sizeof(int32_t) * 2 * (size_t)n_jobs,
-                             sizeof(int64_t) * ((size_t)P.n_pslots + 1), sizeof(double) * n_bins * n_edges, sizeof(float) * 3 * n_bins,
-                             sizeof(double) * n_bins, sizeof(float) * 2 * n_bins, sizeof(float) * thr32.size(), sizeof h_tabs,
-                             sizeof(int64_t) * cprefix.size()};
-    size_t off[9], off_in = 0;
-    for (int i = 0; i < 9; ++i) { off[i] = off_in; off_in = align16(off_in + bytes[i]); }
-    std::vector<unsigned char> image(off_in, 0);
-    for (int i = 0; i < 9; ++i)
-        if (bytes[i]) memcpy(image.data() + off[i], src[i], bytes[i]);
-    HIP_TRY(P.d_in.alloc(std::max<size_t>(off_in, 16)));
-    HIP_TRY(hipMemcpy(P.d_in, image.data(), off_in, hipMemcpyHostToDevice));  // once per plan
-    P.d_jobs = reinterpret_cast<int32_t *>(P.d_in + off[0]);
-    P.d_prefix = reinterpret_cast<int64_t *>(P.d_in + off[1]);
-    P.d_t = reinterpret_cast<double *>(P.d_in + off[2]);
-    P.d_dthr = reinterpret_cast<float *>(P.d_in + off[3]);
-    P.d_rwin = reinterpret_cast<double *>(P.d_in + off[4]);
-    P.d_ucap = reinterpret_cast<float *>(P.d_in + off[5]);
-    P.d_thr32 = reinterpret_cast<float *>(P.d_in + off[6]);
-    P.d_tabs = reinterpret_cast<DevTab *>(P.d_in + off[7]);
-    P.d_cprefix = reinterpret_cast<int64_t *>(P.d_in + off[8]);
-    P.n_orient = (L1[0] ? 1 : 0) + (L1[1] ? 1 : 0) + (L1[2] ? 1 : 0);
-    // Workgroups of the band kernels = potential items / grid_div (the kernel loops over the rest). Uniform catalogues, whose
-    // items are alike, run best with few, longer-lived workgroups: / 8, / 16 for the per-bin items of binned x binned counts, of
-    // which the builder keeps a third (headline 4 / 8 / 16 -> 0.277 / 0.275 / 0.292 ms; config #4 DR 1.59 / 1.53 / 1.48, RR 3.08 /
-    // 3.04 / 3.02). On CLUSTERED catalogues items differ a hundredfold and the hardware's dispatch of many short workgroups is the
-    // load balancer: / 4 (clustered survey, 3M x 4M: cross count 40.1 against 43.3 ms with / 8, autocorrelation count 7.1
-    // against 8.2 with / 16). Clustered = the run the typical OBJECT sits in (sum len^2 / sum len) is more than twice the mean run.
-    double skew = 1.0;
-    for (const StripLayout *const *LX : {L1, L2})
-        for (int o = 0; o < 3; ++o)
-            if (LX[o] && LX[o]->built) {
-                const yawhip_catalog *cx = LX == L1 ? c1 : c2;
-                const double runs = (double)std::max<int64_t>(LX[o]->h_vbase[(size_t)LX[o]->n_groups], 1);
-                skew = std::max(skew, LX[o]->obj_run / std::max((double)cx->n / runs, 1.0));
-            }
-    P.grid_div = ctx->band_grid_div > 0 ? ctx->band_grid_div : (skew > 2.0 ? 4 : (P.mode == 3 ? 16 : 8));
-    if (g_trace.on) fprintf(stderr, "[yawhip trace] run skew %.2f -> grid / %d\n", skew, P.grid_div);
-    return YAWHIP_OK;
-}
-
-// The host half of a count call (its arguments passed check_call): every decision, the tables -- into a plan (see HostPlan).
-// for_work: the plan of a cost estimate (count_enqueue's job_work).
-int make_plan(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-              int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
-              HostPlan &P) {
-    Planner pl{ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, for_work, P};
-    int rc = pl.kernel_and_sizes(kernel, want_counts, want_sums);
-    if (rc == YAWHIP_OK && !P.empty) rc = pl.layouts();
-    if (rc == YAWHIP_OK && !P.empty) rc = pl.tile_and_stage();
-    if (rc == YAWHIP_OK && !P.empty) rc = pl.histogram();
-    if (rc == YAWHIP_OK && !P.empty) rc = pl.items();
-    if (rc == YAWHIP_OK && !P.empty && !P.split) rc = pl.tables();
-    if (rc == YAWHIP_OK) g_trace.mark("planned");
-    return rc;
+hipError_t launch_plain(const CountLaunch &L, bool wgt, int32_t *variant) {
+    return pick<Bool<true>, Bool<false>>(wgt, [&](auto w) {
+        return pick<Bool<false>, Bool<true>>(L.priv, [&](auto pv) {
+            return pick<Bool<false>, Bool<true>>(L.filter, [&](auto f) {
+                return pick<Int<4>, Int<2>, Int<1>>(L.R, [&](auto r) {
+                    *variant = variant_code(VF_COUNT, r, 0, w, 0, false, false, pv, f);
+                    return in_pieces(L.n_items, WG, [&](dim3 g, int64_t base) {
+                        return launch(k_count<r, w, pv, f>, g, dim3(WG), L.lds, L.stream, L.c1, L.c2,
+                                      L.d_items, L.n_bins, L.n_edges, L.d_t, L.d_dthr, base, L.d_counts,
+                                      L.d_partials, L.d_ctr);
+                    });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace
 
 namespace yawhip_detail {
 
-// First half of yawhip_count_pairs on ONE device: everything up to and including the copy of the results into the
-// context's pinned buffer is put on the context's stream; nothing waits for the device (SWEEP's grid sizing aside).
-// The host side of it (make_plan) is done once per distinct set of inputs and looked up afterwards.
-// job_work != nullptr: cost estimate only -- the item builder runs, evaluated pairs per job are returned, no counting.
-int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
-                  const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                  bool want_counts, bool want_sums, int64_t *job_work, CallState &cs, bool fetch_results) {
-    cs = CallState{};
-    cs.wall0 = std::chrono::steady_clock::now();
-    g_trace.mark("enqueue");
-    cs.want_counts = want_counts;
-    cs.want_sums = want_sums;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CallKey key(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, want_counts, want_sums, job_work != nullptr);
-    HostPlan *plan = nullptr;
-    for (HostPlan *cand_plan : ctx->plans)
-        if (cand_plan->key == key) {
-            plan = cand_plan;
-            break;
-        }
-    if (!plan) {
-        std::unique_ptr<HostPlan> fresh(new (std::nothrow) HostPlan());
-        if (!fresh) return fail(YAWHIP_ERR_OOM, "host allocation failed");
-        const int rc = make_plan(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, want_counts, want_sums, job_work != nullptr, *fresh);
-        if (rc != YAWHIP_OK) return rc;
-        key.keep();
-        fresh->key = std::move(key);
-        if (ctx->plans.size() >= MAX_PLANS) {  // evict the least recently used one (nothing of it is in flight: calls are blocking,
-            size_t old = 0;                    // and a batch is never longer than the plans kept)
-            for (size_t i = 1; i < ctx->plans.size(); ++i)
-                if (ctx->plans[i]->stamp < ctx->plans[old]->stamp) old = i;
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            delete ctx->plans[old];
-            ctx->plans[old] = ctx->plans.back();
-            ctx->plans.pop_back();
-        }
-        plan = fresh.release();
-        ctx->plans.push_back(plan);
+hipError_t launch_count(const CountLaunch &L, bool weighted, int32_t *variant) {
+    switch (L.family) {
+    case CountFamily::BAND32: return launch_band32(L, weighted, variant);
+    case CountFamily::BAND32_FINE: return launch_fine(L, weighted, variant);
+    case CountFamily::BAND64: return launch_band64(L, weighted, variant);
+    case CountFamily::LEAN: return launch_lean(L, weighted, variant);
+    case CountFamily::PLAIN: return launch_plain(L, weighted, variant);
     }
-    plan->stamp = ++ctx->plan_clock;
-    const HostPlan &P = *plan;
-    cs.n_out = P.n_out;
-    if (P.empty) return YAWHIP_OK;
-    if (P.split) return SPLIT_JOBS;
-    if (P.run_weighted) HIP_TRY(reserve_call(ctx->d_partials, (size_t)std::max<int64_t>(P.n_items, 1) * P.slab));
-    g_trace.mark("plan");
-    // results: [counters][counts][sums] in one device buffer; counters and counts are zero when no call of the slot is in
-    // flight (CallBufs::dirty; sums are always fully written), and k_call_tail brings back what was asked for
-    const size_t o_ctr = 0, o_counts = align16(N_CTR * sizeof(unsigned long long)),
-                 o_sums = o_counts + align16((size_t)P.n_out * sizeof(unsigned long long));
-    const size_t out_bytes = o_sums + align16((size_t)P.n_out * sizeof(double));
-    const unsigned char *const block_was = ctx->out.d;
-    HIP_TRY(ctx->out.reserve(out_bytes));
-    if (ctx->out.d != block_was) {  // a new block: nothing is known of it, and no call has signed it off
-        ctx->dirty = true;
-        reinterpret_cast<unsigned long long *>(ctx->out.h)[CTR_DONE] = 0;
-    }
-    ctx->d_ctr = reinterpret_cast<unsigned long long *>(ctx->out.d + o_ctr);
-    ctx->d_counts = reinterpret_cast<unsigned long long *>(ctx->out.d + o_counts);
-    ctx->d_sums = reinterpret_cast<double *>(ctx->out.d + o_sums);
-    // (no items: no kernel writes the sums either)
-    const size_t zero_needed = P.n_items > 0 ? o_sums : out_bytes;
-    if (ctx->dirty) ctx->zero_upto = 0;
-    if (ctx->zero_upto < zero_needed) {
-        HIP_TRY(hipMemsetAsync(ctx->out.d + ctx->zero_upto, 0, zero_needed - ctx->zero_upto, ctx->stream));
-        ctx->zero_upto = zero_needed;
-    }
-    ctx->dirty = true;  // until count_finish has seen this call's tail complete
-    cs.seq = ++ctx->seq;
-    cs.stamps = P.n_items > 0;  // a builder runs
-
-    int launches = 0;
-    const int64_t n_pot = P.n_items;
-    int64_t n_items = P.n_items;  // the count grid: all potential items, or what the builder kept (SWEEP)
-    unsigned long long seg_cap = 0;  // > 0: the item list is kept in ITEM_SEGS segments of this many records
-    g_trace.mark("memset");
-    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    if (n_pot > 0) {
-        if (n_pot >= (1ll << 31))
-            return fail(YAWHIP_ERR_INVALID, "too many work items (%lld) in one job", (long long)n_pot);
-        const int bwg = build_wg_for(n_pot);
-        const unsigned bgrid = (unsigned)((n_pot + bwg - 1) / bwg);
-        // item list in segments (append_items): where the float32 band kernels consume what the strip builder keeps
-        if (P.strip_items && (P.band32 || P.band_fine) && !job_work && ctx->item_segments)
-            seg_cap = (unsigned long long)((bgrid + ITEM_SEGS - 1) / ITEM_SEGS) * (unsigned long long)bwg;
-        HIP_TRY(reserve_call(ctx->d_items, seg_cap ? (size_t)(seg_cap * ITEM_SEGS) : (size_t)n_pot));
-        unsigned char *kept_flags = nullptr;  // weighted runs of the culling builders: which potential items write a slab
-        if (P.run_weighted && P.sweep) {
-            HIP_TRY(reserve_call(ctx->d_kept, (size_t)n_pot));
-            HIP_TRY(hipMemsetAsync(ctx->d_kept.ptr, 0, (size_t)n_pot, ctx->stream));
-            kept_flags = ctx->d_kept.ptr;
-        }
-        if (P.strip_items)
-            hipLaunchKernelGGL(k_build_items_strips, dim3(bgrid), dim3(bwg), 0, ctx->stream, P.d_tabs,
-                               reinterpret_cast<const JobRec *>(P.d_jobs), P.d_prefix, (int)P.n_sjobs,
-                               P.triple ? 0 : P.reach, (int)P.tile, P.rwin_max, P.cap_c, P.cap_s, P.swap ? 1 : 0, P.triple ? 1 : 0,
-                               n_pot, ctx->d_items.ptr,
-                               ctx->d_ctr, kept_flags, seg_cap);
-        else if (P.sweep)
-            hipLaunchKernelGGL(k_build_items<true>, dim3(bgrid), dim3(bwg), 0, ctx->stream, view_of(c1), view_of(c2),
-                               P.d_jobs, P.d_prefix, (int)P.n_pslots, n_bins, (int)P.tile,
-                               P.d_rwin, n_pot, ctx->d_items.ptr, ctx->d_ctr, kept_flags);
-        else
-            hipLaunchKernelGGL(k_build_items<false>, dim3(bgrid), dim3(bwg), 0, ctx->stream, view_of(c1), view_of(c2),
-                               P.d_jobs, P.d_prefix, (int)P.n_pslots, n_bins, (int)P.tile, P.d_rwin, n_pot,
-                               ctx->d_items.ptr, ctx->d_ctr, nullptr);
-        HIP_TRY(hipGetLastError());
-        ++launches;
-        // The count kernels are launched over all potential items and return at once for indices beyond the
-        // number the builder kept (device counter): no host round trip between the two kernels.
-        n_items = n_pot;
-        if (P.strip_items && !P.band && n_pot > SYNC_GRID_MIN_ITEMS) {
-            // SWEEP: the strip path keeps about one potential item in five; a grid over all of them spends ~0.2 ms
-            // dispatching workgroups that exit at once (measured at 1.6e6 potential items, 10M x 10M), more than
-            // this round trip (~0.05 ms) costs. Small calls (one GPU's share of a sharded job list) skip it.
-            // (The band kernel sizes its grid from the potential items and loops: no round trip.)
-            HIP_TRY(hipMemcpyAsync(ctx->out.h, ctx->d_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            n_items = (int64_t)reinterpret_cast<unsigned long long *>(ctx->out.h)[0];
-        }
-    }
-    if (job_work) {  // cost estimate only: evaluated pairs per job from the item list, no counting
-        HIP_TRY(reserve_call(ctx->d_jobwork, (size_t)n_jobs));
-        HIP_TRY(hipMemsetAsync(ctx->d_jobwork.ptr, 0, sizeof(unsigned long long) * (size_t)n_jobs, ctx->stream));
-        if (n_pot > 0) {
-            hipLaunchKernelGGL(k_item_work, dim3((unsigned)((n_pot + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_items.ptr,
-                               ctx->d_ctr, P.merged ? 1 : n_bins, ctx->d_jobwork.ptr);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(job_work, ctx->d_jobwork.ptr, sizeof(int64_t) * (size_t)n_jobs, hipMemcpyDeviceToHost,
-                               ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return YAWHIP_OK;
-    }
-    // two-level ordered reduction of the weighted slabs (k_reduce_chunks / k_reduce_slots), per output slot; prefix = first
-    // potential item of every output slot, chunk prefix = first chunk of every output slot
-    auto reduce_partials = [&]() -> hipError_t {
-        const int64_t n_oslots = P.n_pslots, values = P.slab, n_chunks = P.n_chunks;
-        hipError_t er = reserve_call(ctx->d_chunk_sums, (size_t)std::max<int64_t>(n_chunks, 1) * values);
-        if (er != hipSuccess) return er;
-        const int thr = 256;
-        const bool all_kept = !(P.run_weighted && P.sweep);
-        if (n_chunks > 0)
-            hipLaunchKernelGGL(k_reduce_chunks, dim3((unsigned)((n_chunks * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                               ctx->d_partials.ptr, all_kept ? nullptr : ctx->d_kept.ptr, P.d_prefix, P.d_cprefix,
-                               (int)n_oslots, (int)values, ctx->d_chunk_sums.ptr, ctx->d_ctr);
-        hipLaunchKernelGGL(k_reduce_slots, dim3((unsigned)((n_oslots * values + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_chunk_sums.ptr, P.d_cprefix, (int)n_oslots, (int)values, ctx->d_sums,
-                           n_chunks > 0 ? nullptr : ctx->d_ctr);
-        return hipGetLastError();
-    };
-    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->evc0, ctx->stream));
-    // The count kernels. Their variants are picked from the plan (pick; each list runs from the last variant to the first:
-    // the compiler lays the kernels out in the reverse order, which keeps the code object as it was).
-    // Every launch records its variant in cs.variant[weighted] (yawhip_stats.count_variant*).
-    // Band kernels: grid from the number of POTENTIAL items (known on the host); the kernel reads the number the builder kept
-    // from the device counter, workgroups beyond it exit, workgroups loop if more were kept than the grid holds.
-    // The strip builder keeps about one potential item in five, ordinary items are all kept.
-    int64_t grid = P.strip_items && n_pot > 65536 ? n_pot / P.grid_div : n_pot;
-    // Batches of consecutive items (one flush of the histogram per batch) are a tunable, off by default: consecutive
-    // items are tiles of the same run, so on clustered data a batch strings the heaviest items together on one
-    // workgroup (measured: DD of the clustered survey with 31 fine bins 7.2 -> 20.6 ms with batches of four), and on
-    // uniform data the flush they save is not what the time goes to (2.27 ms either way at the headline, 51 fine bins).
-    const int batch_log2 = ctx->band_batch_log2 >= 0 ? ctx->band_batch_log2 : 0;
-    if (!P.run_weighted) grid = std::max<int64_t>(grid >> batch_log2, 8);
-    grid = std::min<int64_t>((grid + 7) & ~7ll, 1ll << 22);
-    const dim3 band_grid((unsigned)grid), wave(64);
-    // 32-bit LDS counters: one stage adds at most 64 R x CAP to a cell, so flush at the latest every
-    // 2^32 / (64 R CAP) stages (2^17 for two objects per lane and 192-entry stages, 2^15 for four and 288)
-    int flush_log2 = ctx->flush_log2;
-    while (flush_log2 > 0 && ((uint64_t)64 * P.R * 2 * P.cap << flush_log2) >= (1ull << 32)) --flush_log2;  // (x 2: half bands count double)
-    const unsigned flush_mask = (1u << flush_log2) - 1u;
-    const std::pair<int, int> stage{P.R, P.cap};
-    const std::pair<bool, bool> rows{P.merged, P.uni};
-    auto launch_band32 = [&](bool wgt) -> hipError_t {
-        const size_t lds = band32_lds(P.weighted, P.cap, P.lean_bins * P.nf, P.merged && !P.uniform_t ? n_bins : 0, n_edges);
-        const bool one_chunk = P.triple || !P.strip_items;  // every item has one window
-        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
-            return pick<Int<4>, Int<3>, Int<2>>(n_edges, [&](auto ne) {
-                return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
-                    return pick<Stage<4, B32_CAP_BIG>, Stage<2, B32_CAP_BIG>, Stage<2, B32_CAP>, Stage<1, B32_CAP>>(stage, [&](auto s) {
-                        using S = decltype(s);
-                        using M = decltype(r);
-                        auto kern = one_chunk ? k_count_band32_one<S::R, S::CAP, w, ne, M::MERGED, M::UNI>
-                                              : k_count_band32<S::R, S::CAP, w, ne, M::MERGED, M::UNI>;
-                        cs.variant[w] = variant_code(one_chunk ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
-                        return launch(kern, band_grid, wave, lds, ctx->stream, P.d_tabs, ctx->d_items.ptr, n_bins, P.d_t,
-                                      P.d_thr32, P.d_rwin, P.d_ucap, flush_mask, P.swap ? 1 : 0, ctx->d_counts,
-                                      ctx->d_partials.ptr, ctx->d_ctr, seg_cap);
-                    });
-                });
-            });
-        });
-    };
-    auto launch_band64 = [&](bool wgt) -> hipError_t {
-        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
-            return pick<Int<0>, Int<4>, Int<3>, Int<2>>(P.band_ne, [&](auto ne) {
-                return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
-                    return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
-                        using S = decltype(s);
-                        using M = decltype(r);
-                        cs.variant[w] = variant_code(VF_BAND, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
-                        return launch(k_count_band<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, P.lds_band, ctx->stream,
-                                      P.d_tabs, ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_rwin, flush_mask,
-                                      P.hp_shift, w ? 0 : batch_log2, ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr);
-                    });
-                });
-            });
-        });
-    };
-    auto launch_fine = [&](bool wgt) -> hipError_t {
-        const size_t lds = band32_fine_lds(P.weighted, P.cap, P.lean_bins * P.nf, P.uniform_t ? 1 : n_bins, n_edges);
-        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
-            return pick<Rows<true, false>, Rows<true, true>, Rows<false, false>, Rows<false, true>>(rows, [&](auto r) {
-                return pick<Stage<4, BCAP_MID>, Stage<2, BCAP_MID>, Stage<2, BCAP>, Stage<1, BCAP>>(stage, [&](auto s) {
-                    using S = decltype(s);
-                    using M = decltype(r);
-                    cs.variant[w] = variant_code(VF_BAND32_FINE, S::R, S::CAP, w, 0, M::MERGED, M::UNI);
-                    return launch(k_count_band32_fine<S::R, S::CAP, w, M::MERGED, M::UNI>, band_grid, wave, lds, ctx->stream,
-                                  P.d_tabs, ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_thr32, P.d_rwin,
-                                  P.d_ucap, flush_mask, P.swap ? 1 : 0, ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr, seg_cap);
-                });
-            });
-        });
-    };
-    // The lean kernel (k_count_merged / _occ8) and k_count, one workgroup per item: grids in pieces of at most 2^32 - 1
-    // work-items per launch dimension.
-    auto in_pieces = [&](int wg, auto &&launch_at) -> hipError_t {
-        const int64_t max_grid = (1ll << 31) / wg;
-        for (int64_t base = 0; base < n_items; base += max_grid) {
-            const hipError_t e = launch_at(dim3((unsigned)std::min(max_grid, n_items - base)), base);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    };
-    auto launch_lean = [&](bool wgt) -> hipError_t {
-        return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
-            return pick<Bool<false>, Bool<true>>(P.nf == 1, [&](auto nf1) {
-                return pick<Bool<false>, Bool<true>>(P.merged, [&](auto m) {
-                    return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
-                        cs.variant[w] = variant_code(r <= 2 ? VF_MERGED_OCC8 : VF_MERGED,  // (the choice of pick_count_merged)
-                                                      r, 0, w, 0, m, false, false, false, nf1);
-                        return in_pieces(MWG, [&](dim3 g, int64_t base) {
-                            return launch(pick_count_merged<r, w, nf1, m>(), g, dim3(MWG), P.lds_merged, ctx->stream, P.d_tabs,
-                                          ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_dthr, P.d_rwin, base,
-                                          ctx->d_counts, ctx->d_partials.ptr, ctx->d_ctr);
-                        });
-                    });
-                });
-            });
-        });
-    };
-    // LDS of k_count: two stages + thresholds + histogram(s)
-    const size_t lds_fixed = 2 * STAGE * (sizeof(Obj) + sizeof(ObjF)) + (size_t)((n_edges + 1) & ~1) * sizeof(double);
-    auto lds_for = [&](bool w, bool priv) { return lds_fixed + (size_t)P.nf * (priv ? WG : 1) * (w ? 8 : 4); };
-    auto launch_plain = [&](bool wgt) -> hipError_t {
-        const bool priv = lds_for(wgt, true) <= (size_t)ctx->lds_limit;
-        return pick<Bool<true>, Bool<false>>(wgt, [&](auto w) {
-            return pick<Bool<false>, Bool<true>>(priv, [&](auto pv) {
-                return pick<Bool<false>, Bool<true>>(P.filter, [&](auto f) {
-                    return pick<Int<4>, Int<2>, Int<1>>(P.R, [&](auto r) {
-                        cs.variant[w] = variant_code(VF_COUNT, r, 0, w, 0, false, false, pv, f);
-                        return in_pieces(WG, [&](dim3 g, int64_t base) {
-                            return launch(k_count<r, w, pv, f>, g, dim3(WG), lds_for(w, pv), ctx->stream, view_of(c1), view_of(c2),
-                                          ctx->d_items.ptr, n_bins, n_edges, P.d_t, P.d_dthr, base, ctx->d_counts,
-                                          ctx->d_partials.ptr, ctx->d_ctr);
-                        });
-                    });
-                });
-            });
-        });
-    };
-    const bool band_ran = n_items > 0 && P.lean && P.band;
-    auto launch_count = [&](bool wgt) {
-        if (band_ran) return P.band32 ? launch_band32(wgt) : (P.band_fine ? launch_fine(wgt) : launch_band64(wgt));
-        return P.lean ? launch_lean(wgt) : launch_plain(wgt);
-    };
-    if (n_items > 0 && P.run_unweighted) {
-        HIP_TRY(launch_count(false));
-        ++launches;
-    }
-    if (n_items > 0 && P.run_weighted) {
-        HIP_TRY(launch_count(true));
-        ++launches;
-        HIP_TRY(reduce_partials());
-        launches += 2;
-    }
-    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->evc1, ctx->stream));
-    if (!P.weighted && want_sums) {
-        const int thr = 256;
-        hipLaunchKernelGGL(k_counts_to_double, dim3((unsigned)((P.n_out + thr - 1) / thr)), dim3(thr), 0, ctx->stream,
-                           ctx->d_counts, ctx->d_sums, P.n_out, ctx->d_ctr);
-        HIP_TRY(hipGetLastError());
-        ++launches;
-    }
-    if (!cs.stamps) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    // the tail brings back the counters and whatever was asked for, into pinned memory, and cleans behind itself
-    // (fetch_results = false: the caller reduces the results on the device first and fetches what is left; counters only here,
-    // and the counts stay where they are: the slot stays dirty)
-    const size_t fetch = !fetch_results ? o_counts : (want_sums ? out_bytes : (want_counts ? o_sums : o_counts));
-    const size_t clean = std::min(fetch, o_sums);
-    const bool sums_written = P.n_items > 0 && (P.run_weighted || want_sums);
-    cs.cleaned = clean == o_sums;
-    cs.zero_after = sums_written ? o_sums : ctx->zero_upto;
-    const unsigned n_copy = (unsigned)(fetch / 16), n_clean = (unsigned)(clean / 16);
-    static_assert(N_CTR * sizeof(unsigned long long) % 16 == 0 && (CTR_DONE + 2) * sizeof(unsigned long long) <= N_CTR * sizeof(unsigned long long),
-                  "the tail's words lie inside the counter block");
-    if (fetch / 16 > 0xffffffffull) return fail(YAWHIP_ERR_INVALID, "result block too large (%zu bytes)", fetch);
-    unsigned char *const out_d = ctx->out.d;
-    hipLaunchKernelGGL(k_call_tail, dim3(std::min((n_copy + TAIL_WG - 1) / TAIL_WG, TAIL_MAX_GRID)), dim3(TAIL_WG), 0, ctx->stream,
-                       reinterpret_cast<uint4 *>(out_d), reinterpret_cast<uint4 *>(ctx->out.h), n_copy, n_clean,
-                       (unsigned long long)cs.seq);
-    HIP_TRY(hipGetLastError());
-    ++launches;
-    cs.pending = true;
-    cs.o_ctr = o_ctr; cs.o_counts = o_counts; cs.o_sums = o_sums;
-    cs.band_ran = band_ran; cs.run_unweighted = P.run_unweighted; cs.run_weighted = P.run_weighted;
-    cs.cand = P.cand; cs.abytes = P.abytes; cs.n_pot = n_pot; cs.segmented = seg_cap != 0;
-    cs.launches = launches; cs.kernel = P.kernel; cs.mode = P.mode;
-    cs.n_orient = P.n_orient;
-    cs.band_variant = !band_ran ? 0 : (P.band32 ? 32 : (P.band_fine ? 33 : 64));
-    cs.merged_triples = band_ran && P.triple ? 1 : 0;
-    g_trace.mark("launched");
-    return YAWHIP_OK;
+    return hipErrorInvalidValue;
 }
 
-// Second half: wait for the context's stream, hand the results (contiguous rows of the jobs given to count_enqueue) and
-// the statistics over.
-// row_index != nullptr: row r of this call's result goes to row row_index[r] of the caller's arrays (rows of row_len values):
-// the devices of a multi-device call write their shares straight into place.
-// wait_done: wait for the active slot's ev_done (recorded by the caller behind everything this call put on the stream)
-// instead of the whole stream -- the requests of a batch behind it keep running.
-int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, double *fine_sums, yawhip_stats *stats,
-                 const int32_t *row_index, int64_t row_len, bool wait_done) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    const int64_t n_rows = !row_index ? 1 : (row_len > 0 ? cs.n_out / row_len : 0), row = row_index ? row_len : cs.n_out;
-    if (!cs.pending) {
-        place_rows<int64_t>(fine_counts, nullptr, n_rows, row, row_index);
-        place_rows<double>(fine_sums, nullptr, n_rows, row, row_index);
-        return YAWHIP_OK;
-    }
-    g_trace.mark("meanwhile");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->spin_wait) {
-        // poll for up to 2 ms (a headline call takes 0.5 ms; the wake-up of a blocked thread costs ~0.01 ms), then block.
-        // What is polled is the completion word k_call_tail writes into the slot's pinned block behind the results -- no
-        // runtime call per look -- unless the caller put more behind the tail: then the stream or the slot's ev_done, as before.
-        const unsigned long long *done_word = reinterpret_cast<const unsigned long long *>(ctx->out.h) + CTR_DONE;
-        auto query = [&]() { return wait_done ? hipEventQuery(ctx->ev_done) : hipStreamQuery(ctx->stream); };
-        hipError_t qe = hipErrorNotReady;
-        const auto spin0 = std::chrono::steady_clock::now();
-        do {
-            if (cs.word_wait) {
-                if (__atomic_load_n(done_word, __ATOMIC_ACQUIRE) == cs.seq) qe = hipSuccess;
-            } else {
-                qe = query();
-            }
-            if (qe != hipErrorNotReady) break;
-            __builtin_ia32_pause();
-        } while (std::chrono::steady_clock::now() - spin0 < std::chrono::milliseconds(2));
-        if (qe == hipSuccess && cs.word_wait) {  // one look at the runtime: an asynchronous error surfaces here, not a call later
-            const hipError_t late = query();
-            if (late != hipErrorNotReady) qe = late;  // (not ready: the packets behind the tail, or other slots' requests)
-        }
-        if (qe == hipErrorNotReady) qe = wait_done ? hipEventSynchronize(ctx->ev_done) : hipStreamSynchronize(ctx->stream);
-        HIP_TRY(qe);
-    } else {
-        HIP_TRY(wait_done ? hipEventSynchronize(ctx->ev_done) : hipStreamSynchronize(ctx->stream));
-    }
-    g_trace.mark("waited");
-    if (cs.cleaned) {  // the tail has left [counters][counts] of the slot's block at zero
-        ctx->dirty = false;
-        ctx->zero_upto = cs.zero_after;
-    }
-    place_rows(fine_counts, reinterpret_cast<const int64_t *>(ctx->out.h + cs.o_counts), n_rows, row, row_index);
-    place_rows(fine_sums, reinterpret_cast<const double *>(ctx->out.h + cs.o_sums), n_rows, row, row_index);
-    const unsigned long long *ctr = reinterpret_cast<const unsigned long long *>(ctx->out.h + cs.o_ctr);
-    g_trace.mark("copied");
-    if (stats) {
-        float ms = 0.f, cms = 0.f;
-        if (cs.stamps) {
-            // device clock stamps (see CTR_T_BUILD): the builder's start to the tail's start, and the latest builder exit to the
-            // start of the first kernel behind the count kernel(s) -- the count kernels with the dispatch gaps on either side
-            unsigned long long built = 0;
-            for (int sg = 0; sg < ITEM_SEGS; ++sg) built = std::max(built, ctr[SEG_EXIT_CTR(sg)]);
-            ms = (float)((double)(ctr[CTR_T_TAIL] - ctr[CTR_T_BUILD]) * CLOCK_MS);
-            cms = (float)((double)(ctr[CTR_T_COUNTED] - built) * CLOCK_MS);
-        } else {
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-            HIP_TRY(hipEventElapsedTime(&cms, ctx->evc0, ctx->evc1));
-        }
-        stats->count_ms = cms;
-        stats->candidate_pairs = cs.cand;
-        unsigned long long tile_pairs = 0;
-        for (int i = 0; i < EVAL_SLOTS; ++i) tile_pairs += ctr[10 + 8 * (size_t)i];
-        stats->evaluated_pairs = (int64_t)tile_pairs * ((cs.run_unweighted ? 1 : 0) + (cs.run_weighted ? 1 : 0));
-        if (cs.band_ran) {  // band kernel: the entries its lanes really walked (both launches of a weighted + counts call)
-            unsigned long long ev = 0;
-            for (int i = 0; i < EVAL_SLOTS; ++i) ev += ctr[8 + 8 * (size_t)i];
-            stats->evaluated_pairs = (int64_t)ev;
-        }
-        stats->algorithmic_bytes = cs.abytes;
-        stats->n_workgroups = cs.n_pot > 0 ? (int64_t)ctr[0] : 0;
-        if (cs.segmented && cs.n_pot > 0)
-            for (int sg = 0; sg < ITEM_SEGS; ++sg) stats->n_workgroups += (int64_t)ctr[ITEM_SEG_CTR(sg)];
-        stats->n_launches = cs.launches;
-        stats->kernel_used = cs.kernel;
-        stats->layout_mode = cs.mode;
-        stats->n_orientations = cs.n_orient;
-        stats->band_variant = cs.band_variant;
-        stats->merged_triples = cs.merged_triples;
-        stats->count_variant = cs.variant[0];
-        stats->count_variant_weighted = cs.variant[1];
-        if (cs.band_ran)
-            for (int i = 0; i < EVAL_SLOTS; ++i) stats->exact_reevaluations += (int64_t)ctr[9 + 8 * (size_t)i];
-        stats->kernel_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - cs.wall0).count();
-    }
-    g_trace.mark("stats");
-    return YAWHIP_OK;
+hipError_t launch_counts_to_double(const CountLaunch &L, int64_t n_out) {
+    const int thr = 256;
+    hipLaunchKernelGGL(k_counts_to_double, dim3((unsigned)((n_out + thr - 1) / thr)), dim3(thr), 0, L.stream,
+                       L.d_counts, L.d_sums, n_out, L.d_ctr);
+    return hipGetLastError();
 }
-
-void add_stats(yawhip_stats &total, const yawhip_stats &part, bool side_by_side) {
-    total.candidate_pairs += part.candidate_pairs;
-    total.evaluated_pairs += part.evaluated_pairs;
-    total.algorithmic_bytes += part.algorithmic_bytes;
-    total.n_workgroups += part.n_workgroups;
-    total.n_launches += part.n_launches;
-    total.kernel_used = part.kernel_used;
-    total.layout_mode = part.layout_mode;
-    total.n_orientations = std::max(total.n_orientations, part.n_orientations);
-    total.band_variant = part.band_variant;
-    total.merged_triples = part.merged_triples;
-    total.count_variant = merge_variant(total.count_variant, part.count_variant);
-    total.count_variant_weighted = merge_variant(total.count_variant_weighted, part.count_variant_weighted);
-    total.exact_reevaluations += part.exact_reevaluations;
-    if (side_by_side) {  // devices of one call run at the same time: the slowest counts
-        total.kernel_ms = std::max(total.kernel_ms, part.kernel_ms);
-        total.count_ms = std::max(total.count_ms, part.count_ms);
-    } else {             // pieces of one job list on one device run one after the other
-        total.kernel_ms += part.kernel_ms;
-        total.count_ms += part.count_ms;
-    }
-}
-
-// One job list on one device, cut in halves as often as count_enqueue asks for (SPLIT_JOBS).
-int run_single(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-               int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, int64_t *fine_counts, double *fine_sums,
-               yawhip_stats *stats, const std::function<void()> *meanwhile) {
-    // meanwhile: host work of the caller that does not need the result, done while the device counts (once)
-    CallState cs;
-    int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_counts != nullptr, fine_sums != nullptr,
-                           nullptr, cs);
-    if (meanwhile && (rc == YAWHIP_OK || rc == SPLIT_JOBS)) (*meanwhile)();
-    if (rc == YAWHIP_OK) return count_finish(ctx, cs, fine_counts, fine_sums, stats);
-    if (rc != SPLIT_JOBS) return rc;
-    const int32_t half = n_jobs / 2;
-    const size_t row = (size_t)n_bins * (size_t)(n_edges - 1);
-    yawhip_stats a{}, b{};
-    rc = run_single(ctx, c1, c2, half, jobs, n_bins, n_edges, t, kernel, fine_counts, fine_sums, &a);
-    if (rc != YAWHIP_OK) return rc;
-    rc = run_single(ctx, c1, c2, n_jobs - half, jobs + 2 * (size_t)half, n_bins, n_edges, t, kernel,
-                    fine_counts ? fine_counts + (size_t)half * row : nullptr, fine_sums ? fine_sums + (size_t)half * row : nullptr, &b);
-    if (rc != YAWHIP_OK) return rc;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        add_stats(*stats, a, false);
-        add_stats(*stats, b, false);
-        stats->total_ms = a.total_ms + b.total_ms;
-    }
-    return YAWHIP_OK;
+hipError_t launch_call_tail(hipStream_t stream, unsigned char *dev, unsigned char *host, unsigned n_copy, unsigned n_clean,
+                            unsigned long long seq) {
+    hipLaunchKernelGGL(k_call_tail, dim3(std::min((n_copy + TAIL_WG - 1) / TAIL_WG, TAIL_MAX_GRID)), dim3(TAIL_WG), 0, stream,
+                       reinterpret_cast<uint4 *>(dev), reinterpret_cast<uint4 *>(host), n_copy, n_clean, seq);
+    return hipGetLastError();
 }
 
 }  // namespace yawhip_detail
-
-extern "C" {
-
-int yawhip_count_pairs(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
-                       const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                       int64_t *fine_counts, double *fine_sums, yawhip_stats *stats) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    const int rc_args = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
-    if (rc_args != YAWHIP_OK) return rc_args;
-    if (ctx->peers.empty() || n_jobs < 2)
-        return run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_counts, fine_sums, stats);
-    // ---- several devices: the independent jobs are split over them (replaces the reference's process pool,
-    // src/yaw/utils/parallel.py:251-346). Every device holds both catalogues; a job's rows of the result come from
-    // exactly one device, so nothing has to be reduced: the rows are copied into place.
-    const size_t n_dev = ctx->peers.size() + 1;
-    if (c1->replicas.size() != n_dev - 1 || c2->replicas.size() != n_dev - 1)
-        return fail(YAWHIP_ERR_MISMATCH, "catalogue was not uploaded to every device of the context");
-    const auto wall0 = std::chrono::steady_clock::now();
-    // the plan: evaluated pairs per job from the item builder (device 0), longest-processing-time-first over the devices;
-    // it depends on the inputs only and is kept for the next call with the same inputs
-    // (the inputs of the cost estimate below, and the device count)
-    CallKey key(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, true, (int32_t)n_dev);
-    if (!(ctx->plan.key == key)) {
-        std::vector<int64_t> work((size_t)n_jobs, 0);
-        CallState cs;
-        int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, work.data(), cs);
-        if (rc != YAWHIP_OK) return rc;
-        std::vector<int32_t> order((size_t)n_jobs);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return work[(size_t)a] > work[(size_t)b]; });
-        std::vector<double> load(n_dev, 0.0);
-        ctx->plan.parts.assign(n_dev, {});
-        const double fixed = 2.0e5;  // evaluated-pair equivalent of touching a job at all
-        for (int32_t j : order) {
-            const size_t d = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-            ctx->plan.parts[d].push_back(j);
-            load[d] += (double)work[(size_t)j] + fixed;
-        }
-        for (auto &part : ctx->plan.parts) std::sort(part.begin(), part.end());
-        key.keep();
-        ctx->plan.key = std::move(key);
-    }
-    const int64_t row = (int64_t)n_bins * (n_edges - 1);
-    std::vector<CallState> states(n_dev);
-    std::vector<std::vector<int32_t>> sub(n_dev);
-    std::vector<char> later(n_dev, 0);  // shares that have to be cut in pieces: counted after the others, one by one
-    for (size_t d = 0; d < n_dev; ++d) {  // enqueue everywhere first: the devices work side by side
-        for (int32_t j : ctx->plan.parts[d]) { sub[d].push_back(jobs[2 * j]); sub[d].push_back(jobs[2 * j + 1]); }
-        yawhip_ctx *dc = d == 0 ? ctx : ctx->peers[d - 1];
-        const yawhip_catalog *a = d == 0 ? c1 : c1->replicas[d - 1], *b = d == 0 ? c2 : c2->replicas[d - 1];
-        const int rc = count_enqueue(dc, a, b, (int32_t)ctx->plan.parts[d].size(), sub[d].data(), n_bins, n_edges, t, kernel,
-                                     fine_counts != nullptr, fine_sums != nullptr, nullptr, states[d]);
-        if (rc == SPLIT_JOBS) {
-            later[d] = 1;
-        } else if (rc != YAWHIP_OK) {
-            for (size_t e = 0; e < d; ++e) (void)hipStreamSynchronize((e == 0 ? ctx : ctx->peers[e - 1])->stream);
-            return rc;
-        }
-    }
-    std::vector<int64_t> rows_c;
-    std::vector<double> rows_s;
-    yawhip_stats total{}, part{};
-    int rc_all = YAWHIP_OK;
-    for (size_t d = 0; d < n_dev; ++d) {  // every device's copy into its pinned buffer is already under way: drain in turn
-        yawhip_ctx *dc = d == 0 ? ctx : ctx->peers[d - 1];
-        const yawhip_catalog *a = d == 0 ? c1 : c1->replicas[d - 1], *b = d == 0 ? c2 : c2->replicas[d - 1];
-        const size_t nj = ctx->plan.parts[d].size();
-        int rc;
-        if (later[d]) {  // a share that is counted in pieces: through a temporary, then into place
-            if (fine_counts) rows_c.resize(nj * (size_t)row);
-            if (fine_sums) rows_s.resize(nj * (size_t)row);
-            rc = run_single(dc, a, b, (int32_t)nj, sub[d].data(), n_bins, n_edges, t, kernel, fine_counts ? rows_c.data() : nullptr,
-                            fine_sums ? rows_s.data() : nullptr, &part);
-            if (rc == YAWHIP_OK) {
-                place_rows(fine_counts, (const int64_t *)rows_c.data(), (int64_t)nj, row, ctx->plan.parts[d].data());
-                place_rows(fine_sums, (const double *)rows_s.data(), (int64_t)nj, row, ctx->plan.parts[d].data());
-            }
-        } else {         // rows go from the device's pinned buffer straight into the caller's arrays
-            rc = count_finish(dc, states[d], fine_counts, fine_sums, &part, ctx->plan.parts[d].data(), row);
-        }
-        if (rc != YAWHIP_OK) { rc_all = rc; continue; }  // keep draining the other devices
-        add_stats(total, part, true);
-    }
-    (void)hipSetDevice(ctx->device);  // leave the thread on the context's first device, as single-device calls do
-    if (rc_all != YAWHIP_OK) return rc_all;
-    total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    if (stats) *stats = total;
-    return YAWHIP_OK;
-}
-
-int yawhip_job_work(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-                    int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, int64_t *work) {
-    if (!ctx || !work) return fail(YAWHIP_ERR_INVALID, "yawhip_job_work: NULL argument");
-    for (int j = 0; j < n_jobs; ++j) work[j] = 0;
-    const int rc = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
-    if (rc != YAWHIP_OK) return rc;
-    CallState cs;
-    return count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, false, work, cs);
-}
-
-}  // extern "C"

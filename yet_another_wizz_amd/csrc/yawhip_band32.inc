@@ -2,7 +2,8 @@
 // stage -- YAW_B32_CH = 3 as k_count_band32, = 1 as k_count_band32_one (every item has one window: merged triple runs, items of
 // k_build_items; the bookkeeping of two more chunks costs scalar registers and instructions per item). The chunk count is a
 // macro of two inclusions rather than a template parameter because hipcc 7.2 emits no host stubs for this kernel as soon as a
-// template parameter sizes its chunk arrays. Not a translation unit of its own: everything it uses is defined in yawhip.hip.
+// template parameter sizes its chunk arrays. Not a translation unit of its own: everything it uses is defined in yawhip.hip
+// or yawhip_count_kernels.h.
 template <int R, int CAP, bool WEIGHTED, int NE, bool MERGED, bool UNI>
 __global__ __launch_bounds__(64, band32_min_waves(R, CAP, WEIGHTED, NE, UNI))
 void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
@@ -433,7 +434,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                             const ExactEval<NE> ev = band32_exact<NE>(cl.x, cl.y, cl.z, it.a0 + lane_obj * R + r, cs.x, cs.y, cs.z,
                                                                       cs.idx ? (int64_t)cs.idx[cb[c] + eidx] : cb[c] + (int64_t)eidx,
                                                                       t + (size_t)(MERGED ? kb[r] : kfix) * NE,
-                                                                      counters + 9 + 8 * (ticket & (EVAL_SLOTS - 1)));
+                                                                      counters + EXACT_EVAL_CTR(0) + CTR_SLOT_WORDS * (ticket & (EVAL_SLOTS - 1)));
                             const double sd = ev.s;
                             if constexpr (NE == 2) {
                                 const bool in = sd > ev.th[0] && sd <= ev.th[1];
@@ -485,7 +486,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
             flush_counts();
         }
         nev = wave_sum_lane63(nev);  // (DPP: the shuffle form is six trips through the LDS crossbar, per item, for a statistic)
-        if (lane == 63 && nev) atomicAdd(&counters[8 + 8 * (ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
+        if (lane == 63 && nev) atomicAdd(&counters[BAND_ENTRY_CTR(ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
     }
 }
 

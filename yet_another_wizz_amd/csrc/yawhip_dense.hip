@@ -1,4 +1,4 @@
-// yawhip_dense.hip -- the dense epilogue on top of the count call of yawhip.hip (count_enqueue / count_finish / run_single):
+// yawhip_dense.hip -- the dense epilogue on top of the count call of yawhip_count.hip (count_enqueue / count_finish / run_single):
 // yawhip_count_pairs_dense and yawhip_count_pairs_dense_batch recombine the fine bins of every scale (k_combine_scales, or
 // numpy_sum on the host) and scatter the jobs into [scale][bin][patch i][patch j]; yawhip_count_pairs_rows_device leaves the
 // rows of a sharded count on the device (k_scatter_rows). The two kernels are launched only from here.
@@ -105,9 +105,14 @@ struct DenseState {
     size_t h_comb_off = 0;
 };
 
-int dense_check(const yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t,
+// the count a request asks for
+CountArgs request_args(const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel) {
+    return CountArgs{r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t, kernel};
+}
+
+int dense_check(const yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
                 int32_t n_scales, const int32_t *slices) {
-    const int rc = check_call(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t);
+    const int rc = check_call(ctx, request_args(r, n_bins, n_edges, t, kernel));
     if (rc != YAWHIP_OK) return rc;
     if (n_scales <= 0 || !slices || !r.dense) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense: bad sizes or NULL arrays");
     return YAWHIP_OK;
@@ -122,7 +127,7 @@ int dense_enqueue(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bins
     ds.weighted = r.c1->w != nullptr || r.c2->w != nullptr;
     ds.slot = ctx->slot;
     ds.device_combine = nf > 1;
-    int rc = count_enqueue(ctx, r.c1, r.c2, r.n_jobs, r.jobs, n_bins, n_edges, t, kernel, !ds.weighted, ds.weighted, nullptr, ds.cs,
+    int rc = count_enqueue(ctx, request_args(r, n_bins, n_edges, t, kernel), !ds.weighted, ds.weighted, nullptr, ds.cs,
                            /*fetch_results=*/!ds.device_combine);
     if (rc == SPLIT_JOBS) return YAWHIP_OK;  // counted in pieces by the blocking route when its turn comes (ds.enqueued stays false)
     if (rc != YAWHIP_OK) return rc;
@@ -238,7 +243,7 @@ int dense_blocking(yawhip_ctx *ctx, const yawhip_dense_request &r, int32_t n_bin
         dense_clear(r, n_bins, n_scales);
         cleared = true;
     };
-    const int rc = ctx->peers.empty() ? run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats, &clear)
+    const int rc = ctx->peers.empty() ? run_single(ctx, request_args(r, n_bins, n_edges, t, kernel), fine_c.get(), fine_s.get(), r.stats, &clear)
                                       : yawhip_count_pairs(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, fine_c.get(), fine_s.get(), r.stats);
     if (rc != YAWHIP_OK) return rc;
     g_trace.mark("finished");
@@ -293,7 +298,8 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
     if (!ctx || !c1 || !c2 || !device_rows) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: NULL argument");
     *device_rows = nullptr;
     if (!ctx->peers.empty()) return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: single-device contexts only");
-    const int rc_args = check_call(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t);
+    const CountArgs args{c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel};
+    const int rc_args = check_call(ctx, args);
     if (rc_args != YAWHIP_OK) return rc_args;
     if (n_rows_total < n_jobs || (n_jobs > 0 && !row_index))
         return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_rows_device: bad sizes or NULL arrays");
@@ -307,11 +313,11 @@ int yawhip_count_pairs_rows_device(yawhip_ctx *ctx, const yawhip_catalog *c1, co
     HIP_TRY(reserve_call(ctx->d_rowidx, (size_t)std::max(n_jobs, 1)));
     CallState cs;
     // (the rows stay on the device: only the statistics counters are fetched)
-    int rc = count_enqueue(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, false, true, nullptr, cs, /*fetch_results=*/false);
+    int rc = count_enqueue(ctx, args, false, true, nullptr, cs, /*fetch_results=*/false);
     if (rc == SPLIT_JOBS) {
         // a job list that is counted in pieces: through the host (rare: weighted slabs beyond the budget)
         std::vector<double> rows((size_t)n_jobs * (size_t)row), full(n_full, 0.0);
-        rc = run_single(ctx, c1, c2, n_jobs, jobs, n_bins, n_edges, t, kernel, nullptr, rows.data(), stats);
+        rc = run_single(ctx, args, nullptr, rows.data(), stats);
         if (rc != YAWHIP_OK) return rc;
         place_rows(full.data(), (const double *)rows.data(), n_jobs, row, row_index);
         HIP_TRY(hipMemcpy(ctx->d_full.ptr, full.data(), sizeof(double) * n_full, hipMemcpyHostToDevice));
@@ -349,7 +355,7 @@ int yawhip_count_pairs_dense_batch(yawhip_ctx *ctx, int32_t n_requests, const ya
         return fail(YAWHIP_ERR_INVALID, "yawhip_count_pairs_dense_batch: NULL argument");
     for (int i = 0; i < n_requests; ++i) {
         if (requests[i].stats) memset(requests[i].stats, 0, sizeof(yawhip_stats));
-        const int rc = dense_check(ctx, requests[i], n_bins, n_edges, t, n_scales, slices);
+        const int rc = dense_check(ctx, requests[i], n_bins, n_edges, t, kernel, n_scales, slices);
         if (rc != YAWHIP_OK) return rc;
     }
     const int nf = n_edges - 1;

@@ -1,4 +1,5 @@
-// Shared by the translation units behind the C ABI of include/yawhip.h -- yawhip.hip (count kernels and the count call),
+// Shared by the translation units behind the C ABI of include/yawhip.h -- yawhip.hip (count kernels and their launch layer),
+// yawhip_count.hip (the count call that plans and launches them; the two share yawhip_count_kernels.h besides),
 // yawhip_ingest.hip (catalogue upload and layouts), yawhip_dense.hip (dense epilogue) and yawhip_api.hip (contexts, options,
 // error reporting, wrappers of the other units): error reporting, the records the kernels and the layouts share, the context
 // and catalogue handles, and the few functions that cross units. Private: never installed, not part of the C ABI.
@@ -223,7 +224,25 @@ struct CallBufs {
 constexpr int MAX_BATCH = 4;  // counts of one measurement on the stream at once (DD, DR, RD, RR)
 constexpr size_t MAX_PLANS = 16;  // plans kept per context (least recently used one goes)
 
-struct HostPlan;  // what a call derives from its inputs on the host, kept for the next call with the same inputs (yawhip.hip)
+struct HostPlan;  // what a call derives from its inputs on the host, kept for the next call with the same inputs (yawhip_count.hip)
+
+// What is to be counted, as every step of a count call passes it on: made once at the C entry point from its arguments, then
+// handed down by reference. A step that counts a part of the job list (the halves of run_single, a device's share in
+// yawhip_count_pairs) makes its record from the whole call's with with_jobs.
+struct CountArgs {
+    const yawhip_catalog *c1, *c2;
+    int32_t n_jobs;
+    const int32_t *jobs;  // [n_jobs][2] patch ids (c1, c2)
+    int32_t n_bins, n_edges;
+    const double *t;      // [n_bins][n_edges] thresholds
+    int32_t kernel;       // YAWHIP_KERNEL_*
+    CountArgs with_jobs(int32_t n, const int32_t *j) const {
+        CountArgs a = *this;
+        a.n_jobs = n;
+        a.jobs = j;
+        return a;
+    }
+};
 
 // Everything a plan depends on: the catalogue pair (by upload id), the option set, sizes, kernel, the outputs asked for, job
 // list and thresholds (compared exactly) -- and, for the job partition of a multi-device call, the device count. A key made
@@ -238,9 +257,8 @@ struct CallKey {
     std::vector<double> own_t;
 
     CallKey() = default;
-    CallKey(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-            int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, bool want_counts, bool want_sums, bool for_work,
-            int32_t n_dev = 0);  // (yawhip.hip)
+    CallKey(const yawhip_ctx *ctx, const CountArgs &a, bool want_counts, bool want_sums, bool for_work,
+            int32_t n_dev = 0);  // (yawhip_count.hip)
     // (moves keep jobs / t valid: a vector's elements stay where they are; copies would not)
     CallKey(CallKey &&) = default;
     CallKey &operator=(CallKey &&) = default;
@@ -422,20 +440,17 @@ void place_rows(T *out, const T *in, int64_t n_rows, int64_t row, const int32_t 
     }
 }
 
-// ---- yawhip.hip: the count call
-int check_call(const yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-               int32_t n_bins, int32_t n_edges, const double *t);
+// ---- yawhip_count.hip: the count call
+int check_call(const yawhip_ctx *ctx, const CountArgs &a);
 int check_band_cap(int64_t value);
 void drop_plans(yawhip_ctx *ctx, const yawhip_catalog *c);  // (defined with HostPlan)
-int count_enqueue(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs,
-                  const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel,
-                  bool want_counts, bool want_sums, int64_t *job_work, CallState &cs, bool fetch_results = true);
+int count_enqueue(yawhip_ctx *ctx, const CountArgs &a, bool want_counts, bool want_sums, int64_t *job_work, CallState &cs,
+                  bool fetch_results = true);
 int count_finish(yawhip_ctx *ctx, const CallState &cs, int64_t *fine_counts, double *fine_sums, yawhip_stats *stats,
                  const int32_t *row_index = nullptr, int64_t row_len = 0, bool wait_done = false);
 void add_stats(yawhip_stats &total, const yawhip_stats &part, bool side_by_side);
-int run_single(yawhip_ctx *ctx, const yawhip_catalog *c1, const yawhip_catalog *c2, int32_t n_jobs, const int32_t *jobs,
-               int32_t n_bins, int32_t n_edges, const double *t, int32_t kernel, int64_t *fine_counts, double *fine_sums,
-               yawhip_stats *stats, const std::function<void()> *meanwhile = nullptr);
+int run_single(yawhip_ctx *ctx, const CountArgs &a, int64_t *fine_counts, double *fine_sums, yawhip_stats *stats,
+               const std::function<void()> *meanwhile = nullptr);
 // ---- yawhip_ingest.hip: the layouts a count call builds on first use
 int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg);
 int build_triples(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg);
