@@ -574,6 +574,34 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
                             int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c, double *fine_w,
                             yawhip_stats *stats);
 
+/*
+ * Shear-shear sums between ANY two (patch, redshift bin) segments of one or of two binned shear catalogues: the cross-bin
+ * signals xi^{ij} of a tomographic analysis and the correlations between two shape samples
+ * (measurements.correlate_shear_tomographic; no counterpart in the reference). Additive to ABI 6: one new symbol.
+ *
+ * yawhip_shear_pair_count   a, b: two handles of yawhip_shear_upload_binned (or yawhip_shear_upload: one bin) on the context;
+ *                       they may be the same handle, and need neither equal patch counts nor equal bin counts nor one sort
+ *                       axis. Cell c = (p, q, ka, kb, row) holds, per fine bin e, the sums over the pairs (object a_obj of
+ *                       segment (p, ka) of a, object b_obj of segment (q, kb) of b) with t[row][e] < s2 <= t[row][e + 1].
+ *                       Membership and the four terms fine_p, fine_m, fine_c, fine_w of a pair are those of
+ *                       yawhip_shear_auto_count above, operation by operation, with the same den == 0 rule.
+ *     A cell is DIAGONAL iff a == b, ka == kb and p == q: it holds every unordered pair of the segment once. Every other cell
+ *     holds every (a_obj, b_obj) once -- also (p, p, k, k) between two different handles. With a == b and ka == kb a cell
+ *     with p > q is refused, as a job with p > q is by yawhip_shear_auto_count; cells (p, q, k, k, k) with p <= q on one
+ *     handle return the bits of yawhip_shear_auto_count for the jobs (p, q), the same thresholds and bin k.
+ *   cells        int32[n_cells][5];  t  float64[n_rows][E] ascending and non-negative per row, E <= 256
+ *   fine_p, fine_m, fine_c, fine_w   float64[n_cells][E-1] each (host); every element is written
+ *   stats        as for yawhip_shear_auto_count
+ * Kernel, accumulation and reproducibility as yawhip_shear_auto_count: one workgroup per cell, (p, ka) of a streamed through
+ * LDS and (q, kb) of b in the lanes; the sort-key window is used iff the two handles are sorted along the same axis. The
+ * per-call device buffers are those of a. n_cells == 0 returns at once. Errors, before any device work: a patch, bin or row
+ * outside its range, thresholds that do not ascend, E > 256, p > q as above: YAWHIP_ERR_INVALID; a handle of another
+ * context: YAWHIP_ERR_MISMATCH.
+ */
+int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                            int32_t n_rows, int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c,
+                            double *fine_w, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

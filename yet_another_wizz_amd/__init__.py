@@ -22,7 +22,8 @@ from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
-                           crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map, crosscorrelate_shear)
+                           correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
+                           crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -51,6 +52,7 @@ __all__ = [
     "autocorrelate",
     "autocorrelate_scalar",
     "autocorrelate_shear",
+    "correlate_shear_tomographic",
     "compute_scalar_normalisation",
     "crosscorrelate",
     "crosscorrelate_scalar",

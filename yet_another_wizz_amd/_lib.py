@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     "yawhip_shear_count",
     "yawhip_shear_upload_binned",
     "yawhip_shear_auto_count",
+    "yawhip_shear_pair_count",
 )
 
 
@@ -275,6 +276,8 @@ def load_library() -> ctypes.CDLL:
                                                _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
     lib.yawhip_shear_auto_count.argtypes = [_vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp, _dp,
                                             ctypes.POINTER(_Stats)]
+    lib.yawhip_shear_pair_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                            _dp, ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -832,6 +835,26 @@ def shear_auto_count(ctx: Context, sources: ShearSources, jobs, thresholds):
     f64[B, E]. Returns ``(P, M, C, W, CountStats)``: the numerators of xi_plus, xi_minus and xi_cross and the weight sums,
     f64[n_jobs, B, E-1] each; a diagonal job holds every unordered pair once."""
     return _shear_counts("yawhip_shear_auto_count", 4, (ctx._h, sources._h), jobs, thresholds)
+
+
+def shear_pair_count(ctx: Context, a: ShearSources, b: ShearSources, cells, thresholds):
+    """Run ``yawhip_shear_pair_count`` on two binned handles (``a is b`` allowed): cells int[n_cells, 5] = ``(p, q, ka, kb, row)``
+    -- segment ``(p, ka)`` of ``a`` against ``(q, kb)`` of ``b``, classified against thresholds row ``row``; thresholds
+    f64[n_rows, E]. Returns ``(P, M, C, W, CountStats)``, f64[n_cells, E-1] each; a cell of one handle with ``ka == kb`` and
+    ``p == q`` holds every unordered pair once."""
+    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 5)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError("thresholds must be [n_rows, n_edges]")
+    n_rows, n_edges = t.shape
+    out = [np.empty((len(cells), max(n_edges - 1, 0)), dtype=np.float64) for _ in range(4)]  # the library writes every element
+    st = _Stats()
+    _check(
+        load_library().yawhip_shear_pair_count(ctx._h, a._h, b._h, len(cells), _ptr(cells, _i32p), n_rows, n_edges, _ptr(t, _dp),
+                                               *(_ptr(o, _dp) for o in out), ctypes.byref(st)),
+        "yawhip_shear_pair_count",
+    )
+    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
 
 
 def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,

@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (tangential shear and shear-shear counts, yawhip_shear_*, include/yawhip.h; DESIGN.md sections
-// 15 and 16): the source handle and what its kernels see of it. Never installed, not part of the C ABI.
+// 15 to 17): the source handle and what its kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -10,7 +10,8 @@
 #pragma GCC visibility push(hidden)  // (its destructor is not an export)
 
 // A shear catalogue resident on its context's device: the objects of every (patch, bin) segment sorted along `axis`; nb == 1
-// (yawhip_shear_upload) is the unbinned catalogue of yawhip_shear_count, nb redshift bins that of yawhip_shear_auto_count.
+// (yawhip_shear_upload) is the unbinned catalogue of yawhip_shear_count, nb redshift bins that of yawhip_shear_auto_count and
+// of yawhip_shear_pair_count.
 struct yawhip_shear_sources {
     yawhip_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -21,8 +22,8 @@ struct yawhip_shear_sources {
     yawhip_detail::DevPtr<double> wg1, wg2;     // w * g1, w * g2, each product rounded on its own (g1, g2 without weights)
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;
-    // per-call buffers of the two counts (grow-only)
-    yawhip_detail::DevBuf<unsigned char> d_in;  // thresholds, window half widths, jobs
+    // per-call buffers of the counts (grow-only; yawhip_shear_pair_count uses those of its first handle)
+    yawhip_detail::DevBuf<unsigned char> d_in;  // thresholds, window half widths, jobs or cells
     yawhip_detail::DevBuf<double> d_out;        // [3 or 4][cells][E-1] sums, then [cells] evaluated pairs (64-bit integers)
 };
 

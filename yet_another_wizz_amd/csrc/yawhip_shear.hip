@@ -1,10 +1,13 @@
-// yawhip_shear.hip -- the two shear counts of a catalogue with (g1, g2): tangential and cross shear of a source catalogue around
-// the lenses of a catalogue binned in redshift (yawhip_shear_count; measurements.crosscorrelate_shear), and
+// yawhip_shear.hip -- the shear counts of a catalogue with (g1, g2): tangential and cross shear of a source catalogue around
+// the lenses of a catalogue binned in redshift (yawhip_shear_count; measurements.crosscorrelate_shear),
 // the shear-shear sums of a source catalogue inside its own redshift bins (yawhip_shear_auto_count;
-// measurements.autocorrelate_shear). include/yawhip.h has both contracts, product by product.
+// measurements.autocorrelate_shear), and the same sums between any two (patch, bin) segments of one or
+// two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic). include/yawhip.h
+// has the contracts, product by product.
 //
-// Both are ONE streaming walk, shear_walk<P>, under two thin entry kernels. One workgroup of 256 threads owns one (job, bin)
-// cell. Lanes hold 256 objects of the cell's lane segment in registers (parked far away where the tile is padded); the cell's
+// All are ONE streaming walk, shear_walk<P>, under three thin entry kernels. One workgroup of 256 threads owns one cell (a
+// (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
+// segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
 // sort key lies within the chord sqrt(t_max) of the tile's keys. The hot loop is the 8-flop separation of k_count,
 //   s2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2,   fine bin e iff t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
@@ -21,6 +24,10 @@
 //   key window         only if both sides are sorted along one axis         always
 //   diagonal cells     none                                                 p == q walks only partners with a LARGER index
 //   pair term, planes  one rotation: T, X, W                                two rotations: P, M, C, W
+//   cell, thresholds   cell = job * n_bins + k, row k                       the same
+// ShearPair (k_count_shear_pair) is ShearShear with two views: segment (p, ka) of handle a streamed, (q, kb) of handle b in the
+// lanes, both and the thresholds row read from the call's cell table; the key window is on iff the two handles are sorted along
+// one axis (Tangential's rule); a cell is diagonal iff it pairs one segment of one handle with itself.
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -80,16 +87,30 @@ __device__ __forceinline__ O load_xyzw(const View &v, int64_t i, bool have) {
     return o;
 }
 
-// The two policies of shear_walk (the table at the head of the file). add() is the pair term: `wh` the wave's histogram
-// [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of include/yawhip.h.
+// What a policy's cell() tells the walk of workgroup `cell`: the streamed segment and the one in the lanes (indices into the
+// two views' offsets), the row of the threshold table, and whether the cell pairs a segment with itself.
+struct Cell {
+    int64_t sseg, lseg;
+    int row;
+    bool diag;
+};
+
+// The three policies of shear_walk (the table at the head of the file). cell() reads the call's table; add() is the pair term:
+// `wh` the wave's histogram [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of
+// include/yawhip.h.
 struct Tangential {
     using View = CatView;  // the streamed side: the lenses
     using Streamed = Obj;
     using Read = Obj;      // the hot loop reads the whole object: two ds_read_b128
     static constexpr int PLANES = 3;  // T, X, W
     static constexpr bool DIAGONAL = false;
-    static __device__ int64_t streamed_segment(const CatView &lens, int64_t p, int k, int) { return p * lens.nb + (lens.nb == 1 ? 0 : k); }
-    static __device__ int64_t lane_segment(int64_t q, int, int) { return q; }
+    // table: jobs [n_jobs][2]; cell = job * n_bins + k, thresholds row k
+    static __device__ Cell cell(const CatView &lens, const int32_t *__restrict__ jobs, int n_bins, int64_t cell) {
+        const int64_t job = cell / n_bins;
+        const int k = (int)(cell - job * n_bins);
+        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+        return Cell{p * lens.nb + (lens.nb == 1 ? 0 : k), q, k, false};
+    }
     // else the keys say nothing about each other: the whole segment
     static __device__ bool windowed(const CatView &lens, const ShearView &src) { return lens.axis == src.axis; }
     static __device__ Obj load(const CatView &lens, int64_t i, bool have) { return load_xyzw<Obj>(lens, i, have); }
@@ -118,8 +139,13 @@ struct ShearShear {
     using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
     static constexpr int PLANES = 4;  // P, M, C, W
     static constexpr bool DIAGONAL = true;
-    static __device__ int64_t streamed_segment(const ShearView &, int64_t p, int k, int nb) { return p * nb + k; }
-    static __device__ int64_t lane_segment(int64_t q, int k, int nb) { return q * nb + k; }
+    // table: jobs [n_jobs][2]; cell = job * nb + k, thresholds row k
+    static __device__ Cell cell(const ShearView &, const int32_t *__restrict__ jobs, int nb, int64_t cell) {
+        const int64_t job = cell / nb;
+        const int k = (int)(cell - job * nb);
+        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+        return Cell{p * nb + k, q * nb + k, k, p == q};
+    }
     static __device__ bool windowed(const ShearView &, const ShearView &) { return true; }  // segments of one handle: one sort axis
     static __device__ Obj6 load(const ShearView &src, int64_t i, bool have) {
         Obj6 o = load_xyzw<Obj6>(src, i, have);
@@ -157,13 +183,25 @@ struct ShearShear {
     }
 };
 
+// ShearShear between any two segments of one or two handles: the pair term and the objects are ShearShear's; the cell comes
+// from a table the host resolved, the key window is Tangential's rule.
+struct ShearPair : ShearShear {
+    // table: [n_cells][4] = (streamed segment of a, lane segment of b, thresholds row, diagonal)
+    static __device__ Cell cell(const ShearView &, const int32_t *__restrict__ cells, int, int64_t cell) {
+        const int32_t *c = cells + 4 * cell;
+        return Cell{c[0], c[1], c[2], c[3] != 0};
+    }
+    static __device__ bool windowed(const ShearView &a, const ShearView &b) { return a.axis == b.axis; }
+};
+
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
 template <class P>
 constexpr size_t lds_bytes(int n_edges) {
     return 2 * STAGE * sizeof(typename P::Streamed) + (size_t)((n_edges + 1) & ~1) * sizeof(double) +
            (size_t)WAVES * P::PLANES * (n_edges - 1) * sizeof(double);
 }
-static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024,
+static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024 &&
+                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024,
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
@@ -189,11 +227,12 @@ __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, con
     }
 }
 
-// The walk of one (job, bin) cell = one workgroup. str: the streamed side, src: the side in the lanes.
+// The walk of one cell = one workgroup. str: the streamed side, src: the side in the lanes; `table` and n_bins are the policy's
+// (P::cell); t: [rows][n_edges], rwin: [rows].
 // out: [PLANES][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
 // diagonal cell that includes the few of a tile's first stage that the index test then drops)
 template <class P>
-__device__ __forceinline__ void shear_walk(const typename P::View &str, const ShearView &src, const int32_t *__restrict__ jobs,
+__device__ __forceinline__ void shear_walk(const typename P::View &str, const ShearView &src, const int32_t *__restrict__ table,
                                            int n_bins, int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
                                            int64_t n_cells, double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     using O = typename P::Streamed;
@@ -206,13 +245,11 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const Sh
     const int tid = threadIdx.x;
     const int nf = n_edges - 1;
     const int64_t cell = blockIdx.x;
-    const int64_t job = cell / n_bins;
-    const int k = (int)(cell - job * n_bins);
-    const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
-    const bool diag = P::DIAGONAL && p == q;
-    const int64_t sseg = P::streamed_segment(str, p, k, n_bins), lseg = P::lane_segment(q, k, n_bins);
-    const int64_t seg0 = str.off[sseg], seg1 = str.off[sseg + 1];  // streamed
-    const int64_t a_beg = src.off[lseg], a_end = src.off[lseg + 1];  // in lanes
+    const Cell c = P::cell(str, table, n_bins, cell);
+    const bool diag = P::DIAGONAL && c.diag;
+    const int k = c.row;
+    const int64_t seg0 = str.off[c.sseg], seg1 = str.off[c.sseg + 1];  // streamed
+    const int64_t a_beg = src.off[c.lseg], a_end = src.off[c.lseg + 1];  // in lanes
 
     for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
     for (int j = tid; j < WAVES * NP * nf; j += WG) hist[j] = 0.0;
@@ -311,8 +348,8 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const Sh
     const int64_t plane = n_cells * nf;
     for (int j = tid; j < NP * nf; j += WG) {  // the four waves' histograms in a fixed order
         const double v = ((hist[j] + hist[NP * nf + j]) + hist[2 * NP * nf + j]) + hist[3 * NP * nf + j];
-        const int c = j / nf;
-        out[(int64_t)c * plane + cell * nf + (j - c * nf)] = v;
+        const int pl = j / nf;
+        out[(int64_t)pl * plane + cell * nf + (j - pl * nf)] = v;
     }
     if (tid == 0) evaluated[cell] = work;
 }
@@ -331,6 +368,14 @@ __global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, 
                                                          int64_t n_cells, double *__restrict__ out,
                                                          unsigned long long *__restrict__ evaluated) {
     shear_walk<ShearShear>(src, src, jobs, nb, n_edges, t, rwin, n_cells, out, evaluated);
+}
+
+// out: [4][n_cells][E-1] (P, M, C, W); cells: [n_cells][4] (ShearPair::cell); a is streamed, b sits in the lanes
+__global__ __launch_bounds__(WG) void k_count_shear_pair(ShearView a, ShearView b, const int32_t *__restrict__ cells, int n_edges,
+                                                         const double *__restrict__ t, const double *__restrict__ rwin,
+                                                         int64_t n_cells, double *__restrict__ out,
+                                                         unsigned long long *__restrict__ evaluated) {
+    shear_walk<ShearPair>(a, b, cells, 0, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -415,14 +460,29 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
     return YAWHIP_OK;
 }
 
-// the argument checks the two counts share (check_call of a count call), before any device work
-int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_patches, int32_t n_bins, int32_t n_edges, const double *t) {
-    for (int k = 0; k < n_bins; ++k)
+// the argument checks the counts share (check_call of a count call), before any device work: the sizes and arrays of a call
+// over n_items jobs or cells (`arrays`: none of them is NULL) ...
+int check_sizes(const char *fn, int32_t n_items, int32_t n_rows, int32_t n_edges, const double *t, bool arrays) {
+    if (n_items < 0 || n_rows <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_items > 0 && !arrays))
+        return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)", fn, n_items, n_rows,
+                    n_edges, MAX_EDGES);
+    return YAWHIP_OK;
+}
+
+// ... the thresholds t[n_rows][n_edges] ...
+int check_thresholds(int32_t n_rows, int32_t n_edges, const double *t) {
+    for (int k = 0; k < n_rows; ++k)
         for (int e = 0; e < n_edges; ++e) {
             const double v = t[(size_t)k * n_edges + e];
             if (!(v >= 0.0) || (e > 0 && !(v >= t[(size_t)k * n_edges + e - 1])))
                 return fail(YAWHIP_ERR_INVALID, "thresholds of bin %d are not ascending non-negative numbers", k);
         }
+    return YAWHIP_OK;
+}
+
+// ... and the job list of the two counts over (job, bin) cells
+int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_patches, int32_t n_bins, int32_t n_edges, const double *t) {
+    if (const int rc = check_thresholds(n_bins, n_edges, t)) return rc;
     for (int j = 0; j < n_jobs; ++j)
         if (jobs[2 * j] < 0 || jobs[2 * j] >= n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= n_patches)
             return fail(YAWHIP_ERR_INVALID, "job %d has a patch id outside [0,%d)", j, n_patches);
@@ -431,18 +491,19 @@ int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_p
 }
 
 
-// What the two counts share once their arguments are checked. One table goes to the handle's d_in (thresholds [B][E], window
-// half widths [B], jobs [n_jobs][2]); launch(jobs, t, rwin, n_cells, out, evaluated) puts the kernel on the stream between the
-// context's two events, writing the result block in d_out (n_planes planes [cells][E-1], then the cells' evaluated
-// separations); the planes come back to fine[], the counters and the event time to the statistics.
+// What the counts share once their arguments are checked. One table goes to the handle's d_in (thresholds [rows][E], window
+// half widths [rows], the policy's table of n_table 32-bit integers: jobs [n_jobs][2] or cells [n_cells][4]);
+// launch(table, t, rwin, n_cells, out, evaluated) puts the kernel on the stream between the context's two events, writing the
+// result block in d_out (n_planes planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[],
+// the counters and the event time to the statistics. n_bins: the rows of t.
 template <class Launch>
-int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
-              int32_t n_edges, const double *t, int n_planes, double *const *fine, int64_t candidates,
+int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, size_t n_table, const int32_t *table, size_t n_cells,
+              int32_t n_bins, int32_t n_edges, const double *t, int n_planes, double *const *fine, int64_t candidates,
               std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Launch launch) {
     if (stats) *stats = yawhip_stats{};
-    if (n_jobs == 0) return YAWHIP_OK;
-    const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + 2 * (size_t)n_jobs * sizeof(int32_t);
-    const size_t n_cells = (size_t)n_jobs * (size_t)n_bins, plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)n_planes * plane;
+    if (n_cells == 0) return YAWHIP_OK;
+    const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + n_table * sizeof(int32_t);
+    const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)n_planes * plane;
     std::vector<unsigned char> h_in;
     std::vector<unsigned long long> h_eval;
     try {
@@ -456,7 +517,7 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, in
     // a pair passes s2 <= t_max only if |du| <= sqrt(t_max) (1 + 2 eps) along any axis u (s2 >= fl(du^2), du rounded once);
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
     for (int k = 0; k < n_bins; ++k) h_rwin[k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-    memcpy(h_rwin + n_bins, jobs, 2 * (size_t)n_jobs * sizeof(int32_t));
+    memcpy(h_rwin + n_bins, table, n_table * sizeof(int32_t));
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
@@ -514,9 +575,7 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
     const char *fn = "yawhip_shear_count";
     const auto wall0 = std::chrono::steady_clock::now();
     if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_jobs > 0 && (!jobs || !fine_t || !fine_x || !fine_w)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
-                    n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
     if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
     if (sources->nb != 1)
         return fail(YAWHIP_ERR_MISMATCH, "yawhip_shear_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
@@ -535,7 +594,7 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
         candidates += n_src * n_lens;
     }
     double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, Tangential::PLANES, fine, candidates, wall0, stats,
+    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, Tangential::PLANES, fine, candidates, wall0, stats,
                      [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
                          unsigned long long *d_eval) {
                          hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes<Tangential>(n_edges), ctx->stream,
@@ -549,10 +608,7 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
     const char *fn = "yawhip_shear_auto_count";
     const auto wall0 = std::chrono::steady_clock::now();
     if (!ctx || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: NULL handle");
-    if (n_jobs < 0 || n_bins <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t ||
-        (n_jobs > 0 && (!jobs || !fine_p || !fine_m || !fine_c || !fine_w)))
-        return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)",
-                    n_jobs, n_bins, n_edges, MAX_EDGES);
+    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_p && fine_m && fine_c && fine_w)) return rc;
     if (sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
     if (sources->nb != n_bins)
         return fail(YAWHIP_ERR_MISMATCH, "source catalogue bin count (%d) does not fit n_bins=%d", sources->nb, n_bins);
@@ -569,11 +625,58 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
             candidates += sp == sq ? n_p * (n_p - 1) / 2 : n_p * n_q;
         }
     double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
-    return run_count(fn, ctx, sources, n_jobs, jobs, n_bins, n_edges, t, ShearShear::PLANES, fine, candidates, wall0, stats,
+    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, ShearShear::PLANES, fine, candidates, wall0, stats,
                      [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
                          unsigned long long *d_eval) {
                          hipLaunchKernelGGL(k_count_shear_auto, dim3((unsigned)n_cells), dim3(WG), lds_bytes<ShearShear>(n_edges), ctx->stream,
                                             view_of(sources), n_bins, d_jobs, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
+                     });
+}
+
+int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                            int32_t n_rows, int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c,
+                            double *fine_w, yawhip_stats *stats) {
+    const char *fn = "yawhip_shear_pair_count";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_pair_count: NULL handle");
+    if (const int rc = check_sizes(fn, n_cells, n_rows, n_edges, t, cells && fine_p && fine_m && fine_c && fine_w)) return rc;
+    if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if ((int64_t)a->n_patches * a->nb > INT32_MAX || (int64_t)b->n_patches * b->nb > INT32_MAX)
+        return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
+    if (const int rc = check_thresholds(n_rows, n_edges, t)) return rc;
+
+    // the kernel's table: (streamed segment of a, lane segment of b, thresholds row, diagonal) per cell
+    std::vector<int32_t> table;
+    try {
+        table.resize(4 * (size_t)n_cells);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
+    for (int c = 0; c < n_cells; ++c) {
+        const int32_t *cell = cells + 5 * (size_t)c;
+        const int32_t p = cell[0], q = cell[1], ka = cell[2], kb = cell[3], row = cell[4];
+        if (p < 0 || p >= a->n_patches || q < 0 || q >= b->n_patches)
+            return fail(YAWHIP_ERR_INVALID, "cell %d has a patch id outside [0,%d) x [0,%d)", c, a->n_patches, b->n_patches);
+        if (ka < 0 || ka >= a->nb || kb < 0 || kb >= b->nb)
+            return fail(YAWHIP_ERR_INVALID, "cell %d has a redshift bin outside [0,%d) x [0,%d)", c, a->nb, b->nb);
+        if (row < 0 || row >= n_rows) return fail(YAWHIP_ERR_INVALID, "cell %d has a thresholds row outside [0,%d)", c, n_rows);
+        if (a == b && ka == kb && p > q)
+            return fail(YAWHIP_ERR_INVALID, "cell %d = (%d, %d) inside bin %d of one handle: such a cell has p <= q", c, p, q, ka);
+        const size_t sa = (size_t)p * a->nb + ka, sb = (size_t)q * b->nb + kb;
+        const bool diag = a == b && sa == sb;
+        const int64_t n_a = a->h_off[sa + 1] - a->h_off[sa], n_b = b->h_off[sb + 1] - b->h_off[sb];
+        candidates += diag ? n_a * (n_a - 1) / 2 : n_a * n_b;
+        int32_t *entry = &table[4 * (size_t)c];
+        entry[0] = (int32_t)sa, entry[1] = (int32_t)sb, entry[2] = row, entry[3] = diag;
+    }
+    double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
+    return run_count(fn, ctx, a, table.size(), table.data(), (size_t)n_cells, n_rows, n_edges, t, ShearPair::PLANES, fine, candidates,
+                     wall0, stats,
+                     [&](const int32_t *d_cells, const double *d_t, const double *d_rwin, int64_t cells_n, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_shear_pair, dim3((unsigned)cells_n), dim3(WG), lds_bytes<ShearPair>(n_edges), ctx->stream,
+                                            view_of(a), view_of(b), d_cells, n_edges, d_t, d_rwin, cells_n, d_out, d_eval);
                      });
 }
 

@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -194,6 +194,20 @@ def count_shear_auto_fine(layout, jobs, thresholds, *, sort_axis: int = 2):
         raise ValueError("catalog has no 'g1'/'g2' attached")
     ctx = get_context()
     return _lib.shear_auto_count(ctx, _shear_sources(layout, ctx, sort_axis), jobs, thresholds)
+
+
+def count_shear_pair_fine(layout_a, layout_b, cells, thresholds, *, sort_axis: int = 2):
+    """Fine-bin shear-shear sums between (patch, bin) segments of one or two catalogues for ``cells`` (int[n, 5] =
+    ``(p, q, ka, kb, row)``: segment ``(p, ka)`` of ``layout_a`` against ``(q, kb)`` of ``layout_b``, thresholds row ``row``) ->
+    ``(P, M, C, W, CountStats)``, f64[n_cells, E-1] each (``yawhip_shear_pair_count``). Both are binned layouts with ``g1`` /
+    ``g2``, resident as for ``count_shear_auto_fine``; the same layout twice is ONE handle passed twice, and only then a cell
+    with ``p == q`` and ``ka == kb`` holds every unordered pair once. No CPU fallback; the CPU tests replace this function."""
+    if any(layout.g1 is None or layout.g2 is None for layout in (layout_a, layout_b)):
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    ctx = get_context()
+    a = _shear_sources(layout_a, ctx, sort_axis)
+    b = a if layout_b is layout_a else _shear_sources(layout_b, ctx, sort_axis)
+    return _lib.shear_pair_count(ctx, a, b, cells, thresholds)
 
 
 def _shear_sources(layout, ctx, sort_axis):

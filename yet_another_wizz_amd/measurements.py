@@ -25,7 +25,7 @@ from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
 __all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
-           "crosscorrelate_shear", "autocorrelate_shear", "compute_scalar_normalisation",
+           "crosscorrelate_shear", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -518,6 +518,76 @@ class PatchLinkage:
                       for num in (P, M, C))
                 for s in range(len(W))]
 
+    def count_shear_tomographic_pairs(self, sources: Catalog, sources2: Catalog | None = None, *, bin_pairs=None,
+                                      progress: bool = False, max_workers: int | None = None,
+                                      count_type_info: str | None = None) -> list:
+        """Shear-shear sums between redshift bin ``i`` of ``sources`` and bin ``j`` of ``sources2`` (of ``sources`` itself when
+        it is left out), both binned with ``g1`` / ``g2`` (``build_trees(edges, with_shear=True)``) -> per scale a list of
+        ``B`` rows, row ``i`` = ``(NormalisedScalarCounts(P, W), NormalisedScalarCounts(M, W), NormalisedScalarCounts(C, W))``
+        whose ``B`` bins run over ``j``; the pair term is that of ``count_shear_auto_pairs``.
+
+        ``bin_pairs`` lists the ``(i, j)`` to count: all ``i <= j`` of one catalogue (only those are accepted), all ``B * B``
+        ordered pairs of two. Pair ``(i, i)`` of one catalogue runs over the linked patch pairs ``p <= q`` and its diagonal
+        slots hold every unordered pair once, exactly what ``count_shear_auto_pairs`` stores; every other pair runs over all
+        linked ``(p, q)`` in both orders, since the two bins differ. For one catalogue slot ``j < i`` of row ``i`` is the
+        mirror of slot ``i`` of row ``j``, the patch axes transposed. Slots not asked for hold zeros.
+
+        A pair is classified against the thresholds of bin ``min(i, j)``: for physical scales the angle is evaluated at the
+        middle of the NEARER of the two bins (for angular scales every bin has the same). Separation weights and per-scale
+        sums are ``CombinePlan``'s over those plans. ONE library call counts all cells (``engine.count_shear_pair_fine``),
+        on one device of one process: several ranks raise ``NotImplementedError`` (``max_workers`` has no effect)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("shear counts run in one process on one device")
+        if count_type_info is not None:
+            _log_info("counting %s from patch pairs", count_type_info)
+        one = sources2 is None
+        binning = self.config.binning.binning
+        num_bins, num_patches, num_scales = len(binning), len(sources), self.config.scales.num_scales
+        layouts = [_active_layout(cat, num_bins) for cat in ((sources,) if one else (sources, sources2))]
+        for layout in layouts:
+            if layout.g1 is None or layout.g2 is None:
+                raise ValueError("catalog has no 'g1'/'g2' attached")
+            if layout.num_bins != num_bins:
+                raise ValueError("shear-shear counts need the sources binned in redshift")
+        if bin_pairs is None:
+            bin_pairs = [(i, j) for i in range(num_bins) for j in range(i if one else 0, num_bins)]
+        bin_pairs = list(dict.fromkeys((int(i), int(j)) for i, j in bin_pairs))
+        for i, j in bin_pairs:
+            if not (0 <= i < num_bins and 0 <= j < num_bins):
+                raise ValueError(f"bin pair ({i}, {j}) is outside the {num_bins} redshift bins")
+            if one and i > j:
+                raise ValueError(f"bin pair ({i}, {j}): the pairs of one catalogue are given with i <= j")
+        plans, thresholds = self._angular_setup()
+        # the job list of a pair: p <= q inside one bin of one catalogue, every linked (p, q) otherwise
+        job_lists = [self.get_patch_pairs(sources) if one and i == j else self.get_patch_pairs(sources, sources if one else sources2)
+                     for i, j in bin_pairs]
+        cells = np.concatenate([np.column_stack([jobs, np.full(len(jobs), i), np.full(len(jobs), j), np.full(len(jobs), min(i, j))])
+                                for (i, j), jobs in zip(bin_pairs, job_lists)] or [np.empty((0, 5))]).astype(np.int32)
+        *fine, stats = engine.count_shear_pair_fine(layouts[0], layouts[-1], cells, thresholds, sort_axis=self.sort_axis)
+        self.last_stats = stats
+        self._report(count_type_info, len(cells), stats, progress)
+
+        planes = np.zeros((4, num_scales, num_bins, num_bins, num_patches, num_patches))  # [plane, S, i, j, p, q]
+        first = np.cumsum([0] + [len(jobs) for jobs in job_lists])
+        for same_bin in (True, False):  # the two job lists: pairs of each kind are combined in one pass
+            group = [n for n, (i, j) in enumerate(bin_pairs) if (one and i == j) == same_bin]
+            if not group:
+                continue
+            combine = CombinePlan([plans[min(bin_pairs[n])] for n in group])
+            jobs = job_lists[group[0]]
+            i_of, j_of = (np.array([bin_pairs[n][c] for n in group])[:, np.newaxis] for c in (0, 1))
+            for plane, f in zip(planes, fine):
+                fine_bej = np.stack([f[first[n]:first[n + 1]].T for n in group])  # [pairs, E-1, jobs]
+                per_scale = combine(fine_bej)  # [S, pairs, jobs]
+                plane[:, i_of, j_of, jobs[:, 0], jobs[:, 1]] = per_scale
+                if one and not same_bin:
+                    plane[:, j_of, i_of, jobs[:, 1], jobs[:, 0]] = per_scale
+        P, M, C, W = planes
+        return [[tuple(NormalisedScalarCounts(PatchedCounts(binning, num[s, i], auto=False), PatchedCounts(binning, W[s, i], auto=False))
+                       for num in (P, M, C))
+                 for i in range(num_bins)]
+                for s in range(num_scales)]
+
     def _count_shear_planes(self, catalogs, layouts, count_type_info, progress):
         """What the two shear counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the engine's
         count (``count_shear_fine`` / ``count_shear_auto_fine``, looked up at call time: the CPU tests replace them) with the
@@ -789,3 +859,38 @@ def autocorrelate_shear(config, sources: Catalog, *, linkage: PatchLinkage | Non
     links = linkage if linkage is not None else PatchLinkage.from_catalogs(config, sources)
     DD = links.count_shear_auto_pairs(sources, count_type_info="DD", progress=progress, max_workers=max_workers)
     return [tuple(ScalarCorrFunc(dd) for dd in triple) for triple in DD]
+
+
+def correlate_shear_tomographic(config, sources: Catalog, sources2: Catalog | None = None, *, bin_pairs=None,
+                                linkage: PatchLinkage | None = None, progress: bool = False,
+                                max_workers: int | None = None) -> list:
+    """The tomographic matrix of shear-shear correlations: ``xi_plus^{ij}``, ``xi_minus^{ij}`` and the parity-odd
+    ``xi_cross^{ij}`` between redshift bin ``i`` of ``sources`` and bin ``j`` of ``sources2`` -- another shape sample, another
+    survey, the other half of a null test -- or, without ``sources2``, between the bins of ``sources`` itself. Both are
+    catalogues with ``g1`` / ``g2`` and redshifts; the pair term is ``autocorrelate_shear``'s. Returns, per scale, a list of
+    ``B`` rows; row ``i`` is ``(ScalarCorrFunc(dd_plus), ScalarCorrFunc(dd_minus), ScalarCorrFunc(dd_cross))`` on the
+    configuration's binning, whose bins run over ``j``.
+
+    ``bin_pairs=[(i, j), ...]`` restricts the pairs: the default is every ``i <= j`` of one catalogue (``i > j`` is refused:
+    it is the same signal) and all ``B * B`` ordered pairs of two. Slots not asked for hold zero counts and sample to NaN. For
+    one catalogue slot ``(i, i)`` holds exactly what ``autocorrelate_shear`` stores for bin ``i``, and slot ``j < i`` of row
+    ``i`` mirrors slot ``i`` of row ``j`` with the patch axes transposed.
+
+    Scales: the pairs of ``(i, j)`` are binned with the limits of bin ``min(i, j)``. For angular units every bin has the same
+    limits; for physical units this is a convention -- the scale is turned into an angle at the middle of the nearer bin.
+
+    This driver has no counterpart in the reference and needs no randoms. Patches, scales and jackknife are
+    ``autocorrelate``'s (``crosscorrelate``'s checks for two catalogues: distinct objects, consistent patches); ``linkage``
+    may pass a prepared ``PatchLinkage``; the count runs on one device of one process."""
+    catalogs = (sources,) if sources2 is None else (sources, sources2)
+    _require_distinct(*catalogs)
+    if not all(cat.has_shear for cat in catalogs):
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    _log_info("building source trees")
+    for cat in catalogs:
+        cat.build_trees(config.binning.edges, closed=config.binning.closed, with_shear=True)
+    _log_info("computing tomographic shear correlation with DD")
+    links = linkage if linkage is not None else PatchLinkage.from_catalogs(config, *catalogs)
+    DD = links.count_shear_tomographic_pairs(sources, sources2, bin_pairs=bin_pairs, count_type_info="DD", progress=progress,
+                                             max_workers=max_workers)
+    return [[tuple(ScalarCorrFunc(dd) for dd in triple) for triple in rows] for rows in DD]
