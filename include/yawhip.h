@@ -602,6 +602,67 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
                             int32_t n_rows, int32_t n_edges, const double *t, double *fine_p, double *fine_m, double *fine_c,
                             double *fine_w, yawhip_stats *stats);
 
+/*
+ * Excess surface density sums of a source catalogue around the lenses of a catalogue binned in redshift: tangential and
+ * cross shear with the per-pair factor Sigma_crit^-1 (z_l, z_s), which is zero for a source in front of its lens
+ * (measurements.crosscorrelate_delta_sigma; no counterpart in the reference). Additive to ABI 6: new symbols only, the
+ * opaque handle is yawhip_shear_sources.
+ *
+ * The library is unit-free. For a flat cosmology Sigma_crit^-1 = (4 pi G / c^2) D_A(z_l) max(0, 1 - chi_l / chi_s); the caller
+ * passes three extra columns, every entry a finite number >= 0 (else YAWHIP_ERR_INVALID):
+ *   lenses:   f (the driver passes D_A(z_l) in Mpc) and c (chi_l in Mpc)
+ *   sources:  u (1 / chi_s in 1/Mpc; u = 0 is a source at infinity)
+ *
+ * yawhip_dsigma_upload_lenses    the lenses as a handle MARKED as lenses: n_bins segments per patch (offsets
+ *                       int64[n_patches * n_bins + 1]), every segment sorted along sort_axis and gathered as
+ *                       yawhip_shear_upload_binned does; it keeps x, y, z, w (NULL: every weight 1.0) and f, c AS THEY CAME
+ *                       (no product with w). Only yawhip_dsigma_count takes it: yawhip_shear_count, yawhip_shear_auto_count
+ *                       and yawhip_shear_pair_count refuse it (YAWHIP_ERR_MISMATCH).
+ * yawhip_dsigma_upload_sources   yawhip_shear_upload (unbinned: offsets int64[n_patches + 1]) with the extra column u. The
+ *                       three shear counts accept the handle and ignore u.
+ * Both are freed by yawhip_shear_free.
+ * yawhip_dsigma_count   for every job (lens patch p, source patch q) and redshift bin k, over the pairs (lens l of segment
+ *                       (p, k) -- (p, 0) when the lenses have one bin --, source s of patch q). Pair membership is the
+ *                       predicate of every count, bit for bit: t[k][e] < s2 <= t[k][e + 1]. The rotation and the den == 0
+ *                       rule are yawhip_shear_count's, operation by operation:
+ *       a = x ly - y lx,  rho2 = x x + y y,  b = rho2 lz - z (x lx + y ly),  den = a a + b b     (x, y, z: the source)
+ *       c2 = (a a - b b) / den,  s2p = (2 a b) / den
+ *       tv = -((w_s g1) c2 + (w_s g2) s2p)      xv = (w_s g1) s2p - (w_s g2) c2
+ *     A pair in fine bin e then adds, in float64 with every product and sum rounded on its own and nothing contracted
+ *     (1 - c u is a multiply and a subtract, never an FMA):
+ *       eff = 1.0 - c_l u_s
+ *       if eff > 0.0:                       otherwise the pair adds NOTHING, not to fine_w either
+ *           s  = f_l eff
+ *           ws = w_l s
+ *           fine_t += ws tv                 (den == 0: fine_t and fine_x skipped, fine_w still added)
+ *           fine_x += ws xv
+ *           fine_w += (ws s) w_s
+ *     With f = 1, c = 0 and any u every operation reduces to that of yawhip_shear_count: the call returns its bits.
+ *     fine_t / fine_w summed over cells is sum(w_l w_s S gamma_t) / sum(w_l w_s S^2) with S = f (1 - c u): Delta Sigma up to the
+ *     constant c^2 / (4 pi G) of the caller's units.
+ *   lenses       a handle of yawhip_dsigma_upload_lenses with n_bins equal to 1 or the call's n_bins
+ *   sources      a handle of yawhip_dsigma_upload_sources
+ *   jobs, t, fine_t, fine_x, fine_w, stats    shapes and meaning as for yawhip_shear_count; every element is written, a cell
+ *                without pairs is exactly 0
+ * Kernel, accumulation and reproducibility as yawhip_shear_count: the same streaming walk with the lens segment (48-byte
+ * objects x, y, z, w, f, c) going through LDS and the sources with u in the lanes, one float64 LDS histogram per wave, plain
+ * stores, no floating-point atomics on global memory; the sort-key window is used iff both handles are sorted along the same
+ * axis and knows nothing of the three columns: the evaluated separations are those of yawhip_shear_count on the same
+ * catalogues. The per-call device buffers are those of the sources. Errors, before any device work: the checks of
+ * yawhip_shear_count (sizes, thresholds, jobs outside the patches: YAWHIP_ERR_INVALID; handles of another context, unequal
+ * patch counts, a lens bin count that is neither 1 nor n_bins: YAWHIP_ERR_MISMATCH); a lens handle given as sources, a source
+ * handle without u, or a handle that is not marked as lenses given as lenses: YAWHIP_ERR_MISMATCH.
+ */
+int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                const double *f, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                                int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                 const double *g1, const double *g2, const double *u, int32_t n_patches, const int64_t *offsets,
+                                 int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                        const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
+                        double *fine_w, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
-                           crosscorrelate_shear)
+                           crosscorrelate_delta_sigma, crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -57,6 +57,7 @@ __all__ = [
     "crosscorrelate",
     "crosscorrelate_scalar",
     "crosscorrelate_scalar_map",
+    "crosscorrelate_delta_sigma",
     "crosscorrelate_shear",
     "healpix",
     "patches",

@@ -63,6 +63,9 @@ ABI_SYMBOLS = (
     "yawhip_shear_upload_binned",
     "yawhip_shear_auto_count",
     "yawhip_shear_pair_count",
+    "yawhip_dsigma_upload_lenses",
+    "yawhip_dsigma_upload_sources",
+    "yawhip_dsigma_count",
 )
 
 
@@ -278,6 +281,12 @@ def load_library() -> ctypes.CDLL:
                                             ctypes.POINTER(_Stats)]
     lib.yawhip_shear_pair_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
                                             _dp, ctypes.POINTER(_Stats)]
+    lib.yawhip_dsigma_upload_lenses.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32,
+                                                _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
+    lib.yawhip_dsigma_upload_sources.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, _i64p,
+                                                 ctypes.c_int32, ctypes.POINTER(_vp)]
+    lib.yawhip_dsigma_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                        ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -769,22 +778,30 @@ class ShearSources:
     """``yawhip_shear_sources``: a shear catalogue resident in HBM, every (patch, bin) segment sorted along ``sort_axis`` -- unit
     vectors, weights (or None) and the shear components ``g1, g2`` (east / north frame, include/yawhip.h); ``offsets``
     int64[P * n_bins + 1] over the segments. ``n_bins = 1`` is the unbinned catalogue ``shear_count`` takes
-    (``yawhip_shear_upload``), more the binned one of ``shear_auto_count`` (``yawhip_shear_upload_binned``)."""
+    (``yawhip_shear_upload``), more the binned one of ``shear_auto_count`` (``yawhip_shear_upload_binned``). ``u`` (unbinned
+    handles only) is the extra column ``dsigma_count`` reads, finite and ``>= 0`` (``yawhip_dsigma_upload_sources``); the
+    shear counts take such a handle and ignore the column."""
 
-    def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2, n_bins: int = 1):
+    def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2, n_bins: int = 1, u=None):
         self._h = _vp()
-        x, y, z, w, g1, g2 = (_f64(c) for c in (x, y, z, w, g1, g2))
+        x, y, z, w, g1, g2, u = (_f64(c) for c in (x, y, z, w, g1, g2, u))
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(x)
-        if any(c is not None and len(c) != n for c in (y, z, w, g1, g2)):
+        if any(c is not None and len(c) != n for c in (y, z, w, g1, g2, u)):
             raise ValueError("catalogue columns differ in length")
         if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
             raise ValueError("offsets must have n_patches * n_bins + 1 entries")
+        if u is not None and n_bins != 1:
+            raise ValueError("the column 'u' goes with an unbinned catalogue")
         self.ctx = ctx  # keep the context alive
         self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
         self.n_bins = int(n_bins)
         columns = (ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(g1, _dp), _ptr(g2, _dp), self.n_patches)
-        if self.n_bins == 1:
+        if u is not None:
+            _check(load_library().yawhip_dsigma_upload_sources(*columns[:-1], _ptr(u, _dp), self.n_patches, _ptr(offsets, _i64p),
+                                                               self.sort_axis, ctypes.byref(self._h)),
+                   "yawhip_dsigma_upload_sources")
+        elif self.n_bins == 1:
             _check(load_library().yawhip_shear_upload(*columns, _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
                    "yawhip_shear_upload")
         else:
@@ -803,6 +820,31 @@ class ShearSources:
             self.free()
         except Exception:
             pass
+
+
+class DsigmaLenses(ShearSources):
+    """The lenses of ``dsigma_count`` resident in HBM (``yawhip_dsigma_upload_lenses``): every (patch, bin) segment sorted along
+    ``sort_axis`` -- unit vectors, weights (or None) and the two columns ``f, c`` (include/yawhip.h: ``D_A(z_l)`` and ``chi_l``
+    in the driver), finite and ``>= 0``, kept as they come. The handle is a ``yawhip_shear_sources`` marked as lenses: it is
+    freed like one, and the shear counts refuse it."""
+
+    def __init__(self, ctx: Context, x, y, z, w, f, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2):
+        self._h = _vp()
+        x, y, z, w, f, c = (_f64(col) for col in (x, y, z, w, f, c))
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(x)
+        if any(col is not None and len(col) != n for col in (y, z, w, f, c)):
+            raise ValueError("catalogue columns differ in length")
+        if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
+            raise ValueError("offsets must have n_patches * n_bins + 1 entries")
+        self.ctx = ctx  # keep the context alive
+        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
+        self.n_bins = int(n_bins)
+        _check(load_library().yawhip_dsigma_upload_lenses(ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp),
+                                                          _ptr(f, _dp), _ptr(c, _dp), self.n_patches, self.n_bins,
+                                                          _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
+               "yawhip_dsigma_upload_lenses")
+        ctx._shear.add(self)
 
 
 def _shear_counts(symbol: str, n_planes: int, handles, jobs, thresholds):
@@ -828,6 +870,13 @@ def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs
     """Run ``yawhip_shear_count``: jobs int[n_jobs, 2] = (lens patch, source patch); thresholds f64[B, E]. Returns
     ``(T, X, W, CountStats)``: the tangential, cross and weight sums, f64[n_jobs, B, E-1] each."""
     return _shear_counts("yawhip_shear_count", 3, (ctx._h, lenses._h, sources._h), jobs, thresholds)
+
+
+def dsigma_count(ctx: Context, lenses: DsigmaLenses, sources: ShearSources, jobs, thresholds):
+    """Run ``yawhip_dsigma_count``: ``lenses`` a ``DsigmaLenses``, ``sources`` a ``ShearSources`` with ``u``; jobs int[n_jobs, 2] =
+    (lens patch, source patch); thresholds f64[B, E]. Returns ``(T, X, W, CountStats)``, f64[n_jobs, B, E-1] each: the sums of
+    ``w_l w_s S gamma_t``, ``w_l w_s S gamma_x`` and ``w_l w_s S^2`` over the pairs with ``S = f (1 - c u) > 0``."""
+    return _shear_counts("yawhip_dsigma_count", 3, (ctx._h, lenses._h, sources._h), jobs, thresholds)
 
 
 def shear_auto_count(ctx: Context, sources: ShearSources, jobs, thresholds):

@@ -253,10 +253,12 @@ class PatchLayout:
     the binning are dropped (:414), an unbinned catalogue has one segment per patch (:400-404)."""
 
     __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent", "kappa", "twin", "g1", "g2",
-                 "shear_device")
+                 "shear_device", "redshifts", "dsigma_device")
 
-    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None, g1=None, g2=None) -> None:
+    def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None, g1=None, g2=None, redshifts=None) -> None:
         self.x, self.y, self.z, self.w = x, y, z, w
+        self.redshifts = redshifts  # the objects' redshifts in the layout's order (build_trees(with_redshifts=True)), or None
+        self.dsigma_device = {}  # (Context id, role) -> (handle of engine.count_dsigma_fine, the cosmology of its columns)
         self.g1, self.g2 = g1, g2  # shear columns in the layout's order (unbinned layouts, and build_trees(with_shear=True)), or None
         self.shear_device = {}  # Context id -> ShearSources
         self.kappa = kappa  # scalar-field column in the layout's order, or None
@@ -745,32 +747,39 @@ class Catalog(Mapping):
         return self._xyz
 
     def build_trees(self, binning=None, *, closed=Closed.right, leafsize: int = 16, force: bool = False,
-                    progress: bool = False, max_workers: int | None = None, with_shear: bool = False) -> PatchLayout:
+                    progress: bool = False, max_workers: int | None = None, with_shear: bool = False,
+                    with_redshifts: bool = False) -> PatchLayout:
         """Prepare (and cache) the (patch, bin)-sorted layout for ``binning`` (array of edges or
         ``None``).  Keeps the name and arguments of ``yaw.Catalog.build_trees`` (catalog.py:1406-1461);
         no tree is built -- ``leafsize`` is accepted and ignored. ``with_shear`` (no counterpart in the reference) makes a
         binned layout carry ``g1`` / ``g2``, grouped with the other columns, for ``autocorrelate_shear``: a layout of its own
-        in the cache, next to the plain one of the same binning; the unbinned layout always carries them."""
+        in the cache, next to the plain one of the same binning; the unbinned layout always carries them. ``with_redshifts``
+        (no counterpart either) makes the layout, binned or not, carry the objects' redshifts in its order
+        (``PatchLayout.redshifts``) for ``crosscorrelate_delta_sigma``: again a layout of its own in the cache."""
         bins = None if binning is None else (binning if isinstance(binning, Binning) else Binning(binning, closed=closed))
         if with_shear and not self.has_shear:
             raise ValueError("catalog has no 'g1'/'g2' attached")
-        if bins is not None and not self.has_redshifts:
+        if (bins is not None or with_redshifts) and not self.has_redshifts:
             raise ValueError("patch has no 'redshifts' attached")  # trees.py:396-397
         key = None if bins is None else (bins.edges.tobytes(), str(bins.closed), *(("shear",) if with_shear else ()))
+        if with_redshifts:
+            key = (*(key or ()), "redshifts")
         if not force and key in self._layouts:
             self._active_layout = self._layouts[key]
             return self._active_layout
         x, y, z = self._unit_vectors()
         num_patches = self.num_patches
         if bins is None:
-            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1, kappa=self._k, g1=self._g1, g2=self._g2)
+            layout = PatchLayout(x, y, z, self._w, self._patch_off.copy(), num_patches, 1, kappa=self._k, g1=self._g1, g2=self._g2,
+                                 redshifts=self._z if with_redshifts else None)
         else:
             num_bins = len(bins)
             bin_idx = bins.assign(self._z)
             patch_of = np.repeat(np.arange(num_patches), np.diff(self._patch_off))
             offsets = np.zeros(num_patches * num_bins + 1, dtype=np.int64)
             shear = (self._g1, self._g2) if with_shear else ()
-            columns = [x, y, z] + [c for c in (self._w, self._k, *shear) if c is not None]  # kappa is binned (and dropped) as the rest
+            extra = (*shear, *((self._z,) if with_redshifts else ()))
+            columns = [x, y, z] + [c for c in (self._w, self._k, *extra) if c is not None]  # kappa is binned (and dropped) as the rest
             grouped = False
             if len(x) >= HOST_GROUP_MIN:  # (patch, bin) grouping in one threaded pass; objects outside the binning dropped
                 from . import _lib
@@ -791,7 +800,8 @@ class Catalog(Mapping):
             rest = iter(columns[3:])
             layout = PatchLayout(columns[0], columns[1], columns[2], None if self._w is None else next(rest), offsets,
                                  num_patches, num_bins, kappa=None if self._k is None else next(rest),
-                                 g1=next(rest) if with_shear else None, g2=next(rest) if with_shear else None)
+                                 g1=next(rest) if with_shear else None, g2=next(rest) if with_shear else None,
+                                 redshifts=next(rest) if with_redshifts else None)
         self._layouts[key] = layout
         self._active_layout = layout  # what the next count_pairs() uses, like the cached trees.pkl
         return layout
@@ -808,5 +818,8 @@ class Catalog(Mapping):
             for src in layout.shear_device.values():
                 src.free()
             layout.shear_device.clear()
+            for src, *_ in layout.dsigma_device.values():
+                src.free()
+            layout.dsigma_device.clear()
         self._layouts.clear()
         self._active_layout = None

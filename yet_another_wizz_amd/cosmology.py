@@ -25,9 +25,16 @@ __all__ = [
     "new_scales",
     "get_default_cosmology",
     "RedshiftBinningFactory",
+    "distance_column",
+    "DELTA_SIGMA_UNIT",
 ]
 
 C_KM_S = 299792.458
+MPC_M = 3.085677581491367e22  # one Mpc in metres
+GM_SUN = 1.32712440018e20     # the Sun's gravitational parameter G M_sun, m^3 s^-2
+# c^2 Mpc / (4 pi G M_sun) 1e-12: Sigma_crit = DELTA_SIGMA_UNIT / (D_A(z_l) (1 - chi_l / chi_s)) in M_sun / pc^2 for distances in
+# Mpc (a flat cosmology), about 1.6629e6 M_sun / pc^2 per Mpc^-1 -- the factor of ``crosscorrelate_delta_sigma``
+DELTA_SIGMA_UNIT = (C_KM_S * 1e3) ** 2 * MPC_M / (4.0 * np.pi * GM_SUN) * 1e-12
 
 
 class CustomCosmology(ABC):
@@ -121,6 +128,21 @@ def cosmology_is_equal(a, b) -> bool:
 
 def _as_mpc(value):
     return getattr(value, "value", value)  # tolerate astropy Quantity
+
+
+def distance_column(cosmology, redshifts, *, kind: str = "comoving", chunksize: int = 1 << 16):
+    """``comoving_distance(z)`` (``kind="comoving"``) or ``angular_diameter_distance(z)`` (``"angular"``) in Mpc for a whole
+    column of redshifts, float64[n]: the cosmology itself is called, object by object, ``chunksize`` redshifts at a time (no
+    interpolation table; ``FlatLCDM`` integrates every redshift with 64 nodes, so a chunk bounds its work array). A custom
+    cosmology is used as given; ``crosscorrelate_delta_sigma`` takes its line-of-sight comoving distance for the transverse
+    one, i.e. assumes that it is flat."""
+    method = dict(comoving="comoving_distance", angular="angular_diameter_distance")[kind]
+    z = np.ascontiguousarray(redshifts, dtype=np.float64)
+    out = np.empty(len(z), dtype=np.float64)
+    evaluate = getattr(cosmology or get_default_cosmology(), method)
+    for lo in range(0, len(z), chunksize):
+        out[lo : lo + chunksize] = np.asarray(_as_mpc(evaluate(z[lo : lo + chunksize])), dtype=np.float64)
+    return out
 
 
 class Scales:

@@ -1,5 +1,6 @@
-// Private to yawhip_shear.hip (tangential shear and shear-shear counts, yawhip_shear_*, include/yawhip.h; DESIGN.md sections
-// 15 to 17): the source handle and what its kernels see of it. Never installed, not part of the C ABI.
+// Private to yawhip_shear.hip (tangential shear, shear-shear and excess-surface-density counts, yawhip_shear_* and
+// yawhip_dsigma_*, include/yawhip.h; DESIGN.md sections 15 to 18): the source handle and what its kernels see of it. Never
+// installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -11,7 +12,9 @@
 
 // A shear catalogue resident on its context's device: the objects of every (patch, bin) segment sorted along `axis`; nb == 1
 // (yawhip_shear_upload) is the unbinned catalogue of yawhip_shear_count, nb redshift bins that of yawhip_shear_auto_count and
-// of yawhip_shear_pair_count.
+// of yawhip_shear_pair_count. A handle of yawhip_dsigma_upload_sources is an unbinned one with the column u besides; one of
+// yawhip_dsigma_upload_lenses (`lenses`) holds the lens columns f, c, as they came, in the place of wg1, wg2: only
+// yawhip_dsigma_count takes it.
 struct yawhip_shear_sources {
     yawhip_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -20,6 +23,8 @@ struct yawhip_shear_sources {
     int axis = 2;                               // coordinate the patch segments are sorted by (0 = x, 1 = y, 2 = z)
     yawhip_detail::DevPtr<double> x, y, z, w;   // w may be null (every weight 1.0)
     yawhip_detail::DevPtr<double> wg1, wg2;     // w * g1, w * g2, each product rounded on its own (g1, g2 without weights)
+    yawhip_detail::DevPtr<double> u;            // the sources' column of yawhip_dsigma_count, or null
+    bool lenses = false;                        // a lens handle: wg1, wg2 hold f, c
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;
     // per-call buffers of the counts (grow-only; yawhip_shear_pair_count uses those of its first handle)
@@ -35,6 +40,14 @@ struct ShearView {
     const int64_t *off;           // [P * nb + 1]
     const double *key;            // the column the segments are sorted by
     int axis;
+};
+
+struct LensView : ShearView {  // a lens handle streamed by yawhip_dsigma_count: wg1, wg2 are f, c
+    int nb;
+};
+
+struct SourceView : ShearView {  // the sources of yawhip_dsigma_count in the lanes
+    const double *u;
 };
 
 }  // namespace yawhip_detail

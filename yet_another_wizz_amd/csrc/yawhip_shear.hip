@@ -2,10 +2,11 @@
 // the lenses of a catalogue binned in redshift (yawhip_shear_count; measurements.crosscorrelate_shear),
 // the shear-shear sums of a source catalogue inside its own redshift bins (yawhip_shear_auto_count;
 // measurements.autocorrelate_shear), and the same sums between any two (patch, bin) segments of one or
-// two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic). include/yawhip.h
-// has the contracts, product by product.
+// two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic), and the excess
+// surface density sums of sources with a distance column around lenses with two (yawhip_dsigma_count;
+// measurements.crosscorrelate_delta_sigma). include/yawhip.h has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under three thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under four thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -16,7 +17,8 @@
 // of ONE instruction to one cell are serialised by the LDS in a fixed lane order); the four are folded in a fixed order and
 // stored with plain stores, every element written. No floating-point atomic touches global memory. All indices are 64-bit.
 //
-// What differs is a policy P, resolved at compile time -- no branch of it is in the streaming loop:
+// What differs is a policy P, resolved at compile time -- no branch of it is in the streaming loop (the side in the lanes,
+// P::Lanes, is a ShearView, for DeltaSigma one with the column u):
 //                      Tangential (k_count_shear)                           ShearShear (k_count_shear_auto)
 //   streamed segment   lens.off[p * nb + (nb == 1 ? 0 : k)] of a CatView    off[p * nb + k] of the one ShearView
 //   lane segment       off[q] of the unbinned sources                       off[q * nb + k] of the same handle
@@ -28,6 +30,9 @@
 // ShearPair (k_count_shear_pair) is ShearShear with two views: segment (p, ka) of handle a streamed, (q, kb) of handle b in the
 // lanes, both and the thresholds row read from the call's cell table; the key window is on iff the two handles are sorted along
 // one axis (Tangential's rule); a cell is diagonal iff it pairs one segment of one handle with itself.
+// DeltaSigma (k_count_dsigma) is Tangential with the lenses as a handle of their own: the streamed object is an Obj6
+// (x, y, z, w, f, c), the lane carries the source's u besides, and the pair term is Tangential's rotation scaled by the pair's
+// s = f (1 - c u), dropped altogether where 1 - c u <= 0 (the source in front of its lens).
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -37,6 +42,10 @@
 //   T += w_l * -(wg1 c2 + wg2 s2p)     X += w_l * (wg1 s2p - wg2 c2)     W += w_l * w_s        (wg = w_s g, made at upload)
 // den == 0 (the source sits on a pole of the frame): W only.
 //
+// DeltaSigma, the same rotation (c2, s2p), tv = -(wg1 c2 + wg2 s2p), xv = wg1 s2p - wg2 c2:
+//   eff = 1 - c_l u_s;   eff > 0:   s = f_l eff,   ws = w_l s,   T += ws tv,   X += ws xv,   W += (ws s) w_s
+// eff <= 0: the pair adds nothing, not to W either. den == 0: W only.
+//
 // Shear-shear, objects a, b of the same redshift bin k of ONE handle, both shears rotated to the great circle that joins the
 // two -- each end by its own position angle:
 //   pa = ax by - ay bx,  dot = ax bx + ay by,  pbA = (ax ax + ay ay) bz - az dot,  pbB = (bx bx + by by) az - bz dot
@@ -44,7 +53,9 @@
 //   P += tA tB + xA xB    M += tA tB - xA xB    C += tA xB + xA tB    W += w_a w_b        (a den == 0: W only)
 // Every term is bit-symmetric under swapping a and b, so it does not matter which of the two a lane holds.
 //
-//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products.
+//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products (a lens
+//                    handle keeps its two columns f, c as they came).
+//   k_gather_column  the same gather of the sources' column u.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -74,8 +85,8 @@ struct alignas(16) Obj6 {  // one streamed object of the shear-shear count: thre
     double x, y, z, w, g1, g2;  // (g1, g2: the weighted shear wg1, wg2 of the handle)
 };
 
-struct Lane {  // what a lane keeps of its own object in registers (g1, g2: the weighted shear)
-    double x, y, z, w, g1, g2, rho2;
+struct Lane {  // what a lane keeps of its own object in registers (g1, g2: the weighted shear; u: DeltaSigma's column, else 0)
+    double x, y, z, w, g1, g2, rho2, u;
 };
 
 // x, y, z, w of streamed object i of a CatView or a ShearView; beyond the window (!have) an object nobody reads
@@ -95,13 +106,14 @@ struct Cell {
     bool diag;
 };
 
-// The three policies of shear_walk (the table at the head of the file). cell() reads the call's table; add() is the pair term:
+// The policies of shear_walk (the table at the head of the file). cell() reads the call's table; add() is the pair term:
 // `wh` the wave's histogram [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of
 // include/yawhip.h.
 struct Tangential {
     using View = CatView;  // the streamed side: the lenses
     using Streamed = Obj;
     using Read = Obj;      // the hot loop reads the whole object: two ds_read_b128
+    using Lanes = ShearView;  // the side in the lanes: the sources
     static constexpr int PLANES = 3;  // T, X, W
     static constexpr bool DIAGONAL = false;
     // table: jobs [n_jobs][2]; cell = job * n_bins + k, thresholds row k
@@ -114,6 +126,7 @@ struct Tangential {
     // else the keys say nothing about each other: the whole segment
     static __device__ bool windowed(const CatView &lens, const ShearView &src) { return lens.axis == src.axis; }
     static __device__ Obj load(const CatView &lens, int64_t i, bool have) { return load_xyzw<Obj>(lens, i, have); }
+    static __device__ double lane_u(const ShearView &, int64_t, bool) { return 0.0; }  // no such column: nothing is loaded
     static __device__ void add(const Lane &a, const Obj &b, double *wh, int e, int nf) {
         const double pa = a.x * b.y - a.y * b.x;
         const double dot = a.x * b.x + a.y * b.y;
@@ -137,6 +150,7 @@ struct ShearShear {
     using View = ShearView;  // the streamed side: the handle itself
     using Streamed = Obj6;
     using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
+    using Lanes = ShearView;
     static constexpr int PLANES = 4;  // P, M, C, W
     static constexpr bool DIAGONAL = true;
     // table: jobs [n_jobs][2]; cell = job * nb + k, thresholds row k
@@ -152,6 +166,7 @@ struct ShearShear {
         o.g1 = have ? src.wg1[i] : 0.0; o.g2 = have ? src.wg2[i] : 0.0;
         return o;
     }
+    static __device__ double lane_u(const ShearView &, int64_t, bool) { return 0.0; }
     static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf) {
         const double bx = b.x, by = b.y, bz = b.z;
         const double pa = a.x * by - a.y * bx;
@@ -194,6 +209,49 @@ struct ShearPair : ShearShear {
     static __device__ bool windowed(const ShearView &a, const ShearView &b) { return a.axis == b.axis; }
 };
 
+// Tangential around the lenses of a lens handle (its columns wg1, wg2 hold f, c as they came), the sources with their column u.
+struct DeltaSigma {
+    using View = LensView;  // the streamed side: the lens handle, a ShearView with its bin count
+    using Streamed = Obj6;  // (x, y, z, w, f, c)
+    using Read = const Obj6 &;  // the hot loop reads x, y, z; w, f, c behind the ballot (ShearShear's reads)
+    using Lanes = SourceView;
+    static constexpr int PLANES = 3;  // T, X, W
+    static constexpr bool DIAGONAL = false;
+    // table: jobs [n_jobs][2]; cell = job * n_bins + k, thresholds row k (Tangential's)
+    static __device__ Cell cell(const LensView &lens, const int32_t *__restrict__ jobs, int n_bins, int64_t cell) {
+        const int64_t job = cell / n_bins;
+        const int k = (int)(cell - job * n_bins);
+        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+        return Cell{p * lens.nb + (lens.nb == 1 ? 0 : k), q, k, false};
+    }
+    static __device__ bool windowed(const LensView &lens, const SourceView &src) { return lens.axis == src.axis; }
+    static __device__ Obj6 load(const LensView &lens, int64_t i, bool have) { return ShearShear::load(lens, i, have); }
+    static __device__ double lane_u(const SourceView &src, int64_t i, bool ok) { return ok ? src.u[i] : 0.0; }
+    static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf) {
+        const double eff = 1.0 - b.g2 * a.u;  // 1 - c_l u_s: a product and a difference, each rounded (-ffp-contract=off)
+        if (eff > 0.0) {  // else the source is not behind its lens: nothing, not to W either
+            const double s = b.g1 * eff;
+            const double ws = b.w * s;
+            const double bx = b.x, by = b.y;
+            const double pa = a.x * by - a.y * bx;
+            const double dot = a.x * bx + a.y * by;
+            const double pb = a.rho2 * b.z - a.z * dot;
+            const double a2 = pa * pa;
+            const double b2 = pb * pb;
+            const double den = a2 + b2;
+            if (den != 0.0) {
+                const double c2 = (a2 - b2) / den;
+                const double s2 = ((2.0 * pa) * pb) / den;
+                const double tv = -(a.g1 * c2 + a.g2 * s2);
+                const double xv = a.g1 * s2 - a.g2 * c2;
+                atomicAdd(&wh[e], ws * tv);
+                atomicAdd(&wh[nf + e], ws * xv);
+            }
+            atomicAdd(&wh[2 * nf + e], (ws * s) * a.w);
+        }
+    }
+};
+
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
 template <class P>
 constexpr size_t lds_bytes(int n_edges) {
@@ -201,14 +259,14 @@ constexpr size_t lds_bytes(int n_edges) {
            (size_t)WAVES * P::PLANES * (n_edges - 1) * sizeof(double);
 }
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024 &&
-                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024,
+                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024 && lds_bytes<DeltaSigma>(MAX_EDGES) <= 64 * 1024,
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
                                const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
                                const double *__restrict__ sg1, const double *__restrict__ sg2, double *__restrict__ x,
                                double *__restrict__ y, double *__restrict__ z, double *__restrict__ w, double *__restrict__ wg1,
-                               double *__restrict__ wg2) {
+                               double *__restrict__ wg2, bool products) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t j = perm[i];
@@ -219,12 +277,17 @@ __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, con
     if (sw) {
         const double wj = sw[j];
         w[i] = wj;
-        wg1[i] = wj * g1;
-        wg2[i] = wj * g2;
+        wg1[i] = products ? wj * g1 : g1;
+        wg2[i] = products ? wj * g2 : g2;
     } else {
         wg1[i] = g1;
         wg2[i] = g2;
     }
+}
+
+__global__ void k_gather_column(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ src, double *__restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[perm[i]];
 }
 
 // The walk of one cell = one workgroup. str: the streamed side, src: the side in the lanes; `table` and n_bins are the policy's
@@ -232,7 +295,7 @@ __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, con
 // out: [PLANES][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
 // diagonal cell that includes the few of a tile's first stage that the index test then drops)
 template <class P>
-__device__ __forceinline__ void shear_walk(const typename P::View &str, const ShearView &src, const int32_t *__restrict__ table,
+__device__ __forceinline__ void shear_walk(const typename P::View &str, const typename P::Lanes &src, const int32_t *__restrict__ table,
                                            int n_bins, int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
                                            int64_t n_cells, double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     using O = typename P::Streamed;
@@ -294,7 +357,7 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const Sh
         const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
         const double ag1 = ok ? src.wg1[ia] : 0.0;
         const double ag2 = ok ? src.wg2[ia] : 0.0;
-        const Lane a{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay};
+        const Lane a{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay, P::lane_u(src, ia, ok)};
         // a diagonal cell counts the streamed object i of a stage only for lanes with ia < its index: i > ia - (first of stage)
         const int64_t lane_rel = diag ? ia - b0 : (int64_t)-1 - (int64_t)STAGE;
 
@@ -378,6 +441,14 @@ __global__ __launch_bounds__(WG) void k_count_shear_pair(ShearView a, ShearView 
     shear_walk<ShearPair>(a, b, cells, 0, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
+// out: [3][n_cells][E-1] (T, X, W)
+__global__ __launch_bounds__(WG) void k_count_dsigma(LensView lens, SourceView src, const int32_t *__restrict__ jobs, int n_bins,
+                                                     int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
+                                                     int64_t n_cells, double *__restrict__ out,
+                                                     unsigned long long *__restrict__ evaluated) {
+    shear_walk<DeltaSigma>(lens, src, jobs, n_bins, n_edges, t, rwin, n_cells, out, evaluated);
+}
+
 }  // namespace
 
 extern "C" {
@@ -396,11 +467,12 @@ int yawhip_shear_free(yawhip_shear_sources *src) {
 
 namespace {
 
-// the upload of both entry points: n_bins segments per patch (1: the unbinned catalogue of yawhip_shear_upload), each sorted
-// along sort_axis and gathered
+// the upload of every entry point: n_bins segments per patch (1: the unbinned catalogue of yawhip_shear_upload), each sorted
+// along sort_axis and gathered. u: the extra column of yawhip_dsigma_upload_sources or NULL; lenses: a lens handle, whose
+// (g1, g2) = (f, c) are gathered without the weight
 int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                     const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets, int32_t sort_axis,
-                    yawhip_shear_sources **out) {
+                    yawhip_shear_sources **out, const double *u = nullptr, bool lenses = false) {
     if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
     *out = nullptr;
     if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
@@ -420,6 +492,7 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
     s->n_patches = n_patches;
     s->nb = n_bins;
     s->axis = sort_axis;
+    s->lenses = lenses;
     try {
         s->h_off.assign(offsets, offsets + n_seg + 1);
     } catch (const std::bad_alloc &) {
@@ -427,18 +500,20 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
-    DevPtr<double> raw[6];  // x, y, z, g1, g2, w as they came (temporary)
-    const double *host[6] = {x, y, z, g1, g2, w};
+    constexpr int NC = 7;
+    DevPtr<double> raw[NC];  // x, y, z, g1, g2, w, u as they came (temporary)
+    const double *host[NC] = {x, y, z, g1, g2, w, u};
     DevPtr<uint32_t> perm;
     hipError_t e = hipSuccess;
     for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
         if (e == hipSuccess) e = c->alloc(n1);
     if (e == hipSuccess && w) e = s->w.alloc(n1);
+    if (e == hipSuccess && u) e = s->u.alloc(n1);
     if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
-    for (int c = 0; c < 6; ++c)
+    for (int c = 0; c < NC; ++c)
         if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
     if (e == hipSuccess) e = perm.alloc(n1);
-    for (int c = 0; c < 6; ++c)
+    for (int c = 0; c < NC; ++c)
         if (e == hipSuccess && host[c] && n > 0) e = hipMemcpyAsync(raw[c], host[c], col, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(s->off, offsets, ((size_t)n_seg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
@@ -446,7 +521,11 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
         e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_seg, perm);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
-                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2);
+                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2, !lenses);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && u) {
+            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], s->u);
             e = hipGetLastError();
         }
     }
@@ -553,6 +632,21 @@ ShearView view_of(const yawhip_shear_sources *s) {
     return ShearView{s->x, s->y, s->z, s->w, s->wg1, s->wg2, s->off, key_of(s->x, s->y, s->z, s->axis), s->axis};
 }
 
+// the three shear counts take shear handles only
+int refuse_lenses(const char *fn, const yawhip_shear_sources *s) {
+    if (s->lenses) return fail(YAWHIP_ERR_MISMATCH, "%s: a lens handle of yawhip_dsigma_upload_lenses is not a shear catalogue", fn);
+    return YAWHIP_OK;
+}
+
+// the extra columns of yawhip_dsigma_count: finite and >= 0
+int check_column(const char *fn, const char *name, int64_t n, const double *v) {
+    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
+    for (int64_t i = 0; i < n; ++i)
+        if (!(v[i] >= 0.0) || std::isinf(v[i]))
+            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number >= 0 (index %lld)", fn, name, (long long)i);
+    return YAWHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -577,6 +671,7 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
     if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
     if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
     if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (const int rc = refuse_lenses(fn, sources)) return rc;
     if (sources->nb != 1)
         return fail(YAWHIP_ERR_MISMATCH, "yawhip_shear_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
     if (lenses->n_patches != sources->n_patches)
@@ -610,6 +705,7 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
     if (!ctx || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: NULL handle");
     if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_p && fine_m && fine_c && fine_w)) return rc;
     if (sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (const int rc = refuse_lenses(fn, sources)) return rc;
     if (sources->nb != n_bins)
         return fail(YAWHIP_ERR_MISMATCH, "source catalogue bin count (%d) does not fit n_bins=%d", sources->nb, n_bins);
     if (const int rc = check_count(fn, n_jobs, jobs, sources->n_patches, n_bins, n_edges, t)) return rc;
@@ -641,6 +737,8 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
     if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_pair_count: NULL handle");
     if (const int rc = check_sizes(fn, n_cells, n_rows, n_edges, t, cells && fine_p && fine_m && fine_c && fine_w)) return rc;
     if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (const int rc = refuse_lenses(fn, a)) return rc;
+    if (const int rc = refuse_lenses(fn, b)) return rc;
     if ((int64_t)a->n_patches * a->nb > INT32_MAX || (int64_t)b->n_patches * b->nb > INT32_MAX)
         return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
     if (const int rc = check_thresholds(n_rows, n_edges, t)) return rc;
@@ -677,6 +775,67 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
                          unsigned long long *d_eval) {
                          hipLaunchKernelGGL(k_count_shear_pair, dim3((unsigned)cells_n), dim3(WG), lds_bytes<ShearPair>(n_edges), ctx->stream,
                                             view_of(a), view_of(b), d_cells, n_edges, d_t, d_rwin, cells_n, d_out, d_eval);
+                     });
+}
+
+int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                const double *f, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                                int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_lenses";
+    if (out) *out = nullptr;
+    if (n > 0) {
+        if (const int rc = check_column(fn, "f", n, f)) return rc;
+        if (const int rc = check_column(fn, "c", n, c)) return rc;
+    }
+    return upload_segments(fn, ctx, n, x, y, z, w, f, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true);
+}
+
+int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                 const double *g1, const double *g2, const double *u, int32_t n_patches, const int64_t *offsets,
+                                 int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_sources";
+    if (out) *out = nullptr;
+    static const double none = 0.0;  // (n == 0: the handle still carries a column u)
+    if (n > 0) {
+        if (const int rc = check_column(fn, "u", n, u)) return rc;
+    }
+    return upload_segments(fn, ctx, n, x, y, z, w, g1, g2, n_patches, 1, offsets, sort_axis, out, n > 0 ? u : &none, false);
+}
+
+int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                        const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
+                        double *fine_w, yawhip_stats *stats) {
+    const char *fn = "yawhip_dsigma_count";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_dsigma_count: NULL handle");
+    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
+    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (!lenses->lenses) return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the lenses are not a handle of yawhip_dsigma_upload_lenses");
+    if (sources->lenses || !sources->u)
+        return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the sources are not a handle of yawhip_dsigma_upload_sources");
+    if (sources->nb != 1)
+        return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
+    if (lenses->n_patches != sources->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
+    if (lenses->nb != 1 && lenses->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
+
+    int64_t candidates = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
+        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
+        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
+                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
+        candidates += n_src * n_lens;
+    }
+    double *const fine[] = {fine_t, fine_x, fine_w};
+    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, DeltaSigma::PLANES, fine, candidates, wall0, stats,
+                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_dsigma, dim3((unsigned)n_cells), dim3(WG), lds_bytes<DeltaSigma>(n_edges), ctx->stream,
+                                            LensView{view_of(lenses), lenses->nb}, SourceView{view_of(sources), sources->u}, d_jobs, n_bins,
+                                            n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
                      });
 }
 

@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -208,6 +208,77 @@ def count_shear_pair_fine(layout_a, layout_b, cells, thresholds, *, sort_axis: i
     a = _shear_sources(layout_a, ctx, sort_axis)
     b = a if layout_b is layout_a else _shear_sources(layout_b, ctx, sort_axis)
     return _lib.shear_pair_count(ctx, a, b, cells, thresholds)
+
+
+def dsigma_columns(lens_layout, source_layout, cosmology):
+    """The three columns ``yawhip_dsigma_count`` reads (include/yawhip.h), from the layouts' redshifts
+    (``build_trees(with_redshifts=True)``) and ``cosmology`` (assumed flat): ``(f, c, u)`` = ``D_A(z_l)`` and ``chi(z_l)`` of
+    the lenses and ``1 / chi(z_s)`` of the sources, Mpc and 1/Mpc, each in its layout's order. Redshifts must be finite and
+    ``>= 0``, the distances finite, and a source needs ``chi_s > 0`` (``ValueError`` otherwise). A side given as ``None`` is
+    skipped (``None`` in its place)."""
+    from .cosmology import distance_column
+
+    def redshifts(layout, what):
+        z = layout.redshifts
+        if z is None:
+            raise ValueError(f"the {what} carry no redshifts: build_trees(..., with_redshifts=True)")
+        if not (np.all(np.isfinite(z)) and np.all(z >= 0.0)):
+            raise ValueError(f"the redshifts of the {what} must be finite and >= 0")
+        return z
+
+    f = c = u = None
+    if lens_layout is not None:
+        z = redshifts(lens_layout, "lenses")
+        f, c = distance_column(cosmology, z, kind="angular"), distance_column(cosmology, z, kind="comoving")
+        if not (np.all(np.isfinite(f)) and np.all(f >= 0.0) and np.all(np.isfinite(c)) and np.all(c >= 0.0)):
+            raise ValueError("the cosmology gives lens distances that are not finite numbers >= 0")
+    if source_layout is not None:
+        chi = distance_column(cosmology, redshifts(source_layout, "sources"), kind="comoving")
+        if not (np.all(np.isfinite(chi)) and np.all(chi > 0.0)):
+            raise ValueError("a source needs a finite comoving distance > 0 (a redshift > 0)")
+        u = 1.0 / chi
+    return f, c, u
+
+
+def count_dsigma_fine(lens_layout, source_layout, jobs, thresholds, *, cosmology, sort_axis: int = 2):
+    """Fine-bin excess-surface-density sums for ``jobs`` (int[n, 2] = (lens patch, source patch)) -> ``(T, X, W, CountStats)``,
+    f64[n_jobs, B, E-1] each: the sums of ``w_l w_s S gamma_t``, ``w_l w_s S gamma_x`` and ``w_l w_s S^2`` over the pairs with
+    ``S = D_A(z_l) (1 - chi_l / chi_s) > 0`` in Mpc (``yawhip_dsigma_count``; ``dsigma_columns`` makes the three columns).
+    Both layouts carry redshifts (``build_trees(..., with_redshifts=True)``), the sources ``g1`` / ``g2`` besides and no
+    bins. Each reaches the device once per context as a handle kept on the layout (``_lib.DsigmaLenses``, ``_lib.ShearSources``
+    with ``u``), replaced when another sort axis or another cosmology is asked for. On a context of several devices the count
+    runs on its first one. No CPU fallback; the CPU tests replace this function."""
+    if source_layout.g1 is None or source_layout.g2 is None:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    if source_layout.num_bins != 1:
+        raise ValueError("the sources of an excess-surface-density count are not binned in redshift")
+    ctx = get_context()
+
+    def lenses():
+        f, c, _ = dsigma_columns(lens_layout, None, cosmology)
+        return _lib.DsigmaLenses(ctx, lens_layout.x, lens_layout.y, lens_layout.z, lens_layout.w, f, c, lens_layout.num_patches,
+                                 lens_layout.num_bins, lens_layout.offsets, sort_axis=sort_axis)
+
+    def sources():
+        u = dsigma_columns(None, source_layout, cosmology)[2]
+        return _lib.ShearSources(ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1,
+                                 source_layout.g2, source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis, u=u)
+
+    return _lib.dsigma_count(ctx, _dsigma_handle(lens_layout, ctx, sort_axis, cosmology, "lenses", lenses),
+                             _dsigma_handle(source_layout, ctx, sort_axis, cosmology, "sources", sources), jobs, thresholds)
+
+
+def _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload):
+    """The resident handle of ``layout`` in ``role`` ("lenses" / "sources") on ``ctx``, uploaded on first use."""
+    from .cosmology import cosmology_is_equal
+
+    held = layout.dsigma_device.get((id(ctx), role))
+    if held is not None and (held[0].sort_axis != sort_axis or not held[0]._h or not cosmology_is_equal(held[1], cosmology)):
+        held[0].free()
+        held = None
+    if held is None:
+        held = layout.dsigma_device[(id(ctx), role)] = (upload(), cosmology)
+    return held[0]
 
 
 def _shear_sources(layout, ctx, sort_axis):

@@ -21,11 +21,12 @@ from .angular_bins import plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
 from .corrfunc import CorrFunc, ScalarCorrFunc
+from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
 __all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
-           "crosscorrelate_shear", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
+           "crosscorrelate_shear", "crosscorrelate_delta_sigma", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -496,6 +497,31 @@ class PatchLinkage:
                  NormalisedScalarCounts(PatchedCounts(binning, X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
                 for s in range(len(W))]
 
+    def count_dsigma_pairs(self, lenses: Catalog, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
+                           count_type_info: str | None = None) -> list:
+        """Excess surface density of ``sources`` (unbinned, with ``g1`` / ``g2`` and redshifts) around ``lenses`` (binned, with
+        redshifts), both laid out by ``build_trees(..., with_redshifts=True)``, over the linked patch pairs -> per scale
+        ``(NormalisedScalarCounts(K T, W), NormalisedScalarCounts(K X, W))``: the sums of ``w_l w_s S gamma_t`` and
+        ``w_l w_s S gamma_x`` over the pairs with the source behind its lens, times ``K = cosmology.DELTA_SIGMA_UNIT``, each
+        over the sum of ``w_l w_s S^2``, ``S = D_A(z_l) (1 - chi_l / chi_s)`` in Mpc from the configuration's cosmology: the
+        ratio is Delta Sigma in M_sun / pc^2. Everything else is ``count_shear_pairs``'; ONE library call counts all jobs
+        (``engine.count_dsigma_fine``)."""
+        import functools
+
+        def layouts(num_bins):
+            lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
+            if source_layout.g1 is None or source_layout.g2 is None:
+                raise ValueError("catalog has no 'g1'/'g2' attached")
+            if lens_layout.redshifts is None or source_layout.redshifts is None or source_layout.num_bins != 1:
+                raise ValueError("excess surface density needs layouts with redshifts and unbinned sources: "
+                                 "build_trees(..., with_redshifts=True)")
+            return functools.partial(engine.count_dsigma_fine, cosmology=self.config.cosmology), (lens_layout, source_layout)
+
+        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress)
+        return [(NormalisedScalarCounts(PatchedCounts(binning, DELTA_SIGMA_UNIT * T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
+                 NormalisedScalarCounts(PatchedCounts(binning, DELTA_SIGMA_UNIT * X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
+                for s in range(len(W))]
+
     def count_shear_auto_pairs(self, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
                                count_type_info: str | None = None) -> list:
         """Shear-shear sums of ``sources`` (binned in redshift with ``g1`` / ``g2``: ``build_trees(edges, with_shear=True)``)
@@ -836,6 +862,58 @@ def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_ra
     DD = links.count_shear_pairs(reference, sources, count_type_info="DD", **kwargs)
     DR = links.count_shear_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
     return [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
+
+
+def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, ref_rand: Catalog | None = None,
+                               boost: bool = False, progress: bool = False, max_workers: int | None = None) -> list:
+    """Excess surface density of the matter around ``reference`` in its redshift slices, from ``sources`` with ``g1`` / ``g2``
+    and point redshifts: per redshift bin and scale
+
+        Delta Sigma (R) = sum_ls w_l w_s Sigma_c^-1 gamma_t / sum_ls w_l w_s Sigma_c^-2      in M_sun / pc^2 (physical),
+
+    ``Sigma_c^-1 (z_l, z_s) = (4 pi G / c^2) D_A(z_l) max(0, 1 - chi_l / chi_s)`` evaluated per PAIR from the two redshifts
+    with the configuration's cosmology, which is assumed flat (a custom one is used as given): a source in front of its lens
+    adds nothing. The cross component is the null test. Minus the same ratio around the lenses of ``ref_rand`` when it is
+    given -> ``[(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)), ...]``, one tuple per scale, ``dr = None`` without
+    randoms: the shape of ``crosscorrelate_shear``, whose frame, rotation and pair selection these are. With physical scales
+    (``unit="kpc"``) the limits are turned into an angle per lens slice, as everywhere.
+
+    ``boost=True`` (needs ``ref_rand``) adds a third item per scale, a plain ``CorrFunc(dd, dr)`` whose counts are the
+    denominators ``sum w_l w_s Sigma_c^-2`` of DD and DR, already counted, each normalised by the lens weight sums per
+    (patch, bin) times the sources' patch totals as ``crosscorrelate`` normalises its counts: ``cf_boost.sample()`` is the
+    boost factor minus one, ``B(R) - 1``, with its jackknife samples -- the excess of sources around real lenses over random
+    ones, i.e. the dilution of the signal by sources that belong to the lens.
+
+    This driver has no counterpart in the reference. Linkage, scales, patches and jackknife are ``crosscorrelate``'s; the
+    count runs on one device of one process."""
+    _require_distinct(reference, sources, ref_rand)
+    if not sources.has_shear:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    if not sources.has_redshifts:
+        raise ValueError("excess surface density needs source redshifts: the sources have no 'redshifts' attached")
+    if boost and ref_rand is None:
+        raise ValueError("the boost factor needs random lenses: give 'ref_rand'")
+    edges, closed = config.binning.edges, config.binning.closed
+    randoms = []
+    _log_info("building reference data trees")
+    lens_layouts = [reference.build_trees(edges, closed=closed, with_redshifts=True)]
+    if ref_rand is not None:
+        lens_layouts.append(ref_rand.build_trees(edges, closed=closed, with_redshifts=True))
+        randoms.append(ref_rand)
+    source_layout = sources.build_trees(None, with_redshifts=True)
+    _log_info("computing excess surface density with DD" + (", DR" if randoms else ""))
+    links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
+    kwargs = dict(progress=progress, max_workers=max_workers)
+    DD = links.count_dsigma_pairs(reference, sources, count_type_info="DD", **kwargs)
+    DR = links.count_dsigma_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
+    result = [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
+    if boost:  # the W planes of the two counts over the products of the weight sums: (DD - DR) / DR
+        binning, num_bins = config.binning.binning, len(config.binning.binning)
+        norms = [PatchedSumWeights(binning, layout.sum_weights_for(num_bins), source_layout.sum_weights_for(num_bins), auto=False)
+                 for layout in lens_layouts]
+        result = [(cf_t, cf_x, CorrFunc(NormalisedCounts(dd_t.number_counts, norms[0]), NormalisedCounts(dr_t.number_counts, norms[1])))
+                  for (cf_t, cf_x), (dd_t, _), (dr_t, _) in zip(result, DD, DR)]
+    return result
 
 
 def autocorrelate_shear(config, sources: Catalog, *, linkage: PatchLinkage | None = None, progress: bool = False,
