@@ -3,7 +3,7 @@ the numpy brute force of tests/dsigma_oracle.py, on the scene of tests/test_gpu_
 
 The rule for the signed sums is that of the shear count: per (job, bin, fine bin) cell ``|T - T_o| <= 1e-10 * A`` and the same
 for ``X``, with ``A = sum |w_l w_s| s (|g1| + |g2|)`` over the cell's pairs with the source behind its lens (the factor ``s`` is one
-more float64 product per pair: ~1e-16 relative, and no test goes below 0.5 arcmin, where the projection's error is ~1e-12);
+more float64 product per pair: ~1e-16 relative, and no test of this file goes below 0.5 arcmin -- tests/test_gpu_shear_exact.py does --, where the projection's error is ~1e-12);
 a cell without such pairs must be exactly 0. ``W`` is held to ``helpers.RTOL_W``. Every test prints its worst ``|delta| / A``."""
 import functools
 import types

@@ -1,0 +1,347 @@
+"""GPU: the four shear entry points (``shear_count``, ``dsigma_count``, ``shear_auto_count``, ``shear_pair_count``) on job lists
+of the size a measurement sends -- 150 patches, two redshift bins, every patch pair in one call -- against the numpy oracles
+with the rules of their own suites (``1e-10 * A``, ``RTOL_W``, exact zeros): the question here is the bookkeeping of
+``run_count`` and of the policies' ``cell()``, not the arithmetic. What only runs at this scale: result blocks
+``[planes][n_cells][E-1]`` of tens of thousands of cells with the evaluated counters behind them, most cells without a single
+object; the grow-only call buffers of a handle through calls of other sizes; ``nb == 1`` lenses folded under many rows of
+thresholds; handles without any object."""
+import functools
+
+import numpy as np
+import pytest
+
+import dsigma_oracle
+import shear_auto_oracle
+import shear_oracle
+import shear_pair_oracle
+import test_gpu_shear
+import test_gpu_shear_auto
+from conftest import ARCMIN
+from yet_another_wizz_amd import _lib, engine
+from yet_another_wizz_amd.catalog import radec_to_xyz
+
+pytestmark = pytest.mark.gpu
+P, NB, GRID_X, GRID_Y = 150, 2, 15, 10
+BOX_DEG = 2.0
+SMALL = np.array([(16, 16), (16, 17), (17, 16), (31, 16), (32, 32), (0, 149)], dtype=np.int32)  # six jobs for the empty handles
+
+
+def freeze(arrays):
+    for a in arrays:
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return arrays
+
+
+def chord2(arcmin):
+    return (2.0 * np.sin(0.5 * np.asarray(arcmin, dtype=np.float64) * ARCMIN)) ** 2
+
+
+def thresholds(n_rows=NB):
+    """f64[n_rows, 5]: 0.5 to 15 arcmin and other limits in every row; a patch is 8 x 12 arcmin, so neighbouring patches pair."""
+    return chord2([np.geomspace(0.5 * (1.0 + 0.1 * k), 15.0 * (1.0 - 0.04 * k), 5) for k in range(n_rows)])
+
+
+def draw_positions(rng, n_bins):
+    """0 to 3 objects in every patch (a cell of the 15 x 10 grid over the 2-degree box), none in the first and the last, each in
+    any of ``n_bins`` redshift bins -> (ra, dec) ordered by (patch, bin) and the offsets int64[P * n_bins + 1]."""
+    sizes = rng.integers(0, 4, P)
+    sizes[[0, P - 1]] = 0
+    patch = np.repeat(np.arange(P), sizes)
+    bins = rng.integers(0, n_bins, len(patch))
+    order = np.argsort(patch * n_bins + bins, kind="stable")
+    patch, bins = patch[order], bins[order]
+    ra = (100.0 + (patch % GRID_X + rng.uniform(0.0, 1.0, len(patch))) * BOX_DEG / GRID_X) * np.pi / 180.0
+    dec = (30.0 + (patch // GRID_X + rng.uniform(0.0, 1.0, len(patch))) * BOX_DEG / GRID_Y) * np.pi / 180.0
+    off = np.concatenate([[0], np.cumsum(np.bincount(patch * n_bins + bins, minlength=P * n_bins))]).astype(np.int64)
+    return ra, dec, off
+
+
+def shear_catalogue(rng, n_bins):
+    ra, dec, off = draw_positions(rng, n_bins)
+    x, y, z = radec_to_xyz(ra, dec)
+    n = len(x)
+    return dict(x=x, y=y, z=z, w=rng.uniform(0.5, 2.0, n), g1=rng.normal(0, 0.3, n), g2=rng.normal(0, 0.3, n), nb=n_bins, off=off)
+
+
+@functools.lru_cache(maxsize=None)
+def scene():
+    """``(lenses, sources, catalogue, second catalogue)``: lenses in two bins with the columns ``f, c``, unbinned sources with
+    ``u`` (about half the pairs have the source in front), and two shear catalogues in two bins on the same patches."""
+    rng = np.random.default_rng(20261)
+    ra, dec, off = draw_positions(rng, NB)
+    x, y, z = radec_to_xyz(ra, dec)
+    c = rng.uniform(600.0, 2500.0, len(x))
+    lens = dict(x=x, y=y, z=z, w=rng.uniform(0.5, 2.0, len(x)), f=c / rng.uniform(1.2, 1.9, len(x)), c=c, nb=NB, off=off)
+    src = shear_catalogue(rng, 1)
+    src = dict({k: v for k, v in src.items() if k != "nb"}, u=1.0 / rng.uniform(600.0, 2500.0, len(src["x"])))
+    cats = (lens, src, shear_catalogue(rng, NB), shear_catalogue(rng, NB))
+    for cat in cats:
+        assert cat["off"][1] == 0 and cat["off"][-2] == cat["off"][-1] and len(cat["x"]) > 150  # first and last patch empty
+        freeze(cat.values())
+    return cats
+
+
+def all_jobs():
+    return np.array([(p, q) for p in range(P) for q in range(P)], dtype=np.int32)
+
+
+def auto_jobs():
+    return np.array([(p, q) for p in range(P) for q in range(p, P)], dtype=np.int32)
+
+
+def neighbours(reach=2):
+    """Ordered patch pairs at most ``reach`` grid cells apart in either direction."""
+    p = np.arange(P)
+    near = (np.abs(p[:, None] % GRID_X - p[None, :] % GRID_X) <= reach) & (np.abs(p[:, None] // GRID_X - p[None, :] // GRID_X) <= reach)
+    return np.argwhere(near).astype(np.int32)
+
+
+def pair_cells(one_handle):
+    """Cells ``(p, q, ka, kb, row)`` over the neighbouring patch pairs: inside both bins with the row of the bin (one handle:
+    ``p <= q`` only), across the bins with alternating rows, and 600 cells of far patches that hold nothing."""
+    near = neighbours()
+    same = [(p, q, k, k, k) for p, q in near for k in range(NB) if p <= q or not one_handle]
+    cross = [(p, q, ka, 1 - ka, (p + q) % 2) for p, q in near for ka in ((p + q) % 2,)]
+    cross += [(p, q, 1, 0, 1) for p, q in near[::3]]
+    far = [(p, P - 1 - p, p % 2, (p // 2) % 2, p % 2) for p in range(60)] * 10
+    return np.array(same + cross + far, dtype=np.int32)
+
+
+def shuffled(n, n_repeated=20, seed=5):
+    """Indices into a list of ``n`` entries: a fixed permutation with ``n_repeated`` entries inserted a second time."""
+    rng = np.random.default_rng(seed)
+    index = rng.permutation(n)
+    for r in rng.choice(n, n_repeated, replace=False):
+        index = np.insert(index, rng.integers(0, len(index) + 1), r)
+    return index
+
+
+def small_cells(one_handle):
+    """Six cells for the handles without objects (one handle: ``p <= q`` inside a bin)."""
+    return np.array([(16, 16, 0, 0, 0), (16, 17, 1, 1, 1), (17, 16, 0, 1, 1), (31, 16, 1, 0, 0), (32, 32, 1, 1, 1), (0, 149, 0, 1, 0)]
+                    if one_handle else [(16, 16, 0, 0, 0), (16, 17, 1, 1, 1), (17, 16, 0, 1, 1), (17, 16, 1, 1, 1), (32, 32, 1, 1, 1), (0, 149, 0, 1, 0)],
+                    dtype=np.int32)
+
+
+# --------------------------------------------------------------------------- the four counts behind one interface
+class Count:
+    """One entry point: its handles, its full list, the oracle on a list, and the check of its own suite."""
+
+    def __init__(self, name):
+        self.name = name
+        self.lens, self.src, self.cat, self.cat_b = scene()
+        self.t = thresholds()
+
+    def full_list(self):
+        return {"shear": all_jobs, "dsigma": all_jobs, "auto": auto_jobs, "pair": lambda: pair_cells(True),
+                "pair2": lambda: pair_cells(False)}[self.name]()
+
+    def small_list(self):
+        """The 6-entry call: the first four entries of the full list that hold pairs, and its first and last, which hold none."""
+        entries = self.full_list()
+        live = expected(self.name)[-1].reshape(len(entries), -1).sum(axis=1) > 0
+        assert not live[0] and not live[-1]
+        return entries[np.concatenate([np.flatnonzero(live)[:4], [0, len(entries) - 1]])]
+
+    def cells_of(self, entries):
+        return len(entries) * (NB if self.name in ("shear", "dsigma", "auto") else 1)
+
+    def upload(self, ctx, sort_axis=2):
+        if self.name == "shear":
+            return test_gpu_shear.upload(ctx, self.lens, self.src, sort_axis)
+        if self.name == "dsigma":
+            lenses = _lib.DsigmaLenses(ctx, *(self.lens[c] for c in "xyzwfc"), P, NB, self.lens["off"], sort_axis=sort_axis)
+            sources = _lib.ShearSources(ctx, *(self.src[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, self.src["off"], sort_axis=sort_axis,
+                                        u=self.src["u"])
+            return lenses, sources
+        a = test_gpu_shear_auto.upload(ctx, self.cat, sort_axis)
+        return (a,) if self.name != "pair2" else (a, test_gpu_shear_auto.upload(ctx, self.cat_b, sort_axis))
+
+    def run(self, ctx, handles, entries, t=None, exchanged=False):
+        """-> (planes..., stats); ``exchanged`` (pair2): the two handles in the other order, the cells transposed."""
+        t = self.t if t is None else t
+        if self.name == "shear":
+            return _lib.shear_count(ctx, *handles, entries, t)
+        if self.name == "dsigma":
+            return _lib.dsigma_count(ctx, *handles, entries, t)
+        if self.name == "auto":
+            return _lib.shear_auto_count(ctx, handles[0], entries, t)
+        if exchanged:
+            return _lib.shear_pair_count(ctx, handles[1], handles[0], np.ascontiguousarray(entries[:, [1, 0, 3, 2, 4]]), t)
+        return _lib.shear_pair_count(ctx, handles[0], handles[-1], entries, t)
+
+    def oracle(self, entries):
+        if self.name == "shear":
+            return shear_oracle.shear_jobs(self.lens, self.src, entries, self.t)
+        if self.name == "dsigma":
+            return dsigma_oracle.dsigma_jobs(self.lens, self.src, entries, self.t)
+        if self.name == "auto":
+            return shear_auto_oracle.shear_auto_jobs(self.cat, entries, self.t)
+        return shear_pair_oracle.shear_pair_cells(self.cat, self.cat if self.name == "pair" else self.cat_b, entries, self.t)
+
+    def check(self, key, got, exp):
+        (test_gpu_shear if self.name in ("shear", "dsigma") else test_gpu_shear_auto).check_against_oracle(key, got, exp)
+
+
+COUNTS = ["shear", "dsigma", "auto", "pair", "pair2"]
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name):
+    """The oracle of the count's full list: once per count, shared, never modified."""
+    count = Count(name)
+    return freeze(count.oracle(count.full_list()))
+
+
+def free(handles):
+    for h in handles:
+        h.free()
+
+
+# --------------------------------------------------------------------------- 1. the full lists
+@pytest.mark.parametrize("order", ["as listed", "shuffled"])
+@pytest.mark.parametrize("name", COUNTS)
+def test_full_list_matches_the_oracle(name, order):
+    """All 150^2 jobs (tangential, Delta Sigma), all p <= q jobs (auto), thousands of cells (pair count on one and on two
+    handles); shuffled: the same list in a fixed random order with 20 entries twice -- the rows are the oracle's rows of those
+    entries, and a repeated entry returns the same bits in both of its slots."""
+    count = Count(name)
+    entries, exp = count.full_list(), expected(name)
+    live = exp[-1].reshape(len(entries), -1).sum(axis=1) > 0
+    assert len(entries) > 5000 and live.sum() > 250 and (~live).sum() > len(entries) // 3  # many cells with pairs, more without
+    index = np.arange(len(entries)) if order == "as listed" else shuffled(len(entries))
+    ctx = engine.get_context(0)
+    handles = count.upload(ctx)
+    try:
+        *got, stats = count.run(ctx, handles, entries[index])
+    finally:
+        free(handles)
+    n_cells = count.cells_of(index)
+    assert len(index) > 1024 and n_cells > 2048 and stats.n_workgroups == n_cells and stats.evaluated_pairs > 0
+    count.check(f"{name} {order}: {len(index)} entries, {n_cells} cells", got, tuple(plane[index] for plane in exp))
+    if order == "shuffled":
+        twice = [np.flatnonzero(index == v) for v in np.flatnonzero(np.bincount(index) > 1)]
+        assert len(twice) == 20
+        for first, second in twice:
+            for plane in got:
+                assert np.array_equal(plane[first], plane[second]), (name, index[first])
+
+
+# --------------------------------------------------------------------------- 2. one handle through calls of other sizes
+@pytest.mark.parametrize("name", COUNTS)
+def test_a_handle_through_calls_that_grow_and_shrink(name):
+    """A 6-entry call, the full list, the 6-entry call again on the same handles: the first and the third are the same bits,
+    the middle one the bits of the same call on freshly uploaded handles. Between two handles of the pair count the full list
+    also runs with the handles exchanged (and again after it), so that the buffers of both have been the call's."""
+    count = Count(name)
+    entries, few = count.full_list(), count.small_list()
+    ctx = engine.get_context(0)
+    handles = count.upload(ctx)
+    try:
+        first = count.run(ctx, handles, few)[:-1]
+        middle = count.run(ctx, handles, entries)[:-1]
+        if name == "pair2":
+            few_exchanged = count.run(ctx, handles, few, exchanged=True)[:-1]
+            middle_exchanged = count.run(ctx, handles, entries, exchanged=True)[:-1]
+            middle_again = count.run(ctx, handles, entries)[:-1]
+            few_exchanged_again = count.run(ctx, handles, few, exchanged=True)[:-1]
+        third = count.run(ctx, handles, few)[:-1]
+    finally:
+        free(handles)
+    fresh = count.upload(ctx)
+    try:
+        alone = count.run(ctx, fresh, entries)[:-1]
+    finally:
+        free(fresh)
+    exp_few = count.oracle(few)
+    assert np.count_nonzero(exp_few[-1].reshape(len(few), -1).sum(axis=1)) == 4
+    count.check(f"{name} 6 entries", first, exp_few)
+    for a, b in zip(first, third):
+        assert np.array_equal(a, b)
+    for a, b in zip(middle, alone):
+        assert np.array_equal(a, b)
+    if name == "pair2":
+        for a, b in zip(middle, middle_again):
+            assert np.array_equal(a, b)
+        for a, b in zip(few_exchanged, few_exchanged_again):
+            assert np.array_equal(a, b)
+        count.check("pair2 exchanged, 6 entries", few_exchanged, exp_few)
+        count.check("pair2 exchanged, full list", middle_exchanged, expected(name))
+
+
+# --------------------------------------------------------------------------- 3. unbinned lenses under many rows
+@pytest.mark.parametrize("name", ["shear", "dsigma"])
+def test_unbinned_lenses_under_eight_rows_of_thresholds(name):
+    """``nb == 1`` lenses, 8 rows of thresholds, 2000 jobs: all 8 cells of a job stream the one lens segment of its patch, each
+    with the edges of its own row (``Tangential::cell`` / ``DeltaSigma::cell``)."""
+    count = Count(name)
+    count.lens = dict(count.lens, nb=1, off=count.lens["off"][::NB].copy())
+    count.t = thresholds(8)
+    near = neighbours()
+    jobs = near[np.random.default_rng(9).choice(len(near), 2000, replace=False)]
+    exp = count.oracle(jobs)
+    rows_with_pairs = exp[2].sum(axis=(0, 2)) > 0
+    assert rows_with_pairs.all() and np.count_nonzero(np.any(exp[2][:, 0] != exp[2][:, 7], axis=1)) > 100  # the rows differ
+    ctx = engine.get_context(0)
+    if name == "shear":
+        handles = test_gpu_shear.upload(ctx, count.lens, count.src, 2)
+    else:
+        lenses = _lib.DsigmaLenses(ctx, *(count.lens[c] for c in "xyzwfc"), P, 1, count.lens["off"])
+        handles = (lenses, _lib.ShearSources(ctx, *(count.src[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, count.src["off"], u=count.src["u"]))
+    try:
+        *got, stats = count.run(ctx, handles, jobs)
+    finally:
+        free(handles)
+    assert stats.n_workgroups == 2000 * 8 and stats.evaluated_pairs > 0
+    count.check(f"{name} nb=1, 8 rows, 2000 jobs", got, exp)
+
+
+# --------------------------------------------------------------------------- 4. handles without objects
+def empty_like(cat, n_bins):
+    none = np.empty(0, dtype=np.float64)
+    return dict({c: none for c in cat if c not in ("nb", "off")}, nb=n_bins, off=np.zeros(P * n_bins + 1, dtype=np.int64))
+
+
+def assert_nothing(key, result, n_cells):
+    *planes, stats = result
+    assert stats.evaluated_pairs == 0 and stats.candidate_pairs == 0 and stats.n_workgroups == n_cells, key
+    for plane in planes:
+        assert plane.size > 0 and np.all(plane == 0.0) and not np.any(np.signbit(plane)), key
+
+
+def test_handles_without_objects():
+    """A handle uploaded with ``n = 0`` uploads, counts to all-zero planes with no pair evaluated, and is freed: as sources, as
+    lenses (a catalogue handle and a lens handle), as the catalogue of the auto count and on either side of the pair count."""
+    lens, src, cat, _ = scene()
+    no_lens, no_src, no_cat = empty_like(lens, NB), empty_like(src, 1), empty_like(cat, NB)
+    t = thresholds()
+    jobs, cells = SMALL, small_cells(False)
+    ctx = engine.get_context(0)
+
+    def dsigma_handles(lens_, src_):
+        lenses = _lib.DsigmaLenses(ctx, *(lens_[c] for c in "xyzwfc"), P, NB, lens_["off"])
+        return lenses, _lib.ShearSources(ctx, *(src_[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, src_["off"], u=src_["u"])
+
+    for lens_, src_ in ((lens, no_src), (no_lens, src), (no_lens, no_src)):
+        key = f"{len(lens_['x'])} lenses, {len(src_['x'])} sources"
+        handles = test_gpu_shear.upload(ctx, lens_, src_, 2)
+        try:
+            assert_nothing("shear " + key, _lib.shear_count(ctx, *handles, jobs, t), len(jobs) * NB)
+        finally:
+            free(handles)
+        handles = dsigma_handles(lens_, src_)
+        try:
+            assert_nothing("dsigma " + key, _lib.dsigma_count(ctx, *handles, jobs, t), len(jobs) * NB)
+        finally:
+            free(handles)
+    nobody, somebody = test_gpu_shear_auto.upload(ctx, no_cat), test_gpu_shear_auto.upload(ctx, cat)
+    try:
+        assert_nothing("auto", _lib.shear_auto_count(ctx, nobody, np.sort(jobs, axis=1), t), len(jobs) * NB)
+        for key, a, b in (("pair, a empty", nobody, somebody), ("pair, b empty", somebody, nobody), ("pair, one empty handle", nobody, nobody)):
+            assert_nothing(key, _lib.shear_pair_count(ctx, a, b, small_cells(a is b) if a is b else cells, t), 6)
+        count = Count("pair")  # the handle with objects is still good
+        few = count.small_list()
+        count.check("after the empty handles", _lib.shear_pair_count(ctx, somebody, somebody, few, t)[:4], count.oracle(few))
+    finally:
+        free((nobody, somebody))

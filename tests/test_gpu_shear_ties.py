@@ -1,0 +1,243 @@
+"""GPU: the four shear counts on catalogues whose sort keys are tied. ``Catalog.from_healpix_map`` puts one object on every
+pixel centre, and pixel centres sit on iso-latitude rings: along the default ``sort_axis = 2`` hundreds of objects of a
+segment share one key exactly, where every other scene of the shear suites draws positions from a continuous distribution.
+The window of a lane tile is two bisections over the streamed segment's key column and a diagonal cell cuts at ``ta + 1``
+(``shear_walk`` in csrc/yawhip_shear.hip); here the runs of equal keys straddle tile and stage boundaries.
+
+Catalogues: the pixel centres of ``yaw.healpix.map_pixels`` over a patch of an nside-512 map -- 9 rings x 400 pixels of a map in
+RING order (3 patches of 3 rings: 3 keys per segment), a 64 x 64 block of a map in NESTED order (4 patches of 32 x 32: runs of 1
+to 32) -- and 2400 objects at ONE declination (a segment is a single key). ``sort_axis = 0`` is the untied control. Thresholds:
+two rows whose outer edge is three ring spacings of the key times (1 -/+ 1e-9), so that the window's boundary lands on a run
+of ties, and for the pair count a row of two spacings and a wide one besides. Sums hold the rules of the counts' own suites
+against the numpy oracles; unweighted ``W`` is the pair count of the shipped exact kernel, bit for bit."""
+import functools
+
+import numpy as np
+import pytest
+
+import dsigma_oracle
+import shear_auto_oracle
+import shear_oracle
+import shear_pair_oracle
+import test_gpu_shear
+import test_gpu_shear_auto
+from conftest import ARCMIN
+from yet_another_wizz_amd import _lib, engine, healpix
+from yet_another_wizz_amd.catalog import radec_to_xyz
+
+pytestmark = pytest.mark.gpu
+NSIDE = 512
+RING_SPACING = 2.0 / (3.0 * NSIDE)  # of z = sin(dec) between neighbouring rings of the equatorial belt: 4.5 arcmin
+FIRST_RING, N_RINGS, FIRST_PIXEL, PIXELS_PER_RING = 700, 9, 100, 400
+NESTED_BLOCK, NESTED_FIRST = 4096, 276 * 4096  # a 64 x 64 block of base pixel 4, an equatorial one
+CATALOGUES = ["ring", "nested", "one declination"]
+AXES = [2, 0]
+
+
+def thresholds(n_rows=2):
+    """f64[n_rows, 5]: from 1 arcmin to 3 ring spacings x (1 - 1e-9), to 3 x (1 + 1e-9), to 2 x (1 + 1e-9), to 4.4 spacings
+    (pixel centres are 6.9 arcmin apart: one spacing holds no pair)."""
+    outer = np.array([3.0 * (1.0 - 1e-9), 3.0 * (1.0 + 1e-9), 2.0 * (1.0 + 1e-9), 4.4])[:n_rows] * RING_SPACING
+    return np.array([np.geomspace(np.sin(0.5 * ARCMIN) * 2.0, edge, 5) for edge in outer]) ** 2
+
+
+@functools.lru_cache(maxsize=None)
+def positions(name):
+    """``(ra, dec, patch, serial)`` of a catalogue: ``serial`` numbers the objects along their ring (or along the nested curve),
+    so that its parity spreads redshift bins evenly over every run of ties."""
+    if name == "one declination":
+        rng = np.random.default_rng(77)
+        ra = np.sort(rng.uniform(0.5, 0.5 + 2.0 * np.pi / 180.0, 2400))
+        return ra, np.full(2400, 0.35), (np.arange(2400) >= 1100).astype(np.int64), np.arange(2400)
+    values = np.full(12 * NSIDE * NSIDE, healpix.UNSEEN)
+    if name == "ring":
+        belt = 2 * NSIDE * (NSIDE - 1)  # pixels of the polar cap in front of the first ring of the belt, ring NSIDE
+        for ring in range(FIRST_RING, FIRST_RING + N_RINGS):
+            start = belt + (ring - NSIDE) * 4 * NSIDE + FIRST_PIXEL
+            values[start:start + PIXELS_PER_RING] = 1.0
+        ipix, ra, z, _, _ = healpix.map_pixels(values, nested=False)
+        ring, serial = (ipix - belt) // (4 * NSIDE) + NSIDE, (ipix - belt) % (4 * NSIDE)
+        patch = (ring - FIRST_RING) // 3
+    else:
+        values[NESTED_FIRST:NESTED_FIRST + NESTED_BLOCK] = 1.0
+        ipix, ra, z, _, _ = healpix.map_pixels(values, nested=True)
+        serial = ipix - NESTED_FIRST
+        patch = serial // (NESTED_BLOCK // 4)
+    assert np.all(np.abs(z) < 2.0 / 3.0)  # the equatorial belt: rings RING_SPACING apart
+    return ra, np.arcsin(z), patch.astype(np.int64), serial.astype(np.int64)
+
+
+def segments(columns, patch, bins, n_patches, n_bins):
+    """The oracle's dict: the objects ordered by (patch, bin) with the offsets int64[P * n_bins + 1]."""
+    seg = patch * n_bins + bins
+    order = np.argsort(seg, kind="stable")
+    cat = {k: v[order] for k, v in columns.items()}
+    cat["off"] = np.concatenate([[0], np.cumsum(np.bincount(seg, minlength=n_patches * n_bins))]).astype(np.int64)
+    for a in cat.values():
+        a.setflags(write=False)
+    return cat
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    """``(lenses, sources, catalogue, n_patches)`` on the positions of ``name``, all unweighted: every object a source (one
+    segment per patch), every second one a lens (two bins, with the columns ``f, c``), and all of them a shear catalogue in two
+    bins. Along z every segment is a few long runs of equal keys (one run at one declination)."""
+    ra, dec, patch, serial = positions(name)
+    n, n_patches = len(ra), int(patch.max()) + 1
+    rng = np.random.default_rng(len(name))
+    x, y, z = radec_to_xyz(ra, dec)
+    c = rng.uniform(600.0, 2500.0, n)
+    columns = dict(x=x, y=y, z=z, g1=rng.normal(0, 0.3, n), g2=rng.normal(0, 0.3, n), u=1.0 / rng.uniform(600.0, 2500.0, n),
+                   f=c / rng.uniform(1.2, 1.9, n), c=c)
+    shear = {k: columns[k] for k in ("x", "y", "z", "g1", "g2")}
+    src = dict(segments(dict(shear, u=columns["u"]), patch, np.zeros(n, dtype=np.int64), n_patches, 1), w=None)
+    cat = dict(segments(shear, patch, serial % 2, n_patches, 2), w=None, nb=2)
+    even = serial % 2 == 0
+    lens = dict(segments({k: columns[k][even] for k in ("x", "y", "z", "f", "c")}, patch[even], (serial[even] // 2) % 2, n_patches, 2), w=None, nb=2)
+    for tied in (src, cat, lens):  # segments longer than a lane tile / a stage, made of runs of equal keys
+        sizes = np.diff(tied["off"])
+        keys_per_segment = [len(np.unique(tied["z"][a:b])) for a, b in zip(tied["off"][:-1], tied["off"][1:])]
+        assert sizes.min() >= 256 and max(keys_per_segment) <= {"ring": 3, "nested": 63, "one declination": 1}[name], (name, sizes, keys_per_segment)
+        assert len(np.unique(tied["x"])) == len(tied["x"])  # the control axis is untied
+    return lens, src, cat, n_patches
+
+
+def job_lists(n_patches):
+    """Every ordered patch pair for the lens counts, every ``p <= q`` for the auto count, and cells in four rows for the pair
+    count: same-bin (diagonal and not) with the rows 0 and 1, cross-bin in both orders with the rows 2 and 3."""
+    jobs = np.array([(p, q) for p in range(n_patches) for q in range(n_patches)], dtype=np.int32)
+    upper = jobs[jobs[:, 0] <= jobs[:, 1]]
+    cells = [(p, q, k, k, k) for p, q in upper for k in (0, 1)] + [(p, q, 0, 1, 2 + (p + q) % 2) for p, q in jobs]
+    cells += [(p, q, 1, 0, 3) for p, q in upper] + [(p, p, k, k, 3) for p in range(n_patches) for k in (0, 1)]
+    return jobs, upper, np.array(cells, dtype=np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name, count):
+    """The oracle of a count on a catalogue: once, shared by the sort axes, never modified."""
+    lens, src, cat, n_patches = scene(name)
+    jobs, upper, cells = job_lists(n_patches)
+    out = {"shear": lambda: shear_oracle.shear_jobs(lens, src, jobs, thresholds()),
+           "dsigma": lambda: dsigma_oracle.dsigma_jobs(lens, src, jobs, thresholds()),
+           "auto": lambda: shear_auto_oracle.shear_auto_jobs(cat, upper, thresholds()),
+           "pair": lambda: shear_pair_oracle.shear_pair_cells(cat, cat, cells, thresholds(4))}[count]()
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def upload_lens_side(ctx, lens, src, sort_axis, kind):
+    """``kind``: "shear" (a catalogue handle and plain sources), "dsigma" (a lens handle with f, c; sources with u) or "unit"
+    (the same with f = 1, c = 0: W is the pair count)."""
+    n_patches = len(src["off"]) - 1
+    if kind == "shear":
+        return test_gpu_shear.upload(ctx, lens, src, sort_axis)
+    f, c = (lens["f"], lens["c"]) if kind == "dsigma" else (np.ones_like(lens["f"]), np.zeros_like(lens["c"]))
+    lenses = _lib.DsigmaLenses(ctx, lens["x"], lens["y"], lens["z"], None, f, c, n_patches, 2, lens["off"], sort_axis=sort_axis)
+    sources = _lib.ShearSources(ctx, src["x"], src["y"], src["z"], None, src["g1"], src["g2"], n_patches, src["off"], sort_axis=sort_axis, u=src["u"])
+    return lenses, sources
+
+
+def exact_counts(ctx, lens, src, jobs, t, sort_axis):
+    """The pair counts of the shipped exact kernel between the lenses and the sources as plain catalogues."""
+    n_patches = len(src["off"]) - 1
+    one = _lib.DeviceCatalog(ctx, lens["x"], lens["y"], lens["z"], None, n_patches, 2, lens["off"], sort_axis=sort_axis)
+    two = _lib.DeviceCatalog(ctx, src["x"], src["y"], src["z"], None, n_patches, 1, src["off"], sort_axis=sort_axis)
+    try:
+        return _lib.count_pairs(ctx, one, two, jobs, t, kernel="exact")[0].astype(np.float64)
+    finally:
+        one.free(), two.free()
+
+
+# --------------------------------------------------------------------------- 1. the two counts around lenses
+@pytest.mark.parametrize("sort_axis", AXES)
+@pytest.mark.parametrize("count", ["shear", "dsigma"])
+@pytest.mark.parametrize("name", CATALOGUES)
+def test_lens_counts_on_tied_keys(name, count, sort_axis):
+    lens, src, _, n_patches = scene(name)
+    jobs, t = job_lists(n_patches)[0], thresholds()
+    exp = expected(name, count)
+    assert np.count_nonzero(exp[3]) > 4 * n_patches and np.all(exp[3][::n_patches + 1].sum(axis=2) > 0)  # both rows of every diagonal job
+    ctx = engine.get_context(0)
+    call = _lib.shear_count if count == "shear" else _lib.dsigma_count
+    handles = upload_lens_side(ctx, lens, src, sort_axis, count)
+    try:
+        T, X, W, stats = call(ctx, *handles, jobs, t)
+    finally:
+        handles[0].free(), handles[1].free()
+    assert stats.n_workgroups == len(jobs) * 2 and 0 < stats.evaluated_pairs <= stats.candidate_pairs
+    test_gpu_shear.check_against_oracle(f"{count} on {name} axis={sort_axis}", (T, X, W), exp)
+    if count == "dsigma":  # unit columns: W counts the pairs
+        handles = upload_lens_side(ctx, lens, src, sort_axis, "unit")
+        try:
+            W = _lib.dsigma_count(ctx, *handles, jobs, t)[2]
+        finally:
+            handles[0].free(), handles[1].free()
+    pairs = exact_counts(ctx, lens, src, jobs, t, sort_axis)
+    assert pairs.sum() > 5000 and np.array_equal(W, pairs)
+
+
+# --------------------------------------------------------------------------- 2. the two shear-shear counts
+@pytest.mark.parametrize("sort_axis", AXES)
+@pytest.mark.parametrize("name", CATALOGUES)
+def test_auto_count_on_tied_keys(name, sort_axis):
+    _, _, cat, n_patches = scene(name)
+    upper, t = job_lists(n_patches)[1], thresholds()
+    exp = expected(name, "auto")
+    diagonal = upper[:, 0] == upper[:, 1]
+    assert np.all(exp[3][diagonal].sum(axis=2) > 0)
+    P, M, C, W, stats = test_gpu_shear_auto.count(cat, upper, t, sort_axis)
+    assert stats.n_workgroups == len(upper) * 2 and stats.evaluated_pairs > 0
+    test_gpu_shear_auto.check_against_oracle(f"auto on {name} axis={sort_axis}", (P, M, C, W), exp)
+    pairs = test_gpu_shear_auto.exact_pair_count(cat, upper, t, sort_axis)
+    assert pairs.sum() > 3000 and np.array_equal(W, pairs)
+
+
+@pytest.mark.parametrize("sort_axis", AXES)
+@pytest.mark.parametrize("name", CATALOGUES)
+def test_pair_count_on_tied_keys(name, sort_axis):
+    """Against the oracle, whose unweighted ``W`` is a pair count in the float64 predicate of every kernel: equal bit for bit;
+    the same-bin cells of the rows 0 and 1 are the auto count's bits."""
+    _, _, cat, n_patches = scene(name)
+    _, upper, cells = job_lists(n_patches)
+    exp = expected(name, "pair")
+    live = exp[3].sum(axis=1) > 0
+    assert all(np.any(live & (cells[:, 4] == row)) for row in range(4)) and np.any(live & (cells[:, 2] != cells[:, 3]) & (cells[:, 0] > cells[:, 1]))
+    ctx = engine.get_context(0)
+    handle = test_gpu_shear_auto.upload(ctx, cat, sort_axis)
+    try:
+        P, M, C, W, stats = _lib.shear_pair_count(ctx, handle, handle, cells, thresholds(4))
+        auto = _lib.shear_auto_count(ctx, handle, upper, thresholds())
+    finally:
+        handle.free()
+    assert stats.n_workgroups == len(cells) and stats.evaluated_pairs > 0
+    test_gpu_shear_auto.check_against_oracle(f"pair on {name} axis={sort_axis}", (P, M, C, W), exp)
+    assert exp[3].sum() > 5000 and np.array_equal(W, exp[3])
+    for ours, ref in zip((P, M, C, W), auto[:4]):
+        assert np.array_equal(ours[:2 * len(upper)].reshape(ref.shape), ref)
+
+
+# --------------------------------------------------------------------------- 3. the diagonal on tied keys
+@pytest.mark.parametrize("name", ["ring", "one declination"])
+def test_diagonal_cells_hold_every_unordered_pair_once(name):
+    """The sources of patch 0 (1200 objects in 3 runs of equal keys; at one declination 1100 in a single run) as one segment:
+    the diagonal cell against the oracle's unordered sum and the exact kernel's halved count; then cut into two patches inside a
+    run: the three cells together hold every pair of the whole once."""
+    _, src, _, _ = scene(name)
+    n, cut = int(src["off"][1]), 470
+    by_key = np.argsort(src["z"][:n], kind="stable")  # (the upload sorts anyway: this only shows where the cut falls)
+    columns = {k: src[k][:n][by_key] for k in ("x", "y", "z", "g1", "g2")}
+    assert len(np.unique(columns["z"])) == (3 if name == "ring" else 1) and columns["z"][cut - 1] == columns["z"][cut]
+    t = thresholds()[1:]
+    whole = dict(columns, w=None, nb=1, off=np.array([0, n], dtype=np.int64))
+    split = dict(whole, off=np.array([0, cut, n], dtype=np.int64))
+    jobs = np.array([(0, 0), (1, 1), (0, 1)], dtype=np.int32)
+    got_whole = test_gpu_shear_auto.count(whole, [[0, 0]], t)[:4]
+    test_gpu_shear_auto.check_against_oracle(f"diagonal on {name}", got_whole, shear_auto_oracle.shear_auto_jobs(whole, [[0, 0]], t))
+    got_split = test_gpu_shear_auto.count(split, jobs, t)[:4]
+    exp_split = shear_auto_oracle.shear_auto_jobs(split, jobs, t)
+    assert exp_split[3][2].sum() > 100  # pairs across the cut
+    test_gpu_shear_auto.check_against_oracle(f"split on {name}", got_split, exp_split)
+    assert got_whole[3].sum() > 2000 and np.array_equal(got_whole[3][0], got_split[3].sum(axis=0))
+    assert np.array_equal(got_whole[3], test_gpu_shear_auto.exact_pair_count(whole, [[0, 0]], t))

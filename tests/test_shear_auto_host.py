@@ -11,7 +11,7 @@ import shear_auto_oracle
 import shear_oracle
 import yet_another_wizz_amd as yaw
 from conftest import ARCMIN, ROOT
-from test_shear_host import ring_around
+from test_shear_host import ARCSEC, reference_angle, ring_around, rotation_bound
 from yet_another_wizz_amd import catalog as catalog_module
 from yet_another_wizz_amd import engine, measurements
 from yet_another_wizz_amd.catalog import radec_to_xyz
@@ -48,21 +48,30 @@ def test_known_answers_from_two_objects(where):
 
 
 # --------------------------------------------------------------------------- 2. the rotations
-@pytest.mark.parametrize("dec_deg", [0.0, 40.0, 80.0])
+@pytest.mark.parametrize("dec_deg", [0.0, 40.0, 80.0, 89.99, -89.99])
 def test_rotations_match_the_spherical_position_angles(dec_deg):
-    """cos / sin of twice the position angle at EACH end, from tests/shear_oracle.position_angle taken from that end."""
-    rng = np.random.default_rng(int(dec_deg) + 3)
+    """cos / sin of twice the position angle at EACH end, from tests/shear_oracle.position_angle taken from that end, pair by
+    pair within ``K eps / theta`` (test_shear_host.rotation_bound): partners 0.5' .. 30' away, then 0.5" .. 30" (uniform in the
+    logarithm), the last 20 objects within 2" of the wrap of the right ascension."""
+    rng = np.random.default_rng(int(abs(dec_deg)) + 3)
     ra_a = rng.uniform(0.0, 2.0 * np.pi, 200)
     dec_a = np.full(200, dec_deg * DEG)
-    ra_b, dec_b = np.empty(200), np.empty(200)
-    for i in range(200):  # one partner 0.5' .. 30' away in any direction
-        (ra_b[i],), (dec_b[i],) = ring_around(rng, ra_a[i], dec_a[i], 1, 0.5 * ARCMIN, 30.0 * ARCMIN)
-    c_a, s_a, c_b, s_b, den_a, den_b = shear_auto_oracle.rotations(*radec_to_xyz(ra_a, dec_a), *radec_to_xyz(ra_b, dec_b))
-    assert np.all(den_a > 0) and np.all(den_b > 0)
-    phi_a = shear_oracle.position_angle(ra_a, dec_a, ra_b, dec_b)  # b seen from a
-    phi_b = shear_oracle.position_angle(ra_b, dec_b, ra_a, dec_a)  # a seen from b
-    for ours, ref in ((c_a, np.cos(2 * phi_a)), (s_a, np.sin(2 * phi_a)), (c_b, np.cos(2 * phi_b)), (s_b, np.sin(2 * phi_b))):
-        assert np.max(np.abs(ours - ref)) <= 1e-9
+    for rmin, rmax, log_uniform in ((0.5 * ARCMIN, 30.0 * ARCMIN, False), (0.5 * ARCSEC, 30.0 * ARCSEC, True)):
+        if log_uniform:
+            ra_a[-20:] = rng.uniform(-2.0, 2.0, 20) * ARCSEC % (2.0 * np.pi)
+        ra_b, dec_b = np.empty(200), np.empty(200)
+        for i in range(200):  # one partner in any direction
+            (ra_b[i],), (dec_b[i],) = ring_around(rng, ra_a[i], dec_a[i], 1, rmin, rmax, log_uniform=log_uniform)
+        assert not log_uniform or np.count_nonzero(np.abs(ra_a - ra_b) > 6.0) >= 3  # pairs across the wrap
+        xyz_a, xyz_b = radec_to_xyz(ra_a, dec_a), radec_to_xyz(ra_b, dec_b)
+        c_a, s_a, c_b, s_b, den_a, den_b = shear_auto_oracle.rotations(*xyz_a, *xyz_b)
+        assert np.all(den_a > 0) and np.all(den_b > 0)
+        phi_a = reference_angle(ra_a, dec_a, ra_b, dec_b)  # b seen from a
+        phi_b = reference_angle(ra_b, dec_b, ra_a, dec_a)  # a seen from b
+        bound = rotation_bound(*xyz_a, *xyz_b)
+        assert bound.max() < 1e-9  # (tighter than the flat 1e-9 this test had, which went down to 0.5 arcmin)
+        for ours, ref in ((c_a, np.cos(2 * phi_a)), (s_a, np.sin(2 * phi_a)), (c_b, np.cos(2 * phi_b)), (s_b, np.sin(2 * phi_b))):
+            assert np.all(np.abs(ours - ref) <= bound)
 
 
 # --------------------------------------------------------------------------- 3. the binned layout with shear

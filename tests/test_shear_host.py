@@ -12,9 +12,10 @@ from yet_another_wizz_amd import engine
 from yet_another_wizz_amd.catalog import radec_to_xyz
 
 
-def ring_around(rng, ra_l, dec_l, n, rmin, rmax):
-    """``n`` points (ra, dec, radian) at separations rmin .. rmax (radian) and any direction around (ra_l, dec_l)."""
-    r = rng.uniform(rmin, rmax, n)
+def ring_around(rng, ra_l, dec_l, n, rmin, rmax, log_uniform=False):
+    """``n`` points (ra, dec, radian) at separations rmin .. rmax (radian; uniform, or uniform in the logarithm) and any
+    direction around (ra_l, dec_l)."""
+    r = np.exp(rng.uniform(np.log(rmin), np.log(rmax), n)) if log_uniform else rng.uniform(rmin, rmax, n)
     theta = rng.uniform(0.0, 2.0 * np.pi, n)
     lens = np.array([np.cos(dec_l) * np.cos(ra_l), np.cos(dec_l) * np.sin(ra_l), np.sin(dec_l)])
     east = np.array([-np.sin(ra_l), np.cos(ra_l), 0.0])
@@ -24,18 +25,50 @@ def ring_around(rng, ra_l, dec_l, n, rmin, rmax):
 
 
 # --------------------------------------------------------------------------- 1. the projection
-@pytest.mark.parametrize("dec_l", [0.0, 0.9, -1.4])
-def test_projection_matches_the_spherical_position_angle(dec_l):
-    rng = np.random.default_rng(11)
-    ra_l, amplitude = 2.1, 0.03
-    ra, dec = ring_around(rng, ra_l, dec_l, 5000, 0.5 * ARCMIN, 30.0 * ARCMIN)
+ARCSEC = ARCMIN / 60.0
+DEC_EXTREME = 89.99 * np.pi / 180.0
+RA_WRAP = 2.0 * np.pi - 1e-7  # partners on both sides of the wrap
+
+
+def rotation_bound(x, y, z, lx, ly, lz):
+    """The per-pair bound ``K * eps / theta`` on ``c2`` and ``s2p`` (``K`` and ``eps`` are those of
+    tests/shear_exact.py, measured by tools/make_golden_shear_exact.py), ``theta`` the pair's separation in radian."""
+    import shear_exact
+
+    theta = 2.0 * np.arcsin(0.5 * np.sqrt((x - lx) ** 2 + (y - ly) ** 2 + (z - lz) ** 2))
+    return float(shear_exact.fixture()["K"]) * shear_exact.EPS / theta
+
+
+def reference_angle(ra, dec, ra_l, dec_l):
+    """``shear_oracle.position_angle`` in extended precision where the platform has it: at arcseconds the float64 bearing
+    has an error of the size of the one it is to measure (its ``north`` cancels to ``theta``)."""
+    return shear_oracle.position_angle(*(np.asarray(v, dtype=np.longdouble) for v in (ra, dec, ra_l, dec_l)))
+
+
+def check_projection(rng, ra_l, dec_l, rmin, rmax, log_uniform):
+    """``c2`` and ``s2p`` of 5000 sources ``rmin .. rmax`` around the lens against the spherical position angle, pair by pair
+    within ``rotation_bound`` -> the sources and the lens."""
+    ra, dec = ring_around(rng, ra_l, dec_l, 5000, rmin, rmax, log_uniform=log_uniform)
     x, y, z = radec_to_xyz(ra, dec)
     (lx,), (ly,), (lz,) = radec_to_xyz(np.array([ra_l]), np.array([dec_l]))
     c2, s2p, den = shear_oracle.projection(x, y, z, lx, ly, lz)
-    phi = shear_oracle.position_angle(ra, dec, ra_l, dec_l)
-    assert np.all(den > 0)
-    assert np.max(np.abs(c2 - np.cos(2 * phi))) <= 1e-9
-    assert np.max(np.abs(s2p - np.sin(2 * phi))) <= 1e-9
+    phi = reference_angle(ra, dec, ra_l, dec_l)
+    bound = rotation_bound(x, y, z, lx, ly, lz)
+    assert np.all(den > 0) and bound.max() < 1e-9  # (tighter than the flat 1e-9 this test had, which went down to 0.5 arcmin)
+    assert np.all(np.abs(c2 - np.cos(2 * phi)) <= bound)
+    assert np.all(np.abs(s2p - np.sin(2 * phi)) <= bound)
+    return ra, dec, x, y, z, lx, ly, lz
+
+
+@pytest.mark.parametrize("dec_l", [0.0, 0.9, -1.4, DEC_EXTREME, -DEC_EXTREME])
+def test_projection_matches_the_spherical_position_angle(dec_l):
+    rng = np.random.default_rng(11)
+    ra_l, amplitude = 2.1, 0.03
+    ra, dec, x, y, z, lx, ly, lz = check_projection(rng, ra_l, dec_l, 0.5 * ARCMIN, 30.0 * ARCMIN, False)
+    # down to 0.5 arcsec, also just below the wrap of the right ascension and with partners on both sides of it
+    for ra_other in (ra_l, 6.2831, RA_WRAP):
+        ra_s = check_projection(np.random.default_rng(12), ra_other, dec_l, 0.5 * ARCSEC, 30.0 * ARCSEC, True)[0]
+        assert ra_other != RA_WRAP or 1000 < np.count_nonzero(ra_s < np.pi) < 4000
     # a pure tangential pattern comes back as gamma_t = A, gamma_x = 0
     g1, g2 = shear_oracle.tangential_pattern(ra, dec, ra_l, dec_l, amplitude)
     w = rng.uniform(0.5, 2.0, len(ra))
