@@ -79,7 +79,7 @@ def test_dense_request_struct_matches_header():
 
 
 def test_build_lists_cover_every_source_and_header(tmp_path, monkeypatch):
-    """Every csrc/*.hip is compiled (the kernel unit first), every header is watched for staleness, and source_sha16() sees
+    """Every csrc/*.hip is compiled (the kernel units first, each on the private device header), every header is watched for staleness, and source_sha16() sees
     a change of one byte of the private header (hashed from a copy: the tree is not edited)."""
     import glob
     import shutil
@@ -87,7 +87,10 @@ def test_build_lists_cover_every_source_and_header(tmp_path, monkeypatch):
     from yet_another_wizz_amd import build
 
     csrc = os.path.join(ROOT, "yet_another_wizz_amd", "csrc")
-    assert build.SOURCES[0] == build.KERNEL_UNIT == os.path.join(csrc, "yawhip.hip")
+    assert build.KERNEL_UNITS and build.SOURCES[:len(build.KERNEL_UNITS)] == build.KERNEL_UNITS
+    assert os.path.join(csrc, "yawhip.hip") in build.KERNEL_UNITS
+    for unit in build.KERNEL_UNITS:
+        assert '#include "yawhip_count_device.h"' in open(unit).read(), unit
     assert len(build.SOURCES) == len(set(build.SOURCES))
     assert set(build.SOURCES) == set(glob.glob(os.path.join(csrc, "*.hip")))
     headers = {os.path.join(ROOT, "include", "yawhip.h"), *glob.glob(os.path.join(csrc, "*.h")), *glob.glob(os.path.join(csrc, "*.inc"))}

@@ -1,4 +1,4 @@
-"""The float32 guard of the band kernel (k_count_band32, yet_another_wizz_amd/csrc/yawhip.hip): for unit vectors rounded
+"""The float32 guard of the band kernel (k_count_band32, yet_another_wizz_amd/csrc/yawhip_band32.inc): for unit vectors rounded
 to float32, the float32 distance s32 = fma(dz, dz, fma(dy, dy, dx * dx)) stays within
 g(s) = 2.1e-7 sqrt(s) + 5e-7 s + 1e-12 of the float64 value of the parity contract. The derivation is in the kernel's
 header; here the bound is checked on a few million pairs, with adversarial coordinates included (CPU, numpy)."""

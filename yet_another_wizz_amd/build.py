@@ -15,10 +15,13 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-KERNEL_UNIT = os.path.join(CSRC, "yawhip.hip")  # the count kernels: what experiment flags and variant builds recompile
+# the kernel units -- the count kernels, one unit per kernel family, and the device code around them (yawhip.hip has the map):
+# what experiment flags and variant builds recompile. They go first: the longest compile of the build is among them
+KERNEL_UNITS = [*sorted(glob.glob(os.path.join(CSRC, "yawhip_kernel_*.hip"))), os.path.join(CSRC, "yawhip.hip")]
+KERNEL_HEADERS = [os.path.join(CSRC, "yawhip_count_device.h"), os.path.join(CSRC, "yawhip_band32.inc")]  # included by them alone
 # every csrc/*.hip is a translation unit and every header can change one: a new file is never missing from the staleness
 # check or from source_sha16()
-SOURCES = [KERNEL_UNIT, *sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) if p != KERNEL_UNIT)]
+SOURCES = [*KERNEL_UNITS, *sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) if p not in KERNEL_UNITS)]
 HEADERS = [os.path.join(ROOT, "include", "yawhip.h"),
            *sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")))]
 INCLUDE = os.path.join(ROOT, "include")
@@ -79,6 +82,24 @@ def is_stale(extra_flags=()) -> bool:
     return os.path.getmtime(LIB) < newest or _built_with() != _flag_text(extra_flags)
 
 
+def compile_and_link(todo, objects, lib, csrc=CSRC, include=INCLUDE, verbose=False) -> None:
+    """Compile the (source, object, extra flags) of ``todo`` side by side, then link ``objects`` into ``lib``."""
+    hipcc = hipcc_path()
+    running = []
+    for src, obj, flags in todo:
+        cmd = [hipcc, *HIPCC_FLAGS, *flags, f"-I{include}", f"-I{csrc}", "-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        running.append((cmd, subprocess.Popen(cmd)))
+    failed = [(cmd, proc.returncode) for cmd, proc in running if proc.wait() != 0]  # (every compile is waited for)
+    if failed:
+        raise subprocess.CalledProcessError(failed[0][1], failed[0][0])
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objects]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+
+
 def build_library(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
     """Compile every source to an object (objects of unchanged sources are reused unless ``force`` or
     ``extra_flags`` are given: the rocPRIM sorts take 30 s, the kernels are what one iterates on) and link."""
@@ -88,28 +109,18 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=()) ->
     flags_changed = _built_with() != _flag_text(extra_flags)
     if os.path.exists(FLAGS_STAMP):
         os.remove(FLAGS_STAMP)  # no stamp while the build is incomplete
-    hipcc = hipcc_path()
     newest_header = max(os.path.getmtime(p) for p in HEADERS)
-    objects, running = [], []
+    objects, todo = [], []
     for src in SOURCES:
         obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
         objects.append(obj)
-        is_kernels = src == KERNEL_UNIT
+        is_kernels = src in KERNEL_UNITS
         flags = list(extra_flags) if is_kernels else []  # experiment flags only concern the kernels
         fresh = os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_header)
         if fresh and not (is_kernels and (force or flags_changed)) and not (force == "all"):
             continue
-        cmd = [hipcc, *HIPCC_FLAGS, *flags, f"-I{INCLUDE}", f"-I{CSRC}", "-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        running.append((cmd, subprocess.Popen(cmd)))  # the translation units compile side by side
-    for cmd, proc in running:
-        if proc.wait() != 0:
-            raise subprocess.CalledProcessError(proc.returncode, cmd)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objects]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+        todo.append((src, obj, flags))
+    compile_and_link(todo, objects, LIB, verbose=verbose)
     with open(FLAGS_STAMP, "w") as f:
         f.write(_flag_text(extra_flags))
     return LIB

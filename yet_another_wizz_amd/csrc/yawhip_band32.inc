@@ -1,9 +1,53 @@
-// k_count_band32 (float32 band kernel, DESIGN.md section 4), included by yawhip.hip once per number of chunks a round can
-// stage -- YAW_B32_CH = 3 as k_count_band32, = 1 as k_count_band32_one (every item has one window: merged triple runs, items of
-// k_build_items; the bookkeeping of two more chunks costs scalar registers and instructions per item). The chunk count is a
-// macro of two inclusions rather than a template parameter because hipcc 7.2 emits no host stubs for this kernel as soon as a
-// template parameter sizes its chunk arrays. Not a translation unit of its own: everything it uses is defined in yawhip.hip
-// or yawhip_count_kernels.h.
+// k_count_band32 (float32 band kernel, DESIGN.md section 4) and its launcher, included once per number of chunks a round can
+// stage -- by yawhip_kernel_band32.hip with YAW_B32_CH = 3 as k_count_band32 / launch_band32 (up to three windows, or pieces of
+// one, in a round), by yawhip_kernel_band32_one.hip with YAW_B32_CH = 1 as k_count_band32_one / launch_band32_one, for calls whose
+// items all have one window (merged triple runs, items of k_build_items): the bookkeeping of two more chunks costs scalar
+// registers (spilled) and instructions per item, 0.283 against 0.274 ms at the headline. The chunk count is a macro of two
+// inclusions rather than a template parameter because hipcc 7.2 emits no host stubs for this kernel as soon as a template
+// parameter sizes its chunk arrays; and the two are two translation units because together they are 60 % of the library's
+// device instructions. Not a translation unit of its own: the including unit names the kernel (YAW_B32_NAME), the launcher
+// (YAW_B32_LAUNCH) and the chunks (YAW_B32_CH) and has included yawhip_count_device.h.
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// Band kernel, float32 classification (BAND on strip layouts of unit vectors; DESIGN.md section 4).
+// Same items and the same walk as k_count_band, but an entry is decided in FLOAT32 wherever float32 can decide it:
+//   * both catalogues keep a float32 image of every strip layout, 16 bytes per object {x, y, z, bin id} (DevTab::q);
+//     the window is staged from it by LDS-DMA (one dwordx4 per entry) and read back with one ds_read_b128;
+//   * s32 = fma(dz, dz, fma(dy, dy, dx * dx)) on the float32 images, two lane objects per packed instruction
+//     (v_pk_add / v_pk_mul / v_pk_fma_f32: 7 VALU for two evaluations instead of 16 FP64 operations);
+//   * for unit vectors |s32 - s| <= g(t) = 2.1e-7 sqrt(t) + 5e-7 t + 1e-12 around an edge t (rounding of the images to
+//     float32: 2^-25 per coordinate -- |x| <= 1, and values a hair above 1 round to 1 --, of the differences: 2^-24
+//     relative, hence |error of d_i| <= 6e-8 (1 + |d_i|) and 2 |d| sqrt(3) 6e-8 on the sum of squares; of the three-term
+//     sum: 3 x 2^-24 relative), so s32 < t - g proves s <= t and
+//     s32 > t + g proves s > t. The host turns every edge into the two float32 bounds (thr32, build_thr32);
+//   * an evaluation that lands inside a guard band (~1e-4 of them at the headline) is UNCERTAIN: the wave branches, the
+//     lanes concerned fetch both objects in float64 and apply the exact predicate of the parity contract
+//     (((dx*dx + dy*dy) + dz*dz) against the host's float64 thresholds). Every pair is therefore decided exactly as
+//     k_count_band decides it: results are bit-identical.
+// The roles are swapped against k_count_band where one side is binned (MERGED, the cross-correlation counts): the
+// lanes hold the BINNED objects (c1), the window streams the unbinned side (c2). A lane then knows the bin, the edge
+// row and the counter of each of its objects: hits are counted in registers (add with carry) and go to the LDS
+// histogram once per item, not once per evaluation.
+//   NE == 2 (one annulus): classes by |s32 - c| against two half widths (certainly inside / possibly inside);
+//   NE  > 2: cumulative counters per edge (s <= t_e), fine bin j = cum[j + 1] - cum[j] at the flush.
+// ------------------------------------------------------------------------------------------------
+// Waves per SIMD the variants of k_count_band32 are compiled for (the second argument of their __launch_bounds__):
+constexpr int B32_WAVES_PLAIN = 7; // the plain count, one annulus, one threshold row: 72 VGPRs instead of 79, 0.359 against 0.371 ms at the
+                                   // headline (8 spills: 0.405)
+constexpr int B32_WAVES_BIG = 6;   // ... with the big stage: its 6.3 KB of LDS admit 25 workgroups per CU anyway, and at 80 registers
+                                   // nothing is spilled (headline 0.305 -> 0.286 ms; 8: 0.343)
+constexpr int B32_WAVES_W = 5;     // the weighted one-annulus variants (96 VGPRs; the compiler took 97 by itself: 4 waves, 0.57 against 0.51 ms)
+constexpr int B32_WAVES_W1 = 5;    // ... with one object per lane (DD / RR of an autocorrelation: 82 VGPRs)
+constexpr int B32_WAVES_LT = 1;    // the plain count with per-bin thresholds (physical scales): the compiler's choice (87 registers, 5 waves)
+constexpr int band32_min_waves(int R, int CAP, bool WEIGHTED, int NE, bool UNI) {
+    if (NE == 2 && UNI) {
+        if (WEIGHTED) return R == 1 ? B32_WAVES_W1 : B32_WAVES_W;
+        return CAP >= B32_CAP_BIG ? B32_WAVES_BIG : B32_WAVES_PLAIN;
+    }
+    return NE == 2 && !WEIGHTED ? B32_WAVES_LT : 1;  // everything else: the compiler's choice
+}
+
 template <int R, int CAP, bool WEIGHTED, int NE, bool MERGED, bool UNI>
 __global__ __launch_bounds__(64, band32_min_waves(R, CAP, WEIGHTED, NE, UNI))
 void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ items, int n_bins,
@@ -14,7 +58,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                   double *__restrict__ partials,
                   unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
     static_assert(NE >= 2 && NE <= 4, "edges per bin");
-    constexpr int CH = YAW_B32_CH;  // chunks per round (see yawhip.hip)
+    constexpr int CH = YAW_B32_CH;  // chunks per round (see the head of this file)
     // One object per lane (sparse per-bin runs) in the one-chunk kernel: two ENTRIES per trip of the walk, see eval_entry.
     // (A chunk is then followed by two sentinel entries; with several chunks in a stage the second would be the next chunk's first.)
     constexpr bool PAIRS = R == 1 && CH == 1;
@@ -490,3 +534,30 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
     }
 }
 
+}  // namespace
+
+namespace yawhip_detail {
+
+// The variants compiled are the ones named in these lists (pick); launch_count (yawhip.hip) calls this launcher or the other
+// inclusion's by L.one_chunk.
+hipError_t YAW_B32_LAUNCH(const CountLaunch &L, bool wgt, int32_t *variant) {
+    const std::pair<int, int> stage{L.R, L.cap};
+    const std::pair<bool, bool> rows{L.merged, L.uni};
+    const dim3 band_grid(L.band_grid), wave(64);
+    return pick<Bool<false>, Bool<true>>(wgt, [&](auto w) {
+        return pick<Int<4>, Int<3>, Int<2>>(L.n_edges, [&](auto ne) {
+            return pick<Rows<true, false>, Rows<true, true>, Rows<false, true>>(rows, [&](auto r) {
+                return pick<Stage<4, B32_CAP_BIG>, Stage<2, B32_CAP_BIG>, Stage<2, B32_CAP>, Stage<1, B32_CAP>>(stage, [&](auto s) {
+                    using S = decltype(s);
+                    using M = decltype(r);
+                    *variant = variant_code(YAW_B32_CH == 1 ? VF_BAND32_ONE : VF_BAND32, S::R, S::CAP, w, ne, M::MERGED, M::UNI);
+                    return launch(YAW_B32_NAME<S::R, S::CAP, w, ne, M::MERGED, M::UNI>, band_grid, wave, L.lds, L.stream, L.d_tabs,
+                                  L.d_items, L.n_bins, L.d_t, L.d_thr32, L.d_rwin, L.d_ucap, L.flush_mask, L.swap ? 1 : 0,
+                                  L.d_counts, L.d_partials, L.d_ctr, L.seg_cap);
+                });
+            });
+        });
+    });
+}
+
+}  // namespace yawhip_detail

@@ -6,9 +6,10 @@
 //   * count_enqueue, which puts a call on the context's stream -- plan look-up, result block, item builder, count kernel(s),
 //     reductions, tail -- and count_finish, which waits for it and hands over results and statistics; run_single cuts a job
 //     list in halves where one call cannot take it, yawhip_count_pairs splits it over the devices of a context.
-// No kernel is defined here. The kernels and the functions that launch them are yawhip.hip's; yawhip_count_kernels.h is the
-// interface between the two: the geometry a plan reasons about, the counter block count_finish reads, and the launch
-// record (CountLaunch) count_enqueue fills. Experiment flags (-D) of a variant build do not reach this unit.
+// No kernel is defined here. The kernels and the functions that launch them are the kernel units' (yawhip.hip and
+// yawhip_kernel_*.hip, one per kernel family); yawhip_count_kernels.h is the interface between them and this unit: the
+// geometry a plan reasons about, the counter block count_finish reads, and the launch record (CountLaunch) count_enqueue
+// fills. Experiment flags (-D) of a variant build do not reach this unit.
 // DESIGN.md sections 4 and 5 have the reasons and the measurements.
 
 #include <hip/hip_runtime.h>
@@ -497,7 +498,7 @@ int Planner::tile_and_stage() {
     // stage capacity of the band kernel: the smallest compiled one that holds a whole window (see BCAP_MID)
     int cap = ctx->band_cap == BCAP || ctx->band_cap == BCAP_MID ? ctx->band_cap : 0;
     if (band && cap == 0) cap = R >= 4 || est_window > 0.95 * BCAP ? BCAP_MID : BCAP;
-    if (band) {  // (R, stage) pairs that are compiled (the Stage lists of the launch functions, yawhip.hip): the plan names one of them
+    if (band) {  // (R, stage) pairs that are compiled (the Stage lists of the launch functions, kernel units): the plan names one of them
         if (R == 1) cap = BCAP;
         if (R == 4 && cap == BCAP) cap = BCAP_MID;
     }

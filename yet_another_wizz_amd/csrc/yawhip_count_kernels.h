@@ -1,7 +1,8 @@
-// What the count kernels (yawhip.hip) and the count call that plans and launches them (yawhip_count.hip) have to agree on,
-// said once: the geometry of the kernels (workgroup, stage and tile sizes, the LDS a variant takes), the layout of the counter
-// block at the head of a call's result block, and the launch interface -- one record of what a launch needs from the call and
-// the functions that put the kernels on its stream. Included by exactly those two units; private like yawhip_internal.h.
+// What the count kernels (the kernel units: yawhip.hip and yawhip_kernel_*.hip, one per kernel family) and the count call that
+// plans and launches them (yawhip_count.hip) have to agree on, said once: the geometry of the kernels (workgroup, stage and
+// tile sizes, the LDS a variant takes), the layout of the counter block at the head of a call's result block, and the launch
+// interface -- one record of what a launch needs from the call and the functions that put the kernels on its stream. Included
+// by yawhip_count.hip and, through yawhip_count_device.h, by the kernel units; private like yawhip_internal.h.
 #ifndef YAWHIP_COUNT_KERNELS_H
 #define YAWHIP_COUNT_KERNELS_H
 #include <hip/hip_runtime.h>
@@ -89,7 +90,7 @@ constexpr double CLOCK_MS = 1.0e-5;  // milliseconds per tick of wall_clock64
 
 // LDS of a workgroup, per kernel family: the plan checks it against the limit, the launch asks for it, and where the kernel
 // lays out its dynamic LDS by the same sizes, host and device agree through the one function.
-int band_lds_fixed(int cap);  // k_count_band: its static image (BandLds<cap>::FIXED; defined with it, yawhip.hip)
+int band_lds_fixed(int cap);  // k_count_band: its static image (BandLds<cap>::FIXED; defined with it, yawhip_kernel_band64.hip)
 __host__ __device__ inline bool band_small_hist(bool weighted, int nslots, int hp) { return (size_t)nslots * hp * (weighted ? 8 : 4) <= 512; }
 // dynamic LDS bytes of a band workgroup (host and device agree through this one function)
 __host__ __device__ inline size_t band_lds_dynamic(bool weighted, bool need_thr, int nkb, int n_edges, int hp, int cap, int thr_rows) {
@@ -106,7 +107,7 @@ __host__ __device__ inline size_t band32_fine_lds(bool weighted, int cap, int ns
     return (size_t)3 * (cap + 4) * 4 + (weighted ? (size_t)(cap + 2) * 8 : 0) + (size_t)nslots * (weighted ? 8 : 4) + 64 * 8 +
            (size_t)rows * fine32_width(n_edges) * 4 + 48;
 }
-// (these rest on the records the kernels stage: defined with them, yawhip.hip)
+// (these rest on the records the kernels stage: defined with them, yawhip_kernel_plain.hip and yawhip_kernel_lean.hip)
 size_t count_lds(bool weighted, bool priv, int n_edges);   // k_count: two stages + thresholds + histogram(s)
 size_t merged_stage_lds();                                 // k_count_merged: its two float32 stages ...
 size_t merged_lds(bool weighted, int bins, int n_edges);   // ... + thresholds, histogram(s), pre-filter thresholds, survivor queue
@@ -147,7 +148,7 @@ static_assert(CTR_DONE < BAND_ENTRY_CTR(0) && ITEM_SEGS <= EVAL_SLOTS && TILE_PA
 
 // ------------------------------------------------------------------------------------------------
 // Launch interface: what the kernels of a call need from it, filled by count_enqueue from the plan and the active call
-// buffers. The launch functions (yawhip.hip) put kernels on L.stream and return the launch's status; they decide nothing --
+// buffers. The launch functions (kernel units) put kernels on L.stream and return the launch's status; they decide nothing --
 // which variant of a count kernel runs follows from the selectors, and a combination that is not compiled is
 // hipErrorInvalidValue.
 // ------------------------------------------------------------------------------------------------
@@ -191,6 +192,13 @@ hipError_t launch_build_whole(const CountLaunch &L);    // k_build_items<false>:
 hipError_t launch_item_work(const CountLaunch &L, int slots_per_job, unsigned long long *job_work);
 // the count kernel of L.family; its variant code (yawhip_stats.count_variant*) goes to *variant
 hipError_t launch_count(const CountLaunch &L, bool weighted, int32_t *variant);
+// ... which is one of these, each defined in the unit of its kernel family (launch_count chooses by L.family and L.one_chunk)
+hipError_t launch_plain(const CountLaunch &L, bool weighted, int32_t *variant);
+hipError_t launch_lean(const CountLaunch &L, bool weighted, int32_t *variant);
+hipError_t launch_band64(const CountLaunch &L, bool weighted, int32_t *variant);
+hipError_t launch_band32(const CountLaunch &L, bool weighted, int32_t *variant);
+hipError_t launch_band32_one(const CountLaunch &L, bool weighted, int32_t *variant);
+hipError_t launch_fine(const CountLaunch &L, bool weighted, int32_t *variant);
 hipError_t launch_reduce_chunks(const CountLaunch &L);
 hipError_t launch_reduce_slots(const CountLaunch &L);
 hipError_t launch_counts_to_double(const CountLaunch &L, int64_t n_out);

@@ -1,4 +1,4 @@
-// yawhip_ingest.hip -- how a catalogue gets onto the device and into the orders the count kernels read (yawhip.hip): nearest
+// yawhip_ingest.hip -- how a catalogue gets onto the device and into the orders the count kernels read (yawhip_kernel_*.hip): nearest
 // patch centres (yawhip_assign_patches), the upload in (patch, z-bin, u) order with its patch boxes and unit-norm check
 // (yawhip_catalog_*), the strip layouts (build_strip_layout) and their merged triple runs (build_triples), with the kernels
 // that build them. The sorts themselves are yawhip_sort.hip's. No count kernel is launched from here.

@@ -1,5 +1,5 @@
-// Shared by the translation units behind the C ABI of include/yawhip.h -- yawhip.hip (count kernels and their launch layer),
-// yawhip_count.hip (the count call that plans and launches them; the two share yawhip_count_kernels.h besides),
+// Shared by the translation units behind the C ABI of include/yawhip.h -- yawhip.hip and yawhip_kernel_*.hip (count kernels and their
+// launch layer), yawhip_count.hip (the count call that plans and launches them; they share yawhip_count_kernels.h besides),
 // yawhip_ingest.hip (catalogue upload and layouts), yawhip_dense.hip (dense epilogue) and yawhip_api.hip (contexts, options,
 // error reporting, wrappers of the other units): error reporting, the records the kernels and the layouts share, the context
 // and catalogue handles, and the few functions that cross units. Private: never installed, not part of the C ABI.
