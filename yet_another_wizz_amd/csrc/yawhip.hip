@@ -221,7 +221,7 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
         it.pad_ = (jr.o >> 2) & 1;  // 1: diagonal job of a self count: lanes walk only the entries behind their own place (see k_merge_triples)
         // swap: the lane tiles come from the first catalogue of the job (the binned one), the windows from the second
         const DevTab &c1 = s_tabs[swap ? 3 + o : o], &c2 = s_tabs[swap ? o : 3 + o];
-        const gf64p key1d = tab_key(c1), key2 = tab_key(c2);
+        const gf64p key1d = tab_key(c1);
         const gf32p key1f = c1.axis == 0 ? c1.qx : (c1.axis == 1 ? c1.qy : c1.qz);
         auto key1 = [&](int64_t i) { return triple ? (double)key1f[i] : key1d[i]; };
         // potential items of a job in the order (lane tile, group of neighbour offsets). One item carries up to MAX_WIN
@@ -232,15 +232,17 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
         // (a call has fewer than 2^31 potential items: 32-bit division, and none in the usual case of one group)
         const uint32_t local32 = (uint32_t)local, tl = ng == 1 ? local32 : local32 / (uint32_t)ng;
         const int g = (int)(local32 - tl * (uint32_t)ng);
-        const TileRec tr = c2.tile_rec[jr.t_lo + tl];
-        const int64_t r2 = tr.run, a0 = tr.a0, a1 = a0 + tr.na;
+        // (the tile's record brings the keys of its first and last object along: no look-up in the lane side's key column)
+        const __attribute__((address_space(1))) TileRec *trp = (const __attribute__((address_space(1))) TileRec *)(c2.tile_rec + (jr.t_lo + tl));
+        const struct { int64_t a0; int32_t na, run; double klo, khi; } tr = {trp->a0, trp->na, trp->run, trp->klo, trp->khi};
+        const int64_t r2 = tr.run, a0 = tr.a0;
         const double kpad = triple ? 1.2e-7 : 0.0;  // float32 rounding of a streamed key (|u| <= 1: 2^-24)
         // (half bands: no lane of the tile looks at an entry in front of the tile's first object -- the window starts there)
         // cap_s > 0 (band_trim): the window is trimmed to the caps the tile's first and last objects can reach (sep_angle)
-        double wlo = key2[a0] - (it.pad_ ? 0.0 : rwin) - kpad, whi = key2[a1 - 1] + rwin + kpad;
+        double wlo = tr.klo - (it.pad_ ? 0.0 : rwin) - kpad, whi = tr.khi + rwin + kpad;
         if (cap_s > 0.0) {
-            if (!it.pad_) wlo = cap_lo64(key2[a0], cap_c, cap_s) - kpad;
-            whi = cap_hi64(key2[a1 - 1], cap_c, cap_s) + kpad;
+            if (!it.pad_) wlo = cap_lo64(tr.klo, cap_c, cap_s) - kpad;
+            whi = cap_hi64(tr.khi, cap_c, cap_s) + kpad;
         }
         it.a0 = a0; it.na = tr.na; it.nwin = 0;
         it.slot = (int32_t)((unsigned)job | ((unsigned)o << 30)); it.pot = (int32_t)pot;
@@ -256,23 +258,24 @@ __global__ __launch_bounds__(BUILD_WG) void k_build_items_strips(const DevTab *_
             const int64_t s1 = r2 + jr.k_off + (dd - reach);
             const bool valid = dd < nd && s1 >= 0 && s1 < jr.n_strips1;
             const int64_t r1 = jr.vbase1 + (valid ? s1 : 0);
-            int64_t b0 = 0, b1 = 0;
-            if (valid) { b0 = c1.off[r1]; b1 = c1.off[r1 + 1]; }
+            // The head of the run's record says where the run begins, whether it has entries and between which keys they
+            // lie, in one round of loads (the offsets, the two keys behind them and inv were three rounds from three tables).
             // four partner runs in five lie entirely before or behind the tile's window (neighbouring patches share a
-            // boundary only): two loads settle those
-            const bool some = b1 > b0;
+            // boundary only): the head settles those
             // (loads under their condition: the texture path is what this kernel is bound by, and it charges the lanes of a
             // load that are switched on; a wave whose tiles face no live run skips them altogether)
-            double kfirst = 0.0, klast = 0.0;
-            if (some) { kfirst = key1(b0); klast = key1(b1 - 1); }
+            const __attribute__((address_space(1))) RunGrid *rg = (const __attribute__((address_space(1))) RunGrid *)(c1.grid + r1);
+            int64_t b0 = 0;
+            uint32_t n1 = 0;
+            double kfirst = 0.0, klast = 0.0, inv = 0.0;
+            if (valid) { b0 = rg->b0; kfirst = rg->first; klast = rg->last; inv = rg->inv; n1 = rg->n; }
+            const bool some = n1 > 0;
             const bool live = some && !(klast < wlo || kfirst > whi);
             // the run's index along the sort axis narrows both searches to one cell (RunGrid)
             uint32_t l0 = 0, l1 = 0, u0 = 0, u1 = 0;
             if (live) {
-                const double inv = c1.grid[r1].inv;
                 const int cl = run_cell(wlo, kfirst, inv), cu = run_cell(whi, kfirst, inv);
-                const uint32_t *gr = c1.grid[r1].g;
-                l0 = gr[cl]; l1 = gr[cl + 1]; u0 = gr[cu]; u1 = gr[cu + 1];
+                l0 = rg->g[cl]; l1 = rg->g[cl + 1]; u0 = rg->g[cu]; u1 = rg->g[cu + 1];
             }
             wb[j] = b0;
             sl[j] = l0; sh[j] = l1; ul[j] = u0; uh[j] = u1;  // all 0 for a dead window

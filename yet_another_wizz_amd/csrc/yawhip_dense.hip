@@ -185,38 +185,40 @@ void dense_scatter(const yawhip_dense_request &r, int32_t n_bins, int32_t n_scal
         cell[(size_t)j] = (int64_t)jobs[2 * j] * P + jobs[2 * j + 1];
         half[(size_t)j] = (r.halve_diagonal && jobs[2 * j] == jobs[2 * j + 1]) ? 0.5 : 1.0;
     }
-    // Slice by slice: the stores of a (scale, bin) land in one [P, P] slice (32 KB at the headline) while the reads walk the
-    // result block with a stride of one job's values -- 110 KB that stay in the cache over the bins. (Job by job, every store
-    // of a job went to another slice, P * P * 8 bytes apart: one cache set for all of them, 46 us at the headline against 19.)
-    const size_t PP = (size_t)(P * P);
-    auto slice = [&](double *dst, auto value) {
-        for (int64_t j = 0; j < n_jobs; ++j) dst[cell[(size_t)j]] = value(j) * half[(size_t)j];
+    // Two passes. The first reads the values front to back, once -- slice by slice, a walk with a stride of one job's values
+    // touched every line of the 110 KB block once per slice, 30 times in all: 0.65 us a slice at the headline, the first no more
+    // than the others, 21 us against 10 -- and lays them out as rows [row][job] with their factors
+    // applied, in the order of products the slices always had: (value x separation weight) x half. The second scatters slice by slice from a contiguous row: the stores of a (scale, bin) land in one [P, P] slice
+    // (32 KB at the headline). (Job by job, every store of a job went to another slice, P * P * 8 bytes apart: one cache set for
+    // all of them, 46 us at the headline.)
+    // rows: [bin][scale] of comb, else [bin] -- one fine bin per (job, bin) is the value of every scale that takes it
+    const size_t PP = (size_t)(P * P), nj = (size_t)n_jobs, n_rows = comb ? (size_t)n_bins * n_scales : (size_t)n_bins;
+    thread_local std::vector<double> rows;
+    rows.resize(n_rows * nj);
+    double *const rw = rows.data();
+    g_trace.mark("cells");
+    auto gather = [&](auto value) {
+        for (size_t j = 0; j < nj; ++j) {
+            const double hj = half[j];
+            for (size_t q = 0; q < n_rows; ++q) rw[q * nj + j] = value(j * n_rows + q, q) * hj;
+        }
     };
+    if (comb) {
+        gather([=](size_t at, size_t) { return comb[at]; });
+    } else if (weighted) {
+        if (fine_factors) gather([=](size_t at, size_t k) { return hs[at] * fine_factors[k]; });
+        else gather([=](size_t at, size_t) { return hs[at]; });
+    } else {
+        if (fine_factors) gather([=](size_t at, size_t k) { return (double)hc[at] * fine_factors[k]; });
+        else gather([=](size_t at, size_t) { return (double)hc[at]; });
+    }
+    g_trace.mark("rows");
     for (int s_ = 0; s_ < n_scales; ++s_)
         for (int k = 0; k < n_bins; ++k) {
             if (!(slices[2 * ((int64_t)k * n_scales + s_) + 1] > slices[2 * ((int64_t)k * n_scales + s_)])) continue;  // (cleared)
             double *dst = r.dense + ((size_t)s_ * n_bins + (size_t)k) * PP;
-            if (comb) {
-                const double *src = comb + (size_t)k * n_scales + s_;
-                const size_t stride = (size_t)n_bins * n_scales;
-                slice(dst, [=](int64_t j) { return src[(size_t)j * stride]; });
-            } else if (weighted) {
-                const double *src = hs + k;
-                if (fine_factors) {
-                    const double fk = fine_factors[(size_t)k];
-                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins] * fk; });
-                } else {
-                    slice(dst, [=](int64_t j) { return src[(size_t)j * n_bins]; });
-                }
-            } else {
-                const int64_t *src = hc + k;
-                if (fine_factors) {
-                    const double fk = fine_factors[(size_t)k];
-                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins] * fk; });
-                } else {
-                    slice(dst, [=](int64_t j) { return (double)src[(size_t)j * n_bins]; });
-                }
-            }
+            const double *row = rw + (comb ? (size_t)k * n_scales + s_ : (size_t)k) * nj;
+            for (size_t j = 0; j < nj; ++j) dst[cell[j]] = row[j];
         }
     g_trace.mark("scattered");
     g_trace.flush();

@@ -266,10 +266,11 @@ __global__ __launch_bounds__(256) void k_run_grid(int64_t n_runs, const int64_t 
     const int c = (int)(i - r * (RUN_GRID + 1));
     if (r >= n_runs) return;
     const int64_t b0 = off[r], b1 = off[r + 1];
-    double inv = 0.0, first = 0.0;
+    double inv = 0.0, first = 0.0, last = 0.0;
     if (b1 > b0) {
         first = (double)key[b0];
-        const double span = (double)key[b1 - 1] - first;
+        last = (double)key[b1 - 1];
+        const double span = last - first;
         inv = span > 0.0 ? (double)RUN_GRID / span : 0.0;
         if (!(inv < 1e300)) inv = 0.0;  // a denormal span: one cell
     }
@@ -279,7 +280,19 @@ __global__ __launch_bounds__(256) void k_run_grid(int64_t n_runs, const int64_t 
         if (run_cell((double)key[m], first, inv) < c) l = m + 1; else h = m;
     }
     grid[r].g[c] = (uint32_t)(l - b0);
-    if (c == 0) { grid[r].inv = inv; grid[r].g[RUN_GRID + 1] = 0; }
+    if (c == 0) {  // the head of the record: what the item builder reads of the run before g[] (an empty run: n = 0)
+        grid[r].b0 = b0; grid[r].first = first; grid[r].last = last; grid[r].inv = inv;
+        grid[r].n = (uint32_t)(b1 - b0);
+    }
+}
+
+// keys of the first and last object of every lane tile, into its record (the rest of the record comes from the host)
+__global__ __launch_bounds__(256) void k_tile_keys(int64_t n_tiles, const double *__restrict__ key, TileRec *__restrict__ rec) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tiles) return;
+    const int64_t a0 = rec[i].a0;
+    rec[i].klo = key[a0];
+    rec[i].khi = key[a0 + rec[i].na - 1];
 }
 
 // Merged triple runs of a strip layout (streamed side of the float32 band kernels). With a grid as wide as the largest
@@ -456,15 +469,20 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
         {  // record of every tile: the item builder decodes a potential item with one load instead of a search over the
            // prefix and a look-up of the run's offsets
             const int64_t n_tiles = L.h_tiles[ri][(size_t)n_runs];
-            std::vector<TileRec> tile_rec((size_t)std::max<int64_t>(n_tiles, 1), TileRec{0, 0, 0});
+            std::vector<TileRec> tile_rec((size_t)std::max<int64_t>(n_tiles, 1), TileRec{0, 0, 0, 0.0, 0.0});
             for (int64_t r = 0; r < n_runs; ++r)
                 for (int64_t tl = L.h_tiles[ri][(size_t)r]; tl < L.h_tiles[ri][(size_t)r + 1]; ++tl) {
                     const int64_t a0 = voff[(size_t)r] + (tl - L.h_tiles[ri][(size_t)r]) * tile;
-                    tile_rec[(size_t)tl] = TileRec{a0, (int32_t)std::min<int64_t>(tile, voff[(size_t)r + 1] - a0), (int32_t)r};
+                    tile_rec[(size_t)tl] = TileRec{a0, (int32_t)std::min<int64_t>(tile, voff[(size_t)r + 1] - a0), (int32_t)r, 0.0, 0.0};
                 }
             if (e == hipSuccess) e = L.d_tile_rec[ri].alloc(tile_rec.size());
             if (e == hipSuccess)
                 e = hipMemcpy(L.d_tile_rec[ri], tile_rec.data(), tile_rec.size() * sizeof(TileRec), hipMemcpyHostToDevice);
+            if (e == hipSuccess && n_tiles > 0) {  // the end keys live on the device (every tile has an object: a0 + na - 1 >= a0)
+                hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, ctx->stream, n_tiles,
+                                   o == 0 ? L.x : (o == 1 ? L.y : L.z), L.d_tile_rec[ri]);
+                e = hipGetLastError();
+            }
         }
         if (e == hipSuccess) e = L.d_tiles[ri].alloc((size_t)(n_runs + 1));
         if (e == hipSuccess)
@@ -486,9 +504,12 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     L.h_vbase = std::move(vbase);
     L.h_slo = std::move(slo);
     L.n_groups = n_groups;
+    // (the figure is pinned byte for byte by tests/test_gpu_ingest.py: the run and tile records count with RUN_GRID_ACCOUNTED and
+    // TILE_REC_ACCOUNTED bytes, their size without the item builder's heads -- 32 bytes per run and 16 per lane tile that
+    // yawhip_catalog_device_bytes does not report: about half a byte per object, under 1 % of the catalogue's bytes)
     L.device_bytes = (int64_t)col * (c->w ? 4 : 3) + (want_bins ? n * (int64_t)sizeof(int32_t) : 0) + 3 * L.q_stride * (int64_t)sizeof(float) +
-                     (4 * (n_runs + 1) + 2 * (int64_t)n_groups + 1) * (int64_t)sizeof(int64_t) + (n_runs + 1) * (int64_t)sizeof(RunGrid) +
-                     (L.h_tiles[0][(size_t)n_runs] + L.h_tiles[1][(size_t)n_runs] + L.h_tiles[2][(size_t)n_runs]) * (int64_t)sizeof(TileRec);
+                     (4 * (n_runs + 1) + 2 * (int64_t)n_groups + 1) * (int64_t)sizeof(int64_t) + (n_runs + 1) * RUN_GRID_ACCOUNTED +
+                     (L.h_tiles[0][(size_t)n_runs] + L.h_tiles[1][(size_t)n_runs] + L.h_tiles[2][(size_t)n_runs]) * TILE_REC_ACCOUNTED;
     c->device_bytes += L.device_bytes;
     L.built = true;
     return YAWHIP_OK;
@@ -545,7 +566,7 @@ int build_triples(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
         L.release_triples();
         return fail(e == hipErrorOutOfMemory ? YAWHIP_ERR_OOM : YAWHIP_ERR_HIP, "merged triple runs failed: %s", hipGetErrorString(e));
     }
-    const int64_t bytes = 3 * L.q3_stride * (int64_t)sizeof(float) + (int64_t)n3 * (4 + (c->w ? 8 : 0)) + n * 4 + (V3 + 1) * (int64_t)(sizeof(int64_t) + sizeof(RunGrid));
+    const int64_t bytes = 3 * L.q3_stride * (int64_t)sizeof(float) + (int64_t)n3 * (4 + (c->w ? 8 : 0)) + n * 4 + (V3 + 1) * ((int64_t)sizeof(int64_t) + RUN_GRID_ACCOUNTED);
     L.device_bytes += bytes;
     c->device_bytes += bytes;
     L.triples = true;

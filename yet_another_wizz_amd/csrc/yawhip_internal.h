@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -106,8 +107,8 @@ struct DevTab {
     gi32p k;                   // bin id per object (merged cross-correlation layouts), else null
     gi64p off;                 // run offsets [V+1] (strip layouts) or segment offsets
     gi64p vbase, slo, tiles;   // strip layouts: first run of a group, its grid index, lane-tile prefix over runs
-    const struct TileRec *tile_rec;  // strip layouts: first object, length and run of every lane tile
-    const struct RunGrid *grid;      // strip layouts: per-run index along the sort axis (item builder)
+    const struct TileRec *tile_rec;  // strip layouts: first object, length, run and end keys of every lane tile
+    const struct RunGrid *grid;      // strip layouts: per-run record and index along the sort axis (item builder)
     gf32p qx, qy, qz;          // strip layouts: float32 images of the columns (k_count_band32)
     gi32p idx;                 // merged triple runs (streamed side): index of an entry in the layout's own order, else null
     gi32p pos3;                // lane side of a self count on merged triple runs: place of an object in its own strip's triple, else null
@@ -119,11 +120,13 @@ __device__ __forceinline__ gf64p tab_key(const DevTab &t) { return t.axis == 0 ?
 // Tables of the strip item builder. Every thread of the builder walks a chain of dependent loads and the chain's length
 // is the kernel's run time (0.06 of the 0.55 ms of a headline call), so what the host or the layout build can precompute
 // travels as one record per job, per lane tile and per run instead of being looked up table by table.
-struct TileRec {   // per lane tile of a layout (one table per tile size)
+struct alignas(16) TileRec {   // per lane tile of a layout (one table per tile size)
     int64_t a0;    // first object
     int32_t na;    // objects (<= tile)
     int32_t run;   // run the tile belongs to
+    double klo, khi;  // sort keys of the tile's first and last object (k_tile_keys): what the builder's window starts from
 };
+static_assert(sizeof(TileRec) == 32, "TileRec is read as two 16-byte words");
 struct JobRec {    // per job of a call
     int64_t t_lo;      // first lane tile of the job (absolute index into the lane side's tile table)
     int64_t k_off;     // strip of the streamed group facing lane run r2 under neighbour offset d: r2 + k_off + d
@@ -137,11 +140,22 @@ struct JobRec {    // per job of a call
 // table is built and when it is queried, so for any w the first entry with key >= w and the first with key > w both lie in
 // [g[cell(w)], g[cell(w) + 1]] -- exactly, whatever the rounding of the product: the bisection over a run of 900 entries
 // (ten dependent loads) becomes one table look-up and four steps.
+// In front of g[] stands what the item builder needs to know about the run before it looks at g[]: where the run begins, how
+// long it is and the keys of its first and last entry, as the double the builder compares (a merged triple run's keys are
+// float32 images, widened). One aligned read of the record replaces the loads of two offsets, two keys and inv from three
+// tables, two of them dependent on the first. A zeroed record is an empty run.
 constexpr int RUN_GRID = 64;
-struct RunGrid {
+struct alignas(16) RunGrid {
+    int64_t b0;                  // first entry of the run in its table
+    double first, last;          // keys of its first and last entry (0 for an empty run)
     double inv;                  // RUN_GRID / (last - first), 0 for a run with one distinct key
-    uint32_t g[RUN_GRID + 2];    // + 1 pad: 8-byte multiple
+    uint32_t n;                  // entries: 0 = empty run, nothing else of the record is looked at
+    uint32_t g[RUN_GRID + 1];
 };
+static_assert(sizeof(RunGrid) == 304 && offsetof(RunGrid, n) == 32, "RunGrid: a 36-byte head in front of g[]");
+// What a run and a tile record count for in yawhip_catalog_device_bytes: their sizes before the builder's heads were added
+// (inv + g[RUN_GRID + 2]; a0, na, run). The reported figure is pinned by tests/test_gpu_ingest.py.
+constexpr int64_t RUN_GRID_ACCOUNTED = 8 + 4 * (RUN_GRID + 2), TILE_REC_ACCOUNTED = 16;
 __device__ __forceinline__ int run_cell(double key, double first, double inv) {
     const double f = (key - first) * inv;
     return f >= (double)RUN_GRID ? RUN_GRID - 1 : (f >= 1.0 ? (int)f : 0);
@@ -292,7 +306,7 @@ struct StripLayout {
     std::vector<int64_t> h_slo;       // [G]   global strip index of a group's first run
     std::vector<int64_t> h_tiles[3];  // [V+1] prefix of lane tiles over the runs, for tiles of MWG * {1, 2, 4} objects
     DevPtr<int64_t> d_vbase, d_slo, d_tiles[3];
-    DevPtr<TileRec> d_tile_rec[3];    // [tiles] first object, length and run of every lane tile
+    DevPtr<TileRec> d_tile_rec[3];    // [tiles] first object, length, run and end keys of every lane tile
     DevPtr<RunGrid> d_grid;           // [V+1] per-run index along the sort axis (item builder)
     // merged triple runs (k_merge_triples), built when a float32 band kernel first streams this layout
     bool triples = false;
