@@ -663,6 +663,44 @@ int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_sh
                         const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
                         double *fine_w, yawhip_stats *stats);
 
+/*
+ * The excess surface density sums binned in each lens's OWN radius R = D(z_l) theta instead of one angle per redshift slice
+ * (measurements.crosscorrelate_delta_sigma(radius="lens")). Additive to ABI 6: new symbols only.
+ *
+ * yawhip_dsigma_upload_lenses_radial   yawhip_dsigma_upload_lenses with one more column m, float64[n]: the SQUARED transverse
+ *                       distance per radian of the lens, in the squared unit of the radii the caller will pass (the library is
+ *                       unit-free; the driver passes D_A(z_l)^2 for physical radii). Every m is finite and > 0, else
+ *                       YAWHIP_ERR_INVALID (the host pass that checks f and c). The handle keeps m in segment order and, per
+ *                       redshift bin, the minimum of m over all patches (one value with n_bins = 1). It is freed by
+ *                       yawhip_shear_free; yawhip_dsigma_count accepts it and ignores m; the three shear counts refuse it
+ *                       as they refuse any lens handle.
+ * yawhip_dsigma_count_radial   yawhip_dsigma_count with r2 in the place of t: float64[n_bins][n_edges] ascending SQUARED radius
+ *                       edges per row, finite and >= 0, n_edges <= 256. Jobs, cells, segments, output planes and statistics are
+ *                       those of yawhip_dsigma_count. A pair (lens l of segment (p, k), source s of patch q) is handled in
+ *                       float64, every operation rounded on its own and nothing contracted:
+ *       s2  = ((sx - lx)^2 + (sy - ly)^2) + (sz - lz)^2          the separation of every count, source minus lens
+ *       q   = 1/16632;  q = 1/3150 + s2 q;  q = 1/560 + s2 q;  q = 1/90 + s2 q;  q = 1/12 + s2 q;  q = 1 + s2 q
+ *       th2 = s2 q                                               (2 asin(sqrt(s2) / 2))^2: the squared angle
+ *       R2  = m_l th2
+ *       fine bin e  iff  r2[k][e] < R2 <= r2[k][e + 1]           none: the pair adds nothing
+ *     (the coefficients are the double quotients 1.0 / 12.0 ... 1.0 / 16632.0). The pair term, the den == 0 rule and the
+ *     eff <= 0 rule are yawhip_dsigma_count's, operation by operation.
+ *     The series is within 2 * 2^-53 (relative) of the squared angle for s2 <= 0.01, i.e. theta <= 5.73 degrees. The call
+ *     refuses larger reaches before any device work: with smax[k] = r2[k][n_edges - 1] / min_m[k] * (1 + 1e-12) (min_m[k] the
+ *     handle's minimum of bin k, of its one bin when the lenses are unbinned; a bin without lenses has smax = 0), any
+ *     smax[k] > 0.01 is YAWHIP_ERR_INVALID, "a lens is too close for the largest radius".
+ *   lenses       a handle of yawhip_dsigma_upload_lenses_radial (one without m: YAWHIP_ERR_MISMATCH)
+ * Kernel: the walk of yawhip_dsigma_count with 64-byte streamed objects (x, y, z, m | w, f, c, pad); the sort-key window of
+ * row k has the half width sqrt(smax[k]) (1 + 1e-12) + 1e-15, so the evaluated separations follow the NEAREST lens of the bin.
+ * Accumulation, reproducibility and every other error are those of yawhip_dsigma_count.
+ */
+int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                       const double *f, const double *c, const double *m, int32_t n_patches, int32_t n_bins,
+                                       const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                               const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *r2, double *fine_t, double *fine_x,
+                               double *fine_w, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     "yawhip_dsigma_upload_lenses",
     "yawhip_dsigma_upload_sources",
     "yawhip_dsigma_count",
+    "yawhip_dsigma_upload_lenses_radial",
+    "yawhip_dsigma_count_radial",
 )
 
 
@@ -287,6 +289,9 @@ def load_library() -> ctypes.CDLL:
                                                  ctypes.c_int32, ctypes.POINTER(_vp)]
     lib.yawhip_dsigma_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, _dp,
                                         ctypes.POINTER(_Stats)]
+    lib.yawhip_dsigma_upload_lenses_radial.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32,
+                                                       ctypes.c_int32, _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
+    lib.yawhip_dsigma_count_radial.argtypes = lib.yawhip_dsigma_count.argtypes
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -826,24 +831,29 @@ class DsigmaLenses(ShearSources):
     """The lenses of ``dsigma_count`` resident in HBM (``yawhip_dsigma_upload_lenses``): every (patch, bin) segment sorted along
     ``sort_axis`` -- unit vectors, weights (or None) and the two columns ``f, c`` (include/yawhip.h: ``D_A(z_l)`` and ``chi_l``
     in the driver), finite and ``>= 0``, kept as they come. The handle is a ``yawhip_shear_sources`` marked as lenses: it is
-    freed like one, and the shear counts refuse it."""
+    freed like one, and the shear counts refuse it. With ``m`` (finite and ``> 0``: the squared transverse distance per radian
+    of every lens, in the squared unit of the radii) it is the radial handle ``dsigma_count_radial`` needs
+    (``yawhip_dsigma_upload_lenses_radial``); ``dsigma_count`` takes it too and ignores ``m``."""
 
-    def __init__(self, ctx: Context, x, y, z, w, f, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2):
+    def __init__(self, ctx: Context, x, y, z, w, f, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2, m=None):
         self._h = _vp()
-        x, y, z, w, f, c = (_f64(col) for col in (x, y, z, w, f, c))
+        x, y, z, w, f, c, m = (_f64(col) for col in (x, y, z, w, f, c, m))
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(x)
-        if any(col is not None and len(col) != n for col in (y, z, w, f, c)):
+        if any(col is not None and len(col) != n for col in (y, z, w, f, c, m)):
             raise ValueError("catalogue columns differ in length")
         if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
             raise ValueError("offsets must have n_patches * n_bins + 1 entries")
         self.ctx = ctx  # keep the context alive
         self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
         self.n_bins = int(n_bins)
-        _check(load_library().yawhip_dsigma_upload_lenses(ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp),
-                                                          _ptr(f, _dp), _ptr(c, _dp), self.n_patches, self.n_bins,
-                                                          _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
-               "yawhip_dsigma_upload_lenses")
+        self.radial = m is not None
+        columns = (ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(f, _dp), _ptr(c, _dp))
+        layout = (self.n_patches, self.n_bins, _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h))
+        if self.radial:
+            _check(load_library().yawhip_dsigma_upload_lenses_radial(*columns, _ptr(m, _dp), *layout), "yawhip_dsigma_upload_lenses_radial")
+        else:
+            _check(load_library().yawhip_dsigma_upload_lenses(*columns, *layout), "yawhip_dsigma_upload_lenses")
         ctx._shear.add(self)
 
 
@@ -877,6 +887,12 @@ def dsigma_count(ctx: Context, lenses: DsigmaLenses, sources: ShearSources, jobs
     (lens patch, source patch); thresholds f64[B, E]. Returns ``(T, X, W, CountStats)``, f64[n_jobs, B, E-1] each: the sums of
     ``w_l w_s S gamma_t``, ``w_l w_s S gamma_x`` and ``w_l w_s S^2`` over the pairs with ``S = f (1 - c u) > 0``."""
     return _shear_counts("yawhip_dsigma_count", 3, (ctx._h, lenses._h, sources._h), jobs, thresholds)
+
+
+def dsigma_count_radial(ctx: Context, lenses: DsigmaLenses, sources: ShearSources, jobs, r2):
+    """Run ``yawhip_dsigma_count_radial``: ``dsigma_count`` with the pairs binned by ``R^2 = m_l theta^2`` of each lens against
+    the squared radius edges ``r2`` f64[B, E]; ``lenses`` a ``DsigmaLenses`` with ``m``. Returns ``(T, X, W, CountStats)``."""
+    return _shear_counts("yawhip_dsigma_count_radial", 3, (ctx._h, lenses._h, sources._h), jobs, r2)
 
 
 def shear_auto_count(ctx: Context, sources: ShearSources, jobs, thresholds):

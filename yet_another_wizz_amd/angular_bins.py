@@ -15,7 +15,7 @@ import math
 
 import numpy as np
 
-__all__ = ["AngularBinPlan", "plan_for_limits", "parse_ang_limits", "get_ang_bins", "logarithmic_mid",
+__all__ = ["AngularBinPlan", "RadialBinPlan", "plan_for_limits", "radial_plan_for_limits", "parse_ang_limits", "get_ang_bins", "logarithmic_mid",
            "get_counts_for_limits", "chord_thresholds"]
 
 
@@ -74,10 +74,12 @@ class AngularBinPlan:
 
     __slots__ = ("limits", "ang_bins", "thresholds", "rweight", "_scale_factor", "_slices")
 
+    _thresholds_of = staticmethod(chord_thresholds)  # what the device compares against (RadialBinPlan: another rule)
+
     def __init__(self, limits, ang_bins, rweight):
         self.limits = limits
         self.ang_bins = ang_bins
-        self.thresholds = chord_thresholds(ang_bins)
+        self.thresholds = self._thresholds_of(ang_bins)
         self.rweight = rweight
         self._scale_factor = None
         if rweight is not None:  # trees.py:358-360
@@ -104,6 +106,34 @@ class AngularBinPlan:
         for s, (first, last) in enumerate(self._slices):
             out[..., s] = fine[..., first:last].sum(axis=-1)
         return out
+
+
+class RadialBinPlan(AngularBinPlan):
+    """The plan of a count binned in each lens's own radius (``crosscorrelate_delta_sigma(radius="lens")``): ``limits`` and
+    ``ang_bins`` hold radii in the place of angles, made by the same ``get_ang_bins`` with its log10 round trip; the
+    device compares ``R^2 = m_l theta^2`` against ``thresholds = edges * edges``. Slices and separation weights come from the
+    radii as ``AngularBinPlan`` makes them from angles. No redshift enters: the same plan serves every redshift bin."""
+
+    __slots__ = ()
+
+    @staticmethod
+    def _thresholds_of(edges):
+        edges = np.asarray(edges, dtype=np.float64)
+        return edges * edges
+
+
+def radial_plan_for_limits(r_min, r_max, rweight=None, resolution=None) -> RadialBinPlan:
+    """``plan_for_limits`` for lower / upper limits that are radii (any unit, ``> 0`` and finite)."""
+    lo = np.atleast_1d(r_min).astype(np.float64)
+    hi = np.atleast_1d(r_max).astype(np.float64)
+    if lo.ndim != 1 or hi.ndim != 1 or len(lo) != len(hi):
+        raise ValueError("'r_min' and 'r_max' must be 1-dim and of one length")
+    if np.any(lo >= hi) or np.any(lo <= 0.0) or not np.all(np.isfinite(hi)):
+        raise ValueError("0 < 'r_min' < 'r_max' < inf not satisfied")
+    limits = np.column_stack((lo, hi))
+    if rweight is not None and resolution is None:
+        resolution = 50
+    return RadialBinPlan(limits, get_ang_bins(limits, rweight, resolution), rweight)
 
 
 def plan_for_limits(ang_min, ang_max, rweight=None, resolution=None) -> AngularBinPlan:

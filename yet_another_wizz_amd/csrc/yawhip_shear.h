@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (tangential shear, shear-shear and excess-surface-density counts, yawhip_shear_* and
-// yawhip_dsigma_*, include/yawhip.h; DESIGN.md sections 15 to 18): the source handle and what its kernels see of it. Never
+// yawhip_dsigma_*, include/yawhip.h; DESIGN.md sections 15 to 19): the source handle and what its kernels see of it. Never
 // installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
@@ -14,7 +14,8 @@
 // (yawhip_shear_upload) is the unbinned catalogue of yawhip_shear_count, nb redshift bins that of yawhip_shear_auto_count and
 // of yawhip_shear_pair_count. A handle of yawhip_dsigma_upload_sources is an unbinned one with the column u besides; one of
 // yawhip_dsigma_upload_lenses (`lenses`) holds the lens columns f, c, as they came, in the place of wg1, wg2: only
-// yawhip_dsigma_count takes it.
+// yawhip_dsigma_count takes it. One of yawhip_dsigma_upload_lenses_radial is such a lens handle with the column m besides
+// (the squared transverse distance per radian of every lens), which yawhip_dsigma_count_radial bins by.
 struct yawhip_shear_sources {
     yawhip_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -25,6 +26,8 @@ struct yawhip_shear_sources {
     yawhip_detail::DevPtr<double> wg1, wg2;     // w * g1, w * g2, each product rounded on its own (g1, g2 without weights)
     yawhip_detail::DevPtr<double> u;            // the sources' column of yawhip_dsigma_count, or null
     bool lenses = false;                        // a lens handle: wg1, wg2 hold f, c
+    yawhip_detail::DevPtr<double> m;            // a radial lens handle: the lenses' column m in segment order, or null
+    std::vector<double> min_m;                  // ... and its minimum per redshift bin over all patches [nb] (+inf: no lens)
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;
     // per-call buffers of the counts (grow-only; yawhip_shear_pair_count uses those of its first handle)
@@ -44,6 +47,10 @@ struct ShearView {
 
 struct LensView : ShearView {  // a lens handle streamed by yawhip_dsigma_count: wg1, wg2 are f, c
     int nb;
+};
+
+struct RadialView : LensView {  // a radial lens handle streamed by yawhip_dsigma_count_radial
+    const double *m;
 };
 
 struct SourceView : ShearView {  // the sources of yawhip_dsigma_count in the lanes

@@ -4,9 +4,11 @@
 // measurements.autocorrelate_shear), and the same sums between any two (patch, bin) segments of one or
 // two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic), and the excess
 // surface density sums of sources with a distance column around lenses with two (yawhip_dsigma_count;
-// measurements.crosscorrelate_delta_sigma). include/yawhip.h has the contracts, product by product.
+// measurements.crosscorrelate_delta_sigma), those binned in each lens's own radius instead of one angle
+// per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers). include/yawhip.h
+// has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under four thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under five thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -33,6 +35,8 @@
 // DeltaSigma (k_count_dsigma) is Tangential with the lenses as a handle of their own: the streamed object is an Obj6
 // (x, y, z, w, f, c), the lane carries the source's u besides, and the pair term is Tangential's rotation scaled by the pair's
 // s = f (1 - c u), dropped altogether where 1 - c u <= 0 (the source in front of its lens).
+// DeltaSigmaRadial (k_count_dsigma_radial) is DeltaSigma with a 64-byte streamed object (x, y, z, m | w, f, c, pad): the ballot
+// holds m_l s2 against the row's last squared radius, and behind it the pair is binned by R2 = m_l th2(s2) (at the policy).
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -55,7 +59,7 @@
 //
 //   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products (a lens
 //                    handle keeps its two columns f, c as they came).
-//   k_gather_column  the same gather of the sources' column u.
+//   k_gather_column  the same gather of the sources' column u and of a radial lens handle's column m.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,6 +89,12 @@ struct alignas(16) Obj6 {  // one streamed object of the shear-shear count: thre
     double x, y, z, w, g1, g2;  // (g1, g2: the weighted shear wg1, wg2 of the handle)
 };
 
+// One streamed lens of the per-lens radial count: (x, y, z, m | w, f, c, pad). The hot loop reads the first 32 bytes (two
+// 16-byte broadcast reads, as Tangential reads its Obj), the second half only behind the ballot.
+struct alignas(16) Obj8 {
+    double x, y, z, m, w, g1, g2, pad;  // (g1, g2: the lens columns f, c, where a lens handle keeps them)
+};
+
 struct Lane {  // what a lane keeps of its own object in registers (g1, g2: the weighted shear; u: DeltaSigma's column, else 0)
     double x, y, z, w, g1, g2, rho2, u;
 };
@@ -109,7 +119,19 @@ struct Cell {
 // The policies of shear_walk (the table at the head of the file). cell() reads the call's table; add() is the pair term:
 // `wh` the wave's histogram [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of
 // include/yawhip.h.
-struct Tangential {
+//
+// Two seams say what a pair is binned by: outer(b, s) is what the ballot holds against the row's last edge, binned(b, s) what
+// is bisected over the row behind it (s: the pair's squared chord, b: the streamed object). Where a count bins the chord
+// itself both ARE s and compile away; then s <= last edge also keeps the bisection inside the row (CAPPED).
+struct ChordBinned {
+    static constexpr bool CAPPED = true;
+    template <class B>
+    static __device__ __forceinline__ double outer(const B &, double s) { return s; }
+    template <class B>
+    static __device__ __forceinline__ double binned(const B &, double s) { return s; }
+};
+
+struct Tangential : ChordBinned {
     using View = CatView;  // the streamed side: the lenses
     using Streamed = Obj;
     using Read = Obj;      // the hot loop reads the whole object: two ds_read_b128
@@ -146,7 +168,7 @@ struct Tangential {
     }
 };
 
-struct ShearShear {
+struct ShearShear : ChordBinned {
     using View = ShearView;  // the streamed side: the handle itself
     using Streamed = Obj6;
     using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
@@ -210,7 +232,7 @@ struct ShearPair : ShearShear {
 };
 
 // Tangential around the lenses of a lens handle (its columns wg1, wg2 hold f, c as they came), the sources with their column u.
-struct DeltaSigma {
+struct DeltaSigma : ChordBinned {
     using View = LensView;  // the streamed side: the lens handle, a ShearView with its bin count
     using Streamed = Obj6;  // (x, y, z, w, f, c)
     using Read = const Obj6 &;  // the hot loop reads x, y, z; w, f, c behind the ballot (ShearShear's reads)
@@ -252,6 +274,45 @@ struct DeltaSigma {
     }
 };
 
+// DeltaSigma binned in each lens's own radius (k_count_dsigma_radial): the row holds squared radii r2,
+// the lens streams its m (squared transverse distance per radian) next to x, y, z, and a pair is binned by
+//   R2 = m_l th2,   th2 = s2 q(s2) = (2 asin(sqrt(s2) / 2))^2,   q = 1 + s2 / 12 + s2^2 / 90 + s2^3 / 560 + s2^4 / 3150 + s2^5 / 16632
+// (Horner, every operation rounded on its own; the call caps s2 at 0.01, where the series is good to 2 ulp).
+// The ballot holds fl(m_l s2) against the last edge. That is an EXACT superset of the pairs in range, with no guard term:
+// every coefficient and s2 are >= 0, so each Horner step is >= its constant and the last one gives q >= 1 after rounding;
+// rounding is monotone, so th2 = fl(s2 q) >= fl(s2 * 1) = s2 and R2 = fl(m th2) >= fl(m s2) (m > 0). A pair with
+// R2 <= r2max therefore has fl(m s2) <= r2max. The converse fails (R2 may exceed the last edge behind the ballot): the
+// bisection then runs off the row and the pair is dropped (!CAPPED).
+struct DeltaSigmaRadial : DeltaSigma {
+    using View = RadialView;
+    using Streamed = Obj8;      // (x, y, z, m | w, f, c, pad)
+    using Read = const Obj8 &;  // the hot loop reads x, y, z, m (two ds_read_b128); w, f, c behind the ballot
+    static constexpr bool CAPPED = false;
+    // Beyond the window (!have) the object is padding with m = 0, which WOULD pass the outer test: nobody reads it, the loop
+    // over a stage stops at the stage's count n.
+    static __device__ Obj8 load(const RadialView &lens, int64_t i, bool have) {
+        Obj8 o = load_xyzw<Obj8>(lens, i, have);
+        o.m = have ? lens.m[i] : 0.0;
+        o.g1 = have ? lens.wg1[i] : 0.0; o.g2 = have ? lens.wg2[i] : 0.0;
+        o.pad = 0.0;
+        return o;
+    }
+    static __device__ __forceinline__ double outer(const Obj8 &b, double s) { return b.m * s; }
+    static __device__ __forceinline__ double binned(const Obj8 &b, double s) {
+        double q = 1.0 / 16632.0;
+        q = 1.0 / 3150.0 + s * q;
+        q = 1.0 / 560.0 + s * q;
+        q = 1.0 / 90.0 + s * q;
+        q = 1.0 / 12.0 + s * q;
+        q = 1.0 + s * q;
+        const double th2 = s * q;
+        return b.m * th2;
+    }
+    static __device__ void add(const Lane &a, const Obj8 &b, double *wh, int e, int nf) {
+        DeltaSigma::add(a, Obj6{b.x, b.y, b.z, b.w, b.g1, b.g2}, wh, e, nf);  // the pair term is DeltaSigma's
+    }
+};
+
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
 template <class P>
 constexpr size_t lds_bytes(int n_edges) {
@@ -259,7 +320,8 @@ constexpr size_t lds_bytes(int n_edges) {
            (size_t)WAVES * P::PLANES * (n_edges - 1) * sizeof(double);
 }
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024 &&
-                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024 && lds_bytes<DeltaSigma>(MAX_EDGES) <= 64 * 1024,
+                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024 && lds_bytes<DeltaSigma>(MAX_EDGES) <= 64 * 1024 &&
+                  lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= 64 * 1024,  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
@@ -390,15 +452,18 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
                 const double zz = dz * dz;
                 const double sxy = xx + yy;
                 const double s = sxy + zz;
-                if (__builtin_amdgcn_ballot_w64(s <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
-                    if (ok && s <= tmax) {
-                        int cnt = 0, hi = n_edges;  // edges below s (they ascend): the first e with thr[e] >= s, by bisection
+                const double so = P::outer(b, s);  // (s itself, but for the radial count)
+                if (__builtin_amdgcn_ballot_w64(so <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
+                    if (ok && so <= tmax) {
+                        const double v = P::binned(b, s);
+                        int cnt = 0, hi = n_edges;  // edges below v (they ascend): the first e with thr[e] >= v, by bisection
                         while (cnt < hi) {
                             const int mid = (cnt + hi) >> 1;
-                            if (thr[mid] < s) cnt = mid + 1; else hi = mid;
+                            if (thr[mid] < v) cnt = mid + 1; else hi = mid;
                         }
-                        // t[cnt-1] < s <= t[cnt], and not the lower half of a diagonal cell
-                        if (cnt > 0 && (!P::DIAGONAL || i > rel)) P::add(a, b, wh, cnt - 1, nf);
+                        // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the radial count alone -- has cnt == n_edges and no bin:
+                        // the histogram has nf of them), and not the lower half of a diagonal cell
+                        if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) P::add(a, b, wh, cnt - 1, nf);
                     }
                 }
             }
@@ -449,6 +514,14 @@ __global__ __launch_bounds__(WG) void k_count_dsigma(LensView lens, SourceView s
     shear_walk<DeltaSigma>(lens, src, jobs, n_bins, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
+// out: [3][n_cells][E-1] (T, X, W); r2: [n_bins][n_edges] squared radii, rwin: [n_bins] from the nearest lens of each bin
+__global__ __launch_bounds__(WG) void k_count_dsigma_radial(RadialView lens, SourceView src, const int32_t *__restrict__ jobs,
+                                                            int n_bins, int n_edges, const double *__restrict__ r2,
+                                                            const double *__restrict__ rwin, int64_t n_cells, double *__restrict__ out,
+                                                            unsigned long long *__restrict__ evaluated) {
+    shear_walk<DeltaSigmaRadial>(lens, src, jobs, n_bins, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
 }  // namespace
 
 extern "C" {
@@ -469,10 +542,10 @@ namespace {
 
 // the upload of every entry point: n_bins segments per patch (1: the unbinned catalogue of yawhip_shear_upload), each sorted
 // along sort_axis and gathered. u: the extra column of yawhip_dsigma_upload_sources or NULL; lenses: a lens handle, whose
-// (g1, g2) = (f, c) are gathered without the weight
+// (g1, g2) = (f, c) are gathered without the weight; m: the extra column of a radial lens handle or NULL
 int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                     const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets, int32_t sort_axis,
-                    yawhip_shear_sources **out, const double *u = nullptr, bool lenses = false) {
+                    yawhip_shear_sources **out, const double *u = nullptr, bool lenses = false, const double *m = nullptr) {
     if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
     *out = nullptr;
     if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
@@ -500,15 +573,16 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
-    constexpr int NC = 7;
-    DevPtr<double> raw[NC];  // x, y, z, g1, g2, w, u as they came (temporary)
-    const double *host[NC] = {x, y, z, g1, g2, w, u};
+    constexpr int NC = 8;
+    DevPtr<double> raw[NC];  // x, y, z, g1, g2, w, u, m as they came (temporary)
+    const double *host[NC] = {x, y, z, g1, g2, w, u, m};
     DevPtr<uint32_t> perm;
     hipError_t e = hipSuccess;
     for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
         if (e == hipSuccess) e = c->alloc(n1);
     if (e == hipSuccess && w) e = s->w.alloc(n1);
     if (e == hipSuccess && u) e = s->u.alloc(n1);
+    if (e == hipSuccess && m) e = s->m.alloc(n1);
     if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
     for (int c = 0; c < NC; ++c)
         if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
@@ -526,6 +600,10 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
         }
         if (e == hipSuccess && u) {
             hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], s->u);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && m) {
+            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[7], s->m);
             e = hipGetLastError();
         }
     }
@@ -578,7 +656,7 @@ int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_p
 template <class Launch>
 int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, size_t n_table, const int32_t *table, size_t n_cells,
               int32_t n_bins, int32_t n_edges, const double *t, int n_planes, double *const *fine, int64_t candidates,
-              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Launch launch) {
+              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Launch launch, const double *reach = nullptr) {
     if (stats) *stats = yawhip_stats{};
     if (n_cells == 0) return YAWHIP_OK;
     const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + n_table * sizeof(int32_t);
@@ -595,7 +673,9 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, si
     memcpy(h_t, t, n_t * sizeof(double));
     // a pair passes s2 <= t_max only if |du| <= sqrt(t_max) (1 + 2 eps) along any axis u (s2 >= fl(du^2), du rounded once);
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
-    for (int k = 0; k < n_bins; ++k) h_rwin[k] = std::sqrt(t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
+    // (reach[k]: the largest squared chord of a pair in range of row k where the row's last edge is not that -- the radial count)
+    for (int k = 0; k < n_bins; ++k)
+        h_rwin[k] = std::sqrt(reach ? reach[k] : t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
     memcpy(h_rwin + n_bins, table, n_table * sizeof(int32_t));
 
     HIP_TRY(hipSetDevice(ctx->device));
@@ -644,6 +724,42 @@ int check_column(const char *fn, const char *name, int64_t n, const double *v) {
     for (int64_t i = 0; i < n; ++i)
         if (!(v[i] >= 0.0) || std::isinf(v[i]))
             return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number >= 0 (index %lld)", fn, name, (long long)i);
+    return YAWHIP_OK;
+}
+
+// the column m of yawhip_dsigma_upload_lenses_radial: finite and > 0
+int check_positive(const char *fn, const char *name, int64_t n, const double *v) {
+    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
+    for (int64_t i = 0; i < n; ++i)
+        if (!(v[i] > 0.0) || std::isinf(v[i]))
+            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number > 0 (index %lld)", fn, name, (long long)i);
+    return YAWHIP_OK;
+}
+
+// the argument checks of the two excess-surface-density counts (t: thresholds or squared radii), and their candidate pairs
+int check_dsigma(const char *fn, yawhip_ctx *ctx, const yawhip_shear_sources *lenses, const yawhip_shear_sources *sources, int32_t n_jobs,
+                 const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, bool planes, int64_t *candidates) {
+    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "%s: NULL handle", fn);
+    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && planes)) return rc;
+    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (!lenses->lenses) return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses", fn);
+    if (sources->lenses || !sources->u)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are not a handle of yawhip_dsigma_upload_sources", fn);
+    if (sources->nb != 1)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are binned in redshift (%d bins): upload them unbinned", fn, sources->nb);
+    if (lenses->n_patches != sources->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
+    if (lenses->nb != 1 && lenses->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
+    *candidates = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
+        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
+        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
+                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
+        *candidates += n_src * n_lens;
+    }
     return YAWHIP_OK;
 }
 
@@ -807,28 +923,9 @@ int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_sh
                         double *fine_w, yawhip_stats *stats) {
     const char *fn = "yawhip_dsigma_count";
     const auto wall0 = std::chrono::steady_clock::now();
-    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_dsigma_count: NULL handle");
-    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
-    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (!lenses->lenses) return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the lenses are not a handle of yawhip_dsigma_upload_lenses");
-    if (sources->lenses || !sources->u)
-        return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the sources are not a handle of yawhip_dsigma_upload_sources");
-    if (sources->nb != 1)
-        return fail(YAWHIP_ERR_MISMATCH, "yawhip_dsigma_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
-    if (lenses->n_patches != sources->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
-    if (lenses->nb != 1 && lenses->nb != n_bins)
-        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
-    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
-
     int64_t candidates = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
-        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
-        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
-                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
-        candidates += n_src * n_lens;
-    }
+    if (const int rc = check_dsigma(fn, ctx, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, fine_t && fine_x && fine_w, &candidates))
+        return rc;
     double *const fine[] = {fine_t, fine_x, fine_w};
     return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, DeltaSigma::PLANES, fine, candidates, wall0, stats,
                      [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
@@ -837,6 +934,72 @@ int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_sh
                                             LensView{view_of(lenses), lenses->nb}, SourceView{view_of(sources), sources->u}, d_jobs, n_bins,
                                             n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
                      });
+}
+
+int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                       const double *f, const double *c, const double *m, int32_t n_patches, int32_t n_bins,
+                                       const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_lenses_radial";
+    if (out) *out = nullptr;
+    static const double one = 1.0;  // (n == 0: the handle still carries a column m)
+    if (n > 0) {
+        if (const int rc = check_column(fn, "f", n, f)) return rc;
+        if (const int rc = check_column(fn, "c", n, c)) return rc;
+        if (const int rc = check_positive(fn, "m", n, m)) return rc;
+    }
+    if (const int rc = upload_segments(fn, ctx, n, x, y, z, w, f, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true, n > 0 ? m : &one))
+        return rc;
+    // the nearest lens of every redshift bin over all patches (the offsets are checked by now); a bin without lenses: +inf
+    yawhip_shear_sources *s = *out;
+    try {
+        s->min_m.assign((size_t)n_bins, INFINITY);
+    } catch (const std::bad_alloc &) {
+        yawhip_shear_free(s);
+        *out = nullptr;
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    for (int64_t seg = 0; seg < (int64_t)n_patches * n_bins; ++seg) {
+        double &least = s->min_m[(size_t)(seg % n_bins)];
+        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i) least = std::min(least, m[i]);
+    }
+    return YAWHIP_OK;
+}
+
+int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
+                               const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *r2, double *fine_t, double *fine_x,
+                               double *fine_w, yawhip_stats *stats) {
+    const char *fn = "yawhip_dsigma_count_radial";
+    const auto wall0 = std::chrono::steady_clock::now();
+    int64_t candidates = 0;
+    if (const int rc = check_dsigma(fn, ctx, lenses, sources, n_jobs, jobs, n_bins, n_edges, r2, fine_t && fine_x && fine_w, &candidates))
+        return rc;
+    if (!lenses->m) return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses_radial", fn);
+    // the largest squared chord of a pair in range, per row: fl(m s2) <= r2max needs s2 <= r2max / m (1 + 2 eps). Beyond 0.01
+    // (5.73 degrees) the series of the squared angle loses its last bits: refused
+    std::vector<double> smax;
+    try {
+        smax.resize((size_t)n_bins);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    for (int k = 0; k < n_bins; ++k) {
+        const double top = r2[(size_t)k * n_edges + n_edges - 1];
+        if (std::isinf(top)) return fail(YAWHIP_ERR_INVALID, "squared radii of bin %d are not finite", k);
+        smax[(size_t)k] = top / lenses->min_m[lenses->nb == 1 ? 0 : (size_t)k] * (1.0 + 1e-12);
+        if (smax[(size_t)k] > 0.01)
+            return fail(YAWHIP_ERR_INVALID, "%s: a lens is too close for the largest radius (bin %d: the reach is a squared chord of %g, at most 0.01)",
+                        fn, k, smax[(size_t)k]);
+    }
+    double *const fine[] = {fine_t, fine_x, fine_w};
+    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, r2, DeltaSigmaRadial::PLANES, fine, candidates,
+                     wall0, stats,
+                     [&](const int32_t *d_jobs, const double *d_r2, const double *d_rwin, int64_t n_cells, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_dsigma_radial, dim3((unsigned)n_cells), dim3(WG), lds_bytes<DeltaSigmaRadial>(n_edges),
+                                            ctx->stream, RadialView{LensView{view_of(lenses), lenses->nb}, lenses->m},
+                                            SourceView{view_of(sources), sources->u}, d_jobs, n_bins, n_edges, d_r2, d_rwin, n_cells, d_out, d_eval);
+                     },
+                     smax.data());
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -266,6 +266,108 @@ def count_dsigma_fine(lens_layout, source_layout, jobs, thresholds, *, cosmology
 
     return _lib.dsigma_count(ctx, _dsigma_handle(lens_layout, ctx, sort_axis, cosmology, "lenses", lenses),
                              _dsigma_handle(source_layout, ctx, sort_axis, cosmology, "sources", sources), jobs, thresholds)
+
+
+S2_CAP = 0.01  # the largest squared chord yawhip_dsigma_count_radial accepts as the reach of a lens (5.73 degrees)
+
+
+def radial_kind(unit) -> str:
+    """"physical" (kpc, Mpc: ``R = D_A(z_l) theta``) or "comoving" (kpc/h, Mpc/h: ``R = D_A(z_l) (1 + z_l) theta``, the
+    conversion of ``Scales.get_angle_radian``); an angular unit has no radius: ``ValueError``."""
+    from .options import COMOVING_UNITS, PHYSICAL_UNITS, Unit
+
+    unit = Unit.parse(unit)
+    if unit in PHYSICAL_UNITS:
+        return "physical"
+    if unit in COMOVING_UNITS:
+        return "comoving"
+    raise ValueError(f"radius='lens' needs scales in a physical or comoving unit, not '{unit}'")
+
+
+def dsigma_radial_columns(lens_layout, source_layout, cosmology, unit, *, unit_columns: bool = False):
+    """The four columns ``yawhip_dsigma_count_radial`` reads: ``(f, c, m, u)`` = ``dsigma_columns`` with the lenses' squared
+    transverse distance per radian ``m`` in Mpc^2 besides: ``f * f`` for the physical units, ``(f * (1 + z_l))**2`` for the
+    comoving ones (``radial_kind``). Every lens needs ``m > 0``, a redshift ``> 0`` (``ValueError`` otherwise).
+    ``unit_columns`` replaces ``f, c, u`` by ``1, 0, 0`` -- the tangential shear itself, for which the sources need no
+    redshifts. A side given as ``None`` is skipped."""
+    kind = radial_kind(unit)
+    f, c, u = dsigma_columns(lens_layout, None if unit_columns else source_layout, cosmology)
+    m = None
+    if lens_layout is not None:
+        reach = f if kind == "physical" else f * (1.0 + lens_layout.redshifts)
+        m = reach * reach
+        if not (np.all(np.isfinite(m)) and np.all(m > 0.0)):
+            raise ValueError("a lens needs a finite transverse distance > 0 (a redshift > 0) to have a radius")
+        if unit_columns:
+            f, c = np.ones_like(f), np.zeros_like(c)
+    if unit_columns and source_layout is not None:
+        u = np.zeros(len(source_layout.x), dtype=np.float64)
+    return f, c, m, u
+
+
+def radial_reach(lens_layout, m, r2):
+    """``smax`` f64[B] of the library's contract: the largest squared chord of a pair in range per redshift bin, from the
+    nearest lens of the bin over all patches (a bin without lenses: 0), and that lens's index per bin (-1: none)."""
+    r2 = np.asarray(r2, dtype=np.float64)
+    num_bins = len(r2)
+    smax, nearest = np.zeros(num_bins), np.full(num_bins, -1, dtype=np.int64)
+    offsets, nb = lens_layout.offsets, lens_layout.num_bins
+    for k in range(num_bins):
+        bins = [0] if nb == 1 else [k]
+        idx = np.concatenate([np.arange(offsets[p * nb + b], offsets[p * nb + b + 1]) for p in range(lens_layout.num_patches) for b in bins])
+        if len(idx):
+            nearest[k] = idx[np.argmin(m[idx])]
+            smax[k] = r2[k, -1] / m[nearest[k]] * (1.0 + 1e-12)
+    return smax, nearest
+
+
+def check_radial_reach(lens_layout, m, r2):
+    """Turn the library's cap (a reach beyond a squared chord of 0.01) into a ``ValueError`` that names the nearest lens and
+    the largest radius; returns ``smax`` of ``radial_reach``."""
+    smax, nearest = radial_reach(lens_layout, m, r2)
+    for k in np.flatnonzero(smax > S2_CAP):
+        z = lens_layout.redshifts[nearest[k]] if getattr(lens_layout, "redshifts", None) is not None else float("nan")
+        raise ValueError(f"a lens is too close for the largest radius: the nearest lens of redshift bin {k} at z = {z:.6g} sees "
+                         f"R = {np.sqrt(np.asarray(r2)[k, -1]):.6g} Mpc under {np.degrees(2.0 * np.arcsin(0.5 * np.sqrt(smax[k]))):.3g} "
+                         f"degrees; a per-lens count reaches 5.73 degrees at most")
+    return smax
+
+
+def count_dsigma_radial_fine(lens_layout, source_layout, jobs, r2, *, cosmology, unit, sort_axis: int = 2, unit_columns: bool = False):
+    """``count_dsigma_fine`` with the pairs binned in each lens's own radius: ``r2`` f64[B, E] are squared radius edges in
+    Mpc^2 and a pair falls into the fine bin that holds ``R^2 = m_l theta^2`` (``yawhip_dsigma_count_radial``;
+    ``dsigma_radial_columns`` makes the columns from the redshifts, ``unit`` says whether the radii are physical or
+    comoving). ``unit_columns``: the sums of ``count_shear_fine`` in that binning (the sources need no redshifts). The lens
+    handle is kept on the layout per context, sort axis, cosmology, kind of unit and ``unit_columns``; the sources' is that of
+    ``count_dsigma_fine``. A reach beyond the library's cap is a ``ValueError`` (``check_radial_reach``). No CPU fallback;
+    the CPU tests replace this function."""
+    if source_layout.g1 is None or source_layout.g2 is None:
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+    if source_layout.num_bins != 1:
+        raise ValueError("the sources of an excess-surface-density count are not binned in redshift")
+    ctx = get_context()
+
+    def lenses():
+        f, c, m, _ = dsigma_radial_columns(lens_layout, None, cosmology, unit, unit_columns=unit_columns)
+        return _lib.DsigmaLenses(ctx, lens_layout.x, lens_layout.y, lens_layout.z, lens_layout.w, f, c, lens_layout.num_patches,
+                                 lens_layout.num_bins, lens_layout.offsets, sort_axis=sort_axis, m=m)
+
+    def sources():
+        u = dsigma_radial_columns(None, source_layout, cosmology, unit, unit_columns=unit_columns)[3]
+        return _lib.ShearSources(ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1,
+                                 source_layout.g2, source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis, u=u)
+
+    suffix = " unit" if unit_columns else ""
+    lens_handle = _dsigma_handle(lens_layout, ctx, sort_axis, cosmology, f"lenses radial {radial_kind(unit)}{suffix}", lenses)
+    source_handle = _dsigma_handle(source_layout, ctx, sort_axis, cosmology, "sources" + suffix, sources)
+    try:
+        return _lib.dsigma_count_radial(ctx, lens_handle, source_handle, jobs, r2)
+    except _lib.YawhipError as err:
+        if "too close for the largest radius" not in str(err):
+            raise
+        m = dsigma_radial_columns(lens_layout, None, cosmology, unit, unit_columns=unit_columns)[2]
+        check_radial_reach(lens_layout, m, r2)  # the same refusal, with the lens's redshift and the radius
+        raise
 
 
 def _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload):

@@ -11,13 +11,14 @@ are sharded over the processes of a ``torch.distributed`` group (one per GPU) an
 """
 from __future__ import annotations
 
+import functools
 import logging
 from itertools import compress
 
 import numpy as np
 
 from . import _lib, engine, parallel
-from .angular_bins import plan_for_limits
+from .angular_bins import plan_for_limits, radial_plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
 from .corrfunc import CorrFunc, ScalarCorrFunc
@@ -27,7 +28,7 @@ from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts,
 
 __all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
            "crosscorrelate_shear", "crosscorrelate_delta_sigma", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
-           "PatchLinkage", "get_max_angle", "check_patch_conistency"]
+           "PatchLinkage", "get_max_angle", "radial_plans", "radial_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
 
@@ -64,6 +65,33 @@ def angular_plans(config):
                         config.scales.resolution)
         for zmid in config.binning.binning.mids
     ]
+
+
+def radial_plans(config):
+    """One :class:`RadialBinPlan` for every redshift bin (the same object): the scale limits as radii in Mpc (physical for
+    ``kpc`` / ``Mpc``, comoving for ``kpc/h`` / ``Mpc/h``, as ``Scales.get_angle_radian`` reads them) -> edges -> squared
+    radii. No redshift enters: a count with ``radius="lens"`` bins every pair by its lens's own distance. Angular units are a
+    ``ValueError``."""
+    from .options import Unit
+
+    scales = config.scales.scales
+    engine.radial_kind(scales.unit)
+    per_mpc = 1000.0 if scales.unit in (Unit.kpc, Unit.kpc_h) else 1.0
+    plan = radial_plan_for_limits(scales.scale_min / per_mpc, scales.scale_max / per_mpc, config.scales.rweight, config.scales.resolution)
+    return [plan] * len(config.binning.binning)
+
+
+def radial_max_angle(config, *lens_layouts) -> float:
+    """The largest angle (radian) of a pair that a count with ``radius="lens"`` holds: that under which the nearest lens of
+    any redshift bin of ``lens_layouts`` (layouts with redshifts: the lenses and, where given, the random lenses) sees the
+    largest radius. A lens too close for the library's cap (5.73 degrees) is a ``ValueError`` that names its redshift and the
+    radius."""
+    r2 = threshold_table(radial_plans(config))
+    smax = 0.0
+    for layout in lens_layouts:
+        m = engine.dsigma_radial_columns(layout, None, config.cosmology, config.scales.scales.unit, unit_columns=True)[2]
+        smax = max(smax, float(np.max(engine.check_radial_reach(layout, m, r2))))
+    return 2.0 * np.arcsin(0.5 * np.sqrt(smax))
 
 
 class CombinePlan:
@@ -212,10 +240,13 @@ class PatchLinkage:
         return self._plans, self._thresholds
 
     @classmethod
-    def from_catalogs(cls, config, catalog: Catalog, *catalogs: Catalog):
+    def from_catalogs(cls, config, catalog: Catalog, *catalogs: Catalog, max_angle: float | None = None):
+        """``max_angle`` (radian): the largest separation of a pair that counts, where it is not that of the scales at
+        ``max(zmin, 0.05)`` -- a count binned per lens reaches as far as its nearest lens sees its largest radius."""
         if any(set(cat.keys()) != set(catalog.keys()) for cat in catalogs):
             raise InconsistentPatchesError("patch IDs do not match")
-        max_angle = get_max_angle(config).data[0]
+        if max_angle is None:
+            max_angle = get_max_angle(config).data[0]
         # the catalogue with the most records constrains centres / radii best (measurements.py:220-225)
         ranked = sorted([catalog, *catalogs], key=lambda cat: cat.get_num_records(), reverse=True)
         ref_cat, others = ranked[0], ranked[1:]
@@ -522,6 +553,32 @@ class PatchLinkage:
                  NormalisedScalarCounts(PatchedCounts(binning, DELTA_SIGMA_UNIT * X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
                 for s in range(len(W))]
 
+    def count_dsigma_radial_pairs(self, lenses: Catalog, sources: Catalog, *, shear_only: bool = False, progress: bool = False,
+                                  max_workers: int | None = None, count_type_info: str | None = None) -> list:
+        """``count_dsigma_pairs`` with every pair binned in its lens's OWN radius ``R = D(z_l) theta`` (physical or comoving,
+        as the unit of the scales says) instead of one angle per redshift slice: the edges are the radii of ``radial_plans``,
+        the same in every redshift bin (``engine.count_dsigma_radial_fine``). ``shear_only``: the sums of
+        ``count_shear_pairs`` in that binning -- no factor ``S``, no ``K``, and the sources need no redshifts. The linkage must
+        reach as far as the nearest lens sees the largest radius (``from_catalogs(max_angle=radial_max_angle(...))``)."""
+        import functools
+
+        def layouts(num_bins):
+            lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
+            if source_layout.g1 is None or source_layout.g2 is None:
+                raise ValueError("catalog has no 'g1'/'g2' attached")
+            if lens_layout.redshifts is None or (source_layout.redshifts is None and not shear_only) or source_layout.num_bins != 1:
+                raise ValueError("a count binned per lens needs layouts with redshifts and unbinned sources: "
+                                 "build_trees(..., with_redshifts=True)")
+            count = functools.partial(engine.count_dsigma_radial_fine, cosmology=self.config.cosmology,
+                                      unit=self.config.scales.scales.unit, unit_columns=shear_only)
+            return count, (lens_layout, source_layout)
+
+        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress, radial=True)
+        K = 1.0 if shear_only else DELTA_SIGMA_UNIT
+        return [(NormalisedScalarCounts(PatchedCounts(binning, K * T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
+                 NormalisedScalarCounts(PatchedCounts(binning, K * X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
+                for s in range(len(W))]
+
     def count_shear_auto_pairs(self, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
                                count_type_info: str | None = None) -> list:
         """Shear-shear sums of ``sources`` (binned in redshift with ``g1`` / ``g2``: ``build_trees(edges, with_shear=True)``)
@@ -614,11 +671,12 @@ class PatchLinkage:
                  for i in range(num_bins)]
                 for s in range(num_scales)]
 
-    def _count_shear_planes(self, catalogs, layouts, count_type_info, progress):
+    def _count_shear_planes(self, catalogs, layouts, count_type_info, progress, radial: bool = False):
         """What the two shear counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the engine's
         count (``count_shear_fine`` / ``count_shear_auto_fine``, looked up at call time: the CPU tests replace them) with the
         layouts it takes; its job list is ``get_patch_pairs(*catalogs)``. Returns the binning and one f64[S, B, P, P] per
-        plane of the count, zero outside the jobs."""
+        plane of the count, zero outside the jobs. ``radial``: edges and recombination are those of the configuration's
+        radial plan (``radial_plans``), the same for every redshift bin."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("shear counts run in one process on one device")
         if count_type_info is not None:
@@ -627,14 +685,19 @@ class PatchLinkage:
         num_bins, num_patches = len(binning), len(catalogs[0])
         count_fine, count_layouts = layouts(num_bins)
         jobs = self.get_patch_pairs(*catalogs)
-        _, thresholds = self._angular_setup()
+        if radial:
+            plans = radial_plans(self.config)
+            thresholds, combine = threshold_table(plans), CombinePlan(plans)
+        else:
+            _, thresholds = self._angular_setup()
+            combine = self._combine
         *fine, stats = count_fine(*count_layouts, jobs, thresholds, sort_axis=self.sort_axis)
         self.last_stats = stats
         self._report(count_type_info, len(jobs), stats, progress)
         flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
         shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
         # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
-        return binning, [_lib.scatter_rows(shape, flat, self._combine(np.moveaxis(f, 0, -1))) for f in fine]
+        return binning, [_lib.scatter_rows(shape, flat, combine(np.moveaxis(f, 0, -1))) for f in fine]
 
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
@@ -835,7 +898,7 @@ def crosscorrelate_scalar_map(config, reference: Catalog, scalar_map: Catalog, *
 
 
 def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_rand: Catalog | None = None,
-                         progress: bool = False, max_workers: int | None = None) -> list:
+                         radius: str = "slice", progress: bool = False, max_workers: int | None = None) -> list:
     """Tangential shear of ``sources`` (a catalogue with ``g1`` / ``g2``, no redshifts needed) around ``reference`` in its
     redshift slices, and the cross shear as its null test: per redshift bin and scale ``gamma_t = sum T / sum W`` over the
     pairs in range, minus the same ratio around the lenses of ``ref_rand`` when it is given (``gamma_x`` alike) ->
@@ -843,29 +906,49 @@ def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_ra
     A pair adds ``T = w_l w_s * -(g1 cos 2phi + g2 sin 2phi)`` and ``X = w_l w_s * (g1 sin 2phi - g2 cos 2phi)``, ``phi`` the
     position angle of the lens seen from the source, from east towards north (frame of ``g1, g2``: ``Catalog.from_arrays``).
 
+    With physical or comoving scales, ``radius="slice"`` (the default) turns the limits into an angle once per redshift
+    slice, at its middle; ``radius="lens"`` bins every pair by ``R = D(z_l) theta`` of its OWN lens (the references then need
+    redshifts; angular scales are a ``ValueError``), as ``crosscorrelate_delta_sigma`` describes.
+
     This driver has no counterpart in the reference. Linkage, scales, patches and jackknife are ``crosscorrelate``'s; the
     count runs on one device of one process."""
     _require_distinct(reference, sources, ref_rand)
     if not sources.has_shear:
         raise ValueError("catalog has no 'g1'/'g2' attached")
+    per_lens = _per_lens(config, radius)
     edges, closed = config.binning.edges, config.binning.closed
     randoms = []
     _log_info("building reference data trees")
-    reference.build_trees(edges, closed=closed)
+    lens_layouts = [reference.build_trees(edges, closed=closed, with_redshifts=per_lens)]
     if ref_rand is not None:
-        ref_rand.build_trees(edges, closed=closed)
+        lens_layouts.append(ref_rand.build_trees(edges, closed=closed, with_redshifts=per_lens))
         randoms.append(ref_rand)
     sources.build_trees(None)
     _log_info("computing shear cross-correlation with DD" + (", DR" if randoms else ""))
-    links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
     kwargs = dict(progress=progress, max_workers=max_workers)
-    DD = links.count_shear_pairs(reference, sources, count_type_info="DD", **kwargs)
-    DR = links.count_shear_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
+    if per_lens:
+        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms, max_angle=radial_max_angle(config, *lens_layouts))
+        count = functools.partial(links.count_dsigma_radial_pairs, shear_only=True)
+    else:
+        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
+        count = links.count_shear_pairs
+    DD = count(reference, sources, count_type_info="DD", **kwargs)
+    DR = count(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
     return [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
 
 
+def _per_lens(config, radius: str) -> bool:
+    """``radius`` of the two lensing drivers: "slice" (False) or "lens" (True; the scales must not be angular)."""
+    if radius not in ("slice", "lens"):
+        raise ValueError(f"radius must be 'slice' or 'lens', not {radius!r}")
+    if radius == "lens":
+        engine.radial_kind(config.scales.scales.unit)
+    return radius == "lens"
+
+
 def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, ref_rand: Catalog | None = None,
-                               boost: bool = False, progress: bool = False, max_workers: int | None = None) -> list:
+                               boost: bool = False, radius: str = "slice", progress: bool = False,
+                               max_workers: int | None = None) -> list:
     """Excess surface density of the matter around ``reference`` in its redshift slices, from ``sources`` with ``g1`` / ``g2``
     and point redshifts: per redshift bin and scale
 
@@ -875,8 +958,13 @@ def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, 
     with the configuration's cosmology, which is assumed flat (a custom one is used as given): a source in front of its lens
     adds nothing. The cross component is the null test. Minus the same ratio around the lenses of ``ref_rand`` when it is
     given -> ``[(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)), ...]``, one tuple per scale, ``dr = None`` without
-    randoms: the shape of ``crosscorrelate_shear``, whose frame, rotation and pair selection these are. With physical scales
-    (``unit="kpc"``) the limits are turned into an angle per lens slice, as everywhere.
+    randoms: the shape of ``crosscorrelate_shear``, whose frame and rotation these are. With physical or comoving scales
+    (``unit="kpc"``) ``radius`` says how a pair finds its bin. ``"slice"`` (the default) turns the limits into an angle once per
+    redshift slice, at its middle, as the clustering counts do: a lens at the near end of a wide slice is then counted at a
+    radius other than the bin names. ``"lens"`` bins every pair by ``R = D(z_l) theta`` of its OWN lens -- ``D = D_A`` for
+    ``kpc`` / ``Mpc``, ``D_A (1 + z_l)`` for ``kpc/h`` / ``Mpc/h`` --, the same radii in every slice; the linkage then reaches
+    as far as the nearest lens (or random lens) sees the largest radius, at most 5.73 degrees (a ``ValueError`` that names
+    the lens's redshift beyond that), and angular scales are a ``ValueError``.
 
     ``boost=True`` (needs ``ref_rand``) adds a third item per scale, a plain ``CorrFunc(dd, dr)`` whose counts are the
     denominators ``sum w_l w_s Sigma_c^-2`` of DD and DR, already counted, each normalised by the lens weight sums per
@@ -893,6 +981,7 @@ def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, 
         raise ValueError("excess surface density needs source redshifts: the sources have no 'redshifts' attached")
     if boost and ref_rand is None:
         raise ValueError("the boost factor needs random lenses: give 'ref_rand'")
+    per_lens = _per_lens(config, radius)
     edges, closed = config.binning.edges, config.binning.closed
     randoms = []
     _log_info("building reference data trees")
@@ -902,10 +991,15 @@ def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, 
         randoms.append(ref_rand)
     source_layout = sources.build_trees(None, with_redshifts=True)
     _log_info("computing excess surface density with DD" + (", DR" if randoms else ""))
-    links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
     kwargs = dict(progress=progress, max_workers=max_workers)
-    DD = links.count_dsigma_pairs(reference, sources, count_type_info="DD", **kwargs)
-    DR = links.count_dsigma_pairs(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
+    if per_lens:
+        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms, max_angle=radial_max_angle(config, *lens_layouts))
+        count = links.count_dsigma_radial_pairs
+    else:
+        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
+        count = links.count_dsigma_pairs
+    DD = count(reference, sources, count_type_info="DD", **kwargs)
+    DR = count(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
     result = [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
     if boost:  # the W planes of the two counts over the products of the weight sums: (DD - DR) / DR
         binning, num_bins = config.binning.binning, len(config.binning.binning)
