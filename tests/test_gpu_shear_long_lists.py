@@ -4,13 +4,18 @@ with the rules of their own suites (``1e-10 * A``, ``RTOL_W``, exact zeros): the
 ``run_count`` and of the policies' ``cell()``, not the arithmetic. What only runs at this scale: result blocks
 ``[planes][n_cells][E-1]`` of tens of thousands of cells with the evaluated counters behind them, most cells without a single
 object; the grow-only call buffers of a handle through calls of other sizes; ``nb == 1`` lenses folded under many rows of
-thresholds; handles without any object."""
+thresholds; handles without any object.
+
+The count in each lens's own radius (``dsigma_count_radial``, ``"radial"``) runs through the same cases on the same scene with
+``m = f * f`` and squared radii made from the rows of ``thresholds`` at the median ``m``, against tests/dsigma_radial_oracle.py;
+besides, a redshift bin without any lens (``min_m = +inf``) under a last edge of 1e30."""
 import functools
 
 import numpy as np
 import pytest
 
 import dsigma_oracle
+import dsigma_radial_oracle
 import shear_auto_oracle
 import shear_oracle
 import shear_pair_oracle
@@ -40,6 +45,12 @@ def chord2(arcmin):
 def thresholds(n_rows=NB):
     """f64[n_rows, 5]: 0.5 to 15 arcmin and other limits in every row; a patch is 8 x 12 arcmin, so neighbouring patches pair."""
     return chord2([np.geomspace(0.5 * (1.0 + 0.1 * k), 15.0 * (1.0 - 0.04 * k), 5) for k in range(n_rows)])
+
+
+def radii2(m, n_rows=NB):
+    """The rows of ``thresholds`` as squared radii of the radial count: ``median(m) theta^2`` with the angle of each chord, so that
+    around the median lens the bins are the same; neighbouring patches pair."""
+    return np.median(m) * (2.0 * np.arcsin(0.5 * np.sqrt(thresholds(n_rows)))) ** 2
 
 
 def draw_positions(rng, n_bins):
@@ -131,10 +142,16 @@ class Count:
     def __init__(self, name):
         self.name = name
         self.lens, self.src, self.cat, self.cat_b = scene()
-        self.t = thresholds()
+        if name == "radial":  # m = D_A^2 as the driver sends it for kpc and Mpc (engine.dsigma_radial_columns)
+            self.lens = dict(self.lens, m=self.lens["f"] * self.lens["f"])
+        self.t = self.rows()
+
+    def rows(self, n_rows=NB):
+        """The thresholds of the count: squared chords, or squared radii for the radial count."""
+        return radii2(self.lens["m"], n_rows) if self.name == "radial" else thresholds(n_rows)
 
     def full_list(self):
-        return {"shear": all_jobs, "dsigma": all_jobs, "auto": auto_jobs, "pair": lambda: pair_cells(True),
+        return {"shear": all_jobs, "dsigma": all_jobs, "radial": all_jobs, "auto": auto_jobs, "pair": lambda: pair_cells(True),
                 "pair2": lambda: pair_cells(False)}[self.name]()
 
     def small_list(self):
@@ -145,13 +162,14 @@ class Count:
         return entries[np.concatenate([np.flatnonzero(live)[:4], [0, len(entries) - 1]])]
 
     def cells_of(self, entries):
-        return len(entries) * (NB if self.name in ("shear", "dsigma", "auto") else 1)
+        return len(entries) * (NB if self.name in ("shear", "dsigma", "radial", "auto") else 1)
 
     def upload(self, ctx, sort_axis=2):
         if self.name == "shear":
             return test_gpu_shear.upload(ctx, self.lens, self.src, sort_axis)
-        if self.name == "dsigma":
-            lenses = _lib.DsigmaLenses(ctx, *(self.lens[c] for c in "xyzwfc"), P, NB, self.lens["off"], sort_axis=sort_axis)
+        if self.name in ("dsigma", "radial"):
+            lenses = _lib.DsigmaLenses(ctx, *(self.lens[c] for c in "xyzwfc"), P, self.lens["nb"], self.lens["off"], sort_axis=sort_axis,
+                                       m=self.lens.get("m"))
             sources = _lib.ShearSources(ctx, *(self.src[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, self.src["off"], sort_axis=sort_axis,
                                         u=self.src["u"])
             return lenses, sources
@@ -165,6 +183,8 @@ class Count:
             return _lib.shear_count(ctx, *handles, entries, t)
         if self.name == "dsigma":
             return _lib.dsigma_count(ctx, *handles, entries, t)
+        if self.name == "radial":
+            return _lib.dsigma_count_radial(ctx, *handles, entries, t)
         if self.name == "auto":
             return _lib.shear_auto_count(ctx, handles[0], entries, t)
         if exchanged:
@@ -176,15 +196,17 @@ class Count:
             return shear_oracle.shear_jobs(self.lens, self.src, entries, self.t)
         if self.name == "dsigma":
             return dsigma_oracle.dsigma_jobs(self.lens, self.src, entries, self.t)
+        if self.name == "radial":
+            return dsigma_radial_oracle.radial_jobs(self.lens, self.src, entries, self.t)[:4]
         if self.name == "auto":
             return shear_auto_oracle.shear_auto_jobs(self.cat, entries, self.t)
         return shear_pair_oracle.shear_pair_cells(self.cat, self.cat if self.name == "pair" else self.cat_b, entries, self.t)
 
     def check(self, key, got, exp):
-        (test_gpu_shear if self.name in ("shear", "dsigma") else test_gpu_shear_auto).check_against_oracle(key, got, exp)
+        (test_gpu_shear if self.name in ("shear", "dsigma", "radial") else test_gpu_shear_auto).check_against_oracle(key, got, exp)
 
 
-COUNTS = ["shear", "dsigma", "auto", "pair", "pair2"]
+COUNTS = ["shear", "dsigma", "radial", "auto", "pair", "pair2"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -271,13 +293,13 @@ def test_a_handle_through_calls_that_grow_and_shrink(name):
 
 
 # --------------------------------------------------------------------------- 3. unbinned lenses under many rows
-@pytest.mark.parametrize("name", ["shear", "dsigma"])
+@pytest.mark.parametrize("name", ["shear", "dsigma", "radial"])
 def test_unbinned_lenses_under_eight_rows_of_thresholds(name):
     """``nb == 1`` lenses, 8 rows of thresholds, 2000 jobs: all 8 cells of a job stream the one lens segment of its patch, each
     with the edges of its own row (``Tangential::cell`` / ``DeltaSigma::cell``)."""
     count = Count(name)
     count.lens = dict(count.lens, nb=1, off=count.lens["off"][::NB].copy())
-    count.t = thresholds(8)
+    count.t = count.rows(8)
     near = neighbours()
     jobs = near[np.random.default_rng(9).choice(len(near), 2000, replace=False)]
     exp = count.oracle(jobs)
@@ -286,6 +308,8 @@ def test_unbinned_lenses_under_eight_rows_of_thresholds(name):
     ctx = engine.get_context(0)
     if name == "shear":
         handles = test_gpu_shear.upload(ctx, count.lens, count.src, 2)
+    elif name == "radial":
+        handles = count.upload(ctx)  # (the lenses as they are now: one bin)
     else:
         lenses = _lib.DsigmaLenses(ctx, *(count.lens[c] for c in "xyzwfc"), P, 1, count.lens["off"])
         handles = (lenses, _lib.ShearSources(ctx, *(count.src[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, count.src["off"], u=count.src["u"]))
@@ -312,7 +336,8 @@ def assert_nothing(key, result, n_cells):
 
 def test_handles_without_objects():
     """A handle uploaded with ``n = 0`` uploads, counts to all-zero planes with no pair evaluated, and is freed: as sources, as
-    lenses (a catalogue handle and a lens handle), as the catalogue of the auto count and on either side of the pair count."""
+    lenses (a catalogue handle, a lens handle and a radial lens handle), as the catalogue of the auto count and on either side
+    of the pair count. The radial count besides: lenses whose second redshift bin is empty in every patch."""
     lens, src, cat, _ = scene()
     no_lens, no_src, no_cat = empty_like(lens, NB), empty_like(src, 1), empty_like(cat, NB)
     t = thresholds()
@@ -345,3 +370,44 @@ def test_handles_without_objects():
         count.check("after the empty handles", _lib.shear_pair_count(ctx, somebody, somebody, few, t)[:4], count.oracle(few))
     finally:
         free((nobody, somebody))
+
+    # the radial count: a lens handle with n == 0 still carries a column m, and sources without objects
+    radial = Count("radial")
+    full, r2 = radial.lens, radial.t
+
+    def radial_handles(lens_, src_):
+        lenses = _lib.DsigmaLenses(ctx, *(lens_[c] for c in "xyzwfc"), P, NB, lens_["off"], m=lens_["m"])
+        return lenses, _lib.ShearSources(ctx, *(src_[c] for c in ("x", "y", "z", "w", "g1", "g2")), P, src_["off"], u=src_["u"])
+
+    for lens_, src_ in ((full, no_src), (empty_like(full, NB), src), (empty_like(full, NB), no_src)):
+        handles = radial_handles(lens_, src_)
+        try:
+            assert_nothing(f"radial {len(lens_['x'])} lenses, {len(src_['x'])} sources", _lib.dsigma_count_radial(ctx, *handles, jobs, r2),
+                           len(jobs) * NB)
+        finally:
+            free(handles)
+    # ... and a redshift bin without a lens in any patch (min_m = +inf, a reach of 0): its row takes any last edge and stays
+    # exactly +0.0; the first row is the bits of the call on all lenses
+    in_first = (np.searchsorted(full["off"], np.arange(len(full["x"])), side="right") - 1) % NB == 0
+    sizes = np.diff(full["off"]) * (np.arange(P * NB) % NB == 0)
+    first_only = dict({c: full[c][in_first] for c in "xyzwfcm"}, nb=NB, off=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64))
+    assert 50 < in_first.sum() < len(in_first) - 50
+    far_edge = r2.copy()
+    far_edge[1, -1] = 1e30
+    in_row = expected("radial")[2].sum(axis=2) > 0  # three jobs with pairs in the first row, three in the second
+    few = radial.full_list()[np.concatenate([np.flatnonzero(in_row[:, 0])[:3], np.flatnonzero(in_row[:, 1] & ~in_row[:, 0])[:3]])]
+    all_lenses, one_bin = radial_handles(full, src), radial_handles(first_only, src)
+    try:
+        with pytest.raises(_lib.YawhipError, match="a lens is too close for the largest radius"):
+            _lib.dsigma_count_radial(ctx, *all_lenses, few, far_edge)  # (with lenses in that bin the edge is refused)
+        *both, _ = _lib.dsigma_count_radial(ctx, *all_lenses, few, r2)
+        *first, stats = _lib.dsigma_count_radial(ctx, *one_bin, few, far_edge)
+    finally:
+        free(all_lenses + one_bin)
+    assert stats.n_workgroups == len(few) * NB and stats.evaluated_pairs > 0
+    exp = radial.oracle(few)
+    assert np.count_nonzero(exp[2][:, 0].sum(axis=1)) >= 3 and np.count_nonzero(exp[2][:, 1].sum(axis=1)) >= 3  # both rows hold pairs
+    radial.check("radial, 6 jobs", both, exp)
+    for ours, ref in zip(first, both):
+        assert np.array_equal(ours[:, 0], ref[:, 0])
+        assert np.all(ours[:, 1] == 0.0) and not np.any(np.signbit(ours[:, 1]))

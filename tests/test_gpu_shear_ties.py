@@ -9,13 +9,18 @@ RING order (3 patches of 3 rings: 3 keys per segment), a 64 x 64 block of a map 
 to 32) -- and 2400 objects at ONE declination (a segment is a single key). ``sort_axis = 0`` is the untied control. Thresholds:
 two rows whose outer edge is three ring spacings of the key times (1 -/+ 1e-9), so that the window's boundary lands on a run
 of ties, and for the pair count a row of two spacings and a wide one besides. Sums hold the rules of the counts' own suites
-against the numpy oracles; unweighted ``W`` is the pair count of the shipped exact kernel, bit for bit."""
+against the numpy oracles; unweighted ``W`` is the pair count of the shipped exact kernel, bit for bit.
+
+The count in each lens's own radius (``dsigma_count_radial``) runs on the same catalogues with a column ``m`` of three values a
+factor 4 apart mixed inside every run of ties, and squared radii whose last edge puts the reach of the NEAREST lenses at those
+three spacings: its window is the only one that does not come from the row's last edge."""
 import functools
 
 import numpy as np
 import pytest
 
 import dsigma_oracle
+import dsigma_radial_oracle
 import shear_auto_oracle
 import shear_oracle
 import shear_pair_oracle
@@ -176,6 +181,80 @@ def test_lens_counts_on_tied_keys(name, count, sort_axis):
             handles[0].free(), handles[1].free()
     pairs = exact_counts(ctx, lens, src, jobs, t, sort_axis)
     assert pairs.sum() > 5000 and np.array_equal(W, pairs)
+
+
+# --------------------------------------------------------------------------- 1b. the count in each lens's own radius
+RADIAL_M = 900.0**2 * np.array([1.0, 4.0, 16.0])  # the lenses' column m: three values a factor 4 apart
+
+
+def radii2():
+    """f64[2, 5]: squared radii from 1 arcmin at the nearest lenses to a last edge with ``sqrt(r2max / min_m)`` = 3 ring
+    spacings x (1 -/+ 1e-9): the window, whose half width follows the NEAREST lens of the bin (``reach`` in ``run_count``), ends
+    on a run of ties; the lenses 2 and 4 times farther stop 1.5 and 0.75 spacings out."""
+    outer = np.array([3.0 * (1.0 - 1e-9), 3.0 * (1.0 + 1e-9)]) * RING_SPACING
+    return RADIAL_M[0] * np.array([np.geomspace(ARCMIN, edge, 5) for edge in outer]) ** 2
+
+
+@functools.lru_cache(maxsize=None)
+def radial_scene(name):
+    """The lenses and sources of ``scene(name)`` with ``m`` cycling through RADIAL_M along ``serial``, so that every run of
+    ties mixes the three."""
+    lens, src, _, n_patches = scene(name)
+    ra, dec, patch, serial = positions(name)
+    even = serial % 2 == 0
+    order = np.argsort(patch[even] * 2 + (serial[even] // 2) % 2, kind="stable")  # the order of ``segments``
+    assert np.array_equal(radec_to_xyz(ra, dec)[0][even][order], lens["x"])
+    m = RADIAL_M[(serial[even] // 2) % 3][order]
+    m.setflags(write=False)
+    for a, b in zip(lens["off"][:-1], lens["off"][1:]):
+        keys, run = np.unique(lens["z"][a:b], return_inverse=True)
+        long_runs = [r for r in range(len(keys)) if np.count_nonzero(run == r) >= 12]
+        assert long_runs and all(len(np.unique(m[a:b][run == r])) == 3 for r in long_runs), name
+        assert m[a:b].min() == RADIAL_M[0]  # the nearest kind of lens in every segment: both bins reach 3 spacings
+    return dict(lens, m=m), src, n_patches
+
+
+@functools.lru_cache(maxsize=None)
+def radial_expected(name, columns):
+    """The mirror oracle of the radial count on a catalogue (``columns`` "real" or "unit": ``f = 1``, ``c = 0``): once, shared
+    by the sort axes, never modified."""
+    lens, src, n_patches = radial_scene(name)
+    if columns == "unit":
+        lens = dict(lens, f=np.ones_like(lens["f"]), c=np.zeros_like(lens["c"]))
+    out = dsigma_radial_oracle.radial_jobs(lens, src, job_lists(n_patches)[0], radii2())
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("sort_axis", AXES)
+@pytest.mark.parametrize("name", CATALOGUES)
+def test_radial_count_on_tied_keys(name, sort_axis):
+    lens, src, n_patches = radial_scene(name)
+    jobs, r2 = job_lists(n_patches)[0], radii2()
+    exp, exp_unit = radial_expected(name, "real"), radial_expected(name, "unit")
+    assert np.count_nonzero(exp[3]) > 4 * n_patches and np.all(exp[3][::n_patches + 1].sum(axis=2) > 0)  # both rows of every diagonal job
+    # what the nearest lenses alone hold: without them the counts fall (on pixel centres, 6.9 arcmin apart, to nothing: the
+    # farther lenses reach 6.75 arcmin -- any pair counted around them is a pair binned with a neighbour's m)
+    far_only = dsigma_radial_oracle.radial_jobs(dict(lens, f=np.ones_like(lens["f"]), c=np.zeros_like(lens["c"]),
+                                                     m=np.where(lens["m"] == RADIAL_M[0], 1e12, lens["m"])), src, jobs[:1], r2)[2]
+    assert far_only.sum() < exp_unit[2][:1].sum() and (far_only.sum() > 0) == (name == "one declination")
+    ctx = engine.get_context(0)
+    n = len(src["off"]) - 1
+    results = {}
+    for columns in ("real", "unit"):
+        f, c = (lens["f"], lens["c"]) if columns == "real" else (np.ones_like(lens["f"]), np.zeros_like(lens["c"]))
+        lenses = _lib.DsigmaLenses(ctx, lens["x"], lens["y"], lens["z"], None, f, c, n, 2, lens["off"], sort_axis=sort_axis, m=lens["m"])
+        sources = _lib.ShearSources(ctx, src["x"], src["y"], src["z"], None, src["g1"], src["g2"], n, src["off"], sort_axis=sort_axis, u=src["u"])
+        try:
+            results[columns] = _lib.dsigma_count_radial(ctx, lenses, sources, jobs, r2)
+        finally:
+            lenses.free(), sources.free()
+    T, X, W, stats = results["real"]
+    assert stats.n_workgroups == len(jobs) * 2 and 0 < stats.evaluated_pairs <= stats.candidate_pairs
+    test_gpu_shear.check_against_oracle(f"radial on {name} axis={sort_axis}", (T, X, W), exp[:4])
+    W = results["unit"][2]
+    assert exp_unit[2].sum() >= 2000 and np.all(exp_unit[2] == np.rint(exp_unit[2])) and np.array_equal(W, exp_unit[2])
 
 
 # --------------------------------------------------------------------------- 2. the two shear-shear counts
