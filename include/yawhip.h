@@ -701,6 +701,63 @@ int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, ya
                                const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *r2, double *fine_t, double *fine_x,
                                double *fine_w, yawhip_stats *stats);
 
+/*
+ * Projected pair counts: the pairs of one or two catalogues binned in each PAIR's own transverse radius, inside a cut on the
+ * line-of-sight separation -- DD, DR and RR of the projected clustering w_p(r_p) (measurements.autocorrelate_projected;
+ * DESIGN.md section 20; no counterpart in the reference). Additive to ABI 6: new symbols only, the opaque handle is
+ * yawhip_shear_sources.
+ *
+ * The library is unit-free. Every object carries two columns besides x, y, z, w:
+ *   d   its transverse distance per radian, finite and > 0 (the driver passes D_A(z) or D_A(z) (1 + z) in Mpc)
+ *   c   its line-of-sight coordinate, finite (the driver passes the comoving distance chi(z) in Mpc)
+ *
+ * yawhip_proj_upload    yawhip_dsigma_upload_lenses with the two raw columns read as (d, c), on one code path with it: n_bins
+ *                       segments per patch (offsets int64[n_patches * n_bins + 1]), every segment sorted along sort_axis and
+ *                       gathered; the handle keeps x, y, z, w (NULL: every weight 1.0) and d, c as they came, is MARKED as
+ *                       projected and keeps, per redshift bin, the minimum of d over all patches. A d that is not finite and
+ *                       > 0 or a c that is not finite: YAWHIP_ERR_INVALID (a host pass before any device work). Freed by
+ *                       yawhip_shear_free. The three shear counts and the two excess-surface-density counts refuse the handle
+ *                       (YAWHIP_ERR_MISMATCH); yawhip_proj_count refuses every other handle (YAWHIP_ERR_MISMATCH).
+ * yawhip_proj_count     a, b: two projected handles on the context; they may be the same handle, and need neither equal patch
+ *                       counts nor equal bin counts nor one sort axis. Cell c = (sa, sb, row, diagonal) holds, per fine bin e,
+ *                       the sum over the pairs (object a_obj of segment sa of a, object b_obj of segment sb of b; a segment is
+ *                       patch * n_bins + bin of its handle). A pair is handled in float64, every operation rounded on its own
+ *                       and nothing contracted:
+ *       s2  = ((bx - ax)^2 + (by - ay)^2) + (bz - az)^2          the separation of every count (b_obj minus a_obj)
+ *       D   = 0.5 * (d_a + d_b);   DD = D * D
+ *       q   = 1/16632;  q = 1/3150 + s2 q;  q = 1/560 + s2 q;  q = 1/90 + s2 q;  q = 1/12 + s2 q;  q = 1 + s2 q
+ *       th2 = s2 q                                               the series of yawhip_dsigma_count_radial, the same constants
+ *       R2  = DD th2
+ *       fine bin e  iff  r2[row][e] < R2 <= r2[row][e + 1]       none: the pair adds nothing
+ *       p   = fabs(c_a - c_b);   the pair counts  iff  p <= pmax
+ *       fine_w[c][e] += w_a * w_b
+ *     Every term is bit-symmetric under swapping the two objects. A cell is DIAGONAL iff a == b and sa == sb: it holds every
+ *     unordered pair of the segment once (a pair at R2 == 0, an object with itself included, never counts where r2[row][0]
+ *     >= 0). Every other cell holds every (a_obj, b_obj) once. The fourth entry of a cell must say which it is (non-zero:
+ *     diagonal), else YAWHIP_ERR_INVALID.
+ *     Reach: with least[row] the minimum of d over the redshift bins that the cells of the row pair (0 where a row has no cell
+ *     or a bin has no object), smax[row] = r2[row][n_edges - 1] / least[row]^2 * (1 + 1e-12); any smax[row] > 0.01 is
+ *     YAWHIP_ERR_INVALID, "an object is too close for the largest radius", before any device work (the cap of
+ *     yawhip_dsigma_count_radial: the series is within 2 * 2^-53 of the squared angle up to there).
+ *   cells        int32[n_cells][4];  r2  float64[n_rows][n_edges] ascending squared radius edges, finite and >= 0,
+ *                n_edges <= 256;  pmax  >= 0, +inf: no line-of-sight cut (negative or NaN: YAWHIP_ERR_INVALID)
+ *   fine_w       float64[n_cells][n_edges - 1] (host), ONE plane; every element is written
+ *   stats        as for yawhip_shear_pair_count; candidate pairs count a diagonal cell's unordered pairs, and so do the
+ *                evaluated pairs: of a diagonal cell the separations inside the key window whose streamed object has the larger
+ *                index (the waves also evaluate, and drop, the other order inside a lane tile's own range; the shear counts
+ *                report those too). evaluated <= candidates always, with equality where no window is used
+ * Kernel: the walk of yawhip_shear_pair_count (one workgroup per cell, segment sa of a streamed through LDS, sb of b in the
+ * lanes, a diagonal cell walks only partners with a larger index) with 48-byte streamed objects (x, y, z, d | w, c); the
+ * sort-key window is used iff the two handles are sorted along the same axis and has the half width
+ * sqrt(smax[row]) (1 + 1e-12) + 1e-15, so the evaluated separations follow the NEAREST object. Accumulation and
+ * reproducibility as yawhip_shear_count. The per-call device buffers are those of a. n_cells == 0 returns at once.
+ */
+int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                       const double *d, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                       int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                      int32_t n_rows, int32_t n_edges, const double *r2, double pmax, double *fine_w, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
 from .corrfunc import CorrFunc, ScalarCorrFunc
-from .measurements import (PatchLinkage, autocorrelate, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
+from .measurements import (PatchLinkage, autocorrelate, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
                            crosscorrelate_delta_sigma, crosscorrelate_shear)
 from . import healpix, patches, randoms
@@ -50,6 +50,7 @@ __all__ = [
     "SampledData",
     "ScalarCorrFunc",
     "autocorrelate",
+    "autocorrelate_projected",
     "autocorrelate_scalar",
     "autocorrelate_shear",
     "correlate_shear_tomographic",

@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "yawhip_dsigma_count",
     "yawhip_dsigma_upload_lenses_radial",
     "yawhip_dsigma_count_radial",
+    "yawhip_proj_upload",
+    "yawhip_proj_count",
 )
 
 
@@ -292,6 +294,9 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_dsigma_upload_lenses_radial.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32,
                                                        ctypes.c_int32, _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
     lib.yawhip_dsigma_count_radial.argtypes = lib.yawhip_dsigma_count.argtypes
+    lib.yawhip_proj_upload.argtypes = lib.yawhip_dsigma_upload_lenses.argtypes
+    lib.yawhip_proj_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_double, _dp,
+                                      ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -855,6 +860,52 @@ class DsigmaLenses(ShearSources):
         else:
             _check(load_library().yawhip_dsigma_upload_lenses(*columns, *layout), "yawhip_dsigma_upload_lenses")
         ctx._shear.add(self)
+
+
+class ProjHandle(ShearSources):
+    """The objects of ``proj_count`` resident in HBM (``yawhip_proj_upload``): every (patch, bin) segment sorted along
+    ``sort_axis`` -- unit vectors, weights (or None) and the two columns ``d, c`` (include/yawhip.h: the transverse distance
+    per radian, finite and ``> 0``, and the line-of-sight coordinate, finite), kept as they come. The handle is a
+    ``yawhip_shear_sources`` marked as projected: it is freed like one, and every other count refuses it."""
+
+    def __init__(self, ctx: Context, x, y, z, w, d, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2):
+        self._h = _vp()
+        x, y, z, w, d, c = (_f64(col) for col in (x, y, z, w, d, c))
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(x)
+        if any(col is not None and len(col) != n for col in (y, z, w, d, c)):
+            raise ValueError("catalogue columns differ in length")
+        if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
+            raise ValueError("offsets must have n_patches * n_bins + 1 entries")
+        self.ctx = ctx  # keep the context alive
+        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
+        self.n_bins = int(n_bins)
+        _check(load_library().yawhip_proj_upload(ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(d, _dp),
+                                                 _ptr(c, _dp), self.n_patches, self.n_bins, _ptr(offsets, _i64p), self.sort_axis,
+                                                 ctypes.byref(self._h)),
+               "yawhip_proj_upload")
+        ctx._shear.add(self)
+
+
+def proj_count(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pmax: float):
+    """Run ``yawhip_proj_count`` on two projected handles (``a is b`` allowed): cells int[n_cells, 4] = ``(segment of a, segment
+    of b, row, diagonal)`` with a segment ``patch * n_bins + bin`` of its handle and ``diagonal`` non-zero iff the cell pairs
+    a segment of one handle with itself; ``r2`` f64[n_rows, E] squared radius edges; ``pmax >= 0`` the largest
+    ``|c_a - c_b|`` of a pair that counts (``inf``: no cut). Returns ``(W, CountStats)``, W f64[n_cells, E-1]: the sums of
+    ``w_a w_b``, a diagonal cell holding every unordered pair once."""
+    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 4)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    if r2.ndim != 2:
+        raise ValueError("r2 must be [n_rows, n_edges]")
+    n_rows, n_edges = r2.shape
+    out = np.empty((len(cells), max(n_edges - 1, 0)), dtype=np.float64)  # the library writes every element
+    st = _Stats()
+    _check(
+        load_library().yawhip_proj_count(ctx._h, a._h, b._h, len(cells), _ptr(cells, _i32p), n_rows, n_edges, _ptr(r2, _dp),
+                                         float(pmax), _ptr(out, _dp), ctypes.byref(st)),
+        "yawhip_proj_count",
+    )
+    return out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
 
 
 def _shear_counts(symbol: str, n_planes: int, handles, jobs, thresholds):

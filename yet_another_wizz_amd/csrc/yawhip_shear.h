@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (tangential shear, shear-shear and excess-surface-density counts, yawhip_shear_* and
-// yawhip_dsigma_*, include/yawhip.h; DESIGN.md sections 15 to 19): the source handle and what its kernels see of it. Never
+// yawhip_dsigma_* and yawhip_proj_*, include/yawhip.h; DESIGN.md sections 15 to 20): the source handle and what its kernels see of it. Never
 // installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
@@ -15,7 +15,9 @@
 // of yawhip_shear_pair_count. A handle of yawhip_dsigma_upload_sources is an unbinned one with the column u besides; one of
 // yawhip_dsigma_upload_lenses (`lenses`) holds the lens columns f, c, as they came, in the place of wg1, wg2: only
 // yawhip_dsigma_count takes it. One of yawhip_dsigma_upload_lenses_radial is such a lens handle with the column m besides
-// (the squared transverse distance per radian of every lens), which yawhip_dsigma_count_radial bins by.
+// (the squared transverse distance per radian of every lens), which yawhip_dsigma_count_radial bins by. One of
+// yawhip_proj_upload (`projected`) is a lens handle whose two raw columns are d, c (transverse distance per radian and
+// line-of-sight coordinate of every object): only yawhip_proj_count takes it.
 struct yawhip_shear_sources {
     yawhip_ctx *ctx = nullptr;
     int64_t n = 0;
@@ -28,6 +30,8 @@ struct yawhip_shear_sources {
     bool lenses = false;                        // a lens handle: wg1, wg2 hold f, c
     yawhip_detail::DevPtr<double> m;            // a radial lens handle: the lenses' column m in segment order, or null
     std::vector<double> min_m;                  // ... and its minimum per redshift bin over all patches [nb] (+inf: no lens)
+    bool projected = false;                     // a handle of yawhip_proj_upload: a lens handle whose wg1, wg2 hold d, c
+    std::vector<double> min_d;                  // ... and the minimum of d per redshift bin over all patches [nb] (+inf: none)
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;
     // per-call buffers of the counts (grow-only; yawhip_shear_pair_count uses those of its first handle)

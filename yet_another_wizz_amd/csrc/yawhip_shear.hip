@@ -5,10 +5,12 @@
 // two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic), and the excess
 // surface density sums of sources with a distance column around lenses with two (yawhip_dsigma_count;
 // measurements.crosscorrelate_delta_sigma), those binned in each lens's own radius instead of one angle
-// per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers). include/yawhip.h
+// per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers), and the projected
+// pair counts of objects with a transverse distance and a line-of-sight coordinate, binned in each PAIR's own radius inside a
+// line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected). include/yawhip.h
 // has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under five thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under six thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -37,6 +39,9 @@
 // s = f (1 - c u), dropped altogether where 1 - c u <= 0 (the source in front of its lens).
 // DeltaSigmaRadial (k_count_dsigma_radial) is DeltaSigma with a 64-byte streamed object (x, y, z, m | w, f, c, pad): the ballot
 // holds m_l s2 against the row's last squared radius, and behind it the pair is binned by R2 = m_l th2(s2) (at the policy).
+// Projected (k_count_projected) is ShearPair's cell table, window rule and diagonal cells over two projected handles with a
+// 48-byte streamed object (x, y, z, d | w, c) and ONE plane: the ballot holds DD s2, DD = (0.5 (d_a + d_b))^2, against the
+// row's last squared radius, the pair is binned by R2 = DD th2(s2) and adds w_a w_b iff |c_a - c_b| <= pmax (at the policy).
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -95,7 +100,16 @@ struct alignas(16) Obj8 {
     double x, y, z, m, w, g1, g2, pad;  // (g1, g2: the lens columns f, c, where a lens handle keeps them)
 };
 
-struct Lane {  // what a lane keeps of its own object in registers (g1, g2: the weighted shear; u: DeltaSigma's column, else 0)
+// One streamed object of the projected count: (x, y, z, d | w, c). The hot loop reads x, y, z, d (two 16-byte broadcast reads:
+// 48 is a multiple of 16, so every object starts on a 16-byte boundary), w and c only behind the ballot.
+struct alignas(16) ObjP {
+    double x, y, z, d, w, c;
+};
+
+// What a lane keeps of its own object in registers (g1, g2: the weighted shear -- of a lens or projected handle its two raw
+// columns; u: what the policy's lane_u() gives: DeltaSigma's column, Projected's pmax, else 0). Not every policy uses every
+// member (Projected: not rho2); what a kernel does not read the compiler drops.
+struct Lane {
     double x, y, z, w, g1, g2, rho2, u;
 };
 
@@ -120,16 +134,29 @@ struct Cell {
 // `wh` the wave's histogram [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of
 // include/yawhip.h.
 //
-// Two seams say what a pair is binned by: outer(b, s) is what the ballot holds against the row's last edge, binned(b, s) what
-// is bisected over the row behind it (s: the pair's squared chord, b: the streamed object). Where a count bins the chord
-// itself both ARE s and compile away; then s <= last edge also keeps the bisection inside the row (CAPPED).
+// Two seams say what a pair is binned by: outer(a, b, s) is what the ballot holds against the row's last edge, binned(a, b, s)
+// what is bisected over the row behind it (s: the pair's squared chord, a: the lane, b: the streamed object). Where a count
+// bins the chord itself both ARE s and compile away; then s <= last edge also keeps the bisection inside the row (CAPPED).
 struct ChordBinned {
     static constexpr bool CAPPED = true;
+    static constexpr bool KEPT_WORK = false;  // the evaluated separations of a diagonal cell: all of them (else: kept_work)
     template <class B>
-    static __device__ __forceinline__ double outer(const B &, double s) { return s; }
+    static __device__ __forceinline__ double outer(const Lane &, const B &, double s) { return s; }
     template <class B>
-    static __device__ __forceinline__ double binned(const B &, double s) { return s; }
+    static __device__ __forceinline__ double binned(const Lane &, const B &, double s) { return s; }
 };
+
+// th2 = s q(s) = (2 asin(sqrt(s) / 2))^2 of a squared chord s <= 0.01 (Horner, every operation rounded on its own; the
+// contract of the two counts binned in a radius, include/yawhip.h)
+__device__ __forceinline__ double squared_angle(double s) {
+    double q = 1.0 / 16632.0;
+    q = 1.0 / 3150.0 + s * q;
+    q = 1.0 / 560.0 + s * q;
+    q = 1.0 / 90.0 + s * q;
+    q = 1.0 / 12.0 + s * q;
+    q = 1.0 + s * q;
+    return s * q;
+}
 
 struct Tangential : ChordBinned {
     using View = CatView;  // the streamed side: the lenses
@@ -297,21 +324,73 @@ struct DeltaSigmaRadial : DeltaSigma {
         o.pad = 0.0;
         return o;
     }
-    static __device__ __forceinline__ double outer(const Obj8 &b, double s) { return b.m * s; }
-    static __device__ __forceinline__ double binned(const Obj8 &b, double s) {
-        double q = 1.0 / 16632.0;
-        q = 1.0 / 3150.0 + s * q;
-        q = 1.0 / 560.0 + s * q;
-        q = 1.0 / 90.0 + s * q;
-        q = 1.0 / 12.0 + s * q;
-        q = 1.0 + s * q;
-        const double th2 = s * q;
-        return b.m * th2;
-    }
+    static __device__ __forceinline__ double outer(const Lane &, const Obj8 &b, double s) { return b.m * s; }
+    static __device__ __forceinline__ double binned(const Lane &, const Obj8 &b, double s) { return b.m * squared_angle(s); }
     static __device__ void add(const Lane &a, const Obj8 &b, double *wh, int e, int nf) {
         DeltaSigma::add(a, Obj6{b.x, b.y, b.z, b.w, b.g1, b.g2}, wh, e, nf);  // the pair term is DeltaSigma's
     }
 };
+
+// The lanes of the projected count: a projected handle (wg1, wg2 hold d, c as they came) and the call's pmax, which reaches
+// the pair term as the lane's u -- the walk and the other policies know nothing of it.
+struct ProjLanes : ShearView {
+    double pmax;
+};
+
+// Pair counts binned in each PAIR's own radius inside a line-of-sight cut (k_count_projected): cells,
+// window rule and diagonal cells are ShearPair's over two projected handles; the row holds squared radii r2, every object
+// carries d (transverse distance per radian, > 0) and c (line-of-sight coordinate), and a pair is binned by
+//   R2 = DD th2(s2),   DD = D D,   D = 0.5 (d_a + d_b)
+// and adds w_a w_b iff |c_a - c_b| <= pmax. d_a + d_b, fabs of the difference and w_a w_b do not change when a and b swap, so
+// a diagonal cell walks the larger indices only.
+// The ballot holds fl(DD s2) against the last edge: DeltaSigmaRadial's proof with DD in the place of m. Every coefficient of q
+// and s2 are >= 0, so each Horner step is >= its constant and q >= 1 after rounding; rounding is monotone, so
+// th2 = fl(s2 q) >= fl(s2 * 1) = s2 and R2 = fl(DD th2) >= fl(DD s2) (DD >= 0). A pair with R2 <= r2max therefore has
+// fl(DD s2) <= r2max: an EXACT superset, with no guard term. The converse fails: a pair behind the ballot with R2 beyond the last
+// edge runs off the row and is dropped (!CAPPED).
+// A padded lane is parked at PAD_COORD with d_a = c_a = 0 and is excluded by `ok` before anything is binned. A padded streamed
+// object (beyond the window, !have) has d = 0, which WOULD pass the outer test: nobody reads it, the loop over a stage stops at
+// the stage's count n.
+struct Projected : ShearPair {
+    using Streamed = ObjP;      // (x, y, z, d | w, c)
+    using Read = const ObjP &;  // the hot loop reads x, y, z, d (two ds_read_b128); w, c behind the ballot
+    using Lanes = ProjLanes;
+    static constexpr int PLANES = 1;  // W
+    static constexpr bool CAPPED = false;
+    static constexpr bool KEPT_WORK = true;  // evaluated <= candidates also on a diagonal cell smaller than its window
+    static __device__ ObjP load(const ShearView &v, int64_t i, bool have) {
+        ObjP o;
+        o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
+        o.d = have ? v.wg1[i] : 0.0;
+        o.w = (have && v.w) ? v.w[i] : 1.0;
+        o.c = have ? v.wg2[i] : 0.0;
+        return o;
+    }
+    static __device__ double lane_u(const ProjLanes &src, int64_t, bool) { return src.pmax; }  // call-wide: a scalar register
+    static __device__ __forceinline__ double pair_dd(const Lane &a, const ObjP &b) {
+        const double D = 0.5 * (a.g1 + b.d);
+        return D * D;
+    }
+    static __device__ __forceinline__ double outer(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * s; }
+    static __device__ __forceinline__ double binned(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * squared_angle(s); }
+    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int) {
+        if (fabs(a.g2 - b.c) <= a.u) atomicAdd(&wh[e], a.w * b.w);
+    }
+};
+
+// The separations of a diagonal cell's lane tile [ta, t_last] against the streamed objects [b0, b1), b0 > ta, that the index
+// test can keep -- the streamed index larger than the lane's: what a policy with KEPT_WORK reports as evaluated, so that a
+// cell's figure never exceeds its unordered pairs. (The waves evaluate the others of the tile's own range too, and drop them.)
+__device__ __forceinline__ unsigned long long kept_work(int64_t ta, int64_t t_last, int64_t b0, int64_t b1) {
+    const int64_t below = (t_last < b0 - 1 ? t_last : b0 - 1) - ta + 1;  // lanes with every streamed object above them
+    unsigned long long kept = (unsigned long long)below * (unsigned long long)(b1 - b0);
+    const int64_t hi = t_last < b1 - 1 ? t_last : b1 - 1;  // lanes b0 .. hi keep b1 - 1 - ia each
+    if (hi >= b0) {
+        const int64_t m = hi - b0 + 1;
+        kept += (unsigned long long)(m * (2 * (b1 - 1) - b0 - hi) / 2);
+    }
+    return kept;
+}
 
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
 template <class P>
@@ -321,7 +400,8 @@ constexpr size_t lds_bytes(int n_edges) {
 }
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024 &&
                   lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024 && lds_bytes<DeltaSigma>(MAX_EDGES) <= 64 * 1024 &&
-                  lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= 64 * 1024,  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
+                  lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= 64 * 1024 &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
+                  lds_bytes<Projected>(MAX_EDGES) <= 64 * 1024,  // (34 784: 2 * 256 * 48 + 2048 + 4 * 1 * 255 * 8)
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
@@ -355,7 +435,7 @@ __global__ void k_gather_column(int64_t n, const uint32_t *__restrict__ perm, co
 // The walk of one cell = one workgroup. str: the streamed side, src: the side in the lanes; `table` and n_bins are the policy's
 // (P::cell); t: [rows][n_edges], rwin: [rows].
 // out: [PLANES][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
-// diagonal cell that includes the few of a tile's first stage that the index test then drops)
+// diagonal cell that includes the few of a tile's first stage that the index test then drops, unless the policy has KEPT_WORK)
 template <class P>
 __device__ __forceinline__ void shear_walk(const typename P::View &str, const typename P::Lanes &src, const int32_t *__restrict__ table,
                                            int n_bins, int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
@@ -408,7 +488,7 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
         if (diag && b0 <= ta) b0 = ta + 1;  // a partner with a larger index than some lane of the tile
         const int64_t nb_total = b1 - b0;
         if (nb_total <= 0) continue;  // (the same for every thread)
-        work += (unsigned long long)(t_last - ta + 1) * (unsigned long long)nb_total;
+        work += (P::KEPT_WORK && diag) ? kept_work(ta, t_last, b0, b1) : (unsigned long long)(t_last - ta + 1) * (unsigned long long)nb_total;
 
         // this lane's object -> registers; padded lanes are parked far away
         const int64_t ia = ta + tid;
@@ -452,16 +532,16 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
                 const double zz = dz * dz;
                 const double sxy = xx + yy;
                 const double s = sxy + zz;
-                const double so = P::outer(b, s);  // (s itself, but for the radial count)
+                const double so = P::outer(a, b, s);  // (s itself, but for the counts binned in a radius)
                 if (__builtin_amdgcn_ballot_w64(so <= tmax) != 0ull) {  // rare: some lane has a pair inside the outer edge
                     if (ok && so <= tmax) {
-                        const double v = P::binned(b, s);
+                        const double v = P::binned(a, b, s);
                         int cnt = 0, hi = n_edges;  // edges below v (they ascend): the first e with thr[e] >= v, by bisection
                         while (cnt < hi) {
                             const int mid = (cnt + hi) >> 1;
                             if (thr[mid] < v) cnt = mid + 1; else hi = mid;
                         }
-                        // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the radial count alone -- has cnt == n_edges and no bin:
+                        // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the counts binned in a radius -- has cnt == n_edges and no bin:
                         // the histogram has nf of them), and not the lower half of a diagonal cell
                         if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) P::add(a, b, wh, cnt - 1, nf);
                     }
@@ -520,6 +600,14 @@ __global__ __launch_bounds__(WG) void k_count_dsigma_radial(RadialView lens, Sou
                                                             const double *__restrict__ rwin, int64_t n_cells, double *__restrict__ out,
                                                             unsigned long long *__restrict__ evaluated) {
     shear_walk<DeltaSigmaRadial>(lens, src, jobs, n_bins, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
+// out: [1][n_cells][E-1] (W); cells: [n_cells][4] (ShearPair::cell); a is streamed, b sits in the lanes with the call's pmax
+__global__ __launch_bounds__(WG) void k_count_projected(ShearView a, ProjLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                        const double *__restrict__ r2, const double *__restrict__ rwin,
+                                                        int64_t n_cells, double *__restrict__ out,
+                                                        unsigned long long *__restrict__ evaluated) {
+    shear_walk<Projected>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -736,13 +824,42 @@ int check_positive(const char *fn, const char *name, int64_t n, const double *v)
     return YAWHIP_OK;
 }
 
+// the column c of yawhip_proj_upload: finite
+int check_finite(const char *fn, const char *name, int64_t n, const double *v) {
+    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i]))
+            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number (index %lld)", fn, name, (long long)i);
+    return YAWHIP_OK;
+}
+
+// The least entry of column v per redshift bin over all patches of the handle just uploaded (its offsets are checked by
+// now), kept in its member `least`; a bin without objects: +inf. Out of memory frees the handle.
+int least_per_bin(const char *fn, yawhip_shear_sources **out, std::vector<double> yawhip_shear_sources::*least, const double *v,
+                  int32_t n_patches, int32_t n_bins, const int64_t *offsets) {
+    yawhip_shear_sources *s = *out;
+    try {
+        (s->*least).assign((size_t)n_bins, INFINITY);
+    } catch (const std::bad_alloc &) {
+        yawhip_shear_free(s);
+        *out = nullptr;
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    for (int64_t seg = 0; seg < (int64_t)n_patches * n_bins; ++seg) {
+        double &least_of_bin = (s->*least)[(size_t)(seg % n_bins)];
+        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i) least_of_bin = std::min(least_of_bin, v[i]);
+    }
+    return YAWHIP_OK;
+}
+
 // the argument checks of the two excess-surface-density counts (t: thresholds or squared radii), and their candidate pairs
 int check_dsigma(const char *fn, yawhip_ctx *ctx, const yawhip_shear_sources *lenses, const yawhip_shear_sources *sources, int32_t n_jobs,
                  const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, bool planes, int64_t *candidates) {
     if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "%s: NULL handle", fn);
     if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && planes)) return rc;
     if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (!lenses->lenses) return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses", fn);
+    if (!lenses->lenses || lenses->projected)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses", fn);
     if (sources->lenses || !sources->u)
         return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are not a handle of yawhip_dsigma_upload_sources", fn);
     if (sources->nb != 1)
@@ -949,20 +1066,8 @@ int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double 
     }
     if (const int rc = upload_segments(fn, ctx, n, x, y, z, w, f, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true, n > 0 ? m : &one))
         return rc;
-    // the nearest lens of every redshift bin over all patches (the offsets are checked by now); a bin without lenses: +inf
-    yawhip_shear_sources *s = *out;
-    try {
-        s->min_m.assign((size_t)n_bins, INFINITY);
-    } catch (const std::bad_alloc &) {
-        yawhip_shear_free(s);
-        *out = nullptr;
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
-    for (int64_t seg = 0; seg < (int64_t)n_patches * n_bins; ++seg) {
-        double &least = s->min_m[(size_t)(seg % n_bins)];
-        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i) least = std::min(least, m[i]);
-    }
-    return YAWHIP_OK;
+    // the nearest lens of every redshift bin over all patches; a bin without lenses: +inf
+    return least_per_bin(fn, out, &yawhip_shear_sources::min_m, m, n_patches, n_bins, offsets);
 }
 
 int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
@@ -998,6 +1103,82 @@ int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, ya
                          hipLaunchKernelGGL(k_count_dsigma_radial, dim3((unsigned)n_cells), dim3(WG), lds_bytes<DeltaSigmaRadial>(n_edges),
                                             ctx->stream, RadialView{LensView{view_of(lenses), lenses->nb}, lenses->m},
                                             SourceView{view_of(sources), sources->u}, d_jobs, n_bins, n_edges, d_r2, d_rwin, n_cells, d_out, d_eval);
+                     },
+                     smax.data());
+}
+
+int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                       const double *d, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                       int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_proj_upload";
+    if (out) *out = nullptr;
+    if (n > 0) {
+        if (const int rc = check_positive(fn, "d", n, d)) return rc;
+        if (const int rc = check_finite(fn, "c", n, c)) return rc;
+    }
+    // a lens handle: the two columns are kept as they came, in the place of wg1, wg2
+    if (const int rc = upload_segments(fn, ctx, n, x, y, z, w, d, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true)) return rc;
+    (*out)->projected = true;
+    // the nearest object of every redshift bin over all patches; a bin without objects: +inf
+    return least_per_bin(fn, out, &yawhip_shear_sources::min_d, d, n_patches, n_bins, offsets);
+}
+
+int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                      int32_t n_rows, int32_t n_edges, const double *r2, double pmax, double *fine_w, yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "yawhip_proj_count: NULL handle");
+    if (const int rc = check_sizes(fn, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
+    if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    if (!a->projected || !b->projected) return fail(YAWHIP_ERR_MISMATCH, "%s: a handle is not one of yawhip_proj_upload", fn);
+    if (!(pmax >= 0.0)) return fail(YAWHIP_ERR_INVALID, "%s: pmax must be a number >= 0 (+inf: no line-of-sight cut)", fn);
+    const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
+    if (segs_a > INT32_MAX || segs_b > INT32_MAX) return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
+    if (const int rc = check_thresholds(n_rows, n_edges, r2)) return rc;
+
+    // The largest squared chord of a pair in range, per row: fl(DD s2) <= r2max needs s2 <= r2max / DD (1 + 2 eps), and
+    // D = fl(0.5 (d_a + d_b)) is no less than the smaller of the two (rounding is monotone), which is no less than the least d
+    // of the bins that the row's cells pair. A row without cells, or with an empty bin on either side, has no pairs: 0.
+    std::vector<double> least, smax;
+    try {
+        least.assign((size_t)n_rows, 0.0);
+        smax.assign((size_t)n_rows, 0.0);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
+    for (int c = 0; c < n_cells; ++c) {
+        const int32_t *cell = cells + 4 * (size_t)c;
+        const int32_t sa = cell[0], sb = cell[1], row = cell[2];
+        if (sa < 0 || sa >= segs_a || sb < 0 || sb >= segs_b)
+            return fail(YAWHIP_ERR_INVALID, "cell %d has a segment outside [0,%lld) x [0,%lld)", c, (long long)segs_a, (long long)segs_b);
+        if (row < 0 || row >= n_rows) return fail(YAWHIP_ERR_INVALID, "cell %d has a row outside [0,%d)", c, n_rows);
+        const bool diag = a == b && sa == sb;
+        if ((cell[3] != 0) != diag)
+            return fail(YAWHIP_ERR_INVALID, "cell %d: a cell is diagonal iff it pairs a segment of one handle with itself", c);
+        const int64_t n_a = a->h_off[(size_t)sa + 1] - a->h_off[(size_t)sa], n_b = b->h_off[(size_t)sb + 1] - b->h_off[(size_t)sb];
+        candidates += diag ? n_a * (n_a - 1) / 2 : n_a * n_b;
+        const double nearest = std::min(a->min_d[(size_t)(sa % a->nb)], b->min_d[(size_t)(sb % b->nb)]);
+        if (std::isinf(a->min_d[(size_t)(sa % a->nb)]) || std::isinf(b->min_d[(size_t)(sb % b->nb)])) continue;  // an empty bin
+        least[(size_t)row] = least[(size_t)row] == 0.0 ? nearest : std::min(least[(size_t)row], nearest);
+    }
+    // Beyond 0.01 (5.73 degrees) the series of the squared angle loses its last bits: refused
+    for (int k = 0; k < n_rows; ++k) {
+        const double top = r2[(size_t)k * n_edges + n_edges - 1];
+        if (std::isinf(top)) return fail(YAWHIP_ERR_INVALID, "squared radii of row %d are not finite", k);
+        if (least[(size_t)k] == 0.0) continue;
+        smax[(size_t)k] = top / (least[(size_t)k] * least[(size_t)k]) * (1.0 + 1e-12);
+        if (!(smax[(size_t)k] <= 0.01))
+            return fail(YAWHIP_ERR_INVALID, "%s: an object is too close for the largest radius (row %d: the reach is a squared chord of %g, at most 0.01)",
+                        fn, k, smax[(size_t)k]);
+    }
+    double *const fine[] = {fine_w};
+    return run_count(fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, Projected::PLANES, fine, candidates,
+                     wall0, stats,
+                     [&](const int32_t *d_cells, const double *d_r2, const double *d_rwin, int64_t cells_n, double *d_out,
+                         unsigned long long *d_eval) {
+                         hipLaunchKernelGGL(k_count_projected, dim3((unsigned)cells_n), dim3(WG), lds_bytes<Projected>(n_edges), ctx->stream,
+                                            view_of(a), ProjLanes{view_of(b), pmax}, d_cells, n_edges, d_r2, d_rwin, cells_n, d_out, d_eval);
                      },
                      smax.data());
 }

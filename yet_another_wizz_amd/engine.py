@@ -14,7 +14,7 @@ import os
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "count_projected_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -368,6 +368,87 @@ def count_dsigma_radial_fine(lens_layout, source_layout, jobs, r2, *, cosmology,
         m = dsigma_radial_columns(lens_layout, None, cosmology, unit, unit_columns=unit_columns)[2]
         check_radial_reach(lens_layout, m, r2)  # the same refusal, with the lens's redshift and the radius
         raise
+
+
+def proj_columns(layout, cosmology, unit):
+    """The two columns ``yawhip_proj_count`` reads (include/yawhip.h), from the layout's redshifts
+    (``build_trees(edges, with_redshifts=True)``) and ``cosmology`` (assumed flat), each in the layout's order: ``(d, c)`` =
+    the transverse distance per radian in Mpc -- ``D_A(z)`` for ``kpc`` / ``Mpc``, ``D_A(z) (1 + z)`` for ``kpc/h`` /
+    ``Mpc/h`` (``radial_kind``, the conversions of ``dsigma_radial_columns``) -- and the comoving distance ``chi(z)`` in Mpc.
+    ``Scales`` reads a ``/h`` unit as a comoving length in the cosmology's own Mpc (it applies no factor ``h``), and so do
+    the radii of ``radial_plans``; ``c`` and ``pi_max`` are lengths of that kind too, for all four units. Redshifts must be
+    finite and ``> 0`` and the distances finite (``ValueError`` otherwise)."""
+    from .cosmology import distance_column
+
+    kind = radial_kind(unit)
+    z = check_proj_redshifts(layout)
+    d, c = distance_column(cosmology, z, kind="angular"), distance_column(cosmology, z, kind="comoving")
+    if kind == "comoving":
+        d = d * (1.0 + z)
+    if not (np.all(np.isfinite(d)) and np.all(d > 0.0) and np.all(np.isfinite(c))):
+        raise ValueError("the cosmology gives distances that are not finite numbers > 0")
+    return d, c
+
+
+def check_proj_redshifts(layout):
+    """The redshifts of a layout for a projected count: present, finite and ``> 0`` (``ValueError`` otherwise)."""
+    z = layout.redshifts
+    if z is None:
+        raise ValueError("the catalogue carries no redshifts: build_trees(..., with_redshifts=True)")
+    if not (np.all(np.isfinite(z)) and np.all(z > 0.0)):
+        raise ValueError("the redshifts of a projected count must be finite and > 0")
+    return z
+
+
+def check_pi_max(pi_max) -> float:
+    """``pi_max`` of a projected count as a float: a length ``> 0`` and finite (``ValueError`` otherwise)."""
+    pi_max = float(pi_max)
+    if not (np.isfinite(pi_max) and pi_max > 0.0):
+        raise ValueError(f"pi_max must be a finite length > 0, not {pi_max}")
+    return pi_max
+
+
+def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, unit, sort_axis: int = 2):
+    """Fine-bin projected pair counts for ``cells`` (int[n, 4] = ``(segment of layout_a, segment of layout_b, row of r2,
+    diagonal)``, a segment ``patch * num_bins + bin``; ``diagonal`` non-zero iff the cell pairs a segment with itself, which
+    takes ``layout_b is layout_a``) -> ``(W, CountStats)``, W f64[n_cells, E-1]: the sums of ``w_a w_b`` over the pairs
+    with ``|chi_a - chi_b| <= pi_max`` in the fine bin that holds ``R^2 = (0.5 (d_a + d_b))^2 theta^2``, a diagonal cell
+    holding every unordered pair once (``yawhip_proj_count``; ``proj_columns`` makes the columns, ``r2`` f64[n_rows, E] are
+    squared radius edges in Mpc^2). Both are layouts with redshifts; each reaches the device once as a ``_lib.ProjHandle``
+    kept on the layout per context, sort axis, cosmology and kind of unit; the same layout twice is ONE handle passed
+    twice. A reach beyond the library's cap is ``check_radial_reach``'s ``ValueError`` with the object's redshift. No CPU
+    fallback; the CPU tests replace this function."""
+    ctx = get_context()
+    role = f"projected {radial_kind(unit)}"
+
+    def handle(layout):
+        def upload():
+            d, c = proj_columns(layout, cosmology, unit)
+            return _lib.ProjHandle(ctx, layout.x, layout.y, layout.z, layout.w, d, c, layout.num_patches, layout.num_bins,
+                                   layout.offsets, sort_axis=sort_axis)
+
+        return _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload)
+
+    a = handle(layout_a)
+    b = a if layout_b is layout_a else handle(layout_b)
+    try:
+        return _lib.proj_count(ctx, a, b, cells, r2, pi_max)
+    except _lib.YawhipError as err:
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
+        raise
+
+
+def check_projected_reach(layouts, cosmology, unit, r2):
+    """``check_radial_reach`` for the layouts of a projected count whose cells pair bin ``k`` with bin ``k`` and row ``k``: the
+    pair's ``D = (d_a + d_b) / 2`` is no less than the nearest object's ``d``, so ``m = d^2`` of either side bounds the
+    reach. Returns the largest ``smax`` per bin over the layouts."""
+    smax = np.zeros(len(r2))
+    for layout in layouts:
+        d = proj_columns(layout, cosmology, unit)[0]
+        smax = np.maximum(smax, check_radial_reach(layout, d * d, r2))
+    return smax
 
 
 def _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload):

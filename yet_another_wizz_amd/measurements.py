@@ -26,7 +26,7 @@ from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
-__all__ = ["autocorrelate", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
+__all__ = ["autocorrelate", "autocorrelate_projected", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
            "crosscorrelate_shear", "crosscorrelate_delta_sigma", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "radial_plans", "radial_max_angle", "check_patch_conistency"]
 
@@ -671,6 +671,54 @@ class PatchLinkage:
                  for i in range(num_bins)]
                 for s in range(num_scales)]
 
+    def count_projected_pairs(self, main_catalog: Catalog, second_catalog: Catalog | None = None, *, pi_max: float, progress: bool = False,
+                              max_workers: int | None = None, count_type_info: str | None = None) -> list:
+        """Pair counts of one (auto) or two catalogues with every pair binned in its OWN transverse radius
+        ``R = (d_a + d_b) / 2 * theta`` (physical or comoving, as the unit of the scales says) and kept only if its
+        line-of-sight separation ``|chi_a - chi_b|`` is at most ``pi_max`` (a comoving length in Mpc) -> one
+        ``NormalisedCounts`` per scale on the configuration's binning, as ``count_pairs`` returns them. Both catalogues are
+        binned with redshifts (``build_trees(edges, with_redshifts=True)``); bin ``k`` of one side is paired with bin ``k`` of
+        the other over the linked patch pairs (``i <= j`` for an auto count). The edges are the radii of ``radial_plans``,
+        the same in every redshift bin, separation weights and per-scale sums ``CombinePlan``'s. A diagonal slot of an auto
+        count holds every unordered pair of its patch once -- what ``count_pairs`` holds there after its x 0.5 -- and the
+        normalisation is ``count_pairs``' ``PatchedSumWeights``. The linkage must reach as far as the nearest object sees the
+        largest radius (``from_catalogs(max_angle=radial_max_angle(...))``). ONE library call counts all cells
+        (``engine.count_projected_fine``), on one device of one process: several ranks raise ``NotImplementedError``
+        (``max_workers`` is accepted and has no effect)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("projected counts run in one process on one device")
+        pi_max = engine.check_pi_max(pi_max)
+        if count_type_info is not None:
+            _log_info("counting %s from patch pairs", count_type_info)
+        auto = second_catalog is None
+        cat2 = main_catalog if auto else second_catalog
+        binning = self.config.binning.binning
+        num_bins, num_patches = len(binning), len(main_catalog)
+        layout1, layout2 = _active_layout(main_catalog, num_bins), _active_layout(cat2, num_bins)
+        for layout in (layout1, layout2):
+            if layout.redshifts is None or layout.num_bins != num_bins:
+                raise ValueError("a projected count needs layouts binned in redshift that carry redshifts: "
+                                 "build_trees(edges, with_redshifts=True)")
+        jobs = self.get_patch_pairs(main_catalog, None if auto else cat2)
+        plans = radial_plans(self.config)
+        r2, combine = threshold_table(plans), CombinePlan(plans)
+        # cell (job, k): segment (p, k) of the first side against (q, k) of the second, row k; diagonal iff one segment twice
+        seg1 = (jobs[:, :1].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
+        seg2 = (jobs[:, 1:].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
+        diagonal = (seg1 == seg2) if auto else np.zeros(len(seg1), dtype=bool)
+        cells = np.column_stack([seg1, seg2, np.tile(np.arange(num_bins), len(jobs)), diagonal]).astype(np.int32).reshape(-1, 4)
+        fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, cosmology=self.config.cosmology,
+                                                  unit=self.config.scales.scales.unit, sort_axis=self.sort_axis)
+        self.last_stats = stats
+        self._report(count_type_info, len(jobs), stats, progress)
+        flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
+        shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
+        # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
+        fine = np.asarray(fine, dtype=np.float64).reshape(len(jobs), num_bins, r2.shape[1] - 1)
+        counts = _lib.scatter_rows(shape, flat, combine(np.moveaxis(fine, 0, -1)))
+        sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
+        return [NormalisedCounts(PatchedCounts(binning, counts[s], auto=auto), sum_weights) for s in range(shape[0])]
+
     def _count_shear_planes(self, catalogs, layouts, count_type_info, progress, radial: bool = False):
         """What the two shear counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the engine's
         count (``count_shear_fine`` / ``count_shear_auto_fine``, looked up at call time: the CPU tests replace them) with the
@@ -771,6 +819,49 @@ def autocorrelate(config, data: Catalog, random: Catalog, *, count_rr: bool = Tr
     DD, DR, RR = links.count_pairs_batch(
         [((data,), "DD"), ((data, random), "DR"), ((random if count_rr else None,), "RR")],
         progress=progress, max_workers=max_workers)
+    return [CorrFunc(dd, dr, None, rr) for dd, dr, rr in zip(DD, DR, RR)]
+
+
+def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: float, count_rr: bool = True, progress: bool = False,
+                            max_workers: int | None = None) -> list:
+    """Projected clustering of ``data`` in each pair's own transverse radius: DD, DR and (optionally) RR of the pairs with a
+    line-of-sight separation ``|chi_a - chi_b| <= pi_max``, binned by ``r_p = (d_a + d_b) / 2 * theta`` -> ``[CorrFunc(dd, dr,
+    None, rr)]``, one per scale of the configuration (no counterpart in the reference).
+
+    ``cf.sample()`` is the Landy-Szalay estimate (Davis-Peebles without RR) of the correlation function averaged over the
+    cylinder ``|pi| <= pi_max`` in each radius bin, ``xi_bar``, with jackknife samples over the patches; the projected
+    correlation function is ``w_p(r_p) = 2 * pi_max * xi_bar``. This is the single-cylinder estimator: the pairs are not
+    binned in ``pi``, and ``xi(r_p, pi)`` is not integrated bin by bin.
+
+    The scales are transverse radii in a physical (``kpc``, ``Mpc``: ``d = D_A(z)``) or comoving (``kpc/h``, ``Mpc/h``:
+    ``d = D_A(z) (1 + z)``) unit; an angular unit is a ``ValueError``. ``pi_max`` is a comoving length in the Mpc the scales
+    are converted with (``Scales`` reads the ``/h`` units as comoving lengths and applies no factor ``h``), finite and
+    ``> 0``. Both catalogues need redshifts, finite and ``> 0``. An object so near that the largest radius spans more than
+    5.73 degrees is a ``ValueError`` that names its redshift.
+
+    Pairs are counted INSIDE a redshift bin of the configuration, as ``autocorrelate`` and ``autocorrelate_shear`` count
+    them: a pair across a bin edge is not counted however close it is in ``pi``. A ``w_p`` measurement therefore takes one
+    bin (or a few wide bins) over the whole sample. The counts run on one device of one process: several ranks raise
+    ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
+    _require_distinct(data, random)
+    if parallel.world()[1] > 1:
+        raise NotImplementedError("projected counts run in one process on one device")
+    pi_max = engine.check_pi_max(pi_max)
+    unit = config.scales.scales.unit
+    engine.radial_kind(unit)  # angular units have no radius: ValueError
+    edges, closed = config.binning.edges, config.binning.closed
+    _log_info("building data trees")
+    data_layout = data.build_trees(edges, closed=closed, with_redshifts=True)
+    _log_info("building random trees")
+    random_layout = random.build_trees(edges, closed=closed, with_redshifts=True)
+    for layout in (data_layout, random_layout):
+        engine.check_proj_redshifts(layout)
+    _log_info("computing projected auto-correlation from DD, DR" + (", RR" if count_rr else ""))
+    links = PatchLinkage.from_catalogs(config, data, random, max_angle=radial_max_angle(config, data_layout, random_layout))
+    kwargs = dict(pi_max=pi_max, progress=progress, max_workers=max_workers)
+    DD = links.count_projected_pairs(data, count_type_info="DD", **kwargs)
+    DR = links.count_projected_pairs(data, random, count_type_info="DR", **kwargs)
+    RR = links.count_projected_pairs(random, count_type_info="RR", **kwargs) if count_rr else [None] * len(DD)
     return [CorrFunc(dd, dr, None, rr) for dd, dr, rr in zip(DD, DR, RR)]
 
 
