@@ -15,7 +15,7 @@ reaches as far as the nearest lens sees ``--rmax``):
 The two do NOT evaluate the same separations: the key window of the per-lens count follows the nearest lens of a redshift
 bin, that of the per-slice count the slice's middle. The comparison is therefore the device time per evaluated separation.
 Each call is run once to warm up, then ``--repeat`` times: the median and the min - max spread of the device time between
-the call's two events (``CountStats.kernel_ms``).
+the call's two events (``CountStats.kernel_ms``), and of the host's wall time around the blocking call.
 
 Every measurement runs in a process of its own, one after the other; this process only starts them and never opens the
 device. Prints one JSON line and appends it to ``--out`` (profiles/dsigma_radial_probe.jsonl holds the committed runs).
@@ -47,6 +47,7 @@ def arguments():
     ap.add_argument("--fine", type=int, default=50)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--parent-tree", default=None, help="another checkout, its library built, to time the per-slice count with")
+    ap.add_argument("--label", default=None, help="a word for the line's \"label\" key, e.g. which tree this run times")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dsigma_radial_probe.jsonl"))
     ap.add_argument("--call", choices=["radial", "slice"], default=None, help="(internal) time this call in this process")
     ap.add_argument("--tree", default=ROOT, help="(internal) the checkout whose package the measuring process imports")
@@ -114,6 +115,7 @@ def measure(args):
                           candidate_pairs=int(stats.candidate_pairs), evaluated=int(stats.evaluated_pairs),
                           kernel_ms=round(statistics.median(device), 3), kernel_ms_min=round(min(device), 3),
                           kernel_ms_max=round(max(device), 3), wall_ms=round(statistics.median(wall), 3),
+                          wall_ms_min=round(min(wall), 3), wall_ms_max=round(max(wall), 3),
                           cells_with_pairs=int(np.count_nonzero(planes[2])), sum_w=float(planes[2].sum()), library=_lib.LIB_PATH)), flush=True)
 
 
@@ -138,12 +140,13 @@ def main():
     radial = child("radial")
     per_slice = child("slice", args.parent_tree or ROOT)
     assert radial["jobs"] == per_slice["jobs"] and radial["candidate_pairs"] == per_slice["candidate_pairs"]
-    line = dict(lenses=int(float(args.lenses)), sources=int(float(args.sources)), patches=args.patches, bins=args.bins, jobs=radial["jobs"],
+    line = dict(probe="tools/probe_dsigma_radial.py", **({"label": args.label} if args.label else {}), lenses=int(float(args.lenses)), sources=int(float(args.sources)), patches=args.patches, bins=args.bins, jobs=radial["jobs"],
                 fine_bins=radial["fine_bins"], rmin_kpc=args.rmin, rmax_kpc=args.rmax, sort_axis=radial["sort_axis"],
                 candidate_pairs=radial["candidate_pairs"], slice_library="parent" if args.parent_tree else "this tree")
     for name, got in (("radial", radial), ("slice", per_slice)):
         line.update({f"{name}_kernel_ms": got["kernel_ms"], f"{name}_kernel_ms_spread": [got["kernel_ms_min"], got["kernel_ms_max"]],
-                     f"{name}_wall_ms": got["wall_ms"], f"{name}_evaluated": got["evaluated"],
+                     f"{name}_wall_ms": got["wall_ms"], f"{name}_wall_ms_spread": [got["wall_ms_min"], got["wall_ms_max"]],
+                     f"{name}_evaluated": got["evaluated"],
                      f"{name}_ps_per_evaluated": round(1e9 * got["kernel_ms"] / max(got["evaluated"], 1), 3),
                      f"{name}_cells_with_pairs": got["cells_with_pairs"], f"{name}_sum_w": got["sum_w"]})
     line.update(per_evaluated_ratio=round(line["radial_ps_per_evaluated"] / line["slice_ps_per_evaluated"], 3),

@@ -136,6 +136,10 @@ class CountStats:
         return {variant_name(c) for c in (self.count_variant, self.count_variant_weighted) if c != 0}
 
 
+def _count_stats(st: _Stats) -> CountStats:
+    return CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+
+
 # yawhip_stats.count_variant* (include/yawhip.h): family in bits 0-3, then the template arguments
 VARIANT_MIXED = -1
 VARIANT_FAMILIES = {1: "k_count", 2: "k_count_merged", 3: "k_count_merged_occ8", 4: "k_count_band", 5: "k_count_band32",
@@ -494,7 +498,7 @@ def count_pairs(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, jobs, thresh
         ),
         "yawhip_count_pairs",
     )
-    stats = CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    stats = _count_stats(st)
     return counts, sums, stats
 
 
@@ -516,7 +520,7 @@ def count_pairs_dense(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, jobs, 
         ),
         "yawhip_count_pairs_dense",
     )
-    return dense, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    return dense, _count_stats(st)
 
 
 def count_pairs_dense_batch(ctx: Context, requests, thresholds, slices, fine_factors, *, kernel="auto"):
@@ -545,7 +549,7 @@ def count_pairs_dense_batch(ctx: Context, requests, thresholds, slices, fine_fac
             _addr(slices, np.int32), _addr(fine_factors, np.float64)),
         "yawhip_count_pairs_dense_batch",
     )
-    return [(d, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})) for d, st in zip(outs, stats)]
+    return [(d, _count_stats(st)) for d, st in zip(outs, stats)]
 
 
 class DeviceRows:
@@ -577,7 +581,7 @@ def count_pairs_rows_device(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, 
         "yawhip_count_pairs_rows_device",
     )
     n = int(n_rows_total) * n_bins * (n_edges - 1) + 1
-    return DeviceRows(out.value, n, ctx.device), CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    return DeviceRows(out.value, n, ctx.device), _count_stats(st)
 
 
 def job_work(ctx: Context, c1: DeviceCatalog, c2: DeviceCatalog, jobs, thresholds, *, kernel="auto") -> np.ndarray:
@@ -793,32 +797,38 @@ class ShearSources:
     shear counts take such a handle and ignore the column."""
 
     def __init__(self, ctx: Context, x, y, z, w, g1, g2, n_patches: int, offsets, sort_axis: int = 2, n_bins: int = 1, u=None):
+        upload = self._prepare(ctx, (x, y, z, w, g1, g2), u, n_patches, n_bins, offsets, sort_axis)
+        if u is not None and n_bins != 1:
+            raise ValueError("the column 'u' goes with an unbinned catalogue")
+        if u is not None:
+            upload("yawhip_dsigma_upload_sources", with_bins=False)
+        else:
+            upload("yawhip_shear_upload" if self.n_bins == 1 else "yawhip_shear_upload_binned", with_bins=self.n_bins != 1)
+
+    def _prepare(self, ctx, columns, extra, n_patches, n_bins, offsets, sort_axis):
+        """What every kind of handle shares: the columns ``x, y, z, w`` and the kind's two, with the column ``extra`` of some
+        kinds where it is given, as float64 of one length; the offsets over ``n_patches * n_bins`` segments; the attributes.
+        Returns ``upload(symbol, with_bins=True)``, which calls the entry point ``symbol(ctx, n, *columns, n_patches,
+        [n_bins,] offsets, sort_axis, &handle)``."""
         self._h = _vp()
-        x, y, z, w, g1, g2, u = (_f64(c) for c in (x, y, z, w, g1, g2, u))
+        columns = [_f64(c) for c in (columns if extra is None else (*columns, extra))]
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(x)
-        if any(c is not None and len(c) != n for c in (y, z, w, g1, g2, u)):
+        n = len(columns[0])
+        if any(c is not None and len(c) != n for c in columns):
             raise ValueError("catalogue columns differ in length")
         if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
             raise ValueError("offsets must have n_patches * n_bins + 1 entries")
-        if u is not None and n_bins != 1:
-            raise ValueError("the column 'u' goes with an unbinned catalogue")
         self.ctx = ctx  # keep the context alive
-        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
+        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), columns[3] is not None, int(sort_axis)
         self.n_bins = int(n_bins)
-        columns = (ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(g1, _dp), _ptr(g2, _dp), self.n_patches)
-        if u is not None:
-            _check(load_library().yawhip_dsigma_upload_sources(*columns[:-1], _ptr(u, _dp), self.n_patches, _ptr(offsets, _i64p),
-                                                               self.sort_axis, ctypes.byref(self._h)),
-                   "yawhip_dsigma_upload_sources")
-        elif self.n_bins == 1:
-            _check(load_library().yawhip_shear_upload(*columns, _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h)),
-                   "yawhip_shear_upload")
-        else:
-            _check(load_library().yawhip_shear_upload_binned(*columns, self.n_bins, _ptr(offsets, _i64p), self.sort_axis,
-                                                             ctypes.byref(self._h)),
-                   "yawhip_shear_upload_binned")
-        ctx._shear.add(self)
+
+        def upload(symbol, with_bins=True):
+            _check(getattr(load_library(), symbol)(ctx._h, n, *(_ptr(c, _dp) for c in columns), self.n_patches,
+                                                   *((self.n_bins,) if with_bins else ()), _ptr(offsets, _i64p), self.sort_axis,
+                                                   ctypes.byref(self._h)), symbol)
+            ctx._shear.add(self)
+
+        return upload
 
     def free(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
@@ -835,56 +845,47 @@ class ShearSources:
 class DsigmaLenses(ShearSources):
     """The lenses of ``dsigma_count`` resident in HBM (``yawhip_dsigma_upload_lenses``): every (patch, bin) segment sorted along
     ``sort_axis`` -- unit vectors, weights (or None) and the two columns ``f, c`` (include/yawhip.h: ``D_A(z_l)`` and ``chi_l``
-    in the driver), finite and ``>= 0``, kept as they come. The handle is a ``yawhip_shear_sources`` marked as lenses: it is
-    freed like one, and the shear counts refuse it. With ``m`` (finite and ``> 0``: the squared transverse distance per radian
+    in the driver), finite and ``>= 0``, kept as they come. The handle is a ``yawhip_shear_sources`` of the lens kind: it is
+    freed like any, and the shear counts refuse it. With ``m`` (finite and ``> 0``: the squared transverse distance per radian
     of every lens, in the squared unit of the radii) it is the radial handle ``dsigma_count_radial`` needs
     (``yawhip_dsigma_upload_lenses_radial``); ``dsigma_count`` takes it too and ignores ``m``."""
 
     def __init__(self, ctx: Context, x, y, z, w, f, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2, m=None):
-        self._h = _vp()
-        x, y, z, w, f, c, m = (_f64(col) for col in (x, y, z, w, f, c, m))
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(x)
-        if any(col is not None and len(col) != n for col in (y, z, w, f, c, m)):
-            raise ValueError("catalogue columns differ in length")
-        if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
-            raise ValueError("offsets must have n_patches * n_bins + 1 entries")
-        self.ctx = ctx  # keep the context alive
-        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
-        self.n_bins = int(n_bins)
+        upload = self._prepare(ctx, (x, y, z, w, f, c), m, n_patches, n_bins, offsets, sort_axis)
         self.radial = m is not None
-        columns = (ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(f, _dp), _ptr(c, _dp))
-        layout = (self.n_patches, self.n_bins, _ptr(offsets, _i64p), self.sort_axis, ctypes.byref(self._h))
-        if self.radial:
-            _check(load_library().yawhip_dsigma_upload_lenses_radial(*columns, _ptr(m, _dp), *layout), "yawhip_dsigma_upload_lenses_radial")
-        else:
-            _check(load_library().yawhip_dsigma_upload_lenses(*columns, *layout), "yawhip_dsigma_upload_lenses")
-        ctx._shear.add(self)
+        upload("yawhip_dsigma_upload_lenses_radial" if self.radial else "yawhip_dsigma_upload_lenses")
 
 
 class ProjHandle(ShearSources):
     """The objects of ``proj_count`` resident in HBM (``yawhip_proj_upload``): every (patch, bin) segment sorted along
     ``sort_axis`` -- unit vectors, weights (or None) and the two columns ``d, c`` (include/yawhip.h: the transverse distance
     per radian, finite and ``> 0``, and the line-of-sight coordinate, finite), kept as they come. The handle is a
-    ``yawhip_shear_sources`` marked as projected: it is freed like one, and every other count refuses it."""
+    ``yawhip_shear_sources`` of the projected kind: it is freed like any, and every other count refuses it."""
 
     def __init__(self, ctx: Context, x, y, z, w, d, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2):
-        self._h = _vp()
-        x, y, z, w, d, c = (_f64(col) for col in (x, y, z, w, d, c))
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        n = len(x)
-        if any(col is not None and len(col) != n for col in (y, z, w, d, c)):
-            raise ValueError("catalogue columns differ in length")
-        if n_bins < 1 or len(offsets) != n_patches * n_bins + 1:
-            raise ValueError("offsets must have n_patches * n_bins + 1 entries")
-        self.ctx = ctx  # keep the context alive
-        self.n, self.n_patches, self.weighted, self.sort_axis = n, int(n_patches), w is not None, int(sort_axis)
-        self.n_bins = int(n_bins)
-        _check(load_library().yawhip_proj_upload(ctx._h, n, _ptr(x, _dp), _ptr(y, _dp), _ptr(z, _dp), _ptr(w, _dp), _ptr(d, _dp),
-                                                 _ptr(c, _dp), self.n_patches, self.n_bins, _ptr(offsets, _i64p), self.sort_axis,
-                                                 ctypes.byref(self._h)),
-               "yawhip_proj_upload")
-        ctx._shear.add(self)
+        self._prepare(ctx, (x, y, z, w, d, c), None, n_patches, n_bins, offsets, sort_axis)("yawhip_proj_upload")
+
+
+def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
+                  rows: str = "thresholds must be [n_bins, n_edges]"):
+    """What the six counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+    ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
+    entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
+    and the ``CountStats``."""
+    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, width)
+    t = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError(rows)
+    n_rows, n_edges = t.shape
+    shape = (len(table), n_rows, max(n_edges - 1, 0)) if width == 2 else (len(table), max(n_edges - 1, 0))
+    out = [np.empty(shape, dtype=np.float64) for _ in range(n_planes)]  # the library writes every element
+    st = _Stats()
+    _check(
+        getattr(load_library(), symbol)(*handles, len(table), _ptr(table, _i32p), n_rows, n_edges, _ptr(t, _dp), *extra,
+                                        *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
+        symbol,
+    )
+    return (*out, _count_stats(st))
 
 
 def proj_count(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pmax: float):
@@ -893,38 +894,8 @@ def proj_count(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pmax: floa
     a segment of one handle with itself; ``r2`` f64[n_rows, E] squared radius edges; ``pmax >= 0`` the largest
     ``|c_a - c_b|`` of a pair that counts (``inf``: no cut). Returns ``(W, CountStats)``, W f64[n_cells, E-1]: the sums of
     ``w_a w_b``, a diagonal cell holding every unordered pair once."""
-    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 4)
-    r2 = np.ascontiguousarray(r2, dtype=np.float64)
-    if r2.ndim != 2:
-        raise ValueError("r2 must be [n_rows, n_edges]")
-    n_rows, n_edges = r2.shape
-    out = np.empty((len(cells), max(n_edges - 1, 0)), dtype=np.float64)  # the library writes every element
-    st = _Stats()
-    _check(
-        load_library().yawhip_proj_count(ctx._h, a._h, b._h, len(cells), _ptr(cells, _i32p), n_rows, n_edges, _ptr(r2, _dp),
-                                         float(pmax), _ptr(out, _dp), ctypes.byref(st)),
-        "yawhip_proj_count",
-    )
-    return out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-
-
-def _shear_counts(symbol: str, n_planes: int, handles, jobs, thresholds):
-    """What ``shear_count`` and ``shear_auto_count`` share: ``symbol(*handles, n_jobs, jobs, B, E, thresholds, n_planes output
-    planes, stats)`` -> the planes f64[n_jobs, B, E-1] and the ``CountStats``."""
-    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 2)
-    t = np.ascontiguousarray(thresholds, dtype=np.float64)
-    if t.ndim != 2:
-        raise ValueError("thresholds must be [n_bins, n_edges]")
-    n_bins, n_edges = t.shape
-    shape = (len(jobs), n_bins, max(n_edges - 1, 0))
-    out = [np.empty(shape, dtype=np.float64) for _ in range(n_planes)]  # the library writes every element
-    st = _Stats()
-    _check(
-        getattr(load_library(), symbol)(*handles, len(jobs), _ptr(jobs, _i32p), n_bins, n_edges, _ptr(t, _dp),
-                                        *(_ptr(a, _dp) for a in out), ctypes.byref(st)),
-        symbol,
-    )
-    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
+    return _shear_counts("yawhip_proj_count", 1, (ctx._h, a._h, b._h), cells, r2, float(pmax), width=4,
+                         rows="r2 must be [n_rows, n_edges]")
 
 
 def shear_count(ctx: Context, lenses: DeviceCatalog, sources: ShearSources, jobs, thresholds):
@@ -958,19 +929,8 @@ def shear_pair_count(ctx: Context, a: ShearSources, b: ShearSources, cells, thre
     -- segment ``(p, ka)`` of ``a`` against ``(q, kb)`` of ``b``, classified against thresholds row ``row``; thresholds
     f64[n_rows, E]. Returns ``(P, M, C, W, CountStats)``, f64[n_cells, E-1] each; a cell of one handle with ``ka == kb`` and
     ``p == q`` holds every unordered pair once."""
-    cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 5)
-    t = np.ascontiguousarray(thresholds, dtype=np.float64)
-    if t.ndim != 2:
-        raise ValueError("thresholds must be [n_rows, n_edges]")
-    n_rows, n_edges = t.shape
-    out = [np.empty((len(cells), max(n_edges - 1, 0)), dtype=np.float64) for _ in range(4)]  # the library writes every element
-    st = _Stats()
-    _check(
-        load_library().yawhip_shear_pair_count(ctx._h, a._h, b._h, len(cells), _ptr(cells, _i32p), n_rows, n_edges, _ptr(t, _dp),
-                                               *(_ptr(o, _dp) for o in out), ctypes.byref(st)),
-        "yawhip_shear_pair_count",
-    )
-    return (*out, CountStats(**{f: getattr(st, f) for f, _ in _Stats._fields_}))
+    return _shear_counts("yawhip_shear_pair_count", 4, (ctx._h, a._h, b._h), cells, thresholds, width=5,
+                         rows="thresholds must be [n_rows, n_edges]")
 
 
 def healpix_map(ctx: Context, phi, z, w, order: int, nested: bool, *, want_pixels: bool = False, want_map: bool = True,

@@ -253,14 +253,13 @@ class PatchLayout:
     the binning are dropped (:414), an unbinned catalogue has one segment per patch (:400-404)."""
 
     __slots__ = ("x", "y", "z", "w", "offsets", "num_patches", "num_bins", "sum_weights", "device", "z_extent", "kappa", "twin", "g1", "g2",
-                 "shear_device", "redshifts", "dsigma_device")
+                 "redshifts", "handles")
 
     def __init__(self, x, y, z, w, offsets, num_patches: int, num_bins: int, kappa=None, g1=None, g2=None, redshifts=None) -> None:
         self.x, self.y, self.z, self.w = x, y, z, w
         self.redshifts = redshifts  # the objects' redshifts in the layout's order (build_trees(with_redshifts=True)), or None
-        self.dsigma_device = {}  # (Context id, role) -> (handle of engine.count_dsigma_fine, the cosmology of its columns)
         self.g1, self.g2 = g1, g2  # shear columns in the layout's order (unbinned layouts, and build_trees(with_shear=True)), or None
-        self.shear_device = {}  # Context id -> ShearSources
+        self.handles = {}  # (Context id, role) -> (resident handle of a lensing or projected count, the cosmology of its columns or None)
         self.kappa = kappa  # scalar-field column in the layout's order, or None
         self.twin = None if kappa is None else ScalarTwin(self)  # the "k" side of a scalar count
         self.offsets = offsets
@@ -815,11 +814,8 @@ class Catalog(Mapping):
                 for dev in held.device.values():
                     dev.free()
                 held.device.clear()
-            for src in layout.shear_device.values():
-                src.free()
-            layout.shear_device.clear()
-            for src, *_ in layout.dsigma_device.values():
-                src.free()
-            layout.dsigma_device.clear()
+            for handle, _ in layout.handles.values():
+                handle.free()
+            layout.handles.clear()
         self._layouts.clear()
         self._active_layout = None

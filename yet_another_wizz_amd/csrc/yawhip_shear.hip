@@ -628,17 +628,17 @@ int yawhip_shear_free(yawhip_shear_sources *src) {
 
 namespace {
 
-// the upload of every entry point: n_bins segments per patch (1: the unbinned catalogue of yawhip_shear_upload), each sorted
-// along sort_axis and gathered. u: the extra column of yawhip_dsigma_upload_sources or NULL; lenses: a lens handle, whose
-// (g1, g2) = (f, c) are gathered without the weight; m: the extra column of a radial lens handle or NULL
-int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                    const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets, int32_t sort_axis,
-                    yawhip_shear_sources **out, const double *u = nullptr, bool lenses = false, const double *m = nullptr) {
+// The upload of every entry point: a handle of `kind` with n_bins segments per patch, each sorted along sort_axis and
+// gathered. a, b: the kind's two columns, gathered as the products w a, w b for the two kinds of shear catalogue and as they
+// came for the others; extra: the column u of DSIGMA_SOURCES or m of RADIAL_LENSES, else NULL
+int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
+                    const double *w, const double *a, const double *b, const double *extra, int32_t n_patches, int32_t n_bins,
+                    const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
     if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
     *out = nullptr;
     if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
     if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
-    if (n < 0 || n_patches <= 0 || n_bins <= 0 || !offsets || (n > 0 && (!x || !y || !z || !g1 || !g2)))
+    if (n < 0 || n_patches <= 0 || n_bins <= 0 || !offsets || (n > 0 && (!x || !y || !z || !a || !b)))
         return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL columns", fn);
     if (n >= (1ll << 32)) return fail(YAWHIP_ERR_INVALID, "at most 2^32 - 1 objects per catalogue");
     const int64_t n_seg = (int64_t)n_patches * n_bins;
@@ -649,28 +649,35 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
     yawhip_shear_sources *s = new (std::nothrow) yawhip_shear_sources;
     if (!s) return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     s->ctx = ctx;
+    s->kind = kind;
     s->n = n;
     s->n_patches = n_patches;
     s->nb = n_bins;
     s->axis = sort_axis;
-    s->lenses = lenses;
+    // the kinds counted in a radius keep the least entry per redshift bin of the column that bounds their reach (chord_reach)
+    const bool has_least = (kind & (RADIAL_LENSES | PROJECTED)) != 0;
+    const double *scale = kind == RADIAL_LENSES ? extra : a;
     try {
         s->h_off.assign(offsets, offsets + n_seg + 1);
+        if (has_least) s->least.assign((size_t)n_bins, INFINITY);  // (n == 0: the column may be NULL, and no segment reads it)
     } catch (const std::bad_alloc &) {
         delete s;
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
+    for (int64_t seg = 0; has_least && seg < n_seg; ++seg)
+        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i)
+            s->least[(size_t)(seg % n_bins)] = std::min(s->least[(size_t)(seg % n_bins)], scale[i]);
+    DevPtr<double> *const d_extra = kind == DSIGMA_SOURCES ? &s->u : kind == RADIAL_LENSES ? &s->m : nullptr;
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
-    constexpr int NC = 8;
-    DevPtr<double> raw[NC];  // x, y, z, g1, g2, w, u, m as they came (temporary)
-    const double *host[NC] = {x, y, z, g1, g2, w, u, m};
+    constexpr int NC = 7;
+    DevPtr<double> raw[NC];  // x, y, z, a, b, w, extra as they came (temporary)
+    const double *host[NC] = {x, y, z, a, b, w, extra};
     DevPtr<uint32_t> perm;
     hipError_t e = hipSuccess;
     for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
         if (e == hipSuccess) e = c->alloc(n1);
     if (e == hipSuccess && w) e = s->w.alloc(n1);
-    if (e == hipSuccess && u) e = s->u.alloc(n1);
-    if (e == hipSuccess && m) e = s->m.alloc(n1);
+    if (e == hipSuccess && d_extra) e = d_extra->alloc(n1);  // (an empty handle of the kind has the column too)
     if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
     for (int c = 0; c < NC; ++c)
         if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
@@ -683,15 +690,11 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
         e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_seg, perm);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
-                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2, !lenses);
+                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2, (kind & (SHEAR | DSIGMA_SOURCES)) != 0);
             e = hipGetLastError();
         }
-        if (e == hipSuccess && u) {
-            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], s->u);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && m) {
-            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[7], s->m);
+        if (e == hipSuccess && d_extra) {
+            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], *d_extra);
             e = hipGetLastError();
         }
     }
@@ -705,8 +708,27 @@ int upload_segments(const char *fn, yawhip_ctx *ctx, int64_t n, const double *x,
     return YAWHIP_OK;
 }
 
-// the argument checks the counts share (check_call of a count call), before any device work: the sizes and arrays of a call
-// over n_items jobs or cells (`arrays`: none of them is NULL) ...
+// a column of an upload beyond the coordinates: every entry a finite number, and of the rule's sign
+enum Rule { NOT_NEGATIVE, POSITIVE, ANY_SIGN };
+
+int check_column(const char *fn, const char *name, int64_t n, const double *v, Rule rule) {
+    static const char *const WANTED[] = {"a finite number >= 0", "a finite number > 0", "a finite number"};
+    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i]) || (rule == NOT_NEGATIVE && !(v[i] >= 0.0)) || (rule == POSITIVE && !(v[i] > 0.0)))
+            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not %s (index %lld)", fn, name, WANTED[rule], (long long)i);
+    return YAWHIP_OK;
+}
+
+// The one role check of the counts: the handle is of one of the kinds `accepted` (a sum of Kind), else the refusal `what`
+int require_kind(const char *fn, const yawhip_shear_sources *s, unsigned accepted, const char *what) {
+    return s->kind & accepted ? YAWHIP_OK : fail(YAWHIP_ERR_MISMATCH, "%s: %s", fn, what);
+}
+
+constexpr unsigned SHEAR_CATALOGUES = SHEAR | DSIGMA_SOURCES;  // what the three shear counts take (a column u is ignored)
+constexpr const char *NOT_A_SHEAR_CATALOGUE = "a lens handle of yawhip_dsigma_upload_lenses is not a shear catalogue";
+
+// the sizes and arrays of a call over n_items jobs or cells (`arrays`: none of them is NULL)
 int check_sizes(const char *fn, int32_t n_items, int32_t n_rows, int32_t n_edges, const double *t, bool arrays) {
     if (n_items < 0 || n_rows <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_items > 0 && !arrays))
         return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)", fn, n_items, n_rows,
@@ -714,7 +736,7 @@ int check_sizes(const char *fn, int32_t n_items, int32_t n_rows, int32_t n_edges
     return YAWHIP_OK;
 }
 
-// ... the thresholds t[n_rows][n_edges] ...
+// the thresholds t[n_rows][n_edges]
 int check_thresholds(int32_t n_rows, int32_t n_edges, const double *t) {
     for (int k = 0; k < n_rows; ++k)
         for (int e = 0; e < n_edges; ++e) {
@@ -725,8 +747,8 @@ int check_thresholds(int32_t n_rows, int32_t n_edges, const double *t) {
     return YAWHIP_OK;
 }
 
-// ... and the job list of the two counts over (job, bin) cells
-int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_patches, int32_t n_bins, int32_t n_edges, const double *t) {
+// ... and the job list of the counts over (job, bin) cells
+int check_job_list(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_patches, int32_t n_bins, int32_t n_edges, const double *t) {
     if (const int rc = check_thresholds(n_bins, n_edges, t)) return rc;
     for (int j = 0; j < n_jobs; ++j)
         if (jobs[2 * j] < 0 || jobs[2 * j] >= n_patches || jobs[2 * j + 1] < 0 || jobs[2 * j + 1] >= n_patches)
@@ -735,20 +757,98 @@ int check_count(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t n_p
     return YAWHIP_OK;
 }
 
+// The checks of a count come in one order, before any device work: handles, sizes and context (check_handles), the roles
+// (require_kind), then what depends on the kinds: how the handles fit, the thresholds, the job or cell list.
+template <class A>
+int check_handles(const char *fn, const yawhip_ctx *ctx, const A *a, const yawhip_shear_sources *b, int32_t n_items, int32_t n_rows,
+                  int32_t n_edges, const double *t, bool arrays) {
+    if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "%s: NULL handle", fn);
+    if (const int rc = check_sizes(fn, n_items, n_rows, n_edges, t, arrays)) return rc;
+    if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
+    return YAWHIP_OK;
+}
 
-// What the counts share once their arguments are checked. One table goes to the handle's d_in (thresholds [rows][E], window
-// half widths [rows], the policy's table of n_table 32-bit integers: jobs [n_jobs][2] or cells [n_cells][4]);
-// launch(table, t, rwin, n_cells, out, evaluated) puts the kernel on the stream between the context's two events, writing the
-// result block in d_out (n_planes planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[],
-// the counters and the event time to the statistics. n_bins: the rows of t.
-template <class Launch>
-int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, size_t n_table, const int32_t *table, size_t n_cells,
-              int32_t n_bins, int32_t n_edges, const double *t, int n_planes, double *const *fine, int64_t candidates,
-              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Launch launch, const double *reach = nullptr) {
+// A count over jobs (lens patch, source patch) and the n_bins redshift bins of the lenses -- a catalogue or a lens handle --
+// with unbinned sources. candidates: every source of patch q against the lenses of patch p (unbinned lenses: in every bin)
+template <class Lenses>
+int check_jobs(const char *fn, const Lenses *lenses, const yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs,
+               int32_t n_bins, int32_t n_edges, const double *t, int64_t *candidates) {
+    if (sources->nb != 1)
+        return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are binned in redshift (%d bins): upload them unbinned", fn, sources->nb);
+    if (lenses->n_patches != sources->n_patches)
+        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
+    if (lenses->nb != 1 && lenses->nb != n_bins)
+        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
+    if (const int rc = check_job_list(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
+    *candidates = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
+        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
+        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
+                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
+        *candidates += n_src * n_lens;
+    }
+    return YAWHIP_OK;
+}
+
+// the candidate pairs of segment sa of a against segment sb of b: a segment against itself has every unordered pair once
+int64_t segment_pairs(const yawhip_shear_sources *a, size_t sa, const yawhip_shear_sources *b, size_t sb) {
+    const int64_t n_a = a->h_off[sa + 1] - a->h_off[sa], n_b = b->h_off[sb + 1] - b->h_off[sb];
+    return a == b && sa == sb ? n_a * (n_a - 1) / 2 : n_a * n_b;
+}
+
+// a count over a cell list of (patch, bin) segments of two handles: the segments are 32-bit in the kernel's table
+int check_cells(const char *fn, const yawhip_shear_sources *a, const yawhip_shear_sources *b, int32_t n_rows, int32_t n_edges,
+                const double *t) {
+    if ((int64_t)a->n_patches * a->nb > INT32_MAX || (int64_t)b->n_patches * b->nb > INT32_MAX)
+        return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
+    return check_thresholds(n_rows, n_edges, t);
+}
+
+// The window of a count in a radius. reach[k] comes in as the least scale of row k -- what the squared chord of a pair is
+// multiplied by before it meets the row's squared radii; +inf: the row has no pairs -- and leaves as the largest squared chord
+// of a pair in range: fl(scale s2) <= top needs s2 <= top / scale (1 + 2 eps). Beyond 0.01 (5.73 degrees) the series of the
+// squared angle loses its last bits: refused. who, row: the words of the two refusals
+int chord_reach(const char *fn, const char *who, const char *row, int32_t n_rows, int32_t n_edges, const double *r2,
+                std::vector<double> &reach) {
+    for (int k = 0; k < n_rows; ++k) {
+        const double top = r2[(size_t)k * n_edges + n_edges - 1];
+        if (std::isinf(top)) return fail(YAWHIP_ERR_INVALID, "squared radii of %s %d are not finite", row, k);
+        reach[(size_t)k] = top / reach[(size_t)k] * (1.0 + 1e-12);
+        if (!(reach[(size_t)k] <= 0.01))
+            return fail(YAWHIP_ERR_INVALID, "%s: %s is too close for the largest radius (%s %d: the reach is a squared chord of %g, at most 0.01)",
+                        fn, who, row, k, reach[(size_t)k]);
+    }
+    return YAWHIP_OK;
+}
+
+ShearView view_of(const yawhip_shear_sources *s) {
+    return ShearView{s->x, s->y, s->z, s->w, s->wg1, s->wg2, s->off, key_of(s->x, s->y, s->z, s->axis), s->axis};
+}
+
+// What the counts share once their arguments are checked. One table goes to d_in of the handle `buffers` (thresholds
+// [rows][E], window half widths [rows], the policy's table of n_table 32-bit integers: jobs [n_jobs][2] or cells [n_cells][4]);
+// pass(go, slots) names the kernel and its arguments in the kernel's order, go(kernel, arguments...), and run_count puts it on
+// the stream between the context's two events: one workgroup per cell, the policy's LDS. The kernel writes the result block
+// in d_out (P::PLANES planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[], the
+// counters and the event time to the statistics. n_rows: the rows of t; reach[k]: the largest squared chord of a pair in
+// range of row k where the row's last edge is not that (chord_reach), or NULL.
+struct Slots {  // what run_count has on the device for the kernel
+    const int32_t *table;
+    const double *t, *rwin;
+    int64_t n_cells;
+    double *out;
+    unsigned long long *evaluated;
+};
+
+template <class P, class Pass>
+int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, size_t n_table, const int32_t *table, size_t n_cells,
+              int32_t n_rows, int32_t n_edges, const double *t, const double *reach, double *const *fine, int64_t candidates,
+              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Pass pass) {
     if (stats) *stats = yawhip_stats{};
     if (n_cells == 0) return YAWHIP_OK;
-    const size_t n_t = (size_t)n_bins * n_edges, in_bytes = (n_t + (size_t)n_bins) * sizeof(double) + n_table * sizeof(int32_t);
-    const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)n_planes * plane;
+    const size_t n_t = (size_t)n_rows * n_edges, in_bytes = (n_t + (size_t)n_rows) * sizeof(double) + n_table * sizeof(int32_t);
+    const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)P::PLANES * plane;
     std::vector<unsigned char> h_in;
     std::vector<unsigned long long> h_eval;
     try {
@@ -761,25 +861,28 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, si
     memcpy(h_t, t, n_t * sizeof(double));
     // a pair passes s2 <= t_max only if |du| <= sqrt(t_max) (1 + 2 eps) along any axis u (s2 >= fl(du^2), du rounded once);
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
-    // (reach[k]: the largest squared chord of a pair in range of row k where the row's last edge is not that -- the radial count)
-    for (int k = 0; k < n_bins; ++k)
+    for (int k = 0; k < n_rows; ++k)
         h_rwin[k] = std::sqrt(reach ? reach[k] : t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-    memcpy(h_rwin + n_bins, table, n_table * sizeof(int32_t));
+    memcpy(h_rwin + n_rows, table, n_table * sizeof(int32_t));
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
-    HIP_TRY(sources->d_in.reserve(in_bytes, in_bytes / 4 + 64));
-    HIP_TRY(sources->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
+    HIP_TRY(buffers->d_in.reserve(in_bytes, in_bytes / 4 + 64));
+    HIP_TRY(buffers->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
     // (pageable memory: the copy has left h_in when the call returns)
-    HIP_TRY(hipMemcpyAsync(sources->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const double *d_t = reinterpret_cast<const double *>((unsigned char *)sources->d_in.ptr), *d_rwin = d_t + n_t;
-    double *d_out = sources->d_out.ptr;
+    HIP_TRY(hipMemcpyAsync(buffers->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const double *d_t = reinterpret_cast<const double *>((unsigned char *)buffers->d_in.ptr), *d_rwin = d_t + n_t;
+    const int32_t *d_table = reinterpret_cast<const int32_t *>(d_rwin + n_rows);
+    double *d_out = buffers->d_out.ptr;
     unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    launch(reinterpret_cast<const int32_t *>(d_rwin + n_bins), d_t, d_rwin, (int64_t)n_cells, d_out, d_eval);
+    pass([&](auto kernel, auto... arguments) {
+             hipLaunchKernelGGL(kernel, dim3((unsigned)n_cells), dim3(WG), lds_bytes<P>(n_edges), ctx->stream, arguments...);
+         },
+         Slots{d_table, d_t, d_rwin, (int64_t)n_cells, d_out, d_eval});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    for (int c = 0; c < n_planes; ++c)
+    for (int c = 0; c < P::PLANES; ++c)
         HIP_TRY(hipMemcpyAsync(fine[c], d_out + (size_t)c * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (stats) HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -796,88 +899,14 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *sources, si
     return YAWHIP_OK;
 }
 
-ShearView view_of(const yawhip_shear_sources *s) {
-    return ShearView{s->x, s->y, s->z, s->w, s->wg1, s->wg2, s->off, key_of(s->x, s->y, s->z, s->axis), s->axis};
-}
-
-// the three shear counts take shear handles only
-int refuse_lenses(const char *fn, const yawhip_shear_sources *s) {
-    if (s->lenses) return fail(YAWHIP_ERR_MISMATCH, "%s: a lens handle of yawhip_dsigma_upload_lenses is not a shear catalogue", fn);
-    return YAWHIP_OK;
-}
-
-// the extra columns of yawhip_dsigma_count: finite and >= 0
-int check_column(const char *fn, const char *name, int64_t n, const double *v) {
-    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
-    for (int64_t i = 0; i < n; ++i)
-        if (!(v[i] >= 0.0) || std::isinf(v[i]))
-            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number >= 0 (index %lld)", fn, name, (long long)i);
-    return YAWHIP_OK;
-}
-
-// the column m of yawhip_dsigma_upload_lenses_radial: finite and > 0
-int check_positive(const char *fn, const char *name, int64_t n, const double *v) {
-    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
-    for (int64_t i = 0; i < n; ++i)
-        if (!(v[i] > 0.0) || std::isinf(v[i]))
-            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number > 0 (index %lld)", fn, name, (long long)i);
-    return YAWHIP_OK;
-}
-
-// the column c of yawhip_proj_upload: finite
-int check_finite(const char *fn, const char *name, int64_t n, const double *v) {
-    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i]))
-            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not a finite number (index %lld)", fn, name, (long long)i);
-    return YAWHIP_OK;
-}
-
-// The least entry of column v per redshift bin over all patches of the handle just uploaded (its offsets are checked by
-// now), kept in its member `least`; a bin without objects: +inf. Out of memory frees the handle.
-int least_per_bin(const char *fn, yawhip_shear_sources **out, std::vector<double> yawhip_shear_sources::*least, const double *v,
-                  int32_t n_patches, int32_t n_bins, const int64_t *offsets) {
-    yawhip_shear_sources *s = *out;
-    try {
-        (s->*least).assign((size_t)n_bins, INFINITY);
-    } catch (const std::bad_alloc &) {
-        yawhip_shear_free(s);
-        *out = nullptr;
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
-    for (int64_t seg = 0; seg < (int64_t)n_patches * n_bins; ++seg) {
-        double &least_of_bin = (s->*least)[(size_t)(seg % n_bins)];
-        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i) least_of_bin = std::min(least_of_bin, v[i]);
-    }
-    return YAWHIP_OK;
-}
-
-// the argument checks of the two excess-surface-density counts (t: thresholds or squared radii), and their candidate pairs
+// the checks of the two excess-surface-density counts (t: thresholds or squared radii), and their candidate pairs
 int check_dsigma(const char *fn, yawhip_ctx *ctx, const yawhip_shear_sources *lenses, const yawhip_shear_sources *sources, int32_t n_jobs,
                  const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, bool planes, int64_t *candidates) {
-    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "%s: NULL handle", fn);
-    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && planes)) return rc;
-    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (!lenses->lenses || lenses->projected)
-        return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses", fn);
-    if (sources->lenses || !sources->u)
-        return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are not a handle of yawhip_dsigma_upload_sources", fn);
-    if (sources->nb != 1)
-        return fail(YAWHIP_ERR_MISMATCH, "%s: the sources are binned in redshift (%d bins): upload them unbinned", fn, sources->nb);
-    if (lenses->n_patches != sources->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
-    if (lenses->nb != 1 && lenses->nb != n_bins)
-        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
-    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
-    *candidates = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
-        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
-        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
-                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
-        *candidates += n_src * n_lens;
-    }
-    return YAWHIP_OK;
+    if (const int rc = check_handles(fn, ctx, lenses, sources, n_jobs, n_bins, n_edges, t, jobs && planes)) return rc;
+    if (const int rc = require_kind(fn, lenses, DSIGMA_LENSES | RADIAL_LENSES, "the lenses are not a handle of yawhip_dsigma_upload_lenses"))
+        return rc;  // (a column m is ignored)
+    if (const int rc = require_kind(fn, sources, DSIGMA_SOURCES, "the sources are not a handle of yawhip_dsigma_upload_sources")) return rc;
+    return check_jobs(fn, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, candidates);
 }
 
 }  // namespace
@@ -887,13 +916,53 @@ extern "C" {
 int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                         const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
                         yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload", ctx, n, x, y, z, w, g1, g2, n_patches, 1, offsets, sort_axis, out);
+    return upload_segments("yawhip_shear_upload", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, n_patches, 1, offsets, sort_axis, out);
 }
 
 int yawhip_shear_upload_binned(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                                const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
                                int32_t sort_axis, yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload_binned", ctx, n, x, y, z, w, g1, g2, n_patches, n_bins, offsets, sort_axis, out);
+    return upload_segments("yawhip_shear_upload_binned", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+}
+
+int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                 const double *g1, const double *g2, const double *u, int32_t n_patches, const int64_t *offsets,
+                                 int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_sources";
+    if (out) *out = nullptr;
+    if (const int rc = check_column(fn, "u", n, u, NOT_NEGATIVE)) return rc;
+    return upload_segments(fn, DSIGMA_SOURCES, ctx, n, x, y, z, w, g1, g2, u, n_patches, 1, offsets, sort_axis, out);
+}
+
+int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                const double *f, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                                int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_lenses";
+    if (out) *out = nullptr;
+    if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
+    if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
+    return upload_segments(fn, DSIGMA_LENSES, ctx, n, x, y, z, w, f, c, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+}
+
+int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                                       const double *f, const double *c, const double *m, int32_t n_patches, int32_t n_bins,
+                                       const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_dsigma_upload_lenses_radial";
+    if (out) *out = nullptr;
+    if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
+    if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
+    if (const int rc = check_column(fn, "m", n, m, POSITIVE)) return rc;
+    return upload_segments(fn, RADIAL_LENSES, ctx, n, x, y, z, w, f, c, m, n_patches, n_bins, offsets, sort_axis, out);
+}
+
+int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                       const double *d, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
+                       int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_proj_upload";
+    if (out) *out = nullptr;
+    if (const int rc = check_column(fn, "d", n, d, POSITIVE)) return rc;
+    if (const int rc = check_column(fn, "c", n, c, ANY_SIGN)) return rc;
+    return upload_segments(fn, PROJECTED, ctx, n, x, y, z, w, d, c, nullptr, n_patches, n_bins, offsets, sort_axis, out);
 }
 
 int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
@@ -901,33 +970,16 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
                        double *fine_w, yawhip_stats *stats) {
     const char *fn = "yawhip_shear_count";
     const auto wall0 = std::chrono::steady_clock::now();
-    if (!ctx || !lenses || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_count: NULL handle");
-    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
-    if (lenses->ctx != ctx || sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (const int rc = refuse_lenses(fn, sources)) return rc;
-    if (sources->nb != 1)
-        return fail(YAWHIP_ERR_MISMATCH, "yawhip_shear_count: the sources are binned in redshift (%d bins): upload them unbinned", sources->nb);
-    if (lenses->n_patches != sources->n_patches)
-        return fail(YAWHIP_ERR_MISMATCH, "patch counts differ (%d vs %d)", lenses->n_patches, sources->n_patches);
-    if (lenses->nb != 1 && lenses->nb != n_bins)
-        return fail(YAWHIP_ERR_MISMATCH, "lens catalogue bin count (%d) does not fit n_bins=%d", lenses->nb, n_bins);
-    if (const int rc = check_count(fn, n_jobs, jobs, lenses->n_patches, n_bins, n_edges, t)) return rc;
-
     int64_t candidates = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int64_t p = jobs[2 * j], q = jobs[2 * j + 1];
-        const int64_t n_src = sources->h_off[(size_t)q + 1] - sources->h_off[(size_t)q];
-        const int64_t n_lens = lenses->nb == 1 ? n_bins * (lenses->h_off[(size_t)p + 1] - lenses->h_off[(size_t)p])
-                                               : lenses->h_off[(size_t)(p + 1) * n_bins] - lenses->h_off[(size_t)p * n_bins];
-        candidates += n_src * n_lens;
-    }
+    if (const int rc = check_handles(fn, ctx, lenses, sources, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
+    if (const int rc = require_kind(fn, sources, SHEAR_CATALOGUES, NOT_A_SHEAR_CATALOGUE)) return rc;
+    if (const int rc = check_jobs(fn, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, &candidates)) return rc;
     double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, Tangential::PLANES, fine, candidates, wall0, stats,
-                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_shear, dim3((unsigned)n_cells), dim3(WG), lds_bytes<Tangential>(n_edges), ctx->stream,
-                                            view_of(lenses), view_of(sources), d_jobs, n_bins, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
-                     });
+    return run_count<Tangential>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
+                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
+                                     go(k_count_shear, view_of(lenses), view_of(sources), d.table, n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out,
+                                        d.evaluated);
+                                 });
 }
 
 int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int32_t n_jobs, const int32_t *jobs, int32_t n_bins,
@@ -935,31 +987,24 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
                             yawhip_stats *stats) {
     const char *fn = "yawhip_shear_auto_count";
     const auto wall0 = std::chrono::steady_clock::now();
-    if (!ctx || !sources) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_auto_count: NULL handle");
-    if (const int rc = check_sizes(fn, n_jobs, n_bins, n_edges, t, jobs && fine_p && fine_m && fine_c && fine_w)) return rc;
-    if (sources->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (const int rc = refuse_lenses(fn, sources)) return rc;
+    if (const int rc = check_handles(fn, ctx, sources, sources, n_jobs, n_bins, n_edges, t, jobs && fine_p && fine_m && fine_c && fine_w))
+        return rc;
+    if (const int rc = require_kind(fn, sources, SHEAR_CATALOGUES, NOT_A_SHEAR_CATALOGUE)) return rc;
     if (sources->nb != n_bins)
         return fail(YAWHIP_ERR_MISMATCH, "source catalogue bin count (%d) does not fit n_bins=%d", sources->nb, n_bins);
-    if (const int rc = check_count(fn, n_jobs, jobs, sources->n_patches, n_bins, n_edges, t)) return rc;
-    for (int j = 0; j < n_jobs; ++j)
+    if (const int rc = check_job_list(fn, n_jobs, jobs, sources->n_patches, n_bins, n_edges, t)) return rc;
+    int64_t candidates = 0;
+    for (int j = 0; j < n_jobs; ++j) {
         if (jobs[2 * j] > jobs[2 * j + 1])
             return fail(YAWHIP_ERR_INVALID, "job %d = (%d, %d): an autocorrelation job has p <= q", j, jobs[2 * j], jobs[2 * j + 1]);
-
-    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
-    for (int j = 0; j < n_jobs; ++j)
-        for (int k = 0; k < n_bins; ++k) {
-            const size_t sp = (size_t)jobs[2 * j] * n_bins + k, sq = (size_t)jobs[2 * j + 1] * n_bins + k;
-            const int64_t n_p = sources->h_off[sp + 1] - sources->h_off[sp], n_q = sources->h_off[sq + 1] - sources->h_off[sq];
-            candidates += sp == sq ? n_p * (n_p - 1) / 2 : n_p * n_q;
-        }
+        for (int k = 0; k < n_bins; ++k)
+            candidates += segment_pairs(sources, (size_t)jobs[2 * j] * n_bins + k, sources, (size_t)jobs[2 * j + 1] * n_bins + k);
+    }
     double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
-    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, ShearShear::PLANES, fine, candidates, wall0, stats,
-                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_shear_auto, dim3((unsigned)n_cells), dim3(WG), lds_bytes<ShearShear>(n_edges), ctx->stream,
-                                            view_of(sources), n_bins, d_jobs, n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
-                     });
+    return run_count<ShearShear>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
+                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
+                                     go(k_count_shear_auto, view_of(sources), n_bins, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+                                 });
 }
 
 int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
@@ -967,14 +1012,10 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
                             double *fine_w, yawhip_stats *stats) {
     const char *fn = "yawhip_shear_pair_count";
     const auto wall0 = std::chrono::steady_clock::now();
-    if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "yawhip_shear_pair_count: NULL handle");
-    if (const int rc = check_sizes(fn, n_cells, n_rows, n_edges, t, cells && fine_p && fine_m && fine_c && fine_w)) return rc;
-    if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (const int rc = refuse_lenses(fn, a)) return rc;
-    if (const int rc = refuse_lenses(fn, b)) return rc;
-    if ((int64_t)a->n_patches * a->nb > INT32_MAX || (int64_t)b->n_patches * b->nb > INT32_MAX)
-        return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
-    if (const int rc = check_thresholds(n_rows, n_edges, t)) return rc;
+    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, t, cells && fine_p && fine_m && fine_c && fine_w)) return rc;
+    if (const int rc = require_kind(fn, a, SHEAR_CATALOGUES, NOT_A_SHEAR_CATALOGUE)) return rc;
+    if (const int rc = require_kind(fn, b, SHEAR_CATALOGUES, NOT_A_SHEAR_CATALOGUE)) return rc;
+    if (const int rc = check_cells(fn, a, b, n_rows, n_edges, t)) return rc;
 
     // the kernel's table: (streamed segment of a, lane segment of b, thresholds row, diagonal) per cell
     std::vector<int32_t> table;
@@ -983,7 +1024,7 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
     } catch (const std::bad_alloc &) {
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
-    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
+    int64_t candidates = 0;
     for (int c = 0; c < n_cells; ++c) {
         const int32_t *cell = cells + 5 * (size_t)c;
         const int32_t p = cell[0], q = cell[1], ka = cell[2], kb = cell[3], row = cell[4];
@@ -995,44 +1036,15 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
         if (a == b && ka == kb && p > q)
             return fail(YAWHIP_ERR_INVALID, "cell %d = (%d, %d) inside bin %d of one handle: such a cell has p <= q", c, p, q, ka);
         const size_t sa = (size_t)p * a->nb + ka, sb = (size_t)q * b->nb + kb;
-        const bool diag = a == b && sa == sb;
-        const int64_t n_a = a->h_off[sa + 1] - a->h_off[sa], n_b = b->h_off[sb + 1] - b->h_off[sb];
-        candidates += diag ? n_a * (n_a - 1) / 2 : n_a * n_b;
+        candidates += segment_pairs(a, sa, b, sb);
         int32_t *entry = &table[4 * (size_t)c];
-        entry[0] = (int32_t)sa, entry[1] = (int32_t)sb, entry[2] = row, entry[3] = diag;
+        entry[0] = (int32_t)sa, entry[1] = (int32_t)sb, entry[2] = row, entry[3] = a == b && sa == sb;
     }
     double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
-    return run_count(fn, ctx, a, table.size(), table.data(), (size_t)n_cells, n_rows, n_edges, t, ShearPair::PLANES, fine, candidates,
-                     wall0, stats,
-                     [&](const int32_t *d_cells, const double *d_t, const double *d_rwin, int64_t cells_n, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_shear_pair, dim3((unsigned)cells_n), dim3(WG), lds_bytes<ShearPair>(n_edges), ctx->stream,
-                                            view_of(a), view_of(b), d_cells, n_edges, d_t, d_rwin, cells_n, d_out, d_eval);
-                     });
-}
-
-int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                const double *f, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
-                                int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_lenses";
-    if (out) *out = nullptr;
-    if (n > 0) {
-        if (const int rc = check_column(fn, "f", n, f)) return rc;
-        if (const int rc = check_column(fn, "c", n, c)) return rc;
-    }
-    return upload_segments(fn, ctx, n, x, y, z, w, f, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true);
-}
-
-int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                 const double *g1, const double *g2, const double *u, int32_t n_patches, const int64_t *offsets,
-                                 int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_sources";
-    if (out) *out = nullptr;
-    static const double none = 0.0;  // (n == 0: the handle still carries a column u)
-    if (n > 0) {
-        if (const int rc = check_column(fn, "u", n, u)) return rc;
-    }
-    return upload_segments(fn, ctx, n, x, y, z, w, g1, g2, n_patches, 1, offsets, sort_axis, out, n > 0 ? u : &none, false);
+    return run_count<ShearPair>(fn, ctx, a, table.size(), table.data(), (size_t)n_cells, n_rows, n_edges, t, nullptr, fine, candidates, wall0,
+                                stats, [&](auto go, const Slots &d) {
+                                    go(k_count_shear_pair, view_of(a), view_of(b), d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+                                });
 }
 
 int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
@@ -1044,30 +1056,11 @@ int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_sh
     if (const int rc = check_dsigma(fn, ctx, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, fine_t && fine_x && fine_w, &candidates))
         return rc;
     double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, DeltaSigma::PLANES, fine, candidates, wall0, stats,
-                     [&](const int32_t *d_jobs, const double *d_t, const double *d_rwin, int64_t n_cells, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_dsigma, dim3((unsigned)n_cells), dim3(WG), lds_bytes<DeltaSigma>(n_edges), ctx->stream,
-                                            LensView{view_of(lenses), lenses->nb}, SourceView{view_of(sources), sources->u}, d_jobs, n_bins,
-                                            n_edges, d_t, d_rwin, n_cells, d_out, d_eval);
-                     });
-}
-
-int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                       const double *f, const double *c, const double *m, int32_t n_patches, int32_t n_bins,
-                                       const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_lenses_radial";
-    if (out) *out = nullptr;
-    static const double one = 1.0;  // (n == 0: the handle still carries a column m)
-    if (n > 0) {
-        if (const int rc = check_column(fn, "f", n, f)) return rc;
-        if (const int rc = check_column(fn, "c", n, c)) return rc;
-        if (const int rc = check_positive(fn, "m", n, m)) return rc;
-    }
-    if (const int rc = upload_segments(fn, ctx, n, x, y, z, w, f, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true, n > 0 ? m : &one))
-        return rc;
-    // the nearest lens of every redshift bin over all patches; a bin without lenses: +inf
-    return least_per_bin(fn, out, &yawhip_shear_sources::min_m, m, n_patches, n_bins, offsets);
+    return run_count<DeltaSigma>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
+                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
+                                     go(k_count_dsigma, LensView{view_of(lenses), lenses->nb}, SourceView{view_of(sources), sources->u}, d.table,
+                                        n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+                                 });
 }
 
 int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
@@ -1078,109 +1071,65 @@ int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, ya
     int64_t candidates = 0;
     if (const int rc = check_dsigma(fn, ctx, lenses, sources, n_jobs, jobs, n_bins, n_edges, r2, fine_t && fine_x && fine_w, &candidates))
         return rc;
-    if (!lenses->m) return fail(YAWHIP_ERR_MISMATCH, "%s: the lenses are not a handle of yawhip_dsigma_upload_lenses_radial", fn);
-    // the largest squared chord of a pair in range, per row: fl(m s2) <= r2max needs s2 <= r2max / m (1 + 2 eps). Beyond 0.01
-    // (5.73 degrees) the series of the squared angle loses its last bits: refused
-    std::vector<double> smax;
+    if (const int rc = require_kind(fn, lenses, RADIAL_LENSES, "the lenses are not a handle of yawhip_dsigma_upload_lenses_radial")) return rc;
+    std::vector<double> reach;  // the scale of a row is m: the nearest lens of its redshift bin
     try {
-        smax.resize((size_t)n_bins);
+        reach.resize((size_t)n_bins);
     } catch (const std::bad_alloc &) {
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
-    for (int k = 0; k < n_bins; ++k) {
-        const double top = r2[(size_t)k * n_edges + n_edges - 1];
-        if (std::isinf(top)) return fail(YAWHIP_ERR_INVALID, "squared radii of bin %d are not finite", k);
-        smax[(size_t)k] = top / lenses->min_m[lenses->nb == 1 ? 0 : (size_t)k] * (1.0 + 1e-12);
-        if (smax[(size_t)k] > 0.01)
-            return fail(YAWHIP_ERR_INVALID, "%s: a lens is too close for the largest radius (bin %d: the reach is a squared chord of %g, at most 0.01)",
-                        fn, k, smax[(size_t)k]);
-    }
+    for (int k = 0; k < n_bins; ++k) reach[(size_t)k] = lenses->least[lenses->nb == 1 ? 0 : (size_t)k];
+    if (const int rc = chord_reach(fn, "a lens", "bin", n_bins, n_edges, r2, reach)) return rc;
     double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, r2, DeltaSigmaRadial::PLANES, fine, candidates,
-                     wall0, stats,
-                     [&](const int32_t *d_jobs, const double *d_r2, const double *d_rwin, int64_t n_cells, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_dsigma_radial, dim3((unsigned)n_cells), dim3(WG), lds_bytes<DeltaSigmaRadial>(n_edges),
-                                            ctx->stream, RadialView{LensView{view_of(lenses), lenses->nb}, lenses->m},
-                                            SourceView{view_of(sources), sources->u}, d_jobs, n_bins, n_edges, d_r2, d_rwin, n_cells, d_out, d_eval);
-                     },
-                     smax.data());
-}
-
-int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                       const double *d, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
-                       int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_proj_upload";
-    if (out) *out = nullptr;
-    if (n > 0) {
-        if (const int rc = check_positive(fn, "d", n, d)) return rc;
-        if (const int rc = check_finite(fn, "c", n, c)) return rc;
-    }
-    // a lens handle: the two columns are kept as they came, in the place of wg1, wg2
-    if (const int rc = upload_segments(fn, ctx, n, x, y, z, w, d, c, n_patches, n_bins, offsets, sort_axis, out, nullptr, true)) return rc;
-    (*out)->projected = true;
-    // the nearest object of every redshift bin over all patches; a bin without objects: +inf
-    return least_per_bin(fn, out, &yawhip_shear_sources::min_d, d, n_patches, n_bins, offsets);
+    return run_count<DeltaSigmaRadial>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, r2, reach.data(),
+                                       fine, candidates, wall0, stats, [&](auto go, const Slots &d) {
+                                           go(k_count_dsigma_radial, RadialView{LensView{view_of(lenses), lenses->nb}, lenses->m},
+                                              SourceView{view_of(sources), sources->u}, d.table, n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out,
+                                              d.evaluated);
+                                       });
 }
 
 int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                       int32_t n_rows, int32_t n_edges, const double *r2, double pmax, double *fine_w, yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count";
     const auto wall0 = std::chrono::steady_clock::now();
-    if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "yawhip_proj_count: NULL handle");
-    if (const int rc = check_sizes(fn, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
-    if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
-    if (!a->projected || !b->projected) return fail(YAWHIP_ERR_MISMATCH, "%s: a handle is not one of yawhip_proj_upload", fn);
+    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
+    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
+    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
     if (!(pmax >= 0.0)) return fail(YAWHIP_ERR_INVALID, "%s: pmax must be a number >= 0 (+inf: no line-of-sight cut)", fn);
-    const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
-    if (segs_a > INT32_MAX || segs_b > INT32_MAX) return fail(YAWHIP_ERR_INVALID, "%s: more than 2^31 - 1 (patch, bin) segments", fn);
-    if (const int rc = check_thresholds(n_rows, n_edges, r2)) return rc;
+    if (const int rc = check_cells(fn, a, b, n_rows, n_edges, r2)) return rc;
 
-    // The largest squared chord of a pair in range, per row: fl(DD s2) <= r2max needs s2 <= r2max / DD (1 + 2 eps), and
-    // D = fl(0.5 (d_a + d_b)) is no less than the smaller of the two (rounding is monotone), which is no less than the least d
-    // of the bins that the row's cells pair. A row without cells, or with an empty bin on either side, has no pairs: 0.
-    std::vector<double> least, smax;
+    // The scale of a pair is DD, D = fl(0.5 (d_a + d_b)) no less than the smaller of the two (rounding is monotone), which is
+    // no less than the least d of the bins that the row's cells pair. A row without cells, or with an empty bin on either
+    // side, has no pairs.
+    const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
+    std::vector<double> reach;
     try {
-        least.assign((size_t)n_rows, 0.0);
-        smax.assign((size_t)n_rows, 0.0);
+        reach.assign((size_t)n_rows, INFINITY);
     } catch (const std::bad_alloc &) {
         return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
     }
-    int64_t candidates = 0;  // unordered pairs of a diagonal cell, all pairs of the others
+    int64_t candidates = 0;
     for (int c = 0; c < n_cells; ++c) {
         const int32_t *cell = cells + 4 * (size_t)c;
         const int32_t sa = cell[0], sb = cell[1], row = cell[2];
         if (sa < 0 || sa >= segs_a || sb < 0 || sb >= segs_b)
             return fail(YAWHIP_ERR_INVALID, "cell %d has a segment outside [0,%lld) x [0,%lld)", c, (long long)segs_a, (long long)segs_b);
         if (row < 0 || row >= n_rows) return fail(YAWHIP_ERR_INVALID, "cell %d has a row outside [0,%d)", c, n_rows);
-        const bool diag = a == b && sa == sb;
-        if ((cell[3] != 0) != diag)
+        if ((cell[3] != 0) != (a == b && sa == sb))
             return fail(YAWHIP_ERR_INVALID, "cell %d: a cell is diagonal iff it pairs a segment of one handle with itself", c);
-        const int64_t n_a = a->h_off[(size_t)sa + 1] - a->h_off[(size_t)sa], n_b = b->h_off[(size_t)sb + 1] - b->h_off[(size_t)sb];
-        candidates += diag ? n_a * (n_a - 1) / 2 : n_a * n_b;
-        const double nearest = std::min(a->min_d[(size_t)(sa % a->nb)], b->min_d[(size_t)(sb % b->nb)]);
-        if (std::isinf(a->min_d[(size_t)(sa % a->nb)]) || std::isinf(b->min_d[(size_t)(sb % b->nb)])) continue;  // an empty bin
-        least[(size_t)row] = least[(size_t)row] == 0.0 ? nearest : std::min(least[(size_t)row], nearest);
+        candidates += segment_pairs(a, (size_t)sa, b, (size_t)sb);
+        const double d_a = a->least[(size_t)(sa % a->nb)], d_b = b->least[(size_t)(sb % b->nb)];
+        if (!std::isinf(d_a) && !std::isinf(d_b)) reach[(size_t)row] = std::min(reach[(size_t)row], std::min(d_a, d_b));
     }
-    // Beyond 0.01 (5.73 degrees) the series of the squared angle loses its last bits: refused
-    for (int k = 0; k < n_rows; ++k) {
-        const double top = r2[(size_t)k * n_edges + n_edges - 1];
-        if (std::isinf(top)) return fail(YAWHIP_ERR_INVALID, "squared radii of row %d are not finite", k);
-        if (least[(size_t)k] == 0.0) continue;
-        smax[(size_t)k] = top / (least[(size_t)k] * least[(size_t)k]) * (1.0 + 1e-12);
-        if (!(smax[(size_t)k] <= 0.01))
-            return fail(YAWHIP_ERR_INVALID, "%s: an object is too close for the largest radius (row %d: the reach is a squared chord of %g, at most 0.01)",
-                        fn, k, smax[(size_t)k]);
-    }
+    for (double &least_d : reach) least_d *= least_d;
+    if (const int rc = chord_reach(fn, "an object", "row", n_rows, n_edges, r2, reach)) return rc;
     double *const fine[] = {fine_w};
-    return run_count(fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, Projected::PLANES, fine, candidates,
-                     wall0, stats,
-                     [&](const int32_t *d_cells, const double *d_r2, const double *d_rwin, int64_t cells_n, double *d_out,
-                         unsigned long long *d_eval) {
-                         hipLaunchKernelGGL(k_count_projected, dim3((unsigned)cells_n), dim3(WG), lds_bytes<Projected>(n_edges), ctx->stream,
-                                            view_of(a), ProjLanes{view_of(b), pmax}, d_cells, n_edges, d_r2, d_rwin, cells_n, d_out, d_eval);
-                     },
-                     smax.data());
+    return run_count<Projected>(fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), fine, candidates,
+                                wall0, stats, [&](auto go, const Slots &d) {
+                                    go(k_count_projected, view_of(a), ProjLanes{view_of(b), pmax}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out,
+                                       d.evaluated);
+                                });
 }
 
 }  // extern "C"

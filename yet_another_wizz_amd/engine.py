@@ -169,18 +169,22 @@ def count_rows_device(layout1, layout2, jobs, thresholds, n_rows_total: int, row
     return _lib.count_pairs_rows_device(ctx, d1, d2, jobs, thresholds, n_rows_total, row_index, kernel=kernel or default_kernel)
 
 
+def _require_shear(*layouts) -> None:
+    if any(layout.g1 is None or layout.g2 is None for layout in layouts):
+        raise ValueError("catalog has no 'g1'/'g2' attached")
+
+
 def count_shear_fine(lens_layout, source_layout, jobs, thresholds, *, sort_axis: int = 2):
     """Fine-bin shear sums for ``jobs`` (int[n, 2] = (lens patch, source patch)) -> ``(T, X, W, CountStats)``, f64[n_jobs, B, E-1]
     each: tangential and cross shear sums and the sum of ``w_l * w_s`` of the pairs (``yawhip_shear_count``). The lenses are the
     resident catalogue of ``lens_layout``; the sources (an unbinned layout with ``g1`` / ``g2``) reach the device once per
     context as a ``_lib.ShearSources`` kept on the layout, replaced when another sort axis is asked for. On a context of
     several devices the count runs on its first one. No CPU fallback; the CPU tests replace this function."""
-    if source_layout.g1 is None or source_layout.g2 is None:
-        raise ValueError("catalog has no 'g1'/'g2' attached")
+    _require_shear(source_layout)
     ctx = get_context()
     micro = forced_strip_micro if forced_strip_micro is not None else strip_micro_for(thresholds)
     lenses = device_catalog(lens_layout, ctx, sort_axis, micro, exact=forced_strip_micro is not None)
-    return _lib.shear_count(ctx, lenses, _shear_sources(source_layout, ctx, sort_axis), jobs, thresholds)
+    return _lib.shear_count(ctx, lenses, _shear_handle(source_layout, ctx, sort_axis), jobs, thresholds)
 
 
 def count_shear_auto_fine(layout, jobs, thresholds, *, sort_axis: int = 2):
@@ -190,10 +194,9 @@ def count_shear_auto_fine(layout, jobs, thresholds, *, sort_axis: int = 2):
     binned layout with ``g1`` / ``g2`` (``build_trees(edges, with_shear=True)``); it reaches the device once per context as a
     binned ``_lib.ShearSources`` kept on the layout, replaced when another sort axis is asked for. On a context of several
     devices the count runs on its first one. No CPU fallback; the CPU tests replace this function."""
-    if layout.g1 is None or layout.g2 is None:
-        raise ValueError("catalog has no 'g1'/'g2' attached")
+    _require_shear(layout)
     ctx = get_context()
-    return _lib.shear_auto_count(ctx, _shear_sources(layout, ctx, sort_axis), jobs, thresholds)
+    return _lib.shear_auto_count(ctx, _shear_handle(layout, ctx, sort_axis), jobs, thresholds)
 
 
 def count_shear_pair_fine(layout_a, layout_b, cells, thresholds, *, sort_axis: int = 2):
@@ -202,11 +205,10 @@ def count_shear_pair_fine(layout_a, layout_b, cells, thresholds, *, sort_axis: i
     ``(P, M, C, W, CountStats)``, f64[n_cells, E-1] each (``yawhip_shear_pair_count``). Both are binned layouts with ``g1`` /
     ``g2``, resident as for ``count_shear_auto_fine``; the same layout twice is ONE handle passed twice, and only then a cell
     with ``p == q`` and ``ka == kb`` holds every unordered pair once. No CPU fallback; the CPU tests replace this function."""
-    if any(layout.g1 is None or layout.g2 is None for layout in (layout_a, layout_b)):
-        raise ValueError("catalog has no 'g1'/'g2' attached")
+    _require_shear(layout_a, layout_b)
     ctx = get_context()
-    a = _shear_sources(layout_a, ctx, sort_axis)
-    b = a if layout_b is layout_a else _shear_sources(layout_b, ctx, sort_axis)
+    a = _shear_handle(layout_a, ctx, sort_axis)
+    b = a if layout_b is layout_a else _shear_handle(layout_b, ctx, sort_axis)
     return _lib.shear_pair_count(ctx, a, b, cells, thresholds)
 
 
@@ -248,24 +250,7 @@ def count_dsigma_fine(lens_layout, source_layout, jobs, thresholds, *, cosmology
     bins. Each reaches the device once per context as a handle kept on the layout (``_lib.DsigmaLenses``, ``_lib.ShearSources``
     with ``u``), replaced when another sort axis or another cosmology is asked for. On a context of several devices the count
     runs on its first one. No CPU fallback; the CPU tests replace this function."""
-    if source_layout.g1 is None or source_layout.g2 is None:
-        raise ValueError("catalog has no 'g1'/'g2' attached")
-    if source_layout.num_bins != 1:
-        raise ValueError("the sources of an excess-surface-density count are not binned in redshift")
-    ctx = get_context()
-
-    def lenses():
-        f, c, _ = dsigma_columns(lens_layout, None, cosmology)
-        return _lib.DsigmaLenses(ctx, lens_layout.x, lens_layout.y, lens_layout.z, lens_layout.w, f, c, lens_layout.num_patches,
-                                 lens_layout.num_bins, lens_layout.offsets, sort_axis=sort_axis)
-
-    def sources():
-        u = dsigma_columns(None, source_layout, cosmology)[2]
-        return _lib.ShearSources(ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1,
-                                 source_layout.g2, source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis, u=u)
-
-    return _lib.dsigma_count(ctx, _dsigma_handle(lens_layout, ctx, sort_axis, cosmology, "lenses", lenses),
-                             _dsigma_handle(source_layout, ctx, sort_axis, cosmology, "sources", sources), jobs, thresholds)
+    return _count_dsigma(lens_layout, source_layout, jobs, thresholds, cosmology, sort_axis)
 
 
 S2_CAP = 0.01  # the largest squared chord yawhip_dsigma_count_radial accepts as the reach of a lens (5.73 degrees)
@@ -341,32 +326,45 @@ def count_dsigma_radial_fine(lens_layout, source_layout, jobs, r2, *, cosmology,
     handle is kept on the layout per context, sort axis, cosmology, kind of unit and ``unit_columns``; the sources' is that of
     ``count_dsigma_fine``. A reach beyond the library's cap is a ``ValueError`` (``check_radial_reach``). No CPU fallback;
     the CPU tests replace this function."""
-    if source_layout.g1 is None or source_layout.g2 is None:
-        raise ValueError("catalog has no 'g1'/'g2' attached")
+    return _count_dsigma(lens_layout, source_layout, jobs, r2, cosmology, sort_axis, unit, unit_columns)
+
+
+def _count_dsigma(lens_layout, source_layout, jobs, table, cosmology, sort_axis, unit=None, unit_columns=False):
+    """The body of ``count_dsigma_fine`` (``unit`` None: ``table`` holds thresholds) and of ``count_dsigma_radial_fine`` (``table``
+    holds squared radii in ``unit``): the checks of the sources, the two resident handles, the count."""
+    _require_shear(source_layout)
     if source_layout.num_bins != 1:
         raise ValueError("the sources of an excess-surface-density count are not binned in redshift")
     ctx = get_context()
 
+    def columns(lens_side, source_side):  # (f, c, m, u)
+        if unit is not None:
+            return dsigma_radial_columns(lens_side, source_side, cosmology, unit, unit_columns=unit_columns)
+        f, c, u = dsigma_columns(lens_side, source_side, cosmology)
+        return f, c, None, u
+
     def lenses():
-        f, c, m, _ = dsigma_radial_columns(lens_layout, None, cosmology, unit, unit_columns=unit_columns)
+        f, c, m, _ = columns(lens_layout, None)
         return _lib.DsigmaLenses(ctx, lens_layout.x, lens_layout.y, lens_layout.z, lens_layout.w, f, c, lens_layout.num_patches,
                                  lens_layout.num_bins, lens_layout.offsets, sort_axis=sort_axis, m=m)
 
     def sources():
-        u = dsigma_radial_columns(None, source_layout, cosmology, unit, unit_columns=unit_columns)[3]
+        u = columns(None, source_layout)[3]
         return _lib.ShearSources(ctx, source_layout.x, source_layout.y, source_layout.z, source_layout.w, source_layout.g1,
                                  source_layout.g2, source_layout.num_patches, source_layout.offsets, sort_axis=sort_axis, u=u)
 
     suffix = " unit" if unit_columns else ""
-    lens_handle = _dsigma_handle(lens_layout, ctx, sort_axis, cosmology, f"lenses radial {radial_kind(unit)}{suffix}", lenses)
-    source_handle = _dsigma_handle(source_layout, ctx, sort_axis, cosmology, "sources" + suffix, sources)
+    lens_role = "lenses" if unit is None else f"lenses radial {radial_kind(unit)}{suffix}"
+    lens_handle = _handle(lens_layout, ctx, sort_axis, lens_role, lenses, cosmology)
+    source_handle = _handle(source_layout, ctx, sort_axis, "sources" + suffix, sources, cosmology)
+    if unit is None:
+        return _lib.dsigma_count(ctx, lens_handle, source_handle, jobs, table)
     try:
-        return _lib.dsigma_count_radial(ctx, lens_handle, source_handle, jobs, r2)
+        return _lib.dsigma_count_radial(ctx, lens_handle, source_handle, jobs, table)
     except _lib.YawhipError as err:
         if "too close for the largest radius" not in str(err):
             raise
-        m = dsigma_radial_columns(lens_layout, None, cosmology, unit, unit_columns=unit_columns)[2]
-        check_radial_reach(lens_layout, m, r2)  # the same refusal, with the lens's redshift and the radius
+        check_radial_reach(lens_layout, columns(lens_layout, None)[2], table)  # the same refusal, with the lens's redshift and the radius
         raise
 
 
@@ -427,7 +425,7 @@ def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, un
             return _lib.ProjHandle(ctx, layout.x, layout.y, layout.z, layout.w, d, c, layout.num_patches, layout.num_bins,
                                    layout.offsets, sort_axis=sort_axis)
 
-        return _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload)
+        return _handle(layout, ctx, sort_axis, role, upload, cosmology)
 
     a = handle(layout_a)
     b = a if layout_b is layout_a else handle(layout_b)
@@ -451,30 +449,26 @@ def check_projected_reach(layouts, cosmology, unit, r2):
     return smax
 
 
-def _dsigma_handle(layout, ctx, sort_axis, cosmology, role, upload):
-    """The resident handle of ``layout`` in ``role`` ("lenses" / "sources") on ``ctx``, uploaded on first use."""
+def _handle(layout, ctx, sort_axis, role, upload, cosmology=None):
+    """The resident handle of ``layout`` in ``role`` on ``ctx`` (``layout.handles``), made by ``upload()`` on first use and
+    anew where the one held has another sort axis, was freed, or was made with another ``cosmology`` than the one asked for
+    (None, the same for every call of a role whose columns need none, equals only None)."""
     from .cosmology import cosmology_is_equal
 
-    held = layout.dsigma_device.get((id(ctx), role))
+    held = layout.handles.get((id(ctx), role))
     if held is not None and (held[0].sort_axis != sort_axis or not held[0]._h or not cosmology_is_equal(held[1], cosmology)):
         held[0].free()
         held = None
     if held is None:
-        held = layout.dsigma_device[(id(ctx), role)] = (upload(), cosmology)
+        held = layout.handles[(id(ctx), role)] = (upload(), cosmology)
     return held[0]
 
 
-def _shear_sources(layout, ctx, sort_axis):
-    """The resident ``_lib.ShearSources`` of a layout with shear columns on ``ctx``, uploaded on first use."""
-    sources = layout.shear_device.get(id(ctx))
-    if sources is not None and (sources.sort_axis != sort_axis or not sources._h):
-        sources.free()
-        sources = None
-    if sources is None:
-        sources = layout.shear_device[id(ctx)] = _lib.ShearSources(
-            ctx, layout.x, layout.y, layout.z, layout.w, layout.g1, layout.g2, layout.num_patches, layout.offsets,
-            sort_axis=sort_axis, n_bins=layout.num_bins)
-    return sources
+def _shear_handle(layout, ctx, sort_axis):
+    """The role "shear": the ``_lib.ShearSources`` of a layout with shear columns, binned as the layout is."""
+    return _handle(layout, ctx, sort_axis, "shear", lambda: _lib.ShearSources(
+        ctx, layout.x, layout.y, layout.z, layout.w, layout.g1, layout.g2, layout.num_patches, layout.offsets, sort_axis=sort_axis,
+        n_bins=layout.num_bins))
 
 
 def _device_pair(layout1, layout2, thresholds, sort_axis, max_workers=None):

@@ -340,10 +340,7 @@ class PatchLinkage:
                                                sort_axis=self.sort_axis, max_workers=max_workers)
             self.last_stats = stats
             self._report(count_type_info, len(jobs), stats, progress)
-            scale_counts = [PatchedCounts(binning, counts[s], auto=auto) for s in range(counts.shape[0])]
-            sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins),
-                                            auto=auto)
-            return [NormalisedCounts(c, sum_weights) for c in scale_counts]
+            return _normalised_counts(binning, counts, layout1, layout2, auto)
         # Several ranks: balance what the device will really evaluate (lane tile x window sizes, from the item builder); the
         # partition is a plan: rank 0 derives it once per (catalogue pair, thresholds, group size) and broadcasts it.
         # The key is rank independent (every rank enters the broadcast below, or none does) and identifies the catalogue pair
@@ -428,13 +425,9 @@ class PatchLinkage:
         flat, halve = self._scatter[skey]
         # [S, B, jobs] -> [S, B, i * P + j], zero elsewhere (one pass in the library: yawhip_host_scatter_rows)
         counts = _lib.scatter_rows((num_scales, num_bins, num_patches, num_patches), flat, per_scale, halve)
-        scale_counts = [PatchedCounts(binning, counts[s], auto=auto) for s in range(num_scales)]
-
-        sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins),
-                                        auto=auto)
         if failure is None and self.last_stats is not None:
             self._report(count_type_info, len(jobs), self.last_stats, progress)
-        return [NormalisedCounts(counts, sum_weights) for counts in scale_counts]
+        return _normalised_counts(binning, counts, layout1, layout2, auto)
 
     def count_pairs_batch(self, requests, *, progress: bool = False, max_workers: int | None = None) -> list:
         """The pair counts of ONE measurement -- ``requests`` = ``[(catalogs, info), ...]`` or ``[(catalogs, info, mode), ...]``
@@ -484,9 +477,7 @@ class PatchLinkage:
             self.last_stats = stats
             self.last_batch_stats[info or str(i)] = stats
             self._report(info, n_jobs, stats, progress)
-            scale_counts = [PatchedCounts(binning, counts[s], auto=auto) for s in range(counts.shape[0])]
-            sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
-            results[i] = [NormalisedCounts(c, sum_weights) for c in scale_counts]
+            results[i] = _normalised_counts(binning, counts, layout1, layout2, auto)
         return results
 
     def count_scalar_pairs(self, main_catalog: Catalog, *optional_catalog: Catalog, progress: bool = False,
@@ -517,16 +508,7 @@ class PatchLinkage:
         the cross shear of the pairs, each over the sum of their weights ``w_l * w_s``. Thresholds, separation weights and
         per-scale sums are those of ``count_pairs``; ONE library call counts all jobs (``engine.count_shear_fine``), on one
         device of one process: several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
-        def layouts(num_bins):
-            lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
-            if source_layout.g1 is None or source_layout.g2 is None:
-                raise ValueError("catalog has no 'g1'/'g2' attached")
-            return engine.count_shear_fine, (lens_layout, source_layout)
-
-        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress)
-        return [(NormalisedScalarCounts(PatchedCounts(binning, T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
-                 NormalisedScalarCounts(PatchedCounts(binning, X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
-                for s in range(len(W))]
+        return self._count_lens_pairs(lenses, sources, count_type_info, progress, "count_shear_fine")
 
     def count_dsigma_pairs(self, lenses: Catalog, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
                            count_type_info: str | None = None) -> list:
@@ -537,21 +519,8 @@ class PatchLinkage:
         over the sum of ``w_l w_s S^2``, ``S = D_A(z_l) (1 - chi_l / chi_s)`` in Mpc from the configuration's cosmology: the
         ratio is Delta Sigma in M_sun / pc^2. Everything else is ``count_shear_pairs``'; ONE library call counts all jobs
         (``engine.count_dsigma_fine``)."""
-        import functools
-
-        def layouts(num_bins):
-            lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
-            if source_layout.g1 is None or source_layout.g2 is None:
-                raise ValueError("catalog has no 'g1'/'g2' attached")
-            if lens_layout.redshifts is None or source_layout.redshifts is None or source_layout.num_bins != 1:
-                raise ValueError("excess surface density needs layouts with redshifts and unbinned sources: "
-                                 "build_trees(..., with_redshifts=True)")
-            return functools.partial(engine.count_dsigma_fine, cosmology=self.config.cosmology), (lens_layout, source_layout)
-
-        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress)
-        return [(NormalisedScalarCounts(PatchedCounts(binning, DELTA_SIGMA_UNIT * T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
-                 NormalisedScalarCounts(PatchedCounts(binning, DELTA_SIGMA_UNIT * X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
-                for s in range(len(W))]
+        return self._count_lens_pairs(lenses, sources, count_type_info, progress, "count_dsigma_fine", needs="excess surface density",
+                                      K=DELTA_SIGMA_UNIT, cosmology=self.config.cosmology)
 
     def count_dsigma_radial_pairs(self, lenses: Catalog, sources: Catalog, *, shear_only: bool = False, progress: bool = False,
                                   max_workers: int | None = None, count_type_info: str | None = None) -> list:
@@ -560,23 +529,28 @@ class PatchLinkage:
         the same in every redshift bin (``engine.count_dsigma_radial_fine``). ``shear_only``: the sums of
         ``count_shear_pairs`` in that binning -- no factor ``S``, no ``K``, and the sources need no redshifts. The linkage must
         reach as far as the nearest lens sees the largest radius (``from_catalogs(max_angle=radial_max_angle(...))``)."""
-        import functools
+        return self._count_lens_pairs(lenses, sources, count_type_info, progress, "count_dsigma_radial_fine", needs="a count binned per lens",
+                                      source_redshifts=not shear_only, K=1.0 if shear_only else DELTA_SIGMA_UNIT, radial=True,
+                                      cosmology=self.config.cosmology, unit=self.config.scales.scales.unit, unit_columns=shear_only)
 
+    def _count_lens_pairs(self, lenses, sources, count_type_info, progress, count: str, *, needs: str | None = None,
+                          source_redshifts: bool = True, K: float = 1.0, radial: bool = False, **count_args) -> list:
+        """What ``count_shear_pairs``, ``count_dsigma_pairs`` and ``count_dsigma_radial_pairs`` share: the layout checks
+        (``needs``: the count takes lens layouts with redshifts and unbinned sources, with redshifts too unless
+        ``source_redshifts`` is off; the word opens the ``ValueError``), the engine's function ``count`` with ``count_args``
+        (looked up at call time: the CPU tests replace it) and the two ratios per scale, the numerators times ``K``."""
         def layouts(num_bins):
             lens_layout, source_layout = _active_layout(lenses, num_bins), _active_layout(sources, num_bins)
             if source_layout.g1 is None or source_layout.g2 is None:
                 raise ValueError("catalog has no 'g1'/'g2' attached")
-            if lens_layout.redshifts is None or (source_layout.redshifts is None and not shear_only) or source_layout.num_bins != 1:
-                raise ValueError("a count binned per lens needs layouts with redshifts and unbinned sources: "
-                                 "build_trees(..., with_redshifts=True)")
-            count = functools.partial(engine.count_dsigma_radial_fine, cosmology=self.config.cosmology,
-                                      unit=self.config.scales.scales.unit, unit_columns=shear_only)
-            return count, (lens_layout, source_layout)
+            if needs is not None and (lens_layout.redshifts is None or (source_layout.redshifts is None and source_redshifts)
+                                      or source_layout.num_bins != 1):
+                raise ValueError(f"{needs} needs layouts with redshifts and unbinned sources: build_trees(..., with_redshifts=True)")
+            return functools.partial(getattr(engine, count), **count_args), (lens_layout, source_layout)
 
-        binning, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress, radial=True)
-        K = 1.0 if shear_only else DELTA_SIGMA_UNIT
-        return [(NormalisedScalarCounts(PatchedCounts(binning, K * T[s], auto=False), PatchedCounts(binning, W[s], auto=False)),
-                 NormalisedScalarCounts(PatchedCounts(binning, K * X[s], auto=False), PatchedCounts(binning, W[s], auto=False)))
+        binning, _, (T, X, W) = self._count_shear_planes((lenses, sources), layouts, count_type_info, progress, radial=radial)
+        return [tuple(NormalisedScalarCounts(PatchedCounts(binning, K * num[s], auto=False), PatchedCounts(binning, W[s], auto=False))
+                      for num in (T, X))
                 for s in range(len(W))]
 
     def count_shear_auto_pairs(self, sources: Catalog, *, progress: bool = False, max_workers: int | None = None,
@@ -596,7 +570,7 @@ class PatchLinkage:
                 raise ValueError("shear-shear counts need the sources binned in redshift")
             return engine.count_shear_auto_fine, (layout,)
 
-        binning, (P, M, C, W) = self._count_shear_planes((sources,), layouts, count_type_info, progress)
+        binning, _, (P, M, C, W) = self._count_shear_planes((sources,), layouts, count_type_info, progress)
         return [tuple(NormalisedScalarCounts(PatchedCounts(binning, num[s], auto=True), PatchedCounts(binning, W[s], auto=True))
                       for num in (P, M, C))
                 for s in range(len(W))]
@@ -688,43 +662,37 @@ class PatchLinkage:
         if parallel.world()[1] > 1:
             raise NotImplementedError("projected counts run in one process on one device")
         pi_max = engine.check_pi_max(pi_max)
-        if count_type_info is not None:
-            _log_info("counting %s from patch pairs", count_type_info)
         auto = second_catalog is None
-        cat2 = main_catalog if auto else second_catalog
-        binning = self.config.binning.binning
-        num_bins, num_patches = len(binning), len(main_catalog)
-        layout1, layout2 = _active_layout(main_catalog, num_bins), _active_layout(cat2, num_bins)
-        for layout in (layout1, layout2):
-            if layout.redshifts is None or layout.num_bins != num_bins:
-                raise ValueError("a projected count needs layouts binned in redshift that carry redshifts: "
-                                 "build_trees(edges, with_redshifts=True)")
-        jobs = self.get_patch_pairs(main_catalog, None if auto else cat2)
-        plans = radial_plans(self.config)
-        r2, combine = threshold_table(plans), CombinePlan(plans)
-        # cell (job, k): segment (p, k) of the first side against (q, k) of the second, row k; diagonal iff one segment twice
-        seg1 = (jobs[:, :1].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
-        seg2 = (jobs[:, 1:].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
-        diagonal = (seg1 == seg2) if auto else np.zeros(len(seg1), dtype=bool)
-        cells = np.column_stack([seg1, seg2, np.tile(np.arange(num_bins), len(jobs)), diagonal]).astype(np.int32).reshape(-1, 4)
-        fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, cosmology=self.config.cosmology,
-                                                  unit=self.config.scales.scales.unit, sort_axis=self.sort_axis)
-        self.last_stats = stats
-        self._report(count_type_info, len(jobs), stats, progress)
-        flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
-        shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
-        # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
-        fine = np.asarray(fine, dtype=np.float64).reshape(len(jobs), num_bins, r2.shape[1] - 1)
-        counts = _lib.scatter_rows(shape, flat, combine(np.moveaxis(fine, 0, -1)))
-        sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
-        return [NormalisedCounts(PatchedCounts(binning, counts[s], auto=auto), sum_weights) for s in range(shape[0])]
+
+        def layouts(num_bins):
+            layout1, layout2 = _active_layout(main_catalog, num_bins), _active_layout(main_catalog if auto else second_catalog, num_bins)
+            for layout in (layout1, layout2):
+                if layout.redshifts is None or layout.num_bins != num_bins:
+                    raise ValueError("a projected count needs layouts binned in redshift that carry redshifts: "
+                                     "build_trees(edges, with_redshifts=True)")
+
+            def count(layout1, layout2, jobs, r2, *, sort_axis):
+                # cell (job, k): segment (p, k) of the first side against (q, k) of the second, row k; diagonal iff one segment twice
+                seg1 = (jobs[:, :1].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
+                seg2 = (jobs[:, 1:].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
+                diagonal = (seg1 == seg2) if auto else np.zeros(len(seg1), dtype=bool)
+                cells = np.column_stack([seg1, seg2, np.tile(np.arange(num_bins), len(jobs)), diagonal]).astype(np.int32).reshape(-1, 4)
+                fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, cosmology=self.config.cosmology,
+                                                          unit=self.config.scales.scales.unit, sort_axis=sort_axis)
+                return np.asarray(fine, dtype=np.float64).reshape(len(jobs), num_bins, r2.shape[1] - 1), stats
+
+            return count, (layout1, layout2)
+
+        catalogs = (main_catalog,) if auto else (main_catalog, second_catalog)
+        binning, (layout1, layout2), (counts,) = self._count_shear_planes(catalogs, layouts, count_type_info, progress, radial=True)
+        return _normalised_counts(binning, counts, layout1, layout2, auto)
 
     def _count_shear_planes(self, catalogs, layouts, count_type_info, progress, radial: bool = False):
-        """What the two shear counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the engine's
-        count (``count_shear_fine`` / ``count_shear_auto_fine``, looked up at call time: the CPU tests replace them) with the
-        layouts it takes; its job list is ``get_patch_pairs(*catalogs)``. Returns the binning and one f64[S, B, P, P] per
-        plane of the count, zero outside the jobs. ``radial``: edges and recombination are those of the configuration's
-        radial plan (``radial_plans``), the same for every redshift bin."""
+        """What the lensing and projected counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the
+        count (a function of the engine, looked up at call time: the CPU tests replace them) with the layouts it takes; its job
+        list is ``get_patch_pairs(*catalogs)``. Returns the binning, those layouts and one f64[S, B, P, P] per plane of the
+        count, zero outside the jobs. ``radial``: edges and recombination are those of the configuration's radial plan
+        (``radial_plans``), the same for every redshift bin."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("shear counts run in one process on one device")
         if count_type_info is not None:
@@ -745,7 +713,7 @@ class PatchLinkage:
         flat = np.ascontiguousarray(jobs[:, 0].astype(np.int64) * num_patches + jobs[:, 1])
         shape = (self.config.scales.num_scales, num_bins, num_patches, num_patches)
         # [jobs, B, E-1] -> separation weights and per-scale sums [S, B, jobs] -> [S, B, i * P + j], zero elsewhere
-        return binning, [_lib.scatter_rows(shape, flat, combine(np.moveaxis(f, 0, -1))) for f in fine]
+        return binning, count_layouts, [_lib.scatter_rows(shape, flat, combine(np.moveaxis(f, 0, -1))) for f in fine]
 
     @staticmethod
     def _report(what, n_jobs, stats, progress) -> None:
@@ -778,6 +746,14 @@ def _active_layout(catalog: Catalog, num_bins: int):
     if layout.num_bins not in (1, num_bins):
         raise ValueError(f"catalog was binned into {layout.num_bins} redshift bins, configuration has {num_bins}")
     return layout
+
+
+def _normalised_counts(binning, counts, layout1, layout2, auto: bool) -> list:
+    """The result tensor ``counts`` f64[S, B, P, P] of a pair count between two layouts as one ``NormalisedCounts`` per scale,
+    all over the one ``PatchedSumWeights`` of the layouts."""
+    num_bins = len(binning)
+    sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
+    return [NormalisedCounts(PatchedCounts(binning, counts[s], auto=auto), sum_weights) for s in range(len(counts))]
 
 
 def _count_sides(layout1, layout2, mode):
@@ -934,24 +910,35 @@ def crosscorrelate_scalar(config, reference: Catalog, unknown: Catalog, *, unk_r
     """Angular cross-correlation amplitude between the scalar field carried by ``reference`` (with redshifts) and the
     ``unknown`` sample: "kn" DD, minus the same count against ``unk_rand`` when it is given, else minus the mean field per
     patch (``compute_scalar_normalisation``) -> ``[ScalarCorrFunc]``, one per scale (measurements.py:708-794)."""
-    _require_distinct(reference, unknown, unk_rand)
-    count_dr = unk_rand is not None
+    return _crosscorrelate_scalar(config, reference, unknown, unk_rand, "kn", progress, max_workers)
+
+
+def _crosscorrelate_scalar(config, reference, other, rand, mode: str, progress, max_workers) -> list:
+    """The two scalar cross-correlation drivers: ``reference`` is binned in redshift, ``other`` is not. ``mode`` "kn": the
+    field rides on the reference and ``rand`` stands in for ``other``; "nk": the field rides on ``other`` (a map) and ``rand``
+    stands in for the reference. Without ``rand`` the mean field per patch of the side that carries it takes DR's place."""
+    _require_distinct(reference, other, rand)
+    count_dr, field_on_reference = rand is not None, mode == "kn"
     edges, closed = config.binning.edges, config.binning.closed
     randoms = []
     _log_info("building reference data trees")
     reference.build_trees(edges, closed=closed)
-    unknown.build_trees(None)
+    other.build_trees(None)
     if count_dr:
-        unk_rand.build_trees(None)
-        randoms.append(unk_rand)
+        if field_on_reference:
+            rand.build_trees(None)
+        else:
+            rand.build_trees(edges, closed=closed)
+        randoms.append(rand)
     _log_info("computing cross-correlation with DD" + (", DR" if count_dr else ""))
-    links = PatchLinkage.from_catalogs(config, reference, unknown, *randoms)
+    links = PatchLinkage.from_catalogs(config, reference, other, *randoms)
     kwargs = dict(progress=progress, max_workers=max_workers)
     if count_dr:  # the reference counts DD (kn), DD (nn), DR (kn), DR (nn) one after the other; here they are ONE submission
-        DD, DR = links._count_scalar_batch([((reference, unknown), "DD"), ((reference, unk_rand), "DR")], "kn", **kwargs)
+        dr = (reference, rand) if field_on_reference else (rand, other)
+        DD, DR = links._count_scalar_batch([((reference, other), "DD"), (dr, "DR")], mode, **kwargs)
     else:
-        DD = links.count_scalar_pairs(reference, unknown, mode="kn", count_type_info="DD", **kwargs)
-        DR = [compute_scalar_normalisation(reference, config.binning.binning)] * len(DD)
+        DD = links.count_scalar_pairs(reference, other, mode=mode, count_type_info="DD", **kwargs)
+        DR = [compute_scalar_normalisation(reference if field_on_reference else other, config.binning.binning)] * len(DD)
     return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]
 
 
@@ -967,25 +954,7 @@ def crosscorrelate_scalar_map(config, reference: Catalog, scalar_map: Catalog, *
     it can only be the unbinned side of the count, and the count that fits, "nk", is one the reference's drivers never
     issue. The pieces are the reference's all the same: the "nk" mode of its pair counts, ``NormalisedScalarCounts`` and
     ``ScalarCorrFunc``."""
-    _require_distinct(reference, scalar_map, ref_rand)
-    count_dr = ref_rand is not None
-    edges, closed = config.binning.edges, config.binning.closed
-    randoms = []
-    _log_info("building reference data trees")
-    reference.build_trees(edges, closed=closed)
-    scalar_map.build_trees(None)
-    if count_dr:
-        ref_rand.build_trees(edges, closed=closed)
-        randoms.append(ref_rand)
-    _log_info("computing cross-correlation with DD" + (", DR" if count_dr else ""))
-    links = PatchLinkage.from_catalogs(config, reference, scalar_map, *randoms)
-    kwargs = dict(progress=progress, max_workers=max_workers)
-    if count_dr:  # DD (nk), DD (nn), DR (nk), DR (nn) in ONE submission
-        DD, DR = links._count_scalar_batch([((reference, scalar_map), "DD"), ((ref_rand, scalar_map), "DR")], "nk", **kwargs)
-    else:
-        DD = links.count_scalar_pairs(reference, scalar_map, mode="nk", count_type_info="DD", **kwargs)
-        DR = [compute_scalar_normalisation(scalar_map, config.binning.binning)] * len(DD)
-    return [ScalarCorrFunc(dd, dr) for dd, dr in zip(DD, DR)]
+    return _crosscorrelate_scalar(config, reference, scalar_map, ref_rand, "nk", progress, max_workers)
 
 
 def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_rand: Catalog | None = None,
@@ -1006,23 +975,35 @@ def crosscorrelate_shear(config, reference: Catalog, sources: Catalog, *, ref_ra
     _require_distinct(reference, sources, ref_rand)
     if not sources.has_shear:
         raise ValueError("catalog has no 'g1'/'g2' attached")
+    return _crosscorrelate_lensing(config, reference, sources, ref_rand, radius, progress, max_workers, delta_sigma=False)
+
+
+def _crosscorrelate_lensing(config, reference, sources, ref_rand, radius, progress, max_workers, *, delta_sigma: bool):
+    """What ``crosscorrelate_shear`` and ``crosscorrelate_delta_sigma`` (``delta_sigma``: every layout carries redshifts) share
+    after their own argument checks: the layouts, the linkage -- as far as the nearest lens sees the largest radius for
+    ``radius="lens"`` -- and DD with the optional DR. Returns the result list of ``crosscorrelate_shear``."""
     per_lens = _per_lens(config, radius)
     edges, closed = config.binning.edges, config.binning.closed
+    lens_redshifts = delta_sigma or per_lens
     randoms = []
     _log_info("building reference data trees")
-    lens_layouts = [reference.build_trees(edges, closed=closed, with_redshifts=per_lens)]
+    lens_layouts = [reference.build_trees(edges, closed=closed, with_redshifts=lens_redshifts)]
     if ref_rand is not None:
-        lens_layouts.append(ref_rand.build_trees(edges, closed=closed, with_redshifts=per_lens))
+        lens_layouts.append(ref_rand.build_trees(edges, closed=closed, with_redshifts=lens_redshifts))
         randoms.append(ref_rand)
-    sources.build_trees(None)
-    _log_info("computing shear cross-correlation with DD" + (", DR" if randoms else ""))
+    if delta_sigma:
+        sources.build_trees(None, with_redshifts=True)
+    else:
+        sources.build_trees(None)
+    _log_info(("computing excess surface density" if delta_sigma else "computing shear cross-correlation") + " with DD"
+              + (", DR" if randoms else ""))
     kwargs = dict(progress=progress, max_workers=max_workers)
     if per_lens:
         links = PatchLinkage.from_catalogs(config, reference, sources, *randoms, max_angle=radial_max_angle(config, *lens_layouts))
-        count = functools.partial(links.count_dsigma_radial_pairs, shear_only=True)
+        count = functools.partial(links.count_dsigma_radial_pairs, shear_only=not delta_sigma)
     else:
         links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
-        count = links.count_shear_pairs
+        count = links.count_dsigma_pairs if delta_sigma else links.count_shear_pairs
     DD = count(reference, sources, count_type_info="DD", **kwargs)
     DR = count(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
     return [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
@@ -1072,32 +1053,15 @@ def crosscorrelate_delta_sigma(config, reference: Catalog, sources: Catalog, *, 
         raise ValueError("excess surface density needs source redshifts: the sources have no 'redshifts' attached")
     if boost and ref_rand is None:
         raise ValueError("the boost factor needs random lenses: give 'ref_rand'")
-    per_lens = _per_lens(config, radius)
-    edges, closed = config.binning.edges, config.binning.closed
-    randoms = []
-    _log_info("building reference data trees")
-    lens_layouts = [reference.build_trees(edges, closed=closed, with_redshifts=True)]
-    if ref_rand is not None:
-        lens_layouts.append(ref_rand.build_trees(edges, closed=closed, with_redshifts=True))
-        randoms.append(ref_rand)
-    source_layout = sources.build_trees(None, with_redshifts=True)
-    _log_info("computing excess surface density with DD" + (", DR" if randoms else ""))
-    kwargs = dict(progress=progress, max_workers=max_workers)
-    if per_lens:
-        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms, max_angle=radial_max_angle(config, *lens_layouts))
-        count = links.count_dsigma_radial_pairs
-    else:
-        links = PatchLinkage.from_catalogs(config, reference, sources, *randoms)
-        count = links.count_dsigma_pairs
-    DD = count(reference, sources, count_type_info="DD", **kwargs)
-    DR = count(ref_rand, sources, count_type_info="DR", **kwargs) if randoms else [(None, None)] * len(DD)
-    result = [(ScalarCorrFunc(dd_t, dr_t), ScalarCorrFunc(dd_x, dr_x)) for (dd_t, dd_x), (dr_t, dr_x) in zip(DD, DR)]
+    result = _crosscorrelate_lensing(config, reference, sources, ref_rand, radius, progress, max_workers, delta_sigma=True)
     if boost:  # the W planes of the two counts over the products of the weight sums: (DD - DR) / DR
         binning, num_bins = config.binning.binning, len(config.binning.binning)
-        norms = [PatchedSumWeights(binning, layout.sum_weights_for(num_bins), source_layout.sum_weights_for(num_bins), auto=False)
-                 for layout in lens_layouts]
-        result = [(cf_t, cf_x, CorrFunc(NormalisedCounts(dd_t.number_counts, norms[0]), NormalisedCounts(dr_t.number_counts, norms[1])))
-                  for (cf_t, cf_x), (dd_t, _), (dr_t, _) in zip(result, DD, DR)]
+        source_layout = _active_layout(sources, num_bins)  # (the layouts the counts ran on)
+        norms = [PatchedSumWeights(binning, _active_layout(lenses, num_bins).sum_weights_for(num_bins),
+                                   source_layout.sum_weights_for(num_bins), auto=False)
+                 for lenses in (reference, ref_rand)]
+        result = [(cf_t, cf_x, CorrFunc(NormalisedCounts(cf_t.dd.number_counts, norms[0]), NormalisedCounts(cf_t.dr.number_counts, norms[1])))
+                  for cf_t, cf_x in result]
     return result
 
 
