@@ -758,6 +758,43 @@ int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double
 int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                       int32_t n_rows, int32_t n_edges, const double *r2, double pmax, double *fine_w, yawhip_stats *stats);
 
+/*
+ * Projected pair counts binned in the line-of-sight separation besides: the planes DD, DR and RR of xi(r_p, pi), from which
+ * w_p(r_p) = 2 sum_j xi(r_p, pi_j) dpi_j is summed (measurements.autocorrelate_projected(pi_bins=...); DESIGN.md section 22;
+ * no counterpart in the reference). Additive to ABI 6: one new symbol.
+ *
+ * yawhip_proj_count_pi  yawhip_proj_count argument for argument, with the call-wide edges pe float64[n_pi + 1] (host) in the
+ *                       place of pmax. s2, D, DD, q, th2, R2 and the fine bin e of a pair are exactly yawhip_proj_count's
+ *                       (float64, every operation rounded on its own). Then
+ *       p = fabs(c_a - c_b)
+ *       j = the number of edges pe[1 .. n_pi] that are < p        plane 0 is [0, pe[1]], plane j is (pe[j], pe[j + 1]]
+ *       the pair counts  iff  j < n_pi                            that is, p <= pe[n_pi]
+ *       fine_w[j][c][e] += w_a * w_b
+ *     p is bit-symmetric, so a diagonal cell holds every unordered pair once, as in yawhip_proj_count. A pair behind the
+ *     outer test whose R2 lies beyond the last radius edge is in no plane.
+ *     Two consequences: over unit weights the sum over j of fine_w[j] equals the fine_w of yawhip_proj_count with
+ *     pmax = pe[n_pi], as integers; and candidate_pairs and evaluated_pairs equal those of that call -- it is the same
+ *     walk, with the same window and the same count of a diagonal cell's kept separations.
+ *   n_pi, pe     n_pi >= 1; pe[0] exactly 0; pe finite and strictly ascending, except that pe[n_pi] may be +inf (no outer
+ *                cut). Anything else (NaN, ties, a NULL pe): YAWHIP_ERR_INVALID.
+ *   the cap      a workgroup keeps two stages of 48-byte objects, the n_edges thresholds, the n_pi + 1 pi edges (both
+ *                rounded up to an even number of float64) and one histogram [n_pi][n_edges - 1] per wave, four waves, in
+ *                the 64 KiB of dynamic LDS of every count here:
+ *                  24576 + 8 (((n_edges + 1) & ~1) + ((n_pi + 2) & ~1)) + 32 n_pi (n_edges - 1) <= 65536
+ *                -- n_pi <= 104 at 13 edges, <= 4 at 256, <= 1023 at 2. A larger n_pi is YAWHIP_ERR_INVALID with a message
+ *                that names the largest n_pi that fits at this n_edges; the library does not split a call.
+ *   fine_w       float64[n_pi][n_cells][n_edges - 1] (host); every element is written
+ *   checks       those of yawhip_proj_count in its order -- handles, sizes and context, both handles projected
+ *                (YAWHIP_ERR_MISMATCH), then n_pi and pe and the cap where that call checks pmax, the radius edges, the
+ *                cells, the reach. stats, buffers, n_cells == 0: as yawhip_proj_count.
+ * Kernel: yawhip_proj_count's, its loop up to the wave-wide test unchanged; the pi edges are staged into LDS once per
+ * workgroup, and behind the test p is bisected over them as R2 is over the row. Accumulation and reproducibility as
+ * yawhip_shear_count: per-wave LDS histograms, folded in a fixed order, plain stores.
+ */
+int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                         int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine_w,
+                         yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

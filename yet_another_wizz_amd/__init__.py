@@ -20,7 +20,7 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import CorrFunc, ScalarCorrFunc
+from .corrfunc import CorrFunc, ProjectedCorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
                            crosscorrelate_delta_sigma, crosscorrelate_shear)
@@ -46,6 +46,7 @@ __all__ = [
     "PatchLinkage",
     "PatchedCounts",
     "PatchedSumWeights",
+    "ProjectedCorrFunc",
     "RedshiftData",
     "SampledData",
     "ScalarCorrFunc",

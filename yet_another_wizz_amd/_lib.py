@@ -70,6 +70,7 @@ ABI_SYMBOLS = (
     "yawhip_dsigma_count_radial",
     "yawhip_proj_upload",
     "yawhip_proj_count",
+    "yawhip_proj_count_pi",
 )
 
 
@@ -301,6 +302,8 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_proj_upload.argtypes = lib.yawhip_dsigma_upload_lenses.argtypes
     lib.yawhip_proj_count.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_double, _dp,
                                       ctypes.POINTER(_Stats)]
+    lib.yawhip_proj_count_pi.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
+                                         _dp, ctypes.POINTER(_Stats)]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -867,18 +870,22 @@ class ProjHandle(ShearSources):
 
 
 def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
-                  rows: str = "thresholds must be [n_bins, n_edges]"):
-    """What the six counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+                  rows: str = "thresholds must be [n_bins, n_edges]", stacked: bool = False):
+    """What the seven counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
     ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
     entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
-    and the ``CountStats``."""
+    and the ``CountStats``. ``stacked``: the symbol takes the planes as ONE array f64[n_planes, ...], which is what comes
+    back in their place."""
     table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, width)
     t = np.ascontiguousarray(thresholds, dtype=np.float64)
     if t.ndim != 2:
         raise ValueError(rows)
     n_rows, n_edges = t.shape
     shape = (len(table), n_rows, max(n_edges - 1, 0)) if width == 2 else (len(table), max(n_edges - 1, 0))
-    out = [np.empty(shape, dtype=np.float64) for _ in range(n_planes)]  # the library writes every element
+    if stacked:
+        out = [np.empty((n_planes, *shape), dtype=np.float64)]
+    else:
+        out = [np.empty(shape, dtype=np.float64) for _ in range(n_planes)]  # the library writes every element
     st = _Stats()
     _check(
         getattr(load_library(), symbol)(*handles, len(table), _ptr(table, _i32p), n_rows, n_edges, _ptr(t, _dp), *extra,
@@ -886,6 +893,20 @@ def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra
         symbol,
     )
     return (*out, _count_stats(st))
+
+
+def proj_count_pi(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pi_edges):
+    """Run ``yawhip_proj_count_pi``: ``proj_count`` with the pairs binned in ``p = |c_a - c_b|`` besides; ``pi_edges``
+    f64[n_pi + 1] starts at exactly 0 and ascends strictly, finite but for a last edge that may be ``inf``; bin 0 is
+    ``[0, pe[1]]``, bin j ``(pe[j], pe[j + 1]]``. Returns ``(W, CountStats)``, W f64[n_pi, n_cells, E-1]; its sum over the pi
+    bins is ``proj_count``'s W at ``pmax = pi_edges[-1]`` (exactly, for unit weights), and the statistics are that call's.
+    ``n_pi (E - 1)`` is capped by the LDS of a workgroup (include/yawhip.h); beyond it the library refuses."""
+    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
+    if pe.ndim != 1:
+        raise ValueError("pi_edges must be [n_pi + 1]")
+    n_pi = len(pe) - 1
+    return _shear_counts("yawhip_proj_count_pi", max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp), width=4,
+                         rows="r2 must be [n_rows, n_edges]", stacked=True)
 
 
 def proj_count(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pmax: float):

@@ -2,10 +2,12 @@
 ``yaw.correlation.corrfunc``, src/yaw/correlation/corrfunc.py:69-352; file I/O out of scope)."""
 from __future__ import annotations
 
+import numpy as np
+
 from .corrdata import CorrData
 from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "ScalarCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -146,3 +148,98 @@ class ScalarCorrFunc(CorrFunc):
 
     def get_estimator(self):
         return scalar_correlation
+
+
+class ProjectedCorrFunc:
+    """The pair counts of one scale of the projected clustering binned in the line-of-sight separation ``pi``
+    (``autocorrelate_projected(pi_bins=...)``; no counterpart in the reference): ``pi_edges`` f64[n_pi + 1], from 0 and
+    strictly ascending, and ``pi_bins``, a tuple of ``n_pi`` ``CorrFunc(dd, dr, None, rr)`` -- bin 0 holds the pairs with
+    ``pi`` in ``[0, pe[1]]``, bin j those in ``(pe[j], pe[j + 1]]``. All bins hold the same kinds of counts on one binning
+    and one set of patches.
+
+    ``sample_xi()`` is ``xi(r_p, pi_j)`` per pi bin, ``sample()`` the summed ``w_p(r_p) = 2 sum_j dpi_j xi_j`` and
+    ``cylinder()`` the single-cylinder measurement over the pi-summed counts. A pi bin whose RR (DR for Davis-Peebles) is
+    empty in some redshift bin gives NaN there, in ``sample_xi()`` and in the sum of ``sample()``, as ``CorrFunc.sample()``
+    does: nothing is masked. ``to_dict`` / ``from_dict``, ``==`` and the bin and patch subsets go bin by bin through
+    ``CorrFunc``'s."""
+
+    __slots__ = ("pi_edges", "pi_bins")
+
+    def __init__(self, pi_edges, pi_bins) -> None:
+        edges = np.array(pi_edges, dtype=np.float64)
+        bins = tuple(pi_bins)
+        if edges.ndim != 1 or len(edges) != len(bins) + 1 or len(bins) < 1:
+            raise ValueError("'pi_edges' must hold one edge more than there are pi bins, and there is at least one bin")
+        if edges[0] != 0.0 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0):
+            raise ValueError("'pi_edges' must start at 0, be finite and ascend strictly")
+        for cf in bins:
+            if type(cf) is not CorrFunc:
+                raise TypeError(f"the pi bins must be of type {CorrFunc}")
+            bins[0].is_compatible(cf, require=True)
+            if cf.to_dict().keys() != bins[0].to_dict().keys():
+                raise ValueError("the pi bins must hold the same kinds of pair counts")
+        edges.setflags(write=False)
+        self.pi_edges = edges
+        self.pi_bins = bins
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(num_pi={self.num_pi}, pi_max={self.pi_edges[-1]}, pi_bins[0]={self.pi_bins[0]!r})"
+
+    binning = property(lambda self: self.pi_bins[0].binning)
+    auto = property(lambda self: self.pi_bins[0].auto)
+    num_patches = property(lambda self: self.pi_bins[0].num_patches)
+    num_bins = property(lambda self: self.pi_bins[0].num_bins)
+    num_pi = property(lambda self: len(self.pi_bins))
+
+    def to_dict(self) -> dict:
+        return dict(pi_edges=self.pi_edges.copy(), pi_bins=[cf.to_dict() for cf in self.pi_bins])
+
+    @classmethod
+    def from_dict(cls, state: dict):
+        return cls(state["pi_edges"], [CorrFunc.from_dict(counts) for counts in state["pi_bins"]])
+
+    def __eq__(self, other) -> bool:
+        if type(self) is not type(other):
+            return NotImplemented
+        return np.array_equal(self.pi_edges, other.pi_edges) and self.pi_bins == other.pi_bins
+
+    def is_compatible(self, other, *, require: bool = False) -> bool:
+        if type(self) is not type(other):
+            if require:
+                raise TypeError(f"{type(other)} is not compatible with {type(self)}")
+            return False
+        if not np.array_equal(self.pi_edges, other.pi_edges):
+            if require:
+                raise ValueError("the pi edges differ")
+            return False
+        return self.pi_bins[0].is_compatible(other.pi_bins[0], require=require)
+
+    def sample_xi(self) -> list:
+        """``xi(r_p, pi_j)`` per pi bin: ``CorrFunc.sample()`` of each, Landy-Szalay or (without RR) Davis-Peebles, for the
+        data and every jackknife sample."""
+        return [cf.sample() for cf in self.pi_bins]
+
+    def sample(self) -> CorrData:
+        """``w_p = 2 sum_j dpi_j xi_j``, summed in the order of the pi bins for the data and for each jackknife sample
+        separately; errors and covariance are those of the summed samples."""
+        data, samples = 0.0, 0.0
+        for dpi, xi in zip(np.diff(self.pi_edges), self.sample_xi()):
+            data, samples = data + dpi * xi.data, samples + dpi * xi.samples
+        return CorrData(self.binning, 2.0 * data, 2.0 * samples)
+
+    def cylinder(self) -> CorrFunc:
+        """The single-cylinder measurement ``|pi| <= pi_edges[-1]``: the ``CorrFunc`` over the counts summed over the pi bins
+        (in their order), on the bins' one normalisation -- what ``autocorrelate_projected(pi_bins=None)`` counts."""
+        summed = {}
+        for kind, first in self.pi_bins[0].to_dict().items():
+            counts = first.counts
+            for cf in self.pi_bins[1:]:
+                counts = counts + cf.to_dict()[kind].counts
+            summed[kind] = NormalisedCounts(counts, first.sum_weights)
+        return CorrFunc.from_dict(summed)
+
+    def bins_subset(self, item):
+        return type(self)(self.pi_edges, [cf.bins_subset(item) for cf in self.pi_bins])
+
+    def patches_subset(self, item):
+        return type(self)(self.pi_edges, [cf.patches_subset(item) for cf in self.pi_bins])

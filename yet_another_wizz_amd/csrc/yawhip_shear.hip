@@ -7,10 +7,11 @@
 // measurements.crosscorrelate_delta_sigma), those binned in each lens's own radius instead of one angle
 // per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers), and the projected
 // pair counts of objects with a transverse distance and a line-of-sight coordinate, binned in each PAIR's own radius inside a
-// line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected). include/yawhip.h
-// has the contracts, product by product.
+// line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected), and those binned in the
+// line-of-sight separation besides (yawhip_proj_count_pi; autocorrelate_projected(pi_bins=...)).
+// include/yawhip.h has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under six thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under seven thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -42,6 +43,8 @@
 // Projected (k_count_projected) is ShearPair's cell table, window rule and diagonal cells over two projected handles with a
 // 48-byte streamed object (x, y, z, d | w, c) and ONE plane: the ballot holds DD s2, DD = (0.5 (d_a + d_b))^2, against the
 // row's last squared radius, the pair is binned by R2 = DD th2(s2) and adds w_a w_b iff |c_a - c_b| <= pmax (at the policy).
+// ProjectedPi (k_count_projected_pi) is Projected with the call's n_pi planes instead of one: the pi edges are staged into
+// LDS next to the thresholds, and behind the ballot p = |c_a - c_b| is bisected over them as R2 is over the row.
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -107,8 +110,8 @@ struct alignas(16) ObjP {
 };
 
 // What a lane keeps of its own object in registers (g1, g2: the weighted shear -- of a lens or projected handle its two raw
-// columns; u: what the policy's lane_u() gives: DeltaSigma's column, Projected's pmax, else 0). Not every policy uses every
-// member (Projected: not rho2); what a kernel does not read the compiler drops.
+// columns; u: what the policy's lane_u() gives: DeltaSigma's column, Projected's pmax and ProjectedPi's last edge, else 0).
+// Not every policy uses every member (Projected: not rho2); what a kernel does not read the compiler drops.
 struct Lane {
     double x, y, z, w, g1, g2, rho2, u;
 };
@@ -378,6 +381,51 @@ struct Projected : ShearPair {
     }
 };
 
+// The lanes of the pi-binned projected count: a projected handle and the call's pi edges pe[n_pi + 1] (device memory; the
+// workgroup stages them into LDS once) in the place of pmax; the last of them, pe[n_pi], comes by value besides and
+// reaches the pair term as the lane's u, as Projected's pmax does.
+struct ProjPiLanes : ShearView {
+    const double *pe;
+    int n_pi;
+    double pmax;
+};
+
+// the LDS slots of the pi edges of n_pi planes: an even number, as the thresholds take (lds_bytes and the walk's carve-up)
+constexpr int pi_slots(int n_pi) { return (n_pi + 2) & ~1; }
+
+// Projected binned in the line-of-sight separation besides (k_count_projected_pi): object, lane, outer,
+// binned, window and diagonal rule are Projected's; the planes are the call's n_pi (PLANES == 0 tells the walk and the host
+// to ask the lanes' view), [n_pi][nf] per wave. With p = |c_a - c_b| and j the number of edges pe[1 .. n_pi] below p -- plane 0
+// is [0, pe[1]], plane j is (pe[j], pe[j + 1]], pe[0] == 0 is never read -- the pair adds w_a w_b to plane j iff j < n_pi
+// (p <= pe[n_pi]: over the planes, exactly the pairs Projected keeps at pmax = pe[n_pi]). The pair term asks that first,
+// against the lane's u as Projected does, and bisects only the inner edges pe[1 .. n_pi - 1] for the pairs that count:
+// behind the ballot most pairs are in range of the radius and beyond the line-of-sight cut (at one pi bin nothing is
+// bisected at all). The loop keeps ONE shape for both -- a start past the edges instead of a branch around it: the walk is
+// at the limit of its scalar registers, and a nested branch costs the exec masks that spill them. p is bit-symmetric, so a
+// diagonal cell walks the larger indices only, as Projected's.
+struct ProjectedPi : Projected {
+    using Lanes = ProjPiLanes;
+    static constexpr int PLANES = 0;  // the call's: planes()
+    static __device__ __forceinline__ int planes(const ProjPiLanes &src) { return src.n_pi; }
+    static __device__ __forceinline__ int extra_slots(const ProjPiLanes &src) { return pi_slots(src.n_pi); }
+    static __device__ __forceinline__ void stage_extra(const ProjPiLanes &src, double *ext, int tid) {
+        for (int j = tid; j <= src.n_pi; j += WG) ext[j] = src.pe[j];
+    }
+    static __device__ double lane_u(const ProjPiLanes &src, int64_t, bool) { return src.pmax; }  // call-wide: a scalar register
+    // pe: the staged edges in LDS
+    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int n_pi) {
+        const double p = fabs(a.g2 - b.c);
+        // the inner edges pe[1 .. n_pi - 1] below p (they ascend), by bisection; a pair beyond pe[n_pi] -- the lane's u, as
+        // Projected's pmax; most pairs behind the ballot -- starts past them and bisects nothing
+        int j = a.u < p ? n_pi : 0, hi = n_pi - 1;
+        while (j < hi) {
+            const int mid = (j + hi) >> 1;
+            if (pe[mid + 1] < p) j = mid + 1; else hi = mid;
+        }
+        if (j < n_pi) atomicAdd(&wh[j * nf + e], a.w * b.w);
+    }
+};
+
 // The separations of a diagonal cell's lane tile [ta, t_last] against the streamed objects [b0, b1), b0 > ta, that the index
 // test can keep -- the streamed index larger than the lane's: what a policy with KEPT_WORK reports as evaluated, so that a
 // cell's figure never exceeds its unordered pairs. (The waves evaluate the others of the tile's own range too, and drop them.)
@@ -392,16 +440,29 @@ __device__ __forceinline__ unsigned long long kept_work(int64_t ta, int64_t t_la
     return kept;
 }
 
-// dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk)
+// dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk);
+// a policy with the call's planes (PLANES == 0) has n_pi of them and its pi edges between the thresholds and the histograms
 template <class P>
-constexpr size_t lds_bytes(int n_edges) {
-    return 2 * STAGE * sizeof(typename P::Streamed) + (size_t)((n_edges + 1) & ~1) * sizeof(double) +
-           (size_t)WAVES * P::PLANES * (n_edges - 1) * sizeof(double);
+constexpr size_t lds_bytes(int n_edges, int n_pi = 0) {
+    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)n_pi, extra = P::PLANES ? 0 : (size_t)pi_slots(n_pi);
+    return 2 * STAGE * sizeof(typename P::Streamed) + ((size_t)((n_edges + 1) & ~1) + extra) * sizeof(double) +
+           (size_t)WAVES * planes * (n_edges - 1) * sizeof(double);
 }
-static_assert(lds_bytes<Tangential>(MAX_EDGES) <= 64 * 1024 && lds_bytes<ShearShear>(MAX_EDGES) <= 64 * 1024 &&
-                  lds_bytes<ShearPair>(MAX_EDGES) <= 64 * 1024 && lds_bytes<DeltaSigma>(MAX_EDGES) <= 64 * 1024 &&
-                  lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= 64 * 1024 &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
-                  lds_bytes<Projected>(MAX_EDGES) <= 64 * 1024,  // (34 784: 2 * 256 * 48 + 2048 + 4 * 1 * 255 * 8)
+constexpr size_t LDS_LIMIT = 64 * 1024;  // of dynamic LDS per workgroup, without asking for more
+
+// the largest n_pi of ProjectedPi whose carve-up fits LDS_LIMIT at n_edges: 0 if not even one plane does
+constexpr int max_pi_planes(int n_edges) {
+    int n = 0;
+    while (lds_bytes<ProjectedPi>(n_edges, n + 1) <= LDS_LIMIT) ++n;
+    return n;
+}
+static_assert(max_pi_planes(MAX_EDGES) == 4 && max_pi_planes(13) == 104 && max_pi_planes(2) == 1023,
+              "ProjectedPi: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 22 quote it)");
+static_assert(lds_bytes<Tangential>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<ShearShear>(MAX_EDGES) <= LDS_LIMIT &&
+                  lds_bytes<ShearPair>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<DeltaSigma>(MAX_EDGES) <= LDS_LIMIT &&
+                  lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= LDS_LIMIT &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
+                  lds_bytes<Projected>(MAX_EDGES) <= LDS_LIMIT &&  // (34 784: 2 * 256 * 48 + 2048 + 4 * 1 * 255 * 8)
+                  lds_bytes<ProjectedPi>(MAX_EDGES, 1) <= LDS_LIMIT,  // (34 800: 16 more for pe[2]; yawhip_proj_count_pi caps n_pi)
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
 
 __global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
@@ -434,18 +495,24 @@ __global__ void k_gather_column(int64_t n, const uint32_t *__restrict__ perm, co
 
 // The walk of one cell = one workgroup. str: the streamed side, src: the side in the lanes; `table` and n_bins are the policy's
 // (P::cell); t: [rows][n_edges], rwin: [rows].
-// out: [PLANES][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
+// out: [planes][n_cells][E-1], every element written; evaluated: [n_cells] separations the cell's workgroup evaluated (on a
 // diagonal cell that includes the few of a tile's first stage that the index test then drops, unless the policy has KEPT_WORK)
 template <class P>
 __device__ __forceinline__ void shear_walk(const typename P::View &str, const typename P::Lanes &src, const int32_t *__restrict__ table,
                                            int n_bins, int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
                                            int64_t n_cells, double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     using O = typename P::Streamed;
-    constexpr int NP = P::PLANES;
+    constexpr bool CALL_PLANES = P::PLANES == 0;  // the planes are the call's, and the policy stages what its pair term bisects
+    int NP = P::PLANES;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     O *stage = reinterpret_cast<O *>(lds_raw);                                  // [2][STAGE]
     double *thr = reinterpret_cast<double *>(lds_raw + 2 * STAGE * sizeof(O));  // [n_edges]
     double *hist = thr + ((n_edges + 1) & ~1);                                  // [WAVES][NP][nf]
+    double *const ext = hist;                                                   // (CALL_PLANES: [P::extra_slots], then hist)
+    if constexpr (CALL_PLANES) {
+        NP = P::planes(src);
+        hist += P::extra_slots(src);
+    }
 
     const int tid = threadIdx.x;
     const int nf = n_edges - 1;
@@ -457,6 +524,7 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
     const int64_t a_beg = src.off[c.lseg], a_end = src.off[c.lseg + 1];  // in lanes
 
     for (int e = tid; e < n_edges; e += WG) thr[e] = t[(int64_t)k * n_edges + e];
+    if constexpr (CALL_PLANES) P::stage_extra(src, ext, tid);
     for (int j = tid; j < WAVES * NP * nf; j += WG) hist[j] = 0.0;
     const double tmax = t[(int64_t)k * n_edges + n_edges - 1];
     const double rw = rwin[k];
@@ -543,7 +611,10 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
                         }
                         // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the counts binned in a radius -- has cnt == n_edges and no bin:
                         // the histogram has nf of them), and not the lower half of a diagonal cell
-                        if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) P::add(a, b, wh, cnt - 1, nf);
+                        if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) {
+                            if constexpr (CALL_PLANES) P::add(a, b, wh, cnt - 1, nf, ext, NP);
+                            else P::add(a, b, wh, cnt - 1, nf);
+                        }
                     }
                 }
             }
@@ -608,6 +679,14 @@ __global__ __launch_bounds__(WG) void k_count_projected(ShearView a, ProjLanes b
                                                         int64_t n_cells, double *__restrict__ out,
                                                         unsigned long long *__restrict__ evaluated) {
     shear_walk<Projected>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
+// out: [n_pi][n_cells][E-1] (W per pi bin); as k_count_projected, b with the call's pi edges in the place of pmax
+__global__ __launch_bounds__(WG) void k_count_projected_pi(ShearView a, ProjPiLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                           const double *__restrict__ r2, const double *__restrict__ rwin,
+                                                           int64_t n_cells, double *__restrict__ out,
+                                                           unsigned long long *__restrict__ evaluated) {
+    shear_walk<ProjectedPi>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -832,10 +911,11 @@ ShearView view_of(const yawhip_shear_sources *s) {
 // the stream between the context's two events: one workgroup per cell, the policy's LDS. The kernel writes the result block
 // in d_out (P::PLANES planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[], the
 // counters and the event time to the statistics. n_rows: the rows of t; reach[k]: the largest squared chord of a pair in
-// range of row k where the row's last edge is not that (chord_reach), or NULL.
+// range of row k where the row's last edge is not that (chord_reach), or NULL. A policy with the call's planes (PLANES == 0)
+// has n_pi of them, contiguous in fine[0], and its edges pe[n_pi + 1] travel in d_in between the half widths and the table.
 struct Slots {  // what run_count has on the device for the kernel
     const int32_t *table;
-    const double *t, *rwin;
+    const double *t, *rwin, *pe;
     int64_t n_cells;
     double *out;
     unsigned long long *evaluated;
@@ -844,11 +924,12 @@ struct Slots {  // what run_count has on the device for the kernel
 template <class P, class Pass>
 int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, size_t n_table, const int32_t *table, size_t n_cells,
               int32_t n_rows, int32_t n_edges, const double *t, const double *reach, double *const *fine, int64_t candidates,
-              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Pass pass) {
+              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Pass pass, int32_t n_pi = 0, const double *pe = nullptr) {
     if (stats) *stats = yawhip_stats{};
     if (n_cells == 0) return YAWHIP_OK;
-    const size_t n_t = (size_t)n_rows * n_edges, in_bytes = (n_t + (size_t)n_rows) * sizeof(double) + n_table * sizeof(int32_t);
-    const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = (size_t)P::PLANES * plane;
+    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)n_pi, n_pe = pe ? (size_t)n_pi + 1 : 0;
+    const size_t n_t = (size_t)n_rows * n_edges, in_bytes = (n_t + (size_t)n_rows + n_pe) * sizeof(double) + n_table * sizeof(int32_t);
+    const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = planes * plane;
     std::vector<unsigned char> h_in;
     std::vector<unsigned long long> h_eval;
     try {
@@ -863,7 +944,8 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, si
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
     for (int k = 0; k < n_rows; ++k)
         h_rwin[k] = std::sqrt(reach ? reach[k] : t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-    memcpy(h_rwin + n_rows, table, n_table * sizeof(int32_t));
+    if (n_pe) memcpy(h_rwin + n_rows, pe, n_pe * sizeof(double));
+    memcpy(h_rwin + n_rows + n_pe, table, n_table * sizeof(int32_t));
 
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
@@ -872,16 +954,18 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, si
     // (pageable memory: the copy has left h_in when the call returns)
     HIP_TRY(hipMemcpyAsync(buffers->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const double *d_t = reinterpret_cast<const double *>((unsigned char *)buffers->d_in.ptr), *d_rwin = d_t + n_t;
-    const int32_t *d_table = reinterpret_cast<const int32_t *>(d_rwin + n_rows);
+    const double *d_pe = d_rwin + n_rows;
+    const int32_t *d_table = reinterpret_cast<const int32_t *>(d_pe + n_pe);
     double *d_out = buffers->d_out.ptr;
     unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     pass([&](auto kernel, auto... arguments) {
-             hipLaunchKernelGGL(kernel, dim3((unsigned)n_cells), dim3(WG), lds_bytes<P>(n_edges), ctx->stream, arguments...);
+             hipLaunchKernelGGL(kernel, dim3((unsigned)n_cells), dim3(WG), lds_bytes<P>(n_edges, n_pi), ctx->stream, arguments...);
          },
-         Slots{d_table, d_t, d_rwin, (int64_t)n_cells, d_out, d_eval});
+         Slots{d_table, d_t, d_rwin, d_pe, (int64_t)n_cells, d_out, d_eval});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    if (P::PLANES == 0) HIP_TRY(hipMemcpyAsync(fine[0], d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     for (int c = 0; c < P::PLANES; ++c)
         HIP_TRY(hipMemcpyAsync(fine[c], d_out + (size_t)c * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (stats) HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -907,6 +991,36 @@ int check_dsigma(const char *fn, yawhip_ctx *ctx, const yawhip_shear_sources *le
         return rc;  // (a column m is ignored)
     if (const int rc = require_kind(fn, sources, DSIGMA_SOURCES, "the sources are not a handle of yawhip_dsigma_upload_sources")) return rc;
     return check_jobs(fn, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, candidates);
+}
+
+// What the two projected counts check once their own arguments passed, and in this order: the cells' segments, rows and diagonal
+// marks, then the reach of every row (reach: [n_rows] out, for run_count). The scale of a pair is DD, D = fl(0.5 (d_a + d_b))
+// no less than the smaller of the two (rounding is monotone), which is no less than the least d of the bins that the row's
+// cells pair. A row without cells, or with an empty bin on either side, has no pairs.
+int check_proj_cells(const char *fn, const yawhip_shear_sources *a, const yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                     int32_t n_rows, int32_t n_edges, const double *r2, std::vector<double> &reach, int64_t *candidates) {
+    if (const int rc = check_cells(fn, a, b, n_rows, n_edges, r2)) return rc;
+    const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
+    try {
+        reach.assign((size_t)n_rows, INFINITY);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    *candidates = 0;
+    for (int c = 0; c < n_cells; ++c) {
+        const int32_t *cell = cells + 4 * (size_t)c;
+        const int32_t sa = cell[0], sb = cell[1], row = cell[2];
+        if (sa < 0 || sa >= segs_a || sb < 0 || sb >= segs_b)
+            return fail(YAWHIP_ERR_INVALID, "cell %d has a segment outside [0,%lld) x [0,%lld)", c, (long long)segs_a, (long long)segs_b);
+        if (row < 0 || row >= n_rows) return fail(YAWHIP_ERR_INVALID, "cell %d has a row outside [0,%d)", c, n_rows);
+        if ((cell[3] != 0) != (a == b && sa == sb))
+            return fail(YAWHIP_ERR_INVALID, "cell %d: a cell is diagonal iff it pairs a segment of one handle with itself", c);
+        *candidates += segment_pairs(a, (size_t)sa, b, (size_t)sb);
+        const double d_a = a->least[(size_t)(sa % a->nb)], d_b = b->least[(size_t)(sb % b->nb)];
+        if (!std::isinf(d_a) && !std::isinf(d_b)) reach[(size_t)row] = std::min(reach[(size_t)row], std::min(d_a, d_b));
+    }
+    for (double &least_d : reach) least_d *= least_d;
+    return chord_reach(fn, "an object", "row", n_rows, n_edges, r2, reach);
 }
 
 }  // namespace
@@ -1097,39 +1211,43 @@ int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sou
     if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
     if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
     if (!(pmax >= 0.0)) return fail(YAWHIP_ERR_INVALID, "%s: pmax must be a number >= 0 (+inf: no line-of-sight cut)", fn);
-    if (const int rc = check_cells(fn, a, b, n_rows, n_edges, r2)) return rc;
-
-    // The scale of a pair is DD, D = fl(0.5 (d_a + d_b)) no less than the smaller of the two (rounding is monotone), which is
-    // no less than the least d of the bins that the row's cells pair. A row without cells, or with an empty bin on either
-    // side, has no pairs.
-    const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
     std::vector<double> reach;
-    try {
-        reach.assign((size_t)n_rows, INFINITY);
-    } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
     int64_t candidates = 0;
-    for (int c = 0; c < n_cells; ++c) {
-        const int32_t *cell = cells + 4 * (size_t)c;
-        const int32_t sa = cell[0], sb = cell[1], row = cell[2];
-        if (sa < 0 || sa >= segs_a || sb < 0 || sb >= segs_b)
-            return fail(YAWHIP_ERR_INVALID, "cell %d has a segment outside [0,%lld) x [0,%lld)", c, (long long)segs_a, (long long)segs_b);
-        if (row < 0 || row >= n_rows) return fail(YAWHIP_ERR_INVALID, "cell %d has a row outside [0,%d)", c, n_rows);
-        if ((cell[3] != 0) != (a == b && sa == sb))
-            return fail(YAWHIP_ERR_INVALID, "cell %d: a cell is diagonal iff it pairs a segment of one handle with itself", c);
-        candidates += segment_pairs(a, (size_t)sa, b, (size_t)sb);
-        const double d_a = a->least[(size_t)(sa % a->nb)], d_b = b->least[(size_t)(sb % b->nb)];
-        if (!std::isinf(d_a) && !std::isinf(d_b)) reach[(size_t)row] = std::min(reach[(size_t)row], std::min(d_a, d_b));
-    }
-    for (double &least_d : reach) least_d *= least_d;
-    if (const int rc = chord_reach(fn, "an object", "row", n_rows, n_edges, r2, reach)) return rc;
+    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
     double *const fine[] = {fine_w};
     return run_count<Projected>(fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), fine, candidates,
                                 wall0, stats, [&](auto go, const Slots &d) {
                                     go(k_count_projected, view_of(a), ProjLanes{view_of(b), pmax}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out,
                                        d.evaluated);
                                 });
+}
+
+int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                         int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine_w,
+                         yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_pi";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
+    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
+    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
+    if (n_pi < 1 || !pe) return fail(YAWHIP_ERR_INVALID, "%s: n_pi must be >= 1 and pe not NULL (n_pi=%d)", fn, n_pi);
+    if (pe[0] != 0.0) return fail(YAWHIP_ERR_INVALID, "%s: the first pi edge must be 0", fn);
+    for (int j = 1; j <= n_pi; ++j)  // (a NaN fails either comparison)
+        if (!(pe[j] > pe[j - 1]) || (j < n_pi && !std::isfinite(pe[j])))
+            return fail(YAWHIP_ERR_INVALID, "%s: the pi edges must be finite (the last may be +inf) and strictly ascending (edge %d)", fn, j);
+    if (n_pi > max_pi_planes(n_edges))
+        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
+                    n_pi, n_edges - 1, max_pi_planes(n_edges), n_edges);
+    std::vector<double> reach;
+    int64_t candidates = 0;
+    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
+    double *const fine[] = {fine_w};
+    return run_count<ProjectedPi>(
+        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), fine, candidates, wall0, stats,
+        [&](auto go, const Slots &d) {
+            go(k_count_projected_pi, view_of(a), ProjPiLanes{view_of(b), d.pe, n_pi, pe[n_pi]}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+        },
+        n_pi, pe);
 }
 
 }  // extern "C"

@@ -10,11 +10,12 @@ from __future__ import annotations
 import numpy as np
 
 import os
+import re
 
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "count_projected_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "count_projected_fine", "count_projected_pi_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -406,16 +407,37 @@ def check_pi_max(pi_max) -> float:
     return pi_max
 
 
-def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, unit, sort_axis: int = 2):
-    """Fine-bin projected pair counts for ``cells`` (int[n, 4] = ``(segment of layout_a, segment of layout_b, row of r2,
-    diagonal)``, a segment ``patch * num_bins + bin``; ``diagonal`` non-zero iff the cell pairs a segment with itself, which
-    takes ``layout_b is layout_a``) -> ``(W, CountStats)``, W f64[n_cells, E-1]: the sums of ``w_a w_b`` over the pairs
-    with ``|chi_a - chi_b| <= pi_max`` in the fine bin that holds ``R^2 = (0.5 (d_a + d_b))^2 theta^2``, a diagonal cell
-    holding every unordered pair once (``yawhip_proj_count``; ``proj_columns`` makes the columns, ``r2`` f64[n_rows, E] are
-    squared radius edges in Mpc^2). Both are layouts with redshifts; each reaches the device once as a ``_lib.ProjHandle``
-    kept on the layout per context, sort axis, cosmology and kind of unit; the same layout twice is ONE handle passed
-    twice. A reach beyond the library's cap is ``check_radial_reach``'s ``ValueError`` with the object's redshift. No CPU
-    fallback; the CPU tests replace this function."""
+def check_pi_edges(pi_bins, pi_max) -> np.ndarray:
+    """The line-of-sight bin edges f64[n_pi + 1] of a pi-binned projected count from ``pi_bins``: an int ``n >= 1`` gives
+    ``np.linspace(0.0, pi_max, n + 1)``; a sequence of edges must start at 0, ascend strictly, be finite and end at ``pi_max``
+    (``ValueError`` otherwise)."""
+    pi_max = check_pi_max(pi_max)
+    if isinstance(pi_bins, (bool, np.bool_)):
+        raise ValueError("pi_bins must be a number of bins >= 1 or a sequence of edges")
+    if isinstance(pi_bins, (int, np.integer)):
+        if pi_bins < 1:
+            raise ValueError(f"pi_bins must be >= 1, not {pi_bins}")
+        return np.linspace(0.0, pi_max, int(pi_bins) + 1)
+    try:
+        edges = np.array(pi_bins, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+        raise ValueError("pi_bins must be a number of bins >= 1 or a sequence of edges") from err
+    if edges.ndim != 1 or len(edges) < 2:
+        raise ValueError("pi_bins as edges must be a sequence of at least two numbers")
+    if not np.all(np.isfinite(edges)):
+        raise ValueError("the pi edges must be finite")
+    if edges[0] != 0.0:
+        raise ValueError(f"the pi edges must start at 0, not {edges[0]}")
+    if not np.all(np.diff(edges) > 0.0):
+        raise ValueError("the pi edges must ascend strictly")
+    if edges[-1] != pi_max:
+        raise ValueError(f"the pi edges must end at pi_max = {pi_max}, not {edges[-1]}")
+    return edges
+
+
+def _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis):
+    """The context and the two resident ``_lib.ProjHandle`` of a projected count (role "projected <kind of unit>"): the same
+    layout twice is ONE handle passed twice."""
     ctx = get_context()
     role = f"projected {radial_kind(unit)}"
 
@@ -428,7 +450,40 @@ def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, un
         return _handle(layout, ctx, sort_axis, role, upload, cosmology)
 
     a = handle(layout_a)
-    b = a if layout_b is layout_a else handle(layout_b)
+    return ctx, a, a if layout_b is layout_a else handle(layout_b)
+
+
+def count_projected_pi_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
+    """``count_projected_fine`` with the pairs binned in ``|chi_a - chi_b|`` by ``pi_edges`` f64[n_pi + 1]
+    (``check_pi_edges``; bin 0 is ``[0, pe[1]]``, bin j ``(pe[j], pe[j + 1]]``) -> ``(W, CountStats)``, W f64[n_pi, n_cells,
+    E-1] (``yawhip_proj_count_pi``). Handles, their role and the reach translation are ``count_projected_fine``'s. More pi
+    bins than a workgroup's LDS holds at this number of radius edges is a ``ValueError`` that states the cap; the library
+    does not split a call and neither does this. No CPU fallback; the CPU tests replace this function."""
+    ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
+    try:
+        return _lib.proj_count_pi(ctx, a, b, cells, r2, pi_edges)
+    except _lib.YawhipError as err:
+        if "do not fit the LDS" in str(err):
+            cap = re.search(r"at most (\d+) pi bins", str(err)).group(1)
+            raise ValueError(f"{len(pi_edges) - 1} pi bins are too many for {np.shape(r2)[1]} radius edges (the fine bins of the "
+                             f"configuration's resolution): at most {cap} pi bins fit; use fewer pi bins or a lower resolution") from err
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
+        raise
+
+
+def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, unit, sort_axis: int = 2):
+    """Fine-bin projected pair counts for ``cells`` (int[n, 4] = ``(segment of layout_a, segment of layout_b, row of r2,
+    diagonal)``, a segment ``patch * num_bins + bin``; ``diagonal`` non-zero iff the cell pairs a segment with itself, which
+    takes ``layout_b is layout_a``) -> ``(W, CountStats)``, W f64[n_cells, E-1]: the sums of ``w_a w_b`` over the pairs
+    with ``|chi_a - chi_b| <= pi_max`` in the fine bin that holds ``R^2 = (0.5 (d_a + d_b))^2 theta^2``, a diagonal cell
+    holding every unordered pair once (``yawhip_proj_count``; ``proj_columns`` makes the columns, ``r2`` f64[n_rows, E] are
+    squared radius edges in Mpc^2). Both are layouts with redshifts; each reaches the device once as a ``_lib.ProjHandle``
+    kept on the layout per context, sort axis, cosmology and kind of unit; the same layout twice is ONE handle passed
+    twice. A reach beyond the library's cap is ``check_radial_reach``'s ``ValueError`` with the object's redshift. No CPU
+    fallback; the CPU tests replace this function."""
+    ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
     try:
         return _lib.proj_count(ctx, a, b, cells, r2, pi_max)
     except _lib.YawhipError as err:

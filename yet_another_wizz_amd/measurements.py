@@ -21,7 +21,7 @@ from . import _lib, engine, parallel
 from .angular_bins import plan_for_limits, radial_plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
-from .corrfunc import CorrFunc, ScalarCorrFunc
+from .corrfunc import CorrFunc, ProjectedCorrFunc, ScalarCorrFunc
 from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
@@ -646,7 +646,7 @@ class PatchLinkage:
                 for s in range(num_scales)]
 
     def count_projected_pairs(self, main_catalog: Catalog, second_catalog: Catalog | None = None, *, pi_max: float, progress: bool = False,
-                              max_workers: int | None = None, count_type_info: str | None = None) -> list:
+                              max_workers: int | None = None, count_type_info: str | None = None, pi_bins=None) -> list:
         """Pair counts of one (auto) or two catalogues with every pair binned in its OWN transverse radius
         ``R = (d_a + d_b) / 2 * theta`` (physical or comoving, as the unit of the scales says) and kept only if its
         line-of-sight separation ``|chi_a - chi_b|`` is at most ``pi_max`` (a comoving length in Mpc) -> one
@@ -658,10 +658,17 @@ class PatchLinkage:
         normalisation is ``count_pairs``' ``PatchedSumWeights``. The linkage must reach as far as the nearest object sees the
         largest radius (``from_catalogs(max_angle=radial_max_angle(...))``). ONE library call counts all cells
         (``engine.count_projected_fine``), on one device of one process: several ranks raise ``NotImplementedError``
-        (``max_workers`` is accepted and has no effect)."""
+        (``max_workers`` is accepted and has no effect).
+
+        ``pi_bins`` (``engine.check_pi_edges``: a number of equal bins up to ``pi_max``, or their edges from 0 to ``pi_max``)
+        bins the kept pairs in ``|chi_a - chi_b|`` besides, bin 0 ``[0, pe[1]]`` and bin j ``(pe[j], pe[j + 1]]``: the result
+        is then a list over scales of lists over pi bins of ``NormalisedCounts``, every plane recombined like the one of
+        ``pi_bins=None`` and all over ONE ``PatchedSumWeights``, still from one library call
+        (``engine.count_projected_pi_fine``)."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("projected counts run in one process on one device")
         pi_max = engine.check_pi_max(pi_max)
+        pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
         auto = second_catalog is None
 
         def layouts(num_bins):
@@ -677,15 +684,20 @@ class PatchLinkage:
                 seg2 = (jobs[:, 1:].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
                 diagonal = (seg1 == seg2) if auto else np.zeros(len(seg1), dtype=bool)
                 cells = np.column_stack([seg1, seg2, np.tile(np.arange(num_bins), len(jobs)), diagonal]).astype(np.int32).reshape(-1, 4)
-                fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, cosmology=self.config.cosmology,
-                                                          unit=self.config.scales.scales.unit, sort_axis=sort_axis)
+                kwargs = dict(cosmology=self.config.cosmology, unit=self.config.scales.scales.unit, sort_axis=sort_axis)
+                if pi_edges is not None:  # one plane per pi bin
+                    fine, stats = engine.count_projected_pi_fine(layout1, layout2, cells, r2, pi_edges=pi_edges, **kwargs)
+                    return (*np.asarray(fine, dtype=np.float64).reshape(len(pi_edges) - 1, len(jobs), num_bins, r2.shape[1] - 1), stats)
+                fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, **kwargs)
                 return np.asarray(fine, dtype=np.float64).reshape(len(jobs), num_bins, r2.shape[1] - 1), stats
 
             return count, (layout1, layout2)
 
         catalogs = (main_catalog,) if auto else (main_catalog, second_catalog)
-        binning, (layout1, layout2), (counts,) = self._count_shear_planes(catalogs, layouts, count_type_info, progress, radial=True)
-        return _normalised_counts(binning, counts, layout1, layout2, auto)
+        binning, (layout1, layout2), planes = self._count_shear_planes(catalogs, layouts, count_type_info, progress, radial=True)
+        if pi_edges is None:
+            return _normalised_counts(binning, planes[0], layout1, layout2, auto)
+        return [list(per_pi) for per_pi in zip(*_normalised_counts(binning, planes, layout1, layout2, auto))]
 
     def _count_shear_planes(self, catalogs, layouts, count_type_info, progress, radial: bool = False):
         """What the lensing and projected counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the
@@ -750,10 +762,15 @@ def _active_layout(catalog: Catalog, num_bins: int):
 
 def _normalised_counts(binning, counts, layout1, layout2, auto: bool) -> list:
     """The result tensor ``counts`` f64[S, B, P, P] of a pair count between two layouts as one ``NormalisedCounts`` per scale,
-    all over the one ``PatchedSumWeights`` of the layouts."""
+    all over the one ``PatchedSumWeights`` of the layouts. A list of such tensors (the planes of one count) gives a list of
+    such lists, over the same ``PatchedSumWeights``."""
     num_bins = len(binning)
     sum_weights = PatchedSumWeights(binning, layout1.sum_weights_for(num_bins), layout2.sum_weights_for(num_bins), auto=auto)
-    return [NormalisedCounts(PatchedCounts(binning, counts[s], auto=auto), sum_weights) for s in range(len(counts))]
+
+    def per_scale(tensor):
+        return [NormalisedCounts(PatchedCounts(binning, tensor[s], auto=auto), sum_weights) for s in range(len(tensor))]
+
+    return [per_scale(tensor) for tensor in counts] if isinstance(counts, list) else per_scale(counts)
 
 
 def _count_sides(layout1, layout2, mode):
@@ -799,7 +816,7 @@ def autocorrelate(config, data: Catalog, random: Catalog, *, count_rr: bool = Tr
 
 
 def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: float, count_rr: bool = True, progress: bool = False,
-                            max_workers: int | None = None) -> list:
+                            max_workers: int | None = None, pi_bins=None) -> list:
     """Projected clustering of ``data`` in each pair's own transverse radius: DD, DR and (optionally) RR of the pairs with a
     line-of-sight separation ``|chi_a - chi_b| <= pi_max``, binned by ``r_p = (d_a + d_b) / 2 * theta`` -> ``[CorrFunc(dd, dr,
     None, rr)]``, one per scale of the configuration (no counterpart in the reference).
@@ -808,6 +825,14 @@ def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: f
     cylinder ``|pi| <= pi_max`` in each radius bin, ``xi_bar``, with jackknife samples over the patches; the projected
     correlation function is ``w_p(r_p) = 2 * pi_max * xi_bar``. This is the single-cylinder estimator: the pairs are not
     binned in ``pi``, and ``xi(r_p, pi)`` is not integrated bin by bin.
+
+    ``pi_bins`` asks for that estimator instead: a number ``n >= 1`` of equal bins from 0 to ``pi_max``,
+    or their edges (from 0, strictly ascending, ending at ``pi_max``). DD, DR and RR are then binned in
+    ``pi = |chi_a - chi_b|`` besides -- bin 0 ``[0, pe[1]]``, bin j ``(pe[j], pe[j + 1]]`` -- and the result is
+    ``[ProjectedCorrFunc]``, one per scale: ``sample_xi()`` gives ``xi(r_p, pi_j)`` per pi bin, ``sample()`` the summed
+    ``w_p = 2 sum_j dpi_j xi_j`` with its jackknife samples, ``cylinder()`` the single-cylinder ``CorrFunc`` of
+    ``pi_bins=None``. The number of pi bins times the fine radius bins of the configuration's resolution is capped by the
+    device's LDS (104 pi bins at 12 fine bins); beyond the cap the call is a ``ValueError`` that states it.
 
     The scales are transverse radii in a physical (``kpc``, ``Mpc``: ``d = D_A(z)``) or comoving (``kpc/h``, ``Mpc/h``:
     ``d = D_A(z) (1 + z)``) unit; an angular unit is a ``ValueError``. ``pi_max`` is a comoving length in the Mpc the scales
@@ -823,6 +848,7 @@ def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: f
     if parallel.world()[1] > 1:
         raise NotImplementedError("projected counts run in one process on one device")
     pi_max = engine.check_pi_max(pi_max)
+    pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
     unit = config.scales.scales.unit
     engine.radial_kind(unit)  # angular units have no radius: ValueError
     edges, closed = config.binning.edges, config.binning.closed
@@ -834,11 +860,14 @@ def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: f
         engine.check_proj_redshifts(layout)
     _log_info("computing projected auto-correlation from DD, DR" + (", RR" if count_rr else ""))
     links = PatchLinkage.from_catalogs(config, data, random, max_angle=radial_max_angle(config, data_layout, random_layout))
-    kwargs = dict(pi_max=pi_max, progress=progress, max_workers=max_workers)
+    kwargs = dict(pi_max=pi_max, progress=progress, max_workers=max_workers, pi_bins=pi_edges)
     DD = links.count_projected_pairs(data, count_type_info="DD", **kwargs)
     DR = links.count_projected_pairs(data, random, count_type_info="DR", **kwargs)
     RR = links.count_projected_pairs(random, count_type_info="RR", **kwargs) if count_rr else [None] * len(DD)
-    return [CorrFunc(dd, dr, None, rr) for dd, dr, rr in zip(DD, DR, RR)]
+    if pi_edges is None:
+        return [CorrFunc(dd, dr, None, rr) for dd, dr, rr in zip(DD, DR, RR)]
+    return [ProjectedCorrFunc(pi_edges, [CorrFunc(dd_j, dr_j, None, None if rr is None else rr[j]) for j, (dd_j, dr_j) in enumerate(zip(dd, dr))])
+            for dd, dr, rr in zip(DD, DR, RR)]
 
 
 def crosscorrelate(config, reference: Catalog, unknown: Catalog, *, ref_rand: Catalog | None = None,
