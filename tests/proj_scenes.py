@@ -48,17 +48,17 @@ def radius_edges(n_fine, n_rows):
     return np.array([(edges * (1.0 + 0.03 * k)) ** 2 for k in range(n_rows)])
 
 
-def cells_one_handle(nb):
+def cells_one_handle(nb, n_sites=len(SITES)):
     """Every diagonal cell, and the two patches of every site against each other in every bin; row = bin."""
-    n_patches = 2 * len(SITES)
+    n_patches = 2 * n_sites
     cells = [(p * nb + k, p * nb + k, k, 1) for p in range(n_patches) for k in range(nb)]
-    cells += [(2 * s * nb + k, (2 * s + 1) * nb + k, k, 0) for s in range(len(SITES)) for k in range(nb)]
+    cells += [(2 * s * nb + k, (2 * s + 1) * nb + k, k, 0) for s in range(n_sites) for k in range(nb)]
     return np.array(cells, dtype=np.int32)
 
 
-def cells_two_handles(nb):
+def cells_two_handles(nb, n_sites=len(SITES)):
     """Patch p of the first handle against the patches of the same site of the second, bin k with bin k; row = bin."""
-    cells = [(p * nb + k, q * nb + k, k, 0) for p in range(2 * len(SITES)) for q in (p, p ^ 1) for k in range(nb)]
+    cells = [(p * nb + k, q * nb + k, k, 0) for p in range(2 * n_sites) for q in (p, p ^ 1) for k in range(nb)]
     return np.array(cells, dtype=np.int32)
 
 

@@ -8,7 +8,13 @@ thresholds; handles without any object.
 
 The count in each lens's own radius (``dsigma_count_radial``, ``"radial"``) runs through the same cases on the same scene with
 ``m = f * f`` and squared radii made from the rows of ``thresholds`` at the median ``m``, against tests/dsigma_radial_oracle.py;
-besides, a redshift bin without any lens (``min_m = +inf``) under a last edge of 1e30."""
+besides, a redshift bin without any lens (``min_m = +inf``) under a last edge of 1e30.
+
+The two projected counts (``proj_count`` on one handle, ``"proj"``, and on two, ``"proj2"``; ``proj_count_pi`` on one handle,
+``"proj_pi"``: the branch of ``run_count`` on which the pi edges travel between the half widths and the cell table and ``n_pi``
+planes leave in one copy) run through the same cases on the positions of the two shear catalogues, with ``d`` taken from the
+lenses' ``f`` and a line-of-sight column ``c``, unit weights, and the cells of the pair count: against tests/proj_oracle.py and
+tests/proj_pi_oracle.py as exact integers. On one pair of handles the two entry points also alternate."""
 import functools
 
 import numpy as np
@@ -16,6 +22,9 @@ import pytest
 
 import dsigma_oracle
 import dsigma_radial_oracle
+import proj_exact
+import proj_oracle
+import proj_pi_oracle
 import shear_auto_oracle
 import shear_oracle
 import shear_pair_oracle
@@ -28,6 +37,8 @@ from yet_another_wizz_amd.catalog import radec_to_xyz
 pytestmark = pytest.mark.gpu
 P, NB, GRID_X, GRID_Y = 150, 2, 15, 10
 BOX_DEG = 2.0
+PROJ = ("proj", "proj2", "proj_pi")
+PROJ_PMAX = 100.0  # against c of 0 .. 300
 SMALL = np.array([(16, 16), (16, 17), (17, 16), (31, 16), (32, 32), (0, 149)], dtype=np.int32)  # six jobs for the empty handles
 
 
@@ -93,6 +104,35 @@ def scene():
     return cats
 
 
+@functools.lru_cache(maxsize=None)
+def proj_scene():
+    """The two shear catalogues as projected handles of unit weight: ``d`` from the lenses' ``f`` (315 .. 2080, repeated to the
+    length), ``c`` 0 .. 300; and the pi edges, the uneven set of tests/golden/proj_exact.npz scaled to ``PROJ_PMAX``."""
+    lens, _, cat, cat_b = scene()
+    rng = np.random.default_rng(20262)
+    out = []
+    for h, shift in ((cat, 0), (cat_b, 7)):
+        n = len(h["x"])
+        out.append(freeze_dict(dict(x=h["x"], y=h["y"], z=h["z"], w=None, d=np.roll(np.resize(lens["f"], n), shift), c=rng.uniform(0.0, 300.0, n),
+                                    nb=NB, off=h["off"])))
+    fx = proj_exact.fixture()
+    pe = fx["pi.uneven"] * (PROJ_PMAX / float(fx["pmax"]))
+    assert len(pe) >= 9 and pe[0] == 0.0 and pe[-1] == PROJ_PMAX
+    return out[0], out[1], freeze([pe])[0]
+
+
+def freeze_dict(cat):
+    freeze(cat.values())
+    return cat
+
+
+def proj_cells(one_handle):
+    """The cells of the pair count as those of the projected counts: ``(segment of a, segment of b, row, diagonal)``."""
+    p, q, ka, kb, row = pair_cells(one_handle).T
+    sa, sb = p * NB + ka, q * NB + kb
+    return np.ascontiguousarray(np.column_stack([sa, sb, row, (sa == sb) & one_handle]).astype(np.int32))
+
+
 def all_jobs():
     return np.array([(p, q) for p in range(P) for q in range(P)], dtype=np.int32)
 
@@ -144,15 +184,22 @@ class Count:
         self.lens, self.src, self.cat, self.cat_b = scene()
         if name == "radial":  # m = D_A^2 as the driver sends it for kpc and Mpc (engine.dsigma_radial_columns)
             self.lens = dict(self.lens, m=self.lens["f"] * self.lens["f"])
+        if name in PROJ:
+            self.pa, self.pb, self.pe = proj_scene()
+            if name != "proj2":
+                self.pb = self.pa
         self.t = self.rows()
 
     def rows(self, n_rows=NB):
         """The thresholds of the count: squared chords, or squared radii for the radial count."""
+        if self.name in PROJ:  # squared radii around the median D of a pair; the nearest object reaches 12 times as far in s2
+            return radii2(self.pa["d"] ** 2, n_rows)
         return radii2(self.lens["m"], n_rows) if self.name == "radial" else thresholds(n_rows)
 
     def full_list(self):
         return {"shear": all_jobs, "dsigma": all_jobs, "radial": all_jobs, "auto": auto_jobs, "pair": lambda: pair_cells(True),
-                "pair2": lambda: pair_cells(False)}[self.name]()
+                "pair2": lambda: pair_cells(False), "proj": lambda: proj_cells(True), "proj2": lambda: proj_cells(False),
+                "proj_pi": lambda: proj_cells(True)}[self.name]()
 
     def small_list(self):
         """The 6-entry call: the first four entries of the full list that hold pairs, and its first and last, which hold none."""
@@ -165,6 +212,10 @@ class Count:
         return len(entries) * (NB if self.name in ("shear", "dsigma", "radial", "auto") else 1)
 
     def upload(self, ctx, sort_axis=2):
+        if self.name in PROJ:
+            handles = tuple(_lib.ProjHandle(ctx, h["x"], h["y"], h["z"], h["w"], h["d"], h["c"], P, NB, h["off"], sort_axis=sort_axis)
+                            for h in ((self.pa,) if self.pb is self.pa else (self.pa, self.pb)))
+            return handles
         if self.name == "shear":
             return test_gpu_shear.upload(ctx, self.lens, self.src, sort_axis)
         if self.name in ("dsigma", "radial"):
@@ -179,6 +230,8 @@ class Count:
     def run(self, ctx, handles, entries, t=None, exchanged=False):
         """-> (planes..., stats); ``exchanged`` (pair2): the two handles in the other order, the cells transposed."""
         t = self.t if t is None else t
+        if self.name in PROJ:
+            return self.run_proj(ctx, handles, entries, self.name == "proj_pi", t)
         if self.name == "shear":
             return _lib.shear_count(ctx, *handles, entries, t)
         if self.name == "dsigma":
@@ -191,7 +244,20 @@ class Count:
             return _lib.shear_pair_count(ctx, handles[1], handles[0], np.ascontiguousarray(entries[:, [1, 0, 3, 2, 4]]), t)
         return _lib.shear_pair_count(ctx, handles[0], handles[-1], entries, t)
 
-    def oracle(self, entries):
+    def run_proj(self, ctx, handles, entries, planes, t=None):
+        """``proj_count`` -> (W[cells, nf], stats), or ``proj_count_pi`` -> (W[cells, n_pi, nf], stats): its planes per cell."""
+        t = self.t if t is None else t
+        if not planes:
+            return _lib.proj_count(ctx, handles[0], handles[-1], entries, t, PROJ_PMAX)
+        W, stats = _lib.proj_count_pi(ctx, handles[0], handles[-1], entries, t, self.pe)
+        assert W.shape == (len(self.pe) - 1, len(entries), t.shape[1] - 1)
+        return np.ascontiguousarray(W.transpose(1, 0, 2)), stats
+
+    def oracle(self, entries, planes=None):
+        if self.name in PROJ:
+            if self.name == "proj_pi" if planes is None else planes:
+                return (np.ascontiguousarray(proj_pi_oracle.proj_pi_cells(self.pa, self.pb, entries, self.t, self.pe)[2].transpose(1, 0, 2)),)
+            return (proj_oracle.proj_cells(self.pa, self.pb, entries, self.t, PROJ_PMAX)[2],)
         if self.name == "shear":
             return shear_oracle.shear_jobs(self.lens, self.src, entries, self.t)
         if self.name == "dsigma":
@@ -203,10 +269,13 @@ class Count:
         return shear_pair_oracle.shear_pair_cells(self.cat, self.cat if self.name == "pair" else self.cat_b, entries, self.t)
 
     def check(self, key, got, exp):
+        if self.name in PROJ:  # unit weights: the integer number of pairs, and +0.0 where there is none
+            assert len(got) == len(exp) == 1 and np.array_equal(got[0], exp[0]) and not np.any(np.signbit(got[0])), (key, np.abs(got[0] - exp[0]).sum())
+            return
         (test_gpu_shear if self.name in ("shear", "dsigma", "radial") else test_gpu_shear_auto).check_against_oracle(key, got, exp)
 
 
-COUNTS = ["shear", "dsigma", "radial", "auto", "pair", "pair2"]
+COUNTS = ["shear", "dsigma", "radial", "auto", "pair", "pair2", "proj", "proj2", "proj_pi"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -255,7 +324,9 @@ def test_full_list_matches_the_oracle(name, order):
 def test_a_handle_through_calls_that_grow_and_shrink(name):
     """A 6-entry call, the full list, the 6-entry call again on the same handles: the first and the third are the same bits,
     the middle one the bits of the same call on freshly uploaded handles. Between two handles of the pair count the full list
-    also runs with the handles exchanged (and again after it), so that the buffers of both have been the call's."""
+    also runs with the handles exchanged (and again after it), so that the buffers of both have been the call's. On the
+    handles of the projected count ``proj_count`` and ``proj_count_pi`` also take turns (few / full / few): the call's input and
+    result blocks are then laid out both ways in the same buffers, and every turn is the bits of that call on fresh handles."""
     count = Count(name)
     entries, few = count.full_list(), count.small_list()
     ctx = engine.get_context(0)
@@ -268,6 +339,8 @@ def test_a_handle_through_calls_that_grow_and_shrink(name):
             middle_exchanged = count.run(ctx, handles, entries, exchanged=True)[:-1]
             middle_again = count.run(ctx, handles, entries)[:-1]
             few_exchanged_again = count.run(ctx, handles, few, exchanged=True)[:-1]
+        if name in ("proj", "proj2"):  # the two entry points in turn: d_in and d_out laid out both ways, few / full / few
+            turns = [count.run_proj(ctx, handles, list_, planes)[0] for list_, planes in ((few, True), (entries, False), (entries, True), (few, False), (few, True))]
         third = count.run(ctx, handles, few)[:-1]
     finally:
         free(handles)
@@ -276,6 +349,18 @@ def test_a_handle_through_calls_that_grow_and_shrink(name):
         alone = count.run(ctx, fresh, entries)[:-1]
     finally:
         free(fresh)
+    if name in ("proj", "proj2"):  # every turn is the bits of the same call on fresh handles, and the oracle's integers
+        for list_ in (few, entries):
+            fresh = count.upload(ctx)
+            try:
+                planes_alone = count.run_proj(ctx, fresh, list_, True)[0]
+            finally:
+                free(fresh)
+            for turn in (turns[0], turns[4]) if list_ is few else (turns[2],):
+                assert np.array_equal(turn, planes_alone)
+            assert np.array_equal(planes_alone, count.oracle(list_, planes=True)[0]) and planes_alone.sum() > 0
+            assert np.array_equal(planes_alone.sum(axis=1), (first if list_ is few else alone)[0])  # the planes sum to the single cylinder
+        assert np.array_equal(turns[1], alone[0]) and np.array_equal(turns[3], first[0])
     exp_few = count.oracle(few)
     assert np.count_nonzero(exp_few[-1].reshape(len(few), -1).sum(axis=1)) == 4
     count.check(f"{name} 6 entries", first, exp_few)
@@ -337,7 +422,8 @@ def assert_nothing(key, result, n_cells):
 def test_handles_without_objects():
     """A handle uploaded with ``n = 0`` uploads, counts to all-zero planes with no pair evaluated, and is freed: as sources, as
     lenses (a catalogue handle, a lens handle and a radial lens handle), as the catalogue of the auto count and on either side
-    of the pair count. The radial count besides: lenses whose second redshift bin is empty in every patch."""
+    of the pair count. The radial count besides: lenses whose second redshift bin is empty in every patch. The two projected
+    counts: an empty handle as the first, as the second and as both."""
     lens, src, cat, _ = scene()
     no_lens, no_src, no_cat = empty_like(lens, NB), empty_like(src, 1), empty_like(cat, NB)
     t = thresholds()
@@ -411,3 +497,20 @@ def test_handles_without_objects():
     for ours, ref in zip(first, both):
         assert np.array_equal(ours[:, 0], ref[:, 0])
         assert np.all(ours[:, 1] == 0.0) and not np.any(np.signbit(ours[:, 1]))
+
+    # the projected counts: a handle with n == 0 on either side and on both, through both entry points
+    proj = Count("proj2")
+    no_proj = dict(empty_like(proj.pa, NB), w=None)
+    few = proj.small_list()
+    for first_, second_ in ((proj.pa, no_proj), (no_proj, proj.pb), (no_proj, no_proj)):
+        handles = tuple(_lib.ProjHandle(ctx, h["x"], h["y"], h["z"], h["w"], h["d"], h["c"], P, NB, h["off"]) for h in (first_, second_))
+        try:
+            key = f"proj {len(first_['x'])} with {len(second_['x'])} objects"
+            assert_nothing(key, _lib.proj_count(ctx, *handles, few, proj.t, PROJ_PMAX), len(few))
+            assert_nothing(key + ", pi", _lib.proj_count_pi(ctx, *handles, few, proj.t, proj.pe), len(few))
+            if first_ is second_:  # one empty handle with itself, its diagonal cells included
+                one = Count("proj").small_list()
+                assert np.any(one[:, 3] != 0)
+                assert_nothing(key + ", one handle", _lib.proj_count_pi(ctx, handles[0], handles[0], one, proj.t, proj.pe), len(one))
+        finally:
+            free(handles)

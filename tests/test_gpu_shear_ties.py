@@ -13,7 +13,11 @@ against the numpy oracles; unweighted ``W`` is the pair count of the shipped exa
 
 The count in each lens's own radius (``dsigma_count_radial``) runs on the same catalogues with a column ``m`` of three values a
 factor 4 apart mixed inside every run of ties, and squared radii whose last edge puts the reach of the NEAREST lenses at those
-three spacings: its window is the only one that does not come from the row's last edge."""
+three spacings: its window is the only one that does not come from the row's last edge.
+
+The two projected counts (``proj_count``, ``proj_count_pi``) run on the shear catalogues with ``d`` of three values a factor 2
+apart mixed inside every run of ties and ``c`` a multiple of 1/4 (``p`` is exact and falls ON pi edges), the reach of the nearest
+objects again at three spacings: exact integers against tests/proj_oracle.py and tests/proj_pi_oracle.py."""
 import functools
 
 import numpy as np
@@ -21,6 +25,8 @@ import pytest
 
 import dsigma_oracle
 import dsigma_radial_oracle
+import proj_oracle
+import proj_pi_oracle
 import shear_auto_oracle
 import shear_oracle
 import shear_pair_oracle
@@ -297,6 +303,76 @@ def test_pair_count_on_tied_keys(name, sort_axis):
         assert np.array_equal(ours[:2 * len(upper)].reshape(ref.shape), ref)
 
 
+# --------------------------------------------------------------------------- 2b. the two projected counts
+PROJ_D = 900.0 * np.array([1.0, 2.0, 4.0])  # the column d: three values a factor 2 apart
+PROJ_PMAX = 40.0
+PROJ_PI = np.linspace(0.0, PROJ_PMAX, 5)  # c is a multiple of 1/4: pairs fall ON the edges 10, 20, 30 and 40
+
+
+def proj_radii2():
+    """f64[2, 5]: squared radii from 1 arcmin at the nearest pairs to a last edge with ``sqrt(r2max) / min d`` = 3 ring spacings
+    x (1 -/+ 1e-9): the window, whose half width follows the least ``d`` of the bins a row pairs, ends on a run of ties."""
+    outer = np.array([3.0 * (1.0 - 1e-9), 3.0 * (1.0 + 1e-9)]) * RING_SPACING
+    return (PROJ_D[0] * np.array([np.geomspace(ARCMIN, edge, 5) for edge in outer])) ** 2
+
+
+def proj_columns(n):
+    """``(d, c)`` by index: ``d`` cycles through PROJ_D, a step further after every third object (rings that alternate with a
+    period of 3 inside a segment mix them too), ``c`` through the multiples of 1/4 below 120 in strides of a prime."""
+    index = np.arange(n)
+    return PROJ_D[(index + index // 3) % 3], ((index * 7919) % 480) * 0.25
+
+
+@functools.lru_cache(maxsize=None)
+def proj_scene(name):
+    """The shear catalogue of ``scene(name)`` as a projected handle of unit weight, and its cells: same-bin (diagonal and
+    ``p < q``) with the row of the bin, cross-bin in both orders with alternating rows."""
+    _, _, cat, n_patches = scene(name)
+    d, c = proj_columns(len(cat["x"]))
+    h = dict(x=cat["x"], y=cat["y"], z=cat["z"], w=None, d=d, c=c, nb=2, off=cat["off"])
+    for a, b in zip(h["off"][:-1], h["off"][1:]):
+        keys, run = np.unique(h["z"][a:b], return_inverse=True)
+        long_runs = [r for r in range(len(keys)) if np.count_nonzero(run == r) >= 12]
+        assert long_runs and all(len(np.unique(d[a:b][run == r])) == 3 for r in long_runs), name  # every run of ties mixes the three
+    jobs, upper, _ = job_lists(n_patches)
+    cells = [(p * 2 + k, q * 2 + k, k, p == q) for p, q in upper for k in (0, 1)] + [(p * 2, q * 2 + 1, (p + q) % 2, 0) for p, q in jobs]
+    cells = np.array(cells, dtype=np.int32)
+    out = (proj_oracle.proj_cells(h, h, cells, proj_radii2(), PROJ_PMAX)[2], proj_pi_oracle.proj_pi_cells(h, h, cells, proj_radii2(), PROJ_PI)[2])
+    for a in (d, c, cells) + out:
+        a.setflags(write=False)
+    return h, cells, out
+
+
+@pytest.mark.parametrize("sort_axis", AXES)
+@pytest.mark.parametrize("name", CATALOGUES)
+def test_projected_counts_on_tied_keys(name, sort_axis):
+    """The single cylinder and four pi planes, as exact integers; the planes sum to the cylinder."""
+    import test_gpu_projected
+
+    h, cells, (exp, exp_pi) = proj_scene(name)
+    r2 = proj_radii2()
+    live = exp.sum(axis=1) > 0
+    # (pixel centres are 6.9 arcmin apart and only pairs of the two nearer kinds reach that far: a thousand pairs, not more)
+    assert exp.sum() > 1000 and np.any(live[cells[:, 3] != 0]) and np.any(live & (cells[:, 0] % 2 != cells[:, 1] % 2))
+    assert np.all(exp_pi.sum(axis=(1, 2)) > 0) and np.array_equal(exp_pi.sum(axis=0), exp)
+    # what the nearest objects hold: with every d = 900 sent far away the counts fall
+    far_only = proj_oracle.proj_cells(dict(h, d=np.where(h["d"] == PROJ_D[0], 1e9, h["d"])), h, cells[:1], r2, PROJ_PMAX, same=True)[2]
+    assert far_only.sum() < exp[:1].sum()
+    on_an_edge = np.abs(h["c"][:300, None] - h["c"][None, :300])
+    assert np.any(on_an_edge == 10.0) and np.any(on_an_edge == PROJ_PMAX)
+    ctx = engine.get_context(0)
+    handle = test_gpu_projected.upload(ctx, h, sort_axis)
+    try:
+        W, stats = _lib.proj_count(ctx, handle, handle, cells, r2, PROJ_PMAX)
+        W_pi, stats_pi = _lib.proj_count_pi(ctx, handle, handle, cells, r2, PROJ_PI)
+    finally:
+        handle.free()
+    for st in (stats, stats_pi):
+        assert st.n_workgroups == len(cells) and 0 < st.evaluated_pairs <= st.candidate_pairs
+    assert np.array_equal(W, exp), (name, sort_axis, np.abs(W - exp).sum())
+    assert np.array_equal(W_pi, exp_pi), (name, sort_axis, np.abs(W_pi - exp_pi).sum())
+
+
 # --------------------------------------------------------------------------- 3. the diagonal on tied keys
 @pytest.mark.parametrize("name", ["ring", "one declination"])
 def test_diagonal_cells_hold_every_unordered_pair_once(name):
@@ -320,3 +396,16 @@ def test_diagonal_cells_hold_every_unordered_pair_once(name):
     test_gpu_shear_auto.check_against_oracle(f"split on {name}", got_split, exp_split)
     assert got_whole[3].sum() > 2000 and np.array_equal(got_whole[3][0], got_split[3].sum(axis=0))
     assert np.array_equal(got_whole[3], test_gpu_shear_auto.exact_pair_count(whole, [[0, 0]], t))
+    # the projected count: the diagonal cell is the oracle's, and half the segment against a bit-identical copy uploaded as a
+    # second handle (that one sees every pair twice, and every object with itself at R2 = 0, which no bin holds)
+    import test_gpu_projected
+
+    d, c = proj_columns(n)
+    proj = dict({k: columns[k] for k in "xyz"}, w=None, d=d, c=c, nb=1, off=np.array([0, n], dtype=np.int64))
+    copy = {key: (value.copy() if isinstance(value, np.ndarray) else value) for key, value in proj.items()}
+    r2 = proj_radii2()[1:]
+    assert r2[0, 0] > 0.0
+    once, _ = test_gpu_projected.count(proj, proj, test_gpu_projected.DIAGONAL, r2, PROJ_PMAX)
+    both, stats = test_gpu_projected.count(proj, copy, test_gpu_projected.ACROSS, r2, PROJ_PMAX)
+    assert stats.candidate_pairs == n * n and once.sum() > 300 and np.array_equal(both, 2.0 * once)
+    assert np.array_equal(once, proj_oracle.proj_cells(proj, proj, test_gpu_projected.DIAGONAL, r2, PROJ_PMAX)[2])

@@ -218,6 +218,80 @@ def test_the_driver_on_the_oracle_stand_in(stand_in, unit, count_rr):
     check_driver(unit, count_rr)
 
 
+# --------------------------------------------------------------------------- 4b. the linkage at wide angles
+WIDE_GRID, WIDE_STEP = 5, np.deg2rad(3.0)  # 25 patches of 3 x 3 degrees over a field of 15 degrees
+
+
+def wide_scenario():
+    """A nearby sample in ONE redshift bin: 300 objects and 400 randoms of unit weight over a field of 15 x 15 degrees around
+    dec 8 degrees, in 25 patches, at 0.0055 <= z < 0.02 with the nearest at z = 0.0055 (24 Mpc: the largest radius of 2 Mpc
+    spans 4.7 degrees there, a patch and a half, and 1.3 degrees at the far end)."""
+    rng = np.random.default_rng(31)
+    grid = (np.arange(WIDE_GRID) + 0.5) * WIDE_STEP
+    centers = np.array([(0.5 + x, np.deg2rad(0.5) + y) for y in grid for x in grid])
+    cats = []
+    for n in (300, 400):
+        ra = 0.5 + rng.uniform(0.0, WIDE_GRID * WIDE_STEP, n)
+        dec = np.deg2rad(0.5) + rng.uniform(0.0, WIDE_GRID * WIDE_STEP, n)
+        z = np.concatenate([[0.0055], rng.uniform(0.0055, 0.02, n - 1)])
+        cats.append(yaw.Catalog.from_arrays(ra, dec, redshifts=z, patch_centers=yaw.AngularCoordinates(centers), degrees=False))
+    config = yaw.Configuration.create(rmin=0.1, rmax=2.0, unit="Mpc", edges=np.array([0.004, 0.03]))
+    return config, cats[0], cats[1]
+
+
+def check_wide_linkage(pi_max=19.0):
+    """``autocorrelate_projected`` on the nearby sample, whose linkage must reach past neighbouring patches
+    (``radial_max_angle`` between 4 and 5.7 degrees): DD, DR and RR summed over all patch pairs, the diagonal as the driver
+    stores it, are the patch-free brute force of tests/proj_oracle.py over the whole catalogues as integers -- a linkage too
+    short would lose pairs without a word. Then with four pi bins: the planes sum to the same totals.
+    ``engine.count_projected_fine`` and ``engine.count_projected_pi_fine`` are whatever the caller left in place."""
+    config, data, random = wide_scenario()
+    edges, closed = config.binning.edges, config.binning.closed
+    layouts = [cat.build_trees(edges, closed=closed, with_redshifts=True) for cat in (data, random)]
+    reach = measurements.radial_max_angle(config, *layouts)
+    assert np.deg2rad(4.0) < reach < np.deg2rad(5.7) and WIDE_GRID * WIDE_STEP >= 3.0 * reach and len(data) == WIDE_GRID**2 >= 12
+    r2 = measurements.threshold_table(measurements.radial_plans(config))
+    assert r2.shape == (1, 2)
+    whole = []
+    for layout in layouts:  # the whole catalogue as one segment: no patches
+        assert layout.w is None and 200 < len(layout.x) < 500
+        h = proj_oracle.as_handle(layout, *engine.proj_columns(layout, config.cosmology, "Mpc"))
+        whole.append(dict(h, nb=1, off=np.array([0, len(layout.x)], dtype=np.int64)))
+    diagonal, across = np.array([[0, 0, 0, 1]]), np.array([[0, 0, 0, 0]])
+    expected, uncut = {}, {}
+    for kind, (a, b, cell) in dict(dd=(whole[0], whole[0], diagonal), dr=(whole[0], whole[1], across), rr=(whole[1], whole[1], diagonal)).items():
+        expected[kind] = proj_oracle.proj_cells(a, b, cell, r2, pi_max)[2].sum()
+        uncut[kind] = proj_oracle.proj_cells(a, b, cell, r2, float("inf"))[2].sum()
+        assert min(proj_oracle.nearest_margin(a, b, cell, r2, pi_max)) > 1e-9
+        assert expected[kind] > 100 and 0.3 < expected[kind] / uncut[kind] < 0.7  # pi_max cuts roughly half the pairs
+    (cf,) = yaw.autocorrelate_projected(config, data, random, pi_max=pi_max)
+    row, col = np.divmod(np.arange(WIDE_GRID**2), WIDE_GRID)
+    apart = np.maximum(np.abs(row[:, None] - row[None, :]), np.abs(col[:, None] - col[None, :]))  # in patches, along either axis
+    for kind in ("dd", "dr", "rr"):
+        counts = getattr(cf, kind).counts.counts
+        assert counts.shape == (1, WIDE_GRID**2, WIDE_GRID**2) and np.all(counts == np.rint(counts))
+        assert counts.sum() == expected[kind], (kind, counts.sum(), expected[kind])
+        assert counts[0][apart > 0].sum() >= 0.1 * counts.sum()  # a tenth of the member pairs between different patches
+        assert counts[0][apart >= 2].sum() > 0  # ... and some between patches that share no boundary
+        print(f"{kind}: {counts.sum():.0f} pairs, {counts[0][apart > 0].sum():.0f} between patches, {counts[0][apart >= 2].sum():.0f} past a neighbour")
+    (planes,) = yaw.autocorrelate_projected(config, data, random, pi_max=pi_max, pi_bins=4)
+    assert len(planes.pi_bins) == 4
+    for kind in ("dd", "dr", "rr"):
+        per_plane = [getattr(plane, kind).counts.counts for plane in planes.pi_bins]
+        assert all(plane.sum() > 0 for plane in per_plane) and np.array_equal(sum(per_plane), getattr(cf, kind).counts.counts)
+        assert sum(plane.sum() for plane in per_plane) == expected[kind]
+    for cat in (data, random):
+        cat.drop_layouts()
+    return cf
+
+
+def test_the_linkage_reaches_past_neighbouring_patches(stand_in, monkeypatch):
+    import proj_pi_oracle
+
+    monkeypatch.setattr(engine, "count_projected_pi_fine", proj_pi_oracle.count_projected_pi_fine)
+    check_wide_linkage()
+
+
 # --------------------------------------------------------------------------- 5. symmetry
 def test_the_oracle_is_bit_symmetric_under_swapping_the_sides():
     a, b = proj_scenes.handle(proj_scenes.SEED_A, 4, 24), proj_scenes.handle(proj_scenes.SEED_B, 4, 24)
