@@ -263,6 +263,85 @@ def test_multi_device_context_replicates_both(monkeypatch):
     cats["ref"].drop_layouts()
 
 
+# --------------------------------------------------------------------------- exact sums through the API
+def _dyadic_catalogs():
+    """The positions of the count-variant table's ``c1`` (binned, 17 033 objects) and ``c2u`` (27 258, with the partners at
+    the bin edges and the clump) in 1.5 x 1.5 deg, cut into four strips of right ascension (the table's own patch 3 holds no
+    ``c1`` object, and a catalogue takes no empty patch). Weights ``m / 16`` with m in [1, 64], kappa ``m / 16`` with m in
+    [-64, 64]: ``kappa * w`` is a multiple of 2^-8 of magnitude at most 16, a product of two of them a multiple of 2^-16 of at
+    most 2^8, and the catalogues hold fewer than 2^29 pairs -- every float64 sum of such products is exact in any order."""
+    import test_gpu_count_variants as table
+    from oracle import oracle
+
+    cats = table._catalogues()[0]
+    rng = np.random.default_rng(20261023)
+    zedges = np.linspace(0.1, 0.9, table.B + 1)
+    centers = yaw.AngularCoordinates(np.deg2rad([[30.1875, 0.0], [30.5625, 0.0], [30.9375, 0.0], [31.3125, 0.0]]))
+    out = []
+    for name in ("c1", "c2u"):
+        cat = cats[name]
+        n = len(cat["x"])
+        ra, dec = oracle.from_3d(cat["x"], cat["y"], cat["z"])
+        frame = dict(ra=np.rad2deg(ra), dec=np.rad2deg(dec), w=rng.integers(1, 65, n) / 16.0, kappa=rng.integers(-64, 65, n) / 16.0)
+        if cat["nb"] > 1:  # the redshift bin of the table's segment, at the middle of the bin
+            k = np.repeat(np.arange(len(cat["off"]) - 1) % cat["nb"], np.diff(cat["off"]))
+            frame["z"] = 0.5 * (zedges[k] + zedges[k + 1])
+        out.append(yaw.Catalog.from_dataframe(None, frame, ra_name="ra", dec_name="dec", weight_name="w", kappa_name="kappa",
+                                              redshift_name="z" if "z" in frame else None, patch_centers=centers))
+    assert 17033 * 27258 < 2 ** 29
+    return (*out, zedges)
+
+
+def test_scalar_modes_are_exact_on_dyadic_input(monkeypatch):
+    """``kappa * w`` through the API on catalogues large enough for the kernels production runs (a band or merged-sweep
+    variant, not the brute-force ``k_count``): with exactly summable input the counts of every mode equal, bit for bit, the
+    same calls made on the CPU oracle -- the kernel's sums, the halving of an autocorrelation's diagonal jobs, the per-scale
+    sums and the scatter are all exact."""
+    one, two, zedges = _dyadic_catalogs()
+    config = yaw.Configuration.create(rmin=[1.0, 2.0], rmax=[3.5, 6.0], unit="arcmin", edges=zedges, closed="right")
+    one.build_trees(config.binning.edges, closed="right")
+    two.build_trees(None)
+    links = yaw.PatchLinkage.from_catalogs(config, one, two)
+    calls = {**{mode: ((one, two), mode) for mode in ("kn", "nk", "kk")}, "auto kk": ((one,), "kk")}
+
+    def production_kernel(stats):
+        names = stats.variants
+        return bool(names) and all(v.startswith(("k_count_band", "k_count_merged")) for v in names)
+
+    def run(check_variants):
+        out = {}
+        for key, (cats, mode) in calls.items():
+            out[key] = np.stack([c.counts.counts for c in links.count_pairs(*cats, mode=mode)])
+            if check_variants:
+                print(f"{key}: {sorted(links.last_stats.variants)}")
+                assert production_kernel(links.last_stats), (key, links.last_stats.variants)
+                assert links.last_stats.count_variant == 0  # the sums alone: the weighted instantiation
+        dd = links.count_scalar_pairs(one, two, mode="kk", count_type_info="DD")
+        out["scalar kk"] = np.stack([c.kappa_counts.counts for c in dd])
+        out["scalar nn"] = np.stack([c.number_counts.counts for c in dd])
+        if check_variants:
+            assert sorted(links.last_batch_stats) == ["DD (kk)", "DD (nn)"]
+            assert all(production_kernel(st) for st in links.last_batch_stats.values()), links.last_batch_stats
+        return out
+
+    got = run(True)
+    with monkeypatch.context() as patch:
+        helpers.use_oracle_engine(patch)
+        exp = run(False)
+    assert sorted(got) == sorted(exp) and len(got) == 6
+    for key in got:
+        assert got[key].shape == exp[key].shape and np.any(exp[key] != 0), key
+        differ = np.count_nonzero(got[key] != exp[key])
+        assert np.array_equal(got[key], exp[key]), (key, differ)
+        if key != "scalar nn":
+            assert np.any(exp[key] < 0) and np.any(exp[key] > 0), key
+    assert np.array_equal(got["scalar kk"], got["kk"])
+    # the diagonal jobs of the autocorrelation hold pairs, counted once
+    assert np.any(np.diagonal(exp["auto kk"], axis1=2, axis2=3) != 0)
+    one.drop_layouts()
+    two.drop_layouts()
+
+
 # --------------------------------------------------------------------------- submissions
 def test_scalar_counts_are_one_submission_and_equal_single_calls(monkeypatch):
     g = load_golden("scalar_drivers.npz")
