@@ -795,6 +795,49 @@ int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_
                          int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine_w,
                          yawhip_stats *stats);
 
+/*
+ * Redshift-space pair counts: the planes DD, DR and RR of xi(s, mu), from which the multipoles xi_l(s) are summed
+ * (measurements.autocorrelate_multipoles; no counterpart in the reference). Additive to ABI 6: one new
+ * symbol.
+ *
+ * yawhip_proj_count_smu  yawhip_proj_count_pi argument for argument: handles (both of yawhip_proj_upload), cell list
+ *                        (segment of a, segment of b, row, diagonal), window, diagonal rule and statistics are
+ *                        yawhip_proj_count's. The rows s2 float64[n_rows][n_edges] (host) hold SQUARED edges of s, the call-wide
+ *                        m2 float64[n_mu + 1] (host) SQUARED edges of mu. s2c (the squared chord), D, DD, th2 and R2 of a pair
+ *                        are exactly yawhip_proj_count's (float64, every operation rounded on its own). Then
+ *       p = fabs(c_a - c_b),   P2 = p p,   S2 = R2 + P2
+ *       e = the fine bin with s2[row][e] < S2 <= s2[row][e + 1]     a pair with S2 beyond the last edge, or not above the
+ *                                                                   first, is in no bin
+ *       j = the number of INNER edges k = 1 .. n_mu - 1 with fl(m2[k] S2) < P2
+ *                                                                   plane 0 is mu^2 in [0, m2[1]], plane j (m2[j], m2[j + 1]]
+ *       fine_w[j][c][e] += w_a * w_b
+ *     m2 ascends and rounding is monotone, so the predicate holds for a prefix of the edges. m2[0] and m2[n_mu] are never
+ *     read by the kernel: fl(R2 + P2) >= P2 always, so every pair inside the s range lands in a plane -- there is no
+ *     line-of-sight cut. All terms are bit-symmetric under a <-> b, so a diagonal cell holds every unordered pair once.
+ *     Consequences: over unit weights the sum over j of fine_w[j] equals the n_mu = 1 call as integers; on handles whose c
+ *     column is constant (p = 0, S2 = R2 exactly) the n_mu = 1 plane is yawhip_proj_count's fine_w at pmax = +inf and every
+ *     pair of a several-plane call is in plane 0; candidate_pairs and evaluated_pairs equal those of yawhip_proj_count on
+ *     the same cells and table; two objects at one sky position with different c (R2 = 0, S2 = P2) ARE counted, in the last
+ *     plane, which yawhip_proj_count never does; exact duplicates (S2 = 0) are in no bin.
+ *   n_mu, m2     n_mu >= 1; m2[0] exactly 0 and m2[n_mu] exactly 1; finite and strictly ascending. Anything else (NaN, ties,
+ *                a NULL m2): YAWHIP_ERR_INVALID.
+ *   the cap      the carve-up of a workgroup's LDS is yawhip_proj_count_pi's with m2 in the place of pe, and so is the cap:
+ *                n_mu <= 104 at 13 edges, <= 25 at 51, <= 4 at 256. A larger n_mu is YAWHIP_ERR_INVALID with a message that
+ *                names the largest number of mu bins that fits at this n_edges; the library does not split a call.
+ *   the reach    R2 <= S2 (P2 >= 0, rounding is monotone), so the reach of the largest s bounds the reach of every counted
+ *                pair: the s2 table is checked as yawhip_proj_count checks its radius table, with the same refusals.
+ *   fine_w       float64[n_mu][n_cells][n_edges - 1] (host); every element is written
+ *   checks       those of yawhip_proj_count_pi in its order, with n_mu and m2 and the cap where that call checks n_pi and
+ *                pe. stats, buffers, n_cells == 0: as yawhip_proj_count.
+ * Kernel: the walk of yawhip_proj_count with an outer test that knows the line of sight: the wave-wide test holds
+ * fl(fl(DD s2c) + P2) against the row's last edge -- an exact superset of the pairs in range, since fl(DD s2c) <= R2 and the
+ * one sum is rounded monotonely (an FMA of p, p and DD s2c would not be: it adds the unrounded square). Accumulation and
+ * reproducibility as yawhip_shear_count: per-wave LDS histograms, folded in a fixed order, plain stores.
+ */
+int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                          int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu, const double *m2, double *fine_w,
+                          yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

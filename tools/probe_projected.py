@@ -22,6 +22,11 @@ cells against tests/proj_pi_oracle.py in every pi bin, and adds to its line ``pi
 (the formula of include/yawhip.h) and the workgroups of 256 threads that this LDS lets one CU hold (160 KiB per CU). More
 pi bins than that LDS formula admits at ``--fine`` is the library's refusal, passed on.
 
+``--mu-bins N`` times the redshift-space count (``engine.count_smu_fine``, ``yawhip_proj_count_smu``, kernel ``k_count_smu``;
+DESIGN.md section 23) on the same input with the radii read as ``s`` and ``N`` equal bins of mu in [0, 1] -- there is no
+line-of-sight cut, ``--pi-max`` is not used -- checks the same cells against tests/smu_oracle.py in every mu bin, and adds
+``mu_bins`` and the same LDS figures to its line.
+
 The evaluated separations of a diagonal cell count one order of every pair (include/yawhip.h), where ``k_count_shear_auto``
 also reports the other order inside a lane tile's own range: per diagonal tile of 256 lanes that is 32 640 separations which
 this figure leaves out and that one has.
@@ -59,6 +64,7 @@ def main():
     ap.add_argument("--pi-max", type=float, default=60.0, help="Mpc")
     ap.add_argument("--fine", type=int, default=50)
     ap.add_argument("--pi-bins", type=int, default=None, help="time yawhip_proj_count_pi with this many equal pi bins")
+    ap.add_argument("--mu-bins", type=int, default=None, help="time yawhip_proj_count_smu with this many equal mu bins")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--check", type=int, default=4, help="cells compared with the oracle")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "projected_probe.jsonl"))
@@ -91,9 +97,16 @@ def main():
     seg2 = (jobs[:, 1:].astype(np.int64) * nb + np.arange(nb)).ravel()
     cells = np.column_stack([seg1, seg2, np.tile(np.arange(nb), len(jobs)), seg1 == seg2]).astype(np.int32)
 
+    if args.pi_bins is not None and args.mu_bins is not None:
+        raise SystemExit("--pi-bins and --mu-bins are two counts: one at a time")
     pi_edges = None if args.pi_bins is None else engine.check_pi_edges(args.pi_bins, args.pi_max)
+    mu_edges = None if args.mu_bins is None else engine.check_mu_edges(args.mu_bins)
+    planes = pi_edges if pi_edges is not None else mu_edges  # the edges of a count with planes, else None
 
     def call():
+        if mu_edges is not None:
+            return engine.count_smu_fine(layout, layout, cells, r2, mu_edges=mu_edges, cosmology=config.cosmology, unit=unit,
+                                         sort_axis=links.sort_axis)
         if pi_edges is not None:
             return engine.count_projected_pi_fine(layout, layout, cells, r2, pi_edges=pi_edges, cosmology=config.cosmology, unit=unit,
                                                   sort_axis=links.sort_axis)
@@ -112,13 +125,18 @@ def main():
     handle = proj_oracle.as_handle(layout, *engine.proj_columns(layout, config.cosmology, unit))
     sizes = np.diff(layout.offsets)
     cost = sizes[cells[:, 0]].astype(np.float64) * sizes[cells[:, 1]]
-    holds = W.sum(axis=-1).sum(axis=0) > 0 if pi_edges is not None else W.sum(axis=1) > 0
+    holds = W.sum(axis=-1).sum(axis=0) > 0 if planes is not None else W.sum(axis=1) > 0
     checked, worst = [], 0.0
     for diagonal in (1, 0):
         of_kind = np.flatnonzero((cells[:, 3] == diagonal) & holds)
         checked += list(of_kind[np.argsort(cost[of_kind], kind="stable")][: (args.check + diagonal) // 2])
     if checked:
-        if pi_edges is not None:
+        if mu_edges is not None:
+            import smu_oracle
+
+            exp_w, exp_a, _ = smu_oracle.smu_cells(handle, handle, cells[checked], r2, mu_edges * mu_edges)
+            differs = np.abs(W[:, checked] - exp_w)
+        elif pi_edges is not None:
             import proj_pi_oracle
 
             exp_w, exp_a, _ = proj_pi_oracle.proj_pi_cells(handle, handle, cells[checked], r2, pi_edges)
@@ -137,10 +155,13 @@ def main():
                 wall_ms=round(statistics.median(wall), 3), ps_per_evaluated=round(1e9 * median / max(stats.evaluated_pairs, 1), 3),
                 weight_in_range=float(W.sum()), cells_with_pairs=int(np.count_nonzero(holds)), cells_checked=[int(c) for c in checked],
                 worst_difference_over_A=worst, repeat=args.repeat, source_sha16=source_sha16())
-    if pi_edges is not None:
-        n_edges, n_pi = int(r2.shape[1]), len(pi_edges) - 1
+    if planes is not None:
+        n_edges, n_pi = int(r2.shape[1]), len(planes) - 1
         lds = 2 * 256 * 48 + 8 * (((n_edges + 1) & ~1) + ((n_pi + 2) & ~1)) + 4 * n_pi * (n_edges - 1) * 8
-        line.update(pi_bins=n_pi, kernel="k_count_projected_pi", lds_bytes_per_workgroup=lds, workgroups_per_cu_by_lds=(160 * 1024) // lds)
+        line.update(dict(pi_bins=n_pi, kernel="k_count_projected_pi") if pi_edges is not None else dict(mu_bins=n_pi, kernel="k_count_smu"),
+                    lds_bytes_per_workgroup=lds, workgroups_per_cu_by_lds=(160 * 1024) // lds)
+    if mu_edges is not None:
+        del line["pi_max_mpc"]  # no cut
     text = json.dumps(line)
     print(text, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

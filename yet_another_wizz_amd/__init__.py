@@ -20,8 +20,8 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import CorrFunc, ProjectedCorrFunc, ScalarCorrFunc
-from .measurements import (PatchLinkage, autocorrelate, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
+from .corrfunc import CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
+from .measurements import (PatchLinkage, autocorrelate, autocorrelate_multipoles, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
                            crosscorrelate_delta_sigma, crosscorrelate_shear)
 from . import healpix, patches, randoms
@@ -43,6 +43,7 @@ __all__ = [
     "NormalisedCounts",
     "NormalisedScalarCounts",
     "Patch",
+    "MultipoleCorrFunc",
     "PatchLinkage",
     "PatchedCounts",
     "PatchedSumWeights",
@@ -51,6 +52,7 @@ __all__ = [
     "SampledData",
     "ScalarCorrFunc",
     "autocorrelate",
+    "autocorrelate_multipoles",
     "autocorrelate_projected",
     "autocorrelate_scalar",
     "autocorrelate_shear",

@@ -71,6 +71,7 @@ ABI_SYMBOLS = (
     "yawhip_proj_upload",
     "yawhip_proj_count",
     "yawhip_proj_count_pi",
+    "yawhip_proj_count_smu",
 )
 
 
@@ -304,6 +305,7 @@ def load_library() -> ctypes.CDLL:
                                       ctypes.POINTER(_Stats)]
     lib.yawhip_proj_count_pi.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
                                          _dp, ctypes.POINTER(_Stats)]
+    lib.yawhip_proj_count_smu.argtypes = lib.yawhip_proj_count_pi.argtypes
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -871,7 +873,7 @@ class ProjHandle(ShearSources):
 
 def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
                   rows: str = "thresholds must be [n_bins, n_edges]", stacked: bool = False):
-    """What the seven counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+    """What the eight counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
     ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
     entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
     and the ``CountStats``. ``stacked``: the symbol takes the planes as ONE array f64[n_planes, ...], which is what comes
@@ -907,6 +909,21 @@ def proj_count_pi(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pi_edge
     n_pi = len(pe) - 1
     return _shear_counts("yawhip_proj_count_pi", max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp), width=4,
                          rows="r2 must be [n_rows, n_edges]", stacked=True)
+
+
+def proj_count_smu(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, m2):
+    """Run ``yawhip_proj_count_smu``: the pairs of ``proj_count``'s cells binned by ``S2 = R2 + P2`` (``P2`` the square of
+    ``p = |c_a - c_b|``) over the rows ``s2`` f64[n_rows, E] of SQUARED s edges, and by ``mu^2 = P2 / S2`` over the squared mu
+    edges ``m2`` f64[n_mu + 1], from exactly 0 to exactly 1 and strictly ascending: a pair is in the plane j that counts the
+    inner edges k with ``fl(m2[k] S2) < P2``. There is no line-of-sight cut. Returns ``(W, CountStats)``, W f64[n_mu, n_cells,
+    E-1]; the statistics are ``proj_count``'s on the same cells and table. ``n_mu (E - 1)`` is capped by the LDS of a
+    workgroup as ``proj_count_pi``'s ``n_pi (E - 1)`` is (include/yawhip.h); beyond it the library refuses."""
+    m2 = np.ascontiguousarray(m2, dtype=np.float64)
+    if m2.ndim != 1:
+        raise ValueError("m2 must be [n_mu + 1]")
+    n_mu = len(m2) - 1
+    return _shear_counts("yawhip_proj_count_smu", max(n_mu, 0), (ctx._h, a._h, b._h), cells, s2, n_mu, _ptr(m2, _dp), width=4,
+                         rows="s2 must be [n_rows, n_edges]", stacked=True)
 
 
 def proj_count(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pmax: float):

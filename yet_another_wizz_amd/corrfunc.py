@@ -7,7 +7,7 @@ import numpy as np
 from .corrdata import CorrData
 from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -243,3 +243,99 @@ class ProjectedCorrFunc:
 
     def patches_subset(self, item):
         return type(self)(self.pi_edges, [cf.patches_subset(item) for cf in self.pi_bins])
+
+
+class MultipoleCorrFunc:
+    """The pair counts of one scale of the redshift-space clustering binned in ``mu = pi / s``
+    (``autocorrelate_multipoles``; no counterpart in the reference): ``mu_edges`` f64[n_mu + 1], from 0 to 1 and strictly
+    ascending, and ``mu_bins``, a tuple of ``n_mu`` ``CorrFunc(dd, dr, None, rr)`` -- bin 0 holds the pairs with ``mu`` in
+    ``[0, mu_1]``, bin j those in ``(mu_j, mu_{j+1}]``; ``mu`` is unsigned. All bins hold the same kinds of counts on one
+    binning and one set of patches.
+
+    ``sample_xi()`` is ``xi(s, mu_j)`` per mu bin, ``sample(ell)`` the multipole ``xi_ell(s)`` and ``sample_multipoles()``
+    several of them. A mu bin whose RR (DR for Davis-Peebles) is empty in some redshift bin gives NaN there, in
+    ``sample_xi()`` and in EVERY multipole, as ``CorrFunc.sample()`` does: nothing is masked. ``to_dict`` / ``from_dict``,
+    ``==`` and the bin and patch subsets go bin by bin through ``CorrFunc``'s, as ``ProjectedCorrFunc``'s do."""
+
+    __slots__ = ("mu_edges", "mu_bins")
+
+    def __init__(self, mu_edges, mu_bins) -> None:
+        edges = np.array(mu_edges, dtype=np.float64)
+        bins = tuple(mu_bins)
+        if edges.ndim != 1 or len(edges) != len(bins) + 1 or len(bins) < 1:
+            raise ValueError("'mu_edges' must hold one edge more than there are mu bins, and there is at least one bin")
+        if edges[0] != 0.0 or edges[-1] != 1.0 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0):
+            raise ValueError("'mu_edges' must start at 0, end at 1, be finite and ascend strictly")
+        for cf in bins:
+            if type(cf) is not CorrFunc:
+                raise TypeError(f"the mu bins must be of type {CorrFunc}")
+            bins[0].is_compatible(cf, require=True)
+            if cf.to_dict().keys() != bins[0].to_dict().keys():
+                raise ValueError("the mu bins must hold the same kinds of pair counts")
+        edges.setflags(write=False)
+        self.mu_edges = edges
+        self.mu_bins = bins
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(num_mu={self.num_mu}, mu_bins[0]={self.mu_bins[0]!r})"
+
+    binning = property(lambda self: self.mu_bins[0].binning)
+    auto = property(lambda self: self.mu_bins[0].auto)
+    num_patches = property(lambda self: self.mu_bins[0].num_patches)
+    num_bins = property(lambda self: self.mu_bins[0].num_bins)
+    num_mu = property(lambda self: len(self.mu_bins))
+
+    def to_dict(self) -> dict:
+        return dict(mu_edges=self.mu_edges.copy(), mu_bins=[cf.to_dict() for cf in self.mu_bins])
+
+    @classmethod
+    def from_dict(cls, state: dict):
+        return cls(state["mu_edges"], [CorrFunc.from_dict(counts) for counts in state["mu_bins"]])
+
+    def __eq__(self, other) -> bool:
+        if type(self) is not type(other):
+            return NotImplemented
+        return np.array_equal(self.mu_edges, other.mu_edges) and self.mu_bins == other.mu_bins
+
+    def is_compatible(self, other, *, require: bool = False) -> bool:
+        if type(self) is not type(other):
+            if require:
+                raise TypeError(f"{type(other)} is not compatible with {type(self)}")
+            return False
+        if not np.array_equal(self.mu_edges, other.mu_edges):
+            if require:
+                raise ValueError("the mu edges differ")
+            return False
+        return self.mu_bins[0].is_compatible(other.mu_bins[0], require=require)
+
+    def sample_xi(self) -> list:
+        """``xi(s, mu_j)`` per mu bin: ``CorrFunc.sample()`` of each, Landy-Szalay or (without RR) Davis-Peebles, for the data
+        and every jackknife sample."""
+        return [cf.sample() for cf in self.mu_bins]
+
+    def legendre_weights(self, ell: int) -> np.ndarray:
+        """``I_ell,j = int_{mu_j}^{mu_{j+1}} P_ell(mu) dmu`` per mu bin, f64[n_mu], from the antiderivative of the Legendre
+        polynomial. ``ell`` is even and in 0 ... 8: ``mu`` is unsigned, so the odd multipoles are not measured."""
+        if isinstance(ell, (bool, np.bool_)) or not isinstance(ell, (int, np.integer)) or ell < 0 or ell > 8 or ell % 2:
+            raise ValueError(f"ell must be an even integer in 0 ... 8 (mu is unsigned), not {ell!r}")
+        primitive = np.polynomial.legendre.Legendre.basis(int(ell)).integ()
+        return np.diff(primitive(self.mu_edges))
+
+    def sample(self, ell: int = 0) -> CorrData:
+        """``xi_ell(s) = (2 ell + 1) sum_j xi_j I_ell,j`` (``legendre_weights``), summed in the order of the mu bins for the
+        data and for each jackknife sample separately; errors and covariance are those of the summed samples. With equal
+        weights over [0, 1] this is the usual ``(2 ell + 1) int_0^1 xi(s, mu) P_ell(mu) dmu`` with ``xi`` constant per bin."""
+        data, samples = 0.0, 0.0
+        for weight, xi in zip(self.legendre_weights(ell), self.sample_xi()):
+            data, samples = data + weight * xi.data, samples + weight * xi.samples
+        return CorrData(self.binning, (2 * int(ell) + 1) * data, (2 * int(ell) + 1) * samples)
+
+    def sample_multipoles(self, ells=(0, 2, 4)) -> tuple:
+        """``sample(ell)`` for every ``ell`` of ``ells``."""
+        return tuple(self.sample(ell) for ell in ells)
+
+    def bins_subset(self, item):
+        return type(self)(self.mu_edges, [cf.bins_subset(item) for cf in self.mu_bins])
+
+    def patches_subset(self, item):
+        return type(self)(self.mu_edges, [cf.patches_subset(item) for cf in self.mu_bins])

@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (the yawhip_shear_*, yawhip_dsigma_* and yawhip_proj_* calls of include/yawhip.h; DESIGN.md
-// sections 15 to 22): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
+// sections 15 to 23): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>

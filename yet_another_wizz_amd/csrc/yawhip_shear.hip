@@ -8,10 +8,12 @@
 // per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers), and the projected
 // pair counts of objects with a transverse distance and a line-of-sight coordinate, binned in each PAIR's own radius inside a
 // line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected), and those binned in the
-// line-of-sight separation besides (yawhip_proj_count_pi; autocorrelate_projected(pi_bins=...)).
+// line-of-sight separation besides (yawhip_proj_count_pi; autocorrelate_projected(pi_bins=...)), and
+// the pair counts of the same handles binned in the redshift-space separation s and in mu = pi / s (yawhip_proj_count_smu;
+// measurements.autocorrelate_multipoles).
 // include/yawhip.h has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under seven thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under eight thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -45,6 +47,9 @@
 // row's last squared radius, the pair is binned by R2 = DD th2(s2) and adds w_a w_b iff |c_a - c_b| <= pmax (at the policy).
 // ProjectedPi (k_count_projected_pi) is Projected with the call's n_pi planes instead of one: the pi edges are staged into
 // LDS next to the thresholds, and behind the ballot p = |c_a - c_b| is bisected over them as R2 is over the row.
+// RedshiftSpace (k_count_smu) is Projected with the call's n_mu planes and no cut: the ballot holds fl(DD s2) + P2,
+// P2 = |c_a - c_b|^2 with c read in the hot loop, against the row's last squared s; the pair is binned by S2 = R2 + P2 and goes
+// to the plane that the staged squared mu edges give for P2 against m2 S2 (at the policy).
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -143,6 +148,7 @@ struct Cell {
 struct ChordBinned {
     static constexpr bool CAPPED = true;
     static constexpr bool KEPT_WORK = false;  // the evaluated separations of a diagonal cell: all of them (else: kept_work)
+    static constexpr bool ADD_BINNED = false;  // a policy with the call's planes whose add() takes what binned() gave
     template <class B>
     static __device__ __forceinline__ double outer(const Lane &, const B &, double s) { return s; }
     template <class B>
@@ -426,6 +432,72 @@ struct ProjectedPi : Projected {
     }
 };
 
+// The lanes of the redshift-space count: a projected handle and the call's squared mu edges m2[n_mu + 1] (device memory; the
+// workgroup stages them into LDS once, where ProjPiLanes has pe) with the first step of their bisection, the largest power of
+// two <= n_mu - 1 (0 at one plane: nothing is bisected). No call-wide cut comes with them: the lane's u is unused.
+struct SmuLanes : ShearView {
+    const double *m2;
+    int n_mu, step;
+};
+
+// Pair counts binned in the redshift-space separation s and in mu = pi / s (k_count_smu): object, lane,
+// cells, window, diagonal rule and KEPT_WORK are Projected's; planes, extra_slots and stage_extra are ProjectedPi's with m2
+// in the place of pe. With R2 = DD th2(s2c) of Projected (s2c: the squared chord),
+//   p = fabs(c_a - c_b),   P2 = p p,   S2 = R2 + P2            (every operation rounded on its own)
+// the row holds squared s edges and is bisected by S2; the plane j is the number of INNER edges k = 1 .. n_mu - 1 with
+// fl(m2[k] S2) < P2 -- plane 0 is mu^2 in [0, m2[1]], plane j is (m2[j], m2[j + 1]]. m2 ascends and rounding is monotone, so
+// the predicate holds for a prefix of the edges and a bisection finds j. m2[0] and m2[n_mu] are never read: fl(R2 + P2) >= P2,
+// so every pair inside the s range has a plane and there is no cut. All terms are bit-symmetric under a <-> b.
+//
+// The ballot holds so = fl(fl(DD s2c) + P2) against the last squared s edge, with c read in the hot loop (one more 16-byte LDS
+// read, three more FP64 operations per trip). Two candidates, both EXACT supersets of the pairs in range, no guard term:
+//   (A) Projected::outer, x = fl(DD s2c). Projected's proof gives x <= R2 (q >= 1 after rounding, rounding monotone, DD >= 0);
+//       P2 >= 0 and monotone rounding give R2 = fl(R2 + 0) <= fl(R2 + P2) = S2. So S2 <= last edge implies x <= last edge.
+//   (B) fl(x + P2), the same x and the SAME separately rounded P2 as in the pair term: x <= R2, so by monotone rounding of
+//       the one sum fl(x + P2) <= fl(R2 + P2) = S2. So S2 <= last edge implies so <= last edge.
+// An FMA fma(p, p, x) is NOT a superset: it adds the unrounded p^2, which may exceed fl(p^2) = P2, and at x = R2 the sum can
+// round one ulp above S2 -- a pair with S2 exactly on the last edge would be lost. It is left out (and the build contracts
+// nothing). (B) keeps out of the branch the pairs that are close on the sky and far along the line of sight, which are the
+// bulk of what passes (A); DESIGN.md section 23 has both measured. The converse fails as for Projected: a pair behind the
+// ballot with S2 beyond the last edge runs off the row and is dropped (!CAPPED). Padded lanes and padded streamed objects:
+// as Projected's (c = 0 there, so P2 is finite; `ok` and the stage's count n exclude them).
+struct RedshiftSpace : Projected {
+    using Lanes = SmuLanes;
+    static constexpr int PLANES = 0;         // the call's: planes()
+    static constexpr bool ADD_BINNED = true;  // the walk hands what binned() gave (S2) on to add()
+    static __device__ __forceinline__ int planes(const SmuLanes &src) { return src.n_mu; }
+    static __device__ __forceinline__ int extra_slots(const SmuLanes &src) { return pi_slots(src.n_mu); }
+    static __device__ __forceinline__ void stage_extra(const SmuLanes &src, double *ext, int tid) {
+        for (int j = tid; j <= src.n_mu; j += WG) ext[j] = src.m2[j];
+    }
+    static __device__ __forceinline__ int first_step(const SmuLanes &src) { return src.step; }
+    static __device__ double lane_u(const SmuLanes &, int64_t, bool) { return 0.0; }
+    static __device__ __forceinline__ double pair_p2(const Lane &a, const ObjP &b) {
+        const double p = fabs(a.g2 - b.c);
+        return p * p;
+    }
+    static __device__ __forceinline__ double outer(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * s + pair_p2(a, b); }
+    static __device__ __forceinline__ double binned(const Lane &a, const ObjP &b, double s) {
+        return pair_dd(a, b) * squared_angle(s) + pair_p2(a, b);
+    }
+    // m2: the staged edges in LDS; top: first_step(); S2: what binned() returned for this pair (squared_angle is not evaluated again)
+    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *m2, int n_mu, int top, double S2) {
+        const double P2 = pair_p2(a, b);
+        // j: the inner edges m2[1 .. n_mu - 1] with fl(m2[k] S2) < P2, a prefix of them. Bisected by descending powers of two,
+        // the same trips for every lane (a scalar loop: no exec mask is saved for it, and the walk is at the limit of its
+        // scalar registers): j + step edges hold iff edge k = j + step is an inner one and holds. At least one trip, so
+        // that no entry test is kept in scalar registers either; at one plane top == 0, k == 0 is no inner edge and
+        // nothing is read.
+        int j = 0, step = top;
+        do {
+            const int k = j + step;
+            if ((unsigned)(k - 1) < (unsigned)(n_mu - 1) && m2[k] * S2 < P2) j = k;
+            step >>= 1;
+        } while (step > 0);
+        atomicAdd(&wh[j * nf + e], a.w * b.w);
+    }
+};
+
 // The separations of a diagonal cell's lane tile [ta, t_last] against the streamed objects [b0, b1), b0 > ta, that the index
 // test can keep -- the streamed index larger than the lane's: what a policy with KEPT_WORK reports as evaluated, so that a
 // cell's figure never exceeds its unordered pairs. (The waves evaluate the others of the tile's own range too, and drop them.)
@@ -458,6 +530,9 @@ constexpr int max_pi_planes(int n_edges) {
 }
 static_assert(max_pi_planes(MAX_EDGES) == 4 && max_pi_planes(13) == 104 && max_pi_planes(2) == 1023,
               "ProjectedPi: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 22 quote it)");
+static_assert(lds_bytes<RedshiftSpace>(13, 104) == lds_bytes<ProjectedPi>(13, 104) && lds_bytes<RedshiftSpace>(51, 25) == lds_bytes<ProjectedPi>(51, 25) &&
+                  lds_bytes<RedshiftSpace>(MAX_EDGES, 4) == lds_bytes<ProjectedPi>(MAX_EDGES, 4),
+              "RedshiftSpace: its carve-up is ProjectedPi's, so that max_pi_planes caps n_mu too (DESIGN.md section 23)");
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<ShearShear>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<ShearPair>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<DeltaSigma>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= LDS_LIMIT &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
@@ -612,7 +687,8 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
                         // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the counts binned in a radius -- has cnt == n_edges and no bin:
                         // the histogram has nf of them), and not the lower half of a diagonal cell
                         if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) {
-                            if constexpr (CALL_PLANES) P::add(a, b, wh, cnt - 1, nf, ext, NP);
+                            if constexpr (CALL_PLANES && P::ADD_BINNED) P::add(a, b, wh, cnt - 1, nf, ext, NP, P::first_step(src), v);
+                            else if constexpr (CALL_PLANES) P::add(a, b, wh, cnt - 1, nf, ext, NP);
                             else P::add(a, b, wh, cnt - 1, nf);
                         }
                     }
@@ -687,6 +763,14 @@ __global__ __launch_bounds__(WG) void k_count_projected_pi(ShearView a, ProjPiLa
                                                            int64_t n_cells, double *__restrict__ out,
                                                            unsigned long long *__restrict__ evaluated) {
     shear_walk<ProjectedPi>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
+// out: [n_mu][n_cells][E-1] (W per mu bin); as k_count_projected_pi, s2: [rows][n_edges] squared s edges, b with the call's
+// squared mu edges
+__global__ __launch_bounds__(WG) void k_count_smu(ShearView a, SmuLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                  const double *__restrict__ s2, const double *__restrict__ rwin, int64_t n_cells,
+                                                  double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
+    shear_walk<RedshiftSpace>(a, b, cells, 0, n_edges, s2, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -1248,6 +1332,39 @@ int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_
             go(k_count_projected_pi, view_of(a), ProjPiLanes{view_of(b), d.pe, n_pi, pe[n_pi]}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
         },
         n_pi, pe);
+}
+
+int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                          int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu, const double *m2, double *fine_w,
+                          yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_smu";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, s2, cells && fine_w)) return rc;
+    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
+    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
+    if (n_mu < 1 || !m2) return fail(YAWHIP_ERR_INVALID, "%s: n_mu must be >= 1 and m2 not NULL (n_mu=%d)", fn, n_mu);
+    if (m2[0] != 0.0 || m2[n_mu] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must start at 0 and end at 1", fn);
+    for (int j = 1; j <= n_mu; ++j)  // (a NaN fails the comparison; between 0 and 1 ascending edges are finite)
+        if (!(m2[j] > m2[j - 1]))
+            return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must be finite and strictly ascending (edge %d)", fn, j);
+    if (n_mu > max_pi_planes(n_edges))
+        return fail(YAWHIP_ERR_INVALID, "%s: %d mu bins of %d s bins do not fit the LDS of a workgroup: at most %d mu bins at n_edges=%d", fn,
+                    n_mu, n_edges - 1, max_pi_planes(n_edges), n_edges);
+    // The row holds squared s edges where yawhip_proj_count's holds squared radii. R2 <= S2 = fl(R2 + P2) (P2 >= 0, rounding is
+    // monotone), so a counted pair has R2 <= the row's last edge: the reach of the largest s bounds the reach of every counted
+    // pair, and the checks and the window of the radius table hold on this one as they are.
+    std::vector<double> reach;
+    int64_t candidates = 0;
+    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, s2, reach, &candidates)) return rc;
+    int step = 0;  // the largest power of two <= n_mu - 1: the first step of the kernel's bisection of the inner edges
+    for (int two = 1; two <= n_mu - 1; two *= 2) step = two;
+    double *const fine[] = {fine_w};
+    return run_count<RedshiftSpace>(
+        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, s2, reach.data(), fine, candidates, wall0, stats,
+        [&](auto go, const Slots &d) {
+            go(k_count_smu, view_of(a), SmuLanes{view_of(b), d.pe, n_mu, step}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+        },
+        n_mu, m2);
 }
 
 }  // extern "C"

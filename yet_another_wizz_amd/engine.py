@@ -15,7 +15,7 @@ import re
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "count_projected_fine", "count_projected_pi_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -470,6 +470,58 @@ def count_projected_pi_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmolog
         if "too close for the largest radius" not in str(err):
             raise
         check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
+        raise
+
+
+def check_mu_edges(mu_bins) -> np.ndarray:
+    """The edges f64[n_mu + 1] of the bins in ``mu = pi / s`` of a redshift-space count from ``mu_bins``: an int ``n >= 1``
+    gives ``np.linspace(0.0, 1.0, n + 1)``; a sequence of edges must start at 0, ascend strictly, be finite and end at 1
+    (``ValueError`` otherwise)."""
+    if isinstance(mu_bins, (bool, np.bool_)):
+        raise ValueError("mu_bins must be a number of bins >= 1 or a sequence of edges")
+    if isinstance(mu_bins, (int, np.integer)):
+        if mu_bins < 1:
+            raise ValueError(f"mu_bins must be >= 1, not {mu_bins}")
+        return np.linspace(0.0, 1.0, int(mu_bins) + 1)
+    try:
+        edges = np.array(mu_bins, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+        raise ValueError("mu_bins must be a number of bins >= 1 or a sequence of edges") from err
+    if edges.ndim != 1 or len(edges) < 2:
+        raise ValueError("mu_bins as edges must be a sequence of at least two numbers")
+    if not np.all(np.isfinite(edges)):
+        raise ValueError("the mu edges must be finite")
+    if edges[0] != 0.0:
+        raise ValueError(f"the mu edges must start at 0, not {edges[0]}")
+    if not np.all(np.diff(edges) > 0.0):
+        raise ValueError("the mu edges must ascend strictly")
+    if edges[-1] != 1.0:
+        raise ValueError(f"the mu edges must end at 1, not {edges[-1]}")
+    return edges
+
+
+def count_smu_fine(layout_a, layout_b, cells, s2, *, mu_edges, cosmology, unit, sort_axis: int = 2):
+    """Fine-bin redshift-space pair counts for ``cells`` (``count_projected_fine``'s) -> ``(W, CountStats)``, W f64[n_mu,
+    n_cells, E-1]: the sums of ``w_a w_b`` over the pairs whose ``S^2 = R^2 + (chi_a - chi_b)^2`` lies in the fine bin of the
+    row of ``s2`` f64[n_rows, E] (squared s edges in Mpc^2) and whose ``mu = |chi_a - chi_b| / S`` lies in the mu bin of
+    ``mu_edges`` f64[n_mu + 1] (``check_mu_edges``; bin 0 is ``[0, mu_1]``, bin j ``(mu_j, mu_{j+1}]``), with no line-of-sight
+    cut (``yawhip_proj_count_smu``). The library receives the squares ``mu_edges * mu_edges`` as float64 products and refuses
+    them if they no longer ascend strictly. Handles, their role and the reach translation are ``count_projected_fine``'s:
+    a layout that was counted in ``r_p`` is not uploaded again. More mu bins than a workgroup's LDS holds at this number of
+    s edges is a ``ValueError`` that states the cap; the library does not split a call and neither does this. No CPU
+    fallback; the CPU tests replace this function."""
+    ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
+    mu_edges = np.asarray(mu_edges, dtype=np.float64)
+    try:
+        return _lib.proj_count_smu(ctx, a, b, cells, s2, mu_edges * mu_edges)
+    except _lib.YawhipError as err:
+        if "do not fit the LDS" in str(err):
+            cap = re.search(r"at most (\d+) mu bins", str(err)).group(1)
+            raise ValueError(f"{len(mu_edges) - 1} mu bins are too many for {np.shape(s2)[1]} s edges (the fine bins of the "
+                             f"configuration's resolution): at most {cap} mu bins fit; use fewer mu bins or a lower resolution") from err
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach((layout_a, layout_b), cosmology, unit, s2)  # the same refusal, with the redshift and the radius
         raise
 
 

@@ -21,12 +21,12 @@ from . import _lib, engine, parallel
 from .angular_bins import plan_for_limits, radial_plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
-from .corrfunc import CorrFunc, ProjectedCorrFunc, ScalarCorrFunc
+from .corrfunc import CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
 from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
-__all__ = ["autocorrelate", "autocorrelate_projected", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
+__all__ = ["autocorrelate", "autocorrelate_projected", "autocorrelate_multipoles", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
            "crosscorrelate_shear", "crosscorrelate_delta_sigma", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "radial_plans", "radial_max_angle", "check_patch_conistency"]
 
@@ -669,6 +669,41 @@ class PatchLinkage:
             raise NotImplementedError("projected counts run in one process on one device")
         pi_max = engine.check_pi_max(pi_max)
         pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
+
+        def call(layout1, layout2, cells, r2, **kwargs):
+            if pi_edges is not None:  # one plane per pi bin
+                return engine.count_projected_pi_fine(layout1, layout2, cells, r2, pi_edges=pi_edges, **kwargs)
+            fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, **kwargs)
+            return np.asarray(fine, dtype=np.float64)[None], stats
+
+        planes = self._count_projected_cells(main_catalog, second_catalog, call, count_type_info, progress)
+        return planes[0] if pi_edges is None else [list(per_pi) for per_pi in zip(*planes)]
+
+    def count_smu_pairs(self, main_catalog: Catalog, second_catalog: Catalog | None = None, *, mu_bins, progress: bool = False,
+                        max_workers: int | None = None, count_type_info: str | None = None) -> list:
+        """Pair counts of one (auto) or two catalogues binned in the redshift-space separation ``s`` and in ``mu = pi / s``:
+        ``s^2 = r_p^2 + pi^2`` with ``r_p = (d_a + d_b) / 2 * theta`` and ``pi = |chi_a - chi_b|`` of
+        ``count_projected_pairs``, and no line-of-sight cut -> a list over scales of lists over mu bins of
+        ``NormalisedCounts``. The scales of the configuration are read as ``s``; ``mu_bins`` (``engine.check_mu_edges``) is
+        a number of equal bins of ``mu`` in [0, 1] or their edges, bin 0 ``[0, mu_1]`` and bin j ``(mu_j, mu_{j+1}]``.
+        Catalogues, cells, recombination (``CombinePlan`` of ``radial_plans``), diagonal slots, linkage and the one-process
+        rule are ``count_projected_pairs``'; every plane is recombined alike and all are over ONE ``PatchedSumWeights``,
+        from one library call (``engine.count_smu_fine``)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("projected counts run in one process on one device")
+        mu_edges = engine.check_mu_edges(mu_bins)
+
+        def call(layout1, layout2, cells, s2, **kwargs):
+            return engine.count_smu_fine(layout1, layout2, cells, s2, mu_edges=mu_edges, **kwargs)
+
+        planes = self._count_projected_cells(main_catalog, second_catalog, call, count_type_info, progress)
+        return [list(per_mu) for per_mu in zip(*planes)]
+
+    def _count_projected_cells(self, main_catalog, second_catalog, call, count_type_info, progress) -> list:
+        """What the counts over projected handles share: the layout checks, the cell list of the linked patch pairs and
+        ``_count_shear_planes`` on the radial plan. ``call(layout1, layout2, cells, r2, cosmology=, unit=, sort_axis=)`` is the
+        engine's count and returns ``(f64[n_planes, n_cells, E-1], CountStats)``. Returns per plane the list over scales of
+        ``NormalisedCounts``, all over one ``PatchedSumWeights``."""
         auto = second_catalog is None
 
         def layouts(num_bins):
@@ -684,20 +719,16 @@ class PatchLinkage:
                 seg2 = (jobs[:, 1:].astype(np.int64) * num_bins + np.arange(num_bins)).ravel()
                 diagonal = (seg1 == seg2) if auto else np.zeros(len(seg1), dtype=bool)
                 cells = np.column_stack([seg1, seg2, np.tile(np.arange(num_bins), len(jobs)), diagonal]).astype(np.int32).reshape(-1, 4)
-                kwargs = dict(cosmology=self.config.cosmology, unit=self.config.scales.scales.unit, sort_axis=sort_axis)
-                if pi_edges is not None:  # one plane per pi bin
-                    fine, stats = engine.count_projected_pi_fine(layout1, layout2, cells, r2, pi_edges=pi_edges, **kwargs)
-                    return (*np.asarray(fine, dtype=np.float64).reshape(len(pi_edges) - 1, len(jobs), num_bins, r2.shape[1] - 1), stats)
-                fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, **kwargs)
-                return np.asarray(fine, dtype=np.float64).reshape(len(jobs), num_bins, r2.shape[1] - 1), stats
+                fine, stats = call(layout1, layout2, cells, r2, cosmology=self.config.cosmology, unit=self.config.scales.scales.unit,
+                                   sort_axis=sort_axis)
+                fine = np.asarray(fine, dtype=np.float64)
+                return (*fine.reshape(len(fine), len(jobs), num_bins, r2.shape[1] - 1), stats)
 
             return count, (layout1, layout2)
 
         catalogs = (main_catalog,) if auto else (main_catalog, second_catalog)
         binning, (layout1, layout2), planes = self._count_shear_planes(catalogs, layouts, count_type_info, progress, radial=True)
-        if pi_edges is None:
-            return _normalised_counts(binning, planes[0], layout1, layout2, auto)
-        return [list(per_pi) for per_pi in zip(*_normalised_counts(binning, planes, layout1, layout2, auto))]
+        return _normalised_counts(binning, planes, layout1, layout2, auto)
 
     def _count_shear_planes(self, catalogs, layouts, count_type_info, progress, radial: bool = False):
         """What the lensing and projected counts share. ``layouts(num_bins)`` makes the caller's layout checks and returns the
@@ -867,6 +898,51 @@ def autocorrelate_projected(config, data: Catalog, random: Catalog, *, pi_max: f
     if pi_edges is None:
         return [CorrFunc(dd, dr, None, rr) for dd, dr, rr in zip(DD, DR, RR)]
     return [ProjectedCorrFunc(pi_edges, [CorrFunc(dd_j, dr_j, None, None if rr is None else rr[j]) for j, (dd_j, dr_j) in enumerate(zip(dd, dr))])
+            for dd, dr, rr in zip(DD, DR, RR)]
+
+
+def autocorrelate_multipoles(config, data: Catalog, random: Catalog, *, mu_bins, count_rr: bool = True, progress: bool = False,
+                             max_workers: int | None = None) -> list:
+    """Redshift-space clustering of ``data``: DD, DR and (optionally) RR binned in the redshift-space separation
+    ``s = sqrt(r_p^2 + pi^2)`` and in ``mu = pi / s``, with ``r_p = (d_a + d_b) / 2 * theta`` and ``pi = |chi_a - chi_b|`` as
+    ``autocorrelate_projected`` has them and no line-of-sight cut -> ``[MultipoleCorrFunc]``, one per scale of the
+    configuration (no counterpart in the reference). ``sample_xi()`` gives ``xi(s, mu_j)`` per mu bin,
+    ``sample(ell)`` the multipole ``xi_ell(s) = (2 ell + 1) sum_j xi_j int_{mu_j}^{mu_{j+1}} P_ell(mu) dmu`` with its jackknife
+    samples, ``sample_multipoles()`` the monopole, quadrupole and hexadecapole.
+
+    ``mu_bins`` is a number ``n >= 1`` of equal bins of ``mu`` in [0, 1], or their edges (from 0 to 1, strictly ascending):
+    bin 0 is ``[0, mu_1]``, bin j ``(mu_j, mu_{j+1}]``; ``mu`` is unsigned. The number of mu bins times the fine bins of the
+    configuration's resolution is capped by the device's LDS (104 mu bins at 12 fine bins, 25 at 50); beyond the cap the
+    call is a ``ValueError`` that states it.
+
+    The scales of the configuration are read as ``s``: in ``kpc`` / ``Mpc`` with ``d = D_A(z)``, in ``kpc/h`` / ``Mpc/h``
+    with the comoving ``d = D_A(z) (1 + z)``; an angular unit is a ``ValueError``. The line-of-sight coordinate is the
+    comoving distance whatever the unit, as for ``w_p``, so the comoving units are the consistent choice for ``s``: with a
+    physical unit the transverse part of ``s`` is physical and the line-of-sight part comoving. Both catalogues need
+    redshifts, finite and ``> 0``. An object so near that the largest ``s`` spans more than 5.73 degrees is a
+    ``ValueError`` that names its redshift.
+
+    Pairs are counted INSIDE a redshift bin of the configuration, as ``autocorrelate_projected`` counts them, on one device
+    of one process: several ranks raise ``NotImplementedError`` (``max_workers`` is accepted and has no effect)."""
+    _require_distinct(data, random)
+    if parallel.world()[1] > 1:
+        raise NotImplementedError("projected counts run in one process on one device")
+    mu_edges = engine.check_mu_edges(mu_bins)
+    engine.radial_kind(config.scales.scales.unit)  # angular units have no radius: ValueError
+    edges, closed = config.binning.edges, config.binning.closed
+    _log_info("building data trees")
+    data_layout = data.build_trees(edges, closed=closed, with_redshifts=True)
+    _log_info("building random trees")
+    random_layout = random.build_trees(edges, closed=closed, with_redshifts=True)
+    for layout in (data_layout, random_layout):
+        engine.check_proj_redshifts(layout)
+    _log_info("computing redshift-space auto-correlation from DD, DR" + (", RR" if count_rr else ""))
+    links = PatchLinkage.from_catalogs(config, data, random, max_angle=radial_max_angle(config, data_layout, random_layout))
+    kwargs = dict(mu_bins=mu_edges, progress=progress, max_workers=max_workers)
+    DD = links.count_smu_pairs(data, count_type_info="DD", **kwargs)
+    DR = links.count_smu_pairs(data, random, count_type_info="DR", **kwargs)
+    RR = links.count_smu_pairs(random, count_type_info="RR", **kwargs) if count_rr else [None] * len(DD)
+    return [MultipoleCorrFunc(mu_edges, [CorrFunc(dd_j, dr_j, None, None if rr is None else rr[j]) for j, (dd_j, dr_j) in enumerate(zip(dd, dr))])
             for dd, dr, rr in zip(DD, DR, RR)]
 
 
