@@ -838,6 +838,60 @@ int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear
                           int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu, const double *m2, double *fine_w,
                           yawhip_stats *stats);
 
+/*
+ * Projected position-shape sums: the tangential and cross ellipticity of the shapes of one catalogue about the objects of
+ * another, binned in each PAIR's own radius and in the line-of-sight separation -- the planes of the intrinsic-alignment
+ * measurement w_g+(r_p) and its null test w_gx(r_p) (measurements.crosscorrelate_alignment; no
+ * counterpart in the reference). Additive to ABI 6: two new symbols.
+ *
+ * yawhip_proj_upload_shapes  yawhip_proj_upload with the shear columns g1, g2 (east / north frame, as yawhip_shear_upload)
+ *                        besides d, c, on the one code path of every upload: the handle keeps x, y, z, w (NULL: every
+ *                        weight 1.0), the products w g1, w g2 each rounded on its own (as a handle of yawhip_shear_upload
+ *                        makes them), d and c as they came and, per redshift bin, the minimum of d over all patches. g1, g2
+ *                        or c not finite, or a d that is not finite and > 0: YAWHIP_ERR_INVALID (a host pass before any
+ *                        device work). The handle is MARKED as a shape handle: freed by yawhip_shear_free, and refused by
+ *                        every other count of this header (YAWHIP_ERR_MISMATCH).
+ * yawhip_proj_count_shear    dens: a handle of yawhip_proj_upload, as it is -- a density sample or its randoms that sit on
+ *                        the device for yawhip_proj_count are not uploaded again; shapes: a handle of
+ *                        yawhip_proj_upload_shapes. The wrong kind in either slot is YAWHIP_ERR_MISMATCH. Cell
+ *                        c = (segment of dens, segment of shapes, row, 0): the fourth entry must be 0, two handles of
+ *                        different kinds never pair a segment with itself (else YAWHIP_ERR_INVALID). With a the shape and b
+ *                        the density object, s2, D, DD, q, th2, R2 and the fine bin e are exactly yawhip_proj_count's, p and
+ *                        j exactly yawhip_proj_count_pi's (float64, every operation rounded on its own, nothing contracted):
+ *       p = fabs(c_a - c_b);   j = the number of edges pe[1 .. n_pi] that are < p;   the pair counts  iff  j < n_pi
+ *       pa = ax by - ay bx;   dot = ax bx + ay by;   pb = (ax ax + ay ay) bz - az dot
+ *       a2 = pa pa;   b2 = pb pb;   den = a2 + b2
+ *       den != 0:   c2 = (a2 - b2) / den;   s2p = ((2 pa) pb) / den
+ *                   tv = -(wg1_a c2 + wg2_a s2p);   xv = wg1_a s2p - wg2_a c2
+ *                   T[j][c][e] += w_b tv;   X[j][c][e] += w_b xv
+ *       W[j][c][e] += w_b w_a                                     (den == 0, the shape on a pole of the frame: W only)
+ *     This is yawhip_shear_count's pair term, term for term, with the density object in the place of the lens: T is the
+ *     tangential ellipticity of the shape about the density object (negative for a shape that points at it). A shape and a
+ *     density object at one sky position have R2 == 0 and are in no bin, so a sample that serves as both sides never pairs
+ *     an object with itself. Consequences: with g == 0 T and X are exactly 0; (g1, g2) -> (-g2, g1) gives T' == -X and
+ *     X' == T bit for bit; over unit weights W equals yawhip_proj_count_pi's planes on the shapes' (x, y, z, w, d, c) as
+ *     integers, and candidate_pairs and evaluated_pairs equal that call's.
+ *   n_pi, pe     as yawhip_proj_count_pi; the single cylinder |pi| <= pmax is n_pi = 1, pe = {0, pmax}
+ *   the cap      the carve-up of yawhip_proj_count_pi with three planes per pi bin:
+ *                  24576 + 8 (((n_edges + 1) & ~1) + ((n_pi + 2) & ~1)) + 96 n_pi (n_edges - 1) <= 65536
+ *                -- n_pi <= 35 at 13 edges, <= 8 at 51, <= 1 at 256, <= 393 at 2. A larger n_pi is YAWHIP_ERR_INVALID with a
+ *                message that names the largest n_pi that fits at this n_edges; the library does not split a call.
+ *   fine         float64[3][n_pi][n_cells][n_edges - 1] (host), the planes in the order T, X, W; every element is written
+ *   checks       those of yawhip_proj_count_pi in its order, with the two kinds where that call asks for two projected
+ *                handles. r2, the reach rule and its refusal, stats, n_cells == 0: as yawhip_proj_count_pi. The per-call
+ *                device buffers are those of dens.
+ * Kernel: yawhip_proj_count_pi's walk with dens streamed and the shapes in the lanes; its loop up to the wave-wide test is
+ * unchanged (fl(DD s2) against the row's last edge, an exact superset). Behind it R2 and p are bisected as there, and only a
+ * pair that counts is rotated. Accumulation and reproducibility as yawhip_shear_count: per-wave LDS histograms, folded in a
+ * fixed order, plain stores.
+ */
+int yawhip_proj_upload_shapes(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                              const double *g1, const double *g2, const double *d, const double *c, int32_t n_patches, int32_t n_bins,
+                              const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out);
+int yawhip_proj_count_shear(yawhip_ctx *ctx, yawhip_shear_sources *dens, yawhip_shear_sources *shapes, int32_t n_cells,
+                            const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe,
+                            double *fine, yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,10 +20,10 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
+from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_multipoles, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
-                           crosscorrelate_delta_sigma, crosscorrelate_shear)
+                           crosscorrelate_alignment, crosscorrelate_delta_sigma, crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -31,6 +31,7 @@ from .redshifts import HistData, RedshiftData
 __version__ = "0.1.0"
 
 __all__ = [
+    "AlignmentCorrFunc",
     "AngularCoordinates",
     "AngularDistances",
     "Binning",
@@ -59,6 +60,7 @@ __all__ = [
     "correlate_shear_tomographic",
     "compute_scalar_normalisation",
     "crosscorrelate",
+    "crosscorrelate_alignment",
     "crosscorrelate_scalar",
     "crosscorrelate_scalar_map",
     "crosscorrelate_delta_sigma",

@@ -72,6 +72,8 @@ ABI_SYMBOLS = (
     "yawhip_proj_count",
     "yawhip_proj_count_pi",
     "yawhip_proj_count_smu",
+    "yawhip_proj_upload_shapes",
+    "yawhip_proj_count_shear",
 )
 
 
@@ -306,6 +308,9 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_proj_count_pi.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
                                          _dp, ctypes.POINTER(_Stats)]
     lib.yawhip_proj_count_smu.argtypes = lib.yawhip_proj_count_pi.argtypes
+    lib.yawhip_proj_upload_shapes.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32,
+                                              _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
+    lib.yawhip_proj_count_shear.argtypes = lib.yawhip_proj_count_pi.argtypes
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -871,9 +876,20 @@ class ProjHandle(ShearSources):
         self._prepare(ctx, (x, y, z, w, d, c), None, n_patches, n_bins, offsets, sort_axis)("yawhip_proj_upload")
 
 
+class ProjShapesHandle(ShearSources):
+    """The shapes of ``proj_count_shear`` resident in HBM (``yawhip_proj_upload_shapes``): every (patch, bin) segment sorted
+    along ``sort_axis`` -- unit vectors, weights (or None), the shear components ``g1, g2`` (east / north frame, finite; the
+    handle keeps the products ``w g1, w g2`` as a ``ShearSources`` does) and the two columns ``d, c`` of a ``ProjHandle``, kept
+    as they come. The handle is a ``yawhip_shear_sources`` of the shape kind: it is freed like any, and every other count
+    refuses it."""
+
+    def __init__(self, ctx: Context, x, y, z, w, g1, g2, d, c, n_patches: int, n_bins: int, offsets, sort_axis: int = 2):
+        self._prepare(ctx, (x, y, z, w, g1, g2, d, c), None, n_patches, n_bins, offsets, sort_axis)("yawhip_proj_upload_shapes")
+
+
 def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
                   rows: str = "thresholds must be [n_bins, n_edges]", stacked: bool = False):
-    """What the eight counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+    """What the nine counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
     ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
     entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
     and the ``CountStats``. ``stacked``: the symbol takes the planes as ONE array f64[n_planes, ...], which is what comes
@@ -909,6 +925,22 @@ def proj_count_pi(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pi_edge
     n_pi = len(pe) - 1
     return _shear_counts("yawhip_proj_count_pi", max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp), width=4,
                          rows="r2 must be [n_rows, n_edges]", stacked=True)
+
+
+def proj_count_shear(ctx: Context, dens: ProjHandle, shapes: ProjShapesHandle, cells, r2, pi_edges):
+    """Run ``yawhip_proj_count_shear``: the shapes of ``shapes`` rotated to the great circle through each pair with an object of
+    ``dens``, binned as ``proj_count_pi`` bins the pair. cells int[n_cells, 4] = ``(segment of dens, segment of shapes, row,
+    0)``; ``r2`` and ``pi_edges`` as ``proj_count_pi``. Returns ``((T, X, W), CountStats)``, each plane f64[n_pi, n_cells, E-1]:
+    the sums of ``w_d w_s e_t``, ``w_d w_s e_x`` and ``w_d w_s`` with ``e_t`` the tangential ellipticity of the shape about the
+    density object (negative where the shape points at it). ``3 n_pi (E - 1)`` is capped by the LDS of a workgroup
+    (include/yawhip.h); beyond it the library refuses."""
+    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
+    if pe.ndim != 1:
+        raise ValueError("pi_edges must be [n_pi + 1]")
+    n_pi = len(pe) - 1
+    fine, stats = _shear_counts("yawhip_proj_count_shear", 3 * max(n_pi, 0), (ctx._h, dens._h, shapes._h), cells, r2, n_pi, _ptr(pe, _dp),
+                                width=4, rows="r2 must be [n_rows, n_edges]", stacked=True)
+    return tuple(fine.reshape(3, max(n_pi, 0), *fine.shape[1:])), stats
 
 
 def proj_count_smu(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, m2):

@@ -7,7 +7,7 @@ import numpy as np
 from .corrdata import CorrData
 from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "AlignmentCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -339,3 +339,116 @@ class MultipoleCorrFunc:
 
     def patches_subset(self, item):
         return type(self)(self.mu_edges, [cf.patches_subset(item) for cf in self.mu_bins])
+
+
+class AlignmentCorrFunc:
+    """The sums of one scale of the projected position-shape correlation (``crosscorrelate_alignment``; no counterpart in the
+    reference): ``pi_edges`` f64[n_pi + 1], from 0 and strictly ascending, and ``pi_bins``, a tuple of ``n_pi`` dicts of
+    ``NormalisedCounts`` -- bin 0 holds the pairs with ``pi`` in ``[0, pe[1]]``, bin j those in ``(pe[j], pe[j + 1]]``. Each
+    dict holds the planes of shapes x density, ``t_sd``, ``x_sd``, ``w_sd``, those of shapes x density randoms, ``t_sr``,
+    ``x_sr``, ``w_sr`` (T and X are signed sums), and optionally ``rr``, the pair count of shape randoms x density randoms.
+    The slot ``[bin, p, q]`` of every tensor pairs patch ``p`` of the density side with patch ``q`` of the shape side.
+
+    Sign convention: the device sums the TANGENTIAL ellipticity ``e_t`` of a shape about the density object, which is
+    negative for a shape that points at it. ``w_g+`` is positive for radial alignment, so the sign is flipped here, once:
+    with ``/n`` the division by the product of the two weight sums of the redshift bin and ``N`` the normalising pair count
+    -- ``rr`` where given, else ``w_sr`` -- per pi bin j, for the data and every jackknife sample separately,
+
+        xi_plus_j  = -(t_sd/n - t_sr/n) / (N/n)
+        xi_cross_j =  (x_sd/n - x_sr/n) / (N/n)
+        sample("plus" | "cross") = 2 sum_j dpi_j xi_j     -> w_g+(r_p), w_gx(r_p)
+
+    ``sample_xi(component)`` gives the pi bins. An empty ``N`` gives NaN there and in the sum: nothing is masked.
+    ``to_dict`` / ``from_dict``, ``==``, ``is_compatible`` and the bin and patch subsets go bin by bin."""
+
+    __slots__ = ("pi_edges", "pi_bins")
+    _required = ("t_sd", "x_sd", "w_sd", "t_sr", "x_sr", "w_sr")
+
+    def __init__(self, pi_edges, pi_bins) -> None:
+        edges = np.array(pi_edges, dtype=np.float64)
+        bins = tuple(dict(planes) for planes in pi_bins)
+        if edges.ndim != 1 or len(edges) != len(bins) + 1 or len(bins) < 1:
+            raise ValueError("'pi_edges' must hold one edge more than there are pi bins, and there is at least one bin")
+        if edges[0] != 0.0 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0):
+            raise ValueError("'pi_edges' must start at 0, be finite and ascend strictly")
+        first = bins[0].get("t_sd")
+        for planes in bins:
+            if planes.keys() != bins[0].keys() or not set(self._required) <= planes.keys() <= {*self._required, "rr"}:
+                raise ValueError(f"every pi bin holds the planes {self._required}, and all or none of them 'rr'")
+            for kind, counts in planes.items():
+                if type(counts) is not NormalisedCounts:
+                    raise TypeError(f"the planes must be of type {NormalisedCounts}")
+                try:
+                    first.is_compatible(counts, require=True)
+                except ValueError as err:
+                    raise ValueError(f"plane '{kind}' and 't_sd' of the first pi bin are not compatible") from err
+        edges.setflags(write=False)
+        self.pi_edges = edges
+        self.pi_bins = bins
+
+    def __repr__(self) -> str:
+        return (f"{type(self).__name__}(num_pi={self.num_pi}, pi_max={self.pi_edges[-1]}, planes={'|'.join(self.pi_bins[0])}, "
+                f"binning={self.binning}, num_patches={self.num_patches})")
+
+    binning = property(lambda self: self.pi_bins[0]["t_sd"].binning)
+    num_patches = property(lambda self: self.pi_bins[0]["t_sd"].num_patches)
+    num_bins = property(lambda self: len(self.binning))
+    num_pi = property(lambda self: len(self.pi_bins))
+
+    def to_dict(self) -> dict:
+        return dict(pi_edges=self.pi_edges.copy(), pi_bins=[dict(planes) for planes in self.pi_bins])
+
+    @classmethod
+    def from_dict(cls, state: dict):
+        return cls(state["pi_edges"], state["pi_bins"])
+
+    def __eq__(self, other) -> bool:
+        if type(self) is not type(other):
+            return NotImplemented
+        return (np.array_equal(self.pi_edges, other.pi_edges) and len(self.pi_bins) == len(other.pi_bins)
+                and all(mine.keys() == theirs.keys() and all(mine[k] == theirs[k] for k in mine)
+                        for mine, theirs in zip(self.pi_bins, other.pi_bins)))
+
+    def is_compatible(self, other, *, require: bool = False) -> bool:
+        if type(self) is not type(other):
+            if require:
+                raise TypeError(f"{type(other)} is not compatible with {type(self)}")
+            return False
+        if not np.array_equal(self.pi_edges, other.pi_edges):
+            if require:
+                raise ValueError("the pi edges differ")
+            return False
+        return self.pi_bins[0]["t_sd"].is_compatible(other.pi_bins[0]["t_sd"], require=require)
+
+    @staticmethod
+    def _component(component: str):
+        if component not in ("plus", "cross"):
+            raise ValueError(f"component must be 'plus' or 'cross', not {component!r}")
+        return ("t", -1.0) if component == "plus" else ("x", 1.0)
+
+    def sample_xi(self, component: str = "plus") -> list:
+        """``xi_plus_j`` or ``xi_cross_j`` per pi bin as ``CorrData``, for the data and every jackknife sample."""
+        plane, sign = self._component(component)
+        out = []
+        for planes in self.pi_bins:
+            sd, sr = planes[f"{plane}_sd"].sample_patch_sum(), planes[f"{plane}_sr"].sample_patch_sum()
+            norm = planes.get("rr", planes["w_sr"]).sample_patch_sum()
+            with np.errstate(divide="ignore", invalid="ignore"):  # an empty N: NaN, whatever the numerator holds
+                data = np.where(norm.data == 0.0, np.nan, sign * (sd.data - sr.data) / norm.data)
+                samples = np.where(norm.samples == 0.0, np.nan, sign * (sd.samples - sr.samples) / norm.samples)
+            out.append(CorrData(self.binning, data, samples))
+        return out
+
+    def sample(self, component: str = "plus") -> CorrData:
+        """``w_g+(r_p)`` ("plus") or ``w_gx(r_p)`` ("cross"): ``2 sum_j dpi_j xi_j``, summed in the order of the pi bins for
+        the data and for each jackknife sample separately; errors and covariance are those of the summed samples."""
+        data, samples = 0.0, 0.0
+        for dpi, xi in zip(np.diff(self.pi_edges), self.sample_xi(component)):
+            data, samples = data + dpi * xi.data, samples + dpi * xi.samples
+        return CorrData(self.binning, 2.0 * data, 2.0 * samples)
+
+    def bins_subset(self, item):
+        return type(self)(self.pi_edges, [{k: c.bins_subset(item) for k, c in planes.items()} for planes in self.pi_bins])
+
+    def patches_subset(self, item):
+        return type(self)(self.pi_edges, [{k: c.patches_subset(item) for k, c in planes.items()} for planes in self.pi_bins])

@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (the yawhip_shear_*, yawhip_dsigma_* and yawhip_proj_* calls of include/yawhip.h; DESIGN.md
-// sections 15 to 23): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
+// sections 15 to 24): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -17,6 +17,7 @@ enum Kind : unsigned {
     DSIGMA_LENSES = 4,   // yawhip_dsigma_upload_lenses: the two columns are f, c as they came
     RADIAL_LENSES = 8,   // yawhip_dsigma_upload_lenses_radial: such lenses with the column m besides
     PROJECTED = 16,      // yawhip_proj_upload: the two columns are d, c as they came
+    PROJECTED_SHAPES = 32,  // yawhip_proj_upload_shapes: the two columns are w g1, w g2, with d in the column u and c in m
 };
 }  // namespace yawhip_detail
 
@@ -29,8 +30,8 @@ struct yawhip_shear_sources {
     int axis = 2;                               // coordinate the patch segments are sorted by (0 = x, 1 = y, 2 = z)
     yawhip_detail::DevPtr<double> x, y, z, w;   // w may be null (every weight 1.0)
     yawhip_detail::DevPtr<double> wg1, wg2;     // the kind's two columns (a, b); the products w * g1, w * g2 each rounded on its own
-    yawhip_detail::DevPtr<double> u, m;         // u: DSIGMA_SOURCES only; m: RADIAL_LENSES only
-    std::vector<double> least;                  // RADIAL_LENSES, PROJECTED: least m or d per redshift bin over all patches [nb] (+inf: none)
+    yawhip_detail::DevPtr<double> u, m;         // u: DSIGMA_SOURCES (u), PROJECTED_SHAPES (d); m: RADIAL_LENSES (m), PROJECTED_SHAPES (c)
+    std::vector<double> least;                  // RADIAL_LENSES, PROJECTED, PROJECTED_SHAPES: least m or d per redshift bin over all patches [nb] (+inf: none)
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;                 // the same on the host
     // per-call buffers of the counts (grow-only; a count over jobs uses those of its sources, one over cells those of its first handle)

@@ -10,10 +10,12 @@
 // line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected), and those binned in the
 // line-of-sight separation besides (yawhip_proj_count_pi; autocorrelate_projected(pi_bins=...)), and
 // the pair counts of the same handles binned in the redshift-space separation s and in mu = pi / s (yawhip_proj_count_smu;
-// measurements.autocorrelate_multipoles).
+// measurements.autocorrelate_multipoles), and the projected position-shape sums of a shape catalogue
+// with d, c around such handles, the tangential and cross ellipticity per radius and pi bin (yawhip_proj_count_shear;
+// measurements.crosscorrelate_alignment).
 // include/yawhip.h has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under eight thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under nine thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -50,6 +52,8 @@
 // RedshiftSpace (k_count_smu) is Projected with the call's n_mu planes and no cut: the ballot holds fl(DD s2) + P2,
 // P2 = |c_a - c_b|^2 with c read in the hot loop, against the row's last squared s; the pair is binned by S2 = R2 + P2 and goes
 // to the plane that the staged squared mu edges give for P2 against m2 S2 (at the policy).
+// ProjectedShear (k_count_projected_shear) is ProjectedPi with a projected handle streamed and a shape handle (w g1, w g2 | d, c)
+// in the lanes, no diagonal cells and three planes T, X, W per pi bin: the pair that counts gets Tangential's rotation.
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -72,7 +76,7 @@
 //
 //   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products (a lens
 //                    handle keeps its two columns f, c as they came).
-//   k_gather_column  the same gather of the sources' column u and of a radial lens handle's column m.
+//   k_gather_column  the same gather of the sources' column u, of a radial lens handle's column m and of a shape handle's d, c.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -149,6 +153,11 @@ struct ChordBinned {
     static constexpr bool CAPPED = true;
     static constexpr bool KEPT_WORK = false;  // the evaluated separations of a diagonal cell: all of them (else: kept_work)
     static constexpr bool ADD_BINNED = false;  // a policy with the call's planes whose add() takes what binned() gave
+    static constexpr int PER_BIN = 1;  // a policy with the call's planes: the planes per bin of the call (lds_bytes, run_count)
+    // what the walk keeps of a lane's object: a Lane, or a policy's own type that holds more columns and is made from it
+    using LaneT = Lane;
+    template <class L>
+    static __device__ __forceinline__ Lane lane(const L &, int64_t, bool, const Lane &a) { return a; }
     template <class B>
     static __device__ __forceinline__ double outer(const Lane &, const B &, double s) { return s; }
     template <class B>
@@ -418,16 +427,19 @@ struct ProjectedPi : Projected {
         for (int j = tid; j <= src.n_pi; j += WG) ext[j] = src.pe[j];
     }
     static __device__ double lane_u(const ProjPiLanes &src, int64_t, bool) { return src.pmax; }  // call-wide: a scalar register
-    // pe: the staged edges in LDS
-    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int n_pi) {
-        const double p = fabs(a.g2 - b.c);
+    // the plane of p over the staged edges pe (LDS); n_pi: the pair does not count. pmax: pe[n_pi], the lane's u
+    static __device__ __forceinline__ int plane(const double *pe, int n_pi, double p, double pmax) {
         // the inner edges pe[1 .. n_pi - 1] below p (they ascend), by bisection; a pair beyond pe[n_pi] -- the lane's u, as
         // Projected's pmax; most pairs behind the ballot -- starts past them and bisects nothing
-        int j = a.u < p ? n_pi : 0, hi = n_pi - 1;
+        int j = pmax < p ? n_pi : 0, hi = n_pi - 1;
         while (j < hi) {
             const int mid = (j + hi) >> 1;
             if (pe[mid + 1] < p) j = mid + 1; else hi = mid;
         }
+        return j;
+    }
+    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int n_pi) {
+        const int j = plane(pe, n_pi, fabs(a.g2 - b.c), a.u);
         if (j < n_pi) atomicAdd(&wh[j * nf + e], a.w * b.w);
     }
 };
@@ -498,6 +510,69 @@ struct RedshiftSpace : Projected {
     }
 };
 
+// The lanes of the projected position-shape count: a shape handle (wg1, wg2 hold w g1, w g2; d and c are columns of their own)
+// with the call's pi edges, as ProjPiLanes has them.
+struct ProjShapeLanes : ProjPiLanes {
+    const double *d, *c;
+};
+
+// What a lane of that count keeps besides: its d and c, which a projected handle has where the shape handle has its shear,
+// and the call's n_pi (call-wide: a scalar register, as the lane's u is), since the walk hands add() all 3 n_pi planes.
+struct ShapeLane : Lane {
+    double d, c;
+    int n_pi;
+};
+
+// The tangential and cross ellipticity of shapes about the objects of a projected handle, binned in each pair's own radius
+// and in the line-of-sight separation (k_count_projected_shear). The streamed side is the projected
+// handle -- object, load, cells and window rule are ProjectedPi's, the hot loop up to the ballot too: it holds fl(DD s2)
+// against the last edge, and Projected's proof of the exact superset applies unchanged, with the lane's d in the place of
+// its g1. Two handles of different kinds never pair a segment with itself: no diagonal cells. Behind the ballot R2 is
+// bisected over the row, then p = |c_a - c_b| over the staged edges by ProjectedPi::plane, and only a pair that
+// counts (j < n_pi) gets Tangential's rotation, term for term: T is the tangential ellipticity of the shape a about the
+// streamed object b. The planes are [3][n_pi] per wave, T, X, W: plane (t, j) sits at (t n_pi + j) nf.
+struct ProjectedShear : ProjectedPi {
+    using Lanes = ProjShapeLanes;
+    using LaneT = ShapeLane;
+    static constexpr bool DIAGONAL = false;
+    static constexpr int PER_BIN = 3;  // T, X, W
+    static __device__ __forceinline__ int planes(const ProjShapeLanes &src) { return 3 * src.n_pi; }
+    static __device__ __forceinline__ ShapeLane lane(const ProjShapeLanes &src, int64_t i, bool ok, const Lane &a) {
+        return ShapeLane{a, ok ? src.d[i] : 0.0, ok ? src.c[i] : 0.0, src.n_pi};  // (a padded lane: as Projected parks it)
+    }
+    static __device__ __forceinline__ double pair_dd(const ShapeLane &a, const ObjP &b) {
+        const double D = 0.5 * (a.d + b.d);
+        return D * D;
+    }
+    static __device__ __forceinline__ double outer(const ShapeLane &a, const ObjP &b, double s) { return pair_dd(a, b) * s; }
+    static __device__ __forceinline__ double binned(const ShapeLane &a, const ObjP &b, double s) { return pair_dd(a, b) * squared_angle(s); }
+    // pe: the staged edges in LDS (the walk's count of planes, 3 n_pi, is not used)
+    static __device__ void add(const ShapeLane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int) {
+        const int n_pi = a.n_pi;
+        const int j = plane(pe, n_pi, fabs(a.c - b.c), a.u);
+        if (j < n_pi) {
+            double *const bin = wh + j * nf + e;
+            const int plane = n_pi * nf;
+            const double pa = a.x * b.y - a.y * b.x;
+            const double dot = a.x * b.x + a.y * b.y;
+            const double pb = a.rho2 * b.z - a.z * dot;
+            const double a2 = pa * pa;
+            const double b2 = pb * pb;
+            const double den = a2 + b2;
+            // den == 0 (the shape on a pole of the frame) adds to W only: as a select, T and X get a zero that changes no sum,
+            // since a third nested branch costs the exec masks that spill the walk's scalar registers (ProjectedPi::add)
+            const bool rotated = den != 0.0;
+            const double c2 = (a2 - b2) / den;
+            const double s2 = ((2.0 * pa) * pb) / den;
+            const double tv = rotated ? -(a.g1 * c2 + a.g2 * s2) : 0.0;
+            const double xv = rotated ? a.g1 * s2 - a.g2 * c2 : 0.0;
+            atomicAdd(bin, b.w * tv);
+            atomicAdd(bin + plane, b.w * xv);
+            atomicAdd(bin + 2 * plane, b.w * a.w);
+        }
+    }
+};
+
 // The separations of a diagonal cell's lane tile [ta, t_last] against the streamed objects [b0, b1), b0 > ta, that the index
 // test can keep -- the streamed index larger than the lane's: what a policy with KEPT_WORK reports as evaluated, so that a
 // cell's figure never exceeds its unordered pairs. (The waves evaluate the others of the tile's own range too, and drop them.)
@@ -513,23 +588,28 @@ __device__ __forceinline__ unsigned long long kept_work(int64_t ta, int64_t t_la
 }
 
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk);
-// a policy with the call's planes (PLANES == 0) has n_pi of them and its pi edges between the thresholds and the histograms
+// a policy with the call's planes (PLANES == 0) has PER_BIN n_pi of them and its pi edges between the thresholds and the histograms
 template <class P>
 constexpr size_t lds_bytes(int n_edges, int n_pi = 0) {
-    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)n_pi, extra = P::PLANES ? 0 : (size_t)pi_slots(n_pi);
+    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)P::PER_BIN * n_pi, extra = P::PLANES ? 0 : (size_t)pi_slots(n_pi);
     return 2 * STAGE * sizeof(typename P::Streamed) + ((size_t)((n_edges + 1) & ~1) + extra) * sizeof(double) +
            (size_t)WAVES * planes * (n_edges - 1) * sizeof(double);
 }
 constexpr size_t LDS_LIMIT = 64 * 1024;  // of dynamic LDS per workgroup, without asking for more
 
-// the largest n_pi of ProjectedPi whose carve-up fits LDS_LIMIT at n_edges: 0 if not even one plane does
-constexpr int max_pi_planes(int n_edges) {
+// the largest n_pi of a policy with the call's planes whose carve-up fits LDS_LIMIT at n_edges: 0 if not even one bin does
+template <class P>
+constexpr int max_bins(int n_edges) {
     int n = 0;
-    while (lds_bytes<ProjectedPi>(n_edges, n + 1) <= LDS_LIMIT) ++n;
+    while (lds_bytes<P>(n_edges, n + 1) <= LDS_LIMIT) ++n;
     return n;
 }
+constexpr int max_pi_planes(int n_edges) { return max_bins<ProjectedPi>(n_edges); }
 static_assert(max_pi_planes(MAX_EDGES) == 4 && max_pi_planes(13) == 104 && max_pi_planes(2) == 1023,
               "ProjectedPi: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 22 quote it)");
+static_assert(max_bins<ProjectedShear>(MAX_EDGES) == 1 && max_bins<ProjectedShear>(51) == 8 && max_bins<ProjectedShear>(13) == 35 &&
+                  max_bins<ProjectedShear>(2) == 393,
+              "ProjectedShear: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 24 quote it)");
 static_assert(lds_bytes<RedshiftSpace>(13, 104) == lds_bytes<ProjectedPi>(13, 104) && lds_bytes<RedshiftSpace>(51, 25) == lds_bytes<ProjectedPi>(51, 25) &&
                   lds_bytes<RedshiftSpace>(MAX_EDGES, 4) == lds_bytes<ProjectedPi>(MAX_EDGES, 4),
               "RedshiftSpace: its carve-up is ProjectedPi's, so that max_pi_planes caps n_mu too (DESIGN.md section 23)");
@@ -642,7 +722,7 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
         const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
         const double ag1 = ok ? src.wg1[ia] : 0.0;
         const double ag2 = ok ? src.wg2[ia] : 0.0;
-        const Lane a{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay, P::lane_u(src, ia, ok)};
+        const typename P::LaneT a = P::lane(src, ia, ok, Lane{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay, P::lane_u(src, ia, ok)});
         // a diagonal cell counts the streamed object i of a stage only for lanes with ia < its index: i > ia - (first of stage)
         const int64_t lane_rel = diag ? ia - b0 : (int64_t)-1 - (int64_t)STAGE;
 
@@ -773,6 +853,15 @@ __global__ __launch_bounds__(WG) void k_count_smu(ShearView a, SmuLanes b, const
     shear_walk<RedshiftSpace>(a, b, cells, 0, n_edges, s2, rwin, n_cells, out, evaluated);
 }
 
+// out: [3][n_pi][n_cells][E-1] (T, X, W per pi bin); cells: [n_cells][4] (ShearPair::cell, no diagonal ones); the projected
+// handle a is streamed, the shape handle b sits in the lanes with its d, c and the call's pi edges
+__global__ __launch_bounds__(WG) void k_count_projected_shear(ShearView a, ProjShapeLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                              const double *__restrict__ r2, const double *__restrict__ rwin,
+                                                              int64_t n_cells, double *__restrict__ out,
+                                                              unsigned long long *__restrict__ evaluated) {
+    shear_walk<ProjectedShear>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
 }  // namespace
 
 extern "C" {
@@ -793,10 +882,11 @@ namespace {
 
 // The upload of every entry point: a handle of `kind` with n_bins segments per patch, each sorted along sort_axis and
 // gathered. a, b: the kind's two columns, gathered as the products w a, w b for the two kinds of shear catalogue and as they
-// came for the others; extra: the column u of DSIGMA_SOURCES or m of RADIAL_LENSES, else NULL
+// came for the others; extra: the column u of DSIGMA_SOURCES, m of RADIAL_LENSES or d of PROJECTED_SHAPES, else NULL; extra2:
+// the column c of PROJECTED_SHAPES, else NULL
 int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                    const double *w, const double *a, const double *b, const double *extra, int32_t n_patches, int32_t n_bins,
-                    const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
+                    const double *w, const double *a, const double *b, const double *extra, const double *extra2, int32_t n_patches,
+                    int32_t n_bins, const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
     if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
     *out = nullptr;
     if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
@@ -818,8 +908,8 @@ int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const
     s->nb = n_bins;
     s->axis = sort_axis;
     // the kinds counted in a radius keep the least entry per redshift bin of the column that bounds their reach (chord_reach)
-    const bool has_least = (kind & (RADIAL_LENSES | PROJECTED)) != 0;
-    const double *scale = kind == RADIAL_LENSES ? extra : a;
+    const bool has_least = (kind & (RADIAL_LENSES | PROJECTED | PROJECTED_SHAPES)) != 0;
+    const double *scale = kind == PROJECTED ? a : extra;
     try {
         s->h_off.assign(offsets, offsets + n_seg + 1);
         if (has_least) s->least.assign((size_t)n_bins, INFINITY);  // (n == 0: the column may be NULL, and no segment reads it)
@@ -830,17 +920,19 @@ int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const
     for (int64_t seg = 0; has_least && seg < n_seg; ++seg)
         for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i)
             s->least[(size_t)(seg % n_bins)] = std::min(s->least[(size_t)(seg % n_bins)], scale[i]);
-    DevPtr<double> *const d_extra = kind == DSIGMA_SOURCES ? &s->u : kind == RADIAL_LENSES ? &s->m : nullptr;
+    DevPtr<double> *const d_extra = (kind & (DSIGMA_SOURCES | PROJECTED_SHAPES)) ? &s->u : kind == RADIAL_LENSES ? &s->m : nullptr;
+    DevPtr<double> *const d_extra2 = kind == PROJECTED_SHAPES ? &s->m : nullptr;
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
-    constexpr int NC = 7;
-    DevPtr<double> raw[NC];  // x, y, z, a, b, w, extra as they came (temporary)
-    const double *host[NC] = {x, y, z, a, b, w, extra};
+    constexpr int NC = 8;
+    DevPtr<double> raw[NC];  // x, y, z, a, b, w, extra, extra2 as they came (temporary)
+    const double *host[NC] = {x, y, z, a, b, w, extra, extra2};
     DevPtr<uint32_t> perm;
     hipError_t e = hipSuccess;
     for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
         if (e == hipSuccess) e = c->alloc(n1);
     if (e == hipSuccess && w) e = s->w.alloc(n1);
     if (e == hipSuccess && d_extra) e = d_extra->alloc(n1);  // (an empty handle of the kind has the column too)
+    if (e == hipSuccess && d_extra2) e = d_extra2->alloc(n1);
     if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
     for (int c = 0; c < NC; ++c)
         if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
@@ -853,11 +945,16 @@ int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const
         e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_seg, perm);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
-                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2, (kind & (SHEAR | DSIGMA_SOURCES)) != 0);
+                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2,
+                               (kind & (SHEAR | DSIGMA_SOURCES | PROJECTED_SHAPES)) != 0);
             e = hipGetLastError();
         }
         if (e == hipSuccess && d_extra) {
             hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], *d_extra);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && d_extra2) {
+            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[7], *d_extra2);
             e = hipGetLastError();
         }
     }
@@ -996,7 +1093,7 @@ ShearView view_of(const yawhip_shear_sources *s) {
 // in d_out (P::PLANES planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[], the
 // counters and the event time to the statistics. n_rows: the rows of t; reach[k]: the largest squared chord of a pair in
 // range of row k where the row's last edge is not that (chord_reach), or NULL. A policy with the call's planes (PLANES == 0)
-// has n_pi of them, contiguous in fine[0], and its edges pe[n_pi + 1] travel in d_in between the half widths and the table.
+// has PER_BIN n_pi of them, contiguous in fine[0], and its edges pe[n_pi + 1] travel in d_in between the half widths and the table.
 struct Slots {  // what run_count has on the device for the kernel
     const int32_t *table;
     const double *t, *rwin, *pe;
@@ -1011,7 +1108,7 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, si
               std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Pass pass, int32_t n_pi = 0, const double *pe = nullptr) {
     if (stats) *stats = yawhip_stats{};
     if (n_cells == 0) return YAWHIP_OK;
-    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)n_pi, n_pe = pe ? (size_t)n_pi + 1 : 0;
+    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)P::PER_BIN * n_pi, n_pe = pe ? (size_t)n_pi + 1 : 0;
     const size_t n_t = (size_t)n_rows * n_edges, in_bytes = (n_t + (size_t)n_rows + n_pe) * sizeof(double) + n_table * sizeof(int32_t);
     const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = planes * plane;
     std::vector<unsigned char> h_in;
@@ -1107,6 +1204,16 @@ int check_proj_cells(const char *fn, const yawhip_shear_sources *a, const yawhip
     return chord_reach(fn, "an object", "row", n_rows, n_edges, r2, reach);
 }
 
+// the pi edges pe[n_pi + 1] of the two counts binned in the line-of-sight separation
+int check_pi_edges(const char *fn, int32_t n_pi, const double *pe) {
+    if (n_pi < 1 || !pe) return fail(YAWHIP_ERR_INVALID, "%s: n_pi must be >= 1 and pe not NULL (n_pi=%d)", fn, n_pi);
+    if (pe[0] != 0.0) return fail(YAWHIP_ERR_INVALID, "%s: the first pi edge must be 0", fn);
+    for (int j = 1; j <= n_pi; ++j)  // (a NaN fails either comparison)
+        if (!(pe[j] > pe[j - 1]) || (j < n_pi && !std::isfinite(pe[j])))
+            return fail(YAWHIP_ERR_INVALID, "%s: the pi edges must be finite (the last may be +inf) and strictly ascending (edge %d)", fn, j);
+    return YAWHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1114,13 +1221,13 @@ extern "C" {
 int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                         const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
                         yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, n_patches, 1, offsets, sort_axis, out);
+    return upload_segments("yawhip_shear_upload", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, nullptr, n_patches, 1, offsets, sort_axis, out);
 }
 
 int yawhip_shear_upload_binned(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
                                const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
                                int32_t sort_axis, yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload_binned", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+    return upload_segments("yawhip_shear_upload_binned", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
 }
 
 int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
@@ -1129,7 +1236,7 @@ int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, co
     const char *fn = "yawhip_dsigma_upload_sources";
     if (out) *out = nullptr;
     if (const int rc = check_column(fn, "u", n, u, NOT_NEGATIVE)) return rc;
-    return upload_segments(fn, DSIGMA_SOURCES, ctx, n, x, y, z, w, g1, g2, u, n_patches, 1, offsets, sort_axis, out);
+    return upload_segments(fn, DSIGMA_SOURCES, ctx, n, x, y, z, w, g1, g2, u, nullptr, n_patches, 1, offsets, sort_axis, out);
 }
 
 int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
@@ -1139,7 +1246,7 @@ int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, con
     if (out) *out = nullptr;
     if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
     if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
-    return upload_segments(fn, DSIGMA_LENSES, ctx, n, x, y, z, w, f, c, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+    return upload_segments(fn, DSIGMA_LENSES, ctx, n, x, y, z, w, f, c, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
 }
 
 int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
@@ -1150,7 +1257,7 @@ int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double 
     if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
     if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
     if (const int rc = check_column(fn, "m", n, m, POSITIVE)) return rc;
-    return upload_segments(fn, RADIAL_LENSES, ctx, n, x, y, z, w, f, c, m, n_patches, n_bins, offsets, sort_axis, out);
+    return upload_segments(fn, RADIAL_LENSES, ctx, n, x, y, z, w, f, c, m, nullptr, n_patches, n_bins, offsets, sort_axis, out);
 }
 
 int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
@@ -1160,7 +1267,19 @@ int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double
     if (out) *out = nullptr;
     if (const int rc = check_column(fn, "d", n, d, POSITIVE)) return rc;
     if (const int rc = check_column(fn, "c", n, c, ANY_SIGN)) return rc;
-    return upload_segments(fn, PROJECTED, ctx, n, x, y, z, w, d, c, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+    return upload_segments(fn, PROJECTED, ctx, n, x, y, z, w, d, c, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
+}
+
+int yawhip_proj_upload_shapes(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
+                              const double *g1, const double *g2, const double *d, const double *c, int32_t n_patches, int32_t n_bins,
+                              const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
+    const char *fn = "yawhip_proj_upload_shapes";
+    if (out) *out = nullptr;
+    if (const int rc = check_column(fn, "g1", n, g1, ANY_SIGN)) return rc;
+    if (const int rc = check_column(fn, "g2", n, g2, ANY_SIGN)) return rc;
+    if (const int rc = check_column(fn, "d", n, d, POSITIVE)) return rc;
+    if (const int rc = check_column(fn, "c", n, c, ANY_SIGN)) return rc;
+    return upload_segments(fn, PROJECTED_SHAPES, ctx, n, x, y, z, w, g1, g2, d, c, n_patches, n_bins, offsets, sort_axis, out);
 }
 
 int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
@@ -1314,11 +1433,7 @@ int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_
     if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
     if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
     if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (n_pi < 1 || !pe) return fail(YAWHIP_ERR_INVALID, "%s: n_pi must be >= 1 and pe not NULL (n_pi=%d)", fn, n_pi);
-    if (pe[0] != 0.0) return fail(YAWHIP_ERR_INVALID, "%s: the first pi edge must be 0", fn);
-    for (int j = 1; j <= n_pi; ++j)  // (a NaN fails either comparison)
-        if (!(pe[j] > pe[j - 1]) || (j < n_pi && !std::isfinite(pe[j])))
-            return fail(YAWHIP_ERR_INVALID, "%s: the pi edges must be finite (the last may be +inf) and strictly ascending (edge %d)", fn, j);
+    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
     if (n_pi > max_pi_planes(n_edges))
         return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
                     n_pi, n_edges - 1, max_pi_planes(n_edges), n_edges);
@@ -1365,6 +1480,32 @@ int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear
             go(k_count_smu, view_of(a), SmuLanes{view_of(b), d.pe, n_mu, step}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
         },
         n_mu, m2);
+}
+
+int yawhip_proj_count_shear(yawhip_ctx *ctx, yawhip_shear_sources *dens, yawhip_shear_sources *shapes, int32_t n_cells,
+                            const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe,
+                            double *fine, yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_shear";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (const int rc = check_handles(fn, ctx, dens, shapes, n_cells, n_rows, n_edges, r2, cells && fine)) return rc;
+    if (const int rc = require_kind(fn, dens, PROJECTED, "the density handle is not one of yawhip_proj_upload")) return rc;
+    if (const int rc = require_kind(fn, shapes, PROJECTED_SHAPES, "the shape handle is not one of yawhip_proj_upload_shapes")) return rc;
+    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
+    if (n_pi > max_bins<ProjectedShear>(n_edges))
+        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
+                    n_pi, n_edges - 1, max_bins<ProjectedShear>(n_edges), n_edges);
+    // (the two handles differ, so check_proj_cells refuses every cell that is marked diagonal)
+    std::vector<double> reach;
+    int64_t candidates = 0;
+    if (const int rc = check_proj_cells(fn, dens, shapes, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
+    double *const planes[] = {fine};
+    return run_count<ProjectedShear>(
+        fn, ctx, dens, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), planes, candidates, wall0, stats,
+        [&](auto go, const Slots &d) {
+            go(k_count_projected_shear, view_of(dens), ProjShapeLanes{{view_of(shapes), d.pe, n_pi, pe[n_pi]}, shapes->u, shapes->m}, d.table,
+               n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+        },
+        n_pi, pe);
 }
 
 }  // extern "C"

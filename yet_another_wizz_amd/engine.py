@@ -15,7 +15,7 @@ import re
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_projected_shear_fine", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -470,6 +470,40 @@ def count_projected_pi_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmolog
         if "too close for the largest radius" not in str(err):
             raise
         check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
+        raise
+
+
+def count_projected_shear_fine(dens_layout, shape_layout, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
+    """Fine-bin projected position-shape sums for ``cells`` (int[n, 4] = ``(segment of dens_layout, segment of shape_layout,
+    row of r2, 0)``) -> ``((T, X, W), CountStats)``, each plane f64[n_pi, n_cells, E-1]: over the pairs that
+    ``count_projected_pi_fine`` puts into a radius and pi bin, the sums of ``w_d w_s e_t``, ``w_d w_s e_x`` and ``w_d w_s``
+    with ``e_t``, ``e_x`` the shape's ellipticity rotated to the great circle through the pair -- ``e_t`` is negative where
+    the shape points at the density object (``yawhip_proj_count_shear``). ``shape_layout`` carries shear and redshifts
+    (``build_trees(edges, with_shear=True, with_redshifts=True)``); the columns of both come from ``proj_columns``. The
+    density side is the resident handle of role "projected <kind>", the one ``count_projected_fine`` uses: a layout counted
+    for ``w_p`` is not uploaded again. The shapes get a handle of their own (role "projected shapes <kind>"), also when
+    the layout is the density layout. Cap and reach refusals become ``ValueError`` as in ``count_projected_pi_fine``. No CPU
+    fallback; the CPU tests replace this function."""
+    _require_shear(shape_layout)
+    ctx, dens, _ = _proj_handles(dens_layout, dens_layout, cosmology, unit, sort_axis)
+
+    def upload():
+        d, c = proj_columns(shape_layout, cosmology, unit)
+        return _lib.ProjShapesHandle(ctx, shape_layout.x, shape_layout.y, shape_layout.z, shape_layout.w, shape_layout.g1, shape_layout.g2,
+                                     d, c, shape_layout.num_patches, shape_layout.num_bins, shape_layout.offsets, sort_axis=sort_axis)
+
+    shapes = _handle(shape_layout, ctx, sort_axis, f"projected shapes {radial_kind(unit)}", upload, cosmology)
+    try:
+        return _lib.proj_count_shear(ctx, dens, shapes, cells, r2, pi_edges)
+    except _lib.YawhipError as err:
+        if "do not fit the LDS" in str(err):
+            cap = re.search(r"at most (\d+) pi bins", str(err)).group(1)
+            raise ValueError(f"{len(pi_edges) - 1} pi bins are too many for {np.shape(r2)[1]} radius edges (the fine bins of the "
+                             f"configuration's resolution) with three planes each: at most {cap} pi bins fit; use fewer pi bins or "
+                             "a lower resolution") from err
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach((dens_layout, shape_layout), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
         raise
 
 
