@@ -892,6 +892,56 @@ int yawhip_proj_count_shear(yawhip_ctx *ctx, yawhip_shear_sources *dens, yawhip_
                             const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe,
                             double *fine, yawhip_stats *stats);
 
+/*
+ * Projected shape-shape sums: the products of the ellipticities of two shapes, BOTH rotated to the great circle through the
+ * pair, binned in each PAIR's own radius and in the line-of-sight separation -- the planes of the intrinsic-alignment
+ * measurements w_++(r_p) and w_xx(r_p) and of the parity-odd null test w_+x (measurements.autocorrelate_alignment; DESIGN.md
+ * section 25; no counterpart in the reference). Additive to ABI 6: one new symbol, no new upload and no new handle kind.
+ *
+ * yawhip_proj_count_shapes   a (streamed) and b (in the lanes): handles of yawhip_proj_upload_shapes, which may be ONE handle;
+ *                        they need neither equal patch counts, nor equal bin counts, nor one sort axis. Any other kind in
+ *                        either slot is YAWHIP_ERR_MISMATCH. Cell c = (segment of a, segment of b, row, diagonal) with the
+ *                        rules of yawhip_proj_count: a cell is diagonal iff a == b and the two segments are one segment, it
+ *                        then holds every unordered pair once, and a wrong flag is refused as there. s2, D, DD, q, th2, R2
+ *                        and the fine bin e are exactly yawhip_proj_count's, p and j exactly yawhip_proj_count_pi's, and the
+ *                        pair term is yawhip_shear_auto_count's up to tA, xA, tB, xB (float64, every operation rounded on
+ *                        its own, nothing contracted):
+ *       p = fabs(c_a - c_b);   j = the number of edges pe[1 .. n_pi] that are < p;   the pair counts  iff  j < n_pi
+ *       pa = ax by - ay bx;   dot = ax bx + ay by
+ *       pbA = (ax ax + ay ay) bz - az dot;   pbB = (bx bx + by by) az - bz dot
+ *       a2 = pa pa;   bA2 = pbA pbA;   bB2 = pbB pbB;   denA = a2 + bA2;   denB = a2 + bB2
+ *       denA != 0 and denB != 0:
+ *                   cA = (a2 - bA2) / denA;   sA = ((2 pa) pbA) / denA;   cB = (a2 - bB2) / denB;   sB = ((-2 pa) pbB) / denB
+ *                   tA = -(wg1_a cA + wg2_a sA);   xA = wg1_a sA - wg2_a cA
+ *                   tB = -(wg1_b cB + wg2_b sB);   xB = wg1_b sB - wg2_b cB
+ *                   PP[j][c][e] += tA tB;   XX[j][c][e] += xA xB;   PX[j][c][e] += tA xB + xA tB
+ *       W[j][c][e] += w_a w_b                  (denA == 0 or denB == 0, a shape on a pole of the frame: W only)
+ *     The planes are ++, xx and +x separately, not xi_+ / xi_-: the estimator wants ++ and xx apart. All four terms are
+ *     BIT-SYMMETRIC under a <-> b (products and two-operand sums commute; pa changes its sign and enters as pa pa and as
+ *     (2 pa) pbA against (-2 pa) pbB; pbA and pbB swap), so it does not matter which of the two objects a lane holds, and a
+ *     diagonal cell walks every unordered pair once. Consequences: with g == 0 on either side PP, XX and PX are exactly 0;
+ *     (g1, g2) -> (-g2, g1) on both sides gives PP' == XX, XX' == PP and PX' == -PX bit for bit; over unit weights W equals
+ *     yawhip_proj_count_pi's planes on the same (x, y, z, w, d, c) as integers, and candidate_pairs and evaluated_pairs equal
+ *     that call's, diagonal cells included; two objects at one sky position have R2 == 0 and are in no bin.
+ *   n_pi, pe     as yawhip_proj_count_pi; the single cylinder |pi| <= pmax is n_pi = 1, pe = {0, pmax}
+ *   the cap      two stages of 64-byte streamed objects (x, y, z, d | w, c, wg1, wg2) and four planes per pi bin:
+ *                  32768 + 8 (((n_edges + 1) & ~1) + ((n_pi + 2) & ~1)) + 128 n_pi (n_edges - 1) <= 65536
+ *                -- n_pi <= 21 at 13 edges, <= 5 at 51, <= 1 at 241, <= 240 at 2; above n_edges = 241 not even one pi bin
+ *                fits. A larger n_pi is YAWHIP_ERR_INVALID with a message that names the largest n_pi that fits at this
+ *                n_edges, or, where none does, the largest n_edges at one pi bin; the library does not split a call.
+ *   fine         float64[4][n_pi][n_cells][n_edges - 1] (host), the planes in the order PP, XX, PX, W; every element is written
+ *   checks       those of yawhip_proj_count_pi in its order, with the shape kind where that call asks for two projected
+ *                handles. r2, the reach rule and its refusal, stats, n_cells == 0: as yawhip_proj_count_pi. The per-call
+ *                device buffers are those of a.
+ * Kernel: yawhip_proj_count_shear's walk with a shape handle streamed too; its loop up to the wave-wide test is unchanged
+ * (fl(DD s2) against the row's last edge, an exact superset) and reads the first 32 bytes of the streamed object. Behind it
+ * R2 and p are bisected as there, the lower half of a diagonal cell is dropped, and only a pair that counts is rotated.
+ * Accumulation and reproducibility as yawhip_shear_count: per-wave LDS histograms, folded in a fixed order, plain stores.
+ */
+int yawhip_proj_count_shapes(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                             int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine,
+                             yawhip_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,8 +20,8 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
-from .measurements import (PatchLinkage, autocorrelate, autocorrelate_multipoles, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
+from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc
+from .measurements import (PatchLinkage, autocorrelate, autocorrelate_alignment, autocorrelate_multipoles, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
                            crosscorrelate_alignment, crosscorrelate_delta_sigma, crosscorrelate_shear)
 from . import healpix, patches, randoms
@@ -52,7 +52,9 @@ __all__ = [
     "RedshiftData",
     "SampledData",
     "ScalarCorrFunc",
+    "ShapeShapeCorrFunc",
     "autocorrelate",
+    "autocorrelate_alignment",
     "autocorrelate_multipoles",
     "autocorrelate_projected",
     "autocorrelate_scalar",

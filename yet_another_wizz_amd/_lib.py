@@ -74,6 +74,7 @@ ABI_SYMBOLS = (
     "yawhip_proj_count_smu",
     "yawhip_proj_upload_shapes",
     "yawhip_proj_count_shear",
+    "yawhip_proj_count_shapes",
 )
 
 
@@ -311,6 +312,7 @@ def load_library() -> ctypes.CDLL:
     lib.yawhip_proj_upload_shapes.argtypes = [_vp, ctypes.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int32, ctypes.c_int32,
                                               _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
     lib.yawhip_proj_count_shear.argtypes = lib.yawhip_proj_count_pi.argtypes
+    lib.yawhip_proj_count_shapes.argtypes = lib.yawhip_proj_count_pi.argtypes
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -889,7 +891,7 @@ class ProjShapesHandle(ShearSources):
 
 def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
                   rows: str = "thresholds must be [n_bins, n_edges]", stacked: bool = False):
-    """What the nine counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+    """What the ten counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
     ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
     entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
     and the ``CountStats``. ``stacked``: the symbol takes the planes as ONE array f64[n_planes, ...], which is what comes
@@ -941,6 +943,24 @@ def proj_count_shear(ctx: Context, dens: ProjHandle, shapes: ProjShapesHandle, c
     fine, stats = _shear_counts("yawhip_proj_count_shear", 3 * max(n_pi, 0), (ctx._h, dens._h, shapes._h), cells, r2, n_pi, _ptr(pe, _dp),
                                 width=4, rows="r2 must be [n_rows, n_edges]", stacked=True)
     return tuple(fine.reshape(3, max(n_pi, 0), *fine.shape[1:])), stats
+
+
+def proj_count_shapes(ctx: Context, a: ProjShapesHandle, b: ProjShapesHandle, cells, r2, pi_edges):
+    """Run ``yawhip_proj_count_shapes`` on two shape handles (``a is b`` allowed): the shapes of both rotated to the great circle
+    through each pair, binned as ``proj_count_pi`` bins the pair. cells int[n_cells, 4] = ``(segment of a, segment of b, row,
+    diagonal)`` with ``proj_count``'s rules -- a diagonal cell holds every unordered pair once; ``r2`` and ``pi_edges`` as
+    ``proj_count_pi``. Returns ``((PP, XX, PX, W), CountStats)``, each plane f64[n_pi, n_cells, E-1]: the sums of
+    ``w_a w_b et_a et_b``, ``w_a w_b ex_a ex_b``, ``w_a w_b (et_a ex_b + ex_a et_b)`` and ``w_a w_b`` with ``et`` the TANGENTIAL
+    ellipticity of a shape about its partner, as ``proj_count_shear`` has it: ``e+ = -et``, so PP and XX are the ``++`` and
+    ``xx`` products and PX is MINUS the ``+x`` product. ``4 n_pi (E - 1)`` is capped by the LDS of a workgroup
+    (include/yawhip.h); beyond it the library refuses."""
+    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
+    if pe.ndim != 1:
+        raise ValueError("pi_edges must be [n_pi + 1]")
+    n_pi = len(pe) - 1
+    fine, stats = _shear_counts("yawhip_proj_count_shapes", 4 * max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp),
+                                width=4, rows="r2 must be [n_rows, n_edges]", stacked=True)
+    return tuple(fine.reshape(4, max(n_pi, 0), *fine.shape[1:])), stats
 
 
 def proj_count_smu(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, m2):

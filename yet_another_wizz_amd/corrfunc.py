@@ -7,7 +7,7 @@ import numpy as np
 from .corrdata import CorrData
 from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "AlignmentCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "AlignmentCorrFunc", "ShapeShapeCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -362,7 +362,7 @@ class AlignmentCorrFunc:
     ``to_dict`` / ``from_dict``, ``==``, ``is_compatible`` and the bin and patch subsets go bin by bin."""
 
     __slots__ = ("pi_edges", "pi_bins")
-    _required = ("t_sd", "x_sd", "w_sd", "t_sr", "x_sr", "w_sr")
+    _required = ("t_sd", "x_sd", "w_sd", "t_sr", "x_sr", "w_sr")  # (the first of them stands for the binning and the patches)
 
     def __init__(self, pi_edges, pi_bins) -> None:
         edges = np.array(pi_edges, dtype=np.float64)
@@ -371,7 +371,7 @@ class AlignmentCorrFunc:
             raise ValueError("'pi_edges' must hold one edge more than there are pi bins, and there is at least one bin")
         if edges[0] != 0.0 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0):
             raise ValueError("'pi_edges' must start at 0, be finite and ascend strictly")
-        first = bins[0].get("t_sd")
+        first = bins[0].get(self._required[0])
         for planes in bins:
             if planes.keys() != bins[0].keys() or not set(self._required) <= planes.keys() <= {*self._required, "rr"}:
                 raise ValueError(f"every pi bin holds the planes {self._required}, and all or none of them 'rr'")
@@ -381,7 +381,7 @@ class AlignmentCorrFunc:
                 try:
                     first.is_compatible(counts, require=True)
                 except ValueError as err:
-                    raise ValueError(f"plane '{kind}' and 't_sd' of the first pi bin are not compatible") from err
+                    raise ValueError(f"plane '{kind}' and '{self._required[0]}' of the first pi bin are not compatible") from err
         edges.setflags(write=False)
         self.pi_edges = edges
         self.pi_bins = bins
@@ -390,8 +390,8 @@ class AlignmentCorrFunc:
         return (f"{type(self).__name__}(num_pi={self.num_pi}, pi_max={self.pi_edges[-1]}, planes={'|'.join(self.pi_bins[0])}, "
                 f"binning={self.binning}, num_patches={self.num_patches})")
 
-    binning = property(lambda self: self.pi_bins[0]["t_sd"].binning)
-    num_patches = property(lambda self: self.pi_bins[0]["t_sd"].num_patches)
+    binning = property(lambda self: self.pi_bins[0][self._required[0]].binning)
+    num_patches = property(lambda self: self.pi_bins[0][self._required[0]].num_patches)
     num_bins = property(lambda self: len(self.binning))
     num_pi = property(lambda self: len(self.pi_bins))
 
@@ -418,7 +418,7 @@ class AlignmentCorrFunc:
             if require:
                 raise ValueError("the pi edges differ")
             return False
-        return self.pi_bins[0]["t_sd"].is_compatible(other.pi_bins[0]["t_sd"], require=require)
+        return self.pi_bins[0][self._required[0]].is_compatible(other.pi_bins[0][self._required[0]], require=require)
 
     @staticmethod
     def _component(component: str):
@@ -452,3 +452,43 @@ class AlignmentCorrFunc:
 
     def patches_subset(self, item):
         return type(self)(self.pi_edges, [{k: c.patches_subset(item) for k, c in planes.items()} for planes in self.pi_bins])
+
+
+class ShapeShapeCorrFunc(AlignmentCorrFunc):
+    """The sums of one scale of the projected shape-shape correlation (``autocorrelate_alignment``; no counterpart in the
+    reference): ``pi_edges`` and ``pi_bins`` as ``AlignmentCorrFunc`` has them, each pi bin a dict of ``NormalisedCounts``
+    with the planes of shapes x shapes -- ``pp``, ``xx``, ``px`` (signed sums of ``w_a w_b et_a et_b``, ``w_a w_b ex_a ex_b``
+    and ``w_a w_b (et_a ex_b + ex_a et_b)``, both ellipticities rotated to the great circle through the pair) and ``w`` (the
+    sum of ``w_a w_b``) -- and optionally ``rr``, the pair count of the shape randoms with themselves.
+
+    Sign convention: the device sums the TANGENTIAL ellipticity ``et``, as for ``AlignmentCorrFunc``, and ``e+ = -et``. In
+    ``pp`` the two signs cancel; ``px`` holds one of them, so the ``+x`` component flips it here, once. With ``/n`` the
+    division by a count's own normalisation, per pi bin j, for the data and every jackknife sample separately,
+
+        with randoms:     xi_j = (pp/n) / (rr/n)          S+S+ over R_S R_S
+        without randoms:  xi_j = pp / w                   the pair-weighted mean product, as autocorrelate_shear reports xi_+
+        sample("plus" | "cross" | "plus_cross") = 2 sum_j dpi_j xi_j     -> w_++(r_p), w_xx(r_p), w_+x(r_p)
+
+    from ``pp``, ``xx`` and ``-px``. The two estimators differ by the factor ``1 + xi_gg`` of the shape sample's own
+    clustering (``w/n`` over ``rr/n``). ``plus_cross`` is parity-odd and vanishes without systematics: the null test.
+    ``sample_xi(component)`` gives the pi bins. An empty denominator gives NaN there and in the sum: nothing is masked.
+    ``to_dict`` / ``from_dict``, ``==``, ``is_compatible`` and the bin and patch subsets go bin by bin."""
+
+    __slots__ = ()
+    _required = ("pp", "xx", "px", "w")
+    _planes = dict(plus=("pp", 1.0), cross=("xx", 1.0), plus_cross=("px", -1.0))
+
+    def sample_xi(self, component: str = "plus") -> list:
+        """``xi_j`` of the component per pi bin as ``CorrData``, for the data and every jackknife sample."""
+        if component not in self._planes:
+            raise ValueError(f"component must be 'plus', 'cross' or 'plus_cross', not {component!r}")
+        plane, sign = self._planes[component]
+        out = []
+        for planes in self.pi_bins:
+            num = planes[plane].sample_patch_sum()
+            norm = planes.get("rr", planes["w"]).sample_patch_sum()
+            with np.errstate(divide="ignore", invalid="ignore"):  # an empty denominator: NaN, whatever the numerator holds
+                data = np.where(norm.data == 0.0, np.nan, sign * num.data / norm.data)
+                samples = np.where(norm.samples == 0.0, np.nan, sign * num.samples / norm.samples)
+            out.append(CorrData(self.binning, data, samples))
+        return out

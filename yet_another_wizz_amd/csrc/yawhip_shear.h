@@ -1,5 +1,5 @@
 // Private to yawhip_shear.hip (the yawhip_shear_*, yawhip_dsigma_* and yawhip_proj_* calls of include/yawhip.h; DESIGN.md
-// sections 15 to 24): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
+// sections 15 to 25): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -58,6 +58,10 @@ struct RadialView : LensView {  // a radial lens handle streamed by yawhip_dsigm
 
 struct SourceView : ShearView {  // the sources of yawhip_dsigma_count in the lanes
     const double *u;
+};
+
+struct ShapeView : ShearView {  // a shape handle streamed by yawhip_proj_count_shapes: wg1, wg2 are w g1, w g2, with d, c besides
+    const double *d, *c;
 };
 
 }  // namespace yawhip_detail

@@ -12,10 +12,12 @@
 // the pair counts of the same handles binned in the redshift-space separation s and in mu = pi / s (yawhip_proj_count_smu;
 // measurements.autocorrelate_multipoles), and the projected position-shape sums of a shape catalogue
 // with d, c around such handles, the tangential and cross ellipticity per radius and pi bin (yawhip_proj_count_shear;
-// measurements.crosscorrelate_alignment).
+// measurements.crosscorrelate_alignment), and the projected shape-shape sums between two such shape
+// catalogues, both ends rotated to the great circle through the pair (yawhip_proj_count_shapes;
+// measurements.autocorrelate_alignment).
 // include/yawhip.h has the contracts, product by product.
 //
-// All are ONE streaming walk, shear_walk<P>, under nine thin entry kernels. One workgroup of 256 threads owns one cell (a
+// All are ONE streaming walk, shear_walk<P>, under ten thin entry kernels. One workgroup of 256 threads owns one cell (a
 // (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
 // segment in registers (parked far away where the tile is padded); the cell's
 // streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
@@ -54,6 +56,9 @@
 // to the plane that the staged squared mu edges give for P2 against m2 S2 (at the policy).
 // ProjectedShear (k_count_projected_shear) is ProjectedPi with a projected handle streamed and a shape handle (w g1, w g2 | d, c)
 // in the lanes, no diagonal cells and three planes T, X, W per pi bin: the pair that counts gets Tangential's rotation.
+// ProjectedShapes (k_count_projected_shapes) is ProjectedShear with a shape handle streamed too, as a 64-byte object
+// (x, y, z, d | w, c, wg1, wg2), Projected's diagonal cells and four planes PP, XX, PX, W per pi bin: the pair that counts
+// gets ShearShear's two rotations.
 //
 // Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
 //   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
@@ -573,6 +578,84 @@ struct ProjectedShear : ProjectedPi {
     }
 };
 
+// One streamed shape of the projected shape-shape count: (x, y, z, d | w, c, wg1, wg2). The hot loop reads the first 32 bytes
+// (two 16-byte broadcast reads, as Projected reads its ObjP), the second half only behind the ballot.
+struct alignas(16) ObjS {
+    double x, y, z, d, w, c, g1, g2;
+};
+
+// The products of the rotated ellipticities of two shape samples, binned in each pair's own radius and in the line-of-sight
+// separation (k_count_projected_shapes). Both sides are shape handles: the lane is ProjectedShear's
+// ShapeLane, the streamed side a ShapeView, which carries d and c next to the ShearView columns as ProjShapeLanes carries them
+// for the lanes. Cells, window rule and the diagonal cells are Projected's -- one segment of one handle against itself walks
+// the larger indices only, which rests on every term below being bit-symmetric under a <-> b: products and sums of two
+// operands commute, pa changes its sign with the swap and enters as pa pa and as (2 pa) pbA against (-2 pa) pbB, dot is
+// symmetric, and pbA, pbB swap their roles. The hot loop up to the ballot is ProjectedShear's: it holds fl(DD s2) against the
+// last edge, DD from the lane's d and the streamed d, and Projected's proof of the exact superset applies as it stands. Behind
+// the ballot R2 is bisected over the row, the walk drops the lower half of a diagonal cell, p = |c_a - c_b| is bisected by
+// ProjectedPi::plane, and only a pair that counts (j < n_pi) gets ShearShear's two rotations, term for term up to
+// tA, xA, tB, xB. The planes are [4][n_pi] per wave, PP, XX, PX, W: plane (t, j) sits at (t n_pi + j) nf.
+struct ProjectedShapes : ProjectedShear {
+    using View = ShapeView;     // the streamed side: a shape handle with its d, c
+    using Streamed = ObjS;      // (x, y, z, d | w, c, wg1, wg2)
+    using Read = const ObjS &;  // the hot loop reads x, y, z, d (two ds_read_b128); w, c, wg1, wg2 behind the ballot
+    static constexpr bool DIAGONAL = true;
+    static constexpr int PER_BIN = 4;  // PP, XX, PX, W
+    static __device__ __forceinline__ int planes(const ProjShapeLanes &src) { return 4 * src.n_pi; }
+    // (a padded streamed object has d = 0 and would pass the outer test: nobody reads it, as Projected's)
+    static __device__ ObjS load(const ShapeView &v, int64_t i, bool have) {
+        ObjS o;
+        o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
+        o.d = have ? v.d[i] : 0.0;
+        o.w = (have && v.w) ? v.w[i] : 1.0;
+        o.c = have ? v.c[i] : 0.0;
+        o.g1 = have ? v.wg1[i] : 0.0; o.g2 = have ? v.wg2[i] : 0.0;
+        return o;
+    }
+    static __device__ __forceinline__ double pair_dd(const ShapeLane &a, const ObjS &b) {
+        const double D = 0.5 * (a.d + b.d);
+        return D * D;
+    }
+    static __device__ __forceinline__ double outer(const ShapeLane &a, const ObjS &b, double s) { return pair_dd(a, b) * s; }
+    static __device__ __forceinline__ double binned(const ShapeLane &a, const ObjS &b, double s) { return pair_dd(a, b) * squared_angle(s); }
+    // pe: the staged edges in LDS (the walk's count of planes, 4 n_pi, is not used)
+    static __device__ void add(const ShapeLane &a, const ObjS &b, double *wh, int e, int nf, const double *pe, int) {
+        const int n_pi = a.n_pi;
+        const int j = plane(pe, n_pi, fabs(a.c - b.c), a.u);
+        if (j < n_pi) {
+            double *const bin = wh + j * nf + e;
+            const int plane = n_pi * nf;
+            const double bx = b.x, by = b.y, bz = b.z;
+            const double pa = a.x * by - a.y * bx;
+            const double dot = a.x * bx + a.y * by;
+            const double pbA = a.rho2 * bz - a.z * dot;
+            const double pbB = (bx * bx + by * by) * a.z - bz * dot;
+            const double a2 = pa * pa;
+            const double bA2 = pbA * pbA;
+            const double bB2 = pbB * pbB;
+            const double denA = a2 + bA2;
+            const double denB = a2 + bB2;
+            // denA == 0 or denB == 0 (a shape on a pole of the frame) adds to W only: as a select, the three sums get a zero
+            // that changes none of them, since another nested branch costs the exec masks that spill the walk's scalar
+            // registers (ProjectedShear::add)
+            const bool rotated = denA != 0.0 && denB != 0.0;
+            const double cA = (a2 - bA2) / denA;
+            const double sA = ((2.0 * pa) * pbA) / denA;
+            const double cB = (a2 - bB2) / denB;
+            const double sB = ((-2.0 * pa) * pbB) / denB;
+            const double bg1 = b.g1, bg2 = b.g2;
+            const double tA = -(a.g1 * cA + a.g2 * sA);
+            const double xA = a.g1 * sA - a.g2 * cA;
+            const double tB = -(bg1 * cB + bg2 * sB);
+            const double xB = bg1 * sB - bg2 * cB;
+            atomicAdd(bin, rotated ? tA * tB : 0.0);
+            atomicAdd(bin + plane, rotated ? xA * xB : 0.0);
+            atomicAdd(bin + 2 * plane, rotated ? tA * xB + xA * tB : 0.0);
+            atomicAdd(bin + 3 * plane, a.w * b.w);
+        }
+    }
+};
+
 // The separations of a diagonal cell's lane tile [ta, t_last] against the streamed objects [b0, b1), b0 > ta, that the index
 // test can keep -- the streamed index larger than the lane's: what a policy with KEPT_WORK reports as evaluated, so that a
 // cell's figure never exceeds its unordered pairs. (The waves evaluate the others of the tile's own range too, and drop them.)
@@ -610,6 +693,9 @@ static_assert(max_pi_planes(MAX_EDGES) == 4 && max_pi_planes(13) == 104 && max_p
 static_assert(max_bins<ProjectedShear>(MAX_EDGES) == 1 && max_bins<ProjectedShear>(51) == 8 && max_bins<ProjectedShear>(13) == 35 &&
                   max_bins<ProjectedShear>(2) == 393,
               "ProjectedShear: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 24 quote it)");
+static_assert(max_bins<ProjectedShapes>(13) == 21 && max_bins<ProjectedShapes>(51) == 5 && max_bins<ProjectedShapes>(241) == 1 &&
+                  max_bins<ProjectedShapes>(242) == 0 && max_bins<ProjectedShapes>(2) == 240,
+              "ProjectedShapes: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 25 quote it)");
 static_assert(lds_bytes<RedshiftSpace>(13, 104) == lds_bytes<ProjectedPi>(13, 104) && lds_bytes<RedshiftSpace>(51, 25) == lds_bytes<ProjectedPi>(51, 25) &&
                   lds_bytes<RedshiftSpace>(MAX_EDGES, 4) == lds_bytes<ProjectedPi>(MAX_EDGES, 4),
               "RedshiftSpace: its carve-up is ProjectedPi's, so that max_pi_planes caps n_mu too (DESIGN.md section 23)");
@@ -860,6 +946,15 @@ __global__ __launch_bounds__(WG) void k_count_projected_shear(ShearView a, ProjS
                                                               int64_t n_cells, double *__restrict__ out,
                                                               unsigned long long *__restrict__ evaluated) {
     shear_walk<ProjectedShear>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
+// out: [4][n_pi][n_cells][E-1] (PP, XX, PX, W per pi bin); cells: [n_cells][4] (ShearPair::cell); the shape handle a is streamed
+// with its d, c, the shape handle b sits in the lanes with its d, c and the call's pi edges
+__global__ __launch_bounds__(WG) void k_count_projected_shapes(ShapeView a, ProjShapeLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                               const double *__restrict__ r2, const double *__restrict__ rwin,
+                                                               int64_t n_cells, double *__restrict__ out,
+                                                               unsigned long long *__restrict__ evaluated) {
+    shear_walk<ProjectedShapes>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
 }  // namespace
@@ -1214,6 +1309,14 @@ int check_pi_edges(const char *fn, int32_t n_pi, const double *pe) {
     return YAWHIP_OK;
 }
 
+// the largest n_edges at which one pi bin of the shape-shape count still fits (its refusal names it where no n_pi does)
+constexpr int max_shape_edges() {
+    int n = 2;
+    while (n < MAX_EDGES && max_bins<ProjectedShapes>(n + 1) >= 1) ++n;
+    return n;
+}
+static_assert(max_shape_edges() == 241, "ProjectedShapes: the largest n_edges moved (include/yawhip.h quotes it)");
+
 }  // namespace
 
 extern "C" {
@@ -1503,6 +1606,34 @@ int yawhip_proj_count_shear(yawhip_ctx *ctx, yawhip_shear_sources *dens, yawhip_
         fn, ctx, dens, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), planes, candidates, wall0, stats,
         [&](auto go, const Slots &d) {
             go(k_count_projected_shear, view_of(dens), ProjShapeLanes{{view_of(shapes), d.pe, n_pi, pe[n_pi]}, shapes->u, shapes->m}, d.table,
+               n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+        },
+        n_pi, pe);
+}
+
+int yawhip_proj_count_shapes(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                             int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine,
+                             yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_shapes";
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine)) return rc;
+    if (const int rc = require_kind(fn, a, PROJECTED_SHAPES, "a handle is not one of yawhip_proj_upload_shapes")) return rc;
+    if (const int rc = require_kind(fn, b, PROJECTED_SHAPES, "a handle is not one of yawhip_proj_upload_shapes")) return rc;
+    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
+    if (max_bins<ProjectedShapes>(n_edges) == 0)
+        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: not even 1 pi bin at n_edges=%d, at most n_edges=%d at 1 pi bin",
+                    fn, n_pi, n_edges - 1, n_edges, max_shape_edges());
+    if (n_pi > max_bins<ProjectedShapes>(n_edges))
+        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
+                    n_pi, n_edges - 1, max_bins<ProjectedShapes>(n_edges), n_edges);
+    std::vector<double> reach;
+    int64_t candidates = 0;
+    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
+    double *const planes[] = {fine};
+    return run_count<ProjectedShapes>(
+        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), planes, candidates, wall0, stats,
+        [&](auto go, const Slots &d) {
+            go(k_count_projected_shapes, ShapeView{view_of(a), a->u, a->m}, ProjShapeLanes{{view_of(b), d.pe, n_pi, pe[n_pi]}, b->u, b->m}, d.table,
                n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
         },
         n_pi, pe);

@@ -15,7 +15,7 @@ import re
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_projected_shear_fine", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_projected_shear_fine", "count_projected_shapes_fine", "max_shape_pi_bins", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -486,13 +486,7 @@ def count_projected_shear_fine(dens_layout, shape_layout, cells, r2, *, pi_edges
     fallback; the CPU tests replace this function."""
     _require_shear(shape_layout)
     ctx, dens, _ = _proj_handles(dens_layout, dens_layout, cosmology, unit, sort_axis)
-
-    def upload():
-        d, c = proj_columns(shape_layout, cosmology, unit)
-        return _lib.ProjShapesHandle(ctx, shape_layout.x, shape_layout.y, shape_layout.z, shape_layout.w, shape_layout.g1, shape_layout.g2,
-                                     d, c, shape_layout.num_patches, shape_layout.num_bins, shape_layout.offsets, sort_axis=sort_axis)
-
-    shapes = _handle(shape_layout, ctx, sort_axis, f"projected shapes {radial_kind(unit)}", upload, cosmology)
+    shapes = _proj_shape_handle(shape_layout, ctx, cosmology, unit, sort_axis)
     try:
         return _lib.proj_count_shear(ctx, dens, shapes, cells, r2, pi_edges)
     except _lib.YawhipError as err:
@@ -505,6 +499,63 @@ def count_projected_shear_fine(dens_layout, shape_layout, cells, r2, *, pi_edges
             raise
         check_projected_reach((dens_layout, shape_layout), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
         raise
+
+
+def _proj_shape_handle(layout, ctx, cosmology, unit, sort_axis):
+    """The resident ``_lib.ProjShapesHandle`` of a layout with shear and redshifts (role "projected shapes <kind of unit>"):
+    what ``count_projected_shear_fine`` keeps in its lanes and ``count_projected_shapes_fine`` on either side."""
+
+    def upload():
+        d, c = proj_columns(layout, cosmology, unit)
+        return _lib.ProjShapesHandle(ctx, layout.x, layout.y, layout.z, layout.w, layout.g1, layout.g2, d, c, layout.num_patches,
+                                     layout.num_bins, layout.offsets, sort_axis=sort_axis)
+
+    return _handle(layout, ctx, sort_axis, f"projected shapes {radial_kind(unit)}", upload, cosmology)
+
+
+def max_shape_pi_bins(n_edges: int) -> int:
+    """The largest number of pi bins of a shape-shape count at ``n_edges`` radius edges: the formula of include/yawhip.h for
+    ``yawhip_proj_count_shapes`` -- two stages of 64-byte objects, the edges, four planes per pi bin and wave -- within 64 KiB
+    of LDS. 0: not even one pi bin fits (above 241 edges)."""
+    n_pi = 0
+    while 32768 + 8 * (((n_edges + 1) & ~1) + ((n_pi + 3) & ~1)) + 128 * (n_pi + 1) * (n_edges - 1) <= 65536:
+        n_pi += 1
+    return n_pi
+
+
+def count_projected_shapes_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
+    """Fine-bin projected shape-shape sums for ``cells`` (int[n, 4] = ``(segment of layout_a, segment of layout_b, row of r2,
+    diagonal)``, ``count_projected_fine``'s) -> ``((PP, XX, PX, W), CountStats)``, each plane f64[n_pi, n_cells, E-1]: over the
+    pairs that ``count_projected_pi_fine`` puts into a radius and pi bin, the sums of ``w_a w_b et_a et_b``,
+    ``w_a w_b ex_a ex_b``, ``w_a w_b (et_a ex_b + ex_a et_b)`` and ``w_a w_b``, with ``et``, ``ex`` the ellipticity of either
+    shape rotated to the great circle through the pair (``yawhip_proj_count_shapes``). ``et`` is the tangential ellipticity
+    of ``count_projected_shear_fine``, ``e+ = -et``: the two signs cancel in PP, and PX is minus the ``+x`` product. Both layouts carry shear and redshifts (``build_trees(edges, with_shear=True, with_redshifts=True)``)
+    and are the resident shape handles of ``count_projected_shear_fine`` (role "projected shapes <kind>"): a catalogue
+    uploaded for ``w_g+`` is not uploaded again, and the same layout twice is ONE handle passed twice -- only then a cell
+    may be diagonal. More pi bins than ``max_shape_pi_bins`` gives at this number of radius edges is a ``ValueError`` that
+    states the cap, raised before anything reaches the device; the reach refusal becomes one as in
+    ``count_projected_pi_fine``. No CPU fallback; the CPU tests replace this function."""
+    _require_shear(layout_a, layout_b)
+    check_shape_pi_cap(len(pi_edges) - 1, np.shape(r2)[1])
+    ctx = get_context()
+    a = _proj_shape_handle(layout_a, ctx, cosmology, unit, sort_axis)
+    b = a if layout_b is layout_a else _proj_shape_handle(layout_b, ctx, cosmology, unit, sort_axis)
+    try:
+        return _lib.proj_count_shapes(ctx, a, b, cells, r2, pi_edges)
+    except _lib.YawhipError as err:
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
+        raise
+
+
+def check_shape_pi_cap(n_pi: int, n_edges: int) -> None:
+    """The cap of ``count_projected_shapes_fine`` as a ``ValueError`` that states it."""
+    cap = max_shape_pi_bins(n_edges)
+    if n_pi > cap:
+        fits = f"at most {cap} pi bins fit" if cap else "not even one pi bin fits above 241 radius edges"
+        raise ValueError(f"{n_pi} pi bins are too many for {n_edges} radius edges (the fine bins of the configuration's resolution) "
+                         f"with four planes each: {fits}; use fewer pi bins or a lower resolution")
 
 
 def check_mu_edges(mu_bins) -> np.ndarray:

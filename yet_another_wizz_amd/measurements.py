@@ -21,13 +21,13 @@ from . import _lib, engine, parallel
 from .angular_bins import plan_for_limits, radial_plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
-from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc
+from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc
 from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
 __all__ = ["autocorrelate", "autocorrelate_projected", "autocorrelate_multipoles", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
-           "crosscorrelate_shear", "crosscorrelate_delta_sigma", "crosscorrelate_alignment", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
+           "crosscorrelate_shear", "crosscorrelate_delta_sigma", "crosscorrelate_alignment", "autocorrelate_alignment", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "radial_plans", "radial_max_angle", "check_patch_conistency"]
 
 logger = logging.getLogger("yet_another_wizz_amd")
@@ -727,6 +727,34 @@ class PatchLinkage:
         return [[(t[s], x[s], w[s]) for t, x, w in zip(planes[:n_pi], planes[n_pi:2 * n_pi], planes[2 * n_pi:])]
                 for s in range(self.config.scales.num_scales)]
 
+    def count_shape_pairs(self, shapes: Catalog, shapes2: Catalog | None = None, *, pi_max: float, pi_bins=None, progress: bool = False,
+                          max_workers: int | None = None, count_type_info: str | None = None) -> list:
+        """The projected shape-shape sums of the catalogue ``shapes`` with itself (``shapes2=None``: the linked patch pairs
+        ``p <= q``, a diagonal slot holding every unordered pair of its patch once, as ``count_projected_pairs`` counts an
+        auto count) or with a second shape catalogue (all linked patch pairs): every pair is binned in its own radius and in
+        ``pi = |chi_a - chi_b|`` as ``count_projected_pairs(pi_bins=...)`` bins it (``pi_bins=None``: one bin ``[0, pi_max]``),
+        and BOTH ellipticities are rotated to the great circle through the pair -> a list over scales of lists over pi bins
+        of ``(PP, XX, PX, W)``, four ``NormalisedCounts`` over ONE ``PatchedSumWeights``: the sums of ``w_a w_b et_a et_b``,
+        ``w_a w_b ex_a ex_b``, ``w_a w_b (et_a ex_b + ex_a et_b)`` (signed; ``et = -e+`` the tangential ellipticity of
+        ``count_alignment_pairs``, so PX is minus the ``+x`` product) and of ``w_a w_b``. The catalogues carry shear and
+        redshifts (``build_trees(edges, with_shear=True, with_redshifts=True)``). Cells, recombination, linkage and the
+        one-process rule are ``count_projected_pairs``'; ONE library call counts all cells
+        (``engine.count_projected_shapes_fine``)."""
+        if parallel.world()[1] > 1:
+            raise NotImplementedError("projected counts run in one process on one device")
+        _require_distinct(shapes, shapes2)
+        pi_edges = engine.check_pi_edges(1 if pi_bins is None else pi_bins, pi_max)
+
+        def call(layout_a, layout_b, cells, r2, **kwargs):
+            if any(layout.g1 is None or layout.g2 is None for layout in (layout_a, layout_b)):
+                raise ValueError("a shape catalogue carries no shear: build_trees(edges, with_shear=True, with_redshifts=True)")
+            planes, stats = engine.count_projected_shapes_fine(layout_a, layout_b, cells, r2, pi_edges=pi_edges, **kwargs)
+            return np.concatenate([np.asarray(plane, dtype=np.float64) for plane in planes]), stats  # [4 n_pi, n_cells, E-1]
+
+        planes = self._count_projected_cells(shapes, shapes2, call, count_type_info, progress)
+        n_pi = len(pi_edges) - 1
+        return [[tuple(planes[c * n_pi + j][s] for c in range(4)) for j in range(n_pi)] for s in range(self.config.scales.num_scales)]
+
     def _count_projected_cells(self, main_catalog, second_catalog, call, count_type_info, progress) -> list:
         """What the counts over projected handles share: the layout checks, the cell list of the linked patch pairs and
         ``_count_shear_planes`` on the radial plan. ``call(layout1, layout2, cells, r2, cosmology=, unit=, sort_axis=)`` is the
@@ -1021,6 +1049,57 @@ def crosscorrelate_alignment(config, shapes: Catalog, density: Catalog, density_
             for planes, counts in zip(bins, rr):
                 planes["rr"] = counts
         result.append(AlignmentCorrFunc(pi_edges, bins))
+    return result
+
+
+def autocorrelate_alignment(config, shapes: Catalog, shape_rand: Catalog | None = None, *, pi_max: float, pi_bins=None,
+                            progress: bool = False, max_workers: int | None = None) -> list:
+    """Projected shape-shape correlation of the shape sample ``shapes``: the intrinsic-alignment signals ``w_++(r_p)`` and
+    ``w_xx(r_p)`` and the parity-odd null test ``w_+x(r_p)`` -> ``[ShapeShapeCorrFunc]``, one per scale of the configuration
+    (no counterpart in the reference). ``cf.sample("plus")`` is ``w_++``, ``cf.sample("cross")`` is
+    ``w_xx``, ``cf.sample("plus_cross")`` is ``w_+x``, each with jackknife samples over the patches;
+    ``cf.sample_xi(component)`` gives the pi bins.
+
+    Every unordered pair of two shapes is binned in its own radius ``r_p = (d_a + d_b) / 2 * theta`` and in
+    ``pi = |chi_a - chi_b| <= pi_max``, and both ellipticities are rotated to the great circle through the pair. One
+    library call sums the planes ``S+S+``, ``SxSx``, ``S+Sx`` and the pair weights. With ``shape_rand`` one more call, of
+    the count of ``autocorrelate_projected``, gives ``R_S R_S`` and the estimator is ``S+S+ / R_S R_S`` per pi bin, each
+    count over its own normalisation; without randoms it is ``S+S+ / W``, the pair-weighted mean product, as
+    ``autocorrelate_shear`` reports ``xi_+``. The two differ by the factor ``1 + xi_gg`` of the sample's own clustering.
+    ``pi_bins`` is a number of equal bins from 0 to ``pi_max`` or their edges; ``None`` is one bin ``[0, pi_max]``. The
+    number of pi bins is capped by the device's LDS (21 at 12 fine bins, 5 at 50); beyond the cap the call is a
+    ``ValueError`` that states it.
+
+    ``shapes`` carries ``g1`` / ``g2`` and redshifts, ``shape_rand`` redshifts. Units, ``pi_max``, redshift bins (pairs are
+    counted INSIDE a bin), reach and the one-process rule are ``autocorrelate_projected``'s; the catalogues are separate
+    ``Catalog`` instances."""
+    _require_distinct(shapes, shape_rand)
+    if parallel.world()[1] > 1:
+        raise NotImplementedError("projected counts run in one process on one device")
+    pi_edges = engine.check_pi_edges(1 if pi_bins is None else pi_bins, pi_max)
+    engine.radial_kind(config.scales.scales.unit)  # angular units have no radius: ValueError
+    edges, closed = config.binning.edges, config.binning.closed
+    if not shapes.has_shear:
+        raise ValueError("the shape catalogue has no 'g1'/'g2' attached")
+    _log_info("building trees")
+    layouts = [shapes.build_trees(edges, closed=closed, with_shear=True, with_redshifts=True)]
+    if shape_rand is not None:
+        layouts.append(shape_rand.build_trees(edges, closed=closed, with_redshifts=True))
+    for layout in layouts:
+        engine.check_proj_redshifts(layout)
+    _log_info("computing shape-shape correlation from SS" + (", RR" if shape_rand is not None else ""))
+    catalogs = [cat for cat in (shapes, shape_rand) if cat is not None]
+    links = PatchLinkage.from_catalogs(config, *catalogs, max_angle=radial_max_angle(config, *layouts))
+    kwargs = dict(pi_max=pi_max, pi_bins=pi_edges, progress=progress, max_workers=max_workers)
+    SS = links.count_shape_pairs(shapes, count_type_info="SS", **kwargs)
+    RR = [None] * len(SS) if shape_rand is None else links.count_projected_pairs(shape_rand, count_type_info="RR", **kwargs)
+    result = []
+    for ss, rr in zip(SS, RR):
+        bins = [dict(pp=pp, xx=xx, px=px, w=w) for pp, xx, px, w in ss]
+        if rr is not None:
+            for planes, counts in zip(bins, rr):
+                planes["rr"] = counts
+        result.append(ShapeShapeCorrFunc(pi_edges, bins))
     return result
 
 
