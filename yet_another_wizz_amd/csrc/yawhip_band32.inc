@@ -59,7 +59,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                   unsigned long long *__restrict__ counters, unsigned long long seg_cap) {
     static_assert(NE >= 2 && NE <= 4, "edges per bin");
     constexpr int CH = YAW_B32_CH;  // chunks per round (see the head of this file)
-    // One object per lane (sparse per-bin runs) in the one-chunk kernel: two ENTRIES per trip of the walk, see eval_entry.
+    // One object per lane (sparse per-bin runs) in the one-chunk kernel: two ENTRIES per trip of the walk, see classify_entry.
     // (A chunk is then followed by two sentinel entries; with several chunks in a stage the second would be the next chunk's first.)
     constexpr bool PAIRS = R == 1 && CH == 1;
     constexpr int NS = PAIRS ? 2 : R;  // evaluations per trip
@@ -74,8 +74,15 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
     const int nkb = MERGED ? n_bins : 1;
     const int nslots = nkb * NF;
     unsigned char *p = lds_dyn;
-    constexpr unsigned COLB = (CAP + 4) * 4;  // bytes of one staged float32 column
-    float *stage = reinterpret_cast<float *>(p); p += (size_t)3 * COLB;  // columns x, y, z
+    // The plain one-annulus count with two objects per lane and one threshold row has its trip spelled out (classify_two_objects);
+    // in the one-chunk kernel it also walks its bands DOWNWARDS, from entry hi - 1, so that one saturating subtraction is both
+    // the advance and the clamp of the entry address: below the chunk lie LEAD sentinel entries, the first at LDS address 0.
+    constexpr bool SLOT_TRIP = NE == 2 && !WEIGHTED && R == 2 && !LANE_THR;
+    constexpr bool DOWN = SLOT_TRIP && CH == 1;
+    constexpr int LEAD = DOWN ? 4 : 0;  // (four entries: the chunk keeps the 16-byte alignment the LDS-DMA needs; band32_lds has the 48 bytes)
+    constexpr unsigned COLB = (CAP + 4 + LEAD) * 4;  // bytes of one staged float32 column
+    float *const stage_lead = reinterpret_cast<float *>(p);
+    float *stage = stage_lead + LEAD; p += (size_t)3 * COLB;  // columns x, y, z
     double *sw = reinterpret_cast<double *>(p); if (WEIGHTED) p += (size_t)(CAP + 4) * 8;
     HistT *hist = reinterpret_cast<HistT *>(p); p += (size_t)nslots * sizeof(HistT);
     p = reinterpret_cast<unsigned char *>(((size_t)p + 15) & ~(size_t)15);
@@ -88,6 +95,10 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
     const TicketMap tmap = ticket_map(counters, seg_cap);
     const unsigned long long n_kept = tmap.n_kept;
     for (int e = lane; e < nslots; e += 64) hist[e] = HistT(0);  // every flush leaves the histogram zeroed again
+    if constexpr (DOWN) {
+        if (a_stage != 4u * LEAD) __builtin_trap();  // (the dynamic LDS starts at address 0: nothing is declared in front of it)
+        if (lane < LEAD) { stage_lead[lane] = PAD_COORD32; stage_lead[COLB / 4 + lane] = PAD_COORD32; stage_lead[2 * (COLB / 4) + lane] = PAD_COORD32; }
+    }
     if (LANE_THR)
         for (int e = lane; e < n_bins * TW; e += 64) sthr[e] = thr32[e];
     unsigned round_no = 0;
@@ -328,6 +339,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                 }
             }
             int len = hi - lo;
+            int top = hi - 1;  // the band's last entry (where a downward walk begins)
             unsigned stride = PAIRS ? 8u : 4u;  // bytes between the entries (pairs of entries) a lane evaluates (wave-uniform)
             nev += (unsigned int)(len * n_own);
             // Sparse items -- a lane tile at the border of its patch whose partner run reaches only a few of its objects, the
@@ -379,6 +391,7 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                         stride = 8u << sh;
                     } else {
                         lo = idle ? n : lo_s + part;  // (idle lanes walk the sentinel)
+                        top = lo_s + len_s - 1 - part;  // downwards: the entries hi - 1 - part, hi - 1 - part - S, ... (the same number)
                         len = !idle && len_s > part ? (len_s - part + (1 << sh) - 1) >> sh : 0;
                         stride = 4u << sh;
                     }
@@ -392,7 +405,9 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
             // One entry per evaluation step: three 4-byte reads from columns a fixed distance apart (lanes read nearly
             // consecutive words of a column). A trip past the end of the longest band meets entries beyond every band, or
             // the sentinel: they fail the predicate by themselves.
-            auto eval_entry = [&](const unsigned a16) {
+            // classify_entry is the whole trip of the walk loop: it leaves the undecided evaluations of the entry as wave masks
+            // (any lane undecided: the return value is non-zero) and settle_entry, on the unlikely side of a branch, decides them.
+            auto classify_entry = [&](const unsigned a16, unsigned long long (&unc_mask)[NS], float (&s32)[NS], double (&ewi)[NS]) {
                 // PAIRS (one object per lane, one chunk per round): the trip evaluates TWO neighbouring entries for the lane's
                 // object -- the packed float32 instructions that serve two objects per entry elsewhere serve two entries per
                 // object here (evaluation i = entry a16 + 4 i of object 0); otherwise evaluation i = object i of the entry.
@@ -405,7 +420,6 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                     en1.y = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 4u + COLB);
                     en1.z = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 4u + 2 * COLB);
                 }
-                double ewi[NS];
                 const unsigned a_w = ((a16 - a_stage) << 1) + a_sw;  // the entry's weight (one address for both entries of a pair)
                 ewi[0] = WEIGHTED ? lds_f64(a_w) : 1.0;
                 if constexpr (PAIRS) ewi[1] = WEIGHTED ? lds_f64(a_w + 8u) : 1.0;
@@ -416,7 +430,6 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                 // One annulus: the centre c of the annulus is the addend of the first product, q = s32 - c comes out of the three
                 // fused multiply-adds (no subtraction per evaluation; the host widens both classes by the rounding of the
                 // intermediate sums, build_thr32). More edges: s32 itself.
-                float s32[NS];
                 if constexpr (PAIRS) {
                     const f32x2 dx = ax[0] - f32x2{en.x, en1.x}, dy = ay[0] - f32x2{en.y, en1.y}, dz = az[0] - f32x2{en.z, en1.z};
                     f32x2 sq;
@@ -441,7 +454,6 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                 }
                 // classes as wave masks: "certainly inside / below" feeds the lane counters (add with carry), "possibly" stays
                 // on the scalar unit -- undecided = possibly & ~certainly costs no vector instruction
-                unsigned long long unc_mask[NS];
                 unsigned long long any_mask = 0ull;
 #pragma unroll
                 for (int i = 0; i < NS; ++i) {
@@ -467,47 +479,141 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
                     }
                     any_mask |= unc_mask[i];
                 }
-                if (any_mask != 0ull) {
-                    // inside a guard band: the exact float64 predicate on the float64 columns decides (rare)
+                return any_mask;
+            };
+            // The trip of the plain one-annulus count with two objects per lane and one threshold row (the headline), with every
+            // issue slot spelled out. A wave issues one instruction per turn whatever its class, and hipcc's trip spends 31 turns
+            // on 17 instructions of arithmetic and reads: a result of a packed float32 instruction cannot be read by the very
+            // next instruction and a compare's mask not by an add-with-carry within two, and hipcc fills those places with
+            // s_nop. Here the address of the next trip (advance, clamp) stands where two of them stood, the four compares come
+            // before the two adds, and the reads are waited for once (hipcc: three waits, the first of them for everything).
+            // Same instructions on the same operands as classify_entry: the same float32 values, classes and masks.
+            // Vector and scalar ALU only: the reads stay with the compiler (it places their one wait in front of the statement;
+            // two dependent statements would get an s_nop between them from hipcc's hazard recogniser, hence one).
+            // Walking downwards (DOWN) the two address instructions are one, "a16 = max(a16 - stride, 0)", and the other slot
+            // takes the loop counter's decrement: 13 vector instructions, 25 in all.
+            auto classify_two_objects = [&](unsigned &a16, unsigned &cur_, int &rem, unsigned long long (&unc_mask)[NS]) {
+                // a16: the (clamped) address of this trip's entry on entry, of the next trip's on return; upwards cur_ is
+                // advanced, downwards rem (the trips left) is counted down
+                if constexpr (!SLOT_TRIP) return 0ull;
+                else {
+                f32x2 ex, ey, ez, q, dy, dz;  // an entry's coordinate is the low half of its operand (op_sel_hi: both halves read it)
+                ex.x = *(const __attribute__((address_space(3))) float *)(size_t)a16;
+                ey.x = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + COLB);
+                ez.x = *(const __attribute__((address_space(3))) float *)(size_t)(a16 + 2 * COLB);
+                // (q is pinned to v[0:1], a pair the compiler keeps for temporaries: the compares name its halves)
+                unsigned long long in1, any_mask;
+#define YAW_TRIP_SUMS_(slot)                                                                          \
+    "v_pk_add_f32 v[0:1], %[ax], %[ex] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"                   \
+    "v_pk_add_f32 %[dy], %[ay], %[ey] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"                    \
+    "v_pk_fma_f32 v[0:1], v[0:1], v[0:1], %[nc]\n\t"                                                    \
+    "v_pk_add_f32 %[dz], %[az], %[ez] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]\n\t"                    \
+    "v_pk_fma_f32 v[0:1], %[dy], %[dy], v[0:1]\n\t" slot "\n\t"                                        \
+    "v_pk_fma_f32 v[0:1], %[dz], %[dz], v[0:1]\n\t"
+#define YAW_TRIP_CLASSES_                                     \
+    "v_cmp_lt_f32_e64 vcc, |v0|, %[hin]\n\t"                  \
+    "v_cmp_lt_f32_e64 %[in1], |v1|, %[hin]\n\t"               \
+    "v_cmp_lt_f32_e64 %[u0], |v0|, %[hout]\n\t"               \
+    "v_cmp_lt_f32_e64 %[u1], |v1|, %[hout]\n\t"               \
+    "s_andn2_b64 %[u0], %[u0], vcc\n\t"                       \
+    "s_andn2_b64 %[u1], %[u1], %[in1]\n\t"                    \
+    "v_addc_co_u32_e64 %[c0], vcc, 0, %[c0], vcc\n\t"         \
+    "v_addc_co_u32_e64 %[c1], %[in1], 0, %[c1], %[in1]\n\t"   \
+    "s_or_b64 %[any], %[u0], %[u1]"
+                if constexpr (DOWN) {
+                    asm volatile(YAW_TRIP_SUMS_("v_sub_u32_e64 %[a], %[a], %[stride] clamp") "s_add_i32 %[rem], %[rem], -1\n\t" YAW_TRIP_CLASSES_
+                                 : [q] "=&{v[0:1]}"(q), [dy] "=&v"(dy), [dz] "=&v"(dz), [a] "+v"(a16), [rem] "+s"(rem),
+                                   [in1] "=&s"(in1), [u0] "=&s"(unc_mask[0]), [u1] "=&s"(unc_mask[1]), [any] "=&s"(any_mask),
+                                   [c0] "+v"(cnt[0][0]), [c1] "+v"(cnt[1][0])
+                                 : [ax] "v"(ax2[0]), [ay] "v"(ay2[0]), [az] "v"(az2[0]), [ex] "v"(ex), [ey] "v"(ey), [ez] "v"(ez),
+                                   [nc] "s"(nc2[0]), [stride] "s"(stride), [hin] "s"(th[0][1]), [hout] "s"(th[0][2])
+                                 : "vcc", "scc");
+                } else {
+                    asm volatile(YAW_TRIP_SUMS_("v_add_u32 %[cur], %[stride], %[cur]") "v_min_u32 %[nxt], %[last], %[cur]\n\t" YAW_TRIP_CLASSES_
+                                 : [q] "=&{v[0:1]}"(q), [dy] "=&v"(dy), [dz] "=&v"(dz), [cur] "+v"(cur_), [nxt] "=&v"(a16),
+                                   [in1] "=&s"(in1), [u0] "=&s"(unc_mask[0]), [u1] "=&s"(unc_mask[1]), [any] "=&s"(any_mask),
+                                   [c0] "+v"(cnt[0][0]), [c1] "+v"(cnt[1][0])
+                                 : [ax] "v"(ax2[0]), [ay] "v"(ay2[0]), [az] "v"(az2[0]), [ex] "v"(ex), [ey] "v"(ey), [ez] "v"(ez),
+                                   [nc] "s"(nc2[0]), [stride] "s"(stride), [last] "s"(last), [hin] "s"(th[0][1]), [hout] "s"(th[0][2])
+                                 : "vcc", "scc");
+                }
+#undef YAW_TRIP_SUMS_
+#undef YAW_TRIP_CLASSES_
+                return any_mask;
+                }
+            };
+            // inside a guard band: the exact float64 predicate on the float64 columns decides (rare). The entry's address, masks,
+            // float32 distances and weights are what classify_entry left of the trip.
+            auto settle_entry = [&](const unsigned a16, const unsigned long long (&unc_mask)[NS], const float (&s32)[NS], const double (&ewi)[NS]) {
 #pragma unroll
-                    for (int i = 0; i < NS; ++i) {
-                        const int r = PAIRS ? 0 : i;
-                        const unsigned eidx = ((a16 - a_chunk) >> 2) + (PAIRS ? (unsigned)i : 0u);
-                        const double ew = ewi[i];
-                        if (((unc_mask[i] >> lane) & 1ull) && eidx < (unsigned)n && r < n_own) {
-                            const ExactEval<NE> ev = band32_exact<NE>(cl.x, cl.y, cl.z, it.a0 + lane_obj * R + r, cs.x, cs.y, cs.z,
-                                                                      cs.idx ? (int64_t)cs.idx[cb[c] + eidx] : cb[c] + (int64_t)eidx,
-                                                                      t + (size_t)(MERGED ? kb[r] : kfix) * NE,
-                                                                      counters + EXACT_EVAL_CTR(0) + CTR_SLOT_WORDS * (ticket & (EVAL_SLOTS - 1)));
-                            const double sd = ev.s;
-                            if constexpr (NE == 2) {
-                                const bool in = sd > ev.th[0] && sd <= ev.th[1];
-                                if constexpr (WEIGHTED) acc[r][0] += in ? ew : 0.0;
-                                else cnt[r][0] += in ? 1u : 0u;
-                            } else {
+                for (int i = 0; i < NS; ++i) {
+                    const int r = PAIRS ? 0 : i;
+                    const unsigned eidx = ((a16 - a_chunk) >> 2) + (PAIRS ? (unsigned)i : 0u);
+                    const double ew = ewi[i];
+                    if (((unc_mask[i] >> lane) & 1ull) && eidx < (unsigned)n && r < n_own) {
+                        const ExactEval<NE> ev = band32_exact<NE>(cl.x, cl.y, cl.z, it.a0 + lane_obj * R + r, cs.x, cs.y, cs.z,
+                                                                  cs.idx ? (int64_t)cs.idx[cb[c] + eidx] : cb[c] + (int64_t)eidx,
+                                                                  t + (size_t)(MERGED ? kb[r] : kfix) * NE,
+                                                                  counters + EXACT_EVAL_CTR(0) + CTR_SLOT_WORDS * (ticket & (EVAL_SLOTS - 1)));
+                        const double sd = ev.s;
+                        if constexpr (NE == 2) {
+                            const bool in = sd > ev.th[0] && sd <= ev.th[1];
+                            if constexpr (WEIGHTED) acc[r][0] += in ? ew : 0.0;
+                            else cnt[r][0] += in ? 1u : 0u;
+                        } else {
 #pragma unroll
-                                for (int e = 0; e < NE; ++e) {
-                                    const bool open = !(s32[i] < th[r][2 * e]) && s32[i] <= th[r][2 * e + 1];  // this edge was left undecided
-                                    const bool le = open && sd <= ev.th[e];
-                                    if constexpr (WEIGHTED) acc[r][e] += le ? ew : 0.0;
-                                    else cnt[r][e] += le ? 1u : 0u;
-                                }
+                            for (int e = 0; e < NE; ++e) {
+                                const bool open = !(s32[i] < th[r][2 * e]) && s32[i] <= th[r][2 * e + 1];  // this edge was left undecided
+                                const bool le = open && sd <= ev.th[e];
+                                if constexpr (WEIGHTED) acc[r][e] += le ? ew : 0.0;
+                                else cnt[r][e] += le ? 1u : 0u;
                             }
                         }
                     }
                 }
             };
-            // UNROLL entries per trip of the loop: their LDS reads go out together and the loop's own instructions are shared.
-            // 1, 2 and 4 measure the same (0.362 / 0.366 / 0.374 ms at the headline). The loop keeps its two levels at depth 1:
-            // written as one plain loop, hipcc 7.2 schedules every variant differently (and, in sum, to more instructions).
-            constexpr int UNROLL = 1;
-            for (int s = 0; s < steps; s += UNROLL) {
-#pragma unroll
-                for (int uu = 0; uu < UNROLL; ++uu) {
-                    const unsigned at = cur + stride * (unsigned)uu;
-                    eval_entry(at < last ? at : last);
+            // One entry per trip (1, 2 and 4 measured the same: 0.362 / 0.366 / 0.374 ms at the headline). The exact path is the
+            // unlikely side of a branch inside the loop: the trip falls through to the latch. (Taken out of the loop -- an inner
+            // loop left with the undecided entry, a resume loop around it -- hipcc 7.2 unifies the two exits through flag
+            // registers: 42 instead of 31 instructions per trip. DESIGN.md section 8.)
+            if constexpr (DOWN) {
+                // from the band's last entry down to its first, then on into the entries below the band or the sentinels in front
+                // of the chunk (lanes without a band: the sentinel at address 0 from the start)
+                const unsigned start = len > 0 ? a_chunk + ((unsigned)top << 2) : 0u;
+                unsigned a16 = start, unused = 0u;
+                int rem = steps;
+                while (rem != 0) {
+                    unsigned long long unc_mask[NS];
+                    if (__builtin_expect(classify_two_objects(a16, unused, rem, unc_mask) != 0ull, 0)) {
+                        const float s32[NS] = {0.0f, 0.0f};  // (one annulus, no weights: the exact path reads neither)
+                        const double ewi[NS] = {1.0, 1.0};
+                        const unsigned back = (unsigned)(steps - rem - 1) * stride;  // the entry of this trip again
+                        settle_entry(start > back ? start - back : 0u, unc_mask, s32, ewi);
+                    }
                 }
-                cur += stride * UNROLL;
+            } else if constexpr (SLOT_TRIP) {
+                unsigned a16 = cur < last ? cur : last;  // the clamped address of a trip is made in a slot of the trip before
+                int unused = 0;
+                for (int s = 0; s < steps; ++s) {
+                    unsigned long long unc_mask[NS];
+                    if (__builtin_expect(classify_two_objects(a16, cur, unused, unc_mask) != 0ull, 0)) {
+                        const float s32[NS] = {0.0f, 0.0f};  // (one annulus, no weights: the exact path reads neither)
+                        const double ewi[NS] = {1.0, 1.0};
+                        const unsigned at = cur - stride;    // the entry of this trip again
+                        settle_entry(at < last ? at : last, unc_mask, s32, ewi);
+                    }
+                }
+            } else {
+                auto eval_entry = [&](const unsigned a16) {
+                    unsigned long long unc_mask[NS];
+                    float s32[NS];
+                    double ewi[NS];
+                    if (__builtin_expect(classify_entry(a16, unc_mask, s32, ewi) != 0ull, 0)) settle_entry(a16, unc_mask, s32, ewi);
+                };
+                for (int s = 0; s < steps; ++s) {
+                    eval_entry(cur < last ? cur : last);
+                    cur += stride;
+                }
             }
             }
             }

@@ -100,8 +100,10 @@ __host__ __device__ inline size_t band_lds_dynamic(bool weighted, bool need_thr,
 }
 // dynamic LDS of a k_count_band32 workgroup (host and device agree through this one function)
 __host__ __device__ inline size_t band32_lds(bool weighted, int cap, int nslots, int thr_rows, int ne) {
+    // (+ 48: the plain one-annulus count with one threshold row walks its bands downwards onto four sentinel entries in front
+    // of each column, yawhip_band32.inc DOWN)
     return (size_t)3 * (cap + 4) * 4 + (weighted ? (size_t)(cap + 4) * 8 : 0) + (size_t)nslots * (weighted ? 8 : 4) +
-           (size_t)thr_rows * thr32_width(ne) * 4 + 32;
+           (size_t)thr_rows * thr32_width(ne) * 4 + 32 + (!weighted && ne == 2 && thr_rows == 0 ? 48 : 0);
 }
 __host__ __device__ inline size_t band32_fine_lds(bool weighted, int cap, int nslots, int rows, int n_edges) {
     return (size_t)3 * (cap + 4) * 4 + (weighted ? (size_t)(cap + 2) * 8 : 0) + (size_t)nslots * (weighted ? 8 : 4) + 64 * 8 +
