@@ -1,19 +1,22 @@
-"""GPU: which kind of ``yawhip_shear_sources`` handle each argument of the six lensing and projected counts takes (DESIGN.md
-section 21). One handle of each of the five kinds -- shear, excess-surface-density sources, lenses, radial lenses, projected
--- from the same 8 objects in 2 patches goes to every handle argument of every count, with an empty job or cell list: no
-kernel runs, and the role checks precede everything that depends on the list.
+"""GPU: which kind of ``yawhip_shear_sources`` handle each argument of the ten lensing and projected counts takes (DESIGN.md
+sections 21 and 26). One handle of each of the six kinds -- shear, excess-surface-density sources, lenses, radial lenses,
+projected, projected shapes -- from the same 8 objects in 2 patches goes to every handle argument of every count, with an
+empty job or cell list: no kernel runs, and the role checks precede everything that depends on the list.
 
-The table below was written from the checks of the library as it stood before the handle had a ``kind`` (flags and pointer
-tests per entry point) and run against that library; the single role check that replaced them must answer the same. The six
-counts have ten handle arguments (the lens side of ``yawhip_shear_count`` is a ``yawhip_catalog``, not such a handle): 50 cases,
-and two more where another check than the role's answers first. A last case uploads the kinds without objects from NULL columns."""
+The first six counts of the table below were written from the checks of the library as it stood before the handle had a
+``kind`` (flags and pointer tests per entry point), the four counts over projected cells that came later from the five entry
+points as they stood before they shared one path; each part was run against that library, and the code that replaced it must
+answer the same. The ten counts have eighteen handle arguments (the lens side of ``yawhip_shear_count`` is a
+``yawhip_catalog``, not such a handle): 108 cases, and two more where another check than the role's answers first. One case
+uploads the kinds without objects from NULL columns, and the last ones hold the order of the refusals of the five counts over
+projected cells: a call that is wrong in two places answers with the earlier check."""
 import numpy as np
 import pytest
 
 from yet_another_wizz_amd import _lib, engine
 
 pytestmark = pytest.mark.gpu
-KINDS = ("shear", "dsigma_sources", "lenses", "radial_lenses", "projected")
+KINDS = ("shear", "dsigma_sources", "lenses", "radial_lenses", "projected", "projected_shapes")
 N_PATCHES, N_BINS = 2, 2
 
 # the refusals, as regular expressions of ``re.search`` (the library's message ends the exception's text)
@@ -21,24 +24,36 @@ NOT_SHEAR = "not a shear catalogue"
 NOT_LENSES = "lenses are not a handle of yawhip_dsigma_upload_lenses$"
 NOT_RADIAL = "not a handle of yawhip_dsigma_upload_lenses_radial$"
 NOT_SOURCES = "sources are not a handle of yawhip_dsigma_upload_sources"
-NOT_PROJECTED = "is not one of yawhip_proj_upload"
+NOT_PROJECTED = "a handle is not one of yawhip_proj_upload$"
+NOT_DENSITY = "the density handle is not one of yawhip_proj_upload$"
+NOT_A_SHAPE = "the shape handle is not one of yawhip_proj_upload_shapes"
+NOT_SHAPES = "a handle is not one of yawhip_proj_upload_shapes"
 OK = None
 
 # argument -> what it answers to a handle of each kind, in the order of KINDS
 TABLE = {
-    ("shear_count", "sources"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
-    ("shear_auto_count", "sources"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
-    ("shear_pair_count", "a"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
-    ("shear_pair_count", "b"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
-    ("dsigma_count", "lenses"): (NOT_LENSES, NOT_LENSES, OK, OK, NOT_LENSES),
-    ("dsigma_count", "sources"): (NOT_SOURCES, OK, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES),
+    ("shear_count", "sources"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
+    ("shear_auto_count", "sources"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
+    ("shear_pair_count", "a"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
+    ("shear_pair_count", "b"): (OK, OK, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR, NOT_SHEAR),
+    ("dsigma_count", "lenses"): (NOT_LENSES, NOT_LENSES, OK, OK, NOT_LENSES, NOT_LENSES),
+    ("dsigma_count", "sources"): (NOT_SOURCES, OK, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES),
     # (a handle that is no lens handle at all is told so before the radial count asks for the column m)
-    ("dsigma_count_radial", "lenses"): (NOT_LENSES, NOT_LENSES, NOT_RADIAL, OK, NOT_LENSES),
-    ("dsigma_count_radial", "sources"): (NOT_SOURCES, OK, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES),
-    ("proj_count", "a"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK),
-    ("proj_count", "b"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK),
+    ("dsigma_count_radial", "lenses"): (NOT_LENSES, NOT_LENSES, NOT_RADIAL, OK, NOT_LENSES, NOT_LENSES),
+    ("dsigma_count_radial", "sources"): (NOT_SOURCES, OK, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES, NOT_SOURCES),
+    ("proj_count", "a"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count", "b"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count_pi", "a"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count_pi", "b"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count_smu", "a"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count_smu", "b"): (NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, NOT_PROJECTED, OK, NOT_PROJECTED),
+    ("proj_count_shear", "dens"): (NOT_DENSITY, NOT_DENSITY, NOT_DENSITY, NOT_DENSITY, OK, NOT_DENSITY),
+    ("proj_count_shear", "shapes"): (NOT_A_SHAPE, NOT_A_SHAPE, NOT_A_SHAPE, NOT_A_SHAPE, NOT_A_SHAPE, OK),
+    ("proj_count_shapes", "a"): (NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, OK),
+    ("proj_count_shapes", "b"): (NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, NOT_SHAPES, OK),
 }
-PLANES = {"shear_count": 3, "shear_auto_count": 4, "shear_pair_count": 4, "dsigma_count": 3, "dsigma_count_radial": 3, "proj_count": 1}
+PLANES = {"shear_count": 3, "shear_auto_count": 4, "shear_pair_count": 4, "dsigma_count": 3, "dsigma_count_radial": 3, "proj_count": 1,
+          "proj_count_pi": 1, "proj_count_smu": 1, "proj_count_shear": 3, "proj_count_shapes": 4}  # (one pi or mu bin each)
 CASES = [(count, arg, kind) for (count, arg) in TABLE for kind in KINDS]
 
 
@@ -64,6 +79,7 @@ def handles():
         "lenses": _lib.DsigmaLenses(ctx, x, y, z, w, f, c, N_PATCHES, N_BINS, binned),
         "radial_lenses": _lib.DsigmaLenses(ctx, x, y, z, w, f, c, N_PATCHES, N_BINS, binned, m=m),
         "projected": _lib.ProjHandle(ctx, x, y, z, w, d, c, N_PATCHES, N_BINS, binned),
+        "projected_shapes": _lib.ProjShapesHandle(ctx, x, y, z, w, g1, g2, d, c, N_PATCHES, N_BINS, binned),
     }
     yield made
     for name, handle in made.items():
@@ -91,8 +107,29 @@ def call(h, count, arg, given):
         lenses = given if arg == "lenses" else h["radial_lenses"]
         sources = given if arg == "sources" else h["dsigma_sources"]
         return getattr(_lib, count)(ctx, lenses, sources, jobs, table_of(N_BINS))
-    a, b = (given, h["projected"]) if arg == "a" else (h["projected"], given)
-    return _lib.proj_count(ctx, a, b, np.empty((0, 4), dtype=np.int32), table_of(N_BINS), 40.0)
+    return call_projected(h, count, arg, given, np.empty((0, 4), dtype=np.int32))
+
+
+PI_EDGES, M2_EDGES = np.array([0.0, 40.0]), np.array([0.0, 1.0])  # one bin each
+
+
+def call_projected(h, count, arg, given, cells, *, pmax=40.0, pi_edges=PI_EDGES, m2=M2_EDGES):
+    """One of the five counts over projected cells with ``given`` as its argument ``arg`` and a handle it takes as the other;
+    the planes of the counts with a second binning come back one per bin, as the others' do."""
+    ctx, r2 = h["ctx"], table_of(N_BINS)
+    if count == "proj_count_shear":
+        dens, shapes = (given, h["projected_shapes"]) if arg == "dens" else (h["projected"], given)
+        planes, stats = _lib.proj_count_shear(ctx, dens, shapes, cells, r2, pi_edges)
+        return (*(p for plane in planes for p in plane), stats)
+    other = h["projected_shapes" if count == "proj_count_shapes" else "projected"]
+    a, b = (given, other) if arg == "a" else (other, given)
+    if count == "proj_count":
+        return _lib.proj_count(ctx, a, b, cells, r2, pmax)
+    if count == "proj_count_shapes":
+        planes, stats = _lib.proj_count_shapes(ctx, a, b, cells, r2, pi_edges)
+        return (*(p for plane in planes for p in plane), stats)
+    fine, stats = _lib.proj_count_pi(ctx, a, b, cells, r2, pi_edges) if count == "proj_count_pi" else _lib.proj_count_smu(ctx, a, b, cells, r2, m2)
+    return (*fine, stats)
 
 
 def check(h, count, arg, given, expected):
@@ -156,3 +193,47 @@ def test_a_check_after_the_roles_still_answers_an_accepted_kind(handles):
         _lib.shear_count(handles["ctx"], handles["catalog"], handles["shear_binned"], jobs, table_of(N_BINS))
     with pytest.raises(_lib.YawhipError, match=r"bin count \(1\) does not fit n_bins=2"):
         _lib.shear_auto_count(handles["ctx"], handles["dsigma_sources"], jobs, table_of(N_BINS))
+
+
+# the five counts over projected cells: (count, its second handle argument, a kind that argument refuses, the refusal, what makes
+# its own argument bad, the refusal of that)
+BAD_PI = dict(pi_edges=np.array([1.0, 2.0]))
+OWN_ARGUMENT = [
+    ("proj_count", "b", "projected_shapes", NOT_PROJECTED, dict(pmax=-1.0), "pmax must be a number >= 0"),
+    ("proj_count_pi", "b", "projected_shapes", NOT_PROJECTED, BAD_PI, "the first pi edge must be 0"),
+    ("proj_count_smu", "b", "projected_shapes", NOT_PROJECTED, dict(m2=np.array([0.0, 0.5])), "squared mu edges must start at 0 and end at 1"),
+    ("proj_count_shear", "shapes", "projected", NOT_A_SHAPE, BAD_PI, "the first pi edge must be 0"),
+    ("proj_count_shapes", "b", "projected", NOT_SHAPES, BAD_PI, "the first pi edge must be 0"),
+]
+# (count, a number of bins beyond its cap at the 2 edges of ``table_of``, the cap): the caps that the library's static_asserts quote
+BEYOND_CAP = [("proj_count_pi", 1024, 1023), ("proj_count_smu", 1024, 1023), ("proj_count_shear", 394, 393), ("proj_count_shapes", 241, 240)]
+
+
+def taken(h, count, arg):
+    """A handle that ``count`` takes as its argument ``arg``."""
+    return h[KINDS[TABLE[count, arg].index(OK)]]
+
+
+@pytest.mark.parametrize("count,arg,kind,not_kind,bad,not_own", OWN_ARGUMENT, ids=[case[0] for case in OWN_ARGUMENT])
+def test_projected_counts_refuse_in_the_order_of_their_checks(handles, count, arg, kind, not_kind, bad, not_own):
+    """The kind of ``b`` is asked before the count's own argument, that before the cap, and the cap before the cells."""
+    cells = np.empty((0, 4), dtype=np.int32)
+    with pytest.raises(_lib.YawhipError, match=not_kind) as refusal:  # the wrong kind of b and a bad pmax / pi edges / mu edges
+        call_projected(handles, count, arg, handles[kind], cells, **bad)
+    assert "(status -5)" in str(refusal.value)  # YAWHIP_ERR_MISMATCH
+    with pytest.raises(_lib.YawhipError, match=not_own):  # (the own argument alone is refused too)
+        call_projected(handles, count, arg, taken(handles, count, arg), cells, **bad)
+    for name, n_bins, cap in BEYOND_CAP:
+        if name != count:
+            continue
+        what = "mu" if count == "proj_count_smu" else "pi"
+        edges = np.linspace(0.0, 1.0, n_bins + 1)
+        bad_edges = dict(m2=edges[::-1].copy()) if what == "mu" else dict(pi_edges=edges + 1.0)
+        with pytest.raises(_lib.YawhipError, match=not_own):  # a bad edge array and a cap that is exceeded
+            call_projected(handles, count, arg, taken(handles, count, arg), cells, **bad_edges)
+        good_edges = dict(m2=edges) if what == "mu" else dict(pi_edges=edges)
+        no_such_cell = np.array([[99, 0, 0, 0]], dtype=np.int32)
+        with pytest.raises(_lib.YawhipError, match=f"do not fit the LDS of a workgroup: at most {cap} {what} bins at n_edges=2$"):
+            call_projected(handles, count, arg, taken(handles, count, arg), no_such_cell, **good_edges)  # ... and a bad cell list
+        with pytest.raises(_lib.YawhipError, match="cell 0 has a segment outside"):  # (within the cap the cell is refused)
+            call_projected(handles, count, arg, taken(handles, count, arg), no_such_cell)

@@ -14,7 +14,7 @@ run of tools/probe_shear_auto.py; the windows of the farther redshift bins are n
 * checks ``--check`` of the cells -- the smallest diagonal and off-diagonal ones that hold pairs -- against the numpy brute force
   of tests/proj_oracle.py: ``|ours - oracle| <= 1e-10 A`` per fine bin, ``A`` the sum of ``|w_a w_b|`` of its pairs;
 * prints one JSON line (device ms, candidates, evaluated, ps per evaluated separation) and appends it to ``--out``
-  (profiles/projected_probe.jsonl holds the committed runs).
+  (profiles/projected_probe.jsonl holds the committed runs), with the word of ``--label`` if one is given.
 
 ``--pi-bins N`` times the pi-binned count instead (``engine.count_projected_pi_fine``, ``yawhip_proj_count_pi``, kernel
 ``k_count_projected_pi``) on the same input, with ``N`` equal bins from 0 to ``--pi-max``, checks the same
@@ -68,6 +68,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--check", type=int, default=4, help="cells compared with the oracle")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "projected_probe.jsonl"))
+    ap.add_argument("--label", default=None, help="a word for the line's \"label\" key, e.g. which tree this run times")
     args = ap.parse_args()
     if _lib.device_count() < 1:
         raise SystemExit("no GPU: nothing to time")
@@ -148,7 +149,7 @@ def main():
             raise SystemExit(f"cells {checked} differ from the oracle by up to {np.max(differs / np.maximum(exp_a, 1e-300)):.3e} A")
         worst = float(np.max(differs[exp_a > 0] / exp_a[exp_a > 0]))
     median = statistics.median(device)
-    line = dict(objects=n, patches=args.patches, bins=nb, jobs=int(len(jobs)), cells=int(len(cells)), fine_bins=int(r2.shape[1] - 1),
+    line = dict(**({"label": args.label} if args.label else {}), objects=n, patches=args.patches, bins=nb, jobs=int(len(jobs)), cells=int(len(cells)), fine_bins=int(r2.shape[1] - 1),
                 rmin_kpc=args.rmin, rmax_kpc=rmax, pi_max_mpc=args.pi_max, max_angle_arcmin=round(float(np.rad2deg(max_angle)) * 60.0, 3),
                 sort_axis=int(links.sort_axis), candidate_pairs=int(stats.candidate_pairs), evaluated=int(stats.evaluated_pairs),
                 kernel_ms=round(median, 3), kernel_ms_spread=[round(min(device), 3), round(max(device), 3)],

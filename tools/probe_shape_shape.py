@@ -18,7 +18,8 @@ to ``--pi-max`` Mpc, all in one process on the same resident handles.
 * asserts that over the whole call ``W`` equals the pair count's planes to 1e-10 and that all report the same candidate and
   evaluated pairs, and checks ``--check`` of the smallest cells that hold pairs against the numpy brute force of
   tests/proj_shape_oracle.py: ``|ours - oracle| <= 1e-10 A`` per pi bin and fine bin;
-* prints one JSON line per case and appends it to ``--out`` (profiles/shape_shape_probe.jsonl holds the committed runs).
+* prints one JSON line per case and appends it to ``--out`` (profiles/shape_shape_probe.jsonl holds the committed runs), with
+  ``wall_ms``, the median wall time of the shape-shape call around its ``kernel_ms``, and the word of ``--label`` if one is given.
 
 Usage:  python tools/probe_shape_shape.py --objects 2e6 --patches 64 --cases 50x1 50x5 12x1 12x21
 """
@@ -29,6 +30,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--check", type=int, default=4, help="cells compared with the oracle")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "shape_shape_probe.jsonl"))
+    ap.add_argument("--label", default=None, help="a word for the line's \"label\" key, e.g. which tree this run times")
     args = ap.parse_args()
     if _lib.device_count() < 1:
         raise SystemExit("no GPU: nothing to time")
@@ -93,10 +96,13 @@ def main():
                       shear=lambda: engine.count_projected_shear_fine(layout_a, layout_b, cells, r2, **kwargs))
         for count in counts.values():
             count()  # warm-up (uploads, code objects)
-        ms, last = {name: [] for name in counts}, {}
+        ms, wall, last = {name: [] for name in counts}, [], {}
         for _ in range(args.repeat):  # in turns: all see the same state of the device
             for name, count in counts.items():
+                t0 = time.perf_counter()
                 last[name] = count()
+                if name == "shapes":
+                    wall.append(1e3 * (time.perf_counter() - t0))
                 ms[name].append(last[name][1].kernel_ms)
         (PP, XX, PX, W), stats = last["shapes"]
         W_pi = last["pairs"][0]
@@ -128,10 +134,11 @@ def main():
         edges_bytes = 8 * (((n_edges + 1) & ~1) + ((n_pi + 2) & ~1))
         lds = {name: 2 * 256 * size + edges_bytes + 4 * planes * n_pi * (n_edges - 1) * 8 for name, (size, planes) in
                dict(shapes=(64, 4), pairs=(48, 1), shear=(48, 3)).items()}
-        line = dict(objects=n, patches=args.patches, bins=nb, jobs=int(len(jobs)), cells=int(len(cells)), fine_bins=n_edges - 1, pi_bins=n_pi,
+        line = dict(**({"label": args.label} if args.label else {}), objects=n, patches=args.patches, bins=nb, jobs=int(len(jobs)), cells=int(len(cells)), fine_bins=n_edges - 1, pi_bins=n_pi,
                     rmin_kpc=args.rmin, rmax_kpc=rmax, pi_max_mpc=args.pi_max, max_angle_arcmin=round(float(np.rad2deg(max_angle)) * 60.0, 3),
                     sort_axis=int(links.sort_axis), candidate_pairs=int(stats.candidate_pairs), evaluated=int(stats.evaluated_pairs),
                     kernel="k_count_projected_shapes", kernel_ms=round(median["shapes"], 3), kernel_ms_spread=spread["shapes"],
+                    wall_ms=round(statistics.median(wall), 3),
                     pairs_kernel="k_count_projected_pi", pairs_kernel_ms=round(median["pairs"], 3), pairs_kernel_ms_spread=spread["pairs"],
                     shear_kernel="k_count_projected_shear", shear_kernel_ms=round(median["shear"], 3), shear_kernel_ms_spread=spread["shear"],
                     ratio_to_pairs=round(median["shapes"] / median["pairs"], 3), ratio_to_shear=round(median["shapes"] / median["shear"], 3),

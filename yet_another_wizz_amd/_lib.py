@@ -915,18 +915,26 @@ def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra
     return (*out, _count_stats(st))
 
 
+def _pi_counts(symbol: str, per_bin: int, ctx: Context, a, b, cells, r2, pi_edges):
+    """What the three counts with pi edges share: ``pi_edges`` as f64[n_pi + 1], ``symbol`` run on ``per_bin * n_pi`` stacked
+    planes, and those as ``per_bin`` planes f64[n_pi, n_cells, E-1] each. Returns ``(planes, CountStats)``."""
+    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
+    if pe.ndim != 1:
+        raise ValueError("pi_edges must be [n_pi + 1]")
+    n_pi = len(pe) - 1
+    fine, stats = _shear_counts(symbol, per_bin * max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp), width=4,
+                                rows="r2 must be [n_rows, n_edges]", stacked=True)
+    return tuple(fine.reshape(per_bin, max(n_pi, 0), *fine.shape[1:])), stats
+
+
 def proj_count_pi(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pi_edges):
     """Run ``yawhip_proj_count_pi``: ``proj_count`` with the pairs binned in ``p = |c_a - c_b|`` besides; ``pi_edges``
     f64[n_pi + 1] starts at exactly 0 and ascends strictly, finite but for a last edge that may be ``inf``; bin 0 is
     ``[0, pe[1]]``, bin j ``(pe[j], pe[j + 1]]``. Returns ``(W, CountStats)``, W f64[n_pi, n_cells, E-1]; its sum over the pi
     bins is ``proj_count``'s W at ``pmax = pi_edges[-1]`` (exactly, for unit weights), and the statistics are that call's.
     ``n_pi (E - 1)`` is capped by the LDS of a workgroup (include/yawhip.h); beyond it the library refuses."""
-    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
-    if pe.ndim != 1:
-        raise ValueError("pi_edges must be [n_pi + 1]")
-    n_pi = len(pe) - 1
-    return _shear_counts("yawhip_proj_count_pi", max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp), width=4,
-                         rows="r2 must be [n_rows, n_edges]", stacked=True)
+    (fine,), stats = _pi_counts("yawhip_proj_count_pi", 1, ctx, a, b, cells, r2, pi_edges)
+    return fine, stats
 
 
 def proj_count_shear(ctx: Context, dens: ProjHandle, shapes: ProjShapesHandle, cells, r2, pi_edges):
@@ -936,13 +944,7 @@ def proj_count_shear(ctx: Context, dens: ProjHandle, shapes: ProjShapesHandle, c
     the sums of ``w_d w_s e_t``, ``w_d w_s e_x`` and ``w_d w_s`` with ``e_t`` the tangential ellipticity of the shape about the
     density object (negative where the shape points at it). ``3 n_pi (E - 1)`` is capped by the LDS of a workgroup
     (include/yawhip.h); beyond it the library refuses."""
-    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
-    if pe.ndim != 1:
-        raise ValueError("pi_edges must be [n_pi + 1]")
-    n_pi = len(pe) - 1
-    fine, stats = _shear_counts("yawhip_proj_count_shear", 3 * max(n_pi, 0), (ctx._h, dens._h, shapes._h), cells, r2, n_pi, _ptr(pe, _dp),
-                                width=4, rows="r2 must be [n_rows, n_edges]", stacked=True)
-    return tuple(fine.reshape(3, max(n_pi, 0), *fine.shape[1:])), stats
+    return _pi_counts("yawhip_proj_count_shear", 3, ctx, dens, shapes, cells, r2, pi_edges)
 
 
 def proj_count_shapes(ctx: Context, a: ProjShapesHandle, b: ProjShapesHandle, cells, r2, pi_edges):
@@ -954,13 +956,7 @@ def proj_count_shapes(ctx: Context, a: ProjShapesHandle, b: ProjShapesHandle, ce
     ellipticity of a shape about its partner, as ``proj_count_shear`` has it: ``e+ = -et``, so PP and XX are the ``++`` and
     ``xx`` products and PX is MINUS the ``+x`` product. ``4 n_pi (E - 1)`` is capped by the LDS of a workgroup
     (include/yawhip.h); beyond it the library refuses."""
-    pe = np.ascontiguousarray(pi_edges, dtype=np.float64)
-    if pe.ndim != 1:
-        raise ValueError("pi_edges must be [n_pi + 1]")
-    n_pi = len(pe) - 1
-    fine, stats = _shear_counts("yawhip_proj_count_shapes", 4 * max(n_pi, 0), (ctx._h, a._h, b._h), cells, r2, n_pi, _ptr(pe, _dp),
-                                width=4, rows="r2 must be [n_rows, n_edges]", stacked=True)
-    return tuple(fine.reshape(4, max(n_pi, 0), *fine.shape[1:])), stats
+    return _pi_counts("yawhip_proj_count_shapes", 4, ctx, a, b, cells, r2, pi_edges)
 
 
 def proj_count_smu(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, m2):

@@ -1,5 +1,6 @@
-// Private to yawhip_shear.hip (the yawhip_shear_*, yawhip_dsigma_* and yawhip_proj_* calls of include/yawhip.h; DESIGN.md
-// sections 15 to 25): the one handle of its uploads and what its kernels see of it. Never installed, not part of the C ABI.
+// Private to yawhip_shear_upload.hip and yawhip_shear.hip (the yawhip_shear_*, yawhip_dsigma_* and yawhip_proj_* calls of
+// include/yawhip.h; DESIGN.md sections 15 to 26): the one handle that the first makes and the second counts on, and what the
+// kernels see of it. Never installed, not part of the C ABI.
 #ifndef YAWHIP_SHEAR_H
 #define YAWHIP_SHEAR_H
 #include <cstdint>
@@ -17,7 +18,7 @@ enum Kind : unsigned {
     DSIGMA_LENSES = 4,   // yawhip_dsigma_upload_lenses: the two columns are f, c as they came
     RADIAL_LENSES = 8,   // yawhip_dsigma_upload_lenses_radial: such lenses with the column m besides
     PROJECTED = 16,      // yawhip_proj_upload: the two columns are d, c as they came
-    PROJECTED_SHAPES = 32,  // yawhip_proj_upload_shapes: the two columns are w g1, w g2, with d in the column u and c in m
+    PROJECTED_SHAPES = 32,  // yawhip_proj_upload_shapes: the two columns are w g1, w g2, with the columns d and c besides
 };
 }  // namespace yawhip_detail
 
@@ -30,7 +31,10 @@ struct yawhip_shear_sources {
     int axis = 2;                               // coordinate the patch segments are sorted by (0 = x, 1 = y, 2 = z)
     yawhip_detail::DevPtr<double> x, y, z, w;   // w may be null (every weight 1.0)
     yawhip_detail::DevPtr<double> wg1, wg2;     // the kind's two columns (a, b); the products w * g1, w * g2 each rounded on its own
-    yawhip_detail::DevPtr<double> u, m;         // u: DSIGMA_SOURCES (u), PROJECTED_SHAPES (d); m: RADIAL_LENSES (m), PROJECTED_SHAPES (c)
+    yawhip_detail::DevPtr<double> extra, extra2;  // what a kind has besides; a count reads them through the view of its kind:
+    //   DSIGMA_SOURCES    extra = u
+    //   RADIAL_LENSES     extra = m
+    //   PROJECTED_SHAPES  extra = d, extra2 = c
     std::vector<double> least;                  // RADIAL_LENSES, PROJECTED, PROJECTED_SHAPES: least m or d per redshift bin over all patches [nb] (+inf: none)
     yawhip_detail::DevPtr<int64_t> off;         // [P * nb + 1]
     std::vector<int64_t> h_off;                 // the same on the host

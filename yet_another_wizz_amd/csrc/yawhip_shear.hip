@@ -1,93 +1,69 @@
-// yawhip_shear.hip -- the shear counts of a catalogue with (g1, g2): tangential and cross shear of a source catalogue around
-// the lenses of a catalogue binned in redshift (yawhip_shear_count; measurements.crosscorrelate_shear),
-// the shear-shear sums of a source catalogue inside its own redshift bins (yawhip_shear_auto_count;
-// measurements.autocorrelate_shear), and the same sums between any two (patch, bin) segments of one or
-// two catalogues (yawhip_shear_pair_count; measurements.correlate_shear_tomographic), and the excess
-// surface density sums of sources with a distance column around lenses with two (yawhip_dsigma_count;
-// measurements.crosscorrelate_delta_sigma), those binned in each lens's own radius instead of one angle
-// per slice (yawhip_dsigma_count_radial; radius="lens" of the two lensing drivers), and the projected
-// pair counts of objects with a transverse distance and a line-of-sight coordinate, binned in each PAIR's own radius inside a
-// line-of-sight cut (yawhip_proj_count; measurements.autocorrelate_projected), and those binned in the
-// line-of-sight separation besides (yawhip_proj_count_pi; autocorrelate_projected(pi_bins=...)), and
-// the pair counts of the same handles binned in the redshift-space separation s and in mu = pi / s (yawhip_proj_count_smu;
-// measurements.autocorrelate_multipoles), and the projected position-shape sums of a shape catalogue
-// with d, c around such handles, the tangential and cross ellipticity per radius and pi bin (yawhip_proj_count_shear;
-// measurements.crosscorrelate_alignment), and the projected shape-shape sums between two such shape
-// catalogues, both ends rotated to the great circle through the pair (yawhip_proj_count_shapes;
-// measurements.autocorrelate_alignment).
-// include/yawhip.h has the contracts, product by product.
+// yawhip_shear.hip -- the counts over the handles of yawhip_shear_upload.hip (yawhip_shear_sources, yawhip_shear.h), ten entry
+// points; include/yawhip.h has the contracts, product by product:
+//   yawhip_shear_count          tangential and cross shear of sources around binned lenses          DESIGN.md section 15
+//   yawhip_shear_auto_count     shear-shear sums inside the redshift bins of one catalogue                              16
+//   yawhip_shear_pair_count     the same between any two (patch, bin) segments of one or two catalogues                 17
+//   yawhip_dsigma_count         excess surface density of sources with a distance column around lenses with two         18
+//   yawhip_dsigma_count_radial  the same binned in each lens's own radius                                               19
+//   yawhip_proj_count           pair counts binned in each PAIR's own radius inside a line-of-sight cut                 20
+//   yawhip_proj_count_pi        ... and binned in the line-of-sight separation besides                                  22
+//   yawhip_proj_count_smu       ... binned in the redshift-space separation s and in mu = pi / s instead                23
+//   yawhip_proj_count_shear     position-shape: tangential and cross ellipticity per radius and pi bin                  24
+//   yawhip_proj_count_shapes    shape-shape: both ends rotated to the great circle through the pair                     25
 //
-// All are ONE streaming walk, shear_walk<P>, under ten thin entry kernels. One workgroup of 256 threads owns one cell (a
-// (job, bin) of the first two counts, an entry of the cell list of the third). Lanes hold 256 objects of the cell's lane
-// segment in registers (parked far away where the tile is padded); the cell's
-// streamed segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose
-// sort key lies within the chord sqrt(t_max) of the tile's keys. The hot loop is the 8-flop separation of k_count,
+// All are ONE streaming walk, shear_walk<P>, under ten thin entry kernels. One workgroup of 256 threads owns one cell. Lanes
+// hold 256 objects of the cell's lane segment in registers (parked far away where the tile is padded); the cell's streamed
+// segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose sort key
+// lies within the chord sqrt(t_max) of the tile's keys. The hot loop is the 8-flop separation of k_count,
 //   s2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2,   fine bin e iff t[k][e] < s2 <= t[k][e + 1]      (float64, nothing contracted)
 // behind a wave-wide ballot; the fine-bin bisection and the pair term run only inside the outer edge. Sums go to one float64
 // LDS histogram [planes][E-1] per wave that only its own wave adds to (the reproducibility assumption of the band kernels: adds
 // of ONE instruction to one cell are serialised by the LDS in a fixed lane order); the four are folded in a fixed order and
 // stored with plain stores, every element written. No floating-point atomic touches global memory. All indices are 64-bit.
 //
-// What differs is a policy P, resolved at compile time -- no branch of it is in the streaming loop (the side in the lanes,
-// P::Lanes, is a ShearView, for DeltaSigma one with the column u):
-//                      Tangential (k_count_shear)                           ShearShear (k_count_shear_auto)
-//   streamed segment   lens.off[p * nb + (nb == 1 ? 0 : k)] of a CatView    off[p * nb + k] of the one ShearView
-//   lane segment       off[q] of the unbinned sources                       off[q * nb + k] of the same handle
-//   streamed object    Obj  (x, y, z, w: 32 bytes)                          Obj6 (x, y, z, w, wg1, wg2: 48 bytes)
-//   key window         only if both sides are sorted along one axis         always
-//   diagonal cells     none                                                 p == q walks only partners with a LARGER index
-//   pair term, planes  one rotation: T, X, W                                two rotations: P, M, C, W
-//   cell, thresholds   cell = job * n_bins + k, row k                       the same
-// ShearPair (k_count_shear_pair) is ShearShear with two views: segment (p, ka) of handle a streamed, (q, kb) of handle b in the
-// lanes, both and the thresholds row read from the call's cell table; the key window is on iff the two handles are sorted along
-// one axis (Tangential's rule); a cell is diagonal iff it pairs one segment of one handle with itself.
-// DeltaSigma (k_count_dsigma) is Tangential with the lenses as a handle of their own: the streamed object is an Obj6
-// (x, y, z, w, f, c), the lane carries the source's u besides, and the pair term is Tangential's rotation scaled by the pair's
-// s = f (1 - c u), dropped altogether where 1 - c u <= 0 (the source in front of its lens).
-// DeltaSigmaRadial (k_count_dsigma_radial) is DeltaSigma with a 64-byte streamed object (x, y, z, m | w, f, c, pad): the ballot
-// holds m_l s2 against the row's last squared radius, and behind it the pair is binned by R2 = m_l th2(s2) (at the policy).
-// Projected (k_count_projected) is ShearPair's cell table, window rule and diagonal cells over two projected handles with a
-// 48-byte streamed object (x, y, z, d | w, c) and ONE plane: the ballot holds DD s2, DD = (0.5 (d_a + d_b))^2, against the
-// row's last squared radius, the pair is binned by R2 = DD th2(s2) and adds w_a w_b iff |c_a - c_b| <= pmax (at the policy).
-// ProjectedPi (k_count_projected_pi) is Projected with the call's n_pi planes instead of one: the pi edges are staged into
-// LDS next to the thresholds, and behind the ballot p = |c_a - c_b| is bisected over them as R2 is over the row.
-// RedshiftSpace (k_count_smu) is Projected with the call's n_mu planes and no cut: the ballot holds fl(DD s2) + P2,
-// P2 = |c_a - c_b|^2 with c read in the hot loop, against the row's last squared s; the pair is binned by S2 = R2 + P2 and goes
-// to the plane that the staged squared mu edges give for P2 against m2 S2 (at the policy).
-// ProjectedShear (k_count_projected_shear) is ProjectedPi with a projected handle streamed and a shape handle (w g1, w g2 | d, c)
-// in the lanes, no diagonal cells and three planes T, X, W per pi bin: the pair that counts gets Tangential's rotation.
-// ProjectedShapes (k_count_projected_shapes) is ProjectedShear with a shape handle streamed too, as a 64-byte object
-// (x, y, z, d | w, c, wg1, wg2), Projected's diagonal cells and four planes PP, XX, PX, W per pi bin: the pair that counts
-// gets ShearShear's two rotations.
+// What differs is a policy P, resolved at compile time -- no branch of it is in the streaming loop. A policy is put together
+// from parts, each written once and described where it stands: where the cells come from (JobCells: a
+// job list and the bins of the streamed side; CellTable: resolved by the host), the seam that says what a pair is binned by
+// (ChordSeam: the squared chord; RadiusSeam: the pair's own radius), the streamed object, what a lane keeps, the staged edges
+// of a second binning with N planes per bin (StagedEdges<N>), and the pair term around rotation() or rotations():
+//   policy (kernel)                               cells      seam         streamed       lane        pair term, planes
+//   Tangential (k_count_shear)                    JobCells   ChordSeam    Obj, CatView   PlainLane   one rotation: T, X, W
+//   ShearShear (k_count_shear_auto)               its own    ChordSeam    StreamedShear  PlainLane   two rotations: P, M, C, W
+//   ShearPair (k_count_shear_pair)                ShearShear with CellTable in the place of its cells
+//   DeltaSigma (k_count_dsigma)                   JobCells   ChordSeam    StreamedShear  with u      DeltaSigmaTerm: T, X, W
+//   DeltaSigmaRadial (k_count_dsigma_radial)      JobCells   m_l of the lens, in an Obj8 with u      DeltaSigmaTerm: T, X, W
+//   Projected (k_count_projected)                 CellTable  RadiusSeam   StreamedProj   CutLane     w_a w_b inside the cut: W
+//   ProjectedPi (k_count_projected_pi)            CellTable  RadiusSeam   StreamedProj   CutLane     StagedEdges<1>: W per pi bin
+//   RedshiftSpace (k_count_smu)                   CellTable  S2 = R2 + P2 StreamedProj   no cut      StagedEdges<1>: W per mu bin
+//   ProjectedShear (k_count_projected_shear)      CellTable  RadiusSeam   StreamedProj   ShapeLanes  StagedEdges<3>: T, X, W
+//   ProjectedShapes (k_count_projected_shapes)    CellTable  RadiusSeam   ObjS, ShapeView ShapeLanes StagedEdges<4>: PP, XX, PX, W
+// A cell is diagonal iff it pairs one segment of one handle with itself; it then walks only partners with a LARGER index,
+// which rests on every term of its policy being bit-symmetric under swapping a and b (stated at the term).
 //
-// Tangential, (x, y, z) the source in the lane and (lx, ly, lz) the lens:
-//   a = x ly - y lx,   rho2 = x x + y y,   b = rho2 lz - z (x lx + y ly),   den = a a + b b
-//   c2 = (a a - b b) / den,   s2p = (2 a b) / den       cos / sin of twice the position angle of the lens seen from the
-//                                                       source, from east towards north (the 1 / rho of the local basis
-//                                                       cancels: no square root, no trigonometry)
-//   T += w_l * -(wg1 c2 + wg2 s2p)     X += w_l * (wg1 s2p - wg2 c2)     W += w_l * w_s        (wg = w_s g, made at upload)
-// den == 0 (the source sits on a pole of the frame): W only.
+// One rotation, (x, y, z) the object a in the lane and (lx, ly, lz) the streamed object b:
+//   pa = x ly - y lx,   rho2 = x x + y y,   pb = rho2 lz - z (x lx + y ly),   den = pa pa + pb pb
+//   c2 = (pa pa - pb pb) / den,   s2p = (2 pa pb) / den   cos / sin of twice the position angle of b seen from a, from east
+//                                                         towards north (the 1 / rho of the local basis cancels: no square
+//                                                         root, no trigonometry)
+//   tv = -(wg1 c2 + wg2 s2p),   xv = wg1 s2p - wg2 c2     (wg = w g of the lane's object, made at upload)
+// Tangential:  T += w_l tv     X += w_l xv     W += w_l w_s.     den == 0 (a sits on a pole of the frame): W only.
+// DeltaSigma:  eff = 1 - c_l u_s;   eff > 0:   s = f_l eff,   ws = w_l s,   T += ws tv,   X += ws xv,   W += (ws s) w_s
+//              eff <= 0: the pair adds nothing, not to W either. den == 0: W only.
 //
-// DeltaSigma, the same rotation (c2, s2p), tv = -(wg1 c2 + wg2 s2p), xv = wg1 s2p - wg2 c2:
-//   eff = 1 - c_l u_s;   eff > 0:   s = f_l eff,   ws = w_l s,   T += ws tv,   X += ws xv,   W += (ws s) w_s
-// eff <= 0: the pair adds nothing, not to W either. den == 0: W only.
-//
-// Shear-shear, objects a, b of the same redshift bin k of ONE handle, both shears rotated to the great circle that joins the
-// two -- each end by its own position angle:
+// Two rotations, each end by its own position angle:
 //   pa = ax by - ay bx,  dot = ax bx + ay by,  pbA = (ax ax + ay ay) bz - az dot,  pbB = (bx bx + by by) az - bz dot
 //   cA, sA from (pa, pbA) and cB, sB from (-pa, pbB) as above;  tA, xA, tB, xB the rotated (weighted) shears
 //   P += tA tB + xA xB    M += tA tB - xA xB    C += tA xB + xA tB    W += w_a w_b        (a den == 0: W only)
-// Every term is bit-symmetric under swapping a and b, so it does not matter which of the two a lane holds.
-//
-//   k_gather_shear   the upload's one gather: columns into the order of the segment sort, with the two products (a lens
-//                    handle keeps its two columns f, c as they came).
-//   k_gather_column  the same gather of the sources' column u, of a radial lens handle's column m and of a shape handle's d, c.
+// Every term is bit-symmetric under swapping a and b, so it does not matter which of the two a lane holds: products and sums
+// of two operands commute, pa changes its sign with the swap and enters as pa pa and as (2 pa) pbA against (-2 pa) pbB, dot is
+// symmetric, and pbA, pbB swap their roles.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <new>
 #include <vector>
 
@@ -106,28 +82,30 @@ constexpr double PAD_COORD = 4.0;  // padded lanes sit >= 3 away from any unit v
 struct alignas(16) Obj {  // one streamed lens in LDS: two 16-byte broadcast reads
     double x, y, z, w;
 };
-
-struct alignas(16) Obj6 {  // one streamed object of the shear-shear count: three 16-byte broadcast reads
-    double x, y, z, w, g1, g2;  // (g1, g2: the weighted shear wg1, wg2 of the handle)
+struct alignas(16) Obj6 {  // one streamed object of a ShearView: three 16-byte broadcast reads
+    double x, y, z, w, g1, g2;  // (g1, g2: the handle's two columns)
 };
-
-// One streamed lens of the per-lens radial count: (x, y, z, m | w, f, c, pad). The hot loop reads the first 32 bytes (two
-// 16-byte broadcast reads, as Tangential reads its Obj), the second half only behind the ballot.
-struct alignas(16) Obj8 {
-    double x, y, z, m, w, g1, g2, pad;  // (g1, g2: the lens columns f, c, where a lens handle keeps them)
+struct alignas(16) Obj8 {  // one streamed lens of the per-lens radial count: (x, y, z, m | w, f, c, pad)
+    double x, y, z, m, w, g1, g2, pad;  // (g1, g2: the lens columns f, c)
 };
-
-// One streamed object of the projected count: (x, y, z, d | w, c). The hot loop reads x, y, z, d (two 16-byte broadcast reads:
-// 48 is a multiple of 16, so every object starts on a 16-byte boundary), w and c only behind the ballot.
-struct alignas(16) ObjP {
+struct alignas(16) ObjP {  // one streamed object of a projected handle: (x, y, z, d | w, c); 48 bytes, so each starts on a 16-byte boundary
     double x, y, z, d, w, c;
 };
+struct alignas(16) ObjS {  // one streamed shape of the shape-shape count: (x, y, z, d | w, c, wg1, wg2)
+    double x, y, z, d, w, c, g1, g2;
+};
 
-// What a lane keeps of its own object in registers (g1, g2: the weighted shear -- of a lens or projected handle its two raw
-// columns; u: what the policy's lane_u() gives: DeltaSigma's column, Projected's pmax and ProjectedPi's last edge, else 0).
-// Not every policy uses every member (Projected: not rho2); what a kernel does not read the compiler drops.
+// What every lane keeps of its own object in registers (g1, g2: the handle's two columns), and what the two families keep
+// besides. What a kernel does not read the compiler drops.
 struct Lane {
-    double x, y, z, w, g1, g2, rho2, u;
+    double x, y, z, w, g1, g2, rho2;
+};
+struct SourceLane : Lane {  // DeltaSigma: the source's column u
+    double u;
+};
+struct ProjLane : Lane {  // the projected counts: the object's d and c, the call's cut and n_pi (call-wide: scalar registers)
+    double cut, d, c;
+    int n_pi;
 };
 
 // x, y, z, w of streamed object i of a CatView or a ShearView; beyond the window (!have) an object nobody reads
@@ -147,30 +125,61 @@ struct Cell {
     bool diag;
 };
 
-// The policies of shear_walk (the table at the head of the file). cell() reads the call's table; add() is the pair term:
-// `wh` the wave's histogram [PLANES][nf], `e` the pair's fine bin. The order of every product and sum is the contract of
-// include/yawhip.h.
-//
-// Two seams say what a pair is binned by: outer(a, b, s) is what the ballot holds against the row's last edge, binned(a, b, s)
-// what is bisected over the row behind it (s: the pair's squared chord, a: the lane, b: the streamed object). Where a count
-// bins the chord itself both ARE s and compile away; then s <= last edge also keeps the bisection inside the row (CAPPED).
-struct ChordBinned {
-    static constexpr bool CAPPED = true;
-    static constexpr bool KEPT_WORK = false;  // the evaluated separations of a diagonal cell: all of them (else: kept_work)
-    static constexpr bool ADD_BINNED = false;  // a policy with the call's planes whose add() takes what binned() gave
-    static constexpr int PER_BIN = 1;  // a policy with the call's planes: the planes per bin of the call (lds_bytes, run_count)
-    // what the walk keeps of a lane's object: a Lane, or a policy's own type that holds more columns and is made from it
-    using LaneT = Lane;
-    template <class L>
-    static __device__ __forceinline__ Lane lane(const L &, int64_t, bool, const Lane &a) { return a; }
-    template <class B>
-    static __device__ __forceinline__ double outer(const Lane &, const B &, double s) { return s; }
-    template <class B>
-    static __device__ __forceinline__ double binned(const Lane &, const B &, double s) { return s; }
+// What a policy with the call's planes has staged in LDS for its pair term (else unused): the edges of its second binning,
+// their planes (P::planes) and P::first_step().
+struct Staged {
+    const double *ext;
+    int planes, top;
 };
 
-// th2 = s q(s) = (2 asin(sqrt(s) / 2))^2 of a squared chord s <= 0.01 (Horner, every operation rounded on its own; the
-// contract of the two counts binned in a radius, include/yawhip.h)
+// ---- The parts of a policy. cell() reads the call's table; add(a, b, wh, e, nf, staged, v) is the pair term: a the lane,
+// b the streamed object, `wh` the wave's histogram [planes][nf], `e` the pair's fine bin, v what binned() gave. The order of
+// every product and sum is the contract of include/yawhip.h.
+
+// what the walk asks of every policy and few answer differently
+struct Policy {
+    static constexpr bool KEPT_WORK = false;  // the evaluated separations of a diagonal cell: all of them (else: kept_work)
+    template <class L> static __device__ __forceinline__ int first_step(const L &) { return 0; }
+};
+
+// the key window of two views: on iff both are sorted along one axis (else the keys say nothing about each other: the whole segment)
+struct SameAxisWindow {
+    template <class A, class B> static __device__ bool windowed(const A &a, const B &b) { return a.axis == b.axis; }
+};
+
+// cells from a job list [n_jobs][2] of (streamed patch, lane patch) over the n_bins redshift bins of the streamed side (a
+// side with one bin is in every bin), the lanes unbinned: cell = job * n_bins + k, thresholds row k
+template <class View>
+struct JobCells : SameAxisWindow {
+    static __device__ Cell cell(const View &lens, const int32_t *__restrict__ jobs, int n_bins, int64_t cell) {
+        const int64_t job = cell / n_bins;
+        const int k = (int)(cell - job * n_bins);
+        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
+        return Cell{p * lens.nb + (lens.nb == 1 ? 0 : k), q, k, false};
+    }
+};
+
+// cells from a table the host resolved: [n_cells][4] = (streamed segment of a, lane segment of b, thresholds row, diagonal)
+struct CellTable : SameAxisWindow {
+    static __device__ Cell cell(const ShearView &, const int32_t *__restrict__ cells, int, int64_t cell) {
+        const int32_t *c = cells + 4 * cell;
+        return Cell{c[0], c[1], c[2], c[3] != 0};
+    }
+};
+
+// Two seams say what a pair is binned by: outer(a, b, s) is what the ballot holds against the row's last edge, binned(a, b, s)
+// what is bisected over the row behind it (s: the pair's squared chord). Where a count bins the chord itself both ARE s and
+// compile away; then s <= last edge also keeps the bisection inside the row (CAPPED).
+struct ChordSeam {
+    static constexpr bool CAPPED = true;
+    template <class A, class B> static __device__ __forceinline__ double outer(const A &, const B &, double s) { return s; }
+    template <class A, class B> static __device__ __forceinline__ double binned(const A &, const B &, double s) { return s; }
+};
+
+// th2 = s q(s) = (2 asin(sqrt(s) / 2))^2 of a squared chord s <= 0.01,
+//   q = 1 + s / 12 + s^2 / 90 + s^3 / 560 + s^4 / 3150 + s^5 / 16632
+// (Horner, every operation rounded on its own; the contract of the counts binned in a radius, include/yawhip.h; the calls cap
+// s at 0.01, where the series is good to 2 ulp)
 __device__ __forceinline__ double squared_angle(double s) {
     double q = 1.0 / 16632.0;
     q = 1.0 / 3150.0 + s * q;
@@ -181,36 +190,204 @@ __device__ __forceinline__ double squared_angle(double s) {
     return s * q;
 }
 
-struct Tangential : ChordBinned {
+// DD = D D, D = 0.5 (d_a + d_b), of a projected lane and a streamed object with d: bit-symmetric under a <-> b
+template <class B>
+__device__ __forceinline__ double pair_dd(const ProjLane &a, const B &b) {
+    const double D = 0.5 * (a.d + b.d);
+    return D * D;
+}
+
+// The seam of the counts binned in each PAIR's own radius: the row holds squared radii r2, every object carries d (transverse
+// distance per radian, > 0), and a pair is binned by R2 = DD th2(s2).
+// The ballot holds fl(scale s2), scale = DD, against the last edge. That is an EXACT superset of the pairs in range, with no
+// guard term: every coefficient of q and s2 are >= 0, so each Horner step is >= its constant and the last one gives q >= 1
+// after rounding; rounding is monotone, so th2 = fl(s2 q) >= fl(s2 * 1) = s2 and R2 = fl(scale th2) >= fl(scale s2)
+// (scale >= 0). A pair with R2 <= r2max therefore has fl(scale s2) <= r2max. The converse fails (R2 may exceed the last edge
+// behind the ballot): the bisection then runs off the row and the pair is dropped (!CAPPED).
+// A padded lane is parked at PAD_COORD with d_a = c_a = 0 and is excluded by `ok` before anything is binned. A padded streamed
+// object (beyond the window, !have) has d = 0, which WOULD pass the outer test: nobody reads it, the loop over a stage stops at
+// the stage's count n.
+struct RadiusSeam {
+    static constexpr bool CAPPED = false;
+    template <class B> static __device__ __forceinline__ double outer(const ProjLane &a, const B &b, double s) { return pair_dd(a, b) * s; }
+    template <class B> static __device__ __forceinline__ double binned(const ProjLane &a, const B &b, double s) { return pair_dd(a, b) * squared_angle(s); }
+};
+
+// the streamed side is a ShearView (or a view that is one) with its two columns
+struct StreamedShear {
+    using Streamed = Obj6;
+    using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
+    static __device__ Obj6 load(const ShearView &v, int64_t i, bool have) {
+        Obj6 o = load_xyzw<Obj6>(v, i, have);
+        o.g1 = have ? v.wg1[i] : 0.0; o.g2 = have ? v.wg2[i] : 0.0;
+        return o;
+    }
+};
+
+// the streamed side is a projected handle: its two columns are d, c as they came
+struct StreamedProj {
+    using View = ShearView;
+    using Streamed = ObjP;      // (x, y, z, d | w, c)
+    using Read = const ObjP &;  // the hot loop reads x, y, z, d (two ds_read_b128); w, c behind the ballot
+    static __device__ ObjP load(const ShearView &v, int64_t i, bool have) {
+        ObjP o;
+        o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
+        o.d = have ? v.wg1[i] : 0.0;
+        o.w = (have && v.w) ? v.w[i] : 1.0;
+        o.c = have ? v.wg2[i] : 0.0;
+        return o;
+    }
+};
+
+// the lane keeps what the walk loaded and nothing else
+struct PlainLane {
+    using LaneT = Lane;
+    template <class L> static __device__ __forceinline__ Lane lane(const L &, int64_t, bool, const Lane &a) { return a; }
+};
+
+// The lanes of the projected counts (device memory; the kernels take them by value) ...
+struct ProjLanes : ShearView {  // a projected handle (wg1, wg2 hold d, c as they came) and the call's pmax
+    double pmax;
+};
+
+// ... with a second binning: the call's edges[n + 1] of it, which the workgroup stages into LDS once -- pi edges, the last of
+// which comes by value besides as the cut (Projected's pmax)
+struct ProjPiLanes : ShearView {
+    const double *edges;
+    int n;
+    double pmax;
+};
+// ... or squared mu edges, with the first step of their bisection, the largest power of two <= n - 1 (0 at one plane: nothing
+// is bisected) and no call-wide cut
+struct SmuLanes : ShearView {
+    const double *edges;
+    int n, step;
+};
+struct ProjShapeLanes : ProjPiLanes {  // ... a shape handle (wg1, wg2 hold w g1, w g2; d and c are columns of their own)
+    const double *d, *c;
+};
+
+// a projected handle in the lanes: its two columns are d, c, and the call's cut (pmax, or the last pi edge) comes with the view
+struct CutLane {
+    using LaneT = ProjLane;
+    template <class L>
+    static __device__ __forceinline__ ProjLane lane(const L &src, int64_t, bool, const Lane &a) {
+        return ProjLane{a, src.pmax, a.g1, a.g2, 0};  // (call-wide: a scalar register)
+    }
+};
+
+// a shape handle in the lanes: d and c are columns of the view, and n_pi comes along since the walk hands add() all of a
+// count's planes
+struct ShapeLanes {
+    using Lanes = ProjShapeLanes;
+    using LaneT = ProjLane;
+    static __device__ __forceinline__ ProjLane lane(const ProjShapeLanes &src, int64_t i, bool ok, const Lane &a) {
+        return ProjLane{a, src.pmax, ok ? src.d[i] : 0.0, ok ? src.c[i] : 0.0, src.n};  // (a padded lane: as RadiusSeam parks it)
+    }
+};
+
+// the LDS slots of the n + 1 edges of a second binning: an even number, as the thresholds take (lds_bytes and the walk's carve-up)
+constexpr int pi_slots(int n_pi) { return (n_pi + 2) & ~1; }
+
+// The planes are the call's: N per bin of the second binning that the lanes' view brings (PLANES == 0 tells the walk and the
+// host to ask), [N n][nf] per wave, plane (t, j) at (t n + j) nf; the edges are staged into LDS next to the thresholds.
+template <int N>
+struct StagedEdges {
+    static constexpr int PLANES = 0;  // the call's: planes()
+    static constexpr int PER_BIN = N;  // (planes_of)
+    template <class L> static __device__ __forceinline__ int planes(const L &src) { return N * src.n; }
+    template <class L> static __device__ __forceinline__ int extra_slots(const L &src) { return pi_slots(src.n); }
+    template <class L>
+    static __device__ __forceinline__ void stage_extra(const L &src, double *ext, int tid) {
+        for (int j = tid; j <= src.n; j += WG) ext[j] = src.edges[j];
+    }
+    // The plane of p = |c_a - c_b| over staged pi edges pe (LDS), and n_pi where the pair does not count. With j the number of
+    // edges pe[1 .. n_pi] below p -- plane 0 is [0, pe[1]], plane j is (pe[j], pe[j + 1]], pe[0] == 0 is never read -- the pair
+    // counts iff j < n_pi (p <= pe[n_pi]: over the planes, exactly the pairs Projected keeps at pmax = pe[n_pi]). That is asked
+    // first, against the lane's cut, and only the inner edges pe[1 .. n_pi - 1] are bisected for the pairs that count: behind
+    // the ballot most pairs are in range of the radius and beyond the line-of-sight cut (at one pi bin nothing is bisected at
+    // all). The loop keeps ONE shape for both -- a start past the edges instead of a branch around it: the walk is at the
+    // limit of its scalar registers, and a nested branch costs the exec masks that spill them.
+    static __device__ __forceinline__ int plane(const double *pe, int n_pi, double p, double pmax) {
+        int j = pmax < p ? n_pi : 0, hi = n_pi - 1;
+        while (j < hi) {
+            const int mid = (j + hi) >> 1;
+            if (pe[mid + 1] < p) j = mid + 1; else hi = mid;
+        }
+        return j;
+    }
+};
+
+// One end of a pair rotated to the great circle through it (the head of the file), in two parts: rotation(a, b) gives what
+// decides whether there is a rotation (den != 0); apply() does the two divisions (angle) and rotates the columns (g1, g2) of
+// that end (turn). A pair term that branches on den and one that selects afterwards are different code on purpose: each
+// keeps its own form around apply().
+struct Rotation {
+    double pa, pb, a2, b2, den;
+    __device__ __forceinline__ void angle(double &c2, double &s2) const {
+        c2 = (a2 - b2) / den;
+        s2 = ((2.0 * pa) * pb) / den;
+    }
+    static __device__ __forceinline__ void turn(double g1, double g2, double c2, double s2, double &tv, double &xv) {
+        tv = -(g1 * c2 + g2 * s2);
+        xv = g1 * s2 - g2 * c2;
+    }
+    __device__ __forceinline__ void apply(double g1, double g2, double &tv, double &xv) const {
+        double c2, s2;
+        angle(c2, s2);
+        turn(g1, g2, c2, s2, tv, xv);
+    }
+};
+// the lane's object a about the streamed object b
+template <class B>
+__device__ __forceinline__ Rotation rotation(const Lane &a, const B &b) {
+    const double pa = a.x * b.y - a.y * b.x;
+    const double dot = a.x * b.x + a.y * b.y;
+    const double pb = a.rho2 * b.z - a.z * dot;
+    const double a2 = pa * pa;
+    const double b2 = pb * pb;
+    return Rotation{pa, pb, a2, b2, a2 + b2};
+}
+// Both ends, each about the other: A for the lane's object, B for the streamed one. apply() does both pairs of divisions
+// before either end is turned, and reads b's two columns only there (the LDS read of a pair that has a rotation).
+struct Rotations {
+    Rotation A, B;
+    template <class O>
+    __device__ __forceinline__ void apply(const Lane &a, const O &b, double &tA, double &xA, double &tB, double &xB) const {
+        double cA, sA, cB, sB;
+        A.angle(cA, sA);
+        B.angle(cB, sB);
+        Rotation::turn(a.g1, a.g2, cA, sA, tA, xA);
+        Rotation::turn(b.g1, b.g2, cB, sB, tB, xB);
+    }
+};
+template <class B>
+__device__ __forceinline__ Rotations rotations(const Lane &a, const B &b) {
+    const double bx = b.x, by = b.y, bz = b.z;
+    const double pa = a.x * by - a.y * bx;
+    const double dot = a.x * bx + a.y * by;
+    const double pbA = a.rho2 * bz - a.z * dot;
+    const double pbB = (bx * bx + by * by) * a.z - bz * dot;
+    const double a2 = pa * pa;
+    const double bA2 = pbA * pbA;
+    const double bB2 = pbB * pbB;
+    return Rotations{Rotation{pa, pbA, a2, bA2, a2 + bA2}, Rotation{-pa, pbB, a2, bB2, a2 + bB2}};  // ((-pa)^2 is a2, bit for bit)
+}
+
+// ---- The policies
+struct Tangential : Policy, JobCells<CatView>, ChordSeam, PlainLane {
     using View = CatView;  // the streamed side: the lenses
     using Streamed = Obj;
     using Read = Obj;      // the hot loop reads the whole object: two ds_read_b128
     using Lanes = ShearView;  // the side in the lanes: the sources
     static constexpr int PLANES = 3;  // T, X, W
     static constexpr bool DIAGONAL = false;
-    // table: jobs [n_jobs][2]; cell = job * n_bins + k, thresholds row k
-    static __device__ Cell cell(const CatView &lens, const int32_t *__restrict__ jobs, int n_bins, int64_t cell) {
-        const int64_t job = cell / n_bins;
-        const int k = (int)(cell - job * n_bins);
-        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
-        return Cell{p * lens.nb + (lens.nb == 1 ? 0 : k), q, k, false};
-    }
-    // else the keys say nothing about each other: the whole segment
-    static __device__ bool windowed(const CatView &lens, const ShearView &src) { return lens.axis == src.axis; }
     static __device__ Obj load(const CatView &lens, int64_t i, bool have) { return load_xyzw<Obj>(lens, i, have); }
-    static __device__ double lane_u(const ShearView &, int64_t, bool) { return 0.0; }  // no such column: nothing is loaded
-    static __device__ void add(const Lane &a, const Obj &b, double *wh, int e, int nf) {
-        const double pa = a.x * b.y - a.y * b.x;
-        const double dot = a.x * b.x + a.y * b.y;
-        const double pb = a.rho2 * b.z - a.z * dot;
-        const double a2 = pa * pa;
-        const double b2 = pb * pb;
-        const double den = a2 + b2;
-        if (den != 0.0) {
-            const double c2 = (a2 - b2) / den;
-            const double s2 = ((2.0 * pa) * pb) / den;
-            const double tv = -(a.g1 * c2 + a.g2 * s2);
-            const double xv = a.g1 * s2 - a.g2 * c2;
+    static __device__ void add(const Lane &a, const Obj &b, double *wh, int e, int nf, const Staged &, double) {
+        const Rotation r = rotation(a, b);
+        if (r.den != 0.0) {
+            double tv, xv;
+            r.apply(a.g1, a.g2, tv, xv);
             atomicAdd(&wh[e], b.w * tv);
             atomicAdd(&wh[nf + e], b.w * xv);
         }
@@ -218,10 +395,8 @@ struct Tangential : ChordBinned {
     }
 };
 
-struct ShearShear : ChordBinned {
+struct ShearShear : Policy, ChordSeam, StreamedShear, PlainLane {
     using View = ShearView;  // the streamed side: the handle itself
-    using Streamed = Obj6;
-    using Read = const Obj6 &;  // the hot loop reads x, y, z (ds_read_b128 + ds_read_b64), the other 24 bytes behind the ballot
     using Lanes = ShearView;
     static constexpr int PLANES = 4;  // P, M, C, W
     static constexpr bool DIAGONAL = true;
@@ -233,33 +408,11 @@ struct ShearShear : ChordBinned {
         return Cell{p * nb + k, q * nb + k, k, p == q};
     }
     static __device__ bool windowed(const ShearView &, const ShearView &) { return true; }  // segments of one handle: one sort axis
-    static __device__ Obj6 load(const ShearView &src, int64_t i, bool have) {
-        Obj6 o = load_xyzw<Obj6>(src, i, have);
-        o.g1 = have ? src.wg1[i] : 0.0; o.g2 = have ? src.wg2[i] : 0.0;
-        return o;
-    }
-    static __device__ double lane_u(const ShearView &, int64_t, bool) { return 0.0; }
-    static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf) {
-        const double bx = b.x, by = b.y, bz = b.z;
-        const double pa = a.x * by - a.y * bx;
-        const double dot = a.x * bx + a.y * by;
-        const double pbA = a.rho2 * bz - a.z * dot;
-        const double pbB = (bx * bx + by * by) * a.z - bz * dot;
-        const double a2 = pa * pa;
-        const double bA2 = pbA * pbA;
-        const double bB2 = pbB * pbB;
-        const double denA = a2 + bA2;
-        const double denB = a2 + bB2;
-        if (denA != 0.0 && denB != 0.0) {
-            const double cA = (a2 - bA2) / denA;
-            const double sA = ((2.0 * pa) * pbA) / denA;
-            const double cB = (a2 - bB2) / denB;
-            const double sB = ((-2.0 * pa) * pbB) / denB;
-            const double bg1 = b.g1, bg2 = b.g2;
-            const double tA = -(a.g1 * cA + a.g2 * sA);
-            const double xA = a.g1 * sA - a.g2 * cA;
-            const double tB = -(bg1 * cB + bg2 * sB);
-            const double xB = bg1 * sB - bg2 * cB;
+    static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf, const Staged &, double) {
+        const Rotations r = rotations(a, b);
+        if (r.A.den != 0.0 && r.B.den != 0.0) {
+            double tA, xA, tB, xB;
+            r.apply(a, b, tA, xA, tB, xB);
             const double tt = tA * tB;
             const double xx2 = xA * xB;
             atomicAdd(&wh[e], tt + xx2);
@@ -270,52 +423,32 @@ struct ShearShear : ChordBinned {
     }
 };
 
-// ShearShear between any two segments of one or two handles: the pair term and the objects are ShearShear's; the cell comes
-// from a table the host resolved, the key window is Tangential's rule.
-struct ShearPair : ShearShear {
-    // table: [n_cells][4] = (streamed segment of a, lane segment of b, thresholds row, diagonal)
-    static __device__ Cell cell(const ShearView &, const int32_t *__restrict__ cells, int, int64_t cell) {
-        const int32_t *c = cells + 4 * cell;
-        return Cell{c[0], c[1], c[2], c[3] != 0};
-    }
-    static __device__ bool windowed(const ShearView &a, const ShearView &b) { return a.axis == b.axis; }
+// ShearShear between any two segments of one or two handles: the cells come from the host's table, with its window rule
+struct ShearPair : ShearShear, CellTable {
+    using CellTable::cell;
+    using CellTable::windowed;
 };
 
-// Tangential around the lenses of a lens handle (its columns wg1, wg2 hold f, c as they came), the sources with their column u.
-struct DeltaSigma : ChordBinned {
-    using View = LensView;  // the streamed side: the lens handle, a ShearView with its bin count
-    using Streamed = Obj6;  // (x, y, z, w, f, c)
-    using Read = const Obj6 &;  // the hot loop reads x, y, z; w, f, c behind the ballot (ShearShear's reads)
+// Tangential's rotation scaled by the pair's s = f (1 - c u), around the lenses of a lens handle (its two columns hold f, c
+// as they came), the sources with their column u: what DeltaSigma and DeltaSigmaRadial share
+struct DeltaSigmaTerm : Policy, JobCells<LensView> {
     using Lanes = SourceView;
+    using LaneT = SourceLane;
     static constexpr int PLANES = 3;  // T, X, W
     static constexpr bool DIAGONAL = false;
-    // table: jobs [n_jobs][2]; cell = job * n_bins + k, thresholds row k (Tangential's)
-    static __device__ Cell cell(const LensView &lens, const int32_t *__restrict__ jobs, int n_bins, int64_t cell) {
-        const int64_t job = cell / n_bins;
-        const int k = (int)(cell - job * n_bins);
-        const int64_t p = jobs[2 * job], q = jobs[2 * job + 1];
-        return Cell{p * lens.nb + (lens.nb == 1 ? 0 : k), q, k, false};
+    static __device__ __forceinline__ SourceLane lane(const SourceView &src, int64_t i, bool ok, const Lane &a) {
+        return SourceLane{a, ok ? src.u[i] : 0.0};
     }
-    static __device__ bool windowed(const LensView &lens, const SourceView &src) { return lens.axis == src.axis; }
-    static __device__ Obj6 load(const LensView &lens, int64_t i, bool have) { return ShearShear::load(lens, i, have); }
-    static __device__ double lane_u(const SourceView &src, int64_t i, bool ok) { return ok ? src.u[i] : 0.0; }
-    static __device__ void add(const Lane &a, const Obj6 &b, double *wh, int e, int nf) {
+    template <class B>  // (an Obj6 or an Obj8: x, y, z, w, g1 = f, g2 = c)
+    static __device__ void add(const SourceLane &a, const B &b, double *wh, int e, int nf, const Staged &, double) {
         const double eff = 1.0 - b.g2 * a.u;  // 1 - c_l u_s: a product and a difference, each rounded (-ffp-contract=off)
         if (eff > 0.0) {  // else the source is not behind its lens: nothing, not to W either
             const double s = b.g1 * eff;
             const double ws = b.w * s;
-            const double bx = b.x, by = b.y;
-            const double pa = a.x * by - a.y * bx;
-            const double dot = a.x * bx + a.y * by;
-            const double pb = a.rho2 * b.z - a.z * dot;
-            const double a2 = pa * pa;
-            const double b2 = pb * pb;
-            const double den = a2 + b2;
-            if (den != 0.0) {
-                const double c2 = (a2 - b2) / den;
-                const double s2 = ((2.0 * pa) * pb) / den;
-                const double tv = -(a.g1 * c2 + a.g2 * s2);
-                const double xv = a.g1 * s2 - a.g2 * c2;
+            const Rotation r = rotation(a, b);
+            if (r.den != 0.0) {
+                double tv, xv;
+                r.apply(a.g1, a.g2, tv, xv);
                 atomicAdd(&wh[e], ws * tv);
                 atomicAdd(&wh[nf + e], ws * xv);
             }
@@ -324,22 +457,19 @@ struct DeltaSigma : ChordBinned {
     }
 };
 
-// DeltaSigma binned in each lens's own radius (k_count_dsigma_radial): the row holds squared radii r2,
-// the lens streams its m (squared transverse distance per radian) next to x, y, z, and a pair is binned by
-//   R2 = m_l th2,   th2 = s2 q(s2) = (2 asin(sqrt(s2) / 2))^2,   q = 1 + s2 / 12 + s2^2 / 90 + s2^3 / 560 + s2^4 / 3150 + s2^5 / 16632
-// (Horner, every operation rounded on its own; the call caps s2 at 0.01, where the series is good to 2 ulp).
-// The ballot holds fl(m_l s2) against the last edge. That is an EXACT superset of the pairs in range, with no guard term:
-// every coefficient and s2 are >= 0, so each Horner step is >= its constant and the last one gives q >= 1 after rounding;
-// rounding is monotone, so th2 = fl(s2 q) >= fl(s2 * 1) = s2 and R2 = fl(m th2) >= fl(m s2) (m > 0). A pair with
-// R2 <= r2max therefore has fl(m s2) <= r2max. The converse fails (R2 may exceed the last edge behind the ballot): the
-// bisection then runs off the row and the pair is dropped (!CAPPED).
-struct DeltaSigmaRadial : DeltaSigma {
+struct DeltaSigma : DeltaSigmaTerm, ChordSeam, StreamedShear {
+    using View = LensView;  // the streamed side: the lens handle, a ShearView with its bin count
+};
+
+// DeltaSigma binned in each lens's own radius: the row holds squared radii r2, the lens streams its m
+// (squared transverse distance per radian) next to x, y, z, and a pair is binned by R2 = m_l th2(s2). The ballot holds
+// fl(m_l s2) against the last edge: RadiusSeam's proof of the exact superset with the scale m_l > 0 in the place of DD.
+struct DeltaSigmaRadial : DeltaSigmaTerm {
     using View = RadialView;
     using Streamed = Obj8;      // (x, y, z, m | w, f, c, pad)
     using Read = const Obj8 &;  // the hot loop reads x, y, z, m (two ds_read_b128); w, f, c behind the ballot
     static constexpr bool CAPPED = false;
-    // Beyond the window (!have) the object is padding with m = 0, which WOULD pass the outer test: nobody reads it, the loop
-    // over a stage stops at the stage's count n.
+    // (a padded streamed object has m = 0 and would pass the outer test: nobody reads it, as RadiusSeam says of d)
     static __device__ Obj8 load(const RadialView &lens, int64_t i, bool have) {
         Obj8 o = load_xyzw<Obj8>(lens, i, have);
         o.m = have ? lens.m[i] : 0.0;
@@ -349,117 +479,38 @@ struct DeltaSigmaRadial : DeltaSigma {
     }
     static __device__ __forceinline__ double outer(const Lane &, const Obj8 &b, double s) { return b.m * s; }
     static __device__ __forceinline__ double binned(const Lane &, const Obj8 &b, double s) { return b.m * squared_angle(s); }
-    static __device__ void add(const Lane &a, const Obj8 &b, double *wh, int e, int nf) {
-        DeltaSigma::add(a, Obj6{b.x, b.y, b.z, b.w, b.g1, b.g2}, wh, e, nf);  // the pair term is DeltaSigma's
-    }
 };
 
-// The lanes of the projected count: a projected handle (wg1, wg2 hold d, c as they came) and the call's pmax, which reaches
-// the pair term as the lane's u -- the walk and the other policies know nothing of it.
-struct ProjLanes : ShearView {
-    double pmax;
+// What the five projected counts share: the host's cell table over two projected or shape handles,
+// whose objects carry d and c (line-of-sight coordinate), and evaluated <= candidates also on a diagonal cell smaller than
+// its window. Where a term reads the two only as d_a + d_b, |c_a - c_b| and w_a w_b it does not change when a and b swap.
+struct ProjectedCells : Policy, CellTable {
+    static constexpr bool KEPT_WORK = true;
 };
 
-// Pair counts binned in each PAIR's own radius inside a line-of-sight cut (k_count_projected): cells,
-// window rule and diagonal cells are ShearPair's over two projected handles; the row holds squared radii r2, every object
-// carries d (transverse distance per radian, > 0) and c (line-of-sight coordinate), and a pair is binned by
-//   R2 = DD th2(s2),   DD = D D,   D = 0.5 (d_a + d_b)
-// and adds w_a w_b iff |c_a - c_b| <= pmax. d_a + d_b, fabs of the difference and w_a w_b do not change when a and b swap, so
-// a diagonal cell walks the larger indices only.
-// The ballot holds fl(DD s2) against the last edge: DeltaSigmaRadial's proof with DD in the place of m. Every coefficient of q
-// and s2 are >= 0, so each Horner step is >= its constant and q >= 1 after rounding; rounding is monotone, so
-// th2 = fl(s2 q) >= fl(s2 * 1) = s2 and R2 = fl(DD th2) >= fl(DD s2) (DD >= 0). A pair with R2 <= r2max therefore has
-// fl(DD s2) <= r2max: an EXACT superset, with no guard term. The converse fails: a pair behind the ballot with R2 beyond the last
-// edge runs off the row and is dropped (!CAPPED).
-// A padded lane is parked at PAD_COORD with d_a = c_a = 0 and is excluded by `ok` before anything is binned. A padded streamed
-// object (beyond the window, !have) has d = 0, which WOULD pass the outer test: nobody reads it, the loop over a stage stops at
-// the stage's count n.
-struct Projected : ShearPair {
-    using Streamed = ObjP;      // (x, y, z, d | w, c)
-    using Read = const ObjP &;  // the hot loop reads x, y, z, d (two ds_read_b128); w, c behind the ballot
+// Pair counts inside a line-of-sight cut: a pair adds w_a w_b iff |c_a - c_b| <= pmax.
+struct Projected : ProjectedCells, RadiusSeam, StreamedProj, CutLane {
     using Lanes = ProjLanes;
     static constexpr int PLANES = 1;  // W
-    static constexpr bool CAPPED = false;
-    static constexpr bool KEPT_WORK = true;  // evaluated <= candidates also on a diagonal cell smaller than its window
-    static __device__ ObjP load(const ShearView &v, int64_t i, bool have) {
-        ObjP o;
-        o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
-        o.d = have ? v.wg1[i] : 0.0;
-        o.w = (have && v.w) ? v.w[i] : 1.0;
-        o.c = have ? v.wg2[i] : 0.0;
-        return o;
-    }
-    static __device__ double lane_u(const ProjLanes &src, int64_t, bool) { return src.pmax; }  // call-wide: a scalar register
-    static __device__ __forceinline__ double pair_dd(const Lane &a, const ObjP &b) {
-        const double D = 0.5 * (a.g1 + b.d);
-        return D * D;
-    }
-    static __device__ __forceinline__ double outer(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * s; }
-    static __device__ __forceinline__ double binned(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * squared_angle(s); }
-    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int) {
-        if (fabs(a.g2 - b.c) <= a.u) atomicAdd(&wh[e], a.w * b.w);
+    static constexpr bool DIAGONAL = true;
+    static __device__ void add(const ProjLane &a, const ObjP &b, double *wh, int e, int, const Staged &, double) {
+        if (fabs(a.c - b.c) <= a.cut) atomicAdd(&wh[e], a.w * b.w);
     }
 };
 
-// The lanes of the pi-binned projected count: a projected handle and the call's pi edges pe[n_pi + 1] (device memory; the
-// workgroup stages them into LDS once) in the place of pmax; the last of them, pe[n_pi], comes by value besides and
-// reaches the pair term as the lane's u, as Projected's pmax does.
-struct ProjPiLanes : ShearView {
-    const double *pe;
-    int n_pi;
-    double pmax;
-};
-
-// the LDS slots of the pi edges of n_pi planes: an even number, as the thresholds take (lds_bytes and the walk's carve-up)
-constexpr int pi_slots(int n_pi) { return (n_pi + 2) & ~1; }
-
-// Projected binned in the line-of-sight separation besides (k_count_projected_pi): object, lane, outer,
-// binned, window and diagonal rule are Projected's; the planes are the call's n_pi (PLANES == 0 tells the walk and the host
-// to ask the lanes' view), [n_pi][nf] per wave. With p = |c_a - c_b| and j the number of edges pe[1 .. n_pi] below p -- plane 0
-// is [0, pe[1]], plane j is (pe[j], pe[j + 1]], pe[0] == 0 is never read -- the pair adds w_a w_b to plane j iff j < n_pi
-// (p <= pe[n_pi]: over the planes, exactly the pairs Projected keeps at pmax = pe[n_pi]). The pair term asks that first,
-// against the lane's u as Projected does, and bisects only the inner edges pe[1 .. n_pi - 1] for the pairs that count:
-// behind the ballot most pairs are in range of the radius and beyond the line-of-sight cut (at one pi bin nothing is
-// bisected at all). The loop keeps ONE shape for both -- a start past the edges instead of a branch around it: the walk is
-// at the limit of its scalar registers, and a nested branch costs the exec masks that spill them. p is bit-symmetric, so a
-// diagonal cell walks the larger indices only, as Projected's.
-struct ProjectedPi : Projected {
+// Projected binned in the line-of-sight separation besides: the pair adds w_a w_b to the plane of
+// p = |c_a - c_b| over the call's pi edges (StagedEdges::plane), the cut being the last of them.
+struct ProjectedPi : ProjectedCells, RadiusSeam, StreamedProj, CutLane, StagedEdges<1> {
     using Lanes = ProjPiLanes;
-    static constexpr int PLANES = 0;  // the call's: planes()
-    static __device__ __forceinline__ int planes(const ProjPiLanes &src) { return src.n_pi; }
-    static __device__ __forceinline__ int extra_slots(const ProjPiLanes &src) { return pi_slots(src.n_pi); }
-    static __device__ __forceinline__ void stage_extra(const ProjPiLanes &src, double *ext, int tid) {
-        for (int j = tid; j <= src.n_pi; j += WG) ext[j] = src.pe[j];
-    }
-    static __device__ double lane_u(const ProjPiLanes &src, int64_t, bool) { return src.pmax; }  // call-wide: a scalar register
-    // the plane of p over the staged edges pe (LDS); n_pi: the pair does not count. pmax: pe[n_pi], the lane's u
-    static __device__ __forceinline__ int plane(const double *pe, int n_pi, double p, double pmax) {
-        // the inner edges pe[1 .. n_pi - 1] below p (they ascend), by bisection; a pair beyond pe[n_pi] -- the lane's u, as
-        // Projected's pmax; most pairs behind the ballot -- starts past them and bisects nothing
-        int j = pmax < p ? n_pi : 0, hi = n_pi - 1;
-        while (j < hi) {
-            const int mid = (j + hi) >> 1;
-            if (pe[mid + 1] < p) j = mid + 1; else hi = mid;
-        }
-        return j;
-    }
-    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int n_pi) {
-        const int j = plane(pe, n_pi, fabs(a.g2 - b.c), a.u);
-        if (j < n_pi) atomicAdd(&wh[j * nf + e], a.w * b.w);
+    static constexpr bool DIAGONAL = true;
+    static __device__ void add(const ProjLane &a, const ObjP &b, double *wh, int e, int nf, const Staged &st, double) {
+        const int j = plane(st.ext, st.planes, fabs(a.c - b.c), a.cut);
+        if (j < st.planes) atomicAdd(&wh[j * nf + e], a.w * b.w);
     }
 };
 
-// The lanes of the redshift-space count: a projected handle and the call's squared mu edges m2[n_mu + 1] (device memory; the
-// workgroup stages them into LDS once, where ProjPiLanes has pe) with the first step of their bisection, the largest power of
-// two <= n_mu - 1 (0 at one plane: nothing is bisected). No call-wide cut comes with them: the lane's u is unused.
-struct SmuLanes : ShearView {
-    const double *m2;
-    int n_mu, step;
-};
-
-// Pair counts binned in the redshift-space separation s and in mu = pi / s (k_count_smu): object, lane,
-// cells, window, diagonal rule and KEPT_WORK are Projected's; planes, extra_slots and stage_extra are ProjectedPi's with m2
-// in the place of pe. With R2 = DD th2(s2c) of Projected (s2c: the squared chord),
+// Pair counts binned in the redshift-space separation s and in mu = pi / s, a seam of its own. With
+// R2 = DD th2(s2c) of RadiusSeam (s2c: the squared chord),
 //   p = fabs(c_a - c_b),   P2 = p p,   S2 = R2 + P2            (every operation rounded on its own)
 // the row holds squared s edges and is bisected by S2; the plane j is the number of INNER edges k = 1 .. n_mu - 1 with
 // fl(m2[k] S2) < P2 -- plane 0 is mu^2 in [0, m2[1]], plane j is (m2[j], m2[j + 1]]. m2 ascends and rounding is monotone, so
@@ -468,44 +519,44 @@ struct SmuLanes : ShearView {
 //
 // The ballot holds so = fl(fl(DD s2c) + P2) against the last squared s edge, with c read in the hot loop (one more 16-byte LDS
 // read, three more FP64 operations per trip). Two candidates, both EXACT supersets of the pairs in range, no guard term:
-//   (A) Projected::outer, x = fl(DD s2c). Projected's proof gives x <= R2 (q >= 1 after rounding, rounding monotone, DD >= 0);
+//   (A) RadiusSeam::outer, x = fl(DD s2c). Its proof gives x <= R2 (q >= 1 after rounding, rounding monotone, DD >= 0);
 //       P2 >= 0 and monotone rounding give R2 = fl(R2 + 0) <= fl(R2 + P2) = S2. So S2 <= last edge implies x <= last edge.
 //   (B) fl(x + P2), the same x and the SAME separately rounded P2 as in the pair term: x <= R2, so by monotone rounding of
 //       the one sum fl(x + P2) <= fl(R2 + P2) = S2. So S2 <= last edge implies so <= last edge.
 // An FMA fma(p, p, x) is NOT a superset: it adds the unrounded p^2, which may exceed fl(p^2) = P2, and at x = R2 the sum can
 // round one ulp above S2 -- a pair with S2 exactly on the last edge would be lost. It is left out (and the build contracts
 // nothing). (B) keeps out of the branch the pairs that are close on the sky and far along the line of sight, which are the
-// bulk of what passes (A); DESIGN.md section 23 has both measured. The converse fails as for Projected: a pair behind the
+// bulk of what passes (A); DESIGN.md section 23 has both measured. The converse fails as for RadiusSeam: a pair behind the
 // ballot with S2 beyond the last edge runs off the row and is dropped (!CAPPED). Padded lanes and padded streamed objects:
-// as Projected's (c = 0 there, so P2 is finite; `ok` and the stage's count n exclude them).
-struct RedshiftSpace : Projected {
+// as RadiusSeam's (c = 0 there, so P2 is finite; `ok` and the stage's count n exclude them).
+struct RedshiftSpace : ProjectedCells, StreamedProj, StagedEdges<1> {
     using Lanes = SmuLanes;
-    static constexpr int PLANES = 0;         // the call's: planes()
-    static constexpr bool ADD_BINNED = true;  // the walk hands what binned() gave (S2) on to add()
-    static __device__ __forceinline__ int planes(const SmuLanes &src) { return src.n_mu; }
-    static __device__ __forceinline__ int extra_slots(const SmuLanes &src) { return pi_slots(src.n_mu); }
-    static __device__ __forceinline__ void stage_extra(const SmuLanes &src, double *ext, int tid) {
-        for (int j = tid; j <= src.n_mu; j += WG) ext[j] = src.m2[j];
-    }
+    using LaneT = ProjLane;
+    static constexpr bool CAPPED = false;
+    static constexpr bool DIAGONAL = true;
     static __device__ __forceinline__ int first_step(const SmuLanes &src) { return src.step; }
-    static __device__ double lane_u(const SmuLanes &, int64_t, bool) { return 0.0; }
-    static __device__ __forceinline__ double pair_p2(const Lane &a, const ObjP &b) {
-        const double p = fabs(a.g2 - b.c);
+    static __device__ __forceinline__ ProjLane lane(const SmuLanes &, int64_t, bool, const Lane &a) {
+        return ProjLane{a, 0.0, a.g1, a.g2, 0};
+    }
+    static __device__ __forceinline__ double pair_p2(const ProjLane &a, const ObjP &b) {
+        const double p = fabs(a.c - b.c);
         return p * p;
     }
-    static __device__ __forceinline__ double outer(const Lane &a, const ObjP &b, double s) { return pair_dd(a, b) * s + pair_p2(a, b); }
-    static __device__ __forceinline__ double binned(const Lane &a, const ObjP &b, double s) {
+    static __device__ __forceinline__ double outer(const ProjLane &a, const ObjP &b, double s) { return pair_dd(a, b) * s + pair_p2(a, b); }
+    static __device__ __forceinline__ double binned(const ProjLane &a, const ObjP &b, double s) {
         return pair_dd(a, b) * squared_angle(s) + pair_p2(a, b);
     }
-    // m2: the staged edges in LDS; top: first_step(); S2: what binned() returned for this pair (squared_angle is not evaluated again)
-    static __device__ void add(const Lane &a, const ObjP &b, double *wh, int e, int nf, const double *m2, int n_mu, int top, double S2) {
+    // st.ext: the staged edges m2 in LDS; S2: what binned() returned for this pair (squared_angle is not evaluated again)
+    static __device__ void add(const ProjLane &a, const ObjP &b, double *wh, int e, int nf, const Staged &st, double S2) {
+        const double *const m2 = st.ext;
+        const int n_mu = st.planes;
         const double P2 = pair_p2(a, b);
         // j: the inner edges m2[1 .. n_mu - 1] with fl(m2[k] S2) < P2, a prefix of them. Bisected by descending powers of two,
         // the same trips for every lane (a scalar loop: no exec mask is saved for it, and the walk is at the limit of its
         // scalar registers): j + step edges hold iff edge k = j + step is an inner one and holds. At least one trip, so
         // that no entry test is kept in scalar registers either; at one plane top == 0, k == 0 is no inner edge and
         // nothing is read.
-        int j = 0, step = top;
+        int j = 0, step = st.top;
         do {
             const int k = j + step;
             if ((unsigned)(k - 1) < (unsigned)(n_mu - 1) && m2[k] * S2 < P2) j = k;
@@ -515,94 +566,42 @@ struct RedshiftSpace : Projected {
     }
 };
 
-// The lanes of the projected position-shape count: a shape handle (wg1, wg2 hold w g1, w g2; d and c are columns of their own)
-// with the call's pi edges, as ProjPiLanes has them.
-struct ProjShapeLanes : ProjPiLanes {
-    const double *d, *c;
-};
-
-// What a lane of that count keeps besides: its d and c, which a projected handle has where the shape handle has its shear,
-// and the call's n_pi (call-wide: a scalar register, as the lane's u is), since the walk hands add() all 3 n_pi planes.
-struct ShapeLane : Lane {
-    double d, c;
-    int n_pi;
-};
-
-// The tangential and cross ellipticity of shapes about the objects of a projected handle, binned in each pair's own radius
-// and in the line-of-sight separation (k_count_projected_shear). The streamed side is the projected
-// handle -- object, load, cells and window rule are ProjectedPi's, the hot loop up to the ballot too: it holds fl(DD s2)
-// against the last edge, and Projected's proof of the exact superset applies unchanged, with the lane's d in the place of
-// its g1. Two handles of different kinds never pair a segment with itself: no diagonal cells. Behind the ballot R2 is
-// bisected over the row, then p = |c_a - c_b| over the staged edges by ProjectedPi::plane, and only a pair that
-// counts (j < n_pi) gets Tangential's rotation, term for term: T is the tangential ellipticity of the shape a about the
-// streamed object b. The planes are [3][n_pi] per wave, T, X, W: plane (t, j) sits at (t n_pi + j) nf.
-struct ProjectedShear : ProjectedPi {
-    using Lanes = ProjShapeLanes;
-    using LaneT = ShapeLane;
+// The tangential and cross ellipticity of shapes about the objects of a projected handle, binned as ProjectedPi bins the pair
+// (DESIGN.md section 24). The streamed side is the projected handle; two handles of different kinds never pair a segment
+// with itself: no diagonal cells. Only a pair that counts (j < n_pi) gets Tangential's rotation, term for term: T is the
+// tangential ellipticity of the shape a about the streamed object b. The planes are T, X, W per pi bin.
+struct ProjectedShear : ProjectedCells, RadiusSeam, StreamedProj, ShapeLanes, StagedEdges<3> {
     static constexpr bool DIAGONAL = false;
-    static constexpr int PER_BIN = 3;  // T, X, W
-    static __device__ __forceinline__ int planes(const ProjShapeLanes &src) { return 3 * src.n_pi; }
-    static __device__ __forceinline__ ShapeLane lane(const ProjShapeLanes &src, int64_t i, bool ok, const Lane &a) {
-        return ShapeLane{a, ok ? src.d[i] : 0.0, ok ? src.c[i] : 0.0, src.n_pi};  // (a padded lane: as Projected parks it)
-    }
-    static __device__ __forceinline__ double pair_dd(const ShapeLane &a, const ObjP &b) {
-        const double D = 0.5 * (a.d + b.d);
-        return D * D;
-    }
-    static __device__ __forceinline__ double outer(const ShapeLane &a, const ObjP &b, double s) { return pair_dd(a, b) * s; }
-    static __device__ __forceinline__ double binned(const ShapeLane &a, const ObjP &b, double s) { return pair_dd(a, b) * squared_angle(s); }
-    // pe: the staged edges in LDS (the walk's count of planes, 3 n_pi, is not used)
-    static __device__ void add(const ShapeLane &a, const ObjP &b, double *wh, int e, int nf, const double *pe, int) {
+    // st.ext: the staged edges in LDS (the walk's count of planes, 3 n_pi, is not used)
+    static __device__ void add(const ProjLane &a, const ObjP &b, double *wh, int e, int nf, const Staged &st, double) {
         const int n_pi = a.n_pi;
-        const int j = plane(pe, n_pi, fabs(a.c - b.c), a.u);
+        const int j = plane(st.ext, n_pi, fabs(a.c - b.c), a.cut);
         if (j < n_pi) {
             double *const bin = wh + j * nf + e;
             const int plane = n_pi * nf;
-            const double pa = a.x * b.y - a.y * b.x;
-            const double dot = a.x * b.x + a.y * b.y;
-            const double pb = a.rho2 * b.z - a.z * dot;
-            const double a2 = pa * pa;
-            const double b2 = pb * pb;
-            const double den = a2 + b2;
+            const Rotation r = rotation(a, b);
             // den == 0 (the shape on a pole of the frame) adds to W only: as a select, T and X get a zero that changes no sum,
-            // since a third nested branch costs the exec masks that spill the walk's scalar registers (ProjectedPi::add)
-            const bool rotated = den != 0.0;
-            const double c2 = (a2 - b2) / den;
-            const double s2 = ((2.0 * pa) * pb) / den;
-            const double tv = rotated ? -(a.g1 * c2 + a.g2 * s2) : 0.0;
-            const double xv = rotated ? a.g1 * s2 - a.g2 * c2 : 0.0;
-            atomicAdd(bin, b.w * tv);
-            atomicAdd(bin + plane, b.w * xv);
+            // since a third nested branch costs the exec masks that spill the walk's scalar registers (StagedEdges::plane)
+            const bool rotated = r.den != 0.0;
+            double tv, xv;
+            r.apply(a.g1, a.g2, tv, xv);
+            atomicAdd(bin, b.w * (rotated ? tv : 0.0));
+            atomicAdd(bin + plane, b.w * (rotated ? xv : 0.0));
             atomicAdd(bin + 2 * plane, b.w * a.w);
         }
     }
 };
 
-// One streamed shape of the projected shape-shape count: (x, y, z, d | w, c, wg1, wg2). The hot loop reads the first 32 bytes
-// (two 16-byte broadcast reads, as Projected reads its ObjP), the second half only behind the ballot.
-struct alignas(16) ObjS {
-    double x, y, z, d, w, c, g1, g2;
-};
-
-// The products of the rotated ellipticities of two shape samples, binned in each pair's own radius and in the line-of-sight
-// separation (k_count_projected_shapes). Both sides are shape handles: the lane is ProjectedShear's
-// ShapeLane, the streamed side a ShapeView, which carries d and c next to the ShearView columns as ProjShapeLanes carries them
-// for the lanes. Cells, window rule and the diagonal cells are Projected's -- one segment of one handle against itself walks
-// the larger indices only, which rests on every term below being bit-symmetric under a <-> b: products and sums of two
-// operands commute, pa changes its sign with the swap and enters as pa pa and as (2 pa) pbA against (-2 pa) pbB, dot is
-// symmetric, and pbA, pbB swap their roles. The hot loop up to the ballot is ProjectedShear's: it holds fl(DD s2) against the
-// last edge, DD from the lane's d and the streamed d, and Projected's proof of the exact superset applies as it stands. Behind
-// the ballot R2 is bisected over the row, the walk drops the lower half of a diagonal cell, p = |c_a - c_b| is bisected by
-// ProjectedPi::plane, and only a pair that counts (j < n_pi) gets ShearShear's two rotations, term for term up to
-// tA, xA, tB, xB. The planes are [4][n_pi] per wave, PP, XX, PX, W: plane (t, j) sits at (t n_pi + j) nf.
-struct ProjectedShapes : ProjectedShear {
+// The products of the rotated ellipticities of two shape samples, binned as ProjectedPi bins the pair (DESIGN.md section
+// 25). Both sides are shape handles: the streamed side is a ShapeView, which carries d and c next to the ShearView columns as
+// ProjShapeLanes carries them for the lanes; one segment of one handle against itself is a diagonal cell. Only a pair that
+// counts (j < n_pi) gets ShearShear's two rotations, term for term up to tA, xA, tB, xB. The planes are PP, XX, PX, W per pi bin.
+struct ProjectedShapes : ProjectedCells, RadiusSeam, ShapeLanes, StagedEdges<4> {
     using View = ShapeView;     // the streamed side: a shape handle with its d, c
     using Streamed = ObjS;      // (x, y, z, d | w, c, wg1, wg2)
     using Read = const ObjS &;  // the hot loop reads x, y, z, d (two ds_read_b128); w, c, wg1, wg2 behind the ballot
     static constexpr bool DIAGONAL = true;
-    static constexpr int PER_BIN = 4;  // PP, XX, PX, W
-    static __device__ __forceinline__ int planes(const ProjShapeLanes &src) { return 4 * src.n_pi; }
-    // (a padded streamed object has d = 0 and would pass the outer test: nobody reads it, as Projected's)
+    // (a padded streamed object has d = 0 and would pass the outer test: nobody reads it, as RadiusSeam says)
     static __device__ ObjS load(const ShapeView &v, int64_t i, bool have) {
         ObjS o;
         o.x = have ? v.x[i] : 0.0; o.y = have ? v.y[i] : 0.0; o.z = have ? v.z[i] : 0.0;
@@ -612,42 +611,19 @@ struct ProjectedShapes : ProjectedShear {
         o.g1 = have ? v.wg1[i] : 0.0; o.g2 = have ? v.wg2[i] : 0.0;
         return o;
     }
-    static __device__ __forceinline__ double pair_dd(const ShapeLane &a, const ObjS &b) {
-        const double D = 0.5 * (a.d + b.d);
-        return D * D;
-    }
-    static __device__ __forceinline__ double outer(const ShapeLane &a, const ObjS &b, double s) { return pair_dd(a, b) * s; }
-    static __device__ __forceinline__ double binned(const ShapeLane &a, const ObjS &b, double s) { return pair_dd(a, b) * squared_angle(s); }
-    // pe: the staged edges in LDS (the walk's count of planes, 4 n_pi, is not used)
-    static __device__ void add(const ShapeLane &a, const ObjS &b, double *wh, int e, int nf, const double *pe, int) {
+    // st.ext: the staged edges in LDS (the walk's count of planes, 4 n_pi, is not used)
+    static __device__ void add(const ProjLane &a, const ObjS &b, double *wh, int e, int nf, const Staged &st, double) {
         const int n_pi = a.n_pi;
-        const int j = plane(pe, n_pi, fabs(a.c - b.c), a.u);
+        const int j = plane(st.ext, n_pi, fabs(a.c - b.c), a.cut);
         if (j < n_pi) {
             double *const bin = wh + j * nf + e;
             const int plane = n_pi * nf;
-            const double bx = b.x, by = b.y, bz = b.z;
-            const double pa = a.x * by - a.y * bx;
-            const double dot = a.x * bx + a.y * by;
-            const double pbA = a.rho2 * bz - a.z * dot;
-            const double pbB = (bx * bx + by * by) * a.z - bz * dot;
-            const double a2 = pa * pa;
-            const double bA2 = pbA * pbA;
-            const double bB2 = pbB * pbB;
-            const double denA = a2 + bA2;
-            const double denB = a2 + bB2;
-            // denA == 0 or denB == 0 (a shape on a pole of the frame) adds to W only: as a select, the three sums get a zero
-            // that changes none of them, since another nested branch costs the exec masks that spill the walk's scalar
-            // registers (ProjectedShear::add)
-            const bool rotated = denA != 0.0 && denB != 0.0;
-            const double cA = (a2 - bA2) / denA;
-            const double sA = ((2.0 * pa) * pbA) / denA;
-            const double cB = (a2 - bB2) / denB;
-            const double sB = ((-2.0 * pa) * pbB) / denB;
-            const double bg1 = b.g1, bg2 = b.g2;
-            const double tA = -(a.g1 * cA + a.g2 * sA);
-            const double xA = a.g1 * sA - a.g2 * cA;
-            const double tB = -(bg1 * cB + bg2 * sB);
-            const double xB = bg1 * sB - bg2 * cB;
+            const Rotations r = rotations(a, b);
+            // a den == 0 (a shape on a pole of the frame) adds to W only: as a select, the three sums get a zero that changes
+            // none of them, since another nested branch costs the exec masks that spill the walk's scalar registers
+            const bool rotated = r.A.den != 0.0 && r.B.den != 0.0;
+            double tA, xA, tB, xB;
+            r.apply(a, b, tA, xA, tB, xB);
             atomicAdd(bin, rotated ? tA * tB : 0.0);
             atomicAdd(bin + plane, rotated ? xA * xB : 0.0);
             atomicAdd(bin + 2 * plane, rotated ? tA * xB + xA * tB : 0.0);
@@ -673,8 +649,13 @@ __device__ __forceinline__ unsigned long long kept_work(int64_t ta, int64_t t_la
 // dynamic LDS of a cell: two stages + thresholds + one histogram [PLANES][E-1] per wave (the carve-up at the head of shear_walk);
 // a policy with the call's planes (PLANES == 0) has PER_BIN n_pi of them and its pi edges between the thresholds and the histograms
 template <class P>
+constexpr size_t planes_of(int n_pi) {
+    if constexpr (P::PLANES != 0) return P::PLANES;
+    else return (size_t)P::PER_BIN * n_pi;
+}
+template <class P>
 constexpr size_t lds_bytes(int n_edges, int n_pi = 0) {
-    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)P::PER_BIN * n_pi, extra = P::PLANES ? 0 : (size_t)pi_slots(n_pi);
+    const size_t planes = planes_of<P>(n_pi), extra = P::PLANES ? 0 : (size_t)pi_slots(n_pi);
     return 2 * STAGE * sizeof(typename P::Streamed) + ((size_t)((n_edges + 1) & ~1) + extra) * sizeof(double) +
            (size_t)WAVES * planes * (n_edges - 1) * sizeof(double);
 }
@@ -687,8 +668,7 @@ constexpr int max_bins(int n_edges) {
     while (lds_bytes<P>(n_edges, n + 1) <= LDS_LIMIT) ++n;
     return n;
 }
-constexpr int max_pi_planes(int n_edges) { return max_bins<ProjectedPi>(n_edges); }
-static_assert(max_pi_planes(MAX_EDGES) == 4 && max_pi_planes(13) == 104 && max_pi_planes(2) == 1023,
+static_assert(max_bins<ProjectedPi>(MAX_EDGES) == 4 && max_bins<ProjectedPi>(13) == 104 && max_bins<ProjectedPi>(2) == 1023,
               "ProjectedPi: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 22 quote it)");
 static_assert(max_bins<ProjectedShear>(MAX_EDGES) == 1 && max_bins<ProjectedShear>(51) == 8 && max_bins<ProjectedShear>(13) == 35 &&
                   max_bins<ProjectedShear>(2) == 393,
@@ -698,41 +678,13 @@ static_assert(max_bins<ProjectedShapes>(13) == 21 && max_bins<ProjectedShapes>(5
               "ProjectedShapes: the cap on n_pi moved (include/yawhip.h and DESIGN.md section 25 quote it)");
 static_assert(lds_bytes<RedshiftSpace>(13, 104) == lds_bytes<ProjectedPi>(13, 104) && lds_bytes<RedshiftSpace>(51, 25) == lds_bytes<ProjectedPi>(51, 25) &&
                   lds_bytes<RedshiftSpace>(MAX_EDGES, 4) == lds_bytes<ProjectedPi>(MAX_EDGES, 4),
-              "RedshiftSpace: its carve-up is ProjectedPi's, so that max_pi_planes caps n_mu too (DESIGN.md section 23)");
+              "RedshiftSpace: its carve-up is ProjectedPi's, so that ProjectedPi's cap is the cap on n_mu too (DESIGN.md section 23)");
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<ShearShear>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<ShearPair>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<DeltaSigma>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= LDS_LIMIT &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
                   lds_bytes<Projected>(MAX_EDGES) <= LDS_LIMIT &&  // (34 784: 2 * 256 * 48 + 2048 + 4 * 1 * 255 * 8)
                   lds_bytes<ProjectedPi>(MAX_EDGES, 1) <= LDS_LIMIT,  // (34 800: 16 more for pe[2]; yawhip_proj_count_pi caps n_pi)
               "shear_walk: more than 64 KiB of dynamic LDS at MAX_EDGES");
-
-__global__ void k_gather_shear(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ sx,
-                               const double *__restrict__ sy, const double *__restrict__ sz, const double *__restrict__ sw,
-                               const double *__restrict__ sg1, const double *__restrict__ sg2, double *__restrict__ x,
-                               double *__restrict__ y, double *__restrict__ z, double *__restrict__ w, double *__restrict__ wg1,
-                               double *__restrict__ wg2, bool products) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t j = perm[i];
-    x[i] = sx[j];
-    y[i] = sy[j];
-    z[i] = sz[j];
-    const double g1 = sg1[j], g2 = sg2[j];
-    if (sw) {
-        const double wj = sw[j];
-        w[i] = wj;
-        wg1[i] = products ? wj * g1 : g1;
-        wg2[i] = products ? wj * g2 : g2;
-    } else {
-        wg1[i] = g1;
-        wg2[i] = g2;
-    }
-}
-
-__global__ void k_gather_column(int64_t n, const uint32_t *__restrict__ perm, const double *__restrict__ src, double *__restrict__ dst) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[perm[i]];
-}
 
 // The walk of one cell = one workgroup. str: the streamed side, src: the side in the lanes; `table` and n_bins are the policy's
 // (P::cell); t: [rows][n_edges], rwin: [rows].
@@ -808,7 +760,7 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
         const double aw = ok ? (src.w ? src.w[ia] : 1.0) : 0.0;
         const double ag1 = ok ? src.wg1[ia] : 0.0;
         const double ag2 = ok ? src.wg2[ia] : 0.0;
-        const typename P::LaneT a = P::lane(src, ia, ok, Lane{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay, P::lane_u(src, ia, ok)});
+        const typename P::LaneT a = P::lane(src, ia, ok, Lane{ax, ay, az, aw, ag1, ag2, ax * ax + ay * ay});
         // a diagonal cell counts the streamed object i of a stage only for lanes with ia < its index: i > ia - (first of stage)
         const int64_t lane_rel = diag ? ia - b0 : (int64_t)-1 - (int64_t)STAGE;
 
@@ -852,11 +804,8 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
                         }
                         // t[cnt-1] < v <= t[cnt] (a v beyond the row -- the counts binned in a radius -- has cnt == n_edges and no bin:
                         // the histogram has nf of them), and not the lower half of a diagonal cell
-                        if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel)) {
-                            if constexpr (CALL_PLANES && P::ADD_BINNED) P::add(a, b, wh, cnt - 1, nf, ext, NP, P::first_step(src), v);
-                            else if constexpr (CALL_PLANES) P::add(a, b, wh, cnt - 1, nf, ext, NP);
-                            else P::add(a, b, wh, cnt - 1, nf);
-                        }
+                        if (cnt > 0 && (P::CAPPED || cnt < n_edges) && (!P::DIAGONAL || i > rel))
+                            P::add(a, b, wh, cnt - 1, nf, Staged{ext, NP, P::first_step(src)}, v);
                     }
                 }
             }
@@ -876,58 +825,51 @@ __device__ __forceinline__ void shear_walk(const typename P::View &str, const ty
 }
 
 // out: [3][n_cells][E-1] (T, X, W)
-__global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src, const int32_t *__restrict__ jobs, int n_bins,
-                                                    int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
-                                                    int64_t n_cells, double *__restrict__ out,
-                                                    unsigned long long *__restrict__ evaluated) {
+__global__ __launch_bounds__(WG) void k_count_shear(CatView lens, ShearView src, const int32_t *__restrict__ jobs, int n_bins, int n_edges,
+                                                    const double *__restrict__ t, const double *__restrict__ rwin, int64_t n_cells,
+                                                    double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<Tangential>(lens, src, jobs, n_bins, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
 // out: [4][n_cells][E-1] (P, M, C, W); nb: the handle's redshift bins = the bins of the call
 __global__ __launch_bounds__(WG) void k_count_shear_auto(ShearView src, int nb, const int32_t *__restrict__ jobs, int n_edges,
-                                                         const double *__restrict__ t, const double *__restrict__ rwin,
-                                                         int64_t n_cells, double *__restrict__ out,
-                                                         unsigned long long *__restrict__ evaluated) {
+                                                         const double *__restrict__ t, const double *__restrict__ rwin, int64_t n_cells,
+                                                         double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<ShearShear>(src, src, jobs, nb, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
-// out: [4][n_cells][E-1] (P, M, C, W); cells: [n_cells][4] (ShearPair::cell); a is streamed, b sits in the lanes
+// out: [4][n_cells][E-1] (P, M, C, W); cells: [n_cells][4] (CellTable); a is streamed, b sits in the lanes
 __global__ __launch_bounds__(WG) void k_count_shear_pair(ShearView a, ShearView b, const int32_t *__restrict__ cells, int n_edges,
-                                                         const double *__restrict__ t, const double *__restrict__ rwin,
-                                                         int64_t n_cells, double *__restrict__ out,
-                                                         unsigned long long *__restrict__ evaluated) {
+                                                         const double *__restrict__ t, const double *__restrict__ rwin, int64_t n_cells,
+                                                         double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<ShearPair>(a, b, cells, 0, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
 // out: [3][n_cells][E-1] (T, X, W)
-__global__ __launch_bounds__(WG) void k_count_dsigma(LensView lens, SourceView src, const int32_t *__restrict__ jobs, int n_bins,
-                                                     int n_edges, const double *__restrict__ t, const double *__restrict__ rwin,
-                                                     int64_t n_cells, double *__restrict__ out,
-                                                     unsigned long long *__restrict__ evaluated) {
+__global__ __launch_bounds__(WG) void k_count_dsigma(LensView lens, SourceView src, const int32_t *__restrict__ jobs, int n_bins, int n_edges,
+                                                     const double *__restrict__ t, const double *__restrict__ rwin, int64_t n_cells,
+                                                     double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<DeltaSigma>(lens, src, jobs, n_bins, n_edges, t, rwin, n_cells, out, evaluated);
 }
 
 // out: [3][n_cells][E-1] (T, X, W); r2: [n_bins][n_edges] squared radii, rwin: [n_bins] from the nearest lens of each bin
-__global__ __launch_bounds__(WG) void k_count_dsigma_radial(RadialView lens, SourceView src, const int32_t *__restrict__ jobs,
-                                                            int n_bins, int n_edges, const double *__restrict__ r2,
-                                                            const double *__restrict__ rwin, int64_t n_cells, double *__restrict__ out,
-                                                            unsigned long long *__restrict__ evaluated) {
+__global__ __launch_bounds__(WG) void k_count_dsigma_radial(RadialView lens, SourceView src, const int32_t *__restrict__ jobs, int n_bins,
+                                                            int n_edges, const double *__restrict__ r2, const double *__restrict__ rwin,
+                                                            int64_t n_cells, double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<DeltaSigmaRadial>(lens, src, jobs, n_bins, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
-// out: [1][n_cells][E-1] (W); cells: [n_cells][4] (ShearPair::cell); a is streamed, b sits in the lanes with the call's pmax
+// out: [1][n_cells][E-1] (W); cells: [n_cells][4] (CellTable); a is streamed, b sits in the lanes with the call's pmax
 __global__ __launch_bounds__(WG) void k_count_projected(ShearView a, ProjLanes b, const int32_t *__restrict__ cells, int n_edges,
-                                                        const double *__restrict__ r2, const double *__restrict__ rwin,
-                                                        int64_t n_cells, double *__restrict__ out,
-                                                        unsigned long long *__restrict__ evaluated) {
+                                                        const double *__restrict__ r2, const double *__restrict__ rwin, int64_t n_cells,
+                                                        double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<Projected>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
 // out: [n_pi][n_cells][E-1] (W per pi bin); as k_count_projected, b with the call's pi edges in the place of pmax
 __global__ __launch_bounds__(WG) void k_count_projected_pi(ShearView a, ProjPiLanes b, const int32_t *__restrict__ cells, int n_edges,
-                                                           const double *__restrict__ r2, const double *__restrict__ rwin,
-                                                           int64_t n_cells, double *__restrict__ out,
-                                                           unsigned long long *__restrict__ evaluated) {
+                                                           const double *__restrict__ r2, const double *__restrict__ rwin, int64_t n_cells,
+                                                           double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<ProjectedPi>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
@@ -939,141 +881,25 @@ __global__ __launch_bounds__(WG) void k_count_smu(ShearView a, SmuLanes b, const
     shear_walk<RedshiftSpace>(a, b, cells, 0, n_edges, s2, rwin, n_cells, out, evaluated);
 }
 
-// out: [3][n_pi][n_cells][E-1] (T, X, W per pi bin); cells: [n_cells][4] (ShearPair::cell, no diagonal ones); the projected
+// out: [3][n_pi][n_cells][E-1] (T, X, W per pi bin); cells: [n_cells][4] (CellTable, no diagonal ones); the projected
 // handle a is streamed, the shape handle b sits in the lanes with its d, c and the call's pi edges
 __global__ __launch_bounds__(WG) void k_count_projected_shear(ShearView a, ProjShapeLanes b, const int32_t *__restrict__ cells, int n_edges,
-                                                              const double *__restrict__ r2, const double *__restrict__ rwin,
-                                                              int64_t n_cells, double *__restrict__ out,
-                                                              unsigned long long *__restrict__ evaluated) {
+                                                              const double *__restrict__ r2, const double *__restrict__ rwin, int64_t n_cells,
+                                                              double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<ProjectedShear>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
-// out: [4][n_pi][n_cells][E-1] (PP, XX, PX, W per pi bin); cells: [n_cells][4] (ShearPair::cell); the shape handle a is streamed
+// out: [4][n_pi][n_cells][E-1] (PP, XX, PX, W per pi bin); cells: [n_cells][4] (CellTable); the shape handle a is streamed
 // with its d, c, the shape handle b sits in the lanes with its d, c and the call's pi edges
 __global__ __launch_bounds__(WG) void k_count_projected_shapes(ShapeView a, ProjShapeLanes b, const int32_t *__restrict__ cells, int n_edges,
-                                                               const double *__restrict__ r2, const double *__restrict__ rwin,
-                                                               int64_t n_cells, double *__restrict__ out,
-                                                               unsigned long long *__restrict__ evaluated) {
+                                                               const double *__restrict__ r2, const double *__restrict__ rwin, int64_t n_cells,
+                                                               double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<ProjectedShapes>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
 }
 
-}  // namespace
-
-extern "C" {
-
-int yawhip_shear_free(yawhip_shear_sources *src) {
-    if (!src) return YAWHIP_OK;
-    if (src->ctx) {
-        (void)hipSetDevice(src->ctx->device);
-        if (src->ctx->stream) (void)hipStreamSynchronize(src->ctx->stream);
-    }
-    delete src;  // its device memory goes with it
-    return YAWHIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The upload of every entry point: a handle of `kind` with n_bins segments per patch, each sorted along sort_axis and
-// gathered. a, b: the kind's two columns, gathered as the products w a, w b for the two kinds of shear catalogue and as they
-// came for the others; extra: the column u of DSIGMA_SOURCES, m of RADIAL_LENSES or d of PROJECTED_SHAPES, else NULL; extra2:
-// the column c of PROJECTED_SHAPES, else NULL
-int upload_segments(const char *fn, Kind kind, yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z,
-                    const double *w, const double *a, const double *b, const double *extra, const double *extra2, int32_t n_patches,
-                    int32_t n_bins, const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
-    if (!out) return fail(YAWHIP_ERR_INVALID, "%s: out is NULL", fn);
-    *out = nullptr;
-    if (!ctx) return fail(YAWHIP_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (sort_axis < 0 || sort_axis > 2) return fail(YAWHIP_ERR_INVALID, "sort_axis must be 0 (x), 1 (y) or 2 (z)");
-    if (n < 0 || n_patches <= 0 || n_bins <= 0 || !offsets || (n > 0 && (!x || !y || !z || !a || !b)))
-        return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL columns", fn);
-    if (n >= (1ll << 32)) return fail(YAWHIP_ERR_INVALID, "at most 2^32 - 1 objects per catalogue");
-    const int64_t n_seg = (int64_t)n_patches * n_bins;
-    if (offsets[0] != 0 || offsets[n_seg] != n) return fail(YAWHIP_ERR_INVALID, "offsets must start at 0 and end at n");
-    for (int64_t i = 0; i < n_seg; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(YAWHIP_ERR_INVALID, "offsets must be non-decreasing");
-    HIP_TRY(hipSetDevice(ctx->device));
-    yawhip_shear_sources *s = new (std::nothrow) yawhip_shear_sources;
-    if (!s) return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    s->ctx = ctx;
-    s->kind = kind;
-    s->n = n;
-    s->n_patches = n_patches;
-    s->nb = n_bins;
-    s->axis = sort_axis;
-    // the kinds counted in a radius keep the least entry per redshift bin of the column that bounds their reach (chord_reach)
-    const bool has_least = (kind & (RADIAL_LENSES | PROJECTED | PROJECTED_SHAPES)) != 0;
-    const double *scale = kind == PROJECTED ? a : extra;
-    try {
-        s->h_off.assign(offsets, offsets + n_seg + 1);
-        if (has_least) s->least.assign((size_t)n_bins, INFINITY);  // (n == 0: the column may be NULL, and no segment reads it)
-    } catch (const std::bad_alloc &) {
-        delete s;
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
-    for (int64_t seg = 0; has_least && seg < n_seg; ++seg)
-        for (int64_t i = offsets[seg]; i < offsets[seg + 1]; ++i)
-            s->least[(size_t)(seg % n_bins)] = std::min(s->least[(size_t)(seg % n_bins)], scale[i]);
-    DevPtr<double> *const d_extra = (kind & (DSIGMA_SOURCES | PROJECTED_SHAPES)) ? &s->u : kind == RADIAL_LENSES ? &s->m : nullptr;
-    DevPtr<double> *const d_extra2 = kind == PROJECTED_SHAPES ? &s->m : nullptr;
-    const size_t n1 = (size_t)std::max<int64_t>(n, 1), col = (size_t)n * sizeof(double);
-    constexpr int NC = 8;
-    DevPtr<double> raw[NC];  // x, y, z, a, b, w, extra, extra2 as they came (temporary)
-    const double *host[NC] = {x, y, z, a, b, w, extra, extra2};
-    DevPtr<uint32_t> perm;
-    hipError_t e = hipSuccess;
-    for (DevPtr<double> *c : {&s->x, &s->y, &s->z, &s->wg1, &s->wg2})
-        if (e == hipSuccess) e = c->alloc(n1);
-    if (e == hipSuccess && w) e = s->w.alloc(n1);
-    if (e == hipSuccess && d_extra) e = d_extra->alloc(n1);  // (an empty handle of the kind has the column too)
-    if (e == hipSuccess && d_extra2) e = d_extra2->alloc(n1);
-    if (e == hipSuccess) e = s->off.alloc((size_t)n_seg + 1);
-    for (int c = 0; c < NC; ++c)
-        if (e == hipSuccess && host[c]) e = raw[c].alloc(n1);
-    if (e == hipSuccess) e = perm.alloc(n1);
-    for (int c = 0; c < NC; ++c)
-        if (e == hipSuccess && host[c] && n > 0) e = hipMemcpyAsync(raw[c], host[c], col, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(s->off, offsets, ((size_t)n_seg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n > 0) {
-        e = yawsort::sort_segments(ctx->sort_ws, ctx->stream, n, key_of(raw[0], raw[1], raw[2], sort_axis), s->off, n_seg, perm);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_gather_shear, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[0], raw[1], raw[2], raw[5],
-                               raw[3], raw[4], s->x, s->y, s->z, s->w, s->wg1, s->wg2,
-                               (kind & (SHEAR | DSIGMA_SOURCES | PROJECTED_SHAPES)) != 0);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && d_extra) {
-            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[6], *d_extra);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && d_extra2) {
-            hipLaunchKernelGGL(k_gather_column, dim3(grid_for(n)), dim3(256), 0, ctx->stream, n, perm, raw[7], *d_extra2);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (ctx->sort_ws.cap > ((size_t)1 << 25)) ctx->sort_ws.release();  // as the catalogue upload: keep only small workspaces
-    if (e != hipSuccess) {
-        yawhip_shear_free(s);
-        return hip_fail(fn, e);
-    }
-    *out = s;
-    return YAWHIP_OK;
-}
-
-// a column of an upload beyond the coordinates: every entry a finite number, and of the rule's sign
-enum Rule { NOT_NEGATIVE, POSITIVE, ANY_SIGN };
-
-int check_column(const char *fn, const char *name, int64_t n, const double *v, Rule rule) {
-    static const char *const WANTED[] = {"a finite number >= 0", "a finite number > 0", "a finite number"};
-    if (n > 0 && !v) return fail(YAWHIP_ERR_INVALID, "%s: column %s is NULL", fn, name);
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i]) || (rule == NOT_NEGATIVE && !(v[i] >= 0.0)) || (rule == POSITIVE && !(v[i] > 0.0)))
-            return fail(YAWHIP_ERR_INVALID, "%s: column %s has an entry that is not %s (index %lld)", fn, name, WANTED[rule], (long long)i);
-    return YAWHIP_OK;
-}
+// ---- The host half. The checks of a count come in one order, before any device work: handles, sizes and context
+// (check_handles), the roles (require_kind), then what depends on the kinds: how the handles fit, the count's own arguments,
+// the thresholds, the job or cell list. Then run_count.
 
 // The one role check of the counts: the handle is of one of the kinds `accepted` (a sum of Kind), else the refusal `what`
 int require_kind(const char *fn, const yawhip_shear_sources *s, unsigned accepted, const char *what) {
@@ -1082,14 +908,6 @@ int require_kind(const char *fn, const yawhip_shear_sources *s, unsigned accepte
 
 constexpr unsigned SHEAR_CATALOGUES = SHEAR | DSIGMA_SOURCES;  // what the three shear counts take (a column u is ignored)
 constexpr const char *NOT_A_SHEAR_CATALOGUE = "a lens handle of yawhip_dsigma_upload_lenses is not a shear catalogue";
-
-// the sizes and arrays of a call over n_items jobs or cells (`arrays`: none of them is NULL)
-int check_sizes(const char *fn, int32_t n_items, int32_t n_rows, int32_t n_edges, const double *t, bool arrays) {
-    if (n_items < 0 || n_rows <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_items > 0 && !arrays))
-        return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)", fn, n_items, n_rows,
-                    n_edges, MAX_EDGES);
-    return YAWHIP_OK;
-}
 
 // the thresholds t[n_rows][n_edges]
 int check_thresholds(int32_t n_rows, int32_t n_edges, const double *t) {
@@ -1112,13 +930,13 @@ int check_job_list(const char *fn, int32_t n_jobs, const int32_t *jobs, int32_t 
     return YAWHIP_OK;
 }
 
-// The checks of a count come in one order, before any device work: handles, sizes and context (check_handles), the roles
-// (require_kind), then what depends on the kinds: how the handles fit, the thresholds, the job or cell list.
 template <class A>
 int check_handles(const char *fn, const yawhip_ctx *ctx, const A *a, const yawhip_shear_sources *b, int32_t n_items, int32_t n_rows,
                   int32_t n_edges, const double *t, bool arrays) {
     if (!ctx || !a || !b) return fail(YAWHIP_ERR_INVALID, "%s: NULL handle", fn);
-    if (const int rc = check_sizes(fn, n_items, n_rows, n_edges, t, arrays)) return rc;
+    if (n_items < 0 || n_rows <= 0 || n_edges < 2 || n_edges > MAX_EDGES || !t || (n_items > 0 && !arrays))  // (`arrays`: none is NULL)
+        return fail(YAWHIP_ERR_INVALID, "%s: bad sizes or NULL arrays (n_jobs=%d n_bins=%d n_edges=%d, max edges %d)", fn, n_items, n_rows,
+                    n_edges, MAX_EDGES);
     if (a->ctx != ctx || b->ctx != ctx) return fail(YAWHIP_ERR_MISMATCH, "catalogues belong to another context");
     return YAWHIP_OK;
 }
@@ -1160,6 +978,16 @@ int check_cells(const char *fn, const yawhip_shear_sources *a, const yawhip_shea
     return check_thresholds(n_rows, n_edges, t);
 }
 
+// reach[n_rows] of a count in a radius, every row without pairs yet (+inf)
+int no_reach(const char *fn, int32_t n_rows, std::vector<double> &reach) {
+    try {
+        reach.assign((size_t)n_rows, INFINITY);
+    } catch (const std::bad_alloc &) {
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+    }
+    return YAWHIP_OK;
+}
+
 // The window of a count in a radius. reach[k] comes in as the least scale of row k -- what the squared chord of a pair is
 // multiplied by before it meets the row's squared radii; +inf: the row has no pairs -- and leaves as the largest squared chord
 // of a pair in range: fl(scale s2) <= top needs s2 <= top / scale (1 + 2 eps). Beyond 0.01 (5.73 degrees) the series of the
@@ -1177,18 +1005,41 @@ int chord_reach(const char *fn, const char *who, const char *row, int32_t n_rows
     return YAWHIP_OK;
 }
 
+// What a kernel sees of a handle: view_of for the columns every kind has, and one view per kind with a column besides
+// (yawhip_shear.h has which). A count names its columns through these alone.
 ShearView view_of(const yawhip_shear_sources *s) {
     return ShearView{s->x, s->y, s->z, s->w, s->wg1, s->wg2, s->off, key_of(s->x, s->y, s->z, s->axis), s->axis};
 }
+LensView lens_view_of(const yawhip_shear_sources *s) { return LensView{view_of(s), s->nb}; }
+RadialView radial_view_of(const yawhip_shear_sources *s) { return RadialView{lens_view_of(s), s->extra}; }  // m
+SourceView source_view_of(const yawhip_shear_sources *s) { return SourceView{view_of(s), s->extra}; }       // u
+ShapeView shape_view_of(const yawhip_shear_sources *s) { return ShapeView{view_of(s), s->extra, s->extra2}; }  // d, c
+// ... and a shape handle in the lanes, with the staged pi edges pe[n_pi + 1] (device) and the last of them
+ProjShapeLanes shape_lanes_of(const yawhip_shear_sources *s, const double *pe, int32_t n_pi, double cut) {
+    return ProjShapeLanes{{view_of(s), pe, n_pi, cut}, s->extra, s->extra2};
+}
 
-// What the counts share once their arguments are checked. One table goes to d_in of the handle `buffers` (thresholds
-// [rows][E], window half widths [rows], the policy's table of n_table 32-bit integers: jobs [n_jobs][2] or cells [n_cells][4]);
-// pass(go, slots) names the kernel and its arguments in the kernel's order, go(kernel, arguments...), and run_count puts it on
-// the stream between the context's two events: one workgroup per cell, the policy's LDS. The kernel writes the result block
-// in d_out (P::PLANES planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[], the
-// counters and the event time to the statistics. n_rows: the rows of t; reach[k]: the largest squared chord of a pair in
-// range of row k where the row's last edge is not that (chord_reach), or NULL. A policy with the call's planes (PLANES == 0)
-// has PER_BIN n_pi of them, contiguous in fine[0], and its edges pe[n_pi + 1] travel in d_in between the half widths and the table.
+// What an entry point hands on of its arguments once they are checked: the handle whose per-call buffers the call uses (a count
+// over jobs its sources, one over cells its first handle); the policy's table -- jobs [n_items][2], a cell per job and row, or
+// cells [n_items][4], a cell each; the thresholds t[n_rows][n_edges]; the host planes. A policy with the call's planes
+// (PLANES == 0) has PER_BIN n_pi of them, contiguous in fine[0], and the edges pe[n_pi + 1] of its second binning.
+enum Table { JOBS = 2, CELLS = 4 };  // (the integers per item)
+struct Call {
+    const char *fn;
+    std::chrono::steady_clock::time_point wall0;
+    yawhip_ctx *ctx;
+    yawhip_shear_sources *buffers;
+    int32_t n_items;
+    Table width;
+    const int32_t *table;
+    int32_t n_rows, n_edges;
+    const double *t;
+    double *fine[4];
+    yawhip_stats *stats;
+    int32_t n_pi = 0;
+    const double *pe = nullptr;
+};
+
 struct Slots {  // what run_count has on the device for the kernel
     const int32_t *table;
     const double *t, *rwin, *pe;
@@ -1197,13 +1048,21 @@ struct Slots {  // what run_count has on the device for the kernel
     unsigned long long *evaluated;
 };
 
+// What the counts share once their arguments are checked. One table goes to d_in of the call's buffers (thresholds [rows][E],
+// window half widths [rows], the edges pe where there are some, the policy's table); pass(go, slots) names the kernel and its
+// arguments in the kernel's order, go(kernel, arguments...) -- the staged edges' device address is only known here -- and
+// run_count puts it on the stream between the context's two events: one workgroup per cell, the policy's LDS. The kernel writes
+// the result block in d_out (the planes [cells][E-1], then the cells' evaluated separations); the planes come back to fine[],
+// the counters and the event time to the statistics. reach[k]: the largest squared chord of a pair in range of row k where the
+// row's last edge is not that (chord_reach), or NULL.
 template <class P, class Pass>
-int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, size_t n_table, const int32_t *table, size_t n_cells,
-              int32_t n_rows, int32_t n_edges, const double *t, const double *reach, double *const *fine, int64_t candidates,
-              std::chrono::steady_clock::time_point wall0, yawhip_stats *stats, Pass pass, int32_t n_pi = 0, const double *pe = nullptr) {
+int run_count(const Call &c, const double *reach, int64_t candidates, Pass pass) {
+    yawhip_stats *const stats = c.stats;
+    const int32_t n_rows = c.n_rows, n_edges = c.n_edges;
+    const size_t n_table = (size_t)c.width * c.n_items, n_cells = (size_t)c.n_items * (c.width == JOBS ? n_rows : 1);
     if (stats) *stats = yawhip_stats{};
     if (n_cells == 0) return YAWHIP_OK;
-    const size_t planes = P::PLANES ? (size_t)P::PLANES : (size_t)P::PER_BIN * n_pi, n_pe = pe ? (size_t)n_pi + 1 : 0;
+    const size_t planes = planes_of<P>(c.n_pi), n_pe = c.pe ? (size_t)c.n_pi + 1 : 0;
     const size_t n_t = (size_t)n_rows * n_edges, in_bytes = (n_t + (size_t)n_rows + n_pe) * sizeof(double) + n_table * sizeof(int32_t);
     const size_t plane = n_cells * (size_t)(n_edges - 1), n_out = planes * plane;
     std::vector<unsigned char> h_in;
@@ -1212,38 +1071,39 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, si
         h_in.resize(in_bytes);
         if (stats) h_eval.resize(n_cells);
     } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
+        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", c.fn);
     }
     double *h_t = reinterpret_cast<double *>(h_in.data()), *h_rwin = h_t + n_t;
-    memcpy(h_t, t, n_t * sizeof(double));
+    memcpy(h_t, c.t, n_t * sizeof(double));
     // a pair passes s2 <= t_max only if |du| <= sqrt(t_max) (1 + 2 eps) along any axis u (s2 >= fl(du^2), du rounded once);
     // 1e-15 more covers the rounding of key -/+ rwin (|key -/+ rwin| <= 3): the window of k_build_items
     for (int k = 0; k < n_rows; ++k)
-        h_rwin[k] = std::sqrt(reach ? reach[k] : t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
-    if (n_pe) memcpy(h_rwin + n_rows, pe, n_pe * sizeof(double));
-    memcpy(h_rwin + n_rows + n_pe, table, n_table * sizeof(int32_t));
+        h_rwin[k] = std::sqrt(reach ? reach[k] : c.t[(size_t)k * n_edges + n_edges - 1]) * (1.0 + 1e-12) + 1e-15;
+    if (n_pe) memcpy(h_rwin + n_rows, c.pe, n_pe * sizeof(double));
+    memcpy(h_rwin + n_rows + n_pe, c.table, n_table * sizeof(int32_t));
 
+    yawhip_ctx *const ctx = c.ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(ctx->make_events());
-    HIP_TRY(buffers->d_in.reserve(in_bytes, in_bytes / 4 + 64));
-    HIP_TRY(buffers->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
+    HIP_TRY(c.buffers->d_in.reserve(in_bytes, in_bytes / 4 + 64));
+    HIP_TRY(c.buffers->d_out.reserve(n_out + n_cells, n_out / 4 + 64));
     // (pageable memory: the copy has left h_in when the call returns)
-    HIP_TRY(hipMemcpyAsync(buffers->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const double *d_t = reinterpret_cast<const double *>((unsigned char *)buffers->d_in.ptr), *d_rwin = d_t + n_t;
+    HIP_TRY(hipMemcpyAsync(c.buffers->d_in.ptr, h_in.data(), in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const double *d_t = reinterpret_cast<const double *>((unsigned char *)c.buffers->d_in.ptr), *d_rwin = d_t + n_t;
     const double *d_pe = d_rwin + n_rows;
     const int32_t *d_table = reinterpret_cast<const int32_t *>(d_pe + n_pe);
-    double *d_out = buffers->d_out.ptr;
+    double *d_out = c.buffers->d_out.ptr;
     unsigned long long *d_eval = reinterpret_cast<unsigned long long *>(d_out + n_out);
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     pass([&](auto kernel, auto... arguments) {
-             hipLaunchKernelGGL(kernel, dim3((unsigned)n_cells), dim3(WG), lds_bytes<P>(n_edges, n_pi), ctx->stream, arguments...);
+             hipLaunchKernelGGL(kernel, dim3((unsigned)n_cells), dim3(WG), lds_bytes<P>(n_edges, c.n_pi), ctx->stream, arguments...);
          },
          Slots{d_table, d_t, d_rwin, d_pe, (int64_t)n_cells, d_out, d_eval});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    if (P::PLANES == 0) HIP_TRY(hipMemcpyAsync(fine[0], d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    for (int c = 0; c < P::PLANES; ++c)
-        HIP_TRY(hipMemcpyAsync(fine[c], d_out + (size_t)c * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (P::PLANES == 0) HIP_TRY(hipMemcpyAsync(c.fine[0], d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    for (int p = 0; p < P::PLANES; ++p)
+        HIP_TRY(hipMemcpyAsync(c.fine[p], d_out + (size_t)p * plane, plane * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (stats) HIP_TRY(hipMemcpyAsync(h_eval.data(), d_eval, n_cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (stats) {
@@ -1254,7 +1114,7 @@ int run_count(const char *fn, yawhip_ctx *ctx, yawhip_shear_sources *buffers, si
         stats->n_workgroups = (int64_t)n_cells;
         stats->n_launches = 1;
         stats->kernel_ms = stats->count_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c.wall0).count();
     }
     return YAWHIP_OK;
 }
@@ -1269,19 +1129,15 @@ int check_dsigma(const char *fn, yawhip_ctx *ctx, const yawhip_shear_sources *le
     return check_jobs(fn, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, candidates);
 }
 
-// What the two projected counts check once their own arguments passed, and in this order: the cells' segments, rows and diagonal
-// marks, then the reach of every row (reach: [n_rows] out, for run_count). The scale of a pair is DD, D = fl(0.5 (d_a + d_b))
+// What a count over projected cells checks once its own arguments passed, and in this order: the cells' segments, rows and
+// diagonal marks, then the reach of every row (reach: [n_rows] out, for run_count). The scale of a pair is DD, D = fl(0.5 (d_a + d_b))
 // no less than the smaller of the two (rounding is monotone), which is no less than the least d of the bins that the row's
 // cells pair. A row without cells, or with an empty bin on either side, has no pairs.
 int check_proj_cells(const char *fn, const yawhip_shear_sources *a, const yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                      int32_t n_rows, int32_t n_edges, const double *r2, std::vector<double> &reach, int64_t *candidates) {
     if (const int rc = check_cells(fn, a, b, n_rows, n_edges, r2)) return rc;
     const int64_t segs_a = (int64_t)a->n_patches * a->nb, segs_b = (int64_t)b->n_patches * b->nb;
-    try {
-        reach.assign((size_t)n_rows, INFINITY);
-    } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
+    if (const int rc = no_reach(fn, n_rows, reach)) return rc;
     *candidates = 0;
     for (int c = 0; c < n_cells; ++c) {
         const int32_t *cell = cells + 4 * (size_t)c;
@@ -1299,7 +1155,7 @@ int check_proj_cells(const char *fn, const yawhip_shear_sources *a, const yawhip
     return chord_reach(fn, "an object", "row", n_rows, n_edges, r2, reach);
 }
 
-// the pi edges pe[n_pi + 1] of the two counts binned in the line-of-sight separation
+// the pi edges pe[n_pi + 1] of the counts binned in the line-of-sight separation
 int check_pi_edges(const char *fn, int32_t n_pi, const double *pe) {
     if (n_pi < 1 || !pe) return fail(YAWHIP_ERR_INVALID, "%s: n_pi must be >= 1 and pe not NULL (n_pi=%d)", fn, n_pi);
     if (pe[0] != 0.0) return fail(YAWHIP_ERR_INVALID, "%s: the first pi edge must be 0", fn);
@@ -1309,81 +1165,71 @@ int check_pi_edges(const char *fn, int32_t n_pi, const double *pe) {
     return YAWHIP_OK;
 }
 
-// the largest n_edges at which one pi bin of the shape-shape count still fits (its refusal names it where no n_pi does)
-constexpr int max_shape_edges() {
+// the squared mu edges m2[n_mu + 1] of the redshift-space count
+int check_mu_edges(const char *fn, int32_t n_mu, const double *m2) {
+    if (n_mu < 1 || !m2) return fail(YAWHIP_ERR_INVALID, "%s: n_mu must be >= 1 and m2 not NULL (n_mu=%d)", fn, n_mu);
+    if (m2[0] != 0.0 || m2[n_mu] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must start at 0 and end at 1", fn);
+    for (int j = 1; j <= n_mu; ++j)  // (a NaN fails the comparison; between 0 and 1 ascending edges are finite)
+        if (!(m2[j] > m2[j - 1]))
+            return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must be finite and strictly ascending (edge %d)", fn, j);
+    return YAWHIP_OK;
+}
+
+// the largest n_edges at which one bin of P's second binning still fits (the cap refusal names it where no number of bins does)
+template <class P>
+constexpr int max_edges_at_one_bin() {
     int n = 2;
-    while (n < MAX_EDGES && max_bins<ProjectedShapes>(n + 1) >= 1) ++n;
+    while (n < MAX_EDGES && max_bins<P>(n + 1) >= 1) ++n;
     return n;
 }
-static_assert(max_shape_edges() == 241, "ProjectedShapes: the largest n_edges moved (include/yawhip.h quotes it)");
+static_assert(max_edges_at_one_bin<ProjectedShapes>() == 241, "ProjectedShapes: the largest n_edges moved (include/yawhip.h quotes it)");
+
+// The cap of a second binning: its planes times the row's bins fit the LDS of a workgroup (max_bins), else the one refusal of
+// all such counts, about `bins` ("pi") of `rows` ("radius") bins. Only the shape-shape count has n_edges <= MAX_EDGES at which
+// nothing fits.
+template <class P>
+int check_cap(const Call &c, const char *bins, const char *rows) {
+    const int cap = max_bins<P>(c.n_edges);
+    if (c.n_pi <= cap) return YAWHIP_OK;
+    char most[96];
+    if (cap) snprintf(most, sizeof most, "at most %d %s bins at n_edges=%d", cap, bins, c.n_edges);
+    else snprintf(most, sizeof most, "not even 1 %s bin at n_edges=%d, at most n_edges=%d at 1 %s bin", bins, c.n_edges, max_edges_at_one_bin<P>(), bins);
+    return fail(YAWHIP_ERR_INVALID, "%s: %d %s bins of %d %s bins do not fit the LDS of a workgroup: %s", c.fn, c.n_pi, bins, c.n_edges - 1, rows, most);
+}
+
+constexpr const char *NOT_PROJECTED = "a handle is not one of yawhip_proj_upload";
+constexpr const char *NOT_SHAPES = "a handle is not one of yawhip_proj_upload_shapes";
+
+// the streamed side of a policy with that view
+ShearView streamed(const yawhip_shear_sources *s, const ShearView *) { return view_of(s); }
+ShapeView streamed(const yawhip_shear_sources *s, const ShapeView *) { return shape_view_of(s); }
+
+// The one path of the five counts over a cell list of projected or shape handles: a = c.buffers is streamed, b sits in the
+// lanes. An entry point states its policy P with its kernel, the kind it takes for a and for b with the refusal of every
+// other, check() of its own arguments, the words of its cap refusal (a count with a second binning: c.n_pi, c.pe) and
+// lanes(pe): the view of b, given the device address of the staged edges. The checks come in one order (the head of the host
+// half); the five kernels share one argument order.
+template <class P, class Kernel, class Check, class Lanes>
+int count_projected(Kernel kernel, const Call &c, yawhip_shear_sources *b, Kind kind_a, const char *not_a, Kind kind_b, const char *not_b,
+                    Check check, const char *bins, const char *rows, Lanes lanes) {
+    yawhip_shear_sources *const a = c.buffers;
+    if (const int rc = check_handles(c.fn, c.ctx, a, b, c.n_items, c.n_rows, c.n_edges, c.t, c.table && c.fine[0])) return rc;
+    if (const int rc = require_kind(c.fn, a, kind_a, not_a)) return rc;
+    if (const int rc = require_kind(c.fn, b, kind_b, not_b)) return rc;
+    if (const int rc = check()) return rc;
+    if constexpr (P::PLANES == 0)
+        if (const int rc = check_cap<P>(c, bins, rows)) return rc;
+    std::vector<double> reach;
+    int64_t candidates = 0;
+    if (const int rc = check_proj_cells(c.fn, a, b, c.n_items, c.table, c.n_rows, c.n_edges, c.t, reach, &candidates)) return rc;
+    return run_count<P>(c, reach.data(), candidates, [&](auto go, const Slots &d) {
+        go(kernel, streamed(a, (const typename P::View *)nullptr), lanes(d.pe), d.table, c.n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+    });
+}
 
 }  // namespace
 
 extern "C" {
-
-int yawhip_shear_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                        const double *g1, const double *g2, int32_t n_patches, const int64_t *offsets, int32_t sort_axis,
-                        yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, nullptr, n_patches, 1, offsets, sort_axis, out);
-}
-
-int yawhip_shear_upload_binned(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                               const double *g1, const double *g2, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
-                               int32_t sort_axis, yawhip_shear_sources **out) {
-    return upload_segments("yawhip_shear_upload_binned", SHEAR, ctx, n, x, y, z, w, g1, g2, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
-}
-
-int yawhip_dsigma_upload_sources(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                 const double *g1, const double *g2, const double *u, int32_t n_patches, const int64_t *offsets,
-                                 int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_sources";
-    if (out) *out = nullptr;
-    if (const int rc = check_column(fn, "u", n, u, NOT_NEGATIVE)) return rc;
-    return upload_segments(fn, DSIGMA_SOURCES, ctx, n, x, y, z, w, g1, g2, u, nullptr, n_patches, 1, offsets, sort_axis, out);
-}
-
-int yawhip_dsigma_upload_lenses(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                const double *f, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
-                                int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_lenses";
-    if (out) *out = nullptr;
-    if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
-    if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
-    return upload_segments(fn, DSIGMA_LENSES, ctx, n, x, y, z, w, f, c, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
-}
-
-int yawhip_dsigma_upload_lenses_radial(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                                       const double *f, const double *c, const double *m, int32_t n_patches, int32_t n_bins,
-                                       const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_dsigma_upload_lenses_radial";
-    if (out) *out = nullptr;
-    if (const int rc = check_column(fn, "f", n, f, NOT_NEGATIVE)) return rc;
-    if (const int rc = check_column(fn, "c", n, c, NOT_NEGATIVE)) return rc;
-    if (const int rc = check_column(fn, "m", n, m, POSITIVE)) return rc;
-    return upload_segments(fn, RADIAL_LENSES, ctx, n, x, y, z, w, f, c, m, nullptr, n_patches, n_bins, offsets, sort_axis, out);
-}
-
-int yawhip_proj_upload(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                       const double *d, const double *c, int32_t n_patches, int32_t n_bins, const int64_t *offsets,
-                       int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_proj_upload";
-    if (out) *out = nullptr;
-    if (const int rc = check_column(fn, "d", n, d, POSITIVE)) return rc;
-    if (const int rc = check_column(fn, "c", n, c, ANY_SIGN)) return rc;
-    return upload_segments(fn, PROJECTED, ctx, n, x, y, z, w, d, c, nullptr, nullptr, n_patches, n_bins, offsets, sort_axis, out);
-}
-
-int yawhip_proj_upload_shapes(yawhip_ctx *ctx, int64_t n, const double *x, const double *y, const double *z, const double *w,
-                              const double *g1, const double *g2, const double *d, const double *c, int32_t n_patches, int32_t n_bins,
-                              const int64_t *offsets, int32_t sort_axis, yawhip_shear_sources **out) {
-    const char *fn = "yawhip_proj_upload_shapes";
-    if (out) *out = nullptr;
-    if (const int rc = check_column(fn, "g1", n, g1, ANY_SIGN)) return rc;
-    if (const int rc = check_column(fn, "g2", n, g2, ANY_SIGN)) return rc;
-    if (const int rc = check_column(fn, "d", n, d, POSITIVE)) return rc;
-    if (const int rc = check_column(fn, "c", n, c, ANY_SIGN)) return rc;
-    return upload_segments(fn, PROJECTED_SHAPES, ctx, n, x, y, z, w, g1, g2, d, c, n_patches, n_bins, offsets, sort_axis, out);
-}
 
 int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_shear_sources *sources, int32_t n_jobs,
                        const int32_t *jobs, int32_t n_bins, int32_t n_edges, const double *t, double *fine_t, double *fine_x,
@@ -1394,9 +1240,8 @@ int yawhip_shear_count(yawhip_ctx *ctx, const yawhip_catalog *lenses, yawhip_she
     if (const int rc = check_handles(fn, ctx, lenses, sources, n_jobs, n_bins, n_edges, t, jobs && fine_t && fine_x && fine_w)) return rc;
     if (const int rc = require_kind(fn, sources, SHEAR_CATALOGUES, NOT_A_SHEAR_CATALOGUE)) return rc;
     if (const int rc = check_jobs(fn, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, &candidates)) return rc;
-    double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count<Tangential>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
-                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
+    return run_count<Tangential>(Call{fn, wall0, ctx, sources, n_jobs, JOBS, jobs, n_bins, n_edges, t, {fine_t, fine_x, fine_w}, stats}, nullptr, candidates,
+                                 [&](auto go, const Slots &d) {
                                      go(k_count_shear, view_of(lenses), view_of(sources), d.table, n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out,
                                         d.evaluated);
                                  });
@@ -1420,11 +1265,11 @@ int yawhip_shear_auto_count(yawhip_ctx *ctx, yawhip_shear_sources *sources, int3
         for (int k = 0; k < n_bins; ++k)
             candidates += segment_pairs(sources, (size_t)jobs[2 * j] * n_bins + k, sources, (size_t)jobs[2 * j + 1] * n_bins + k);
     }
-    double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
-    return run_count<ShearShear>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
-                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
-                                     go(k_count_shear_auto, view_of(sources), n_bins, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
-                                 });
+    return run_count<ShearShear>(
+        Call{fn, wall0, ctx, sources, n_jobs, JOBS, jobs, n_bins, n_edges, t, {fine_p, fine_m, fine_c, fine_w}, stats}, nullptr, candidates,
+        [&](auto go, const Slots &d) {
+            go(k_count_shear_auto, view_of(sources), n_bins, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+        });
 }
 
 int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
@@ -1460,9 +1305,8 @@ int yawhip_shear_pair_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_she
         int32_t *entry = &table[4 * (size_t)c];
         entry[0] = (int32_t)sa, entry[1] = (int32_t)sb, entry[2] = row, entry[3] = a == b && sa == sb;
     }
-    double *const fine[] = {fine_p, fine_m, fine_c, fine_w};
-    return run_count<ShearPair>(fn, ctx, a, table.size(), table.data(), (size_t)n_cells, n_rows, n_edges, t, nullptr, fine, candidates, wall0,
-                                stats, [&](auto go, const Slots &d) {
+    return run_count<ShearPair>(Call{fn, wall0, ctx, a, n_cells, CELLS, table.data(), n_rows, n_edges, t, {fine_p, fine_m, fine_c, fine_w}, stats}, nullptr, candidates,
+                                [&](auto go, const Slots &d) {
                                     go(k_count_shear_pair, view_of(a), view_of(b), d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
                                 });
 }
@@ -1475,11 +1319,10 @@ int yawhip_dsigma_count(yawhip_ctx *ctx, yawhip_shear_sources *lenses, yawhip_sh
     int64_t candidates = 0;
     if (const int rc = check_dsigma(fn, ctx, lenses, sources, n_jobs, jobs, n_bins, n_edges, t, fine_t && fine_x && fine_w, &candidates))
         return rc;
-    double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count<DeltaSigma>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, t, nullptr, fine,
-                                 candidates, wall0, stats, [&](auto go, const Slots &d) {
-                                     go(k_count_dsigma, LensView{view_of(lenses), lenses->nb}, SourceView{view_of(sources), sources->u}, d.table,
-                                        n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
+    return run_count<DeltaSigma>(Call{fn, wall0, ctx, sources, n_jobs, JOBS, jobs, n_bins, n_edges, t, {fine_t, fine_x, fine_w}, stats}, nullptr, candidates,
+                                 [&](auto go, const Slots &d) {
+                                     go(k_count_dsigma, lens_view_of(lenses), source_view_of(sources), d.table, n_bins, n_edges, d.t, d.rwin,
+                                        d.n_cells, d.out, d.evaluated);
                                  });
 }
 
@@ -1493,150 +1336,74 @@ int yawhip_dsigma_count_radial(yawhip_ctx *ctx, yawhip_shear_sources *lenses, ya
         return rc;
     if (const int rc = require_kind(fn, lenses, RADIAL_LENSES, "the lenses are not a handle of yawhip_dsigma_upload_lenses_radial")) return rc;
     std::vector<double> reach;  // the scale of a row is m: the nearest lens of its redshift bin
-    try {
-        reach.resize((size_t)n_bins);
-    } catch (const std::bad_alloc &) {
-        return fail(YAWHIP_ERR_OOM, "%s: out of host memory", fn);
-    }
+    if (const int rc = no_reach(fn, n_bins, reach)) return rc;
     for (int k = 0; k < n_bins; ++k) reach[(size_t)k] = lenses->least[lenses->nb == 1 ? 0 : (size_t)k];
     if (const int rc = chord_reach(fn, "a lens", "bin", n_bins, n_edges, r2, reach)) return rc;
-    double *const fine[] = {fine_t, fine_x, fine_w};
-    return run_count<DeltaSigmaRadial>(fn, ctx, sources, 2 * (size_t)n_jobs, jobs, (size_t)n_jobs * n_bins, n_bins, n_edges, r2, reach.data(),
-                                       fine, candidates, wall0, stats, [&](auto go, const Slots &d) {
-                                           go(k_count_dsigma_radial, RadialView{LensView{view_of(lenses), lenses->nb}, lenses->m},
-                                              SourceView{view_of(sources), sources->u}, d.table, n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out,
-                                              d.evaluated);
-                                       });
+    return run_count<DeltaSigmaRadial>(
+        Call{fn, wall0, ctx, sources, n_jobs, JOBS, jobs, n_bins, n_edges, r2, {fine_t, fine_x, fine_w}, stats}, reach.data(), candidates,
+        [&](auto go, const Slots &d) {
+            go(k_count_dsigma_radial, radial_view_of(lenses), source_view_of(sources), d.table, n_bins, n_edges, d.t, d.rwin, d.n_cells, d.out,
+               d.evaluated);
+        });
 }
 
 int yawhip_proj_count(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                       int32_t n_rows, int32_t n_edges, const double *r2, double pmax, double *fine_w, yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count";
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
-    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (!(pmax >= 0.0)) return fail(YAWHIP_ERR_INVALID, "%s: pmax must be a number >= 0 (+inf: no line-of-sight cut)", fn);
-    std::vector<double> reach;
-    int64_t candidates = 0;
-    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
-    double *const fine[] = {fine_w};
-    return run_count<Projected>(fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), fine, candidates,
-                                wall0, stats, [&](auto go, const Slots &d) {
-                                    go(k_count_projected, view_of(a), ProjLanes{view_of(b), pmax}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out,
-                                       d.evaluated);
-                                });
+    return count_projected<Projected>(
+        k_count_projected, Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, r2, {fine_w}, stats}, b,
+        PROJECTED, NOT_PROJECTED, PROJECTED, NOT_PROJECTED,
+        [&] { return pmax >= 0.0 ? YAWHIP_OK : fail(YAWHIP_ERR_INVALID, "%s: pmax must be a number >= 0 (+inf: no line-of-sight cut)", fn); },
+        "", "", [&](const double *) { return ProjLanes{view_of(b), pmax}; });
 }
 
 int yawhip_proj_count_pi(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                          int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine_w,
                          yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count_pi";
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine_w)) return rc;
-    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
-    if (n_pi > max_pi_planes(n_edges))
-        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
-                    n_pi, n_edges - 1, max_pi_planes(n_edges), n_edges);
-    std::vector<double> reach;
-    int64_t candidates = 0;
-    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
-    double *const fine[] = {fine_w};
-    return run_count<ProjectedPi>(
-        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), fine, candidates, wall0, stats,
-        [&](auto go, const Slots &d) {
-            go(k_count_projected_pi, view_of(a), ProjPiLanes{view_of(b), d.pe, n_pi, pe[n_pi]}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
-        },
-        n_pi, pe);
+    return count_projected<ProjectedPi>(
+        k_count_projected_pi, Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, r2, {fine_w}, stats, n_pi, pe},
+        b, PROJECTED, NOT_PROJECTED, PROJECTED, NOT_PROJECTED, [&] { return check_pi_edges(fn, n_pi, pe); }, "pi", "radius",
+        [&](const double *d_pe) { return ProjPiLanes{view_of(b), d_pe, n_pi, pe[n_pi]}; });
 }
 
+// The row holds squared s edges where yawhip_proj_count's holds squared radii. R2 <= S2 = fl(R2 + P2) (P2 >= 0, rounding is
+// monotone), so a counted pair has R2 <= the row's last edge: the reach of the largest s bounds the reach of every counted
+// pair, and the checks and the window of the radius table hold on this one as they are.
 int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                           int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu, const double *m2, double *fine_w,
                           yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count_smu";
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, s2, cells && fine_w)) return rc;
-    if (const int rc = require_kind(fn, a, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (const int rc = require_kind(fn, b, PROJECTED, "a handle is not one of yawhip_proj_upload")) return rc;
-    if (n_mu < 1 || !m2) return fail(YAWHIP_ERR_INVALID, "%s: n_mu must be >= 1 and m2 not NULL (n_mu=%d)", fn, n_mu);
-    if (m2[0] != 0.0 || m2[n_mu] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must start at 0 and end at 1", fn);
-    for (int j = 1; j <= n_mu; ++j)  // (a NaN fails the comparison; between 0 and 1 ascending edges are finite)
-        if (!(m2[j] > m2[j - 1]))
-            return fail(YAWHIP_ERR_INVALID, "%s: the squared mu edges must be finite and strictly ascending (edge %d)", fn, j);
-    if (n_mu > max_pi_planes(n_edges))
-        return fail(YAWHIP_ERR_INVALID, "%s: %d mu bins of %d s bins do not fit the LDS of a workgroup: at most %d mu bins at n_edges=%d", fn,
-                    n_mu, n_edges - 1, max_pi_planes(n_edges), n_edges);
-    // The row holds squared s edges where yawhip_proj_count's holds squared radii. R2 <= S2 = fl(R2 + P2) (P2 >= 0, rounding is
-    // monotone), so a counted pair has R2 <= the row's last edge: the reach of the largest s bounds the reach of every counted
-    // pair, and the checks and the window of the radius table hold on this one as they are.
-    std::vector<double> reach;
-    int64_t candidates = 0;
-    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, s2, reach, &candidates)) return rc;
-    int step = 0;  // the largest power of two <= n_mu - 1: the first step of the kernel's bisection of the inner edges
-    for (int two = 1; two <= n_mu - 1; two *= 2) step = two;
-    double *const fine[] = {fine_w};
-    return run_count<RedshiftSpace>(
-        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, s2, reach.data(), fine, candidates, wall0, stats,
-        [&](auto go, const Slots &d) {
-            go(k_count_smu, view_of(a), SmuLanes{view_of(b), d.pe, n_mu, step}, d.table, n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
-        },
-        n_mu, m2);
+    return count_projected<RedshiftSpace>(
+        k_count_smu, Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, s2, {fine_w}, stats, n_mu, m2}, b,
+        PROJECTED, NOT_PROJECTED, PROJECTED, NOT_PROJECTED, [&] { return check_mu_edges(fn, n_mu, m2); }, "mu", "s",
+        [&](const double *d_m2) {
+            int step = 0;  // the largest power of two <= n_mu - 1: the first step of the kernel's bisection of the inner edges
+            for (int two = 1; two <= n_mu - 1; two *= 2) step = two;
+            return SmuLanes{view_of(b), d_m2, n_mu, step};
+        });
 }
 
+// (the two handles differ, so check_proj_cells refuses every cell that is marked diagonal)
 int yawhip_proj_count_shear(yawhip_ctx *ctx, yawhip_shear_sources *dens, yawhip_shear_sources *shapes, int32_t n_cells,
                             const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe,
                             double *fine, yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count_shear";
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (const int rc = check_handles(fn, ctx, dens, shapes, n_cells, n_rows, n_edges, r2, cells && fine)) return rc;
-    if (const int rc = require_kind(fn, dens, PROJECTED, "the density handle is not one of yawhip_proj_upload")) return rc;
-    if (const int rc = require_kind(fn, shapes, PROJECTED_SHAPES, "the shape handle is not one of yawhip_proj_upload_shapes")) return rc;
-    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
-    if (n_pi > max_bins<ProjectedShear>(n_edges))
-        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
-                    n_pi, n_edges - 1, max_bins<ProjectedShear>(n_edges), n_edges);
-    // (the two handles differ, so check_proj_cells refuses every cell that is marked diagonal)
-    std::vector<double> reach;
-    int64_t candidates = 0;
-    if (const int rc = check_proj_cells(fn, dens, shapes, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
-    double *const planes[] = {fine};
-    return run_count<ProjectedShear>(
-        fn, ctx, dens, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), planes, candidates, wall0, stats,
-        [&](auto go, const Slots &d) {
-            go(k_count_projected_shear, view_of(dens), ProjShapeLanes{{view_of(shapes), d.pe, n_pi, pe[n_pi]}, shapes->u, shapes->m}, d.table,
-               n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
-        },
-        n_pi, pe);
+    return count_projected<ProjectedShear>(
+        k_count_projected_shear, Call{fn, std::chrono::steady_clock::now(), ctx, dens, n_cells, CELLS, cells, n_rows, n_edges, r2, {fine}, stats, n_pi, pe},
+        shapes, PROJECTED, "the density handle is not one of yawhip_proj_upload", PROJECTED_SHAPES,
+        "the shape handle is not one of yawhip_proj_upload_shapes", [&] { return check_pi_edges(fn, n_pi, pe); }, "pi", "radius",
+        [&](const double *d_pe) { return shape_lanes_of(shapes, d_pe, n_pi, pe[n_pi]); });
 }
 
 int yawhip_proj_count_shapes(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
                              int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine,
                              yawhip_stats *stats) {
     const char *fn = "yawhip_proj_count_shapes";
-    const auto wall0 = std::chrono::steady_clock::now();
-    if (const int rc = check_handles(fn, ctx, a, b, n_cells, n_rows, n_edges, r2, cells && fine)) return rc;
-    if (const int rc = require_kind(fn, a, PROJECTED_SHAPES, "a handle is not one of yawhip_proj_upload_shapes")) return rc;
-    if (const int rc = require_kind(fn, b, PROJECTED_SHAPES, "a handle is not one of yawhip_proj_upload_shapes")) return rc;
-    if (const int rc = check_pi_edges(fn, n_pi, pe)) return rc;
-    if (max_bins<ProjectedShapes>(n_edges) == 0)
-        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: not even 1 pi bin at n_edges=%d, at most n_edges=%d at 1 pi bin",
-                    fn, n_pi, n_edges - 1, n_edges, max_shape_edges());
-    if (n_pi > max_bins<ProjectedShapes>(n_edges))
-        return fail(YAWHIP_ERR_INVALID, "%s: %d pi bins of %d radius bins do not fit the LDS of a workgroup: at most %d pi bins at n_edges=%d", fn,
-                    n_pi, n_edges - 1, max_bins<ProjectedShapes>(n_edges), n_edges);
-    std::vector<double> reach;
-    int64_t candidates = 0;
-    if (const int rc = check_proj_cells(fn, a, b, n_cells, cells, n_rows, n_edges, r2, reach, &candidates)) return rc;
-    double *const planes[] = {fine};
-    return run_count<ProjectedShapes>(
-        fn, ctx, a, 4 * (size_t)n_cells, cells, (size_t)n_cells, n_rows, n_edges, r2, reach.data(), planes, candidates, wall0, stats,
-        [&](auto go, const Slots &d) {
-            go(k_count_projected_shapes, ShapeView{view_of(a), a->u, a->m}, ProjShapeLanes{{view_of(b), d.pe, n_pi, pe[n_pi]}, b->u, b->m}, d.table,
-               n_edges, d.t, d.rwin, d.n_cells, d.out, d.evaluated);
-        },
-        n_pi, pe);
+    return count_projected<ProjectedShapes>(
+        k_count_projected_shapes, Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, r2, {fine}, stats, n_pi, pe},
+        b, PROJECTED_SHAPES, NOT_SHAPES, PROJECTED_SHAPES, NOT_SHAPES, [&] { return check_pi_edges(fn, n_pi, pe); }, "pi", "radius",
+        [&](const double *d_pe) { return shape_lanes_of(b, d_pe, n_pi, pe[n_pi]); });
 }
 
 }  // extern "C"

@@ -453,6 +453,26 @@ def _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis):
     return ctx, a, a if layout_b is layout_a else handle(layout_b)
 
 
+def _run_projected(count, layouts, cosmology, unit, table, cap=None):
+    """``count()``, a ``_lib`` call over projected cells with the edge table ``table`` of ``layouts``, with the library's two
+    refusals as ``ValueError``: more bins of a second binning than a workgroup's LDS holds -- ``cap = (n, bins, rows, planes)``,
+    the words of the message -- and a reach beyond the library's cap (``check_projected_reach``, with the redshift and the
+    radius). Anything else is raised as it came."""
+    try:
+        return count()
+    except _lib.YawhipError as err:
+        if cap is not None and "do not fit the LDS" in str(err):
+            n, bins, rows, planes = cap
+            most = re.search(rf"at most (\d+) {bins} bins", str(err)).group(1)
+            raise ValueError(f"{n} {bins} bins are too many for {np.shape(table)[1]} {rows} edges (the fine bins of the "
+                             f"configuration's resolution){planes}: at most {most} {bins} bins fit; use fewer {bins} bins or a lower "
+                             "resolution") from err
+        if "too close for the largest radius" not in str(err):
+            raise
+        check_projected_reach(layouts, cosmology, unit, table)  # the same refusal, with the redshift and the radius
+        raise
+
+
 def count_projected_pi_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
     """``count_projected_fine`` with the pairs binned in ``|chi_a - chi_b|`` by ``pi_edges`` f64[n_pi + 1]
     (``check_pi_edges``; bin 0 is ``[0, pe[1]]``, bin j ``(pe[j], pe[j + 1]]``) -> ``(W, CountStats)``, W f64[n_pi, n_cells,
@@ -460,17 +480,8 @@ def count_projected_pi_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmolog
     bins than a workgroup's LDS holds at this number of radius edges is a ``ValueError`` that states the cap; the library
     does not split a call and neither does this. No CPU fallback; the CPU tests replace this function."""
     ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
-    try:
-        return _lib.proj_count_pi(ctx, a, b, cells, r2, pi_edges)
-    except _lib.YawhipError as err:
-        if "do not fit the LDS" in str(err):
-            cap = re.search(r"at most (\d+) pi bins", str(err)).group(1)
-            raise ValueError(f"{len(pi_edges) - 1} pi bins are too many for {np.shape(r2)[1]} radius edges (the fine bins of the "
-                             f"configuration's resolution): at most {cap} pi bins fit; use fewer pi bins or a lower resolution") from err
-        if "too close for the largest radius" not in str(err):
-            raise
-        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
-        raise
+    return _run_projected(lambda: _lib.proj_count_pi(ctx, a, b, cells, r2, pi_edges), (layout_a, layout_b), cosmology, unit, r2,
+                          cap=(len(pi_edges) - 1, "pi", "radius", ""))
 
 
 def count_projected_shear_fine(dens_layout, shape_layout, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
@@ -487,18 +498,8 @@ def count_projected_shear_fine(dens_layout, shape_layout, cells, r2, *, pi_edges
     _require_shear(shape_layout)
     ctx, dens, _ = _proj_handles(dens_layout, dens_layout, cosmology, unit, sort_axis)
     shapes = _proj_shape_handle(shape_layout, ctx, cosmology, unit, sort_axis)
-    try:
-        return _lib.proj_count_shear(ctx, dens, shapes, cells, r2, pi_edges)
-    except _lib.YawhipError as err:
-        if "do not fit the LDS" in str(err):
-            cap = re.search(r"at most (\d+) pi bins", str(err)).group(1)
-            raise ValueError(f"{len(pi_edges) - 1} pi bins are too many for {np.shape(r2)[1]} radius edges (the fine bins of the "
-                             f"configuration's resolution) with three planes each: at most {cap} pi bins fit; use fewer pi bins or "
-                             "a lower resolution") from err
-        if "too close for the largest radius" not in str(err):
-            raise
-        check_projected_reach((dens_layout, shape_layout), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
-        raise
+    return _run_projected(lambda: _lib.proj_count_shear(ctx, dens, shapes, cells, r2, pi_edges), (dens_layout, shape_layout), cosmology,
+                          unit, r2, cap=(len(pi_edges) - 1, "pi", "radius", " with three planes each"))
 
 
 def _proj_shape_handle(layout, ctx, cosmology, unit, sort_axis):
@@ -540,13 +541,7 @@ def count_projected_shapes_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosm
     ctx = get_context()
     a = _proj_shape_handle(layout_a, ctx, cosmology, unit, sort_axis)
     b = a if layout_b is layout_a else _proj_shape_handle(layout_b, ctx, cosmology, unit, sort_axis)
-    try:
-        return _lib.proj_count_shapes(ctx, a, b, cells, r2, pi_edges)
-    except _lib.YawhipError as err:
-        if "too close for the largest radius" not in str(err):
-            raise
-        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
-        raise
+    return _run_projected(lambda: _lib.proj_count_shapes(ctx, a, b, cells, r2, pi_edges), (layout_a, layout_b), cosmology, unit, r2)
 
 
 def check_shape_pi_cap(n_pi: int, n_edges: int) -> None:
@@ -597,17 +592,8 @@ def count_smu_fine(layout_a, layout_b, cells, s2, *, mu_edges, cosmology, unit, 
     fallback; the CPU tests replace this function."""
     ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
     mu_edges = np.asarray(mu_edges, dtype=np.float64)
-    try:
-        return _lib.proj_count_smu(ctx, a, b, cells, s2, mu_edges * mu_edges)
-    except _lib.YawhipError as err:
-        if "do not fit the LDS" in str(err):
-            cap = re.search(r"at most (\d+) mu bins", str(err)).group(1)
-            raise ValueError(f"{len(mu_edges) - 1} mu bins are too many for {np.shape(s2)[1]} s edges (the fine bins of the "
-                             f"configuration's resolution): at most {cap} mu bins fit; use fewer mu bins or a lower resolution") from err
-        if "too close for the largest radius" not in str(err):
-            raise
-        check_projected_reach((layout_a, layout_b), cosmology, unit, s2)  # the same refusal, with the redshift and the radius
-        raise
+    return _run_projected(lambda: _lib.proj_count_smu(ctx, a, b, cells, s2, mu_edges * mu_edges), (layout_a, layout_b), cosmology, unit, s2,
+                          cap=(len(mu_edges) - 1, "mu", "s", ""))
 
 
 def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, unit, sort_axis: int = 2):
@@ -621,13 +607,7 @@ def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, un
     twice. A reach beyond the library's cap is ``check_radial_reach``'s ``ValueError`` with the object's redshift. No CPU
     fallback; the CPU tests replace this function."""
     ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
-    try:
-        return _lib.proj_count(ctx, a, b, cells, r2, pi_max)
-    except _lib.YawhipError as err:
-        if "too close for the largest radius" not in str(err):
-            raise
-        check_projected_reach((layout_a, layout_b), cosmology, unit, r2)  # the same refusal, with the redshift and the radius
-        raise
+    return _run_projected(lambda: _lib.proj_count(ctx, a, b, cells, r2, pi_max), (layout_a, layout_b), cosmology, unit, r2)
 
 
 def check_projected_reach(layouts, cosmology, unit, r2):
