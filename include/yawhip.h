@@ -839,6 +839,64 @@ int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear
                           yawhip_stats *stats);
 
 /*
+ * The two counts above BETWEEN two samples, with a signed line of sight: the planes D1D2, D1R2, R1D2 and R1R2 of
+ * xi(r_p, pi) and xi(s, mu) of two different tracers, which are not symmetric in pi and have odd multipoles
+ * (measurements.crosscorrelate_projected / crosscorrelate_multipoles with signed=True; no counterpart in
+ * the reference). Additive to ABI 6: two new symbols.
+ *
+ * Both take yawhip_proj_count_pi's arguments one for one. Handles (both of yawhip_proj_upload, nothing is uploaded again),
+ * cells (sa, sb, row, diagonal), the rows of squared radius / s edges, the reach rule, the window, the statistics, the outer
+ * (wave-wide) tests, the accumulation and the output layout [n][n_cells][n_edges - 1] are those of the unsigned siblings.
+ * Every operation is float64, rounded on its own, nothing contracted.
+ *       ps = c_b - c_a                 b_obj an object of the SECOND handle, a_obj one of the first: "b minus a", as s2 is
+ *                                      defined. The sign belongs to the handle order of the call; it does not depend on
+ *                                      which side the kernel streams. fabs(ps) is the siblings' p bit for bit, so R2, P2
+ *                                      and S2 are the siblings' values.
+ *   cells        a segment against itself has no order: a cell whose fourth entry is non-zero, or with a == b and sa == sb,
+ *                is YAWHIP_ERR_INVALID. Every cell holds every (a_obj, b_obj) once. Swapping the handles, the cells' first
+ *                two columns and the edges for their negatives in reverse order gives the planes in reverse order.
+ *
+ * yawhip_proj_count_pi_signed   R2 and the fine bin e are yawhip_proj_count's. Then
+ *       the pair counts  iff  pe[0] <= ps <= pe[n_pi]
+ *       j = the number of INNER edges pe[1 .. n_pi - 1] that are < ps     plane 0 is [pe[0], pe[1]], plane j (pe[j], pe[j + 1]]
+ *       fine_w[j][c][e] += w_a * w_b
+ *     Only the inner edges are bisected (at n_pi == 1 nothing is); the two cuts are asked first.
+ *     Consequence: over edges mirrored about 0, pe = {-q[n] .. -q[1], 0, q[1] .. q[n]}, and where no pair has ps == 0 or lies on
+ *     an edge, fine_w[n + j] + fine_w[n - 1 - j] equals plane j of yawhip_proj_count_pi at the edges q, as integers over unit
+ *     weights (a pair at ps == 0 is in plane n - 1 here; a pair at ps == -q[j] is in plane n - 1 - j, the mirror of the
+ *     unsigned plane j, where the unsigned call has p == q[j] in plane j - 1).
+ *   n_pi, pe     n_pi >= 1; pe finite and strictly ascending, of any sign: pe[0] may be negative, zero or positive (a one-
+ *                sided range). Anything else (NaN, an infinity, ties, a NULL pe): YAWHIP_ERR_INVALID.
+ *   the cap      yawhip_proj_count_pi's formula with the signed bins counted as they are: n_pi <= 104 at 13 edges, <= 25 at
+ *                51, <= 4 at 256; the same refusal.
+ *
+ * yawhip_proj_count_smu_signed  S2 and the fine bin e are yawhip_proj_count_smu's (by the UNSIGNED S2). The host passes the
+ *                        signed squares sm2[k] = copysign(mu_k mu_k, mu_k). Then
+ *       sP2 = copysign(P2, ps)
+ *       j = the number of INNER edges k = 1 .. n_mu - 1 with fl(sm2[k] S2) < sP2
+ *                                                                   plane 0 is mu in [-1, mu_1], plane j is (mu_j, mu_j+1]
+ *       fine_w[j][c][e] += w_a * w_b
+ *     sm2 ascends, S2 >= 0 and rounding is monotone, so fl(sm2[k] S2) ascends with k and the predicate holds for a prefix of
+ *     the edges whatever the sign of sP2 (for ps < 0 the negative edges, whose squares descend; for ps > 0 every negative
+ *     edge and then a prefix of the others). sm2[0] and sm2[n_mu] are never read: there is no cut.
+ *     yawhip_proj_count_smu is the special case in which all signs are positive: the predicate then reads fl(m2[k] S2) < P2.
+ *     Consequence: over edges mirrored about 0 and where no pair has ps == 0 and no product fl(m2[k] S2) equals P2,
+ *     fine_w[n + j] + fine_w[n - 1 - j] equals plane j of yawhip_proj_count_smu at the edges m2, as integers over unit weights.
+ *   n_mu, sm2    n_mu >= 1; sm2[0] exactly -1 and sm2[n_mu] exactly 1; strictly ascending -- a sequence of mu that does not
+ *                ascend strictly after squaring is refused, as yawhip_proj_count_smu refuses it. Anything else (NaN, ties, a
+ *                NULL sm2): YAWHIP_ERR_INVALID.
+ *   the cap, the reach   yawhip_proj_count_smu's.
+ *   checks       those of the sibling in its order, with the refusal of diagonal cells after the edges.
+ * Kernels: the siblings' walks without diagonal cells; the lane carries the lower cut pe[0] next to the upper one.
+ */
+int yawhip_proj_count_pi_signed(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells,
+                                const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi,
+                                const double *pe, double *fine_w, yawhip_stats *stats);
+int yawhip_proj_count_smu_signed(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells,
+                                 const int32_t *cells, int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu,
+                                 const double *sm2, double *fine_w, yawhip_stats *stats);
+
+/*
  * Projected position-shape sums: the tangential and cross ellipticity of the shapes of one catalogue about the objects of
  * another, binned in each PAIR's own radius and in the line-of-sight separation -- the planes of the intrinsic-alignment
  * measurement w_g+(r_p) and its null test w_gx(r_p) (measurements.crosscorrelate_alignment; no

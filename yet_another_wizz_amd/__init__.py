@@ -20,10 +20,12 @@ from .catalog import Catalog, InconsistentPatchesError, Patch
 from .config import Configuration
 from .coordinates import AngularCoordinates, AngularDistances
 from .corrdata import CorrData, SampledData
-from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc
+from .corrfunc import (AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc,
+                       SignedMultipoleCorrFunc, SignedProjectedCorrFunc)
 from .measurements import (PatchLinkage, autocorrelate, autocorrelate_alignment, autocorrelate_multipoles, autocorrelate_projected, autocorrelate_scalar, autocorrelate_shear, compute_scalar_normalisation,
                            correlate_shear_tomographic, crosscorrelate, crosscorrelate_scalar, crosscorrelate_scalar_map,
-                           crosscorrelate_alignment, crosscorrelate_delta_sigma, crosscorrelate_shear)
+                           crosscorrelate_alignment, crosscorrelate_delta_sigma, crosscorrelate_multipoles, crosscorrelate_projected,
+                           crosscorrelate_shear)
 from . import healpix, patches, randoms
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 from .redshifts import HistData, RedshiftData
@@ -53,6 +55,8 @@ __all__ = [
     "SampledData",
     "ScalarCorrFunc",
     "ShapeShapeCorrFunc",
+    "SignedMultipoleCorrFunc",
+    "SignedProjectedCorrFunc",
     "autocorrelate",
     "autocorrelate_alignment",
     "autocorrelate_multipoles",
@@ -66,6 +70,8 @@ __all__ = [
     "crosscorrelate_scalar",
     "crosscorrelate_scalar_map",
     "crosscorrelate_delta_sigma",
+    "crosscorrelate_multipoles",
+    "crosscorrelate_projected",
     "crosscorrelate_shear",
     "healpix",
     "patches",

@@ -75,6 +75,8 @@ ABI_SYMBOLS = (
     "yawhip_proj_upload_shapes",
     "yawhip_proj_count_shear",
     "yawhip_proj_count_shapes",
+    "yawhip_proj_count_pi_signed",
+    "yawhip_proj_count_smu_signed",
 )
 
 
@@ -313,6 +315,8 @@ def load_library() -> ctypes.CDLL:
                                               _i64p, ctypes.c_int32, ctypes.POINTER(_vp)]
     lib.yawhip_proj_count_shear.argtypes = lib.yawhip_proj_count_pi.argtypes
     lib.yawhip_proj_count_shapes.argtypes = lib.yawhip_proj_count_pi.argtypes
+    lib.yawhip_proj_count_pi_signed.argtypes = lib.yawhip_proj_count_pi.argtypes
+    lib.yawhip_proj_count_smu_signed.argtypes = lib.yawhip_proj_count_pi.argtypes
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("yawhip_last_error", "yawhip_kmeans_close"):
@@ -891,7 +895,7 @@ class ProjShapesHandle(ShearSources):
 
 def _shear_counts(symbol: str, n_planes: int, handles, table, thresholds, *extra, width: int = 2,
                   rows: str = "thresholds must be [n_bins, n_edges]", stacked: bool = False):
-    """What the ten counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
+    """What the twelve counts share: ``symbol(*handles, n, table, R, E, thresholds, *extra, n_planes output planes, stats)`` with
     ``table`` int32[n, width] -- jobs (width 2: a cell per job and row, planes f64[n, R, E-1]) or cells (wider: a cell per
     entry, planes f64[n, E-1]) -- and ``thresholds`` f64[R, E] (``rows``: what to say of another shape). Returns the planes
     and the ``CountStats``. ``stacked``: the symbol takes the planes as ONE array f64[n_planes, ...], which is what comes
@@ -971,6 +975,31 @@ def proj_count_smu(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, m2):
         raise ValueError("m2 must be [n_mu + 1]")
     n_mu = len(m2) - 1
     return _shear_counts("yawhip_proj_count_smu", max(n_mu, 0), (ctx._h, a._h, b._h), cells, s2, n_mu, _ptr(m2, _dp), width=4,
+                         rows="s2 must be [n_rows, n_edges]", stacked=True)
+
+
+def proj_count_pi_signed(ctx: Context, a: ProjHandle, b: ProjHandle, cells, r2, pi_edges):
+    """Run ``yawhip_proj_count_pi_signed``: ``proj_count_pi`` between two samples with the pairs binned in the SIGNED
+    ``ps = c_b - c_a`` (object of ``b`` minus object of ``a``: the sign belongs to the handle order); ``pi_edges`` f64[n_pi + 1]
+    finite and strictly ascending, of any sign; a pair counts iff ``pe[0] <= ps <= pe[n_pi]``, bin 0 is ``[pe[0], pe[1]]``, bin j
+    ``(pe[j], pe[j + 1]]``. No cell may be diagonal or pair a segment of one handle with itself. Returns ``(W, CountStats)``, W
+    f64[n_pi, n_cells, E-1]; over edges mirrored about 0, planes ``n + j`` and ``n - 1 - j`` sum to ``proj_count_pi``'s plane
+    j (exactly, for unit weights and no pair at ``ps == 0`` or on an edge). The cap is ``proj_count_pi``'s."""
+    (fine,), stats = _pi_counts("yawhip_proj_count_pi_signed", 1, ctx, a, b, cells, r2, pi_edges)
+    return fine, stats
+
+
+def proj_count_smu_signed(ctx: Context, a: ProjHandle, b: ProjHandle, cells, s2, sm2):
+    """Run ``yawhip_proj_count_smu_signed``: ``proj_count_smu`` between two samples with mu signed by ``ps = c_b - c_a``. The
+    edges ``sm2`` f64[n_mu + 1] are the signed squares ``copysign(mu mu, mu)``, from exactly -1 to exactly 1 and strictly
+    ascending: a pair is in the plane j that counts the inner edges k with ``fl(sm2[k] S2) < copysign(P2, ps)``. No cell may
+    be diagonal or pair a segment of one handle with itself. Returns ``(W, CountStats)``, W f64[n_mu, n_cells, E-1]. The cap
+    is ``proj_count_smu``'s."""
+    sm2 = np.ascontiguousarray(sm2, dtype=np.float64)
+    if sm2.ndim != 1:
+        raise ValueError("sm2 must be [n_mu + 1]")
+    n_mu = len(sm2) - 1
+    return _shear_counts("yawhip_proj_count_smu_signed", max(n_mu, 0), (ctx._h, a._h, b._h), cells, s2, n_mu, _ptr(sm2, _dp), width=4,
                          rows="s2 must be [n_rows, n_edges]", stacked=True)
 
 

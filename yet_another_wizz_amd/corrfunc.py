@@ -7,7 +7,7 @@ import numpy as np
 from .corrdata import CorrData
 from .paircounts import NormalisedCounts, NormalisedScalarCounts
 
-__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "AlignmentCorrFunc", "ShapeShapeCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
+__all__ = ["CorrFunc", "ScalarCorrFunc", "ProjectedCorrFunc", "MultipoleCorrFunc", "SignedProjectedCorrFunc", "SignedMultipoleCorrFunc", "AlignmentCorrFunc", "ShapeShapeCorrFunc", "EstimatorError", "davis_peebles", "landy_szalay", "scalar_correlation"]
 
 
 class EstimatorError(Exception):
@@ -339,6 +339,171 @@ class MultipoleCorrFunc:
 
     def patches_subset(self, item):
         return type(self)(self.mu_edges, [cf.patches_subset(item) for cf in self.mu_bins])
+
+
+class _SignedBinnedCorrFunc:
+    """What the two results with a signed line of sight share: ``edges`` f64[n + 1], finite and strictly ascending with
+    ``edges[0] == -edges[-1]``, and ``n`` ``CorrFunc`` of the same kinds on one binning and one set of patches -- bin 0 holds
+    ``[e[0], e[1]]``, bin j ``(e[j], e[j + 1]]``. The sign is that of the count: second sample minus first. A subclass names
+    the second binning (``_name``: its edges and bins are the attributes ``<name>_edges``, ``<name>_bins`` and the keys of
+    ``to_dict``), checks the ends of the edges and says what ``folded()`` builds."""
+
+    __slots__ = ("_edges", "_bins")
+    _name = ""
+    _folded_type = None
+
+    def __init__(self, edges, bins) -> None:
+        name = self._name
+        edges = np.array(edges, dtype=np.float64)
+        bins = tuple(bins)
+        if edges.ndim != 1 or len(edges) != len(bins) + 1 or len(bins) < 1:
+            raise ValueError(f"'{name}_edges' must hold one edge more than there are {name} bins, and there is at least one bin")
+        if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0.0) or edges[0] != -edges[-1]:
+            raise ValueError(f"'{name}_edges' must be finite, ascend strictly and span zero symmetrically at the ends")
+        self._check_ends(edges)
+        for cf in bins:
+            if type(cf) is not CorrFunc:
+                raise TypeError(f"the {name} bins must be of type {CorrFunc}")
+            bins[0].is_compatible(cf, require=True)
+            if cf.to_dict().keys() != bins[0].to_dict().keys():
+                raise ValueError(f"the {name} bins must hold the same kinds of pair counts")
+        edges.setflags(write=False)
+        self._edges = edges
+        self._bins = bins
+
+    def _check_ends(self, edges) -> None:
+        pass
+
+    binning = property(lambda self: self._bins[0].binning)
+    auto = property(lambda self: self._bins[0].auto)
+    num_patches = property(lambda self: self._bins[0].num_patches)
+    num_bins = property(lambda self: self._bins[0].num_bins)
+
+    def to_dict(self) -> dict:
+        return {f"{self._name}_edges": self._edges.copy(), f"{self._name}_bins": [cf.to_dict() for cf in self._bins]}
+
+    @classmethod
+    def from_dict(cls, state: dict):
+        return cls(state[f"{cls._name}_edges"], [CorrFunc.from_dict(counts) for counts in state[f"{cls._name}_bins"]])
+
+    def __eq__(self, other) -> bool:
+        if type(self) is not type(other):
+            return NotImplemented
+        return np.array_equal(self._edges, other._edges) and self._bins == other._bins
+
+    def is_compatible(self, other, *, require: bool = False) -> bool:
+        if type(self) is not type(other):
+            if require:
+                raise TypeError(f"{type(other)} is not compatible with {type(self)}")
+            return False
+        if not np.array_equal(self._edges, other._edges):
+            if require:
+                raise ValueError(f"the {self._name} edges differ")
+            return False
+        return self._bins[0].is_compatible(other._bins[0], require=require)
+
+    def sample_xi(self) -> list:
+        """The correlation function per signed bin: ``CorrFunc.sample()`` of each -- Landy-Szalay with RR, else
+        Davis-Peebles -- for the data and every jackknife sample."""
+        return [cf.sample() for cf in self._bins]
+
+    def _weighted_sum(self, weights, factor: float) -> CorrData:
+        """``factor * sum_j weights[j] xi_j``, summed in the order of the bins, data and jackknife samples separately."""
+        data, samples = 0.0, 0.0
+        for weight, xi in zip(weights, self.sample_xi()):
+            data, samples = data + weight * xi.data, samples + weight * xi.samples
+        return CorrData(self.binning, factor * data, factor * samples)
+
+    def folded(self):
+        """The unsigned result over the counts of mirrored bins summed: with ``2 m`` bins whose edges are symmetric about 0,
+        folded bin j holds bin ``m + j`` plus bin ``m - 1 - j`` on the bins' one normalisation, over the edges ``e[m:]``.
+        Possible only where the edges are symmetric about 0 and 0 is an edge (``ValueError`` otherwise)."""
+        edges, m = self._edges, len(self._bins) // 2
+        if len(self._bins) % 2 or edges[m] != 0.0 or not np.array_equal(edges, -edges[::-1]):
+            raise ValueError(f"folding needs {self._name} edges that are symmetric about 0 with 0 among them")
+        bins = []
+        for upper, lower in zip(self._bins[m:], self._bins[:m][::-1]):
+            mirrored = lower.to_dict()
+            bins.append(CorrFunc.from_dict({kind: NormalisedCounts(counts.counts + mirrored[kind].counts, counts.sum_weights)
+                                            for kind, counts in upper.to_dict().items()}))
+        return self._folded_type(edges[m:], bins)
+
+    def bins_subset(self, item):
+        return type(self)(self._edges, [cf.bins_subset(item) for cf in self._bins])
+
+    def patches_subset(self, item):
+        return type(self)(self._edges, [cf.patches_subset(item) for cf in self._bins])
+
+
+class SignedProjectedCorrFunc(_SignedBinnedCorrFunc):
+    """The pair counts of one scale of the projected cross-correlation of two samples binned in the SIGNED line-of-sight
+    separation ``pi = chi_2 - chi_1`` (``crosscorrelate_projected(signed=True)``; no counterpart in the reference):
+    ``pi_edges`` f64[n + 1], strictly ascending from ``-pi_max`` to ``pi_max`` and symmetric inside or not, and ``pi_bins``, a
+    tuple of ``n`` ``CorrFunc(dd, dr, rd, rr)`` -- bin 0 holds ``[pe[0], pe[1]]``, bin j ``(pe[j], pe[j + 1]]``; positive where
+    the object of the second sample lies behind.
+
+    ``sample_xi()`` is ``xi(r_p, pi_j)`` per bin, ``sample()`` the summed ``w_p(r_p) = sum_j dpi_j xi_j`` -- the bins cover
+    both signs, so there is no factor 2 -- and ``folded()`` the ``ProjectedCorrFunc`` of ``signed=False``. An empty RR (DR)
+    gives NaN as in ``ProjectedCorrFunc``. ``to_dict`` / ``from_dict``, ``==``, ``is_compatible`` and the bin and patch
+    subsets go bin by bin through ``CorrFunc``'s."""
+
+    __slots__ = ()
+    _name = "pi"
+    _folded_type = ProjectedCorrFunc
+
+    pi_edges = property(lambda self: self._edges)
+    pi_bins = property(lambda self: self._bins)
+    num_pi = property(lambda self: len(self._bins))
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(num_pi={self.num_pi}, pi_max={self.pi_edges[-1]}, pi_bins[0]={self.pi_bins[0]!r})"
+
+    def sample(self) -> CorrData:
+        """``w_p = sum_j dpi_j xi_j`` over the signed bins; errors and covariance are those of the summed samples."""
+        return self._weighted_sum(np.diff(self.pi_edges), 1.0)
+
+
+class SignedMultipoleCorrFunc(_SignedBinnedCorrFunc):
+    """The pair counts of one scale of the redshift-space cross-correlation of two samples binned in the SIGNED
+    ``mu = pi / s``, ``pi = chi_2 - chi_1`` (``crosscorrelate_multipoles(signed=True)``; no counterpart in the reference):
+    ``mu_edges`` f64[n + 1], strictly ascending from -1 to 1, and ``mu_bins``, a tuple of ``n`` ``CorrFunc(dd, dr, rd, rr)`` --
+    bin 0 holds ``[-1, mu_1]``, bin j ``(mu_j, mu_{j+1}]``.
+
+    ``sample_xi()`` is ``xi(s, mu_j)`` per bin, ``sample(ell)`` the multipole ``xi_ell(s)`` of EVERY integer ``ell`` in
+    0 ... 8 -- the odd ones are what the sign is kept for -- ``sample_multipoles()`` several of them and ``folded()`` the
+    ``MultipoleCorrFunc`` of ``signed=False``. The rest is ``SignedProjectedCorrFunc``'s."""
+
+    __slots__ = ()
+    _name = "mu"
+    _folded_type = MultipoleCorrFunc
+
+    mu_edges = property(lambda self: self._edges)
+    mu_bins = property(lambda self: self._bins)
+    num_mu = property(lambda self: len(self._bins))
+
+    def _check_ends(self, edges) -> None:
+        if edges[0] != -1.0 or edges[-1] != 1.0:
+            raise ValueError("'mu_edges' must start at -1 and end at 1")
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(num_mu={self.num_mu}, mu_bins[0]={self.mu_bins[0]!r})"
+
+    def legendre_weights(self, ell: int) -> np.ndarray:
+        """``I_ell,j = int_{mu_j}^{mu_{j+1}} P_ell(mu) dmu`` per mu bin, f64[n_mu], from the antiderivative of the Legendre
+        polynomial, for every integer ``ell`` in 0 ... 8."""
+        if isinstance(ell, (bool, np.bool_)) or not isinstance(ell, (int, np.integer)) or ell < 0 or ell > 8:
+            raise ValueError(f"ell must be an integer in 0 ... 8, not {ell!r}")
+        primitive = np.polynomial.legendre.Legendre.basis(int(ell)).integ()
+        return np.diff(primitive(self.mu_edges))
+
+    def sample(self, ell: int = 0) -> CorrData:
+        """``xi_ell(s) = (2 ell + 1) / 2 sum_j xi_j I_ell,j`` (``legendre_weights``): the usual
+        ``(2 ell + 1) / 2 int_{-1}^{1} xi(s, mu) P_ell(mu) dmu`` with ``xi`` constant per bin."""
+        return self._weighted_sum(self.legendre_weights(ell), (2 * int(ell) + 1) / 2.0)
+
+    def sample_multipoles(self, ells=(0, 1, 2, 3, 4)) -> tuple:
+        """``sample(ell)`` for every ``ell`` of ``ells``."""
+        return tuple(self.sample(ell) for ell in ells)
 
 
 class AlignmentCorrFunc:

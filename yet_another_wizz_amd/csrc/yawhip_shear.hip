@@ -1,4 +1,4 @@
-// yawhip_shear.hip -- the counts over the handles of yawhip_shear_upload.hip (yawhip_shear_sources, yawhip_shear.h), ten entry
+// yawhip_shear.hip -- the counts over the handles of yawhip_shear_upload.hip (yawhip_shear_sources, yawhip_shear.h), twelve entry
 // points; include/yawhip.h has the contracts, product by product:
 //   yawhip_shear_count          tangential and cross shear of sources around binned lenses          DESIGN.md section 15
 //   yawhip_shear_auto_count     shear-shear sums inside the redshift bins of one catalogue                              16
@@ -10,8 +10,10 @@
 //   yawhip_proj_count_smu       ... binned in the redshift-space separation s and in mu = pi / s instead                23
 //   yawhip_proj_count_shear     position-shape: tangential and cross ellipticity per radius and pi bin                  24
 //   yawhip_proj_count_shapes    shape-shape: both ends rotated to the great circle through the pair                     25
+//   yawhip_proj_count_pi_signed   yawhip_proj_count_pi between two samples, the line of sight signed: pi = c_b - c_a    27
+//   yawhip_proj_count_smu_signed  yawhip_proj_count_smu between two samples, mu signed with it                          27
 //
-// All are ONE streaming walk, shear_walk<P>, under ten thin entry kernels. One workgroup of 256 threads owns one cell. Lanes
+// All are ONE streaming walk, shear_walk<P>, under twelve thin entry kernels. One workgroup of 256 threads owns one cell. Lanes
 // hold 256 objects of the cell's lane segment in registers (parked far away where the tile is padded); the cell's streamed
 // segment goes through LDS 256 objects at a time, double-buffered, per lane tile only the window of objects whose sort key
 // lies within the chord sqrt(t_max) of the tile's keys. The hot loop is the 8-flop separation of k_count,
@@ -37,6 +39,8 @@
 //   RedshiftSpace (k_count_smu)                   CellTable  S2 = R2 + P2 StreamedProj   no cut      StagedEdges<1>: W per mu bin
 //   ProjectedShear (k_count_projected_shear)      CellTable  RadiusSeam   StreamedProj   ShapeLanes  StagedEdges<3>: T, X, W
 //   ProjectedShapes (k_count_projected_shapes)    CellTable  RadiusSeam   ObjS, ShapeView ShapeLanes StagedEdges<4>: PP, XX, PX, W
+//   ProjectedPiSigned (k_count_projected_pi_signed)  CellTable  RadiusSeam  StreamedProj  SignedCutLane  StagedEdges<1>: W per signed pi bin
+//   RedshiftSpaceSigned (k_count_smu_signed)      CellTable  S2 = R2 + P2 StreamedProj   no cut      StagedEdges<1>: W per signed mu bin
 // A cell is diagonal iff it pairs one segment of one handle with itself; it then walks only partners with a LARGER index,
 // which rests on every term of its policy being bit-symmetric under swapping a and b (stated at the term).
 //
@@ -566,6 +570,77 @@ struct RedshiftSpace : ProjectedCells, StreamedProj, StagedEdges<1> {
     }
 };
 
+// ---- The two counts between two samples with a SIGNED line of sight. The walk streams the call's
+// first handle and keeps its second in the lanes, so with a the lane and b the streamed object of add() the signed separation
+// "object of the second handle minus object of the first" is
+//   ps = a.c - b.c,
+// whatever the cells pair: the sign belongs to the handle order of the call. fabs(ps) is the siblings' p bit for bit -- the
+// same difference, its sign cleared -- so R2, P2 and S2 are theirs. ps is NOT symmetric under a <-> b: a segment against
+// itself has no order and the host refuses it, there are no diagonal cells.
+
+// ... the lanes of the signed pi count: ProjPiLanes with the first edge by value besides, the lower cut
+struct ProjPiSignedLanes : ProjPiLanes {
+    double pmin;
+};
+struct SignedLane : ProjLane {  // the lower cut next to the upper one (call-wide: scalar registers)
+    double lo;
+};
+struct SignedCutLane {
+    using LaneT = SignedLane;
+    static __device__ __forceinline__ SignedLane lane(const ProjPiSignedLanes &src, int64_t, bool, const Lane &a) {
+        return SignedLane{{a, src.pmax, a.g1, a.g2, 0}, src.pmin};
+    }
+};
+
+// ProjectedPi with ps in the place of p: the edges pe[0 .. n] are of any sign, the pair counts iff pe[0] <= ps <= pe[n], plane
+// 0 is [pe[0], pe[1]], plane j is (pe[j], pe[j + 1]]. The two cuts are asked first, against the lane's copies; the loop is
+// StagedEdges::plane's, one shape with a start past the edges, and bisects only the inner edges pe[1 .. n - 1] (at one bin
+// nothing). A copy of that loop and not a change to it: the siblings' code stays what it was.
+struct ProjectedPiSigned : ProjectedCells, RadiusSeam, StreamedProj, SignedCutLane, StagedEdges<1> {
+    using Lanes = ProjPiSignedLanes;
+    static constexpr bool DIAGONAL = false;
+    static __device__ __forceinline__ int signed_plane(const double *pe, int n_pi, double ps, double lo, double pmax) {
+        int j = (ps < lo || pmax < ps) ? n_pi : 0, hi = n_pi - 1;
+        while (j < hi) {
+            const int mid = (j + hi) >> 1;
+            if (pe[mid + 1] < ps) j = mid + 1; else hi = mid;
+        }
+        return j;
+    }
+    static __device__ void add(const SignedLane &a, const ObjP &b, double *wh, int e, int nf, const Staged &st, double) {
+        const int j = signed_plane(st.ext, st.planes, a.c - b.c, a.lo, a.cut);
+        if (j < st.planes) atomicAdd(&wh[j * nf + e], a.w * b.w);
+    }
+};
+
+// RedshiftSpace with the sign of ps on mu: the staged edges are sm2[k] = copysign(mu_k mu_k, mu_k), sm2[0] == -1 and
+// sm2[n_mu] == 1 never read, and with sP2 = copysign(P2, ps) the plane j is the number of INNER edges k = 1 .. n_mu - 1 with
+//   fl(sm2[k] S2) < sP2                       plane 0 is mu in [-1, mu_1], plane j is (mu_j, mu_j+1]
+// sm2 ascends, S2 >= 0 and rounding is monotone, so fl(sm2[k] S2) ascends with k (not strictly) and the predicate, one
+// comparison against a number that does not depend on k, holds for a prefix of the edges whatever the sign of sP2: for
+// ps < 0 it reads fl(|sm2[k]| S2) > P2 on the negative edges, whose squares descend, and fails on every edge >= 0; for
+// ps > 0 every negative edge holds (a product <= -0 against P2 > 0; at P2 == 0 a product -0 fails as 0 < 0 does, and every
+// later one with it) and then RedshiftSpace's prefix of the others. The bisection by descending powers of two is
+// RedshiftSpace's, and so are seam, outer test, window and the absence of a cut: that kernel is the special case in which
+// every sign is positive.
+struct RedshiftSpaceSigned : RedshiftSpace {
+    static constexpr bool DIAGONAL = false;
+    static __device__ void add(const ProjLane &a, const ObjP &b, double *wh, int e, int nf, const Staged &st, double S2) {
+        const double *const sm2 = st.ext;
+        const int n_mu = st.planes;
+        const double ps = a.c - b.c;
+        const double p = fabs(ps);
+        const double sP2 = copysign(p * p, ps);
+        int j = 0, step = st.top;
+        do {
+            const int k = j + step;
+            if ((unsigned)(k - 1) < (unsigned)(n_mu - 1) && sm2[k] * S2 < sP2) j = k;
+            step >>= 1;
+        } while (step > 0);
+        atomicAdd(&wh[j * nf + e], a.w * b.w);
+    }
+};
+
 // The tangential and cross ellipticity of shapes about the objects of a projected handle, binned as ProjectedPi bins the pair
 // (DESIGN.md section 24). The streamed side is the projected handle; two handles of different kinds never pair a segment
 // with itself: no diagonal cells. Only a pair that counts (j < n_pi) gets Tangential's rotation, term for term: T is the
@@ -679,6 +754,9 @@ static_assert(max_bins<ProjectedShapes>(13) == 21 && max_bins<ProjectedShapes>(5
 static_assert(lds_bytes<RedshiftSpace>(13, 104) == lds_bytes<ProjectedPi>(13, 104) && lds_bytes<RedshiftSpace>(51, 25) == lds_bytes<ProjectedPi>(51, 25) &&
                   lds_bytes<RedshiftSpace>(MAX_EDGES, 4) == lds_bytes<ProjectedPi>(MAX_EDGES, 4),
               "RedshiftSpace: its carve-up is ProjectedPi's, so that ProjectedPi's cap is the cap on n_mu too (DESIGN.md section 23)");
+static_assert(max_bins<ProjectedPiSigned>(MAX_EDGES) == 4 && max_bins<ProjectedPiSigned>(13) == 104 && max_bins<ProjectedPiSigned>(51) == 25 &&
+                  max_bins<RedshiftSpaceSigned>(MAX_EDGES) == 4 && max_bins<RedshiftSpaceSigned>(13) == 104 && max_bins<RedshiftSpaceSigned>(51) == 25,
+              "the signed counts: the siblings' carve-up and cap with the signed bins counted as they are (include/yawhip.h and DESIGN.md section 27 quote it)");
 static_assert(lds_bytes<Tangential>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<ShearShear>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<ShearPair>(MAX_EDGES) <= LDS_LIMIT && lds_bytes<DeltaSigma>(MAX_EDGES) <= LDS_LIMIT &&
                   lds_bytes<DeltaSigmaRadial>(MAX_EDGES) <= LDS_LIMIT &&  // (59 296: 2 * 256 * 64 + 2048 + 4 * 3 * 255 * 8)
@@ -879,6 +957,22 @@ __global__ __launch_bounds__(WG) void k_count_smu(ShearView a, SmuLanes b, const
                                                   const double *__restrict__ s2, const double *__restrict__ rwin, int64_t n_cells,
                                                   double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
     shear_walk<RedshiftSpace>(a, b, cells, 0, n_edges, s2, rwin, n_cells, out, evaluated);
+}
+
+// out: [n_pi][n_cells][E-1] (W per signed pi bin); as k_count_projected_pi without diagonal cells, b with the call's signed
+// edges and the first of them besides the last
+__global__ __launch_bounds__(WG) void k_count_projected_pi_signed(ShearView a, ProjPiSignedLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                                  const double *__restrict__ r2, const double *__restrict__ rwin, int64_t n_cells,
+                                                                  double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
+    shear_walk<ProjectedPiSigned>(a, b, cells, 0, n_edges, r2, rwin, n_cells, out, evaluated);
+}
+
+// out: [n_mu][n_cells][E-1] (W per signed mu bin); as k_count_smu without diagonal cells, b with the call's signed squared
+// mu edges
+__global__ __launch_bounds__(WG) void k_count_smu_signed(ShearView a, SmuLanes b, const int32_t *__restrict__ cells, int n_edges,
+                                                         const double *__restrict__ s2, const double *__restrict__ rwin, int64_t n_cells,
+                                                         double *__restrict__ out, unsigned long long *__restrict__ evaluated) {
+    shear_walk<RedshiftSpaceSigned>(a, b, cells, 0, n_edges, s2, rwin, n_cells, out, evaluated);
 }
 
 // out: [3][n_pi][n_cells][E-1] (T, X, W per pi bin); cells: [n_cells][4] (CellTable, no diagonal ones); the projected
@@ -1175,6 +1269,37 @@ int check_mu_edges(const char *fn, int32_t n_mu, const double *m2) {
     return YAWHIP_OK;
 }
 
+// the signed pi edges pe[n_pi + 1]: of any sign, every one finite
+int check_signed_pi_edges(const char *fn, int32_t n_pi, const double *pe) {
+    if (n_pi < 1 || !pe) return fail(YAWHIP_ERR_INVALID, "%s: n_pi must be >= 1 and pe not NULL (n_pi=%d)", fn, n_pi);
+    if (!std::isfinite(pe[0])) return fail(YAWHIP_ERR_INVALID, "%s: the signed pi edges must be finite and strictly ascending (edge 0)", fn);
+    for (int j = 1; j <= n_pi; ++j)  // (a NaN fails either comparison)
+        if (!(pe[j] > pe[j - 1]) || !std::isfinite(pe[j]))
+            return fail(YAWHIP_ERR_INVALID, "%s: the signed pi edges must be finite and strictly ascending (edge %d)", fn, j);
+    return YAWHIP_OK;
+}
+
+// the signed squared mu edges sm2[n_mu + 1] = copysign(mu mu, mu)
+int check_signed_mu_edges(const char *fn, int32_t n_mu, const double *sm2) {
+    if (n_mu < 1 || !sm2) return fail(YAWHIP_ERR_INVALID, "%s: n_mu must be >= 1 and sm2 not NULL (n_mu=%d)", fn, n_mu);
+    if (sm2[0] != -1.0 || sm2[n_mu] != 1.0) return fail(YAWHIP_ERR_INVALID, "%s: the signed squared mu edges must start at -1 and end at 1", fn);
+    for (int j = 1; j <= n_mu; ++j)  // (a NaN fails the comparison; between -1 and 1 ascending edges are finite)
+        if (!(sm2[j] > sm2[j - 1]))
+            return fail(YAWHIP_ERR_INVALID, "%s: the signed squared mu edges must be finite and strictly ascending (edge %d)", fn, j);
+    return YAWHIP_OK;
+}
+
+// the cells of a signed count: a segment against itself has no order, so no cell is diagonal, marked or not (the segments'
+// range is check_proj_cells's to check; n_cells > 0 has cells != NULL by check_handles)
+int check_ordered_cells(const char *fn, const yawhip_shear_sources *a, const yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells) {
+    for (int c = 0; c < n_cells; ++c) {
+        const int32_t *cell = cells + 4 * (size_t)c;
+        if (cell[3] != 0 || (a == b && cell[0] == cell[1]))
+            return fail(YAWHIP_ERR_INVALID, "%s: cell %d pairs a segment with itself or is marked diagonal: a signed count has no such cell", fn, c);
+    }
+    return YAWHIP_OK;
+}
+
 // the largest n_edges at which one bin of P's second binning still fits (the cap refusal names it where no number of bins does)
 template <class P>
 constexpr int max_edges_at_one_bin() {
@@ -1379,6 +1504,42 @@ int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear
         PROJECTED, NOT_PROJECTED, PROJECTED, NOT_PROJECTED, [&] { return check_mu_edges(fn, n_mu, m2); }, "mu", "s",
         [&](const double *d_m2) {
             int step = 0;  // the largest power of two <= n_mu - 1: the first step of the kernel's bisection of the inner edges
+            for (int two = 1; two <= n_mu - 1; two *= 2) step = two;
+            return SmuLanes{view_of(b), d_m2, n_mu, step};
+        });
+}
+
+// yawhip_proj_count_pi with the signed edges; the first of them goes by value next to the last: the two cuts
+int yawhip_proj_count_pi_signed(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                                int32_t n_rows, int32_t n_edges, const double *r2, int32_t n_pi, const double *pe, double *fine_w,
+                                yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_pi_signed";
+    return count_projected<ProjectedPiSigned>(
+        k_count_projected_pi_signed,
+        Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, r2, {fine_w}, stats, n_pi, pe}, b, PROJECTED,
+        NOT_PROJECTED, PROJECTED, NOT_PROJECTED,
+        [&] {
+            if (const int rc = check_signed_pi_edges(fn, n_pi, pe)) return rc;
+            return check_ordered_cells(fn, a, b, n_cells, cells);
+        },
+        "pi", "radius", [&](const double *d_pe) { return ProjPiSignedLanes{{view_of(b), d_pe, n_pi, pe[n_pi]}, pe[0]}; });
+}
+
+// yawhip_proj_count_smu with the signed squared edges: |sm2| <= 1, so R2 <= S2 and the reach rule hold as they do there
+int yawhip_proj_count_smu_signed(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear_sources *b, int32_t n_cells, const int32_t *cells,
+                                 int32_t n_rows, int32_t n_edges, const double *s2, int32_t n_mu, const double *sm2, double *fine_w,
+                                 yawhip_stats *stats) {
+    const char *fn = "yawhip_proj_count_smu_signed";
+    return count_projected<RedshiftSpaceSigned>(
+        k_count_smu_signed, Call{fn, std::chrono::steady_clock::now(), ctx, a, n_cells, CELLS, cells, n_rows, n_edges, s2, {fine_w}, stats, n_mu, sm2},
+        b, PROJECTED, NOT_PROJECTED, PROJECTED, NOT_PROJECTED,
+        [&] {
+            if (const int rc = check_signed_mu_edges(fn, n_mu, sm2)) return rc;
+            return check_ordered_cells(fn, a, b, n_cells, cells);
+        },
+        "mu", "s",
+        [&](const double *d_m2) {
+            int step = 0;  // the largest power of two <= n_mu - 1, as yawhip_proj_count_smu
             for (int two = 1; two <= n_mu - 1; two *= 2) step = two;
             return SmuLanes{view_of(b), d_m2, n_mu, step};
         });

@@ -15,7 +15,7 @@ import re
 from . import _lib
 from .parallel import local_device_index, world
 
-__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "count_projected_fine", "count_projected_pi_fine", "count_projected_shear_fine", "count_projected_shapes_fine", "max_shape_pi_bins", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
+__all__ = ["get_context", "device_catalog", "count_fine", "count_shear_fine", "count_shear_auto_fine", "count_shear_pair_fine", "count_dsigma_fine", "dsigma_columns", "count_dsigma_radial_fine", "dsigma_radial_columns", "radial_kind", "radial_reach", "check_radial_reach", "proj_columns", "check_proj_redshifts", "check_pi_max", "check_pi_edges", "check_mu_edges", "check_signed_pi_edges", "check_signed_mu_edges", "count_projected_pi_signed_fine", "count_smu_signed_fine", "count_projected_fine", "count_projected_pi_fine", "count_projected_shear_fine", "count_projected_shapes_fine", "max_shape_pi_bins", "count_smu_fine", "check_projected_reach", "count_dense", "count_dense_batch", "job_work", "assign_patches", "kmeans_open", "draw_box_randoms", "draw_healpix_randoms",
            "healpix_map", "healpix_pixels", "redshift_histogram", "scalar_segment_sums", "release", "default_kernel"]
 
 _contexts: dict = {}
@@ -594,6 +594,71 @@ def count_smu_fine(layout_a, layout_b, cells, s2, *, mu_edges, cosmology, unit, 
     mu_edges = np.asarray(mu_edges, dtype=np.float64)
     return _run_projected(lambda: _lib.proj_count_smu(ctx, a, b, cells, s2, mu_edges * mu_edges), (layout_a, layout_b), cosmology, unit, s2,
                           cap=(len(mu_edges) - 1, "mu", "s", ""))
+
+
+def _check_signed_edges(bins, name: str, top: float, top_name: str) -> np.ndarray:
+    """What the two signed edge checks share: ``bins`` as an int ``n >= 1`` gives ``np.linspace(-top, top, n + 1)``, each edge
+    averaged with minus its mirror -- at most an ulp from ``linspace``, and exactly antisymmetric with an exact 0 in the middle
+    of an even number of bins, which is what folding the result asks for; a sequence must run from ``-top`` to ``top``, finite
+    and strictly ascending, symmetric inside or not (``ValueError`` otherwise)."""
+    if isinstance(bins, (bool, np.bool_)):
+        raise ValueError(f"{name}_bins must be a number of bins >= 1 or a sequence of edges")
+    if isinstance(bins, (int, np.integer)):
+        if bins < 1:
+            raise ValueError(f"{name}_bins must be >= 1, not {bins}")
+        edges = np.linspace(-top, top, int(bins) + 1)
+        return 0.5 * (edges - edges[::-1])
+    try:
+        edges = np.array(bins, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"{name}_bins must be a number of bins >= 1 or a sequence of edges") from err
+    if edges.ndim != 1 or len(edges) < 2:
+        raise ValueError(f"{name}_bins as edges must be a sequence of at least two numbers")
+    if not np.all(np.isfinite(edges)):
+        raise ValueError(f"the signed {name} edges must be finite")
+    if edges[0] != -top:
+        raise ValueError(f"the signed {name} edges must start at -{top_name} = {-top}, not {edges[0]}")
+    if not np.all(np.diff(edges) > 0.0):
+        raise ValueError(f"the signed {name} edges must ascend strictly")
+    if edges[-1] != top:
+        raise ValueError(f"the signed {name} edges must end at {top_name} = {top}, not {edges[-1]}")
+    return edges
+
+
+def check_signed_pi_edges(pi_bins, pi_max) -> np.ndarray:
+    """The edges f64[n + 1] of a SIGNED line-of-sight binning from ``pi_bins``: an int ``n >= 1`` gives
+    ``np.linspace(-pi_max, pi_max, n + 1)`` (made exactly antisymmetric: ``_check_signed_edges``); a sequence of edges must run from ``-pi_max`` to ``pi_max``, finite and strictly
+    ascending -- it need not be symmetric inside (``ValueError`` otherwise)."""
+    return _check_signed_edges(pi_bins, "pi", check_pi_max(pi_max), "pi_max")
+
+
+def check_signed_mu_edges(mu_bins) -> np.ndarray:
+    """The edges f64[n + 1] of a SIGNED binning in ``mu = pi / s`` from ``mu_bins``: ``check_signed_pi_edges`` from -1 to 1."""
+    return _check_signed_edges(mu_bins, "mu", 1.0, "1")
+
+
+def count_projected_pi_signed_fine(layout_a, layout_b, cells, r2, *, pi_edges, cosmology, unit, sort_axis: int = 2):
+    """``count_projected_pi_fine`` between two different layouts with the pairs binned in the SIGNED
+    ``chi_b - chi_a`` -- object of ``layout_b`` minus object of ``layout_a`` -- by ``pi_edges`` f64[n + 1], finite and strictly
+    ascending, of any sign (bin 0 is ``[pe[0], pe[1]]``, bin j ``(pe[j], pe[j + 1]]``) -> ``(W, CountStats)``, W f64[n, n_cells,
+    E-1] (``yawhip_proj_count_pi_signed``). No cell is diagonal. The handles are the resident ones of role "projected <kind>":
+    a layout counted for the unsigned ``w_p`` is not uploaded again. Cap and reach refusals become ``ValueError`` as in
+    ``count_projected_pi_fine``. No CPU fallback; the CPU tests replace this function."""
+    ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
+    return _run_projected(lambda: _lib.proj_count_pi_signed(ctx, a, b, cells, r2, pi_edges), (layout_a, layout_b), cosmology, unit, r2,
+                          cap=(len(pi_edges) - 1, "pi", "radius", ""))
+
+
+def count_smu_signed_fine(layout_a, layout_b, cells, s2, *, mu_edges, cosmology, unit, sort_axis: int = 2):
+    """``count_smu_fine`` between two different layouts with ``mu`` signed by ``chi_b - chi_a`` -- object of ``layout_b`` minus
+    object of ``layout_a`` -- over ``mu_edges`` f64[n + 1] from -1 to 1 (``check_signed_mu_edges``; bin 0 is ``[-1, mu_1]``, bin
+    j ``(mu_j, mu_{j+1}]``) -> ``(W, CountStats)``, W f64[n, n_cells, E-1] (``yawhip_proj_count_smu_signed``). The library
+    receives the signed squares ``copysign(mu mu, mu)`` and refuses them if they no longer ascend strictly. No cell is
+    diagonal. Handles, cap and reach refusals: as ``count_smu_fine``. No CPU fallback; the CPU tests replace this function."""
+    ctx, a, b = _proj_handles(layout_a, layout_b, cosmology, unit, sort_axis)
+    mu_edges = np.asarray(mu_edges, dtype=np.float64)
+    return _run_projected(lambda: _lib.proj_count_smu_signed(ctx, a, b, cells, s2, np.copysign(mu_edges * mu_edges, mu_edges)),
+                          (layout_a, layout_b), cosmology, unit, s2, cap=(len(mu_edges) - 1, "mu", "s", ""))
 
 
 def count_projected_fine(layout_a, layout_b, cells, r2, *, pi_max, cosmology, unit, sort_axis: int = 2):

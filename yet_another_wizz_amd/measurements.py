@@ -21,12 +21,13 @@ from . import _lib, engine, parallel
 from .angular_bins import plan_for_limits, radial_plan_for_limits
 from .catalog import Catalog, InconsistentPatchesError
 from .coordinates import AngularDistances
-from .corrfunc import AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc
+from .corrfunc import (AlignmentCorrFunc, CorrFunc, MultipoleCorrFunc, ProjectedCorrFunc, ScalarCorrFunc, ShapeShapeCorrFunc,
+                       SignedMultipoleCorrFunc, SignedProjectedCorrFunc)
 from .cosmology import DELTA_SIGMA_UNIT
 from .options import CountMode
 from .paircounts import NormalisedCounts, NormalisedScalarCounts, PatchedCounts, PatchedSumWeights
 
-__all__ = ["autocorrelate", "autocorrelate_projected", "autocorrelate_multipoles", "crosscorrelate", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
+__all__ = ["autocorrelate", "autocorrelate_projected", "autocorrelate_multipoles", "crosscorrelate", "crosscorrelate_projected", "crosscorrelate_multipoles", "autocorrelate_scalar", "crosscorrelate_scalar", "crosscorrelate_scalar_map",
            "crosscorrelate_shear", "crosscorrelate_delta_sigma", "crosscorrelate_alignment", "autocorrelate_alignment", "autocorrelate_shear", "correlate_shear_tomographic", "compute_scalar_normalisation",
            "PatchLinkage", "get_max_angle", "radial_plans", "radial_max_angle", "check_patch_conistency"]
 
@@ -646,7 +647,7 @@ class PatchLinkage:
                 for s in range(num_scales)]
 
     def count_projected_pairs(self, main_catalog: Catalog, second_catalog: Catalog | None = None, *, pi_max: float, progress: bool = False,
-                              max_workers: int | None = None, count_type_info: str | None = None, pi_bins=None) -> list:
+                              max_workers: int | None = None, count_type_info: str | None = None, pi_bins=None, signed: bool = False) -> list:
         """Pair counts of one (auto) or two catalogues with every pair binned in its OWN transverse radius
         ``R = (d_a + d_b) / 2 * theta`` (physical or comoving, as the unit of the scales says) and kept only if its
         line-of-sight separation ``|chi_a - chi_b|`` is at most ``pi_max`` (a comoving length in Mpc) -> one
@@ -664,13 +665,27 @@ class PatchLinkage:
         bins the kept pairs in ``|chi_a - chi_b|`` besides, bin 0 ``[0, pe[1]]`` and bin j ``(pe[j], pe[j + 1]]``: the result
         is then a list over scales of lists over pi bins of ``NormalisedCounts``, every plane recombined like the one of
         ``pi_bins=None`` and all over ONE ``PatchedSumWeights``, still from one library call
-        (``engine.count_projected_pi_fine``)."""
+        (``engine.count_projected_pi_fine``).
+
+        ``signed=True`` keeps the sign of the line of sight between TWO catalogues: ``pi = chi(object of second_catalog) -
+        chi(object of main_catalog)``, binned by ``pi_bins`` as ``engine.check_signed_pi_edges`` reads them (a number of equal
+        bins from ``-pi_max`` to ``pi_max``, or edges between the two), bin 0 ``[pe[0], pe[1]]`` and bin j ``(pe[j], pe[j + 1]]``
+        (``engine.count_projected_pi_signed_fine``). It needs the second catalogue and ``pi_bins`` (``ValueError``); cells and
+        result are those of the unsigned count of two catalogues."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("projected counts run in one process on one device")
         pi_max = engine.check_pi_max(pi_max)
-        pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
+        if signed:
+            if second_catalog is None or pi_bins is None:
+                raise ValueError("a signed projected count needs a second catalogue and pi_bins: one catalogue against itself "
+                                 "has no order, and the sign lives in the pi bins")
+            pi_edges = engine.check_signed_pi_edges(pi_bins, pi_max)
+        else:
+            pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
 
         def call(layout1, layout2, cells, r2, **kwargs):
+            if signed:
+                return engine.count_projected_pi_signed_fine(layout1, layout2, cells, r2, pi_edges=pi_edges, **kwargs)
             if pi_edges is not None:  # one plane per pi bin
                 return engine.count_projected_pi_fine(layout1, layout2, cells, r2, pi_edges=pi_edges, **kwargs)
             fine, stats = engine.count_projected_fine(layout1, layout2, cells, r2, pi_max=pi_max, **kwargs)
@@ -680,7 +695,7 @@ class PatchLinkage:
         return planes[0] if pi_edges is None else [list(per_pi) for per_pi in zip(*planes)]
 
     def count_smu_pairs(self, main_catalog: Catalog, second_catalog: Catalog | None = None, *, mu_bins, progress: bool = False,
-                        max_workers: int | None = None, count_type_info: str | None = None) -> list:
+                        max_workers: int | None = None, count_type_info: str | None = None, signed: bool = False) -> list:
         """Pair counts of one (auto) or two catalogues binned in the redshift-space separation ``s`` and in ``mu = pi / s``:
         ``s^2 = r_p^2 + pi^2`` with ``r_p = (d_a + d_b) / 2 * theta`` and ``pi = |chi_a - chi_b|`` of
         ``count_projected_pairs``, and no line-of-sight cut -> a list over scales of lists over mu bins of
@@ -688,13 +703,20 @@ class PatchLinkage:
         a number of equal bins of ``mu`` in [0, 1] or their edges, bin 0 ``[0, mu_1]`` and bin j ``(mu_j, mu_{j+1}]``.
         Catalogues, cells, recombination (``CombinePlan`` of ``radial_plans``), diagonal slots, linkage and the one-process
         rule are ``count_projected_pairs``'; every plane is recombined alike and all are over ONE ``PatchedSumWeights``,
-        from one library call (``engine.count_smu_fine``)."""
+        from one library call (``engine.count_smu_fine``).
+
+        ``signed=True`` keeps the sign of ``mu`` between TWO catalogues: ``pi = chi(object of second_catalog) - chi(object of
+        main_catalog)`` and ``mu_bins`` as ``engine.check_signed_mu_edges`` reads them, from -1 to 1
+        (``engine.count_smu_signed_fine``). It needs the second catalogue (``ValueError``)."""
         if parallel.world()[1] > 1:
             raise NotImplementedError("projected counts run in one process on one device")
-        mu_edges = engine.check_mu_edges(mu_bins)
+        if signed and second_catalog is None:
+            raise ValueError("a signed redshift-space count needs a second catalogue: one catalogue against itself has no order")
+        mu_edges = engine.check_signed_mu_edges(mu_bins) if signed else engine.check_mu_edges(mu_bins)
+        count_fine = engine.count_smu_signed_fine if signed else engine.count_smu_fine
 
         def call(layout1, layout2, cells, s2, **kwargs):
-            return engine.count_smu_fine(layout1, layout2, cells, s2, mu_edges=mu_edges, **kwargs)
+            return count_fine(layout1, layout2, cells, s2, mu_edges=mu_edges, **kwargs)
 
         planes = self._count_projected_cells(main_catalog, second_catalog, call, count_type_info, progress)
         return [list(per_mu) for per_mu in zip(*planes)]
@@ -1000,6 +1022,111 @@ def autocorrelate_multipoles(config, data: Catalog, random: Catalog, *, mu_bins,
     RR = links.count_smu_pairs(random, count_type_info="RR", **kwargs) if count_rr else [None] * len(DD)
     return [MultipoleCorrFunc(mu_edges, [CorrFunc(dd_j, dr_j, None, None if rr is None else rr[j]) for j, (dd_j, dr_j) in enumerate(zip(dd, dr))])
             for dd, dr, rr in zip(DD, DR, RR)]
+
+
+def _crosscorrelate_radial(config, data1, data2, rand1, rand2, count_rr, what: str, count) -> list:
+    """What the two cross-correlations in a radius share: the checks, the trees with redshifts of every catalogue given, ONE
+    linkage that reaches as far as the nearest object of any of them sees the largest scale, and the four counts in the
+    slots in which ``crosscorrelate`` puts them -- D1D2, D1R2 (``dr``) where ``rand2`` is given, R1D2 (``rd``) where ``rand1`` is,
+    R1R2 where both are and ``count_rr``. ``count(links, first, second, info)`` is the linkage's count of two catalogues, a
+    list over scales of lists over the bins of the second binning (or of ``NormalisedCounts``, where there is none).
+    Returns ``(DD, DR, RD, RR)``, ``None`` for a count that was not asked for."""
+    _require_distinct(data1, data2, rand1, rand2)
+    if parallel.world()[1] > 1:
+        raise NotImplementedError("projected counts run in one process on one device")
+    count_dr, count_rd = rand2 is not None, rand1 is not None
+    if not count_dr and not count_rd:
+        raise ValueError("at least one random dataset must be provided")
+    engine.radial_kind(config.scales.scales.unit)  # angular units have no radius: ValueError
+    edges, closed = config.binning.edges, config.binning.closed
+    catalogs = [cat for cat in (data1, data2, rand1, rand2) if cat is not None]
+    _log_info("building trees")
+    layouts = [cat.build_trees(edges, closed=closed, with_redshifts=True) for cat in catalogs]
+    for layout in layouts:
+        engine.check_proj_redshifts(layout)
+    count_rr = count_rr and count_dr and count_rd
+    _log_info(f"computing {what} cross-correlation from DD" + (", DR" if count_dr else "") + (", RD" if count_rd else "")
+              + (", RR" if count_rr else ""))
+    # (the linkage holds every catalogue's patch centres against those of the largest: check_patch_conistency)
+    links = PatchLinkage.from_catalogs(config, *catalogs, max_angle=radial_max_angle(config, *layouts))
+    return (count(links, data1, data2, "DD"), count(links, data1, rand2, "DR") if count_dr else None,
+            count(links, rand1, data2, "RD") if count_rd else None, count(links, rand1, rand2, "RR") if count_rr else None)
+
+
+def _binned_corrfuncs(result_type, edges, DD, DR, RD, RR) -> list:
+    """One ``result_type(edges, [CorrFunc(dd_j, dr_j, rd_j, rr_j) per bin j])`` per scale from the four counts of
+    ``_crosscorrelate_radial`` with a second binning."""
+    num_scales = len(DD)
+    DR, RD, RR = ([None] * num_scales if counts is None else counts for counts in (DR, RD, RR))
+    return [result_type(edges, [CorrFunc(dd_j, *(None if counts is None else counts[j] for counts in (dr, rd, rr))) for j, dd_j in enumerate(dd)])
+            for dd, dr, rd, rr in zip(DD, DR, RD, RR)]
+
+
+def crosscorrelate_projected(config, data1: Catalog, data2: Catalog, rand1: Catalog | None = None, rand2: Catalog | None = None, *,
+                             pi_max: float, pi_bins=None, signed: bool = False, count_rr: bool = True, progress: bool = False,
+                             max_workers: int | None = None) -> list:
+    """Projected cross-correlation of two samples in each pair's own transverse radius: ``autocorrelate_projected`` between
+    ``data1`` and ``data2`` (no counterpart in the reference). D1D2 is always counted, D1R2 where
+    ``rand2`` is given, R1D2 where ``rand1`` is, R1R2 where both are and ``count_rr``; at least one random catalogue is
+    required. The four go into ``CorrFunc(dd, dr, rd, rr)`` as ``crosscorrelate`` fills it, and ``CorrFunc`` chooses the
+    estimator: Landy-Szalay with RR, Davis-Peebles otherwise.
+
+    ``signed=False`` bins ``pi = |chi_2 - chi_1|`` and returns, per scale, what ``autocorrelate_projected`` returns: a
+    ``CorrFunc`` of the cylinder ``pi <= pi_max`` (``pi_bins=None``) or a ``ProjectedCorrFunc``.
+
+    ``signed=True`` keeps the sign, ``pi = chi(object of data2 or rand2) - chi(object of data1 or rand1)``, positive where the
+    second sample's object lies behind: for two different tracers ``xi(r_p, pi)`` is not symmetric in ``pi``. ``pi_bins`` is
+    then required: a number ``n >= 1`` of equal bins from ``-pi_max`` to ``pi_max``, or their edges, strictly ascending
+    between the two and symmetric inside or not. The result is ``[SignedProjectedCorrFunc]``, one per scale: ``sample_xi()``
+    per signed bin, ``sample()`` the ``w_p = sum_j dpi_j xi_j`` over both signs, ``folded()`` the result of ``signed=False``
+    over the mirrored edges. The cap on the number of bins is ``autocorrelate_projected``'s, the signed bins counted as
+    they are.
+
+    All catalogues carry redshifts and share their patch centres. Units, ``pi_max``, redshift bins (pairs are counted INSIDE
+    a bin), reach and the one-process rule are ``autocorrelate_projected``'s."""
+    pi_max = engine.check_pi_max(pi_max)
+    if signed:
+        if pi_bins is None:
+            raise ValueError("a signed projected correlation needs pi_bins: the sign lives in the pi bins")
+        pi_edges = engine.check_signed_pi_edges(pi_bins, pi_max)
+    else:
+        pi_edges = None if pi_bins is None else engine.check_pi_edges(pi_bins, pi_max)
+
+    def count(links, first, second, info):
+        return links.count_projected_pairs(first, second, pi_max=pi_max, pi_bins=pi_edges, signed=signed, progress=progress,
+                                           max_workers=max_workers, count_type_info=info)
+
+    DD, DR, RD, RR = _crosscorrelate_radial(config, data1, data2, rand1, rand2, count_rr, "projected", count)
+    if pi_edges is None:
+        DR, RD, RR = ([None] * len(DD) if counts is None else counts for counts in (DR, RD, RR))
+        return [CorrFunc(dd, dr, rd, rr) for dd, dr, rd, rr in zip(DD, DR, RD, RR)]
+    return _binned_corrfuncs(SignedProjectedCorrFunc if signed else ProjectedCorrFunc, pi_edges, DD, DR, RD, RR)
+
+
+def crosscorrelate_multipoles(config, data1: Catalog, data2: Catalog, rand1: Catalog | None = None, rand2: Catalog | None = None, *,
+                              mu_bins, signed: bool = False, count_rr: bool = True, progress: bool = False,
+                              max_workers: int | None = None) -> list:
+    """Redshift-space cross-correlation of two samples: ``autocorrelate_multipoles`` between ``data1`` and ``data2`` (no
+    counterpart in the reference), with the counts, the randoms and the estimator of
+    ``crosscorrelate_projected``.
+
+    ``signed=False`` bins the unsigned ``mu`` over ``mu_bins`` in [0, 1] and returns ``[MultipoleCorrFunc]``. ``signed=True``
+    keeps the sign of ``pi = chi(object of data2 or rand2) - chi(object of data1 or rand1)`` on ``mu = pi / s``: ``mu_bins`` is a
+    number ``n >= 1`` of equal bins from -1 to 1, or their edges, and the result is ``[SignedMultipoleCorrFunc]``, whose
+    ``sample(ell)`` measures the odd multipoles too (the dipole and octupole of two different tracers) and whose ``folded()``
+    is the result of ``signed=False`` over the mirrored edges. The cap on the number of bins is
+    ``autocorrelate_multipoles``', the signed bins counted as they are.
+
+    All catalogues carry redshifts and share their patch centres. Units, redshift bins (pairs are counted INSIDE a bin),
+    reach and the one-process rule are ``autocorrelate_multipoles``'."""
+    mu_edges = engine.check_signed_mu_edges(mu_bins) if signed else engine.check_mu_edges(mu_bins)
+
+    def count(links, first, second, info):
+        return links.count_smu_pairs(first, second, mu_bins=mu_edges, signed=signed, progress=progress, max_workers=max_workers,
+                                     count_type_info=info)
+
+    DD, DR, RD, RR = _crosscorrelate_radial(config, data1, data2, rand1, rand2, count_rr, "redshift-space", count)
+    return _binned_corrfuncs(SignedMultipoleCorrFunc if signed else MultipoleCorrFunc, mu_edges, DD, DR, RD, RR)
 
 
 def crosscorrelate_alignment(config, shapes: Catalog, density: Catalog, density_rand: Catalog, *, pi_max: float, pi_bins=None,
