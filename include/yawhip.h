@@ -880,6 +880,10 @@ int yawhip_proj_count_smu(yawhip_ctx *ctx, yawhip_shear_sources *a, yawhip_shear
  *     the edges whatever the sign of sP2 (for ps < 0 the negative edges, whose squares descend; for ps > 0 every negative
  *     edge and then a prefix of the others). sm2[0] and sm2[n_mu] are never read: there is no cut.
  *     yawhip_proj_count_smu is the special case in which all signs are positive: the predicate then reads fl(m2[k] S2) < P2.
+ *     A pair with c_a == c_b has ps == +0 and sP2 == +0 whichever handle comes first: every product of a negative edge is
+ *     below it, fl(+-0 S2) < +0 fails, so the pair is in the plane whose UPPER edge is the first one >= 0 -- at an edge
+ *     mu == 0 (of either sign of zero) the plane below it, which is closed above. Exchanging the handles and passing
+ *     -sm2 reversed therefore mirrors the planes of every pair but these, which stay below 0 in both calls.
  *     Consequence: over edges mirrored about 0 and where no pair has ps == 0 and no product fl(m2[k] S2) equals P2,
  *     fine_w[n + j] + fine_w[n - 1 - j] equals plane j of yawhip_proj_count_smu at the edges m2, as integers over unit weights.
  *   n_mu, sm2    n_mu >= 1; sm2[0] exactly -1 and sm2[n_mu] exactly 1; strictly ascending -- a sequence of mu that does not

@@ -5,8 +5,10 @@ The pi count is held to the exact reference of tests/golden/proj_exact.npz: test
 oracle's membership folds to the file's mpmath integers with no pair at ``ps == 0`` or on an edge, and the sign of a float64
 difference is the sign of the true difference, so the oracle's member pairs per signed plane ARE the exact ones; over them
 the weighted reference is the sum of the exact products ``w_a w_b`` in ``fractions.Fraction``, rounded once, and the rule is the
-file's ``|ours - exact| <= K 2^-53 A``. The mu count is held to the signed oracle (integers) and to ``yawhip_proj_count_smu``
-on the same handles (the fold), its weighted planes by the rule of tests/test_gpu_smu.py."""
+file's ``|ours - exact| <= K 2^-53 A``. The mu count has an exact file of its own, tests/golden/smu_exact.npz, and meets it in
+tests/test_gpu_smu_exact.py (both scenes up to the cap, the tie ``ps == 0`` at an edge ``mu == 0`` included); here it is held
+to the signed oracle (integers) and to ``yawhip_proj_count_smu`` on the same handles (the fold), its weighted planes by the
+rule of tests/test_gpu_smu.py."""
 import functools
 from fractions import Fraction
 
