@@ -212,6 +212,8 @@ int yawhip_catalog_segment_sums(const yawhip_catalog *cat, double *sums);
 int yawhip_catalog_sort_axis(const yawhip_catalog *cat, int32_t *axis);
 int yawhip_catalog_free(yawhip_catalog *cat);
 /* Device bytes held by a catalogue (for memory accounting). */
+/* (The library also exports a symbol yawhip_debug_lane_image. It is a hook of the test suite, deliberately not declared
+ * here and not part of this ABI: it builds a strip layout as a side effect and may change or go without notice.) */
 int yawhip_catalog_device_bytes(const yawhip_catalog *cat, int64_t *bytes);
 
 /*

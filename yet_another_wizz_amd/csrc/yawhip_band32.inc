@@ -102,6 +102,15 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
     if (LANE_THR)
         for (int e = lane; e < n_bins * TW; e += 64) sthr[e] = thr32[e];
     unsigned round_no = 0;
+    // statistics: the band entries the lanes walked, summed per lane over the workgroup's items and sent once -- only the sum
+    // over the launch is read. (DPP: the shuffle form is six trips through the LDS crossbar. The halves of the lane sums are
+    // reduced separately: 64 x 65535 fits a word.)
+    unsigned int nev = 0;
+    auto send_entries = [&](unsigned int lane_sum) {
+        const unsigned int lo16 = wave_sum_lane63(lane_sum & 0xffffu), hi16 = wave_sum_lane63(lane_sum >> 16);
+        const unsigned long long sum = (unsigned long long)lo16 + ((unsigned long long)hi16 << 16);
+        if (lane == 63 && sum) atomicAdd(&counters[BAND_ENTRY_CTR(blockIdx.x & (EVAL_SLOTS - 1))], sum);
+    };
     for (unsigned long long v = blockIdx.x;; v += gridDim.x) {
         if ((v >> 3) >= tmap.per_xcd) break;
         const unsigned long long ticket = tmap.ticket(v);
@@ -182,14 +191,23 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
         int lane_obj = lane;  // whose objects this lane counts for: its own, until the bands of a sparse item are shared out
         int n_own = (int)it.na - lane * R;
         n_own = n_own < 0 ? 0 : (n_own > R ? R : n_own);
+        // One 16-byte record per object {x, y, z, bin} (DevTab::q4), fetched whether the lane has the object or not -- the table
+        // ends with LANE_IMAGE_PAD records, a whole lane tile beyond the last object -- and padded in registers afterwards:
+        // R loads in one round, no exec-masked blocks, instead of a dword load per object and column.
+        lane_words rec[R];
+        {
+            const glanep lane_q = cl.q4 + it.a0 + lane * R;
+#pragma unroll
+            for (int r = 0; r < R; ++r) rec[r] = lane_q[r];
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const bool have = r < n_own;
             const unsigned ic = have ? (unsigned)(lane * R + r) : 0u;
-            ax[r] = have ? (cl.qx + it.a0)[ic] : PAD_COORD32;
-            ay[r] = have ? (cl.qy + it.a0)[ic] : PAD_COORD32;
-            az[r] = have ? (cl.qz + it.a0)[ic] : PAD_COORD32;
-            kb[r] = MERGED ? (have ? (cl.k + it.a0)[ic] : 0) : 0;
+            ax[r] = have ? rec[r].x : PAD_COORD32;
+            ay[r] = have ? rec[r].y : PAD_COORD32;
+            az[r] = have ? rec[r].z : PAD_COORD32;
+            kb[r] = MERGED ? (have ? __float_as_int(rec[r].w) : 0) : 0;
             // weighted: the object's own weight travels with its coordinates (one memory latency for both) instead of being
             // fetched at the flush, at the end of the item's chain of dependent latencies (config #4: DD 0.370 -> 0.349,
             // DR 1.67 -> 1.56, RR 3.20 -> 3.13 ms)
@@ -235,7 +253,6 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int c = 0; c < NC; ++c) { cnt[r][c] = 0u; acc[r][c] = 0.0; }
-        unsigned int nev = 0;
         // lane counters -> LDS histogram (cell = bin of the object x fine bin)
         // half bands (one object per lane, one chunk per round: the only variant that runs them): every pair was met once
         constexpr bool HALF = R == 1 && CH == 1;
@@ -300,26 +317,31 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
             }
             __syncthreads();
             // bands of the lane inside the chunks: [lo, hi) = entries with klo <= key <= khi, by branch-free binary searches
-            // on LDS byte addresses, all chunks in lockstep (q = address of entry lo - 1; a probe beyond a chunk is clamped
-            // onto its sentinel, whose key 4.0 fails both comparisons -- so one step schedule serves chunks of any length)
-            unsigned a_key[CH], a_sent[CH], ql[CH], qh[CH];
-            int n_max = 1;
+            // on LDS byte addresses, all chunks in lockstep. q = address of entry base - 1 of a search that has narrowed its
+            // answer to [base, base + len]: a step probes entry base + half - 1, half = len / 2 (wave-uniform), and keeps the
+            // upper len - half entries where the probe passes. Every probe lies inside the chunk by construction -- no clamp
+            // onto the sentinel --, and the step after the last halving reads entry base itself: an entry of the chunk or, at
+            // base = n, the sentinel behind it, whose key 4.0 fails both comparisons (so an empty chunk gives lo = hi = 0).
+            unsigned a_key[CH], ql[CH], qh[CH];
+            int left[CH], left_max = 0;  // len of the chunk's two searches
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 a_key[c] = a_stage + COLB * (unsigned)cl.axis + ((unsigned)co[c] << 2);
-                a_sent[c] = a_key[c] + ((unsigned)cn[c] << 2);
                 ql[c] = qh[c] = a_key[c] - 4u;
-                n_max = cn[c] > n_max ? cn[c] : n_max;
+                left[c] = cn[c];
+                left_max = cn[c] > left_max ? cn[c] : left_max;
             }
-            for (unsigned step = 4u << (31 - __builtin_clz(n_max)); step >= 4u; step >>= 1) {  // largest power of two <= n_max
+            for (; left_max > 1; left_max -= left_max >> 1) {  // (the longest chunk takes the most steps)
 #pragma unroll
                 for (int c = 0; c < CH; ++c) {
-                    if (c < nch) {
-                        const unsigned pl = ql[c] + step, ph = qh[c] + step;
-                        const float kl = *(const __attribute__((address_space(3))) float *)(size_t)(pl < a_sent[c] ? pl : a_sent[c]);
-                        const float kh = *(const __attribute__((address_space(3))) float *)(size_t)(ph < a_sent[c] ? ph : a_sent[c]);
+                    if (c < nch && (CH == 1 || left[c] > 1)) {
+                        const unsigned half4 = (unsigned)(left[c] >> 1) << 2;
+                        const unsigned pl = ql[c] + half4, ph = qh[c] + half4;
+                        const float kl = *(const __attribute__((address_space(3))) float *)(size_t)pl;
+                        const float kh = *(const __attribute__((address_space(3))) float *)(size_t)ph;
                         ql[c] = kl < klo ? pl : ql[c];    // entries [0, lo) have key <  klo
                         qh[c] = kh <= khi ? ph : qh[c];   // entries [0, hi) have key <= khi
+                        left[c] -= left[c] >> 1;
                     }
                 }
             }
@@ -328,6 +350,8 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
             if (c < nch) {
             const int n = cn[c];
             int lo = (int)((ql[c] + 4u - a_key[c]) >> 2), hi = (int)((qh[c] + 4u - a_key[c]) >> 2);
+            lo += *(const __attribute__((address_space(3))) float *)(size_t)(ql[c] + 4u) < klo ? 1 : 0;
+            hi += *(const __attribute__((address_space(3))) float *)(size_t)(qh[c] + 4u) <= khi ? 1 : 0;
             if (n_own == 0) lo = hi = n;  // lanes without an object walk the sentinel
             if constexpr (R == 1 && CH == 1) {
                 // diagonal job of a self count: only the entries behind the lane object's own place in the triple run of its strip
@@ -635,9 +659,11 @@ void YAW_B32_NAME(const DevTab *__restrict__ tabs, const Item *__restrict__ item
         } else {
             flush_counts();
         }
-        nev = wave_sum_lane63(nev);  // (DPP: the shuffle form is six trips through the LDS crossbar, per item, for a statistic)
-        if (lane == 63 && nev) atomicAdd(&counters[BAND_ENTRY_CTR(ticket & (EVAL_SLOTS - 1))], (unsigned long long)nev);
+        // (a lane's sum stays below 2^32 as long as an item adds less than 2^31 to it -- the per-item sum over the wave it
+        // replaces needed the whole wave's below 2^32)
+        if (__builtin_amdgcn_ballot_w64((int)nev < 0)) { send_entries(nev); nev = 0; }
     }
+    send_entries(nev);
 }
 
 }  // namespace

@@ -34,10 +34,11 @@ using namespace yawhip_detail;
 namespace {
 inline DevTab make_tab(const double *x, const double *y, const double *z, const double *w, const int32_t *k, const int64_t *off,
                        const int64_t *vbase, const int64_t *slo, const int64_t *tiles, const TileRec *tile_rec, const RunGrid *grid,
-                       int axis, const float *q = nullptr, int64_t q_stride = 0, const int32_t *idx = nullptr) {
+                       int axis, const float *q = nullptr, int64_t q_stride = 0, const int32_t *idx = nullptr,
+                       const LaneObj *q4 = nullptr) {
     return DevTab{(gf64p)x, (gf64p)y, (gf64p)z, (gf64p)w, (gi32p)k, (gi64p)off, (gi64p)vbase, (gi64p)slo, (gi64p)tiles,
-                  tile_rec, grid, (gf32p)q, (gf32p)(q ? q + q_stride : nullptr), (gf32p)(q ? q + 2 * q_stride : nullptr), (gi32p)idx,
-                  (gi32p)nullptr, axis, 0};
+                  tile_rec, grid, (gf32p)q, (gf32p)(q ? q + q_stride : nullptr), (gf32p)(q ? q + 2 * q_stride : nullptr), (glanep)q4,
+                  (gi32p)idx, (gi32p)nullptr, axis, 0};
 }
 
 inline int64_t seg_len(const yawhip_catalog *c, int patch, int k) {
@@ -684,9 +685,9 @@ int Planner::tables() {
             if (!L1[o]) continue;
             const StripLayout &a = *L1[o], &b = *L2[o];
             h_tabs[o] = make_tab(a.x, a.y, a.z, a.w, P.merged ? a.k : nullptr, a.off, a.d_vbase, a.d_slo, a.d_tiles[tile_idx],
-                                 a.d_tile_rec[tile_idx], a.d_grid, o, a.q, a.q_stride);
+                                 a.d_tile_rec[tile_idx], a.d_grid, o, a.q, a.q_stride, nullptr, a.q4);
             h_tabs[3 + o] = make_tab(b.x, b.y, b.z, b.w, nullptr, b.off, b.d_vbase, b.d_slo, b.d_tiles[tile_idx],
-                                     b.d_tile_rec[tile_idx], b.d_grid, o, b.q, b.q_stride);
+                                     b.d_tile_rec[tile_idx], b.d_grid, o, b.q, b.q_stride, nullptr, b.q4);
             if (P.triple) {
                 // the streamed side as merged triple runs: images, weights, offsets and grid index of the triples; the float64
                 // columns stay the layout's own (reached through idx by the exact re-evaluation)

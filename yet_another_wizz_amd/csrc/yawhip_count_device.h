@@ -40,17 +40,27 @@ __device__ __forceinline__ double cap_hi64(double u, double c, double s) {
 // float32 (band kernels): the lane key u is the float32 image, |u - u^| <= 2^-25 + 5e-10 < 3.1e-8. Input shift 1e-7: the
 // rounding of u - 1e-7 (<= 6e-8) still leaves ul <= u^. Clip decisions widened by 1.2e-7 (c rounded to float32: 3e-8, and
 // the rounding of -c + 1.2e-7: 6e-8). The formula in float32: c and s rounded (6e-8 u, 6e-8 s), fma(-u, u, 1) one rounding
-// relative to 1 - u^2 and sqrtf within 2 ulp (together 2e-7 relative, times s), the product and the final fma (6e-8 each),
-// the margin's own subtraction (6e-8): at most 1.8e-7 + 3.2e-7 s; the partner's float32 image adds 3.1e-8. The margin
+// relative to 1 - u^2 and a square root within 2 ulp (together 2e-7 relative, times s), the product and the final fma (6e-8
+// each), the margin's own subtraction (6e-8): at most 1.8e-7 + 3.2e-7 s; the partner's float32 image adds 3.1e-8. The margin
 // CAP32_MARGIN = 8e-7 covers s <= 1 (3e-4 of the band half width r at the headline's r = 2.9e-3).
+// The square root is the hardware's (v_sqrt_f32, within 1 ulp: inside the 2 ulp budgeted above, so the margin stands), not
+// the correctly rounded sqrtf, which costs some twenty vector instructions per bound and item for a culling bound. Its
+// argument is 0 or at least 2^-24 wherever the formula branch is taken: never a denormal.
 constexpr float CAP32_SHIFT = 1e-7f, CAP32_CLIP = 1.2e-7f, CAP32_MARGIN = 8e-7f;
+// (The clipped bound is made where it is used: with the two bounds this short, hipcc keeps both constants in vector registers
+// of their own through the whole kernel, the walk loop included -- one register more in nearly every variant, a wave per
+// SIMD less in five of them. The empty asm statement is not moved out of the item loop; it costs one v_mov per bound.)
+__device__ __forceinline__ float cap32_clipped(float bound) {
+    asm volatile("" : "+v"(bound));
+    return bound;
+}
 __device__ __forceinline__ float cap_lo32(float u, float c, float s) {
-    const float ul = fmaxf(u - CAP32_SHIFT, -1.0f);
-    return ul <= -c + CAP32_CLIP ? -1.0f - CAP32_MARGIN : fmaf(ul, c, -sqrtf(fmaxf(fmaf(-ul, ul, 1.0f), 0.0f)) * s) - CAP32_MARGIN;
+    const float ul = fmaxf(u - CAP32_SHIFT, -1.0f), clipped = cap32_clipped(-1.0f - CAP32_MARGIN);
+    return ul <= -c + CAP32_CLIP ? clipped : fmaf(ul, c, -__builtin_amdgcn_sqrtf(fmaxf(fmaf(-ul, ul, 1.0f), 0.0f)) * s) - CAP32_MARGIN;
 }
 __device__ __forceinline__ float cap_hi32(float u, float c, float s) {
-    const float uh = fminf(u + CAP32_SHIFT, 1.0f);
-    return uh >= c - CAP32_CLIP ? 1.0f + CAP32_MARGIN : fmaf(uh, c, sqrtf(fmaxf(fmaf(-uh, uh, 1.0f), 0.0f)) * s) + CAP32_MARGIN;
+    const float uh = fminf(u + CAP32_SHIFT, 1.0f), clipped = cap32_clipped(1.0f + CAP32_MARGIN);
+    return uh >= c - CAP32_CLIP ? clipped : fmaf(uh, c, __builtin_amdgcn_sqrtf(fmaxf(fmaf(-uh, uh, 1.0f), 0.0f)) * s) + CAP32_MARGIN;
 }
 
 constexpr int SLOT_MASK = 0x3fffffff;

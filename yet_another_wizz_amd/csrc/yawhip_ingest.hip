@@ -125,14 +125,22 @@ __global__ void k_gather_bins(int64_t n, const uint32_t *__restrict__ perm, cons
     if (i < n) bins[i] = segment_of(off, (int)n_seg, (int64_t)perm[i]) % n_bins;
 }
 
-// float32 images of a strip layout's columns, rounded to nearest: [3][stride]
+// float32 images of a strip layout's columns, rounded to nearest: [3][stride] -- and the same values once more as one
+// 16-byte record per object, {x, y, z, bin id} (0 where the layout has no bin ids), for the lane side of the float32 band
+// kernels: a lane fetches an object with one load instead of four. The LANE_IMAGE_PAD records behind the last object are zero.
 __global__ void k_make_q(int64_t n, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-                         int64_t stride, float *__restrict__ q) {
+                         const int32_t *__restrict__ bins, int64_t stride, float *__restrict__ q, LaneObj *__restrict__ q4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    q[i] = (float)x[i];
-    q[stride + i] = (float)y[i];
-    q[2 * stride + i] = (float)z[i];
+    if (i >= n + LANE_IMAGE_PAD) return;
+    if (i >= n) {
+        q4[i] = LaneObj{0.0f, 0.0f, 0.0f, 0};
+        return;
+    }
+    const float fx = (float)x[i], fy = (float)y[i], fz = (float)z[i];
+    q[i] = fx;
+    q[stride + i] = fy;
+    q[2 * stride + i] = fz;
+    q4[i] = LaneObj{fx, fy, fz, bins ? bins[i] : 0};
 }
 
 // How often two neighbours of the (strip, u)-sorted order share their redshift bin: ~1/B when redshift and position are
@@ -431,6 +439,7 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     if (e == hipSuccess && want_bins) e = L.k.alloc(n1, 16);
     L.q_stride = (int64_t)((n1 + 3) & ~(size_t)3) + 8;  // a 16-byte load of the band kernel may run up to 12 bytes past a column
     if (e == hipSuccess) e = L.q.alloc((size_t)3 * L.q_stride);
+    if (e == hipSuccess) e = L.q4.alloc((size_t)(n + LANE_IMAGE_PAD));
     if (e == hipSuccess) e = L.off.alloc((size_t)(n_runs + 1));
     if (e == hipSuccess) e = L.d_grid.alloc((size_t)(n_runs + 1));
     if (e == hipSuccess) e = hipMemsetAsync(L.d_grid, 0, (size_t)(n_runs + 1) * sizeof(RunGrid), ctx->stream);  // [V]: read for groups without runs
@@ -438,7 +447,8 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     hipLaunchKernelGGL(k_gather_columns, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm2, c->x, c->y, c->z, c->w, L.x, L.y, L.z, L.w);
     if (want_bins)
         hipLaunchKernelGGL(k_gather_bins, dim3(ngrid), dim3(256), 0, ctx->stream, n, perm2, c->off, nseg, c->nb, L.k);
-    hipLaunchKernelGGL(k_make_q, dim3(ngrid), dim3(256), 0, ctx->stream, n, L.x, L.y, L.z, L.q_stride, L.q);
+    hipLaunchKernelGGL(k_make_q, dim3((unsigned)((n + LANE_IMAGE_PAD + 255) / 256)), dim3(256), 0, ctx->stream, n, L.x, L.y, L.z,
+                       want_bins ? (const int32_t *)L.k : nullptr, L.q_stride, L.q, L.q4);
     hipLaunchKernelGGL(k_run_offsets, dim3((unsigned)((n_runs + 1 + 255) / 256)), dim3(256), 0, ctx->stream, run_sorted, n, n_runs,
                        L.off);
     if (n_runs > 0)
@@ -506,7 +516,8 @@ int build_strip_layout(yawhip_ctx *ctx, yawhip_catalog *c, int o, bool seg) {
     L.n_groups = n_groups;
     // (the figure is pinned byte for byte by tests/test_gpu_ingest.py: the run and tile records count with RUN_GRID_ACCOUNTED and
     // TILE_REC_ACCOUNTED bytes, their size without the item builder's heads -- 32 bytes per run and 16 per lane tile that
-    // yawhip_catalog_device_bytes does not report: about half a byte per object, under 1 % of the catalogue's bytes)
+    // yawhip_catalog_device_bytes does not report: about half a byte per object, under 1 % of the catalogue's bytes; and, in
+    // the same way, not the lane records q4: 16 bytes per object and LANE_IMAGE_PAD records per layout)
     L.device_bytes = (int64_t)col * (c->w ? 4 : 3) + (want_bins ? n * (int64_t)sizeof(int32_t) : 0) + 3 * L.q_stride * (int64_t)sizeof(float) +
                      (4 * (n_runs + 1) + 2 * (int64_t)n_groups + 1) * (int64_t)sizeof(int64_t) + (n_runs + 1) * RUN_GRID_ACCOUNTED +
                      (L.h_tiles[0][(size_t)n_runs] + L.h_tiles[1][(size_t)n_runs] + L.h_tiles[2][(size_t)n_runs]) * TILE_REC_ACCOUNTED;
@@ -790,6 +801,34 @@ int yawhip_catalog_free(yawhip_catalog *c) {
         drop_plans(c->ctx, c);
     }
     delete c;  // its columns and layouts go with it
+    return YAWHIP_OK;
+}
+
+// Test hook (tests/test_gpu_lane_image.py; not part of the ABI of include/yawhip.h): builds the strip layout of orientation o
+// (seg: the per-segment one) if it is not built yet, reads its lane records back and compares them word for word with the
+// float32 columns and the bin ids they restate. *n_checked = objects compared, *n_differing = records that differ in any of
+// their four words, plus the records of the padding that are not zero.
+int yawhip_debug_lane_image(yawhip_ctx *ctx, yawhip_catalog *cat, int32_t o, int32_t seg, int64_t *n_checked, int64_t *n_differing) {
+    if (!ctx || !cat || !n_checked || !n_differing || o < 0 || o > 2) return fail(YAWHIP_ERR_INVALID, "yawhip_debug_lane_image: bad argument");
+    if (cat->strip_width <= 0.0 || (seg && cat->nb <= 1)) return fail(YAWHIP_ERR_INVALID, "yawhip_debug_lane_image: no such layout");
+    if (const int rc = build_strip_layout(ctx, cat, o, seg != 0)) return rc;
+    const StripLayout &L = seg ? cat->seg[o] : cat->strips[o];
+    const int64_t n = cat->n;
+    std::vector<LaneObj> rec((size_t)(n + LANE_IMAGE_PAD));
+    std::vector<float> q((size_t)3 * L.q_stride);
+    std::vector<int32_t> bins((size_t)n, 0);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpy(rec.data(), L.q4, rec.size() * sizeof(LaneObj), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(q.data(), L.q, q.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (L.k && n > 0) HIP_TRY(hipMemcpy(bins.data(), L.k, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    for (int64_t i = 0; i < n + LANE_IMAGE_PAD; ++i) {
+        const LaneObj want = i < n ? LaneObj{q[(size_t)i], q[(size_t)(L.q_stride + i)], q[(size_t)(2 * L.q_stride + i)], bins[(size_t)i]}
+                                   : LaneObj{0.0f, 0.0f, 0.0f, 0};
+        bad += memcmp(&rec[(size_t)i], &want, sizeof(LaneObj)) != 0;
+    }
+    *n_checked = n;
+    *n_differing = bad;
     return YAWHIP_OK;
 }
 

@@ -102,6 +102,18 @@ typedef const __attribute__((address_space(1))) double *gf64p;
 typedef const __attribute__((address_space(1))) int32_t *gi32p;
 typedef const __attribute__((address_space(1))) int64_t *gi64p;
 typedef const __attribute__((address_space(1))) float *gf32p;
+// Lane image of a strip layout: the float32 images of an object's coordinates and its bin id as ONE 16-byte record, what a
+// lane of the float32 band kernels fetches per object (k_make_q writes it beside the columns; 0 where the layout has no bin
+// ids -- unbinned catalogues, per-segment layouts: their kernels ignore the bin). A lane loads its R records whether it
+// has R objects or not, so the table ends with the records of a whole lane tile of the largest kind (64 lanes x 4 objects).
+struct alignas(16) LaneObj {
+    float x, y, z;
+    int32_t bin;
+};
+static_assert(sizeof(LaneObj) == 16, "LaneObj is read with one 16-byte load");
+constexpr int64_t LANE_IMAGE_PAD = 256;
+typedef float lane_words __attribute__((ext_vector_type(4)));  // a record as the kernels load it: the bin id is the bit pattern of .w
+typedef const __attribute__((address_space(1))) lane_words *glanep;
 struct DevTab {
     gf64p x, y, z, w;          // columns; w may be null
     gi32p k;                   // bin id per object (merged cross-correlation layouts), else null
@@ -109,8 +121,9 @@ struct DevTab {
     gi64p vbase, slo, tiles;   // strip layouts: first run of a group, its grid index, lane-tile prefix over runs
     const struct TileRec *tile_rec;  // strip layouts: first object, length, run and end keys of every lane tile
     const struct RunGrid *grid;      // strip layouts: per-run record and index along the sort axis (item builder)
-    gf32p qx, qy, qz;          // strip layouts: float32 images of the columns (k_count_band32)
-    gi32p idx;                 // merged triple runs (streamed side): index of an entry in the layout's own order, else null
+    gf32p qx, qy, qz;          // strip layouts: float32 images of the columns (k_count_band32: the streamed side, LDS-DMA)
+    glanep q4;                 // strip layouts: the same images with the bin id, one record per object (the lane side), else null
+    gi32p idx;                // merged triple runs (streamed side): index of an entry in the layout's own order, else null
     gi32p pos3;                // lane side of a self count on merged triple runs: place of an object in its own strip's triple, else null
     int32_t axis;              // sort axis inside a run / segment
     int32_t pad_;
@@ -300,6 +313,7 @@ struct StripLayout {
     DevPtr<int32_t> k;                // bin id per object (patch-level layout of a binned catalogue)
     DevPtr<float> q;                  // [3][q_stride] float32 images of x, y, z (k_count_band32)
     int64_t q_stride = 0;
+    DevPtr<LaneObj> q4;               // [n + LANE_IMAGE_PAD] the same images with the bin id (or 0), one record per object
     DevPtr<int64_t> off;              // [V+1] offsets of the runs
     std::vector<int64_t> h_off;       // same on the host
     std::vector<int64_t> h_vbase;     // [G+1] first run of every group
